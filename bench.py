@@ -4,6 +4,7 @@ phoneme ids -> 22.05 kHz waveform.
 
   python bench.py --gpus N --steps K --warmup W
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+  --dump-outputs DIR: after the timed steps, the waveforms and frame counts of the last timed step go to DIR/*.npy
 
 Workload (BASELINE.json configs[3]; with N = 8 it is configs[4]): per GPU a batch of 32 mixed-length utterances
 (32..256 phonemes, seeded), T = 1024 frames each, medium geometry (emb 512+16, 4 encoder layers, 512 -> 32 vocoder
@@ -157,6 +158,29 @@ def resblock_roofline(stats, psteps, timing_note):
             "timing": "hipEvent pair around each stage's run of consecutive ResBlock launches on the model's stream (eager); " + timing_note}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, rank, world):
+    """what zv_synthesize_batch handed back in the last timed step: wav[n_utts, T * hop] (float32) and n_frames[n_utts]
+    (float64).  Past the 64 MB budget (split evenly over the ranks) wav.npy holds a fixed seeded sample of the flattened
+    waveforms and wav_index.npy (float64) their flat indices.  With N > 1 every rank writes its own shard as rank<r>_<name>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = "rank%d_" % rank if world > 1 else ""
+    wav = np.stack([w for w, _ in res]).astype(np.float32)
+    arrays = {"n_frames": np.array([nf for _, nf in res], np.float64)}
+    budget = DUMP_BUDGET_BYTES // world - arrays["n_frames"].nbytes - 4096      # (less room for the .npy headers)
+    if wav.nbytes <= budget:
+        arrays["wav"] = wav
+    else:
+        k = budget // (4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(wav.size, size=k, replace=False))
+        arrays["wav"] = wav.reshape(-1)[idx]
+        arrays["wav_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -170,7 +194,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the configs[1]/[2] extras (used under rocprofv3)")
     ap.add_argument("--no-pipeline", action="store_true", help="one synchronous zv_synthesize_batch per step instead of two batches in flight")
     ap.add_argument("--dump-dir", default=None, help="every rank saves its utterances' waveforms there (tests: union of the shards)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, save what the last timed step returned (every utterance's waveform and frame "
+                         "count) as DIR/<name>.npy, float32 / float64, at most 64 MB in all; the inputs are the same on every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -294,13 +323,17 @@ def main():
         rank_ms = {"min": 1e3 * float(tmin.item()) / args.steps, "max": 1e3 * float(tmax.item()) / args.steps}
         dt = float(tmax.item())
 
-    res = call.results()
+    # the lane that ran the last timed step (every lane holds the same utterances)
+    last = call if (args.no_pipeline or depth == 1) else lanes[(args.steps - 1) % depth]
+    res = last.results()
     if not all(np.isfinite(w).all() and 0 < nf <= T for (w, nf) in res):
         sys.exit("bench.py: non-finite waveform or bad frame count")
     live_frames = int(sum(nf for _, nf in res))
     if args.dump_dir:
         np.savez(os.path.join(args.dump_dir, "rank%d.npz" % rank), index=np.arange(lo, hi), n_frames=np.array([nf for _, nf in res]),
                  **{"wav%d" % u: w for u, (w, _) in zip(range(lo, hi), res)})
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
 
     # ---- roofline of the dominant kernel family, same batch workload: live HIP-event timing, eager launches ----
     roofline, roofline_c1, kernels = None, None, []

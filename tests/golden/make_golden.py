@@ -2,7 +2,8 @@
 """Generate the golden fixtures from the compiled reference (oracle/_ref/zvref).
 
 Run in the build container only (it needs /root/reference to have been compiled by `make -C oracle ref`):
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py          (all fixtures)
+    python tests/golden/make_golden.py fresh    (only the fresh-seed fixtures)
 Fixtures hold inputs' *recipes* (geometry, seeds — inputs are regenerated bit-identically by
 zerovox.cpp_amd/synth.py) and the reference's OUTPUTS: in full for the small geometries, as strided
 samples + SHA-256 of the full f32 buffer for the full-size configs of BASELINE.json.  ISA of the
@@ -268,9 +269,53 @@ def norm_kat():
     print("instnorm KAT:", x_in[sel].shape)
 
 
+def fresh_cases(tmp="/tmp"):
+    """The reference's outputs on weights seeds no other fixture uses (the cases of
+    tests/test_oracle_golden.py::test_oracle_vs_live_reference_fresh_seed and
+    tests/test_gpu_vocoder.py::test_gpu_vs_live_reference_fresh_seed), stored in full so that those tests run where
+    oracle/_ref/zvref is not built; where it is, the tests also check that it still reproduces these files."""
+    g = synth.TINY
+    path = os.path.join(tmp, "golden_fresh_tiny.gguf")
+    synth.write_checkpoint(path, g, 99, trim_dims=True)      # ggml-C-writer style n_dims
+    _, tensors = gguf.read_gguf(path)
+    out = dict(geometry="tiny", seed_w=99, trim_dims=True, seed_mel=21, seed_hidden=22, seed_enc=23, cases=np.array([[7, 3], [33, 17]]))
+    for T, N in out["cases"]:
+        T, N = int(T), int(N)
+        mel = synth.vocoder_mel(g, tensors, 21, T)
+        hid = synth.decoder_hidden(g, 22, T)
+        ids, puncts, style = synth.encoder_inputs(g, 23, N)
+        k = "T%d_N%d_" % (T, N)
+        out[k + "wav"] = zvoracle.run_reference(path, T=T, voc=mel)["wav"]
+        out[k + "mel"] = zvoracle.run_reference(path, T=T, dec=(hid, style))["mel"]
+        r = zvoracle.run_reference(path, T=T, N=N, enc=(ids, puncts, style), E=g.E)
+        for name in ("hidden", "features", "logdur", "energy", "pitch_bucket", "energy_bucket", "n_frames"):
+            out[k + name] = r[name]
+    np.savez_compressed(os.path.join(HERE, "fresh_tiny_seed99.npz"), **out)
+    os.remove(path)
+    g = synth.SMALL
+    path = os.path.join(tmp, "golden_fresh_small.gguf")
+    synth.write_checkpoint(path, g, 4321)
+    _, tensors = gguf.read_gguf(path)
+    T, N = 72, 18
+    mel = synth.vocoder_mel(g, tensors, 23, T)
+    ids, puncts, style = synth.encoder_inputs(g, 24, N)
+    hid = synth.decoder_hidden(g, 25, T)
+    v = zvoracle.run_reference(path, T=T, voc=mel)
+    d = zvoracle.run_reference(path, T=T, dec=(hid, style))
+    e = zvoracle.run_reference(path, T=T, N=N, enc=(ids, puncts, style), E=g.E)
+    np.savez_compressed(os.path.join(HERE, "fresh_small_seed4321_T%d_N%d.npz" % (T, N)), geometry="small", seed_w=4321, T=T, N=N,
+                        seed_mel=23, seed_enc=24, seed_hidden=25, wav=v["wav"], mel=d["mel"], logdur=e["logdur"],
+                        n_frames=e["n_frames"])
+    print("fresh-seed cases: tiny seed 99 (T, N) =", [tuple(c) for c in out["cases"]], "| small seed 4321 frames", e["n_frames"])
+    os.remove(path)
+
+
 if __name__ == "__main__":
     if not zvoracle.have_reference():
         sys.exit("oracle/_ref/zvref missing: run `make -C oracle ref` first")
+    if sys.argv[1:] == ["fresh"]:           # only the fresh-seed fixtures (the others are left as they are)
+        fresh_cases()
+        sys.exit(0)
     case("tiny", 40, 10, full=True)
     case("small", 64, 16, full=True)
     case("medium", 512, 64, full=False)      # BASELINE.json configs[0] (N=64) and [1] (vocoder, 512 frames)
@@ -282,3 +327,4 @@ if __name__ == "__main__":
     robust_case()
     add_floors()
     add_encoder_margins()
+    fresh_cases()

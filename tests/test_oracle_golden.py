@@ -2,8 +2,7 @@
 
 The fixtures under tests/golden/ are OUTPUTS OF THE REFERENCE ITSELF (tests/golden/make_golden.py drives
 oracle/_ref/zvref = the unmodified stage classes on ggml-CPU).  The oracle must reproduce them bit for bit
-(ZVO_ORDER_GGML_AVX2).  Where oracle/_ref exists (it travels to the GPU box as a prebuilt binary) the same
-is checked live on fresh seeds."""
+(ZVO_ORDER_GGML_AVX2).  Where oracle/_ref exists the fresh-seed case is also checked live against it."""
 import hashlib
 import os
 
@@ -68,27 +67,36 @@ def test_oracle_reproduces_reference_full_size(ckpt, fixture):
 
 
 def test_oracle_vs_live_reference_fresh_seed(tmp_path):
-    """different weights seed + ragged sizes, compared live against oracle/_ref when it is present"""
+    """different weights seed + ragged sizes against the reference's outputs stored in tests/golden/fresh_tiny_seed99.npz,
+    and live against oracle/_ref when it is present (which must still reproduce the stored outputs)"""
     from zerovox_cpp_amd import gguf, synth
     from oracle import zvoracle
-    if not zvoracle.have_reference():
-        pytest.skip("oracle/_ref/zvref not built on this machine")
-    g = synth.TINY
+    z = np.load(os.path.join(GOLD, "fresh_tiny_seed99.npz"))
+    live = zvoracle.have_reference()
+    g = synth.GEOMETRIES[str(z["geometry"])]
     path = str(tmp_path / "t.gguf")
-    synth.write_checkpoint(path, g, 99, trim_dims=True)      # ggml-C-writer style n_dims
+    synth.write_checkpoint(path, g, int(z["seed_w"]), trim_dims=bool(z["trim_dims"]))      # ggml-C-writer style n_dims
     _, tensors = gguf.read_gguf(path)
     orc = zvoracle.Oracle(tensors)
-    for T, N in ((7, 3), (33, 17)):
-        mel = synth.vocoder_mel(g, tensors, 21, T)
-        hid = synth.decoder_hidden(g, 22, T)
-        ids, puncts, style = synth.encoder_inputs(g, 23, N)
-        assert np.array_equal(orc.vocoder(mel), zvoracle.run_reference(path, T=T, voc=mel)["wav"])
-        assert np.array_equal(orc.decoder(hid, style), zvoracle.run_reference(path, T=T, dec=(hid, style))["mel"])
-        r = zvoracle.run_reference(path, T=T, N=N, enc=(ids, puncts, style), E=g.E)
+    for T, N in z["cases"]:
+        T, N = int(T), int(N)
+        k = "T%d_N%d_" % (T, N)
+        mel = synth.vocoder_mel(g, tensors, int(z["seed_mel"]), T)
+        hid = synth.decoder_hidden(g, int(z["seed_hidden"]), T)
+        ids, puncts, style = synth.encoder_inputs(g, int(z["seed_enc"]), N)
+        assert np.array_equal(orc.vocoder(mel), z[k + "wav"])
+        assert np.array_equal(orc.decoder(hid, style), z[k + "mel"])
         e = orc.encoder(g, ids, puncts, style, T)
-        for k in ("hidden", "features", "logdur", "energy", "pitch_bucket", "energy_bucket"):
-            assert np.array_equal(e[k], r[k]), k
-        assert e["n_frames"] == r["n_frames"]
+        for name in ("hidden", "features", "logdur", "energy", "pitch_bucket", "energy_bucket"):
+            assert np.array_equal(e[name], z[k + name]), name
+        assert e["n_frames"] == int(z[k + "n_frames"])
+        if live:
+            assert np.array_equal(zvoracle.run_reference(path, T=T, voc=mel)["wav"], z[k + "wav"])
+            assert np.array_equal(zvoracle.run_reference(path, T=T, dec=(hid, style))["mel"], z[k + "mel"])
+            r = zvoracle.run_reference(path, T=T, N=N, enc=(ids, puncts, style), E=g.E)
+            for name in ("hidden", "features", "logdur", "energy", "pitch_bucket", "energy_bucket"):
+                assert np.array_equal(r[name], z[k + name]), name
+            assert r["n_frames"] == int(z[k + "n_frames"])
 
 
 def test_instancenorm_known_answer():
