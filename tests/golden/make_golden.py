@@ -4,6 +4,7 @@
 Run in the build container only (it needs /root/reference to have been compiled by `make -C oracle ref`):
     python tests/golden/make_golden.py          (all fixtures)
     python tests/golden/make_golden.py fresh    (only the fresh-seed fixtures)
+    python tests/golden/make_golden.py heads    (only the encoder head-count fixture)
 Fixtures hold inputs' *recipes* (geometry, seeds — inputs are regenerated bit-identically by
 zerovox.cpp_amd/synth.py) and the reference's OUTPUTS: in full for the small geometries, as strided
 samples + SHA-256 of the full f32 buffer for the full-size configs of BASELINE.json.  ISA of the
@@ -200,6 +201,29 @@ def add_floors(tmp="/tmp"):
     os.remove(path)
 
 
+def _encoder_margins(ref, a, ex):
+    """the reference semantics' own re-association noise on an encoder run: ref = the reference's outputs, a = our oracle in
+    sequential-f32 order, ex = our oracle in the reference's order (bit-exact; it supplies the float pitch prediction)"""
+    # the float pitch prediction comes from the bit-exact oracle: the reference's own pitch tensor is recycled by ggml's
+    # graph allocator before the harness can read it (its buckets, energy, log-durations and hidden are read and agree)
+    assert np.array_equal(ex["pitch_bucket"], ref["pitch_bucket"]) and np.array_equal(ex["energy"], ref["energy"])
+    assert np.array_equal(ex["logdur"], ref["logdur"]) and np.array_equal(ex["energy_bucket"], ref["energy_bucket"])
+    ref = dict(ref, pitch=ex["pitch"])
+    dur_r = np.exp(ref["logdur"].astype(np.float64)) - 1 + 0.5
+    dur_a = np.exp(a["logdur"].astype(np.float64)) - 1 + 0.5
+    pflip = a["pitch_bucket"] != ref["pitch_bucket"]
+    near = np.convolve(pflip.astype(np.int32), np.ones(5, np.int32), mode="same") > 0      # the energy predictor sees two k = 3 convs of x + pitch embedding
+    clean = ~near
+    return dict(pitch=ref["pitch"], energy=ref["energy"],
+                floor_logdur_max=float(np.max(np.abs(a["logdur"] - ref["logdur"]))),
+                floor_pitch_max=float(np.max(np.abs(a["pitch"] - ref["pitch"]))),
+                floor_energy_max=float(np.max(np.abs(a["energy"][clean] - ref["energy"][clean]))) if clean.any() else 0.0,
+                floor_dur_flips=int(np.sum(dur_r.astype(np.int64) != dur_a.astype(np.int64))),
+                floor_pitch_flips=int(pflip.sum()),
+                floor_energy_flips=int(np.sum(a["energy_bucket"] != ref["energy_bucket"])),
+                floor_frames=int(abs(int(a["n_frames"]) - int(ref["n_frames"]))))
+
+
 def add_encoder_margins(tmp="/tmp"):
     """what the reference semantics' own re-association noise does to the ENCODER of each full-size fixture (our oracle in
     sequential-f32 order against the reference on the same ids): the floors of the float predictions and of the integer
@@ -214,26 +238,7 @@ def add_encoder_margins(tmp="/tmp"):
     alt = zvoracle.Oracle(tensors, threads=8, order=zvoracle.ORDER_SEQ_F32)
     exact = zvoracle.Oracle(tensors, threads=8)          # the reference's summation order: reproduces it bit for bit
 
-    def margins(ref, a, ex):
-        # the float pitch prediction comes from the bit-exact oracle: the reference's own pitch tensor is recycled by ggml's
-        # graph allocator before the harness can read it (its buckets, energy, log-durations and hidden are read and agree)
-        assert np.array_equal(ex["pitch_bucket"], ref["pitch_bucket"]) and np.array_equal(ex["energy"], ref["energy"])
-        assert np.array_equal(ex["logdur"], ref["logdur"]) and np.array_equal(ex["energy_bucket"], ref["energy_bucket"])
-        ref = dict(ref, pitch=ex["pitch"])
-        dur_r = np.exp(ref["logdur"].astype(np.float64)) - 1 + 0.5
-        dur_a = np.exp(a["logdur"].astype(np.float64)) - 1 + 0.5
-        pflip = a["pitch_bucket"] != ref["pitch_bucket"]
-        near = np.convolve(pflip.astype(np.int32), np.ones(5, np.int32), mode="same") > 0      # the energy predictor sees two k = 3 convs of x + pitch embedding
-        clean = ~near
-        return dict(pitch=ref["pitch"], energy=ref["energy"],
-                    floor_logdur_max=float(np.max(np.abs(a["logdur"] - ref["logdur"]))),
-                    floor_pitch_max=float(np.max(np.abs(a["pitch"] - ref["pitch"]))),
-                    floor_energy_max=float(np.max(np.abs(a["energy"][clean] - ref["energy"][clean]))) if clean.any() else 0.0,
-                    floor_dur_flips=int(np.sum(dur_r.astype(np.int64) != dur_a.astype(np.int64))),
-                    floor_pitch_flips=int(pflip.sum()),
-                    floor_energy_flips=int(np.sum(a["energy_bucket"] != ref["energy_bucket"])),
-                    floor_frames=int(abs(int(a["n_frames"]) - int(ref["n_frames"]))))
-
+    margins = _encoder_margins
     for name in ("medium_T512_N64.npz", "medium_T512_N128.npz", "medium_T1024_N256.npz"):
         f = os.path.join(HERE, name)
         z = dict(np.load(f))
@@ -254,6 +259,36 @@ def add_encoder_margins(tmp="/tmp"):
     np.savez_compressed(f, **z)
     print("demo", {k: z[k] for k in z if k.startswith("floor_") and "mel" not in k and "wav" not in k})
     os.remove(path)
+
+
+HEAD_GEOMETRIES = ("medium_h1", "medium_h3", "medium_h4", "medium_h8")
+HEAD_CASES = ((37, 160), (300, 1200), (450, 1500))       # (N, T): attention over 37 / 300 / 450 keys
+
+
+def heads_cases(tmp="/tmp"):
+    """The reference's encoder at `encoder.head` = 1, 3, 4, 8 (dk = 528, 176, 132, 66; every other fixture has 2): log-durations,
+    energies, buckets and frame counts in full, features / hidden as SHA-256, and the re-association floors of
+    _encoder_margins (so that a GPU test can gate its encoder on them).  One file for the four geometries."""
+    out = dict(geometries=np.array(HEAD_GEOMETRIES), cases=np.array(HEAD_CASES), seed_w=SEED_W, seed_enc=5)
+    for gname in HEAD_GEOMETRIES:
+        g = synth.GEOMETRIES[gname]
+        path = os.path.join(tmp, f"golden_{gname}.gguf")
+        synth.write_checkpoint(path, g, SEED_W)
+        _, tensors = gguf.read_gguf(path)
+        alt = zvoracle.Oracle(tensors, threads=8, order=zvoracle.ORDER_SEQ_F32)
+        exact = zvoracle.Oracle(tensors, threads=8)
+        for N, T in HEAD_CASES:
+            ids, puncts, style = synth.encoder_inputs(g, 5, N)
+            r = zvoracle.run_reference(path, T=T, N=N, enc=(ids, puncts, style), E=g.E)
+            k = "%s_N%d_" % (gname, N)
+            for name in ("logdur", "energy", "pitch_bucket", "energy_bucket", "n_frames"):
+                out[k + name] = r[name]
+            out[k + "features_sha256"], out[k + "hidden_sha256"] = sha(r["features"]), sha(r["hidden"])
+            m = _encoder_margins(r, alt.encoder(g, ids, puncts, style, T), exact.encoder(g, ids, puncts, style, T))
+            out.update({k + name: v for name, v in m.items()})
+            print(gname, N, T, "frames", r["n_frames"], {n: m[n] for n in m if n.startswith("floor_")})
+        os.remove(path)
+    np.savez_compressed(os.path.join(HERE, "medium_heads.npz"), **out)
 
 
 def norm_kat():
@@ -316,6 +351,9 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["fresh"]:           # only the fresh-seed fixtures (the others are left as they are)
         fresh_cases()
         sys.exit(0)
+    if sys.argv[1:] == ["heads"]:           # only the encoder head-count fixture
+        heads_cases()
+        sys.exit(0)
     case("tiny", 40, 10, full=True)
     case("small", 64, 16, full=True)
     case("medium", 512, 64, full=False)      # BASELINE.json configs[0] (N=64) and [1] (vocoder, 512 frames)
@@ -328,3 +366,4 @@ if __name__ == "__main__":
     add_floors()
     add_encoder_margins()
     fresh_cases()
+    heads_cases()

@@ -44,3 +44,64 @@ def encoder_decisions_vs_reference(e, z, nb, T):
     assert int(eflip.sum()) <= 2 * int(z["floor_energy_flips"]) + 2
     assert min(e["n_frames"], int(z["n_frames"])) == T or abs(e["n_frames"] - int(z["n_frames"])) <= int(dflip.sum())
     return int(dflip.sum()), int(pflip.sum()), int(eflip.sum())
+
+
+def _rms(a):
+    return float(np.sqrt(np.mean(np.asarray(a, np.float64) ** 2)))
+
+
+def layer_gate(name, got, ref, alt, rel_gate, floor_mult=2.0):
+    """got: GPU, ref: oracle (ggml AVX2 order), alt: oracle (sequential f32).  rel = rms(err) / rms(signal)."""
+    sig = _rms(ref)
+    err, floor = _rms(got - ref) / sig, _rms(alt - ref) / sig
+    mx = float(np.max(np.abs(got - ref))) / sig
+    print(f"{name:28s} rel rms err {err:.2e} (oracle self-noise {floor:.2e}), max {mx:.2e}, signal rms {sig:.3f}")
+    assert np.isfinite(got).all()
+    assert err <= max(floor_mult * floor, 3e-7), name          # no worse than the reference's own re-association noise
+    assert err <= rel_gate, name
+
+
+def oracle_pair(o, fn, *args, **kw):
+    """fn(*args, **kw) of the oracle o in the reference's summation order (ggml AVX2) and in sequential f32 order"""
+    from oracle import zvoracle
+    o.set_order(zvoracle.ORDER_GGML_AVX2)
+    ref = getattr(o, fn)(*args, **kw)
+    o.set_order(zvoracle.ORDER_SEQ_F32)
+    alt = getattr(o, fn)(*args, **kw)
+    o.set_order(zvoracle.ORDER_GGML_AVX2)
+    return ref, alt
+
+
+# the kernels only batches pick by themselves, forced on for one utterance (some are sampled when a model is built: build it
+# inside capi.switches(**BATCH_REGIME))
+BATCH_REGIME = dict(ZV_BLOCK64=-11, ZV_CONV_STREAM=2, ZV_CONV_GEMM=2, ZV_UP_GEMM=2, ZV_PAIR64_RING=2, ZV_TRIPLE_V2=3, ZV_FUSE256=1,
+                    ZV_PAIR_MT=0, ZV_DEC_PREPASS=1)
+
+# every kernel regime of the vocoder (tests/test_gpu_full_size.py::test_kernel_regimes_give_the_same_bits): each sums every
+# output element in the same order, so none may change a bit
+VOCODER_REGIMES = (
+    ("default", {}), ("fuse256", {"ZV_FUSE256": 1}), ("no_triple", {"ZV_NO_TRIPLE": 1}), ("no_fuse", {"ZV_NO_FUSE": 1}),
+    ("no_merge", {"ZV_NO_MERGE": 1}), ("fuse256_no_merge", {"ZV_FUSE256": 1, "ZV_NO_MERGE": 1}),
+    ("merge", {"ZV_MERGE_ALWAYS": 1}), ("fuse256_merge", {"ZV_FUSE256": 1, "ZV_MERGE_ALWAYS": 1}),
+    ("merge_in_one_workgroup", {"ZV_MERGE_ALWAYS": 1, "ZV_MERGE_SEQ": 0}),
+    ("fuse256_merge_in_one_workgroup", {"ZV_FUSE256": 1, "ZV_MERGE_ALWAYS": 1, "ZV_MERGE_SEQ": 0}),
+    ("fuse256_merge_mt3", {"ZV_FUSE256": 1, "ZV_MERGE_ALWAYS": 1, "ZV_PAIR_MT": 3}),
+    ("pair64_ring_merge", {"ZV_PAIR64_RING": 2, "ZV_MERGE_ALWAYS": 1}),
+    ("single_loop_everywhere", {"ZV_CONV_SINGLE": 2}), ("no_single_loop", {"ZV_CONV_SINGLE": 0}),
+    ("block_v1", {"ZV_TRIPLE_V2": 0}), ("block_v2", {"ZV_TRIPLE_V2": 2}),
+    ("block_v2_512", {"ZV_TRIPLE_V2": 3}), ("block_v2_512_one_weight_buffer", {"ZV_TRIPLE_V2": 3, "ZV_TRIPLE_DB": 0}),
+    ("block_v2_not_interleaved", {"ZV_TRIPLE_V2": 2, "ZV_TRIPLE_INTERLEAVE": 0}),
+    ("pair64_ring", {"ZV_PAIR64_RING": 2}), ("pair64_ring_no_merge", {"ZV_PAIR64_RING": 2, "ZV_NO_MERGE": 1}),
+    ("pair64_no_ring", {"ZV_PAIR64_RING": 0}),
+    ("upsample_gemm", {"ZV_UP_GEMM": 2, "ZV_CONV_GEMM": 2}), ("upsample_no_gemm", {"ZV_UP_GEMM": 0}),
+    ("block64_3_merge", {"ZV_BLOCK64": -3, "ZV_PAIR64_RING": 2, "ZV_MERGE_ALWAYS": 1}),
+    ("block64_3_no_merge", {"ZV_BLOCK64": -3, "ZV_PAIR64_RING": 2}), ("block64_11", {"ZV_BLOCK64": -11, "ZV_PAIR64_RING": 2}),
+    ("no_block64", {"ZV_BLOCK64": 0, "ZV_PAIR64_RING": 2}),
+    ("upsample_stream", {"ZV_CONV_STREAM": 2}), ("upsample_no_stream", {"ZV_CONV_STREAM": 0}),
+    # the fused batch kernels run on v_mfma_f32_16x16x32_f16, the generic conv kernel ("no_fuse") and the single-utterance
+    # whole-block kernel on 32x32x16: one k-ordered chain, two instruction shapes, the same bits
+    ("pair_mt4", {"ZV_PAIR_MT": 4, "ZV_FUSE256": 1}),
+    ("pair_no_ring_no_triple", {"ZV_PAIR64_RING": 0, "ZV_NO_TRIPLE": 1, "ZV_MERGE_ALWAYS": 1}),
+    # the single-utterance conv form (loader waves, two LDS tiles) with its channel groups dealt / not dealt over the XCDs
+    ("single_loop_everywhere_plain_grid", {"ZV_CONV_SINGLE": 2, "ZV_CONV_XCD": 0}), ("plain_grid", {"ZV_CONV_XCD": 0}),
+)

@@ -212,31 +212,9 @@ def test_kernel_regimes_give_the_same_bits(ckpt):
     from zerovox_cpp_amd import capi, synth
     path, g, tensors = ckpt("medium")
     mel = synth.vocoder_mel(g, tensors, 51, 384)
+    from parity_helpers import VOCODER_REGIMES
     outs = {}
-    for name, env in (("default", {}), ("fuse256", {"ZV_FUSE256": "1"}), ("no_triple", {"ZV_NO_TRIPLE": "1"}), ("no_fuse", {"ZV_NO_FUSE": "1"}),
-                      ("no_merge", {"ZV_NO_MERGE": "1"}), ("fuse256_no_merge", {"ZV_FUSE256": "1", "ZV_NO_MERGE": "1"}),
-                      ("merge", {"ZV_MERGE_ALWAYS": "1"}), ("fuse256_merge", {"ZV_FUSE256": "1", "ZV_MERGE_ALWAYS": "1"}),
-                      ("merge_in_one_workgroup", {"ZV_MERGE_ALWAYS": "1", "ZV_MERGE_SEQ": "0"}),
-                      ("fuse256_merge_in_one_workgroup", {"ZV_FUSE256": "1", "ZV_MERGE_ALWAYS": "1", "ZV_MERGE_SEQ": "0"}),
-                      ("fuse256_merge_mt3", {"ZV_FUSE256": "1", "ZV_MERGE_ALWAYS": "1", "ZV_PAIR_MT": "3"}),
-                      ("pair64_ring_merge", {"ZV_PAIR64_RING": "2", "ZV_MERGE_ALWAYS": "1"}),
-                      ("single_loop_everywhere", {"ZV_CONV_SINGLE": "2"}), ("no_single_loop", {"ZV_CONV_SINGLE": "0"}),
-                      ("block_v1", {"ZV_TRIPLE_V2": "0"}), ("block_v2", {"ZV_TRIPLE_V2": "2"}),
-                      ("block_v2_512", {"ZV_TRIPLE_V2": "3"}), ("block_v2_512_one_weight_buffer", {"ZV_TRIPLE_V2": "3", "ZV_TRIPLE_DB": "0"}),
-                      ("block_v2_not_interleaved", {"ZV_TRIPLE_V2": "2", "ZV_TRIPLE_INTERLEAVE": "0"}),
-                      ("pair64_ring", {"ZV_PAIR64_RING": "2"}), ("pair64_ring_no_merge", {"ZV_PAIR64_RING": "2", "ZV_NO_MERGE": "1"}),
-                      ("pair64_no_ring", {"ZV_PAIR64_RING": "0"}),
-                      ("upsample_gemm", {"ZV_UP_GEMM": "2", "ZV_CONV_GEMM": "2"}), ("upsample_no_gemm", {"ZV_UP_GEMM": "0"}),
-                      ("block64_3_merge", {"ZV_BLOCK64": "-3", "ZV_PAIR64_RING": "2", "ZV_MERGE_ALWAYS": "1"}),
-                      ("block64_3_no_merge", {"ZV_BLOCK64": "-3", "ZV_PAIR64_RING": "2"}), ("block64_11", {"ZV_BLOCK64": "-11", "ZV_PAIR64_RING": "2"}),
-                      ("no_block64", {"ZV_BLOCK64": "0", "ZV_PAIR64_RING": "2"}),
-                      ("upsample_stream", {"ZV_CONV_STREAM": "2"}), ("upsample_no_stream", {"ZV_CONV_STREAM": "0"}),
-                      # round 4: the fused batch kernels run on v_mfma_f32_16x16x32_f16, the generic conv kernel ("no_fuse") and the
-                      # single-utterance whole-block kernel on 32x32x16: one k-ordered chain, two instruction shapes, the same bits
-                      ("pair_mt4", {"ZV_PAIR_MT": "4", "ZV_FUSE256": "1"}),
-                      ("pair_no_ring_no_triple", {"ZV_PAIR64_RING": "0", "ZV_NO_TRIPLE": "1", "ZV_MERGE_ALWAYS": "1"}),
-                      # the single-utterance conv form (loader waves, two LDS tiles) with its channel groups dealt / not dealt over the XCDs
-                      ("single_loop_everywhere_plain_grid", {"ZV_CONV_SINGLE": "2", "ZV_CONV_XCD": "0"}), ("plain_grid", {"ZV_CONV_XCD": "0"})):
+    for name, env in VOCODER_REGIMES:
         with capi.switches(**{k: int(v) for k, v in env.items()}):      # some switches are sampled when the model is built, some at every launch
             m = capi.Model(path, 0)
             outs[name] = m.vocode(mel)

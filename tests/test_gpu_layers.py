@@ -30,29 +30,14 @@ def teardown_module(module):
     _M.clear()
 
 
-def _rms(a):
-    return float(np.sqrt(np.mean(np.asarray(a, np.float64) ** 2)))
-
-
 def _check(name, got, ref, alt, rel_gate, floor_mult=2.0):
-    """got: GPU, ref: oracle (ggml AVX2 order), alt: oracle (sequential f32).  rel = rms(err) / rms(signal)."""
-    sig = _rms(ref)
-    err, floor = _rms(got - ref) / sig, _rms(alt - ref) / sig
-    mx = float(np.max(np.abs(got - ref))) / sig
-    print(f"{name:28s} rel rms err {err:.2e} (oracle self-noise {floor:.2e}), max {mx:.2e}, signal rms {sig:.3f}")
-    assert np.isfinite(got).all()
-    assert err <= max(floor_mult * floor, 3e-7), name          # no worse than the reference's own re-association noise
-    assert err <= rel_gate, name
+    from parity_helpers import layer_gate
+    layer_gate(name, got, ref, alt, rel_gate, floor_mult)
 
 
 def _oracle_pair(o, *args, **kw):
-    from oracle import zvoracle
-    o.set_order(zvoracle.ORDER_GGML_AVX2)
-    ref = o.layer(*args, **kw)
-    o.set_order(zvoracle.ORDER_SEQ_F32)
-    alt = o.layer(*args, **kw)
-    o.set_order(zvoracle.ORDER_GGML_AVX2)
-    return ref, alt
+    from parity_helpers import oracle_pair
+    return oracle_pair(o, "layer", *args, **kw)
 
 
 @pytest.mark.parametrize("block", list(range(12)))
@@ -220,8 +205,7 @@ def test_every_adain_alone(env, idx):
 
 # ---- round 4: the same per-layer gates with the kernels only BATCHES pick forced on (a regression in a batch kernel then
 # ---- shows at its layer, against the reference semantics, instead of in a whole-vocoder RMS) --------------------------------
-BATCH_REGIME = dict(ZV_BLOCK64=-11, ZV_CONV_STREAM=2, ZV_CONV_GEMM=2, ZV_UP_GEMM=2, ZV_PAIR64_RING=2, ZV_TRIPLE_V2=3, ZV_FUSE256=1,
-                    ZV_PAIR_MT=0, ZV_DEC_PREPASS=1)
+from parity_helpers import BATCH_REGIME  # noqa: E402
 
 
 def _batch_model(ckpt):

@@ -211,3 +211,32 @@ def test_oracle_layers_compose_to_the_oracle_vocoder(tmp_path):
         ys = [o.layer(o.LAYER_VOC_RESBLOCK, i * 3 + j, up, up.shape[1]) for j in range(3)]
         x = ((ys[0] + ys[1]) + ys[2]) * np.float32(1.0 / np.float32(3))          # src/hifigan.cpp:300-315
     assert np.array_equal(o.layer(o.LAYER_VOC_OUTPUT, 0, x, 0), o.vocoder(mel))
+
+
+@pytest.mark.parametrize("geom", ["medium_h1", "medium_h3", "medium_h4", "medium_h8"])
+def test_oracle_encoder_at_other_head_counts(ckpt, geom):
+    """`encoder.head` is read from the checkpoint (reference src/zerovox.cpp, src/fs2encoder.cpp:71-140 splits E into H heads of
+    dk = E / H); every other fixture has H = 2.  At H = 1, 3, 4, 8 (dk = 528, 176, 132, 66) and 37 / 300 / 450 tokens the oracle's
+    encoder must reproduce the reference's outputs stored in tests/golden/medium_heads.npz bit for bit — and, where oracle/_ref is
+    built, a live run of the reference must still reproduce the stored outputs"""
+    from zerovox_cpp_amd import synth
+    from oracle import zvoracle
+    z = np.load(os.path.join(GOLD, "medium_heads.npz"))
+    assert geom in [str(x) for x in z["geometries"]]
+    path, g, tensors = ckpt(geom, int(z["seed_w"]))
+    assert g.E % g.encoder_head == 0 and g.encoder_head != 2
+    orc = zvoracle.Oracle(tensors)
+    live = zvoracle.have_reference()
+    for N, T in z["cases"]:
+        N, T = int(N), int(T)
+        k = "%s_N%d_" % (geom, N)
+        ids, puncts, style = synth.encoder_inputs(g, int(z["seed_enc"]), N)
+        e = orc.encoder(g, ids, puncts, style, T)
+        for name in ("logdur", "energy", "pitch_bucket", "energy_bucket"):
+            assert np.array_equal(e[name], z[k + name]), (N, name)
+        assert e["n_frames"] == int(z[k + "n_frames"])
+        assert sha(e["features"]) == str(z[k + "features_sha256"]) and sha(e["hidden"]) == str(z[k + "hidden_sha256"])
+        assert np.array_equal(e["pitch"], z[k + "pitch"])
+        if live:
+            r = zvoracle.run_reference(path, T=T, N=N, enc=(ids, puncts, style), E=g.E)
+            assert np.array_equal(r["logdur"], z[k + "logdur"]) and sha(r["hidden"]) == str(z[k + "hidden_sha256"])

@@ -125,7 +125,15 @@ SMALL = Geometry(name="small", emb_dim=112, punct_emb_dim=16, conv_filter_size=2
 # the same integer decisions under any re-association — the un-forced end-to-end golden (tests/golden/make_golden.py)
 MEDIUM8 = Geometry(name="medium8", ve_n_bins=8)
 
-GEOMETRIES = {g.name: g for g in (MEDIUM, TINY, SMALL, MEDIUM8)}
+# MEDIUM with another `encoder.head` (a free KV of the checkpoint format, read by the reference and the loader alike): head dims
+# dk = E / H = 528 (H = 1: above the matrix-core attention's 288), 176 (H = 3: a matrix-core head dim that is not a multiple of 64),
+# 132 (H = 4: ns = dk / 2 = 66, the MFMA loop's last group of two steps) and 66 (H = 8: dk % 4 != 0, the scalar kernel only)
+MEDIUM_H1 = Geometry(name="medium_h1", encoder_head=1)
+MEDIUM_H3 = Geometry(name="medium_h3", encoder_head=3)
+MEDIUM_H4 = Geometry(name="medium_h4", encoder_head=4)
+MEDIUM_H8 = Geometry(name="medium_h8", encoder_head=8)
+
+GEOMETRIES = {g.name: g for g in (MEDIUM, TINY, SMALL, MEDIUM8, MEDIUM_H1, MEDIUM_H3, MEDIUM_H4, MEDIUM_H8)}
 
 
 def sinusoid_table(n_position: int, d_hid: int) -> np.ndarray:
