@@ -1,4 +1,4 @@
-# per-kernel register / spill / occupancy report of a .hip file: bash scripts/kres.sh conv1d_mfma.hip [substring of the kernel name]
+# per-kernel register / spill / occupancy report of a .hip file: bash scripts/kres.sh conv_kernels.hip (the shipped unit of conv.hip, conv1d_mfma.hip and conv_gemm.hip; any one of them alone also compiles) [substring of the kernel name]
 cd "$(dirname "$0")/../zerovox.cpp_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off $EXTRA -Rpass-analysis=kernel-resource-usage -c "$1" -o /tmp/kres.o 2>&1 |
 python3 -c "

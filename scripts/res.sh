@@ -1,5 +1,5 @@
 # per-kernel register / scratch / occupancy summary of a HIP source (hipcc -Rpass-analysis=kernel-resource-usage)
-# usage: bash scripts/res.sh zerovox.cpp_amd/csrc/conv1d_mfma.hip
+# usage: bash scripts/res.sh zerovox.cpp_amd/csrc/conv_kernels.hip   (the shipped unit of the three conv sources; any .hip file works)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Wno-unused-value $EXTRA -c $1 -o /tmp/res_tmp.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
 import sys,re,subprocess
 cur={}

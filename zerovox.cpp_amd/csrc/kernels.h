@@ -135,7 +135,7 @@ struct ConvJobs
     int     xcd_ny, xcd_nx;      // single-utterance form: channel groups / row tiles of the launch when the groups are dealt over the XCDs (0: plain grid)
     int     warm;                // single-utterance forms: the row tiles of a channel group warm their XCD's L2 with the group's weights first
 #ifdef ZV_STAMPS
-    int     stamp;               // diagnostic build: this launch writes phase stamps
+    unsigned long long *stamp;   // diagnostic build: the phase-stamp buffer this launch writes (stamp_buffer()), or null
 #endif
 };
 
@@ -183,7 +183,7 @@ struct PairJobs
     int     rate;
     int     njobs, kmax;
 #ifdef ZV_STAMPS
-    int     stamp;               // diagnostic build: this launch writes phase stamps
+    unsigned long long *stamp;   // diagnostic build: the phase-stamp buffer this launch writes (stamp_buffer()), or null
 #endif
     float  *merge_out;           // non-null: store (out_0 + out_1) + out_2 here instead of the jobs' own outputs
     int     ring_off;            // resblock_pair64_kernel: byte offset of the weight ring in LDS (set by the launcher)
@@ -232,7 +232,7 @@ struct TripleJobs
     int       db_mask;           // resblock_block32_kernel: bit j = job j keeps two weight buffers in LDS (set by the launcher)
     int       ring_off;          // resblock_block64_kernel: byte offset of the weight ring in LDS (set by the launcher)
 #ifdef ZV_STAMPS
-    int       stamp;
+    unsigned long long *stamp;   // diagnostic build: the phase-stamp buffer this launch writes (stamp_buffer()), or null
 #endif
 };
 // true when a ResBlock (Cp channels, K taps, these dilations) fits the whole-block kernel
