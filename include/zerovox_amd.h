@@ -207,11 +207,13 @@ zv_status zv_profile_end(zv_model *m, zv_kernel_stat *stats, uint32_t cap, uint3
  *   ZV_LAYER_ENC_MHA       index l: MultiHeadAttention l alone, with its residual + LayerNorm (src/fs2encoder.cpp:71-140)
  *   ZV_LAYER_ENC_FFN       index l: PositionwiseFeedForward l alone, with its residual + LayerNorm (src/fs2encoder.cpp:174-228)
  *   ZV_LAYER_DEC_ADAIN     index 2 * b + (norm - 1): AdaIN1d norm1 / norm2 of AdainResBlk1d decode.b alone, with `style`
- *                          (src/stylettsdec.cpp:171-200): x [T][C] -> out [T][C], C = the block's cin (norm1) / cout (norm2) */
+ *                          (src/stylettsdec.cpp:171-200): x [T][C] -> out [T][C], C = the block's cin (norm1) / cout (norm2)
+ *   ZV_LAYER_ENC_LN        index 2 * l + j: the LayerNorm of FFT block l's attention (j = 0) / feed-forward (j = 1) sublayer alone,
+ *                          x being its input (src/fs2encoder.cpp:132-137, 219-224): x [N][E] -> out [N][E] */
 typedef enum { ZV_LAYER_VOC_RESBLOCK = 0, ZV_LAYER_ENC_FFT = 1, ZV_LAYER_DEC_BLOCK = 2, ZV_LAYER_VAR_PRED = 3,
                ZV_LAYER_VOC_UPSAMPLE = 4, ZV_LAYER_VOC_INPUT = 5, ZV_LAYER_VOC_OUTPUT = 6, ZV_LAYER_DEC_ASR_RES = 7,
                ZV_LAYER_DEC_TO_OUT = 8, ZV_LAYER_ENC_EMBED = 9, ZV_LAYER_ENC_MHA = 10, ZV_LAYER_ENC_FFN = 11,
-               ZV_LAYER_DEC_ADAIN = 12 } zv_layer_kind;
+               ZV_LAYER_DEC_ADAIN = 12, ZV_LAYER_ENC_LN = 13 } zv_layer_kind;
 zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint32_t rows, const float *style, float *out);
 
 /* ---- test / measurement switches (none is needed in production; no reference counterpart: the reference's only run-time

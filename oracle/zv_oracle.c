@@ -953,6 +953,14 @@ int zvo_layer(zvo_ctx *c, int kind, int index, const float *x, int rows, int col
         rc = mha(c, x, rows, cols, index, H, out);
     else if (kind == ZVO_LAYER_ENC_FFN)                /* PositionwiseFeedForward `index` alone (src/fs2encoder.cpp:174-228, residual + LayerNorm included) */
         rc = ffn(c, x, rows, cols, index, ksz, out);
+    else if (kind == ZVO_LAYER_ENC_LN)                 /* LayerNorm of FFT block index / 2 alone, x its input (src/fs2encoder.cpp:132-137, 219-224) */
+    {
+        const char *sub = (index & 1) ? "pos_ffn" : "slf_attn";
+        const zvo_tensor *lw = get(c, "_pe._enc.laystk.%d.%s.layer_norm.w", index >> 1, sub);
+        const zvo_tensor *lb = get(c, "_pe._enc.laystk.%d.%s.layer_norm.b", index >> 1, sub);
+        if (index < 0 || !lw || !lb) return index < 0 ? fail("LayerNorm %d", index) : -1;
+        add_layernorm_tm(x, NULL, rows, cols, (const float *)lw->data, (const float *)lb->data, out);
+    }
     else if (kind == ZVO_LAYER_DEC_ADAIN)              /* AdaIN1d alone (src/stylettsdec.cpp:171-200): index = 2 * decode block + (norm - 1): [T][C] -> [T][C] */
     {
         if (index < 0 || index > 9) return fail("AdaIN %d", index);

@@ -5,6 +5,7 @@ Run in the build container only (it needs /root/reference to have been compiled 
     python tests/golden/make_golden.py          (all fixtures)
     python tests/golden/make_golden.py fresh    (only the fresh-seed fixtures)
     python tests/golden/make_golden.py heads    (only the encoder head-count fixture)
+    python tests/golden/make_golden.py value_ranges    (only the value-range stage fixture)
 Fixtures hold inputs' *recipes* (geometry, seeds — inputs are regenerated bit-identically by
 zerovox.cpp_amd/synth.py) and the reference's OUTPUTS: in full for the small geometries, as strided
 samples + SHA-256 of the full f32 buffer for the full-size configs of BASELINE.json.  ISA of the
@@ -345,11 +346,43 @@ def fresh_cases(tmp="/tmp"):
     os.remove(path)
 
 
+def value_ranges_case(tmp="/tmp"):
+    """The reference's decoder and vocoder on the crafted stage inputs of tests/parity_helpers.value_range_stage_inputs (small
+    geometry): a decoder hidden with per-channel offsets up to 1e3 sigma, constant channels and an all-zero band; a vocoder mel
+    in magnitude bands, the first exactly at hifigan.mean.  SHA-256 + strided samples of the outputs, and per gated region the
+    reference semantics' own re-association floor (our oracle in sequential-f32 order against the reference, as add_floors)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import parity_helpers as ph
+    g = synth.SMALL
+    path = os.path.join(tmp, "golden_value_ranges_small.gguf")
+    synth.write_checkpoint(path, g, SEED_W)
+    _, tensors = gguf.read_gguf(path)
+    hid, style, mel_in, dreg, vreg = ph.value_range_stage_inputs(g, tensors)
+    mel = zvoracle.run_reference(path, T=hid.shape[0], dec=(hid, style))["mel"]
+    wav = zvoracle.run_reference(path, T=mel_in.shape[0], voc=mel_in)["wav"]
+    alt = zvoracle.Oracle(tensors, threads=8, order=zvoracle.ORDER_SEQ_F32)
+    dm, dw = alt.decoder(hid, style) - mel, alt.vocoder(mel_in) - wav
+    rms = lambda a: float(np.sqrt(np.mean(np.asarray(a, np.float64) ** 2)))
+    out = dict(geometry="small", seed_w=SEED_W, stride=STRIDE, mel_sha256=sha(mel), wav_sha256=sha(wav),
+               mel_samples=mel.reshape(-1)[::STRIDE].copy(), wav_samples=wav[::STRIDE].copy())
+    for stage, d, ref, regs in (("mel", dm, mel, dreg), ("wav", dw, wav, vreg)):
+        out[stage + "_floor_rms"] = np.array([rms(d[idx]) for _, idx in regs])
+        out[stage + "_floor_max"] = np.array([float(np.max(np.abs(d[idx]))) for _, idx in regs])
+        out[stage + "_rms"] = np.array([rms(ref[idx]) for _, idx in regs])
+        for (lbl, _), f, fm, r in zip(regs, out[stage + "_floor_rms"], out[stage + "_floor_max"], out[stage + "_rms"]):
+            print(f"value ranges {stage} [{lbl}]: rms {r:.3e}, floor rms {f:.3e} max {fm:.3e}")
+    np.savez_compressed(os.path.join(HERE, "value_ranges_small.npz"), **out)
+    os.remove(path)
+
+
 if __name__ == "__main__":
     if not zvoracle.have_reference():
         sys.exit("oracle/_ref/zvref missing: run `make -C oracle ref` first")
     if sys.argv[1:] == ["fresh"]:           # only the fresh-seed fixtures (the others are left as they are)
         fresh_cases()
+        sys.exit(0)
+    if sys.argv[1:] == ["value_ranges"]:    # only the value-range stage fixture
+        value_ranges_case()
         sys.exit(0)
     if sys.argv[1:] == ["heads"]:           # only the encoder head-count fixture
         heads_cases()
@@ -367,3 +400,4 @@ if __name__ == "__main__":
     add_encoder_margins()
     fresh_cases()
     heads_cases()
+    value_ranges_case()

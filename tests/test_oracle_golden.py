@@ -240,3 +240,41 @@ def test_oracle_encoder_at_other_head_counts(ckpt, geom):
         if live:
             r = zvoracle.run_reference(path, T=T, N=N, enc=(ids, puncts, style), E=g.E)
             assert np.array_equal(r["logdur"], z[k + "logdur"]) and sha(r["hidden"]) == str(z[k + "hidden_sha256"])
+
+
+def test_oracle_value_ranges_small(ckpt):
+    """the oracle at the value-range edges (tests/golden/value_ranges_small.npz: a decoder hidden with per-channel offsets up to
+    1e3 sigma, constant channels and an all-zero band; a vocoder mel in magnitude bands, the first exactly at hifigan.mean)
+    against the reference's outputs bit for bit, and live against oracle/_ref where it is present"""
+    import parity_helpers as ph
+    from oracle import zvoracle
+    z = np.load(os.path.join(GOLD, "value_ranges_small.npz"))
+    path, g, tensors = ckpt(str(z["geometry"]), int(z["seed_w"]))
+    hid, style, mel_in, _, _ = ph.value_range_stage_inputs(g, tensors)
+    s = int(z["stride"])
+    orc = zvoracle.Oracle(tensors)
+    mel, wav = orc.decoder(hid, style), orc.vocoder(mel_in)
+    assert np.array_equal(mel.reshape(-1)[::s], z["mel_samples"]) and sha(mel) == str(z["mel_sha256"])
+    assert np.array_equal(wav[::s], z["wav_samples"]) and sha(wav) == str(z["wav_sha256"])
+    if zvoracle.have_reference():
+        assert sha(zvoracle.run_reference(path, T=hid.shape[0], dec=(hid, style))["mel"]) == str(z["mel_sha256"])
+        assert sha(zvoracle.run_reference(path, T=mel_in.shape[0], voc=mel_in)["wav"]) == str(z["wav_sha256"])
+
+
+def test_oracle_layernorm_alone_on_value_range_rows(ckpt):
+    """ZVO_LAYER_ENC_LN (the LayerNorm alone, used by the value-range tests) against an f64 LayerNorm of the same rows: constant
+    rows give b exactly, the others agree to f32 rounding"""
+    import parity_helpers as ph
+    from oracle import zvoracle
+    path, g, tensors = ckpt("small")
+    x, reg = ph.ln_rows(2200, 40, g.E)
+    o = zvoracle.Oracle(tensors)
+    for j, sub in ((0, "slf_attn"), (1, "pos_ffn")):
+        y = o.layer(o.LAYER_ENC_LN, 2 + j, x, g.E)
+        w = tensors[f"_pe._enc.laystk.1.{sub}.layer_norm.w"].astype(np.float64)
+        b = tensors[f"_pe._enc.laystk.1.{sub}.layer_norm.b"].astype(np.float64)
+        xd = x.astype(np.float64)
+        want = (xd - xd.mean(1, keepdims=True)) / np.sqrt(xd.var(1, keepdims=True) + 1e-5) * w + b
+        c = dict(reg)["constant rows"]
+        assert np.array_equal(y[c], np.broadcast_to(b.astype(np.float32), y[c].shape))
+        assert np.max(np.abs(y - want)) <= 1e-5 * np.max(np.abs(want))

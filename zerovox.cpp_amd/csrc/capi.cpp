@@ -732,6 +732,8 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
             ZV_HIP(hipMemcpyAsync(d_sty, sty, E * 4, hipMemcpyHostToDevice, M.stream));
             M.decode_dev(zv::Batch::single(1, T, 1), d_hid, d_sty, d_mel);
         }
+        else if (kind == ZV_LAYER_ENC_LN)
+            M.debug_layernorm(index, rows);
         else
             zv::fail(ZV_ERR_ARG, "unknown layer kind %d", kind);
         M.sync();

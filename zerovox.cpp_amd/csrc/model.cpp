@@ -796,6 +796,20 @@ void Model::dbg_extract(const void *dev, int ld, int cols, size_t rows)
     dbg_layer.done = true;
 }
 
+// the LayerNorm of FFT block index / 2's attention (even index) / feed-forward (odd) sublayer, launched as the encoder launches
+// it but without the residual, on n given rows; an index past the encoder leaves dbg_layer.done false
+void Model::debug_layernorm(int index, uint32_t n)
+{
+    const int l = index >> 1, Ed = (int)E();
+    if (index < 0 || l >= (int)enc_.layers.size()) return;
+    const EncLayer &Ly = enc_.layers[l];
+    float *d = (float *)io_scratch(2 * (size_t)n * Ed * 4), *y = d + (size_t)n * Ed;
+    dbg_inject(d, Ed, Ed, n);
+    ZV_HIP(launch_add_layernorm(stream, d, Ed, nullptr, 0, Ed, Ed, (index & 1) ? Ly.ln2w : Ly.ln1w, (index & 1) ? Ly.ln2b : Ly.ln1b,
+                                1e-5f, y, Ed, segs_single((int)n)));
+    dbg_extract(y, Ed, Ed, n);
+}
+
 int Model::voc_stage_rate(int stage) const
 {
     int r = 1;

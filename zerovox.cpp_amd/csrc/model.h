@@ -188,6 +188,8 @@ class Model
     void prof_clear();
 
     uint32_t E() const { return hp.emb_dim + hp.punct_emb_dim; }
+    // ZV_LAYER_ENC_LN (zv_debug_layer): one encoder LayerNorm alone on dbg_layer.x, outside the encoder's schedule
+    void debug_layernorm(int index, uint32_t n);
 
   private:
     // ---- weights ----

@@ -132,8 +132,11 @@ MEDIUM_H1 = Geometry(name="medium_h1", encoder_head=1)
 MEDIUM_H3 = Geometry(name="medium_h3", encoder_head=3)
 MEDIUM_H4 = Geometry(name="medium_h4", encoder_head=4)
 MEDIUM_H8 = Geometry(name="medium_h8", encoder_head=8)
+# MEDIUM with E = 1024 > 64 x LN_MAXE = 768: the encoder's LayerNorm rows take add_layernorm_kernel's path for wide rows; 4 heads
+# of dk = 256 keep both attention kernels legal
+MEDIUM_E1024 = Geometry(name="medium_e1024", emb_dim=1008, encoder_head=4)
 
-GEOMETRIES = {g.name: g for g in (MEDIUM, TINY, SMALL, MEDIUM8, MEDIUM_H1, MEDIUM_H3, MEDIUM_H4, MEDIUM_H8)}
+GEOMETRIES = {g.name: g for g in (MEDIUM, TINY, SMALL, MEDIUM8, MEDIUM_H1, MEDIUM_H3, MEDIUM_H4, MEDIUM_H8, MEDIUM_E1024)}
 
 
 def sinusoid_table(n_position: int, d_hid: int) -> np.ndarray:
