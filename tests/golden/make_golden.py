@@ -6,6 +6,7 @@ Run in the build container only (it needs /root/reference to have been compiled 
     python tests/golden/make_golden.py fresh    (only the fresh-seed fixtures)
     python tests/golden/make_golden.py heads    (only the encoder head-count fixture)
     python tests/golden/make_golden.py value_ranges    (only the value-range stage fixture)
+    python tests/golden/make_golden.py resblock_geometries    (only the residual-block tap-count fixture)
 Fixtures hold inputs' *recipes* (geometry, seeds — inputs are regenerated bit-identically by
 zerovox.cpp_amd/synth.py) and the reference's OUTPUTS: in full for the small geometries, as strided
 samples + SHA-256 of the full f32 buffer for the full-size configs of BASELINE.json.  ISA of the
@@ -375,6 +376,37 @@ def value_ranges_case(tmp="/tmp"):
     os.remove(path)
 
 
+RB_T = 24                   # frames of the residual-block geometry fixture
+RB_CHAIN = "medium_rb_c1c2"    # the geometry whose decoder -> vocoder chain is stored as well
+
+
+def resblock_geometries_case(tmp="/tmp"):
+    """The reference's vocoder on every residual-block geometry of synth.RESBLOCK_GEOMETRIES (tap counts other than 3 / 7 / 11, a
+    K that changes over one branch's dilations, convs1 and convs2 of one pair with different K), RB_T frames of
+    synth.vocoder_mel; and on RB_CHAIN the decoder -> vocoder chain (the reference's own mel fed to its vocoder).  SHA-256 +
+    strided samples of every output."""
+    out = dict(geometries=np.array(synth.RESBLOCK_GEOMETRIES), seed_w=SEED_W, T=RB_T, seed_mel=7, seed_hidden=11, seed_style=5,
+               stride=STRIDE, chain=RB_CHAIN)
+    for gname in synth.RESBLOCK_GEOMETRIES:
+        g = synth.GEOMETRIES[gname]
+        path = os.path.join(tmp, f"golden_{gname}.gguf")
+        synth.write_checkpoint(path, g, SEED_W)
+        _, tensors = gguf.read_gguf(path)
+        wav = zvoracle.run_reference(path, T=RB_T, voc=synth.vocoder_mel(g, tensors, 7, RB_T))["wav"]
+        out[gname + "/wav_sha256"] = sha(wav)
+        out[gname + "/wav_samples"] = wav[::STRIDE].copy()
+        print(f"{gname}: wav rms {float(np.sqrt(np.mean(wav.astype(np.float64) ** 2))):.4f}")
+        if gname == RB_CHAIN:
+            hid = synth.decoder_hidden(g, 11, RB_T)
+            style = synth.encoder_inputs(g, 5, 8)[2]
+            mel = zvoracle.run_reference(path, T=RB_T, dec=(hid, style))["mel"]
+            cw = zvoracle.run_reference(path, T=RB_T, voc=mel)["wav"]
+            out.update(chain_mel_sha256=sha(mel), chain_mel_samples=mel.reshape(-1)[::STRIDE].copy(), chain_wav_sha256=sha(cw),
+                       chain_wav_samples=cw[::STRIDE].copy())
+        os.remove(path)
+    np.savez_compressed(os.path.join(HERE, "resblock_geometries_T%d.npz" % RB_T), **out)
+
+
 if __name__ == "__main__":
     if not zvoracle.have_reference():
         sys.exit("oracle/_ref/zvref missing: run `make -C oracle ref` first")
@@ -383,6 +415,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["value_ranges"]:    # only the value-range stage fixture
         value_ranges_case()
+        sys.exit(0)
+    if sys.argv[1:] == ["resblock_geometries"]:     # only the residual-block tap-count fixture
+        resblock_geometries_case()
         sys.exit(0)
     if sys.argv[1:] == ["heads"]:           # only the encoder head-count fixture
         heads_cases()
@@ -401,3 +436,4 @@ if __name__ == "__main__":
     fresh_cases()
     heads_cases()
     value_ranges_case()
+    resblock_geometries_case()

@@ -379,3 +379,42 @@ def value_range_stage_inputs(g, tensors, seed=31):
     voc_regions = [(f"mel band n x {s:g}", slice((i * VR_BAND + lo) * g.hop_size, (i * VR_BAND + lo + VR_GATED) * g.hop_size))
                    for i, s in enumerate(VR_MEL_SCALES)]
     return hidden, style, mel, dec_regions, voc_regions
+
+
+# ---- vocoder receptive field (tests/test_gpu_vocoder_geometries.py, tests/test_boundary_cpu.py) ----------------------------
+
+def upsample_window(K, s):
+    """input rows relative to floor(t / s) that output row t of the reference's transposed conv reads (kernel K, stride s,
+    padding s / 2 + s % 2, output padding s % 2, src/hifigan.cpp:22-71): (lowest, highest)"""
+    p = s // 2 + s % 2
+    off = K - 1 - p
+    ds = [(k - off + r) // s for r in range(s) for k in range(K) if (k - off + r) % s == 0]
+    return min(ds), max(ds)
+
+
+def receptive_radius(g, tensors):
+    """exact receptive radius of one output sample in mel frames, from the checkpoint's tensors: the input rows each output sample
+    of one frame reads, walked back through output conv, 4 x (residual blocks, transposed conv) and input conv.  A stage's residual
+    blocks reach the widest branch's sum over its pairs of (K1 - 1) / 2 d + (K2 - 1) / 2 rows."""
+    k_in = tensors["_meldec.input_conv.w"].shape[2]
+    k_out = tensors["_meldec.output_conv.1.w"].shape[2]
+    stages = []
+    for i in range(len(g.upsample_kernels)):
+        K = tensors[f"_meldec.upsamples.{i}.1.w"].shape[2]
+        reach = 0
+        for j in range(len(g.resblock_kernels)):
+            n = i * len(g.resblock_kernels) + j
+            reach = max(reach, sum((tensors[f"_meldec.blocks.{n}.convs1.{d}.1.w"].shape[2] - 1) // 2 * dil +
+                                   (tensors[f"_meldec.blocks.{n}.convs2.{d}.1.w"].shape[2] - 1) // 2
+                                   for d, dil in enumerate(g.resblock_dilations)))
+        stages.append((K, K // 2, reach))
+    worst = 0
+    for t in range(g.hop_size):             # the samples of frame 0: every frame's samples read the same offsets
+        a, b = t - (k_out - 1) // 2, t + (k_out - 1) // 2
+        for K, s, reach in reversed(stages):
+            a, b = a - reach, b + reach
+            lo, hi = upsample_window(K, s)
+            a, b = a // s + lo, b // s + hi
+        a, b = a - (k_in - 1) // 2, b + (k_in - 1) // 2
+        worst = max(worst, -a, b)
+    return worst

@@ -192,3 +192,33 @@ def test_reference_style_call_site_compiles(tmp_path):
         synth.write_checkpoint(p, synth.TINY, 5)
         r = subprocess.run([exe, p, "8", str(tmp_path / "o.f32")], capture_output=True, text=True)
         assert r.returncode == 1 and "facade_callsite:" in r.stderr
+
+
+def test_receptive_radius_of_the_vocoder_geometries(ckpt):
+    """parity_helpers.receptive_radius (the bound tests/test_gpu_vocoder_geometries.py holds zv_vocoder_halo_frames to) on synth.MEDIUM:
+    3 / 7 / 11 everywhere, 60 rows per stage -> 20 frames; medium_rb_c1c2 (one convs2 of 13 taps) stays at 20; medium_rb_c2wide
+    (convs2 of 25 taps in the 11-tap branch) reaches 25 frames — beyond the 23 of a halo counted from the convs1 of dilation 0
+    alone, so that geometry fails a halo that leaves convs2 out"""
+    import math
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from parity_helpers import receptive_radius, upsample_window
+
+    def halo_from_convs1_d0(g, t):
+        """ceil(sum of per-layer reaches in frames) + 1, each stage's residual blocks counted as (K - 1) / 2 (sum d + 3) with K the
+        widest convs1 of dilation 0"""
+        frames, rate = (t["_meldec.input_conv.w"].shape[2] - 1) // 2, 1
+        for i, s in enumerate(g.upsample_scales):
+            lo, hi = upsample_window(t[f"_meldec.upsamples.{i}.1.w"].shape[2], s)
+            frames += (2 * max(-lo, hi) + 1) / rate
+            rate *= s
+            k = max(t[f"_meldec.blocks.{3 * i + j}.convs1.0.1.w"].shape[2] for j in range(3))
+            frames += (k - 1) // 2 * (sum(g.resblock_dilations) + 3) / rate
+        frames += (t["_meldec.output_conv.1.w"].shape[2] - 1) // 2 / rate
+        return math.ceil(frames) + 1
+
+    want = {"medium": 20, "medium_rb_c1c2": 20, "medium_rb_c2wide": 25}
+    for name, r in want.items():
+        _, g, tensors = ckpt(name)
+        assert receptive_radius(g, tensors) == r, name
+        assert halo_from_convs1_d0(g, tensors) == 23, name

@@ -278,3 +278,32 @@ def test_oracle_layernorm_alone_on_value_range_rows(ckpt):
         c = dict(reg)["constant rows"]
         assert np.array_equal(y[c], np.broadcast_to(b.astype(np.float32), y[c].shape))
         assert np.max(np.abs(y - want)) <= 1e-5 * np.max(np.abs(want))
+
+
+def test_oracle_resblock_geometries(ckpt):
+    """the oracle on checkpoints whose residual-block convs have other tap counts (synth.RESBLOCK_GEOMETRIES: 3 / 5 / 7, 15 / 9 / 1,
+    a branch whose last dilation pair is narrower, convs1 and convs2 of one pair with different K) against the reference's
+    vocoder outputs (tests/golden/resblock_geometries_T24.npz) bit for bit, plus one decoder -> vocoder chain; and live against
+    oracle/_ref where it is present"""
+    from zerovox_cpp_amd import synth
+    from oracle import zvoracle
+    z = np.load(os.path.join(GOLD, "resblock_geometries_T24.npz"))
+    T, s = int(z["T"]), int(z["stride"])
+    assert tuple(str(n) for n in z["geometries"]) == synth.RESBLOCK_GEOMETRIES
+    for gname in synth.RESBLOCK_GEOMETRIES:
+        path, g, tensors = ckpt(gname, int(z["seed_w"]))
+        orc = zvoracle.Oracle(tensors)
+        mel_in = synth.vocoder_mel(g, tensors, int(z["seed_mel"]), T)
+        wav = orc.vocoder(mel_in)
+        assert np.array_equal(wav[::s], z[gname + "/wav_samples"]) and sha(wav) == str(z[gname + "/wav_sha256"]), gname
+        if zvoracle.have_reference():
+            assert sha(zvoracle.run_reference(path, T=T, voc=mel_in)["wav"]) == str(z[gname + "/wav_sha256"]), gname
+        if gname == str(z["chain"]):
+            hid = synth.decoder_hidden(g, int(z["seed_hidden"]), T)
+            style = synth.encoder_inputs(g, int(z["seed_style"]), 8)[2]
+            mel = orc.decoder(hid, style)
+            assert np.array_equal(mel.reshape(-1)[::s], z["chain_mel_samples"]) and sha(mel) == str(z["chain_mel_sha256"])
+            cw = orc.vocoder(mel)
+            assert np.array_equal(cw[::s], z["chain_wav_samples"]) and sha(cw) == str(z["chain_wav_sha256"])
+            if zvoracle.have_reference():
+                assert sha(zvoracle.run_reference(path, T=T, dec=(hid, style))["mel"]) == str(z["chain_mel_sha256"])

@@ -206,6 +206,8 @@ Model::Model(const std::string &path, int dev) : device(dev)
     voc_.mean = upload_vec(g, "hifigan.mean", M);
     voc_.scale = upload_vec(g, "hifigan.scale", M, 0, 1.f);
     voc_.in_conv = load_conv(g, "_meldec.input_conv.w", "_meldec.input_conv.b", M);
+    // the reference pads the input and output convs for kernel_size = 7 whatever the file holds (src/hifigan.cpp:261,338)
+    if (voc_.in_conv.K != 7) fail(ZV_ERR_SHAPE, "tensor _meldec.input_conv.w: kernel size %d, the reference pads for 7", voc_.in_conv.K);
     int C = voc_.in_conv.Cout;
     hp.voc_channels = C;
     int n_up = 0;
@@ -216,8 +218,11 @@ Model::Model(const std::string &path, int dev) : device(dev)
         n_up++;
     }
     if (n_up == 0) fail(ZV_ERR_MISSING, "tensor '_meldec.upsamples.0.1.w' not found");
-    // the stride is not stored in the file: the reference hard-codes {5,5,4,3} (src/zerovox.cpp:129);
-    // every HiFi-GAN config has kernel = 2 * stride, which is what we derive and check against hop_size.
+    // the stride is not stored in the file: the reference hard-codes 4 stages of {5,5,4,3} (src/zerovox.cpp:127-129);
+    // every HiFi-GAN config has kernel = 2 * stride, which is what we derive, and a file whose strides differ is refused.
+    static const int REF_SCALES[4] = {5, 5, 4, 3};
+    if (n_up != 4) fail(ZV_ERR_SHAPE, "tensor _meldec.upsamples.%d.1.w: %s; the reference runs 4 upsample stages, the file has %d", std::min(n_up, 4),
+                          n_up < 4 ? "missing" : "unexpected", n_up);
     int hop = 1;
     voc_.n_up = n_up;
     hp.voc_num_upsamples = n_up;
@@ -238,6 +243,7 @@ Model::Model(const std::string &path, int dev) : device(dev)
         const int K = (int)g.get(nm).ne[0];
         if (K % 2) fail(ZV_ERR_SHAPE, "tensor %s: odd transposed-conv kernel %d", nm, K);
         const int s = K / 2;
+        if (s != REF_SCALES[i]) fail(ZV_ERR_SHAPE, "tensor %s: kernel %d gives stride %d, the reference uses %d at stage %d", nm, K, s, REF_SCALES[i], i);
         voc_.scales[i] = s;
         hp.voc_upsample_scales[i] = s;
         hop *= s;
@@ -297,6 +303,7 @@ Model::Model(const std::string &path, int dev) : device(dev)
         if (b.type != GGML_F32 || b.nelements() != 1) fail(ZV_ERR_SHAPE, "_meldec.output_conv.1.b: expected f32 [1]");
         if ((hp.voc_channels >> n_up) != (uint32_t)C) fail(ZV_ERR_SHAPE, "vocoder channels %u do not halve down to %d over %d stages", hp.voc_channels, C, n_up);
         voc_.out_K = (int)w.ne[0];
+        if (voc_.out_K != 7) fail(ZV_ERR_SHAPE, "tensor _meldec.output_conv.1.w: kernel size %d, the reference pads for 7", voc_.out_K);
         voc_.out_C = C;
         const int Cp = round_up(C, 16);
         std::vector<uint16_t> h((size_t)voc_.out_K * Cp, 0);
@@ -533,16 +540,24 @@ uint32_t Model::vocoder_halo_frames() const
 {
     double frames = (voc_.in_conv.K - 1) / 2;            // input conv, at the frame rate
     double rate = 1.0;                                   // samples per frame at the current stage
-    int sumd = 0;
-    for (int d = 0; d < voc_.n_dil; d++) sumd += voc_.dil[d];
     for (int i = 0; i < voc_.n_up; i++)
     {
         // polyphase transposed conv: ups[i].K taps at the INPUT rate of the stage
         frames += (double)voc_.ups[i].K / rate;
         rate *= voc_.scales[i];
-        int kmax = 1;
-        for (int j = 0; j < voc_.n_rb; j++) kmax = std::max(kmax, voc_.pairs[((size_t)i * voc_.n_rb + j) * voc_.n_dil].c1.K);
-        frames += (double)((kmax - 1) / 2) * (sumd + voc_.n_dil) / rate;      // dilated conv + plain conv per dilation
+        // residual blocks: per branch, every pair's dilated conv + plain conv (each conv's own K); the widest branch
+        int reach = 0;
+        for (int j = 0; j < voc_.n_rb; j++)
+        {
+            int r = 0;
+            for (int d = 0; d < voc_.n_dil; d++)
+            {
+                const ResPair &rp = voc_.pairs[((size_t)i * voc_.n_rb + j) * voc_.n_dil + d];
+                r += (rp.c1.K - 1) / 2 * voc_.dil[d] + (rp.c2.K - 1) / 2;
+            }
+            reach = std::max(reach, r);
+        }
+        frames += (double)reach / rate;
     }
     frames += (double)((voc_.out_K - 1) / 2) / rate;
     return (uint32_t)std::ceil(frames) + 1;
@@ -984,13 +999,16 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         // V2: the 3 MRF branches run side by side (one job each).  Fused path: one launch per dilation
         // (conv -> lrelu -> conv -> + residual, xt kept in LDS), y ping-pongs between two buffers because a
         // workgroup's halo rows belong to its neighbours' output tiles.
-        const ResPair &rp0 = voc_.pairs[((size_t)i * voc_.n_rb) * voc_.n_dil];
+        // every pair of the stage must have fused weights (one K for both convs, pair_supported): a stage runs fused or not as a
+        // whole, so the MRF sum keeps one association whichever kernels a checkpoint's tap counts allow
+        bool all_fusable = true;
+        for (int q = 0; q < voc_.n_rb * voc_.n_dil; q++) all_fusable = all_fusable && voc_.pairs[(size_t)i * voc_.n_rb * voc_.n_dil + q].p1;
         // 256-channel stage: the fused kernel needs all 256 xt channels in one workgroup, which leaves few workgroups per
         // branch for a short utterance — two unfused launches (480 workgroups at 512 frames) win below about a round
         // of fused ones (round 4, on the 16 x 16 x 32 kernel, whole vocoder under graph replay: 128 frames 0.276 unfused /
         // 0.291 fused ms, 256: 0.320 / 0.333, 512: 0.470 / 0.465, 1 024: 0.852 / 0.814)
         const bool enough_rows = Cp != 256 || force_fuse256_ || (Lbatch / 54) * 3 >= (long)n_cu;
-        const bool fused = !no_fuse_ && rp0.p1 != nullptr && enough_rows;
+        const bool fused = !no_fuse_ && all_fusable && enough_rows;
         const float *ycur[3] = {ub, ub, ub};
         const float *merged_sum = nullptr;
         group_begin();
@@ -999,10 +1017,14 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         bool whole_block = fused && !no_triple_ && voc_.n_dil <= TRIPLE_MAX_DIL;
         for (int jb = 0; jb < 3 && whole_block; jb++)
         {
+            // one K per job (TripleJob::K): every dilation pair of the branch must have it
             const ResPair &r0 = voc_.pairs[((size_t)i * voc_.n_rb + jb) * voc_.n_dil];
             whole_block = triple_supported(Cp, r0.c1.K, voc_.dil, voc_.n_dil);
             for (int d = 0; d < voc_.n_dil && whole_block; d++)
-                whole_block = voc_.pairs[((size_t)i * voc_.n_rb + jb) * voc_.n_dil + d].p1 != nullptr;
+            {
+                const ResPair &rp = voc_.pairs[((size_t)i * voc_.n_rb + jb) * voc_.n_dil + d];
+                whole_block = rp.p1 != nullptr && rp.c1.K == r0.c1.K && rp.c2.K == r0.c1.K;
+            }
         }
         if (whole_block)
         {
@@ -1049,7 +1071,9 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
                 for (int jb = 0; jb < 3; jb++)
                 {
                     const ResPair *rp = &voc_.pairs[((size_t)i * voc_.n_rb + jb) * voc_.n_dil];
-                    if (rp[0].c1.K > kmax64 || !rp[0].r1 || !rp[0].r2 || !rp[1].r1 || !rp[1].r2 || !block64_supported(Cp, rp[0].c1.K, voc_.dil, 2)) continue;
+                    // one K for the two pairs it runs (TripleJob::K)
+                    const bool one_k = rp[1].c1.K == rp[0].c1.K && rp[0].c2.K == rp[0].c1.K && rp[1].c2.K == rp[0].c1.K;
+                    if (!one_k || rp[0].c1.K > kmax64 || !rp[0].r1 || !rp[0].r2 || !rp[1].r1 || !rp[1].r2 || !block64_supported(Cp, rp[0].c1.K, voc_.dil, 2)) continue;
                     TripleJob &t = tj[nj++];
                     memset(&t, 0, sizeof(t));
                     t.y = ub;

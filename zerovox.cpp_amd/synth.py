@@ -85,6 +85,16 @@ class Geometry:
     upsample_kernels: Tuple[int, ...] = (10, 10, 8, 6)
     resblock_kernels: Tuple[int, ...] = (3, 7, 11)
     resblock_dilations: Tuple[int, ...] = (1, 3, 5)        # hard-coded, src/zerovox.cpp:132
+    # per-conv tap counts that differ from resblock_kernels[branch]: (branch, dilation, conv (1 or 2), K), in every stage
+    # (the file stores one tensor per conv, and the reference reads each one's K from its shape, src/hifigan.cpp:125,164)
+    resblock_overrides: Tuple[Tuple[int, int, int, int], ...] = ()
+
+    def resblock_k(self, branch: int, dilation: int, conv: int) -> int:
+        k = self.resblock_kernels[branch]
+        for b, d, c, kk in self.resblock_overrides:
+            if (b, d, c) == (branch, dilation, conv):
+                k = kk
+        return k
 
     @property
     def E(self) -> int:
@@ -136,7 +146,32 @@ MEDIUM_H8 = Geometry(name="medium_h8", encoder_head=8)
 # of dk = 256 keep both attention kernels legal
 MEDIUM_E1024 = Geometry(name="medium_e1024", emb_dim=1008, encoder_head=4)
 
-GEOMETRIES = {g.name: g for g in (MEDIUM, TINY, SMALL, MEDIUM8, MEDIUM_H1, MEDIUM_H3, MEDIUM_H4, MEDIUM_H8, MEDIUM_E1024)}
+# MEDIUM with other residual-block tap counts (every conv's K is a free shape of the checkpoint format).  Stages of 256, 128, 64 and
+# 32 channels reach every fused kernel:
+#  * rb357: K = 5 is not pair-fusable at 32 channels (an odd number of 4-step MFMA bodies) while 3 and 7 are; at 64 channels
+#    K = 5 runs resblock_pair64 and resblock_block64;
+#  * rb_wide: 15 taps (no whole-block kernel at 32 channels: the halo leaves too few rows; 256- and 128-channel tiles with 14 halo
+#    rows), 9 (fusable at 64 channels and up) and 1 (a 'same' 1-tap conv, fusable at 128 and 256 channels only);
+#  * rb_dilk: the 11-tap branch's last dilation pair has 7 taps (a branch whose K changes over its dilations);
+#  * rb_c1c2: convs1 and convs2 of one pair differ (7 / 3 in branch 1, 11 / 13 in branch 2, dilation 0), a convs2 wider than
+#    every convs1 of the stage;
+#  * rb_c2wide: every convs2 of the 11-tap branch has 25 taps — a receptive radius of 25 frames, beyond the 23 of a halo that
+#    counts convs1 of dilation 0 alone (such pairs are never fused: convs1 and convs2 differ)
+MEDIUM_RB357 = Geometry(name="medium_rb357", resblock_kernels=(3, 5, 7))
+MEDIUM_RB_WIDE = Geometry(name="medium_rb_wide", resblock_kernels=(15, 9, 1))
+MEDIUM_RB_DILK = Geometry(name="medium_rb_dilk", resblock_overrides=((2, 2, 1, 7), (2, 2, 2, 7)))
+MEDIUM_RB_C1C2 = Geometry(name="medium_rb_c1c2", resblock_overrides=((1, 0, 2, 3), (2, 0, 2, 13)))
+MEDIUM_RB_C2WIDE = Geometry(name="medium_rb_c2wide", resblock_overrides=((2, 0, 2, 25), (2, 1, 2, 25), (2, 2, 2, 25)))
+RESBLOCK_GEOMETRIES = ("medium_rb357", "medium_rb_wide", "medium_rb_dilk", "medium_rb_c1c2", "medium_rb_c2wide")
+
+# checkpoints the loader refuses (the reference hard-codes what these change, src/zerovox.cpp:127-129, src/hifigan.cpp:261,338):
+# upsample strides (4, 5, 5, 3) — still a hop of 300 — and 5-tap input / output convs
+MEDIUM_UP4553 = Geometry(name="medium_up4553", upsample_scales=(4, 5, 5, 3), upsample_kernels=(8, 10, 10, 6))
+MEDIUM_VOCK5 = Geometry(name="medium_vock5", voc_kernel_size=5)
+
+GEOMETRIES = {g.name: g for g in (MEDIUM, TINY, SMALL, MEDIUM8, MEDIUM_H1, MEDIUM_H3, MEDIUM_H4, MEDIUM_H8, MEDIUM_E1024,
+                                  MEDIUM_RB357, MEDIUM_RB_WIDE, MEDIUM_RB_DILK, MEDIUM_RB_C1C2, MEDIUM_RB_C2WIDE, MEDIUM_UP4553,
+                                  MEDIUM_VOCK5)}
 
 
 def sinusoid_table(n_position: int, d_hid: int) -> np.ndarray:
@@ -254,12 +289,12 @@ def make_tensors(g: Geometry, seed: int) -> List[Tuple[str, np.ndarray]]:
         amp_gain = np.sqrt(s)
         conv_w(f"_meldec.upsamples.{i}.1.w", co, ci, k, gain=1.0 * amp_gain)
         vec(f"_meldec.upsamples.{i}.1.b", co)
-        for j, rk in enumerate(g.resblock_kernels):
+        for j in range(len(g.resblock_kernels)):
             n = i * len(g.resblock_kernels) + j
             for d in range(len(g.resblock_dilations)):
-                conv_w(f"_meldec.blocks.{n}.convs1.{d}.1.w", co, co, rk, gain=1.0)
+                conv_w(f"_meldec.blocks.{n}.convs1.{d}.1.w", co, co, g.resblock_k(j, d, 1), gain=1.0)
                 vec(f"_meldec.blocks.{n}.convs1.{d}.1.b", co)
-                conv_w(f"_meldec.blocks.{n}.convs2.{d}.1.w", co, co, rk, gain=0.2)
+                conv_w(f"_meldec.blocks.{n}.convs2.{d}.1.w", co, co, g.resblock_k(j, d, 2), gain=0.2)
                 vec(f"_meldec.blocks.{n}.convs2.{d}.1.b", co)
     cl = C >> len(g.upsample_scales)
     conv_w("_meldec.output_conv.1.w", 1, cl, g.voc_kernel_size, gain=0.5)
