@@ -83,6 +83,27 @@ zv_status zv_model_get_hparams(const zv_model *m, zv_hparams *out);
  * the arena also grows on demand, outside any timed / captured region) */
 zv_status zv_model_reserve(zv_model *m, uint32_t max_phonemes, uint32_t max_frames);
 
+/* ---- prosody controls (speaking rate, pitch, energy), one set per utterance ----------------------------------------
+ * The variance adaptor's three decisions, steered per utterance.  All arithmetic is f32, every step rounded separately (the
+ * library builds with -ffp-contract=off):
+ *   duration: dur = (float)(exp((double)logdur) - 1.0); dur = dur * duration_scale;  d = (int)((double)dur + 0.5) clamped to
+ *             [0, T]; the cumulative durations and n_frames follow from the scaled d
+ *   pitch:    p = pred; p = p * pitch_scale; p = p + pitch_shift; p = p * (float)(nbins - 1);  bucket = (int)((double)p + 0.5)
+ *             (truncating) clamped to [0, nbins - 1]; the pitch embedding added to the features is the one at this bucket, so
+ *             the energy predictor sees it (reference src/fs2encoder.cpp:565-572)
+ *   energy:   the same steps with energy_scale / energy_shift
+ * Taps: logdur, pitch and energy stay the RAW predictions; pitch_bucket, energy_bucket, features, hidden and n_frames are the
+ * controlled values.  The identity {1, 1, 0, 1, 0} gives exactly the bits of the uncontrolled entry points (x * 1.0f and
+ * x + 0.0f are exact), and so does prosody == NULL.
+ * Validation: every field finite and 0 < duration_scale <= 16, else ZV_ERR_ARG before any work is enqueued (the message names
+ * the utterance index and the field). */
+typedef struct
+{
+    float duration_scale;               /* > 0; 1 = as predicted, 2 = every phoneme twice as long */
+    float pitch_scale, pitch_shift;     /* pitch prediction p -> p * pitch_scale + pitch_shift before bucketing */
+    float energy_scale, energy_shift;   /* the same for energy */
+} zv_prosody;                           /* identity: {1, 1, 0, 1, 0} */
+
 /* ---- the hot path: host buffers in / out, synchronous (same protocol as the reference) ---- */
 /* ids[n], puncts[n] i32; style[E] f32; hidden[T*E] f32 frame-major, zero-padded tail; returns the
  * regulator's frame count in *n_frames (may be NULL).  Optional taps (NULL to skip): logdur[n],
@@ -96,6 +117,10 @@ zv_status zv_encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts,
                          uint32_t n, uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames,
                          float *features, float *logdur, float *pitch, float *energy, int32_t *pitch_bucket,
                          int32_t *energy_bucket);
+/* zv_encode_taps with prosody controls (NULL = identity: the bits of zv_encode_taps) */
+zv_status zv_encode_taps_prosody(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
+                                 uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
+                                 float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody);
 /* hidden[T*E], style[E] -> mel[T*num_mels] frame-major */
 zv_status zv_decode(zv_model *m, const float *hidden, const float *style, uint32_t T, float *mel);
 /* mel[T*num_mels] -> wav[T*hop_size] */
@@ -114,6 +139,9 @@ uint32_t  zv_vocoder_halo_frames(zv_model *m);
 /* encoder -> decoder -> vocoder with every intermediate kept in HBM; wav[T*hop_size] */
 zv_status zv_synthesize(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style,
                         uint32_t n, uint32_t T, float *wav, uint32_t *n_frames);
+/* zv_synthesize with prosody controls (NULL = identity: the bits of zv_synthesize) */
+zv_status zv_synthesize_prosody(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                                float *wav, uint32_t *n_frames, const zv_prosody *prosody);
 
 /* n_utt independent utterances, each with its own (n_phonemes[u], T[u]): bit for bit the result of n_utt zv_synthesize
  * calls (no batch padding: padding would change the numbers, SURVEY Appx C-H2).  Up to 64 utterances / 64 Ki frames go
@@ -127,6 +155,12 @@ zv_status zv_synthesize(zv_model *m, const int32_t *ids, const int32_t *puncts, 
 zv_status zv_synthesize_batch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
                               const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
                               float *const *wav, uint32_t *n_frames);
+/* the same with prosody controls: prosody[n_utt], one set per utterance (NULL = identity for all: the bits of
+ * zv_synthesize_batch).  The controls travel in the batch's device input block with the styles, so a replayed graph picks
+ * up new values without being captured again; utterance u gives the bits of zv_synthesize_prosody(..., &prosody[u]). */
+zv_status zv_synthesize_batch_prosody(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                      const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                      float *const *wav, uint32_t *n_frames, const zv_prosody *prosody);
 
 /* The two halves of zv_synthesize_batch for a serving loop that keeps a batch in flight per lane (additive):
  * _begin builds the input block, enqueues the upload, the kernels and the waveform downloads of ONE launch group (at most
@@ -141,6 +175,10 @@ zv_status zv_synthesize_batch(zv_model *m, uint32_t n_utt, const int32_t *const 
 zv_status zv_synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
                                     const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
                                     const uint32_t *T, float *const *wav, uint32_t *n_frames);
+/* _begin with prosody controls, prosody[n_utt] (NULL = identity); the array is read before the call returns */
+zv_status zv_synthesize_batch_begin_prosody(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                            const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                            const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody);
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel

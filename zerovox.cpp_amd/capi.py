@@ -20,7 +20,8 @@ SYMBOLS = [
     "zv_encode", "zv_encode_taps", "zv_decode", "zv_vocode", "zv_synthesize", "zv_synthesize_batch", "zv_synthesize_batch_begin", "zv_synthesize_batch_end", "zv_device_alloc", "zv_device_free",
     "zv_memcpy_h2d", "zv_memcpy_d2h", "zv_vocode_device", "zv_vocode_stream", "zv_vocoder_halo_frames", "zv_decode_device", "zv_synchronize", "zv_set_graph_mode",
     "zv_profile_begin", "zv_profile_end", "zv_write_wav", "zv_gguf_inspect", "zv_max_frames", "zv_demo_utterance", "zv_debug_layer", "zv_debug_set",
-    "zv_debug_get", "zv_batch_timeline",
+    "zv_debug_get", "zv_batch_timeline", "zv_encode_taps_prosody", "zv_synthesize_prosody", "zv_synthesize_batch_prosody",
+    "zv_synthesize_batch_begin_prosody",
 ]
 
 
@@ -36,6 +37,28 @@ class HParams(C.Structure):
                 ("audio_sampling_rate", C.c_uint32), ("audio_num_mels", C.c_uint32), ("audio_hop_size", C.c_uint32),
                 ("voc_channels", C.c_uint32), ("voc_num_upsamples", C.c_uint32), ("voc_upsample_scales", C.c_uint32 * 8),
                 ("voc_num_resblocks", C.c_uint32), ("voc_resblock_kernels", C.c_uint32 * 8)]
+
+
+class Prosody(C.Structure):
+    """zv_prosody of include/zerovox_amd.h: per-utterance speaking rate, pitch and energy controls (identity: the defaults)"""
+    _fields_ = [("duration_scale", C.c_float), ("pitch_scale", C.c_float), ("pitch_shift", C.c_float),
+                ("energy_scale", C.c_float), ("energy_shift", C.c_float)]
+
+    def __init__(self, duration_scale=1.0, pitch_scale=1.0, pitch_shift=0.0, energy_scale=1.0, energy_shift=0.0):
+        super().__init__(duration_scale, pitch_scale, pitch_shift, energy_scale, energy_shift)
+
+    def __repr__(self):
+        return (f"Prosody(duration_scale={self.duration_scale}, pitch_scale={self.pitch_scale}, pitch_shift={self.pitch_shift}, "
+                f"energy_scale={self.energy_scale}, energy_shift={self.energy_shift})")
+
+
+def _prosody(p) -> Optional[Prosody]:
+    """None, a Prosody, a dict of its fields or a 5-sequence -> Prosody / None"""
+    if p is None or isinstance(p, Prosody):
+        return p
+    if isinstance(p, dict):
+        return Prosody(**p)
+    return Prosody(*p)
 
 
 class KernelStat(C.Structure):
@@ -86,6 +109,11 @@ def load_library(path: Optional[str] = None):
     lib.zv_synthesize_batch_begin.argtypes = [vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u32), C.POINTER(u32),
                                               C.POINTER(vp), C.POINTER(u32)]
     lib.zv_synthesize_batch_end.argtypes = [vp, u32]
+    pp = C.POINTER(Prosody)
+    lib.zv_encode_taps_prosody.argtypes = lib.zv_encode_taps.argtypes + [pp]
+    lib.zv_synthesize_prosody.argtypes = lib.zv_synthesize.argtypes + [pp]
+    lib.zv_synthesize_batch_prosody.argtypes = lib.zv_synthesize_batch.argtypes + [pp]
+    lib.zv_synthesize_batch_begin_prosody.argtypes = lib.zv_synthesize_batch_begin.argtypes + [pp]
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -256,8 +284,9 @@ class Model:
     def max_frames(self) -> int:
         return int(self.lib.zv_max_frames(self.h))
 
-    def encode(self, ids, puncts, style, T: int, num_phonemes: Optional[int] = None) -> dict:
-        """num_phonemes < len(ids): all ids are encoded, the length regulator walks the first num_phonemes (FS2Encoder::eval)"""
+    def encode(self, ids, puncts, style, T: int, num_phonemes: Optional[int] = None, prosody=None) -> dict:
+        """num_phonemes < len(ids): all ids are encoded, the length regulator walks the first num_phonemes (FS2Encoder::eval).
+        prosody (Prosody, dict or 5-sequence): zv_encode_taps_prosody; None: zv_encode_taps"""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
@@ -266,20 +295,30 @@ class Model:
                    logdur=np.empty(N, np.float32), pitch=np.empty(N, np.float32), energy=np.empty(N, np.float32),
                    pitch_bucket=np.empty(N, np.int32), energy_bucket=np.empty(N, np.int32))
         nf = C.c_uint32(0)
-        self._chk(self.lib.zv_encode_taps(self.h, _ptr(ids), _ptr(puncts), _ptr(style), N,
-                                          N if num_phonemes is None else num_phonemes, T, _ptr(out["hidden"]),
-                                          C.byref(nf), _ptr(out["features"]), _ptr(out["logdur"]), _ptr(out["pitch"]),
-                                          _ptr(out["energy"]), _ptr(out["pitch_bucket"]), _ptr(out["energy_bucket"])))
+        args = (self.h, _ptr(ids), _ptr(puncts), _ptr(style), N, N if num_phonemes is None else num_phonemes, T, _ptr(out["hidden"]),
+                C.byref(nf), _ptr(out["features"]), _ptr(out["logdur"]), _ptr(out["pitch"]), _ptr(out["energy"]),
+                _ptr(out["pitch_bucket"]), _ptr(out["energy_bucket"]))
+        pr = _prosody(prosody)
+        if pr is None:
+            self._chk(self.lib.zv_encode_taps(*args))
+        else:
+            self._chk(self.lib.zv_encode_taps_prosody(*args, C.byref(pr)))
         out["n_frames"] = int(nf.value)
         return out
 
-    def synthesize(self, ids, puncts, style, T: int):
+    def synthesize(self, ids, puncts, style, T: int, prosody=None):
+        """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize"""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
         wav = np.empty(T * self.hp.audio_hop_size, np.float32)
         nf = C.c_uint32(0)
-        self._chk(self.lib.zv_synthesize(self.h, _ptr(ids), _ptr(puncts), _ptr(style), len(ids), T, _ptr(wav), C.byref(nf)))
+        args = (self.h, _ptr(ids), _ptr(puncts), _ptr(style), len(ids), T, _ptr(wav), C.byref(nf))
+        pr = _prosody(prosody)
+        if pr is None:
+            self._chk(self.lib.zv_synthesize(*args))
+        else:
+            self._chk(self.lib.zv_synthesize_prosody(*args, C.byref(pr)))
         return wav, int(nf.value)
 
     def prepare_batch(self, utterances) -> "BatchCall":
@@ -288,7 +327,8 @@ class Model:
         return BatchCall(self, utterances)
 
     def synthesize_batch(self, utterances):
-        """utterances: list of (ids, puncts, style, T) -> list of (wav, n_frames); each utterance keeps its own (N, T)"""
+        """utterances: list of (ids, puncts, style, T[, prosody]) -> list of (wav, n_frames); each utterance keeps its own (N, T)
+        and, with a fifth element, its own prosody controls (None: identity)"""
         call = BatchCall(self, utterances)
         call.run()
         return call.results()
@@ -344,6 +384,10 @@ class Model:
 
 
 class BatchCall:
+    """utterances: (ids, puncts, style, T) or (ids, puncts, style, T, prosody) tuples.  When any utterance carries a prosody
+    (the others get the identity) the _prosody entry points are called with the array .prosody, which set_prosody() rewrites
+    in place: the next run() / begin() uses the new values with the same buffers (a captured graph replays with them)."""
+
     def __init__(self, model: Model, utterances):
         self.model = model
         n = self.n = len(utterances)
@@ -351,7 +395,11 @@ class BatchCall:
         P = C.c_void_p * n
         self.ids_p, self.pun_p, self.sty_p, self.wav_p = P(), P(), P(), P()
         self.Ns, self.Ts, self.nf = (C.c_uint32 * n)(), (C.c_uint32 * n)(), (C.c_uint32 * n)()
-        for i, (ids, puncts, style, T) in enumerate(utterances):
+        prs = [_prosody(u[4]) if len(u) > 4 else None for u in utterances]
+        self.prosody = None
+        if any(p is not None for p in prs):
+            self.prosody = (Prosody * n)(*[p if p is not None else Prosody() for p in prs])
+        for i, (ids, puncts, style, T) in enumerate(u[:4] for u in utterances):
             a = np.ascontiguousarray(ids, dtype=np.int32)
             b = np.ascontiguousarray(puncts, dtype=np.int32)
             c = np.ascontiguousarray(style, dtype=np.float32)
@@ -361,14 +409,28 @@ class BatchCall:
             self.ids_p[i], self.pun_p[i], self.sty_p[i], self.wav_p[i] = a.ctypes.data, b.ctypes.data, c.ctypes.data, w.ctypes.data
             self.Ns[i], self.Ts[i] = len(a), T
 
+    def set_prosody(self, i: int, prosody):
+        """utterance i's controls for the following run() / begin() (the call must have been built with controls)"""
+        if self.prosody is None:
+            raise ValueError("this BatchCall was built without prosody controls")
+        self.prosody[i] = _prosody(prosody) or Prosody()
+
     def run(self):
         m = self.model
-        m._chk(m.lib.zv_synthesize_batch(m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf))
+        args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
+        if self.prosody is None:
+            m._chk(m.lib.zv_synthesize_batch(*args))
+        else:
+            m._chk(m.lib.zv_synthesize_batch_prosody(*args, self.prosody))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
-        m._chk(m.lib.zv_synthesize_batch_begin(m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf))
+        args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
+        if self.prosody is None:
+            m._chk(m.lib.zv_synthesize_batch_begin(*args))
+        else:
+            m._chk(m.lib.zv_synthesize_batch_begin_prosody(*args, self.prosody))
 
     def end(self, lane: int):
         m = self.model

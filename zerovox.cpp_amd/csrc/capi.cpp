@@ -1,5 +1,6 @@
 // capi.cpp — the extern "C" boundary declared in include/zerovox_amd.h.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <string>
@@ -127,42 +128,99 @@ static void check_T(const Model &M, uint32_t T)
                  T, M.max_frames_per_utterance());
 }
 
+// Prosody controls (zv_prosody) -> the kernels' layout, f32 [n_utt][zv::CTL_STRIDE] (kernels.h CTL_*).  Every set is checked
+// before the caller enqueues anything: ZV_ERR_ARG names the utterance and the field.
+static void check_prosody(const zv_prosody *p, uint32_t n_utt)
+{
+    if (!p) return;
+    static const char *const names[5] = {"duration_scale", "pitch_scale", "pitch_shift", "energy_scale", "energy_shift"};
+    for (uint32_t u = 0; u < n_utt; u++)
+    {
+        const float f[5] = {p[u].duration_scale, p[u].pitch_scale, p[u].pitch_shift, p[u].energy_scale, p[u].energy_shift};
+        for (int k = 0; k < 5; k++)
+            if (!std::isfinite(f[k])) zv::fail(ZV_ERR_ARG, "utterance %u: prosody %s = %g is not finite", u, names[k], (double)f[k]);
+        if (!(f[0] > 0.0f && f[0] <= 16.0f))
+            zv::fail(ZV_ERR_ARG, "utterance %u: prosody duration_scale = %g is outside (0, 16]", u, (double)f[0]);
+    }
+}
+
+static void prosody_rows(const zv_prosody *p, uint32_t n_utt, float *rows)
+{
+    memset(rows, 0, (size_t)n_utt * zv::CTL_STRIDE * sizeof(float));
+    for (uint32_t u = 0; u < n_utt; u++)
+    {
+        float *r = rows + (size_t)u * zv::CTL_STRIDE;
+        r[zv::CTL_DURATION] = p[u].duration_scale;
+        r[zv::CTL_PITCH] = p[u].pitch_scale;
+        r[zv::CTL_PITCH + 1] = p[u].pitch_shift;
+        r[zv::CTL_ENERGY] = p[u].energy_scale;
+        r[zv::CTL_ENERGY + 1] = p[u].energy_shift;
+    }
+}
+
+static void encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t num_phonemes,
+                        uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur, float *pitch, float *energy,
+                        int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody, const char *fn)
+{
+    if (!(m && ids && puncts && style && hidden)) zv::fail(ZV_ERR_ARG, "%s: null argument", fn);
+    if (!(n > 0)) zv::fail(ZV_ERR_ARG, "%s: n must be > 0", fn);
+    if (!(num_phonemes <= n)) zv::fail(ZV_ERR_ARG, "%s: num_phonemes exceeds n", fn);
+    check_prosody(prosody, 1);
+    Model &M = *m->m;
+    use_lane0(m);
+    check_T(M, T);
+    check_ids(M, ids, puncts, n);
+    const size_t E = M.E();
+    const size_t b_ids = (size_t)n * 4, b_sty = E * 4, b_hid = (size_t)T * E * 4;
+    char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + 1024 + (prosody ? 256 : 0));
+    int32_t *d_nf = (int32_t *)io;
+    io += 256;
+    int32_t *d_ids = (int32_t *)io, *d_pun = (int32_t *)(io + b_ids);
+    float *d_sty = (float *)(io + 2 * b_ids + 256 - (2 * b_ids) % 256);
+    float *d_hid = (float *)((char *)d_sty + ((b_sty + 255) & ~(size_t)255));
+    ZV_HIP(hipMemcpyAsync(d_ids, ids, b_ids, hipMemcpyHostToDevice, M.stream));
+    ZV_HIP(hipMemcpyAsync(d_pun, puncts, b_ids, hipMemcpyHostToDevice, M.stream));
+    ZV_HIP(hipMemcpyAsync(d_sty, style, b_sty, hipMemcpyHostToDevice, M.stream));
+    zv::Batch bt = zv::Batch::single(n, T, num_phonemes);
+    float ctl[zv::CTL_STRIDE];                   // lives until the M.sync() below
+    if (prosody)
+    {
+        float *d_ctl = (float *)((char *)d_hid + ((b_hid + 255) & ~(size_t)255));
+        prosody_rows(prosody, 1, ctl);
+        ZV_HIP(hipMemcpyAsync(d_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, M.stream));
+        bt.d_ctl = d_ctl;
+    }
+    Model::EncoderTaps t = M.encode_dev(bt, d_ids, d_pun, d_sty, d_hid, d_nf);
+    ZV_HIP(hipMemcpyAsync(hidden, d_hid, b_hid, hipMemcpyDeviceToHost, M.stream));
+    int32_t nf = 0;
+    ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
+    if (features) ZV_HIP(hipMemcpyAsync(features, t.features, (size_t)n * E * 4, hipMemcpyDeviceToHost, M.stream));
+    if (logdur) ZV_HIP(hipMemcpyAsync(logdur, t.logdur, b_ids, hipMemcpyDeviceToHost, M.stream));
+    if (pitch) ZV_HIP(hipMemcpyAsync(pitch, t.pitch, b_ids, hipMemcpyDeviceToHost, M.stream));
+    if (energy) ZV_HIP(hipMemcpyAsync(energy, t.energy, b_ids, hipMemcpyDeviceToHost, M.stream));
+    if (pitch_bucket) ZV_HIP(hipMemcpyAsync(pitch_bucket, t.pitch_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
+    if (energy_bucket) ZV_HIP(hipMemcpyAsync(energy_bucket, t.energy_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
+    M.sync();
+    if (n_frames) *n_frames = (uint32_t)nf;
+}
+
 zv_status zv_encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
                          uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
                          float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket)
 {
     return guarded([&] {
-        ZV_NEED(m && ids && puncts && style && hidden, "null argument");
-        ZV_NEED(n > 0, "n must be > 0");
-        ZV_NEED(num_phonemes <= n, "num_phonemes exceeds n");
-        Model &M = *m->m;
-        use_lane0(m);
-        check_T(M, T);
-        check_ids(M, ids, puncts, n);
-        const size_t E = M.E();
-        const size_t b_ids = (size_t)n * 4, b_sty = E * 4, b_hid = (size_t)T * E * 4;
-        char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + 1024);
-        int32_t *d_nf = (int32_t *)io;
-        io += 256;
-        int32_t *d_ids = (int32_t *)io, *d_pun = (int32_t *)(io + b_ids);
-        float *d_sty = (float *)(io + 2 * b_ids + 256 - (2 * b_ids) % 256);
-        float *d_hid = (float *)((char *)d_sty + ((b_sty + 255) & ~(size_t)255));
-        ZV_HIP(hipMemcpyAsync(d_ids, ids, b_ids, hipMemcpyHostToDevice, M.stream));
-        ZV_HIP(hipMemcpyAsync(d_pun, puncts, b_ids, hipMemcpyHostToDevice, M.stream));
-        ZV_HIP(hipMemcpyAsync(d_sty, style, b_sty, hipMemcpyHostToDevice, M.stream));
-        const zv::Batch bt = zv::Batch::single(n, T, num_phonemes);
-        Model::EncoderTaps t = M.encode_dev(bt, d_ids, d_pun, d_sty, d_hid, d_nf);
-        ZV_HIP(hipMemcpyAsync(hidden, d_hid, b_hid, hipMemcpyDeviceToHost, M.stream));
-        int32_t nf = 0;
-        ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
-        if (features) ZV_HIP(hipMemcpyAsync(features, t.features, (size_t)n * E * 4, hipMemcpyDeviceToHost, M.stream));
-        if (logdur) ZV_HIP(hipMemcpyAsync(logdur, t.logdur, b_ids, hipMemcpyDeviceToHost, M.stream));
-        if (pitch) ZV_HIP(hipMemcpyAsync(pitch, t.pitch, b_ids, hipMemcpyDeviceToHost, M.stream));
-        if (energy) ZV_HIP(hipMemcpyAsync(energy, t.energy, b_ids, hipMemcpyDeviceToHost, M.stream));
-        if (pitch_bucket) ZV_HIP(hipMemcpyAsync(pitch_bucket, t.pitch_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
-        if (energy_bucket) ZV_HIP(hipMemcpyAsync(energy_bucket, t.energy_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
-        M.sync();
-        if (n_frames) *n_frames = (uint32_t)nf;
+        encode_taps(m, ids, puncts, style, n, num_phonemes, T, hidden, n_frames, features, logdur, pitch, energy, pitch_bucket,
+                    energy_bucket, nullptr, __func__);
+    });
+}
+
+zv_status zv_encode_taps_prosody(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
+                                 uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
+                                 float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody)
+{
+    return guarded([&] {
+        encode_taps(m, ids, puncts, style, n, num_phonemes, T, hidden, n_frames, features, logdur, pitch, energy, pitch_bucket,
+                    energy_bucket, prosody, __func__);
     });
 }
 
@@ -269,9 +327,10 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
     });
 }
 
-// one utterance end to end on the currently selected lane; no host synchronisation
+// one utterance end to end on the currently selected lane; no host synchronisation.  ctl_host: the utterance's control row
+// (prosody_rows) or null; like the other host buffers it must stay valid until the caller synchronises
 static void synthesize_enqueue(Model &M, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
-                               float *wav, int32_t *nf_host)
+                               float *wav, int32_t *nf_host, const float *ctl_host = nullptr)
 {
     check_ids(M, ids, puncts, n);
     check_T(M, T);
@@ -280,7 +339,7 @@ static void synthesize_enqueue(Model &M, const int32_t *ids, const int32_t *punc
     const size_t b_ids = al((size_t)n * 4), b_sty = al(E * 4), b_hid = al((size_t)T * E * 4), b_mel = al((size_t)T * Mm * 4),
                  b_wav = al((size_t)T * hop * 4);
     M.reserve(n, T);
-    char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + b_mel + b_wav);
+    char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + b_mel + b_wav + (ctl_host ? al(zv::CTL_STRIDE * 4) : 0));
     int32_t *d_nf = (int32_t *)io;
     io += 256;
     int32_t *d_ids = (int32_t *)io, *d_pun = (int32_t *)(io + b_ids);
@@ -289,7 +348,14 @@ static void synthesize_enqueue(Model &M, const int32_t *ids, const int32_t *punc
     ZV_HIP(hipMemcpyAsync(d_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, M.stream));
     ZV_HIP(hipMemcpyAsync(d_pun, puncts, (size_t)n * 4, hipMemcpyHostToDevice, M.stream));
     ZV_HIP(hipMemcpyAsync(d_sty, style, E * 4, hipMemcpyHostToDevice, M.stream));
-    M.chain_dev(zv::Batch::single(n, T, n), d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
+    zv::Batch bt = zv::Batch::single(n, T, n);
+    if (ctl_host)
+    {
+        float *d_ctl = (float *)((char *)d_wav + b_wav);
+        ZV_HIP(hipMemcpyAsync(d_ctl, ctl_host, zv::CTL_STRIDE * 4, hipMemcpyHostToDevice, M.stream));
+        bt.d_ctl = d_ctl;
+    }
+    M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
     ZV_HIP(hipMemcpyAsync(nf_host, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
     ZV_HIP(hipMemcpyAsync(wav, d_wav, (size_t)T * hop * 4, hipMemcpyDeviceToHost, M.stream));
 }
@@ -304,6 +370,24 @@ zv_status zv_synthesize(zv_model *m, const int32_t *ids, const int32_t *puncts, 
         use_lane0(m);
         int32_t nf = 0;
         synthesize_enqueue(M, ids, puncts, style, n, T, wav, &nf);
+        M.sync();
+        if (n_frames) *n_frames = (uint32_t)nf;
+    });
+}
+
+zv_status zv_synthesize_prosody(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                                float *wav, uint32_t *n_frames, const zv_prosody *prosody)
+{
+    return guarded([&] {
+        ZV_NEED(m && ids && puncts && style && wav, "null argument");
+        ZV_NEED(n > 0 && T > 0, "n and T must be > 0");
+        check_prosody(prosody, 1);
+        Model &M = *m->m;
+        use_lane0(m);
+        int32_t nf = 0;
+        float ctl[zv::CTL_STRIDE];
+        if (prosody) prosody_rows(prosody, 1, ctl);
+        synthesize_enqueue(M, ids, puncts, style, n, T, wav, &nf, prosody ? ctl : nullptr);
         M.sync();
         if (n_frames) *n_frames = (uint32_t)nf;
     });
@@ -376,9 +460,10 @@ static void use_lane0(zv_model *m)
     m->m->select_lane(0);
 }
 
+// prosody[n_utt] or null (checked by the caller)
 static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
                           const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
-                          uint32_t *n_frames)
+                          uint32_t *n_frames, const zv_prosody *prosody)
 {
     Model &M = *m->m;
     PendingBatch &pb = pending_slot(m, lane);
@@ -399,10 +484,12 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
     bt.t_max = zv::round_up((int)tmax, 64);
     bt.n_rows = (size_t)bt.nseg * bt.n_max;
     bt.t_rows = (size_t)bt.nseg * bt.t_max;
-    // device block: [frame counts][inputs: token table | frame table | ids | puncts | styles][hidden][mel][wav]
-    // (tables: one entry per utterance + one that spans all of them, see Batch::tokens_merged)
+    // device block: [frame counts][inputs: token table | frame table | ids | puncts | styles | controls][hidden][mel][wav]
+    // (tables: one entry per utterance + one that spans all of them, see Batch::tokens_merged; controls: only with prosody, one
+    // zv::CTL_STRIDE row per utterance — uploaded with the rest, so a replayed graph reads the values of this call)
     const size_t b_tab = al((size_t)(bt.nseg + 1) * sizeof(zv::Seg)), b_ids = al(bt.n_rows * 4), b_sty = al((size_t)bt.nseg * E * 4);
-    const size_t b_in = 2 * b_tab + 2 * b_ids + b_sty;
+    const size_t b_ctl = prosody ? al((size_t)bt.nseg * zv::CTL_STRIDE * 4) : 0;
+    const size_t b_in = 2 * b_tab + 2 * b_ids + b_sty + b_ctl;
     const size_t b_nf = al((size_t)bt.nseg * 4), b_hid = al(bt.t_rows * E * 4), b_mel = al(bt.t_rows * Mm * 4),
                  b_wav = al(bt.t_rows * hop * 4);
     M.reserve_batch(bt);
@@ -412,6 +499,7 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
     zv::Seg *d_tok = (zv::Seg *)d_in, *d_frm = (zv::Seg *)(d_in + b_tab);
     int32_t *d_ids = (int32_t *)(d_in + 2 * b_tab), *d_pun = (int32_t *)(d_in + 2 * b_tab + b_ids);
     float *d_sty = (float *)(d_in + 2 * b_tab + 2 * b_ids);
+    if (prosody) bt.d_ctl = (const float *)(d_in + 2 * b_tab + 2 * b_ids + b_sty);
     float *d_hid = (float *)(d_in + b_in), *d_mel = (float *)((char *)d_hid + b_hid), *d_wav = (float *)((char *)d_mel + b_mel);
     bt.d_tok = d_tok;
     bt.d_frm = d_frm;
@@ -442,6 +530,7 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
         }
         h_tok[n_utt] = zv::Seg{0, n0, n0, 0};
         h_frm[n_utt] = zv::Seg{0, t0, 0, 0};
+        if (prosody) prosody_rows(prosody, n_utt, (float *)(pin + 2 * b_tab + 2 * b_ids + b_sty));
     }
     int32_t *h_nf = (int32_t *)(pin + b_in);
     char *h_wav = pin + b_in + b_nf;
@@ -543,8 +632,9 @@ static void batch_finish(zv_model *m, int lane)
 }
 
 static void batch_check(Model &M, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts, const float *const *styles,
-                        const uint32_t *n_phonemes, const uint32_t *T, float *const *wav)
+                        const uint32_t *n_phonemes, const uint32_t *T, float *const *wav, const zv_prosody *prosody)
 {
+    check_prosody(prosody, n_utt);
     for (uint32_t u = 0; u < n_utt; u++)
     {
         ZV_NEED(ids[u] && puncts[u] && styles[u] && wav[u], "null utterance pointer");
@@ -570,27 +660,60 @@ static uint32_t batch_group_end(uint32_t a, uint32_t n_utt, const uint32_t *T)
     return b;
 }
 
+static void synthesize_batch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                             const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                             uint32_t *n_frames, const zv_prosody *prosody)
+{
+    Model &M = *m->m;
+    ZV_HIP(hipSetDevice(M.device));
+    batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav, prosody);
+    // Groups of up to 64 utterances / 64 Ki frames go through the chain as ONE launch per kernel: every tensor is
+    // the row concatenation of the group, the segment tables tell the kernels where each utterance starts and ends.
+    // Capacities are rounded up so that batches of similar shape replay the same captured graph.
+    uint32_t a = 0;
+    while (a < n_utt)
+    {
+        const uint32_t b = batch_group_end(a, n_utt, T);
+        batch_enqueue(m, 0, b - a, ids + a, puncts + a, styles + a, n_phonemes + a, T + a, wav + a, n_frames ? n_frames + a : nullptr,
+                      prosody ? prosody + a : nullptr);
+        batch_finish(m, 0);
+        a = b;
+    }
+}
+
 zv_status zv_synthesize_batch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
                               const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
                               uint32_t *n_frames)
 {
     return guarded([&] {
         ZV_NEED(m && ids && puncts && styles && n_phonemes && T && wav, "null argument");
-        Model &M = *m->m;
-        ZV_HIP(hipSetDevice(M.device));
-        batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav);
-        // Groups of up to 64 utterances / 64 Ki frames go through the chain as ONE launch per kernel: every tensor is
-        // the row concatenation of the group, the segment tables tell the kernels where each utterance starts and ends.
-        // Capacities are rounded up so that batches of similar shape replay the same captured graph.
-        uint32_t a = 0;
-        while (a < n_utt)
-        {
-            const uint32_t b = batch_group_end(a, n_utt, T);
-            batch_enqueue(m, 0, b - a, ids + a, puncts + a, styles + a, n_phonemes + a, T + a, wav + a, n_frames ? n_frames + a : nullptr);
-            batch_finish(m, 0);
-            a = b;
-        }
+        synthesize_batch(m, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, nullptr);
     });
+}
+
+zv_status zv_synthesize_batch_prosody(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                      const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                      uint32_t *n_frames, const zv_prosody *prosody)
+{
+    return guarded([&] {
+        ZV_NEED(m && ids && puncts && styles && n_phonemes && T && wav, "null argument");
+        synthesize_batch(m, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody);
+    });
+}
+
+static void synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                   const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                   uint32_t *n_frames, const zv_prosody *prosody, const char *fn)
+{
+    if (!(m && ids && puncts && styles && n_phonemes && T && wav)) zv::fail(ZV_ERR_ARG, "%s: null argument", fn);
+    if (!(lane < ZV_BATCH_LANES)) zv::fail(ZV_ERR_ARG, "%s: lane out of range", fn);
+    if (!(n_utt > 0)) zv::fail(ZV_ERR_ARG, "%s: empty batch", fn);
+    Model &M = *m->m;
+    ZV_HIP(hipSetDevice(M.device));
+    batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav, prosody);
+    if (batch_group_end(0, n_utt, T) != n_utt)
+        zv::fail(ZV_ERR_ARG, "%s: an asynchronous batch must fit one launch group (64 utterances, 64 Ki frames of capacity)", fn);
+    batch_enqueue(m, (int)lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody);
 }
 
 zv_status zv_synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
@@ -598,14 +721,16 @@ zv_status zv_synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, 
                                     uint32_t *n_frames)
 {
     return guarded([&] {
-        ZV_NEED(m && ids && puncts && styles && n_phonemes && T && wav, "null argument");
-        ZV_NEED(lane < ZV_BATCH_LANES, "lane out of range");
-        ZV_NEED(n_utt > 0, "empty batch");
-        Model &M = *m->m;
-        ZV_HIP(hipSetDevice(M.device));
-        batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav);
-        ZV_NEED(batch_group_end(0, n_utt, T) == n_utt, "an asynchronous batch must fit one launch group (64 utterances, 64 Ki frames of capacity)");
-        batch_enqueue(m, (int)lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames);
+        synthesize_batch_begin(m, lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, nullptr, __func__);
+    });
+}
+
+zv_status zv_synthesize_batch_begin_prosody(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                            const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                            const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody)
+{
+    return guarded([&] {
+        synthesize_batch_begin(m, lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody, __func__);
     });
 }
 

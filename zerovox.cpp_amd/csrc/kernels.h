@@ -293,6 +293,13 @@ hipError_t launch_embed(hipStream_t s, const int32_t *ids, const int32_t *puncts
 // softmax(q k^T * inv_temp) v per (segment, head); q, k, v [rows][ld] token-major, heads side by side
 hipError_t launch_attention(hipStream_t s, const float *q, const float *k, const float *v, int ld, int H, int dk,
                             float inv_temp, float *o, int ldo, const Segs &segs);
+// Prosody controls (include/zerovox_amd.h zv_prosody): f32 [segment][CTL_STRIDE], one row per utterance of the batch, read by the
+// kernels below as ctl[segment * CTL_STRIDE + field].  A null ctl is the uncontrolled instruction path (uniform branch).
+constexpr int CTL_STRIDE = 8;
+constexpr int CTL_DURATION = 0;        // duration_scale
+constexpr int CTL_PITCH = 1;           // pitch_scale, pitch_shift
+constexpr int CTL_ENERGY = 3;          // energy_scale, energy_shift
+
 // y = LayerNorm(x + res) * w + b  over the C real channels (res may be null); channels [C, Cp) are zeroed
 hipError_t launch_add_layernorm(hipStream_t s, const float *x, int ldx, const float *res, int ldr, int C, int Cp,
                                 const float *w, const float *b, float eps, float *y, int ldy, const Segs &segs);
@@ -300,22 +307,26 @@ hipError_t launch_add_layernorm(hipStream_t s, const float *x, int ldx, const fl
 //   y += post[segment][:]                                   (post_seg: floats between segments' vectors)
 //   pred[row] = dot(y[row][:C], dot_w) + dot_b[0]           (launch_rowdot's chain)
 //   bucket[row] = clamp((int)(pred * (nbins - 1) + 0.5)); feat[row][:embC] += emb[bucket][:]   (launch_bucket_embed_add; needs dot_w)
+//     ctl (or null): pred -> pred * ctl[seg][ctl_field] + ctl[seg][ctl_field + 1] before the bucket (pred itself is stored raw)
 // layernorm_tail_ok(C): the tail exists in the rows-in-registers form only (C <= 768)
 bool       layernorm_tail_ok(int C);
 hipError_t launch_layernorm_tail(hipStream_t s, const float *x, int ldx, const float *res, int ldr, int C, int Cp, const float *w,
                                  const float *b, float eps, float *y, int ldy, const Segs &segs, const float *post, int post_seg,
                                  const float *dot_w, const float *dot_b, float *pred, const float *emb, int nbins, int embC, float *feat,
-                                 int ldf, int32_t *bucket);
+                                 int ldf, int32_t *bucket, const float *ctl = nullptr, int ctl_field = 0);
 // x[row][:] += v[segment][:]
 hipError_t launch_add_rowvec(hipStream_t s, float *x, int ld, int C, const float *v, int v_seg, const Segs &segs);
 // pred[n] = dot(x[n][:], w) + b
 hipError_t launch_rowdot(hipStream_t s, const float *x, int ld, int C, const float *w, const float *b, float *y, const Segs &segs);
 // bucket[n] = clamp((int)(pred*(nbins-1) + 0.5), 0, nbins-1); x[n][:] += emb[bucket[n]][:]
+//   ctl (or null): pred -> pred * ctl[seg][ctl_field] + ctl[seg][ctl_field + 1] first
 hipError_t launch_bucket_embed_add(hipStream_t s, const float *pred, int nbins, const float *emb, int C, float *x, int ld,
-                                   int32_t *bucket, const Segs &segs);
+                                   int32_t *bucket, const Segs &segs, const float *ctl = nullptr, int ctl_field = 0);
 // device length regulator: rounded durations of the first `aux` tokens of a segment -> inclusive scan (cum[], one int
 // per token row) -> gather into the segment's frames, zero tail; n_frames[segment] = frames
+//   ctl (or null): each duration is multiplied by ctl[seg][CTL_DURATION] (f32) before it is rounded
 hipError_t launch_length_regulator(hipStream_t s, const float *feat, int ld, const float *logdur, int C, float *hidden,
-                                   int ldh, int32_t *cum, int32_t *n_frames, const Segs &tokens, const Segs &frames);
+                                   int ldh, int32_t *cum, int32_t *n_frames, const Segs &tokens, const Segs &frames,
+                                   const float *ctl = nullptr);
 
 }  // namespace zv

@@ -925,6 +925,8 @@ hipError_t launch_attention(hipStream_t s, const float *q, const float *k, const
 //   dot_w  : pred[row] = dot(y[row], dot_w) + dot_b[0]   (VariancePredictor linear_layer, :434-435; lane l sums channels l, l + 64, ...
 //            in that order and the wave sum follows: rowdot_kernel's chain)
 //   emb    : bucket[row] = clamp((int)((double)(pred * (nbins - 1)) + 0.5)); feat[row][:] += emb[bucket][:]   (:442-474, 565-569)
+//   ctl    : prosody control of the bucket step (kernels.h CTL_*): pred * ctl[seg][ctl_field] + ctl[seg][ctl_field + 1] is bucketed
+//            instead of pred (pred is stored raw); null = the uncontrolled path
 struct LnTail
 {
     const float *post;
@@ -936,6 +938,8 @@ struct LnTail
     float       *feat;
     int          ldf;
     int32_t     *bucket;
+    const float *ctl;
+    int          ctl_field;
 };
 
 template <bool TAIL>
@@ -1032,7 +1036,14 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const float *__restr
             if (tail.emb)
             {
                 const int bin_max = tail.nbins - 1;
-                const float p = pr * (float)bin_max;
+                float p = pr;
+                if (tail.ctl)
+                {
+                    const float *cv = tail.ctl + (size_t)blockIdx.y * CTL_STRIDE + tail.ctl_field;
+                    p = p * cv[0];
+                    p = p + cv[1];
+                }
+                p = p * (float)bin_max;
                 int yb = (int)((double)p + 0.5);          // truncating cast of x + 0.5 (double), not round-half-even
                 yb = yb < 0 ? 0 : (yb > bin_max ? bin_max : yb);
                 if (lane == 0) tail.bucket[row] = yb;
@@ -1080,11 +1091,12 @@ bool layernorm_tail_ok(int C) { return C <= 64 * 12; }
 hipError_t launch_layernorm_tail(hipStream_t s, const float *x, int ldx, const float *res, int ldr, int C, int Cp, const float *w,
                                  const float *b, float eps, float *y, int ldy, const Segs &segs, const float *post, int post_seg,
                                  const float *dot_w, const float *dot_b, float *pred, const float *emb, int nbins, int embC, float *feat,
-                                 int ldf, int32_t *bucket)
+                                 int ldf, int32_t *bucket, const float *ctl, int ctl_field)
 {
     if (!layernorm_tail_ok(C)) return hipErrorInvalidValue;        // the tail lives in the rows-in-registers form
     if (emb && (!dot_w || !feat || !bucket || nbins < 1)) return hipErrorInvalidValue;
     if (dot_w && (!dot_b || !pred)) return hipErrorInvalidValue;
+    if (ctl && !emb) return hipErrorInvalidValue;
     LnTail tail;
     tail.post = post;
     tail.post_seg = post_seg;
@@ -1097,6 +1109,8 @@ hipError_t launch_layernorm_tail(hipStream_t s, const float *x, int ldx, const f
     tail.feat = feat;
     tail.ldf = ldf;
     tail.bucket = bucket;
+    tail.ctl = ctl;
+    tail.ctl_field = ctl_field;
     hipLaunchKernelGGL(add_layernorm_kernel<true>, dim3((segs.max_rows + 3) / 4, segs.nseg), dim3(256), 0, s, x, ldx, res, ldr, C, Cp, w, b,
                        eps, y, ldy, segs, tail);
     return hipGetLastError();
@@ -1139,14 +1153,22 @@ hipError_t launch_rowdot(hipStream_t s, const float *x, int ld, int C, const flo
 }
 
 // ggml_zv_mul_clamp_to_i32 + get_rows + add (reference src/fs2encoder.cpp:442-474,565-569)
+// ctl (or null): the prosody control, p * ctl[seg][ctl_field] + ctl[seg][ctl_field + 1] is bucketed (kernels.h CTL_*)
 __global__ void bucket_embed_add_kernel(const float *__restrict__ pred, int nbins, const float *__restrict__ emb, int C,
-                                        float *__restrict__ x, int ld, int32_t *__restrict__ bucket, const Segs segs)
+                                        float *__restrict__ x, int ld, int32_t *__restrict__ bucket, const Segs segs,
+                                        const float *__restrict__ ctl, int ctl_field)
 {
     const Seg sg = seg_at(segs, blockIdx.y);
     if ((int)blockIdx.x >= sg.rows) return;
     const size_t n = (size_t)sg.row0 + blockIdx.x;
     const int bin_max = nbins - 1;
     float p = pred[n];
+    if (ctl)
+    {
+        const float *cv = ctl + (size_t)blockIdx.y * CTL_STRIDE + ctl_field;
+        p = p * cv[0];
+        p = p + cv[1];
+    }
     p = p * (float)bin_max;
     int y = (int)((double)p + 0.5);          // truncating cast of x + 0.5 (double), not round-half-even
     y = y < 0 ? 0 : (y > bin_max ? bin_max : y);
@@ -1155,10 +1177,10 @@ __global__ void bucket_embed_add_kernel(const float *__restrict__ pred, int nbin
 }
 
 hipError_t launch_bucket_embed_add(hipStream_t s, const float *pred, int nbins, const float *emb, int C, float *x, int ld,
-                                   int32_t *bucket, const Segs &segs)
+                                   int32_t *bucket, const Segs &segs, const float *ctl, int ctl_field)
 {
     hipLaunchKernelGGL(bucket_embed_add_kernel, dim3(segs.max_rows, segs.nseg), dim3(256), 0, s, pred, nbins, emb, C, x, ld, bucket,
-                       segs);
+                       segs, ctl, ctl_field);
     return hipGetLastError();
 }
 
@@ -1166,8 +1188,10 @@ hipError_t launch_bucket_embed_add(hipStream_t s, const float *pred, int nbins, 
 // Length regulator on the device (the reference does it on the host, src/fs2encoder.cpp:611-654):
 //   dur_i = (int)((float)(exp(logdur_i) - 1.0) + 0.5) for the first num_phonemes (= aux) tokens of the utterance;
 //   frame f belongs to the token whose cumulative duration first exceeds f; frames past the total (or past T) are zero.
+//   ctl (or null): the (float) duration is multiplied by ctl[seg][CTL_DURATION] before it is rounded (prosody control).
 __global__ __launch_bounds__(1024) void lr_scan_kernel(const float *__restrict__ logdur, int32_t *__restrict__ cum,
-                                                       int32_t *__restrict__ n_frames, const Segs tokens, const Segs frames)
+                                                       int32_t *__restrict__ n_frames, const Segs tokens, const Segs frames,
+                                                       const float *__restrict__ ctl)
 {
     __shared__ int buf[1024];
     const Seg tk = seg_at(tokens, blockIdx.x), fr = seg_at(frames, blockIdx.x);
@@ -1177,6 +1201,7 @@ __global__ __launch_bounds__(1024) void lr_scan_kernel(const float *__restrict__
     const float *ld_ = logdur + tk.row0;
     int32_t *cm = cum + tk.row0;
     const int tid = threadIdx.x;
+    const float dscale = ctl ? ctl[(size_t)blockIdx.x * CTL_STRIDE + CTL_DURATION] : 1.f;
     int carry = 0;
     for (int base = 0; base < n; base += 1024)
     {
@@ -1184,7 +1209,8 @@ __global__ __launch_bounds__(1024) void lr_scan_kernel(const float *__restrict__
         int d = 0;
         if (i < nwalk)
         {
-            const float dur = (float)(exp((double)ld_[i]) - 1.0);
+            float dur = (float)(exp((double)ld_[i]) - 1.0);
+            if (ctl) dur = dur * dscale;
             d = (int)((double)dur + 0.5);
             if (d < 0) d = 0;
             if (d > T) d = T;          // keeps the running sum far from int overflow; frames stop at T anyway
@@ -1261,7 +1287,8 @@ __global__ __launch_bounds__(256) void lr_gather16_kernel(const float *__restric
 // workgroup of a segment also stores the scan (the `cum` tap) and the frame count.  Integer sums: any scan order, the same values.
 __global__ __launch_bounds__(256) void lr_fused16_kernel(const float *__restrict__ feat, int ld, const float *__restrict__ logdur, int C,
                                                          float *__restrict__ hidden, int ldh, int32_t *__restrict__ cum,
-                                                         int32_t *__restrict__ n_frames, const Segs tokens, const Segs frames)
+                                                         int32_t *__restrict__ n_frames, const Segs tokens, const Segs frames,
+                                                         const float *__restrict__ ctl)
 {
     __shared__ int32_t lr_cs[1024];
     __shared__ int32_t lr_part[256];
@@ -1271,6 +1298,7 @@ __global__ __launch_bounds__(256) void lr_fused16_kernel(const float *__restrict
     if (f0 >= T) return;
     const int nwalk = tk.aux < n ? tk.aux : n;
     const int tid = threadIdx.x;
+    const float dscale = ctl ? ctl[(size_t)blockIdx.y * CTL_STRIDE + CTL_DURATION] : 1.f;
     // four consecutive tokens per thread: durations (lr_scan_kernel's arithmetic), their running sums, the thread's total
     int d[4], tot = 0;
 #pragma unroll
@@ -1280,7 +1308,8 @@ __global__ __launch_bounds__(256) void lr_fused16_kernel(const float *__restrict
         int v = 0;
         if (i < nwalk)
         {
-            const float dur = (float)(exp((double)logdur[tk.row0 + i]) - 1.0);
+            float dur = (float)(exp((double)logdur[tk.row0 + i]) - 1.0);
+            if (ctl) dur = dur * dscale;
             v = (int)((double)dur + 0.5);
             if (v < 0) v = 0;
             if (v > T) v = T;
@@ -1329,16 +1358,16 @@ __global__ __launch_bounds__(256) void lr_fused16_kernel(const float *__restrict
 }
 
 hipError_t launch_length_regulator(hipStream_t s, const float *feat, int ld, const float *logdur, int C, float *hidden,
-                                   int ldh, int32_t *cum, int32_t *n_frames, const Segs &tokens, const Segs &frames)
+                                   int ldh, int32_t *cum, int32_t *n_frames, const Segs &tokens, const Segs &frames, const float *ctl)
 {
     if (tokens.nseg != frames.nseg || tokens.nseg < 1) return hipErrorInvalidValue;
     if ((C & 3) == 0 && (ld & 3) == 0 && (ldh & 3) == 0 && tokens.max_rows >= 1 && tokens.max_rows <= 1024 && frames.max_rows >= 1)
     {
         hipLaunchKernelGGL(lr_fused16_kernel, dim3((frames.max_rows + 15) / 16, frames.nseg), dim3(256), 0, s, feat, ld, logdur, C, hidden,
-                           ldh, cum, n_frames, tokens, frames);
+                           ldh, cum, n_frames, tokens, frames, ctl);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(lr_scan_kernel, dim3(tokens.nseg), dim3(1024), 0, s, logdur, cum, n_frames, tokens, frames);
+    hipLaunchKernelGGL(lr_scan_kernel, dim3(tokens.nseg), dim3(1024), 0, s, logdur, cum, n_frames, tokens, frames, ctl);
     if ((C & 3) == 0 && (ld & 3) == 0 && (ldh & 3) == 0 && (size_t)tokens.max_rows * 4 <= 48 * 1024 && tokens.max_rows >= 1)
         hipLaunchKernelGGL(lr_gather16_kernel, dim3((frames.max_rows + 15) / 16, frames.nseg), dim3(256), (size_t)tokens.max_rows * 4, s,
                            feat, ld, cum, C, hidden, ldh, tokens, frames);

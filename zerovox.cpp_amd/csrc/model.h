@@ -60,6 +60,9 @@ struct Batch
     size_t     n_rows = 0, t_rows = 0;      // >= sum of phonemes / frames (rows of the concatenated buffers)
     const Seg *d_tok = nullptr, *d_frm = nullptr;
     Seg        tok1{0, 0, 0, 0}, frm1{0, 0, 0, 0};
+    // prosody controls, f32 [nseg][CTL_STRIDE] in HBM (kernels.h CTL_*), or null: the uncontrolled schedule.  Part of a chain
+    // graph's key (chain_dev: the kernels' arguments differ); the VALUES are read at run time, so a replay picks up new ones.
+    const float *d_ctl = nullptr;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -83,10 +86,11 @@ struct Batch
 // a captured schedule: replayed when the same entry point is called with the same capacities and buffers
 struct CapturedGraph
 {
+    static constexpr int NKEY = 12;
     int            kind = 0;               // 0 vocoder, 1 chain
     unsigned       epoch = 0;              // knob_epoch() at capture
     Batch          b;
-    const void    *p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const void    *p[NKEY] = {};
     hipGraphExec_t exec = nullptr;
 };
 

@@ -110,6 +110,10 @@ class ZeroVOXModel
 
     bool write_wav_file(const std::string &fname);
 
+    // prosody controls (include/zerovox_amd.h zv_prosody: speaking rate, pitch, energy) for the eval() calls that follow, until
+    // set again; the identity {1, 1, 0, 1, 0} gives the uncontrolled bits.  Values are checked when eval() runs (ZV_ERR_ARG).
+    void set_prosody(const zv_prosody &p);
+
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
     uint32_t     get_num_frames() const { return n_frames; }
@@ -125,6 +129,8 @@ class ZeroVOXModel
     float           *mel;
     float           *wav;
     uint32_t         n_frames;
+    zv_prosody       prosody;
+    bool             has_prosody;
 };
 
 }  // namespace ZeroVOX

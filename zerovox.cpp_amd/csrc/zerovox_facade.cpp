@@ -96,7 +96,8 @@ void HiFiGAN::eval(const float *mel, float *wav)
 // ---------------------------------------------------------------------------------------------------
 
 ZeroVOXModel::ZeroVOXModel(const std::string &fname)
-    : model(nullptr), encoder(nullptr), decoder(nullptr), meldec(nullptr), hidden_state(nullptr), mel(nullptr), wav(nullptr), n_frames(0)
+    : model(nullptr), encoder(nullptr), decoder(nullptr), meldec(nullptr), hidden_state(nullptr), mel(nullptr), wav(nullptr), n_frames(0),
+      prosody{1.0f, 1.0f, 0.0f, 1.0f, 0.0f}, has_prosody(false)
 {
     int device = 0;
     if (const char *e = getenv("ZEROVOX_DEVICE")) device = atoi(e);
@@ -142,15 +143,29 @@ void ZeroVOXModel::release()
     model = nullptr;
 }
 
+void ZeroVOXModel::set_prosody(const zv_prosody &p)
+{
+    prosody = p;
+    has_prosody = true;
+}
+
 void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const float *style_embed, uint32_t num_phonemes)
 {
+    const zv_prosody *pr = has_prosody ? &prosody : nullptr;
     if (num_phonemes != (uint32_t)MAX_N_PHONEMES)
     {
         // any length: run the C-ABI path directly with N = num_phonemes (the stage objects are pinned to MAX_N_PHONEMES)
-        chk(zv_synthesize(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames));
+        chk(zv_synthesize_prosody(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr));
         return;
     }
-    n_frames = encoder->eval(src_seq, puncts, style_embed, num_phonemes, hidden_state);
+    if (pr)
+    {
+        // the encoder stage with controls (FS2Encoder::eval keeps the reference's signature): the same call it makes, plus prosody
+        chk(zv_encode_taps_prosody(model, src_seq, puncts, style_embed, MAX_N_PHONEMES, num_phonemes, hparams.max_seq_len,
+                                   hidden_state, &n_frames, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pr));
+    }
+    else
+        n_frames = encoder->eval(src_seq, puncts, style_embed, num_phonemes, hidden_state);
     decoder->eval(hidden_state, style_embed, mel);
     meldec->eval(mel, wav);
 }

@@ -9,10 +9,14 @@
 //     line 2: punctuation ids        (N integers)
 //     line 3: style embedding        (emb_dim + punct_emb_dim floats; a single 0 means the zero vector)
 //
-// usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--info]
+// usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--info] [prosody flags]
+//   --duration-scale S, --pitch-scale S, --pitch-shift D, --energy-scale S, --energy-shift D
+//            prosody controls (include/zerovox_amd.h zv_prosody): durations * S (0 < S <= 16), pitch / energy predictions
+//            p * S + D before bucketing; defaults 1, 1, 0, 1, 0 (the uncontrolled result).  A bad value is a usage error.
 //   --trim   write only the frames the length regulator produced (the reference always writes max_seq_len frames,
 //            src/zerovox.cpp:369)
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,8 +34,14 @@ static const char *k_default_out = "foo.wav";                   // reference src
 static void usage(FILE *f)
 {
     fprintf(f, "usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--info]\n"
+               "               [--duration-scale S] [--pitch-scale S] [--pitch-shift D] [--energy-scale S] [--energy-shift D]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
-               "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n",
+               "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
+               "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
+               "  --pitch-scale S      pitch prediction p -> p * S + shift before bucketing, default 1\n"
+               "  --pitch-shift D      (see --pitch-scale), default 0\n"
+               "  --energy-scale S     energy prediction e -> e * S + shift before bucketing, default 1\n"
+               "  --energy-shift D     (see --energy-scale), default 0\n",
             k_default_model, k_default_out);
 }
 
@@ -45,10 +55,25 @@ template <typename T> static std::vector<T> parse_line(const std::string &line)
     return v;
 }
 
+// a whole-string finite float, else a usage error (exit 2)
+static float parse_flag_float(const char *flag, const std::string &v)
+{
+    char *end = nullptr;
+    const float x = strtof(v.c_str(), &end);
+    if (v.empty() || end != v.c_str() + v.size() || !std::isfinite(x))
+    {
+        fprintf(stderr, "zerovox: %s needs a finite number, got '%s'\n", flag, v.c_str());
+        usage(stderr);
+        exit(2);
+    }
+    return x;
+}
+
 int main(int argc, char **argv)
 {
     std::string model_path = k_default_model, out_path = k_default_out, utt_path;
-    bool trim = false, info = false;
+    bool trim = false, info = false, controlled = false;
+    zv_prosody prosody = {1.0f, 1.0f, 0.0f, 1.0f, 0.0f};
     for (int i = 1; i < argc; i++)
     {
         const std::string a = argv[i];
@@ -61,6 +86,25 @@ int main(int argc, char **argv)
         else if (a == "-o") out_path = need("-o");
         else if (a == "--trim") trim = true;
         else if (a == "--info") info = true;
+        else if (a == "--duration-scale" || a == "--pitch-scale" || a == "--pitch-shift" || a == "--energy-scale" || a == "--energy-shift")
+        {
+            const float x = parse_flag_float(a.c_str(), need(a.c_str()));
+            if (a == "--duration-scale")
+            {
+                if (!(x > 0.0f && x <= 16.0f))
+                {
+                    fprintf(stderr, "zerovox: --duration-scale must be in (0, 16], got %g\n", (double)x);
+                    usage(stderr);
+                    return 2;
+                }
+                prosody.duration_scale = x;
+            }
+            else if (a == "--pitch-scale") prosody.pitch_scale = x;
+            else if (a == "--pitch-shift") prosody.pitch_shift = x;
+            else if (a == "--energy-scale") prosody.energy_scale = x;
+            else prosody.energy_shift = x;
+            controlled = true;
+        }
         else if (a == "-h" || a == "--help") { usage(stdout); return 0; }
         else { fprintf(stderr, "zerovox: unknown argument '%s'\n", a.c_str()); usage(stderr); return 2; }
     }
@@ -88,6 +132,7 @@ int main(int argc, char **argv)
 
         ZeroVOX::ZeroVOXModel model(model_path);
         const ZeroVOX::zerovox_hparams &hp = model.get_hparams();
+        if (controlled) model.set_prosody(prosody);
         if (utt_path.empty())
             model.eval();
         else
