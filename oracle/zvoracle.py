@@ -74,6 +74,14 @@ class Oracle:
             build()
         self.lib = _load(path)
         self.ctx = C.c_void_p(self.lib.zvo_new())
+        # shapes the reference reads from the checkpoint (src/zerovox.cpp): mels from to_out, FFN / predictor taps from the convs
+        shp = lambda n: tuple(tensors[n].shape) if n in tensors else None
+        to_out = shp("_mel_decoder.to_out.0.w")
+        self.num_mels = to_out[0] if to_out else None
+        w1, w2 = shp("_pe._enc.laystk.0.pos_ffn.w_1.w"), shp("_pe._enc.laystk.0.pos_ffn.w_2.w")
+        self.ffn_taps = (w1[2], w2[2]) if w1 and w2 else None
+        vp = shp("_pe._var_adapt.duration_predictor.conv_layer.conv1d_1.conv.w")
+        self.vp_taps = vp[2] if vp else None
         self._keep = []
         for name, arr in tensors.items():
             arr = np.ascontiguousarray(arr)
@@ -117,11 +125,22 @@ class Oracle:
         self._chk(self.lib.zvo_vocoder(self.ctx, _p(mel), T, _p(wav)))
         return wav
 
-    def decoder(self, hidden: np.ndarray, style: np.ndarray, num_mels: int = 80) -> np.ndarray:
+    @staticmethod
+    def _agree(what, given, loaded):
+        """a shape argument is only a check of the checkpoint's own: a value that disagrees is an error, never a silent override"""
+        if given is not None and loaded is not None and tuple(np.atleast_1d(given)) != tuple(np.atleast_1d(loaded)):
+            raise ValueError(f"oracle: {what} = {given} but the checkpoint has {loaded}")
+        return loaded if loaded is not None else given
+
+    def decoder(self, hidden: np.ndarray, style: np.ndarray, num_mels: Optional[int] = None) -> np.ndarray:
+        """mel [T, M], M from _mel_decoder.to_out.0.w (num_mels: a check only)"""
         hidden = np.ascontiguousarray(hidden, dtype=np.float32)
         style = np.ascontiguousarray(style, dtype=np.float32)
         T = hidden.shape[0]
-        mel = np.empty((T, num_mels), dtype=np.float32)
+        M = self._agree("num_mels", num_mels, self.num_mels)
+        if M is None:
+            raise ValueError("oracle: no _mel_decoder.to_out.0.w tensor")
+        mel = np.empty((T, M), dtype=np.float32)
         self._chk(self.lib.zvo_decoder(self.ctx, _p(hidden), _p(style), T, _p(mel)))
         return mel
 
@@ -130,8 +149,10 @@ class Oracle:
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
         N, E = len(ids), geom.E
+        ksz = self._agree("conv_kernel_size", tuple(geom.conv_kernel_size), self.ffn_taps)
+        vpk = self._agree("vp_kernel_size", geom.vp_kernel_size, self.vp_taps)
         p = _EncParams(N, T, geom.emb_dim, geom.punct_emb_dim, geom.encoder_layer, geom.encoder_head,
-                       (C.c_int * 2)(*geom.conv_kernel_size), geom.vp_kernel_size, geom.ve_n_bins)
+                       (C.c_int * 2)(*ksz), int(np.atleast_1d(vpk)[0]), geom.ve_n_bins)
         out = dict(hidden=np.empty((T, E), np.float32), features=np.empty((N, E), np.float32),
                    logdur=np.empty(N, np.float32), pitch=np.empty(N, np.float32), energy=np.empty(N, np.float32),
                    pitch_bucket=np.empty(N, np.int32), energy_bucket=np.empty(N, np.int32))
@@ -172,11 +193,18 @@ class Oracle:
     LAYER_VOC_UPSAMPLE, LAYER_VOC_INPUT, LAYER_VOC_OUTPUT, LAYER_DEC_ASR_RES, LAYER_DEC_TO_OUT, LAYER_ENC_EMBED = 4, 5, 6, 7, 8, 9
     LAYER_ENC_MHA, LAYER_ENC_FFN, LAYER_DEC_ADAIN, LAYER_ENC_LN = 10, 11, 12, 13
 
-    def layer(self, kind: int, index: int, x: np.ndarray, out_cols: int, style=None, heads: int = 2, ksz=(9, 1),
+    def layer(self, kind: int, index: int, x: np.ndarray, out_cols: int, style=None, heads: int = 2, ksz=None,
               out_rows: Optional[int] = None) -> np.ndarray:
         """one layer of the reference semantics on a given input (time-major [rows][cols]): HiFi-GAN residual block,
         FFT block, decoder residual block, variance predictor, transposed conv (out_rows = rows x scale), vocoder input /
-        output conv, asr_res, to_out, embedding (out_cols = 0 -> a vector of out_rows values)"""
+        output conv, asr_res, to_out, embedding (out_cols = 0 -> a vector of out_rows values).  ksz: the FFN's two tap counts
+        (the predictors': (vp_kernel_size,)), taken from the checkpoint; a value given that disagrees raises.  heads is not a
+        shape of any tensor: pass the geometry's encoder_head for the attention layers"""
+        if kind == self.LAYER_VAR_PRED:
+            ksz = (self._agree("vp_kernel_size", None if ksz is None else ksz[0], self.vp_taps),)
+        elif kind in (self.LAYER_ENC_FFT, self.LAYER_ENC_MHA, self.LAYER_ENC_FFN):
+            ksz = self._agree("conv_kernel_size", None if ksz is None else tuple(ksz), self.ffn_taps)
+        ksz = (9, 1) if ksz is None else tuple(np.atleast_1d(ksz))
         x = np.ascontiguousarray(x, dtype=np.float32)
         rows, cols = x.shape
         orows = rows if out_rows is None else out_rows
@@ -201,7 +229,7 @@ def have_reference() -> bool:
 
 
 def run_reference_chain(gguf_path: str, ids, puncts, style, *, T: int, threads: int = 4, num_phonemes: Optional[int] = None,
-                        num_mels: int = 80, hop: int = 300) -> dict:
+                        num_mels: Optional[int] = None, hop: int = 300) -> dict:
     """The three stage evals back to back on one utterance, as ZeroVOXModel::eval does (reference src/zerovox.cpp:326-334):
     the decoder reads the encoder's hidden, the vocoder the decoder's mel.  Returns every stage's outputs + timings."""
     return run_reference(gguf_path, N=len(ids), T=T, threads=threads, enc=(ids, puncts, style), dec=(None, style), voc=None,
@@ -209,9 +237,10 @@ def run_reference_chain(gguf_path: str, ids, puncts, style, *, T: int, threads: 
 
 
 def run_reference(gguf_path: str, *, N: Optional[int] = None, T: Optional[int] = None, threads: int = 4, reps: int = 1,
-                  enc=None, dec=None, voc=None, E: Optional[int] = None, num_mels: int = 80, hop: int = 300,
+                  enc=None, dec=None, voc=None, E: Optional[int] = None, num_mels: Optional[int] = None, hop: int = 300,
                   chain: bool = False, num_phonemes: Optional[int] = None) -> dict:
-    """enc=(ids, puncts, style), dec=(hidden[T,E], style), voc=mel[T,80].  Returns outputs + timings.
+    """enc=(ids, puncts, style), dec=(hidden[T,E], style), voc=mel[T,M].  Returns outputs + timings.  The mel is T rows of the
+    checkpoint's audio.num_mels (what the reference writes); num_mels, if given, is a check of it.
     chain=True: dec / voc inputs come from the previous stage (their input arrays may be None)."""
     if not have_reference():
         raise RuntimeError("oracle/_ref/zvref not built (run `make -C oracle ref` where /root/reference exists)")
@@ -258,7 +287,11 @@ def run_reference(gguf_path: str, *, N: Optional[int] = None, T: Optional[int] =
             out["energy_bucket"] = np.fromfile(td + "/enc.energy_bucket.i32", np.int32)
             out["n_frames"] = int(np.fromfile(td + "/enc.nframes.i32", np.int32)[0])
         if dec is not None:
-            out["mel"] = np.fromfile(td + "/mel_out", np.float32).reshape(-1, num_mels)
+            mel = np.fromfile(td + "/mel_out", np.float32)
+            if T is None or mel.size % T:
+                raise RuntimeError(f"zvref wrote {mel.size} mel values for T = {T}")
+            Oracle._agree("num_mels", num_mels, mel.size // T)
+            out["mel"] = mel.reshape(T, -1)
         if voc is not None or chain:
             out["wav"] = np.fromfile(td + "/wav_out", np.float32)
     return out

@@ -7,6 +7,7 @@ Run in the build container only (it needs /root/reference to have been compiled 
     python tests/golden/make_golden.py heads    (only the encoder head-count fixture)
     python tests/golden/make_golden.py value_ranges    (only the value-range stage fixture)
     python tests/golden/make_golden.py resblock_geometries    (only the residual-block tap-count fixture)
+    python tests/golden/make_golden.py encdec_geometries    (only the encoder / decoder width, FFN tap and mel-count fixture)
 Fixtures hold inputs' *recipes* (geometry, seeds — inputs are regenerated bit-identically by
 zerovox.cpp_amd/synth.py) and the reference's OUTPUTS: in full for the small geometries, as strided
 samples + SHA-256 of the full f32 buffer for the full-size configs of BASELINE.json.  ISA of the
@@ -407,6 +408,37 @@ def resblock_geometries_case(tmp="/tmp"):
     np.savez_compressed(os.path.join(HERE, "resblock_geometries_T%d.npz" % RB_T), **out)
 
 
+ED_N, ED_T_ENC, ED_T = 16, 160, 24       # phonemes and frames of the encoder, frames of the decoder -> vocoder chain
+
+
+def encdec_geometries_case(tmp="/tmp"):
+    """The reference on every geometry of synth.ENCDEC_GEOMETRIES (other widths E, FFN tap counts, predictor widths V, layer and
+    mel counts): the encoder on ED_N phonemes (log-durations, energies, buckets and frame count in full; features / hidden as
+    SHA-256 — the reference's float pitch tensor is recycled by ggml's allocator before the harness reads it), the decoder on
+    ED_T frames of synth.decoder_hidden and the vocoder on that mel (SHA-256 + strided samples)."""
+    out = dict(geometries=np.array(synth.ENCDEC_GEOMETRIES), seed_w=SEED_W, N=ED_N, T_enc=ED_T_ENC, T=ED_T, seed_enc=5,
+               seed_hidden=11, seed_style=5, stride=STRIDE)
+    for gname in synth.ENCDEC_GEOMETRIES:
+        g = synth.GEOMETRIES[gname]
+        path = os.path.join(tmp, f"golden_{gname}.gguf")
+        synth.write_checkpoint(path, g, SEED_W)
+        ids, puncts, style = synth.encoder_inputs(g, 5, ED_N)
+        e = zvoracle.run_reference(path, T=ED_T_ENC, N=ED_N, enc=(ids, puncts, style), E=g.E)
+        for name in ("logdur", "energy", "pitch_bucket", "energy_bucket", "n_frames"):
+            out[f"{gname}/{name}"] = e[name]
+        out[gname + "/features_sha256"], out[gname + "/hidden_sha256"] = sha(e["features"]), sha(e["hidden"])
+        hid = synth.decoder_hidden(g, 11, ED_T)
+        mel = zvoracle.run_reference(path, T=ED_T, dec=(hid, synth.encoder_inputs(g, 5, 8)[2]))["mel"]
+        assert mel.shape == (ED_T, g.num_mels)
+        wav = zvoracle.run_reference(path, T=ED_T, voc=mel)["wav"]
+        out.update({gname + "/mel_sha256": sha(mel), gname + "/mel_samples": mel.reshape(-1)[::STRIDE].copy(),
+                    gname + "/wav_sha256": sha(wav), gname + "/wav_samples": wav[::STRIDE].copy()})
+        print(f"{gname}: frames {e['n_frames']}, mel rms {float(np.sqrt(np.mean(mel.astype(np.float64) ** 2))):.3f}, "
+              f"wav rms {float(np.sqrt(np.mean(wav.astype(np.float64) ** 2))):.4f}")
+        os.remove(path)
+    np.savez_compressed(os.path.join(HERE, "encdec_geometries_N%d_T%d.npz" % (ED_N, ED_T)), **out)
+
+
 if __name__ == "__main__":
     if not zvoracle.have_reference():
         sys.exit("oracle/_ref/zvref missing: run `make -C oracle ref` first")
@@ -418,6 +450,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["resblock_geometries"]:     # only the residual-block tap-count fixture
         resblock_geometries_case()
+        sys.exit(0)
+    if sys.argv[1:] == ["encdec_geometries"]:       # only the encoder / decoder geometry fixture
+        encdec_geometries_case()
         sys.exit(0)
     if sys.argv[1:] == ["heads"]:           # only the encoder head-count fixture
         heads_cases()
@@ -437,3 +472,4 @@ if __name__ == "__main__":
     heads_cases()
     value_ranges_case()
     resblock_geometries_case()
+    encdec_geometries_case()

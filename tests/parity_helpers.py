@@ -2,7 +2,14 @@
 import numpy as np
 
 
-def encoder_decisions_vs_reference(e, z, nb, T):
+def near_flips(flip):
+    """tokens within two rows of a flipped pitch bucket (the energy predictor sees two k = 3 convs of x + pitch embedding).  Also
+    for fewer than 5 tokens, where np.convolve(mode="same") returns the longer operand's length"""
+    n = len(flip)
+    return np.convolve(flip.astype(np.int32), np.ones(5, np.int32), mode="full")[2:2 + n] > 0
+
+
+def encoder_decisions_vs_reference(e, z, nb, T, count_energy_near_pitch=True):
     """Integer decisions of the encoder against a reference fixture, gated on the reference semantics' OWN re-association noise
     (tests/golden/make_golden.py add_encoder_margins: our oracle in sequential-f32 order against the reference, stored per
     fixture) — no hand-written tolerance:
@@ -11,7 +18,9 @@ def encoder_decisions_vs_reference(e, z, nb, T):
       * every flipped decision moved by ONE step and sat, in the reference, no further from its rounding boundary than 2 x the
         floor of the value it rounds (a flip elsewhere is an error, not noise); an energy flip may instead sit within two rows of
         a pitch flip;
-      * no more flips than 2 x the floor's own count + 2."""
+      * no more flips than 2 x the floor's own count + 2 (count_energy_near_pitch=False: energy flips within two rows of a pitch
+        flip, which the pitch flip explains, are not counted — for short runs of a wide energy embedding, where one pitch flip
+        moves up to five energy buckets)."""
     N = len(z["logdur"])
     f_ld, f_p, f_e = float(z["floor_logdur_max"]), float(z["floor_pitch_max"]), float(z["floor_energy_max"])
     ld_err = float(np.max(np.abs(e["logdur"] - z["logdur"])))
@@ -22,7 +31,7 @@ def encoder_decisions_vs_reference(e, z, nb, T):
     dflip = dur_g != dur_r
     pflip = e["pitch_bucket"] != z["pitch_bucket"]
     eflip = e["energy_bucket"] != z["energy_bucket"]
-    near = np.convolve(pflip.astype(np.int32), np.ones(5, np.int32), mode="same") > 0
+    near = near_flips(pflip)
     e_err = float(np.max(np.abs(e["energy"][~near] - z["energy"][~near]))) if (~near).any() else 0.0
     print(f"   N={N}: logdur err {ld_err:.2e} (floor {f_ld:.2e}), pitch err {p_err:.2e} ({f_p:.2e}), energy err away from pitch flips "
           f"{e_err:.2e} ({f_e:.2e}); flips dur {int(dflip.sum())} (floor {int(z['floor_dur_flips'])}) pitch {int(pflip.sum())} "
@@ -41,7 +50,7 @@ def encoder_decisions_vs_reference(e, z, nb, T):
     assert np.all(tie[eflip] | near[eflip]), "an energy bucket flipped away from a boundary and away from any pitch flip"
     assert int(dflip.sum()) <= 2 * int(z["floor_dur_flips"]) + 2
     assert int(pflip.sum()) <= 2 * int(z["floor_pitch_flips"]) + 2
-    assert int(eflip.sum()) <= 2 * int(z["floor_energy_flips"]) + 2
+    assert int((eflip if count_energy_near_pitch else eflip & ~near).sum()) <= 2 * int(z["floor_energy_flips"]) + 2
     assert min(e["n_frames"], int(z["n_frames"])) == T or abs(e["n_frames"] - int(z["n_frames"])) <= int(dflip.sum())
     return int(dflip.sum()), int(pflip.sum()), int(eflip.sum())
 
@@ -418,3 +427,43 @@ def receptive_radius(g, tensors):
         a, b = a - (k_in - 1) // 2, b + (k_in - 1) // 2
         worst = max(worst, -a, b)
     return worst
+
+
+# ---- decoder conv tile split (tests/test_gpu_encdec_geometries.py, tests/test_boundary_cpu.py) ------------------------------
+# restated from zerovox.cpp_amd/csrc/conv_gemm.hip (conv_gemm_groups / conv_gemm_tiles): a wide conv of a batch runs whole groups
+# of 8 32-channel output tiles on conv_gemm_kernel, which also takes ONE leftover tile; two or more leftovers run on
+# conv1d_mfma_kernel from tile nt_begin = conv_gemm_tiles on (conv.hip launch_conv)
+
+def conv_gemm_groups(cout_p):
+    return ((cout_p + 31) // 32) // 8
+
+
+def conv_gemm_tiles(cout_p):
+    nt = (cout_p + 31) // 32
+    ng = nt // 8
+    return ng * 8 + (1 if nt - ng * 8 == 1 and ng >= 1 else 0)
+
+
+def conv_tile_split(cout):
+    """(tiles, tiles on conv_gemm_kernel, tiles left to the generic kernel) of a decoder conv of cout channels"""
+    cout_p = (cout + 15) // 16 * 16
+    nt = (cout_p + 31) // 32
+    done = conv_gemm_tiles(cout_p)
+    return nt, done, nt - done
+
+
+def encoder_margins(ex, alt):
+    """the reference semantics' own re-association noise on one encoder run, in the form encoder_decisions_vs_reference reads:
+    ex = the oracle in the reference's summation order (bit-exact to it: tests/test_oracle_golden.py), alt = the oracle in
+    sequential f32 order (as tests/golden/make_golden.py _encoder_margins, computed live)"""
+    dur_r = np.exp(ex["logdur"].astype(np.float64)) - 1 + 0.5
+    dur_a = np.exp(alt["logdur"].astype(np.float64)) - 1 + 0.5
+    pflip = alt["pitch_bucket"] != ex["pitch_bucket"]
+    clean = ~near_flips(pflip)
+    return dict(logdur=ex["logdur"], pitch=ex["pitch"], energy=ex["energy"], pitch_bucket=ex["pitch_bucket"],
+                energy_bucket=ex["energy_bucket"], n_frames=ex["n_frames"],
+                floor_logdur_max=float(np.max(np.abs(alt["logdur"] - ex["logdur"]))),
+                floor_pitch_max=float(np.max(np.abs(alt["pitch"] - ex["pitch"]))),
+                floor_energy_max=float(np.max(np.abs(alt["energy"][clean] - ex["energy"][clean]))) if clean.any() else 0.0,
+                floor_dur_flips=int(np.sum(dur_r.astype(np.int64) != dur_a.astype(np.int64))),
+                floor_pitch_flips=int(pflip.sum()), floor_energy_flips=int(np.sum(alt["energy_bucket"] != ex["energy_bucket"])))

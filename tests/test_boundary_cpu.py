@@ -222,3 +222,40 @@ def test_receptive_radius_of_the_vocoder_geometries(ckpt):
         _, g, tensors = ckpt(name)
         assert receptive_radius(g, tensors) == r, name
         assert halo_from_convs1_d0(g, tensors) == 23, name
+
+
+def test_encdec_geometries_reach_what_they_claim(ckpt):
+    """synth.ENCDEC_GEOMETRIES: every one is legal for the loader (E % 16 == 0, H divides E, odd FFN taps, num_mels % 16 == 0) and
+    splits its decoder convs (E and 2E output channels) over conv_gemm_kernel and the generic kernel as synth.py says — e576 / e720
+    / e304 leave 2 / 4, 7 / 5 and 2 / 3 tiles at nt_begin > 0 (medium's 17 / 33 tiles leave one, which the GEMM takes; e1024's
+    none); e576's head dim is the matrix-core attention's widest, e720's V turns the LayerNorm tails off alone.  And the tensors
+    carry the KVs' shapes"""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from parity_helpers import conv_tile_split
+    from zerovox_cpp_amd import synth
+    ATT_NS_MAX, LN_TAIL_MAX = 144, 64 * 12             # misc_kernels.hip
+    split = {"medium": ((17, 17, 0), (33, 33, 0)), "medium_e576": ((18, 16, 2), (36, 32, 4)),
+             "medium_e720": ((23, 16, 7), (45, 40, 5)), "small_e304": ((10, 8, 2), (19, 16, 3)),
+             "medium_e1024": ((32, 32, 0), (64, 64, 0))}
+    assert set(split) == {"medium", *synth.ENCDEC_GEOMETRIES}
+    for name, want in split.items():
+        g = synth.GEOMETRIES[name]
+        E, H = g.E, g.encoder_head
+        assert E % 16 == 0 and E % H == 0 and g.num_mels % 16 == 0, name
+        assert all(k % 2 == 1 for k in g.conv_kernel_size), name
+        assert (conv_tile_split(E), conv_tile_split(2 * E)) == want, name
+    g = synth.GEOMETRIES["medium_e576"]
+    assert g.E // g.encoder_head == 2 * ATT_NS_MAX
+    g = synth.GEOMETRIES["medium_e720"]
+    assert g.E <= LN_TAIL_MAX < g.vp_filter_size and g.num_mels > 256 and g.E % 32 == 16 and g.num_mels % 32 == 16
+    assert synth.GEOMETRIES["medium_e1024"].E > LN_TAIL_MAX
+    g = synth.GEOMETRIES["small_e304"]
+    assert g.encoder_layer == 1 and g.conv_filter_size % 16 != 0 and g.conv_kernel_size == (1, 5)
+    for name in synth.ENCDEC_GEOMETRIES:
+        _, g, t = ckpt(name)
+        assert t["_pe._enc.laystk.0.pos_ffn.w_1.w"].shape == (g.conv_filter_size, g.E, g.conv_kernel_size[0]), name
+        assert t["_pe._enc.laystk.0.pos_ffn.w_2.w"].shape == (g.E, g.conv_filter_size, g.conv_kernel_size[1]), name
+        assert t["_mel_decoder.to_out.0.w"].shape == (g.num_mels, g.E, 1) and t["_meldec.input_conv.w"].shape[1] == g.num_mels
+        assert f"_pe._enc.laystk.{g.encoder_layer}.pos_ffn.w_1.w" not in t, name
+    assert synth.GEOMETRIES["medium_m100"].num_mels % 16 and synth.GEOMETRIES["medium_ffn8"].conv_kernel_size[0] % 2 == 0

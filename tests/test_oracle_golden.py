@@ -307,3 +307,42 @@ def test_oracle_resblock_geometries(ckpt):
             assert np.array_equal(cw[::s], z["chain_wav_samples"]) and sha(cw) == str(z["chain_wav_sha256"])
             if zvoracle.have_reference():
                 assert sha(zvoracle.run_reference(path, T=T, dec=(hid, style))["mel"]) == str(z["chain_mel_sha256"])
+
+
+def test_oracle_encdec_geometries(ckpt):
+    """the oracle on checkpoints of other widths, FFN tap counts, predictor widths and mel counts (synth.ENCDEC_GEOMETRIES: E = 576 /
+    720 / 304 / 1 024, FFN taps (3, 3) / (17, 1) / (1, 5), V = 784, one encoder layer, 128 / 272 / 16 mels) against the reference's
+    encoder, decoder and vocoder outputs (tests/golden/encdec_geometries_N16_T24.npz) bit for bit; every shape it runs comes from the
+    checkpoint (a num_mels or FFN tap count given that disagrees raises); and live against oracle/_ref where it is present"""
+    from zerovox_cpp_amd import synth
+    from oracle import zvoracle
+    z = np.load(os.path.join(GOLD, "encdec_geometries_N16_T24.npz"))
+    N, T_enc, T, s = int(z["N"]), int(z["T_enc"]), int(z["T"]), int(z["stride"])
+    assert tuple(str(n) for n in z["geometries"]) == synth.ENCDEC_GEOMETRIES
+    for gname in synth.ENCDEC_GEOMETRIES:
+        path, g, tensors = ckpt(gname, int(z["seed_w"]))
+        orc = zvoracle.Oracle(tensors)
+        assert orc.num_mels == g.num_mels and orc.ffn_taps == tuple(g.conv_kernel_size), gname
+        ids, puncts, style = synth.encoder_inputs(g, int(z["seed_enc"]), N)
+        e = orc.encoder(g, ids, puncts, style, T_enc)
+        for name in ("logdur", "energy", "pitch_bucket", "energy_bucket"):
+            assert np.array_equal(e[name], z[f"{gname}/{name}"]), (gname, name)
+        assert e["n_frames"] == int(z[gname + "/n_frames"]), gname
+        assert sha(e["features"]) == str(z[gname + "/features_sha256"]) and sha(e["hidden"]) == str(z[gname + "/hidden_sha256"]), gname
+        hid = synth.decoder_hidden(g, int(z["seed_hidden"]), T)
+        dstyle = synth.encoder_inputs(g, int(z["seed_style"]), 8)[2]
+        mel = orc.decoder(hid, dstyle)
+        assert mel.shape == (T, g.num_mels), gname
+        assert np.array_equal(mel.reshape(-1)[::s], z[gname + "/mel_samples"]) and sha(mel) == str(z[gname + "/mel_sha256"]), gname
+        wav = orc.vocoder(mel)
+        assert np.array_equal(wav[::s], z[gname + "/wav_samples"]) and sha(wav) == str(z[gname + "/wav_sha256"]), gname
+        with pytest.raises(ValueError):
+            orc.decoder(hid, dstyle, num_mels=g.num_mels + 16)
+        with pytest.raises(ValueError):
+            orc.layer(orc.LAYER_ENC_FFN, 0, np.zeros((4, g.E), np.float32), g.E, heads=g.encoder_head, ksz=(g.conv_kernel_size[0] + 2, 1))
+        if zvoracle.have_reference():
+            r = zvoracle.run_reference(path, T=T, dec=(hid, dstyle))
+            assert r["mel"].shape == (T, g.num_mels) and sha(r["mel"]) == str(z[gname + "/mel_sha256"]), gname
+            assert sha(zvoracle.run_reference(path, T=T, voc=mel)["wav"]) == str(z[gname + "/wav_sha256"]), gname
+            r = zvoracle.run_reference(path, T=T_enc, N=N, enc=(ids, puncts, style), E=g.E)
+            assert np.array_equal(r["logdur"], e["logdur"]) and sha(r["hidden"]) == str(z[gname + "/hidden_sha256"]), gname

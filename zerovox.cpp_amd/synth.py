@@ -169,9 +169,35 @@ RESBLOCK_GEOMETRIES = ("medium_rb357", "medium_rb_wide", "medium_rb_dilk", "medi
 MEDIUM_UP4553 = Geometry(name="medium_up4553", upsample_scales=(4, 5, 5, 3), upsample_kernels=(8, 10, 10, 6))
 MEDIUM_VOCK5 = Geometry(name="medium_vock5", voc_kernel_size=5)
 
+# other encoder / decoder widths, FFN tap counts and mel counts (emb_dim + punct_emb_dim, decoder.conv_kernel_size.{0,1},
+# encoder.vp_filter_size, encoder.layer and audio.num_mels are free KVs of the checkpoint format).  A decoder conv of Cout
+# channels has ceil(Cout / 32) output tiles: batches run whole groups of 8 on conv_gemm_kernel (plus one leftover tile), two
+# or more leftovers on conv1d_mfma_kernel from tile nt_begin = 8 x groups on (conv.hip launch_conv):
+#  * e576: decoder convs of 18 / 36 tiles (GEMM 16 / 32 + 2 / 4 at nt_begin); dk = 288 = 2 x ATT_NS_MAX, the matrix-core
+#    attention's widest head, whose LDS takes at most 320 tokens (the scalar kernel above); 128 mels; a 3-tap FFN w_2 over
+#    F = 1 024 f16 channels, run per utterance;
+#  * e720: 23 / 45 tiles (7 / 5 leftover; the last tile half padding, 720 = 22.5 x 32); dk = 240; 272 mels: the vocoder input
+#    conv stages two 256-channel chunks under its (mel - mean) / scale prologue, to_out has 8.5 tiles; V = 784 > 768 turns the
+#    LayerNorm tails off by V alone; a 17-tap FFN w_1 (16 halo rows);
+#  * small_e304: 10 / 19 tiles (GEMM 8 / 16 + 2 / 3); one encoder layer; 16 mels; the FFN's f16 operand has padded columns
+#    (200 -> 208) and a 1-tap w_1 / 5-tap w_2
+MEDIUM_E576 = Geometry(name="medium_e576", emb_dim=560, encoder_head=2, num_mels=128, conv_kernel_size=(3, 3))
+MEDIUM_E720 = Geometry(name="medium_e720", emb_dim=704, encoder_head=3, num_mels=272, conv_kernel_size=(17, 1), vp_filter_size=784)
+SMALL_E304 = Geometry(name="small_e304", emb_dim=272, punct_emb_dim=32, conv_filter_size=200, conv_kernel_size=(1, 5),
+                      encoder_layer=1, encoder_head=2, vp_filter_size=64, ve_n_bins=32, max_seq_len=256, voc_channels=128,
+                      num_mels=16)
+# (medium_e1024 above: the whole encoder with the tails off by E; decoder convs of 2 048 / 2 112 channels, GEMM groups with no
+# leftover)
+ENCDEC_GEOMETRIES = ("medium_e576", "medium_e720", "small_e304", "medium_e1024")
+
+# checkpoints the loader refuses: 100 mels (the loader requires num_mels % 16 == 0; the reference does not) and an 8-tap FFN
+# conv (not a 'same' conv)
+MEDIUM_M100 = Geometry(name="medium_m100", num_mels=100)
+MEDIUM_FFN8 = Geometry(name="medium_ffn8", conv_kernel_size=(8, 1))
+
 GEOMETRIES = {g.name: g for g in (MEDIUM, TINY, SMALL, MEDIUM8, MEDIUM_H1, MEDIUM_H3, MEDIUM_H4, MEDIUM_H8, MEDIUM_E1024,
                                   MEDIUM_RB357, MEDIUM_RB_WIDE, MEDIUM_RB_DILK, MEDIUM_RB_C1C2, MEDIUM_RB_C2WIDE, MEDIUM_UP4553,
-                                  MEDIUM_VOCK5)}
+                                  MEDIUM_VOCK5, MEDIUM_E576, MEDIUM_E720, SMALL_E304, MEDIUM_M100, MEDIUM_FFN8)}
 
 
 def sinusoid_table(n_position: int, d_hid: int) -> np.ndarray:
