@@ -11,6 +11,8 @@
  *   zv_decode          <- StyleTTSDecoder::eval               src/zerovox.h:323, src/stylettsdec.cpp:457-470
  *   zv_vocode          <- HiFiGAN::eval                       src/zerovox.h:378, src/hifigan.cpp:358-377
  *   zv_synthesize      <- ZeroVOXModel::eval                  src/zerovox.cpp:198-335 (three stages back to back)
+ *   *_prosody          the same with per-utterance duration / pitch / energy controls (zv_prosody)
+ *   *_phonemes         the same with per-phoneme controls as well (zv_phoneme_controls) and the phoneme timings out
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file        src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -104,6 +106,42 @@ typedef struct
     float energy_scale, energy_shift;   /* the same for energy */
 } zv_prosody;                           /* identity: {1, 1, 0, 1, 0} */
 
+/* ---- per-phoneme controls (forced durations, local rate, local pitch / energy) and phoneme timings -------------------------
+ * One struct per utterance; every pointer is [n] (the utterance's phoneme count) or NULL = no control of that kind, so a
+ * zero-initialised struct is the identity.  They act after the utterance's zv_prosody (NULL prosody = its identity).  All
+ * arithmetic is f32, every step rounded separately:
+ *   duration, for token i < num_phonemes:
+ *     1. dur = (float)(exp((double)logdur) - 1.0)
+ *     2. dur = dur * prosody.duration_scale                      (if prosody is given)
+ *     3. dur = dur * duration_scale[i]                           (if given)
+ *     4. d = (int)((double)dur + 0.5), clamped to [0, T]
+ *     5. if duration_frames[i] >= 0: d = min(duration_frames[i], T)
+ *     tokens at or past num_phonemes keep d = 0, even when a duration is forced for them
+ *   pitch, for every token i < n:
+ *     1. p = pred
+ *     2. p = p * prosody.pitch_scale; p = p + prosody.pitch_shift
+ *     3. p = p + pitch_shift[i]
+ *     4. p = p * (float)(nbins - 1)
+ *     5. bucket = (int)((double)p + 0.5), clamped to [0, nbins - 1]
+ *   energy:   the same steps with energy_scale / energy_shift / energy_shift[i]
+ * The identity values (frames -1, scale 1, shift 0), NULL pointers and a NULL struct give exactly the bits of the same call
+ * without per-phoneme controls (x * 1.0f and x + 0.0f are exact; a -0.0 may become +0.0, which lands in the same bucket).
+ * Taps: logdur, pitch and energy stay RAW; buckets, features, hidden, n_frames and durations are the controlled values.
+ * Timings: durations[i] = min(cum_i, T) - min(cum_{i-1}, T), cum the running sum of d (cum_{-1} = 0): the frames phoneme i
+ * occupies in hidden, starting at start_i = durations[0] + ... + durations[i-1]; its samples in wav are
+ * [hop * start_i, hop * (start_i + durations[i])).  The durations sum to n_frames; phonemes cut off by T get the part that
+ * fits, or 0.
+ * Validation: ZV_ERR_ARG before any work is enqueued when a duration_frames[i] < -1 or > min(32768, zv_max_frames()), a
+ * duration_scale[i] is not finite or outside (0, 16], or a shift is not finite (the message names the utterance index, the
+ * field and the phoneme index). */
+typedef struct
+{
+    const int32_t *duration_frames;     /* -1: keep the (scaled) prediction; 0..32768: phoneme i lasts exactly this many frames */
+    const float   *duration_scale;      /* > 0, <= 16: multiplies phoneme i's duration after the utterance's duration_scale     */
+    const float   *pitch_shift;         /* added to phoneme i's pitch prediction after the utterance's scale / shift           */
+    const float   *energy_shift;        /* the same for energy                                                                  */
+} zv_phoneme_controls;
+
 /* ---- the hot path: host buffers in / out, synchronous (same protocol as the reference) ---- */
 /* ids[n], puncts[n] i32; style[E] f32; hidden[T*E] f32 frame-major, zero-padded tail; returns the
  * regulator's frame count in *n_frames (may be NULL).  Optional taps (NULL to skip): logdur[n],
@@ -121,6 +159,11 @@ zv_status zv_encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts,
 zv_status zv_encode_taps_prosody(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
                                  uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
                                  float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody);
+/* zv_encode_taps_prosody with per-phoneme controls (NULL = none) and the phoneme timings durations[n] (NULL to skip) */
+zv_status zv_encode_taps_phonemes(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
+                                  uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
+                                  float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody,
+                                  const zv_phoneme_controls *phonemes, int32_t *durations);
 /* hidden[T*E], style[E] -> mel[T*num_mels] frame-major */
 zv_status zv_decode(zv_model *m, const float *hidden, const float *style, uint32_t T, float *mel);
 /* mel[T*num_mels] -> wav[T*hop_size] */
@@ -142,6 +185,10 @@ zv_status zv_synthesize(zv_model *m, const int32_t *ids, const int32_t *puncts, 
 /* zv_synthesize with prosody controls (NULL = identity: the bits of zv_synthesize) */
 zv_status zv_synthesize_prosody(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
                                 float *wav, uint32_t *n_frames, const zv_prosody *prosody);
+/* zv_synthesize_prosody with per-phoneme controls (NULL = none) and the phoneme timings durations[n] (NULL to skip) */
+zv_status zv_synthesize_phonemes(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                                 float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                 int32_t *durations);
 
 /* n_utt independent utterances, each with its own (n_phonemes[u], T[u]): bit for bit the result of n_utt zv_synthesize
  * calls (no batch padding: padding would change the numbers, SURVEY Appx C-H2).  Up to 64 utterances / 64 Ki frames go
@@ -161,6 +208,14 @@ zv_status zv_synthesize_batch(zv_model *m, uint32_t n_utt, const int32_t *const 
 zv_status zv_synthesize_batch_prosody(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
                                       const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
                                       float *const *wav, uint32_t *n_frames, const zv_prosody *prosody);
+/* the same with per-phoneme controls, phonemes[n_utt] (NULL = none for all; each struct is [n_phonemes[u]]), and the phoneme
+ * timings, durations[n_utt] (NULL to skip; each entry [n_phonemes[u]] or NULL).  The rows travel in the batch's device input
+ * block like the prosody rows, so a replayed graph reads new values; utterance u gives the bits and the durations of
+ * zv_synthesize_phonemes(..., &prosody[u], &phonemes[u], durations[u]). */
+zv_status zv_synthesize_batch_phonemes(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                       const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                       float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                       const zv_phoneme_controls *phonemes, int32_t *const *durations);
 
 /* The two halves of zv_synthesize_batch for a serving loop that keeps a batch in flight per lane (additive):
  * _begin builds the input block, enqueues the upload, the kernels and the waveform downloads of ONE launch group (at most
@@ -179,6 +234,12 @@ zv_status zv_synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, 
 zv_status zv_synthesize_batch_begin_prosody(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
                                             const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
                                             const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody);
+/* _begin with per-phoneme controls and timings (as zv_synthesize_batch_phonemes): the controls are read before the call returns;
+ * _end fills durations[u], whose buffers must stay valid until then */
+zv_status zv_synthesize_batch_begin_phonemes(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                             const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                             const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                             const zv_phoneme_controls *phonemes, int32_t *const *durations);
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel

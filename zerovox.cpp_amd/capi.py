@@ -21,7 +21,8 @@ SYMBOLS = [
     "zv_memcpy_h2d", "zv_memcpy_d2h", "zv_vocode_device", "zv_vocode_stream", "zv_vocoder_halo_frames", "zv_decode_device", "zv_synchronize", "zv_set_graph_mode",
     "zv_profile_begin", "zv_profile_end", "zv_write_wav", "zv_gguf_inspect", "zv_max_frames", "zv_demo_utterance", "zv_debug_layer", "zv_debug_set",
     "zv_debug_get", "zv_batch_timeline", "zv_encode_taps_prosody", "zv_synthesize_prosody", "zv_synthesize_batch_prosody",
-    "zv_synthesize_batch_begin_prosody",
+    "zv_synthesize_batch_begin_prosody", "zv_encode_taps_phonemes", "zv_synthesize_phonemes", "zv_synthesize_batch_phonemes",
+    "zv_synthesize_batch_begin_phonemes",
 ]
 
 
@@ -59,6 +60,55 @@ def _prosody(p) -> Optional[Prosody]:
     if isinstance(p, dict):
         return Prosody(**p)
     return Prosody(*p)
+
+
+class PhonemeControlsC(C.Structure):
+    """zv_phoneme_controls of include/zerovox_amd.h: four pointers, each [n] or NULL (a zeroed struct is the identity)"""
+    _fields_ = [("duration_frames", C.c_void_p), ("duration_scale", C.c_void_p), ("pitch_shift", C.c_void_p),
+                ("energy_shift", C.c_void_p)]
+
+
+PHONEME_FIELDS = (("duration_frames", np.int32), ("duration_scale", np.float32), ("pitch_shift", np.float32),
+                  ("energy_shift", np.float32))
+
+
+class PhonemeControls:
+    """Per-phoneme controls of one utterance of n phonemes: a dict (or keywords) of arrays [n], or None per field (no control of
+    that kind).  .struct is the zv_phoneme_controls the C calls read; the converted arrays are kept alive here for the call."""
+
+    def __init__(self, n: int, controls: Optional[dict] = None, **fields):
+        d = dict(controls or {})
+        d.update(fields)
+        names = [name for name, _ in PHONEME_FIELDS]
+        unknown = sorted(set(d) - set(names))
+        if unknown:
+            raise ValueError(f"unknown phoneme control(s) {unknown}; known: {names}")
+        self.n = int(n)
+        self.arrays = {}
+        self.struct = PhonemeControlsC()
+        for name, dt in PHONEME_FIELDS:
+            v = d.get(name)
+            if v is None:
+                continue
+            a = np.ascontiguousarray(v, dtype=dt)
+            if a.ndim != 1 or a.shape[0] != self.n:
+                raise ValueError(f"{name}: shape {a.shape}, the utterance has {self.n} phonemes")
+            self.arrays[name] = a
+            setattr(self.struct, name, a.ctypes.data)
+
+    def __repr__(self):
+        return f"PhonemeControls(n={self.n}, fields={sorted(self.arrays)})"
+
+
+def _phoneme_controls(p, n: int) -> Optional[PhonemeControls]:
+    """None, a PhonemeControls for n phonemes or a dict of its fields -> PhonemeControls / None"""
+    if p is None:
+        return None
+    if isinstance(p, PhonemeControls):
+        if p.n != n:
+            raise ValueError(f"PhonemeControls for {p.n} phonemes, the utterance has {n}")
+        return p
+    return PhonemeControls(n, p)
 
 
 class KernelStat(C.Structure):
@@ -114,6 +164,11 @@ def load_library(path: Optional[str] = None):
     lib.zv_synthesize_prosody.argtypes = lib.zv_synthesize.argtypes + [pp]
     lib.zv_synthesize_batch_prosody.argtypes = lib.zv_synthesize_batch.argtypes + [pp]
     lib.zv_synthesize_batch_begin_prosody.argtypes = lib.zv_synthesize_batch_begin.argtypes + [pp]
+    pc = C.POINTER(PhonemeControlsC)
+    lib.zv_encode_taps_phonemes.argtypes = lib.zv_encode_taps_prosody.argtypes + [pc, i32p]
+    lib.zv_synthesize_phonemes.argtypes = lib.zv_synthesize_prosody.argtypes + [pc, i32p]
+    lib.zv_synthesize_batch_phonemes.argtypes = lib.zv_synthesize_batch_prosody.argtypes + [pc, C.POINTER(vp)]
+    lib.zv_synthesize_batch_begin_phonemes.argtypes = lib.zv_synthesize_batch_begin_prosody.argtypes + [pc, C.POINTER(vp)]
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -284,9 +339,12 @@ class Model:
     def max_frames(self) -> int:
         return int(self.lib.zv_max_frames(self.h))
 
-    def encode(self, ids, puncts, style, T: int, num_phonemes: Optional[int] = None, prosody=None) -> dict:
+    def encode(self, ids, puncts, style, T: int, num_phonemes: Optional[int] = None, prosody=None, phonemes=None,
+               return_durations: bool = False) -> dict:
         """num_phonemes < len(ids): all ids are encoded, the length regulator walks the first num_phonemes (FS2Encoder::eval).
-        prosody (Prosody, dict or 5-sequence): zv_encode_taps_prosody; None: zv_encode_taps"""
+        prosody (Prosody, dict or 5-sequence): zv_encode_taps_prosody; None: zv_encode_taps.
+        phonemes (PhonemeControls or dict of arrays [len(ids)]) or return_durations: zv_encode_taps_phonemes, and the result gains
+        "durations" (the phoneme timings, int32 [len(ids)])"""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
@@ -299,15 +357,22 @@ class Model:
                 C.byref(nf), _ptr(out["features"]), _ptr(out["logdur"]), _ptr(out["pitch"]), _ptr(out["energy"]),
                 _ptr(out["pitch_bucket"]), _ptr(out["energy_bucket"]))
         pr = _prosody(prosody)
-        if pr is None:
+        if phonemes is not None or return_durations:
+            pc = _phoneme_controls(phonemes, N)
+            out["durations"] = np.empty(N, np.int32)
+            self._chk(self.lib.zv_encode_taps_phonemes(*args, None if pr is None else C.byref(pr),
+                                                       None if pc is None else C.byref(pc.struct), _ptr(out["durations"])))
+        elif pr is None:
             self._chk(self.lib.zv_encode_taps(*args))
         else:
             self._chk(self.lib.zv_encode_taps_prosody(*args, C.byref(pr)))
         out["n_frames"] = int(nf.value)
         return out
 
-    def synthesize(self, ids, puncts, style, T: int, prosody=None):
-        """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize"""
+    def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False):
+        """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
+        arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
+        as a third element"""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
@@ -315,22 +380,32 @@ class Model:
         nf = C.c_uint32(0)
         args = (self.h, _ptr(ids), _ptr(puncts), _ptr(style), len(ids), T, _ptr(wav), C.byref(nf))
         pr = _prosody(prosody)
-        if pr is None:
+        if phonemes is not None or return_durations:
+            pc = _phoneme_controls(phonemes, len(ids))
+            dur = np.empty(len(ids), np.int32) if return_durations else None
+            self._chk(self.lib.zv_synthesize_phonemes(*args, None if pr is None else C.byref(pr),
+                                                      None if pc is None else C.byref(pc.struct), _ptr(dur)))
+            if return_durations:
+                return wav, int(nf.value), dur
+        elif pr is None:
             self._chk(self.lib.zv_synthesize(*args))
         else:
             self._chk(self.lib.zv_synthesize_prosody(*args, C.byref(pr)))
         return wav, int(nf.value)
 
-    def prepare_batch(self, utterances) -> "BatchCall":
+    def prepare_batch(self, utterances, durations: bool = False) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
         buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list"""
-        return BatchCall(self, utterances)
+        return BatchCall(self, utterances, durations)
 
-    def synthesize_batch(self, utterances):
-        """utterances: list of (ids, puncts, style, T[, prosody]) -> list of (wav, n_frames); each utterance keeps its own (N, T)
-        and, with a fifth element, its own prosody controls (None: identity)"""
-        call = BatchCall(self, utterances)
+    def synthesize_batch(self, utterances, return_durations: bool = False):
+        """utterances: list of (ids, puncts, style, T[, prosody[, phonemes]]) -> list of (wav, n_frames); each utterance keeps its
+        own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its per-phoneme controls
+        (PhonemeControls, dict of arrays or None).  return_durations: (wav, n_frames, durations) tuples"""
+        call = BatchCall(self, utterances, return_durations)
         call.run()
+        if return_durations:
+            return [r + (d,) for r, d in zip(call.results(), call.durations)]
         return call.results()
 
     # ---- device-resident API ----
@@ -384,11 +459,14 @@ class Model:
 
 
 class BatchCall:
-    """utterances: (ids, puncts, style, T) or (ids, puncts, style, T, prosody) tuples.  When any utterance carries a prosody
-    (the others get the identity) the _prosody entry points are called with the array .prosody, which set_prosody() rewrites
-    in place: the next run() / begin() uses the new values with the same buffers (a captured graph replays with them)."""
+    """utterances: (ids, puncts, style, T), (ids, puncts, style, T, prosody) or (ids, puncts, style, T, prosody, phonemes)
+    tuples.  When any utterance carries a prosody (the others get the identity) the _prosody entry points are called with the
+    array .prosody, which set_prosody() rewrites in place: the next run() / begin() uses the new values with the same buffers (a
+    captured graph replays with them).  When any utterance carries per-phoneme controls, or durations=True, the _phonemes entry
+    points are called with the array .phonemes (set_phoneme_controls() rewrites an entry) and .durations[i] holds utterance i's
+    phoneme timings after run() / end()."""
 
-    def __init__(self, model: Model, utterances):
+    def __init__(self, model: Model, utterances, durations: bool = False):
         self.model = model
         n = self.n = len(utterances)
         self.keep, self.wavs = [], []
@@ -408,6 +486,22 @@ class BatchCall:
             self.wavs.append(w)
             self.ids_p[i], self.pun_p[i], self.sty_p[i], self.wav_p[i] = a.ctypes.data, b.ctypes.data, c.ctypes.data, w.ctypes.data
             self.Ns[i], self.Ts[i] = len(a), T
+        pcs = [_phoneme_controls(u[5], len(u[0])) if len(u) > 5 else None for u in utterances]
+        self.phonemes = self.durations = self.dur_p = None
+        self.pkeep = pcs
+        if durations or any(p is not None for p in pcs):
+            self.phonemes = (PhonemeControlsC * n)(*[p.struct if p is not None else PhonemeControlsC() for p in pcs])
+            self.durations = [np.zeros(int(self.Ns[i]), np.int32) for i in range(n)]
+            self.dur_p = P(*[d.ctypes.data for d in self.durations])
+
+    def set_phoneme_controls(self, i: int, controls):
+        """utterance i's per-phoneme controls (PhonemeControls, dict of arrays or None) for the following run() / begin() (the call
+        must have been built with per-phoneme controls or durations=True)"""
+        if self.phonemes is None:
+            raise ValueError("this BatchCall was built without per-phoneme controls")
+        pc = _phoneme_controls(controls, int(self.Ns[i]))
+        self.pkeep[i] = pc
+        self.phonemes[i] = pc.struct if pc is not None else PhonemeControlsC()
 
     def set_prosody(self, i: int, prosody):
         """utterance i's controls for the following run() / begin() (the call must have been built with controls)"""
@@ -418,7 +512,9 @@ class BatchCall:
     def run(self):
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        if self.prosody is None:
+        if self.phonemes is not None:
+            m._chk(m.lib.zv_synthesize_batch_phonemes(*args, self.prosody, self.phonemes, self.dur_p))
+        elif self.prosody is None:
             m._chk(m.lib.zv_synthesize_batch(*args))
         else:
             m._chk(m.lib.zv_synthesize_batch_prosody(*args, self.prosody))
@@ -427,7 +523,9 @@ class BatchCall:
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        if self.prosody is None:
+        if self.phonemes is not None:
+            m._chk(m.lib.zv_synthesize_batch_begin_phonemes(*args, self.prosody, self.phonemes, self.dur_p))
+        elif self.prosody is None:
             m._chk(m.lib.zv_synthesize_batch_begin(*args))
         else:
             m._chk(m.lib.zv_synthesize_batch_begin_prosody(*args, self.prosody))

@@ -158,21 +158,78 @@ static void prosody_rows(const zv_prosody *p, uint32_t n_utt, float *rows)
     }
 }
 
+// Per-phoneme controls (zv_phoneme_controls) -> the kernels' layout, f32 [token row][zv::PCTL_STRIDE] (kernels.h PCTL_*).  Checked
+// like check_prosody: ZV_ERR_ARG names the utterance, the field and the phoneme.
+static bool has_phoneme_controls(const zv_phoneme_controls *p)
+{
+    return p && (p->duration_frames || p->duration_scale || p->pitch_shift || p->energy_shift);
+}
+
+static void check_phoneme_controls(const Model &M, const zv_phoneme_controls *p, uint32_t u, uint32_t n)
+{
+    if (!p) return;
+    const int64_t fmax = std::min<int64_t>(32768, M.max_frames_per_utterance());      // forced frames travel as exact f32 integers
+    for (uint32_t i = 0; i < n; i++)
+    {
+        if (p->duration_frames && (p->duration_frames[i] < -1 || p->duration_frames[i] > fmax))
+            zv::fail(ZV_ERR_ARG, "utterance %u: duration_frames[%u] = %d is outside [-1, %lld]", u, i, p->duration_frames[i], (long long)fmax);
+        if (p->duration_scale)
+        {
+            const float v = p->duration_scale[i];
+            if (!std::isfinite(v)) zv::fail(ZV_ERR_ARG, "utterance %u: duration_scale[%u] = %g is not finite", u, i, (double)v);
+            if (!(v > 0.0f && v <= 16.0f)) zv::fail(ZV_ERR_ARG, "utterance %u: duration_scale[%u] = %g is outside (0, 16]", u, i, (double)v);
+        }
+        if (p->pitch_shift && !std::isfinite(p->pitch_shift[i]))
+            zv::fail(ZV_ERR_ARG, "utterance %u: pitch_shift[%u] = %g is not finite", u, i, (double)p->pitch_shift[i]);
+        if (p->energy_shift && !std::isfinite(p->energy_shift[i]))
+            zv::fail(ZV_ERR_ARG, "utterance %u: energy_shift[%u] = %g is not finite", u, i, (double)p->energy_shift[i]);
+    }
+}
+
+// n rows; p may be null or hold null fields: those rows / fields get the identity {-1, 1, 0, 0}
+static void phoneme_rows(const zv_phoneme_controls *p, uint32_t n, float *rows)
+{
+    for (uint32_t i = 0; i < n; i++)
+    {
+        float *r = rows + (size_t)i * zv::PCTL_STRIDE;
+        r[zv::PCTL_FRAMES] = p && p->duration_frames ? (float)p->duration_frames[i] : -1.0f;
+        r[zv::PCTL_DURATION] = p && p->duration_scale ? p->duration_scale[i] : 1.0f;
+        r[zv::PCTL_PITCH] = p && p->pitch_shift ? p->pitch_shift[i] : 0.0f;
+        r[zv::PCTL_ENERGY] = p && p->energy_shift ? p->energy_shift[i] : 0.0f;
+    }
+}
+
+// the phoneme timings: durations[i] = min(cum[i], T) - min(cum[i - 1], T), the frames token i occupies in hidden
+static void durations_from_cum(const int32_t *cum, uint32_t n, uint32_t T, int32_t *durations)
+{
+    int64_t prev = 0;
+    for (uint32_t i = 0; i < n; i++)
+    {
+        const int64_t c = std::min<int64_t>(cum[i], T);
+        durations[i] = (int32_t)(c - prev);
+        prev = c;
+    }
+}
+
 static void encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t num_phonemes,
                         uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur, float *pitch, float *energy,
-                        int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody, const char *fn)
+                        int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody, const char *fn,
+                        const zv_phoneme_controls *phonemes = nullptr, int32_t *durations = nullptr)
 {
     if (!(m && ids && puncts && style && hidden)) zv::fail(ZV_ERR_ARG, "%s: null argument", fn);
     if (!(n > 0)) zv::fail(ZV_ERR_ARG, "%s: n must be > 0", fn);
     if (!(num_phonemes <= n)) zv::fail(ZV_ERR_ARG, "%s: num_phonemes exceeds n", fn);
     check_prosody(prosody, 1);
+    check_phoneme_controls(*m->m, phonemes, 0, n);
+    const bool pctl = has_phoneme_controls(phonemes);
     Model &M = *m->m;
     use_lane0(m);
     check_T(M, T);
     check_ids(M, ids, puncts, n);
     const size_t E = M.E();
     const size_t b_ids = (size_t)n * 4, b_sty = E * 4, b_hid = (size_t)T * E * 4;
-    char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + 1024 + (prosody ? 256 : 0));
+    const size_t b_pctl = pctl ? (((size_t)n * zv::PCTL_STRIDE * 4 + 255) & ~(size_t)255) : 0;
+    char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + 1024 + (prosody || pctl ? 256 : 0) + b_pctl);
     int32_t *d_nf = (int32_t *)io;
     io += 256;
     int32_t *d_ids = (int32_t *)io, *d_pun = (int32_t *)(io + b_ids);
@@ -190,6 +247,15 @@ static void encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts, 
         ZV_HIP(hipMemcpyAsync(d_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, M.stream));
         bt.d_ctl = d_ctl;
     }
+    std::vector<float> prow;                     // lives until the M.sync() below
+    if (pctl)
+    {
+        float *d_pctl = (float *)((char *)d_hid + ((b_hid + 255) & ~(size_t)255) + 256);
+        prow.resize((size_t)n * zv::PCTL_STRIDE);
+        phoneme_rows(phonemes, n, prow.data());
+        ZV_HIP(hipMemcpyAsync(d_pctl, prow.data(), prow.size() * 4, hipMemcpyHostToDevice, M.stream));
+        bt.d_pctl = d_pctl;
+    }
     Model::EncoderTaps t = M.encode_dev(bt, d_ids, d_pun, d_sty, d_hid, d_nf);
     ZV_HIP(hipMemcpyAsync(hidden, d_hid, b_hid, hipMemcpyDeviceToHost, M.stream));
     int32_t nf = 0;
@@ -200,8 +266,11 @@ static void encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts, 
     if (energy) ZV_HIP(hipMemcpyAsync(energy, t.energy, b_ids, hipMemcpyDeviceToHost, M.stream));
     if (pitch_bucket) ZV_HIP(hipMemcpyAsync(pitch_bucket, t.pitch_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
     if (energy_bucket) ZV_HIP(hipMemcpyAsync(energy_bucket, t.energy_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
+    std::vector<int32_t> cum(durations ? n : 0);
+    if (durations) ZV_HIP(hipMemcpyAsync(cum.data(), t.cum, b_ids, hipMemcpyDeviceToHost, M.stream));
     M.sync();
     if (n_frames) *n_frames = (uint32_t)nf;
+    if (durations) durations_from_cum(cum.data(), n, T, durations);
 }
 
 zv_status zv_encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
@@ -221,6 +290,17 @@ zv_status zv_encode_taps_prosody(zv_model *m, const int32_t *ids, const int32_t 
     return guarded([&] {
         encode_taps(m, ids, puncts, style, n, num_phonemes, T, hidden, n_frames, features, logdur, pitch, energy, pitch_bucket,
                     energy_bucket, prosody, __func__);
+    });
+}
+
+zv_status zv_encode_taps_phonemes(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
+                                  uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
+                                  float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody,
+                                  const zv_phoneme_controls *phonemes, int32_t *durations)
+{
+    return guarded([&] {
+        encode_taps(m, ids, puncts, style, n, num_phonemes, T, hidden, n_frames, features, logdur, pitch, energy, pitch_bucket,
+                    energy_bucket, prosody, __func__, phonemes, durations);
     });
 }
 
@@ -328,9 +408,11 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
 }
 
 // one utterance end to end on the currently selected lane; no host synchronisation.  ctl_host: the utterance's control row
-// (prosody_rows) or null; like the other host buffers it must stay valid until the caller synchronises
+// (prosody_rows) or null; pctl_host: its n per-phoneme rows (phoneme_rows) or null; cum_host: receives the length regulator's
+// scan (int32 [n]) or null.  Like the other host buffers they must stay valid until the caller synchronises
 static void synthesize_enqueue(Model &M, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
-                               float *wav, int32_t *nf_host, const float *ctl_host = nullptr)
+                               float *wav, int32_t *nf_host, const float *ctl_host = nullptr, const float *pctl_host = nullptr,
+                               int32_t *cum_host = nullptr)
 {
     check_ids(M, ids, puncts, n);
     check_T(M, T);
@@ -339,7 +421,8 @@ static void synthesize_enqueue(Model &M, const int32_t *ids, const int32_t *punc
     const size_t b_ids = al((size_t)n * 4), b_sty = al(E * 4), b_hid = al((size_t)T * E * 4), b_mel = al((size_t)T * Mm * 4),
                  b_wav = al((size_t)T * hop * 4);
     M.reserve(n, T);
-    char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + b_mel + b_wav + (ctl_host ? al(zv::CTL_STRIDE * 4) : 0));
+    const size_t b_ctl = ctl_host ? al(zv::CTL_STRIDE * 4) : 0, b_pctl = pctl_host ? al((size_t)n * zv::PCTL_STRIDE * 4) : 0;
+    char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + b_mel + b_wav + b_ctl + b_pctl + (cum_host ? b_ids : 0));
     int32_t *d_nf = (int32_t *)io;
     io += 256;
     int32_t *d_ids = (int32_t *)io, *d_pun = (int32_t *)(io + b_ids);
@@ -355,8 +438,16 @@ static void synthesize_enqueue(Model &M, const int32_t *ids, const int32_t *punc
         ZV_HIP(hipMemcpyAsync(d_ctl, ctl_host, zv::CTL_STRIDE * 4, hipMemcpyHostToDevice, M.stream));
         bt.d_ctl = d_ctl;
     }
+    if (pctl_host)
+    {
+        float *d_pctl = (float *)((char *)d_wav + b_wav + b_ctl);
+        ZV_HIP(hipMemcpyAsync(d_pctl, pctl_host, (size_t)n * zv::PCTL_STRIDE * 4, hipMemcpyHostToDevice, M.stream));
+        bt.d_pctl = d_pctl;
+    }
+    if (cum_host) bt.d_cum = (int32_t *)((char *)d_wav + b_wav + b_ctl + b_pctl);
     M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
     ZV_HIP(hipMemcpyAsync(nf_host, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
+    if (cum_host) ZV_HIP(hipMemcpyAsync(cum_host, bt.d_cum, (size_t)n * 4, hipMemcpyDeviceToHost, M.stream));
     ZV_HIP(hipMemcpyAsync(wav, d_wav, (size_t)T * hop * 4, hipMemcpyDeviceToHost, M.stream));
 }
 
@@ -390,6 +481,35 @@ zv_status zv_synthesize_prosody(zv_model *m, const int32_t *ids, const int32_t *
         synthesize_enqueue(M, ids, puncts, style, n, T, wav, &nf, prosody ? ctl : nullptr);
         M.sync();
         if (n_frames) *n_frames = (uint32_t)nf;
+    });
+}
+
+zv_status zv_synthesize_phonemes(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                                 float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                 int32_t *durations)
+{
+    return guarded([&] {
+        ZV_NEED(m && ids && puncts && style && wav, "null argument");
+        ZV_NEED(n > 0 && T > 0, "n and T must be > 0");
+        check_prosody(prosody, 1);
+        Model &M = *m->m;
+        check_phoneme_controls(M, phonemes, 0, n);
+        use_lane0(m);
+        int32_t nf = 0;
+        float ctl[zv::CTL_STRIDE];
+        if (prosody) prosody_rows(prosody, 1, ctl);
+        std::vector<float> prow;
+        if (has_phoneme_controls(phonemes))
+        {
+            prow.resize((size_t)n * zv::PCTL_STRIDE);
+            phoneme_rows(phonemes, n, prow.data());
+        }
+        std::vector<int32_t> cum(durations ? n : 0);
+        synthesize_enqueue(M, ids, puncts, style, n, T, wav, &nf, prosody ? ctl : nullptr, prow.empty() ? nullptr : prow.data(),
+                           durations ? cum.data() : nullptr);
+        M.sync();
+        if (n_frames) *n_frames = (uint32_t)nf;
+        if (durations) durations_from_cum(cum.data(), n, T, durations);
     });
 }
 
@@ -434,6 +554,10 @@ struct PendingBatch
     const char           *h_wav = nullptr;
     const int32_t        *h_nf = nullptr;
     size_t                hop = 0;
+    // phoneme timings (zv_synthesize_batch_begin_phonemes): the regulator's scan lands in h_cum, packed utterance after utterance
+    std::vector<uint32_t> N;
+    std::vector<int32_t *> dur;
+    const int32_t        *h_cum = nullptr;
 };
 static PendingBatch &pending_slot(zv_model *m, int lane)
 {
@@ -460,10 +584,11 @@ static void use_lane0(zv_model *m)
     m->m->select_lane(0);
 }
 
-// prosody[n_utt] or null (checked by the caller)
+// prosody[n_utt], phonemes[n_utt] or null (checked by the caller); durations[n_utt] or null, entries may be null
 static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
                           const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
-                          uint32_t *n_frames, const zv_prosody *prosody)
+                          uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes = nullptr,
+                          int32_t *const *durations = nullptr)
 {
     Model &M = *m->m;
     PendingBatch &pb = pending_slot(m, lane);
@@ -471,11 +596,15 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    uint32_t nmax = 0, tmax = 0;
+    uint32_t nmax = 0, tmax = 0, ntot = 0;
+    bool pctl = false, want_dur = false;
     for (uint32_t u = 0; u < n_utt; u++)
     {
         nmax = std::max(nmax, n_phonemes[u]);
         tmax = std::max(tmax, T[u]);
+        ntot += n_phonemes[u];
+        pctl = pctl || (phonemes && has_phoneme_controls(&phonemes[u]));
+        want_dur = want_dur || (durations && durations[u]);
     }
     zv::Batch bt;
     bt.nseg = (int)n_utt;
@@ -484,23 +613,29 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
     bt.t_max = zv::round_up((int)tmax, 64);
     bt.n_rows = (size_t)bt.nseg * bt.n_max;
     bt.t_rows = (size_t)bt.nseg * bt.t_max;
-    // device block: [frame counts][inputs: token table | frame table | ids | puncts | styles | controls][hidden][mel][wav]
+    // device block: [frame counts][inputs: token table | frame table | ids | puncts | styles | controls | phoneme controls][hidden]
+    // [mel][wav][scan]
     // (tables: one entry per utterance + one that spans all of them, see Batch::tokens_merged; controls: only with prosody, one
-    // zv::CTL_STRIDE row per utterance — uploaded with the rest, so a replayed graph reads the values of this call)
+    // zv::CTL_STRIDE row per utterance; phoneme controls: only with per-phoneme controls, one zv::PCTL_STRIDE row per token row —
+    // uploaded with the rest, so a replayed graph reads the values of this call; scan: only when timings are asked for, the
+    // length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
     const size_t b_tab = al((size_t)(bt.nseg + 1) * sizeof(zv::Seg)), b_ids = al(bt.n_rows * 4), b_sty = al((size_t)bt.nseg * E * 4);
     const size_t b_ctl = prosody ? al((size_t)bt.nseg * zv::CTL_STRIDE * 4) : 0;
-    const size_t b_in = 2 * b_tab + 2 * b_ids + b_sty + b_ctl;
+    const size_t b_pctl = pctl ? al(bt.n_rows * zv::PCTL_STRIDE * 4) : 0;
+    const size_t b_in = 2 * b_tab + 2 * b_ids + b_sty + b_ctl + b_pctl;
     const size_t b_nf = al((size_t)bt.nseg * 4), b_hid = al(bt.t_rows * E * 4), b_mel = al(bt.t_rows * Mm * 4),
-                 b_wav = al(bt.t_rows * hop * 4);
+                 b_wav = al(bt.t_rows * hop * 4), b_cum = want_dur ? b_ids : 0;
     M.reserve_batch(bt);
-    char *io = (char *)M.io_scratch(b_nf + b_in + b_hid + b_mel + b_wav);
+    char *io = (char *)M.io_scratch(b_nf + b_in + b_hid + b_mel + b_wav + b_cum);
     int32_t *d_nf = (int32_t *)io;
     char *d_in = io + b_nf;
     zv::Seg *d_tok = (zv::Seg *)d_in, *d_frm = (zv::Seg *)(d_in + b_tab);
     int32_t *d_ids = (int32_t *)(d_in + 2 * b_tab), *d_pun = (int32_t *)(d_in + 2 * b_tab + b_ids);
     float *d_sty = (float *)(d_in + 2 * b_tab + 2 * b_ids);
     if (prosody) bt.d_ctl = (const float *)(d_in + 2 * b_tab + 2 * b_ids + b_sty);
+    if (pctl) bt.d_pctl = (const float *)(d_in + 2 * b_tab + 2 * b_ids + b_sty + b_ctl);
     float *d_hid = (float *)(d_in + b_in), *d_mel = (float *)((char *)d_hid + b_hid), *d_wav = (float *)((char *)d_mel + b_mel);
+    if (want_dur) bt.d_cum = (int32_t *)((char *)d_wav + b_wav);
     bt.d_tok = d_tok;
     bt.d_frm = d_frm;
     // pinned mirror of the input block + landing area of the results
@@ -511,7 +646,7 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
         pb.woff[u] = wav_bytes;
         wav_bytes += (size_t)T[u] * hop * 4;
     }
-    char *pin = (char *)M.pinned_scratch(b_in + b_nf + al(wav_bytes));
+    char *pin = (char *)M.pinned_scratch(b_in + b_nf + al(wav_bytes) + b_cum);
     {
         zv::Seg *h_tok = (zv::Seg *)pin, *h_frm = (zv::Seg *)(pin + b_tab);
         int32_t *h_ids = (int32_t *)(pin + 2 * b_tab), *h_pun = (int32_t *)(pin + 2 * b_tab + b_ids);
@@ -531,9 +666,13 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
         h_tok[n_utt] = zv::Seg{0, n0, n0, 0};
         h_frm[n_utt] = zv::Seg{0, t0, 0, 0};
         if (prosody) prosody_rows(prosody, n_utt, (float *)(pin + 2 * b_tab + 2 * b_ids + b_sty));
+        if (pctl)           // the utterances' rows, packed like the token table (rows past them are never read)
+            for (uint32_t u = 0, r = 0; u < n_utt; r += n_phonemes[u], u++)
+                phoneme_rows(&phonemes[u], n_phonemes[u], (float *)(pin + 2 * b_tab + 2 * b_ids + b_sty + b_ctl) + (size_t)r * zv::PCTL_STRIDE);
     }
     int32_t *h_nf = (int32_t *)(pin + b_in);
     char *h_wav = pin + b_in + b_nf;
+    int32_t *h_cum = want_dur ? (int32_t *)(h_wav + al(wav_bytes)) : nullptr;
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
     // run.  Same kernels on the same rows: same bits.
@@ -560,6 +699,7 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, pin, d_in, b_in);
             ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream));
             ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream));
+            if (want_dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream));
             ZV_HIP(hipMemcpyAsync(h_wav, d_wav, wav_bytes, hipMemcpyDeviceToHost, M.stream));
             ZV_HIP(hipEventRecord(M.tail_event(1), M.stream));
         }
@@ -567,6 +707,7 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
         {
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, pin, d_in, b_in, 1);
             ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream));
+            if (want_dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream));
             for (int g = 1; g < G; g++)               // contiguous groups of about wav_bytes / G each
             {
                 uint32_t u = pb.gb[g - 1] + 1;
@@ -601,6 +742,10 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
     pb.h_wav = h_wav;
     pb.h_nf = h_nf;
     pb.hop = hop;
+    pb.h_cum = h_cum;
+    pb.N.assign(n_phonemes, n_phonemes + n_utt);
+    if (want_dur) pb.dur.assign(durations, durations + n_utt);
+    else pb.dur.clear();
 }
 
 static void batch_finish(zv_model *m, int lane)
@@ -629,10 +774,14 @@ static void batch_finish(zv_model *m, int lane)
     pb.active = false;
     if (pb.n_frames)
         for (uint32_t u = 0; u < pb.n_utt; u++) pb.n_frames[u] = (uint32_t)pb.h_nf[u];
+    if (pb.h_cum)
+        for (uint32_t u = 0, r = 0; u < pb.n_utt; r += pb.N[u], u++)
+            if (pb.dur[u]) durations_from_cum(pb.h_cum + r, pb.N[u], pb.T[u], pb.dur[u]);
 }
 
 static void batch_check(Model &M, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts, const float *const *styles,
-                        const uint32_t *n_phonemes, const uint32_t *T, float *const *wav, const zv_prosody *prosody)
+                        const uint32_t *n_phonemes, const uint32_t *T, float *const *wav, const zv_prosody *prosody,
+                        const zv_phoneme_controls *phonemes = nullptr)
 {
     check_prosody(prosody, n_utt);
     for (uint32_t u = 0; u < n_utt; u++)
@@ -643,6 +792,7 @@ static void batch_check(Model &M, uint32_t n_utt, const int32_t *const *ids, con
         if (n_phonemes[u] > M.max_phonemes())
             zv::fail(ZV_ERR_ARG, "utterance %u: %u phonemes exceed the %u rows of the sinusoid table", u, n_phonemes[u], M.max_phonemes());
         check_ids(M, ids[u], puncts[u], n_phonemes[u]);
+        if (phonemes) check_phoneme_controls(M, &phonemes[u], u, n_phonemes[u]);
     }
 }
 
@@ -662,11 +812,12 @@ static uint32_t batch_group_end(uint32_t a, uint32_t n_utt, const uint32_t *T)
 
 static void synthesize_batch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
                              const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
-                             uint32_t *n_frames, const zv_prosody *prosody)
+                             uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes = nullptr,
+                             int32_t *const *durations = nullptr)
 {
     Model &M = *m->m;
     ZV_HIP(hipSetDevice(M.device));
-    batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav, prosody);
+    batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav, prosody, phonemes);
     // Groups of up to 64 utterances / 64 Ki frames go through the chain as ONE launch per kernel: every tensor is
     // the row concatenation of the group, the segment tables tell the kernels where each utterance starts and ends.
     // Capacities are rounded up so that batches of similar shape replay the same captured graph.
@@ -675,7 +826,7 @@ static void synthesize_batch(zv_model *m, uint32_t n_utt, const int32_t *const *
     {
         const uint32_t b = batch_group_end(a, n_utt, T);
         batch_enqueue(m, 0, b - a, ids + a, puncts + a, styles + a, n_phonemes + a, T + a, wav + a, n_frames ? n_frames + a : nullptr,
-                      prosody ? prosody + a : nullptr);
+                      prosody ? prosody + a : nullptr, phonemes ? phonemes + a : nullptr, durations ? durations + a : nullptr);
         batch_finish(m, 0);
         a = b;
     }
@@ -703,17 +854,18 @@ zv_status zv_synthesize_batch_prosody(zv_model *m, uint32_t n_utt, const int32_t
 
 static void synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
                                    const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
-                                   uint32_t *n_frames, const zv_prosody *prosody, const char *fn)
+                                   uint32_t *n_frames, const zv_prosody *prosody, const char *fn,
+                                   const zv_phoneme_controls *phonemes = nullptr, int32_t *const *durations = nullptr)
 {
     if (!(m && ids && puncts && styles && n_phonemes && T && wav)) zv::fail(ZV_ERR_ARG, "%s: null argument", fn);
     if (!(lane < ZV_BATCH_LANES)) zv::fail(ZV_ERR_ARG, "%s: lane out of range", fn);
     if (!(n_utt > 0)) zv::fail(ZV_ERR_ARG, "%s: empty batch", fn);
     Model &M = *m->m;
     ZV_HIP(hipSetDevice(M.device));
-    batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav, prosody);
+    batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav, prosody, phonemes);
     if (batch_group_end(0, n_utt, T) != n_utt)
         zv::fail(ZV_ERR_ARG, "%s: an asynchronous batch must fit one launch group (64 utterances, 64 Ki frames of capacity)", fn);
-    batch_enqueue(m, (int)lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody);
+    batch_enqueue(m, (int)lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody, phonemes, durations);
 }
 
 zv_status zv_synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
@@ -731,6 +883,28 @@ zv_status zv_synthesize_batch_begin_prosody(zv_model *m, uint32_t lane, uint32_t
 {
     return guarded([&] {
         synthesize_batch_begin(m, lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody, __func__);
+    });
+}
+
+zv_status zv_synthesize_batch_phonemes(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                       const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                       uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                       int32_t *const *durations)
+{
+    return guarded([&] {
+        ZV_NEED(m && ids && puncts && styles && n_phonemes && T && wav, "null argument");
+        synthesize_batch(m, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody, phonemes, durations);
+    });
+}
+
+zv_status zv_synthesize_batch_begin_phonemes(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                             const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                             const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                             const zv_phoneme_controls *phonemes, int32_t *const *durations)
+{
+    return guarded([&] {
+        synthesize_batch_begin(m, lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody, __func__, phonemes,
+                               durations);
     });
 }
 

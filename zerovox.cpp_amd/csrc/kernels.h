@@ -299,6 +299,13 @@ constexpr int CTL_STRIDE = 8;
 constexpr int CTL_DURATION = 0;        // duration_scale
 constexpr int CTL_PITCH = 1;           // pitch_scale, pitch_shift
 constexpr int CTL_ENERGY = 3;          // energy_scale, energy_shift
+// Per-phoneme controls (include/zerovox_amd.h zv_phoneme_controls): f32 [token row][PCTL_STRIDE], indexed by ABSOLUTE token row (so
+// the batch's segments, tokens_merged() and the inline single segment index them alike).  A null pctl is the uncontrolled path.
+constexpr int PCTL_STRIDE = 4;
+constexpr int PCTL_FRAMES = 0;         // forced frames, -1 = none (integers up to 32768 are exact in f32)
+constexpr int PCTL_DURATION = 1;       // duration scale, after the utterance's
+constexpr int PCTL_PITCH = 2;          // pitch shift, after the utterance's scale / shift
+constexpr int PCTL_ENERGY = 3;         // energy shift
 
 // y = LayerNorm(x + res) * w + b  over the C real channels (res may be null); channels [C, Cp) are zeroed
 hipError_t launch_add_layernorm(hipStream_t s, const float *x, int ldx, const float *res, int ldr, int C, int Cp,
@@ -308,25 +315,30 @@ hipError_t launch_add_layernorm(hipStream_t s, const float *x, int ldx, const fl
 //   pred[row] = dot(y[row][:C], dot_w) + dot_b[0]           (launch_rowdot's chain)
 //   bucket[row] = clamp((int)(pred * (nbins - 1) + 0.5)); feat[row][:embC] += emb[bucket][:]   (launch_bucket_embed_add; needs dot_w)
 //     ctl (or null): pred -> pred * ctl[seg][ctl_field] + ctl[seg][ctl_field + 1] before the bucket (pred itself is stored raw)
+//     pctl (or null): per-phoneme rows offset to their field (PCTL_PITCH / PCTL_ENERGY): then pred -> pred + pctl[row * PCTL_STRIDE]
 // layernorm_tail_ok(C): the tail exists in the rows-in-registers form only (C <= 768)
 bool       layernorm_tail_ok(int C);
 hipError_t launch_layernorm_tail(hipStream_t s, const float *x, int ldx, const float *res, int ldr, int C, int Cp, const float *w,
                                  const float *b, float eps, float *y, int ldy, const Segs &segs, const float *post, int post_seg,
                                  const float *dot_w, const float *dot_b, float *pred, const float *emb, int nbins, int embC, float *feat,
-                                 int ldf, int32_t *bucket, const float *ctl = nullptr, int ctl_field = 0);
+                                 int ldf, int32_t *bucket, const float *ctl = nullptr, int ctl_field = 0,
+                                 const float *pctl = nullptr);
 // x[row][:] += v[segment][:]
 hipError_t launch_add_rowvec(hipStream_t s, float *x, int ld, int C, const float *v, int v_seg, const Segs &segs);
 // pred[n] = dot(x[n][:], w) + b
 hipError_t launch_rowdot(hipStream_t s, const float *x, int ld, int C, const float *w, const float *b, float *y, const Segs &segs);
 // bucket[n] = clamp((int)(pred*(nbins-1) + 0.5), 0, nbins-1); x[n][:] += emb[bucket[n]][:]
 //   ctl (or null): pred -> pred * ctl[seg][ctl_field] + ctl[seg][ctl_field + 1] first
+//   pctl (or null): per-phoneme rows offset to their field, then pred -> pred + pctl[n * PCTL_STRIDE]
 hipError_t launch_bucket_embed_add(hipStream_t s, const float *pred, int nbins, const float *emb, int C, float *x, int ld,
-                                   int32_t *bucket, const Segs &segs, const float *ctl = nullptr, int ctl_field = 0);
+                                   int32_t *bucket, const Segs &segs, const float *ctl = nullptr, int ctl_field = 0,
+                                   const float *pctl = nullptr);
 // device length regulator: rounded durations of the first `aux` tokens of a segment -> inclusive scan (cum[], one int
 // per token row) -> gather into the segment's frames, zero tail; n_frames[segment] = frames
 //   ctl (or null): each duration is multiplied by ctl[seg][CTL_DURATION] (f32) before it is rounded
+//   pctl (or null): then by pctl[row][PCTL_DURATION]; after rounding, pctl[row][PCTL_FRAMES] >= 0 replaces d by min(frames, T)
 hipError_t launch_length_regulator(hipStream_t s, const float *feat, int ld, const float *logdur, int C, float *hidden,
                                    int ldh, int32_t *cum, int32_t *n_frames, const Segs &tokens, const Segs &frames,
-                                   const float *ctl = nullptr);
+                                   const float *ctl = nullptr, const float *pctl = nullptr);
 
 }  // namespace zv

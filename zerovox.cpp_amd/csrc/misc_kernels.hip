@@ -927,6 +927,8 @@ hipError_t launch_attention(hipStream_t s, const float *q, const float *k, const
 //   emb    : bucket[row] = clamp((int)((double)(pred * (nbins - 1)) + 0.5)); feat[row][:] += emb[bucket][:]   (:442-474, 565-569)
 //   ctl    : prosody control of the bucket step (kernels.h CTL_*): pred * ctl[seg][ctl_field] + ctl[seg][ctl_field + 1] is bucketed
 //            instead of pred (pred is stored raw); null = the uncontrolled path
+//   pctl   : per-phoneme control of the bucket step (kernels.h PCTL_*), rows offset to their field: pctl[row * PCTL_STRIDE] is added
+//            after the ctl step; null = no per-phoneme control
 struct LnTail
 {
     const float *post;
@@ -940,6 +942,7 @@ struct LnTail
     int32_t     *bucket;
     const float *ctl;
     int          ctl_field;
+    const float *pctl;
 };
 
 template <bool TAIL>
@@ -1043,6 +1046,7 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const float *__restr
                     p = p * cv[0];
                     p = p + cv[1];
                 }
+                if (tail.pctl) p = p + tail.pctl[row * PCTL_STRIDE];
                 p = p * (float)bin_max;
                 int yb = (int)((double)p + 0.5);          // truncating cast of x + 0.5 (double), not round-half-even
                 yb = yb < 0 ? 0 : (yb > bin_max ? bin_max : yb);
@@ -1091,12 +1095,12 @@ bool layernorm_tail_ok(int C) { return C <= 64 * 12; }
 hipError_t launch_layernorm_tail(hipStream_t s, const float *x, int ldx, const float *res, int ldr, int C, int Cp, const float *w,
                                  const float *b, float eps, float *y, int ldy, const Segs &segs, const float *post, int post_seg,
                                  const float *dot_w, const float *dot_b, float *pred, const float *emb, int nbins, int embC, float *feat,
-                                 int ldf, int32_t *bucket, const float *ctl, int ctl_field)
+                                 int ldf, int32_t *bucket, const float *ctl, int ctl_field, const float *pctl)
 {
     if (!layernorm_tail_ok(C)) return hipErrorInvalidValue;        // the tail lives in the rows-in-registers form
     if (emb && (!dot_w || !feat || !bucket || nbins < 1)) return hipErrorInvalidValue;
     if (dot_w && (!dot_b || !pred)) return hipErrorInvalidValue;
-    if (ctl && !emb) return hipErrorInvalidValue;
+    if ((ctl || pctl) && !emb) return hipErrorInvalidValue;
     LnTail tail;
     tail.post = post;
     tail.post_seg = post_seg;
@@ -1111,6 +1115,7 @@ hipError_t launch_layernorm_tail(hipStream_t s, const float *x, int ldx, const f
     tail.bucket = bucket;
     tail.ctl = ctl;
     tail.ctl_field = ctl_field;
+    tail.pctl = pctl;
     hipLaunchKernelGGL(add_layernorm_kernel<true>, dim3((segs.max_rows + 3) / 4, segs.nseg), dim3(256), 0, s, x, ldx, res, ldr, C, Cp, w, b,
                        eps, y, ldy, segs, tail);
     return hipGetLastError();
@@ -1154,9 +1159,10 @@ hipError_t launch_rowdot(hipStream_t s, const float *x, int ld, int C, const flo
 
 // ggml_zv_mul_clamp_to_i32 + get_rows + add (reference src/fs2encoder.cpp:442-474,565-569)
 // ctl (or null): the prosody control, p * ctl[seg][ctl_field] + ctl[seg][ctl_field + 1] is bucketed (kernels.h CTL_*)
+// pctl (or null): the per-phoneme control, rows offset to their field: p + pctl[n * PCTL_STRIDE] is bucketed (kernels.h PCTL_*)
 __global__ void bucket_embed_add_kernel(const float *__restrict__ pred, int nbins, const float *__restrict__ emb, int C,
                                         float *__restrict__ x, int ld, int32_t *__restrict__ bucket, const Segs segs,
-                                        const float *__restrict__ ctl, int ctl_field)
+                                        const float *__restrict__ ctl, int ctl_field, const float *__restrict__ pctl)
 {
     const Seg sg = seg_at(segs, blockIdx.y);
     if ((int)blockIdx.x >= sg.rows) return;
@@ -1169,6 +1175,7 @@ __global__ void bucket_embed_add_kernel(const float *__restrict__ pred, int nbin
         p = p * cv[0];
         p = p + cv[1];
     }
+    if (pctl) p = p + pctl[n * PCTL_STRIDE];
     p = p * (float)bin_max;
     int y = (int)((double)p + 0.5);          // truncating cast of x + 0.5 (double), not round-half-even
     y = y < 0 ? 0 : (y > bin_max ? bin_max : y);
@@ -1177,10 +1184,10 @@ __global__ void bucket_embed_add_kernel(const float *__restrict__ pred, int nbin
 }
 
 hipError_t launch_bucket_embed_add(hipStream_t s, const float *pred, int nbins, const float *emb, int C, float *x, int ld,
-                                   int32_t *bucket, const Segs &segs, const float *ctl, int ctl_field)
+                                   int32_t *bucket, const Segs &segs, const float *ctl, int ctl_field, const float *pctl)
 {
     hipLaunchKernelGGL(bucket_embed_add_kernel, dim3(segs.max_rows, segs.nseg), dim3(256), 0, s, pred, nbins, emb, C, x, ld, bucket,
-                       segs, ctl, ctl_field);
+                       segs, ctl, ctl_field, pctl);
     return hipGetLastError();
 }
 
@@ -1189,9 +1196,11 @@ hipError_t launch_bucket_embed_add(hipStream_t s, const float *pred, int nbins, 
 //   dur_i = (int)((float)(exp(logdur_i) - 1.0) + 0.5) for the first num_phonemes (= aux) tokens of the utterance;
 //   frame f belongs to the token whose cumulative duration first exceeds f; frames past the total (or past T) are zero.
 //   ctl (or null): the (float) duration is multiplied by ctl[seg][CTL_DURATION] before it is rounded (prosody control).
+//   pctl (or null): then by pctl[row][PCTL_DURATION]; after rounding and clamping, pctl[row][PCTL_FRAMES] >= 0 replaces the
+//   duration by min(frames, T) (per-phoneme control; row = the token's absolute row).
 __global__ __launch_bounds__(1024) void lr_scan_kernel(const float *__restrict__ logdur, int32_t *__restrict__ cum,
                                                        int32_t *__restrict__ n_frames, const Segs tokens, const Segs frames,
-                                                       const float *__restrict__ ctl)
+                                                       const float *__restrict__ ctl, const float *__restrict__ pctl)
 {
     __shared__ int buf[1024];
     const Seg tk = seg_at(tokens, blockIdx.x), fr = seg_at(frames, blockIdx.x);
@@ -1211,9 +1220,16 @@ __global__ __launch_bounds__(1024) void lr_scan_kernel(const float *__restrict__
         {
             float dur = (float)(exp((double)ld_[i]) - 1.0);
             if (ctl) dur = dur * dscale;
+            const float *pr = pctl ? pctl + ((size_t)tk.row0 + i) * PCTL_STRIDE : nullptr;
+            if (pctl) dur = dur * pr[PCTL_DURATION];
             d = (int)((double)dur + 0.5);
             if (d < 0) d = 0;
             if (d > T) d = T;          // keeps the running sum far from int overflow; frames stop at T anyway
+            if (pctl && pr[PCTL_FRAMES] >= 0.f)
+            {
+                const int forced = (int)pr[PCTL_FRAMES];
+                d = forced < T ? forced : T;
+            }
         }
         buf[tid] = d;
         __syncthreads();
@@ -1284,18 +1300,19 @@ __global__ __launch_bounds__(256) void lr_gather16_kernel(const float *__restric
 
 // Scan and gather in ONE launch for utterances of at most 1 024 tokens: every workgroup (16 frames) recomputes its utterance's
 // rounded durations and their inclusive scan in LDS — a few hundred integer operations against a launch boundary — and the first
-// workgroup of a segment also stores the scan (the `cum` tap) and the frame count.  Integer sums: any scan order, the same values.
+// workgroup of a segment also stores the scan (the `cum` tap) and the frame count, even for a segment without frames (the phoneme
+// timings are read from `cum`).  Integer sums: any scan order, the same values.  ctl / pctl: lr_scan_kernel's controls.
 __global__ __launch_bounds__(256) void lr_fused16_kernel(const float *__restrict__ feat, int ld, const float *__restrict__ logdur, int C,
                                                          float *__restrict__ hidden, int ldh, int32_t *__restrict__ cum,
                                                          int32_t *__restrict__ n_frames, const Segs tokens, const Segs frames,
-                                                         const float *__restrict__ ctl)
+                                                         const float *__restrict__ ctl, const float *__restrict__ pctl)
 {
     __shared__ int32_t lr_cs[1024];
     __shared__ int32_t lr_part[256];
     const Seg tk = seg_at(tokens, blockIdx.y), fr = seg_at(frames, blockIdx.y);
     const int f0 = blockIdx.x * 16;
     const int n = tk.rows, T = fr.rows;
-    if (f0 >= T) return;
+    if (f0 >= T && blockIdx.x != 0) return;      // workgroup 0 stores cum / n_frames whatever T is
     const int nwalk = tk.aux < n ? tk.aux : n;
     const int tid = threadIdx.x;
     const float dscale = ctl ? ctl[(size_t)blockIdx.y * CTL_STRIDE + CTL_DURATION] : 1.f;
@@ -1310,9 +1327,16 @@ __global__ __launch_bounds__(256) void lr_fused16_kernel(const float *__restrict
         {
             float dur = (float)(exp((double)logdur[tk.row0 + i]) - 1.0);
             if (ctl) dur = dur * dscale;
+            const float *pr = pctl ? pctl + ((size_t)tk.row0 + i) * PCTL_STRIDE : nullptr;
+            if (pctl) dur = dur * pr[PCTL_DURATION];
             v = (int)((double)dur + 0.5);
             if (v < 0) v = 0;
             if (v > T) v = T;
+            if (pctl && pr[PCTL_FRAMES] >= 0.f)
+            {
+                const int forced = (int)pr[PCTL_FRAMES];
+                v = forced < T ? forced : T;
+            }
         }
         tot += v;
         d[j] = tot;
@@ -1358,16 +1382,19 @@ __global__ __launch_bounds__(256) void lr_fused16_kernel(const float *__restrict
 }
 
 hipError_t launch_length_regulator(hipStream_t s, const float *feat, int ld, const float *logdur, int C, float *hidden,
-                                   int ldh, int32_t *cum, int32_t *n_frames, const Segs &tokens, const Segs &frames, const float *ctl)
+                                   int ldh, int32_t *cum, int32_t *n_frames, const Segs &tokens, const Segs &frames, const float *ctl,
+                                   const float *pctl)
 {
     if (tokens.nseg != frames.nseg || tokens.nseg < 1) return hipErrorInvalidValue;
-    if ((C & 3) == 0 && (ld & 3) == 0 && (ldh & 3) == 0 && tokens.max_rows >= 1 && tokens.max_rows <= 1024 && frames.max_rows >= 1)
+    // the fused form keeps a segment's scan in 1 024 LDS entries (4 tokens x 256 threads): longer segments take the scan + gather form
+    const bool fused_fits = tokens.max_rows >= 1 && tokens.max_rows <= 1024;
+    if ((C & 3) == 0 && (ld & 3) == 0 && (ldh & 3) == 0 && fused_fits && frames.max_rows >= 1)
     {
         hipLaunchKernelGGL(lr_fused16_kernel, dim3((frames.max_rows + 15) / 16, frames.nseg), dim3(256), 0, s, feat, ld, logdur, C, hidden,
-                           ldh, cum, n_frames, tokens, frames, ctl);
+                           ldh, cum, n_frames, tokens, frames, ctl, pctl);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(lr_scan_kernel, dim3(tokens.nseg), dim3(1024), 0, s, logdur, cum, n_frames, tokens, frames, ctl);
+    hipLaunchKernelGGL(lr_scan_kernel, dim3(tokens.nseg), dim3(1024), 0, s, logdur, cum, n_frames, tokens, frames, ctl, pctl);
     if ((C & 3) == 0 && (ld & 3) == 0 && (ldh & 3) == 0 && (size_t)tokens.max_rows * 4 <= 48 * 1024 && tokens.max_rows >= 1)
         hipLaunchKernelGGL(lr_gather16_kernel, dim3((frames.max_rows + 15) / 16, frames.nseg), dim3(256), (size_t)tokens.max_rows * 4, s,
                            feat, ld, cum, C, hidden, ldh, tokens, frames);

@@ -1311,9 +1311,9 @@ void Model::chain_dev(const Batch &b, const int32_t *d_ids, const int32_t *d_pun
         run();
         return;
     }
-    // (b.d_ctl: a controlled schedule and an uncontrolled one are different graphs)
-    const void *key[9] = {d_ids, d_puncts, d_styles, d_hidden, d_mel, d_wav, d_nframes, h2d_src, b.d_ctl};
-    run_captured(voc_part == 1 ? 2 : 1, b, key, 9, run);
+    // (b.d_ctl, b.d_pctl, b.d_cum: a controlled schedule and an uncontrolled one are different graphs)
+    const void *key[11] = {d_ids, d_puncts, d_styles, d_hidden, d_mel, d_wav, d_nframes, h2d_src, b.d_ctl, b.d_pctl, b.d_cum};
+    run_captured(voc_part == 1 ? 2 : 1, b, key, 11, run);
 }
 
 void Model::vocode_dev_graph(const Batch &b, const float *d_mel, float *d_wav)
@@ -1586,7 +1586,7 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
     t.energy = arena_.take_n<float>(n);
     t.pitch_bucket = arena_.take_n<int32_t>(n);
     t.energy_bucket = arena_.take_n<int32_t>(n);
-    t.cum = arena_.take_n<int32_t>(n);
+    t.cum = bt.d_cum ? bt.d_cum : arena_.take_n<int32_t>(n);
 
     ZV_LAUNCH("enc_embed", 8.0 * nd * Ed, 1.0 * nd * Ed,
               launch_embed(stream, d_ids, d_puncts, enc_.wemb, hp.emb_dim, enc_.pemb, hp.punct_emb_dim, enc_.posenc, x, Ed, tk));
@@ -1658,8 +1658,10 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
     // VariancePredictor::graph (:386-440): conv + relu, LayerNorm, conv + relu, LayerNorm, linear.  `emb` (pitch / energy): the
     // prediction's bucket and x += embedding[bucket] (:442-474, 565-569) follow.  With `tails` the second LayerNorm's launch also
     // does the linear layer and the bucket / embedding step (5 + 1 launches -> 4).
-    // ctl_field: the prosody control of the bucket step (kernels.h CTL_PITCH / CTL_ENERGY), used when bt.d_ctl is set
-    auto predictor = [&](const VarPred &v, float *out, const float *emb, int32_t *bucket, int ctl_field) {
+    // ctl_field / pctl_field: the prosody control of the bucket step (kernels.h CTL_PITCH / CTL_ENERGY) and the per-phoneme one
+    // (PCTL_PITCH / PCTL_ENERGY), used when bt.d_ctl / bt.d_pctl are set
+    auto predictor = [&](const VarPred &v, float *out, const float *emb, int32_t *bucket, int ctl_field, int pctl_field) {
+        const float *pctl = emb && bt.d_pctl ? bt.d_pctl + pctl_field : nullptr;
         const bool dbg_here = dbg_layer.kind == 3 && dbg_layer.index == pred_no && !dbg_layer.done;
         pred_no++;
         if (dbg_layer.done) return;
@@ -1683,7 +1685,7 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
         {
             ZV_LAUNCH("enc_layernorm", 8.0 * nd * v.V + (emb ? 12.0 * nd * Ed : 0.0), 10.0 * nd * v.V,
                       launch_layernorm_tail(stream, va, Vp, nullptr, 0, v.V, Vp, v.l2w, v.l2b, 1e-5f, vb, Vp, tk, nullptr, 0, v.lw, v.lb, out,
-                                            emb, (int)hp.encoder_ve_n_bins, Ed, x, Ed, bucket, emb ? bt.d_ctl : nullptr, ctl_field));
+                                            emb, (int)hp.encoder_ve_n_bins, Ed, x, Ed, bucket, emb ? bt.d_ctl : nullptr, ctl_field, pctl));
             return;
         }
         ZV_LAUNCH("enc_layernorm", 8.0 * nd * v.V, 8.0 * nd * v.V,
@@ -1692,15 +1694,15 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
         if (dbg_here) dbg_extract(out, 1, 1, n);
         if (emb && !dbg_layer.done)
             ZV_LAUNCH("enc_bucket_embed", 12.0 * nd * Ed, 1.0 * nd * Ed,
-                      launch_bucket_embed_add(stream, out, hp.encoder_ve_n_bins, emb, Ed, x, Ed, bucket, tk, bt.d_ctl, ctl_field));
+                      launch_bucket_embed_add(stream, out, hp.encoder_ve_n_bins, emb, Ed, x, Ed, bucket, tk, bt.d_ctl, ctl_field, pctl));
     };
-    predictor(enc_.dur, t.logdur, nullptr, nullptr, 0);
-    predictor(enc_.pitch, t.pitch, enc_.pitch_emb, t.pitch_bucket, CTL_PITCH);
+    predictor(enc_.dur, t.logdur, nullptr, nullptr, 0, 0);
+    predictor(enc_.pitch, t.pitch, enc_.pitch_emb, t.pitch_bucket, CTL_PITCH, PCTL_PITCH);
     if (dbg_layer.done) return t;
-    predictor(enc_.energy, t.energy, enc_.energy_emb, t.energy_bucket, CTL_ENERGY);      // sees the pitch-augmented features (:569-572)
+    predictor(enc_.energy, t.energy, enc_.energy_emb, t.energy_bucket, CTL_ENERGY, PCTL_ENERGY);      // sees the pitch-augmented features (:569-572)
     if (dbg_layer.done) return t;
     ZV_LAUNCH("enc_length_regulator", 4.0 * (nd + (double)bt.t_rows) * Ed, 0.0,
-              launch_length_regulator(stream, x, Ed, t.logdur, Ed, d_hidden, Ed, t.cum, d_nframes, tk, fr, bt.d_ctl));
+              launch_length_regulator(stream, x, Ed, t.logdur, Ed, d_hidden, Ed, t.cum, d_nframes, tk, fr, bt.d_ctl, bt.d_pctl));
     return t;
 }
 

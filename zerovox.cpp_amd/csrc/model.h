@@ -63,6 +63,12 @@ struct Batch
     // prosody controls, f32 [nseg][CTL_STRIDE] in HBM (kernels.h CTL_*), or null: the uncontrolled schedule.  Part of a chain
     // graph's key (chain_dev: the kernels' arguments differ); the VALUES are read at run time, so a replay picks up new ones.
     const float *d_ctl = nullptr;
+    // per-phoneme controls, f32 [n_rows][PCTL_STRIDE] in HBM indexed by absolute token row (kernels.h PCTL_*), or null; keyed and read
+    // like d_ctl
+    const float *d_pctl = nullptr;
+    // where the length regulator stores its scan (the `cum` tap, int32 [n_rows]) when it must outlive the encoder (phoneme timings of a
+    // chain: the decoder and the vocoder reuse the arena), or null: the arena
+    int32_t *d_cum = nullptr;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {

@@ -19,6 +19,7 @@
 #include <cinttypes>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/zerovox_amd.h"
 
@@ -113,6 +114,12 @@ class ZeroVOXModel
     // prosody controls (include/zerovox_amd.h zv_prosody: speaking rate, pitch, energy) for the eval() calls that follow, until
     // set again; the identity {1, 1, 0, 1, 0} gives the uncontrolled bits.  Values are checked when eval() runs (ZV_ERR_ARG).
     void set_prosody(const zv_prosody &p);
+    // per-phoneme controls (include/zerovox_amd.h zv_phoneme_controls) of the next eval() calls' utterance of n phonemes, copied; any
+    // pointer may be NULL, p == NULL clears the controls.  From the first call on, eval() also records the phoneme timings
+    // (get_durations()).  n must equal eval()'s num_phonemes (ZV_ERR_ARG otherwise).
+    void set_phoneme_controls(const zv_phoneme_controls *p, uint32_t n);
+    // the phoneme timings of the last eval() after set_phoneme_controls(): frames of each phoneme in the hidden state / waveform
+    const std::vector<int32_t> &get_durations() const { return durations; }
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
@@ -131,6 +138,12 @@ class ZeroVOXModel
     uint32_t         n_frames;
     zv_prosody       prosody;
     bool             has_prosody;
+    // per-phoneme controls (owned copies; an empty vector = that field is NULL) and the recorded timings
+    std::vector<int32_t> pc_frames;
+    std::vector<float>   pc_scale, pc_pitch, pc_energy;
+    uint32_t             pc_n = 0;
+    bool                 has_phonemes = false, record_durations = false;
+    std::vector<int32_t> durations;
 };
 
 }  // namespace ZeroVOX

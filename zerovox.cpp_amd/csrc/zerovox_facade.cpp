@@ -149,9 +149,49 @@ void ZeroVOXModel::set_prosody(const zv_prosody &p)
     has_prosody = true;
 }
 
+void ZeroVOXModel::set_phoneme_controls(const zv_phoneme_controls *p, uint32_t n)
+{
+    auto take = [n](auto *src, auto &dst) {
+        if (src) dst.assign(src, src + n);
+        else dst.clear();
+    };
+    has_phonemes = p != nullptr;
+    pc_n = p ? n : 0;
+    take(p ? p->duration_frames : nullptr, pc_frames);
+    take(p ? p->duration_scale : nullptr, pc_scale);
+    take(p ? p->pitch_shift : nullptr, pc_pitch);
+    take(p ? p->energy_shift : nullptr, pc_energy);
+    record_durations = true;
+}
+
 void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const float *style_embed, uint32_t num_phonemes)
 {
     const zv_prosody *pr = has_prosody ? &prosody : nullptr;
+    if (record_durations)
+    {
+        // the per-phoneme entry points (controls and / or timings); N = num_phonemes on both of eval()'s paths
+        if (has_phonemes && pc_n != num_phonemes)
+        {
+            std::string msg = "set_phoneme_controls: controls for " + std::to_string(pc_n) + " phonemes, eval() has " +
+                              std::to_string(num_phonemes);
+            throw zv::Error(ZV_ERR_ARG, msg);
+        }
+        auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
+        const zv_phoneme_controls pc = {ptr(pc_frames), ptr(pc_scale), ptr(pc_pitch), ptr(pc_energy)};
+        const zv_phoneme_controls *pcp = has_phonemes ? &pc : nullptr;
+        durations.assign(num_phonemes, 0);
+        if (num_phonemes != (uint32_t)MAX_N_PHONEMES)
+        {
+            chk(zv_synthesize_phonemes(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr, pcp,
+                                       durations.data()));
+            return;
+        }
+        chk(zv_encode_taps_phonemes(model, src_seq, puncts, style_embed, MAX_N_PHONEMES, num_phonemes, hparams.max_seq_len, hidden_state,
+                                    &n_frames, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pr, pcp, durations.data()));
+        decoder->eval(hidden_state, style_embed, mel);
+        meldec->eval(mel, wav);
+        return;
+    }
     if (num_phonemes != (uint32_t)MAX_N_PHONEMES)
     {
         // any length: run the C-ABI path directly with N = num_phonemes (the stage objects are pinned to MAX_N_PHONEMES)

@@ -13,6 +13,12 @@
 //   --duration-scale S, --pitch-scale S, --pitch-shift D, --energy-scale S, --energy-shift D
 //            prosody controls (include/zerovox_amd.h zv_prosody): durations * S (0 < S <= 16), pitch / energy predictions
 //            p * S + D before bucketing; defaults 1, 1, 0, 1, 0 (the uncontrolled result).  A bad value is a usage error.
+//   --phoneme-controls FILE
+//            per-phoneme controls (include/zerovox_amd.h zv_phoneme_controls): one line per phoneme of the utterance,
+//            "frames scale pitch_shift energy_shift" (frames -1 = keep the prediction, 0..32768 = exactly this many frames;
+//            0 < scale <= 16; finite shifts); "-1 1 0 0" is the identity.  A wrong line count or a bad value is a usage error.
+//   --alignment FILE
+//            write the phoneme timings as TSV: index, phoneme_id, start_frame, frames, start_sample, samples
 //   --trim   write only the frames the length regulator produced (the reference always writes max_seq_len frames,
 //            src/zerovox.cpp:369)
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
@@ -35,13 +41,17 @@ static void usage(FILE *f)
 {
     fprintf(f, "usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--info]\n"
                "               [--duration-scale S] [--pitch-scale S] [--pitch-shift D] [--energy-scale S] [--energy-shift D]\n"
+               "               [--phoneme-controls FILE] [--alignment FILE]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
                "  --pitch-scale S      pitch prediction p -> p * S + shift before bucketing, default 1\n"
                "  --pitch-shift D      (see --pitch-scale), default 0\n"
                "  --energy-scale S     energy prediction e -> e * S + shift before bucketing, default 1\n"
-               "  --energy-shift D     (see --energy-scale), default 0\n",
+               "  --energy-shift D     (see --energy-scale), default 0\n"
+               "  --phoneme-controls FILE  one line per phoneme: frames scale pitch_shift energy_shift (identity: -1 1 0 0;\n"
+               "                       frames -1 keeps the prediction, 0..32768 forces it; 0 < scale <= 16)\n"
+               "  --alignment FILE     write the phoneme timings as TSV: index phoneme_id start_frame frames start_sample samples\n",
             k_default_model, k_default_out);
 }
 
@@ -69,9 +79,74 @@ static float parse_flag_float(const char *flag, const std::string &v)
     return x;
 }
 
+// --phoneme-controls FILE for an utterance of n phonemes: a usage error (exit 2) on a wrong line count or a bad value
+struct PhonemeControlFile
+{
+    std::vector<int32_t> frames;
+    std::vector<float>   scale, pitch, energy;
+};
+
+static PhonemeControlFile read_phoneme_controls(const std::string &path, size_t n)
+{
+    auto bad = [&](const std::string &what) {
+        fprintf(stderr, "zerovox: --phoneme-controls %s: %s\n", path.c_str(), what.c_str());
+        usage(stderr);
+        exit(2);
+    };
+    std::ifstream f(path);
+    if (!f) bad("cannot open the file");
+    PhonemeControlFile pc;
+    std::string line;
+    size_t lineno = 0;
+    while (std::getline(f, line))
+    {
+        lineno++;
+        if (line.find_first_not_of(" \t\r") == std::string::npos) continue;       // blank lines carry no phoneme
+        std::istringstream is(line);
+        std::vector<std::string> tok;
+        std::string t;
+        while (is >> t) tok.push_back(t);
+        const std::string where = "line " + std::to_string(lineno);
+        if (tok.size() != 4) bad(where + ": needs 4 values (frames scale pitch_shift energy_shift), got " + std::to_string(tok.size()));
+        char *end = nullptr;
+        const long fr = strtol(tok[0].c_str(), &end, 10);
+        if (end != tok[0].c_str() + tok[0].size() || fr < -1 || fr > 32768) bad(where + ": frames '" + tok[0] + "' is not an integer in [-1, 32768]");
+        float v[3];
+        for (int k = 0; k < 3; k++)
+        {
+            v[k] = strtof(tok[k + 1].c_str(), &end);
+            if (end != tok[k + 1].c_str() + tok[k + 1].size() || !std::isfinite(v[k])) bad(where + ": '" + tok[k + 1] + "' is not a finite number");
+        }
+        if (!(v[0] > 0.0f && v[0] <= 16.0f)) bad(where + ": scale " + tok[1] + " is outside (0, 16]");
+        pc.frames.push_back((int32_t)fr);
+        pc.scale.push_back(v[0]);
+        pc.pitch.push_back(v[1]);
+        pc.energy.push_back(v[2]);
+    }
+    if (pc.frames.size() != n)
+        bad(std::to_string(pc.frames.size()) + " lines, the utterance has " + std::to_string(n) + " phonemes");
+    return pc;
+}
+
+// the utterance's phoneme ids before the model is loaded: line 1 of the utterance file, or the built-in utterance
+static std::vector<int32_t> utterance_ids(const std::string &utt_path)
+{
+    if (utt_path.empty())
+    {
+        const int32_t *ids = nullptr;
+        uint32_t n = 0;
+        zv_demo_utterance(&ids, nullptr, nullptr, &n, nullptr);
+        return std::vector<int32_t>(ids, ids + n);
+    }
+    std::ifstream f(utt_path);
+    std::string l1;
+    if (!f || !std::getline(f, l1)) throw std::runtime_error("cannot read utterance file '" + utt_path + "'");
+    return parse_line<int32_t>(l1);
+}
+
 int main(int argc, char **argv)
 {
-    std::string model_path = k_default_model, out_path = k_default_out, utt_path;
+    std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path;
     bool trim = false, info = false, controlled = false;
     zv_prosody prosody = {1.0f, 1.0f, 0.0f, 1.0f, 0.0f};
     for (int i = 1; i < argc; i++)
@@ -84,6 +159,8 @@ int main(int argc, char **argv)
         if (a == "-m") model_path = need("-m");
         else if (a == "-u") utt_path = need("-u");
         else if (a == "-o") out_path = need("-o");
+        else if (a == "--phoneme-controls") pc_path = need("--phoneme-controls");
+        else if (a == "--alignment") align_path = need("--alignment");
         else if (a == "--trim") trim = true;
         else if (a == "--info") info = true;
         else if (a == "--duration-scale" || a == "--pitch-scale" || a == "--pitch-shift" || a == "--energy-scale" || a == "--energy-shift")
@@ -130,9 +207,22 @@ int main(int argc, char **argv)
             return 0;
         }
 
+        // per-phoneme controls and timings: the file is checked against the utterance before the model is loaded
+        std::vector<int32_t> ids0;
+        PhonemeControlFile pcf;
+        if (!pc_path.empty() || !align_path.empty()) ids0 = utterance_ids(utt_path);
+        if (!pc_path.empty()) pcf = read_phoneme_controls(pc_path, ids0.size());
+
         ZeroVOX::ZeroVOXModel model(model_path);
         const ZeroVOX::zerovox_hparams &hp = model.get_hparams();
         if (controlled) model.set_prosody(prosody);
+        if (!pc_path.empty())
+        {
+            const zv_phoneme_controls pc = {pcf.frames.data(), pcf.scale.data(), pcf.pitch.data(), pcf.energy.data()};
+            model.set_phoneme_controls(&pc, (uint32_t)ids0.size());
+        }
+        else if (!align_path.empty())
+            model.set_phoneme_controls(nullptr, (uint32_t)ids0.size());        // timings only
         if (utt_path.empty())
             model.eval();
         else
@@ -155,6 +245,21 @@ int main(int argc, char **argv)
         }
 
         const uint32_t nf = model.get_num_frames();
+        if (!align_path.empty())
+        {
+            FILE *af = fopen(align_path.c_str(), "w");
+            if (!af) throw std::runtime_error("cannot open '" + align_path + "' for writing");
+            const std::vector<int32_t> &dur = model.get_durations();
+            fprintf(af, "index\tphoneme_id\tstart_frame\tframes\tstart_sample\tsamples\n");
+            uint64_t start = 0;
+            for (size_t i = 0; i < dur.size() && i < ids0.size(); i++)
+            {
+                fprintf(af, "%zu\t%d\t%llu\t%d\t%llu\t%llu\n", i, ids0[i], (unsigned long long)start, dur[i],
+                        (unsigned long long)(start * hp.audio_hop_size), (unsigned long long)dur[i] * hp.audio_hop_size);
+                start += (uint64_t)dur[i];
+            }
+            if (fclose(af) != 0) throw std::runtime_error("short write to '" + align_path + "'");
+        }
         if (trim)
         {
             const size_t n = (size_t)nf * hp.audio_hop_size;
