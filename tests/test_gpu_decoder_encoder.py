@@ -211,9 +211,10 @@ def test_encoder_edge_cases(models):
     e = model.encode(ids, puncts, style, 32)
     assert np.isfinite(e["features"]).all() and e["features"].shape == (nmax, g.E)
     ids, puncts, style = synth.encoder_inputs(g, 12, nmax + 1)
-    with pytest.raises(capi.ZvError) as ei:
-        model.encode(ids, puncts, style, 32)
-    assert ei.value.status == 5
+    for call in (lambda: model.encode(ids, puncts, style, 32), lambda: model.synthesize(ids, puncts, style, 32)):
+        with pytest.raises(capi.ZvError) as ei:
+            call()                                          # refused before any upload, like a batch's utterance
+        assert ei.value.status == 5 and "utterance 0" in str(ei.value) and "sinusoid" in str(ei.value), str(ei.value)
     with pytest.raises(capi.ZvError):
         model.encode(ids4, puncts4, style4, 0)
     # negative and too-large punctuation ids are rejected too

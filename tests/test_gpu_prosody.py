@@ -12,6 +12,7 @@ with ZV_LN_TAIL=0).  Checked here:
     energy tap and features;
   * batches with a different setting per utterance = stand-alone calls; graph replay after changing only the control values;
   * validation (ZV_ERR_ARG before any work) and the CLI flags."""
+import ctypes
 import os
 import subprocess
 
@@ -332,6 +333,11 @@ def test_validation_rejects_bad_controls_before_any_work(env, ckpt):
             with pytest.raises(capi.ZvError) as ei:
                 call()
             assert ei.value.status == ZV_ERR_ARG and "utterance 2" in str(ei.value) and field in str(ei.value), str(ei.value)
+    # a null pointer: the message names the entry point that was called
+    wav, nf = np.empty(T * g.hop_size, np.float32), ctypes.c_uint32(0)
+    st = m.lib.zv_synthesize(m.h, None, capi._ptr(puncts), capi._ptr(style), N, T, capi._ptr(wav), ctypes.byref(nf))
+    msg = m.lib.zv_last_error().decode()
+    assert st == ZV_ERR_ARG and msg.startswith("zv_synthesize: "), msg
     # nothing was left in flight: lane 1 is idle, and the next valid call gives a fresh model's bits
     with pytest.raises(capi.ZvError):
         bc.end(1)

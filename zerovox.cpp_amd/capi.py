@@ -213,6 +213,20 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _ref(x):
+    return None if x is None else C.byref(x)
+
+
+def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None):
+    """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
+    name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status"""
+    if phonemes is not None or durations is not None:
+        return getattr(lib, name + "_phonemes")(*args, prosody, phonemes, durations)
+    if prosody is not None:
+        return getattr(lib, name + "_prosody")(*args, prosody)
+    return getattr(lib, name)(*args)
+
+
 def debug_set(name: Optional[str], value: int = 0):
     """zv_debug_set: one test / measurement switch (csrc/knobs.h); name None resets every switch to its default"""
     lib = load_library()
@@ -356,16 +370,11 @@ class Model:
         args = (self.h, _ptr(ids), _ptr(puncts), _ptr(style), N, N if num_phonemes is None else num_phonemes, T, _ptr(out["hidden"]),
                 C.byref(nf), _ptr(out["features"]), _ptr(out["logdur"]), _ptr(out["pitch"]), _ptr(out["energy"]),
                 _ptr(out["pitch_bucket"]), _ptr(out["energy_bucket"]))
-        pr = _prosody(prosody)
-        if phonemes is not None or return_durations:
-            pc = _phoneme_controls(phonemes, N)
+        pc = _phoneme_controls(phonemes, N)
+        if pc is not None or return_durations:
             out["durations"] = np.empty(N, np.int32)
-            self._chk(self.lib.zv_encode_taps_phonemes(*args, None if pr is None else C.byref(pr),
-                                                       None if pc is None else C.byref(pc.struct), _ptr(out["durations"])))
-        elif pr is None:
-            self._chk(self.lib.zv_encode_taps(*args))
-        else:
-            self._chk(self.lib.zv_encode_taps_prosody(*args, C.byref(pr)))
+        self._chk(_call_variant(self.lib, "zv_encode_taps", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct),
+                                _ptr(out.get("durations"))))
         out["n_frames"] = int(nf.value)
         return out
 
@@ -379,19 +388,10 @@ class Model:
         wav = np.empty(T * self.hp.audio_hop_size, np.float32)
         nf = C.c_uint32(0)
         args = (self.h, _ptr(ids), _ptr(puncts), _ptr(style), len(ids), T, _ptr(wav), C.byref(nf))
-        pr = _prosody(prosody)
-        if phonemes is not None or return_durations:
-            pc = _phoneme_controls(phonemes, len(ids))
-            dur = np.empty(len(ids), np.int32) if return_durations else None
-            self._chk(self.lib.zv_synthesize_phonemes(*args, None if pr is None else C.byref(pr),
-                                                      None if pc is None else C.byref(pc.struct), _ptr(dur)))
-            if return_durations:
-                return wav, int(nf.value), dur
-        elif pr is None:
-            self._chk(self.lib.zv_synthesize(*args))
-        else:
-            self._chk(self.lib.zv_synthesize_prosody(*args, C.byref(pr)))
-        return wav, int(nf.value)
+        pc = _phoneme_controls(phonemes, len(ids))
+        dur = np.empty(len(ids), np.int32) if return_durations else None
+        self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur)))
+        return (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
 
     def prepare_batch(self, utterances, durations: bool = False) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
@@ -512,23 +512,13 @@ class BatchCall:
     def run(self):
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        if self.phonemes is not None:
-            m._chk(m.lib.zv_synthesize_batch_phonemes(*args, self.prosody, self.phonemes, self.dur_p))
-        elif self.prosody is None:
-            m._chk(m.lib.zv_synthesize_batch(*args))
-        else:
-            m._chk(m.lib.zv_synthesize_batch_prosody(*args, self.prosody))
+        m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        if self.phonemes is not None:
-            m._chk(m.lib.zv_synthesize_batch_begin_phonemes(*args, self.prosody, self.phonemes, self.dur_p))
-        elif self.prosody is None:
-            m._chk(m.lib.zv_synthesize_batch_begin(*args))
-        else:
-            m._chk(m.lib.zv_synthesize_batch_begin_prosody(*args, self.prosody))
+        m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p))
 
     def end(self, lane: int):
         m = self.model

@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -128,169 +129,265 @@ static void check_T(const Model &M, uint32_t T)
                  T, M.max_frames_per_utterance());
 }
 
-// Prosody controls (zv_prosody) -> the kernels' layout, f32 [n_utt][zv::CTL_STRIDE] (kernels.h CTL_*).  Every set is checked
-// before the caller enqueues anything: ZV_ERR_ARG names the utterance and the field.
-static void check_prosody(const zv_prosody *p, uint32_t n_utt)
+// The layout of an I/O block (io_scratch, pinned_scratch): regions in the order they are carved, each on a 256-byte boundary
+// (DeviceArena's rounding).  size() comes from the same carve, so it covers every region handed out.
+struct Layout
 {
-    if (!p) return;
+    size_t end = 0;
+    size_t at(size_t bytes)
+    {
+        const size_t o = zv::DeviceArena::align(end);
+        end = o + bytes;
+        return o;
+    }
+    size_t size() const { return zv::DeviceArena::align(end); }
+};
+
+// One call's utterances, in the form the batch entry points take them; a single-utterance entry point makes a request of one
+// that points at its own arguments.  out[u] receives utterance u's waveform (zv_encode_taps*: its hidden frames); n_frames,
+// prosody and phonemes are [count] or null; durations is [count] or null, and its entries may be null.
+struct Request
+{
+    const char                *fn;                     // the C entry point, for messages
+    uint32_t                   count;
+    const int32_t *const      *ids, *const *puncts;
+    const float *const        *styles;
+    const uint32_t            *n, *num_phonemes, *T;   // num_phonemes[u] <= n[u]: the tokens the length regulator walks
+    float *const              *out;
+    uint32_t                  *n_frames = nullptr;
+    const zv_prosody          *prosody = nullptr;
+    const zv_phoneme_controls *phonemes = nullptr;
+    int32_t *const            *durations = nullptr;
+
+    // any utterance with per-phoneme controls: then every utterance gets rows (the identity where it has none)
+    bool phoneme_controls() const
+    {
+        for (uint32_t u = 0; phonemes && u < count; u++)
+            if (phonemes[u].duration_frames || phonemes[u].duration_scale || phonemes[u].pitch_shift || phonemes[u].energy_shift)
+                return true;
+        return false;
+    }
+    // any utterance that asks for its phoneme timings
+    bool timings() const
+    {
+        for (uint32_t u = 0; durations && u < count; u++)
+            if (durations[u]) return true;
+        return false;
+    }
+    // utterances [a, b)
+    Request slice(uint32_t a, uint32_t b) const
+    {
+        Request s = *this;
+        s.count = b - a;
+        s.ids += a;
+        s.puncts += a;
+        s.styles += a;
+        s.n += a;
+        s.num_phonemes += a;
+        s.T += a;
+        s.out += a;
+        if (n_frames) s.n_frames += a;
+        if (prosody) s.prosody += a;
+        if (phonemes) s.phonemes += a;
+        if (durations) s.durations += a;
+        return s;
+    }
+};
+
+static void check_prosody(const zv_prosody &p)
+{
     static const char *const names[5] = {"duration_scale", "pitch_scale", "pitch_shift", "energy_scale", "energy_shift"};
-    for (uint32_t u = 0; u < n_utt; u++)
-    {
-        const float f[5] = {p[u].duration_scale, p[u].pitch_scale, p[u].pitch_shift, p[u].energy_scale, p[u].energy_shift};
-        for (int k = 0; k < 5; k++)
-            if (!std::isfinite(f[k])) zv::fail(ZV_ERR_ARG, "utterance %u: prosody %s = %g is not finite", u, names[k], (double)f[k]);
-        if (!(f[0] > 0.0f && f[0] <= 16.0f))
-            zv::fail(ZV_ERR_ARG, "utterance %u: prosody duration_scale = %g is outside (0, 16]", u, (double)f[0]);
-    }
+    const float f[5] = {p.duration_scale, p.pitch_scale, p.pitch_shift, p.energy_scale, p.energy_shift};
+    for (int k = 0; k < 5; k++)
+        if (!std::isfinite(f[k])) zv::fail(ZV_ERR_ARG, "prosody %s = %g is not finite", names[k], (double)f[k]);
+    if (!(f[0] > 0.0f && f[0] <= 16.0f)) zv::fail(ZV_ERR_ARG, "prosody duration_scale = %g is outside (0, 16]", (double)f[0]);
 }
 
-static void prosody_rows(const zv_prosody *p, uint32_t n_utt, float *rows)
+static void check_phoneme_controls(const Model &M, const zv_phoneme_controls &p, uint32_t n)
 {
-    memset(rows, 0, (size_t)n_utt * zv::CTL_STRIDE * sizeof(float));
-    for (uint32_t u = 0; u < n_utt; u++)
-    {
-        float *r = rows + (size_t)u * zv::CTL_STRIDE;
-        r[zv::CTL_DURATION] = p[u].duration_scale;
-        r[zv::CTL_PITCH] = p[u].pitch_scale;
-        r[zv::CTL_PITCH + 1] = p[u].pitch_shift;
-        r[zv::CTL_ENERGY] = p[u].energy_scale;
-        r[zv::CTL_ENERGY + 1] = p[u].energy_shift;
-    }
-}
-
-// Per-phoneme controls (zv_phoneme_controls) -> the kernels' layout, f32 [token row][zv::PCTL_STRIDE] (kernels.h PCTL_*).  Checked
-// like check_prosody: ZV_ERR_ARG names the utterance, the field and the phoneme.
-static bool has_phoneme_controls(const zv_phoneme_controls *p)
-{
-    return p && (p->duration_frames || p->duration_scale || p->pitch_shift || p->energy_shift);
-}
-
-static void check_phoneme_controls(const Model &M, const zv_phoneme_controls *p, uint32_t u, uint32_t n)
-{
-    if (!p) return;
     const int64_t fmax = std::min<int64_t>(32768, M.max_frames_per_utterance());      // forced frames travel as exact f32 integers
     for (uint32_t i = 0; i < n; i++)
     {
-        if (p->duration_frames && (p->duration_frames[i] < -1 || p->duration_frames[i] > fmax))
-            zv::fail(ZV_ERR_ARG, "utterance %u: duration_frames[%u] = %d is outside [-1, %lld]", u, i, p->duration_frames[i], (long long)fmax);
-        if (p->duration_scale)
+        if (p.duration_frames && (p.duration_frames[i] < -1 || p.duration_frames[i] > fmax))
+            zv::fail(ZV_ERR_ARG, "duration_frames[%u] = %d is outside [-1, %lld]", i, p.duration_frames[i], (long long)fmax);
+        if (p.duration_scale)
         {
-            const float v = p->duration_scale[i];
-            if (!std::isfinite(v)) zv::fail(ZV_ERR_ARG, "utterance %u: duration_scale[%u] = %g is not finite", u, i, (double)v);
-            if (!(v > 0.0f && v <= 16.0f)) zv::fail(ZV_ERR_ARG, "utterance %u: duration_scale[%u] = %g is outside (0, 16]", u, i, (double)v);
+            const float v = p.duration_scale[i];
+            if (!std::isfinite(v)) zv::fail(ZV_ERR_ARG, "duration_scale[%u] = %g is not finite", i, (double)v);
+            if (!(v > 0.0f && v <= 16.0f)) zv::fail(ZV_ERR_ARG, "duration_scale[%u] = %g is outside (0, 16]", i, (double)v);
         }
-        if (p->pitch_shift && !std::isfinite(p->pitch_shift[i]))
-            zv::fail(ZV_ERR_ARG, "utterance %u: pitch_shift[%u] = %g is not finite", u, i, (double)p->pitch_shift[i]);
-        if (p->energy_shift && !std::isfinite(p->energy_shift[i]))
-            zv::fail(ZV_ERR_ARG, "utterance %u: energy_shift[%u] = %g is not finite", u, i, (double)p->energy_shift[i]);
+        if (p.pitch_shift && !std::isfinite(p.pitch_shift[i]))
+            zv::fail(ZV_ERR_ARG, "pitch_shift[%u] = %g is not finite", i, (double)p.pitch_shift[i]);
+        if (p.energy_shift && !std::isfinite(p.energy_shift[i]))
+            zv::fail(ZV_ERR_ARG, "energy_shift[%u] = %g is not finite", i, (double)p.energy_shift[i]);
     }
 }
 
-// n rows; p may be null or hold null fields: those rows / fields get the identity {-1, 1, 0, 0}
-static void phoneme_rows(const zv_phoneme_controls *p, uint32_t n, float *rows)
+// Every check of a request, utterance by utterance, before the caller enqueues anything.  ZV_ERR_ARG; the message names the
+// entry point, the utterance and what is wrong (for per-phoneme controls the field and the phoneme).
+static void check_request(zv_model *m, const Request &r)
 {
-    for (uint32_t i = 0; i < n; i++)
+    if (!(m && r.ids && r.puncts && r.styles && r.n && r.T && r.out)) zv::fail(ZV_ERR_ARG, "%s: null argument", r.fn);
+    const Model &M = *m->m;
+    for (uint32_t u = 0; u < r.count; u++)
     {
-        float *r = rows + (size_t)i * zv::PCTL_STRIDE;
-        r[zv::PCTL_FRAMES] = p && p->duration_frames ? (float)p->duration_frames[i] : -1.0f;
-        r[zv::PCTL_DURATION] = p && p->duration_scale ? p->duration_scale[i] : 1.0f;
-        r[zv::PCTL_PITCH] = p && p->pitch_shift ? p->pitch_shift[i] : 0.0f;
-        r[zv::PCTL_ENERGY] = p && p->energy_shift ? p->energy_shift[i] : 0.0f;
+        try
+        {
+            if (!(r.ids[u] && r.puncts[u] && r.styles[u] && r.out[u])) zv::fail(ZV_ERR_ARG, "null argument");
+            if (!(r.n[u] > 0 && r.T[u] > 0)) zv::fail(ZV_ERR_ARG, "n and T must be > 0");
+            check_T(M, r.T[u]);
+            if (r.num_phonemes[u] > r.n[u]) zv::fail(ZV_ERR_ARG, "num_phonemes exceeds n");
+            if (r.n[u] > M.max_phonemes())
+                zv::fail(ZV_ERR_ARG, "%u phonemes exceed the %u rows of the sinusoid table", r.n[u], M.max_phonemes());
+            check_ids(M, r.ids[u], r.puncts[u], r.n[u]);
+            if (r.prosody) check_prosody(r.prosody[u]);
+            if (r.phonemes) check_phoneme_controls(M, r.phonemes[u], r.n[u]);
+        }
+        catch (const zv::Error &e)
+        {
+            zv::fail(e.status, "%s: utterance %u: %s", r.fn, u, e.what());
+        }
     }
 }
 
-// the phoneme timings: durations[i] = min(cum[i], T) - min(cum[i - 1], T), the frames token i occupies in hidden
-static void durations_from_cum(const int32_t *cum, uint32_t n, uint32_t T, int32_t *durations)
+// A request's controls in the kernels' layouts (kernels.h CTL_*, PCTL_*), written where the caller says: a batch's pinned input
+// block, or a single utterance's host staging.  ctl: with prosody, one zv::CTL_STRIDE row per utterance.  pctl: with per-phoneme
+// controls, one zv::PCTL_STRIDE row per token, packed like the token table; absent fields get the identity {-1, 1, 0, 0}.
+static void pack_controls(const Request &r, float *ctl, float *pctl)
 {
-    int64_t prev = 0;
-    for (uint32_t i = 0; i < n; i++)
+    const bool pc = r.phoneme_controls();
+    for (uint32_t u = 0, row = 0; u < r.count; row += r.n[u], u++)
     {
-        const int64_t c = std::min<int64_t>(cum[i], T);
-        durations[i] = (int32_t)(c - prev);
-        prev = c;
+        if (r.prosody)
+        {
+            const zv_prosody &p = r.prosody[u];
+            float *c = ctl + (size_t)u * zv::CTL_STRIDE;
+            std::fill(c, c + zv::CTL_STRIDE, 0.0f);
+            c[zv::CTL_DURATION] = p.duration_scale;
+            c[zv::CTL_PITCH] = p.pitch_scale;
+            c[zv::CTL_PITCH + 1] = p.pitch_shift;
+            c[zv::CTL_ENERGY] = p.energy_scale;
+            c[zv::CTL_ENERGY + 1] = p.energy_shift;
+        }
+        for (uint32_t i = 0; pc && i < r.n[u]; i++)
+        {
+            const zv_phoneme_controls &p = r.phonemes[u];
+            float *c = pctl + (size_t)(row + i) * zv::PCTL_STRIDE;
+            c[zv::PCTL_FRAMES] = p.duration_frames ? (float)p.duration_frames[i] : -1.0f;
+            c[zv::PCTL_DURATION] = p.duration_scale ? p.duration_scale[i] : 1.0f;
+            c[zv::PCTL_PITCH] = p.pitch_shift ? p.pitch_shift[i] : 0.0f;
+            c[zv::PCTL_ENERGY] = p.energy_shift ? p.energy_shift[i] : 0.0f;
+        }
     }
 }
 
-static void encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t num_phonemes,
-                        uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur, float *pitch, float *energy,
-                        int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody, const char *fn,
-                        const zv_phoneme_controls *phonemes = nullptr, int32_t *durations = nullptr)
+// The phoneme timings from the length regulator's scan, packed like the token table: durations[u][i] = min(cum[i], T[u]) -
+// min(cum[i - 1], T[u]), the frames token i of utterance u occupies in hidden (null entries are skipped)
+static void durations_from_cum(const int32_t *cum, uint32_t count, const uint32_t *n, const uint32_t *T, int32_t *const *durations)
 {
-    if (!(m && ids && puncts && style && hidden)) zv::fail(ZV_ERR_ARG, "%s: null argument", fn);
-    if (!(n > 0)) zv::fail(ZV_ERR_ARG, "%s: n must be > 0", fn);
-    if (!(num_phonemes <= n)) zv::fail(ZV_ERR_ARG, "%s: num_phonemes exceeds n", fn);
-    check_prosody(prosody, 1);
-    check_phoneme_controls(*m->m, phonemes, 0, n);
-    const bool pctl = has_phoneme_controls(phonemes);
-    Model &M = *m->m;
-    use_lane0(m);
-    check_T(M, T);
-    check_ids(M, ids, puncts, n);
-    const size_t E = M.E();
-    const size_t b_ids = (size_t)n * 4, b_sty = E * 4, b_hid = (size_t)T * E * 4;
-    const size_t b_pctl = pctl ? (((size_t)n * zv::PCTL_STRIDE * 4 + 255) & ~(size_t)255) : 0;
-    char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + 1024 + (prosody || pctl ? 256 : 0) + b_pctl);
-    int32_t *d_nf = (int32_t *)io;
-    io += 256;
-    int32_t *d_ids = (int32_t *)io, *d_pun = (int32_t *)(io + b_ids);
-    float *d_sty = (float *)(io + 2 * b_ids + 256 - (2 * b_ids) % 256);
-    float *d_hid = (float *)((char *)d_sty + ((b_sty + 255) & ~(size_t)255));
-    ZV_HIP(hipMemcpyAsync(d_ids, ids, b_ids, hipMemcpyHostToDevice, M.stream));
-    ZV_HIP(hipMemcpyAsync(d_pun, puncts, b_ids, hipMemcpyHostToDevice, M.stream));
-    ZV_HIP(hipMemcpyAsync(d_sty, style, b_sty, hipMemcpyHostToDevice, M.stream));
-    zv::Batch bt = zv::Batch::single(n, T, num_phonemes);
-    float ctl[zv::CTL_STRIDE];                   // lives until the M.sync() below
-    if (prosody)
+    for (uint32_t u = 0; u < count; cum += n[u], u++)
     {
-        float *d_ctl = (float *)((char *)d_hid + ((b_hid + 255) & ~(size_t)255));
-        prosody_rows(prosody, 1, ctl);
-        ZV_HIP(hipMemcpyAsync(d_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, M.stream));
-        bt.d_ctl = d_ctl;
+        int64_t prev = 0;
+        for (uint32_t i = 0; durations[u] && i < n[u]; i++)
+        {
+            const int64_t c = std::min<int64_t>(cum[i], T[u]);
+            durations[u][i] = (int32_t)(c - prev);
+            prev = c;
+        }
     }
-    std::vector<float> prow;                     // lives until the M.sync() below
-    if (pctl)
-    {
-        float *d_pctl = (float *)((char *)d_hid + ((b_hid + 255) & ~(size_t)255) + 256);
-        prow.resize((size_t)n * zv::PCTL_STRIDE);
-        phoneme_rows(phonemes, n, prow.data());
-        ZV_HIP(hipMemcpyAsync(d_pctl, prow.data(), prow.size() * 4, hipMemcpyHostToDevice, M.stream));
-        bt.d_pctl = d_pctl;
-    }
-    Model::EncoderTaps t = M.encode_dev(bt, d_ids, d_pun, d_sty, d_hid, d_nf);
-    ZV_HIP(hipMemcpyAsync(hidden, d_hid, b_hid, hipMemcpyDeviceToHost, M.stream));
-    int32_t nf = 0;
-    ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
-    if (features) ZV_HIP(hipMemcpyAsync(features, t.features, (size_t)n * E * 4, hipMemcpyDeviceToHost, M.stream));
-    if (logdur) ZV_HIP(hipMemcpyAsync(logdur, t.logdur, b_ids, hipMemcpyDeviceToHost, M.stream));
-    if (pitch) ZV_HIP(hipMemcpyAsync(pitch, t.pitch, b_ids, hipMemcpyDeviceToHost, M.stream));
-    if (energy) ZV_HIP(hipMemcpyAsync(energy, t.energy, b_ids, hipMemcpyDeviceToHost, M.stream));
-    if (pitch_bucket) ZV_HIP(hipMemcpyAsync(pitch_bucket, t.pitch_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
-    if (energy_bucket) ZV_HIP(hipMemcpyAsync(energy_bucket, t.energy_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
-    std::vector<int32_t> cum(durations ? n : 0);
-    if (durations) ZV_HIP(hipMemcpyAsync(cum.data(), t.cum, b_ids, hipMemcpyDeviceToHost, M.stream));
-    M.sync();
-    if (n_frames) *n_frames = (uint32_t)nf;
-    if (durations) durations_from_cum(cum.data(), n, T, durations);
 }
 
+// the taps zv_encode_taps* returns beside hidden, each [n] (features [n][E]) or null
+struct Taps
+{
+    float   *features, *logdur, *pitch, *energy;
+    int32_t *pitch_bucket, *energy_bucket;
+};
+
+// One utterance on lane 0, host buffers in and out: the encoder with its taps (taps given, r.out[0] is hidden) or the whole chain
+// (r.out[0] is the waveform).  The schedule of one utterance (Batch::single, inline segments), not a batch of one.
+static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> taps = std::nullopt)
+{
+    return guarded([&] {
+        check_request(m, r);
+        Model &M = *m->m;
+        use_lane0(m);
+        const uint32_t n = r.n[0], T = r.T[0];
+        const bool pc = r.phoneme_controls(), dur = r.timings();
+        const size_t E = M.E(), b_ids = (size_t)n * 4, b_hid = (size_t)T * E * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
+        const size_t b_ctl = r.prosody ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
+        if (!taps) M.reserve(n, T);
+        // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
+        // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
+        Layout L;
+        const size_t o_nf = L.at(4), o_ids = L.at(b_ids), o_pun = L.at(b_ids), o_sty = L.at(E * 4), o_ctl = L.at(b_ctl),
+                     o_pctl = L.at(b_pctl), o_hid = L.at(b_hid);
+        const size_t o_mel = taps ? 0 : L.at((size_t)T * M.hp.audio_num_mels * 4), o_wav = taps ? 0 : L.at(b_wav),
+                     o_cum = taps ? 0 : L.at(dur ? b_ids : 0);
+        char *io = (char *)M.io_scratch(L.size());
+        int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
+        float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
+        std::vector<float> ctl(b_ctl / 4), pctl(b_pctl / 4);         // host staging: lives until the M.sync() below
+        std::vector<int32_t> cum(dur ? n : 0);
+        pack_controls(r, ctl.data(), pctl.data());
+        zv::Batch bt = zv::Batch::single(n, T, r.num_phonemes[0]);
+        ZV_HIP(hipMemcpyAsync(d_ids, r.ids[0], b_ids, hipMemcpyHostToDevice, M.stream));
+        ZV_HIP(hipMemcpyAsync(d_pun, r.puncts[0], b_ids, hipMemcpyHostToDevice, M.stream));
+        ZV_HIP(hipMemcpyAsync(d_sty, r.styles[0], E * 4, hipMemcpyHostToDevice, M.stream));
+        if (b_ctl)
+        {
+            bt.d_ctl = (const float *)(io + o_ctl);
+            ZV_HIP(hipMemcpyAsync(io + o_ctl, ctl.data(), b_ctl, hipMemcpyHostToDevice, M.stream));
+        }
+        if (b_pctl)
+        {
+            bt.d_pctl = (const float *)(io + o_pctl);
+            ZV_HIP(hipMemcpyAsync(io + o_pctl, pctl.data(), b_pctl, hipMemcpyHostToDevice, M.stream));
+        }
+        int32_t nf = 0;
+        if (taps)
+        {
+            const Model::EncoderTaps t = M.encode_dev(bt, d_ids, d_pun, d_sty, d_hid, d_nf);
+            ZV_HIP(hipMemcpyAsync(r.out[0], d_hid, b_hid, hipMemcpyDeviceToHost, M.stream));
+            ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
+            if (taps->features) ZV_HIP(hipMemcpyAsync(taps->features, t.features, (size_t)n * E * 4, hipMemcpyDeviceToHost, M.stream));
+            if (taps->logdur) ZV_HIP(hipMemcpyAsync(taps->logdur, t.logdur, b_ids, hipMemcpyDeviceToHost, M.stream));
+            if (taps->pitch) ZV_HIP(hipMemcpyAsync(taps->pitch, t.pitch, b_ids, hipMemcpyDeviceToHost, M.stream));
+            if (taps->energy) ZV_HIP(hipMemcpyAsync(taps->energy, t.energy, b_ids, hipMemcpyDeviceToHost, M.stream));
+            if (taps->pitch_bucket) ZV_HIP(hipMemcpyAsync(taps->pitch_bucket, t.pitch_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
+            if (taps->energy_bucket) ZV_HIP(hipMemcpyAsync(taps->energy_bucket, t.energy_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
+            if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), t.cum, b_ids, hipMemcpyDeviceToHost, M.stream));
+        }
+        else
+        {
+            float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
+            if (dur) bt.d_cum = (int32_t *)(io + o_cum);
+            M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
+            ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
+            if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), bt.d_cum, b_ids, hipMemcpyDeviceToHost, M.stream));
+            ZV_HIP(hipMemcpyAsync(r.out[0], d_wav, b_wav, hipMemcpyDeviceToHost, M.stream));
+        }
+        M.sync();
+        if (r.n_frames) r.n_frames[0] = (uint32_t)nf;
+        if (dur) durations_from_cum(cum.data(), 1, r.n, r.T, r.durations);
+    });
+}
+
+// The plain and _prosody forms are the _phonemes form with NULLs: the same request, the same code path, the same bits.
 zv_status zv_encode_taps(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
                          uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
                          float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket)
 {
-    return guarded([&] {
-        encode_taps(m, ids, puncts, style, n, num_phonemes, T, hidden, n_frames, features, logdur, pitch, energy, pitch_bucket,
-                    energy_bucket, nullptr, __func__);
-    });
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &num_phonemes, &T, &hidden, n_frames},
+                      Taps{features, logdur, pitch, energy, pitch_bucket, energy_bucket});
 }
 
 zv_status zv_encode_taps_prosody(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
                                  uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
                                  float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody)
 {
-    return guarded([&] {
-        encode_taps(m, ids, puncts, style, n, num_phonemes, T, hidden, n_frames, features, logdur, pitch, energy, pitch_bucket,
-                    energy_bucket, prosody, __func__);
-    });
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &num_phonemes, &T, &hidden, n_frames, prosody},
+                      Taps{features, logdur, pitch, energy, pitch_bucket, energy_bucket});
 }
 
 zv_status zv_encode_taps_phonemes(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
@@ -298,10 +395,8 @@ zv_status zv_encode_taps_phonemes(zv_model *m, const int32_t *ids, const int32_t
                                   float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody,
                                   const zv_phoneme_controls *phonemes, int32_t *durations)
 {
-    return guarded([&] {
-        encode_taps(m, ids, puncts, style, n, num_phonemes, T, hidden, n_frames, features, logdur, pitch, energy, pitch_bucket,
-                    energy_bucket, prosody, __func__, phonemes, durations);
-    });
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &num_phonemes, &T, &hidden, n_frames, prosody, phonemes, &durations},
+                      Taps{features, logdur, pitch, energy, pitch_bucket, energy_bucket});
 }
 
 zv_status zv_encode(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
@@ -317,10 +412,11 @@ zv_status zv_decode(zv_model *m, const float *hidden, const float *style, uint32
         Model &M = *m->m;
         use_lane0(m);
         check_T(M, T);
-        const size_t E = M.E(), Mm = M.hp.audio_num_mels;
-        const size_t b_hid = (size_t)T * E * 4, b_sty = (E * 4 + 255) & ~(size_t)255, b_mel = (size_t)T * Mm * 4;
-        char *io = (char *)M.io_scratch(b_hid + b_sty + b_mel + 1024);
-        float *d_sty = (float *)io, *d_hid = (float *)(io + b_sty), *d_mel = (float *)(io + b_sty + ((b_hid + 255) & ~(size_t)255));
+        const size_t E = M.E(), b_hid = (size_t)T * E * 4, b_mel = (size_t)T * M.hp.audio_num_mels * 4;
+        Layout L;
+        const size_t o_sty = L.at(E * 4), o_hid = L.at(b_hid), o_mel = L.at(b_mel);
+        char *io = (char *)M.io_scratch(L.size());
+        float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel);
         ZV_HIP(hipMemcpyAsync(d_hid, hidden, b_hid, hipMemcpyHostToDevice, M.stream));
         ZV_HIP(hipMemcpyAsync(d_sty, style, E * 4, hipMemcpyHostToDevice, M.stream));
         M.decode_dev(zv::Batch::single(1, T, 1), d_hid, d_sty, d_mel);
@@ -336,10 +432,12 @@ zv_status zv_vocode(zv_model *m, const float *mel, uint32_t T, float *wav)
         Model &M = *m->m;
         use_lane0(m);
         check_T(M, T);
-        const size_t b_mel = ((size_t)T * M.hp.audio_num_mels * 4 + 255) & ~(size_t)255, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
-        char *io = (char *)M.io_scratch(b_mel + b_wav);
-        float *d_mel = (float *)io, *d_wav = (float *)(io + b_mel);
-        ZV_HIP(hipMemcpyAsync(d_mel, mel, (size_t)T * M.hp.audio_num_mels * 4, hipMemcpyHostToDevice, M.stream));
+        const size_t b_mel = (size_t)T * M.hp.audio_num_mels * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
+        Layout L;
+        const size_t o_mel = L.at(b_mel), o_wav = L.at(b_wav);
+        char *io = (char *)M.io_scratch(L.size());
+        float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
+        ZV_HIP(hipMemcpyAsync(d_mel, mel, b_mel, hipMemcpyHostToDevice, M.stream));
         M.vocode_dev_graph(zv::Batch::single(1, T, 1), d_mel, d_wav);
         ZV_HIP(hipMemcpyAsync(wav, d_wav, b_wav, hipMemcpyDeviceToHost, M.stream));
         M.sync();
@@ -359,13 +457,15 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
         const uint32_t H = M.vocoder_halo_frames();
         const uint32_t ctx_max = std::min<uint64_t>(T, (uint64_t)chunk_frames + 2 * H);
         check_T(M, ctx_max);                          // only a chunk plus its context is ever vocoded at once
-        const size_t b_mel = ((size_t)T * Mm * 4 + 255) & ~(size_t)255, b_wav = (size_t)ctx_max * hop * 4;
         M.reserve(1, ctx_max);
-        char *io = (char *)M.io_scratch(b_mel + b_wav);
-        float *d_mel = (float *)io, *d_wav = (float *)(io + b_mel);
+        Layout L;
+        const size_t o_mel = L.at((size_t)T * Mm * 4), o_wav = L.at((size_t)ctx_max * hop * 4);
+        char *io = (char *)M.io_scratch(L.size());
+        float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
         // two pinned slots: chunk c is copied out and delivered while chunk c + 1 is being computed
-        const size_t slot = ((size_t)chunk_frames * hop * 4 + 255) & ~(size_t)255;
-        char *pin = (char *)M.pinned_scratch(2 * slot);
+        Layout P;
+        const size_t slot[2] = {P.at((size_t)chunk_frames * hop * 4), P.at((size_t)chunk_frames * hop * 4)};
+        char *pin = (char *)M.pinned_scratch(P.size());
         hipEvent_t done[2] = {nullptr, nullptr};
         ZV_HIP(hipEventCreateWithFlags(&done[0], hipEventDisableTiming));
         ZV_HIP(hipEventCreateWithFlags(&done[1], hipEventDisableTiming));
@@ -373,7 +473,7 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
         auto deliver = [&](int k) {
             if (!pend[k].live) return;
             ZV_HIP(hipEventSynchronize(done[k]));
-            sink(user, (const float *)(pin + k * slot), pend[k].first, pend[k].n);
+            sink(user, (const float *)(pin + slot[k]), pend[k].first, pend[k].n);
             pend[k].live = false;
         };
         try
@@ -386,7 +486,7 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
                 const uint32_t c0 = a > H ? a - H : 0, c1 = std::min<uint64_t>(T, (uint64_t)b + H);
                 deliver(k);                                   // the slot we are about to overwrite
                 M.vocode_dev(zv::Batch::single(1, c1 - c0, 1), d_mel + (size_t)c0 * Mm, d_wav);
-                ZV_HIP(hipMemcpyAsync(pin + k * slot, d_wav + (size_t)(a - c0) * hop, (size_t)(b - a) * hop * 4, hipMemcpyDeviceToHost, M.stream));
+                ZV_HIP(hipMemcpyAsync(pin + slot[k], d_wav + (size_t)(a - c0) * hop, (size_t)(b - a) * hop * 4, hipMemcpyDeviceToHost, M.stream));
                 ZV_HIP(hipEventRecord(done[k], M.stream));
                 pend[k] = {true, (uint64_t)a * hop, (uint64_t)(b - a) * hop};
                 deliver(k ^ 1);                               // the previous chunk, while this one runs
@@ -407,110 +507,23 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
     });
 }
 
-// one utterance end to end on the currently selected lane; no host synchronisation.  ctl_host: the utterance's control row
-// (prosody_rows) or null; pctl_host: its n per-phoneme rows (phoneme_rows) or null; cum_host: receives the length regulator's
-// scan (int32 [n]) or null.  Like the other host buffers they must stay valid until the caller synchronises
-static void synthesize_enqueue(Model &M, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
-                               float *wav, int32_t *nf_host, const float *ctl_host = nullptr, const float *pctl_host = nullptr,
-                               int32_t *cum_host = nullptr)
-{
-    check_ids(M, ids, puncts, n);
-    check_T(M, T);
-    const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_ids = al((size_t)n * 4), b_sty = al(E * 4), b_hid = al((size_t)T * E * 4), b_mel = al((size_t)T * Mm * 4),
-                 b_wav = al((size_t)T * hop * 4);
-    M.reserve(n, T);
-    const size_t b_ctl = ctl_host ? al(zv::CTL_STRIDE * 4) : 0, b_pctl = pctl_host ? al((size_t)n * zv::PCTL_STRIDE * 4) : 0;
-    char *io = (char *)M.io_scratch(256 + 2 * b_ids + b_sty + b_hid + b_mel + b_wav + b_ctl + b_pctl + (cum_host ? b_ids : 0));
-    int32_t *d_nf = (int32_t *)io;
-    io += 256;
-    int32_t *d_ids = (int32_t *)io, *d_pun = (int32_t *)(io + b_ids);
-    float *d_sty = (float *)(io + 2 * b_ids), *d_hid = (float *)(io + 2 * b_ids + b_sty);
-    float *d_mel = (float *)((char *)d_hid + b_hid), *d_wav = (float *)((char *)d_mel + b_mel);
-    ZV_HIP(hipMemcpyAsync(d_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, M.stream));
-    ZV_HIP(hipMemcpyAsync(d_pun, puncts, (size_t)n * 4, hipMemcpyHostToDevice, M.stream));
-    ZV_HIP(hipMemcpyAsync(d_sty, style, E * 4, hipMemcpyHostToDevice, M.stream));
-    zv::Batch bt = zv::Batch::single(n, T, n);
-    if (ctl_host)
-    {
-        float *d_ctl = (float *)((char *)d_wav + b_wav);
-        ZV_HIP(hipMemcpyAsync(d_ctl, ctl_host, zv::CTL_STRIDE * 4, hipMemcpyHostToDevice, M.stream));
-        bt.d_ctl = d_ctl;
-    }
-    if (pctl_host)
-    {
-        float *d_pctl = (float *)((char *)d_wav + b_wav + b_ctl);
-        ZV_HIP(hipMemcpyAsync(d_pctl, pctl_host, (size_t)n * zv::PCTL_STRIDE * 4, hipMemcpyHostToDevice, M.stream));
-        bt.d_pctl = d_pctl;
-    }
-    if (cum_host) bt.d_cum = (int32_t *)((char *)d_wav + b_wav + b_ctl + b_pctl);
-    M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
-    ZV_HIP(hipMemcpyAsync(nf_host, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
-    if (cum_host) ZV_HIP(hipMemcpyAsync(cum_host, bt.d_cum, (size_t)n * 4, hipMemcpyDeviceToHost, M.stream));
-    ZV_HIP(hipMemcpyAsync(wav, d_wav, (size_t)T * hop * 4, hipMemcpyDeviceToHost, M.stream));
-}
-
 zv_status zv_synthesize(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
                         float *wav, uint32_t *n_frames)
 {
-    return guarded([&] {
-        ZV_NEED(m && ids && puncts && style && wav, "null argument");
-        ZV_NEED(n > 0 && T > 0, "n and T must be > 0");
-        Model &M = *m->m;
-        use_lane0(m);
-        int32_t nf = 0;
-        synthesize_enqueue(M, ids, puncts, style, n, T, wav, &nf);
-        M.sync();
-        if (n_frames) *n_frames = (uint32_t)nf;
-    });
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames});
 }
 
 zv_status zv_synthesize_prosody(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
                                 float *wav, uint32_t *n_frames, const zv_prosody *prosody)
 {
-    return guarded([&] {
-        ZV_NEED(m && ids && puncts && style && wav, "null argument");
-        ZV_NEED(n > 0 && T > 0, "n and T must be > 0");
-        check_prosody(prosody, 1);
-        Model &M = *m->m;
-        use_lane0(m);
-        int32_t nf = 0;
-        float ctl[zv::CTL_STRIDE];
-        if (prosody) prosody_rows(prosody, 1, ctl);
-        synthesize_enqueue(M, ids, puncts, style, n, T, wav, &nf, prosody ? ctl : nullptr);
-        M.sync();
-        if (n_frames) *n_frames = (uint32_t)nf;
-    });
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody});
 }
 
 zv_status zv_synthesize_phonemes(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
                                  float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
                                  int32_t *durations)
 {
-    return guarded([&] {
-        ZV_NEED(m && ids && puncts && style && wav, "null argument");
-        ZV_NEED(n > 0 && T > 0, "n and T must be > 0");
-        check_prosody(prosody, 1);
-        Model &M = *m->m;
-        check_phoneme_controls(M, phonemes, 0, n);
-        use_lane0(m);
-        int32_t nf = 0;
-        float ctl[zv::CTL_STRIDE];
-        if (prosody) prosody_rows(prosody, 1, ctl);
-        std::vector<float> prow;
-        if (has_phoneme_controls(phonemes))
-        {
-            prow.resize((size_t)n * zv::PCTL_STRIDE);
-            phoneme_rows(phonemes, n, prow.data());
-        }
-        std::vector<int32_t> cum(durations ? n : 0);
-        synthesize_enqueue(M, ids, puncts, style, n, T, wav, &nf, prosody ? ctl : nullptr, prow.empty() ? nullptr : prow.data(),
-                           durations ? cum.data() : nullptr);
-        M.sync();
-        if (n_frames) *n_frames = (uint32_t)nf;
-        if (durations) durations_from_cum(cum.data(), n, T, durations);
-    });
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody, phonemes, &durations});
 }
 
 // copies the finished waveforms out of the pinned staging block, on a few threads when there is enough to move
@@ -584,95 +597,87 @@ static void use_lane0(zv_model *m)
     m->m->select_lane(0);
 }
 
-// prosody[n_utt], phonemes[n_utt] or null (checked by the caller); durations[n_utt] or null, entries may be null
-static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
-                          const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
-                          uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes = nullptr,
-                          int32_t *const *durations = nullptr)
+// one launch group of a checked request, enqueued on `lane`
+static void batch_enqueue(zv_model *m, int lane, const Request &r)
 {
     Model &M = *m->m;
     PendingBatch &pb = pending_slot(m, lane);
     if (pb.active) zv::fail(ZV_ERR_ARG, "lane %d already has a batch in flight", lane);
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const bool pc = r.phoneme_controls(), dur = r.timings();
     uint32_t nmax = 0, tmax = 0, ntot = 0;
-    bool pctl = false, want_dur = false;
-    for (uint32_t u = 0; u < n_utt; u++)
+    for (uint32_t u = 0; u < r.count; u++)
     {
-        nmax = std::max(nmax, n_phonemes[u]);
-        tmax = std::max(tmax, T[u]);
-        ntot += n_phonemes[u];
-        pctl = pctl || (phonemes && has_phoneme_controls(&phonemes[u]));
-        want_dur = want_dur || (durations && durations[u]);
+        nmax = std::max(nmax, r.n[u]);
+        tmax = std::max(tmax, r.T[u]);
+        ntot += r.n[u];
     }
     zv::Batch bt;
-    bt.nseg = (int)n_utt;
+    bt.nseg = (int)r.count;
     bt.n_max = zv::round_up((int)nmax, 32);
     bt.n_real = (int)nmax;
     bt.t_max = zv::round_up((int)tmax, 64);
     bt.n_rows = (size_t)bt.nseg * bt.n_max;
     bt.t_rows = (size_t)bt.nseg * bt.t_max;
-    // device block: [frame counts][inputs: token table | frame table | ids | puncts | styles | controls | phoneme controls][hidden]
-    // [mel][wav][scan]
-    // (tables: one entry per utterance + one that spans all of them, see Batch::tokens_merged; controls: only with prosody, one
-    // zv::CTL_STRIDE row per utterance; phoneme controls: only with per-phoneme controls, one zv::PCTL_STRIDE row per token row —
-    // uploaded with the rest, so a replayed graph reads the values of this call; scan: only when timings are asked for, the
-    // length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
-    const size_t b_tab = al((size_t)(bt.nseg + 1) * sizeof(zv::Seg)), b_ids = al(bt.n_rows * 4), b_sty = al((size_t)bt.nseg * E * 4);
-    const size_t b_ctl = prosody ? al((size_t)bt.nseg * zv::CTL_STRIDE * 4) : 0;
-    const size_t b_pctl = pctl ? al(bt.n_rows * zv::PCTL_STRIDE * 4) : 0;
-    const size_t b_in = 2 * b_tab + 2 * b_ids + b_sty + b_ctl + b_pctl;
-    const size_t b_nf = al((size_t)bt.nseg * 4), b_hid = al(bt.t_rows * E * 4), b_mel = al(bt.t_rows * Mm * 4),
-                 b_wav = al(bt.t_rows * hop * 4), b_cum = want_dur ? b_ids : 0;
+    // input block, uploaded in one copy from its pinned mirror: [token table][frame table][ids][puncts][styles][controls]
+    // [phoneme controls] (tables: one entry per utterance + one that spans all of them, see Batch::tokens_merged; controls: only
+    // with prosody, one zv::CTL_STRIDE row per utterance; phoneme controls: only with per-phoneme controls, one zv::PCTL_STRIDE
+    // row per token row — uploaded with the rest, so a replayed graph reads the values of this call)
+    Layout in;
+    const size_t b_tab = (size_t)(bt.nseg + 1) * sizeof(zv::Seg);
+    const size_t i_tok = in.at(b_tab), i_frm = in.at(b_tab), i_ids = in.at(bt.n_rows * 4), i_pun = in.at(bt.n_rows * 4),
+                 i_sty = in.at((size_t)bt.nseg * E * 4), i_ctl = in.at(r.prosody ? (size_t)bt.nseg * zv::CTL_STRIDE * 4 : 0),
+                 i_pctl = in.at(pc ? bt.n_rows * zv::PCTL_STRIDE * 4 : 0), b_in = in.size();
+    // device block: [frame counts][input block][hidden][mel][wav][scan] (scan: only when timings are asked for, the length
+    // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
+    Layout dev;
+    const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
+                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur ? bt.n_rows * 4 : 0);
     M.reserve_batch(bt);
-    char *io = (char *)M.io_scratch(b_nf + b_in + b_hid + b_mel + b_wav + b_cum);
-    int32_t *d_nf = (int32_t *)io;
-    char *d_in = io + b_nf;
-    zv::Seg *d_tok = (zv::Seg *)d_in, *d_frm = (zv::Seg *)(d_in + b_tab);
-    int32_t *d_ids = (int32_t *)(d_in + 2 * b_tab), *d_pun = (int32_t *)(d_in + 2 * b_tab + b_ids);
-    float *d_sty = (float *)(d_in + 2 * b_tab + 2 * b_ids);
-    if (prosody) bt.d_ctl = (const float *)(d_in + 2 * b_tab + 2 * b_ids + b_sty);
-    if (pctl) bt.d_pctl = (const float *)(d_in + 2 * b_tab + 2 * b_ids + b_sty + b_ctl);
-    float *d_hid = (float *)(d_in + b_in), *d_mel = (float *)((char *)d_hid + b_hid), *d_wav = (float *)((char *)d_mel + b_mel);
-    if (want_dur) bt.d_cum = (int32_t *)((char *)d_wav + b_wav);
-    bt.d_tok = d_tok;
-    bt.d_frm = d_frm;
-    // pinned mirror of the input block + landing area of the results
+    char *io = (char *)M.io_scratch(dev.size());
+    // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan]
     size_t wav_bytes = 0;
-    pb.woff.assign(n_utt, 0);
-    for (uint32_t u = 0; u < n_utt; u++)
+    pb.woff.assign(r.count, 0);
+    for (uint32_t u = 0; u < r.count; u++)
     {
         pb.woff[u] = wav_bytes;
-        wav_bytes += (size_t)T[u] * hop * 4;
+        wav_bytes += (size_t)r.T[u] * hop * 4;
     }
-    char *pin = (char *)M.pinned_scratch(b_in + b_nf + al(wav_bytes) + b_cum);
+    Layout host;
+    const size_t p_in = host.at(b_in), p_nf = host.at((size_t)bt.nseg * 4), p_wav = host.at(wav_bytes),
+                 p_cum = host.at(dur ? bt.n_rows * 4 : 0);
+    char *pin = (char *)M.pinned_scratch(host.size());
+    char *d_in = io + o_in, *h_in = pin + p_in;
     {
-        zv::Seg *h_tok = (zv::Seg *)pin, *h_frm = (zv::Seg *)(pin + b_tab);
-        int32_t *h_ids = (int32_t *)(pin + 2 * b_tab), *h_pun = (int32_t *)(pin + 2 * b_tab + b_ids);
-        float *h_sty = (float *)(pin + 2 * b_tab + 2 * b_ids);
+        zv::Seg *h_tok = (zv::Seg *)(h_in + i_tok), *h_frm = (zv::Seg *)(h_in + i_frm);
+        int32_t *h_ids = (int32_t *)(h_in + i_ids), *h_pun = (int32_t *)(h_in + i_pun);
+        float *h_sty = (float *)(h_in + i_sty);
         int32_t n0 = 0, t0 = 0;
-        for (uint32_t u = 0; u < n_utt; u++)
+        for (uint32_t u = 0; u < r.count; u++)
         {
-            const int32_t n = (int32_t)n_phonemes[u], t = (int32_t)T[u];
+            const int32_t n = (int32_t)r.n[u], t = (int32_t)r.T[u];
             h_tok[u] = zv::Seg{n0, n, n, 0};
             h_frm[u] = zv::Seg{t0, t, 0, 0};
-            memcpy(h_ids + n0, ids[u], (size_t)n * 4);
-            memcpy(h_pun + n0, puncts[u], (size_t)n * 4);
-            memcpy(h_sty + (size_t)u * E, styles[u], E * 4);
+            memcpy(h_ids + n0, r.ids[u], (size_t)n * 4);
+            memcpy(h_pun + n0, r.puncts[u], (size_t)n * 4);
+            memcpy(h_sty + (size_t)u * E, r.styles[u], E * 4);
             n0 += n;
             t0 += t;
         }
-        h_tok[n_utt] = zv::Seg{0, n0, n0, 0};
-        h_frm[n_utt] = zv::Seg{0, t0, 0, 0};
-        if (prosody) prosody_rows(prosody, n_utt, (float *)(pin + 2 * b_tab + 2 * b_ids + b_sty));
-        if (pctl)           // the utterances' rows, packed like the token table (rows past them are never read)
-            for (uint32_t u = 0, r = 0; u < n_utt; r += n_phonemes[u], u++)
-                phoneme_rows(&phonemes[u], n_phonemes[u], (float *)(pin + 2 * b_tab + 2 * b_ids + b_sty + b_ctl) + (size_t)r * zv::PCTL_STRIDE);
+        h_tok[r.count] = zv::Seg{0, n0, n0, 0};
+        h_frm[r.count] = zv::Seg{0, t0, 0, 0};
+        pack_controls(r, (float *)(h_in + i_ctl), (float *)(h_in + i_pctl));      // (phoneme rows past the utterances are never read)
     }
-    int32_t *h_nf = (int32_t *)(pin + b_in);
-    char *h_wav = pin + b_in + b_nf;
-    int32_t *h_cum = want_dur ? (int32_t *)(h_wav + al(wav_bytes)) : nullptr;
+    bt.d_tok = (const zv::Seg *)(d_in + i_tok);
+    bt.d_frm = (const zv::Seg *)(d_in + i_frm);
+    if (r.prosody) bt.d_ctl = (const float *)(d_in + i_ctl);
+    if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
+    if (dur) bt.d_cum = (int32_t *)(io + o_cum);
+    int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(d_in + i_ids), *d_pun = (int32_t *)(d_in + i_pun);
+    float *d_sty = (float *)(d_in + i_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
+    int32_t *h_nf = (int32_t *)(pin + p_nf), *h_cum = dur ? (int32_t *)(pin + p_cum) : nullptr;
+    char *h_wav = pin + p_wav;
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
     // run.  Same kernels on the same rows: same bits.
@@ -685,7 +690,7 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
     try
     {
         hipStream_t cs = M.copy_stream();
-        pb.gb.assign(G + 1, n_utt);
+        pb.gb.assign(G + 1, r.count);
         pb.gb[0] = 0;
         // Batches in flight on different lanes share the GPU kernel by kernel (worth 1.4 ms per batch: the latency-bound encoder /
         // decoder launches of one fill the other's vocoder).  Every batch owns a (start, done) pair of timing events on its lane's
@@ -696,29 +701,29 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
         ZV_HIP(hipEventRecord(M.batch_event(seq, 0), M.stream));
         if (G <= 1)
         {
-            M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, pin, d_in, b_in);
+            M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, h_in, d_in, b_in);
             ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream));
             ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream));
-            if (want_dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream));
+            if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream));
             ZV_HIP(hipMemcpyAsync(h_wav, d_wav, wav_bytes, hipMemcpyDeviceToHost, M.stream));
             ZV_HIP(hipEventRecord(M.tail_event(1), M.stream));
         }
         else
         {
-            M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, pin, d_in, b_in, 1);
+            M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, h_in, d_in, b_in, 1);
             ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream));
-            if (want_dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream));
+            if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream));
             for (int g = 1; g < G; g++)               // contiguous groups of about wav_bytes / G each
             {
                 uint32_t u = pb.gb[g - 1] + 1;
-                while (u < n_utt && pb.woff[u] < wav_bytes * g / G) u++;
-                pb.gb[g] = std::min(u, n_utt - (uint32_t)(G - g));
+                while (u < r.count && pb.woff[u] < wav_bytes * g / G) u++;
+                pb.gb[g] = std::min(u, r.count - (uint32_t)(G - g));
             }
             for (int g = 0; g < G; g++)
             {
                 const uint32_t u0 = pb.gb[g], u1 = pb.gb[g + 1];
                 M.vocode_tail(bt, d_mel, d_wav, (int)u0, (int)(u1 - u0));
-                const size_t o0 = pb.woff[u0], o1 = u1 < n_utt ? pb.woff[u1] : wav_bytes;
+                const size_t o0 = pb.woff[u0], o1 = u1 < r.count ? pb.woff[u1] : wav_bytes;
                 ZV_HIP(hipEventRecord(M.tail_event(2 * g), M.stream));
                 ZV_HIP(hipStreamWaitEvent(cs, M.tail_event(2 * g), 0));
                 ZV_HIP(hipMemcpyAsync(h_wav + o0, (const char *)d_wav + o0, o1 - o0, hipMemcpyDeviceToHost, cs));
@@ -734,17 +739,17 @@ static void batch_enqueue(zv_model *m, int lane, uint32_t n_utt, const int32_t *
         throw;
     }
     pb.active = true;
-    pb.n_utt = n_utt;
+    pb.n_utt = r.count;
     pb.G = G;
-    pb.T.assign(T, T + n_utt);
-    pb.wav.assign(wav, wav + n_utt);
-    pb.n_frames = n_frames;
+    pb.T.assign(r.T, r.T + r.count);
+    pb.wav.assign(r.out, r.out + r.count);
+    pb.n_frames = r.n_frames;
     pb.h_wav = h_wav;
     pb.h_nf = h_nf;
     pb.hop = hop;
     pb.h_cum = h_cum;
-    pb.N.assign(n_phonemes, n_phonemes + n_utt);
-    if (want_dur) pb.dur.assign(durations, durations + n_utt);
+    pb.N.assign(r.n, r.n + r.count);
+    if (dur) pb.dur.assign(r.durations, r.durations + r.count);
     else pb.dur.clear();
 }
 
@@ -774,26 +779,7 @@ static void batch_finish(zv_model *m, int lane)
     pb.active = false;
     if (pb.n_frames)
         for (uint32_t u = 0; u < pb.n_utt; u++) pb.n_frames[u] = (uint32_t)pb.h_nf[u];
-    if (pb.h_cum)
-        for (uint32_t u = 0, r = 0; u < pb.n_utt; r += pb.N[u], u++)
-            if (pb.dur[u]) durations_from_cum(pb.h_cum + r, pb.N[u], pb.T[u], pb.dur[u]);
-}
-
-static void batch_check(Model &M, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts, const float *const *styles,
-                        const uint32_t *n_phonemes, const uint32_t *T, float *const *wav, const zv_prosody *prosody,
-                        const zv_phoneme_controls *phonemes = nullptr)
-{
-    check_prosody(prosody, n_utt);
-    for (uint32_t u = 0; u < n_utt; u++)
-    {
-        ZV_NEED(ids[u] && puncts[u] && styles[u] && wav[u], "null utterance pointer");
-        ZV_NEED(n_phonemes[u] > 0 && T[u] > 0, "n and T must be > 0");
-        check_T(M, T[u]);
-        if (n_phonemes[u] > M.max_phonemes())
-            zv::fail(ZV_ERR_ARG, "utterance %u: %u phonemes exceed the %u rows of the sinusoid table", u, n_phonemes[u], M.max_phonemes());
-        check_ids(M, ids[u], puncts[u], n_phonemes[u]);
-        if (phonemes) check_phoneme_controls(M, &phonemes[u], u, n_phonemes[u]);
-    }
+    if (pb.h_cum) durations_from_cum(pb.h_cum, pb.n_utt, pb.N.data(), pb.T.data(), pb.dur.data());
 }
 
 // how many utterances from `a` on form one launch group: up to 64 utterances / 64 Ki frames of capacity
@@ -810,80 +796,50 @@ static uint32_t batch_group_end(uint32_t a, uint32_t n_utt, const uint32_t *T)
     return b;
 }
 
-static void synthesize_batch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
-                             const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
-                             uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes = nullptr,
-                             int32_t *const *durations = nullptr)
+// zv_synthesize_batch*: every launch group enqueued and finished on lane 0
+static zv_status synthesize_batch(zv_model *m, const Request &r)
 {
-    Model &M = *m->m;
-    ZV_HIP(hipSetDevice(M.device));
-    batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav, prosody, phonemes);
-    // Groups of up to 64 utterances / 64 Ki frames go through the chain as ONE launch per kernel: every tensor is
-    // the row concatenation of the group, the segment tables tell the kernels where each utterance starts and ends.
-    // Capacities are rounded up so that batches of similar shape replay the same captured graph.
-    uint32_t a = 0;
-    while (a < n_utt)
-    {
-        const uint32_t b = batch_group_end(a, n_utt, T);
-        batch_enqueue(m, 0, b - a, ids + a, puncts + a, styles + a, n_phonemes + a, T + a, wav + a, n_frames ? n_frames + a : nullptr,
-                      prosody ? prosody + a : nullptr, phonemes ? phonemes + a : nullptr, durations ? durations + a : nullptr);
-        batch_finish(m, 0);
-        a = b;
-    }
+      return guarded([&] {
+        check_request(m, r);
+        ZV_HIP(hipSetDevice(m->m->device));
+        // Groups of up to 64 utterances / 64 Ki frames go through the chain as ONE launch per kernel: every tensor is
+        // the row concatenation of the group, the segment tables tell the kernels where each utterance starts and ends.
+        // Capacities are rounded up so that batches of similar shape replay the same captured graph.
+        for (uint32_t a = 0, b; a < r.count; a = b)
+        {
+            b = batch_group_end(a, r.count, r.T);
+            batch_enqueue(m, 0, r.slice(a, b));
+            batch_finish(m, 0);
+        }
+    });
+}
+
+// zv_synthesize_batch_begin*: one launch group, left in flight on `lane`
+static zv_status begin_batch(zv_model *m, uint32_t lane, const Request &r)
+{
+    return guarded([&] {
+        check_request(m, r);
+        if (!(lane < ZV_BATCH_LANES)) zv::fail(ZV_ERR_ARG, "%s: lane out of range", r.fn);
+        if (!(r.count > 0)) zv::fail(ZV_ERR_ARG, "%s: empty batch", r.fn);
+        if (batch_group_end(0, r.count, r.T) != r.count)
+            zv::fail(ZV_ERR_ARG, "%s: an asynchronous batch must fit one launch group (64 utterances, 64 Ki frames of capacity)", r.fn);
+        ZV_HIP(hipSetDevice(m->m->device));
+        batch_enqueue(m, (int)lane, r);
+    });
 }
 
 zv_status zv_synthesize_batch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
                               const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
                               uint32_t *n_frames)
 {
-    return guarded([&] {
-        ZV_NEED(m && ids && puncts && styles && n_phonemes && T && wav, "null argument");
-        synthesize_batch(m, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, nullptr);
-    });
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames});
 }
 
 zv_status zv_synthesize_batch_prosody(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
                                       const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
                                       uint32_t *n_frames, const zv_prosody *prosody)
 {
-    return guarded([&] {
-        ZV_NEED(m && ids && puncts && styles && n_phonemes && T && wav, "null argument");
-        synthesize_batch(m, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody);
-    });
-}
-
-static void synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
-                                   const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
-                                   uint32_t *n_frames, const zv_prosody *prosody, const char *fn,
-                                   const zv_phoneme_controls *phonemes = nullptr, int32_t *const *durations = nullptr)
-{
-    if (!(m && ids && puncts && styles && n_phonemes && T && wav)) zv::fail(ZV_ERR_ARG, "%s: null argument", fn);
-    if (!(lane < ZV_BATCH_LANES)) zv::fail(ZV_ERR_ARG, "%s: lane out of range", fn);
-    if (!(n_utt > 0)) zv::fail(ZV_ERR_ARG, "%s: empty batch", fn);
-    Model &M = *m->m;
-    ZV_HIP(hipSetDevice(M.device));
-    batch_check(M, n_utt, ids, puncts, styles, n_phonemes, T, wav, prosody, phonemes);
-    if (batch_group_end(0, n_utt, T) != n_utt)
-        zv::fail(ZV_ERR_ARG, "%s: an asynchronous batch must fit one launch group (64 utterances, 64 Ki frames of capacity)", fn);
-    batch_enqueue(m, (int)lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody, phonemes, durations);
-}
-
-zv_status zv_synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
-                                    const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
-                                    uint32_t *n_frames)
-{
-    return guarded([&] {
-        synthesize_batch_begin(m, lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, nullptr, __func__);
-    });
-}
-
-zv_status zv_synthesize_batch_begin_prosody(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
-                                            const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
-                                            const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody)
-{
-    return guarded([&] {
-        synthesize_batch_begin(m, lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody, __func__);
-    });
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody});
 }
 
 zv_status zv_synthesize_batch_phonemes(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
@@ -891,10 +847,22 @@ zv_status zv_synthesize_batch_phonemes(zv_model *m, uint32_t n_utt, const int32_
                                        uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
                                        int32_t *const *durations)
 {
-    return guarded([&] {
-        ZV_NEED(m && ids && puncts && styles && n_phonemes && T && wav, "null argument");
-        synthesize_batch(m, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody, phonemes, durations);
-    });
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                durations});
+}
+
+zv_status zv_synthesize_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                    const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                    uint32_t *n_frames)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames});
+}
+
+zv_status zv_synthesize_batch_begin_prosody(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                            const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                            const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody});
 }
 
 zv_status zv_synthesize_batch_begin_phonemes(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
@@ -902,10 +870,8 @@ zv_status zv_synthesize_batch_begin_phonemes(zv_model *m, uint32_t lane, uint32_
                                              const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
                                              const zv_phoneme_controls *phonemes, int32_t *const *durations)
 {
-    return guarded([&] {
-        synthesize_batch_begin(m, lane, n_utt, ids, puncts, styles, n_phonemes, T, wav, n_frames, prosody, __func__, phonemes,
-                               durations);
-    });
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                 durations});
 }
 
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)
@@ -961,7 +927,6 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
         M.dbg_layer.x = x;
         M.dbg_layer.out = out;
         struct Reset { Model &M; ~Reset() { M.dbg_layer = Model::DebugLayer(); } } reset{M};
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
         if (kind == ZV_LAYER_VOC_RESBLOCK || kind == ZV_LAYER_VOC_UPSAMPLE || kind == ZV_LAYER_VOC_INPUT || kind == ZV_LAYER_VOC_OUTPUT)
         {
             // rows are rows at the layer's INPUT rate: frames x samples per frame of the stage the layer reads
@@ -982,22 +947,26 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
             ZV_NEED(rows % rate == 0, "rows must be a multiple of the layer's samples per frame");
             const uint32_t T = rows / rate;
             check_T(M, T);
-            char *io = (char *)M.io_scratch(al((size_t)T * Mm * 4) + (size_t)T * hop * 4);
+            Layout L;
+            const size_t b_mel = (size_t)T * Mm * 4, o_mel = L.at(b_mel), o_wav = L.at((size_t)T * hop * 4);
+            char *io = (char *)M.io_scratch(L.size());
             if (kind == ZV_LAYER_VOC_INPUT)
-                ZV_HIP(hipMemcpyAsync(io, x, (size_t)T * Mm * 4, hipMemcpyHostToDevice, M.stream));      // the layer's input IS the mel
+                ZV_HIP(hipMemcpyAsync(io + o_mel, x, b_mel, hipMemcpyHostToDevice, M.stream));      // the layer's input IS the mel
             else
-                ZV_HIP(hipMemsetAsync(io, 0, (size_t)T * Mm * 4, M.stream));
-            M.vocode_dev(zv::Batch::single(1, T, 1), (const float *)io, (float *)(io + al((size_t)T * Mm * 4)));
+                ZV_HIP(hipMemsetAsync(io + o_mel, 0, b_mel, M.stream));
+            M.vocode_dev(zv::Batch::single(1, T, 1), (const float *)(io + o_mel), (float *)(io + o_wav));
         }
         else if (kind == ZV_LAYER_ENC_FFT || kind == ZV_LAYER_VAR_PRED || kind == ZV_LAYER_ENC_EMBED || kind == ZV_LAYER_ENC_MHA ||
                  kind == ZV_LAYER_ENC_FFN)
         {
             const uint32_t n = rows, T = 8;
-            char *io = (char *)M.io_scratch(256 + 2 * al((size_t)n * 4) + al(E * 4) + (size_t)T * E * 4);
-            int32_t *d_nf = (int32_t *)io;
-            int32_t *d_ids = (int32_t *)(io + 256), *d_pun = (int32_t *)(io + 256 + al((size_t)n * 4));
-            float *d_sty = (float *)(io + 256 + 2 * al((size_t)n * 4)), *d_hid = (float *)((char *)d_sty + al(E * 4));
-            ZV_HIP(hipMemsetAsync(io, 0, 256 + 2 * al((size_t)n * 4), M.stream));
+            Layout L;
+            const size_t o_nf = L.at(4), o_ids = L.at((size_t)n * 4), o_pun = L.at((size_t)n * 4), o_sty = L.at(E * 4),
+                         o_hid = L.at((size_t)T * E * 4);
+            char *io = (char *)M.io_scratch(L.size());
+            int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
+            float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
+            ZV_HIP(hipMemsetAsync(io, 0, o_sty, M.stream));                 // frame count, ids and puncts: all in front of the style
             std::vector<int32_t> hid, hpu;
             if (kind == ZV_LAYER_ENC_EMBED)
             {
@@ -1021,13 +990,14 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
         {
             const uint32_t T = rows;
             check_T(M, T);
-            const size_t b_hid = al((size_t)T * E * 4), b_sty = al(E * 4);
-            char *io = (char *)M.io_scratch(b_hid + b_sty + (size_t)T * Mm * 4);
-            float *d_sty = (float *)io, *d_hid = (float *)(io + b_sty), *d_mel = (float *)(io + b_sty + b_hid);
+            Layout L;
+            const size_t o_sty = L.at(E * 4), o_hid = L.at((size_t)T * E * 4), o_mel = L.at((size_t)T * Mm * 4);
+            char *io = (char *)M.io_scratch(L.size());
+            float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel);
             if (kind == ZV_LAYER_DEC_ASR_RES)
                 ZV_HIP(hipMemcpyAsync(d_hid, x, (size_t)T * E * 4, hipMemcpyHostToDevice, M.stream));     // asr_res reads the stage input itself
             else
-                ZV_HIP(hipMemsetAsync(d_hid, 0, b_hid, M.stream));
+                ZV_HIP(hipMemsetAsync(d_hid, 0, o_mel - o_hid, M.stream));                               // the region, padding included
             ZV_HIP(hipMemcpyAsync(d_sty, sty, E * 4, hipMemcpyHostToDevice, M.stream));
             M.decode_dev(zv::Batch::single(1, T, 1), d_hid, d_sty, d_mel);
         }

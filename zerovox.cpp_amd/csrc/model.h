@@ -30,9 +30,10 @@ struct DeviceArena
 {
     char  *base = nullptr;
     size_t cap = 0, used = 0;
+    static size_t align(size_t off) { return (off + 255) & ~(size_t)255; }     // every region starts on a 256-byte boundary
     void  *take(size_t bytes)
     {
-        const size_t a = (used + 255) & ~(size_t)255;
+        const size_t a = align(used);
         if (a + bytes > cap) fail(ZV_ERR_OOM, "device arena overflow (%zu + %zu > %zu)", a, bytes, cap);
         used = a + bytes;
         return base + a;
