@@ -241,6 +241,38 @@ zv_status zv_synthesize_batch_begin_phonemes(zv_model *m, uint32_t lane, uint32_
                                              const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
                                              const zv_phoneme_controls *phonemes, int32_t *const *durations);
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane);
+
+/* ---- fitted synthesis: only the frames the length regulator fills ----------------------------------------------------
+ * Every synthesize call takes T, a frame CAPACITY chosen before the duration predictor has run; the calls above decode and
+ * vocode all T frames (the reference's static graph does, src/zerovox.cpp:326-334), zero tail of `hidden` included, so the
+ * audio of an utterance depends on the capacity its caller picked (the decoder's InstanceNorm / AdaIN statistics run over the
+ * tail too) and the tail's samples are computed for nobody.  The fitted forms keep T[u] as the size of buffers and grids, but
+ * the decoder and the vocoder treat utterance u as exactly n_frames[u] frames long: after the length regulator a small kernel
+ * writes a second frame table in HBM, {row0 of the capacity table, n_frames[u]}, and every later kernel reads its extents
+ * there — one pass, one captured graph, no host round trip; a replayed graph picks up new lengths like new controls.
+ * With nf the frame count the length regulator produces under capacity T (controls included), for each utterance:
+ *   - wav[0 .. nf*hop) has exactly the bits of the unfitted call of the same kind (zv_synthesize / _prosody / _phonemes, or
+ *     utterance u of the batch forms) with the same inputs and T = nf.  (Well defined: with T' = nf no duration clamp becomes
+ *     active that was not before — every d_i <= sum d = nf when nothing was cut off, nf = T otherwise — so the encoder gives
+ *     the same nf and the same hidden[0 .. nf).)
+ *   - wav[nf*hop .. T*hop) is 0.0f.
+ *   - *n_frames = nf; durations[] mean what they mean in the _phonemes forms and sum to nf.
+ *   - nf == 0 (every walked phoneme got 0 frames): ZV_OK, n_frames = 0, all of wav 0.0f.
+ *   - nf == T: the bits of the unfitted call at T, all of them.
+ * Arguments, validation, limits (zv_max_frames(), 64 utterances / 64 Ki frames of CAPACITY per launch group) and error
+ * messages are those of the _phonemes forms; prosody, phonemes and durations may be NULL.  The copies to the host stay sized
+ * by capacity.  zv_synthesize_batch_begin_fitted is finished by zv_synthesize_batch_end like every other _begin. */
+zv_status zv_synthesize_fitted(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                               float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                               int32_t *durations);
+zv_status zv_synthesize_batch_fitted(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                     const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                     float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                     const zv_phoneme_controls *phonemes, int32_t *const *durations);
+zv_status zv_synthesize_batch_begin_fitted(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                           const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                           const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                           const zv_phoneme_controls *phonemes, int32_t *const *durations);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the
@@ -272,7 +304,8 @@ zv_status zv_synchronize(zv_model *m);
 zv_status zv_set_graph_mode(zv_model *m, int on);
 
 /* ---- measurement ------------------------------------------------------------------------ */
-/* per-kernel-family timing measured with HIP events on the model's stream (eager launches) */
+/* per-kernel-family timing measured with HIP events on the model's stream (eager launches).  algo_bytes / algo_flops are
+ * priced by CAPACITY rows, also for a fitted call (whose kernels do less than that when n_frames < T) */
 typedef struct
 {
     char     name[48];

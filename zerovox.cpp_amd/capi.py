@@ -22,7 +22,7 @@ SYMBOLS = [
     "zv_profile_begin", "zv_profile_end", "zv_write_wav", "zv_gguf_inspect", "zv_max_frames", "zv_demo_utterance", "zv_debug_layer", "zv_debug_set",
     "zv_debug_get", "zv_batch_timeline", "zv_encode_taps_prosody", "zv_synthesize_prosody", "zv_synthesize_batch_prosody",
     "zv_synthesize_batch_begin_prosody", "zv_encode_taps_phonemes", "zv_synthesize_phonemes", "zv_synthesize_batch_phonemes",
-    "zv_synthesize_batch_begin_phonemes",
+    "zv_synthesize_batch_begin_phonemes", "zv_synthesize_fitted", "zv_synthesize_batch_fitted", "zv_synthesize_batch_begin_fitted",
 ]
 
 
@@ -169,6 +169,12 @@ def load_library(path: Optional[str] = None):
     lib.zv_synthesize_phonemes.argtypes = lib.zv_synthesize_prosody.argtypes + [pc, i32p]
     lib.zv_synthesize_batch_phonemes.argtypes = lib.zv_synthesize_batch_prosody.argtypes + [pc, C.POINTER(vp)]
     lib.zv_synthesize_batch_begin_phonemes.argtypes = lib.zv_synthesize_batch_begin_prosody.argtypes + [pc, C.POINTER(vp)]
+    # the fitted forms take the argument lists of their _phonemes counterparts (an older build named by ZEROVOX_AMD_LIB for an A/B
+    # run may lack them: calling one then fails with AttributeError; build() checks SYMBOLS on the tree's own library)
+    if hasattr(lib, "zv_synthesize_fitted"):
+        lib.zv_synthesize_fitted.argtypes = lib.zv_synthesize_phonemes.argtypes
+        lib.zv_synthesize_batch_fitted.argtypes = lib.zv_synthesize_batch_phonemes.argtypes
+        lib.zv_synthesize_batch_begin_fitted.argtypes = lib.zv_synthesize_batch_begin_phonemes.argtypes
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -217,9 +223,24 @@ def _ref(x):
     return None if x is None else C.byref(x)
 
 
-def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None):
+def _check_fitted(fitted, Ts):
+    """the `fitted` flag and the frame capacities of a synthesize call, checked before anything reaches the library"""
+    if not isinstance(fitted, (bool, np.bool_)):
+        raise TypeError(f"fitted must be a bool, not {type(fitted).__name__}")
+    for T in Ts:
+        if isinstance(T, (bool, np.bool_)) or not isinstance(T, (int, np.integer)):
+            raise TypeError(f"T must be an integer frame capacity, not {type(T).__name__}")
+        if T <= 0:
+            raise ValueError(f"T = {T}: the frame capacity must be > 0")
+    return bool(fitted)
+
+
+def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False):
     """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
-    name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status"""
+    name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status.
+    fitted: name_fitted, which takes everything (NULL for what the call lacks)"""
+    if fitted:
+        return getattr(lib, name + "_fitted")(*args, prosody, phonemes, durations)
     if phonemes is not None or durations is not None:
         return getattr(lib, name + "_phonemes")(*args, prosody, phonemes, durations)
     if prosody is not None:
@@ -378,10 +399,13 @@ class Model:
         out["n_frames"] = int(nf.value)
         return out
 
-    def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False):
+    def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False,
+                   fitted: bool = False):
         """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
         arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
-        as a third element"""
+        as a third element.  fitted: zv_synthesize_fitted — T is a capacity, the utterance is decoded and vocoded as the n_frames
+        the length regulator fills; wav keeps the capacity shape [T * hop], zero behind n_frames * hop"""
+        fitted = _check_fitted(fitted, [T])
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
@@ -390,19 +414,22 @@ class Model:
         args = (self.h, _ptr(ids), _ptr(puncts), _ptr(style), len(ids), T, _ptr(wav), C.byref(nf))
         pc = _phoneme_controls(phonemes, len(ids))
         dur = np.empty(len(ids), np.int32) if return_durations else None
-        self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur)))
+        self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur),
+                                fitted))
         return (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
 
-    def prepare_batch(self, utterances, durations: bool = False) -> "BatchCall":
+    def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
-        buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list"""
-        return BatchCall(self, utterances, durations)
+        buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list.  fitted: the
+        zv_synthesize_batch_fitted / _begin_fitted entry points (the lane form: .begin(lane) / .end(lane))"""
+        return BatchCall(self, utterances, durations, fitted)
 
-    def synthesize_batch(self, utterances, return_durations: bool = False):
+    def synthesize_batch(self, utterances, return_durations: bool = False, fitted: bool = False):
         """utterances: list of (ids, puncts, style, T[, prosody[, phonemes]]) -> list of (wav, n_frames); each utterance keeps its
         own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its per-phoneme controls
-        (PhonemeControls, dict of arrays or None).  return_durations: (wav, n_frames, durations) tuples"""
-        call = BatchCall(self, utterances, return_durations)
+        (PhonemeControls, dict of arrays or None).  return_durations: (wav, n_frames, durations) tuples.  fitted:
+        zv_synthesize_batch_fitted — every T is a capacity, wav keeps the capacity shape with zeros behind n_frames * hop"""
+        call = BatchCall(self, utterances, return_durations, fitted)
         call.run()
         if return_durations:
             return [r + (d,) for r, d in zip(call.results(), call.durations)]
@@ -464,9 +491,10 @@ class BatchCall:
     array .prosody, which set_prosody() rewrites in place: the next run() / begin() uses the new values with the same buffers (a
     captured graph replays with them).  When any utterance carries per-phoneme controls, or durations=True, the _phonemes entry
     points are called with the array .phonemes (set_phoneme_controls() rewrites an entry) and .durations[i] holds utterance i's
-    phoneme timings after run() / end()."""
+    phoneme timings after run() / end().  fitted: the _fitted entry points, whatever controls the utterances carry."""
 
-    def __init__(self, model: Model, utterances, durations: bool = False):
+    def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False):
+        self.fitted = _check_fitted(fitted, [u[3] for u in utterances])
         self.model = model
         n = self.n = len(utterances)
         self.keep, self.wavs = [], []
@@ -512,13 +540,13 @@ class BatchCall:
     def run(self):
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p))
+        m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p))
+        m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted))
 
     def end(self, lane: int):
         m = self.model

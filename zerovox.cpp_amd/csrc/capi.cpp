@@ -158,6 +158,8 @@ struct Request
     const zv_prosody          *prosody = nullptr;
     const zv_phoneme_controls *phonemes = nullptr;
     int32_t *const            *durations = nullptr;
+    // fitted (zv_synthesize_fitted): decode and vocode each utterance as the n_frames the length regulator fills, not as T
+    bool                       fitted = false;
 
     // any utterance with per-phoneme controls: then every utterance gets rows (the identity where it has none)
     bool phoneme_controls() const
@@ -319,11 +321,12 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
         // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
+        // [live frame table] (fitted: one entry, written on the device)
         Layout L;
         const size_t o_nf = L.at(4), o_ids = L.at(b_ids), o_pun = L.at(b_ids), o_sty = L.at(E * 4), o_ctl = L.at(b_ctl),
                      o_pctl = L.at(b_pctl), o_hid = L.at(b_hid);
         const size_t o_mel = taps ? 0 : L.at((size_t)T * M.hp.audio_num_mels * 4), o_wav = taps ? 0 : L.at(b_wav),
-                     o_cum = taps ? 0 : L.at(dur ? b_ids : 0);
+                     o_cum = taps ? 0 : L.at(dur ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0);
         char *io = (char *)M.io_scratch(L.size());
         int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
@@ -362,6 +365,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         {
             float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
             if (dur) bt.d_cum = (int32_t *)(io + o_cum);
+            if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
             ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
             if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), bt.d_cum, b_ids, hipMemcpyDeviceToHost, M.stream));
@@ -633,7 +637,8 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
     Layout dev;
     const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
-                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur ? bt.n_rows * 4 : 0);
+                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur ? bt.n_rows * 4 : 0),
+                 o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0);      // fitted: the live frame table, written on the device
     M.reserve_batch(bt);
     char *io = (char *)M.io_scratch(dev.size());
     // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan]
@@ -674,6 +679,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     if (r.prosody) bt.d_ctl = (const float *)(d_in + i_ctl);
     if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
     if (dur) bt.d_cum = (int32_t *)(io + o_cum);
+    if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
     int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(d_in + i_ids), *d_pun = (int32_t *)(d_in + i_pun);
     float *d_sty = (float *)(d_in + i_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
     int32_t *h_nf = (int32_t *)(pin + p_nf), *h_cum = dur ? (int32_t *)(pin + p_cum) : nullptr;
@@ -872,6 +878,32 @@ zv_status zv_synthesize_batch_begin_phonemes(zv_model *m, uint32_t lane, uint32_
 {
     return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
                                  durations});
+}
+
+// The fitted forms: the _phonemes requests with the flag set (NULL prosody / phonemes / durations as there).
+zv_status zv_synthesize_fitted(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                               float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                               int32_t *durations)
+{
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody, phonemes, &durations, true});
+}
+
+zv_status zv_synthesize_batch_fitted(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                     const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                     uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                     int32_t *const *durations)
+{
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                durations, true});
+}
+
+zv_status zv_synthesize_batch_begin_fitted(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                           const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                           const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                           const zv_phoneme_controls *phonemes, int32_t *const *durations)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                 durations, true});
 }
 
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)

@@ -341,4 +341,12 @@ hipError_t launch_length_regulator(hipStream_t s, const float *feat, int ld, con
                                    int ldh, int32_t *cum, int32_t *n_frames, const Segs &tokens, const Segs &frames,
                                    const float *ctl = nullptr, const float *pctl = nullptr);
 
+// ---- fitted mode (include/zerovox_amd.h zv_synthesize_fitted): the decoder and the vocoder run over the frames the length regulator
+// filled instead of the capacity.  live[u] = {frames[u].row0, min(n_frames[u], frames[u].rows), 0, 0} for the nseg entries of
+// `frames` (table or inline segment), written on the device so that the schedule stays one graph without a host round trip
+hipError_t launch_live_frames(hipStream_t s, const int32_t *n_frames, Seg *live, const Segs &frames);
+// x[row][0 .. C) = 0 for the rows [live[u].rows * rate, frames[u].rows * rate) of every segment (x: rows of C floats at `rate` rows per
+// base row, laid out by `frames`): what the fitted schedule leaves unwritten of a segment's capacity
+hipError_t launch_zero_tail(hipStream_t s, float *x, int C, const Segs &frames, const Segs &live, int rate);
+
 }  // namespace zv

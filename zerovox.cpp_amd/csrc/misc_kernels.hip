@@ -1404,4 +1404,55 @@ hipError_t launch_length_regulator(hipStream_t s, const float *feat, int ld, con
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Fitted mode: the frame table the decoder and the vocoder read, written on the device from the length regulator's frame counts.
+//   live[u] = {frames[u].row0, min(n_frames[u], frames[u].rows), 0, 0}
+// row0 stays the capacity table's (buffers are laid out by capacity, so every output stays where the host expects it); a segment
+// whose regulator produced no frame gets rows = 0, and every frame-rate kernel then leaves it alone (its workgroups exit on
+// `t0 >= L`, the statistics kernels on `L <= 0`).  One thread per segment, HBM tables in and out.
+__global__ __launch_bounds__(64) void live_frames_kernel(const int32_t *__restrict__ n_frames, Seg *__restrict__ live, const Segs frames)
+{
+    const int u = blockIdx.x * 64 + threadIdx.x;
+    if (u >= frames.nseg) return;
+    const Seg cap = frames.tab ? frames.tab[u] : frames.one;
+    int nf = n_frames[u];
+    nf = nf < 0 ? 0 : (nf < cap.rows ? nf : cap.rows);
+    *(int4 *)(live + u) = make_int4(cap.row0, nf, 0, 0);
+}
+
+hipError_t launch_live_frames(hipStream_t s, const int32_t *n_frames, Seg *live, const Segs &frames)
+{
+    if (frames.nseg < 1 || !n_frames || !live || (!frames.tab && frames.nseg != 1)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(live_frames_kernel, dim3((frames.nseg + 63) / 64), dim3(64), 0, s, n_frames, live, frames);
+    return hipGetLastError();
+}
+
+// Fitted mode: x[(row0 + t) * C + c] = 0 for the rows t in [live.rows * rate, frames.rows * rate) of every segment — the part of a
+// segment's capacity that the fitted schedule never writes (the waveform behind an utterance's last frame).  grid.x walks a
+// segment's capacity in chunks of 1 024 elements; a chunk that lies inside the live part exits at once.
+__global__ __launch_bounds__(256) void zero_tail_kernel(float *__restrict__ x, int C, const Segs frames, const Segs live, int rate)
+{
+    const Seg cap = seg_at(frames, blockIdx.y), lv = seg_at(live, blockIdx.y);
+    const long end = (long)cap.rows * rate * C;
+    long lo = (long)(lv.rows < cap.rows ? lv.rows : cap.rows) * rate * C;
+    if (lo < 0) lo = 0;
+    const long i0 = (long)blockIdx.x * 1024;
+    if (i0 + 1024 <= lo || i0 >= end) return;
+    float *xs = x + (size_t)cap.row0 * rate * C;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+    {
+        const long i = i0 + k * 256 + threadIdx.x;
+        if (i >= lo && i < end) xs[i] = 0.f;
+    }
+}
+
+hipError_t launch_zero_tail(hipStream_t s, float *x, int C, const Segs &frames, const Segs &live, int rate)
+{
+    if (frames.nseg < 1 || frames.nseg != live.nseg || frames.max_rows < 1 || C < 1 || rate < 1 || !live.tab) return hipErrorInvalidValue;
+    const long per_seg = (long)frames.max_rows * rate * C;
+    hipLaunchKernelGGL(zero_tail_kernel, dim3((unsigned)((per_seg + 1023) / 1024), frames.nseg), dim3(256), 0, s, x, C, frames, live, rate);
+    return hipGetLastError();
+}
+
 }  // namespace zv

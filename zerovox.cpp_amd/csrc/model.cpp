@@ -862,6 +862,7 @@ void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g
     if (!bt.d_frm || g0 < 0 || cnt < 1 || g0 + cnt > bt.nseg) fail(ZV_ERR_ARG, "internal: bad segment group");
     Batch sub = bt;
     sub.d_frm = bt.d_frm + g0;
+    if (bt.d_frm_live) sub.d_frm_live = bt.d_frm_live + g0;
     sub.nseg = cnt;
     vocode_group(sub, d_mel, d_wav, 2);
 }
@@ -1236,6 +1237,8 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         }
         ZV_LAUNCH("voc_output_conv", 12.0 * La * C + 4.0 * La, 2.0 * La * C * a.K, launch_out_conv(stream, a));
         if (dbg_layer.kind == ZV_LAYER_VOC_OUTPUT) dbg_extract(d_wav, 1, 1, L);
+        // fitted: the output conv stops at each utterance's last frame; the rest of its capacity is silence
+        if (bt.d_frm_live) ZV_LAUNCH("voc_zero_tail", 4.0 * La, 0.0, launch_zero_tail(stream, d_wav, 1, bt.frames_cap(), fr, rate));
     }
 }
 
@@ -1311,9 +1314,10 @@ void Model::chain_dev(const Batch &b, const int32_t *d_ids, const int32_t *d_pun
         run();
         return;
     }
-    // (b.d_ctl, b.d_pctl, b.d_cum: a controlled schedule and an uncontrolled one are different graphs)
-    const void *key[11] = {d_ids, d_puncts, d_styles, d_hidden, d_mel, d_wav, d_nframes, h2d_src, b.d_ctl, b.d_pctl, b.d_cum};
-    run_captured(voc_part == 1 ? 2 : 1, b, key, 11, run);
+    // (b.d_ctl, b.d_pctl, b.d_cum, b.d_frm_live: a controlled schedule and an uncontrolled one are different graphs, and so are a
+    // fitted and an unfitted one)
+    const void *key[12] = {d_ids, d_puncts, d_styles, d_hidden, d_mel, d_wav, d_nframes, h2d_src, b.d_ctl, b.d_pctl, b.d_cum, b.d_frm_live};
+    run_captured(voc_part == 1 ? 2 : 1, b, key, 12, run);
 }
 
 void Model::vocode_dev_graph(const Batch &b, const float *d_mel, float *d_wav)
@@ -1564,7 +1568,7 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
     if (n_longest > enc_.posenc_rows) fail(ZV_ERR_ARG, "%d phonemes exceed the %d rows of the sinusoid table", n_longest, enc_.posenc_rows);
     arena_require(arena_bytes_for(bt.n_rows, bt.t_rows, bt.nseg));
     arena_.used = 0;
-    const Segs tk = bt.tokens(), fr = bt.frames();
+    const Segs tk = bt.tokens(), fr = bt.frames_cap();       // (the regulator clamps and zero-fills by capacity, fitted or not)
     const Segs tkm = knob(ZV_LINEAR_MERGED) != 0 ? bt.tokens_merged() : tk;      // the per-token layers (linear, 1-tap conv, plain LayerNorm) see one dense segment
     const int Ed = (int)E(), H = hp.encoder_head, dk = Ed / H;
     const size_t n = bt.n_rows;
@@ -1703,6 +1707,9 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
     if (dbg_layer.done) return t;
     ZV_LAUNCH("enc_length_regulator", 4.0 * (nd + (double)bt.t_rows) * Ed, 0.0,
               launch_length_regulator(stream, x, Ed, t.logdur, Ed, d_hidden, Ed, t.cum, d_nframes, tk, fr, bt.d_ctl, bt.d_pctl));
+    // fitted: the frame table of everything downstream, from the counts the regulator has just stored
+    if (bt.d_frm_live)
+        ZV_LAUNCH("enc_live_frames", 36.0 * bt.nseg, 0.0, launch_live_frames(stream, d_nframes, bt.d_frm_live, fr));
     return t;
 }
 

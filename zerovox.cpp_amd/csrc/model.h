@@ -70,6 +70,12 @@ struct Batch
     // where the length regulator stores its scan (the `cum` tap, int32 [n_rows]) when it must outlive the encoder (phoneme timings of a
     // chain: the decoder and the vocoder reuse the arena), or null: the arena
     int32_t *d_cum = nullptr;
+    // Fitted mode: the LIVE frame table, Seg [nseg] in HBM outside the arena, or null.  The encoder writes it behind the length
+    // regulator (live[u] = {d_frm[u].row0, n_frames[u], 0, 0}, kernels.h launch_live_frames) and everything after the regulator —
+    // decoder, vocoder — takes its extents from it, so an utterance is decoded and vocoded as exactly n_frames[u] frames; buffers,
+    // grids and the regulator itself stay by capacity.  A single utterance has a one-entry table.  Keyed like d_ctl: a fitted and
+    // an unfitted schedule are different graphs, and a fitted graph replays for new lengths.
+    Seg *d_frm_live = nullptr;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -87,7 +93,10 @@ struct Batch
     // every token row of the batch as ONE segment (table entry nseg: rows [0, sum of phonemes)) — for the per-token layers, whose row
     // tiles then pack the utterances densely instead of padding every utterance to a tile
     Segs tokens_merged() const { return d_tok ? Segs{d_tok + nseg, 1, (int)n_rows, tok1} : tokens(); }
-    Segs frames() const { return Segs{d_frm, nseg, t_max, frm1}; }
+    // the frames by capacity: buffer layout, the length regulator's clamps and zero fill
+    Segs frames_cap() const { return Segs{d_frm, nseg, t_max, frm1}; }
+    // the frames the decoder and the vocoder run over: the live table in fitted mode, else the capacity
+    Segs frames() const { return d_frm_live ? Segs{d_frm_live, nseg, t_max, frm1} : frames_cap(); }
 };
 
 // a captured schedule: replayed when the same entry point is called with the same capacities and buffers

@@ -120,6 +120,10 @@ class ZeroVOXModel
     void set_phoneme_controls(const zv_phoneme_controls *p, uint32_t n);
     // the phoneme timings of the last eval() after set_phoneme_controls(): frames of each phoneme in the hidden state / waveform
     const std::vector<int32_t> &get_durations() const { return durations; }
+    // fitted synthesis (include/zerovox_amd.h zv_synthesize_fitted) for the eval() calls that follow: max_seq_len stays the
+    // capacity, the utterance is decoded and vocoded as the get_num_frames() frames the length regulator fills, the rest of
+    // get_wav() is zero.  Prosody, per-phoneme controls and timings work as without it.
+    void set_fitted(bool on) { fitted = on; }
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
@@ -144,6 +148,7 @@ class ZeroVOXModel
     uint32_t             pc_n = 0;
     bool                 has_phonemes = false, record_durations = false;
     std::vector<int32_t> durations;
+    bool                 fitted = false;
 };
 
 }  // namespace ZeroVOX

@@ -167,9 +167,9 @@ void ZeroVOXModel::set_phoneme_controls(const zv_phoneme_controls *p, uint32_t n
 void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const float *style_embed, uint32_t num_phonemes)
 {
     const zv_prosody *pr = has_prosody ? &prosody : nullptr;
-    if (record_durations)
+    if (record_durations || fitted)
     {
-        // the per-phoneme entry points (controls and / or timings); N = num_phonemes on both of eval()'s paths
+        // the per-phoneme entry points (controls and / or timings) and the fitted one; N = num_phonemes on both of eval()'s paths
         if (has_phonemes && pc_n != num_phonemes)
         {
             std::string msg = "set_phoneme_controls: controls for " + std::to_string(pc_n) + " phonemes, eval() has " +
@@ -179,7 +179,13 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
         auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
         const zv_phoneme_controls pc = {ptr(pc_frames), ptr(pc_scale), ptr(pc_pitch), ptr(pc_energy)};
         const zv_phoneme_controls *pcp = has_phonemes ? &pc : nullptr;
-        durations.assign(num_phonemes, 0);
+        if (record_durations) durations.assign(num_phonemes, 0);
+        if (fitted)
+        {
+            chk(zv_synthesize_fitted(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr, pcp,
+                                     record_durations ? durations.data() : nullptr));
+            return;
+        }
         if (num_phonemes != (uint32_t)MAX_N_PHONEMES)
         {
             chk(zv_synthesize_phonemes(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr, pcp,

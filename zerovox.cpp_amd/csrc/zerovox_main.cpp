@@ -9,7 +9,7 @@
 //     line 2: punctuation ids        (N integers)
 //     line 3: style embedding        (emb_dim + punct_emb_dim floats; a single 0 means the zero vector)
 //
-// usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--info] [prosody flags]
+// usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info] [prosody flags]
 //   --duration-scale S, --pitch-scale S, --pitch-shift D, --energy-scale S, --energy-shift D
 //            prosody controls (include/zerovox_amd.h zv_prosody): durations * S (0 < S <= 16), pitch / energy predictions
 //            p * S + D before bucketing; defaults 1, 1, 0, 1, 0 (the uncontrolled result).  A bad value is a usage error.
@@ -21,6 +21,9 @@
 //            write the phoneme timings as TSV: index, phoneme_id, start_frame, frames, start_sample, samples
 //   --trim   write only the frames the length regulator produced (the reference always writes max_seq_len frames,
 //            src/zerovox.cpp:369)
+//   --fit    fitted synthesis (include/zerovox_amd.h zv_synthesize_fitted): decode and vocode only the frames the length regulator
+//            produced, and write exactly those n_frames * hop samples — the audio of the utterance at its own length, where --trim
+//            cuts the file of the max_seq_len-frame run.  Works with the prosody flags, --phoneme-controls and --alignment.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
 #include <cmath>
 #include <cstdio>
@@ -39,7 +42,7 @@ static const char *k_default_out = "foo.wav";                   // reference src
 
 static void usage(FILE *f)
 {
-    fprintf(f, "usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--info]\n"
+    fprintf(f, "usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info]\n"
                "               [--duration-scale S] [--pitch-scale S] [--pitch-shift D] [--energy-scale S] [--energy-shift D]\n"
                "               [--phoneme-controls FILE] [--alignment FILE]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
@@ -51,7 +54,9 @@ static void usage(FILE *f)
                "  --energy-shift D     (see --energy-scale), default 0\n"
                "  --phoneme-controls FILE  one line per phoneme: frames scale pitch_shift energy_shift (identity: -1 1 0 0;\n"
                "                       frames -1 keeps the prediction, 0..32768 forces it; 0 < scale <= 16)\n"
-               "  --alignment FILE     write the phoneme timings as TSV: index phoneme_id start_frame frames start_sample samples\n",
+               "  --alignment FILE     write the phoneme timings as TSV: index phoneme_id start_frame frames start_sample samples\n"
+               "  --trim               write only the frames the length regulator produced (cut from the max_seq_len-frame run)\n"
+               "  --fit                synthesize only those frames (the utterance at its own length) and write them\n",
             k_default_model, k_default_out);
 }
 
@@ -147,7 +152,7 @@ static std::vector<int32_t> utterance_ids(const std::string &utt_path)
 int main(int argc, char **argv)
 {
     std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path;
-    bool trim = false, info = false, controlled = false;
+    bool trim = false, fit = false, info = false, controlled = false;
     zv_prosody prosody = {1.0f, 1.0f, 0.0f, 1.0f, 0.0f};
     for (int i = 1; i < argc; i++)
     {
@@ -162,6 +167,7 @@ int main(int argc, char **argv)
         else if (a == "--phoneme-controls") pc_path = need("--phoneme-controls");
         else if (a == "--alignment") align_path = need("--alignment");
         else if (a == "--trim") trim = true;
+        else if (a == "--fit") fit = true;
         else if (a == "--info") info = true;
         else if (a == "--duration-scale" || a == "--pitch-scale" || a == "--pitch-shift" || a == "--energy-scale" || a == "--energy-shift")
         {
@@ -216,6 +222,7 @@ int main(int argc, char **argv)
         ZeroVOX::ZeroVOXModel model(model_path);
         const ZeroVOX::zerovox_hparams &hp = model.get_hparams();
         if (controlled) model.set_prosody(prosody);
+        if (fit) model.set_fitted(true);
         if (!pc_path.empty())
         {
             const zv_phoneme_controls pc = {pcf.frames.data(), pcf.scale.data(), pcf.pitch.data(), pcf.energy.data()};
@@ -260,7 +267,7 @@ int main(int argc, char **argv)
             }
             if (fclose(af) != 0) throw std::runtime_error("short write to '" + align_path + "'");
         }
-        if (trim)
+        if (trim || fit)
         {
             const size_t n = (size_t)nf * hp.audio_hop_size;
             if (zv_write_wav(out_path.c_str(), model.get_wav(), n, hp.audio_sampling_rate) != ZV_OK)
