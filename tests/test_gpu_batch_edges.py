@@ -1,7 +1,7 @@
 """-m gpu: ragged batches at the production geometry (synth.MEDIUM) against stand-alone calls, under every kernel regime.
 
 A batch is one launch per kernel over segment tables (one Seg per utterance + one spanning the batch, capi.cpp); the kernels that
-only batches select are chosen from the rows a launch covers, Lbatch = t_max x rate x nseg (model.cpp, t_max = the longest T
+only batches select are chosen from the rows a launch covers, Lbatch = t_max x rate x nseg (vocoder.cpp, t_max = the longest T
 rounded up to 64), with n_cu = 256.  Composition (a) has 18 utterances, T from 1 to 1 500 (t_max = 1 536), so:
   * conv_gemm_kernel for the two deep upsample convs (ZV_UP_GEMM): L = t_max x nseg = 27 648 >= 16 384 input rows;
   * resblock_block64_kernel (64 channels, rate 100): Lbatch / 244 = 11 331 >= 4 x 256;

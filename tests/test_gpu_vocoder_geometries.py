@@ -11,7 +11,7 @@ so does the loader, which packs fused weights per pair where both convs share a 
   * medium_rb_c1c2: convs1 / convs2 of 7 / 3 and 11 / 13 taps in one pair (never fused), a convs2 wider than every convs1;
   * medium_rb_c2wide: every convs2 of the 11-tap branch has 25 taps (never fused): a receptive radius of 25 frames, which a halo
     that left out convs2 (23) would not cover.
-Not reached by any geometry: model.cpp's one-K guard on the block64 path (two pairs of different K at dilations 0 and 1 of a
+Not reached by any geometry: vocoder.cpp's one-K guard on the block64 path (two pairs of different K at dilations 0 and 1 of a
 64-channel branch).  A checkpoint that reaches it safely on a library without the guard would need dilation 1 wider than
 dilation 0 in every stage, with the 32-channel whole-block kernel kept off.
 Checked: every residual block alone against the oracle (default and batch kernels, same bits), the whole vocoder against the
@@ -23,7 +23,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 WAV_RMS_GATE = 1e-4                 # tests/test_gpu_vocoder.py
-BUILD_SWITCHES = ("ZV_NO_FUSE", "ZV_NO_TRIPLE", "ZV_FUSE256", "ZV_NO_MERGE", "ZV_TAIL_GROUPS")     # sampled by Model() (model.cpp)
+BUILD_SWITCHES = ("ZV_NO_FUSE", "ZV_NO_TRIPLE", "ZV_FUSE256", "ZV_NO_MERGE", "ZV_TAIL_GROUPS")     # sampled by Model() (model_load.cpp)
 ZV_ERR_SHAPE = 4
 
 

@@ -4,7 +4,7 @@ that put each kernel's row count on both sides of its tile heights, every length
 Vocoder stages: 256 / 128 / 64 / 32 channels at 5 / 25 / 100 / 300 rows per mel frame (rows = T x rate).  Output rows per
 tile (TM = rows a workgroup stores, from the launch_* functions of conv1d_mfma.hip; K = 3 / 7 / 11 taps, Kmax = 11 sizes the grid):
   * resblock_pair_kernel<256>: BM = 32 MT (4 / 4) rows less K - 1 halo rows -> 62 / 58 / 54 (MT = 2, ZV_FUSE256 or
-    T >= 929 by itself: enough_rows, model.cpp, floor(5 T / 54) x 3 >= 256 CUs) and 94 / 90 / 86 (the batches' 96-row tiles, MT = 3);
+    T >= 929 by itself: enough_rows, vocoder.cpp, floor(5 T / 54) x 3 >= 256 CUs) and 94 / 90 / 86 (the batches' 96-row tiles, MT = 3);
   * resblock_pair_kernel<128>: 62 / 58 / 54 (MT = 2) and 126 / 122 / 118 (MT = 4; the merged MRF sum's 118-row tile);
   * resblock_pair_kernel<64>: 126 / 122 / 118; resblock_pair64_kernel (LDS weight ring): 257 - K = 254 / 250 / 246 (the merged
     sum's 246-row tile); resblock_block64_kernel (two dilation pairs, dil 1 and 3): 256 - 2 h (1 + 3 + 2) = 244 at K = 3;
@@ -19,7 +19,7 @@ order vs sequential f32); the same bits from models built under the batch regime
 pair<256> tiles (ZV_PAIR_MT = 3) and with the merged MRF sum (ZV_MERGE_ALWAYS); and the prefix property (the first T frames of
 vocode(mel[:T + H]) are those of the long utterance).
 
-Decoder at T = 255 / 256 / 257 / 513: the operand pre-pass threshold (t_max x nseg >= 256, model.cpp) and conv_gemm_kernel's
+Decoder at T = 255 / 256 / 257 / 513: the operand pre-pass threshold (t_max x nseg >= 256, decoder.cpp) and conv_gemm_kernel's
 256-row tiles (one tile, one tile + 1 row, two tiles + 1 row), against the oracle with the gate of
 test_gpu_decoder_encoder.py::test_medium_geometry_length_sweep, and the same bits under ZV_CONV_GEMM = 2, ZV_GEMM_ORDER = 0 and
 ZV_DEC_PREPASS = 0 / 1."""

@@ -334,32 +334,32 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         std::vector<int32_t> cum(dur ? n : 0);
         pack_controls(r, ctl.data(), pctl.data());
         zv::Batch bt = zv::Batch::single(n, T, r.num_phonemes[0]);
-        ZV_HIP(hipMemcpyAsync(d_ids, r.ids[0], b_ids, hipMemcpyHostToDevice, M.stream));
-        ZV_HIP(hipMemcpyAsync(d_pun, r.puncts[0], b_ids, hipMemcpyHostToDevice, M.stream));
-        ZV_HIP(hipMemcpyAsync(d_sty, r.styles[0], E * 4, hipMemcpyHostToDevice, M.stream));
+        ZV_HIP(hipMemcpyAsync(d_ids, r.ids[0], b_ids, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(d_pun, r.puncts[0], b_ids, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(d_sty, r.styles[0], E * 4, hipMemcpyHostToDevice, M.stream()));
         if (b_ctl)
         {
             bt.d_ctl = (const float *)(io + o_ctl);
-            ZV_HIP(hipMemcpyAsync(io + o_ctl, ctl.data(), b_ctl, hipMemcpyHostToDevice, M.stream));
+            ZV_HIP(hipMemcpyAsync(io + o_ctl, ctl.data(), b_ctl, hipMemcpyHostToDevice, M.stream()));
         }
         if (b_pctl)
         {
             bt.d_pctl = (const float *)(io + o_pctl);
-            ZV_HIP(hipMemcpyAsync(io + o_pctl, pctl.data(), b_pctl, hipMemcpyHostToDevice, M.stream));
+            ZV_HIP(hipMemcpyAsync(io + o_pctl, pctl.data(), b_pctl, hipMemcpyHostToDevice, M.stream()));
         }
         int32_t nf = 0;
         if (taps)
         {
             const Model::EncoderTaps t = M.encode_dev(bt, d_ids, d_pun, d_sty, d_hid, d_nf);
-            ZV_HIP(hipMemcpyAsync(r.out[0], d_hid, b_hid, hipMemcpyDeviceToHost, M.stream));
-            ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
-            if (taps->features) ZV_HIP(hipMemcpyAsync(taps->features, t.features, (size_t)n * E * 4, hipMemcpyDeviceToHost, M.stream));
-            if (taps->logdur) ZV_HIP(hipMemcpyAsync(taps->logdur, t.logdur, b_ids, hipMemcpyDeviceToHost, M.stream));
-            if (taps->pitch) ZV_HIP(hipMemcpyAsync(taps->pitch, t.pitch, b_ids, hipMemcpyDeviceToHost, M.stream));
-            if (taps->energy) ZV_HIP(hipMemcpyAsync(taps->energy, t.energy, b_ids, hipMemcpyDeviceToHost, M.stream));
-            if (taps->pitch_bucket) ZV_HIP(hipMemcpyAsync(taps->pitch_bucket, t.pitch_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
-            if (taps->energy_bucket) ZV_HIP(hipMemcpyAsync(taps->energy_bucket, t.energy_bucket, b_ids, hipMemcpyDeviceToHost, M.stream));
-            if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), t.cum, b_ids, hipMemcpyDeviceToHost, M.stream));
+            ZV_HIP(hipMemcpyAsync(r.out[0], d_hid, b_hid, hipMemcpyDeviceToHost, M.stream()));
+            ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream()));
+            if (taps->features) ZV_HIP(hipMemcpyAsync(taps->features, t.features, (size_t)n * E * 4, hipMemcpyDeviceToHost, M.stream()));
+            if (taps->logdur) ZV_HIP(hipMemcpyAsync(taps->logdur, t.logdur, b_ids, hipMemcpyDeviceToHost, M.stream()));
+            if (taps->pitch) ZV_HIP(hipMemcpyAsync(taps->pitch, t.pitch, b_ids, hipMemcpyDeviceToHost, M.stream()));
+            if (taps->energy) ZV_HIP(hipMemcpyAsync(taps->energy, t.energy, b_ids, hipMemcpyDeviceToHost, M.stream()));
+            if (taps->pitch_bucket) ZV_HIP(hipMemcpyAsync(taps->pitch_bucket, t.pitch_bucket, b_ids, hipMemcpyDeviceToHost, M.stream()));
+            if (taps->energy_bucket) ZV_HIP(hipMemcpyAsync(taps->energy_bucket, t.energy_bucket, b_ids, hipMemcpyDeviceToHost, M.stream()));
+            if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), t.cum, b_ids, hipMemcpyDeviceToHost, M.stream()));
         }
         else
         {
@@ -367,9 +367,9 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
             if (dur) bt.d_cum = (int32_t *)(io + o_cum);
             if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
-            ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream));
-            if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), bt.d_cum, b_ids, hipMemcpyDeviceToHost, M.stream));
-            ZV_HIP(hipMemcpyAsync(r.out[0], d_wav, b_wav, hipMemcpyDeviceToHost, M.stream));
+            ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream()));
+            if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), bt.d_cum, b_ids, hipMemcpyDeviceToHost, M.stream()));
+            ZV_HIP(hipMemcpyAsync(r.out[0], d_wav, b_wav, hipMemcpyDeviceToHost, M.stream()));
         }
         M.sync();
         if (r.n_frames) r.n_frames[0] = (uint32_t)nf;
@@ -421,10 +421,10 @@ zv_status zv_decode(zv_model *m, const float *hidden, const float *style, uint32
         const size_t o_sty = L.at(E * 4), o_hid = L.at(b_hid), o_mel = L.at(b_mel);
         char *io = (char *)M.io_scratch(L.size());
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel);
-        ZV_HIP(hipMemcpyAsync(d_hid, hidden, b_hid, hipMemcpyHostToDevice, M.stream));
-        ZV_HIP(hipMemcpyAsync(d_sty, style, E * 4, hipMemcpyHostToDevice, M.stream));
+        ZV_HIP(hipMemcpyAsync(d_hid, hidden, b_hid, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(d_sty, style, E * 4, hipMemcpyHostToDevice, M.stream()));
         M.decode_dev(zv::Batch::single(1, T, 1), d_hid, d_sty, d_mel);
-        ZV_HIP(hipMemcpyAsync(mel, d_mel, b_mel, hipMemcpyDeviceToHost, M.stream));
+        ZV_HIP(hipMemcpyAsync(mel, d_mel, b_mel, hipMemcpyDeviceToHost, M.stream()));
         M.sync();
     });
 }
@@ -441,9 +441,9 @@ zv_status zv_vocode(zv_model *m, const float *mel, uint32_t T, float *wav)
         const size_t o_mel = L.at(b_mel), o_wav = L.at(b_wav);
         char *io = (char *)M.io_scratch(L.size());
         float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
-        ZV_HIP(hipMemcpyAsync(d_mel, mel, b_mel, hipMemcpyHostToDevice, M.stream));
+        ZV_HIP(hipMemcpyAsync(d_mel, mel, b_mel, hipMemcpyHostToDevice, M.stream()));
         M.vocode_dev_graph(zv::Batch::single(1, T, 1), d_mel, d_wav);
-        ZV_HIP(hipMemcpyAsync(wav, d_wav, b_wav, hipMemcpyDeviceToHost, M.stream));
+        ZV_HIP(hipMemcpyAsync(wav, d_wav, b_wav, hipMemcpyDeviceToHost, M.stream()));
         M.sync();
     });
 }
@@ -482,7 +482,7 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
         };
         try
         {
-            ZV_HIP(hipMemcpyAsync(d_mel, mel, (size_t)T * Mm * 4, hipMemcpyHostToDevice, M.stream));
+            ZV_HIP(hipMemcpyAsync(d_mel, mel, (size_t)T * Mm * 4, hipMemcpyHostToDevice, M.stream()));
             int k = 0;
             for (uint32_t a = 0; a < T; a += chunk_frames, k ^= 1)
             {
@@ -490,8 +490,8 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
                 const uint32_t c0 = a > H ? a - H : 0, c1 = std::min<uint64_t>(T, (uint64_t)b + H);
                 deliver(k);                                   // the slot we are about to overwrite
                 M.vocode_dev(zv::Batch::single(1, c1 - c0, 1), d_mel + (size_t)c0 * Mm, d_wav);
-                ZV_HIP(hipMemcpyAsync(pin + slot[k], d_wav + (size_t)(a - c0) * hop, (size_t)(b - a) * hop * 4, hipMemcpyDeviceToHost, M.stream));
-                ZV_HIP(hipEventRecord(done[k], M.stream));
+                ZV_HIP(hipMemcpyAsync(pin + slot[k], d_wav + (size_t)(a - c0) * hop, (size_t)(b - a) * hop * 4, hipMemcpyDeviceToHost, M.stream()));
+                ZV_HIP(hipEventRecord(done[k], M.stream()));
                 pend[k] = {true, (uint64_t)a * hop, (uint64_t)(b - a) * hop};
                 deliver(k ^ 1);                               // the previous chunk, while this one runs
             }
@@ -500,7 +500,7 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
         }
         catch (...)
         {
-            hipStreamSynchronize(M.stream);
+            hipStreamSynchronize(M.stream());
             hipEventDestroy(done[0]);
             hipEventDestroy(done[1]);
             throw;
@@ -704,21 +704,21 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         // without a profiler: 0.00 ms per step with two batches in flight; a device-side limit of two concurrent batches with a
         // third queued behind them, built to close gaps a kernel trace had shown, changed nothing and was removed again.)
         const uint64_t seq = M.next_batch_seq();
-        ZV_HIP(hipEventRecord(M.batch_event(seq, 0), M.stream));
+        ZV_HIP(hipEventRecord(M.batch_event(seq, 0), M.stream()));
         if (G <= 1)
         {
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, h_in, d_in, b_in);
-            ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream));
-            ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream));
-            if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream));
-            ZV_HIP(hipMemcpyAsync(h_wav, d_wav, wav_bytes, hipMemcpyDeviceToHost, M.stream));
-            ZV_HIP(hipEventRecord(M.tail_event(1), M.stream));
+            ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream()));
+            ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream()));
+            if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream()));
+            ZV_HIP(hipMemcpyAsync(h_wav, d_wav, wav_bytes, hipMemcpyDeviceToHost, M.stream()));
+            ZV_HIP(hipEventRecord(M.tail_event(1), M.stream()));
         }
         else
         {
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, h_in, d_in, b_in, 1);
-            ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream));
-            if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream));
+            ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream()));
+            if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream()));
             for (int g = 1; g < G; g++)               // contiguous groups of about wav_bytes / G each
             {
                 uint32_t u = pb.gb[g - 1] + 1;
@@ -730,17 +730,17 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
                 const uint32_t u0 = pb.gb[g], u1 = pb.gb[g + 1];
                 M.vocode_tail(bt, d_mel, d_wav, (int)u0, (int)(u1 - u0));
                 const size_t o0 = pb.woff[u0], o1 = u1 < r.count ? pb.woff[u1] : wav_bytes;
-                ZV_HIP(hipEventRecord(M.tail_event(2 * g), M.stream));
+                ZV_HIP(hipEventRecord(M.tail_event(2 * g), M.stream()));
                 ZV_HIP(hipStreamWaitEvent(cs, M.tail_event(2 * g), 0));
                 ZV_HIP(hipMemcpyAsync(h_wav + o0, (const char *)d_wav + o0, o1 - o0, hipMemcpyDeviceToHost, cs));
                 ZV_HIP(hipEventRecord(M.tail_event(2 * g + 1), cs));
             }
-            ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream));
+            ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream()));
         }
     }
     catch (...)
     {
-        hipStreamSynchronize(M.stream);
+        hipStreamSynchronize(M.stream());
         if (M.copy_stream()) hipStreamSynchronize(M.copy_stream());
         throw;
     }
@@ -777,7 +777,7 @@ static void batch_finish(zv_model *m, int lane)
     catch (...)
     {
         // a failed wait: drain what can be drained, then give the lane up as idle (its buffers are no longer in use)
-        hipStreamSynchronize(M.stream);
+        hipStreamSynchronize(M.stream());
         if (M.copy_stream()) hipStreamSynchronize(M.copy_stream());
         pb.active = false;
         throw;
@@ -983,9 +983,9 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
             const size_t b_mel = (size_t)T * Mm * 4, o_mel = L.at(b_mel), o_wav = L.at((size_t)T * hop * 4);
             char *io = (char *)M.io_scratch(L.size());
             if (kind == ZV_LAYER_VOC_INPUT)
-                ZV_HIP(hipMemcpyAsync(io + o_mel, x, b_mel, hipMemcpyHostToDevice, M.stream));      // the layer's input IS the mel
+                ZV_HIP(hipMemcpyAsync(io + o_mel, x, b_mel, hipMemcpyHostToDevice, M.stream()));      // the layer's input IS the mel
             else
-                ZV_HIP(hipMemsetAsync(io + o_mel, 0, b_mel, M.stream));
+                ZV_HIP(hipMemsetAsync(io + o_mel, 0, b_mel, M.stream()));
             M.vocode_dev(zv::Batch::single(1, T, 1), (const float *)(io + o_mel), (float *)(io + o_wav));
         }
         else if (kind == ZV_LAYER_ENC_FFT || kind == ZV_LAYER_VAR_PRED || kind == ZV_LAYER_ENC_EMBED || kind == ZV_LAYER_ENC_MHA ||
@@ -998,7 +998,7 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
             char *io = (char *)M.io_scratch(L.size());
             int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
             float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
-            ZV_HIP(hipMemsetAsync(io, 0, o_sty, M.stream));                 // frame count, ids and puncts: all in front of the style
+            ZV_HIP(hipMemsetAsync(io, 0, o_sty, M.stream()));                 // frame count, ids and puncts: all in front of the style
             std::vector<int32_t> hid, hpu;
             if (kind == ZV_LAYER_ENC_EMBED)
             {
@@ -1011,11 +1011,11 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
                     hpu[i] = (int32_t)x[2 * i + 1];
                 }
                 check_ids(M, hid.data(), hpu.data(), n);
-                ZV_HIP(hipMemcpyAsync(d_ids, hid.data(), (size_t)n * 4, hipMemcpyHostToDevice, M.stream));
-                ZV_HIP(hipMemcpyAsync(d_pun, hpu.data(), (size_t)n * 4, hipMemcpyHostToDevice, M.stream));
-                ZV_HIP(hipStreamSynchronize(M.stream));            // the staging vectors go out of scope below
+                ZV_HIP(hipMemcpyAsync(d_ids, hid.data(), (size_t)n * 4, hipMemcpyHostToDevice, M.stream()));
+                ZV_HIP(hipMemcpyAsync(d_pun, hpu.data(), (size_t)n * 4, hipMemcpyHostToDevice, M.stream()));
+                ZV_HIP(hipStreamSynchronize(M.stream()));            // the staging vectors go out of scope below
             }
-            ZV_HIP(hipMemcpyAsync(d_sty, sty, E * 4, hipMemcpyHostToDevice, M.stream));
+            ZV_HIP(hipMemcpyAsync(d_sty, sty, E * 4, hipMemcpyHostToDevice, M.stream()));
             M.encode_dev(zv::Batch::single(n, T, n), d_ids, d_pun, d_sty, d_hid, d_nf);
         }
         else if (kind == ZV_LAYER_DEC_BLOCK || kind == ZV_LAYER_DEC_ASR_RES || kind == ZV_LAYER_DEC_TO_OUT || kind == ZV_LAYER_DEC_ADAIN)
@@ -1027,10 +1027,10 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
             char *io = (char *)M.io_scratch(L.size());
             float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel);
             if (kind == ZV_LAYER_DEC_ASR_RES)
-                ZV_HIP(hipMemcpyAsync(d_hid, x, (size_t)T * E * 4, hipMemcpyHostToDevice, M.stream));     // asr_res reads the stage input itself
+                ZV_HIP(hipMemcpyAsync(d_hid, x, (size_t)T * E * 4, hipMemcpyHostToDevice, M.stream()));     // asr_res reads the stage input itself
             else
-                ZV_HIP(hipMemsetAsync(d_hid, 0, o_mel - o_hid, M.stream));                               // the region, padding included
-            ZV_HIP(hipMemcpyAsync(d_sty, sty, E * 4, hipMemcpyHostToDevice, M.stream));
+                ZV_HIP(hipMemsetAsync(d_hid, 0, o_mel - o_hid, M.stream()));                               // the region, padding included
+            ZV_HIP(hipMemcpyAsync(d_sty, sty, E * 4, hipMemcpyHostToDevice, M.stream()));
             M.decode_dev(zv::Batch::single(1, T, 1), d_hid, d_sty, d_mel);
         }
         else if (kind == ZV_LAYER_ENC_LN)
@@ -1092,7 +1092,7 @@ zv_status zv_memcpy_h2d(zv_model *m, void *dst, const void *src, size_t bytes)
         // lane 0's stream, the one zv_vocode_device / zv_decode_device run on, whatever lane was touched last (the lanes' streams
         // are not ordered with each other); no busy check: the copy only queues behind what lane 0 already holds
         lane0_select(m);
-        ZV_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, m->m->stream));
+        ZV_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, m->m->stream()));
         m->m->sync();
     });
 }
@@ -1102,7 +1102,7 @@ zv_status zv_memcpy_d2h(zv_model *m, void *dst, const void *src, size_t bytes)
     return guarded([&] {
         ZV_NEED(m && dst && src, "null argument");
         lane0_select(m);
-        ZV_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, m->m->stream));
+        ZV_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, m->m->stream()));
         m->m->sync();
     });
 }

@@ -1,0 +1,239 @@
+// decoder.cpp — the StyleTTS mel decoder's arena layout and kernel schedule (see model.h).
+#include "schedule.h"
+
+#include <cmath>
+
+namespace zv
+{
+
+// The decoder's buffers: per-segment vectors and statistics partials, then the [t_rows] activations and f16 operands.
+Model::DecLayout Model::dec_layout(DeviceArena &a, const Batch &bt) const
+{
+    const size_t S = (size_t)bt.nseg, L = bt.t_rows, B = 2 * E(), R = (size_t)dec_.R, CAT = B + R;
+    DecLayout d{(bt.t_max + 31) / 32, round_up(dec_.fc_out + 64, 64), 2 * (int)CAT + 64};
+    d.h = a.take_n<float>(S * d.hs);
+    for (float **st : {&d.st_x, &d.st_t, &d.st_y, &d.st_a}) *st = a.take_n<float>(S * d.ss);
+    for (double **p : {&d.part_t, &d.part_o}) *p = a.take_n<double>(S * d.nblk * CAT * 2);
+    d.cat = a.take_n<float>(L * CAT);
+    for (float **x : {&d.t1, &d.sc, &d.x0, &d.xa}) *x = a.take_n<float>(L * B);
+    d.asr_t = a.take_n<float>(L * R);
+    d.xa16 = a.take_n<_Float16>(L * CAT);
+    d.t16 = a.take_n<_Float16>(L * B);
+    d.xr16 = a.take_n<_Float16>(L * CAT);
+    return d;
+}
+
+// StyleTTS mel decoder (reference src/stylettsdec.cpp:306-470)
+void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_styles, float *d_mel)
+{
+    if (bt.t_rows == 0 || bt.t_max <= 0) fail(ZV_ERR_ARG, "T must be > 0");
+    const DecLayout lay = dec_layout(stage_arena(bt), bt);
+    const Segs fr = bt.frames();
+    const int Ed = (int)E(), B = 2 * Ed, R = dec_.R, CAT = B + R, S = bt.nseg;
+    const size_t L = bt.t_rows;
+    const int nblk = lay.nblk, hs = lay.hs, ss = lay.ss;
+    float *const h = lay.h, *const st_x = lay.st_x, *const st_t = lay.st_t, *const st_y = lay.st_y, *const st_a = lay.st_a;
+    double *const part_t = lay.part_t, *const part_o = lay.part_o;
+    float *const cat = lay.cat, *const t1 = lay.t1, *const sc = lay.sc, *const x0 = lay.x0, *const xa = lay.xa, *const asr_t = lay.asr_t;
+    _Float16 *const xa16 = lay.xa16, *const t16 = lay.t16, *const xr16 = lay.xr16;
+    const double Ld = (double)L;
+    // Two ways to feed a conv its normalised operand, same bits (tests): (a) the conv normalises while it stages its
+    // input tile (PRO_NORM_ACT) — no extra launch, right for a very short utterance where every launch is latency; (b) one
+    // pass writes the f16 operand (launch_norm_act_f16) and the conv copies it (PRO_RAW_F16) — right when launches have
+    // many rounds of workgroups: a 1 056-wide conv stages every input tile 9 times (once per group of 128 output
+    // channels), so (a) repeats the f32 prologue 9 times and reads twice the bytes.
+    const int pre_env = knob(ZV_DEC_PREPASS);      // test / A-B hook
+    // (round 4: with the single-utterance conv form's loader waves the pass pays from 256 frames on — it takes the statistics launch's
+    // place and leaves the loaders a plain copy: one utterance of 128 / 256 / 512 / 1 024 frames 1.32 / 1.345 / 1.62 / 2.16 ms fused,
+    // 1.33 / 1.33 / 1.58 / 2.07 ms with the pass)
+    const bool prepass = pre_env >= 0 ? pre_env != 0 : (size_t)bt.t_max * bt.nseg >= 256;
+
+    // D2: all ten AdaIN fc layers at once for every utterance's style vector            (src/stylettsdec.cpp:175-189)
+    ZV_LAUNCH("dec_adain_fc", 4.0 * dec_.fc_out * (Ed + 2), 2.0 * S * dec_.fc_out * Ed,
+              launch_linear(stream(), d_styles, Ed, Ed, dec_.fcW, dec_.fcB, dec_.fc_out, h, hs, dec_.fcExtra, segs_single(S)));
+
+    const float rsqrt2 = (float)(1.0 / sqrt(2.0));                       // src/stylettsdec.cpp:146,301
+
+    auto finalize = [&](const double *part, int C, float *stat, int c_off) {
+        ZV_LAUNCH("dec_in_stats", 16.0 * S * nblk * C, 4.0 * S * nblk * C,
+                  launch_stats_finalize(stream(), part, nblk, C, 1e-5f, stat, ss, c_off, fr, 1));
+    };
+    // make `j` read lrelu(norm(x)) with x's statistics still in `part` (channels [0, Cpart)); stores them in `stat`
+    auto norm_input = [&](ConvJob &j, const float *x, int ldx, int C, const double *part, int Cpart, float *stat, const float *g,
+                          const float *b, int gb_seg, _Float16 *op16, _Float16 *raw16 = nullptr) {
+        if (prepass)
+        {
+            ZV_LAUNCH("dec_norm_operand", 6.0 * Ld * C, 8.0 * Ld * C,
+                      launch_norm_act_f16(stream(), x, ldx, C, part, nblk, Cpart, 1e-5f, stat, ss, g, b, gb_seg, 0.2f, op16, C, fr, raw16));
+            j.x0 = op16;
+            j.ldx = C;
+            j.pro = PRO_RAW_F16;
+        }
+        else
+        {
+            finalize(part, Cpart, stat, 0);
+            j.x0 = x;
+            j.ldx = ldx;
+            j.pro = PRO_NORM_ACT;
+            j.pstat = stat;
+            j.pstat_seg = ss;
+            j.pa = g;
+            j.pb = b;
+            j.pab_seg = gb_seg;
+            j.slope = 0.2f;
+        }
+    };
+
+    // InstanceNorm statistics of the stage input (it comes from the encoder or the host, not from a conv of ours)
+    ZV_LAUNCH("dec_in_stats", 4.0 * Ld * Ed, 3.0 * Ld * Ed, launch_stats_partial(stream(), d_hidden, Ed, Ed, part_o, nblk, fr, 1));
+
+    // one residual block: IN/AdaIN -> lrelu -> conv1 -> IN/AdaIN -> lrelu -> conv2 -> (+ shortcut) / sqrt2.
+    // The partial sums of x's statistics are in part_o (channels [0, Cpart) of x; the others are final in st_in already);
+    // the block leaves the partial sums of its output in part_o again when want_stats.  gb_seg: per-segment stride of the
+    // affine vectors (0 for the encode blocks' shared InstanceNorm weights, hs for the decode blocks' AdaIN vectors).
+    int blk_no = 0;              // 0,1: encode blocks; 2..6: decode blocks (dbg_layer.index)
+    auto block = [&](const DecBlk &b, const float *x, int ldx, int Cpart, float *st_in, const float *g1, const float *b1,
+                     const float *g2, const float *b2, int gb_seg, float *out, int ldo, bool want_stats) {
+        const bool dbg_here = dbg_layer.kind == 2 && dbg_layer.index == blk_no && !dbg_layer.done;
+        blk_no++;
+        if (dbg_layer.done) return;
+        if (dbg_here)
+        {   // the layer's input comes from the host; its statistics are recomputed for every channel
+            dbg_inject(const_cast<float *>(x), ldx, b.cin, L);
+            ZV_HIP(launch_stats_partial(stream(), x, ldx, b.cin, part_o, nblk, fr, 1));
+            Cpart = b.cin;
+        }
+        const float *res = x;
+        int ldres = ldx;
+        ConvJob jj[2];
+        int nj = 0;
+        {
+            ConvJob j = job(b.conv1);
+            // (a learned shortcut reads f16(x): with the pre-pass on, that operand is written by the same pass)
+            norm_input(j, x, ldx, b.cin, part_o, Cpart, st_in, g1, b1, gb_seg, xa16, b.learned_sc ? xr16 : nullptr);
+            j.out = t1;
+            j.stat_part = part_t;
+            j.stat_nblk = nblk;
+            j.stat_C = b.conv1.Cout;
+            jj[nj++] = j;
+        }
+        double bytes = conv_bytes(Ld, b.cin, b.conv1.Cout, 3, false), flops = conv_flops(Ld, b.cin, b.conv1.Cout, 3);
+        if (b.learned_sc)
+        {
+            ConvJob j = job(b.sc);
+            j.x0 = x;
+            j.ldx = ldx;
+            if (prepass)
+            {
+                j.x0 = xr16;
+                j.ldx = b.cin;
+                j.pro = PRO_RAW_F16;
+            }
+            j.out = sc;
+            res = sc;
+            ldres = b.sc.Cout_p;
+            const double sb = conv_bytes(Ld, b.cin, b.cout, 1, false), sf = conv_flops(Ld, b.cin, b.cout, 1);
+            if (b.sc.Cout_p == b.conv1.Cout_p)
+            {   // same output width as conv1: second job of the same launch
+                jj[nj++] = j;
+                bytes += sb;
+                flops += sf;
+            }
+            else
+                conv(&j, 1, fr, 1, "dec_conv", sb, sf);
+        }
+        conv(jj, nj, fr, 1, "dec_conv", bytes, flops);
+        const int Cm = b.conv1.Cout;
+        {
+            ConvJob j = job(b.conv2);
+            norm_input(j, t1, b.conv1.Cout_p, Cm, part_t, Cm, st_t, g2, b2, gb_seg, t16);
+            j.res = res;
+            j.ldres = ldres;
+            j.escale = rsqrt2;
+            j.out = out;
+            j.ldo = ldo;
+            if (want_stats)
+            {
+                j.stat_part = part_o;
+                j.stat_nblk = nblk;
+                j.stat_C = b.cout;
+            }
+            conv(&j, 1, fr, 1, "dec_conv", conv_bytes(Ld, Cm, b.cout, 3, true), conv_flops(Ld, Cm, b.cout, 3));
+        }
+        if (dbg_here) dbg_extract(out, ldo, b.cout, L);
+    };
+
+    // AdaIN1d alone (sub-block tap, ZV_LAYER_DEC_ADAIN; index = 2 * decode block + (norm - 1); reference src/stylettsdec.cpp:171-200):
+    // the production fc GEMM above, the production statistics (partial sums + finalise) and the prologue's arithmetic
+    // ((x - mean) * rstd) * gamma + beta written out by norm_apply_kernel — no activation, no conv
+    if (dbg_layer.kind == ZV_LAYER_DEC_ADAIN)
+    {
+        const int bi = dbg_layer.index / 2, k = dbg_layer.index & 1;
+        if (bi < 0 || bi >= 5) return;
+        const DecBlk &b = dec_.dec[bi];
+        const int Cn = k ? b.cout : b.cin, go = k ? b.g2 : b.g1;
+        float *xin = cat;                                  // [L][Cn] with leading dimension Cn: any buffer of L * CAT floats
+        dbg_inject(xin, Cn, Cn, L);
+        ZV_HIP(launch_stats_partial(stream(), xin, Cn, Cn, part_o, nblk, fr, 1));
+        ZV_HIP(launch_stats_finalize(stream(), part_o, nblk, Cn, 1e-5f, st_x, ss, 0, fr, 1));
+        ZV_HIP(launch_norm_apply(stream(), xin, Cn, Cn, st_x, ss, h + go, h + go + Cn, t1, Cn, nullptr, nblk, fr));
+        dbg_extract(t1, Cn, Cn, L);
+        return;
+    }
+
+    // encode0 / encode1: ResBlk1d with affine InstanceNorm                         (src/stylettsdec.cpp:69-149,373-374)
+    block(dec_.enc[0], d_hidden, Ed, Ed, st_x, dec_.enc[0].n1w, dec_.enc[0].n1b, dec_.enc[0].n2w, dec_.enc[0].n2b, 0, x0, B, true);
+    block(dec_.enc[1], x0, B, B, st_y, dec_.enc[1].n1w, dec_.enc[1].n1b, dec_.enc[1].n2w, dec_.enc[1].n2b, 0, cat, CAT, true);
+
+    // asr_res = IN_affine(conv1x1(enc_seq) + b) written straight into the concat buffer      (:382-404)
+    if (dbg_layer.done) return;
+    {
+        ConvJob j = job(dec_.asr0);
+        j.x0 = d_hidden;
+        j.ldx = Ed;
+        j.out = asr_t;
+        j.stat_part = part_t;
+        j.stat_nblk = nblk;
+        j.stat_C = R;
+        conv(&j, 1, fr, 1, "dec_conv", conv_bytes(Ld, Ed, R, 1, false), conv_flops(Ld, Ed, R, 1));
+        finalize(part_t, R, st_a, 0);
+        ZV_LAUNCH("dec_norm_apply", 8.0 * Ld * R, 3.0 * Ld * R,
+                  launch_norm_apply(stream(), asr_t, R, R, st_a, ss, dec_.asr1w, dec_.asr1b, cat + B, CAT, part_t, nblk, fr));
+        finalize(part_t, R, st_x, B);            // statistics of the concat's asr columns: final for decode0..2
+        if (dbg_layer.kind == ZV_LAYER_DEC_ASR_RES)
+        {
+            dbg_extract(cat + B, CAT, R, L);
+            return;
+        }
+    }
+
+    // decode0..4: AdainResBlk1d; blocks 0..2 read cat([x, asr]) and 0,1 write x back into it   (:406-428).  The x
+    // columns' statistics arrive as partial sums from the producing conv2, the asr columns' are already in st_x.
+    const float *cur = cat;
+    int ldc = CAT;
+    float *outs[5] = {cat, cat, xa, x0, xa};
+    const int ldos[5] = {CAT, CAT, Ed, Ed, Ed};
+    const int cparts[5] = {B, B, B, Ed, Ed};
+    float *sts[5] = {st_x, st_x, st_x, st_y, st_y};
+    for (int i = 0; i < 5; i++)
+    {
+        const DecBlk &b = dec_.dec[i];
+        block(b, cur, ldc, cparts[i], sts[i], h + b.g1, h + b.g1 + b.cin, h + b.g2, h + b.g2 + b.cout, hs, outs[i], ldos[i], i < 4);
+        cur = outs[i];
+        ldc = ldos[i];
+    }
+    // to_out: conv1x1 E -> num_mels + b, emitted frame-major                                       (:432-441)
+    if (dbg_layer.done) return;
+    {
+        ConvJob j = job(dec_.to_out);
+        j.x0 = cur;
+        j.ldx = ldc;
+        j.out = d_mel;
+        j.ldo = dec_.M;
+        if (dbg_layer.kind == ZV_LAYER_DEC_TO_OUT) dbg_inject(const_cast<float *>(cur), ldc, Ed, L);
+        conv(&j, 1, fr, 1, "dec_conv", conv_bytes(Ld, Ed, dec_.M, 1, false), conv_flops(Ld, Ed, dec_.M, 1));
+        if (dbg_layer.kind == ZV_LAYER_DEC_TO_OUT) dbg_extract(d_mel, dec_.M, dec_.M, L);
+    }
+}
+
+}  // namespace zv

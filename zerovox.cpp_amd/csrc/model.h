@@ -5,8 +5,8 @@
 // the stage constructors (src/fs2encoder.cpp:477-586, src/stylettsdec.cpp:306-449, src/hifigan.cpp:187-356).
 #pragma once
 
-#include <map>
-#include <memory>
+#include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -31,12 +31,14 @@ struct DeviceArena
     char  *base = nullptr;
     size_t cap = 0, used = 0;
     static size_t align(size_t off) { return (off + 255) & ~(size_t)255; }     // every region starts on a 256-byte boundary
+    // an arena that only counts: no memory behind it, take() hands out null and `used` ends up as the bytes a layout needs
+    static DeviceArena counter() { return DeviceArena{nullptr, SIZE_MAX, 0}; }
     void  *take(size_t bytes)
     {
         const size_t a = align(used);
         if (a + bytes > cap) fail(ZV_ERR_OOM, "device arena overflow (%zu + %zu > %zu)", a, bytes, cap);
         used = a + bytes;
-        return base + a;
+        return base ? base + a : nullptr;
     }
     template <typename T> T *take_n(size_t n) { return (T *)take(n * sizeof(T)); }
 };
@@ -53,16 +55,19 @@ struct ProfEntry
 // frame rows its table entries name (kernels.h: Seg / Segs).  `nseg`, `n_max`, `t_max`, `n_rows`, `t_rows` are
 // CAPACITIES: they size grids and the arena, the real extents are read from the tables on the device, so one captured
 // graph serves every batch that fits.  A single utterance needs no table (inline segment).
+// A NEW FIELD: decide in same_schedule() below whether it keys a captured graph; whatever changes a grid, an arena offset or a kernel
+// argument does.  Deliberately not keyed: n_real (only host-side checks read it, the kernels take the real extents from the tables);
+// the destination and size of chain_dev's input upload (they follow from the keyed buffers).
 struct Batch
 {
     int        nseg = 1;
     int        n_max = 0, t_max = 0;        // >= every utterance's phonemes / frames
-    int        n_real = 0;                  // the longest utterance's real phoneme count (checks; not part of a graph's key)
+    int        n_real = 0;                  // the longest utterance's real phoneme count (checks)
     size_t     n_rows = 0, t_rows = 0;      // >= sum of phonemes / frames (rows of the concatenated buffers)
     const Seg *d_tok = nullptr, *d_frm = nullptr;
     Seg        tok1{0, 0, 0, 0}, frm1{0, 0, 0, 0};
-    // prosody controls, f32 [nseg][CTL_STRIDE] in HBM (kernels.h CTL_*), or null: the uncontrolled schedule.  Part of a chain
-    // graph's key (chain_dev: the kernels' arguments differ); the VALUES are read at run time, so a replay picks up new ones.
+    // prosody controls, f32 [nseg][CTL_STRIDE] in HBM (kernels.h CTL_*), or null: the uncontrolled schedule.  Part of a graph's
+    // key (the kernels' arguments differ); the VALUES are read at run time, so a replay picks up new ones.
     const float *d_ctl = nullptr;
     // per-phoneme controls, f32 [n_rows][PCTL_STRIDE] in HBM indexed by absolute token row (kernels.h PCTL_*), or null; keyed and read
     // like d_ctl
@@ -97,12 +102,20 @@ struct Batch
     Segs frames_cap() const { return Segs{d_frm, nseg, t_max, frm1}; }
     // the frames the decoder and the vocoder run over: the live table in fitted mode, else the capacity
     Segs frames() const { return d_frm_live ? Segs{d_frm_live, nseg, t_max, frm1} : frames_cap(); }
+    // what of a Batch a captured schedule depends on: the capacities (grids, arena layout), the table pointers, the inline segments
+    // where there is no table, and the four optional pointers that change the kernels' arguments
+    bool same_schedule(const Batch &o) const
+    {
+        return nseg == o.nseg && n_max == o.n_max && t_max == o.t_max && n_rows == o.n_rows && t_rows == o.t_rows && d_tok == o.d_tok &&
+               d_frm == o.d_frm && (d_tok || memcmp(&tok1, &o.tok1, sizeof(Seg)) == 0) && (d_frm || memcmp(&frm1, &o.frm1, sizeof(Seg)) == 0) &&
+               d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live;
+    }
 };
 
-// a captured schedule: replayed when the same entry point is called with the same capacities and buffers
+// a captured schedule: replayed when the same entry point is called with the same Batch (same_schedule) and buffers
 struct CapturedGraph
 {
-    static constexpr int NKEY = 12;
+    static constexpr int NKEY = 8;         // the buffers of a call that are not part of its Batch (chain_dev)
     int            kind = 0;               // 0 vocoder, 1 chain
     unsigned       epoch = 0;              // knob_epoch() at capture
     Batch          b;
@@ -119,9 +132,9 @@ class Model
     zv_hparams hp{};
     int        device = 0;
     int        n_cu = 256;
-    hipStream_t stream = nullptr;
+    hipStream_t stream() const { return lanes_[cur_lane_].stream; }      // the selected lane's
 
-    // ---- stages (device pointers in, device pointers out; everything enqueued on `stream`) ----
+    // ---- stages (device pointers in, device pointers out; everything enqueued on stream()) ----
     // every tensor is the row concatenation over the batch: mel [t_rows][M], wav [t_rows * hop], hidden [t_rows][E],
     // ids / puncts [n_rows], styles [nseg][E]
     void vocode_dev(const Batch &b, const float *d_mel, float *d_wav);
@@ -182,9 +195,8 @@ class Model
 
     // Lanes: independent (stream, activation arena, I/O scratch) triples so that several utterances are in flight at
     // once (zv_synthesize_batch): a single short utterance cannot fill 256 CUs in its narrow stages, four can.
-    // `stream` / the arena below always refer to the selected lane; lane 0 is the default.
+    // stream(), the arena and the scratch blocks are the selected lane's (lanes_ may grow: an index, not a reference); lane 0 is the default.
     void select_lane(int i);
-    int  current_lane() const { return cur_lane_; }
     void sync_all_lanes();
 
     // scratch for host-buffer entry points (grows on demand)
@@ -276,18 +288,36 @@ class Model
     } enc_;
 
     // ---- activations ----
-    DeviceArena arena_;
+    // One layout per stage states the stage's buffers in the arena, in carving order.  The stage calls it on the lane's arena for its
+    // pointers; arena_bytes_for calls the very same function on DeviceArena::counter() and reads the bytes used.  Invariants:
+    //   * every stage asks for the largest of the three layouts + ARENA_TAIL, so a chain never regrows the arena between stages;
+    //   * run_captured reserves before capture begins (hipMalloc cannot be captured) with the Batch the stages size by, so the
+    //     arena_require a stage issues inside the capture asks for the same bytes; no layout shrinks when a capacity grows, so a
+    //     sub-batch (vocode_tail) or a Batch that has gained d_cum never asks for more than the reservation did;
+    //   * vocode_tail (part 2 of a split batch) sees the layout the head (part 1) carved: voc_layout reads t_rows alone.
+    struct VocLayout { float *c0; struct Stage { float *ub, *y[3]; _Float16 *xt[3]; } st[8]; };      // stage i: ping-pong pool i & 1
+    struct DecLayout
+    {
+        int    nblk, hs, ss;        // per segment: statistics blocks, floats of AdaIN vectors, floats of (mean, rstd) pairs
+        float *h, *st_x, *st_t, *st_y, *st_a, *cat, *t1, *sc, *x0, *xa, *asr_t;
+        double *part_t, *part_o; _Float16 *xa16, *t16, *xr16;
+    };
+    struct EncLayout { int Vp; float *x, *y, *qkv, *o, *f, *va, *vb; _Float16 *hh; EncoderTaps t; };
+    VocLayout voc_layout(DeviceArena &a, const Batch &b) const;
+    DecLayout dec_layout(DeviceArena &a, const Batch &b) const;
+    EncLayout enc_layout(DeviceArena &a, const Batch &b) const;
+    // the arena's one margin, behind the largest layout: reads that run past a stage's last buffer stay inside the allocation
+    static constexpr size_t ARENA_TAIL = (size_t)1 << 20;
+    size_t arena_bytes_for(const Batch &b) const;
     void  arena_require(size_t bytes);
-    size_t arena_bytes_for(size_t n_rows, size_t t_rows, int nseg) const;
-    void *io_ = nullptr;
-    size_t io_cap_ = 0;
+    DeviceArena &stage_arena(const Batch &b);       // the selected lane's arena, large enough for every stage of b, rewound
 
     // ---- launch helpers ----
     void conv(const ConvJob *jobs, int n, const Segs &segs, int rate, const char *name, double bytes, double flops);
     void dbg_inject(void *dev, int ld, int cols, size_t rows);
     void dbg_extract(const void *dev, int ld, int cols, size_t rows);
     ConvJob job(const ConvW &w) const;
-    void tick(const char *name, double bytes, double flops, hipEvent_t *e0);
+    void tick(hipEvent_t *e0);
     void tock(hipEvent_t e0, const char *name, double bytes, double flops);
     void group_begin();
     void group_end(const char *name);
@@ -309,25 +339,21 @@ class Model
         std::vector<hipEvent_t> tail_events;
     };
     std::vector<Lane> lanes_;
-    void  *pinned_ = nullptr;
-    size_t pinned_cap_ = 0;
     int  cur_lane_ = 0;
+    Lane &lane() { return lanes_[cur_lane_]; }
     uint64_t   batch_seq_ = 0;
     hipEvent_t batch_events_[2 * BATCH_RING] = {};
-    void stash_lane();
 
     bool no_fuse_ = false;        // ZV_NO_FUSE=1: two launches per dilation pair (A/B measurement)
     bool no_triple_ = false;      // ZV_NO_TRIPLE=1: one launch per dilation pair also on the narrow stages (A/B measurement)
     int  tail_groups_ = 8;        // ZV_TAIL_GROUPS=G: utterance groups of a batch's last vocoder stage (0 / 1 = no split)
     bool skip_launch_ = false;    // vocode_group: the launches of the part that is not asked for are skipped
-    hipStream_t copy_stream_ = nullptr;
-    std::vector<hipEvent_t> tail_events_;
     bool no_merge_ = false;       // ZV_NO_MERGE=1: the last dilation pair of a stage stores its three branch outputs instead of their sum (A/B, tests)
     bool force_fuse256_ = false;  // ZV_FUSE256=1: fused kernel for the 256-channel stage at any length (tests: the path
                                   // long / batched utterances take, exercised at sizes the CPU oracle can check)
     std::vector<CapturedGraph> graphs_;
     void drop_graphs();
-    template <typename F> void run_captured(int kind, const Batch &b, const void *const *key, int nkey, F &&enqueue);
+    template <typename F> void run_captured(int kind, const Batch &b, const void *const (&key)[CapturedGraph::NKEY], F &&enqueue);
 };
 
 }  // namespace zv
