@@ -467,3 +467,88 @@ def encoder_margins(ex, alt):
                 floor_energy_max=float(np.max(np.abs(alt["energy"][clean] - ex["energy"][clean]))) if clean.any() else 0.0,
                 floor_dur_flips=int(np.sum(dur_r.astype(np.int64) != dur_a.astype(np.int64))),
                 floor_pitch_flips=int(pflip.sum()), floor_energy_flips=int(np.sum(alt["energy_bucket"] != ex["energy_bucket"])))
+
+
+# ---- sizes at the limits (tests/test_gpu_long.py, tests/test_long_cpu.py) ---------------------------------------------------
+# restated from zerovox.cpp_amd/csrc/capi.cpp (batch_group_end): a launch group takes utterances while it holds at most 64 of
+# them and (count) x (the longest T so far rounded up to 64) stays <= 64 Ki frames of capacity; the first always fits
+
+GROUP_MAX_UTTERANCES, GROUP_MAX_FRAMES = 64, 65536
+
+
+def launch_group_end(a, Ts):
+    b, tmax = a, 0
+    while b < len(Ts) and b - a < GROUP_MAX_UTTERANCES:
+        tm = max(tmax, Ts[b])
+        if b > a and (b - a + 1) * ((tm + 63) // 64 * 64) > GROUP_MAX_FRAMES:
+            break
+        tmax = tm
+        b += 1
+    return b
+
+
+def launch_groups(Ts):
+    """sizes of the launch groups zv_synthesize_batch splits utterances of capacities Ts into"""
+    sizes, a = [], 0
+    while a < len(Ts):
+        b = launch_group_end(a, Ts)
+        sizes.append(b - a)
+        a = b
+    return sizes
+
+
+def voc_stage_bytes_per_frame(scales, voc_channels):
+    """bytes of one mel frame's rows in the f32 tensor of each vocoder stage: rate x channels (padded to 16) x 4"""
+    out, rate = [], 1
+    for i, s in enumerate(scales):
+        rate *= s
+        out.append(rate * (((voc_channels >> (i + 1)) + 15) // 16 * 16) * 4)
+    return out
+
+
+def offset_crossing_frames(bytes_per_frame, T, lowest=27):
+    """{frame: [(stage, k)]}: the frames of a T-frame utterance whose rows hold byte 2^k (k >= lowest) of a stage's tensor"""
+    frames = {}
+    for i, bpf in enumerate(bytes_per_frame):
+        k = lowest
+        while (1 << k) < bpf * T:
+            frames.setdefault((1 << k) // bpf, []).append((i, k))
+            k += 1
+    return frames
+
+
+WINDOW_FRAMES = 64
+
+
+def oracle_windows(crossings, T):
+    """[(a, b)]: 64-frame windows at the start, around every crossing frame (the frame in the middle) and at the end"""
+    w = [(0, WINDOW_FRAMES)] + [(f - WINDOW_FRAMES // 2, f + WINDOW_FRAMES // 2) for f in sorted(crossings)] + [(T - WINDOW_FRAMES, T)]
+    assert all(0 <= a < b <= T for a, b in w)
+    return w
+
+
+def window_of_oracle(o_vocoder, mel, a, b, H, hop):
+    """samples [a hop, b hop) of the vocoder of `mel`, computed from frames [a - H, b + H) alone (clipped to the utterance)"""
+    lo, hi = max(0, a - H), min(len(mel), b + H)
+    w = o_vocoder(mel[lo:hi])
+    return w[(a - lo) * hop:(b - lo) * hop]
+
+
+def block_gates(name, got, ref, alt, block=256, rms_mult=2.0, max_mult=1.5):
+    """rows in blocks of `block`: every block's rms error <= rms_mult x max(its own floor, the median block floor), its max-abs
+    error likewise with max_mult; the floors are the oracle's alone (alt vs ref).  Returns the worst ratios against the block's
+    own floor: (rms ratio, block, max ratio, block)"""
+    n = got.shape[0] // block
+    assert n * block == got.shape[0]
+    e, f = (got - ref).astype(np.float64).reshape(n, -1), (alt - ref).astype(np.float64).reshape(n, -1)
+    e_rms, f_rms = np.sqrt(np.mean(e * e, axis=1)), np.sqrt(np.mean(f * f, axis=1))
+    e_max, f_max = np.max(np.abs(e), axis=1), np.max(np.abs(f), axis=1)
+    assert np.all(f_rms > 0) and np.all(f_max > 0), f"{name}: a block with a zero floor"
+    r_rms, r_max = e_rms / f_rms, e_max / f_max
+    i, j = int(np.argmax(r_rms)), int(np.argmax(r_max))
+    print(f"{name}: {n} blocks of {block} rows; floors rms min {f_rms.min():.2e} median {np.median(f_rms):.2e} max {f_rms.max():.2e}, "
+          f"max-abs {f_max.min():.2e} / {np.median(f_max):.2e} / {f_max.max():.2e}; worst rms ratio to the block's own floor "
+          f"{r_rms[i]:.3f} (block {i}), worst max-abs ratio {r_max[j]:.3f} (block {j})")
+    bad = np.flatnonzero((e_rms > rms_mult * np.maximum(f_rms, np.median(f_rms))) | (e_max > max_mult * np.maximum(f_max, np.median(f_max))))
+    assert not len(bad), f"{name}: blocks {bad[:16]} ({len(bad)}) beyond the gate"
+    return float(r_rms[i]), i, float(r_max[j]), j
