@@ -166,7 +166,15 @@ zv_status zv_encode_taps_phonemes(zv_model *m, const int32_t *ids, const int32_t
                                   const zv_phoneme_controls *phonemes, int32_t *durations);
 /* hidden[T*E], style[E] -> mel[T*num_mels] frame-major */
 zv_status zv_decode(zv_model *m, const float *hidden, const float *style, uint32_t T, float *mel);
-/* mel[T*num_mels] -> wav[T*hop_size] */
+/* mel[T*num_mels] -> wav[T*hop_size]
+ * Run-shortened vocoding (every unfitted entry point that vocodes, batches by default: switch ZV_VOC_RUNS).  The vocoder has no
+ * normalisation over time and a reach of zv_vocoder_halo_frames() = H frames, so over a run of bit-identical mel rows — what the
+ * decoder produces behind an utterance's end — its output is one hop-long frame, repeated.  A small kernel finds, per utterance,
+ * the longest run [a, b) of mel rows that are equal as BITS (-0 and +0 differ, equal NaN patterns are equal); when the run is
+ * longer than 2H + 1 rows by at least 16, only 2H + 1 of its rows are vocoded, the samples behind them land b - a - (2H + 1)
+ * frames further on and the frames in between are copies of frame a + H.  All on the device, inside the same captured graph.
+ * Results are UNCHANGED, bit for bit: every vocoder kernel sums in an order that does not depend on the tile or on T (the
+ * promise zv_vocode_stream relies on).  Off in fitted mode, in zv_vocode_stream and under zv_debug_layer. */
 zv_status zv_vocode(zv_model *m, const float *mel, uint32_t T, float *wav);
 
 /* ---- "next" row f-3 (streaming): chunked vocoding with halo ------------------------------------
@@ -305,7 +313,8 @@ zv_status zv_set_graph_mode(zv_model *m, int on);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* per-kernel-family timing measured with HIP events on the model's stream (eager launches).  algo_bytes / algo_flops are
- * priced by CAPACITY rows, also for a fitted call (whose kernels do less than that when n_frames < T) */
+ * priced by CAPACITY rows, also for a fitted call (whose kernels do less than that when n_frames < T); the vocoder launches of
+ * a run-shortened pass (zv_vocode) are priced by the rows its run table holds, read back once per profiled pass */
 typedef struct
 {
     char     name[48];
@@ -358,6 +367,11 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
  * diagnostic builds, -DZV_DIAG).  zv_debug_get reads a switch. */
 zv_status zv_debug_set(const char *name, int value);
 zv_status zv_debug_get(const char *name, int *value);
+/* Tests: the run table of the most recent vocoder pass on `lane` (run-shortened vocoding, see zv_vocode), after waiting for the
+ * lane: up to cap entries of four int32 each — {first row of the utterance in the batch, frames vocoded, split frame, frames
+ * skipped} — and in *n how many utterances the table has, 0 when that pass ran without one
+ * or when the lane's buffers were reallocated since.  Valid until the lane's next call.  The selected lane stays selected. */
+zv_status zv_debug_voc_runs(zv_model *m, uint32_t lane, int32_t *table, uint32_t cap, uint32_t *n);
 
 /* ---- GGUF inspection without a device (loader half of the boundary; used by the CPU test-suite) ----
  * Parses the file exactly as zv_model_load does and reports the counts; *max_seq_len receives the

@@ -23,6 +23,7 @@ SYMBOLS = [
     "zv_debug_get", "zv_batch_timeline", "zv_encode_taps_prosody", "zv_synthesize_prosody", "zv_synthesize_batch_prosody",
     "zv_synthesize_batch_begin_prosody", "zv_encode_taps_phonemes", "zv_synthesize_phonemes", "zv_synthesize_batch_phonemes",
     "zv_synthesize_batch_begin_phonemes", "zv_synthesize_fitted", "zv_synthesize_batch_fitted", "zv_synthesize_batch_begin_fitted",
+    "zv_debug_voc_runs",
 ]
 
 
@@ -146,6 +147,8 @@ def load_library(path: Optional[str] = None):
     lib.zv_debug_layer.argtypes = [vp, C.c_int, C.c_int, fp, u32, fp, fp]
     lib.zv_debug_set.argtypes = [C.c_char_p, C.c_int]
     lib.zv_debug_get.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
+    if hasattr(lib, "zv_debug_voc_runs"):        # (an older build named by ZEROVOX_AMD_LIB for an A/B run lacks it)
+        lib.zv_debug_voc_runs.argtypes = [vp, u32, C.c_void_p, u32, C.POINTER(u32)]
     lib.zv_batch_timeline.argtypes = [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u32)]
     lib.zv_max_frames.argtypes = [vp]
     lib.zv_max_frames.restype = u32
@@ -472,6 +475,15 @@ class Model:
         a, b, n = (C.c_double * cap)(), (C.c_double * cap)(), C.c_uint32(0)
         self._chk(self.lib.zv_batch_timeline(self.h, cap, a, b, C.byref(n)))
         return [(a[i], b[i]) for i in range(n.value)]
+
+    def voc_runs(self, lane: int = 0) -> np.ndarray:
+        """zv_debug_voc_runs: the run table of the lane's most recent vocoder pass, int32 [utterances][4] = (row0, frames vocoded,
+        split frame, frames skipped); no rows when that pass ran without run-shortening"""
+        cap = 64
+        tab = np.zeros((cap, 4), np.int32)
+        n = C.c_uint32(0)
+        self._chk(self.lib.zv_debug_voc_runs(self.h, lane, _ptr(tab), cap, C.byref(n)))
+        return tab[:min(cap, n.value)].copy()
 
     def profile_begin(self):
         self._chk(self.lib.zv_profile_begin(self.h))

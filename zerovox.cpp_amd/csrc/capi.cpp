@@ -461,6 +461,9 @@ zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t c
         const uint32_t H = M.vocoder_halo_frames();
         const uint32_t ctx_max = std::min<uint64_t>(T, (uint64_t)chunk_frames + 2 * H);
         check_T(M, ctx_max);                          // only a chunk plus its context is ever vocoded at once
+        // the chunks are the schedule here: no run-shortening inside a chunk
+        struct RunsOff { Model &M; ~RunsOff() { M.voc_runs_off = false; } } runs_off{M};
+        M.voc_runs_off = true;
         M.reserve(1, ctx_max);
         Layout L;
         const size_t o_mel = L.at((size_t)T * Mm * 4), o_wav = L.at((size_t)ctx_max * hop * 4);
@@ -1059,6 +1062,24 @@ zv_status zv_debug_get(const char *name, int *value)
     return guarded([&] {
         ZV_NEED(name && value, "null argument");
         if (!zv::knob_get(name, value)) zv::fail(ZV_ERR_ARG, "unknown switch '%s'", name);
+    });
+}
+
+zv_status zv_debug_voc_runs(zv_model *m, uint32_t lane, int32_t *table, uint32_t cap, uint32_t *n)
+{
+    return guarded([&] {
+        ZV_NEED(m && n && (table || !cap), "null argument");
+        ZV_NEED(lane < ZV_BATCH_LANES, "lane out of range");
+        Model &M = *m->m;
+        ZV_HIP(hipSetDevice(M.device));
+        struct Restore { Model &M; int was; ~Restore() { M.select_lane(was); } } restore{M, M.selected_lane()};
+        M.select_lane((int)lane);
+        M.sync();
+        int cnt = 0;
+        const zv::Seg *tab = M.voc_runs_last(&cnt);      // null again once the lane's arena was reallocated
+        *n = tab ? (uint32_t)cnt : 0;
+        const size_t k = std::min<size_t>(*n, cap);
+        if (k) ZV_HIP(hipMemcpy(table, tab, k * sizeof(zv::Seg), hipMemcpyDeviceToHost));
     });
 }
 

@@ -1389,7 +1389,9 @@ __global__ __launch_bounds__(256) void out_conv_tanh_kernel(const OutConvArgs a)
             for (int j = 0; j < 8; j++) acc = fmaf((float)x[j], (float)w[j], acc);
         }
     }
-    a.out[row0 + t] = tanhf(acc + a.bias);
+    // run-shortened schedule: the frames behind the split belong `shift` frames further on in the waveform (launch_voc_run_fill fills the gap)
+    const int skip = a.runs && t >= (sg.aux + 1) * a.rate ? a.segs.tab[useg].pad * a.rate : 0;
+    a.out[row0 + t + skip] = tanhf(acc + a.bias);
 }
 
 hipError_t launch_out_conv(hipStream_t s, const OutConvArgs &a)

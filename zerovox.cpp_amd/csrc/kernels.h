@@ -253,6 +253,7 @@ struct OutConvArgs
     float       *out;            // wav[L]
     Segs         segs;
     int          rate;
+    int          runs;           // segs is a run table (launch_voc_runs): samples of the frames behind seg.aux land seg.pad frames further on
 };
 hipError_t launch_out_conv(hipStream_t s, const OutConvArgs &a);
 
@@ -348,5 +349,17 @@ hipError_t launch_live_frames(hipStream_t s, const int32_t *n_frames, Seg *live,
 // x[row][0 .. C) = 0 for the rows [live[u].rows * rate, frames[u].rows * rate) of every segment (x: rows of C floats at `rate` rows per
 // base row, laid out by `frames`): what the fitted schedule leaves unwritten of a segment's capacity
 hipError_t launch_zero_tail(hipStream_t s, float *x, int C, const Segs &frames, const Segs &live, int rate);
+
+// ---- run-shortened vocoding (unfitted path): behind an utterance's end the mel rows are bit-identical, and over a run of identical
+// rows the vocoder's output is one frame, repeated (it is shift-invariant with a reach of H = Model::vocoder_halo_frames() frames).
+// For every segment of `frames`, with [a, b) its first longest run of bitwise-equal mel rows and Rmin = 2H + 1:
+//   taken (b - a >= Rmin + VOC_RUN_MARGIN): mel_c = rows [0, a + Rmin) ++ rows [b, T);  runs[u] = {row0, T - (b - a) + Rmin, aux = a + H, pad = b - a - Rmin}
+//   otherwise:                              mel_c = mel;                                 runs[u] = {row0, T, aux = T, pad = 0}
+// aux is the SPLIT frame and pad the SHIFT: compact frame f' is wav frame f' up to the split and f' + shift behind it
+// (OutConvArgs::runs); wav frames (split, split + shift] are copies of frame `split` (launch_voc_run_fill).
+// eq: int32 scratch, one per row of the batch.  mel [rows][M] dense.  No host round trip: one graph replays for any lengths.
+constexpr int VOC_RUN_MARGIN = 16;      // frames a run must save to be taken: below a row tile of the narrow stages nothing is saved
+hipError_t launch_voc_runs(hipStream_t s, const float *mel, int M, float *mel_c, int32_t *eq, Seg *runs, const Segs &frames, int H);
+hipError_t launch_voc_run_fill(hipStream_t s, float *x, const Segs &runs, int rate);
 
 }  // namespace zv

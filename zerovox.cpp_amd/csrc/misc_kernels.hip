@@ -1455,4 +1455,136 @@ hipError_t launch_zero_tail(hipStream_t s, float *x, int C, const Segs &frames, 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Run-shortened vocoding (kernels.h: launch_voc_runs).  Behind an utterance's end the decoder's mel rows are bit-identical, and
+// the vocoder is shift-invariant with a reach of H frames, so the waveform over such a run is one frame, repeated.  Three steps,
+// all on the device so that the schedule stays one graph: (1) eq[row] = "this mel row has the bits of the row above it",
+// (2) per segment the first longest run [a, b) of equal rows -> the table entry, (3) the compacted mel.
+//   taken (b - a >= 2H + 1 + VOC_RUN_MARGIN): runs[u] = {row0, T - (b - a - (2H + 1)), split = a + H, shift = b - a - (2H + 1)}
+//   otherwise:                                runs[u] = {row0, T, split = T, shift = 0}
+// Rows are compared as 32-bit integers: -0 and +0 differ, equal NaN patterns are equal.
+__global__ __launch_bounds__(256) void voc_run_flags_kernel(const uint32_t *__restrict__ mel, int M, int32_t *__restrict__ eq, const Segs frames)
+{
+    const Seg sg = seg_at(frames, blockIdx.y);
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= sg.rows) return;
+    int same = t > 0;
+    if (t > 0)
+    {
+        const uint32_t *r = mel + (size_t)(sg.row0 + t) * M;
+        for (int c = lane; c < M; c += 64) same &= r[c] == r[c - M];
+    }
+    same = __all(same);
+    if (lane == 0) eq[sg.row0 + t] = same;
+}
+
+__global__ __launch_bounds__(256) void voc_run_scan_kernel(const int32_t *__restrict__ eq, Seg *__restrict__ runs, const Segs frames, int H)
+{
+    // per thread one contiguous chunk of the segment's flags: leading ones, trailing ones, the first longest run of ones inside
+    __shared__ int s_pre[256], s_suf[256], s_len[256], s_pos[256];
+    const Seg sg = seg_at(frames, blockIdx.x);
+    const int T = sg.rows, tid = threadIdx.x;
+    const int per = (T + 255) / 256;
+    const int p0 = tid * per < T ? tid * per : T, p1 = p0 + per < T ? p0 + per : T;
+    int pre = 0, cur = 0, best = 0, pos = p0;
+    bool lead = true;
+    for (int t = p0; t < p1; t++)
+    {
+        if (eq[sg.row0 + t])
+        {
+            cur++;
+            if (lead) pre = cur;
+            if (cur > best) { best = cur; pos = t - cur + 1; }
+        }
+        else
+        {
+            cur = 0;
+            lead = false;
+        }
+    }
+    s_pre[tid] = pre;
+    s_suf[tid] = cur;
+    s_len[tid] = best;
+    s_pos[tid] = pos;
+    __syncthreads();
+    if (tid != 0) return;
+    // the chunks in order: `run` ones end at the current chunk boundary and began at run_pos; strict > keeps the first longest
+    int run = 0, run_pos = 0, len = 0, at = 0;
+    for (int k = 0; k < 256; k++)
+    {
+        const int q0 = k * per < T ? k * per : T, n = (q0 + per < T ? q0 + per : T) - q0;
+        if (n <= 0) break;
+        if (run == 0) run_pos = q0;
+        if (s_pre[k] == n)
+            run += n;
+        else
+        {
+            if (run + s_pre[k] > len) { len = run + s_pre[k]; at = run_pos; }
+            if (s_len[k] > len) { len = s_len[k]; at = s_pos[k]; }
+            run = s_suf[k];
+            run_pos = q0 + n - run;
+        }
+        if (run > len) { len = run; at = run_pos; }
+    }
+    // `len` flags from `at` on = the rows [at - 1, at + len) are equal
+    const int a = at - 1, b = at + len, Rmin = 2 * H + 1;
+    const bool take = len > 0 && b - a >= Rmin + VOC_RUN_MARGIN;
+    const int shift = take ? b - a - Rmin : 0;
+    *(int4 *)(runs + blockIdx.x) = make_int4(sg.row0, T - shift, take ? a + H : T, shift);
+}
+
+// dst rows [0, split + H + 1) = the segment's own, dst rows behind them = the source rows `shift` further on
+__global__ __launch_bounds__(256) void voc_run_compact_kernel(const uint32_t *__restrict__ mel, uint32_t *__restrict__ dst, int M, const Seg *__restrict__ runs, int H)
+{
+    const int4 e = *(const int4 *)(runs + blockIdx.y);
+    const int row0 = __builtin_amdgcn_readfirstlane(e.x), rows = __builtin_amdgcn_readfirstlane(e.y);
+    const int split = __builtin_amdgcn_readfirstlane(e.z), shift = __builtin_amdgcn_readfirstlane(e.w);
+    const long n = (long)rows * M, keep = (long)(split + H + 1) * M;
+    const size_t base = (size_t)row0 * M;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+    {
+        const long i = (long)blockIdx.x * 1024 + k * 256 + threadIdx.x;
+        if (i < n) dst[base + i] = mel[base + i + (i >= keep ? (long)shift * M : 0)];
+    }
+}
+
+hipError_t launch_voc_runs(hipStream_t s, const float *mel, int M, float *mel_c, int32_t *eq, Seg *runs, const Segs &frames, int H)
+{
+    if (frames.nseg < 1 || frames.max_rows < 1 || M < 1 || H < 0 || !mel || !mel_c || !eq || !runs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(voc_run_flags_kernel, dim3((frames.max_rows + 3) / 4, frames.nseg), dim3(256), 0, s, (const uint32_t *)mel, M, eq, frames);
+    hipLaunchKernelGGL(voc_run_scan_kernel, dim3(frames.nseg), dim3(256), 0, s, eq, runs, frames, H);
+    const long per_seg = (long)frames.max_rows * M;
+    hipLaunchKernelGGL(voc_run_compact_kernel, dim3((unsigned)((per_seg + 1023) / 1024), frames.nseg), dim3(256), 0, s,
+                       (const uint32_t *)mel, (uint32_t *)mel_c, M, runs, H);
+    return hipGetLastError();
+}
+
+// wav frames (split, split + shift] of every segment = copies of frame `split` (x: `rate` samples per frame): the frames the
+// run-shortened schedule did not vocode.  grid.x walks the longest possible fill in chunks of 1 024 samples.
+__global__ __launch_bounds__(256) void voc_run_fill_kernel(float *__restrict__ x, const Seg *__restrict__ runs, int rate)
+{
+    const int4 e = *(const int4 *)(runs + blockIdx.y);
+    const int row0 = __builtin_amdgcn_readfirstlane(e.x), split = __builtin_amdgcn_readfirstlane(e.z);
+    const int shift = __builtin_amdgcn_readfirstlane(e.w);
+    const long n = (long)shift * rate, i0 = (long)blockIdx.x * 1024;
+    if (i0 >= n) return;
+    const float *src = x + (size_t)(row0 + split) * rate;
+    float *dst = x + (size_t)(row0 + split + 1) * rate;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+    {
+        const long i = i0 + k * 256 + threadIdx.x;
+        if (i < n) dst[i] = src[i % rate];
+    }
+}
+
+hipError_t launch_voc_run_fill(hipStream_t s, float *x, const Segs &runs, int rate)
+{
+    if (runs.nseg < 1 || runs.max_rows < 1 || rate < 1 || !runs.tab || !x) return hipErrorInvalidValue;
+    const long per_seg = (long)runs.max_rows * rate;
+    hipLaunchKernelGGL(voc_run_fill_kernel, dim3((unsigned)((per_seg + 1023) / 1024), runs.nseg), dim3(256), 0, s, x, runs.tab, rate);
+    return hipGetLastError();
+}
+
 }  // namespace zv

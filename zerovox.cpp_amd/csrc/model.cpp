@@ -137,6 +137,8 @@ void Model::arena_require(size_t bytes)
     DeviceArena &ar = lane().arena;              // (drop_graphs does not touch lanes_)
     if (ar.base) hipFree(ar.base);
     ar = DeviceArena();
+    lane().runs_tab = nullptr;                   // the last run table lay in the arena just freed (voc_runs_last)
+    lane().runs_n = 0;
     void *p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) fail(ZV_ERR_OOM, "hipMalloc(%zu) for the activation arena failed", bytes);
     // on the lane's own stream: the streams are non-blocking, so a memset on the null stream is NOT ordered with the
@@ -263,10 +265,14 @@ template <typename F> void Model::run_captured(int kind, const Batch &b, const v
         if (g.kind == kind && g.epoch == knob_epoch() && b.same_schedule(g.b) && memcmp(g.p, key, sizeof(key)) == 0)
         {
             ZV_HIP(hipGraphLaunch(g.exec, stream()));
+            lane().runs_tab = g.runs_tab;
+            lane().runs_n = g.runs_n;
             return;
         }
     reserve_batch(b);                            // hipMalloc is not capturable
     hipGraph_t graph = nullptr;
+    lane().runs_tab = nullptr;
+    lane().runs_n = 0;
     ZV_HIP(hipStreamBeginCapture(stream(), hipStreamCaptureModeThreadLocal));
     try
     {
@@ -284,6 +290,8 @@ template <typename F> void Model::run_captured(int kind, const Batch &b, const v
     cg.epoch = knob_epoch();       // a graph replays the kernel regime it was captured in: a later zv_debug_set captures anew
     cg.b = b;
     memcpy(cg.p, key, sizeof(key));
+    cg.runs_tab = lane().runs_tab;
+    cg.runs_n = lane().runs_n;
     hipError_t e = hipGraphInstantiate(&cg.exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
     if (e != hipSuccess) fail(ZV_ERR_DEVICE, "hipGraphInstantiate failed: %s", hipGetErrorString(e));

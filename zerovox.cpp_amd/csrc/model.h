@@ -121,6 +121,8 @@ struct CapturedGraph
     Batch          b;
     const void    *p[NKEY] = {};
     hipGraphExec_t exec = nullptr;
+    const Seg     *runs_tab = nullptr;     // the run table its vocoder writes (Model::voc_runs_last), or null
+    int            runs_n = 0;
 };
 
 class Model
@@ -140,7 +142,8 @@ class Model
     void vocode_dev(const Batch &b, const float *d_mel, float *d_wav);
     // part: 0 = the whole schedule, 1 = everything up to and including the last stage's upsample conv, 2 = the last
     // stage's residual blocks + the output conv
-    void vocode_group(const Batch &b, const float *d_mel, float *d_wav, int part = 0);
+    // seg0: the batch's first segment is entry seg0 of the head's run table (vocode_tail)
+    void vocode_group(const Batch &b, const float *d_mel, float *d_wav, int part = 0, int seg0 = 0);
     // the tail (part 2) of segments [g0, g0 + cnt) of a batch whose head chain_dev(..., voc_part = 1) has enqueued: same
     // arena layout, same row ranges, same bits as the unsplit schedule
     void vocode_tail(const Batch &b, const float *d_mel, float *d_wav, int g0, int cnt);
@@ -191,12 +194,19 @@ class Model
     // receptive field of the vocoder in mel frames per side (input conv + per stage: transposed-conv taps and the widest
     // residual block, converted from the stage's sample rate), rounded up, + 1
     uint32_t vocoder_halo_frames() const;
+    // Run-shortened vocoding of the unfitted path (vocoder.cpp): off in fitted mode, under a dbg_layer tap, where the caller asks
+    // (zv_vocode_stream: its chunks are the schedule) and by ZV_VOC_RUNS.  voc_runs_last: the selected lane's most recent run table
+    // (device, in the lane's arena, valid until the lane's next call) and its entries, or null / 0 when that call ran without one
+    bool voc_runs_off = false;
+    bool voc_runs_on(const Batch &b) const;
+    const Seg *voc_runs_last(int *n) { *n = lane().runs_n; return lane().runs_tab; }
     void sync();
 
     // Lanes: independent (stream, activation arena, I/O scratch) triples so that several utterances are in flight at
     // once (zv_synthesize_batch): a single short utterance cannot fill 256 CUs in its narrow stages, four can.
     // stream(), the arena and the scratch blocks are the selected lane's (lanes_ may grow: an index, not a reference); lane 0 is the default.
     void select_lane(int i);
+    int  selected_lane() const { return cur_lane_; }
     void sync_all_lanes();
 
     // scratch for host-buffer entry points (grows on demand)
@@ -294,8 +304,16 @@ class Model
     //   * run_captured reserves before capture begins (hipMalloc cannot be captured) with the Batch the stages size by, so the
     //     arena_require a stage issues inside the capture asks for the same bytes; no layout shrinks when a capacity grows, so a
     //     sub-batch (vocode_tail) or a Batch that has gained d_cum never asks for more than the reservation did;
-    //   * vocode_tail (part 2 of a split batch) sees the layout the head (part 1) carved: voc_layout reads t_rows alone.
-    struct VocLayout { float *c0; struct Stage { float *ub, *y[3]; _Float16 *xt[3]; } st[8]; };      // stage i: ping-pong pool i & 1
+    //   * vocode_tail (part 2 of a split batch) sees the layout the head (part 1) carved: voc_layout reads t_rows alone, but for the
+    //     size of its last carve (the run table).
+    struct VocLayout
+    {
+        float *c0;
+        struct Stage { float *ub, *y[3]; _Float16 *xt[3]; } st[8];      // stage i: ping-pong pool i & 1
+        // run-shortened schedule (kernels.h launch_voc_runs), behind the pools so that a sub-batch finds them where the head put them:
+        // the compacted mel, the row flags, the run table (one entry per segment: the only carve that reads nseg, hence the last)
+        float *mel_c; int32_t *eq; Seg *runs;
+    };
     struct DecLayout
     {
         int    nblk, hs, ss;        // per segment: statistics blocks, floats of AdaIN vectors, floats of (mean, rstd) pairs
@@ -337,6 +355,8 @@ class Model
         size_t      pinned_cap = 0;
         hipStream_t copy_stream = nullptr;
         std::vector<hipEvent_t> tail_events;
+        const Seg  *runs_tab = nullptr;      // voc_runs_last
+        int         runs_n = 0;
     };
     std::vector<Lane> lanes_;
     int  cur_lane_ = 0;

@@ -66,6 +66,11 @@ Model::VocLayout Model::voc_layout(DeviceArena &a, const Batch &bt) const
         }
         for (int k = 0; k < 2 && pass == 0; k++) pool[k] = DeviceArena{(char *)a.take(need[k]), need[k], 0};
     }
+    // the run-shortened schedule's compacted mel, flags and table: carved whether or not a call uses them (fitted, stream and
+    // switch-off calls pay t_rows x (num_mels + 1) words of arena too), so that a layout depends on the batch's shape alone
+    v.mel_c = a.take_n<float>(bt.t_rows * hp.audio_num_mels);
+    v.eq = a.take_n<int32_t>(bt.t_rows);
+    v.runs = a.take_n<Seg>(bt.nseg);
     return v;
 }
 
@@ -76,6 +81,15 @@ void Model::vocode_dev(const Batch &bt, const float *d_mel, float *d_wav)
     vocode_group(bt, d_mel, d_wav);
 }
 
+// batches (ZV_VOC_RUNS = 1): by capacity, as the other batch switches — a single short utterance has no rounds of workgroups to
+// give back, and its three extra launches would only add latency.  The threshold is the other batch switches', not a measured
+// one: no sweep of capacities below it is on record, so small batches and long single utterances may be giving a gain away
+bool Model::voc_runs_on(const Batch &bt) const
+{
+    const int k = knob(ZV_VOC_RUNS);
+    return !voc_runs_off && !bt.d_frm_live && dbg_layer.kind < 0 && k != 0 && (k == 2 || (long)bt.t_rows >= 16384);
+}
+
 void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g0, int cnt)
 {
     if (!bt.d_frm || g0 < 0 || cnt < 1 || g0 + cnt > bt.nseg) fail(ZV_ERR_ARG, "internal: bad segment group");
@@ -83,18 +97,42 @@ void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g
     sub.d_frm = bt.d_frm + g0;
     if (bt.d_frm_live) sub.d_frm_live = bt.d_frm_live + g0;
     sub.nseg = cnt;
-    vocode_group(sub, d_mel, d_wav, 2);
+    vocode_group(sub, d_mel, d_wav, 2, g0);
 }
 
-void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int part)
+void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int part, int seg0)
 {
     struct Unskip { bool &f; ~Unskip() { f = false; } } unskip{skip_launch_};
     skip_launch_ = part == 2;
     const VocLayout lay = voc_layout(stage_arena(bt), bt);
-    const Segs fr = bt.frames();
     const int M = hp.audio_num_mels;
+    // Run-shortened schedule: every launch below takes its extents from the run table and the input conv reads the compacted mel;
+    // the output conv puts the samples back where they belong and a fill repeats the one frame the run stands for.  The head
+    // (part 0 / 1) writes table and mel, a tail (part 2) finds its segments' entries from seg0 on.
+    const bool runs = voc_runs_on(bt);
+    const Segs fr = runs ? Segs{lay.runs + seg0, bt.nseg, bt.t_max, bt.frm1} : bt.frames();
+    if (part != 2)
+    {
+        lane().runs_tab = runs ? lay.runs : nullptr;
+        lane().runs_n = runs ? bt.nseg : 0;
+    }
+    if (runs)
+    {
+        ZV_LAUNCH("voc_runs", 12.0 * bt.t_rows * M, 0.0,
+                  launch_voc_runs(stream(), d_mel, M, lay.mel_c, lay.eq, lay.runs, bt.frames_cap(), (int)vocoder_halo_frames()));
+        d_mel = lay.mel_c;
+    }
     size_t L = bt.t_rows;                       // capacity rows at the current stage (buffer sizes)
     double La = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg);      // rows this call covers (accounting)
+    if (runs && profiling)
+    {
+        // the profile states work done: the rows the table holds (this path is eager and the host waits anyway)
+        std::vector<Seg> tab((size_t)bt.nseg);
+        ZV_HIP(hipMemcpyAsync(tab.data(), lay.runs + seg0, tab.size() * sizeof(Seg), hipMemcpyDeviceToHost, stream()));
+        ZV_HIP(hipStreamSynchronize(stream()));
+        La = 0;
+        for (const Seg &g : tab) La += g.rows;
+    }
     int rate = 1;
     int C = voc_.in_conv.Cout;
     float *c0 = lay.c0;
@@ -424,6 +462,7 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         a.out = d_wav;
         a.segs = fr;
         a.rate = rate;
+        a.runs = runs;
         if (dbg_layer.kind == ZV_LAYER_VOC_OUTPUT)
         {
             // the layer's input is the MRF mean that enters leaky_relu(0.01) (src/hifigan.cpp:315-324)
@@ -433,6 +472,7 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
             a.pscale = 1.0f;
         }
         ZV_LAUNCH("voc_output_conv", 12.0 * La * C + 4.0 * La, 2.0 * La * C * a.K, launch_out_conv(stream(), a));
+        if (runs) ZV_LAUNCH("voc_run_fill", 8.0 * (L - La), 0.0, launch_voc_run_fill(stream(), d_wav, fr, rate));
         if (dbg_layer.kind == ZV_LAYER_VOC_OUTPUT) dbg_extract(d_wav, 1, 1, L);
         // fitted: the output conv stops at each utterance's last frame; the rest of its capacity is silence
         if (bt.d_frm_live) ZV_LAUNCH("voc_zero_tail", 4.0 * La, 0.0, launch_zero_tail(stream(), d_wav, 1, bt.frames_cap(), fr, rate));
