@@ -372,6 +372,15 @@ zv_status zv_debug_get(const char *name, int *value);
  * skipped} — and in *n how many utterances the table has, 0 when that pass ran without one
  * or when the lane's buffers were reallocated since.  Valid until the lane's next call.  The selected lane stays selected. */
 zv_status zv_debug_voc_runs(zv_model *m, uint32_t lane, int32_t *table, uint32_t cap, uint32_t *n);
+/* Tests: overwrite what `lane` keeps between calls, so that a comparison of two calls on one lane can see a write that did not
+ * happen.  Waits for the lane's stream and copy stream, then fills with `byte` (0..255) the whole capacity of the lane's activation
+ * arena and device I/O block (on the lane's own stream, then waits) and of its pinned staging block; filled[3] (may be NULL)
+ * receives the bytes filled in the three, 0 for a block not yet allocated (a lane never used: ZV_OK, all 0).  Allocates nothing and
+ * leaves captured graphs alone (their pointers stay valid: a replay must work on poisoned buffers); the lane's run table
+ * (zv_debug_voc_runs) is forgotten until its next call.  ZV_ERR_ARG, and nothing is touched, while the lane has a batch in flight,
+ * for lane >= ZV_BATCH_LANES and for a byte outside 0..255.  Not a switch: no graph is captured anew.  The selected lane stays
+ * selected. */
+zv_status zv_debug_poison(zv_model *m, uint32_t lane, int byte, size_t filled[3]);
 
 /* ---- GGUF inspection without a device (loader half of the boundary; used by the CPU test-suite) ----
  * Parses the file exactly as zv_model_load does and reports the counts; *max_seq_len receives the

@@ -5,7 +5,9 @@ The contract is bit equality with the existing unfitted entry points at T = n_fr
 np.array_equal; no tolerance appears anywhere.  For an utterance with frame count nf under capacity T:
     fitted wav[: nf * hop] == unfitted call of the same kind at T = nf,   wav[nf * hop :] == 0,   n_frames == nf,
     durations equal (they sum to nf).
-Lengths are made deterministic with duration_frames (forced frames per phoneme) where a case needs a particular nf.  Checked:
+Lengths are made deterministic with duration_frames (forced frames per phoneme) where a case needs a particular nf.  A lane's
+buffers keep the previous call's waveform, live table and zeroed tail at offsets that depend on the shapes alone, so the lane is
+poisoned (zv_debug_poison, _poison below) before every fitted call of sections 1 to 7.  Checked:
   * single calls, eager and graph: nf at and around the 32-row statistics blocks and the 64 / 256-row tiles, capacities 64-aligned
     and not;
   * predicted durations under duration_scale 0.5 / 1 / 2: fitted call first, then the unfitted call at the n_frames it returned;
@@ -57,6 +59,12 @@ def _forced(N, total):
     return (total // N + (np.arange(N) < total % N)).astype(np.int32)
 
 
+def _poison(m, lane=0):
+    """fills what the lane keeps between calls, 0xFF and 0x3C bytes in turn (tests/test_gpu_poison.py says why these two)"""
+    _M["fill"] = 0xFF ^ 0x3C ^ _M.get("fill", 0x3C)
+    m.poison(_M["fill"], lane)
+
+
 def _check_fitted(hop, got, ref, T, what):
     """got: (wav, n_frames, durations) of a fitted call under capacity T; ref: the unfitted call at T = n_frames, or None when
     n_frames == 0"""
@@ -92,6 +100,7 @@ def test_single_forced_lengths(env, graph):
         pc = dict(duration_frames=_forced(N, nf))
         for T in (nf + 1, 2 * nf + 7, 1024, (nf + 64) // 64 * 64):
             for rep in range(2 if graph else 1):            # graph: capture, then replay
+                _poison(m)
                 got = m.synthesize(ids, puncts, style, T, phonemes=pc, return_durations=True, fitted=True)
                 _check_fitted(hop, got, refs[nf], T, (nf, T, graph, rep))
 
@@ -107,7 +116,9 @@ def test_single_predicted_durations(env, graph):
         for ds in (0.5, 1.0, 2.0):
             pr = dict(duration_scale=ds)
             m.set_graph_mode(graph)
+            _poison(m)
             w, nf = m.synthesize(ids, puncts, style, T, prosody=pr, fitted=True)          # no per-phoneme arguments at all
+            _poison(m)
             got = m.synthesize(ids, puncts, style, T, prosody=pr, return_durations=True, fitted=True)
             assert got[1] == nf and np.array_equal(got[0], w)
             m.set_graph_mode(False)
@@ -138,6 +149,7 @@ def test_full_capacity_gives_the_unfitted_bits(env, graph):
         assert ref[1] == T, (T, ref[1])
         m.set_graph_mode(graph)
         for rep in range(2 if graph else 1):
+            _poison(m)
             got = m.synthesize(ids, puncts, style, T, return_durations=True, fitted=True, **kw)
             assert got[1] == T and np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2]), (T, rep)
 
@@ -153,9 +165,11 @@ def test_empty_utterance_alone_and_between_neighbours(env, graph):
     before = m.synthesize(ids, puncts, style, T, return_durations=True)
     m.set_graph_mode(graph)
     for rep in range(2):
+        _poison(m)
         got = m.synthesize(ids, puncts, style, T, phonemes=zero, return_durations=True, fitted=True)
         _check_fitted(hop, got, None, T, ("alone", rep))
         # the model still gives correct bits on the next call, fitted (same capacity: the same graph, another table) and unfitted
+        _poison(m)
         nxt = m.synthesize(ids, puncts, style, T, phonemes=dict(duration_frames=_forced(N, 77)), return_durations=True, fitted=True)
         assert nxt[1] == 77
         after = m.synthesize(ids, puncts, style, T, return_durations=True)
@@ -165,7 +179,7 @@ def test_empty_utterance_alone_and_between_neighbours(env, graph):
     _check_fitted(hop, nxt, ref77, T, "after the empty call")
     # in a batch: the empty utterance first, in the middle and last
     nbrs = [(*_utt(g, 42 + i, n), t) for i, (n, t) in enumerate(((20, 300), (5, 64), (64, 700)))]
-    alone = [m.synthesize(*u, return_durations=True, fitted=True) for u in nbrs]
+    alone = [(_poison(m), m.synthesize(*u, return_durations=True, fitted=True))[1] for u in nbrs]
     empty = (ids, puncts, style, T, None, zero)
     for pos in (0, 1, 3):
         utts = [u + (None, None) for u in nbrs]
@@ -175,6 +189,7 @@ def test_empty_utterance_alone_and_between_neighbours(env, graph):
         for rep in range(2):
             for w in bc.wavs:
                 w[:] = NAN
+            _poison(m)
             bc.run()
             res = [r + (d,) for r, d in zip(bc.results(), bc.durations)]
             _check_fitted(hop, res.pop(pos), None, T, ("batch", pos, rep))
@@ -212,7 +227,7 @@ def _ragged_sets(g):
 
 
 def _alone_fitted(m, base, prs, pcs):
-    return [m.synthesize(*u, prosody=p, phonemes=c, return_durations=True, fitted=True) for u, p, c in zip(base, prs, pcs)]
+    return [(_poison(m), m.synthesize(*u, prosody=p, phonemes=c, return_durations=True, fitted=True))[1] for u, p, c in zip(base, prs, pcs)]
 
 
 def _alone_unfitted(m, base, prs, pcs, fitted):
@@ -223,6 +238,7 @@ def _alone_unfitted(m, base, prs, pcs, fitted):
 def _batch_results(bc):
     for w in bc.wavs:
         w[:] = NAN
+    _poison(bc.model)
     bc.run()
     return [r + (d,) for r, d in zip(bc.results(), bc.durations)]
 
@@ -255,13 +271,16 @@ def test_ragged_batch_eager_graph_and_replay_with_new_lengths(env):
     _same_as(hop, _batch_results(bc), base, f1, u1, "graph replay, back to the first lengths")
     for w in bc.wavs:
         w[:] = NAN
+    _poison(m, 2)
     bc.begin(2)
     bc.end(2)
     _same_as(hop, [r + (d,) for r, d in zip(bc.results(), bc.durations)], base, f1, u1, "begin / end, graph")
     m.set_graph_mode(False)
     # without prosody, controls or timings: the NULL arguments of the fitted entry point
+    _poison(m)
     plain = m.synthesize_batch([u for u in base], fitted=True)
     for i, (u, (w, nf)) in enumerate(zip(base, plain)):
+        _poison(m)
         wa, nfa = m.synthesize(*u, fitted=True)
         assert nf == nfa and np.array_equal(w, wa), ("plain", i)
         if nf:
@@ -316,6 +335,7 @@ def test_fitted_and_unfitted_lanes_in_flight(env):
             for w in bc.wavs:
                 w[:] = NAN
         for k, bc in enumerate(order):
+            _poison(m, k % 2)                               # idle: the lane's previous batch has ended
             bc.begin(k % 2)
             if k:
                 order[k - 1].end((k - 1) % 2)
@@ -381,11 +401,13 @@ def test_fitted_batch_in_every_kernel_regime(regime_refs, regime):
                 m.set_graph_mode(mode != "eager")
                 for w in bc.wavs:
                     w[:] = NAN
+                _poison(m)
                 bc.run()
                 check(bc.results(), mode)
             m.set_graph_mode(False)
             # a single fitted call goes through a one-entry table: the same regimes
             i = max(range(len(utts)), key=lambda k: nfs[k] if nfs[k] < utts[k][3] else 0)
+            _poison(m)
             w, nf = m.synthesize(*utts[i], fitted=True)
             assert nf == nfs[i] and np.array_equal(w[: nf * hop], refs[i][0]) and not w[nf * hop:].any(), (name, "single", i)
         finally:

@@ -1,6 +1,8 @@
 """-m gpu: history independence.  A long random sequence of calls (all entry points, lengths that grow and shrink the
 arenas, graph mode toggled, batches on the in-flight lanes, chunked vocoding) on ONE model must give, for every call,
-exactly the bits a second model gives that sees each distinct call once, eagerly, in a different order."""
+exactly the bits a second model gives that sees each distinct call once, eagerly, in a different order.
+A second generator, which leaves the first one's call sequence as it is, poisons lane 0 of the first model (zv_debug_poison: everything
+the lane keeps between calls) ahead of about one step in ten, and follows some synth calls and batches with their fitted forms."""
 import numpy as np
 import pytest
 
@@ -16,7 +18,9 @@ def test_random_call_sequences_are_history_independent(ckpt):
     path, g, tensors = ckpt("small")
     a, b = capi.Model(path, 0), capi.Model(path, 0)
     import os
-    rng = np.random.default_rng(int(os.environ.get("ZV_SM_SEED", "2024")))
+    seed0 = int(os.environ.get("ZV_SM_SEED", "2024"))
+    rng = np.random.default_rng(seed0)
+    rng2 = np.random.default_rng([seed0, 1])        # poison and fitted extras: no draw of theirs comes from rng
     Ts = [1, 7, 33, 64, 100, 160, 250]
     Ns = [1, 5, 24, 40, 77]
 
@@ -38,11 +42,23 @@ def test_random_call_sequences_are_history_independent(ckpt):
             ids, puncts, style = synth.encoder_inputs(g, key[3], key[1])
             w, nf = m.synthesize(ids, puncts, style, key[2])
             return [w, np.array([nf])]
+        if op == "synth_fitted":
+            ids, puncts, style = synth.encoder_inputs(g, key[3], key[1])
+            w, nf = m.synthesize(ids, puncts, style, key[2], fitted=True)
+            return [w, np.array([nf])]
         raise AssertionError(op)
 
     seen = {}
     order = []
+    poisons = fitted = 0
     for it in range(140):
+        if rng2.random() < 0.1:
+            a.poison(int(rng2.choice([0xFF, 0x3C])))
+            poisons += 1
+        # a synth call or a batch is followed by its fitted form.  No poison falls between the two: the fitted call then finds the
+        # unfitted waveform of the same shapes in the lane's buffers, non-zero where its own tail must be zero, so a tail that is
+        # not zeroed shows without one
+        extra = rng2.random() < 0.5
         r = rng.integers(0, 100)
         T, N, seed = int(rng.choice(Ts)), int(rng.choice(Ns)), int(rng.integers(0, 3))
         if r < 8:
@@ -68,9 +84,20 @@ def test_random_call_sequences_are_history_independent(ckpt):
             for k, (w, nf) in zip(keys, a.synthesize_batch(utts)):
                 seen.setdefault(k, []).append([w, np.array([nf])])
                 order.append(k)
+            if extra:
+                for k, (w, nf) in zip(keys, a.synthesize_batch(utts, fitted=True)):
+                    k = _key("synth_fitted", *k[1:])
+                    seen.setdefault(k, []).append([w, np.array([nf])])
+                    order.append(k)
+                fitted += 1
             continue
         seen.setdefault(key, []).append(run(a, key))
         order.append(key)
+        if extra and key[0] == "synth":
+            key = _key("synth_fitted", *key[1:])
+            seen.setdefault(key, []).append(run(a, key))
+            order.append(key)
+            fitted += 1
     a.set_graph_mode(False)
     # model b: every distinct call once, eagerly, sorted order (a different history)
     for key in sorted(seen, key=repr):
@@ -79,6 +106,7 @@ def test_random_call_sequences_are_history_independent(ckpt):
             assert len(got) == len(ref)
             for x, y in zip(got, ref):
                 assert np.array_equal(np.asarray(x), np.asarray(y)), key
-    print(f"{len(order)} calls, {len(seen)} distinct")
+    print(f"{len(order)} calls, {len(seen)} distinct, {poisons} poisons, {fitted} fitted extras")
+    assert poisons >= 5 and fitted >= 5
     a.close()
     b.close()

@@ -3,7 +3,9 @@
 The contract is that nothing changes: every comparison is between the switch at 0 and at 2 and is bitwise (uint32 views, so NaN
 patterns and the sign of zero count).  No test passes because nothing was skipped: after every call at 2 the device's run table
 (zv_debug_voc_runs) is compared, utterance by utterance, with the model of tests/test_voc_runs_cpu.py — rows = T - (b - a) + 2H + 1
-for the expected run [a, b), rows = T where no run qualifies — and at 0 the table must be absent."""
+for the expected run [a, b), rows = T where no run qualifies — and at 0 the table must be absent.  The two calls of a comparison
+run on one lane, whose buffers keep the first call's waveform at the same offsets: the lane is poisoned (zv_debug_poison) before every
+call at 1 or 2, so that a sample the shortened schedule does not write cannot pass as the stale right one."""
 import numpy as np
 import pytest
 
@@ -94,6 +96,7 @@ def test_vocode_hand_made_mels(env, graph):
             assert m.voc_runs().shape[0] == 0, name
         with capi.switches(ZV_VOC_RUNS=2):
             for rep in range(2 if graph else 1):                    # graph: capture, then replay
+                m.poison(0x3C if rep else 0xFF)
                 got = m.vocode(mel)
                 tab = m.voc_runs()
                 assert tab.shape == (1, 4) and tuple(tab[0]) == (0,) + want, (name, rep, tab, want)
@@ -112,13 +115,16 @@ def test_default_switch_leaves_single_utterances_alone_and_stream_and_fitted_hav
     ref = m.vocode(mel)
     assert m.voc_runs().shape[0] == 0                               # 400 rows: not a batch
     with capi.switches(ZV_VOC_RUNS=2):
+        m.poison()
         assert np.array_equal(_bits(m.vocode(mel)), _bits(ref)) and m.voc_runs()[0, 3] > 0
+        m.poison(0x3C)
         chunks = m.vocode_stream(mel, 128)
         assert m.voc_runs().shape[0] == 0                           # the chunks are the schedule
         assert np.array_equal(_bits(np.concatenate([c for _, c in chunks])), _bits(ref))
         ids, puncts, style = synth.encoder_inputs(g, 51, 30)
         m.synthesize(ids, puncts, style, 400, fitted=True)
         assert m.voc_runs().shape[0] == 0
+        m.poison()
         w2, nf2 = m.synthesize(ids, puncts, style, 400)
         assert m.voc_runs()[0, 3] > 0
     w0, nf0 = m.synthesize(ids, puncts, style, 400)
@@ -181,6 +187,7 @@ def test_batch_switch_0_and_2_eager_graph_and_lanes(env):
                 for rep in range(2 if graph else 1):
                     for w in bc.wavs:
                         w[:] = np.nan
+                    m.poison(0x3C if rep else 0xFF)
                     bc.run()
                     _check_table(m.voc_runs(0), want, (sw, graph, rep))
                     same(bc.results(), (sw, graph, rep))
@@ -189,6 +196,7 @@ def test_batch_switch_0_and_2_eager_graph_and_lanes(env):
                 for k, c in enumerate(calls):
                     for w in c.wavs:
                         w[:] = np.nan
+                    m.poison(0x3C if k & 2 else 0xFF, k % 2)       # the lane is idle: its previous batch has ended
                     c.begin(k % 2)
                     if k:
                         calls[k - 1].end((k - 1) % 2)
@@ -222,6 +230,7 @@ def test_table_is_gone_once_the_arena_it_lay_in_is_reallocated(ckpt):
             ref = m.vocode(mel)                                                      # ... and the next call runs on it as before
             m.reserve(1, 8192)                                                       # the arena grows: a new allocation
             assert m.voc_runs().shape[0] == 0
+            m.poison()
             assert np.array_equal(_bits(m.vocode(mel)), _bits(ref)) and m.voc_runs().shape == (1, 4)
     finally:
         m.close()

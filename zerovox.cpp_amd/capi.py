@@ -23,7 +23,7 @@ SYMBOLS = [
     "zv_debug_get", "zv_batch_timeline", "zv_encode_taps_prosody", "zv_synthesize_prosody", "zv_synthesize_batch_prosody",
     "zv_synthesize_batch_begin_prosody", "zv_encode_taps_phonemes", "zv_synthesize_phonemes", "zv_synthesize_batch_phonemes",
     "zv_synthesize_batch_begin_phonemes", "zv_synthesize_fitted", "zv_synthesize_batch_fitted", "zv_synthesize_batch_begin_fitted",
-    "zv_debug_voc_runs",
+    "zv_debug_voc_runs", "zv_debug_poison",
 ]
 
 
@@ -149,6 +149,8 @@ def load_library(path: Optional[str] = None):
     lib.zv_debug_get.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     if hasattr(lib, "zv_debug_voc_runs"):        # (an older build named by ZEROVOX_AMD_LIB for an A/B run lacks it)
         lib.zv_debug_voc_runs.argtypes = [vp, u32, C.c_void_p, u32, C.POINTER(u32)]
+    if hasattr(lib, "zv_debug_poison"):
+        lib.zv_debug_poison.argtypes = [vp, u32, C.c_int, C.POINTER(C.c_size_t)]
     lib.zv_batch_timeline.argtypes = [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u32)]
     lib.zv_max_frames.argtypes = [vp]
     lib.zv_max_frames.restype = u32
@@ -484,6 +486,13 @@ class Model:
         n = C.c_uint32(0)
         self._chk(self.lib.zv_debug_voc_runs(self.h, lane, _ptr(tab), cap, C.byref(n)))
         return tab[:min(cap, n.value)].copy()
+
+    def poison(self, byte: int = 0xFF, lane: int = 0):
+        """zv_debug_poison: fills everything `lane` keeps between calls (activation arena, device I/O block, pinned staging block)
+        with `byte`; (arena_bytes, io_bytes, pinned_bytes) filled, 0 for a block the lane has not allocated yet"""
+        filled = (C.c_size_t * 3)()
+        self._chk(self.lib.zv_debug_poison(self.h, lane, int(byte), filled))
+        return int(filled[0]), int(filled[1]), int(filled[2])
 
     def profile_begin(self):
         self._chk(self.lib.zv_profile_begin(self.h))

@@ -1083,6 +1083,20 @@ zv_status zv_debug_voc_runs(zv_model *m, uint32_t lane, int32_t *table, uint32_t
     });
 }
 
+zv_status zv_debug_poison(zv_model *m, uint32_t lane, int byte, size_t filled[3])
+{
+    return guarded([&] {
+        ZV_NEED(m, "null model");
+        ZV_NEED(lane < ZV_BATCH_LANES, "lane out of range");
+        ZV_NEED(byte >= 0 && byte <= 255, "byte must be 0..255");
+        ZV_NEED(!(m->pending && m->pending[lane].active), "the lane has a batch in flight: finish it with zv_synthesize_batch_end first");
+        ZV_HIP(hipSetDevice(m->m->device));
+        size_t f[3];
+        m->m->poison_lane((int)lane, byte, f);       // the selected lane stays selected: nothing is selected
+        for (int k = 0; filled && k < 3; k++) filled[k] = f[k];
+    });
+}
+
 // ---- device-resident entry points ---------------------------------------------------------------
 
 void *zv_device_alloc(zv_model *m, size_t bytes)

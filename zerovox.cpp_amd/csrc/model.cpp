@@ -69,6 +69,25 @@ void Model::select_lane(int i)
 
 void Model::sync_all_lanes() { for (Lane &l : lanes_) ZV_HIP(hipStreamSynchronize(l.stream)); }
 
+void Model::poison_lane(int i, int byte, size_t filled[3])
+{
+    filled[0] = filled[1] = filled[2] = 0;
+    if (i < 0 || i >= (int)lanes_.size()) return;        // never selected: no stream, no blocks
+    Lane &l = lanes_[i];
+    ZV_HIP(hipStreamSynchronize(l.stream));
+    if (l.copy_stream) ZV_HIP(hipStreamSynchronize(l.copy_stream));
+    // on the lane's own stream, as arena_require's fill: the null stream is not ordered with the lane's kernels
+    if (l.arena.base) ZV_HIP(hipMemsetAsync(l.arena.base, byte, l.arena.cap, l.stream));
+    if (l.io) ZV_HIP(hipMemsetAsync(l.io, byte, l.io_cap, l.stream));
+    ZV_HIP(hipStreamSynchronize(l.stream));
+    if (l.pinned) memset(l.pinned, byte, l.pinned_cap);
+    l.runs_tab = nullptr;                        // the last run table lay in the arena just overwritten (voc_runs_last)
+    l.runs_n = 0;
+    filled[0] = l.arena.base ? l.arena.cap : 0;
+    filled[1] = l.io ? l.io_cap : 0;
+    filled[2] = l.pinned ? l.pinned_cap : 0;
+}
+
 void *Model::pinned_scratch(size_t bytes)
 {
     Lane &l = lane();

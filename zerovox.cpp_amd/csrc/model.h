@@ -208,6 +208,10 @@ class Model
     void select_lane(int i);
     int  selected_lane() const { return cur_lane_; }
     void sync_all_lanes();
+    // Tests (zv_debug_poison): fills the whole capacity of lane i's arena, I/O scratch and pinned staging block with `byte` after
+    // waiting for the lane's streams, and forgets its run table (it lay in the arena).  filled[3] = the bytes of each block, 0 for
+    // one that is not allocated (all three for a lane never selected).  Allocates nothing, selects nothing, drops no graph.
+    void poison_lane(int i, int byte, size_t filled[3]);
 
     // scratch for host-buffer entry points (grows on demand)
     void *io_scratch(size_t bytes);
