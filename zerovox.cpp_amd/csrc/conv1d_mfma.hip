@@ -9,6 +9,7 @@
 #include "kernels.h"
 #include "knobs.h"
 #include "mfma_common.h"
+#include "tile_deal.h"
 
 #include <hip/hip_fp16.h>
 #include <algorithm>
@@ -170,22 +171,6 @@ void pack_pair_weight(const uint16_t *w, int K, int C, int Cp, uint16_t *dst)
                         d[lane * 8 + j] = (oc < C && ic < C) ? w[((size_t)oc * C + ic) * K + tap] : (uint16_t)0;
                     }
             }
-}
-
-// XCD-aware tile order.  Workgroups are dealt round-robin over the 8 XCDs (observed, not promised: only the speed
-// depends on it) and each XCD has its own L2.  With grid.x a multiple of 8, workgroup b runs on XCD b % 8; giving XCD
-// x the x-th contiguous eighth of a job's time tiles keeps neighbouring tiles — which share their halo rows — behind the
-// same L2 instead of spreading every halo over two XCDs.
-__device__ __forceinline__ int zv_xcd_tile(int b, int ntiles)
-{
-#ifdef ZV_NO_XCD_MAP
-    return b;
-#else
-    // per job: its own tile count decides the eighths (jobs of one launch have different tile heights), so that
-    // every XCD gets an equal share of every job; workgroups beyond the job's tiles return a tile index >= ntiles
-    const int per = (ntiles + 7) >> 3, idx = b >> 3;
-    return idx < per ? (b & 7) * per + idx : ntiles;
-#endif
 }
 
 // leaky-ReLU for 0 <= slope <= 1 as max(x, x*slope): same bits as (x > 0 ? x : x*slope), one instruction less and
@@ -429,7 +414,7 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(const PairJobs jobs)
     const int jz = (int)blockIdx.z, bx = (int)blockIdx.x;
     const int TM = BM - (MERGE ? jobs.kmax - 1 : jobs.j[jz].K - 1);
     const int tps = (jobs.segs.max_rows * jobs.rate + TM - 1) / TM;
-    const int vt = zv_xcd_tile(bx, tps * jobs.segs.nseg);
+    const int vt = tile_deal(bx, tps, jobs.segs.nseg, jobs.deal_c);
     if (vt >= tps * jobs.segs.nseg) return;
     const int useg = vt / tps;
     const Seg sg = seg_at(jobs.segs, useg);
@@ -638,7 +623,7 @@ __global__ __launch_bounds__(256, 2) void resblock_pair64_kernel(const PairJobs 
     const int jz = (int)blockIdx.z, bx = (int)blockIdx.x;
     const int TM = BM - (MERGE ? jobs.kmax - 1 : jobs.j[jz].K - 1);
     const int tps = (jobs.segs.max_rows * jobs.rate + TM - 1) / TM;
-    const int vt = zv_xcd_tile(bx, tps * jobs.segs.nseg);
+    const int vt = tile_deal(bx, tps, jobs.segs.nseg, jobs.deal_c);
     if (vt >= tps * jobs.segs.nseg) return;
     const int useg = vt / tps;
     const Seg sg = seg_at(jobs.segs, useg);
@@ -862,7 +847,7 @@ static hipError_t launch_pair64_ring(hipStream_t s, PairJobs &js, int njobs, int
 {
     constexpr int BM = 256;
     const int TMmin = BM - (Kmax - 1);
-    dim3 grid(round_up(((Lmax + TMmin - 1) / TMmin) * js.segs.nseg, 8), 1, MERGE ? 1 : njobs);
+    dim3 grid(tile_deal_grid((Lmax + TMmin - 1) / TMmin, js.segs.nseg, js.deal_c), 1, MERGE ? 1 : njobs);
     // operand rows: BM + (K - 1) * dil, + dil: the last tap's prefetch reads one tap past the end
     js.ring_off = round_up((BM + Kmax * dmax) * (64 * 2 + 16), 1024);
     const size_t lds = (size_t)js.ring_off + 4 * 8192;
@@ -890,7 +875,7 @@ __global__ __launch_bounds__(256, 2) void resblock_block64_kernel(const TripleJo
     const int H = h2 * (sumd + nd);
     const int TM = BM - 2 * H;
     const int tps = (jobs.segs.max_rows * jobs.rate + TM - 1) / TM;
-    const int vt = zv_xcd_tile(blockIdx.x, tps * jobs.segs.nseg);
+    const int vt = tile_deal((int)blockIdx.x, tps, jobs.segs.nseg, jobs.deal_c);
     if (vt >= tps * jobs.segs.nseg) return;
     const int useg = vt / tps;
     const Seg sg = seg_at(jobs.segs, useg);
@@ -1140,7 +1125,8 @@ hipError_t launch_block64(hipStream_t s, const TripleJob *jobs, int njobs, const
     js.interleave = 1;
     js.db_mask = 0;
     const int Lmax = segs.max_rows * rate;
-    int gx = 1, rows_max = 0;
+    js.deal_c = tile_deal_chunk(64);
+    int gx = 8, rows_max = 0;
     for (int i = 0; i < njobs; i++)
     {
         js.j[i] = jobs[i];
@@ -1150,14 +1136,14 @@ hipError_t launch_block64(hipStream_t s, const TripleJob *jobs, int njobs, const
         int sumd = 0, dmax = 1;
         for (int d = 0; d < P.n_dil; d++) { sumd += P.dil[d]; dmax = P.dil[d] > dmax ? P.dil[d] : dmax; }
         const int h2 = (P.K - 1) / 2, TM = 256 - 2 * h2 * (sumd + P.n_dil);
-        gx = std::max(gx, ((Lmax + TM - 1) / TM) * segs.nseg);
+        gx = std::max(gx, tile_deal_grid((Lmax + TM - 1) / TM, segs.nseg, js.deal_c));
         rows_max = std::max(rows_max, 256 + 2 * h2 * dmax + 2 * dmax);
     }
     for (int i = njobs; i < PAIR_MAX_JOBS; i++) js.j[i] = js.j[0];
     js.ring_off = round_up(rows_max * (64 * 2 + 16), 1024);
     const size_t lds = (size_t)js.ring_off + 4 * 8192;
     if (lds > 80 * 1024) return hipErrorInvalidValue;
-    return launch_lds(resblock_block64_kernel, dim3(round_up(gx, 8), 1, njobs), dim3(256), lds, s, js);
+    return launch_lds(resblock_block64_kernel, dim3(gx, 1, njobs), dim3(256), lds, s, js);
 }
 
 // the MFMA loop of the fused kernels walks whole 8-step bodies (CP = 64: also half a body at the end) and at least one
@@ -1175,8 +1161,8 @@ static hipError_t launch_pair_cfg(hipStream_t s, const PairJobs &js, int njobs, 
     constexpr int BM = 32 * MT * (4 / WNc);
     const int TMmin = BM - (Kmax - 1);
     if (TMmin < 32) return hipErrorInvalidValue;
-    // jobs differ in K: grid.x is sized for the smallest TM, workgroups beyond a job's extent exit at once
-    dim3 grid(round_up(((Lmax + TMmin - 1) / TMmin) * js.segs.nseg, 8), 1, MERGE ? 1 : njobs);      // multiple of 8: zv_xcd_tile
+    // jobs differ in K: grid.x is sized for the smallest TM (the most tiles per segment), workgroups beyond a job's extent exit at once
+    dim3 grid(tile_deal_grid((Lmax + TMmin - 1) / TMmin, js.segs.nseg, js.deal_c), 1, MERGE ? 1 : njobs);      // multiple of 8: tile_deal.h
     // rows touched: BM + taps (K rounded up to the loop's granularity, + 1 for the last prefetch) * dil.  The loop walks
     // whole taps once a tap is at least a body (CP >= 128): K + 1 taps (51 KB for the 128-channel stage: room for three
     // workgroups per CU instead of two — measured worth 0.6 %)
@@ -1197,6 +1183,7 @@ hipError_t launch_pair(hipStream_t s, const PairJob *jobs, int njobs, int n_cu, 
     js.segs = segs;
     js.rate = rate;
     js.njobs = njobs;
+    js.deal_c = tile_deal_chunk(jobs[0].Cp);
     js.merge_out = merge_out;
 #ifdef ZV_STAMPS
     js.stamp = knob(ZV_STAMP_CP) && knob(ZV_STAMP_CP) == jobs[0].Cp && !merge_out ? stamp_buffer() : nullptr;
@@ -1292,7 +1279,7 @@ __global__ __launch_bounds__(64 * (R / 32 / MT)) void resblock_triple_kernel(con
     const int H = h2 * (sumd + nd);
     const int TM = R - 2 * H;
     const int tps = (jobs.segs.max_rows * jobs.rate + TM - 1) / TM;      // (segment, tile) as in resblock_pair_kernel
-    const int vt = zv_xcd_tile(blockIdx.x, tps * jobs.segs.nseg);
+    const int vt = tile_deal((int)blockIdx.x, tps, jobs.segs.nseg, jobs.deal_c);
     if (vt >= tps * jobs.segs.nseg) return;
     const int useg = vt / tps;
     const Seg sg = seg_at(jobs.segs, useg);
@@ -1544,7 +1531,7 @@ __global__ __launch_bounds__(64 * (R / 32 / MT), (MT >= 4 ? 2 : 4)) void resbloc
     }
     const int TM = R - 2 * H;
     const int tps = (jobs.segs.max_rows * jobs.rate + TM - 1) / TM;
-    const int vt = zv_xcd_tile(bx, tps * jobs.segs.nseg);
+    const int vt = tile_deal(bx, tps, jobs.segs.nseg, jobs.deal_c);
     if (vt >= tps * jobs.segs.nseg) return;
     const int useg = vt / tps;
     const Seg sg = seg_at(jobs.segs, useg);
@@ -1781,6 +1768,7 @@ hipError_t launch_triple(hipStream_t s, const TripleJob *jobs, int njobs, int n_
     TripleJobs js;
     js.segs = segs;
     js.rate = rate;
+    js.deal_c = tile_deal_chunk(32);
     js.interleave = 1;
     js.db_mask = 0;
 #ifdef ZV_STAMPS
@@ -1789,7 +1777,7 @@ hipError_t launch_triple(hipStream_t s, const TripleJob *jobs, int njobs, int n_
     const int Lmax = segs.max_rows * rate;
     int R, MT;
     triple_tile(njobs, n_cu, segs, rate, MT, R);
-    int gx = 1;
+    int gx = 8;
     size_t lds = 0;
     for (int i = 0; i < njobs; i++)
     {
@@ -1800,13 +1788,13 @@ hipError_t launch_triple(hipStream_t s, const TripleJob *jobs, int njobs, int n_
         int sumd = 0, dmax = 1;
         for (int d = 0; d < P.n_dil; d++) { sumd += P.dil[d]; dmax = P.dil[d] > dmax ? P.dil[d] : dmax; }
         const int h2 = (P.K - 1) / 2, TM = R - 2 * h2 * (sumd + P.n_dil);
-        gx = std::max(gx, ((Lmax + TM - 1) / TM) * segs.nseg);
+        gx = std::max(gx, tile_deal_grid((Lmax + TM - 1) / TM, segs.nseg, js.deal_c));
         const size_t rows = R + 2 * h2 * dmax + 5 * dmax;
         lds = std::max(lds, rows * (P.Cp * 2 + 16));
     }
     for (int i = njobs; i < PAIR_MAX_JOBS; i++) js.j[i] = js.j[0];
     if (lds > 64 * 1024) return hipErrorInvalidValue;
-    const dim3 grid(round_up(gx, 8), 1, njobs);      // multiple of 8: zv_xcd_tile
+    const dim3 grid(gx, 1, njobs);      // multiple of 8: tile_deal.h
     // batches: the form with the weights in LDS (two workgroups per CU); ZV_TRIPLE_V2 = 0 never, 2 always, 3 always and on 512-row tiles (A/B, tests)
     const int v2_env = knob(ZV_TRIPLE_V2);
     if (v2_env && (R == 512 || v2_env >= 2))
@@ -1829,7 +1817,7 @@ hipError_t launch_triple(hipStream_t s, const TripleJob *jobs, int njobs, int n_
         if (lds2 <= 80 * 1024)
         {
             js.interleave = knob(ZV_TRIPLE_INTERLEAVE) != 0 ? njobs : 1;
-            const dim3 grid2 = js.interleave > 1 ? dim3(round_up(gx, 8) * njobs, 1, 1) : grid;
+            const dim3 grid2 = js.interleave > 1 ? dim3(gx * njobs, 1, 1) : grid;
             // (the whole-block kernel of batches reads the 16 x 16 x 32 fragment order: TripleJob::w1x / w2x)
             for (int i = 0; i < njobs; i++)
                 for (int d = 0; d < jobs[i].n_dil; d++)

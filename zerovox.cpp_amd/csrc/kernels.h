@@ -182,6 +182,7 @@ struct PairJobs
     Segs    segs;
     int     rate;
     int     njobs, kmax;
+    int     deal_c;              // tile_deal.h: tiles per chunk of the segments' deal over the XCDs (set by the launcher)
 #ifdef ZV_STAMPS
     unsigned long long *stamp;   // diagnostic build: the phase-stamp buffer this launch writes (stamp_buffer()), or null
 #endif
@@ -228,6 +229,7 @@ struct TripleJobs
     TripleJob j[PAIR_MAX_JOBS];
     Segs      segs;
     int       rate;
+    int       deal_c;            // tile_deal.h: tiles per chunk of the segments' deal over the XCDs (set by the launcher)
     int       interleave;        // resblock_block32_kernel: > 1 = that many jobs share grid.x, interleaved per XCD
     int       db_mask;           // resblock_block32_kernel: bit j = job j keeps two weight buffers in LDS (set by the launcher)
     int       ring_off;          // resblock_block64_kernel: byte offset of the weight ring in LDS (set by the launcher)
