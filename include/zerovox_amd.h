@@ -13,6 +13,7 @@
  *   zv_synthesize      <- ZeroVOXModel::eval                  src/zerovox.cpp:198-335 (three stages back to back)
  *   *_prosody          the same with per-utterance duration / pitch / energy controls (zv_prosody)
  *   *_phonemes         the same with per-phoneme controls as well (zv_phoneme_controls) and the phoneme timings out
+ *   *_target           the same with a target frame count the utterance's durations are fitted to
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file        src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -281,6 +282,51 @@ zv_status zv_synthesize_batch_begin_fitted(zv_model *m, uint32_t lane, uint32_t 
                                            const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
                                            const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
                                            const zv_phoneme_controls *phonemes, int32_t *const *durations);
+/* ---- target durations: fit an utterance to an exact frame count ------------------------------------------------------------
+ * "Say this in exactly target frames" (dubbing, subtitle and animation sync, fixed-length slots), in one pass: between the
+ * duration predictor and the length regulator a device step turns the predicted durations and the target into integer
+ * durations that sum to the target exactly, and the length regulator takes them as forced frame counts.  The target travels in
+ * the batch's device input block like the other controls, so a replayed graph picks up new targets.  A target in seconds is
+ * floor(seconds * audio_sampling_rate / audio_hop_size + 0.5) frames (the caller converts).
+ * The rule, per utterance with 0 < target <= T (target == 0: none), over the tokens i < num_phonemes, in 64-bit integers from the
+ * weights on, so that it does not depend on the order of any sum and can be restated bit for bit:
+ *   dur_i    steps 1-3 of the per-phoneme duration rule above: (float)(exp((double)logdur) - 1.0), times prosody.duration_scale
+ *            (if prosody is given), times duration_scale[i] (if given), f32, every step rounded separately
+ *   forced   phonemes with duration_frames[i] >= 0 keep d_i = min(duration_frames[i], T); Fs = their sum
+ *   free     all the others share R = target - Fs.  R <= 0 or no free phoneme: every free phoneme gets 0 (forced durations
+ *            win; n_frames = min(Fs, T) as without a target)
+ *   weights  q_i = dur_i > 0 ? (int64)min((double)dur_i * 65536.0, 2^40) : 0  (NaN and values <= 0 give 0, +inf gives 2^40);
+ *            Q = sum of q_i over the free phonemes; Q == 0: every free q_i = 1 and Q = the number of free phonemes (equal shares)
+ *   shares   base_i = (q_i * R) / Q, rem_i = (q_i * R) % Q; L = R - sum of base_i (0 <= L < number of free phonemes); the L free
+ *            phonemes with the largest rem_i — ties go to the lower index — get d_i = base_i + 1, the others d_i = base_i
+ *   tokens at or past num_phonemes keep 0.
+ * sum d_i = target whenever a free phoneme exists and Fs <= target; every d_i <= T.  The result is defined as exactly the bits
+ * of the _phonemes call (fitted != 0: the _fitted call) with duration_frames[i] = d_i for every i < num_phonemes: hidden,
+ * n_frames, durations[] and wav.  A uniform duration_scale changes nothing but the rounding of q_i; per-phoneme scales shift
+ * the shares.  Pitch and energy decisions do not depend on durations and stay as they are; the taps logdur, pitch, energy stay RAW.
+ * With fitted != 0 and a reachable target, wav[0 .. target*hop) is the audio and the rest is 0.0f.
+ * target_frames == 0 (batches: a NULL array, or 0 for that utterance) gives the bits of the same call without a target.
+ * Arguments, limits and messages are those of the _phonemes / _fitted forms; in addition ZV_ERR_ARG before any work is enqueued
+ * when target_frames[u] > T[u] (the message names the entry point, the utterance and target_frames), or when a request with
+ * a target has an utterance of more than 3584 phonemes.  The header csrc/fit_durations.h holds the rule as plain C++ (host
+ * reference included).  zv_synthesize_batch_begin_target is finished by zv_synthesize_batch_end. */
+zv_status zv_encode_taps_target(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
+                                uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
+                                float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody,
+                                const zv_phoneme_controls *phonemes, int32_t *durations, uint32_t target_frames);
+zv_status zv_synthesize_target(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                               float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                               int32_t *durations, uint32_t target_frames, int fitted);
+zv_status zv_synthesize_batch_target(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                     const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                     float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                     const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                     const uint32_t *target_frames, int fitted);
+zv_status zv_synthesize_batch_begin_target(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                           const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                           const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                           const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                           const uint32_t *target_frames, int fitted);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

@@ -23,7 +23,8 @@ SYMBOLS = [
     "zv_debug_get", "zv_batch_timeline", "zv_encode_taps_prosody", "zv_synthesize_prosody", "zv_synthesize_batch_prosody",
     "zv_synthesize_batch_begin_prosody", "zv_encode_taps_phonemes", "zv_synthesize_phonemes", "zv_synthesize_batch_phonemes",
     "zv_synthesize_batch_begin_phonemes", "zv_synthesize_fitted", "zv_synthesize_batch_fitted", "zv_synthesize_batch_begin_fitted",
-    "zv_debug_voc_runs", "zv_debug_poison",
+    "zv_debug_voc_runs", "zv_debug_poison", "zv_encode_taps_target", "zv_synthesize_target", "zv_synthesize_batch_target",
+    "zv_synthesize_batch_begin_target",
 ]
 
 
@@ -180,6 +181,12 @@ def load_library(path: Optional[str] = None):
         lib.zv_synthesize_fitted.argtypes = lib.zv_synthesize_phonemes.argtypes
         lib.zv_synthesize_batch_fitted.argtypes = lib.zv_synthesize_batch_phonemes.argtypes
         lib.zv_synthesize_batch_begin_fitted.argtypes = lib.zv_synthesize_batch_begin_phonemes.argtypes
+    # the target forms: the _phonemes argument lists, the target (batches: uint32 [n_utt] or NULL) and, for the synthesize forms, fitted
+    if hasattr(lib, "zv_synthesize_target"):
+        lib.zv_encode_taps_target.argtypes = lib.zv_encode_taps_phonemes.argtypes + [u32]
+        lib.zv_synthesize_target.argtypes = lib.zv_synthesize_phonemes.argtypes + [u32, C.c_int]
+        lib.zv_synthesize_batch_target.argtypes = lib.zv_synthesize_batch_phonemes.argtypes + [C.POINTER(u32), C.c_int]
+        lib.zv_synthesize_batch_begin_target.argtypes = lib.zv_synthesize_batch_begin_phonemes.argtypes + [C.POINTER(u32), C.c_int]
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -240,10 +247,26 @@ def _check_fitted(fitted, Ts):
     return bool(fitted)
 
 
-def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False):
+def _check_target(target, T):
+    """a target frame count (None: the call has none) against the capacity T, checked before anything reaches the library"""
+    if target is None:
+        return None
+    if isinstance(target, (bool, np.bool_)) or not isinstance(target, (int, np.integer)):
+        raise TypeError(f"target_frames must be an integer frame count, not {type(target).__name__}")
+    if target < 0:
+        raise ValueError(f"target_frames = {target}: a frame count cannot be negative")
+    if target > T:
+        raise ValueError(f"target_frames = {target} exceeds the frame capacity T = {T}")
+    return int(target)
+
+
+def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None):
     """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
     name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status.
-    fitted: name_fitted, which takes everything (NULL for what the call lacks)"""
+    fitted: name_fitted, which takes everything (NULL for what the call lacks).  target (a frame count, or the batches' uint32
+    array): name_target, which takes everything and the fitted flag"""
+    if target is not None:
+        return getattr(lib, name + "_target")(*args, prosody, phonemes, durations, target, int(fitted))
     if fitted:
         return getattr(lib, name + "_fitted")(*args, prosody, phonemes, durations)
     if phonemes is not None or durations is not None:
@@ -380,11 +403,14 @@ class Model:
         return int(self.lib.zv_max_frames(self.h))
 
     def encode(self, ids, puncts, style, T: int, num_phonemes: Optional[int] = None, prosody=None, phonemes=None,
-               return_durations: bool = False) -> dict:
+               return_durations: bool = False, target_frames: Optional[int] = None) -> dict:
         """num_phonemes < len(ids): all ids are encoded, the length regulator walks the first num_phonemes (FS2Encoder::eval).
         prosody (Prosody, dict or 5-sequence): zv_encode_taps_prosody; None: zv_encode_taps.
         phonemes (PhonemeControls or dict of arrays [len(ids)]) or return_durations: zv_encode_taps_phonemes, and the result gains
-        "durations" (the phoneme timings, int32 [len(ids)])"""
+        "durations" (the phoneme timings, int32 [len(ids)]).
+        target_frames (0 <= frames <= T): zv_encode_taps_target — the durations are fitted to sum to exactly that many frames (0: the
+        bits of the call without it); None: the entry points above"""
+        target = _check_target(target_frames, T)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
@@ -399,18 +425,25 @@ class Model:
         pc = _phoneme_controls(phonemes, N)
         if pc is not None or return_durations:
             out["durations"] = np.empty(N, np.int32)
-        self._chk(_call_variant(self.lib, "zv_encode_taps", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct),
-                                _ptr(out.get("durations"))))
+        if target is not None:
+            self._chk(self.lib.zv_encode_taps_target(*args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct),
+                                                     _ptr(out.get("durations")), target))
+        else:
+            self._chk(_call_variant(self.lib, "zv_encode_taps", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct),
+                                    _ptr(out.get("durations"))))
         out["n_frames"] = int(nf.value)
         return out
 
     def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False,
-                   fitted: bool = False):
+                   fitted: bool = False, target_frames: Optional[int] = None):
         """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
         arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
         as a third element.  fitted: zv_synthesize_fitted — T is a capacity, the utterance is decoded and vocoded as the n_frames
-        the length regulator fills; wav keeps the capacity shape [T * hop], zero behind n_frames * hop"""
+        the length regulator fills; wav keeps the capacity shape [T * hop], zero behind n_frames * hop.
+        target_frames (0 <= frames <= T): zv_synthesize_target — the durations are fitted to sum to exactly that many frames (0: the
+        bits of the call without it); None: the entry points above"""
         fitted = _check_fitted(fitted, [T])
+        target = _check_target(target_frames, T)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
@@ -420,7 +453,7 @@ class Model:
         pc = _phoneme_controls(phonemes, len(ids))
         dur = np.empty(len(ids), np.int32) if return_durations else None
         self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur),
-                                fitted))
+                                fitted, target))
         return (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
 
     def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False) -> "BatchCall":
@@ -430,9 +463,9 @@ class Model:
         return BatchCall(self, utterances, durations, fitted)
 
     def synthesize_batch(self, utterances, return_durations: bool = False, fitted: bool = False):
-        """utterances: list of (ids, puncts, style, T[, prosody[, phonemes]]) -> list of (wav, n_frames); each utterance keeps its
-        own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its per-phoneme controls
-        (PhonemeControls, dict of arrays or None).  return_durations: (wav, n_frames, durations) tuples.  fitted:
+        """utterances: list of (ids, puncts, style, T[, prosody[, phonemes[, target_frames]]]) -> list of (wav, n_frames); each
+        utterance keeps its own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its
+        per-phoneme controls (PhonemeControls, dict of arrays or None), with a seventh its target frame count (None / 0: none).  return_durations: (wav, n_frames, durations) tuples.  fitted:
         zv_synthesize_batch_fitted — every T is a capacity, wav keeps the capacity shape with zeros behind n_frames * hop"""
         call = BatchCall(self, utterances, return_durations, fitted)
         call.run()
@@ -507,8 +540,10 @@ class Model:
 
 
 class BatchCall:
-    """utterances: (ids, puncts, style, T), (ids, puncts, style, T, prosody) or (ids, puncts, style, T, prosody, phonemes)
-    tuples.  When any utterance carries a prosody (the others get the identity) the _prosody entry points are called with the
+    """utterances: (ids, puncts, style, T), (ids, puncts, style, T, prosody), (ids, puncts, style, T, prosody, phonemes) or
+    (ids, puncts, style, T, prosody, phonemes, target_frames) tuples.  When any utterance carries a target frame count (a seventh
+    element that is not None) the _target entry points are called with the uint32 array .targets (0 for the others), which
+    set_target_frames() rewrites in place: the next run() / begin() fits the durations to the new targets with the same buffers.  When any utterance carries a prosody (the others get the identity) the _prosody entry points are called with the
     array .prosody, which set_prosody() rewrites in place: the next run() / begin() uses the new values with the same buffers (a
     captured graph replays with them).  When any utterance carries per-phoneme controls, or durations=True, the _phonemes entry
     points are called with the array .phonemes (set_phoneme_controls() rewrites an entry) and .durations[i] holds utterance i's
@@ -516,6 +551,10 @@ class BatchCall:
 
     def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False):
         self.fitted = _check_fitted(fitted, [u[3] for u in utterances])
+        tgs = [_check_target(u[6], u[3]) if len(u) > 6 else None for u in utterances]
+        self.targets = None
+        if any(t is not None for t in tgs):
+            self.targets = (C.c_uint32 * len(utterances))(*[t or 0 for t in tgs])
         self.model = model
         n = self.n = len(utterances)
         self.keep, self.wavs = [], []
@@ -552,6 +591,13 @@ class BatchCall:
         self.pkeep[i] = pc
         self.phonemes[i] = pc.struct if pc is not None else PhonemeControlsC()
 
+    def set_target_frames(self, i: int, frames):
+        """utterance i's target frame count (0 / None: none) for the following run() / begin() (the call must have been built with a
+        target on some utterance)"""
+        if self.targets is None:
+            raise ValueError("this BatchCall was built without target frame counts")
+        self.targets[i] = _check_target(frames, int(self.Ts[i])) or 0
+
     def set_prosody(self, i: int, prosody):
         """utterance i's controls for the following run() / begin() (the call must have been built with controls)"""
         if self.prosody is None:
@@ -561,13 +607,13 @@ class BatchCall:
     def run(self):
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted))
+        m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted))
+        m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets))
 
     def end(self, lane: int):
         m = self.model

@@ -160,7 +160,17 @@ struct Request
     int32_t *const            *durations = nullptr;
     // fitted (zv_synthesize_fitted): decode and vocode each utterance as the n_frames the length regulator fills, not as T
     bool                       fitted = false;
+    // target durations (zv_*_target): [count] or null, 0 = no target for that utterance
+    const uint32_t            *target_frames = nullptr;
 
+    // any utterance with a target: then every utterance gets a ctl row and pctl rows (the identity where it has no controls), which
+    // the device step between the duration predictor and the length regulator reads and rewrites (kernels.h launch_fit_durations)
+    bool targets() const
+    {
+        for (uint32_t u = 0; target_frames && u < count; u++)
+            if (target_frames[u]) return true;
+        return false;
+    }
     // any utterance with per-phoneme controls: then every utterance gets rows (the identity where it has none)
     bool phoneme_controls() const
     {
@@ -192,6 +202,7 @@ struct Request
         if (prosody) s.prosody += a;
         if (phonemes) s.phonemes += a;
         if (durations) s.durations += a;
+        if (target_frames) s.target_frames += a;
         return s;
     }
 };
@@ -231,6 +242,7 @@ static void check_request(zv_model *m, const Request &r)
 {
     if (!(m && r.ids && r.puncts && r.styles && r.n && r.T && r.out)) zv::fail(ZV_ERR_ARG, "%s: null argument", r.fn);
     const Model &M = *m->m;
+    const bool tg = r.targets();
     for (uint32_t u = 0; u < r.count; u++)
     {
         try
@@ -244,6 +256,10 @@ static void check_request(zv_model *m, const Request &r)
             check_ids(M, r.ids[u], r.puncts[u], r.n[u]);
             if (r.prosody) check_prosody(r.prosody[u]);
             if (r.phonemes) check_phoneme_controls(M, r.phonemes[u], r.n[u]);
+            if (r.target_frames && r.target_frames[u] > r.T[u])
+                zv::fail(ZV_ERR_ARG, "target_frames = %u exceeds the capacity T = %u", r.target_frames[u], r.T[u]);
+            if (tg && r.n[u] > (uint32_t)zv::FIT_MAX_TOKENS)      // one launch covers the request's utterances, with or without a target
+                zv::fail(ZV_ERR_ARG, "target_frames needs n <= %d phonemes, got %u", zv::FIT_MAX_TOKENS, r.n[u]);
         }
         catch (const zv::Error &e)
         {
@@ -255,14 +271,18 @@ static void check_request(zv_model *m, const Request &r)
 // A request's controls in the kernels' layouts (kernels.h CTL_*, PCTL_*), written where the caller says: a batch's pinned input
 // block, or a single utterance's host staging.  ctl: with prosody, one zv::CTL_STRIDE row per utterance.  pctl: with per-phoneme
 // controls, one zv::PCTL_STRIDE row per token, packed like the token table; absent fields get the identity {-1, 1, 0, 0}.
+// With a target on any utterance both are written: the identity prosody {1, 1, 0, 1, 0} where none is given, identity rows for an
+// utterance without per-phoneme controls, and each utterance's target in CTL_TARGET (frame counts up to 32 768 are exact in f32).
 static void pack_controls(const Request &r, float *ctl, float *pctl)
 {
-    const bool pc = r.phoneme_controls();
+    const bool tg = r.targets(), pc = r.phoneme_controls() || tg;
+    static const zv_prosody identity = {1.0f, 1.0f, 0.0f, 1.0f, 0.0f};
+    static const zv_phoneme_controls none = {nullptr, nullptr, nullptr, nullptr};
     for (uint32_t u = 0, row = 0; u < r.count; row += r.n[u], u++)
     {
-        if (r.prosody)
+        if (r.prosody || tg)
         {
-            const zv_prosody &p = r.prosody[u];
+            const zv_prosody &p = r.prosody ? r.prosody[u] : identity;
             float *c = ctl + (size_t)u * zv::CTL_STRIDE;
             std::fill(c, c + zv::CTL_STRIDE, 0.0f);
             c[zv::CTL_DURATION] = p.duration_scale;
@@ -270,10 +290,11 @@ static void pack_controls(const Request &r, float *ctl, float *pctl)
             c[zv::CTL_PITCH + 1] = p.pitch_shift;
             c[zv::CTL_ENERGY] = p.energy_scale;
             c[zv::CTL_ENERGY + 1] = p.energy_shift;
+            if (tg) c[zv::CTL_TARGET] = (float)r.target_frames[u];
         }
         for (uint32_t i = 0; pc && i < r.n[u]; i++)
         {
-            const zv_phoneme_controls &p = r.phonemes[u];
+            const zv_phoneme_controls &p = r.phonemes ? r.phonemes[u] : none;
             float *c = pctl + (size_t)(row + i) * zv::PCTL_STRIDE;
             c[zv::PCTL_FRAMES] = p.duration_frames ? (float)p.duration_frames[i] : -1.0f;
             c[zv::PCTL_DURATION] = p.duration_scale ? p.duration_scale[i] : 1.0f;
@@ -315,9 +336,9 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         Model &M = *m->m;
         use_lane0(m);
         const uint32_t n = r.n[0], T = r.T[0];
-        const bool pc = r.phoneme_controls(), dur = r.timings();
+        const bool tg = r.targets(), pc = r.phoneme_controls() || tg, dur = r.timings();
         const size_t E = M.E(), b_ids = (size_t)n * 4, b_hid = (size_t)T * E * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
-        const size_t b_ctl = r.prosody ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
+        const size_t b_ctl = r.prosody || tg ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
         // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
@@ -334,6 +355,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         std::vector<int32_t> cum(dur ? n : 0);
         pack_controls(r, ctl.data(), pctl.data());
         zv::Batch bt = zv::Batch::single(n, T, r.num_phonemes[0]);
+        bt.has_targets = tg;
         ZV_HIP(hipMemcpyAsync(d_ids, r.ids[0], b_ids, hipMemcpyHostToDevice, M.stream()));
         ZV_HIP(hipMemcpyAsync(d_pun, r.puncts[0], b_ids, hipMemcpyHostToDevice, M.stream()));
         ZV_HIP(hipMemcpyAsync(d_sty, r.styles[0], E * 4, hipMemcpyHostToDevice, M.stream()));
@@ -612,7 +634,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     if (pb.active) zv::fail(ZV_ERR_ARG, "lane %d already has a batch in flight", lane);
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
-    const bool pc = r.phoneme_controls(), dur = r.timings();
+    const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings();
     uint32_t nmax = 0, tmax = 0, ntot = 0;
     for (uint32_t u = 0; u < r.count; u++)
     {
@@ -629,12 +651,13 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     bt.t_rows = (size_t)bt.nseg * bt.t_max;
     // input block, uploaded in one copy from its pinned mirror: [token table][frame table][ids][puncts][styles][controls]
     // [phoneme controls] (tables: one entry per utterance + one that spans all of them, see Batch::tokens_merged; controls: only
-    // with prosody, one zv::CTL_STRIDE row per utterance; phoneme controls: only with per-phoneme controls, one zv::PCTL_STRIDE
-    // row per token row — uploaded with the rest, so a replayed graph reads the values of this call)
+    // with prosody or a target, one zv::CTL_STRIDE row per utterance; phoneme controls: only with per-phoneme controls or a target,
+    // one zv::PCTL_STRIDE row per token row — uploaded with the rest, so a replayed graph reads the values of this call, also where
+    // the previous run's fit_durations_kernel has rewritten the rows' frame column)
     Layout in;
     const size_t b_tab = (size_t)(bt.nseg + 1) * sizeof(zv::Seg);
     const size_t i_tok = in.at(b_tab), i_frm = in.at(b_tab), i_ids = in.at(bt.n_rows * 4), i_pun = in.at(bt.n_rows * 4),
-                 i_sty = in.at((size_t)bt.nseg * E * 4), i_ctl = in.at(r.prosody ? (size_t)bt.nseg * zv::CTL_STRIDE * 4 : 0),
+                 i_sty = in.at((size_t)bt.nseg * E * 4), i_ctl = in.at(ctl ? (size_t)bt.nseg * zv::CTL_STRIDE * 4 : 0),
                  i_pctl = in.at(pc ? bt.n_rows * zv::PCTL_STRIDE * 4 : 0), b_in = in.size();
     // device block: [frame counts][input block][hidden][mel][wav][scan] (scan: only when timings are asked for, the length
     // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
@@ -679,7 +702,8 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     }
     bt.d_tok = (const zv::Seg *)(d_in + i_tok);
     bt.d_frm = (const zv::Seg *)(d_in + i_frm);
-    if (r.prosody) bt.d_ctl = (const float *)(d_in + i_ctl);
+    if (ctl) bt.d_ctl = (const float *)(d_in + i_ctl);
+    bt.has_targets = tg;
     if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
     if (dur) bt.d_cum = (int32_t *)(io + o_cum);
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
@@ -907,6 +931,44 @@ zv_status zv_synthesize_batch_begin_fitted(zv_model *m, uint32_t lane, uint32_t 
 {
     return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
                                  durations, true});
+}
+
+// The target forms: the _phonemes / _fitted requests plus the targets (NULL / 0 = none: the request of the call without them).
+zv_status zv_encode_taps_target(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n,
+                                uint32_t num_phonemes, uint32_t T, float *hidden, uint32_t *n_frames, float *features, float *logdur,
+                                float *pitch, float *energy, int32_t *pitch_bucket, int32_t *energy_bucket, const zv_prosody *prosody,
+                                const zv_phoneme_controls *phonemes, int32_t *durations, uint32_t target_frames)
+{
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &num_phonemes, &T, &hidden, n_frames, prosody, phonemes, &durations,
+                          false, &target_frames},
+                      Taps{features, logdur, pitch, energy, pitch_bucket, energy_bucket});
+}
+
+zv_status zv_synthesize_target(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                               float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                               int32_t *durations, uint32_t target_frames, int fitted)
+{
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody, phonemes, &durations, fitted != 0,
+                          &target_frames});
+}
+
+zv_status zv_synthesize_batch_target(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                     const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                     uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                     int32_t *const *durations, const uint32_t *target_frames, int fitted)
+{
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                durations, fitted != 0, target_frames});
+}
+
+zv_status zv_synthesize_batch_begin_target(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                           const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                           const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                           const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                           const uint32_t *target_frames, int fitted)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                 durations, fitted != 0, target_frames});
 }
 
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)

@@ -158,6 +158,13 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
     if (dbg_layer.done) return t;
     predictor(enc_.energy, t.energy, enc_.energy_emb, t.energy_bucket, CTL_ENERGY, PCTL_ENERGY);      // sees the pitch-augmented features (:569-572)
     if (dbg_layer.done) return t;
+    // target durations: the integer durations that sum to each utterance's target become forced frames in the phoneme control rows,
+    // which the regulator below reads as it reads a caller's (kernels.h launch_fit_durations)
+    if (bt.has_targets)
+    {
+        if (!bt.d_ctl || !bt.d_pctl) fail(ZV_ERR_ARG, "a batch with target durations needs its control rows");
+        ZV_LAUNCH("enc_fit_durations", 24.0 * nd, 0.0, launch_fit_durations(stream(), t.logdur, bt.d_ctl, bt.d_pctl, tk, fr));
+    }
     ZV_LAUNCH("enc_length_regulator", 4.0 * (nd + (double)bt.t_rows) * Ed, 0.0,
               launch_length_regulator(stream(), x, Ed, t.logdur, Ed, d_hidden, Ed, t.cum, d_nframes, tk, fr, bt.d_ctl, bt.d_pctl));
     // fitted: the frame table of everything downstream, from the counts the regulator has just stored

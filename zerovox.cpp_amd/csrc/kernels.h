@@ -302,6 +302,7 @@ constexpr int CTL_STRIDE = 8;
 constexpr int CTL_DURATION = 0;        // duration_scale
 constexpr int CTL_PITCH = 1;           // pitch_scale, pitch_shift
 constexpr int CTL_ENERGY = 3;          // energy_scale, energy_shift
+constexpr int CTL_TARGET = 5;          // target frames as an exact f32 integer, 0 = none (launch_fit_durations; slots 6, 7 unused)
 // Per-phoneme controls (include/zerovox_amd.h zv_phoneme_controls): f32 [token row][PCTL_STRIDE], indexed by ABSOLUTE token row (so
 // the batch's segments, tokens_merged() and the inline single segment index them alike).  A null pctl is the uncontrolled path.
 constexpr int PCTL_STRIDE = 4;
@@ -343,6 +344,15 @@ hipError_t launch_bucket_embed_add(hipStream_t s, const float *pred, int nbins, 
 hipError_t launch_length_regulator(hipStream_t s, const float *feat, int ld, const float *logdur, int C, float *hidden,
                                    int ldh, int32_t *cum, int32_t *n_frames, const Segs &tokens, const Segs &frames,
                                    const float *ctl = nullptr, const float *pctl = nullptr);
+
+// target durations (include/zerovox_amd.h "target durations", fit_durations.h): for every segment whose ctl[seg][CTL_TARGET] > 0 the
+// integer durations that sum to the target replace pctl[row][PCTL_FRAMES] of the segment's first `aux` token rows IN PLACE (the
+// pointer is const for every other kernel), so the length regulator launched next takes them as forced frames.  ctl and pctl must
+// both be set; at most FIT_MAX_TOKENS tokens per segment (two 64-bit LDS entries each, with the workgroup's 8 KiB of sums inside the
+// 64 KiB a workgroup gets by default), else hipErrorInvalidValue
+constexpr int FIT_MAX_TOKENS = 3584;
+hipError_t launch_fit_durations(hipStream_t s, const float *logdur, const float *ctl, const float *pctl, const Segs &tokens,
+                                const Segs &frames);
 
 // ---- fitted mode (include/zerovox_amd.h zv_synthesize_fitted): the decoder and the vocoder run over the frames the length regulator
 // filled instead of the capacity.  live[u] = {frames[u].row0, min(n_frames[u], frames[u].rows), 0, 0} for the nseg entries of

@@ -4,6 +4,7 @@
 // covers all utterances of a batch while each utterance keeps its own extents.
 #include "kernels.h"
 #include "knobs.h"
+#include "fit_durations.h"
 
 #include <cstring>
 
@@ -1401,6 +1402,116 @@ hipError_t launch_length_regulator(hipStream_t s, const float *feat, int ld, con
     else
         hipLaunchKernelGGL(lr_gather_kernel, dim3(frames.max_rows, frames.nseg), dim3(256), 0, s, feat, ld, cum, C, hidden, ldh, tokens,
                            frames);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Target durations (include/zerovox_amd.h "target durations", the rule: fit_durations.h): between the duration predictor and the
+// length regulator.  One workgroup per utterance; a segment whose ctl row holds no target (CTL_TARGET <= 0) returns at once and
+// leaves its rows alone.  Otherwise the durations d_i that sum to the target are stored as FORCED frame counts in the PCTL_FRAMES
+// column of the utterance's pctl rows, where the regulator kernels read them as they read a caller's duration_frames: those
+// kernels do not change.  The rows are uploaded at the head of every run, so a replay starts from the caller's values again.
+//   pass 1: forced phonemes add min(frames, T) to Fs, free ones get their weight q (lr_scan_kernel's f32 duration, fit_weight)
+//   pass 2: share and remainder of every free phoneme (64-bit integers from here on); L = R - sum of the shares
+//   pass 3: free phoneme i gets one frame more when fewer than L free phonemes come before it (largest remainder, then lower
+//           index): counted over the LDS-resident remainders, broadcast reads, n^2 compares (2.3 M at 1 501 phonemes)
+// Sums are integer sums over the workgroup: any order, the same values.  Tokens at or past num_phonemes (aux) are left alone: the
+// regulator gives them 0 whatever their row says.
+__device__ __forceinline__ long long fit_block_sum(long long v, long long *red)
+{
+    const int tid = threadIdx.x;
+    __syncthreads();                         // the previous sum's red[0] has been read by everyone
+    red[tid] = v;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1)
+    {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(1024) void fit_durations_kernel(const float *__restrict__ logdur, const float *__restrict__ ctl,
+                                                             float *__restrict__ pctl, const Segs tokens, const Segs frames)
+{
+    extern __shared__ long long fit_lds[];   // [max_rows] weight, then share (-1: not free), [max_rows] remainder (-1: not free)
+    __shared__ long long red[1024];
+    const Seg tk = seg_at(tokens, blockIdx.x), fr = seg_at(frames, blockIdx.x);
+    const float *cv = ctl + (size_t)blockIdx.x * CTL_STRIDE;
+    const int target = (int)cv[CTL_TARGET];
+    const int n = tk.rows < tokens.max_rows ? tk.rows : tokens.max_rows, T = fr.rows;      // (the LDS arrays hold max_rows entries)
+    if (target <= 0 || n <= 0) return;
+    const int nwalk = tk.aux < n ? tk.aux : n;
+    const int tid = threadIdx.x;
+    long long *qs = fit_lds, *rs = fit_lds + tokens.max_rows;
+    float *rows = pctl + (size_t)tk.row0 * PCTL_STRIDE;
+    const float *ld_ = logdur + tk.row0;
+    const float dscale = cv[CTL_DURATION];
+    long long Fs = 0, Q = 0, n_free = 0;
+    for (int i = tid; i < nwalk; i += 1024)
+    {
+        const float *pr = rows + (size_t)i * PCTL_STRIDE;
+        const float f = pr[PCTL_FRAMES];
+        long long q = -1;
+        if (f >= 0.f)
+        {
+            const int forced = (int)f;
+            Fs += forced < T ? forced : T;
+        }
+        else
+        {
+            float dur = (float)(exp((double)ld_[i]) - 1.0);
+            dur = dur * dscale;
+            dur = dur * pr[PCTL_DURATION];
+            q = fit_weight(dur);
+            Q += q;
+            n_free++;
+        }
+        qs[i] = q;
+    }
+    Fs = fit_block_sum(Fs, red);
+    Q = fit_block_sum(Q, red);
+    n_free = fit_block_sum(n_free, red);
+    const long long R = (long long)target - Fs;
+    if (R <= 0 || n_free == 0)               // forced durations win: every free phoneme gets 0
+    {
+        for (int i = tid; i < nwalk; i += 1024)
+            if (qs[i] >= 0) rows[(size_t)i * PCTL_STRIDE + PCTL_FRAMES] = 0.f;
+        return;
+    }
+    const bool equal = Q == 0;               // no weight at all: equal shares
+    if (equal) Q = n_free;
+    long long shares = 0;
+    for (int i = tid; i < nwalk; i += 1024)
+    {
+        const long long q = equal ? 1 : qs[i];
+        const bool is_free = qs[i] >= 0;
+        const long long base = is_free ? fit_share(q, R, Q) : -1;
+        rs[i] = is_free ? fit_remainder(q, R, Q) : -1;
+        qs[i] = base;
+        if (is_free) shares += base;
+    }
+    const long long L = R - fit_block_sum(shares, red);       // (its barriers also publish rs[])
+    for (int i = tid; i < nwalk; i += 1024)
+    {
+        const long long ri = rs[i];
+        if (ri < 0) continue;
+        long long before = 0;
+        if (L > 0)
+            for (int j = 0; j < nwalk; j++) before += fit_before(rs[j], j, ri, i) ? 1 : 0;      // (a forced j holds -1: never before)
+        const long long d = qs[i] + (before < L ? 1 : 0);
+        rows[(size_t)i * PCTL_STRIDE + PCTL_FRAMES] = (float)d;
+    }
+}
+
+hipError_t launch_fit_durations(hipStream_t s, const float *logdur, const float *ctl, const float *pctl, const Segs &tokens,
+                                const Segs &frames)
+{
+    if (!logdur || !ctl || !pctl || tokens.nseg != frames.nseg || tokens.nseg < 1 || tokens.max_rows < 1) return hipErrorInvalidValue;
+    if (tokens.max_rows > FIT_MAX_TOKENS) return hipErrorInvalidValue;
+    const size_t lds = (size_t)tokens.max_rows * 2 * sizeof(long long);
+    // the rows are the caller's controls and read-only to every other kernel; this one rewrites their PCTL_FRAMES column in place
+    hipLaunchKernelGGL(fit_durations_kernel, dim3(tokens.nseg), dim3(1024), lds, s, logdur, ctl, const_cast<float *>(pctl), tokens, frames);
     return hipGetLastError();
 }
 

@@ -81,6 +81,10 @@ struct Batch
     // grids and the regulator itself stay by capacity.  A single utterance has a one-entry table.  Keyed like d_ctl: a fitted and
     // an unfitted schedule are different graphs, and a fitted graph replays for new lengths.
     Seg *d_frm_live = nullptr;
+    // Target durations (include/zerovox_amd.h "target durations"): some utterance's ctl row carries a target frame count, so the
+    // encoder launches fit_durations_kernel ahead of the length regulator (d_ctl and d_pctl are then both set).  Keyed: one launch
+    // more.  WHICH utterances have a target, and its value, is read at run time: a replay picks up new targets.
+    bool has_targets = false;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -103,12 +107,12 @@ struct Batch
     // the frames the decoder and the vocoder run over: the live table in fitted mode, else the capacity
     Segs frames() const { return d_frm_live ? Segs{d_frm_live, nseg, t_max, frm1} : frames_cap(); }
     // what of a Batch a captured schedule depends on: the capacities (grids, arena layout), the table pointers, the inline segments
-    // where there is no table, and the four optional pointers that change the kernels' arguments
+    // where there is no table, the four optional pointers that change the kernels' arguments and the flag that adds a launch
     bool same_schedule(const Batch &o) const
     {
         return nseg == o.nseg && n_max == o.n_max && t_max == o.t_max && n_rows == o.n_rows && t_rows == o.t_rows && d_tok == o.d_tok &&
                d_frm == o.d_frm && (d_tok || memcmp(&tok1, &o.tok1, sizeof(Seg)) == 0) && (d_frm || memcmp(&frm1, &o.frm1, sizeof(Seg)) == 0) &&
-               d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live;
+               d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live && has_targets == o.has_targets;
     }
 };
 

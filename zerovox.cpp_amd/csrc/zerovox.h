@@ -124,6 +124,9 @@ class ZeroVOXModel
     // capacity, the utterance is decoded and vocoded as the get_num_frames() frames the length regulator fills, the rest of
     // get_wav() is zero.  Prosody, per-phoneme controls and timings work as without it.
     void set_fitted(bool on) { fitted = on; }
+    // target durations (include/zerovox_amd.h "target durations") for the eval() calls that follow: the utterance's durations are
+    // fitted to sum to exactly `frames` (<= max_seq_len, ZV_ERR_ARG otherwise; 0 = none).  Works with everything above.
+    void set_target_frames(uint32_t frames) { target_frames = frames; }
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
@@ -149,6 +152,7 @@ class ZeroVOXModel
     bool                 has_phonemes = false, record_durations = false;
     std::vector<int32_t> durations;
     bool                 fitted = false;
+    uint32_t             target_frames = 0;
 };
 
 }  // namespace ZeroVOX

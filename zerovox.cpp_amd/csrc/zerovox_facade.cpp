@@ -167,7 +167,7 @@ void ZeroVOXModel::set_phoneme_controls(const zv_phoneme_controls *p, uint32_t n
 void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const float *style_embed, uint32_t num_phonemes)
 {
     const zv_prosody *pr = has_prosody ? &prosody : nullptr;
-    if (record_durations || fitted)
+    if (record_durations || fitted || target_frames)
     {
         // the per-phoneme entry points (controls and / or timings) and the fitted one; N = num_phonemes on both of eval()'s paths
         if (has_phonemes && pc_n != num_phonemes)
@@ -180,6 +180,22 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
         const zv_phoneme_controls pc = {ptr(pc_frames), ptr(pc_scale), ptr(pc_pitch), ptr(pc_energy)};
         const zv_phoneme_controls *pcp = has_phonemes ? &pc : nullptr;
         if (record_durations) durations.assign(num_phonemes, 0);
+        if (target_frames)
+        {
+            // the target forms take what the _phonemes and _fitted forms take; the stage-by-stage path keeps N = MAX_N_PHONEMES
+            int32_t *dur = record_durations ? durations.data() : nullptr;
+            if (fitted || num_phonemes != (uint32_t)MAX_N_PHONEMES)
+            {
+                chk(zv_synthesize_target(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr, pcp,
+                                         dur, target_frames, fitted ? 1 : 0));
+                return;
+            }
+            chk(zv_encode_taps_target(model, src_seq, puncts, style_embed, MAX_N_PHONEMES, num_phonemes, hparams.max_seq_len, hidden_state,
+                                      &n_frames, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pr, pcp, dur, target_frames));
+            decoder->eval(hidden_state, style_embed, mel);
+            meldec->eval(mel, wav);
+            return;
+        }
         if (fitted)
         {
             chk(zv_synthesize_fitted(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr, pcp,

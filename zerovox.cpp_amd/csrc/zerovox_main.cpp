@@ -9,7 +9,7 @@
 //     line 2: punctuation ids        (N integers)
 //     line 3: style embedding        (emb_dim + punct_emb_dim floats; a single 0 means the zero vector)
 //
-// usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info] [prosody flags]
+// usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info] [prosody flags] [target flags]
 //   --duration-scale S, --pitch-scale S, --pitch-shift D, --energy-scale S, --energy-shift D
 //            prosody controls (include/zerovox_amd.h zv_prosody): durations * S (0 < S <= 16), pitch / energy predictions
 //            p * S + D before bucketing; defaults 1, 1, 0, 1, 0 (the uncontrolled result).  A bad value is a usage error.
@@ -24,7 +24,13 @@
 //   --fit    fitted synthesis (include/zerovox_amd.h zv_synthesize_fitted): decode and vocode only the frames the length regulator
 //            produced, and write exactly those n_frames * hop samples — the audio of the utterance at its own length, where --trim
 //            cuts the file of the max_seq_len-frame run.  Works with the prosody flags, --phoneme-controls and --alignment.
+//   --target-frames F, --target-seconds S
+//            target durations (include/zerovox_amd.h "target durations"): the utterance's durations are fitted to sum to exactly F
+//            frames, or to floor(S * sampling rate / hop size + 0.5) frames; with --fit the file holds exactly that many frames.
+//            Work with --fit, the prosody flags, --phoneme-controls (forced frames stay) and --alignment.  A bad value, or a
+//            target above the checkpoint's max_seq_len, is a usage error.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -44,7 +50,7 @@ static void usage(FILE *f)
 {
     fprintf(f, "usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info]\n"
                "               [--duration-scale S] [--pitch-scale S] [--pitch-shift D] [--energy-scale S] [--energy-shift D]\n"
-               "               [--phoneme-controls FILE] [--alignment FILE]\n"
+               "               [--phoneme-controls FILE] [--alignment FILE] [--target-frames F | --target-seconds S]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
@@ -56,7 +62,9 @@ static void usage(FILE *f)
                "                       frames -1 keeps the prediction, 0..32768 forces it; 0 < scale <= 16)\n"
                "  --alignment FILE     write the phoneme timings as TSV: index phoneme_id start_frame frames start_sample samples\n"
                "  --trim               write only the frames the length regulator produced (cut from the max_seq_len-frame run)\n"
-               "  --fit                synthesize only those frames (the utterance at its own length) and write them\n",
+               "  --fit                synthesize only those frames (the utterance at its own length) and write them\n"
+               "  --target-frames F    fit the durations to exactly F frames (1 <= F <= the checkpoint's max_seq_len)\n"
+               "  --target-seconds S   the same for floor(S * sampling rate / hop size + 0.5) frames (S > 0)\n",
             k_default_model, k_default_out);
 }
 
@@ -153,6 +161,8 @@ int main(int argc, char **argv)
 {
     std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path;
     bool trim = false, fit = false, info = false, controlled = false;
+    long target_frames = 0;            // --target-frames
+    double target_seconds = 0.0;       // --target-seconds
     zv_prosody prosody = {1.0f, 1.0f, 0.0f, 1.0f, 0.0f};
     for (int i = 1; i < argc; i++)
     {
@@ -166,6 +176,32 @@ int main(int argc, char **argv)
         else if (a == "-o") out_path = need("-o");
         else if (a == "--phoneme-controls") pc_path = need("--phoneme-controls");
         else if (a == "--alignment") align_path = need("--alignment");
+        else if (a == "--target-frames")
+        {
+            const std::string v = need("--target-frames");
+            char *end = nullptr;
+            target_frames = strtol(v.c_str(), &end, 10);
+            if (v.empty() || end != v.c_str() + v.size() || target_frames < 1 || target_frames > 32768)
+            {
+                fprintf(stderr, "zerovox: --target-frames needs an integer in [1, 32768], got '%s'\n", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+            target_seconds = 0.0;
+        }
+        else if (a == "--target-seconds")
+        {
+            const std::string v = need("--target-seconds");
+            char *end = nullptr;
+            target_seconds = strtod(v.c_str(), &end);
+            if (v.empty() || end != v.c_str() + v.size() || !std::isfinite(target_seconds) || !(target_seconds > 0.0))
+            {
+                fprintf(stderr, "zerovox: --target-seconds needs a finite number > 0, got '%s'\n", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+            target_frames = 0;
+        }
         else if (a == "--trim") trim = true;
         else if (a == "--fit") fit = true;
         else if (a == "--info") info = true;
@@ -223,6 +259,20 @@ int main(int argc, char **argv)
         const ZeroVOX::zerovox_hparams &hp = model.get_hparams();
         if (controlled) model.set_prosody(prosody);
         if (fit) model.set_fitted(true);
+        if (target_seconds > 0.0)
+            target_frames = (long)std::min(floor(target_seconds * hp.audio_sampling_rate / hp.audio_hop_size + 0.5), 1e9);
+        if (target_frames > 0 || target_seconds > 0.0)
+        {
+            // the capacity of every eval() is the checkpoint's max_seq_len
+            if (target_frames < 1 || target_frames > (long)hp.max_seq_len)
+            {
+                fprintf(stderr, "zerovox: a target of %ld frames is outside [1, %u], the checkpoint's max_seq_len\n", target_frames,
+                        hp.max_seq_len);
+                usage(stderr);
+                return 2;
+            }
+            model.set_target_frames((uint32_t)target_frames);
+        }
         if (!pc_path.empty())
         {
             const zv_phoneme_controls pc = {pcf.frames.data(), pcf.scale.data(), pcf.pitch.data(), pcf.energy.data()};
