@@ -188,7 +188,13 @@ typedef void (*zv_wav_sink)(void *user, const float *wav, uint64_t first_sample,
 zv_status zv_vocode_stream(zv_model *m, const float *mel, uint32_t T, uint32_t chunk_frames, zv_wav_sink sink, void *user);
 /* frames of context (per side) outside which a mel frame cannot influence a sample: the vocoder's receptive field */
 uint32_t  zv_vocoder_halo_frames(zv_model *m);
-/* encoder -> decoder -> vocoder with every intermediate kept in HBM; wav[T*hop_size] */
+/* encoder -> decoder -> vocoder with every intermediate kept in HBM; wav[T*hop_size]
+ * Run-shortened decoding (the unfitted synthesize entry points, batches by default: switch ZV_DEC_RUNS).  Behind an utterance's
+ * n_frames the decoder's input is zero up to T and its convs reach 14 frames, so its tensors are constant in between: the
+ * decoder computes the rows in front of a = round_up(n_frames + 14 + 32, 32) and from b = round_down(T - 15, 32) on, counts the
+ * 32-row blocks in between in its InstanceNorm statistics as copies of the block in front of a, and one pass writes all T mel
+ * rows.  Results are UNCHANGED, bit for bit.  Off in fitted mode, under zv_debug_layer and in zv_decode*, whose hidden is the
+ * caller's. */
 zv_status zv_synthesize(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style,
                         uint32_t n, uint32_t T, float *wav, uint32_t *n_frames);
 /* zv_synthesize with prosody controls (NULL = identity: the bits of zv_synthesize) */

@@ -342,12 +342,13 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
         // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
-        // [live frame table] (fitted: one entry, written on the device)
+        // [live frame table] (fitted: one entry, written on the device) [decoder run table] (run-shortened decoding: one entry, likewise)
         Layout L;
         const size_t o_nf = L.at(4), o_ids = L.at(b_ids), o_pun = L.at(b_ids), o_sty = L.at(E * 4), o_ctl = L.at(b_ctl),
                      o_pctl = L.at(b_pctl), o_hid = L.at(b_hid);
         const size_t o_mel = taps ? 0 : L.at((size_t)T * M.hp.audio_num_mels * 4), o_wav = taps ? 0 : L.at(b_wav),
-                     o_cum = taps ? 0 : L.at(dur ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0);
+                     o_cum = taps ? 0 : L.at(dur ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
+                     o_runs = L.at(!r.fitted && !taps ? sizeof(zv::Seg) : 0);
         char *io = (char *)M.io_scratch(L.size());
         int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
@@ -356,6 +357,8 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         pack_controls(r, ctl.data(), pctl.data());
         zv::Batch bt = zv::Batch::single(n, T, r.num_phonemes[0]);
         bt.has_targets = tg;
+        if (r.fitted && !taps) bt.d_frm_live = (zv::Seg *)(io + o_live);
+        if (!taps && M.dec_runs_on(bt)) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
         ZV_HIP(hipMemcpyAsync(d_ids, r.ids[0], b_ids, hipMemcpyHostToDevice, M.stream()));
         ZV_HIP(hipMemcpyAsync(d_pun, r.puncts[0], b_ids, hipMemcpyHostToDevice, M.stream()));
         ZV_HIP(hipMemcpyAsync(d_sty, r.styles[0], E * 4, hipMemcpyHostToDevice, M.stream()));
@@ -387,7 +390,6 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         {
             float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
             if (dur) bt.d_cum = (int32_t *)(io + o_cum);
-            if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
             ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream()));
             if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), bt.d_cum, b_ids, hipMemcpyDeviceToHost, M.stream()));
@@ -664,7 +666,8 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     Layout dev;
     const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
                  o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur ? bt.n_rows * 4 : 0),
-                 o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0);      // fitted: the live frame table, written on the device
+                 o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0),      // fitted: the live frame table, written on the device
+                 o_runs = dev.at(!r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0);     // run-shortened decoding: the decoder's run table, likewise
     M.reserve_batch(bt);
     char *io = (char *)M.io_scratch(dev.size());
     // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan]
@@ -707,6 +710,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
     if (dur) bt.d_cum = (int32_t *)(io + o_cum);
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
+    if (M.dec_runs_on(bt)) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
     int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(d_in + i_ids), *d_pun = (int32_t *)(d_in + i_pun);
     float *d_sty = (float *)(d_in + i_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
     int32_t *h_nf = (int32_t *)(pin + p_nf), *h_cum = dur ? (int32_t *)(pin + p_cum) : nullptr;

@@ -1,6 +1,7 @@
 // decoder.cpp — the StyleTTS mel decoder's arena layout and kernel schedule (see model.h).
 #include "schedule.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace zv
@@ -20,7 +21,42 @@ Model::DecLayout Model::dec_layout(DeviceArena &a, const Batch &bt) const
     d.xa16 = a.take_n<_Float16>(L * CAT);
     d.t16 = a.take_n<_Float16>(L * B);
     d.xr16 = a.take_n<_Float16>(L * CAT);
+    // carved whether or not a call decodes run-shortened, so that a layout depends on the batch's shape alone
+    d.mel_c = a.take_n<float>(L * dec_.M);
     return d;
+}
+
+// Two ways to feed a conv its normalised operand, same bits (tests): (a) the conv normalises while it stages its
+// input tile (PRO_NORM_ACT) — no extra launch, right for a very short utterance where every launch is latency; (b) one
+// pass writes the f16 operand (launch_norm_act_f16) and the conv copies it (PRO_RAW_F16) — right when launches have
+// many rounds of workgroups: a 1 056-wide conv stages every input tile 9 times (once per group of 128 output
+// channels), so (a) repeats the f32 prologue 9 times and reads twice the bytes.
+bool Model::dec_prepass_on(const Batch &bt) const
+{
+    const int pre_env = knob(ZV_DEC_PREPASS);      // test / A-B hook
+    // (round 4: with the single-utterance conv form's loader waves the pass pays from 256 frames on — it takes the statistics launch's
+    // place and leaves the loaders a plain copy: one utterance of 128 / 256 / 512 / 1 024 frames 1.32 / 1.345 / 1.62 / 2.16 ms fused,
+    // 1.33 / 1.33 / 1.58 / 2.07 ms with the pass)
+    return pre_env >= 0 ? pre_env != 0 : (size_t)bt.t_max * bt.nseg >= 256;
+}
+
+// batches (ZV_DEC_RUNS = 1): by capacity, with the threshold of ZV_VOC_RUNS and the other batch switches, so that a single utterance
+// keeps its schedule; no sweep of capacities below it is on record
+bool Model::dec_runs_on(const Batch &bt) const
+{
+    const int k = knob(ZV_DEC_RUNS);
+    return k != 0 && !bt.d_frm_live && dbg_layer.kind < 0 && dec_prepass_on(bt) && (k == 2 || (long)bt.t_rows >= 16384);
+}
+
+// a residual block reaches as far as the longer of its two paths (conv1 -> conv2, the shortcut); the concat joins the encode
+// blocks' path and the asr conv's; the output conv ends the chain
+int Model::dec_reach_frames() const
+{
+    auto half = [](const ConvW &w) { return w.K > 0 ? (w.K - 1) / 2 : 0; };
+    auto blk = [&](const DecBlk &b) { return std::max(half(b.conv1) + half(b.conv2), b.learned_sc ? half(b.sc) : 0); };
+    int r = std::max(blk(dec_.enc[0]) + blk(dec_.enc[1]), half(dec_.asr0));
+    for (const DecBlk &b : dec_.dec) r += blk(b);
+    return r + half(dec_.to_out);
 }
 
 // StyleTTS mel decoder (reference src/stylettsdec.cpp:306-470)
@@ -28,7 +64,11 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
 {
     if (bt.t_rows == 0 || bt.t_max <= 0) fail(ZV_ERR_ARG, "T must be > 0");
     const DecLayout lay = dec_layout(stage_arena(bt), bt);
-    const Segs fr = bt.frames();
+    // Run-shortened decoding: every launch below takes its extents from the run table the encoder wrote, the statistics add the
+    // dropped blocks back, the last conv writes the compact mel and one pass expands it to d_mel's T rows per utterance.
+    const bool runs = bt.d_dec_runs != nullptr;
+    if (runs && !dec_runs_on(bt)) fail(ZV_ERR_ARG, "internal: a decoder run table on a schedule that takes none");
+    const Segs fr = runs ? Segs{bt.d_dec_runs, bt.nseg, bt.t_max, bt.frm1} : bt.frames();
     const int Ed = (int)E(), B = 2 * Ed, R = dec_.R, CAT = B + R, S = bt.nseg;
     const size_t L = bt.t_rows;
     const int nblk = lay.nblk, hs = lay.hs, ss = lay.ss;
@@ -36,17 +76,17 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
     double *const part_t = lay.part_t, *const part_o = lay.part_o;
     float *const cat = lay.cat, *const t1 = lay.t1, *const sc = lay.sc, *const x0 = lay.x0, *const xa = lay.xa, *const asr_t = lay.asr_t;
     _Float16 *const xa16 = lay.xa16, *const t16 = lay.t16, *const xr16 = lay.xr16;
-    const double Ld = (double)L;
-    // Two ways to feed a conv its normalised operand, same bits (tests): (a) the conv normalises while it stages its
-    // input tile (PRO_NORM_ACT) — no extra launch, right for a very short utterance where every launch is latency; (b) one
-    // pass writes the f16 operand (launch_norm_act_f16) and the conv copies it (PRO_RAW_F16) — right when launches have
-    // many rounds of workgroups: a 1 056-wide conv stages every input tile 9 times (once per group of 128 output
-    // channels), so (a) repeats the f32 prologue 9 times and reads twice the bytes.
-    const int pre_env = knob(ZV_DEC_PREPASS);      // test / A-B hook
-    // (round 4: with the single-utterance conv form's loader waves the pass pays from 256 frames on — it takes the statistics launch's
-    // place and leaves the loaders a plain copy: one utterance of 128 / 256 / 512 / 1 024 frames 1.32 / 1.345 / 1.62 / 2.16 ms fused,
-    // 1.33 / 1.33 / 1.58 / 2.07 ms with the pass)
-    const bool prepass = pre_env >= 0 ? pre_env != 0 : (size_t)bt.t_max * bt.nseg >= 256;
+    double Ld = (double)L;                          // rows the launches cover (accounting)
+    if (runs && profiling)
+    {
+        // the profile states work done: the rows the table holds (this path is eager and the host waits anyway)
+        std::vector<Seg> tab((size_t)S);
+        ZV_HIP(hipMemcpyAsync(tab.data(), bt.d_dec_runs, tab.size() * sizeof(Seg), hipMemcpyDeviceToHost, stream()));
+        ZV_HIP(hipStreamSynchronize(stream()));
+        Ld = 0;
+        for (const Seg &g : tab) Ld += g.rows;
+    }
+    const bool prepass = dec_prepass_on(bt);       // (see there)
 
     // D2: all ten AdaIN fc layers at once for every utterance's style vector            (src/stylettsdec.cpp:175-189)
     ZV_LAUNCH("dec_adain_fc", 4.0 * dec_.fc_out * (Ed + 2), 2.0 * S * dec_.fc_out * Ed,
@@ -56,7 +96,7 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
 
     auto finalize = [&](const double *part, int C, float *stat, int c_off) {
         ZV_LAUNCH("dec_in_stats", 16.0 * S * nblk * C, 4.0 * S * nblk * C,
-                  launch_stats_finalize(stream(), part, nblk, C, 1e-5f, stat, ss, c_off, fr, 1));
+                  launch_stats_finalize(stream(), part, nblk, C, 1e-5f, stat, ss, c_off, fr, 1, runs));
     };
     // make `j` read lrelu(norm(x)) with x's statistics still in `part` (channels [0, Cpart)); stores them in `stat`
     auto norm_input = [&](ConvJob &j, const float *x, int ldx, int C, const double *part, int Cpart, float *stat, const float *g,
@@ -64,7 +104,7 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
         if (prepass)
         {
             ZV_LAUNCH("dec_norm_operand", 6.0 * Ld * C, 8.0 * Ld * C,
-                      launch_norm_act_f16(stream(), x, ldx, C, part, nblk, Cpart, 1e-5f, stat, ss, g, b, gb_seg, 0.2f, op16, C, fr, raw16));
+                      launch_norm_act_f16(stream(), x, ldx, C, part, nblk, Cpart, 1e-5f, stat, ss, g, b, gb_seg, 0.2f, op16, C, fr, raw16, runs));
             j.x0 = op16;
             j.ldx = C;
             j.pro = PRO_RAW_F16;
@@ -228,12 +268,16 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
         ConvJob j = job(dec_.to_out);
         j.x0 = cur;
         j.ldx = ldc;
-        j.out = d_mel;
+        j.out = runs ? lay.mel_c : d_mel;
         j.ldo = dec_.M;
         if (dbg_layer.kind == ZV_LAYER_DEC_TO_OUT) dbg_inject(const_cast<float *>(cur), ldc, Ed, L);
         conv(&j, 1, fr, 1, "dec_conv", conv_bytes(Ld, Ed, dec_.M, 1, false), conv_flops(Ld, Ed, dec_.M, 1));
         if (dbg_layer.kind == ZV_LAYER_DEC_TO_OUT) dbg_extract(d_mel, dec_.M, dec_.M, L);
     }
+    // all T rows of every utterance's mel from the rows computed: the vocoder sees the mel it always saw
+    if (runs)
+        ZV_LAUNCH("dec_run_expand", 4.0 * (Ld + (double)L) * dec_.M, 0.0,
+                  launch_dec_run_expand(stream(), lay.mel_c, d_mel, dec_.M, fr, bt.frames_cap()));
 }
 
 }  // namespace zv

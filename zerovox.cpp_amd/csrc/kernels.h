@@ -267,8 +267,10 @@ hipError_t launch_out_conv(hipStream_t s, const OutConvArgs &a);
 //   part[((u * nblk) + blk) * C + c] = double2(sum, sumsq);  nblk >= ceil(max_rows * rate / 32)
 //   stat[u * stat_seg + 2 * (c_off + c) + {0, 1}] = mean, rstd
 hipError_t launch_stats_partial(hipStream_t s, const float *x, int ldx, int C, double *part, int nblk, const Segs &segs, int rate);
+// dec_runs (here and in launch_norm_act_f16): segs is a decoder run table (launch_dec_runs) — behind block seg.aux - 1 that block's
+// pair is added seg.pad more times and the sums are divided by rows + 32 * pad (dec_runs.h); rate must be 1
 hipError_t launch_stats_finalize(hipStream_t s, const double *part, int nblk, int C, float eps, float *stat, int stat_seg,
-                                 int c_off, const Segs &segs, int rate);
+                                 int c_off, const Segs &segs, int rate, int dec_runs = 0);
 // y[t][c] = ((x - mean) * rstd) * g[c] + b[c]; `part` (may be null) receives the partial sums of y
 hipError_t launch_norm_apply(hipStream_t s, const float *x, int ldx, int C, const float *stat, int stat_seg, const float *g,
                              const float *b, float *y, int ldy, double *part, int nblk, const Segs &segs);
@@ -282,7 +284,7 @@ hipError_t launch_act_f16(hipStream_t s, const float *x0, const float *x1, const
 // operand of the block's 1x1 shortcut conv (reference src/stylettsdec.cpp:132-140,287-296 converts x to f16 in its im2col).
 hipError_t launch_norm_act_f16(hipStream_t s, const float *x, int ldx, int C, const double *part, int nblk, int Cpart, float eps,
                                float *stat, int stat_seg, const float *ga, const float *be, int gb_seg, float slope, void *y,
-                               int ldy, const Segs &segs, void *yraw = nullptr);
+                               int ldy, const Segs &segs, void *yraw = nullptr, int dec_runs = 0);
 
 // ---- f32 linear layers: y[n][o] = dot(W[o][:], x[n][:]) + b[o] (ggml_mul_mat on f32 weights) --------
 // `extra` (may be null) is a second per-output addend applied after the bias: (acc + b[o]) + extra[o]
@@ -373,5 +375,17 @@ hipError_t launch_zero_tail(hipStream_t s, float *x, int C, const Segs &frames, 
 constexpr int VOC_RUN_MARGIN = 16;      // frames a run must save to be taken: below a row tile of the narrow stages nothing is saved
 hipError_t launch_voc_runs(hipStream_t s, const float *mel, int M, float *mel_c, int32_t *eq, Seg *runs, const Segs &frames, int H);
 hipError_t launch_voc_run_fill(hipStream_t s, float *x, const Segs &runs, int rate);
+
+// ---- run-shortened decoding (unfitted path, dec_runs.h): behind an utterance's n frames `hidden` is zero, so every tensor of the
+// decoder is constant over the rows [n + R, T - R) (R: the reach of its 3-tap convs) and the decoder runs over rows [0, a) ++ [b, T)
+// only, a and b multiples of the 32-row statistics block.  For every segment of `frames` (capacity T), from the regulator's counts:
+//   runs[u] = {row0, rows_c = a + (T - b), aux = a / 32, pad = G = (b - a) / 32}     taken (dec_run)
+//   runs[u] = {row0, T, 0, 0}                                                        otherwise
+// Every decoder launch takes its extents from this table; the statistics add the dropped blocks back (launch_stats_finalize).  No
+// host round trip: one graph replays for any lengths.
+hipError_t launch_dec_runs(hipStream_t s, const int32_t *n_frames, Seg *runs, const Segs &frames, int R);
+// mel[row0 + t][0 .. M) = mel_c[row0 + dec_run_compact_row(t)][0 .. M) for all T rows of every segment of `frames`: the compact
+// mel (the rows the decoder computed, in place at the segment's start) expanded to the capacity.  mel_c and mel must not overlap
+hipError_t launch_dec_run_expand(hipStream_t s, const float *mel_c, float *mel, int M, const Segs &runs, const Segs &frames);
 
 }  // namespace zv

@@ -27,6 +27,7 @@ namespace zv
     X(ZV_CONV_GEMM, 1)         /* 0 never, 1 batches, 2 always: conv_gemm_kernel for wide convs over an f16 operand tensor */         \
     X(ZV_CONV_STREAM, 1)       /* 0 never, 1 batches, 2 always: memory-bound 3-tap convs (the last upsample convs) on conv_stream_kernel */ \
     X(ZV_VOC_RUNS, 1)          /* 0 never, 1 batches, 2 always: the unfitted vocoder skips the repeats of a run of bit-identical mel rows (same bits) */ \
+    X(ZV_DEC_RUNS, 1)          /* 0 never, 1 batches, 2 always: the unfitted decoder computes a padded utterance's constant rows once (same bits) */ \
     X(ZV_UP_GEMM, 1)           /* 0 never, 1 batches, 2 always: the wide upsample convs behind an f16 operand pass on conv_gemm_kernel */ \
     X(ZV_GEMM_ORDER, 2)        /* conv_gemm_kernel's workgroup order: 0 plain (group fastest), 2 the 9-tile group first */ \
     X(ZV_PAIR_MT, 0)           /* 2 / 3 / 4: tile height of the pair kernels */                                                       \

@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "knobs.h"
 #include "fit_durations.h"
+#include "dec_runs.h"
 
 #include <cstring>
 
@@ -74,50 +75,48 @@ hipError_t launch_stats_partial(hipStream_t s, const float *x, int ldx, int C, d
     return hipGetLastError();
 }
 
-// (mean, rstd) of one channel of one segment from its blocks' partial sums, added in block order
-__device__ __forceinline__ float2 stats_from_partials(const double *__restrict__ p, int C, int nb, int L, float eps)
+// (mean, rstd) of one channel of one segment from its blocks' partial sums, added in block order.  A decoder run table's segment
+// (gap_at, G: dec_runs.h) stands for L rows, 32 G more than its nb blocks hold: the G blocks behind block gap_at - 1 were not
+// computed and hold that block's pair, added where they stood.  G = 0: the plain sum.
+__device__ __forceinline__ float2 stats_from_partials(const double *__restrict__ p, int C, int nb, int L, float eps, int gap_at = 0, int G = 0)
 {
-    double s1 = 0.0, s2 = 0.0;
-    for (int b0 = 0; b0 < nb; b0 += 8)          // eight loads in flight, added in block order
-    {
-        double2 v[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) v[i] = *(const double2 *)(p + (size_t)(b0 + i < nb ? b0 + i : nb - 1) * C * 2);
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            if (b0 + i < nb)
-            {
-                s1 += v[i].x;
-                s2 += v[i].y;
-            }
-    }
+    double s1, s2;
+    dec_run_block_sum(p, (size_t)C * 2, nb, gap_at, G, &s1, &s2);
     const double mean = s1 / (double)L;
     double var = s2 / (double)L - mean * mean;
     var = var > 0.0 ? var : 0.0;
     return make_float2((float)mean, 1.0f / sqrtf((float)var + eps));
 }
 
+// the gap of segment useg when segs is a decoder run table: (blocks in front of it, blocks dropped), else (0, 0)
+__device__ __forceinline__ int2 dec_run_gap(const Segs &segs, int useg, int dec_runs)
+{
+    if (!dec_runs || !segs.tab) return make_int2(0, 0);
+    return make_int2(__builtin_amdgcn_readfirstlane(segs.tab[useg].aux), __builtin_amdgcn_readfirstlane(segs.tab[useg].pad));
+}
+
 __global__ __launch_bounds__(64) void stats_finalize_kernel(const double *__restrict__ part, int nblk, int C, float eps,
                                                             float *__restrict__ stat, int stat_seg, int c_off,
-                                                            const Segs segs, int rate)
+                                                            const Segs segs, int rate, int dec_runs)
 {
     const int useg = blockIdx.y;
     const Seg sg = seg_at(segs, useg);
     const int L = sg.rows * rate;
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= C || L <= 0) return;
-    const float2 mr = stats_from_partials(part + ((size_t)useg * nblk * C + c) * 2, C, (L + 31) >> 5, L, eps);
+    const int2 gap = dec_run_gap(segs, useg, dec_runs);
+    const float2 mr = stats_from_partials(part + ((size_t)useg * nblk * C + c) * 2, C, (L + 31) >> 5, L + DEC_RUN_BLOCK * gap.y, eps, gap.x, gap.y);
     float *o = stat + (size_t)useg * stat_seg + 2 * (c_off + c);
     o[0] = mr.x;
     o[1] = mr.y;
 }
 
 hipError_t launch_stats_finalize(hipStream_t s, const double *part, int nblk, int C, float eps, float *stat, int stat_seg,
-                                 int c_off, const Segs &segs, int rate)
+                                 int c_off, const Segs &segs, int rate, int dec_runs)
 {
-    if (segs.nseg < 1) return hipErrorInvalidValue;
+    if (segs.nseg < 1 || (dec_runs && (!segs.tab || rate != 1))) return hipErrorInvalidValue;
     hipLaunchKernelGGL(stats_finalize_kernel, dim3((C + 63) / 64, segs.nseg), dim3(64), 0, s, part, nblk, C, eps, stat, stat_seg,
-                       c_off, segs, rate);
+                       c_off, segs, rate, dec_runs);
     return hipGetLastError();
 }
 
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(256) void norm_act_f16_kernel(const float *__restri
                                                            float *__restrict__ stat, int stat_seg,
                                                            const float *__restrict__ ga, const float *__restrict__ be, int gb_seg,
                                                            float slope, _Float16 *__restrict__ y, int ldy, _Float16 *__restrict__ yraw,
-                                                           const Segs segs)
+                                                           const Segs segs, int dec_runs)
 {
     __shared__ float sm[4][64];                  // mean, rstd, gamma, beta
     const int useg = blockIdx.y;
@@ -209,7 +208,8 @@ __global__ __launch_bounds__(256) void norm_act_f16_kernel(const float *__restri
             float *st = stat + (size_t)useg * stat_seg + 2 * c;
             if (c < Cpart)
             {
-                mr = stats_from_partials(part + ((size_t)useg * nblk * Cpart + c) * 2, Cpart, (L + 31) >> 5, L, eps);
+                const int2 gap = dec_run_gap(segs, useg, dec_runs);
+                mr = stats_from_partials(part + ((size_t)useg * nblk * Cpart + c) * 2, Cpart, (L + 31) >> 5, L + DEC_RUN_BLOCK * gap.y, eps, gap.x, gap.y);
                 st[0] = mr.x;
                 st[1] = mr.y;
             }
@@ -275,15 +275,15 @@ __global__ __launch_bounds__(256) void norm_act_f16_kernel(const float *__restri
 
 hipError_t launch_norm_act_f16(hipStream_t s, const float *x, int ldx, int C, const double *part, int nblk, int Cpart, float eps,
                                float *stat, int stat_seg, const float *ga, const float *be, int gb_seg, float slope, void *y,
-                               int ldy, const Segs &segs, void *yraw)
+                               int ldy, const Segs &segs, void *yraw, int dec_runs)
 {
-    if ((C & 3) || (ldx & 3) || (ldy & 3) || segs.nseg < 1 || Cpart > C) return hipErrorInvalidValue;
+    if ((C & 3) || (ldx & 3) || (ldy & 3) || segs.nseg < 1 || Cpart > C || (dec_runs && !segs.tab)) return hipErrorInvalidValue;
     if (Cpart > 0 && (segs.max_rows + 31) / 32 > nblk) return hipErrorInvalidValue;
     // (row chunks per segment: enough workgroups for about eight per CU, at most one per 128 rows)
     int gz = 1;
     while (gz < 8 && (long)((C + 63) / 64) * segs.nseg * gz < 2048 && gz * 128 < segs.max_rows) gz <<= 1;
     hipLaunchKernelGGL(norm_act_f16_kernel, dim3((C + 63) / 64, segs.nseg, gz), dim3(256), 0, s, x, ldx, C, part, nblk, Cpart, eps, stat,
-                       stat_seg, ga, be, gb_seg, slope, (_Float16 *)y, ldy, (_Float16 *)yraw, segs);
+                       stat_seg, ga, be, gb_seg, slope, (_Float16 *)y, ldy, (_Float16 *)yraw, segs, dec_runs);
     return hipGetLastError();
 }
 
@@ -1695,6 +1695,53 @@ hipError_t launch_voc_run_fill(hipStream_t s, float *x, const Segs &runs, int ra
     if (runs.nseg < 1 || runs.max_rows < 1 || rate < 1 || !runs.tab || !x) return hipErrorInvalidValue;
     const long per_seg = (long)runs.max_rows * rate;
     hipLaunchKernelGGL(voc_run_fill_kernel, dim3((unsigned)((per_seg + 1023) / 1024), runs.nseg), dim3(256), 0, s, x, runs.tab, rate);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Run-shortened decoding (kernels.h: launch_dec_runs, dec_runs.h).  The table: one thread per segment, from the regulator's counts.
+__global__ __launch_bounds__(64) void dec_runs_kernel(const int32_t *__restrict__ n_frames, Seg *__restrict__ runs, const Segs frames, int R)
+{
+    const int u = blockIdx.x * 64 + threadIdx.x;
+    if (u >= frames.nseg) return;
+    const Seg cap = frames.tab ? frames.tab[u] : frames.one;
+    const DecRun r = dec_run(n_frames[u], cap.rows, R);
+    *(int4 *)(runs + u) = make_int4(cap.row0, r.rows_c, r.gap_at, r.G);
+}
+
+hipError_t launch_dec_runs(hipStream_t s, const int32_t *n_frames, Seg *runs, const Segs &frames, int R)
+{
+    if (frames.nseg < 1 || !n_frames || !runs || R < 0 || (!frames.tab && frames.nseg != 1)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dec_runs_kernel, dim3((frames.nseg + 63) / 64), dim3(64), 0, s, n_frames, runs, frames, R);
+    return hipGetLastError();
+}
+
+// every row of a segment's capacity from the compact row that holds its value; grid.x walks the capacity in chunks of 1 024 elements
+__global__ __launch_bounds__(256) void dec_run_expand_kernel(const float *__restrict__ src, float *__restrict__ dst, int M,
+                                                             const Seg *__restrict__ runs, const Segs frames)
+{
+    const Seg cap = seg_at(frames, blockIdx.y);
+    const int4 e = *(const int4 *)(runs + blockIdx.y);
+    const int rows_c = __builtin_amdgcn_readfirstlane(e.y), gap_at = __builtin_amdgcn_readfirstlane(e.z), G = __builtin_amdgcn_readfirstlane(e.w);
+    const long n = (long)cap.rows * M;
+    const size_t base = (size_t)cap.row0 * M;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+    {
+        const long i = (long)blockIdx.x * 1024 + k * 256 + threadIdx.x;
+        if (i >= n) continue;
+        const int t = (int)(i / M), c = (int)(i - (long)t * M);
+        const int tc = dec_run_compact_row(t, gap_at, G);
+        if (tc < rows_c) dst[base + i] = src[base + (size_t)tc * M + c];
+    }
+}
+
+hipError_t launch_dec_run_expand(hipStream_t s, const float *mel_c, float *mel, int M, const Segs &runs, const Segs &frames)
+{
+    if (frames.nseg < 1 || frames.nseg != runs.nseg || frames.max_rows < 1 || M < 1 || !runs.tab || !mel_c || !mel) return hipErrorInvalidValue;
+    const long per_seg = (long)frames.max_rows * M;
+    hipLaunchKernelGGL(dec_run_expand_kernel, dim3((unsigned)((per_seg + 1023) / 1024), frames.nseg), dim3(256), 0, s, mel_c, mel, M,
+                       runs.tab, frames);
     return hipGetLastError();
 }
 

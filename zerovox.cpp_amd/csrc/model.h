@@ -81,6 +81,10 @@ struct Batch
     // grids and the regulator itself stay by capacity.  A single utterance has a one-entry table.  Keyed like d_ctl: a fitted and
     // an unfitted schedule are different graphs, and a fitted graph replays for new lengths.
     Seg *d_frm_live = nullptr;
+    // Run-shortened decoding (dec_runs.h, kernels.h launch_dec_runs): the decoder's run table, Seg [nseg] in HBM outside the arena, or
+    // null.  The encoder writes it behind the length regulator from the frame counts and the decoder takes every extent from it; the
+    // entry points set it where Model::dec_runs_on says so.  A single utterance has a one-entry table.  Keyed like d_frm_live.
+    Seg *d_dec_runs = nullptr;
     // Target durations (include/zerovox_amd.h "target durations"): some utterance's ctl row carries a target frame count, so the
     // encoder launches fit_durations_kernel ahead of the length regulator (d_ctl and d_pctl are then both set).  Keyed: one launch
     // more.  WHICH utterances have a target, and its value, is read at run time: a replay picks up new targets.
@@ -112,7 +116,8 @@ struct Batch
     {
         return nseg == o.nseg && n_max == o.n_max && t_max == o.t_max && n_rows == o.n_rows && t_rows == o.t_rows && d_tok == o.d_tok &&
                d_frm == o.d_frm && (d_tok || memcmp(&tok1, &o.tok1, sizeof(Seg)) == 0) && (d_frm || memcmp(&frm1, &o.frm1, sizeof(Seg)) == 0) &&
-               d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live && has_targets == o.has_targets;
+               d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live && has_targets == o.has_targets &&
+               d_dec_runs == o.d_dec_runs;
     }
 };
 
@@ -204,6 +209,13 @@ class Model
     bool voc_runs_off = false;
     bool voc_runs_on(const Batch &b) const;
     const Seg *voc_runs_last(int *n) { *n = lane().runs_n; return lane().runs_tab; }
+    // Run-shortened decoding of the unfitted synthesize paths (decoder.cpp): whether a chain over b gets a run table (Batch::d_dec_runs).
+    // Off in fitted mode, under a dbg_layer tap, where the operand pre-pass is off and by ZV_DEC_RUNS; never in a stand-alone decode,
+    // whose hidden comes from the caller
+    bool dec_runs_on(const Batch &b) const;
+    bool dec_prepass_on(const Batch &b) const;       // the decoder's convs read an f16 operand written by a pass of its own
+    // frames the decoder's 3-tap convs reach to either side, from the loaded layers (the longest path through its blocks)
+    int  dec_reach_frames() const;
     void sync();
 
     // Lanes: independent (stream, activation arena, I/O scratch) triples so that several utterances are in flight at
@@ -327,6 +339,7 @@ class Model
         int    nblk, hs, ss;        // per segment: statistics blocks, floats of AdaIN vectors, floats of (mean, rstd) pairs
         float *h, *st_x, *st_t, *st_y, *st_a, *cat, *t1, *sc, *x0, *xa, *asr_t;
         double *part_t, *part_o; _Float16 *xa16, *t16, *xr16;
+        float *mel_c;       // run-shortened decoding: the compact mel the last conv writes (launch_dec_run_expand reads it)
     };
     struct EncLayout { int Vp; float *x, *y, *qkv, *o, *f, *va, *vb; _Float16 *hh; EncoderTaps t; };
     VocLayout voc_layout(DeviceArena &a, const Batch &b) const;
