@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 D=/tmp/zvkprof
 rm -rf $D && mkdir -p $D
-rocprofv3 --kernel-trace --stats --output-format csv -d $D -- python "$@" > $D/out.txt 2>$D/err.txt || { tail -20 $D/err.txt; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D -- python "$@" > $D/out.txt 2>$D/err.txt || { tail -20 $D/err.txt; exit 1; }
 cat $D/out.txt
 python - <<'PY'
 import csv, glob, collections

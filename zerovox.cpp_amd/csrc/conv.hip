@@ -21,6 +21,7 @@
 //
 // Also here: conv_stream_kernel (the memory-bound upsample convs of a batch) and out_conv_tanh_kernel (the vocoder's
 // output conv).  The wide decoder convs of a batch run on conv_gemm_kernel (conv_gemm.hip), which launch_conv picks.
+#include "conv_xcd.h"
 #include "kernels.h"
 #include "knobs.h"
 #include "mfma_common.h"
@@ -52,6 +53,11 @@ static constexpr int CK_MAX = 256;
 #endif
 #ifndef ZV_STAGE_ULW
 #define ZV_STAGE_ULW 10
+#endif
+// a launch over several segments that passes the single-utterance form's workgroup count only as capacity, with more than a round of
+// workgroups, takes the ordinary form (0: it keeps the loader-wave form on the spread map of conv_xcd.h; see launch_conv_from)
+#ifndef ZV_CONV_BATCH_ROUTE
+#define ZV_CONV_BATCH_ROUTE 1
 #endif
 // waves per SIMD the 64 x 64 wave-tile instantiation of the generic conv kernel is compiled for (3: 168 registers)
 #ifndef ZV_NT2_OCC
@@ -690,15 +696,19 @@ __global__ __launch_bounds__(SINGLE ? 256 + 64 * ZV_SINGLE_LW : 256, (NT == 2 &&
     // hardware hands workgroup i to XCD i % 8): all row tiles of a channel group run on ONE XCD, whose L2 then holds that group's
     // weight fragments (a 1 056 x 1 056 x 3 conv's 6.7 MB do not fit one XCD's 4 MB; with row tiles dealt over the XCDs every XCD
     // streamed all of them from the memory side: scripts/frag_stream_bw.hip, 7-10 TB/s over the chip)
+    // A launch over several segments with fewer than 8 channel groups deals each group's row tiles over several XCDs instead (conv_xcd.h)
     int bx = blockIdx.x, by = blockIdx.y, ny = gridDim.y;
+    int warm_part = 0, warm_parts = 1;
     if constexpr (SINGLE)
         if (jobs.xcd_ny)
         {
-            const int q = blockIdx.x >> 3, g = q / jobs.xcd_nx;
-            by = (blockIdx.x & 7) + 8 * g;
-            bx = q - g * jobs.xcd_nx;
+            ConvXcdSlot slot;
+            if (!conv_xcd_slot(blockIdx.x, jobs.xcd_nx, jobs.xcd_ny, jobs.xcd_spread, slot)) return;
+            bx = slot.bx;
+            by = slot.by;
             ny = jobs.xcd_ny;
-            if (by >= ny) return;
+            warm_part = slot.part;
+            warm_parts = slot.nparts;
         }
 
     // workgroup -> (segment, row tile inside the segment)
@@ -731,7 +741,7 @@ __global__ __launch_bounds__(SINGLE ? 256 + 64 * ZV_SINGLE_LW : 256, (NT == 2 &&
     const int RS = J.ck * 2 + 16;            // LDS row stride in bytes
     if constexpr (SINGLE)
         if (jobs.xcd_ny && jobs.warm)
-            l2_warm((const char *)J.w + (size_t)gt0 * K * nicb * 1024, (size_t)(gt1 - gt0) * K * nicb * 1024, bx, jobs.xcd_nx, tid, 256 + 64 * LW);
+            l2_warm((const char *)J.w + (size_t)gt0 * K * nicb * 1024, (size_t)(gt1 - gt0) * K * nicb * 1024, warm_part, warm_parts, tid, 256 + 64 * LW);
 
     StageSrc S;
     {
@@ -1016,14 +1026,15 @@ static hipError_t launch_cfg(hipStream_t s, ConvJobs &jobs, int njobs, int Lmax,
 #endif
     // + dil rows: mfma_taps prefetches one tap past the end
     constexpr int LW = SINGLE ? ZV_SINGLE_LW : 0;
-    jobs.xcd_ny = 0;
+    jobs.xcd_ny = jobs.xcd_spread = 0;
     jobs.warm = knob(ZV_CONV_WARM) != 0;
     if (SINGLE && knob(ZV_CONV_XCD) != 0)
     {
-        // (see the kernel) grid.x = 8 XCDs x slots; slot q of XCD k = (channel group k + 8 (q / nx), row tile q % nx)
+        // (see the kernel and conv_xcd.h) grid.x = 8 XCDs x slots; several segments: no XCD idles for want of channel groups
         jobs.xcd_ny = grid.y;
         jobs.xcd_nx = grid.x;
-        grid = dim3(8 * grid.x * ((grid.y + 7) / 8), 1, njobs);
+        jobs.xcd_spread = jobs.segs.nseg > 1;
+        grid = dim3(conv_xcd_grid(jobs.xcd_nx, jobs.xcd_ny, jobs.xcd_spread), 1, njobs);
     }
     jobs.tile_bytes = round_up((BM + halo + dmax_) * (ck * 2 + 16), 16);
     const size_t lds = (size_t)jobs.tile_bytes * (LW > 0 ? 2 : 1);
@@ -1292,7 +1303,11 @@ static hipError_t launch_conv_from(hipStream_t s, const ConvJob *jobs, int njobs
         // ... of convs with SEVERAL such chunks (the decoder's): measured per launch at 512 frames, the one-chunk 256-channel
         // convs of HiFi-GAN stage 1 take 23.0 us on this loop against 20.0 us on mfma_taps (profiles/r02_v2_single_utterance_kernel_trace.txt
         // vs round 1's trace), the five-chunk decoder convs 29.6 against 33
-        if (knob(ZV_CONV_SINGLE) != 0 && MT == 1 && NT == 1 && ck == 256 && wgs(1, 1) <= 2L * n_cu &&
+        // ... and of launches the form was built for.  wgs() counts capacity, not utterances: a batch of 32 utterances x 256 phonemes
+        // has 512 workgroups of 8 waves for the first conv of a variance predictor, two rounds of a form whose loader waves leave
+        // room for one workgroup per CU.  Several segments and more than a round: the ordinary form (measured: DESIGN.md, "Narrow batch convs on all XCDs")
+        const bool batch_rounds = ZV_CONV_BATCH_ROUTE && segs.nseg > 1 && wgs(1, 1) > n_cu;
+        if (knob(ZV_CONV_SINGLE) != 0 && MT == 1 && NT == 1 && ck == 256 && wgs(1, 1) <= 2L * n_cu && !batch_rounds &&
             (jobs[0].Cin_p > 256 || knob(ZV_CONV_SINGLE) == 2))
         {
             if (WN == 4) return launch_cfg<1, 4, 1, true>(s, js, njobs, Lmax, Cout_p, halo, ck, dmax);
