@@ -410,12 +410,13 @@ typedef enum { ZV_LAYER_VOC_RESBLOCK = 0, ZV_LAYER_ENC_FFT = 1, ZV_LAYER_DEC_BLO
 zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint32_t rows, const float *style, float *out);
 
 /* ---- test / measurement switches (none is needed in production; no reference counterpart: the reference's only run-time
- * switch is the thread count, src/zerovox.cpp:86-91).  The shipped library never reads the environment: a switch changes only
- * through this call (the Python test binding forwards ZV_* environment variables through it so that a shell script can A/B a
- * run).  Schedule switches (ZV_NO_FUSE, ZV_NO_TRIPLE, ZV_FUSE256, ZV_NO_MERGE, ZV_TAIL_GROUPS) are sampled when a model is
- * loaded, kernel-regime switches at every launch; a captured hipGraph replays the regime it was captured in, so every call of
- * zv_debug_set makes the models capture anew.  name == NULL resets every switch to its built-in default.  ZV_ERR_ARG for an
- * unknown name.  The list: zerovox.cpp_amd/csrc/knobs.h (timing-only ablation switches that give wrong results exist only in
+ * switch is the thread count, src/zerovox.cpp:86-91).  The shipped library never reads the environment: a switch changes
+ * only through this call (the Python test binding forwards ZV_* environment variables through it so that a shell script can
+ * A/B a run).  Every switch is read at every call, where the schedule is decided: one set on a live model holds from its
+ * next call on (ZV_ARENA_FILL keeps its meaning, the byte a fresh arena gets when it is allocated: it reaches the arenas
+ * allocated after it is set); a captured hipGraph replays the regime it was captured in, so every call of zv_debug_set
+ * makes the models capture anew.  name == NULL resets every switch to its built-in default.  ZV_ERR_ARG for an unknown
+ * name.  The list: zerovox.cpp_amd/csrc/knobs.h (timing-only ablation switches that give wrong results exist only in
  * diagnostic builds, -DZV_DIAG).  zv_debug_get reads a switch. */
 zv_status zv_debug_set(const char *name, int value);
 zv_status zv_debug_get(const char *name, int *value);

@@ -81,7 +81,7 @@ def oracle_pair(o, fn, *args, **kw):
     return ref, alt
 
 
-# the kernels only batches pick by themselves, forced on for one utterance (some are sampled when a model is built: build it
+# the kernels only batches pick by themselves, forced on for one utterance (every switch is read at every call: make the calls
 # inside capi.switches(**BATCH_REGIME))
 BATCH_REGIME = dict(ZV_BLOCK64=-11, ZV_CONV_STREAM=2, ZV_CONV_GEMM=2, ZV_UP_GEMM=2, ZV_PAIR64_RING=2, ZV_TRIPLE_V2=3, ZV_FUSE256=1,
                     ZV_PAIR_MT=0, ZV_DEC_PREPASS=1)

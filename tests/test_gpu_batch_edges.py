@@ -1,7 +1,7 @@
 """-m gpu: ragged batches at the production geometry (synth.MEDIUM) against stand-alone calls, under every kernel regime.
 
 A batch is one launch per kernel over segment tables (one Seg per utterance + one spanning the batch, capi.cpp); the kernels that
-only batches select are chosen from the rows a launch covers, Lbatch = t_max x rate x nseg (vocoder.cpp, t_max = the longest T
+only batches select are chosen from the rows a launch covers, Lbatch = t_max x rate x nseg (voc_plan.h, t_max = the longest T
 rounded up to 64), with n_cu = 256.  Composition (a) has 18 utterances, T from 1 to 1 500 (t_max = 1 536), so:
   * conv_gemm_kernel for the two deep upsample convs (ZV_UP_GEMM): L = t_max x nseg = 27 648 >= 16 384 input rows;
   * resblock_block64_kernel (64 channels, rate 100): Lbatch / 244 = 11 331 >= 4 x 256;
@@ -19,7 +19,7 @@ Ts 1, 2, 11, 54, 55, 255, 256, 257, 1 024 and 1 500 sit next to each other in th
 one of N = max_seq_len + 1 = 1 501: scalar attention_kernel for the whole batch and the scan + gather regulator.  Composition (c)
 is (a) with a longest utterance of exactly N = 1 024: the last size of the fused regulator, scalar attention.
 Every utterance of every batch must equal its stand-alone zv_synthesize (default regime) bit for bit, waveform and frame count,
-in every regime (a fresh model under the switches: some are sampled at load): eager, graph capture + replay, and replay after a
+in every regime (a fresh model per regime, every call inside the regime's switches, which are read at the call): eager, graph capture + replay, and replay after a
 batch of other content with the same capacities (the utterances rotated by one)."""
 import numpy as np
 import pytest

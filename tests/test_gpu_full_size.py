@@ -139,9 +139,9 @@ def test_fused_256_channel_stage_vs_reference_golden(ckpt):
     z = np.load(os.path.join(GOLD, "medium_T512_N64.npz"))
     T, s = int(z["T"]), int(z["stride"])
     mel = synth.vocoder_mel(g, tensors, int(z["seed_mel"]), T)
-    with capi.switches(ZV_FUSE256=1):      # a schedule switch: sampled when the model is built
-        m = capi.Model(path, 0)
-    wav = m.vocode(mel)
+    m = capi.Model(path, 0)
+    with capi.switches(ZV_FUSE256=1):      # read at the call
+        wav = m.vocode(mel)
     m.close()
     err = _rms(wav[::s] - z["wav_samples"])
     print(f"fused 256-channel stage: wav rms err (strided vs reference) {err:.3e}")
@@ -214,11 +214,12 @@ def test_kernel_regimes_give_the_same_bits(ckpt):
     mel = synth.vocoder_mel(g, tensors, 51, 384)
     from parity_helpers import VOCODER_REGIMES
     outs = {}
+    m = capi.Model(path, 0)
     for name, env in VOCODER_REGIMES:
-        with capi.switches(**{k: int(v) for k, v in env.items()}):      # some switches are sampled when the model is built, some at every launch
-            m = capi.Model(path, 0)
+        m.poison()          # one model serves every regime (a switch is read at the call): no regime finds another's values in the lane
+        with capi.switches(**{k: int(v) for k, v in env.items()}):
             outs[name] = m.vocode(mel)
-            m.close()
+    m.close()
     for name, w in outs.items():
         assert np.array_equal(w, outs["default"]), name
 

@@ -24,7 +24,7 @@ def env(ckpt):
 
 
 def teardown_module(module):
-    for k in ("m", "mb"):
+    for k in ("m",):
         if k in _M:
             _M[k].close()
     _M.clear()
@@ -208,17 +208,8 @@ def test_every_adain_alone(env, idx):
 from parity_helpers import BATCH_REGIME  # noqa: E402
 
 
-def _batch_model(ckpt):
-    """a second model built with the regime on (ZV_FUSE256 is sampled when a model is loaded)"""
-    from zerovox_cpp_amd import capi
-    if "mb" not in _M:
-        with capi.switches(**BATCH_REGIME):
-            _M["mb"] = capi.Model(ckpt("medium")[0], 0)
-    return _M["mb"]
-
-
 @pytest.mark.parametrize("block", list(range(12)))
-def test_every_hifigan_residual_block_on_the_batch_kernels(env, ckpt, block):
+def test_every_hifigan_residual_block_on_the_batch_kernels(env, block):
     """resblock_pair_kernel<256> (fused, 96-row tiles) / <128> / resblock_pair64_kernel (LDS weight ring) + resblock_block64_kernel
     (two pairs per launch, every tap count) / resblock_block32_kernel on 512-row tiles, one residual block at a time vs the oracle;
     and the bits of the default kernels"""
@@ -228,9 +219,9 @@ def test_every_hifigan_residual_block_on_the_batch_kernels(env, ckpt, block):
     C, rate = m.voc_channels(stage), m.voc_rate(stage)
     x = (0.5 * np.random.default_rng(100 + block).standard_normal((32 * rate, C))).astype(np.float32)
     dflt = m.debug_layer(m.LAYER_VOC_RESBLOCK, block, x, C)
-    mb = _batch_model(ckpt)
+    m.poison()          # the same model in the other regime (every switch is read at the call): it must not find the default's values
     with capi.switches(**BATCH_REGIME):
-        got = mb.debug_layer(mb.LAYER_VOC_RESBLOCK, block, x, C)
+        got = m.debug_layer(m.LAYER_VOC_RESBLOCK, block, x, C)
     ref, alt = _oracle_pair(o, o.LAYER_VOC_RESBLOCK, block, x, C)
     _check(f"hifigan block {block} (C={C}) batch kernels", got, ref, alt, 2e-4)
     assert np.array_equal(got, dflt)

@@ -46,7 +46,7 @@ ZV_OK, ZV_ERR_ARG = 0, 5
 WAV_RMS_GATE = 1e-4                 # tests/test_gpu_full_size.py, tests/test_gpu_vocoder.py
 TMAX_MEDIUM = 32768
 T_STREAM = 40000                    # zv_vocode_stream "has no such limit on the total"
-N_CU = 256                          # compute units of an MI355X (vocoder.cpp compares workgroup counts with n_cu)
+N_CU = 256                          # compute units of an MI355X (voc_plan.h compares workgroup counts with n_cu)
 THRESHOLD_LENGTHS = (2498, 2499, 3276, 3277, 16383, 16384, TMAX_MEDIUM - 1, TMAX_MEDIUM)
 
 
@@ -146,7 +146,7 @@ def _vocoder_regimes():
 
 @pytest.mark.parametrize("regime", _vocoder_regimes(), ids=lambda r: r[0])
 def test_vocoder_at_tmax_in_every_kernel_regime(env, regime):
-    """a fresh model under the switches (some are sampled at load): the default's bits"""
+    """a fresh model per regime, its call inside the regime's switches (read at the call): the default's bits"""
     from zerovox_cpp_amd import capi
     name, sw = regime
     with capi.switches(**sw):
@@ -160,7 +160,7 @@ def test_vocoder_at_tmax_in_every_kernel_regime(env, regime):
 
 
 def test_threshold_lengths_are_the_ones_the_schedule_switches_at():
-    """vocoder.cpp for one utterance (t_max = T, nseg = 1): resblock_block64_kernel when T x 100 / 244 >= 4 n_cu (integer
+    """csrc/voc_plan.h for one utterance (t_max = T, nseg = 1; tests/test_voc_plan_cpu.py asks the header itself): resblock_block64_kernel when T x 100 / 244 >= 4 n_cu (integer
     division), the f16 operand pass + conv_gemm_kernel for upsample conv i when its input rows T x rate >= 16 384 (i = 1: rate 5,
     i = 0: rate 1)"""
     first = lambda cond: next(T for T in range(1, TMAX_MEDIUM + 1) if cond(T))

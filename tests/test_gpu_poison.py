@@ -48,15 +48,15 @@ def ref(ckpt):
 
 @pytest.fixture(scope="module")
 def under_test(ckpt):
-    """name -> the model under test of that regime (built under the regime's switches: some are sampled when a model is built)"""
+    """name -> the model under test of that regime: a model of its own per regime (and per `extra`), so that no regime finds another's
+    buffers.  Every switch is read at the call: the tests make their calls inside capi.switches(**REGIMES[name], **extra)"""
     from zerovox_cpp_amd import capi
     path, _, _ = ckpt("medium")
 
     def get(name, **extra):
         key = (name,) + tuple(sorted(extra.items()))
         if key not in _M:
-            with capi.switches(**REGIMES[name], **extra):
-                _M[key] = capi.Model(path, 0)
+            _M[key] = capi.Model(path, 0)
         _M[key].set_graph_mode(False)
         return _M[key]
 
@@ -345,24 +345,25 @@ def test_tail_groups(ref, under_test, groups, fitted):
             assert t.shape[0] == 0 if fitted else (t.shape == (len(utts), 4) and int((t[:, 3] > 0).sum()) >= 8), (what, t.tolist())
         return f
 
-    bc = m.prepare_batch(utts, fitted=fitted)
-    _poisoned(m, lambda: _batch_call(bc), check(0), need, what=(groups, fitted, "lane 0"))
-    # two batches in flight on lanes 0 and 1, each lane poisoned while it is idle (the other one is not), before its begin
-    calls = [m.prepare_batch(utts, fitted=fitted) for _ in range(2)]
-    for k in range(4):
-        lane = k % 2
-        if k >= 2:
+    with capi.switches(ZV_TAIL_GROUPS=groups):       # read when a batch is enqueued: every batch call of the test sits in here
+        bc = m.prepare_batch(utts, fitted=fitted)
+        _poisoned(m, lambda: _batch_call(bc), check(0), need, what=(groups, fitted, "lane 0"))
+        # two batches in flight on lanes 0 and 1, each lane poisoned while it is idle (the other one is not), before its begin
+        calls = [m.prepare_batch(utts, fitted=fitted) for _ in range(2)]
+        for k in range(4):
+            lane = k % 2
+            if k >= 2:
+                calls[lane].end(lane)
+                check(lane)(calls[lane].results(), (groups, fitted, "in flight", k - 2))
+                assert all(f >= n for f, n in zip(m.poison(FILLS[k % 2 ^ 1], lane), need)), (groups, fitted, k)
+            else:
+                m.poison(FILLS[k], lane)
+            for w in calls[lane].wavs:
+                w[:] = np.nan
+            calls[lane].begin(lane)
+        for lane in (0, 1):
             calls[lane].end(lane)
-            check(lane)(calls[lane].results(), (groups, fitted, "in flight", k - 2))
-            assert all(f >= n for f, n in zip(m.poison(FILLS[k % 2 ^ 1], lane), need)), (groups, fitted, k)
-        else:
-            m.poison(FILLS[k], lane)
-        for w in calls[lane].wavs:
-            w[:] = np.nan
-        calls[lane].begin(lane)
-    for lane in (0, 1):
-        calls[lane].end(lane)
-        check(lane)(calls[lane].results(), (groups, fitted, "in flight", 2 + lane))
+            check(lane)(calls[lane].results(), (groups, fitted, "in flight", 2 + lane))
 
 
 # ---- 5. the hook's own contract -------------------------------------------------------------------------------------------------

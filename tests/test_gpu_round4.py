@@ -153,6 +153,46 @@ def test_a_switch_change_recaptures_graphs(models):
         model.device_free(d_wav)
 
 
+# launches of voc_resblock_s0 .. s3 for one utterance of 16 frames (medium geometry), as the library reported them for a model LOADED
+# under the switches while five of them were still sampled by the loader
+SCHEDULE_SWITCH_LAUNCHES = (
+    ({}, (6, 3, 3, 1)),
+    ({"ZV_NO_FUSE": 1}, (6, 6, 6, 6)),
+    ({"ZV_NO_TRIPLE": 1}, (6, 3, 3, 3)),
+    ({"ZV_FUSE256": 1}, (3, 3, 3, 1)),
+    ({"ZV_NO_MERGE": 1}, (6, 3, 3, 1)),
+    ({"ZV_FUSE256": 1, "ZV_MERGE_ALWAYS": 1}, (5, 3, 3, 1)),
+    ({"ZV_FUSE256": 1, "ZV_MERGE_ALWAYS": 1, "ZV_NO_MERGE": 1}, (3, 3, 3, 1)),
+)
+
+
+def test_schedule_switches_hold_on_a_live_model(models):
+    """every switch is read at the call: ZV_NO_FUSE, ZV_NO_TRIPLE, ZV_FUSE256 and ZV_NO_MERGE set after the model exists give the
+    launch counts of a model loaded under them, the default's counts come back when the block ends, and the bits never change
+    (ZV_TAIL_GROUPS has no such observable, a profile turns the groups off: tests/test_voc_plan_cpu.py, test_gpu_poison.py)"""
+    from zerovox_cpp_amd import capi, synth
+    model, g, tensors = models("medium")
+    mel = synth.vocoder_mel(g, tensors, 93, 16)
+    model.set_graph_mode(False)
+
+    def run():
+        model.profile_begin()
+        wav = model.vocode(mel)
+        prof = {s["name"]: s["launches"] for s in model.profile_end()}
+        return wav, tuple(prof["voc_resblock_s%d" % i] for i in range(4))
+
+    ref, dflt = run()
+    assert dflt == SCHEDULE_SWITCH_LAUNCHES[0][1]
+    for sw, want in SCHEDULE_SWITCH_LAUNCHES[1:]:
+        with capi.switches(**sw):
+            wav, counts = run()
+        print(sw, counts)
+        assert counts == want, (sw, counts, want)
+        assert np.array_equal(wav, ref), sw
+        wav, counts = run()
+        assert counts == dflt and np.array_equal(wav, ref), (sw, "after the block", counts)
+
+
 def test_fused_tails_and_one_launch_regulator_give_the_same_bits(ckpt):
     """round 4's launch savers for short utterances — LayerNorm launches that also do the style add / the predictor's linear
     layer / the bucket + embedding step, scan + gather of the length regulator in one launch — change which launch does an

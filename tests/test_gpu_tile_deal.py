@@ -143,5 +143,5 @@ def test_fewer_than_eight_tiles_per_segment_at_256_channels(env):
     for K in (3, 7, 11):
         assert -(-T * rate // (128 - (K - 1))) < 8
     n_cu = 256
-    assert (T * rate * 9 // 54) * 3 >= n_cu                   # vocoder.cpp: enough_rows
+    assert (T * rate * 9 // 54) * 3 >= n_cu                   # voc_plan.h: enough_rows
     _check(m, g, 9, T, dict(ZV_PAIR_MT=4), ("tps < 8", 9, T))

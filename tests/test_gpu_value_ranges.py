@@ -37,16 +37,8 @@ def env(ckpt):
     yield _M["m"], _M["g"], _M["t"], _M["o"]
 
 
-def _batch_model(ckpt):
-    from zerovox_cpp_amd import capi
-    if "mb" not in _M:
-        with capi.switches(**ph.BATCH_REGIME):
-            _M["mb"] = capi.Model(ckpt("medium")[0], 0)
-    return _M["mb"]
-
-
 def teardown_module(module):
-    for k in ("m", "mb", "mw"):
+    for k in ("m", "mw"):
         if k in _M:
             _M[k].close()
     _M.clear()
@@ -58,23 +50,25 @@ def _pad_rows(x, mult):
     return np.concatenate([x, np.zeros((extra, x.shape[1]), np.float32)]) if extra else x
 
 
-def _run_both(m, mb, *args, **kw):
-    """the default kernels and the batch kernels on one input; their bits must be equal"""
+def _run_both(m, *args, **kw):
+    """the default kernels and the batch kernels on one input (one model: every switch is read at the call; its lane is poisoned in
+    between, so that the second run cannot find the first one's values); their bits must be equal"""
     from zerovox_cpp_amd import capi
     got = m.debug_layer(*args, **kw)
+    m.poison()
     with capi.switches(**ph.BATCH_REGIME):
-        gb = mb.debug_layer(*args, **kw)
+        gb = m.debug_layer(*args, **kw)
     assert np.array_equal(got, gb) and np.array_equal(np.signbit(got), np.signbit(gb)), "batch kernels"
     return got, gb
 
 
-def _banded_case(name, m, mb, o, kind, idx, x, regions, out_cols, rel_gate, **kw):
-    got, _ = _run_both(m, mb, kind, idx, x, out_cols, **kw)
+def _banded_case(name, m, o, kind, idx, x, regions, out_cols, rel_gate, **kw):
+    got, _ = _run_both(m, kind, idx, x, out_cols, **kw)
     ref, alt, hi = ph.oracle_triple(o, "layer", kind, idx, x, out_cols, **kw)
     ph.region_gates(name, got, ref, alt, hi, regions, rel_gate)
     # the response to the input, with the bias's share cancelled on both sides
     x0 = np.zeros_like(x)
-    g0, _ = _run_both(m, mb, kind, idx, x0, out_cols, **kw)
+    g0, _ = _run_both(m, kind, idx, x0, out_cols, **kw)
     r0, a0 = ph.oracle_pair(o, "layer", kind, idx, x0, out_cols, **kw)
     # (below 2^-16 a residual block's response is made of f16 re-roundings of its bias-level operands: its floor, not a fixed
     # fraction, is the gate there; the error must stay below the response itself)
@@ -82,15 +76,16 @@ def _banded_case(name, m, mb, o, kind, idx, x, regions, out_cols, rel_gate, **kw
                     resolution=np.spacing(np.abs(ref)) + np.spacing(np.abs(r0)))
 
 
-def _crossing_case(name, m, mb, o, kind, idx, x, regions, out_cols, rel_gate, **kw):
+def _crossing_case(name, m, o, kind, idx, x, regions, out_cols, rel_gate, **kw):
     rows = kw.get("out_rows", x.shape[0])
     clean = np.zeros(rows, bool)
     for _, sl in regions:
         clean[sl] = True
     from zerovox_cpp_amd import capi
     got = m.debug_layer(kind, idx, x, out_cols, **kw)
+    m.poison()
     with capi.switches(**ph.BATCH_REGIME):
-        gb = mb.debug_layer(kind, idx, x, out_cols, **kw)
+        gb = m.debug_layer(kind, idx, x, out_cols, **kw)
     ref, alt, hi = ph.oracle_triple(o, "layer", kind, idx, x, out_cols, **kw)
     assert not np.isfinite(ref).all(), "the crossing inputs did not reach inf"
     ph.nonfinite_masks_equal(name + " (oracle orders)", alt, ref)
@@ -103,34 +98,32 @@ def _crossing_case(name, m, mb, o, kind, idx, x, regions, out_cols, rel_gate, **
 
 
 @pytest.mark.parametrize("block", RES_BLOCKS)
-def test_residual_block_value_ranges(env, ckpt, block):
+def test_residual_block_value_ranges(env, block):
     """banded (per band + response), sparse, near-saturation and inf-crossing inputs through one residual block, default and
     batch kernels"""
     m, g, t, o = env
-    mb = _batch_model(ckpt)
     stage, k = block // 3, g.resblock_kernels[block % 3]
     C, rate = m.voc_channels(stage), m.voc_rate(stage)
     halo = ph.resblock_halo(k, g.resblock_dilations)
     K = m.LAYER_VOC_RESBLOCK
     name = f"resblock {block} (C={C}, k={k})"
     x, reg = ph.banded(1000 + block, C, halo)
-    _banded_case(name + " banded", m, mb, o, K, block, _pad_rows(x, rate), reg, C, 1e-3)
+    _banded_case(name + " banded", m, o, K, block, _pad_rows(x, rate), reg, C, 1e-3)
     for fam, (x, reg) in (("sparse", ph.sparse(1100 + block, 32 * rate, C)),
                           ("near-saturation", ph.near_saturation(1200 + block, 32 * rate, C))):
-        got, _ = _run_both(m, mb, K, block, x, C)
+        got, _ = _run_both(m, K, block, x, C)
         ref, alt, hi = ph.oracle_triple(o, "layer", K, block, x, C)
         assert np.isfinite(ref).all(), f"{fam}: the oracle's output is not finite"
         if fam == "near-saturation":
             print(f"   largest f16 operand {np.max(np.abs(x)):.0f}, largest output {np.max(np.abs(ref)):.0f}")
         ph.region_gates(f"{name} {fam}", got, ref, alt, hi, reg, 2e-4)
     x, reg = ph.crossing(1300 + block, C, halo, ph.resblock_cross_margin(g.resblock_dilations))
-    _crossing_case(name + " crossing", m, mb, o, K, block, _pad_rows(x, rate), reg, C, 2e-4)
+    _crossing_case(name + " crossing", m, o, K, block, _pad_rows(x, rate), reg, C, 2e-4)
 
 
 @pytest.mark.parametrize("idx", UPSAMPLES)
-def test_transposed_conv_value_ranges(env, ckpt, idx):
+def test_transposed_conv_value_ranges(env, idx):
     m, g, t, o = env
-    mb = m      # the upsample kernels are chosen at every launch: BATCH_REGIME on the default model
     cin = g.voc_channels >> idx
     cout, s = cin // 2, g.upsample_scales[idx]
     rate_in = 1 if idx == 0 else m.voc_rate(idx - 1)
@@ -139,14 +132,14 @@ def test_transposed_conv_value_ranges(env, ckpt, idx):
     name = f"conv_transpose1d {idx} ({cin}->{cout})"
     x, reg = ph.banded(1400 + idx, cin, halo, out_rate=s)
     x = _pad_rows(x, rate_in)
-    _banded_case(name + " banded", m, mb, o, K, idx, x, reg, cout, 1e-3, out_rows=x.shape[0] * s)
+    _banded_case(name + " banded", m, o, K, idx, x, reg, cout, 1e-3, out_rows=x.shape[0] * s)
     x, reg = ph.sparse(1500 + idx, 48 * rate_in, cin)
-    got, _ = _run_both(m, mb, K, idx, x, cout, out_rows=x.shape[0] * s)
+    got, _ = _run_both(m, K, idx, x, cout, out_rows=x.shape[0] * s)
     ref, alt, hi = ph.oracle_triple(o, "layer", K, idx, x, cout, out_rows=x.shape[0] * s)
     ph.region_gates(name + " sparse", got, ref, alt, hi, reg, 1e-4)
     x, reg = ph.crossing(1600 + idx, cin, halo, 0, out_rate=s)
     x = _pad_rows(x, rate_in)
-    _crossing_case(name + " crossing", m, mb, o, K, idx, x, reg, cout, 1e-4, out_rows=x.shape[0] * s)
+    _crossing_case(name + " crossing", m, o, K, idx, x, reg, cout, 1e-4, out_rows=x.shape[0] * s)
 
 
 def test_vocoder_input_conv_mel_offsets(env):

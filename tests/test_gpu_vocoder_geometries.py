@@ -11,9 +11,10 @@ so does the loader, which packs fused weights per pair where both convs share a 
   * medium_rb_c1c2: convs1 / convs2 of 7 / 3 and 11 / 13 taps in one pair (never fused), a convs2 wider than every convs1;
   * medium_rb_c2wide: every convs2 of the 11-tap branch has 25 taps (never fused): a receptive radius of 25 frames, which a halo
     that left out convs2 (23) would not cover.
-Not reached by any geometry: vocoder.cpp's one-K guard on the block64 path (two pairs of different K at dilations 0 and 1 of a
-64-channel branch).  A checkpoint that reaches it safely on a library without the guard would need dilation 1 wider than
-dilation 0 in every stage, with the 32-channel whole-block kernel kept off.
+Not reached by any geometry: the one-K guard on the block64 path (two pairs of different K at dilations 0 and 1 of a 64-channel
+branch).  A checkpoint that reaches it safely on a library without the guard would need dilation 1 wider than dilation 0 in every
+stage, with the 32-channel whole-block kernel kept off; the guard is plain host arithmetic (csrc/voc_plan.h) and
+tests/test_voc_plan_cpu.py checks it there.
 Checked: every residual block alone against the oracle (default and batch kernels, same bits), the whole vocoder against the
 oracle, every kernel regime's bits, the halo against the exact receptive radius with bit-exact streaming, and ragged batches
 (eager, graph capture, replay) against stand-alone calls.  Also: the loader refuses what the reference would run differently."""
@@ -23,7 +24,6 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 WAV_RMS_GATE = 1e-4                 # tests/test_gpu_vocoder.py
-BUILD_SWITCHES = ("ZV_NO_FUSE", "ZV_NO_TRIPLE", "ZV_FUSE256", "ZV_NO_MERGE", "ZV_TAIL_GROUPS")     # sampled by Model() (model_load.cpp)
 ZV_ERR_SHAPE = 4
 
 
@@ -35,19 +35,16 @@ def _geoms():
 _M = {}
 
 
-def _model(ckpt, gname, env=None):
-    """one model per (geometry, schedule switches sampled at load); env's other switches are read at every launch"""
+def _model(ckpt, gname):
+    """one model per geometry: it serves every regime (every switch is read at the call)"""
     from zerovox_cpp_amd import capi
-    env = env or {}
-    key = (gname, tuple(sorted((k, int(v)) for k, v in env.items() if k in BUILD_SWITCHES)))
-    if key not in _M:
-        with capi.switches(**env):
-            _M[key] = capi.Model(ckpt(gname)[0], 0)
-    return _M[key]
+    if gname not in _M:
+        _M[gname] = capi.Model(ckpt(gname)[0], 0)
+    return _M[gname]
 
 
-def _close(gname=None, keep_default=False):
-    for k in [k for k in _M if (gname is None or k[0] == gname) and not (keep_default and k[1] == ())]:
+def _close(gname=None):
+    for k in [k for k in _M if gname is None or k == gname]:
         _M.pop(k).close()
 
 
@@ -61,23 +58,23 @@ def _rms(a):
 
 @pytest.mark.parametrize("gname", _geoms())
 def test_every_residual_block(ckpt, gname):
-    """all 12 residual blocks through zv_debug_layer against the oracle (32 frames at the stage's rate), on the default model and on
-    one built under BATCH_REGIME (resblock_pair<256> on 96-row tiles, pair64's weight ring, block64 at every tap count, the
-    whole-block kernel's 512-row tiles), which must give the default's bits"""
+    """all 12 residual blocks through zv_debug_layer against the oracle (32 frames at the stage's rate), under the default switches and
+    once more, the lane poisoned in between, under BATCH_REGIME (resblock_pair<256> on 96-row tiles, pair64's weight ring, block64
+    at every tap count, the whole-block kernel's 512-row tiles), which must give the default's bits"""
     from zerovox_cpp_amd import capi
     from oracle import zvoracle
     from parity_helpers import BATCH_REGIME, layer_gate, oracle_pair
     _, g, tensors = ckpt(gname)
     m = _model(ckpt, gname)
-    mb = _model(ckpt, gname, BATCH_REGIME)
     o = zvoracle.Oracle(tensors)
     for block in range(12):
         stage = block // 3
         C, rate = m.voc_channels(stage), m.voc_rate(stage)
         x = (0.5 * np.random.default_rng(100 + block).standard_normal((32 * rate, C))).astype(np.float32)
         got = m.debug_layer(m.LAYER_VOC_RESBLOCK, block, x, C)
+        m.poison()
         with capi.switches(**BATCH_REGIME):
-            gotb = mb.debug_layer(mb.LAYER_VOC_RESBLOCK, block, x, C)
+            gotb = m.debug_layer(m.LAYER_VOC_RESBLOCK, block, x, C)
         ref, alt = oracle_pair(o, "layer", o.LAYER_VOC_RESBLOCK, block, x, C)
         ks = [(g.resblock_k(block % 3, d, 1), g.resblock_k(block % 3, d, 2)) for d in range(3)]
         layer_gate(f"{gname} block {block} (C={C}, K={ks})", got, ref, alt, 2e-4)
@@ -110,19 +107,19 @@ def _regimes():
 @pytest.mark.parametrize("gname", _geoms())
 def test_kernel_regimes_give_the_same_bits(ckpt, gname):
     """every entry of VOCODER_REGIMES and ZV_BLOCK64 = 0 / -3 / -11 at 384 frames: the default's bits (as
-    tests/test_gpu_full_size.py::test_kernel_regimes_give_the_same_bits).  One model per set of the switches sampled at load
-    (BUILD_SWITCHES), the others set around each call: a stage with an unfusable pair runs unfused in every regime, a branch whose
-    K changes over its dilations never runs on the whole-block / block64 kernels"""
+    tests/test_gpu_full_size.py::test_kernel_regimes_give_the_same_bits).  One model, the switches set around each call and the lane
+    poisoned before it: a stage with an unfusable pair runs unfused in every regime, a branch whose K changes over its dilations
+    never runs on the whole-block / block64 kernels"""
     from zerovox_cpp_amd import capi, synth
     _, g, tensors = ckpt(gname)
     mel = synth.vocoder_mel(g, tensors, 51, 384)
-    want = _model(ckpt, gname).vocode(mel)
+    m = _model(ckpt, gname)
+    want = m.vocode(mel)
     for name, env in _regimes():
-        m = _model(ckpt, gname, env)
+        m.poison()
         with capi.switches(**{k: int(v) for k, v in env.items()}):
             got = m.vocode(mel)
         assert np.array_equal(got, want), (gname, name)
-    _close(gname, keep_default=True)
 
 
 @pytest.mark.parametrize("gname", _geoms())

@@ -4,7 +4,8 @@ that put each kernel's row count on both sides of its tile heights, every length
 Vocoder stages: 256 / 128 / 64 / 32 channels at 5 / 25 / 100 / 300 rows per mel frame (rows = T x rate).  Output rows per
 tile (TM = rows a workgroup stores, from the launch_* functions of conv1d_mfma.hip; K = 3 / 7 / 11 taps, Kmax = 11 sizes the grid):
   * resblock_pair_kernel<256>: BM = 32 MT (4 / 4) rows less K - 1 halo rows -> 62 / 58 / 54 (MT = 2, ZV_FUSE256 or
-    T >= 929 by itself: enough_rows, vocoder.cpp, floor(5 T / 54) x 3 >= 256 CUs) and 94 / 90 / 86 (the batches' 96-row tiles, MT = 3);
+    T >= 929 by itself: enough_rows of csrc/voc_plan.h, both sides checked on the host by tests/test_voc_plan_cpu.py) and
+    94 / 90 / 86 (the batches' 96-row tiles, MT = 3);
   * resblock_pair_kernel<128>: 62 / 58 / 54 (MT = 2) and 126 / 122 / 118 (MT = 4; the merged MRF sum's 118-row tile);
   * resblock_pair_kernel<64>: 126 / 122 / 118; resblock_pair64_kernel (LDS weight ring): 257 - K = 254 / 250 / 246 (the merged
     sum's 246-row tile); resblock_block64_kernel (two dilation pairs, dil 1 and 3): 256 - 2 h (1 + 3 + 2) = 244 at K = 3;
@@ -15,8 +16,9 @@ stage 3: one 512-row tile or two), 9 10 (stage 1 around two 118-row tiles), 10 .
 (around 86 / 90 / 94), 21 22 (around two 54-row tiles), and 928 / 929 (either side of the fused-256 threshold; 4 640 rows:
 many tiles at every stage).  ~2 000 frames in all.
 Per length: the waveform against the oracle (WAV_RMS_GATE and three times the oracle's own re-association noise: ggml AVX2
-order vs sequential f32); the same bits from models built under the batch regime (parity_helpers.BATCH_REGIME), with the 96-row
-pair<256> tiles (ZV_PAIR_MT = 3) and with the merged MRF sum (ZV_MERGE_ALWAYS); and the prefix property (the first T frames of
+order vs sequential f32); the same bits from calls under the batch regime (parity_helpers.BATCH_REGIME), with the 96-row
+pair<256> tiles (ZV_PAIR_MT = 3) and with the merged MRF sum (ZV_MERGE_ALWAYS), on the same model with its lane poisoned before
+each (every switch is read at the call); and the prefix property (the first T frames of
 vocode(mel[:T + H]) are those of the long utterance).
 
 Decoder at T = 255 / 256 / 257 / 513: the operand pre-pass threshold (t_max x nseg >= 256, decoder.cpp) and conv_gemm_kernel's
@@ -43,13 +45,8 @@ def test_medium_vocoder_length_sweep_vs_oracle(ckpt):
     path, g, tensors = ckpt("medium")
     regimes = (("batch", BATCH_REGIME), ("batch_pair256_96_rows", dict(BATCH_REGIME, ZV_PAIR_MT=3)),
                ("batch_merged_sum", dict(BATCH_REGIME, ZV_MERGE_ALWAYS=1)))
-    models = {}
+    m = capi.Model(path, 0)
     try:
-        models["default"] = capi.Model(path, 0)
-        for name, sw in regimes:
-            with capi.switches(**sw):               # some of these switches are sampled when the model is built
-                models[name] = capi.Model(path, 0)
-        m = models["default"]
         orc = zvoracle.Oracle(tensors)
         H = m.vocoder_halo_frames()
         mel = synth.vocoder_mel(g, tensors, 19, max(LENGTHS) + H + 8)
@@ -64,13 +61,13 @@ def test_medium_vocoder_length_sweep_vs_oracle(ckpt):
             assert err <= WAV_RMS_GATE, T
             assert err <= max(3.0 * floor, 3e-7 * sig), T
             for name, sw in regimes:
+                m.poison()          # no regime finds another's values in the lane
                 with capi.switches(**sw):
-                    assert np.array_equal(models[name].vocode(mel[:T]), wav), (name, T)
+                    assert np.array_equal(m.vocode(mel[:T]), wav), (name, T)
             ctx = m.vocode(mel[: T + H])
             assert np.array_equal(ctx[: T * hop], full[: T * hop]), T
     finally:
-        for mm in models.values():
-            mm.close()
+        m.close()
 
 
 def test_medium_decoder_pre_pass_and_gemm_tile_edges_vs_oracle(ckpt):

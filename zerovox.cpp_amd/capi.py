@@ -294,8 +294,9 @@ def debug_get(name: str) -> int:
 
 
 class switches:
-    """`with capi.switches(ZV_NO_FUSE=1, ...):` — the switches hold inside the block (schedule switches are sampled by
-    Model(), kernel-regime switches at every launch; captured graphs are re-captured) and go back to the values they had
+    """`with capi.switches(ZV_NO_FUSE=1, ...):` — the switches hold inside the block (every one is read at every
+    call, so a call runs in a regime exactly when it sits inside the block, whenever its model was built; captured graphs are
+    re-captured) and go back to the values they had
     before it afterwards (not to their built-in defaults: a value set for the whole run, e.g. ZV_ARENA_FILL=255, survives,
     and blocks nest)"""
 

@@ -718,10 +718,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
     // run.  Same kernels on the same rows: same bits.
-    // (as many groups as the switch asks for, of at least two utterances each: a group of one utterance leaves the whole-block
-    // kernel two rounds of workgroups — measured 21.4 / 21.1 / 21.1 / 22.7 ms per batch with 4 / 8 / 16 / 32 groups of 32 utterances)
-    const int G = (M.tail_groups() > 1 && bt.nseg >= 4 && wav_bytes >= ((size_t)16 << 20) && !M.profiling && M.dbg_layer.kind < 0)
-                      ? std::min(M.tail_groups(), (int)bt.nseg / 2) : 1;
+    const int G = zv::voc_tail_groups(zv::knob(zv::ZV_TAIL_GROUPS), bt.nseg, wav_bytes, M.profiling, M.dbg_layer.kind >= 0);
     // from here on work is queued that reads the lane's pinned input block and writes its I/O block: if anything fails the
     // lane's streams are drained before the error leaves, so an idle-looking lane never has work in flight
     try

@@ -1107,15 +1107,6 @@ __global__ __launch_bounds__(256, 2) void resblock_block64_kernel(const TripleJo
                 }
 }
 
-// the blocks resblock_block64_kernel takes: 64 channels, few taps (the halo of n_dil pairs leaves most of the 256-row tile)
-bool block64_supported(int Cp, int K, const int *dil, int n_dil)
-{
-    if (Cp != 64 || K < 3 || (K & 1) == 0 || n_dil < 1 || n_dil > TRIPLE_MAX_DIL) return false;
-    int sumd = 0;
-    for (int d = 0; d < n_dil; d++) sumd += dil[d];
-    return 256 - (K - 1) * (sumd + n_dil) >= 192;          // at least three quarters of the tile's rows are output
-}
-
 hipError_t launch_block64(hipStream_t s, const TripleJob *jobs, int njobs, const Segs &segs, int rate)
 {
     if (njobs < 1 || njobs > PAIR_MAX_JOBS || segs.nseg < 1 || segs.max_rows < 1) return hipErrorInvalidValue;
@@ -1144,14 +1135,6 @@ hipError_t launch_block64(hipStream_t s, const TripleJob *jobs, int njobs, const
     const size_t lds = (size_t)js.ring_off + 4 * 8192;
     if (lds > 80 * 1024) return hipErrorInvalidValue;
     return launch_lds(resblock_block64_kernel, dim3(gx, 1, njobs), dim3(256), lds, s, js);
-}
-
-// the MFMA loop of the fused kernels walks whole 8-step bodies (CP = 64: also half a body at the end) and at least one
-bool pair_supported(int Cp, int K)
-{
-    if (!(Cp == 32 || Cp == 64 || Cp == 128 || Cp == 256) || K < 1 || (K & 1) == 0) return false;
-    const int nsb = (K * (Cp / 16) + 3) >> 2;
-    return nsb >= 2 && (Cp == 64 || (nsb & 1) == 0);
 }
 
 template <int CP, int MT, bool MERGE>
@@ -1742,14 +1725,6 @@ __global__ __launch_bounds__(64 * (R / 32 / MT), (MT >= 4 ? 2 : 4)) void resbloc
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ZV_STAMP(11)
 #endif
-}
-
-bool triple_supported(int Cp, int K, const int *dil, int n_dil)
-{
-    if (Cp != 32 || n_dil < 1 || n_dil > TRIPLE_MAX_DIL || !pair_supported(Cp, K) || (K & 1) == 0) return false;
-    int sumd = 0;
-    for (int d = 0; d < n_dil; d++) sumd += dil[d];
-    return 256 - (K - 1) * (sumd + n_dil) >= 96;          // at least 3/8 of the tile's rows are output
 }
 
 // the tile height launch_triple picks: 512 rows (the halo recompute of the 11-tap branch falls from 1.9x to 1.3x) once there are

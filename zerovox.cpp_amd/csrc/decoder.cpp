@@ -45,7 +45,7 @@ bool Model::dec_prepass_on(const Batch &bt) const
 bool Model::dec_runs_on(const Batch &bt) const
 {
     const int k = knob(ZV_DEC_RUNS);
-    return k != 0 && !bt.d_frm_live && dbg_layer.kind < 0 && dec_prepass_on(bt) && (k == 2 || (long)bt.t_rows >= 16384);
+    return !bt.d_frm_live && dbg_layer.kind < 0 && dec_prepass_on(bt) && batch_switch(k, batch_rows((long)bt.t_rows));
 }
 
 // a residual block reaches as far as the longer of its two paths (conv1 -> conv2, the shortcut); the concat joins the encode

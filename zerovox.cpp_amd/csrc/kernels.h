@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "voc_plan.h"      // pair_supported, triple_supported, block64_supported, TRIPLE_MAX_DIL
+
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
 // they select is compiled out.
@@ -190,8 +192,7 @@ struct PairJobs
     float  *merge_out;           // non-null: store (out_0 + out_1) + out_2 here instead of the jobs' own outputs
     int     ring_off;            // resblock_pair64_kernel: byte offset of the weight ring in LDS (set by the launcher)
 };
-// true when a ResBlock conv pair with Cp (padded) channels and K taps can run on the fused kernel
-bool       pair_supported(int Cp, int K);
+// (voc_plan.h pair_supported: whether a ResBlock conv pair with Cp (padded) channels and K taps can run on the fused kernel)
 size_t     pair_weight_halfs(int Cp, int K);
 // GGUF conv weight (ggml ne [K, C, C], f16) -> fused-kernel layout
 void       pack_pair_weight(const uint16_t *w, int K, int C, int Cp, uint16_t *dst);
@@ -209,7 +210,6 @@ hipError_t launch_pair(hipStream_t s, const PairJob *jobs, int njobs, int n_cu, 
 // ---- a whole HiFi-GAN residual block (reference src/hifigan.cpp:74-185: the loop over all dilations) in ONE launch:
 // a workgroup keeps a 256-row f32 tile of y in LDS, runs the n_dil fused pairs on it and writes the centre rows once.
 // HBM traffic per element: 4 B in (x halo factor) + 4 B out for the whole block instead of once per dilation pair.
-constexpr int TRIPLE_MAX_DIL = 3;
 struct TripleJob
 {
     const float *y;                       // [L][Cp] f32 block input (may be shared by several jobs)
@@ -238,10 +238,8 @@ struct TripleJobs
     unsigned long long *stamp;   // diagnostic build: the phase-stamp buffer this launch writes (stamp_buffer()), or null
 #endif
 };
-// true when a ResBlock (Cp channels, K taps, these dilations) fits the whole-block kernel
-bool       triple_supported(int Cp, int K, const int *dil, int n_dil);
+// (voc_plan.h triple_supported / block64_supported: the blocks the two launchers take)
 // several dilation pairs of a 64-channel block in one launch (resblock_block64_kernel): w1 / w2 in pack_pair_weight_ring layout
-bool       block64_supported(int Cp, int K, const int *dil, int n_dil);
 hipError_t launch_block64(hipStream_t s, const TripleJob *jobs, int njobs, const Segs &segs, int rate);
 hipError_t launch_triple(hipStream_t s, const TripleJob *jobs, int njobs, int n_cu, const Segs &segs, int rate);
 

@@ -165,7 +165,6 @@ class Model
     uint64_t    next_batch_seq() { return batch_seq_++; }
     uint64_t    batch_seq() const { return batch_seq_; }
     hipEvent_t  batch_event(uint64_t seq, int which);          // which: 0 start, 1 done
-    int         tail_groups() const { return tail_groups_; }
     void decode_dev(const Batch &b, const float *d_hidden, const float *d_styles, float *d_mel);
     // taps are device pointers inside the arena (token rows as in ids), valid until the next call;
     // n_frames [nseg] is written to d_nframes (outside the arena)
@@ -278,6 +277,14 @@ class Model
         float  out_b = 0.f;
         int    out_K = 0, out_C = 0;
     } voc_;
+    // what of voc_ the schedule's decisions read (voc_plan.h), and a call's numbers; vocode_group issues what voc_plan says of the two
+    VocGeom voc_geom_{};
+    VocCall voc_call(const Batch &b) const;
+    // vocode_group's job filling: a branch's first n_dil dilation pairs as one whole-block job (ring: launch_block64's weights), and
+    // one dilation pair as the two convs' jobs and as the fused kernel's
+    TripleJob block_job(const ResPair *rp, int n_dil, bool ring, const float *y, float *out) const;
+    struct DilPairJobs { ConvJob c1, c2; PairJob p; };
+    DilPairJobs pair_jobs(const ResPair &rp, int dil, const float *yin, float *yout, _Float16 *xt, float *y) const;
 
     struct DecBlk
     {
@@ -385,13 +392,7 @@ class Model
     uint64_t   batch_seq_ = 0;
     hipEvent_t batch_events_[2 * BATCH_RING] = {};
 
-    bool no_fuse_ = false;        // ZV_NO_FUSE=1: two launches per dilation pair (A/B measurement)
-    bool no_triple_ = false;      // ZV_NO_TRIPLE=1: one launch per dilation pair also on the narrow stages (A/B measurement)
-    int  tail_groups_ = 8;        // ZV_TAIL_GROUPS=G: utterance groups of a batch's last vocoder stage (0 / 1 = no split)
     bool skip_launch_ = false;    // vocode_group: the launches of the part that is not asked for are skipped
-    bool no_merge_ = false;       // ZV_NO_MERGE=1: the last dilation pair of a stage stores its three branch outputs instead of their sum (A/B, tests)
-    bool force_fuse256_ = false;  // ZV_FUSE256=1: fused kernel for the 256-channel stage at any length (tests: the path
-                                  // long / batched utterances take, exercised at sizes the CPU oracle can check)
     std::vector<CapturedGraph> graphs_;
     void drop_graphs();
     template <typename F> void run_captured(int kind, const Batch &b, const void *const (&key)[CapturedGraph::NKEY], F &&enqueue);

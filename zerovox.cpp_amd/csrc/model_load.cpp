@@ -158,12 +158,6 @@ Model::Model(const std::string &path, int dev) : device(dev)
     ZV_HIP(hipGetDeviceProperties(&prop, dev));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) fail(ZV_ERR_DEVICE, "device %d is %s; this library is built for gfx950 only", dev, prop.gcnArchName);
     n_cu = prop.multiProcessorCount;
-    // schedule switches are fixed when the model is built (knobs.h: tests force a regime, measurements A/B one)
-    no_fuse_ = knob(ZV_NO_FUSE) != 0;
-    no_triple_ = knob(ZV_NO_TRIPLE) != 0;
-    force_fuse256_ = knob(ZV_FUSE256) != 0;
-    no_merge_ = knob(ZV_NO_MERGE) != 0;
-    tail_groups_ = knob(ZV_TAIL_GROUPS);
     lanes_.resize(1);
     ZV_HIP(hipStreamCreateWithFlags(&lanes_[0].stream, hipStreamNonBlocking));
 
@@ -306,6 +300,27 @@ Model::Model(const std::string &path, int dev) : device(dev)
         voc_.out_w = (uint16_t *)dev_alloc(h.size() * 2);
         ZV_HIP(hipMemcpy(voc_.out_w, h.data(), h.size() * 2, hipMemcpyHostToDevice));
         voc_.out_b = ((const float *)b.data)[0];
+    }
+    // what the schedule's decisions read of all this (voc_plan.h)
+    static_assert(sizeof(voc_.scales) / sizeof(voc_.scales[0]) <= VOC_MAX_STAGES, "VocGeom::st holds every upsample stage");
+    if (voc_.n_rb != VOC_BRANCHES || voc_.n_dil > VOC_MAX_DIL) fail(ZV_ERR_SHAPE, "internal: %d branches of %d dilations do not fit the plan's geometry", voc_.n_rb, voc_.n_dil);
+    voc_geom_.n_up = n_up;
+    voc_geom_.n_dil = voc_.n_dil;
+    for (int d = 0; d < voc_.n_dil; d++) voc_geom_.dil[d] = voc_.dil[d];
+    voc_geom_.in_Cout_p = voc_.in_conv.Cout_p;
+    for (int i = 0; i < n_up; i++)
+    {
+        VocStageGeom &s = voc_geom_.st[i];
+        s.scale = voc_.scales[i];
+        s.Cp = round_up(voc_.in_conv.Cout >> (i + 1), 16);
+        s.up_gemm = voc_.ups[i].w8 != nullptr;
+        s.up_Cin_p = voc_.ups[i].Cin_p;
+        for (int j = 0; j < voc_.n_rb; j++)
+            for (int d = 0; d < voc_.n_dil; d++)
+            {
+                const ResPair &rp = voc_.pairs[((size_t)i * voc_.n_rb + j) * voc_.n_dil + d];
+                s.pair[j][d] = VocPairGeom{rp.c1.K, rp.c2.K, rp.p1 != nullptr, rp.r1 && rp.r2, rp.x1 != nullptr};
+            }
     }
 
     // ---------------- decoder (src/stylettsdec.cpp:33-66,163-168,220-239,334-340) ----------------

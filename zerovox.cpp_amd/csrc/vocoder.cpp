@@ -81,14 +81,13 @@ void Model::vocode_dev(const Batch &bt, const float *d_mel, float *d_wav)
     vocode_group(bt, d_mel, d_wav);
 }
 
-// batches (ZV_VOC_RUNS = 1): by capacity, as the other batch switches — a single short utterance has no rounds of workgroups to
-// give back, and its three extra launches would only add latency.  The threshold is the other batch switches', not a measured
-// one: no sweep of capacities below it is on record, so small batches and long single utterances may be giving a gain away
-bool Model::voc_runs_on(const Batch &bt) const
+VocCall Model::voc_call(const Batch &bt) const
 {
-    const int k = knob(ZV_VOC_RUNS);
-    return !voc_runs_off && !bt.d_frm_live && dbg_layer.kind < 0 && k != 0 && (k == 2 || (long)bt.t_rows >= 16384);
+    return VocCall{bt.nseg, bt.t_max, bt.t_rows, n_cu, bt.d_frm_live != nullptr, voc_runs_off, dbg_layer.kind >= 0,
+                   dbg_layer.kind == 0 ? dbg_layer.index / voc_.n_rb : -1};
 }
+
+bool Model::voc_runs_on(const Batch &bt) const { return voc_runs(voc_call(bt)); }
 
 void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g0, int cnt)
 {
@@ -100,16 +99,80 @@ void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g
     vocode_group(sub, d_mel, d_wav, 2, g0);
 }
 
+TripleJob Model::block_job(const ResPair *rp, int n_dil, bool ring, const float *y, float *out) const
+{
+    TripleJob t;
+    memset(&t, 0, sizeof(t));
+    t.y = y;
+    t.out = out;
+    t.n_dil = n_dil;
+    t.Cp = rp[0].c1.Cout_p;
+    t.K = rp[0].c1.K;            // one K per job: voc_plan.h takes no other branch
+    t.slope = 0.1f;
+    for (int d = 0; d < n_dil; d++)
+    {
+        t.w1[d] = ring ? rp[d].r1 : rp[d].p1;
+        t.w2[d] = ring ? rp[d].r2 : rp[d].p2;
+        if (!ring)
+        {
+            t.w1x[d] = rp[d].x1;
+            t.w2x[d] = rp[d].x2;
+        }
+        t.b1[d] = rp[d].c1.bias;
+        t.b2[d] = rp[d].c2.bias;
+        t.dil[d] = voc_.dil[d];
+    }
+    return t;
+}
+
+Model::DilPairJobs Model::pair_jobs(const ResPair &rp, int dil, const float *yin, float *yout, _Float16 *xt, float *y) const
+{
+    DilPairJobs r;
+    // xt = lrelu(conv(lrelu(y), k, dil) + b)  kept as the f16 operand of the next conv (:108-150)
+    r.c1 = job(rp.c1);
+    r.c1.x0 = yin;
+    r.c1.pro = PRO_ACT;
+    r.c1.slope = 0.1f;
+    r.c1.dil = dil;
+    r.c1.pad = (rp.c1.K - 1) / 2 * dil;
+    r.c1.eact = 1;
+    r.c1.oslope = 0.1f;
+    r.c1.out_f16 = 1;
+    r.c1.out = xt;
+    // y = y + (conv(xt, k, 1) + b)                                                    (:169-181)
+    r.c2 = job(rp.c2);
+    r.c2.x0 = xt;
+    r.c2.pro = PRO_RAW_F16;
+    r.c2.res = yin;
+    r.c2.ldres = rp.c1.Cout_p;
+    r.c2.out = y;
+    memset(&r.p, 0, sizeof(r.p));
+    r.p.y = yin;
+    r.p.out = yout;
+    r.p.w1 = rp.x1;
+    r.p.w2 = rp.x2;
+    r.p.w1r = rp.r1;
+    r.p.w2r = rp.r2;
+    r.p.b1 = rp.c1.bias;
+    r.p.b2 = rp.c2.bias;
+    r.p.Cp = rp.c1.Cout_p;
+    r.p.K = rp.c1.K;
+    r.p.dil = dil;
+    r.p.slope = 0.1f;
+    return r;
+}
+
 void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int part, int seg0)
 {
     struct Unskip { bool &f; ~Unskip() { f = false; } } unskip{skip_launch_};
     skip_launch_ = part == 2;
     const VocLayout lay = voc_layout(stage_arena(bt), bt);
     const int M = hp.audio_num_mels;
+    const VocPlan plan = voc_plan(voc_geom_, voc_call(bt));       // a tail group's plan from its own sub-batch, as its launches
     // Run-shortened schedule: every launch below takes its extents from the run table and the input conv reads the compacted mel;
     // the output conv puts the samples back where they belong and a fill repeats the one frame the run stands for.  The head
     // (part 0 / 1) writes table and mel, a tail (part 2) finds its segments' entries from seg0 on.
-    const bool runs = voc_runs_on(bt);
+    const bool runs = plan.runs;
     const Segs fr = runs ? Segs{lay.runs + seg0, bt.nseg, bt.t_max, bt.frm1} : bt.frames();
     if (part != 2)
     {
@@ -136,10 +199,6 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
     int rate = 1;
     int C = voc_.in_conv.Cout;
     float *c0 = lay.c0;
-    // batches: the first upsample conv runs on conv_gemm_kernel over an f16 operand tensor (see below) — the input conv writes it
-    const int upg0 = knob(ZV_UP_GEMM);
-    const bool c0_f16 = dbg_layer.kind < 0 && voc_.n_up > 0 && voc_.ups[0].w8 && upg0 && knob(ZV_CONV_GEMM) != 0 &&
-                        (upg0 == 2 || (long)L >= 16384) && voc_.ups[0].Cin_p == voc_.in_conv.Cout_p;
 
     // V0: (mel - mean) / scale -> input conv k7 + bias            (src/hifigan.cpp:242-265)
     {
@@ -150,8 +209,8 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         j.pa = voc_.mean;
         j.pb = voc_.scale;
         j.out = c0;
-        if (c0_f16)
-        {   // the only reader is the first upsample conv on conv_gemm_kernel: its operand f16(lrelu(c0, 0.1)) straight from here
+        if (plan.c0_f16)
+        {   // batches: the only reader is the first upsample conv on conv_gemm_kernel: its operand f16(lrelu(c0, 0.1)) straight from here
             j.eact = 1;
             j.oslope = 0.1f;
             j.out_f16 = 1;
@@ -170,6 +229,7 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
     for (int i = 0; i < voc_.n_up; i++)
     {
         const bool last_stage = i == voc_.n_up - 1;
+        const VocStagePlan &sp = plan.st[i];
         skip_launch_ = part == 2;                 // the head runs every upsample conv, the last stage's too (whole batch)
         const int s = voc_.scales[i];
         const ConvW &up = voc_.ups[i];
@@ -199,13 +259,12 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
             j.out = ub;
             // batches, wide upsample convs: the prologue as a pass of its own (f16 operand tensor, parked in the stage's last xt
             // buffer — free until the residual blocks run), the conv on conv_gemm_kernel (ZV_UP_GEMM = 0 never, 2 at any length)
-            const int upg = knob(ZV_UP_GEMM);
-            if (i == 0 && c0_f16)
+            if (i == 0 && plan.c0_f16)
             {
                 j.x0 = c0;
                 j.pro = PRO_RAW_F16;
             }
-            else if (up.w8 && upg && knob(ZV_CONV_GEMM) != 0 && (upg == 2 || (long)L >= 16384) && (size_t)up.Cin_p * 2 * L <= Lo * Cp * 4)
+            else if (sp.up_pass)
             {
                 ZV_LAUNCH("voc_upsample", 0.0, 0.0, launch_act_f16(stream(), (const float *)j.x0, (const float *)j.x1, (const float *)j.x2,
                                                                    j.pro == PRO_ACT ? 1.0f : j.pscale, j.slope, xt[2], (size_t)L * up.Cin_p));
@@ -230,111 +289,50 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         C = Cout;
         const bool dbg_here = dbg_layer.kind == 0 && dbg_layer.index / voc_.n_rb == i;
         if (dbg_here) dbg_inject(ub, Cp, Cout, L);
-        const long Lbatch = (long)bt.t_max * rate * bt.nseg;       // rows the launches of this stage cover
-
         // V2: the 3 MRF branches run side by side (one job each).  Fused path: one launch per dilation
         // (conv -> lrelu -> conv -> + residual, xt kept in LDS), y ping-pongs between two buffers because a
-        // workgroup's halo rows belong to its neighbours' output tiles.
-        // every pair of the stage must have fused weights (one K for both convs, pair_supported): a stage runs fused or not as a
-        // whole, so the MRF sum keeps one association whichever kernels a checkpoint's tap counts allow
-        bool all_fusable = true;
-        for (int q = 0; q < voc_.n_rb * voc_.n_dil; q++) all_fusable = all_fusable && voc_.pairs[(size_t)i * voc_.n_rb * voc_.n_dil + q].p1;
-        // 256-channel stage: the fused kernel needs all 256 xt channels in one workgroup, which leaves few workgroups per
-        // branch for a short utterance — two unfused launches (480 workgroups at 512 frames) win below about a round
-        // of fused ones (round 4, on the 16 x 16 x 32 kernel, whole vocoder under graph replay: 128 frames 0.276 unfused /
-        // 0.291 fused ms, 256: 0.320 / 0.333, 512: 0.470 / 0.465, 1 024: 0.852 / 0.814)
-        const bool enough_rows = Cp != 256 || force_fuse256_ || (Lbatch / 54) * 3 >= (long)n_cu;
-        const bool fused = !no_fuse_ && all_fusable && enough_rows;
+        // workgroup's halo rows belong to its neighbours' output tiles.  Which form a stage runs: voc_plan.h
+        const ResPair *const rps = &voc_.pairs[(size_t)i * voc_.n_rb * voc_.n_dil];       // [branch][dilation]
         const float *ycur[3] = {ub, ub, ub};
         const float *merged_sum = nullptr;
+        // the profile's bytes and flops of a branch's first n dilation pairs
+        auto block_cost = [&](const ResPair *rp, int n, double &bytes, double &flops) {
+            for (int d = 0; d < n; d++)
+            {
+                bytes += conv_bytes(La, C, C, rp[d].c1.K, false) + conv_bytes(La, C, C, rp[d].c2.K, true);
+                flops += conv_flops(La, C, C, rp[d].c1.K) + conv_flops(La, C, C, rp[d].c2.K);
+            }
+        };
         group_begin();
         // narrow stages: the whole residual block (all dilations) of the three branches in ONE launch, y tile kept
         // in registers between the dilation pairs (launch_triple)
-        bool whole_block = fused && !no_triple_ && voc_.n_dil <= TRIPLE_MAX_DIL;
-        for (int jb = 0; jb < 3 && whole_block; jb++)
-        {
-            // one K per job (TripleJob::K): every dilation pair of the branch must have it
-            const ResPair &r0 = voc_.pairs[((size_t)i * voc_.n_rb + jb) * voc_.n_dil];
-            whole_block = triple_supported(Cp, r0.c1.K, voc_.dil, voc_.n_dil);
-            for (int d = 0; d < voc_.n_dil && whole_block; d++)
-            {
-                const ResPair &rp = voc_.pairs[((size_t)i * voc_.n_rb + jb) * voc_.n_dil + d];
-                whole_block = rp.p1 != nullptr && rp.c1.K == r0.c1.K && rp.c2.K == r0.c1.K;
-            }
-        }
-        if (whole_block)
+        if (sp.whole_block)
         {
             TripleJob tj[3];
             double bb = 0, ff = 0;
             for (int jb = 0; jb < 3; jb++)
             {
-                TripleJob &t = tj[jb];
-                memset(&t, 0, sizeof(t));
-                t.y = ub;
-                t.out = y[jb];
-                t.n_dil = voc_.n_dil;
-                t.Cp = Cp;
-                t.slope = 0.1f;
-                for (int d = 0; d < voc_.n_dil; d++)
-                {
-                    const ResPair &rp = voc_.pairs[((size_t)i * voc_.n_rb + jb) * voc_.n_dil + d];
-                    t.K = rp.c1.K;
-                    t.w1[d] = rp.p1;
-                    t.w2[d] = rp.p2;
-                    t.w1x[d] = rp.x1;
-                    t.w2x[d] = rp.x2;
-                    t.b1[d] = rp.c1.bias;
-                    t.b2[d] = rp.c2.bias;
-                    t.dil[d] = voc_.dil[d];
-                    bb += conv_bytes(La, C, C, rp.c1.K, false) + conv_bytes(La, C, C, rp.c2.K, true);
-                    ff += conv_flops(La, C, C, rp.c1.K) + conv_flops(La, C, C, rp.c2.K);
-                }
+                tj[jb] = block_job(rps + jb * voc_.n_dil, voc_.n_dil, false, ub, y[jb]);
+                block_cost(rps + jb * voc_.n_dil, voc_.n_dil, bb, ff);
                 ycur[jb] = y[jb];
             }
             ZV_LAUNCH("voc_resblock_conv", bb, ff, launch_triple(stream(), tj, 3, n_cu, fr, rate));
         }
-        // 64 channels, batches: the first two dilation pairs of the branches with few taps in ONE launch (resblock_block64_kernel:
-        // the branch's tensor crosses HBM once instead of twice; ZV_BLOCK64 = most taps it takes, 0 = never; negative: at any length)
-        bool b64[3] = {false, false, false};
+        // 64 channels, batches: the first two dilation pairs of the branches with few taps in ONE launch (resblock_block64_kernel)
         {
-            const int k64 = knob(ZV_BLOCK64);
-            const int kmax64 = k64 < 0 ? -k64 : k64;
-            if (fused && !whole_block && Cp == 64 && voc_.n_dil == 3 && kmax64 >= 3 && (k64 < 0 || Lbatch / 244 >= 4L * n_cu))
+            TripleJob tj[3];
+            int nj = 0;
+            double bb = 0, ff = 0;
+            for (int jb = 0; jb < 3; jb++)
             {
-                TripleJob tj[3];
-                int nj = 0;
-                double bb = 0, ff = 0;
-                for (int jb = 0; jb < 3; jb++)
-                {
-                    const ResPair *rp = &voc_.pairs[((size_t)i * voc_.n_rb + jb) * voc_.n_dil];
-                    // one K for the two pairs it runs (TripleJob::K)
-                    const bool one_k = rp[1].c1.K == rp[0].c1.K && rp[0].c2.K == rp[0].c1.K && rp[1].c2.K == rp[0].c1.K;
-                    if (!one_k || rp[0].c1.K > kmax64 || !rp[0].r1 || !rp[0].r2 || !rp[1].r1 || !rp[1].r2 || !block64_supported(Cp, rp[0].c1.K, voc_.dil, 2)) continue;
-                    TripleJob &t = tj[nj++];
-                    memset(&t, 0, sizeof(t));
-                    t.y = ub;
-                    t.out = (float *)xt[jb];
-                    t.n_dil = 2;
-                    t.Cp = Cp;
-                    t.K = rp[0].c1.K;
-                    t.slope = 0.1f;
-                    for (int d = 0; d < t.n_dil; d++)
-                    {
-                        t.w1[d] = rp[d].r1;
-                        t.w2[d] = rp[d].r2;
-                        t.b1[d] = rp[d].c1.bias;
-                        t.b2[d] = rp[d].c2.bias;
-                        t.dil[d] = voc_.dil[d];
-                        bb += conv_bytes(La, C, C, rp[d].c1.K, false) + conv_bytes(La, C, C, rp[d].c2.K, true);
-                        ff += conv_flops(La, C, C, rp[d].c1.K) + conv_flops(La, C, C, rp[d].c2.K);
-                    }
-                    b64[jb] = true;
-                    ycur[jb] = (float *)xt[jb];
-                }
-                if (nj) ZV_LAUNCH("voc_resblock_conv", bb, ff, launch_block64(stream(), tj, nj, fr, rate));
+                if (!sp.block64[jb]) continue;
+                tj[nj++] = block_job(rps + jb * voc_.n_dil, 2, true, ub, (float *)xt[jb]);
+                block_cost(rps + jb * voc_.n_dil, 2, bb, ff);
+                ycur[jb] = (float *)xt[jb];
             }
+            if (nj) ZV_LAUNCH("voc_resblock_conv", bb, ff, launch_block64(stream(), tj, nj, fr, rate));
         }
-        for (int d = 0; d < voc_.n_dil && !whole_block; d++)
+        for (int d = 0; d < voc_.n_dil && !sp.whole_block; d++)
         {
             ConvJob j1[3], j2[3];
             PairJob pj[3];
@@ -342,71 +340,32 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
             int npj = 0;                     // pair jobs of this dilation (the branches resblock_block64_kernel has not covered)
             for (int jb = 0; jb < 3; jb++)
             {
-                if (b64[jb] && d < 2) continue;
-                const ResPair &rp = voc_.pairs[((size_t)i * voc_.n_rb + jb) * voc_.n_dil + d];
-                const float *yin = ycur[jb];
-                float *yout = fused ? ((d & 1) ? (float *)xt[jb] : y[jb]) : y[jb];
-                if (fused && !rp.p1) fail(ZV_ERR_SHAPE, "residual block %d: branches of one stage must all be fusable", i * voc_.n_rb + jb);
-                // xt = lrelu(conv(lrelu(y), k, dil) + b)  kept as the f16 operand of the next conv (:108-150)
-                ConvJob a = job(rp.c1);
-                a.x0 = yin;
-                a.pro = PRO_ACT;
-                a.slope = 0.1f;
-                a.dil = voc_.dil[d];
-                a.pad = (rp.c1.K - 1) / 2 * voc_.dil[d];
-                a.eact = 1;
-                a.oslope = 0.1f;
-                a.out_f16 = 1;
-                a.out = xt[jb];
-                j1[jb] = a;
-                // y = y + (conv(xt, k, 1) + b)                                                    (:169-181)
-                ConvJob b = job(rp.c2);
-                b.x0 = xt[jb];
-                b.pro = PRO_RAW_F16;
-                b.res = yin;
-                b.ldres = Cp;
-                b.out = y[jb];
-                j2[jb] = b;
-                PairJob &p = pj[npj++];
-                memset(&p, 0, sizeof(p));
-                p.y = yin;
-                p.out = yout;
-                p.w1 = rp.x1;
-                p.w2 = rp.x2;
-                p.w1r = rp.r1;
-                p.w2r = rp.r2;
-                p.b1 = rp.c1.bias;
-                p.b2 = rp.c2.bias;
-                p.Cp = Cp;
-                p.K = rp.c1.K;
-                p.dil = voc_.dil[d];
-                p.slope = 0.1f;
-                ycur[jb] = fused ? yout : y[jb];
+                if (sp.block64[jb] && d < 2) continue;
+                const ResPair &rp = rps[jb * voc_.n_dil + d];
+                float *yout = sp.fused ? ((d & 1) ? (float *)xt[jb] : y[jb]) : y[jb];
+                if (sp.fused && !rp.p1) fail(ZV_ERR_SHAPE, "residual block %d: branches of one stage must all be fusable", i * voc_.n_rb + jb);
+                const DilPairJobs pq = pair_jobs(rp, voc_.dil[d], ycur[jb], yout, xt[jb], y[jb]);
+                j1[jb] = pq.c1;
+                j2[jb] = pq.c2;
+                pj[npj++] = pq.p;
+                ycur[jb] = sp.fused ? yout : y[jb];
                 b1 += conv_bytes(La, C, C, rp.c1.K, false);
                 f1 += conv_flops(La, C, C, rp.c1.K);
                 b2 += conv_bytes(La, C, C, rp.c2.K, true);
                 f2 += conv_flops(La, C, C, rp.c2.K);
             }
             // the last pair of the stage: the three branches' outputs are only ever used summed (MRF, :300-315), so the
-            // workgroups run all three branches of a tile and store the sum alone
-            // ... once the merged launch (a third of the workgroups, each three times as long) still has rounds of workgroups to
-            // spare: at one round (a single 512-frame utterance) the merged 128- / 64-channel launches took 45.7 / 37.3 us against
-            // 28.4 / 32.8 us for the three branches side by side, more than the upsample conv gains from reading one tensor
-            const int merge_tile = Cp >= 256 ? 54 : (Cp == 128 ? 118 : 246);
-            const bool merge_pays = knob(ZV_MERGE_ALWAYS) != 0 || (Lbatch / merge_tile >= 4L * n_cu && Cp <= knob(ZV_MERGE_MAXC));
-            const bool merge = fused && !no_merge_ && !dbg_here && d == voc_.n_dil - 1 && merge_pays;
-            if (merge)
+            // workgroups run all three branches of a tile and store the sum alone, where voc_plan.h says it pays
+            if (d == voc_.n_dil - 1 && sp.merge != VOC_MERGE_NONE)
             {
                 bool ms_free = true;
                 for (int q = 0; q < npj; q++) ms_free = ms_free && pj[0].out != pj[q].y;
                 float *ms = ms_free ? pj[0].out : nullptr;
                 if (!ms) fail(ZV_ERR_DEVICE, "internal: no free buffer for the merged MRF sum");
-                if (Cp >= 256 && knob(ZV_MERGE_SEQ) != 0)
+                if (sp.merge == VOC_MERGE_SEQ)
                 {
-                    // 256 channels: the branches one launch each on the side-by-side kernel (96-row tiles, all staging loads in flight:
-                    // 1 020 us for the three against 1 105 us for the three-branches-per-workgroup form; at 128 channels the single-
-                    // branch launches' tails cost more than they gain: 1 422 against 1 386 us), every launch adding its term into the
-                    // running sum — (y0 + y1) + y2, the merged form's association, hence its bits
+                    // the branches one launch each on the side-by-side kernel, every launch adding its term into the running
+                    // sum — (y0 + y1) + y2, the merged form's association, hence its bits
                     for (int jb = 0; jb < 3; jb++)
                     {
                         PairJob q = pj[jb];
@@ -420,7 +379,7 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
                               launch_pair(stream(), pj, npj, n_cu, fr, rate, ms));
                 merged_sum = ms;
             }
-            else if (fused)
+            else if (sp.fused)
             {
                 if (npj) ZV_LAUNCH("voc_resblock_conv", b1 + b2, f1 + f2, launch_pair(stream(), pj, npj, n_cu, fr, rate));
             }
