@@ -45,19 +45,9 @@ static constexpr int CK_MAX = 256;
 #ifndef ZV_STAGE_US
 #define ZV_STAGE_US 9
 #endif
-// ... and its loader waves (see conv1d_mfma_kernel): waves that only stage — chunk c + 1 into the second LDS tile while the four
-// MFMA waves walk chunk c.  They have their own vector-memory counters: the MFMA waves' counted waits on the weight stream never
-// queue behind a tile's loads.  0 = the round-3 form (every wave stages, then every wave multiplies).
-#ifndef ZV_SINGLE_LW
-#define ZV_SINGLE_LW 4
-#endif
+// ... and its loader waves (ZV_SINGLE_LW of them, conv_plan.h)
 #ifndef ZV_STAGE_ULW
 #define ZV_STAGE_ULW 10
-#endif
-// a launch over several segments that passes the single-utterance form's workgroup count only as capacity, with more than a round of
-// workgroups, takes the ordinary form (0: it keeps the loader-wave form on the spread map of conv_xcd.h; see launch_conv_from)
-#ifndef ZV_CONV_BATCH_ROUTE
-#define ZV_CONV_BATCH_ROUTE 1
 #endif
 // waves per SIMD the 64 x 64 wave-tile instantiation of the generic conv kernel is compiled for (3: 168 registers)
 #ifndef ZV_NT2_OCC
@@ -1010,36 +1000,20 @@ __global__ __launch_bounds__(SINGLE ? 256 + 64 * ZV_SINGLE_LW : 256, (NT == 2 &&
 #endif
 }
 
+// the plan's geometry (conv_plan.h) into the job table, then the instantiation it names
 template <int MT, int WN, int NT, bool SINGLE = false>
-static hipError_t launch_cfg(hipStream_t s, ConvJobs &jobs, int njobs, int Lmax, int Cout_p, int halo, int ck, int dmax_)
+static hipError_t launch_cfg(hipStream_t s, ConvJobs &jobs, const ConvPlan &p)
 {
-    constexpr int WM = 4 / WN;
-    constexpr int BM = 32 * MT * WM;
-    const int ntiles = (Cout_p + 31) / 32 - jobs.nt_begin;
-    jobs.tps = (Lmax + BM - 1) / BM;
-    dim3 grid(jobs.tps * jobs.segs.nseg, (ntiles + WN * NT - 1) / (WN * NT), njobs);
 #ifdef ZV_STAMPS
-    jobs.stamp = knob(ZV_STAMP_CONV) && knob(ZV_STAMP_CONV) == (int)grid.y && njobs == 1 &&
+    jobs.stamp = knob(ZV_STAMP_CONV) && knob(ZV_STAMP_CONV) == (p.xcd_ny ? p.xcd_ny : p.gy) && p.gz == 1 &&
                          (knob(ZV_STAMP_CIN) ? jobs.j[0].Cin_p == knob(ZV_STAMP_CIN) : jobs.j[0].Cin_p >= 1024)
                      ? stamp_buffer()
                      : nullptr;
 #endif
-    // + dil rows: mfma_taps prefetches one tap past the end
-    constexpr int LW = SINGLE ? ZV_SINGLE_LW : 0;
-    jobs.xcd_ny = jobs.xcd_spread = 0;
-    jobs.warm = knob(ZV_CONV_WARM) != 0;
-    if (SINGLE && knob(ZV_CONV_XCD) != 0)
-    {
-        // (see the kernel and conv_xcd.h) grid.x = 8 XCDs x slots; several segments: no XCD idles for want of channel groups
-        jobs.xcd_ny = grid.y;
-        jobs.xcd_nx = grid.x;
-        jobs.xcd_spread = jobs.segs.nseg > 1;
-        grid = dim3(conv_xcd_grid(jobs.xcd_nx, jobs.xcd_ny, jobs.xcd_spread), 1, njobs);
-    }
-    jobs.tile_bytes = round_up((BM + halo + dmax_) * (ck * 2 + 16), 16);
-    const size_t lds = (size_t)jobs.tile_bytes * (LW > 0 ? 2 : 1);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    return launch_lds(conv1d_mfma_kernel<MT, WN, NT, SINGLE>, grid, dim3(256 + 64 * LW), lds, s, jobs);
+    jobs.tile_bytes = p.tile_bytes;
+    jobs.xcd_nx = p.xcd_nx, jobs.xcd_ny = p.xcd_ny, jobs.xcd_spread = p.xcd_spread;
+    jobs.warm = p.warm;
+    return launch_lds(conv1d_mfma_kernel<MT, WN, NT, SINGLE>, dim3(p.gx, p.gy, p.gz), dim3(p.threads), p.lds_bytes, s, jobs);
 }
 
 // defined in conv_gemm.hip
@@ -1168,38 +1142,10 @@ __global__ __launch_bounds__(256, NKC == 8 ? 2 : 3) void conv_stream_kernel(cons
     }
 }
 
-// the convs conv_stream_kernel takes: one job, 3 taps, one chunk of 64 / 128 input channels read from ONE f32 tensor, bias-only epilogue
-static bool conv_stream_ok(const ConvJob &j, int njobs, int nt_begin)
+// a job as conv_plan.h reads it
+static inline ConvDesc conv_desc(const ConvJob &j)
 {
-    return njobs == 1 && nt_begin == 0 && (j.pro == PRO_ACT || j.pro == PRO_SCALE_ACT) && j.K == 3 && j.dil == 1 && j.pad == 1 &&
-           (j.Cin_p == 64 || j.Cin_p == 128) && j.ck == j.Cin_p && (j.ldx & 3) == 0 && !j.res && !j.stat_part && !j.eact && !j.out_f16 &&
-           !j.x1 && !j.x2;
-}
-
-static hipError_t launch_conv_stream(hipStream_t s, const ConvJob &job, int n_cu, const Segs &segs, int rate)
-{
-    ConvJobs js;
-    js.j[0] = job;
-    js.j[0].dbg = diag_bits();
-    for (int i = 1; i < CONV_MAX_JOBS; i++) js.j[i] = js.j[0];
-    js.segs = segs;
-    js.rate = rate;
-    js.nt_begin = 0;
-    js.order = 0;
-    const int Lmax = segs.max_rows * rate;
-    const int ntiles = (job.Cout_p + 31) / 32, gy = (ntiles + 3) / 4;
-    const int occ = job.Cin_p == 128 ? 2 : 3;
-    // strips of 8 tiles while that still leaves about twelve rounds of workgroups, else 4, 2
-    int strip = 8;
-    while (strip > 2 && (long)((Lmax + 64 * strip - 1) / (64 * strip)) * segs.nseg * gy < 12L * occ * n_cu) strip >>= 1;
-    js.tps = (Lmax + 64 * strip - 1) / (64 * strip);
-    const dim3 grid(js.tps * segs.nseg, gy, 1);
-    const size_t lds = (size_t)2 * 66 * (job.Cin_p * 2 + 16);
-    if (job.Cin_p == 128)
-        hipLaunchKernelGGL(conv_stream_kernel<8>, grid, dim3(256), lds, s, js, strip);
-    else
-        hipLaunchKernelGGL(conv_stream_kernel<4>, grid, dim3(256), lds, s, js, strip);
-    return hipGetLastError();
+    return ConvDesc{j.K, j.dil, j.pad, j.Cin_p, j.Cout_p, j.ck, j.pro, j.ldx, j.w8 != nullptr, j.out_f16 != 0, j.res != nullptr, j.stat_part != nullptr, j.eact != 0, j.x1 || j.x2};
 }
 
 static hipError_t launch_conv_from(hipStream_t s, const ConvJob *jobs, int njobs, int n_cu, const Segs &segs, int rate, int nt_begin);
@@ -1207,115 +1153,64 @@ static hipError_t launch_conv_from(hipStream_t s, const ConvJob *jobs, int njobs
 hipError_t launch_conv(hipStream_t s, const ConvJob *jobs, int njobs, int n_cu, const Segs &segs, int rate)
 {
     if (njobs < 1 || njobs > CONV_MAX_JOBS || segs.nseg < 1 || segs.max_rows < 1) return hipErrorInvalidValue;
-    // batches of wide convs over an f16 operand tensor (the decoder's, behind its pre-pass): whole groups of 8 output tiles
-    // on conv_gemm_kernel, job by job; the tiles left over (1 056 channels = 4 groups + 1 tile) on the kernel below
+    // the jobs conv_gemm_kernel takes (conv_gemm_takes) there, one by one, each with the tiles it leaves over on the generic kernel;
+    // the other jobs in one launch of the generic kernel
+    const ConvCall call{njobs, segs.nseg, segs.max_rows, rate, n_cu, 0};
+    ConvJob rest[CONV_MAX_JOBS];
+    int nrest = 0;
+    for (int i = 0; i < njobs; i++)
     {
-        const int g_env = knob(ZV_CONV_GEMM);
-        const long rows = (long)segs.max_rows * rate * segs.nseg;
-        ConvJob rest[CONV_MAX_JOBS];
-        int nrest = 0, ngemm = 0;
-        for (int i = 0; i < njobs; i++)
+        const ConvJob &j = jobs[i];
+        if (!conv_gemm_takes(conv_desc(j), call))
         {
-            const ConvJob &j = jobs[i];
-            const bool ok = batch_switch(g_env, batch_rows(rows)) && j.w8 && j.pro == PRO_RAW_F16 && j.Cin_p >= 128 &&
-                            conv_gemm_groups(j.Cout_p) >= 1 && !j.out_f16 && (j.ldx & 7) == 0;
-            if (!ok)
-            {
-                rest[nrest++] = j;
-                continue;
-            }
-            ngemm++;
-            hipError_t e = launch_conv_gemm(s, j, segs, rate);
-            if (e != hipSuccess) return e;
-            const int done = conv_gemm_tiles(j.Cout_p);
-            if (done * 32 < j.Cout_p)
-            {
-                e = launch_conv_from(s, &j, 1, n_cu, segs, rate, done);
-                if (e != hipSuccess) return e;
-            }
+            rest[nrest++] = j;
+            continue;
         }
-        if (ngemm) return nrest ? launch_conv_from(s, rest, nrest, n_cu, segs, rate, 0) : hipSuccess;
+        hipError_t e = launch_conv_gemm(s, j, segs, rate);
+        if (e != hipSuccess) return e;
+        const int done = conv_gemm_tiles(j.Cout_p);
+        if (done * 32 < j.Cout_p)
+        {
+            e = launch_conv_from(s, &j, 1, n_cu, segs, rate, done);
+            if (e != hipSuccess) return e;
+        }
     }
-    return launch_conv_from(s, jobs, njobs, n_cu, segs, rate, 0);
+    return nrest ? launch_conv_from(s, rest, nrest, n_cu, segs, rate, 0) : hipSuccess;
 }
 
+// one launch of the generic family from output tile nt_begin on: validate, plan (conv_plan.h), fill the job table, dispatch
 static hipError_t launch_conv_from(hipStream_t s, const ConvJob *jobs, int njobs, int n_cu, const Segs &segs, int rate, int nt_begin)
 {
     const int dbg = diag_bits();
-    ConvJobs js;
-    js.segs = segs;
-    js.rate = rate;
-    js.tps = 0;
-    js.nt_begin = nt_begin;
-    js.order = 0;
     const int Lmax = segs.max_rows * rate;
-    int halo = 0, ck = 0, dmax = 1;
+    ConvJobs js;
+    ConvDesc desc[CONV_MAX_JOBS];
     for (int i = 0; i < njobs; i++)
     {
         js.j[i] = jobs[i];
-        dmax = jobs[i].dil > dmax ? jobs[i].dil : dmax;
         js.j[i].dbg = dbg;
-        if (jobs[i].Cout_p != jobs[0].Cout_p) return hipErrorInvalidValue;
-        const int h = (jobs[i].K - 1) * jobs[i].dil;
-        if (h > halo) halo = h;
-        ck = jobs[i].ck > ck ? jobs[i].ck : ck;
+        desc[i] = conv_desc(jobs[i]);
         if (jobs[i].stat_part && jobs[i].stat_nblk * 32 < Lmax) return hipErrorInvalidValue;
     }
     for (int i = njobs; i < CONV_MAX_JOBS; i++) js.j[i] = js.j[0];
-    const int Cout_p = jobs[0].Cout_p;
-    const int ntiles = (Cout_p + 31) / 32 - nt_begin;
-    if (ntiles < 1) return hipErrorInvalidValue;
-    // three output tiles already take four waves (one idles): the input tile is staged once instead of twice
-    // (two row tiles x two output tiles per workgroup instead, so that row pairs share weight fragments: a single utterance 1.71 -> 1.79 ms)
-    const int WN = ntiles >= 3 ? 4 : (ntiles >= 2 ? 2 : 1);
-    // pick the tallest wave tile (most B-fragment reuse) that still gives every CU about two workgroups; the tile
-    // shape never changes an output bit: every output element is one accumulator chain over (chunk, tap, channel)
-    auto wgs = [&](int MT, int NT) {
-        const int BM = 32 * MT * (4 / WN);
-        return (long)((Lmax + BM - 1) / BM) * segs.nseg * ((ntiles + WN * NT - 1) / (WN * NT)) * njobs;
-    };
-    int MT = 4;
-    while (MT > 1 && wgs(MT, 1) < 2L * n_cu) MT >>= 1;
-    while (MT > 1 && (size_t)(32 * MT * (4 / WN) + halo + dmax) * (ck * 2 + 16) > 80 * 1024) MT >>= 1;   // keep >= 2 workgroups per CU in LDS
+    const ConvPlan p = conv_plan(desc, ConvCall{njobs, segs.nseg, segs.max_rows, rate, n_cu, nt_begin});
+    if (!p.valid) return hipErrorInvalidValue;
+    js.segs = segs;
+    js.rate = rate;
+    js.tps = p.tps;
+    js.nt_begin = nt_begin;
+    js.order = 0;
+    if (p.form == CONV_STREAM)
     {
-        // memory-bound convs (the polyphase transposed convs of the narrow HiFi-GAN stages: a few hundred MACs per output
-        // element against 8 bytes moved) want workgroups in flight, not weight reuse: measured on the batch, the last
-        // three upsample convs take 897 / 595 / 452 us with the tall tiles and 636 / 569 / 416 us with these
-        const double ai = 2.0 * jobs[0].K * jobs[0].Cin_p * Cout_p / (4.0 * (jobs[0].Cin_p + Cout_p));
-        // ... and the ones conv_stream_kernel takes run there (ZV_CONV_STREAM = 0 never, 2 at any length)
-        const int st_env = knob(ZV_CONV_STREAM);
-        if (st_env && conv_stream_ok(jobs[0], njobs, nt_begin) && (st_env == 2 || (ai < 200.0 && wgs(1, 1) >= 16L * n_cu)))
-            return launch_conv_stream(s, jobs[0], n_cu, segs, rate);
-        // (round 3: 64-row tiles for all of them — the 128 -> 4 x 64 channel one 573 -> 501 us: half the weight stream per row)
-        if (ai < 200.0 && wgs(1, 1) >= 16L * n_cu) MT = std::min(MT, 2);
+        if (p.nkc == 8)
+            hipLaunchKernelGGL(conv_stream_kernel<8>, dim3(p.gx, p.gy, p.gz), dim3(p.threads), p.lds_bytes, s, js, p.strip);
+        else
+            hipLaunchKernelGGL(conv_stream_kernel<4>, dim3(p.gx, p.gy, p.gz), dim3(p.threads), p.lds_bytes, s, js, p.strip);
+        return hipGetLastError();
     }
-    if (MT < knob(ZV_CONV_MT)) MT = knob(ZV_CONV_MT);      // measurement hook: minimum MT
-    // two output tiles per wave once a conv is wide and the launch still has rounds of workgroups to spare
-    const int nt_env = knob(ZV_CONV_NT);
-    // ... and deep (>= 2 048 products per output element: the decoder's; the first two upsample convs, 1 536 / 768 deep, measured
-    // 265 / 417 us on 64 x 64 wave tiles and 245 / 395 us on 128 x 32 ones)
-    int NT = (WN == 4 && ntiles >= 8 && MT >= 2 && wgs(MT, 2) >= 4L * n_cu && jobs[0].K * jobs[0].Cin_p >= 2048) ? 2 : 1;
-    if (nt_env == 1 || (nt_env == 2 && WN == 4 && ntiles >= 2 && MT >= 2)) NT = nt_env;
-    if (NT == 2 && MT == 4) MT = 2;        // 64 x 64 per wave: the 128 x 64 shape does not fit 256 registers
-    {
-        // single-utterance launches (at most a round of workgroups, one wave per SIMD): the deep-lookahead loop for the
-        // 256-channel chunks
-        // ... of convs with SEVERAL such chunks (the decoder's): measured per launch at 512 frames, the one-chunk 256-channel
-        // convs of HiFi-GAN stage 1 take 23.0 us on this loop against 20.0 us on mfma_taps (profiles/r02_v2_single_utterance_kernel_trace.txt
-        // vs round 1's trace), the five-chunk decoder convs 29.6 against 33
-        // ... and of launches the form was built for.  wgs() counts capacity, not utterances: a batch of 32 utterances x 256 phonemes
-        // has 512 workgroups of 8 waves for the first conv of a variance predictor, two rounds of a form whose loader waves leave
-        // room for one workgroup per CU.  Several segments and more than a round: the ordinary form (measured: DESIGN.md, "Narrow batch convs on all XCDs")
-        const bool batch_rounds = ZV_CONV_BATCH_ROUTE && segs.nseg > 1 && wgs(1, 1) > n_cu;
-        if (knob(ZV_CONV_SINGLE) != 0 && MT == 1 && NT == 1 && ck == 256 && wgs(1, 1) <= 2L * n_cu && !batch_rounds &&
-            (jobs[0].Cin_p > 256 || knob(ZV_CONV_SINGLE) == 2))
-        {
-            if (WN == 4) return launch_cfg<1, 4, 1, true>(s, js, njobs, Lmax, Cout_p, halo, ck, dmax);
-            if (WN == 2) return launch_cfg<1, 2, 1, true>(s, js, njobs, Lmax, Cout_p, halo, ck, dmax);
-        }
-    }
+    if (p.form == CONV_LOADER) return p.WN == 4 ? launch_cfg<1, 4, 1, true>(s, js, p) : launch_cfg<1, 2, 1, true>(s, js, p);
 #define ZV_CASE(mt, wn, nt) \
-    if (MT == mt && WN == wn && NT == nt) return launch_cfg<mt, wn, nt>(s, js, njobs, Lmax, Cout_p, halo, ck, dmax);
+    if (p.MT == mt && p.WN == wn && p.NT == nt) return launch_cfg<mt, wn, nt>(s, js, p);
     ZV_CASE(4, 4, 1) ZV_CASE(2, 4, 1) ZV_CASE(1, 4, 1) ZV_CASE(2, 4, 2)
     ZV_CASE(4, 2, 1) ZV_CASE(2, 2, 1) ZV_CASE(1, 2, 1)
     ZV_CASE(4, 1, 1) ZV_CASE(2, 1, 1) ZV_CASE(1, 1, 1)

@@ -842,19 +842,6 @@ __global__ __launch_bounds__(256, 2) void resblock_pair64_kernel(const PairJobs 
     }
 }
 
-template <bool MERGE>
-static hipError_t launch_pair64_ring(hipStream_t s, PairJobs &js, int njobs, int Lmax, int Kmax, int dmax)
-{
-    constexpr int BM = 256;
-    const int TMmin = BM - (Kmax - 1);
-    dim3 grid(tile_deal_grid((Lmax + TMmin - 1) / TMmin, js.segs.nseg, js.deal_c), 1, MERGE ? 1 : njobs);
-    // operand rows: BM + (K - 1) * dil, + dil: the last tap's prefetch reads one tap past the end
-    js.ring_off = round_up((BM + Kmax * dmax) * (64 * 2 + 16), 1024);
-    const size_t lds = (size_t)js.ring_off + 4 * 8192;
-    if (lds > 80 * 1024) return hipErrorInvalidValue;
-    return launch_lds(resblock_pair64_kernel<MERGE>, grid, dim3(256), lds, s, js);
-}
-
 // ---------------------------------------------------------------------------------------------------
 // resblock_block64_kernel — SEVERAL dilation pairs of a 64-channel residual block in one launch, for the branches whose halo is
 // small (3 taps: 2 rows per pair and dilation step): resblock_pair64_kernel's machinery (weights of every conv through the
@@ -1107,72 +1094,62 @@ __global__ __launch_bounds__(256, 2) void resblock_block64_kernel(const TripleJo
                 }
 }
 
+// a block as conv_plan.h reads it
+static inline BlockDesc block_desc(const TripleJob &P)
+{
+    BlockDesc b{P.Cp, P.K, P.n_dil, {0, 0, 0}};
+    for (int d = 0; d < P.n_dil && d < TRIPLE_MAX_DIL; d++) b.dil[d] = P.dil[d];
+    return b;
+}
+
 hipError_t launch_block64(hipStream_t s, const TripleJob *jobs, int njobs, const Segs &segs, int rate)
 {
     if (njobs < 1 || njobs > PAIR_MAX_JOBS || segs.nseg < 1 || segs.max_rows < 1) return hipErrorInvalidValue;
     TripleJobs js;
-    js.segs = segs;
-    js.rate = rate;
-    js.interleave = 1;
-    js.db_mask = 0;
-    const int Lmax = segs.max_rows * rate;
-    js.deal_c = tile_deal_chunk(64);
-    int gx = 8, rows_max = 0;
+    BlockDesc desc[PAIR_MAX_JOBS];
     for (int i = 0; i < njobs; i++)
     {
         js.j[i] = jobs[i];
         js.j[i].dbg = 0;
-        const TripleJob &P = jobs[i];
-        if (!block64_supported(P.Cp, P.K, P.dil, P.n_dil)) return hipErrorInvalidValue;
-        int sumd = 0, dmax = 1;
-        for (int d = 0; d < P.n_dil; d++) { sumd += P.dil[d]; dmax = P.dil[d] > dmax ? P.dil[d] : dmax; }
-        const int h2 = (P.K - 1) / 2, TM = 256 - 2 * h2 * (sumd + P.n_dil);
-        gx = std::max(gx, tile_deal_grid((Lmax + TM - 1) / TM, segs.nseg, js.deal_c));
-        rows_max = std::max(rows_max, 256 + 2 * h2 * dmax + 2 * dmax);
+        desc[i] = block_desc(jobs[i]);
     }
     for (int i = njobs; i < PAIR_MAX_JOBS; i++) js.j[i] = js.j[0];
-    js.ring_off = round_up(rows_max * (64 * 2 + 16), 1024);
-    const size_t lds = (size_t)js.ring_off + 4 * 8192;
-    if (lds > 80 * 1024) return hipErrorInvalidValue;
-    return launch_lds(resblock_block64_kernel, dim3(gx, 1, njobs), dim3(256), lds, s, js);
+    const Block64Plan p = block64_plan(desc, ConvCall{njobs, segs.nseg, segs.max_rows, rate, 0, 0});
+    if (!p.valid) return hipErrorInvalidValue;
+    js.segs = segs;
+    js.rate = rate;
+    js.interleave = 1;
+    js.db_mask = 0;
+    js.deal_c = p.deal_c;
+    js.ring_off = p.ring_off;
+    return launch_lds(resblock_block64_kernel, dim3(p.gx, 1, p.gz), dim3(p.threads), p.lds_bytes, s, js);
 }
 
 template <int CP, int MT, bool MERGE>
-static hipError_t launch_pair_cfg(hipStream_t s, const PairJobs &js, int njobs, int Lmax, int Kmax, int dmax)
+static hipError_t launch_pair_cfg(hipStream_t s, const PairJobs &js, const PairPlan &p)
 {
-    constexpr int WNc = (CP == 256) ? 4 : CP / 32;
-    constexpr int BM = 32 * MT * (4 / WNc);
-    const int TMmin = BM - (Kmax - 1);
-    if (TMmin < 32) return hipErrorInvalidValue;
-    // jobs differ in K: grid.x is sized for the smallest TM (the most tiles per segment), workgroups beyond a job's extent exit at once
-    dim3 grid(tile_deal_grid((Lmax + TMmin - 1) / TMmin, js.segs.nseg, js.deal_c), 1, MERGE ? 1 : njobs);      // multiple of 8: tile_deal.h
-    // rows touched: BM + taps (K rounded up to the loop's granularity, + 1 for the last prefetch) * dil.  The loop walks
-    // whole taps once a tap is at least a body (CP >= 128): K + 1 taps (51 KB for the 128-channel stage: room for three
-    // workgroups per CU instead of two — measured worth 0.6 %)
-    // (CP = 256: exactly K taps — the prefetch one tap past the end reads rows that exist but are never used — so that the
-    // 96-row tile of MT = 3 stays under 80 KB: two workgroups per CU)
-    size_t lds = (size_t)(BM + (Kmax + (CP == 256 ? 0 : (CP >= 128 ? 1 : 4))) * dmax) * (CP * 2 + 16);
+    size_t lds = p.lds_bytes;
 #ifdef ZV_DIAG
     lds += (size_t)knob(ZV_LDS_PAD);       // diagnostic build: extra bytes of LDS per workgroup = a lower occupancy on purpose
 #endif
-    return launch_lds(resblock_pair_kernel<CP, MT, MERGE>, grid, dim3(256), lds, s, js);
+    return launch_lds(resblock_pair_kernel<CP, MT, MERGE>, dim3(p.gx, 1, p.gz), dim3(256), lds, s, js);
 }
 
+// validate, plan (conv_plan.h pair_plan: the ring form, the tile height), fill the job table, dispatch
 hipError_t launch_pair(hipStream_t s, const PairJob *jobs, int njobs, int n_cu, const Segs &segs, int rate, float *merge_out)
 {
     if (njobs < 1 || njobs > PAIR_MAX_JOBS || segs.nseg < 1 || segs.max_rows < 1) return hipErrorInvalidValue;
-    const int dbg = diag_bits(), mt_env = knob(ZV_PAIR_MT);
+    const int dbg = diag_bits();
     PairJobs js;
     js.segs = segs;
     js.rate = rate;
     js.njobs = njobs;
-    js.deal_c = tile_deal_chunk(jobs[0].Cp);
     js.merge_out = merge_out;
 #ifdef ZV_STAMPS
     js.stamp = knob(ZV_STAMP_CP) && knob(ZV_STAMP_CP) == jobs[0].Cp && !merge_out ? stamp_buffer() : nullptr;
 #endif
-    const int Lmax = segs.max_rows * rate;
-    int Kmax = 0, dmax = 0;
+    int  Kmax = 0, dmax = 0;
+    bool any_sum = false, all_ring = true;
     for (int i = 0; i < njobs; i++)
     {
         js.j[i] = jobs[i];
@@ -1180,50 +1157,25 @@ hipError_t launch_pair(hipStream_t s, const PairJob *jobs, int njobs, int n_cu, 
         if (jobs[i].Cp != jobs[0].Cp) return hipErrorInvalidValue;
         Kmax = jobs[i].K > Kmax ? jobs[i].K : Kmax;
         dmax = jobs[i].dil > dmax ? jobs[i].dil : dmax;
+        any_sum = any_sum || jobs[i].sum_out || jobs[i].sum_in;
+        all_ring = all_ring && jobs[i].w1r && jobs[i].w2r;
     }
     for (int i = njobs; i < PAIR_MAX_JOBS; i++) js.j[i] = js.j[0];
-    // the running MRF sum (PairJob::sum_in / sum_out) exists only in resblock_pair_kernel<CP, MT, false>: not together with the
-    // merged form, and not on the 64-channel ring kernel (which would silently write P.out instead)
-    bool any_sum = false;
-    for (int i = 0; i < njobs; i++) any_sum = any_sum || jobs[i].sum_out || jobs[i].sum_in;
-    if (any_sum && merge_out) return hipErrorInvalidValue;
     const int Cp = jobs[0].Cp;
-    const int WN = Cp == 256 ? 4 : Cp / 32;
-    auto wgs = [&](int MT) {
-        const int BM = 32 * MT * (4 / WN);
-        const int TM = BM - (Kmax - 1);
-        return TM < 32 ? 0L : (long)((Lmax + TM - 1) / TM) * segs.nseg * njobs;
-    };
-    // tallest tile that still gives every CU about three workgroups, but never a BM so small that the
-    // (k-1)-row halo dominates (MT >= 2: BM >= 64 / 128 / 256 for 128 / 64 / 32 channels)
-    // measured (512 frames, batch 1): BM = 64/128/256 rows (MT = 2) beats MT = 4 at every channel count — three
-    // to four workgroups per CU hide the staging / epilogue phases better than taller tiles save weight traffic
-    // measured (batch of 32 x 1 024 frames): once a launch has many rounds of workgroups the 128-channel stage is
-    // bound by the weight stream from L2 (1 KiB of B fragment per 2 MFMAs per wave at MT = 2) and BM = 128 is 14 % faster;
-    // the 64-channel stage does not care (-1 %).  The tile height never changes an output bit.
-    // 64 channels, batches: the form with the weights through an LDS ring (ZV_PAIR64_RING = 0 never, 2 whenever it fits)
-    {
-        const int ring_env = knob(ZV_PAIR64_RING);
-        bool ok = Cp == 64 && !any_sum && ring_env != 0 && Kmax >= 3 && (256 + Kmax * dmax) * 144 + 4 * 8192 + 1024 <= 80 * 1024;
-        for (int i = 0; i < njobs && ok; i++) ok = jobs[i].w1r && jobs[i].w2r;
-        const long rwgs = (long)((Lmax + 256 - Kmax) / (257 - Kmax)) * segs.nseg * njobs;
-        if (ok && (ring_env == 2 || rwgs >= 6L * n_cu))
-        {
-            js.kmax = Kmax;
-            return merge_out ? launch_pair64_ring<true>(s, js, njobs, Lmax, Kmax, dmax) : launch_pair64_ring<false>(s, js, njobs, Lmax, Kmax, dmax);
-        }
-    }
-    int MT = (Cp == 128 && wgs(4) >= 8L * n_cu) ? 4 : 2;
-    // 256 channels, batches: 96-row tiles (two thirds of the weight-fragment traffic per row, 10 instead of 16 % of conv2 spent
-    // on halo rows at 11 taps; 80 KB of LDS and 234 registers still give two workgroups per CU): 1 010 -> 897 us per launch.
-    // (The merged form would need 330 registers.)
-    if (Cp == 256 && !merge_out && wgs(3) >= 4L * n_cu) MT = 3;
-    if (mt_env == 2 || mt_env == 4 || (mt_env == 3 && Cp == 256 && !merge_out)) MT = mt_env;      // (the merged form of MT = 3 needs 330 registers)
+    const PairPlan p = pair_plan(Cp, Kmax, dmax, any_sum, merge_out != nullptr, all_ring, ConvCall{njobs, segs.nseg, segs.max_rows, rate, n_cu, 0});
+    if (!p.valid) return hipErrorInvalidValue;
     js.kmax = Kmax;
-#define ZV_PCASE(cp, mt)                                                                                 \
-    if (Cp == cp && MT == mt)                                                                            \
-        return merge_out ? launch_pair_cfg<cp, mt, true>(s, js, njobs, Lmax, Kmax, dmax)                 \
-                         : launch_pair_cfg<cp, mt, false>(s, js, njobs, Lmax, Kmax, dmax);
+    js.deal_c = p.deal_c;
+    if (p.ring)
+    {
+        js.ring_off = p.ring_off;
+        return merge_out ? launch_lds(resblock_pair64_kernel<true>, dim3(p.gx, 1, p.gz), dim3(256), p.lds_bytes, s, js)
+                         : launch_lds(resblock_pair64_kernel<false>, dim3(p.gx, 1, p.gz), dim3(256), p.lds_bytes, s, js);
+    }
+#define ZV_PCASE(cp, mt)                                                                 \
+    if (Cp == cp && p.MT == mt)                                                          \
+        return merge_out ? launch_pair_cfg<cp, mt, true>(s, js, p)                       \
+                         : launch_pair_cfg<cp, mt, false>(s, js, p);
     ZV_PCASE(32, 4) ZV_PCASE(32, 2) ZV_PCASE(64, 4) ZV_PCASE(64, 2) ZV_PCASE(128, 4) ZV_PCASE(128, 2) ZV_PCASE(256, 2) ZV_PCASE(256, 3) ZV_PCASE(256, 4)
 #undef ZV_PCASE
     return hipErrorInvalidValue;
@@ -1727,88 +1679,48 @@ __global__ __launch_bounds__(64 * (R / 32 / MT), (MT >= 4 ? 2 : 4)) void resbloc
 #endif
 }
 
-// the tile height launch_triple picks: 512 rows (the halo recompute of the 11-tap branch falls from 1.9x to 1.3x) once there are
-// enough rows for about eight rounds of such workgroups, else 256 (measured at 512 frames: 100 vs 104 us)
-static void triple_tile(int njobs, int n_cu, const Segs &segs, int rate, int &MT, int &R)
-{
-    const int Lmax = segs.max_rows * rate;
-    R = ((long)Lmax * segs.nseg * njobs >= 7000L * n_cu || knob(ZV_TRIPLE_V2) == 3) ? 512 : 256;      // (ZV_TRIPLE_V2 = 3: tests force the batches' tile)
-    MT = 2;
-}
-
+// validate, plan (conv_plan.h triple_plan: the tile height, the form with the weights in LDS, its weight buffers), fill, dispatch
 hipError_t launch_triple(hipStream_t s, const TripleJob *jobs, int njobs, int n_cu, const Segs &segs, int rate)
 {
     if (njobs < 1 || njobs > PAIR_MAX_JOBS || segs.nseg < 1 || segs.max_rows < 1) return hipErrorInvalidValue;
     const int dbg = diag_bits();
     TripleJobs js;
-    js.segs = segs;
-    js.rate = rate;
-    js.deal_c = tile_deal_chunk(32);
-    js.interleave = 1;
-    js.db_mask = 0;
-#ifdef ZV_STAMPS
-    js.stamp = knob(ZV_STAMP_CP) == 32 ? stamp_buffer() : nullptr;
-#endif
-    const int Lmax = segs.max_rows * rate;
-    int R, MT;
-    triple_tile(njobs, n_cu, segs, rate, MT, R);
-    int gx = 8;
-    size_t lds = 0;
+    BlockDesc desc[PAIR_MAX_JOBS];
     for (int i = 0; i < njobs; i++)
     {
         js.j[i] = jobs[i];
         js.j[i].dbg = dbg;
-        const TripleJob &P = jobs[i];
-        if (P.Cp != jobs[0].Cp || !triple_supported(P.Cp, P.K, P.dil, P.n_dil)) return hipErrorInvalidValue;
-        int sumd = 0, dmax = 1;
-        for (int d = 0; d < P.n_dil; d++) { sumd += P.dil[d]; dmax = P.dil[d] > dmax ? P.dil[d] : dmax; }
-        const int h2 = (P.K - 1) / 2, TM = R - 2 * h2 * (sumd + P.n_dil);
-        gx = std::max(gx, tile_deal_grid((Lmax + TM - 1) / TM, segs.nseg, js.deal_c));
-        const size_t rows = R + 2 * h2 * dmax + 5 * dmax;
-        lds = std::max(lds, rows * (P.Cp * 2 + 16));
+        desc[i] = block_desc(jobs[i]);
     }
     for (int i = njobs; i < PAIR_MAX_JOBS; i++) js.j[i] = js.j[0];
-    if (lds > 64 * 1024) return hipErrorInvalidValue;
-    const dim3 grid(gx, 1, njobs);      // multiple of 8: tile_deal.h
-    // batches: the form with the weights in LDS (two workgroups per CU); ZV_TRIPLE_V2 = 0 never, 2 always, 3 always and on 512-row tiles (A/B, tests)
-    const int v2_env = knob(ZV_TRIPLE_V2);
-    if (v2_env && (R == 512 || v2_env >= 2))
+    const TriplePlan p = triple_plan(desc, ConvCall{njobs, segs.nseg, segs.max_rows, rate, n_cu, 0});
+    if (!p.valid) return hipErrorInvalidValue;
+    js.segs = segs;
+    js.rate = rate;
+    js.deal_c = p.deal_c;
+    js.interleave = p.interleave;
+    js.db_mask = p.db_mask;
+#ifdef ZV_STAMPS
+    js.stamp = knob(ZV_STAMP_CP) == 32 ? stamp_buffer() : nullptr;
+#endif
+    const dim3 grid(p.gx, 1, p.gz);
+    if (p.lds_form)
     {
-        size_t lds2 = 0;
-        js.db_mask = 0;
+        // (the whole-block kernel of batches reads the 16 x 16 x 32 fragment order: TripleJob::w1x / w2x)
         for (int i = 0; i < njobs; i++)
-        {
-            const TripleJob &P = jobs[i];
-            int dmax = 1;
-            for (int d = 0; d < P.n_dil; d++) dmax = P.dil[d] > dmax ? P.dil[d] : dmax;
-            const size_t rows = R + 2 * ((P.K - 1) / 2) * dmax + 5 * dmax;
-            const int nb = ((P.K * 2 + 3) >> 2) >> 1;
-            // operand tile + weight buffer(s) + 2 fragments (the last B prefetch) + the block's biases
-            const size_t one = (size_t)round_up((int)(rows * 80), 1024) + (size_t)(8 * nb + 2) * 1024 + 1024;
-            const bool db = knob(ZV_TRIPLE_DB) != 0 && one + (size_t)8 * nb * 1024 <= 80 * 1024;
-            if (db) js.db_mask |= 1 << i;
-            lds2 = std::max(lds2, one + (db ? (size_t)8 * nb * 1024 : 0));
-        }
-        if (lds2 <= 80 * 1024)
-        {
-            js.interleave = knob(ZV_TRIPLE_INTERLEAVE) != 0 ? njobs : 1;
-            const dim3 grid2 = js.interleave > 1 ? dim3(gx * njobs, 1, 1) : grid;
-            // (the whole-block kernel of batches reads the 16 x 16 x 32 fragment order: TripleJob::w1x / w2x)
-            for (int i = 0; i < njobs; i++)
-                for (int d = 0; d < jobs[i].n_dil; d++)
-                    if (!jobs[i].w1x[d] || !jobs[i].w2x[d]) return hipErrorInvalidValue;
-            for (int i = 0; i < PAIR_MAX_JOBS; i++)
-                for (int d = 0; d < TRIPLE_MAX_DIL; d++)
-                {
-                    js.j[i].w1[d] = js.j[i].w1x[d];
-                    js.j[i].w2[d] = js.j[i].w2x[d];
-                }
-            return R == 512 ? launch_lds(resblock_block32_kernel<2, 512>, grid2, dim3(512), lds2, s, js)
-                            : launch_lds(resblock_block32_kernel<2, 256>, grid2, dim3(256), lds2, s, js);
-        }
+            for (int d = 0; d < jobs[i].n_dil; d++)
+                if (!jobs[i].w1x[d] || !jobs[i].w2x[d]) return hipErrorInvalidValue;
+        for (int i = 0; i < PAIR_MAX_JOBS; i++)
+            for (int d = 0; d < TRIPLE_MAX_DIL; d++)
+            {
+                js.j[i].w1[d] = js.j[i].w1x[d];
+                js.j[i].w2[d] = js.j[i].w2x[d];
+            }
+        return p.R == 512 ? launch_lds(resblock_block32_kernel<2, 512>, grid, dim3(p.threads), p.lds_bytes, s, js)
+                          : launch_lds(resblock_block32_kernel<2, 256>, grid, dim3(p.threads), p.lds_bytes, s, js);
     }
 #define ZV_TCASE(mt, r) \
-    if (MT == mt && R == r) { hipLaunchKernelGGL((resblock_triple_kernel<32, mt, r>), grid, dim3(64 * (r / 32 / mt)), lds, s, js); return hipGetLastError(); }
+    if (p.MT == mt && p.R == r) { hipLaunchKernelGGL((resblock_triple_kernel<32, mt, r>), grid, dim3(p.threads), p.lds_bytes, s, js); return hipGetLastError(); }
     ZV_TCASE(2, 256) ZV_TCASE(2, 512)
 #undef ZV_TCASE
     return hipErrorInvalidValue;

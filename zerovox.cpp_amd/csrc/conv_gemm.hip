@@ -26,28 +26,13 @@ namespace zv
 // Units walk (chunk, tap, channel) in conv1d_mfma_kernel's order — 64-channel blocks of a chunk inside a tap — so every
 // output element is the same accumulation chain: same bits as every other regime.  Channels past Cin_p inside the last block
 // read finite neighbours (the next row) against zero weights.
-int conv_gemm_groups(int Cout_p) { return ((Cout_p + 31) / 32) / 8; }
-// tiles the kernel covers: whole groups of 8, plus ONE leftover tile (1 056 channels = 33 tiles, 528 = 17) that the last group's
-// workgroups compute on the side (one extra 32 x 32 tile per wave); more leftovers stay with conv1d_mfma_kernel
-int conv_gemm_tiles(int Cout_p)
-{
-    const int nt = (Cout_p + 31) / 32, ng = nt / 8;
-    return ng * 8 + ((nt - ng * 8 == 1 && ng >= 1) ? 1 : 0);
-}
-
+// (conv_gemm_groups / conv_gemm_tiles / conv_gemm_units, the tiles and K-loop steps of a conv: conv_plan.h)
 __device__ __forceinline__ int gemm_groups_dev(int Cout_p) { return ((Cout_p + 31) >> 5) >> 3; }
 
 __device__ __forceinline__ int conv_gemm_units_dev(int Cin_p, int K)
 {
     const int full = Cin_p >> 8, rem = Cin_p & 255;
     return K * (full * 4 + ((rem + 63) >> 6));
-}
-
-int conv_gemm_units(int Cin_p, int K)
-{
-    int n = 0;
-    for (int c0 = 0; c0 < Cin_p; c0 += 256) n += K * ((std::min(256, Cin_p - c0) + 63) / 64);
-    return n;
 }
 
 size_t conv_gemm_weight_halfs(int Cin_p, int Cout_p, int K)
@@ -468,6 +453,8 @@ __global__ __launch_bounds__(512, 2) void conv_gemm_kernel(const ConvJobs jobs)
 
 hipError_t launch_conv_gemm(hipStream_t s, const ConvJob &job, const Segs &segs, int rate)
 {
+    const ConvGemmPlan p = conv_gemm_plan(job.Cout_p, ConvCall{1, segs.nseg, segs.max_rows, rate, 0, 0});
+    if (job.stat_part && job.stat_nblk * 32 < segs.max_rows * rate) return hipErrorInvalidValue;
     ConvJobs js;
     js.j[0] = job;
     js.j[0].dbg = diag_bits();
@@ -475,15 +462,9 @@ hipError_t launch_conv_gemm(hipStream_t s, const ConvJob &job, const Segs &segs,
     js.segs = segs;
     js.rate = rate;
     js.nt_begin = 0;
-    js.order = knob(ZV_GEMM_ORDER);
-    const int Lmax = segs.max_rows * rate;
-    js.tps = (Lmax + 255) / 256;
-    if (job.stat_part && job.stat_nblk * 32 < Lmax) return hipErrorInvalidValue;
-    const int ng = conv_gemm_groups(job.Cout_p), rts = js.tps * segs.nseg;
-    // (grid.x covers (row tile, group) in the kernel's XCD-aware order: 8 / ng XCDs per group)
-    const dim3 grid((js.order == 1 && (ng == 1 || ng == 2 || ng == 4)) ? round_up(rts, 8 / ng) * ng : rts * ng, 1, 1);
-    const int lds = 4 * (16384 + 18432);
-    return launch_lds(conv_gemm_kernel, grid, dim3(512), lds, s, js);
+    js.order = p.order;
+    js.tps = p.tps;
+    return launch_lds(conv_gemm_kernel, dim3(p.gx, 1, 1), dim3(p.threads), p.lds_bytes, s, js);
 }
 
 }  // namespace zv

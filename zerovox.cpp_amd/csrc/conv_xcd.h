@@ -1,5 +1,5 @@
 // conv_xcd.h — which (row tile, channel group) a workgroup of conv1d_mfma_kernel's loader-wave form (conv.hip) works on when the
-// launch is dealt over the XCDs.  Plain integer arithmetic shared by the kernel, its launcher (launch_cfg) and the host-side
+// launch is dealt over the XCDs.  Plain integer arithmetic shared by the kernel, its launch plan (conv_plan.h) and the host-side
 // test (tests/native/conv_xcd_check.cpp): nothing here needs HIP.
 #pragma once
 

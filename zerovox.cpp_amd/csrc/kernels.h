@@ -10,7 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "voc_plan.h"      // pair_supported, triple_supported, block64_supported, TRIPLE_MAX_DIL
+#include "conv_plan.h"     // the launchers' plans: ConvPrologue, conv_gemm_groups / _tiles / _units, pair_supported, triple_supported, block64_supported, TRIPLE_MAX_DIL
+#include "voc_plan.h"
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -80,16 +81,7 @@ static inline Segs segs_single(int rows, int aux = 0)
 // which is ggml_conv_1d = im2col(F16) + mul_mat (reference ggml/src/ggml.c:3769-3786): operands f16,
 // products exact in f32, f32 accumulation.  Out-of-range taps are zeros *after* the prologue.
 
-enum ConvPrologue : int
-{
-    PRO_RAW_F16 = 0,      // x is already the f16 operand (written by an EPI f16 store)
-    PRO_ACT = 1,          // f16(lrelu(x, slope))            (slope 1 = identity, 0 = relu)
-    PRO_NORM_ACT = 2,     // f16(lrelu(((x - mean_c) * rstd_c) * g_c + b_c, slope))   InstanceNorm/AdaIN
-    PRO_MELNORM = 3,      // f16((x - a_c) / b_c)            (src/hifigan.cpp:242-243)
-    PRO_SUM3_ACT = 4,     // f16(lrelu(((x0 + x1) + x2) * pscale, slope))   MRF mean (src/hifigan.cpp:300-315)
-    PRO_SCALE_ACT = 5     // f16(lrelu(x * pscale, slope))                  MRF mean whose sum the producer already formed
-};
-
+// (ConvPrologue, the `pro` of a job: conv_plan.h)
 struct ConvJob
 {
     // input
@@ -150,10 +142,7 @@ int    conv_pick_ck(int Cin_p, int ck_max = 0);
 void   pack_conv_weight(const uint16_t *w, int K, int IC, int OC, int Cin_p, int Cout_p, int ck, uint16_t *dst);
 // conv_gemm_kernel (batches of wide f16-operand convs): [group of 8 output tiles][unit = (256-chunk, tap, 64-channel block)][k16 step 4]
 // [tile 8][lane][8 halfs]: one unit = 32 KiB contiguous = what one workgroup moves into LDS per step of its K loop.  Only whole
-// groups of 8 tiles are packed (conv_gemm_groups); the remaining tiles run on conv1d_mfma_kernel.
-int    conv_gemm_groups(int Cout_p);
-int    conv_gemm_tiles(int Cout_p);         // output tiles conv_gemm_kernel covers (whole groups of 8, + one leftover tile)
-int    conv_gemm_units(int Cin_p, int K);
+// groups of 8 tiles are packed (conv_plan.h: conv_gemm_groups / conv_gemm_tiles / conv_gemm_units); the remaining tiles run on conv1d_mfma_kernel.
 size_t conv_gemm_weight_halfs(int Cin_p, int Cout_p, int K);
 void   pack_conv_weight_gemm(const uint16_t *w, int K, int IC, int OC, int Cin_p, int Cout_p, uint16_t *dst);
 // all jobs of one launch share the segments, Cout_p and the tile configuration; job.L is ignored (rows come from segs)
@@ -192,7 +181,7 @@ struct PairJobs
     float  *merge_out;           // non-null: store (out_0 + out_1) + out_2 here instead of the jobs' own outputs
     int     ring_off;            // resblock_pair64_kernel: byte offset of the weight ring in LDS (set by the launcher)
 };
-// (voc_plan.h pair_supported: whether a ResBlock conv pair with Cp (padded) channels and K taps can run on the fused kernel)
+// (conv_plan.h pair_supported: whether a ResBlock conv pair with Cp (padded) channels and K taps can run on the fused kernel)
 size_t     pair_weight_halfs(int Cp, int K);
 // GGUF conv weight (ggml ne [K, C, C], f16) -> fused-kernel layout
 void       pack_pair_weight(const uint16_t *w, int K, int C, int Cp, uint16_t *dst);
@@ -238,7 +227,7 @@ struct TripleJobs
     unsigned long long *stamp;   // diagnostic build: the phase-stamp buffer this launch writes (stamp_buffer()), or null
 #endif
 };
-// (voc_plan.h triple_supported / block64_supported: the blocks the two launchers take)
+// (conv_plan.h triple_supported / block64_supported: the blocks the two launchers take)
 // several dilation pairs of a 64-channel block in one launch (resblock_block64_kernel): w1 / w2 in pack_pair_weight_ring layout
 hipError_t launch_block64(hipStream_t s, const TripleJob *jobs, int njobs, const Segs &segs, int rate);
 hipError_t launch_triple(hipStream_t s, const TripleJob *jobs, int njobs, int n_cu, const Segs &segs, int rate);

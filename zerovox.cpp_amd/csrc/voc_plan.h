@@ -1,49 +1,17 @@
 // voc_plan.h — which kernel forms a vocoder call runs (DESIGN.md "Switches"): the decisions of Model::vocode_group as pure host code.
 // Plain integers and booleans in, booleans out; every switch is read here, through knob(), when the call is planned, so a switch set
 // on a live model holds from the next call on (captured graphs are keyed on knob_epoch()).  Shared by the schedule (vocoder.cpp,
-// decoder.cpp, capi.cpp), the launchers (kernels.h includes it: the support predicates) and the host-side test
-// (tests/native/voc_plan_check.cpp): nothing here needs HIP, a Model or a device pointer.
+// decoder.cpp, capi.cpp) and the host-side test (tests/native/voc_plan_check.cpp): nothing here needs HIP, a Model or a device
+// pointer.  What each launcher then does is planned in conv_plan.h, which also says what the fused ResBlock kernels take.
 #pragma once
 
 #include <stddef.h>
 
+#include "conv_plan.h"      // batch_switch / batch_rows, pair_supported / triple_supported / block64_supported, TRIPLE_MAX_DIL
 #include "knobs.h"
 
 namespace zv
 {
-
-// ---- the batch switches: 0 never, 1 batches, 2 always ----
-// "batches" = what the launch picks by itself; where that is a capacity, BATCH_ROWS rows of it (frames for the schedules, rows of a
-// launch for launch_conv).  One threshold for all of them, and not a measured one: no sweep of capacities below it is on record.
-constexpr long BATCH_ROWS = 16384;
-inline bool batch_switch(int value, bool picked_by_itself) { return value != 0 && (value == 2 || picked_by_itself); }
-inline bool batch_rows(long rows) { return rows >= BATCH_ROWS; }
-
-// ---- what the fused ResBlock kernels take (conv1d_mfma.hip) ----
-constexpr int TRIPLE_MAX_DIL = 3;
-// the MFMA loop of the fused kernels walks whole 8-step bodies (CP = 64: also half a body at the end) and at least one
-inline bool pair_supported(int Cp, int K)
-{
-    if (!(Cp == 32 || Cp == 64 || Cp == 128 || Cp == 256) || K < 1 || (K & 1) == 0) return false;
-    const int nsb = (K * (Cp / 16) + 3) >> 2;
-    return nsb >= 2 && (Cp == 64 || (nsb & 1) == 0);
-}
-// a ResBlock (Cp channels, K taps, these dilations) fits the whole-block kernel
-inline bool triple_supported(int Cp, int K, const int *dil, int n_dil)
-{
-    if (Cp != 32 || n_dil < 1 || n_dil > TRIPLE_MAX_DIL || !pair_supported(Cp, K) || (K & 1) == 0) return false;
-    int sumd = 0;
-    for (int d = 0; d < n_dil; d++) sumd += dil[d];
-    return 256 - (K - 1) * (sumd + n_dil) >= 96;          // at least 3/8 of the tile's rows are output
-}
-// the blocks resblock_block64_kernel takes: 64 channels, few taps (the halo of n_dil pairs leaves most of the 256-row tile)
-inline bool block64_supported(int Cp, int K, const int *dil, int n_dil)
-{
-    if (Cp != 64 || K < 3 || (K & 1) == 0 || n_dil < 1 || n_dil > TRIPLE_MAX_DIL) return false;
-    int sumd = 0;
-    for (int d = 0; d < n_dil; d++) sumd += dil[d];
-    return 256 - (K - 1) * (sumd + n_dil) >= 192;          // at least three quarters of the tile's rows are output
-}
 
 // ---- a checkpoint's geometry, filled once by the loader ----
 constexpr int VOC_MAX_STAGES = 8, VOC_MAX_DIL = 8, VOC_BRANCHES = 3;
