@@ -667,7 +667,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
                  o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur ? bt.n_rows * 4 : 0),
                  o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0),      // fitted: the live frame table, written on the device
-                 o_runs = dev.at(!r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0);     // run-shortened decoding: the decoder's run table, likewise
+                 o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0);     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
     M.reserve_batch(bt);
     char *io = (char *)M.io_scratch(dev.size());
     // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan]

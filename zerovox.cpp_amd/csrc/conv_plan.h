@@ -29,12 +29,33 @@ constexpr size_t LDS_DEFAULT = 64 * 1024;      // what a launch gets without ask
 
 inline int plan_round_up(int x, int a) { return (x + a - 1) / a * a; }
 
+// Densely packed decoding (dec_runs.h) hands a launcher ONE segment that holds many utterances back to back.  Such a launch is a
+// batch and must be planned as one: the schedule states the utterance count for the launches it enqueues inside a ConvPackedUtts
+// scope, and a ConvCall built without the field (the launchers' six-value form) takes it from there.  0 everywhere else: the segments
+// are the utterances.  Per thread, like the enqueueing itself; no kernel argument carries it.
+inline int &conv_packed_utts()
+{
+    static thread_local int n = 0;
+    return n;
+}
+struct ConvPackedUtts
+{
+    int saved;
+    explicit ConvPackedUtts(int n) : saved(conv_packed_utts()) { conv_packed_utts() = n; }
+    ~ConvPackedUtts() { conv_packed_utts() = saved; }
+    ConvPackedUtts(const ConvPackedUtts &) = delete;
+    ConvPackedUtts &operator=(const ConvPackedUtts &) = delete;
+};
+
 // the call: jobs of the launch, the segments it covers (Segs::nseg / max_rows), rows per base row, CUs, and the first output tile of a
 // generic conv launch (the tiles before it belong to conv_gemm_kernel)
 struct ConvCall
 {
     int njobs, nseg, max_rows, rate, n_cu, nt_begin;
+    int nutt = conv_packed_utts();      // utterances the segments hold when they are not one each (packed decoding), else 0
 };
+// whether the launch covers several utterances: what the single-utterance forms and the spread map ask
+inline bool conv_call_is_batch(const ConvCall &c) { return c.nseg > 1 || c.nutt > 1; }
 
 // ---- conv_gemm_kernel's tiling (conv_gemm.hip) ----
 // Only whole groups of 8 output tiles are packed for it
@@ -158,7 +179,7 @@ inline bool conv_plan_tiles(ConvPlan &p, bool loader, int MT, int WN, int NT, in
         // (see the kernel and conv_xcd.h) grid.x = 8 XCDs x slots; several segments: no XCD idles for want of channel groups
         p.xcd_ny = p.gy;
         p.xcd_nx = p.gx;
-        p.xcd_spread = c.nseg > 1;
+        p.xcd_spread = conv_call_is_batch(c);
         p.gx = conv_xcd_grid(p.xcd_nx, p.xcd_ny, p.xcd_spread), p.gy = 1;
     }
     // + dil rows: mfma_taps prefetches one tap past the end
@@ -247,7 +268,7 @@ inline ConvPlan conv_plan(const ConvDesc *jobs, const ConvCall &c)
         // ... and of launches the form was built for.  wgs() counts capacity, not utterances: a batch of 32 utterances x 256 phonemes
         // has 512 workgroups of 8 waves for the first conv of a variance predictor, two rounds of a form whose loader waves leave
         // room for one workgroup per CU.  Several segments and more than a round: the ordinary form (measured: DESIGN.md, "Narrow batch convs on all XCDs")
-        const bool batch_rounds = ZV_CONV_BATCH_ROUTE && c.nseg > 1 && wgs(1, 1) > n_cu;
+        const bool batch_rounds = ZV_CONV_BATCH_ROUTE && conv_call_is_batch(c) && wgs(1, 1) > n_cu;
         const int  single_env = knob(ZV_CONV_SINGLE);
         // (two LDS tiles that do not fit a workgroup: the tiled form below, which runs the conv on one)
         if (single_env != 0 && MT == 1 && NT == 1 && ck == 256 && wgs(1, 1) <= 2L * n_cu && !batch_rounds && (jobs[0].Cin_p > 256 || single_env == 2) &&

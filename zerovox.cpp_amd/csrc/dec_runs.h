@@ -99,4 +99,39 @@ ZV_DR_FN void dec_run_block_sum(const double *p, size_t stride, int nb, int gap_
     *sumsq = s2;
 }
 
+// ---- densely packed decoding (DESIGN.md "Densely packed decoding") ----
+// The compact segments of a batch back to back in ONE row space, so that the wide convs tile the batch and not every utterance by
+// itself: utterance u owns the slot [row0_p, row0_p + slot) with
+//     slot(u) = round_up(rows_c[u] + 1, 32),   row0_p[u] = sum of the slots in front of it,   L_p = sum of all slots.
+// Rows [row0_p + rows_c, row0_p + slot) are the GUARD: at least one row, 32 when rows_c is a multiple of 32.  Every f16 conv operand
+// holds zeros there, so a 3-tap conv over the packed rows [0, L_p) sees the zero row on either side of an utterance that the segment
+// ends supply when every utterance is a segment of its own: each output element keeps its accumulation chain.  Every row0_p is a
+// multiple of the statistics block, so an utterance's blocks are the global blocks row0_p / 32 + j.  What the convs leave in guard rows
+// (outputs, partial sums of whole guard blocks) is never read; the last block of an utterance whose rows_c is no multiple of 32 also
+// holds guard rows, and its pair is summed again from the rows that count (dec_pack_tail_pair) where the statistics are finalised.
+constexpr int DEC_PACK_SLOT = 32;
+// (an empty segment takes no rows: it has no row for a neighbour's tap to reach, and the guard in front of it stands)
+ZV_DR_FN int dec_pack_slot(int rows_c) { return rows_c <= 0 ? 0 : (rows_c + DEC_PACK_SLOT) / DEC_PACK_SLOT * DEC_PACK_SLOT; }
+// L_p never exceeds this, whatever the lengths: buffers, statistics partials and grids are sized by it
+ZV_DR_FN long dec_pack_rows_cap(long t_rows, int nseg) { return t_rows + (long)DEC_PACK_SLOT * nseg; }
+
+// The pair (sum, sum of squares) of one channel over the `rows` (1 .. 31) leading rows of a 32-row block, as the conv epilogues add
+// it (mfma_common.h tile_stats_store, conv_gemm.hip): two sequential f64 chains, over the rows 0-3, 8-11, 16-19, 24-27 and over the
+// rows 4-7, 12-15, 20-23, 28-31, a row at or past `rows` counting as zero, then the sum of the two.  x: the channel's value in the
+// block's first row, ld floats from row to row; rows at or past `rows` are not read.
+ZV_DR_FN void dec_pack_tail_pair(const float *x, size_t ld, int rows, double *sum, double *sumsq)
+{
+    double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
+    for (int h = 0; h < 2; h++)
+        for (int r = 0; r < 16; r++)
+        {
+            const int t = 4 * h + (r & 3) + 8 * (r >> 2);
+            const double v = t < rows ? (double)x[(size_t)t * ld] : 0.0;
+            s1[h] += v;
+            s2[h] += v * v;
+        }
+    *sum = s1[0] + s1[1];
+    *sumsq = s2[0] + s2[1];
+}
+
 }  // namespace zv

@@ -1,5 +1,6 @@
 // decoder.cpp — the StyleTTS mel decoder's arena layout and kernel schedule (see model.h).
 #include "schedule.h"
+#include "dec_runs.h"
 
 #include <algorithm>
 #include <cmath>
@@ -10,11 +11,17 @@ namespace zv
 // The decoder's buffers: per-segment vectors and statistics partials, then the [t_rows] activations and f16 operands.
 Model::DecLayout Model::dec_layout(DeviceArena &a, const Batch &bt) const
 {
-    const size_t S = (size_t)bt.nseg, L = bt.t_rows, B = 2 * E(), R = (size_t)dec_.R, CAT = B + R;
+    // Rows and statistics blocks by the packed layout's worst case (dec_runs.h: every utterance's slot ends in up to 32 guard rows),
+    // whether or not a call packs: a layout depends on the batch's shape alone.
+    // Packed decoding keeps the packed copy of `hidden` in xa, which no block writes before decode block 2 and `hidden`'s last
+    // reader, the asr conv, runs ahead of decode block 0 (2 E floats per row against hidden's E).
+    const size_t S = (size_t)bt.nseg, L = (size_t)dec_pack_rows_cap((long)bt.t_rows, bt.nseg), B = 2 * E(), R = (size_t)dec_.R, CAT = B + R;
     DecLayout d{(bt.t_max + 31) / 32, round_up(dec_.fc_out + 64, 64), 2 * (int)CAT + 64};
+    d.rows = (int)L;
+    d.nblk_all = std::max(bt.nseg * d.nblk, (d.rows + 31) / 32);
     d.h = a.take_n<float>(S * d.hs);
     for (float **st : {&d.st_x, &d.st_t, &d.st_y, &d.st_a}) *st = a.take_n<float>(S * d.ss);
-    for (double **p : {&d.part_t, &d.part_o}) *p = a.take_n<double>(S * d.nblk * CAT * 2);
+    for (double **p : {&d.part_t, &d.part_o}) *p = a.take_n<double>((size_t)d.nblk_all * CAT * 2);
     d.cat = a.take_n<float>(L * CAT);
     for (float **x : {&d.t1, &d.sc, &d.x0, &d.xa}) *x = a.take_n<float>(L * B);
     d.asr_t = a.take_n<float>(L * R);
@@ -48,6 +55,10 @@ bool Model::dec_runs_on(const Batch &bt) const
     return !bt.d_frm_live && dbg_layer.kind < 0 && dec_prepass_on(bt) && batch_switch(k, batch_rows((long)bt.t_rows));
 }
 
+// densely packed decoding (dec_runs.h): wherever a batch has a run table.  One utterance has nothing to pack: its rows are tiled as
+// they are either way, and the pass that packs would be one launch more
+bool Model::dec_pack_on(const Batch &bt) const { return bt.d_dec_runs != nullptr && bt.nseg > 1 && knob(ZV_DEC_PACK) != 0; }
+
 // a residual block reaches as far as the longer of its two paths (conv1 -> conv2, the shortcut); the concat joins the encode
 // blocks' path and the asr conv's; the output conv ends the chain
 int Model::dec_reach_frames() const
@@ -69,8 +80,18 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
     const bool runs = bt.d_dec_runs != nullptr;
     if (runs && !dec_runs_on(bt)) fail(ZV_ERR_ARG, "internal: a decoder run table on a schedule that takes none");
     const Segs fr = runs ? Segs{bt.d_dec_runs, bt.nseg, bt.t_max, bt.frm1} : bt.frames();
+    // Densely packed decoding (dec_runs.h): the table's row0 are the utterances' slots in ONE packed row space.  The elementwise and
+    // statistics launches keep the per-utterance table `fr`; every conv runs over the packed rows as the one segment of entry nseg
+    // (`frc`), planned as the batch it is (conv_plan.h ConvPackedUtts), and stores its partial sums by global block, which is where
+    // the finalising launches look (DEC_TAB_PACKED) — the last block of an utterance whose rows are no multiple of 32 apart
+    // (DEC_TAB_CONV_TAIL).  The f16 operands carry zeros in the guard rows; what the convs leave in guard rows is never read.
+    const bool pack = runs && dec_pack_on(bt);
+    const Segs frc = pack ? Segs{bt.d_dec_runs + bt.nseg, 1, lay.rows, Seg{0, 0, 0, 0}} : fr;
+    const ConvPackedUtts packed_utts(pack ? bt.nseg : 0);
+    const int tab_mode = runs ? DEC_TAB_RUNS | (pack ? DEC_TAB_PACKED : 0) : 0, conv_tail = pack ? DEC_TAB_CONV_TAIL : 0;
+    const int nblk_c = pack ? lay.nblk_all : lay.nblk;                  // the blocks a conv's partial sums are laid out by
     const int Ed = (int)E(), B = 2 * Ed, R = dec_.R, CAT = B + R, S = bt.nseg;
-    const size_t L = bt.t_rows;
+    const size_t L = bt.t_rows;                     // (capacity rows: the debug taps', which never pack)
     const int nblk = lay.nblk, hs = lay.hs, ss = lay.ss;
     float *const h = lay.h, *const st_x = lay.st_x, *const st_t = lay.st_t, *const st_y = lay.st_y, *const st_a = lay.st_a;
     double *const part_t = lay.part_t, *const part_o = lay.part_o;
@@ -94,17 +115,20 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
 
     const float rsqrt2 = (float)(1.0 / sqrt(2.0));                       // src/stylettsdec.cpp:146,301
 
-    auto finalize = [&](const double *part, int C, float *stat, int c_off) {
+    // xconv: the tensor whose partial sums a conv stored in `part` (null: an elementwise launch stored them)
+    auto finalize = [&](const double *part, int C, float *stat, int c_off, const float *xconv = nullptr, int ldxc = 0) {
         ZV_LAUNCH("dec_in_stats", 16.0 * S * nblk * C, 4.0 * S * nblk * C,
-                  launch_stats_finalize(stream(), part, nblk, C, 1e-5f, stat, ss, c_off, fr, 1, runs));
+                  launch_stats_finalize(stream(), part, nblk, C, 1e-5f, stat, ss, c_off, fr, 1, tab_mode | (xconv ? conv_tail : 0), xconv, ldxc));
     };
     // make `j` read lrelu(norm(x)) with x's statistics still in `part` (channels [0, Cpart)); stores them in `stat`
+    // from_conv: a conv stored x and `part` (else an elementwise launch did)
     auto norm_input = [&](ConvJob &j, const float *x, int ldx, int C, const double *part, int Cpart, float *stat, const float *g,
-                          const float *b, int gb_seg, _Float16 *op16, _Float16 *raw16 = nullptr) {
+                          const float *b, int gb_seg, bool from_conv, _Float16 *op16, _Float16 *raw16 = nullptr) {
         if (prepass)
         {
             ZV_LAUNCH("dec_norm_operand", 6.0 * Ld * C, 8.0 * Ld * C,
-                      launch_norm_act_f16(stream(), x, ldx, C, part, nblk, Cpart, 1e-5f, stat, ss, g, b, gb_seg, 0.2f, op16, C, fr, raw16, runs));
+                      launch_norm_act_f16(stream(), x, ldx, C, part, nblk, Cpart, 1e-5f, stat, ss, g, b, gb_seg, 0.2f, op16, C, fr, raw16,
+                                          tab_mode | (from_conv ? conv_tail : 0)));
             j.x0 = op16;
             j.ldx = C;
             j.pro = PRO_RAW_F16;
@@ -125,14 +149,20 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
     };
 
     // InstanceNorm statistics of the stage input (it comes from the encoder or the host, not from a conv of ours)
-    ZV_LAUNCH("dec_in_stats", 4.0 * Ld * Ed, 3.0 * Ld * Ed, launch_stats_partial(stream(), d_hidden, Ed, Ed, part_o, nblk, fr, 1));
+    const float *hidden = d_hidden;
+    if (pack)
+    {
+        ZV_LAUNCH("dec_pack_rows", 8.0 * Ld * Ed, 0.0, launch_dec_pack_rows(stream(), d_hidden, xa, Ed, fr, bt.frames_cap()));
+        hidden = xa;
+    }
+    ZV_LAUNCH("dec_in_stats", 4.0 * Ld * Ed, 3.0 * Ld * Ed, launch_stats_partial(stream(), hidden, Ed, Ed, part_o, nblk, fr, 1, pack));
 
     // one residual block: IN/AdaIN -> lrelu -> conv1 -> IN/AdaIN -> lrelu -> conv2 -> (+ shortcut) / sqrt2.
     // The partial sums of x's statistics are in part_o (channels [0, Cpart) of x; the others are final in st_in already);
     // the block leaves the partial sums of its output in part_o again when want_stats.  gb_seg: per-segment stride of the
     // affine vectors (0 for the encode blocks' shared InstanceNorm weights, hs for the decode blocks' AdaIN vectors).
     int blk_no = 0;              // 0,1: encode blocks; 2..6: decode blocks (dbg_layer.index)
-    auto block = [&](const DecBlk &b, const float *x, int ldx, int Cpart, float *st_in, const float *g1, const float *b1,
+    auto block = [&](const DecBlk &b, const float *x, int ldx, int Cpart, bool x_from_conv, float *st_in, const float *g1, const float *b1,
                      const float *g2, const float *b2, int gb_seg, float *out, int ldo, bool want_stats) {
         const bool dbg_here = dbg_layer.kind == 2 && dbg_layer.index == blk_no && !dbg_layer.done;
         blk_no++;
@@ -142,6 +172,7 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
             dbg_inject(const_cast<float *>(x), ldx, b.cin, L);
             ZV_HIP(launch_stats_partial(stream(), x, ldx, b.cin, part_o, nblk, fr, 1));
             Cpart = b.cin;
+            x_from_conv = false;
         }
         const float *res = x;
         int ldres = ldx;
@@ -150,10 +181,10 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
         {
             ConvJob j = job(b.conv1);
             // (a learned shortcut reads f16(x): with the pre-pass on, that operand is written by the same pass)
-            norm_input(j, x, ldx, b.cin, part_o, Cpart, st_in, g1, b1, gb_seg, xa16, b.learned_sc ? xr16 : nullptr);
+            norm_input(j, x, ldx, b.cin, part_o, Cpart, st_in, g1, b1, gb_seg, x_from_conv, xa16, b.learned_sc ? xr16 : nullptr);
             j.out = t1;
             j.stat_part = part_t;
-            j.stat_nblk = nblk;
+            j.stat_nblk = nblk_c;
             j.stat_C = b.conv1.Cout;
             jj[nj++] = j;
         }
@@ -180,13 +211,13 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
                 flops += sf;
             }
             else
-                conv(&j, 1, fr, 1, "dec_conv", sb, sf);
+                conv(&j, 1, frc, 1, "dec_conv", sb, sf);
         }
-        conv(jj, nj, fr, 1, "dec_conv", bytes, flops);
+        conv(jj, nj, frc, 1, "dec_conv", bytes, flops);
         const int Cm = b.conv1.Cout;
         {
             ConvJob j = job(b.conv2);
-            norm_input(j, t1, b.conv1.Cout_p, Cm, part_t, Cm, st_t, g2, b2, gb_seg, t16);
+            norm_input(j, t1, b.conv1.Cout_p, Cm, part_t, Cm, st_t, g2, b2, gb_seg, true, t16);
             j.res = res;
             j.ldres = ldres;
             j.escale = rsqrt2;
@@ -195,10 +226,10 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
             if (want_stats)
             {
                 j.stat_part = part_o;
-                j.stat_nblk = nblk;
+                j.stat_nblk = nblk_c;
                 j.stat_C = b.cout;
             }
-            conv(&j, 1, fr, 1, "dec_conv", conv_bytes(Ld, Cm, b.cout, 3, true), conv_flops(Ld, Cm, b.cout, 3));
+            conv(&j, 1, frc, 1, "dec_conv", conv_bytes(Ld, Cm, b.cout, 3, true), conv_flops(Ld, Cm, b.cout, 3));
         }
         if (dbg_here) dbg_extract(out, ldo, b.cout, L);
     };
@@ -222,23 +253,23 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
     }
 
     // encode0 / encode1: ResBlk1d with affine InstanceNorm                         (src/stylettsdec.cpp:69-149,373-374)
-    block(dec_.enc[0], d_hidden, Ed, Ed, st_x, dec_.enc[0].n1w, dec_.enc[0].n1b, dec_.enc[0].n2w, dec_.enc[0].n2b, 0, x0, B, true);
-    block(dec_.enc[1], x0, B, B, st_y, dec_.enc[1].n1w, dec_.enc[1].n1b, dec_.enc[1].n2w, dec_.enc[1].n2b, 0, cat, CAT, true);
+    block(dec_.enc[0], hidden, Ed, Ed, false, st_x, dec_.enc[0].n1w, dec_.enc[0].n1b, dec_.enc[0].n2w, dec_.enc[0].n2b, 0, x0, B, true);
+    block(dec_.enc[1], x0, B, B, true, st_y, dec_.enc[1].n1w, dec_.enc[1].n1b, dec_.enc[1].n2w, dec_.enc[1].n2b, 0, cat, CAT, true);
 
     // asr_res = IN_affine(conv1x1(enc_seq) + b) written straight into the concat buffer      (:382-404)
     if (dbg_layer.done) return;
     {
         ConvJob j = job(dec_.asr0);
-        j.x0 = d_hidden;
+        j.x0 = hidden;
         j.ldx = Ed;
         j.out = asr_t;
         j.stat_part = part_t;
-        j.stat_nblk = nblk;
+        j.stat_nblk = nblk_c;
         j.stat_C = R;
-        conv(&j, 1, fr, 1, "dec_conv", conv_bytes(Ld, Ed, R, 1, false), conv_flops(Ld, Ed, R, 1));
-        finalize(part_t, R, st_a, 0);
+        conv(&j, 1, frc, 1, "dec_conv", conv_bytes(Ld, Ed, R, 1, false), conv_flops(Ld, Ed, R, 1));
+        finalize(part_t, R, st_a, 0, asr_t, R);
         ZV_LAUNCH("dec_norm_apply", 8.0 * Ld * R, 3.0 * Ld * R,
-                  launch_norm_apply(stream(), asr_t, R, R, st_a, ss, dec_.asr1w, dec_.asr1b, cat + B, CAT, part_t, nblk, fr));
+                  launch_norm_apply(stream(), asr_t, R, R, st_a, ss, dec_.asr1w, dec_.asr1b, cat + B, CAT, part_t, nblk, fr, pack));
         finalize(part_t, R, st_x, B);            // statistics of the concat's asr columns: final for decode0..2
         if (dbg_layer.kind == ZV_LAYER_DEC_ASR_RES)
         {
@@ -258,7 +289,7 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
     for (int i = 0; i < 5; i++)
     {
         const DecBlk &b = dec_.dec[i];
-        block(b, cur, ldc, cparts[i], sts[i], h + b.g1, h + b.g1 + b.cin, h + b.g2, h + b.g2 + b.cout, hs, outs[i], ldos[i], i < 4);
+        block(b, cur, ldc, cparts[i], true, sts[i], h + b.g1, h + b.g1 + b.cin, h + b.g2, h + b.g2 + b.cout, hs, outs[i], ldos[i], i < 4);
         cur = outs[i];
         ldc = ldos[i];
     }
@@ -271,7 +302,7 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
         j.out = runs ? lay.mel_c : d_mel;
         j.ldo = dec_.M;
         if (dbg_layer.kind == ZV_LAYER_DEC_TO_OUT) dbg_inject(const_cast<float *>(cur), ldc, Ed, L);
-        conv(&j, 1, fr, 1, "dec_conv", conv_bytes(Ld, Ed, dec_.M, 1, false), conv_flops(Ld, Ed, dec_.M, 1));
+        conv(&j, 1, frc, 1, "dec_conv", conv_bytes(Ld, Ed, dec_.M, 1, false), conv_flops(Ld, Ed, dec_.M, 1));
         if (dbg_layer.kind == ZV_LAYER_DEC_TO_OUT) dbg_extract(d_mel, dec_.M, dec_.M, L);
     }
     // all T rows of every utterance's mel from the rows computed: the vocoder sees the mel it always saw

@@ -172,7 +172,7 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
         ZV_LAUNCH("enc_live_frames", 36.0 * bt.nseg, 0.0, launch_live_frames(stream(), d_nframes, bt.d_frm_live, fr));
     // run-shortened decoding: the decoder's run table, from the same counts
     if (bt.d_dec_runs)
-        ZV_LAUNCH("enc_dec_runs", 36.0 * bt.nseg, 0.0, launch_dec_runs(stream(), d_nframes, bt.d_dec_runs, fr, dec_reach_frames()));
+        ZV_LAUNCH("enc_dec_runs", 36.0 * bt.nseg, 0.0, launch_dec_runs(stream(), d_nframes, bt.d_dec_runs, fr, dec_reach_frames(), dec_pack_on(bt)));
     return t;
 }
 

@@ -254,14 +254,24 @@ hipError_t launch_out_conv(hipStream_t s, const OutConvArgs &a);
 // and stores (mean, rstd).  The 32-row blocks do not depend on any tile shape, so neither do the statistics.
 //   part[((u * nblk) + blk) * C + c] = double2(sum, sumsq);  nblk >= ceil(max_rows * rate / 32)
 //   stat[u * stat_seg + 2 * (c_off + c) + {0, 1}] = mean, rstd
-hipError_t launch_stats_partial(hipStream_t s, const float *x, int ldx, int C, double *part, int nblk, const Segs &segs, int rate);
-// dec_runs (here and in launch_norm_act_f16): segs is a decoder run table (launch_dec_runs) — behind block seg.aux - 1 that block's
-// pair is added seg.pad more times and the sums are divided by rows + 32 * pad (dec_runs.h); rate must be 1
+// packed (here and in launch_norm_apply; rate must be 1): segs is the run table of densely packed decoding (dec_runs.h), whose row0
+// are multiples of 32 in ONE packed row space — segment u's blocks are then part[(row0 / 32 + blk) * C + c], where a conv over the
+// packed rows as one segment stores them too, and nblk only bounds the blocks of one segment
+hipError_t launch_stats_partial(hipStream_t s, const float *x, int ldx, int C, double *part, int nblk, const Segs &segs, int rate,
+                                int packed = 0);
+// dec_runs (here and in launch_norm_act_f16), a sum of:
+//   DEC_TAB_RUNS        segs is a decoder run table (launch_dec_runs) — behind block seg.aux - 1 that block's pair is added seg.pad
+//                       more times and the sums are divided by rows + 32 * pad (dec_runs.h); rate must be 1
+//   DEC_TAB_PACKED      ... of densely packed decoding: the blocks of `part` as under `packed` above
+//   DEC_TAB_CONV_TAIL   ... and `part` was stored by a conv over the packed rows as one segment, whose last block of a segment with
+//                       rows % 32 != 0 also counts guard rows: that block's pair is summed again from x (the tensor the conv
+//                       stored, ldx floats per row, channel c in column c) in the epilogue's order — dec_pack_tail_pair
+constexpr int DEC_TAB_RUNS = 1, DEC_TAB_PACKED = 2, DEC_TAB_CONV_TAIL = 4;
 hipError_t launch_stats_finalize(hipStream_t s, const double *part, int nblk, int C, float eps, float *stat, int stat_seg,
-                                 int c_off, const Segs &segs, int rate, int dec_runs = 0);
+                                 int c_off, const Segs &segs, int rate, int dec_runs = 0, const float *x = nullptr, int ldx = 0);
 // y[t][c] = ((x - mean) * rstd) * g[c] + b[c]; `part` (may be null) receives the partial sums of y
 hipError_t launch_norm_apply(hipStream_t s, const float *x, int ldx, int C, const float *stat, int stat_seg, const float *g,
-                             const float *b, float *y, int ldy, double *part, int nblk, const Segs &segs);
+                             const float *b, float *y, int ldy, double *part, int nblk, const Segs &segs, int packed = 0);
 
 // out[i] = f16(lrelu(((x0[i] + x1[i]) + x2[i]) * pscale, slope)) over n contiguous elements (x1 = x2 = null: x0[i] * pscale): the
 // operand pre-pass of the upsample convs that run on conv_gemm_kernel
@@ -270,6 +280,7 @@ hipError_t launch_act_f16(hipStream_t s, const float *x0, const float *x1, const
 // once (PRO_RAW_F16 consumers).  Channels below Cpart get their statistics from `part` (and store them in `stat`), the
 // others read `stat`.  g / b: per-segment stride gb_seg (0 = shared).  yraw (may be null, same layout as y): f16(x) itself — the
 // operand of the block's 1x1 shortcut conv (reference src/stylettsdec.cpp:132-140,287-296 converts x to f16 in its im2col).
+// DEC_TAB_PACKED: y and yraw also get zeros in the guard rows [rows, dec_pack_slot(rows)) of every segment's slot.
 hipError_t launch_norm_act_f16(hipStream_t s, const float *x, int ldx, int C, const double *part, int nblk, int Cpart, float eps,
                                float *stat, int stat_seg, const float *ga, const float *be, int gb_seg, float slope, void *y,
                                int ldy, const Segs &segs, void *yraw = nullptr, int dec_runs = 0);
@@ -371,9 +382,15 @@ hipError_t launch_voc_run_fill(hipStream_t s, float *x, const Segs &runs, int ra
 //   runs[u] = {row0, T, 0, 0}                                                        otherwise
 // Every decoder launch takes its extents from this table; the statistics add the dropped blocks back (launch_stats_finalize).  No
 // host round trip: one graph replays for any lengths.
-hipError_t launch_dec_runs(hipStream_t s, const int32_t *n_frames, Seg *runs, const Segs &frames, int R);
-// mel[row0 + t][0 .. M) = mel_c[row0 + dec_run_compact_row(t)][0 .. M) for all T rows of every segment of `frames`: the compact
-// mel (the rows the decoder computed, in place at the segment's start) expanded to the capacity.  mel_c and mel must not overlap
+// packed (densely packed decoding, dec_runs.h): runs[u].row0 = row0_p[u], the sum of dec_pack_slot(rows_c) over the segments in front
+// of u, and runs has one entry more: runs[nseg] = {0, L_p, 0, 0}, the packed rows as the ONE segment the convs run over
+hipError_t launch_dec_runs(hipStream_t s, const int32_t *n_frames, Seg *runs, const Segs &frames, int R, int packed = 0);
+// xp[runs[u].row0 + t][0 .. C) = x[frames[u].row0 + t][0 .. C) for t < runs[u].rows and zeros for the guard rows up to
+// dec_pack_slot(rows): a tensor of the capacity layout into the packed one.  C a multiple of 4; x and xp must not overlap
+hipError_t launch_dec_pack_rows(hipStream_t s, const float *x, float *xp, int C, const Segs &runs, const Segs &frames);
+// mel[row0 + t][0 .. M) = mel_c[runs[u].row0 + dec_run_compact_row(t)][0 .. M) for all T rows of every segment of `frames`: the
+// compact mel (the rows the decoder computed: at the segment's own row0, or at its slot of the packed rows) expanded to the
+// capacity.  mel_c and mel must not overlap
 hipError_t launch_dec_run_expand(hipStream_t s, const float *mel_c, float *mel, int M, const Segs &runs, const Segs &frames);
 
 }  // namespace zv

@@ -28,7 +28,8 @@ namespace zv
     X(ZV_CONV_STREAM, 1)       /* 0 never, 1 batches, 2 always: memory-bound 3-tap convs (the last upsample convs) on conv_stream_kernel */ \
     X(ZV_VOC_RUNS, 1)          /* 0 never, 1 batches, 2 always: the unfitted vocoder skips the repeats of a run of bit-identical mel rows (same bits) */ \
     X(ZV_DEC_RUNS, 1)          /* 0 never, 1 batches, 2 always: the unfitted decoder computes a padded utterance's constant rows once (same bits) */ \
-    X(ZV_UP_GEMM, 1)           /* 0 never, 1 batches, 2 always: the wide upsample convs behind an f16 operand pass on conv_gemm_kernel */ \
+    X(ZV_DEC_PACK, 1)          /* 1: a run-shortened decoder of a batch packs the utterances' rows densely, so its wide convs tile the batch and not each utterance (same bits); 0: every utterance a segment of its own */ \
+    X(ZV_UP_GEMM, 1)          /* 0 never, 1 batches, 2 always: the wide upsample convs behind an f16 operand pass on conv_gemm_kernel */ \
     X(ZV_GEMM_ORDER, 2)        /* conv_gemm_kernel's workgroup order: 0 plain (group fastest), 2 the 9-tile group first */ \
     X(ZV_PAIR_MT, 0)           /* 2 / 3 / 4: tile height of the pair kernels */                                                       \
     X(ZV_CONV_XCD, 1)          /* single-utterance conv launches: a channel group's row tiles all on one XCD (its L2 holds the group's weights; several segments and fewer than 8 groups: on 8 / ny of them, conv_xcd.h); 0 = row tiles dealt over the XCDs */ \

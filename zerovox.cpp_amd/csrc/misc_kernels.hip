@@ -35,14 +35,22 @@ typedef float floatx16m __attribute__((ext_vector_type(16)));
 // elsewhere, or by norm_apply_kernel for its own output; (2) stats_finalize_kernel adds a segment's blocks in block
 // order.  The reference subtracts the f32 mean before squaring (two passes); sum x^2 - (sum x)^2 / L in f64 is the
 // same quantity to ~1e-12 relative, far inside the f32 rounding of the reference's own terms.
+// first block of segment useg in `part`: its own run of nblk blocks, or — densely packed decoding (dec_runs.h), where the conv
+// epilogues store by the block of the ONE packed segment — the global block its slot begins at
+__device__ __forceinline__ size_t part_block0(const Seg &sg, int useg, int nblk, int packed)
+{
+    return packed ? (size_t)(sg.row0 / DEC_RUN_BLOCK) : (size_t)useg * nblk;
+}
+
 __global__ __launch_bounds__(256) void stats_partial_kernel(const float *__restrict__ x, int ldx, int C,
-                                                            double *__restrict__ part, int nblk, const Segs segs, int rate)
+                                                            double *__restrict__ part, int nblk, const Segs segs, int rate, int packed)
 {
     __shared__ double red[2][4][64];
     const int useg = blockIdx.z, blk = blockIdx.y;
     const Seg sg = seg_at(segs, useg);
     const int L = sg.rows * rate;
     if (blk * 32 >= L) return;
+    const size_t blk0 = part_block0(sg, useg, nblk, packed);
     const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cl;
     const float *xs = x + (size_t)sg.row0 * rate * ldx;
@@ -63,25 +71,38 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(const float *__restr
     {
         const double a = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
         const double b = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
-        *(double2 *)(part + (((size_t)useg * nblk + blk) * C + c) * 2) = make_double2(a, b);
+        *(double2 *)(part + ((blk0 + blk) * C + c) * 2) = make_double2(a, b);
     }
 }
 
-hipError_t launch_stats_partial(hipStream_t s, const float *x, int ldx, int C, double *part, int nblk, const Segs &segs, int rate)
+hipError_t launch_stats_partial(hipStream_t s, const float *x, int ldx, int C, double *part, int nblk, const Segs &segs, int rate, int packed)
 {
     const int nb = (segs.max_rows * rate + 31) / 32;
-    if (nb > nblk || segs.nseg < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(stats_partial_kernel, dim3((C + 63) / 64, nb, segs.nseg), dim3(256), 0, s, x, ldx, C, part, nblk, segs, rate);
+    if (nb > nblk || segs.nseg < 1 || (packed && (!segs.tab || rate != 1))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stats_partial_kernel, dim3((C + 63) / 64, nb, segs.nseg), dim3(256), 0, s, x, ldx, C, part, nblk, segs, rate, packed);
     return hipGetLastError();
 }
 
 // (mean, rstd) of one channel of one segment from its blocks' partial sums, added in block order.  A decoder run table's segment
 // (gap_at, G: dec_runs.h) stands for L rows, 32 G more than its nb blocks hold: the G blocks behind block gap_at - 1 were not
 // computed and hold that block's pair, added where they stood.  G = 0: the plain sum.
-__device__ __forceinline__ float2 stats_from_partials(const double *__restrict__ p, int C, int nb, int L, float eps, int gap_at = 0, int G = 0)
+// xtail (packed decoding, the partial sums stored by a conv over the packed rows): the segment's last block also holds guard rows
+// when its nb blocks are not all whole, so that block's pair is summed from the `tail` rows of x that count, in the conv epilogue's
+// order (dec_pack_tail_pair), and added where the stored pair would be: last, behind the whole blocks and the gap.
+__device__ __forceinline__ float2 stats_from_partials(const double *__restrict__ p, int C, int nb, int L, float eps, int gap_at = 0, int G = 0,
+                                                      const float *__restrict__ xtail = nullptr, size_t ldx = 0, int tail = 0)
 {
     double s1, s2;
-    dec_run_block_sum(p, (size_t)C * 2, nb, gap_at, G, &s1, &s2);
+    if (xtail && tail > 0)
+    {
+        double t1, t2;
+        dec_run_block_sum(p, (size_t)C * 2, nb - 1, gap_at, G, &s1, &s2);
+        dec_pack_tail_pair(xtail, ldx, tail, &t1, &t2);
+        s1 += t1;
+        s2 += t2;
+    }
+    else
+        dec_run_block_sum(p, (size_t)C * 2, nb, gap_at, G, &s1, &s2);
     const double mean = s1 / (double)L;
     double var = s2 / (double)L - mean * mean;
     var = var > 0.0 ? var : 0.0;
@@ -91,13 +112,13 @@ __device__ __forceinline__ float2 stats_from_partials(const double *__restrict__
 // the gap of segment useg when segs is a decoder run table: (blocks in front of it, blocks dropped), else (0, 0)
 __device__ __forceinline__ int2 dec_run_gap(const Segs &segs, int useg, int dec_runs)
 {
-    if (!dec_runs || !segs.tab) return make_int2(0, 0);
+    if (!(dec_runs & DEC_TAB_RUNS) || !segs.tab) return make_int2(0, 0);
     return make_int2(__builtin_amdgcn_readfirstlane(segs.tab[useg].aux), __builtin_amdgcn_readfirstlane(segs.tab[useg].pad));
 }
 
 __global__ __launch_bounds__(64) void stats_finalize_kernel(const double *__restrict__ part, int nblk, int C, float eps,
                                                             float *__restrict__ stat, int stat_seg, int c_off,
-                                                            const Segs segs, int rate, int dec_runs)
+                                                            const Segs segs, int rate, int dec_runs, const float *__restrict__ x, int ldx)
 {
     const int useg = blockIdx.y;
     const Seg sg = seg_at(segs, useg);
@@ -105,18 +126,22 @@ __global__ __launch_bounds__(64) void stats_finalize_kernel(const double *__rest
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= C || L <= 0) return;
     const int2 gap = dec_run_gap(segs, useg, dec_runs);
-    const float2 mr = stats_from_partials(part + ((size_t)useg * nblk * C + c) * 2, C, (L + 31) >> 5, L + DEC_RUN_BLOCK * gap.y, eps, gap.x, gap.y);
+    const bool tail = (dec_runs & DEC_TAB_CONV_TAIL) && (L & 31);
+    const float2 mr = stats_from_partials(part + (part_block0(sg, useg, nblk, dec_runs & DEC_TAB_PACKED) * C + c) * 2, C, (L + 31) >> 5,
+                                          L + DEC_RUN_BLOCK * gap.y, eps, gap.x, gap.y,
+                                          tail ? x + ((size_t)sg.row0 + (L & ~31)) * ldx + c : nullptr, (size_t)ldx, L & 31);
     float *o = stat + (size_t)useg * stat_seg + 2 * (c_off + c);
     o[0] = mr.x;
     o[1] = mr.y;
 }
 
 hipError_t launch_stats_finalize(hipStream_t s, const double *part, int nblk, int C, float eps, float *stat, int stat_seg,
-                                 int c_off, const Segs &segs, int rate, int dec_runs)
+                                 int c_off, const Segs &segs, int rate, int dec_runs, const float *x, int ldx)
 {
     if (segs.nseg < 1 || (dec_runs && (!segs.tab || rate != 1))) return hipErrorInvalidValue;
+    if ((dec_runs & DEC_TAB_CONV_TAIL) && (!(dec_runs & DEC_TAB_PACKED) || !x)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(stats_finalize_kernel, dim3((C + 63) / 64, segs.nseg), dim3(64), 0, s, part, nblk, C, eps, stat, stat_seg,
-                       c_off, segs, rate, dec_runs);
+                       c_off, segs, rate, dec_runs, x, ldx);
     return hipGetLastError();
 }
 
@@ -126,7 +151,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float *__restrict
                                                          const float *__restrict__ stat, int stat_seg,
                                                          const float *__restrict__ g, const float *__restrict__ b,
                                                          float *__restrict__ y, int ldy, double *__restrict__ part, int nblk,
-                                                         const Segs segs)
+                                                         const Segs segs, int packed)
 {
     __shared__ double red[2][4][64];
     const int useg = blockIdx.z, blk = blockIdx.y;
@@ -165,17 +190,17 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float *__restrict
     {
         const double a = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
         const double q = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
-        *(double2 *)(part + (((size_t)useg * nblk + blk) * C + c) * 2) = make_double2(a, q);
+        *(double2 *)(part + ((part_block0(sg, useg, nblk, packed) + blk) * C + c) * 2) = make_double2(a, q);
     }
 }
 
 hipError_t launch_norm_apply(hipStream_t s, const float *x, int ldx, int C, const float *stat, int stat_seg, const float *g,
-                             const float *b, float *y, int ldy, double *part, int nblk, const Segs &segs)
+                             const float *b, float *y, int ldy, double *part, int nblk, const Segs &segs, int packed)
 {
     const int nb = (segs.max_rows + 31) / 32;
-    if ((part && nb > nblk) || segs.nseg < 1) return hipErrorInvalidValue;
+    if ((part && nb > nblk) || segs.nseg < 1 || (packed && !segs.tab)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(norm_apply_kernel, dim3((C + 63) / 64, nb, segs.nseg), dim3(256), 0, s, x, ldx, C, stat, stat_seg, g, b, y,
-                       ldy, part, nblk, segs);
+                       ldy, part, nblk, segs, packed);
     return hipGetLastError();
 }
 
@@ -209,7 +234,10 @@ __global__ __launch_bounds__(256) void norm_act_f16_kernel(const float *__restri
             if (c < Cpart)
             {
                 const int2 gap = dec_run_gap(segs, useg, dec_runs);
-                mr = stats_from_partials(part + ((size_t)useg * nblk * Cpart + c) * 2, Cpart, (L + 31) >> 5, L + DEC_RUN_BLOCK * gap.y, eps, gap.x, gap.y);
+                const bool tail = (dec_runs & DEC_TAB_CONV_TAIL) && (L & 31);
+                mr = stats_from_partials(part + (part_block0(sg, useg, nblk, dec_runs & DEC_TAB_PACKED) * Cpart + c) * 2, Cpart, (L + 31) >> 5,
+                                         L + DEC_RUN_BLOCK * gap.y, eps, gap.x, gap.y,
+                                         tail ? x + ((size_t)sg.row0 + (L & ~31)) * ldx + c : nullptr, (size_t)ldx, L & 31);
                 st[0] = mr.x;
                 st[1] = mr.y;
             }
@@ -233,6 +261,18 @@ __global__ __launch_bounds__(256) void norm_act_f16_kernel(const float *__restri
     _Float16 *ys = y + (size_t)sg.row0 * ldy + c;
     _Float16 *yr = yraw ? yraw + (size_t)sg.row0 * ldy + c : nullptr;      // f16(x): the operand of a block's 1x1 shortcut conv
     typedef _Float16 half4v __attribute__((ext_vector_type(4)));
+    // densely packed decoding: zeros in the slot's guard rows [L, dec_pack_slot(L)) of every operand written here — the zero row a
+    // 3-tap conv over the packed rows finds on either side of an utterance.  On every call (the buffers keep nothing between calls),
+    // by the segment's first workgroup of each 64 channels
+    if ((dec_runs & DEC_TAB_PACKED) && blockIdx.z == 0)
+    {
+        const half4v z = {0, 0, 0, 0};
+        for (int t = L + rl; t < dec_pack_slot(L); t += 16)
+        {
+            *(half4v *)(ys + (size_t)t * ldy) = z;
+            if (yr) *(half4v *)(yr + (size_t)t * ldy) = z;
+        }
+    }
     // the rows of a segment are dealt over gridDim.z workgroups in chunks of 128 (every one of them finalises the statistics of
     // its 64 channels for itself: the same arithmetic, the same values); eight 16-byte loads per thread in flight
     for (int t0 = blockIdx.z * 128 + rl; t0 < L; t0 += 128 * gridDim.z)
@@ -1700,19 +1740,67 @@ hipError_t launch_voc_run_fill(hipStream_t s, float *x, const Segs &runs, int ra
 
 // ---------------------------------------------------------------------------------------------------
 // Run-shortened decoding (kernels.h: launch_dec_runs, dec_runs.h).  The table: one thread per segment, from the regulator's counts.
-__global__ __launch_bounds__(64) void dec_runs_kernel(const int32_t *__restrict__ n_frames, Seg *__restrict__ runs, const Segs frames, int R)
+// ONE wave walks the segments 64 at a time.  packed (dec_runs.h "densely packed decoding"): row0 is the start of the segment's slot
+// in the packed row space — the wave's running sum of the slots in front of it — and entry nseg is the packed space as one segment
+__global__ __launch_bounds__(64) void dec_runs_kernel(const int32_t *__restrict__ n_frames, Seg *__restrict__ runs, const Segs frames, int R,
+                                                      int packed)
 {
-    const int u = blockIdx.x * 64 + threadIdx.x;
-    if (u >= frames.nseg) return;
-    const Seg cap = frames.tab ? frames.tab[u] : frames.one;
-    const DecRun r = dec_run(n_frames[u], cap.rows, R);
-    *(int4 *)(runs + u) = make_int4(cap.row0, r.rows_c, r.gap_at, r.G);
+    const int lane = threadIdx.x;
+    int done = 0;                                   // packed rows in front of this round's segments (the same in every lane)
+    for (int u0 = 0; u0 < frames.nseg; u0 += 64)
+    {
+        const int u = u0 + lane;
+        const bool live = u < frames.nseg;
+        const Seg cap = frames.tab ? frames.tab[live ? u : 0] : frames.one;
+        const DecRun r = dec_run(live ? n_frames[u] : 0, cap.rows, R);
+        const int slot = live && packed ? dec_pack_slot(r.rows_c) : 0;
+        int incl = slot;                            // inclusive scan of the slots over the wave
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1)
+        {
+            const int v = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += v;
+        }
+        if (live) *(int4 *)(runs + u) = make_int4(packed ? done + incl - slot : cap.row0, r.rows_c, r.gap_at, r.G);
+        done += __shfl(incl, 63, 64);
+    }
+    if (packed && lane == 0) *(int4 *)(runs + frames.nseg) = make_int4(0, done, 0, 0);
 }
 
-hipError_t launch_dec_runs(hipStream_t s, const int32_t *n_frames, Seg *runs, const Segs &frames, int R)
+hipError_t launch_dec_runs(hipStream_t s, const int32_t *n_frames, Seg *runs, const Segs &frames, int R, int packed)
 {
     if (frames.nseg < 1 || !n_frames || !runs || R < 0 || (!frames.tab && frames.nseg != 1)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dec_runs_kernel, dim3((frames.nseg + 63) / 64), dim3(64), 0, s, n_frames, runs, frames, R);
+    hipLaunchKernelGGL(dec_runs_kernel, dim3(1), dim3(64), 0, s, n_frames, runs, frames, R, packed);
+    return hipGetLastError();
+}
+
+// densely packed decoding: rows [0, rows_c) of every segment from the capacity layout (`frames`) into the segment's slot of the
+// packed layout (`runs`: row0 = the slot's first row), zeros in the slot's guard rows.  C floats per row, a multiple of 4; grid.x
+// walks a slot in chunks of 1 024 float4
+__global__ __launch_bounds__(256) void dec_pack_rows_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst, int C4,
+                                                            const Seg *__restrict__ runs, const Segs frames)
+{
+    const Seg cap = seg_at(frames, blockIdx.y);
+    const int4 e = *(const int4 *)(runs + blockIdx.y);
+    const int row0_p = __builtin_amdgcn_readfirstlane(e.x), rows_c = __builtin_amdgcn_readfirstlane(e.y);
+    const long n = (long)dec_pack_slot(rows_c) * C4, live = (long)rows_c * C4;
+    const float4 *sp = src + (size_t)cap.row0 * C4;
+    float4 *dp = dst + (size_t)row0_p * C4;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+    {
+        const long i = (long)blockIdx.x * 1024 + k * 256 + threadIdx.x;
+        if (i >= n) continue;
+        dp[i] = i < live ? sp[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+hipError_t launch_dec_pack_rows(hipStream_t s, const float *x, float *xp, int C, const Segs &runs, const Segs &frames)
+{
+    if (frames.nseg < 1 || frames.nseg != runs.nseg || frames.max_rows < 1 || C < 4 || (C & 3) || !runs.tab || !x || !xp) return hipErrorInvalidValue;
+    const long per_slot = (long)dec_pack_slot(frames.max_rows) * (C / 4);
+    hipLaunchKernelGGL(dec_pack_rows_kernel, dim3((unsigned)((per_slot + 1023) / 1024), frames.nseg), dim3(256), 0, s, (const float4 *)x,
+                       (float4 *)xp, C / 4, runs.tab, frames);
     return hipGetLastError();
 }
 
@@ -1724,7 +1812,8 @@ __global__ __launch_bounds__(256) void dec_run_expand_kernel(const float *__rest
     const int4 e = *(const int4 *)(runs + blockIdx.y);
     const int rows_c = __builtin_amdgcn_readfirstlane(e.y), gap_at = __builtin_amdgcn_readfirstlane(e.z), G = __builtin_amdgcn_readfirstlane(e.w);
     const long n = (long)cap.rows * M;
-    const size_t base = (size_t)cap.row0 * M;
+    // (the compact rows begin where the run table says: at the capacity's own row0, or at the slot of densely packed decoding)
+    const size_t base = (size_t)cap.row0 * M, cbase = (size_t)__builtin_amdgcn_readfirstlane(e.x) * M;
 #pragma unroll
     for (int k = 0; k < 4; k++)
     {
@@ -1732,7 +1821,7 @@ __global__ __launch_bounds__(256) void dec_run_expand_kernel(const float *__rest
         if (i >= n) continue;
         const int t = (int)(i / M), c = (int)(i - (long)t * M);
         const int tc = dec_run_compact_row(t, gap_at, G);
-        if (tc < rows_c) dst[base + i] = src[base + (size_t)tc * M + c];
+        if (tc < rows_c) dst[base + i] = src[cbase + (size_t)tc * M + c];
     }
 }
 

@@ -84,6 +84,8 @@ struct Batch
     // Run-shortened decoding (dec_runs.h, kernels.h launch_dec_runs): the decoder's run table, Seg [nseg] in HBM outside the arena, or
     // null.  The encoder writes it behind the length regulator from the frame counts and the decoder takes every extent from it; the
     // entry points set it where Model::dec_runs_on says so.  A single utterance has a one-entry table.  Keyed like d_frm_live.
+    // A batch's block holds nseg + 1 entries: densely packed decoding (dec_runs.h, Model::dec_pack_on) writes the packed rows as one
+    // segment into the last.
     Seg *d_dec_runs = nullptr;
     // Target durations (include/zerovox_amd.h "target durations"): some utterance's ctl row carries a target frame count, so the
     // encoder launches fit_durations_kernel ahead of the length regulator (d_ctl and d_pctl are then both set).  Keyed: one launch
@@ -212,6 +214,10 @@ class Model
     // Off in fitted mode, under a dbg_layer tap, where the operand pre-pass is off and by ZV_DEC_RUNS; never in a stand-alone decode,
     // whose hidden comes from the caller
     bool dec_runs_on(const Batch &b) const;
+    // Densely packed decoding (dec_runs.h): a chain with a run table packs the utterances' compact rows into one row space, which the
+    // decoder's convs then run over as one segment.  Wherever a batch of several utterances has a run table (so: never in fitted
+    // mode, under a tap, in a stand-alone decode or with the pre-pass off) unless ZV_DEC_PACK = 0
+    bool dec_pack_on(const Batch &b) const;
     bool dec_prepass_on(const Batch &b) const;       // the decoder's convs read an f16 operand written by a pass of its own
     // frames the decoder's 3-tap convs reach to either side, from the loaded layers (the longest path through its blocks)
     int  dec_reach_frames() const;
@@ -344,6 +350,7 @@ class Model
     struct DecLayout
     {
         int    nblk, hs, ss;        // per segment: statistics blocks, floats of AdaIN vectors, floats of (mean, rstd) pairs
+        int    rows, nblk_all;      // rows of every [rows] buffer (dec_pack_rows_cap: the packed rows fit whatever the lengths), statistics blocks of part_t / part_o
         float *h, *st_x, *st_t, *st_y, *st_a, *cat, *t1, *sc, *x0, *xa, *asr_t;
         double *part_t, *part_o; _Float16 *xa16, *t16, *xr16;
         float *mel_c;       // run-shortened decoding: the compact mel the last conv writes (launch_dec_run_expand reads it)
