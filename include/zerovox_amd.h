@@ -14,6 +14,7 @@
  *   *_prosody          the same with per-utterance duration / pitch / energy controls (zv_prosody)
  *   *_phonemes         the same with per-phoneme controls as well (zv_phoneme_controls) and the phoneme timings out
  *   *_target           the same with a target frame count the utterance's durations are fitted to
+ *   *_volume           the same with a gain, a loudness target and a peak ceiling per utterance (zv_volume) and the measured level out
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file        src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -333,6 +334,63 @@ zv_status zv_synthesize_batch_begin_target(zv_model *m, uint32_t lane, uint32_t 
                                            const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
                                            const zv_phoneme_controls *phonemes, int32_t *const *durations,
                                            const uint32_t *target_frames, int fitted);
+/* ---- volume controls: gain, loudness target, peak ceiling, level meter ----------------------------------------------------------
+ * The level of an utterance is otherwise whatever the vocoder's tanh gives.  The volume forms measure the finished waveform on the
+ * device and scale it there, inside the same captured graph and — for a large batch — per tail group, ahead of that group's
+ * download: two small memory-bound passes over data that is still in HBM.  The output stays f32 at the model's rate; nothing is
+ * resampled or converted.  The volume rows travel in the batch's device input block like the other controls, so a replayed graph
+ * picks up new values.  dB is the caller's: gain = 10^(dB / 20), a level in dBFS likewise (full scale = 1.0).
+ * The rule, per utterance, with hop = audio_hop_size, T the capacity, nf = min(n_frames, T) and x[0 .. T*hop) the waveform the
+ * same call gives without volume; integers wherever the order of a sum could matter, so that it can be restated bit for bit and does
+ * not depend on how the kernels split the work:
+ *   measure  over the speech only, the samples i < nf*hop.  A finite x_i: a = min(|x_i|, 1.0f), q_i = (int64)((double)a * 524288.0
+ *            + 0.5), truncating (0 <= q_i <= 2^19); a NaN or infinite x_i: q_i = 0, and it is left out of the peak.
+ *            S = sum of q_i^2, an unsigned 64-bit integer (< 2^62 up to zv_max_frames()).  peak = the largest finite |x_i|, unclamped:
+ *            the maximum of the sign-cleared f32 bit patterns, 0 when there is no finite sample.
+ *   level    S > 0: rms = sqrt((double)S / ((double)(nf*hop) * 274877906944.0)); otherwise rms = 0.
+ *   gain     gd = (double)gain.  If target_rms > 0 and S > 0: gd = (double)target_rms / rms * (double)gain.  If peak_ceiling > 0 and
+ *            peak > 0 and gd * (double)peak > (double)peak_ceiling: gd = (double)peak_ceiling / (double)peak (the ceiling wins).
+ *            g = (float)gd; where the ceiling applied, while (float)(g * peak) > peak_ceiling: g = nextafterf(g, 0) (at most four
+ *            steps; two suffice).  So no finite sample of the result exceeds the ceiling in magnitude.
+ *   apply    wav[i] = x_i * g for all T*hop samples, one f32 multiply each: fitted zeros stay zero, an unfitted tail is scaled like
+ *            the speech.
+ *   report   zv_level {rms = (float)rms, peak, gain = g, reserved = 0}: level and peak BEFORE the gain.
+ * Every f64 step is one IEEE operation (a u64 -> f64 conversion, *, / or sqrt).  csrc/level.h holds the rule as plain C++ (host
+ * reference included).
+ * volume == NULL and levels == NULL: the request of the _target call, the same launches, the same bits.  volume == NULL with levels
+ * given: a meter only — g = 1, the waveform's bits unchanged.  The identity {1, 0, 0} gives the unchanged bits too (x * 1.0f is
+ * exact).  Batches: volume[n_utt] and levels[n_utt], each may be NULL; utterance u gives the bits and the level of
+ * zv_synthesize_volume(..., &volume[u], &levels[u]).  levels must stay valid until the call (batches in flight: _end) returns.
+ * Arguments, limits and messages are those of the _target forms; in addition ZV_ERR_ARG before any work is enqueued when a field is
+ * not finite, gain is outside [0, 1000], or target_rms or peak_ceiling is outside [0, 1] (the message names the entry point, the
+ * utterance and the field).  zv_synthesize_batch_begin_volume is finished by zv_synthesize_batch_end.
+ * Out of scope: zv_vocode*, zv_vocode_device and zv_vocode_stream (they have no n_frames, and a stream has not seen the whole
+ * utterance when its first chunk leaves); per-phoneme gain and fades. */
+typedef struct
+{
+    float gain;             /* linear, 0 .. 1000; multiplies the result of the loudness target (1 = none)            */
+    float target_rms;       /* 0 = none; else the level the speech is brought to, 0 < target_rms <= 1                 */
+    float peak_ceiling;     /* 0 = none; else no finite sample of the result exceeds it, 0 < peak_ceiling <= 1        */
+} zv_volume;                /* identity: {1, 0, 0} */
+typedef struct
+{
+    float    rms, peak;     /* of the speech, before the gain */
+    float    gain;          /* the factor every sample was multiplied by */
+    uint32_t reserved;      /* 0 */
+} zv_level;
+zv_status zv_synthesize_volume(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                               float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                               int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels);
+zv_status zv_synthesize_batch_volume(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                     const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                     float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                     const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                     const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels);
+zv_status zv_synthesize_batch_begin_volume(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                           const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                           const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                           const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                           const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

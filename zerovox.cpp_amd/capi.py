@@ -24,7 +24,7 @@ SYMBOLS = [
     "zv_synthesize_batch_begin_prosody", "zv_encode_taps_phonemes", "zv_synthesize_phonemes", "zv_synthesize_batch_phonemes",
     "zv_synthesize_batch_begin_phonemes", "zv_synthesize_fitted", "zv_synthesize_batch_fitted", "zv_synthesize_batch_begin_fitted",
     "zv_debug_voc_runs", "zv_debug_poison", "zv_encode_taps_target", "zv_synthesize_target", "zv_synthesize_batch_target",
-    "zv_synthesize_batch_begin_target",
+    "zv_synthesize_batch_begin_target", "zv_synthesize_volume", "zv_synthesize_batch_volume", "zv_synthesize_batch_begin_volume",
 ]
 
 
@@ -62,6 +62,71 @@ def _prosody(p) -> Optional[Prosody]:
     if isinstance(p, dict):
         return Prosody(**p)
     return Prosody(*p)
+
+
+class Volume(C.Structure):
+    """zv_volume of include/zerovox_amd.h: per-utterance linear gain, loudness (RMS) target and peak ceiling; 0 = no target / no
+    ceiling, the defaults are the identity.  from_db() converts from dB / dBFS."""
+    _fields_ = [("gain", C.c_float), ("target_rms", C.c_float), ("peak_ceiling", C.c_float)]
+
+    def __init__(self, gain=1.0, target_rms=0.0, peak_ceiling=0.0):
+        super().__init__(gain, target_rms, peak_ceiling)
+
+    @classmethod
+    def from_db(cls, gain_db=0, target_dbfs=None, peak_dbfs=None):
+        """gain_db: the gain in dB; target_dbfs: the RMS level the speech is brought to, in dB re full scale (None: none);
+        peak_dbfs: the peak ceiling likewise (None: none).  linear = 10 ** (dB / 20)"""
+        lin = lambda db: 10.0 ** (float(db) / 20.0)
+        return cls(lin(gain_db), 0.0 if target_dbfs is None else lin(target_dbfs), 0.0 if peak_dbfs is None else lin(peak_dbfs))
+
+    def __repr__(self):
+        return f"Volume(gain={self.gain}, target_rms={self.target_rms}, peak_ceiling={self.peak_ceiling})"
+
+
+class Level(C.Structure):
+    """zv_level of include/zerovox_amd.h: the speech's rms and peak before the gain, and the gain every sample was multiplied by"""
+    _fields_ = [("rms", C.c_float), ("peak", C.c_float), ("gain", C.c_float), ("reserved", C.c_uint32)]
+
+    def __repr__(self):
+        return f"Level(rms={self.rms}, peak={self.peak}, gain={self.gain})"
+
+
+VOLUME_LIMITS = (("gain", 1000.0), ("target_rms", 1.0), ("peak_ceiling", 1.0))
+
+
+def _volume(v, where: str = "") -> Optional[Volume]:
+    """None, a Volume, a dict of its fields or a 3-sequence -> Volume / None, checked before anything reaches the library: every
+    field a finite number, gain in [0, 1000], target_rms and peak_ceiling in [0, 1]"""
+    if v is None:
+        return None
+    if isinstance(v, Volume):
+        vals = (v.gain, v.target_rms, v.peak_ceiling)
+    elif isinstance(v, dict):
+        unknown = sorted(set(v) - {n for n, _ in VOLUME_LIMITS})
+        if unknown:
+            raise ValueError(f"{where}unknown volume field(s) {unknown}")
+        vals = (v.get("gain", 1.0), v.get("target_rms", 0.0), v.get("peak_ceiling", 0.0))
+    else:
+        vals = tuple(v)
+        if len(vals) != 3:
+            raise ValueError(f"{where}a volume is (gain, target_rms, peak_ceiling), got {len(vals)} values")
+    out = []
+    for (name, hi), x in zip(VOLUME_LIMITS, vals):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{where}volume {name} must be a number, not {type(x).__name__}")
+        x = float(np.float32(x))
+        if not np.isfinite(x):
+            raise ValueError(f"{where}volume {name} = {x} is not finite")
+        if not 0.0 <= x <= hi:
+            raise ValueError(f"{where}volume {name} = {x} is outside [0, {hi:g}]")
+        out.append(x)
+    return Volume(*out)
+
+
+def _check_levels(return_levels):
+    if not isinstance(return_levels, (bool, np.bool_)):
+        raise TypeError(f"return_levels must be a bool, not {type(return_levels).__name__}")
+    return bool(return_levels)
 
 
 class PhonemeControlsC(C.Structure):
@@ -187,6 +252,12 @@ def load_library(path: Optional[str] = None):
         lib.zv_synthesize_target.argtypes = lib.zv_synthesize_phonemes.argtypes + [u32, C.c_int]
         lib.zv_synthesize_batch_target.argtypes = lib.zv_synthesize_batch_phonemes.argtypes + [C.POINTER(u32), C.c_int]
         lib.zv_synthesize_batch_begin_target.argtypes = lib.zv_synthesize_batch_begin_phonemes.argtypes + [C.POINTER(u32), C.c_int]
+    # the volume forms: the _target argument lists, the volumes (zv_volume, batches [n_utt]) and the levels (zv_level, likewise), each or NULL
+    if hasattr(lib, "zv_synthesize_volume"):
+        vl = [C.POINTER(Volume), C.POINTER(Level)]
+        lib.zv_synthesize_volume.argtypes = lib.zv_synthesize_target.argtypes + vl
+        lib.zv_synthesize_batch_volume.argtypes = lib.zv_synthesize_batch_target.argtypes + vl
+        lib.zv_synthesize_batch_begin_volume.argtypes = lib.zv_synthesize_batch_begin_target.argtypes + vl
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -260,11 +331,14 @@ def _check_target(target, T):
     return int(target)
 
 
-def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None):
+def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None, volume=None, levels=None):
     """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
     name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status.
     fitted: name_fitted, which takes everything (NULL for what the call lacks).  target (a frame count, or the batches' uint32
-    array): name_target, which takes everything and the fitted flag"""
+    array): name_target, which takes everything and the fitted flag.  volume / levels (a zv_volume and a zv_level, or the batches'
+    arrays): name_volume, which takes everything the _target form takes and the two (a call without a target passes 0 / NULL)"""
+    if volume is not None or levels is not None:
+        return getattr(lib, name + "_volume")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels)
     if target is not None:
         return getattr(lib, name + "_target")(*args, prosody, phonemes, durations, target, int(fitted))
     if fitted:
@@ -436,15 +510,18 @@ class Model:
         return out
 
     def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False,
-                   fitted: bool = False, target_frames: Optional[int] = None):
+                   fitted: bool = False, target_frames: Optional[int] = None, *, volume=None, return_levels: bool = False):
         """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
         arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
         as a third element.  fitted: zv_synthesize_fitted — T is a capacity, the utterance is decoded and vocoded as the n_frames
         the length regulator fills; wav keeps the capacity shape [T * hop], zero behind n_frames * hop.
         target_frames (0 <= frames <= T): zv_synthesize_target — the durations are fitted to sum to exactly that many frames (0: the
-        bits of the call without it); None: the entry points above"""
+        bits of the call without it); None: the entry points above.
+        volume (Volume, dict or (gain, target_rms, peak_ceiling)) or return_levels: zv_synthesize_volume — the waveform is measured
+        and scaled on the device; return_levels adds the Level (rms and peak before the gain, the gain) as the last element"""
         fitted = _check_fitted(fitted, [T])
         target = _check_target(target_frames, T)
+        vol, return_levels = _volume(volume), _check_levels(return_levels)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
@@ -453,26 +530,37 @@ class Model:
         args = (self.h, _ptr(ids), _ptr(puncts), _ptr(style), len(ids), T, _ptr(wav), C.byref(nf))
         pc = _phoneme_controls(phonemes, len(ids))
         dur = np.empty(len(ids), np.int32) if return_durations else None
+        level = Level() if vol is not None or return_levels else None
+        if level is not None and target is None:
+            target = 0                       # the _volume form takes a count, 0 = none
         self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur),
-                                fitted, target))
-        return (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
+                                fitted, target, _ref(vol), _ref(level)))
+        out = (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
+        return out + (level,) if return_levels else out
 
-    def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False) -> "BatchCall":
+    def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
+                      return_levels: bool = False) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
         buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list.  fitted: the
         zv_synthesize_batch_fitted / _begin_fitted entry points (the lane form: .begin(lane) / .end(lane))"""
-        return BatchCall(self, utterances, durations, fitted)
+        return BatchCall(self, utterances, durations, fitted, volume=volume, return_levels=return_levels)
 
-    def synthesize_batch(self, utterances, return_durations: bool = False, fitted: bool = False):
+    def synthesize_batch(self, utterances, return_durations: bool = False, fitted: bool = False, *, volume=None,
+                         return_levels: bool = False):
         """utterances: list of (ids, puncts, style, T[, prosody[, phonemes[, target_frames]]]) -> list of (wav, n_frames); each
         utterance keeps its own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its
         per-phoneme controls (PhonemeControls, dict of arrays or None), with a seventh its target frame count (None / 0: none).  return_durations: (wav, n_frames, durations) tuples.  fitted:
-        zv_synthesize_batch_fitted — every T is a capacity, wav keeps the capacity shape with zeros behind n_frames * hop"""
-        call = BatchCall(self, utterances, return_durations, fitted)
+        zv_synthesize_batch_fitted — every T is a capacity, wav keeps the capacity shape with zeros behind n_frames * hop.
+        volume: a list, one Volume (dict, 3-sequence) or None per utterance — zv_synthesize_batch_volume; return_levels: every tuple
+        gains the utterance's Level as its last element"""
+        call = BatchCall(self, utterances, return_durations, fitted, volume=volume, return_levels=return_levels)
         call.run()
+        res = call.results()
         if return_durations:
-            return [r + (d,) for r, d in zip(call.results(), call.durations)]
-        return call.results()
+            res = [r + (d,) for r, d in zip(res, call.durations)]
+        if call.return_levels:
+            res = [r + (Level.from_buffer_copy(lv),) for r, lv in zip(res, call.levels)]
+        return res
 
     # ---- device-resident API ----
     def device_alloc(self, nbytes: int) -> int:
@@ -548,10 +636,24 @@ class BatchCall:
     array .prosody, which set_prosody() rewrites in place: the next run() / begin() uses the new values with the same buffers (a
     captured graph replays with them).  When any utterance carries per-phoneme controls, or durations=True, the _phonemes entry
     points are called with the array .phonemes (set_phoneme_controls() rewrites an entry) and .durations[i] holds utterance i's
-    phoneme timings after run() / end().  fitted: the _fitted entry points, whatever controls the utterances carry."""
+    phoneme timings after run() / end().  fitted: the _fitted entry points, whatever controls the utterances carry.
+    volume (a list, one Volume / dict / 3-sequence or None per utterance) or return_levels: the _volume entry points, with the array
+    .volume (None entries get the identity; set_volume() rewrites an entry in place for the next run() / begin()) and the array .levels,
+    which holds every utterance's Level after run() / end()."""
 
-    def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False):
+    def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
+                 return_levels: bool = False):
         self.fitted = _check_fitted(fitted, [u[3] for u in utterances])
+        self.return_levels = _check_levels(return_levels)
+        self.volume = self.levels = None
+        if volume is not None:
+            vols = list(volume)
+            if len(vols) != len(utterances):
+                raise ValueError(f"volume has {len(vols)} entries, the batch has {len(utterances)} utterances")
+            vols = [_volume(v, f"utterance {i}: ") for i, v in enumerate(vols)]
+            self.volume = (Volume * len(utterances))(*[v if v is not None else Volume() for v in vols])
+        if self.volume is not None or self.return_levels:
+            self.levels = (Level * len(utterances))()
         tgs = [_check_target(u[6], u[3]) if len(u) > 6 else None for u in utterances]
         self.targets = None
         if any(t is not None for t in tgs):
@@ -599,6 +701,12 @@ class BatchCall:
             raise ValueError("this BatchCall was built without target frame counts")
         self.targets[i] = _check_target(frames, int(self.Ts[i])) or 0
 
+    def set_volume(self, i: int, volume):
+        """utterance i's volume (None: the identity) for the following run() / begin() (the call must have been built with volume=)"""
+        if self.volume is None:
+            raise ValueError("this BatchCall was built without volume controls")
+        self.volume[i] = _volume(volume, f"utterance {i}: ") or Volume()
+
     def set_prosody(self, i: int, prosody):
         """utterance i's controls for the following run() / begin() (the call must have been built with controls)"""
         if self.prosody is None:
@@ -608,13 +716,15 @@ class BatchCall:
     def run(self):
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets))
+        m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
+                             self.volume, self.levels))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets))
+        m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
+                             self.volume, self.levels))
 
     def end(self, lane: int):
         m = self.model

@@ -162,7 +162,12 @@ struct Request
     bool                       fitted = false;
     // target durations (zv_*_target): [count] or null, 0 = no target for that utterance
     const uint32_t            *target_frames = nullptr;
+    // volume controls (zv_*_volume): volume [count] or null (levels alone: a meter, every gain 1), levels [count] or null
+    const zv_volume           *volume = nullptr;
+    zv_level                  *levels = nullptr;
 
+    // the call measures levels: then every utterance gets a volume row (the identity where none is given) and a level row
+    bool volumes() const { return volume || levels; }
     // any utterance with a target: then every utterance gets a ctl row and pctl rows (the identity where it has no controls), which
     // the device step between the duration predictor and the length regulator reads and rewrites (kernels.h launch_fit_durations)
     bool targets() const
@@ -203,6 +208,8 @@ struct Request
         if (phonemes) s.phonemes += a;
         if (durations) s.durations += a;
         if (target_frames) s.target_frames += a;
+        if (volume) s.volume += a;
+        if (levels) s.levels += a;
         return s;
     }
 };
@@ -215,6 +222,34 @@ static void check_prosody(const zv_prosody &p)
         if (!std::isfinite(f[k])) zv::fail(ZV_ERR_ARG, "prosody %s = %g is not finite", names[k], (double)f[k]);
     if (!(f[0] > 0.0f && f[0] <= 16.0f)) zv::fail(ZV_ERR_ARG, "prosody duration_scale = %g is outside (0, 16]", (double)f[0]);
 }
+
+static void check_volume(const zv_volume &v)
+{
+    static const char *const names[3] = {"gain", "target_rms", "peak_ceiling"};
+    const float f[3] = {v.gain, v.target_rms, v.peak_ceiling};
+    const float hi[3] = {1000.0f, 1.0f, 1.0f};
+    for (int k = 0; k < 3; k++)
+    {
+        if (!std::isfinite(f[k])) zv::fail(ZV_ERR_ARG, "volume %s = %g is not finite", names[k], (double)f[k]);
+        if (!(f[k] >= 0.0f && f[k] <= hi[k])) zv::fail(ZV_ERR_ARG, "volume %s = %g is outside [0, %g]", names[k], (double)f[k], (double)hi[k]);
+    }
+}
+
+// a request's volume rows in the kernels' layout (level.h LEVEL_VOL_STRIDE), the identity {1, 0, 0} where the call only meters
+static void pack_volume(const Request &r, float *vol)
+{
+    static const zv_volume identity = {1.0f, 0.0f, 0.0f};
+    for (uint32_t u = 0; u < r.count; u++)
+    {
+        const zv_volume &v = r.volume ? r.volume[u] : identity;
+        float *c = vol + (size_t)u * zv::LEVEL_VOL_STRIDE;
+        c[0] = v.gain;
+        c[1] = v.target_rms;
+        c[2] = v.peak_ceiling;
+        c[3] = 0.0f;
+    }
+}
+static_assert(sizeof(zv_level) == sizeof(zv::LevelRow) && sizeof(zv_level) == 16, "zv_level is the kernels' LevelRow");
 
 static void check_phoneme_controls(const Model &M, const zv_phoneme_controls &p, uint32_t n)
 {
@@ -256,6 +291,7 @@ static void check_request(zv_model *m, const Request &r)
             check_ids(M, r.ids[u], r.puncts[u], r.n[u]);
             if (r.prosody) check_prosody(r.prosody[u]);
             if (r.phonemes) check_phoneme_controls(M, r.phonemes[u], r.n[u]);
+            if (r.volume) check_volume(r.volume[u]);
             if (r.target_frames && r.target_frames[u] > r.T[u])
                 zv::fail(ZV_ERR_ARG, "target_frames = %u exceeds the capacity T = %u", r.target_frames[u], r.T[u]);
             if (tg && r.n[u] > (uint32_t)zv::FIT_MAX_TOKENS)      // one launch covers the request's utterances, with or without a target
@@ -339,6 +375,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const bool tg = r.targets(), pc = r.phoneme_controls() || tg, dur = r.timings();
         const size_t E = M.E(), b_ids = (size_t)n * 4, b_hid = (size_t)T * E * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
         const size_t b_ctl = r.prosody || tg ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
+        const bool vol = r.volumes() && !taps;
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
         // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
@@ -349,6 +386,8 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const size_t o_mel = taps ? 0 : L.at((size_t)T * M.hp.audio_num_mels * 4), o_wav = taps ? 0 : L.at(b_wav),
                      o_cum = taps ? 0 : L.at(dur ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
                      o_runs = L.at(!r.fitted && !taps ? sizeof(zv::Seg) : 0);
+        // [volume row][level row] (volume controls: the row uploaded, the level written on the device)
+        const size_t o_vol = L.at(vol ? zv::LEVEL_VOL_STRIDE * 4 : 0), o_lvl = L.at(vol ? sizeof(zv::LevelRow) : 0);
         char *io = (char *)M.io_scratch(L.size());
         int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
@@ -372,6 +411,16 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
             bt.d_pctl = (const float *)(io + o_pctl);
             ZV_HIP(hipMemcpyAsync(io + o_pctl, pctl.data(), b_pctl, hipMemcpyHostToDevice, M.stream()));
         }
+        float volrow[zv::LEVEL_VOL_STRIDE];
+        zv_level level = {0.0f, 0.0f, 0.0f, 0};
+        if (vol)
+        {
+            pack_volume(r, volrow);
+            bt.d_vol = (const float *)(io + o_vol);
+            bt.d_levels = (zv::LevelRow *)(io + o_lvl);
+            bt.d_nframes = d_nf;
+            ZV_HIP(hipMemcpyAsync(io + o_vol, volrow, sizeof(volrow), hipMemcpyHostToDevice, M.stream()));
+        }
         int32_t nf = 0;
         if (taps)
         {
@@ -394,8 +443,10 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
             ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream()));
             if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), bt.d_cum, b_ids, hipMemcpyDeviceToHost, M.stream()));
             ZV_HIP(hipMemcpyAsync(r.out[0], d_wav, b_wav, hipMemcpyDeviceToHost, M.stream()));
+            if (vol) ZV_HIP(hipMemcpyAsync(&level, io + o_lvl, sizeof(level), hipMemcpyDeviceToHost, M.stream()));
         }
         M.sync();
+        if (vol && r.levels) r.levels[0] = level;
         if (r.n_frames) r.n_frames[0] = (uint32_t)nf;
         if (dur) durations_from_cum(cum.data(), 1, r.n, r.T, r.durations);
     });
@@ -602,6 +653,9 @@ struct PendingBatch
     std::vector<uint32_t> N;
     std::vector<int32_t *> dur;
     const int32_t        *h_cum = nullptr;
+    // volume controls (zv_synthesize_batch_begin_volume): the level rows land in h_lvl, handed out to levels[n_utt] (may be null)
+    const zv_level       *h_lvl = nullptr;
+    zv_level             *levels = nullptr;
 };
 static PendingBatch &pending_slot(zv_model *m, int lane)
 {
@@ -636,7 +690,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     if (pb.active) zv::fail(ZV_ERR_ARG, "lane %d already has a batch in flight", lane);
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
-    const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings();
+    const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings(), vol = r.volumes();
     uint32_t nmax = 0, tmax = 0, ntot = 0;
     for (uint32_t u = 0; u < r.count; u++)
     {
@@ -660,14 +714,17 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     const size_t b_tab = (size_t)(bt.nseg + 1) * sizeof(zv::Seg);
     const size_t i_tok = in.at(b_tab), i_frm = in.at(b_tab), i_ids = in.at(bt.n_rows * 4), i_pun = in.at(bt.n_rows * 4),
                  i_sty = in.at((size_t)bt.nseg * E * 4), i_ctl = in.at(ctl ? (size_t)bt.nseg * zv::CTL_STRIDE * 4 : 0),
-                 i_pctl = in.at(pc ? bt.n_rows * zv::PCTL_STRIDE * 4 : 0), b_in = in.size();
+                 i_pctl = in.at(pc ? bt.n_rows * zv::PCTL_STRIDE * 4 : 0),
+                 i_vol = in.at(vol ? (size_t)bt.nseg * zv::LEVEL_VOL_STRIDE * 4 : 0),      // volume rows: only with volume controls, like the control rows
+                 b_in = in.size();
     // device block: [frame counts][input block][hidden][mel][wav][scan] (scan: only when timings are asked for, the length
     // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
     Layout dev;
     const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
                  o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur ? bt.n_rows * 4 : 0),
                  o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0),      // fitted: the live frame table, written on the device
-                 o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0);     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
+                 o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0),     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
+                 o_lvl = dev.at(vol ? (size_t)bt.nseg * sizeof(zv::LevelRow) : 0);             // volume controls: the level rows, written on the device
     M.reserve_batch(bt);
     char *io = (char *)M.io_scratch(dev.size());
     // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan]
@@ -680,7 +737,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     }
     Layout host;
     const size_t p_in = host.at(b_in), p_nf = host.at((size_t)bt.nseg * 4), p_wav = host.at(wav_bytes),
-                 p_cum = host.at(dur ? bt.n_rows * 4 : 0);
+                 p_cum = host.at(dur ? bt.n_rows * 4 : 0), p_lvl = host.at(vol ? (size_t)bt.nseg * sizeof(zv_level) : 0);
     char *pin = (char *)M.pinned_scratch(host.size());
     char *d_in = io + o_in, *h_in = pin + p_in;
     {
@@ -702,6 +759,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         h_tok[r.count] = zv::Seg{0, n0, n0, 0};
         h_frm[r.count] = zv::Seg{0, t0, 0, 0};
         pack_controls(r, (float *)(h_in + i_ctl), (float *)(h_in + i_pctl));      // (phoneme rows past the utterances are never read)
+        if (vol) pack_volume(r, (float *)(h_in + i_vol));
     }
     bt.d_tok = (const zv::Seg *)(d_in + i_tok);
     bt.d_frm = (const zv::Seg *)(d_in + i_frm);
@@ -711,10 +769,17 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     if (dur) bt.d_cum = (int32_t *)(io + o_cum);
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
     if (M.dec_runs_on(bt)) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
+    if (vol)
+    {
+        bt.d_vol = (const float *)(d_in + i_vol);
+        bt.d_levels = (zv::LevelRow *)(io + o_lvl);
+        bt.d_nframes = (const int32_t *)(io + o_nf);
+    }
     int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(d_in + i_ids), *d_pun = (int32_t *)(d_in + i_pun);
     float *d_sty = (float *)(d_in + i_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
     int32_t *h_nf = (int32_t *)(pin + p_nf), *h_cum = dur ? (int32_t *)(pin + p_cum) : nullptr;
     char *h_wav = pin + p_wav;
+    zv_level *h_lvl = vol ? (zv_level *)(pin + p_lvl) : nullptr;
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
     // run.  Same kernels on the same rows: same bits.
@@ -740,6 +805,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
             ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream()));
             if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream()));
             ZV_HIP(hipMemcpyAsync(h_wav, d_wav, wav_bytes, hipMemcpyDeviceToHost, M.stream()));
+            if (vol) ZV_HIP(hipMemcpyAsync(h_lvl, io + o_lvl, (size_t)bt.nseg * sizeof(zv_level), hipMemcpyDeviceToHost, M.stream()));
             ZV_HIP(hipEventRecord(M.tail_event(1), M.stream()));
         }
         else
@@ -764,6 +830,8 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
                 ZV_HIP(hipEventRecord(M.tail_event(2 * g + 1), cs));
             }
             ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream()));
+            // the level rows of every group, behind the last group's kernels (batch_finish waits for the lane's stream)
+            if (vol) ZV_HIP(hipMemcpyAsync(h_lvl, io + o_lvl, (size_t)bt.nseg * sizeof(zv_level), hipMemcpyDeviceToHost, M.stream()));
         }
     }
     catch (...)
@@ -782,6 +850,8 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     pb.h_nf = h_nf;
     pb.hop = hop;
     pb.h_cum = h_cum;
+    pb.h_lvl = h_lvl;
+    pb.levels = r.levels;
     pb.N.assign(r.n, r.n + r.count);
     if (dur) pb.dur.assign(r.durations, r.durations + r.count);
     else pb.dur.clear();
@@ -814,6 +884,7 @@ static void batch_finish(zv_model *m, int lane)
     if (pb.n_frames)
         for (uint32_t u = 0; u < pb.n_utt; u++) pb.n_frames[u] = (uint32_t)pb.h_nf[u];
     if (pb.h_cum) durations_from_cum(pb.h_cum, pb.n_utt, pb.N.data(), pb.T.data(), pb.dur.data());
+    if (pb.h_lvl && pb.levels) memcpy(pb.levels, pb.h_lvl, (size_t)pb.n_utt * sizeof(zv_level));
 }
 
 // how many utterances from `a` on form one launch group: up to 64 utterances / 64 Ki frames of capacity
@@ -970,6 +1041,35 @@ zv_status zv_synthesize_batch_begin_target(zv_model *m, uint32_t lane, uint32_t 
 {
     return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
                                  durations, fitted != 0, target_frames});
+}
+
+// The volume forms: the _target requests plus the volumes and the levels (both NULL: the request of the _target call).
+zv_status zv_synthesize_volume(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                               float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                               int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels)
+{
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody, phonemes, &durations, fitted != 0,
+                          &target_frames, volume, levels});
+}
+
+zv_status zv_synthesize_batch_volume(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                     const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                     uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                     int32_t *const *durations, const uint32_t *target_frames, int fitted, const zv_volume *volume,
+                                     zv_level *levels)
+{
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                durations, fitted != 0, target_frames, volume, levels});
+}
+
+zv_status zv_synthesize_batch_begin_volume(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                           const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                           const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                           const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                           const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                 durations, fitted != 0, target_frames, volume, levels});
 }
 
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)

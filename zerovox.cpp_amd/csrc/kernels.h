@@ -12,6 +12,7 @@
 
 #include "conv_plan.h"     // the launchers' plans: ConvPrologue, conv_gemm_groups / _tiles / _units, pair_supported, triple_supported, block64_supported, TRIPLE_MAX_DIL
 #include "voc_plan.h"
+#include "level.h"        // volume controls: LEVEL_CHUNK_SAMPLES, LEVEL_VOL_STRIDE, LevelRow
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -392,5 +393,19 @@ hipError_t launch_dec_pack_rows(hipStream_t s, const float *x, float *xp, int C,
 // compact mel (the rows the decoder computed: at the segment's own row0, or at its slot of the packed rows) expanded to the
 // capacity.  mel_c and mel must not overlap
 hipError_t launch_dec_run_expand(hipStream_t s, const float *mel_c, float *mel, int M, const Segs &runs, const Segs &frames);
+
+// ---- volume controls (include/zerovox_amd.h "volume controls", level.h): two passes over the finished waveform wav [rows * hop], laid
+// out by `frames` (the CAPACITY table or inline segment); n_frames [nseg] are the regulator's counts on the device, so the speech of
+// segment u is its first min(n_frames[u], rows) * hop samples.
+//   measure: slab[u * level_chunks + c] = {sum of squared 1.19 magnitudes, peak bits, 0} of chunk c (LEVEL_CHUNK_SAMPLES samples) of
+//            segment u's speech, one 16-byte store per workgroup; chunks behind the speech are not written
+//   apply:   adds a segment's entries, takes the gain from vol[u * LEVEL_VOL_STRIDE + {0, 1, 2}] = {gain, target_rms, peak_ceiling}
+//            (level_report), multiplies all rows * hop samples of the segment by it and stores levels[u]
+// slab: 16-byte aligned, nseg * level_chunks(frames.max_rows, hop) entries of 16 bytes; levels: 16-byte aligned.  No atomics, nothing
+// to zero: apply reads only what measure has stored in the same run.
+int        level_chunks(int max_rows, int hop);
+hipError_t launch_level_measure(hipStream_t s, const float *wav, const int32_t *n_frames, void *slab, const Segs &frames, int hop);
+hipError_t launch_level_apply(hipStream_t s, float *wav, const int32_t *n_frames, const void *slab, const float *vol, LevelRow *levels,
+                              const Segs &frames, int hop);
 
 }  // namespace zv

@@ -91,6 +91,13 @@ struct Batch
     // encoder launches fit_durations_kernel ahead of the length regulator (d_ctl and d_pctl are then both set).  Keyed: one launch
     // more.  WHICH utterances have a target, and its value, is read at run time: a replay picks up new targets.
     bool has_targets = false;
+    // Volume controls (include/zerovox_amd.h "volume controls", level.h), all three set or none: the volume rows, f32 [nseg]
+    // [LEVEL_VOL_STRIDE] in HBM, the level rows the vocoder's last step stores, LevelRow [nseg] in HBM outside the arena, and the
+    // regulator's frame counts [nseg] on the device (what tells speech from padding).  Keyed like d_ctl: with them the vocoder
+    // ends in two launches more; the VALUES are read at run time, so a replay picks up new ones.
+    const float   *d_vol = nullptr;
+    LevelRow      *d_levels = nullptr;
+    const int32_t *d_nframes = nullptr;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -119,7 +126,7 @@ struct Batch
         return nseg == o.nseg && n_max == o.n_max && t_max == o.t_max && n_rows == o.n_rows && t_rows == o.t_rows && d_tok == o.d_tok &&
                d_frm == o.d_frm && (d_tok || memcmp(&tok1, &o.tok1, sizeof(Seg)) == 0) && (d_frm || memcmp(&frm1, &o.frm1, sizeof(Seg)) == 0) &&
                d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live && has_targets == o.has_targets &&
-               d_dec_runs == o.d_dec_runs;
+               d_dec_runs == o.d_dec_runs && d_vol == o.d_vol && d_levels == o.d_levels && d_nframes == o.d_nframes;
     }
 };
 
@@ -345,8 +352,13 @@ class Model
         struct Stage { float *ub, *y[3]; _Float16 *xt[3]; } st[8];      // stage i: ping-pong pool i & 1
         // run-shortened schedule (kernels.h launch_voc_runs), behind the pools so that a sub-batch finds them where the head put them:
         // the compacted mel, the row flags, the run table (one entry per segment: the only carve that reads nseg, hence the last)
+        // volume controls (kernels.h launch_level_measure): the partial totals, 16 bytes per (segment, chunk).  Sized by t_rows alone
+        // (level_slab_entries) and carved in front of the run table, so that a sub-batch finds the table where the head put it
+        void *level_slab;
         float *mel_c; int32_t *eq; Seg *runs;
     };
+    // entries of VocLayout::level_slab: >= nseg * level_chunks(t_max, hop) for every Batch with nseg * t_max <= t_rows, a sub-batch included
+    size_t level_slab_entries(const Batch &b) const;
     struct DecLayout
     {
         int    nblk, hs, ss;        // per segment: statistics blocks, floats of AdaIN vectors, floats of (mean, rstd) pairs

@@ -70,8 +70,15 @@ Model::VocLayout Model::voc_layout(DeviceArena &a, const Batch &bt) const
     // switch-off calls pay t_rows x (num_mels + 1) words of arena too), so that a layout depends on the batch's shape alone
     v.mel_c = a.take_n<float>(bt.t_rows * hp.audio_num_mels);
     v.eq = a.take_n<int32_t>(bt.t_rows);
+    v.level_slab = a.take(level_slab_entries(bt) * 16);
     v.runs = a.take_n<Seg>(bt.nseg);
     return v;
+}
+
+// nseg * ceil(t_max * hop / chunk) <= nseg * t_max * hop / chunk + nseg <= t_rows * hop / chunk + t_rows / t_max
+size_t Model::level_slab_entries(const Batch &bt) const
+{
+    return (bt.t_rows * hp.audio_hop_size + LEVEL_CHUNK_SAMPLES - 1) / LEVEL_CHUNK_SAMPLES + bt.t_rows / (size_t)std::max(bt.t_max, 1) + 1;
 }
 
 // HiFi-GAN vocoder (reference src/hifigan.cpp:187-377): fixed schedule of 2 + n_up * 7 launches
@@ -95,6 +102,12 @@ void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g
     Batch sub = bt;
     sub.d_frm = bt.d_frm + g0;
     if (bt.d_frm_live) sub.d_frm_live = bt.d_frm_live + g0;
+    if (bt.d_vol)
+    {
+        sub.d_vol = bt.d_vol + (size_t)g0 * LEVEL_VOL_STRIDE;
+        sub.d_levels = bt.d_levels + g0;
+        sub.d_nframes = bt.d_nframes + g0;
+    }
     sub.nseg = cnt;
     vocode_group(sub, d_mel, d_wav, 2, g0);
 }
@@ -435,6 +448,28 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         if (dbg_layer.kind == ZV_LAYER_VOC_OUTPUT) dbg_extract(d_wav, 1, 1, L);
         // fitted: the output conv stops at each utterance's last frame; the rest of its capacity is silence
         if (bt.d_frm_live) ZV_LAUNCH("voc_zero_tail", 4.0 * La, 0.0, launch_zero_tail(stream(), d_wav, 1, bt.frames_cap(), fr, rate));
+    }
+
+    // Volume controls (level.h): the waveform of these segments is final, so measure the speech and scale the capacity — per tail
+    // group, ahead of the group's download.  Only where the call carries volume; never under a one-layer tap.
+    if (bt.d_vol && dbg_layer.kind < 0)
+    {
+        const Segs cap = bt.frames_cap();
+        if ((size_t)bt.nseg * level_chunks(cap.max_rows, rate) > level_slab_entries(bt)) fail(ZV_ERR_DEVICE, "internal: level slab too small");
+        const double cap_samples = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg) * rate;
+        double speech_samples = cap_samples;
+        if (profiling && !skip_launch_)
+        {
+            // the profile states bytes moved: the speech the regulator produced (this path is eager and the host waits anyway)
+            std::vector<int32_t> nf((size_t)bt.nseg);
+            ZV_HIP(hipMemcpyAsync(nf.data(), bt.d_nframes, nf.size() * 4, hipMemcpyDeviceToHost, stream()));
+            ZV_HIP(hipStreamSynchronize(stream()));
+            speech_samples = 0;
+            for (int32_t f : nf) speech_samples += (double)std::min(std::max(f, 0), bt.t_max) * rate;
+        }
+        ZV_LAUNCH("voc_level_measure", 4.0 * speech_samples, 0.0, launch_level_measure(stream(), d_wav, bt.d_nframes, lay.level_slab, cap, rate));
+        ZV_LAUNCH("voc_level_apply", 8.0 * cap_samples, 0.0,
+                  launch_level_apply(stream(), d_wav, bt.d_nframes, lay.level_slab, bt.d_vol, bt.d_levels, cap, rate));
     }
 }
 

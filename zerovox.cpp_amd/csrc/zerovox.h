@@ -127,6 +127,11 @@ class ZeroVOXModel
     // target durations (include/zerovox_amd.h "target durations") for the eval() calls that follow: the utterance's durations are
     // fitted to sum to exactly `frames` (<= max_seq_len, ZV_ERR_ARG otherwise; 0 = none).  Works with everything above.
     void set_target_frames(uint32_t frames) { target_frames = frames; }
+    // volume controls (include/zerovox_amd.h "volume controls") for the eval() calls that follow: the waveform is measured and scaled
+    // on the device (gain, loudness target, peak ceiling; the identity {1, 0, 0} only meters) and get_level() holds the speech's
+    // rms and peak before the gain and the gain applied.  Works with everything above; values are checked when eval() runs.
+    void set_volume(const zv_volume &v) { volume = v; has_volume = true; }
+    const zv_level &get_level() const { return level; }
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
@@ -153,6 +158,9 @@ class ZeroVOXModel
     std::vector<int32_t> durations;
     bool                 fitted = false;
     uint32_t             target_frames = 0;
+    zv_volume            volume = {1.0f, 0.0f, 0.0f};
+    bool                 has_volume = false;
+    zv_level             level = {0.0f, 0.0f, 0.0f, 0};
 };
 
 }  // namespace ZeroVOX

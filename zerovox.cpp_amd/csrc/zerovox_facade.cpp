@@ -167,6 +167,20 @@ void ZeroVOXModel::set_phoneme_controls(const zv_phoneme_controls *p, uint32_t n
 void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const float *style_embed, uint32_t num_phonemes)
 {
     const zv_prosody *pr = has_prosody ? &prosody : nullptr;
+    if (has_volume)
+    {
+        // the volume form takes what every other form takes (the level is measured on the finished waveform of the one-pass chain)
+        if (has_phonemes && pc_n != num_phonemes)
+            throw zv::Error(ZV_ERR_ARG, "set_phoneme_controls: controls for " + std::to_string(pc_n) + " phonemes, eval() has " +
+                                            std::to_string(num_phonemes));
+        auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
+        const zv_phoneme_controls pc = {ptr(pc_frames), ptr(pc_scale), ptr(pc_pitch), ptr(pc_energy)};
+        if (record_durations) durations.assign(num_phonemes, 0);
+        chk(zv_synthesize_volume(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
+                                 has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
+                                 &volume, &level));
+        return;
+    }
     if (record_durations || fitted || target_frames)
     {
         // the per-phoneme entry points (controls and / or timings) and the fitted one; N = num_phonemes on both of eval()'s paths

@@ -29,6 +29,11 @@
 //            frames, or to floor(S * sampling rate / hop size + 0.5) frames; with --fit the file holds exactly that many frames.
 //            Work with --fit, the prosody flags, --phoneme-controls (forced frames stay) and --alignment.  A bad value, or a
 //            target above the checkpoint's max_seq_len, is a usage error.
+//   --gain-db G, --loudness-dbfs L, --peak-dbfs P
+//            volume controls (include/zerovox_amd.h "volume controls"): a gain of G dB (-200 .. 60), the speech brought to an RMS
+//            level of L dB re full scale (-200 .. 0), no sample above P dB re full scale (-200 .. 0); linear = 10^(dB / 20).  The
+//            waveform is measured and scaled on the device; the measured rms / peak (before the gain) and the gain are printed.
+//            Work with everything above.  A bad value is a usage error.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
 #include <algorithm>
 #include <cmath>
@@ -51,6 +56,7 @@ static void usage(FILE *f)
     fprintf(f, "usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info]\n"
                "               [--duration-scale S] [--pitch-scale S] [--pitch-shift D] [--energy-scale S] [--energy-shift D]\n"
                "               [--phoneme-controls FILE] [--alignment FILE] [--target-frames F | --target-seconds S]\n"
+               "               [--gain-db G] [--loudness-dbfs L] [--peak-dbfs P]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
@@ -64,7 +70,10 @@ static void usage(FILE *f)
                "  --trim               write only the frames the length regulator produced (cut from the max_seq_len-frame run)\n"
                "  --fit                synthesize only those frames (the utterance at its own length) and write them\n"
                "  --target-frames F    fit the durations to exactly F frames (1 <= F <= the checkpoint's max_seq_len)\n"
-               "  --target-seconds S   the same for floor(S * sampling rate / hop size + 0.5) frames (S > 0)\n",
+               "  --target-seconds S   the same for floor(S * sampling rate / hop size + 0.5) frames (S > 0)\n"
+               "  --gain-db G          multiply the waveform by 10^(G / 20) (-200 <= G <= 60)\n"
+               "  --loudness-dbfs L    bring the speech to an RMS level of L dB re full scale (-200 <= L <= 0)\n"
+               "  --peak-dbfs P        keep every sample at or under P dB re full scale (-200 <= P <= 0); prints rms / peak / gain\n",
             k_default_model, k_default_out);
 }
 
@@ -160,7 +169,8 @@ static std::vector<int32_t> utterance_ids(const std::string &utt_path)
 int main(int argc, char **argv)
 {
     std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path;
-    bool trim = false, fit = false, info = false, controlled = false;
+    bool trim = false, fit = false, info = false, controlled = false, leveled = false;
+    zv_volume volume = {1.0f, 0.0f, 0.0f};
     long target_frames = 0;            // --target-frames
     double target_seconds = 0.0;       // --target-seconds
     zv_prosody prosody = {1.0f, 1.0f, 0.0f, 1.0f, 0.0f};
@@ -201,6 +211,22 @@ int main(int argc, char **argv)
                 return 2;
             }
             target_frames = 0;
+        }
+        else if (a == "--gain-db" || a == "--loudness-dbfs" || a == "--peak-dbfs")
+        {
+            const float db = parse_flag_float(a.c_str(), need(a.c_str()));
+            const float hi = a == "--gain-db" ? 60.0f : 0.0f;
+            if (!(db >= -200.0f && db <= hi))
+            {
+                fprintf(stderr, "zerovox: %s must be in [-200, %g] dB, got %g\n", a.c_str(), (double)hi, (double)db);
+                usage(stderr);
+                return 2;
+            }
+            const float lin = (float)pow(10.0, (double)db / 20.0);
+            if (a == "--gain-db") volume.gain = lin;
+            else if (a == "--loudness-dbfs") volume.target_rms = lin;
+            else volume.peak_ceiling = lin;
+            leveled = true;
         }
         else if (a == "--trim") trim = true;
         else if (a == "--fit") fit = true;
@@ -259,6 +285,7 @@ int main(int argc, char **argv)
         const ZeroVOX::zerovox_hparams &hp = model.get_hparams();
         if (controlled) model.set_prosody(prosody);
         if (fit) model.set_fitted(true);
+        if (leveled) model.set_volume(volume);
         if (target_seconds > 0.0)
             target_frames = (long)std::min(floor(target_seconds * hp.audio_sampling_rate / hp.audio_hop_size + 0.5), 1e9);
         if (target_frames > 0 || target_seconds > 0.0)
@@ -302,6 +329,11 @@ int main(int argc, char **argv)
         }
 
         const uint32_t nf = model.get_num_frames();
+        if (leveled)
+        {
+            const zv_level &lv = model.get_level();
+            printf("level: rms %.9g peak %.9g gain %.9g\n", (double)lv.rms, (double)lv.peak, (double)lv.gain);
+        }
         if (!align_path.empty())
         {
             FILE *af = fopen(align_path.c_str(), "w");
