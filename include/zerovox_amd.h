@@ -466,6 +466,14 @@ typedef enum { ZV_LAYER_VOC_RESBLOCK = 0, ZV_LAYER_ENC_FFT = 1, ZV_LAYER_DEC_BLO
                ZV_LAYER_DEC_TO_OUT = 8, ZV_LAYER_ENC_EMBED = 9, ZV_LAYER_ENC_MHA = 10, ZV_LAYER_ENC_FFN = 11,
                ZV_LAYER_DEC_ADAIN = 12, ZV_LAYER_ENC_LN = 13 } zv_layer_kind;
 zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint32_t rows, const float *style, float *out);
+/* Tests: one matrix-core accumulation chain at instruction level — out[32][32] = c0[32][32] + a[32][K] . b[K][32] (host, row-major)
+ * by ONE wave, every element one k-ordered chain on the instruction the product's kernels accumulate with:
+ *   form 0  v_mfma_f32_32x32x16_f16 (single-utterance and generic conv kernels): a, b are f16 (uint16 bit patterns)
+ *   form 1  v_mfma_f32_16x16x32_f16 (batch kernels), as four 16x16 tiles: a, b f16
+ *   form 2  v_mfma_f32_32x32x2_f32 (f32 linear layers, attention): a, b f32
+ * The promise "batch == stand-alone, streamed == whole, bit for bit" rests on forms 0 and 1 giving the same bits
+ * (tests/test_gpu_mfma_chain.py measures it on operands that span the f16 range).  K a multiple of 32, at most 4096, else ZV_ERR_ARG. */
+zv_status zv_debug_mfma_chain(zv_model *m, int form, const void *a, const void *b, const float *c0, uint32_t K, float *out);
 
 /* ---- test / measurement switches (none is needed in production; no reference counterpart: the reference's only run-time
  * switch is the thread count, src/zerovox.cpp:86-91).  The shipped library never reads the environment: a switch changes

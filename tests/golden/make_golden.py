@@ -4,6 +4,7 @@
 Run in the build container only (it needs /root/reference to have been compiled by `make -C oracle ref`):
     python tests/golden/make_golden.py          (all fixtures)
     python tests/golden/make_golden.py fresh    (only the fresh-seed fixtures)
+    python tests/golden/make_golden.py trained  (only the trained-like weight family's fixture)
     python tests/golden/make_golden.py heads    (only the encoder head-count fixture)
     python tests/golden/make_golden.py value_ranges    (only the value-range stage fixture)
     python tests/golden/make_golden.py resblock_geometries    (only the residual-block tap-count fixture)
@@ -348,6 +349,34 @@ def fresh_cases(tmp="/tmp"):
     os.remove(path)
 
 
+TRAINED_SEED = 2719         # a weights seed no other fixture uses
+
+
+def trained_cases(tmp="/tmp"):
+    """The reference's outputs on the "trained" weight family of synth.make_tensors (heavy-tailed f16 conv weights with exact
+    zeros, f16 subnormals and pruned channels; norm gains that include 0 and negatives): small geometry, ragged (N, T) = (18, 72),
+    all three stages, stored in full (the case of tests/test_oracle_golden.py::test_oracle_vs_reference_trained_family)."""
+    g = synth.SMALL
+    path = os.path.join(tmp, "golden_trained_small.gguf")
+    synth.write_checkpoint(path, g, TRAINED_SEED, family="trained")
+    _, tensors = gguf.read_gguf(path)
+    T, N = 72, 18
+    mel = synth.vocoder_mel(g, tensors, 26, T)
+    ids, puncts, style = synth.encoder_inputs(g, 27, N)
+    hid = synth.decoder_hidden(g, 28, T)
+    out = dict(geometry="small", family="trained", seed_w=TRAINED_SEED, T=T, N=N, seed_mel=26, seed_enc=27, seed_hidden=28)
+    out["wav"] = zvoracle.run_reference(path, T=T, voc=mel)["wav"]
+    out["mel"] = zvoracle.run_reference(path, T=T, dec=(hid, style))["mel"]
+    r = zvoracle.run_reference(path, T=T, N=N, enc=(ids, puncts, style), E=g.E)
+    for name in ("hidden", "features", "logdur", "energy", "pitch_bucket", "energy_bucket", "n_frames"):
+        out[name] = r[name]
+    assert all(np.isfinite(out[k]).all() for k in ("wav", "mel", "hidden", "features", "logdur", "energy"))
+    np.savez_compressed(os.path.join(HERE, "trained_small_seed%d_T%d_N%d.npz" % (TRAINED_SEED, T, N)), **out)
+    print("trained-family case: small seed %d frames %d wav rms %.4f peak %.3f" % (
+        TRAINED_SEED, r["n_frames"], float(np.sqrt(np.mean(out["wav"].astype(np.float64) ** 2))), float(np.max(np.abs(out["wav"])))))
+    os.remove(path)
+
+
 def value_ranges_case(tmp="/tmp"):
     """The reference's decoder and vocoder on the crafted stage inputs of tests/parity_helpers.value_range_stage_inputs (small
     geometry): a decoder hidden with per-channel offsets up to 1e3 sigma, constant channels and an all-zero band; a vocoder mel
@@ -445,6 +474,9 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["fresh"]:           # only the fresh-seed fixtures (the others are left as they are)
         fresh_cases()
         sys.exit(0)
+    if sys.argv[1:] == ["trained"]:         # only the trained-like weight family's fixture
+        trained_cases()
+        sys.exit(0)
     if sys.argv[1:] == ["value_ranges"]:    # only the value-range stage fixture
         value_ranges_case()
         sys.exit(0)
@@ -469,6 +501,7 @@ if __name__ == "__main__":
     add_floors()
     add_encoder_margins()
     fresh_cases()
+    trained_cases()
     heads_cases()
     value_ranges_case()
     resblock_geometries_case()

@@ -99,6 +99,39 @@ def test_oracle_vs_live_reference_fresh_seed(tmp_path):
             assert r["n_frames"] == int(z[k + "n_frames"])
 
 
+def test_oracle_vs_reference_trained_family(tmp_path):
+    """the "trained" weight family (synth.make_tensors: heavy-tailed f16 weights with exact zeros, f16 subnormals and pruned
+    channels, norm gains that include 0 and negatives), a weights seed no other fixture uses and ragged sizes, against the
+    reference's outputs stored in tests/golden/trained_small_seed2719_T72_N18.npz — the assertions of the fresh-seed case — and
+    live against oracle/_ref when it is present"""
+    from zerovox_cpp_amd import gguf, synth
+    from oracle import zvoracle
+    z = np.load(os.path.join(GOLD, "trained_small_seed2719_T72_N18.npz"))
+    live = zvoracle.have_reference()
+    g = synth.GEOMETRIES[str(z["geometry"])]
+    path = str(tmp_path / "t.gguf")
+    synth.write_checkpoint(path, g, int(z["seed_w"]), family=str(z["family"]))
+    _, tensors = gguf.read_gguf(path)
+    orc = zvoracle.Oracle(tensors)
+    T, N = int(z["T"]), int(z["N"])
+    mel = synth.vocoder_mel(g, tensors, int(z["seed_mel"]), T)
+    hid = synth.decoder_hidden(g, int(z["seed_hidden"]), T)
+    ids, puncts, style = synth.encoder_inputs(g, int(z["seed_enc"]), N)
+    assert np.array_equal(orc.vocoder(mel), z["wav"])
+    assert np.array_equal(orc.decoder(hid, style), z["mel"])
+    e = orc.encoder(g, ids, puncts, style, T)
+    for name in ("hidden", "features", "logdur", "energy", "pitch_bucket", "energy_bucket"):
+        assert np.array_equal(e[name], z[name]), name
+    assert e["n_frames"] == int(z["n_frames"])
+    if live:
+        assert np.array_equal(zvoracle.run_reference(path, T=T, voc=mel)["wav"], z["wav"])
+        assert np.array_equal(zvoracle.run_reference(path, T=T, dec=(hid, style))["mel"], z["mel"])
+        r = zvoracle.run_reference(path, T=T, N=N, enc=(ids, puncts, style), E=g.E)
+        for name in ("hidden", "features", "logdur", "energy", "pitch_bucket", "energy_bucket"):
+            assert np.array_equal(r[name], z[name]), name
+        assert r["n_frames"] == int(z["n_frames"])
+
+
 def test_instancenorm_known_answer():
     """the reference repo's only own golden data: utils/norm1dexample.json (PyTorch InstanceNorm1d(affine) pair,
     weights rounded to 4 decimals in the file -> 2e-4 tolerance)"""

@@ -25,6 +25,7 @@ SYMBOLS = [
     "zv_synthesize_batch_begin_phonemes", "zv_synthesize_fitted", "zv_synthesize_batch_fitted", "zv_synthesize_batch_begin_fitted",
     "zv_debug_voc_runs", "zv_debug_poison", "zv_encode_taps_target", "zv_synthesize_target", "zv_synthesize_batch_target",
     "zv_synthesize_batch_begin_target", "zv_synthesize_volume", "zv_synthesize_batch_volume", "zv_synthesize_batch_begin_volume",
+    "zv_debug_mfma_chain",
 ]
 
 
@@ -211,6 +212,8 @@ def load_library(path: Optional[str] = None):
     lib.zv_encode.argtypes = [vp, i32p, i32p, fp, u32, u32, fp, C.POINTER(u32)]
     lib.zv_encode_taps.argtypes = [vp, i32p, i32p, fp, u32, u32, u32, fp, C.POINTER(u32), fp, fp, fp, fp, i32p, i32p]
     lib.zv_debug_layer.argtypes = [vp, C.c_int, C.c_int, fp, u32, fp, fp]
+    if hasattr(lib, "zv_debug_mfma_chain"):
+        lib.zv_debug_mfma_chain.argtypes = [vp, C.c_int, C.c_void_p, C.c_void_p, fp, u32, fp]
     lib.zv_debug_set.argtypes = [C.c_char_p, C.c_int]
     lib.zv_debug_get.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     if hasattr(lib, "zv_debug_voc_runs"):        # (an older build named by ZEROVOX_AMD_LIB for an A/B run lacks it)
@@ -463,6 +466,23 @@ class Model:
         out = np.empty((orows, out_cols) if out_cols else (orows,), np.float32)
         st = None if style is None else np.ascontiguousarray(style, dtype=np.float32)
         self._chk(self.lib.zv_debug_layer(self.h, kind, index, _ptr(x), x.shape[0], _ptr(st), _ptr(out)))
+        return out
+
+    MFMA_32X32X16_F16, MFMA_16X16X32_F16, MFMA_32X32X2_F32 = 0, 1, 2
+
+    def debug_mfma_chain(self, form: int, a: np.ndarray, b: np.ndarray, c0: np.ndarray) -> np.ndarray:
+        """zv_debug_mfma_chain: out[32][32] = c0 + a[32][K] . b[K][32], every element one k-ordered chain of one wave on the
+        matrix-core instruction `form` (0: 32x32x16 f16, 1: 16x16x32 f16 — a, b float16; 2: 32x32x2 f32 — a, b float32)"""
+        dt = np.float32 if form == self.MFMA_32X32X2_F32 else np.float16
+        if a.dtype != dt or b.dtype != dt:
+            raise TypeError(f"form {form} takes {np.dtype(dt).name} operands, not {a.dtype} / {b.dtype}")
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        c0 = np.ascontiguousarray(c0, dtype=np.float32)
+        K = a.shape[1] if a.ndim == 2 else -1
+        if a.shape != (32, K) or b.shape != (K, 32) or c0.shape != (32, 32):
+            raise ValueError(f"shapes a {a.shape}, b {b.shape}, c0 {c0.shape}: want [32][K], [K][32], [32][32]")
+        out = np.empty((32, 32), np.float32)
+        self._chk(self.lib.zv_debug_mfma_chain(self.h, form, a.ctypes.data, b.ctypes.data, _ptr(c0), K, _ptr(out)))
         return out
 
     def voc_rate(self, stage: int) -> int:

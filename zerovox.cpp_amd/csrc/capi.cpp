@@ -1208,6 +1208,27 @@ zv_status zv_debug_layer(zv_model *m, int kind, int index, const float *x, uint3
     });
 }
 
+zv_status zv_debug_mfma_chain(zv_model *m, int form, const void *a, const void *b, const float *c0, uint32_t K, float *out)
+{
+    return guarded([&] {
+        ZV_NEED(m && a && b && c0 && out, "null argument");
+        ZV_NEED(form >= 0 && form <= 2, "form must be 0 (32x32x16 f16), 1 (16x16x32 f16) or 2 (32x32x2 f32)");
+        ZV_NEED(K >= 32 && K % 32 == 0 && K <= 4096, "K must be a multiple of 32, at most 4096");
+        Model &M = *m->m;
+        use_lane0(m);
+        const size_t elem = form == 2 ? 4 : 2, b_op = (size_t)32 * K * elem, b_c = 32 * 32 * 4;
+        Layout L;
+        const size_t o_a = L.at(b_op), o_b = L.at(b_op), o_c0 = L.at(b_c), o_out = L.at(b_c);
+        char *io = (char *)M.io_scratch(L.size());
+        ZV_HIP(hipMemcpyAsync(io + o_a, a, b_op, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_b, b, b_op, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_c0, c0, b_c, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(zv::launch_mfma_chain(M.stream(), form, io + o_a, io + o_b, (const float *)(io + o_c0), (int)K, (float *)(io + o_out)));
+        ZV_HIP(hipMemcpyAsync(out, io + o_out, b_c, hipMemcpyDeviceToHost, M.stream()));
+        M.sync();
+    });
+}
+
 zv_status zv_debug_set(const char *name, int value)
 {
     return guarded([&] {

@@ -292,6 +292,11 @@ hipError_t launch_norm_act_f16(hipStream_t s, const float *x, int ldx, int C, co
 hipError_t launch_linear(hipStream_t s, const float *x, int ldx, int in, const float *W, const float *b, int out, float *y,
                          int ldy, const float *extra, const Segs &segs);
 
+// ---- tests (zv_debug_mfma_chain): out[32][32] = c0 + a[32][K] * b[K][32] as ONE k-ordered chain of one wave, on the matrix-core
+// instruction the kernels of `form` use — 0: v_mfma_f32_32x32x16_f16, 1: v_mfma_f32_16x16x32_f16 (a, b f16), 2:
+// v_mfma_f32_32x32x2_f32 (a, b f32).  K a multiple of 32.  All pointers device.
+hipError_t launch_mfma_chain(hipStream_t s, int form, const void *a, const void *b, const float *c0, int K, float *out);
+
 // ---- encoder pieces (reference src/fs2encoder.cpp) -------------------------------------------------
 hipError_t launch_embed(hipStream_t s, const int32_t *ids, const int32_t *puncts, const float *wemb, int emb,
                         const float *pemb, int pdim, const float *posenc, float *x, int ld, const Segs &segs);

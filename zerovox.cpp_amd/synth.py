@@ -8,6 +8,10 @@ whose tensor names / shapes / dtypes are those the reference's stage classes loo
 Values come from a counter-based integer hash (splitmix64) -> float, so a (geometry, seed) pair
 produces bit-identical files on every machine: the GPU box regenerates the checkpoints the golden
 fixtures were made from instead of shipping 193 MB files.
+
+Two value families (make_tensors(..., family=)): "uniform", the default every fixture but one was made from, and "trained",
+the same tensors with the value distribution of a trained checkpoint (heavy tails, channel gains spread over octaves, exact zeros,
+f16 subnormals, pruned channels, norm gains that include 0 and negatives) — a statistical stand-in, not a trained model.
 """
 from __future__ import annotations
 
@@ -212,8 +216,85 @@ def sinusoid_table(n_position: int, d_hid: int) -> np.ndarray:
     return ang
 
 
-def make_tensors(g: Geometry, seed: int) -> List[Tuple[str, np.ndarray]]:
-    """All tensors of SURVEY.md Appx A in numpy (C-order) shape = reversed ggml ne."""
+FAMILIES = ("uniform", "trained")
+
+# the "trained" family: octave ranges of the three gains a weight carries (per input channel, per element, per output channel),
+# the shares of exact zeros and of f16 subnormals, the count and size (in tensor RMS) of the outliers, and the fewest channels
+# an axis needs before one of them is pruned
+TRAINED_OCT_IN, TRAINED_OCT_ELEM, TRAINED_OCT_OUT = 3.0, 2.0, 1.5
+TRAINED_ZERO_SHARE, TRAINED_SUBNORMAL_SHARE = 0.02, 0.01
+TRAINED_OUTLIERS, TRAINED_OUTLIER_RMS = 6, (4.0, 8.0)
+TRAINED_PRUNE_MIN = 32
+TRAINED_GAIN_RANGE = (-1.5, 3.0)                 # norm gains
+TRAINED_BIAS_MULT = 10.0                         # biases: ten times the uniform family's (+-0.1 -> +-1)
+# the vocoder has no norm between its convs and ends in tanh: biases of +-1 there saturate the waveform (RMS 0.87), +-0.15 keep
+# its RMS within 2 x the uniform family's
+TRAINED_VOC_BIAS_MULT = 1.5
+F16_SUBNORMAL_STEP = 2.0 ** -24                  # f16 subnormals are 1 .. 1023 of these
+
+
+def _octaves(seed: int, name: str, n: int, span: float) -> np.ndarray:
+    """n gains 2^U(-span, span)"""
+    return np.exp2((u01(seed, name, n) * 2.0 - 1.0) * span)
+
+
+def trained_pruned(seed: int, name: str, oc: int, ic: int) -> Tuple[int, int]:
+    """(output channel, input channel) of a "trained" conv tensor that are all zero; -1 where the axis has fewer than
+    TRAINED_PRUNE_MIN channels"""
+    u = u01(seed, name + "#t/prune", 2)
+    return (int(u[0] * oc) if oc >= TRAINED_PRUNE_MIN else -1, int(u[1] * ic) if ic >= TRAINED_PRUNE_MIN else -1)
+
+
+def _trained_matrix(seed: int, name: str, shape, rms: float) -> np.ndarray:
+    """normal x per-input-channel x per-element x per-output-channel octave gain, renormalised to `rms` (float64);
+    shape = (out, in) or (out, in, k)"""
+    n = int(np.prod(shape))
+    oc, ic = shape[0], shape[1]
+    ax = (slice(None), None) + (None,) * (len(shape) - 2)
+    w = normal(seed, name + "#t/z", shape).astype(np.float64)
+    w = w * _octaves(seed, name + "#t/ge", n, TRAINED_OCT_ELEM).reshape(shape)
+    w = w * _octaves(seed, name + "#t/gi", ic, TRAINED_OCT_IN)[(None,) + ax[:-1]]
+    w = w * _octaves(seed, name + "#t/go", oc, TRAINED_OCT_OUT)[ax]
+    return w * (rms / np.sqrt(np.mean(w * w)))
+
+
+def trained_conv_weight(seed: int, name: str, oc: int, ic: int, k: int, gain: float) -> np.ndarray:
+    """an f16 conv weight [oc][ic][k] with the marks of a trained one: heavy tails and channel gains spread over octaves
+    (_trained_matrix, at the uniform family's RMS gain / sqrt(ic k)), a few outliers at 4-8 x the RMS, ~1 % f16 subnormals,
+    ~2 % exact zeros of both signs, and one all-zero output and input channel where the axis has >= TRAINED_PRUNE_MIN channels"""
+    shape, n = (oc, ic, k), oc * ic * k
+    rms = gain / np.sqrt(ic * k)
+    w = _trained_matrix(seed, name, shape, rms).reshape(n)
+    sign = np.where(u01(seed, name + "#t/sign", n) < 0.5, -1.0, 1.0)
+    kind = u01(seed, name + "#t/kind", n)
+    sub = kind < TRAINED_SUBNORMAL_SHARE
+    steps = np.clip(np.rint(np.exp2(u01(seed, name + "#t/sub", n) * 10.0)), 1, 1023)       # 2^-24 .. 1023 x 2^-24
+    w = np.where(sub, sign * steps * F16_SUBNORMAL_STEP, w)
+    zero = (kind >= TRAINED_SUBNORMAL_SHARE) & (kind < TRAINED_SUBNORMAL_SHARE + TRAINED_ZERO_SHARE)
+    w = np.where(zero, sign * 0.0, w)
+    n_out = max(1, min(TRAINED_OUTLIERS, n // 1024))                  # one per 1 024 elements, so that they do not set the RMS
+    u_out = u01(seed, name + "#t/outlier", 2 * n_out)
+    at = np.minimum((u_out[:n_out] * n).astype(np.int64), n - 1)
+    lo, hi = TRAINED_OUTLIER_RMS
+    w[at] = sign[at] * rms * (lo + (hi - lo) * u_out[n_out:])
+    w = w.reshape(shape)
+    po, pi = trained_pruned(seed, name, oc, ic)
+    if po >= 0:
+        w[po] = 0.0
+    if pi >= 0:
+        w[:, pi] = 0.0
+    return w.astype(np.float16)
+
+
+def make_tensors(g: Geometry, seed: int, family: str = "uniform") -> List[Tuple[str, np.ndarray]]:
+    """All tensors of SURVEY.md Appx A in numpy (C-order) shape = reversed ggml ne.
+
+    family "uniform": every weight uniform in +-sqrt(3 / fan-in), norm gains 1 +- 0.1, biases +-0.1.  family "trained": the same
+    names, shapes and dtypes with the value distribution of a trained checkpoint (DESIGN.md "The trained-like weight family"):
+    a statistical stand-in, not a trained model."""
+    if family not in FAMILIES:
+        raise ValueError(f"unknown weight family {family!r}")
+    trained = family == "trained"
     E, F = g.E, g.conv_filter_size
     T: List[Tuple[str, np.ndarray]] = []
 
@@ -221,23 +302,51 @@ def make_tensors(g: Geometry, seed: int) -> List[Tuple[str, np.ndarray]]:
         T.append((name, np.ascontiguousarray(arr)))
 
     def conv_w(name, oc, ic, k, gain=1.0):           # f16, ggml ne [k, ic, oc]
+        if trained:
+            return add(name, trained_conv_weight(seed, name, oc, ic, k, gain))
         amp = gain * np.sqrt(3.0 / (ic * k))
         add(name, sym(seed, name, (oc, ic, k), amp).astype(np.float16))
 
     def lin_w(name, out, inp, gain=1.0):             # f32, ggml ne [in, out]
+        if trained:
+            return add(name, _trained_matrix(seed, name, (out, inp), gain / np.sqrt(inp)).astype(np.float32))
         add(name, sym(seed, name, (out, inp), gain * np.sqrt(3.0 / inp)))
 
     def vec(name, n, amp=0.1, center=0.0):
+        if trained and center == 1.0:                # a norm gain: spread over TRAINED_GAIN_RANGE, one exact 0, one forced negative
+            lo, hi = TRAINED_GAIN_RANGE
+            v = (lo + (hi - lo) * u01(seed, name + "#t", n)).astype(np.float32)
+            at = np.minimum((u01(seed, name + "#t/at", 2) * n).astype(np.int64), n - 1)
+            v[at[0]] = 0.0
+            if n > 1:
+                i = at[1] if at[1] != at[0] else (at[1] + 1) % n
+                v[i] = np.float32(lo)
+            return add(name, v)
+        if trained:
+            amp = amp * (TRAINED_VOC_BIAS_MULT if name.startswith("_meldec.") else TRAINED_BIAS_MULT)
         add(name, (sym(seed, name, (n,), amp) + np.float32(center)).astype(np.float32))
 
+    def emb(name, key, shape, amp, padding_row=False):
+        if trained:                                  # normal at the uniform family's RMS; row 0 is padding_idx
+            e = normal(seed, key + "#t", shape, amp / np.sqrt(3.0))
+            if padding_row:
+                e[0] = 0.0
+            return add(name, e)
+        add(name, sym(seed, key, shape, amp))
+
     # ---- vocoder statistics
-    vec("hifigan.mean", g.num_mels, amp=1.0, center=-1.0)
-    vec("hifigan.scale", g.num_mels, amp=0.5, center=1.0)
+    if trained:
+        add("hifigan.mean", (sym(seed, "hifigan.mean#t", (g.num_mels,), 2.0) + np.float32(-5.0)).astype(np.float32))
+        u = u01(seed, "hifigan.scale#t", g.num_mels)
+        add("hifigan.scale", (0.05 * np.exp(u * np.log(3.0 / 0.05))).astype(np.float32))
+    else:
+        vec("hifigan.mean", g.num_mels, amp=1.0, center=-1.0)
+        vec("hifigan.scale", g.num_mels, amp=0.5, center=1.0)
 
     # ---- FastSpeech2 encoder
     add("sinusoid_encoding_table", sinusoid_table(g.max_seq_len + 1, E))
-    add("_pe._enc.src_word_emb.w", sym(seed, "_pe._enc.src_word_emb.w", (NUM_PHONEMES + 1, g.emb_dim), 1.0))
-    add("_pe._enc.punct_embed.w", sym(seed, "_pe._enc.punct_embed.w", (NUM_PUNCTS + 1, g.punct_emb_dim), 1.0))
+    emb("_pe._enc.src_word_emb.w", "_pe._enc.src_word_emb.w", (NUM_PHONEMES + 1, g.emb_dim), 1.0, padding_row=True)
+    emb("_pe._enc.punct_embed.w", "_pe._enc.punct_embed.w", (NUM_PUNCTS + 1, g.punct_emb_dim), 1.0, padding_row=True)
     for i in range(g.encoder_layer):
         p = f"_pe._enc.laystk.{i}."
         for nm in ("w_qs", "w_ks", "w_vs", "fc"):
@@ -265,8 +374,8 @@ def make_tensors(g: Geometry, seed: int) -> List[Tuple[str, np.ndarray]]:
         vec(p + "conv_layer.layer_norm_2.b", V)
         lin_w(p + "linear_layer.w", 1, V, gain=lin_gain)
         add(p + "linear_layer.b", np.array([lin_bias], dtype=np.float32))
-    add("_pe._var_adapt.pitch_embedding.w", sym(seed, "pitch_embedding", (g.ve_n_bins, E), 0.5))
-    add("_pe._var_adapt.energy_embedding.w", sym(seed, "energy_embedding", (g.ve_n_bins, E), 0.5))
+    emb("_pe._var_adapt.pitch_embedding.w", "pitch_embedding", (g.ve_n_bins, E), 0.5)
+    emb("_pe._var_adapt.energy_embedding.w", "energy_embedding", (g.ve_n_bins, E), 0.5)
 
     # ---- StyleTTS mel decoder
     R = g.residual_dim
@@ -328,9 +437,9 @@ def make_tensors(g: Geometry, seed: int) -> List[Tuple[str, np.ndarray]]:
     return T
 
 
-def write_checkpoint(path: str, g: Geometry, seed: int, trim_dims: bool = False) -> None:
+def write_checkpoint(path: str, g: Geometry, seed: int, trim_dims: bool = False, family: str = "uniform") -> None:
     from .gguf import write_gguf
-    write_gguf(path, g.kv(), make_tensors(g, seed), arch=ARCH, trim_dims=trim_dims)
+    write_gguf(path, g.kv(), make_tensors(g, seed, family), arch=ARCH, trim_dims=trim_dims)
 
 
 # ---- seeded synthetic inputs -----------------------------------------
