@@ -452,6 +452,23 @@ def conv_tile_split(cout):
     return nt, done, nt - done
 
 
+# ---- attention and LayerNorm-tail limits (tests/test_gpu_attention_heads.py, tests/test_boundary_cpu.py) --------------------
+# restated from zerovox.cpp_amd/csrc/stage_plan.h (att_plan, layernorm_tail_ok); tests/test_stage_plan_cpu.py compares them with
+# what the header gives
+
+ATT_NS_MAX, ATT_LDS_MAX, LN_TAIL_MAX = 144, 160 * 1024 - 4096, 64 * 12
+
+
+def mfma_max_tokens(dk):
+    """largest n the matrix-core attention kernel takes at head dim dk (0: never)"""
+    if dk % 4 or dk > 2 * ATT_NS_MAX:
+        return 0
+    n = 0
+    while ((64 * (dk | 1) + 1 + 64 * ((n + 1 + 31) // 32 * 32)) * 4) <= ATT_LDS_MAX:
+        n += 1
+    return n
+
+
 def encoder_margins(ex, alt):
     """the reference semantics' own re-association noise on one encoder run, in the form encoder_decisions_vs_reference reads:
     ex = the oracle in the reference's summation order (bit-exact to it: tests/test_oracle_golden.py), alt = the oracle in

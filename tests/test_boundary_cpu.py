@@ -232,9 +232,8 @@ def test_encdec_geometries_reach_what_they_claim(ckpt):
     carry the KVs' shapes"""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from parity_helpers import conv_tile_split
+    from parity_helpers import ATT_NS_MAX, LN_TAIL_MAX, conv_tile_split
     from zerovox_cpp_amd import synth
-    ATT_NS_MAX, LN_TAIL_MAX = 144, 64 * 12             # misc_kernels.hip
     split = {"medium": ((17, 17, 0), (33, 33, 0)), "medium_e576": ((18, 16, 2), (36, 32, 4)),
              "medium_e720": ((23, 16, 7), (45, 40, 5)), "small_e304": ((10, 8, 2), (19, 16, 3)),
              "medium_e1024": ((32, 32, 0), (64, 64, 0))}

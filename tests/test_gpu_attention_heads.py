@@ -1,5 +1,6 @@
 """-m gpu: the encoder at `encoder.head` = 1, 3, 4, 8 (synth.MEDIUM_H*: MEDIUM with only the head count changed; every other
-test runs H = 2).  E = 528, so the head dim dk = E / H is 528, 176, 132 or 66, and launch_attention (misc_kernels.hip) picks:
+test runs H = 2).  E = 528, so the head dim dk = E / H is 528, 176, 132 or 66, and launch_attention (encoder_kernels.hip; the rule:
+stage_plan.h att_plan, restated once in parity_helpers.mfma_max_tokens) picks:
   * attention_mfma_kernel only for dk % 4 == 0 and dk <= 2 x ATT_NS_MAX = 288 (H = 3, 4) while its LDS,
     (64 (dk | 1) + 1 + 64 round_up(n, 32)) x 4 bytes, fits ATT_LDS_MAX = 156 KiB: n <= 416 tokens at dk = 176, n <= 480 at dk = 132
     (and by default only with >= 48 workgroups, i.e. for batches; ZV_ATT_MFMA = 1 forces it where it is legal).  dk = 176 is
@@ -14,20 +15,11 @@ import os
 import numpy as np
 import pytest
 
+from parity_helpers import mfma_max_tokens as _mfma_max_tokens
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 HEADS = {"medium_h1": 1, "medium_h3": 3, "medium_h4": 4, "medium_h8": 8}
-ATT_NS_MAX, ATT_LDS_MAX = 144, 160 * 1024 - 4096        # misc_kernels.hip
-
-
-def _mfma_max_tokens(dk):
-    """largest n the matrix-core kernel takes at head dim dk (0: never)"""
-    if dk % 4 or dk > 2 * ATT_NS_MAX:
-        return 0
-    n = 0
-    while ((64 * (dk | 1) + 1 + 64 * ((n + 1 + 31) // 32 * 32)) * 4) <= ATT_LDS_MAX:
-        n += 1
-    return n
 
 
 def test_mfma_token_limits_at_these_head_dims():

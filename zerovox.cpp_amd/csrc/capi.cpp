@@ -397,7 +397,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         zv::Batch bt = zv::Batch::single(n, T, r.num_phonemes[0]);
         bt.has_targets = tg;
         if (r.fitted && !taps) bt.d_frm_live = (zv::Seg *)(io + o_live);
-        if (!taps && M.dec_runs_on(bt)) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
+        if (!taps && M.dec_plan(bt).runs) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
         ZV_HIP(hipMemcpyAsync(d_ids, r.ids[0], b_ids, hipMemcpyHostToDevice, M.stream()));
         ZV_HIP(hipMemcpyAsync(d_pun, r.puncts[0], b_ids, hipMemcpyHostToDevice, M.stream()));
         ZV_HIP(hipMemcpyAsync(d_sty, r.styles[0], E * 4, hipMemcpyHostToDevice, M.stream()));
@@ -768,7 +768,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
     if (dur) bt.d_cum = (int32_t *)(io + o_cum);
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
-    if (M.dec_runs_on(bt)) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
+    if (M.dec_plan(bt).runs) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
     if (vol)
     {
         bt.d_vol = (const float *)(d_in + i_vol);
@@ -783,7 +783,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
     // run.  Same kernels on the same rows: same bits.
-    const int G = zv::voc_tail_groups(zv::knob(zv::ZV_TAIL_GROUPS), bt.nseg, wav_bytes, M.profiling, M.dbg_layer.kind >= 0);
+    const int G = zv::voc_tail_groups(bt.nseg, wav_bytes, M.profiling, M.dbg_layer.kind >= 0);
     // from here on work is queued that reads the lane's pinned input block and writes its I/O block: if anything fails the
     // lane's streams are drained before the error leaves, so an idle-looking lane never has work in flight
     try

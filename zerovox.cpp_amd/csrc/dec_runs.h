@@ -1,6 +1,6 @@
 // dec_runs.h — run-shortened decoding (DESIGN.md "Run-shortened decoding"): which rows of a padded utterance the StyleTTS decoder
 // computes, where a row it skipped finds its value, and how the InstanceNorm statistics count the rows it skipped.  Plain integer
-// arithmetic and one f64 sum, shared by the kernels (misc_kernels.hip), the schedule (decoder.cpp) and the host-side test
+// arithmetic and one f64 sum, shared by the kernels (runs_kernels.hip, norm_kernels.hip), the schedule (decoder.cpp) and the host-side test
 // (tests/native/dec_runs_check.cpp): nothing here needs HIP.
 //
 // Behind an utterance's n frames `hidden` is zero up to its capacity T.  Every decoder conv has 1 or 3 taps and every norm is a

@@ -33,32 +33,6 @@ Model::DecLayout Model::dec_layout(DeviceArena &a, const Batch &bt) const
     return d;
 }
 
-// Two ways to feed a conv its normalised operand, same bits (tests): (a) the conv normalises while it stages its
-// input tile (PRO_NORM_ACT) — no extra launch, right for a very short utterance where every launch is latency; (b) one
-// pass writes the f16 operand (launch_norm_act_f16) and the conv copies it (PRO_RAW_F16) — right when launches have
-// many rounds of workgroups: a 1 056-wide conv stages every input tile 9 times (once per group of 128 output
-// channels), so (a) repeats the f32 prologue 9 times and reads twice the bytes.
-bool Model::dec_prepass_on(const Batch &bt) const
-{
-    const int pre_env = knob(ZV_DEC_PREPASS);      // test / A-B hook
-    // (round 4: with the single-utterance conv form's loader waves the pass pays from 256 frames on — it takes the statistics launch's
-    // place and leaves the loaders a plain copy: one utterance of 128 / 256 / 512 / 1 024 frames 1.32 / 1.345 / 1.62 / 2.16 ms fused,
-    // 1.33 / 1.33 / 1.58 / 2.07 ms with the pass)
-    return pre_env >= 0 ? pre_env != 0 : (size_t)bt.t_max * bt.nseg >= 256;
-}
-
-// batches (ZV_DEC_RUNS = 1): by capacity, with the threshold of ZV_VOC_RUNS and the other batch switches, so that a single utterance
-// keeps its schedule; no sweep of capacities below it is on record
-bool Model::dec_runs_on(const Batch &bt) const
-{
-    const int k = knob(ZV_DEC_RUNS);
-    return !bt.d_frm_live && dbg_layer.kind < 0 && dec_prepass_on(bt) && batch_switch(k, batch_rows((long)bt.t_rows));
-}
-
-// densely packed decoding (dec_runs.h): wherever a batch has a run table.  One utterance has nothing to pack: its rows are tiled as
-// they are either way, and the pass that packs would be one launch more
-bool Model::dec_pack_on(const Batch &bt) const { return bt.d_dec_runs != nullptr && bt.nseg > 1 && knob(ZV_DEC_PACK) != 0; }
-
 // a residual block reaches as far as the longer of its two paths (conv1 -> conv2, the shortcut); the concat joins the encode
 // blocks' path and the asr conv's; the output conv ends the chain
 int Model::dec_reach_frames() const
@@ -77,15 +51,16 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
     const DecLayout lay = dec_layout(stage_arena(bt), bt);
     // Run-shortened decoding: every launch below takes its extents from the run table the encoder wrote, the statistics add the
     // dropped blocks back, the last conv writes the compact mel and one pass expands it to d_mel's T rows per utterance.
+    const DecPlan plan = dec_plan(bt);
     const bool runs = bt.d_dec_runs != nullptr;
-    if (runs && !dec_runs_on(bt)) fail(ZV_ERR_ARG, "internal: a decoder run table on a schedule that takes none");
+    if (runs && !plan.runs) fail(ZV_ERR_ARG, "internal: a decoder run table on a schedule that takes none");
     const Segs fr = runs ? Segs{bt.d_dec_runs, bt.nseg, bt.t_max, bt.frm1} : bt.frames();
     // Densely packed decoding (dec_runs.h): the table's row0 are the utterances' slots in ONE packed row space.  The elementwise and
     // statistics launches keep the per-utterance table `fr`; every conv runs over the packed rows as the one segment of entry nseg
     // (`frc`), planned as the batch it is (conv_plan.h ConvPackedUtts), and stores its partial sums by global block, which is where
     // the finalising launches look (DEC_TAB_PACKED) — the last block of an utterance whose rows are no multiple of 32 apart
     // (DEC_TAB_CONV_TAIL).  The f16 operands carry zeros in the guard rows; what the convs leave in guard rows is never read.
-    const bool pack = runs && dec_pack_on(bt);
+    const bool pack = plan.pack;
     const Segs frc = pack ? Segs{bt.d_dec_runs + bt.nseg, 1, lay.rows, Seg{0, 0, 0, 0}} : fr;
     const ConvPackedUtts packed_utts(pack ? bt.nseg : 0);
     const int tab_mode = runs ? DEC_TAB_RUNS | (pack ? DEC_TAB_PACKED : 0) : 0, conv_tail = pack ? DEC_TAB_CONV_TAIL : 0;
@@ -107,7 +82,7 @@ void Model::decode_dev(const Batch &bt, const float *d_hidden, const float *d_st
         Ld = 0;
         for (const Seg &g : tab) Ld += g.rows;
     }
-    const bool prepass = dec_prepass_on(bt);       // (see there)
+    const bool prepass = plan.prepass;
 
     // D2: all ten AdaIN fc layers at once for every utterance's style vector            (src/stylettsdec.cpp:175-189)
     ZV_LAUNCH("dec_adain_fc", 4.0 * dec_.fc_out * (Ed + 2), 2.0 * S * dec_.fc_out * Ed,

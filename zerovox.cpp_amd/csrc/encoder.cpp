@@ -33,16 +33,15 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
     if (n_longest > enc_.posenc_rows) fail(ZV_ERR_ARG, "%d phonemes exceed the %d rows of the sinusoid table", n_longest, enc_.posenc_rows);
     const EncLayout lay = enc_layout(stage_arena(bt), bt);
     const Segs tk = bt.tokens(), fr = bt.frames_cap();       // (the regulator clamps and zero-fills by capacity, fitted or not)
-    const Segs tkm = knob(ZV_LINEAR_MERGED) != 0 ? bt.tokens_merged() : tk;      // the per-token layers (linear, 1-tap conv, plain LayerNorm) see one dense segment
+    const EncPlan plan = enc_plan((int)E(), enc_.dur.V, dbg_layer.kind >= 0);
+    const Segs tkm = plan.merged ? bt.tokens_merged() : tk;      // the per-token layers (linear, 1-tap conv, plain LayerNorm) see one dense segment
     const int Ed = (int)E(), H = hp.encoder_head, dk = Ed / H;
     const size_t n = bt.n_rows;
     const double nd = (double)n;
     const int Vp = lay.Vp;
     float *const x = lay.x, *const y = lay.y, *const qkv = lay.qkv, *const o = lay.o, *const f = lay.f, *const va = lay.va, *const vb = lay.vb;
     _Float16 *const hh = lay.hh;
-    // LayerNorm launches that carry tail work (kernels.h: launch_layernorm_tail): the style add, the predictors' linear layer, the
-    // bucket + embedding step — 6 launches fewer per call, same operations in the same order (ZV_LN_TAIL = 0: separate launches)
-    const bool tails = dbg_layer.kind < 0 && knob(ZV_LN_TAIL) != 0 && layernorm_tail_ok(Ed) && layernorm_tail_ok(enc_.dur.V);
+    const bool tails = plan.tails;       // LayerNorm launches that carry tail work (kernels.h: launch_layernorm_tail)
     const EncoderTaps t = lay.t;
 
     ZV_LAUNCH("enc_embed", 8.0 * nd * Ed, 1.0 * nd * Ed,
@@ -172,7 +171,7 @@ Model::EncoderTaps Model::encode_dev(const Batch &bt, const int32_t *d_ids, cons
         ZV_LAUNCH("enc_live_frames", 36.0 * bt.nseg, 0.0, launch_live_frames(stream(), d_nframes, bt.d_frm_live, fr));
     // run-shortened decoding: the decoder's run table, from the same counts
     if (bt.d_dec_runs)
-        ZV_LAUNCH("enc_dec_runs", 36.0 * bt.nseg, 0.0, launch_dec_runs(stream(), d_nframes, bt.d_dec_runs, fr, dec_reach_frames(), dec_pack_on(bt)));
+        ZV_LAUNCH("enc_dec_runs", 36.0 * bt.nseg, 0.0, launch_dec_runs(stream(), d_nframes, bt.d_dec_runs, fr, dec_reach_frames(), dec_plan(bt).pack));
     return t;
 }
 

@@ -1,6 +1,6 @@
 // fit_durations.h — target durations (include/zerovox_amd.h "target durations"): the integer rule that turns an utterance's predicted
 // durations and a target frame count into per-phoneme frame counts that sum to the target exactly.  Plain arithmetic shared by
-// fit_durations_kernel (misc_kernels.hip) and the host-side test (tests/native/fit_durations_check.cpp): nothing here needs HIP.
+// fit_durations_kernel (regulator_kernels.hip) and the host-side test (tests/native/fit_durations_check.cpp): nothing here needs HIP.
 //
 // Why integers: the shares must sum to the target whatever order a workgroup adds them in, and a caller must be able to restate
 // them bit for bit.  So the f32 duration is turned into a 16.16 fixed-point weight ONCE (fit_weight, one exactly rounded double

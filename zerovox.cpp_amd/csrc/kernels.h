@@ -12,6 +12,7 @@
 
 #include "conv_plan.h"     // the launchers' plans: ConvPrologue, conv_gemm_groups / _tiles / _units, pair_supported, triple_supported, block64_supported, TRIPLE_MAX_DIL
 #include "voc_plan.h"
+#include "stage_plan.h"    // att_plan, linear_plan, lr_plan, layernorm_tail_ok; the schedules' enc_plan and dec_plan
 #include "level.h"        // volume controls: LEVEL_CHUNK_SAMPLES, LEVEL_VOL_STRIDE, LevelRow
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
@@ -327,8 +328,7 @@ hipError_t launch_add_layernorm(hipStream_t s, const float *x, int ldx, const fl
 //   bucket[row] = clamp((int)(pred * (nbins - 1) + 0.5)); feat[row][:embC] += emb[bucket][:]   (launch_bucket_embed_add; needs dot_w)
 //     ctl (or null): pred -> pred * ctl[seg][ctl_field] + ctl[seg][ctl_field + 1] before the bucket (pred itself is stored raw)
 //     pctl (or null): per-phoneme rows offset to their field (PCTL_PITCH / PCTL_ENERGY): then pred -> pred + pctl[row * PCTL_STRIDE]
-// layernorm_tail_ok(C): the tail exists in the rows-in-registers form only (C <= 768)
-bool       layernorm_tail_ok(int C);
+// stage_plan.h layernorm_tail_ok(C): the tail exists in the rows-in-registers form only (C <= 768); a wider C is refused
 hipError_t launch_layernorm_tail(hipStream_t s, const float *x, int ldx, const float *res, int ldr, int C, int Cp, const float *w,
                                  const float *b, float eps, float *y, int ldy, const Segs &segs, const float *post, int post_seg,
                                  const float *dot_w, const float *dot_b, float *pred, const float *emb, int nbins, int embC, float *feat,

@@ -1,6 +1,6 @@
 // level.h — volume controls (include/zerovox_amd.h "volume controls"): how an utterance's level is measured, how the gain follows
 // from it and from a zv_volume, and what the zv_level reports.  Plain arithmetic shared by level_measure_kernel / level_apply_kernel
-// (misc_kernels.hip) and the host-side test (tests/native/level_check.cpp): nothing here needs HIP.
+// (level_kernels.hip) and the host-side test (tests/native/level_check.cpp): nothing here needs HIP.
 //
 // Why integers: the sum of squares is taken over 16-byte loads, lanes, waves and workgroups, and a caller must be able to restate
 // the gain bit for bit.  So every sample is turned into a 1.19 fixed-point magnitude ONCE (level_quant: one exactly rounded double

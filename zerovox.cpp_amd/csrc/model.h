@@ -83,8 +83,8 @@ struct Batch
     Seg *d_frm_live = nullptr;
     // Run-shortened decoding (dec_runs.h, kernels.h launch_dec_runs): the decoder's run table, Seg [nseg] in HBM outside the arena, or
     // null.  The encoder writes it behind the length regulator from the frame counts and the decoder takes every extent from it; the
-    // entry points set it where Model::dec_runs_on says so.  A single utterance has a one-entry table.  Keyed like d_frm_live.
-    // A batch's block holds nseg + 1 entries: densely packed decoding (dec_runs.h, Model::dec_pack_on) writes the packed rows as one
+    // entry points set it where Model::dec_plan's `runs` says so.  A single utterance has a one-entry table.  Keyed like d_frm_live.
+    // A batch's block holds nseg + 1 entries: densely packed decoding (dec_runs.h, Model::dec_plan's `pack`) writes the packed rows as one
     // segment into the last.
     Seg *d_dec_runs = nullptr;
     // Target durations (include/zerovox_amd.h "target durations"): some utterance's ctl row carries a target frame count, so the
@@ -217,15 +217,13 @@ class Model
     bool voc_runs_off = false;
     bool voc_runs_on(const Batch &b) const;
     const Seg *voc_runs_last(int *n) { *n = lane().runs_n; return lane().runs_tab; }
-    // Run-shortened decoding of the unfitted synthesize paths (decoder.cpp): whether a chain over b gets a run table (Batch::d_dec_runs).
-    // Off in fitted mode, under a dbg_layer tap, where the operand pre-pass is off and by ZV_DEC_RUNS; never in a stand-alone decode,
-    // whose hidden comes from the caller
-    bool dec_runs_on(const Batch &b) const;
-    // Densely packed decoding (dec_runs.h): a chain with a run table packs the utterances' compact rows into one row space, which the
-    // decoder's convs then run over as one segment.  Wherever a batch of several utterances has a run table (so: never in fitted
-    // mode, under a tap, in a stand-alone decode or with the pre-pass off) unless ZV_DEC_PACK = 0
-    bool dec_pack_on(const Batch &b) const;
-    bool dec_prepass_on(const Batch &b) const;       // the decoder's convs read an f16 operand written by a pass of its own
+    // The decoder's regime over b (stage_plan.h dec_plan).  runs: whether a chain over b gets a run table (Batch::d_dec_runs) — the
+    // unfitted synthesize paths; never a stand-alone decode, whose hidden comes from the caller.  pack: a chain with a run table packs
+    // the utterances' compact rows into one row space, which the decoder's convs then run over as one segment (dec_runs.h).
+    DecPlan dec_plan(const Batch &b) const
+    {
+        return zv::dec_plan(b.nseg, b.t_max, b.t_rows, b.d_frm_live != nullptr, dbg_layer.kind >= 0, b.d_dec_runs != nullptr);
+    }
     // frames the decoder's 3-tap convs reach to either side, from the loaded layers (the longest path through its blocks)
     int  dec_reach_frames() const;
     void sync();

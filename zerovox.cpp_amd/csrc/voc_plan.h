@@ -160,5 +160,10 @@ inline int voc_tail_groups(int sw, int nseg, size_t wav_bytes, bool profiling, b
     if (sw <= 1 || nseg < 4 || wav_bytes < TAIL_GROUPS_MIN_BYTES || profiling || dbg_active) return 1;
     return sw < nseg / 2 ? sw : nseg / 2;
 }
+// the call's own: the switch read here, when the call is planned
+inline int voc_tail_groups(int nseg, size_t wav_bytes, bool profiling, bool dbg_active)
+{
+    return voc_tail_groups(knob(ZV_TAIL_GROUPS), nseg, wav_bytes, profiling, dbg_active);
+}
 
 }  // namespace zv
