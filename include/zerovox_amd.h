@@ -15,6 +15,7 @@
  *   *_phonemes         the same with per-phoneme controls as well (zv_phoneme_controls) and the phoneme timings out
  *   *_target           the same with a target frame count the utterance's durations are fitted to
  *   *_volume           the same with a gain, a loudness target and a peak ceiling per utterance (zv_volume) and the measured level out
+ *   *_envelope         the same with per-phoneme gains, cross-fades and fades per utterance (zv_envelope)
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file        src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -365,7 +366,7 @@ zv_status zv_synthesize_batch_begin_target(zv_model *m, uint32_t lane, uint32_t 
  * not finite, gain is outside [0, 1000], or target_rms or peak_ceiling is outside [0, 1] (the message names the entry point, the
  * utterance and the field).  zv_synthesize_batch_begin_volume is finished by zv_synthesize_batch_end.
  * Out of scope: zv_vocode*, zv_vocode_device and zv_vocode_stream (they have no n_frames, and a stream has not seen the whole
- * utterance when its first chunk leaves); per-phoneme gain and fades. */
+ * utterance when its first chunk leaves).  Per-phoneme gain and fades: the amplitude envelope below. */
 typedef struct
 {
     float gain;             /* linear, 0 .. 1000; multiplies the result of the loudness target (1 = none)            */
@@ -391,6 +392,69 @@ zv_status zv_synthesize_batch_begin_volume(zv_model *m, uint32_t lane, uint32_t 
                                            const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
                                            const zv_phoneme_controls *phonemes, int32_t *const *durations,
                                            const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels);
+/* ---- amplitude envelope: per-phoneme gain, cross-fades and fades -----------------------------------------------------------------
+ * The per-phoneme form of the volume controls.  A caller who has the phoneme timings (durations[]) can stress a word, duck a phrase or
+ * soften the cut where T truncates an utterance, without walking the waveform on the host: the envelope forms scale the finished
+ * waveform on the device, inside the same captured graph and — for a large batch — per tail group, ahead of that group's download
+ * and ahead of the volume passes, so a loudness target or a peak ceiling holds on what the caller receives.  The gains and the
+ * scalars travel in the batch's device input block like the other controls, so a replayed graph picks up new values.
+ * The rule, per utterance, with hop = audio_hop_size, T the capacity, nf = min(n_frames, T), n = nf*hop, x[0 .. T*hop) the waveform
+ * the same call gives without an envelope and without volume, and durations[] the phoneme timings of that call as the _phonemes
+ * forms define them (after prosody, per-phoneme controls, forced frames and a target), start_i the sum of the durations before i:
+ *   gains    G_i = (int64)((double)phoneme_gain[i] * 65536.0 + 0.5), truncating, so 0 <= G_i <= 2^20; phoneme_gain == NULL: every
+ *            G_i = 65536.  Tokens at or past num_phonemes own no frame and are never read.
+ *   frames   for 0 <= f < nf: F[f] = G_i of the phoneme that owns frame f (start_i <= f < start_i + durations[i]; a phoneme of 0
+ *            frames owns nothing).  Outside that range F is edge-replicated: F[f < 0] = F[0], F[f >= nf] = F[nf - 1].
+ *   windows  r = ramp_frames, W = 2r + 1, A[f] = sum of F[j] for j = f - r .. f + r: an integer sum, its order does not matter.
+ *   knots    B[f] = A[f - 1] + A[f] for 0 <= f <= nf, at the frame starts; B[f] <= 2 * 129 * 2^20 < 2^29, one uint32.
+ *   sample   s = f*hop + j with 0 <= j < hop; every step one IEEE f64 operation (the library builds with -ffp-contract=off):
+ *            1. num = B[f]*(hop - j) + B[f + 1]*j for s < n, num = B[nf]*hop for s >= n (int64, below 2^38)
+ *            2. den = 2*W*hop*65536
+ *            3. d = (double)num / (double)den
+ *            4. Fi = fade_in_samples > 0 and s < Fi: t = (double)s / (double)Fi; d = d * t
+ *            5. Fo = fade_out_samples > 0 and k = n - 1 - s < Fo: t = (double)max(k, 0) / (double)Fo; d = d * t (so s >= n - 1 gives 0)
+ *            6. e = (float)d; y[s] = x[s] * e, one f32 multiply
+ *   nf == 0  there are no knots: e = 1 for every sample when Fo == 0, e = 0 when Fo > 0.
+ *   volume   if the call carries a zv_volume or asks for levels: measured on y over y[0 .. n) and applied to y, wav[s] = y[s] * g —
+ *            two separately rounded f32 multiplies, in that order.  The zv_level reports the level and the peak of the enveloped
+ *            speech, before g.
+ * What follows: the gain curve is piecewise linear and continuous.  Inside a phoneme of more than 2r + 2 frames it is exactly
+ * (float)(G_i / 65536) from r + 1 frames after the phoneme's start to r + 1 frames before its end (knots start_i + r + 1 ..
+ * start_i + durations[i] - r - 1: one whole frame at exactly 2r + 3 frames); a transition spans 2r + 2 frames centred on the
+ * boundary.  e never leaves [min G, max G] / 65536.  When every G_i is 65536 and both fades are 0, num == den and e == 1.0f:
+ * envelope == NULL, a zeroed struct and all-ones gains at any ramp_frames give the unchanged bits (x * 1.0f is exact).  Fitted zeros
+ * stay zero; without a fade-out an unfitted tail is scaled by the last knot, like the end of the speech.  csrc/envelope.h holds the
+ * rule as plain C++ (host reference included).
+ * envelope == NULL: the request of the _volume call, the same launches, the same bits.  Batches: envelope[n_utt] or NULL, each
+ * struct's phoneme_gain [n_phonemes[u]] or NULL; utterance u gives the bits of zv_synthesize_envelope(..., &envelope[u]).  The arrays
+ * are read before the call returns.  Arguments, limits and messages are those of the _volume forms; in addition ZV_ERR_ARG before
+ * any work is enqueued when a gain is not finite or outside [0, 16], ramp_frames > 64 or a fade is above 0x7fffffff (the message
+ * names the entry point, the utterance, the field and, for a gain, the phoneme index), or when the checkpoint's audio_hop_size is
+ * below 10.  zv_synthesize_batch_begin_envelope is finished by zv_synthesize_batch_end.
+ * Out of scope: zv_vocode* and zv_vocode_stream (they have no timings); curve shapes other than linear. */
+typedef struct
+{
+    const float *phoneme_gain;     /* [n] or NULL (= all 1): linear gain of phoneme i, finite, 0 .. 16           */
+    uint32_t     ramp_frames;      /* 0 .. 64: half-width r of the cross-fade between neighbouring phonemes        */
+    uint32_t     fade_in_samples;  /* 0 = none; the first samples of the speech rise linearly from 0               */
+    uint32_t     fade_out_samples; /* 0 = none; the last samples of the speech fall linearly to 0, the rest is 0   */
+} zv_envelope;                     /* zero-initialised = identity */
+zv_status zv_synthesize_envelope(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                                 float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                 int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                 const zv_envelope *envelope);
+zv_status zv_synthesize_batch_envelope(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                       const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                       float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                       const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                       const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                       const zv_envelope *envelope);
+zv_status zv_synthesize_batch_begin_envelope(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                             const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                             const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                             const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                             const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                             const zv_envelope *envelope);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

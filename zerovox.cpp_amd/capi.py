@@ -6,6 +6,7 @@ There is NO CPU fallback: if the library is missing or no gfx950 device is prese
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -25,7 +26,7 @@ SYMBOLS = [
     "zv_synthesize_batch_begin_phonemes", "zv_synthesize_fitted", "zv_synthesize_batch_fitted", "zv_synthesize_batch_begin_fitted",
     "zv_debug_voc_runs", "zv_debug_poison", "zv_encode_taps_target", "zv_synthesize_target", "zv_synthesize_batch_target",
     "zv_synthesize_batch_begin_target", "zv_synthesize_volume", "zv_synthesize_batch_volume", "zv_synthesize_batch_begin_volume",
-    "zv_debug_mfma_chain",
+    "zv_debug_mfma_chain", "zv_synthesize_envelope", "zv_synthesize_batch_envelope", "zv_synthesize_batch_begin_envelope",
 ]
 
 
@@ -128,6 +129,81 @@ def _check_levels(return_levels):
     if not isinstance(return_levels, (bool, np.bool_)):
         raise TypeError(f"return_levels must be a bool, not {type(return_levels).__name__}")
     return bool(return_levels)
+
+
+class EnvelopeC(C.Structure):
+    """zv_envelope of include/zerovox_amd.h: the gains' pointer ([n] or NULL) and three integers (a zeroed struct is the identity)"""
+    _fields_ = [("phoneme_gain", C.c_void_p), ("ramp_frames", C.c_uint32), ("fade_in_samples", C.c_uint32),
+                ("fade_out_samples", C.c_uint32)]
+
+
+ENVELOPE_MAX_GAIN, ENVELOPE_MAX_RAMP, ENVELOPE_MAX_FADE = 16.0, 64, 0x7fffffff
+
+
+class Envelope:
+    """An utterance's amplitude envelope (include/zerovox_amd.h "amplitude envelope"): linear per-phoneme gains (an array [n] or
+    None: all 1), the cross-fade half-width in frames and the two fades in samples; the defaults are the identity.  from_db()
+    converts from dB and milliseconds.  .struct is the zv_envelope, which points into .phoneme_gain (kept alive here)."""
+
+    def __init__(self, phoneme_gain=None, ramp_frames=0, fade_in_samples=0, fade_out_samples=0):
+        self.phoneme_gain = None if phoneme_gain is None else np.ascontiguousarray(phoneme_gain, dtype=np.float32)
+        self.ramp_frames, self.fade_in_samples, self.fade_out_samples = ramp_frames, fade_in_samples, fade_out_samples
+
+    @classmethod
+    def from_db(cls, phoneme_gain_db=None, ramp_frames=0, fade_in_ms=0, fade_out_ms=0, rate=None):
+        """phoneme_gain_db: one gain in dB per phoneme (None: all 0 dB), linear = 10 ** (dB / 20); fade_in_ms / fade_out_ms: the
+        fades in milliseconds at `rate` samples per second (needed when one is not 0), floor(ms * rate / 1000 + 0.5) samples"""
+        def samples(ms, name):
+            if not ms:
+                return 0
+            if rate is None:
+                raise ValueError(f"{name} needs rate, the sampling rate")
+            return int(math.floor(float(ms) * float(rate) / 1000.0 + 0.5))
+        gain = None if phoneme_gain_db is None else np.array([10.0 ** (float(d) / 20.0) for d in phoneme_gain_db], np.float32)
+        return cls(gain, ramp_frames, samples(fade_in_ms, "fade_in_ms"), samples(fade_out_ms, "fade_out_ms"))
+
+    @property
+    def struct(self) -> EnvelopeC:
+        return EnvelopeC(None if self.phoneme_gain is None else self.phoneme_gain.ctypes.data, self.ramp_frames, self.fade_in_samples,
+                         self.fade_out_samples)
+
+    def __repr__(self):
+        return (f"Envelope(phoneme_gain={None if self.phoneme_gain is None else self.phoneme_gain.tolist()}, ramp_frames={self.ramp_frames}, "
+                f"fade_in_samples={self.fade_in_samples}, fade_out_samples={self.fade_out_samples})")
+
+
+def _envelope(e, n: int, where: str = "") -> Optional[Envelope]:
+    """None, an Envelope or a dict of its fields -> a checked Envelope of its own / None, before anything reaches the library: the
+    gains [n] finite numbers in [0, 16], ramp_frames an integer in [0, 64], the fades integers in [0, 0x7fffffff]"""
+    if e is None:
+        return None
+    if isinstance(e, dict):
+        unknown = sorted(set(e) - {"phoneme_gain", "ramp_frames", "fade_in_samples", "fade_out_samples"})
+        if unknown:
+            raise ValueError(f"{where}unknown envelope field(s) {unknown}")
+        e = Envelope(**e)
+    if not isinstance(e, Envelope):
+        raise TypeError(f"{where}an envelope is an Envelope, a dict of its fields or None, not {type(e).__name__}")
+    gain = e.phoneme_gain
+    if gain is not None:
+        gain = np.array(gain, dtype=np.float32)
+        if gain.shape != (n,):
+            raise ValueError(f"{where}envelope phoneme_gain has shape {gain.shape}, the utterance has {n} phonemes")
+        bad = np.flatnonzero(~np.isfinite(gain))
+        if bad.size:
+            raise ValueError(f"{where}envelope phoneme_gain[{bad[0]}] = {gain[bad[0]]} is not finite")
+        bad = np.flatnonzero((gain < 0.0) | (gain > ENVELOPE_MAX_GAIN))
+        if bad.size:
+            raise ValueError(f"{where}envelope phoneme_gain[{bad[0]}] = {gain[bad[0]]} is outside [0, {ENVELOPE_MAX_GAIN:g}]")
+    ints = []
+    for name, hi in (("ramp_frames", ENVELOPE_MAX_RAMP), ("fade_in_samples", ENVELOPE_MAX_FADE), ("fade_out_samples", ENVELOPE_MAX_FADE)):
+        x = getattr(e, name)
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            raise TypeError(f"{where}envelope {name} must be an integer, not {type(x).__name__}")
+        if not 0 <= x <= hi:
+            raise ValueError(f"{where}envelope {name} = {x} is outside [0, {hi}]")
+        ints.append(int(x))
+    return Envelope(gain, *ints)
 
 
 class PhonemeControlsC(C.Structure):
@@ -261,6 +337,12 @@ def load_library(path: Optional[str] = None):
         lib.zv_synthesize_volume.argtypes = lib.zv_synthesize_target.argtypes + vl
         lib.zv_synthesize_batch_volume.argtypes = lib.zv_synthesize_batch_target.argtypes + vl
         lib.zv_synthesize_batch_begin_volume.argtypes = lib.zv_synthesize_batch_begin_target.argtypes + vl
+    # the envelope forms: the _volume argument lists and the envelopes (zv_envelope, batches [n_utt]) or NULL
+    if hasattr(lib, "zv_synthesize_envelope"):
+        ev = [C.POINTER(EnvelopeC)]
+        lib.zv_synthesize_envelope.argtypes = lib.zv_synthesize_volume.argtypes + ev
+        lib.zv_synthesize_batch_envelope.argtypes = lib.zv_synthesize_batch_volume.argtypes + ev
+        lib.zv_synthesize_batch_begin_envelope.argtypes = lib.zv_synthesize_batch_begin_volume.argtypes + ev
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -334,12 +416,16 @@ def _check_target(target, T):
     return int(target)
 
 
-def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None, volume=None, levels=None):
+def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None, volume=None, levels=None,
+                  envelope=None):
     """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
     name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status.
     fitted: name_fitted, which takes everything (NULL for what the call lacks).  target (a frame count, or the batches' uint32
     array): name_target, which takes everything and the fitted flag.  volume / levels (a zv_volume and a zv_level, or the batches'
-    arrays): name_volume, which takes everything the _target form takes and the two (a call without a target passes 0 / NULL)"""
+    arrays): name_volume, which takes everything the _target form takes and the two (a call without a target passes 0 / NULL).
+    envelope (a zv_envelope, or the batches' array): name_envelope, which takes everything the _volume form takes and the envelope"""
+    if envelope is not None:
+        return getattr(lib, name + "_envelope")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope)
     if volume is not None or levels is not None:
         return getattr(lib, name + "_volume")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels)
     if target is not None:
@@ -530,7 +616,8 @@ class Model:
         return out
 
     def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False,
-                   fitted: bool = False, target_frames: Optional[int] = None, *, volume=None, return_levels: bool = False):
+                   fitted: bool = False, target_frames: Optional[int] = None, *, volume=None, return_levels: bool = False,
+                   envelope=None):
         """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
         arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
         as a third element.  fitted: zv_synthesize_fitted — T is a capacity, the utterance is decoded and vocoded as the n_frames
@@ -538,10 +625,13 @@ class Model:
         target_frames (0 <= frames <= T): zv_synthesize_target — the durations are fitted to sum to exactly that many frames (0: the
         bits of the call without it); None: the entry points above.
         volume (Volume, dict or (gain, target_rms, peak_ceiling)) or return_levels: zv_synthesize_volume — the waveform is measured
-        and scaled on the device; return_levels adds the Level (rms and peak before the gain, the gain) as the last element"""
+        and scaled on the device; return_levels adds the Level (rms and peak before the gain, the gain) as the last element.
+        envelope (Envelope or dict of its fields): zv_synthesize_envelope — per-phoneme gains, cross-fades and fades, applied on the
+        device ahead of the volume"""
         fitted = _check_fitted(fitted, [T])
         target = _check_target(target_frames, T)
         vol, return_levels = _volume(volume), _check_levels(return_levels)
+        env = _envelope(envelope, len(ids))
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
@@ -551,29 +641,30 @@ class Model:
         pc = _phoneme_controls(phonemes, len(ids))
         dur = np.empty(len(ids), np.int32) if return_durations else None
         level = Level() if vol is not None or return_levels else None
-        if level is not None and target is None:
-            target = 0                       # the _volume form takes a count, 0 = none
+        if (level is not None or env is not None) and target is None:
+            target = 0                       # the _volume and _envelope forms take a count, 0 = none
         self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur),
-                                fitted, target, _ref(vol), _ref(level)))
+                                fitted, target, _ref(vol), _ref(level), _ref(None if env is None else env.struct)))
         out = (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
         return out + (level,) if return_levels else out
 
     def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
-                      return_levels: bool = False) -> "BatchCall":
+                      return_levels: bool = False, envelope=None) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
         buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list.  fitted: the
         zv_synthesize_batch_fitted / _begin_fitted entry points (the lane form: .begin(lane) / .end(lane))"""
-        return BatchCall(self, utterances, durations, fitted, volume=volume, return_levels=return_levels)
+        return BatchCall(self, utterances, durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope)
 
     def synthesize_batch(self, utterances, return_durations: bool = False, fitted: bool = False, *, volume=None,
-                         return_levels: bool = False):
+                         return_levels: bool = False, envelope=None):
         """utterances: list of (ids, puncts, style, T[, prosody[, phonemes[, target_frames]]]) -> list of (wav, n_frames); each
         utterance keeps its own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its
         per-phoneme controls (PhonemeControls, dict of arrays or None), with a seventh its target frame count (None / 0: none).  return_durations: (wav, n_frames, durations) tuples.  fitted:
         zv_synthesize_batch_fitted — every T is a capacity, wav keeps the capacity shape with zeros behind n_frames * hop.
         volume: a list, one Volume (dict, 3-sequence) or None per utterance — zv_synthesize_batch_volume; return_levels: every tuple
-        gains the utterance's Level as its last element"""
-        call = BatchCall(self, utterances, return_durations, fitted, volume=volume, return_levels=return_levels)
+        gains the utterance's Level as its last element.  envelope: a list, one Envelope (dict) or None per utterance —
+        zv_synthesize_batch_envelope"""
+        call = BatchCall(self, utterances, return_durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope)
         call.run()
         res = call.results()
         if return_durations:
@@ -659,11 +750,21 @@ class BatchCall:
     phoneme timings after run() / end().  fitted: the _fitted entry points, whatever controls the utterances carry.
     volume (a list, one Volume / dict / 3-sequence or None per utterance) or return_levels: the _volume entry points, with the array
     .volume (None entries get the identity; set_volume() rewrites an entry in place for the next run() / begin()) and the array .levels,
-    which holds every utterance's Level after run() / end()."""
+    which holds every utterance's Level after run() / end().
+    envelope (a list, one Envelope / dict or None per utterance): the _envelope entry points, with the zv_envelope array .envelope (None
+    entries get the identity; set_envelope() rewrites an entry for the next run() / begin()); .ekeep[i] is utterance i's checked
+    Envelope, whose gains the array points into."""
 
     def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
-                 return_levels: bool = False):
+                 return_levels: bool = False, envelope=None):
         self.fitted = _check_fitted(fitted, [u[3] for u in utterances])
+        self.envelope = self.ekeep = None
+        if envelope is not None:
+            envs = list(envelope)
+            if len(envs) != len(utterances):
+                raise ValueError(f"envelope has {len(envs)} entries, the batch has {len(utterances)} utterances")
+            self.ekeep = [_envelope(e, len(u[0]), f"utterance {i}: ") for i, (e, u) in enumerate(zip(envs, utterances))]
+            self.envelope = (EnvelopeC * len(utterances))(*[e.struct if e is not None else EnvelopeC() for e in self.ekeep])
         self.return_levels = _check_levels(return_levels)
         self.volume = self.levels = None
         if volume is not None:
@@ -727,6 +828,14 @@ class BatchCall:
             raise ValueError("this BatchCall was built without volume controls")
         self.volume[i] = _volume(volume, f"utterance {i}: ") or Volume()
 
+    def set_envelope(self, i: int, envelope):
+        """utterance i's envelope (None: the identity) for the following run() / begin() (the call must have been built with envelope=)"""
+        if self.envelope is None:
+            raise ValueError("this BatchCall was built without envelopes")
+        e = _envelope(envelope, int(self.Ns[i]), f"utterance {i}: ")
+        self.ekeep[i] = e
+        self.envelope[i] = e.struct if e is not None else EnvelopeC()
+
     def set_prosody(self, i: int, prosody):
         """utterance i's controls for the following run() / begin() (the call must have been built with controls)"""
         if self.prosody is None:
@@ -737,14 +846,14 @@ class BatchCall:
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels))
+                             self.volume, self.levels, self.envelope))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels))
+                             self.volume, self.levels, self.envelope))
 
     def end(self, lane: int):
         m = self.model

@@ -165,7 +165,11 @@ struct Request
     // volume controls (zv_*_volume): volume [count] or null (levels alone: a meter, every gain 1), levels [count] or null
     const zv_volume           *volume = nullptr;
     zv_level                  *levels = nullptr;
+    // amplitude envelope (zv_*_envelope): [count] or null; each struct's phoneme_gain is [n[u]] or null
+    const zv_envelope         *envelope = nullptr;
 
+    // the call carries an envelope: then every utterance gets a gain row per token and an envelope row (the identity where it has none)
+    bool envelopes() const { return envelope != nullptr; }
     // the call measures levels: then every utterance gets a volume row (the identity where none is given) and a level row
     bool volumes() const { return volume || levels; }
     // any utterance with a target: then every utterance gets a ctl row and pctl rows (the identity where it has no controls), which
@@ -210,6 +214,7 @@ struct Request
         if (target_frames) s.target_frames += a;
         if (volume) s.volume += a;
         if (levels) s.levels += a;
+        if (envelope) s.envelope += a;
         return s;
     }
 };
@@ -251,6 +256,37 @@ static void pack_volume(const Request &r, float *vol)
 }
 static_assert(sizeof(zv_level) == sizeof(zv::LevelRow) && sizeof(zv_level) == 16, "zv_level is the kernels' LevelRow");
 
+static void check_envelope(const zv_envelope &e, uint32_t n)
+{
+    for (uint32_t i = 0; e.phoneme_gain && i < n; i++)
+    {
+        const float v = e.phoneme_gain[i];
+        if (!std::isfinite(v)) zv::fail(ZV_ERR_ARG, "envelope phoneme_gain[%u] = %g is not finite", i, (double)v);
+        if (!(v >= 0.0f && v <= zv::ENV_MAX_GAIN))
+            zv::fail(ZV_ERR_ARG, "envelope phoneme_gain[%u] = %g is outside [0, %g]", i, (double)v, (double)zv::ENV_MAX_GAIN);
+    }
+    if (e.ramp_frames > (uint32_t)zv::ENV_MAX_RAMP)
+        zv::fail(ZV_ERR_ARG, "envelope ramp_frames = %u exceeds %d", e.ramp_frames, zv::ENV_MAX_RAMP);
+    if (e.fade_in_samples > 0x7fffffffu) zv::fail(ZV_ERR_ARG, "envelope fade_in_samples = %u exceeds 2147483647", e.fade_in_samples);
+    if (e.fade_out_samples > 0x7fffffffu) zv::fail(ZV_ERR_ARG, "envelope fade_out_samples = %u exceeds 2147483647", e.fade_out_samples);
+}
+
+// a request's envelopes in the kernels' layouts: gain, one f32 per token packed like the token table (1 where an utterance gives
+// none), and env, one zv::ENV_CTL_STRIDE row of integers per utterance
+static void pack_envelope(const Request &r, float *gain, int32_t *env)
+{
+    for (uint32_t u = 0, row = 0; u < r.count; row += r.n[u], u++)
+    {
+        const zv_envelope &e = r.envelope[u];
+        for (uint32_t i = 0; i < r.n[u]; i++) gain[row + i] = e.phoneme_gain ? e.phoneme_gain[i] : 1.0f;
+        int32_t *c = env + (size_t)u * zv::ENV_CTL_STRIDE;
+        c[0] = (int32_t)e.ramp_frames;
+        c[1] = (int32_t)e.fade_in_samples;
+        c[2] = (int32_t)e.fade_out_samples;
+        c[3] = 0;
+    }
+}
+
 static void check_phoneme_controls(const Model &M, const zv_phoneme_controls &p, uint32_t n)
 {
     const int64_t fmax = std::min<int64_t>(32768, M.max_frames_per_utterance());      // forced frames travel as exact f32 integers
@@ -278,6 +314,9 @@ static void check_request(zv_model *m, const Request &r)
     if (!(m && r.ids && r.puncts && r.styles && r.n && r.T && r.out)) zv::fail(ZV_ERR_ARG, "%s: null argument", r.fn);
     const Model &M = *m->m;
     const bool tg = r.targets();
+    // the one limit of the envelope that is the checkpoint's, not an utterance's (kernels.h env_hop_supported)
+    if (r.envelope && !zv::env_hop_supported(M.hp.audio_hop_size))
+        zv::fail(ZV_ERR_ARG, "%s: an envelope needs audio_hop_size >= 10, the checkpoint has %d", r.fn, (int)M.hp.audio_hop_size);
     for (uint32_t u = 0; u < r.count; u++)
     {
         try
@@ -292,6 +331,7 @@ static void check_request(zv_model *m, const Request &r)
             if (r.prosody) check_prosody(r.prosody[u]);
             if (r.phonemes) check_phoneme_controls(M, r.phonemes[u], r.n[u]);
             if (r.volume) check_volume(r.volume[u]);
+            if (r.envelope) check_envelope(r.envelope[u], r.n[u]);
             if (r.target_frames && r.target_frames[u] > r.T[u])
                 zv::fail(ZV_ERR_ARG, "target_frames = %u exceeds the capacity T = %u", r.target_frames[u], r.T[u]);
             if (tg && r.n[u] > (uint32_t)zv::FIT_MAX_TOKENS)      // one launch covers the request's utterances, with or without a target
@@ -375,7 +415,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const bool tg = r.targets(), pc = r.phoneme_controls() || tg, dur = r.timings();
         const size_t E = M.E(), b_ids = (size_t)n * 4, b_hid = (size_t)T * E * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
         const size_t b_ctl = r.prosody || tg ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
-        const bool vol = r.volumes() && !taps;
+        const bool vol = r.volumes() && !taps, env = r.envelopes() && !taps;
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
         // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
@@ -384,10 +424,12 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const size_t o_nf = L.at(4), o_ids = L.at(b_ids), o_pun = L.at(b_ids), o_sty = L.at(E * 4), o_ctl = L.at(b_ctl),
                      o_pctl = L.at(b_pctl), o_hid = L.at(b_hid);
         const size_t o_mel = taps ? 0 : L.at((size_t)T * M.hp.audio_num_mels * 4), o_wav = taps ? 0 : L.at(b_wav),
-                     o_cum = taps ? 0 : L.at(dur ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
+                     o_cum = taps ? 0 : L.at(dur || env ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
                      o_runs = L.at(!r.fitted && !taps ? sizeof(zv::Seg) : 0);
         // [volume row][level row] (volume controls: the row uploaded, the level written on the device)
         const size_t o_vol = L.at(vol ? zv::LEVEL_VOL_STRIDE * 4 : 0), o_lvl = L.at(vol ? sizeof(zv::LevelRow) : 0);
+        // [gain row per token][envelope row] (amplitude envelope: both uploaded)
+        const size_t o_eg = L.at(env ? b_ids : 0), o_env = L.at(env ? zv::ENV_CTL_STRIDE * 4 : 0);
         char *io = (char *)M.io_scratch(L.size());
         int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
@@ -421,6 +463,17 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
             bt.d_nframes = d_nf;
             ZV_HIP(hipMemcpyAsync(io + o_vol, volrow, sizeof(volrow), hipMemcpyHostToDevice, M.stream()));
         }
+        std::vector<float> egain(env ? n : 0);                       // host staging, like ctl
+        int32_t erow[zv::ENV_CTL_STRIDE];
+        if (env)
+        {
+            pack_envelope(r, egain.data(), erow);
+            bt.d_env_gain = (const float *)(io + o_eg);
+            bt.d_env = (const int32_t *)(io + o_env);
+            bt.d_nframes = d_nf;
+            ZV_HIP(hipMemcpyAsync(io + o_eg, egain.data(), b_ids, hipMemcpyHostToDevice, M.stream()));
+            ZV_HIP(hipMemcpyAsync(io + o_env, erow, sizeof(erow), hipMemcpyHostToDevice, M.stream()));
+        }
         int32_t nf = 0;
         if (taps)
         {
@@ -438,7 +491,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         else
         {
             float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
-            if (dur) bt.d_cum = (int32_t *)(io + o_cum);
+            if (dur || env) bt.d_cum = (int32_t *)(io + o_cum);       // an envelope's knots pass searches the scan behind the vocoder
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
             ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream()));
             if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), bt.d_cum, b_ids, hipMemcpyDeviceToHost, M.stream()));
@@ -690,7 +743,8 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     if (pb.active) zv::fail(ZV_ERR_ARG, "lane %d already has a batch in flight", lane);
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
-    const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings(), vol = r.volumes();
+    const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings(), vol = r.volumes(),
+               env = r.envelopes();
     uint32_t nmax = 0, tmax = 0, ntot = 0;
     for (uint32_t u = 0; u < r.count; u++)
     {
@@ -716,12 +770,14 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
                  i_sty = in.at((size_t)bt.nseg * E * 4), i_ctl = in.at(ctl ? (size_t)bt.nseg * zv::CTL_STRIDE * 4 : 0),
                  i_pctl = in.at(pc ? bt.n_rows * zv::PCTL_STRIDE * 4 : 0),
                  i_vol = in.at(vol ? (size_t)bt.nseg * zv::LEVEL_VOL_STRIDE * 4 : 0),      // volume rows: only with volume controls, like the control rows
+                 i_eg = in.at(env ? bt.n_rows * 4 : 0),                                    // envelope: a gain per token row and a row per utterance, likewise
+                 i_env = in.at(env ? (size_t)bt.nseg * zv::ENV_CTL_STRIDE * 4 : 0),
                  b_in = in.size();
     // device block: [frame counts][input block][hidden][mel][wav][scan] (scan: only when timings are asked for, the length
     // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
     Layout dev;
     const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
-                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur ? bt.n_rows * 4 : 0),
+                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || env ? bt.n_rows * 4 : 0),
                  o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0),      // fitted: the live frame table, written on the device
                  o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0),     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
                  o_lvl = dev.at(vol ? (size_t)bt.nseg * sizeof(zv::LevelRow) : 0);             // volume controls: the level rows, written on the device
@@ -760,19 +816,26 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         h_frm[r.count] = zv::Seg{0, t0, 0, 0};
         pack_controls(r, (float *)(h_in + i_ctl), (float *)(h_in + i_pctl));      // (phoneme rows past the utterances are never read)
         if (vol) pack_volume(r, (float *)(h_in + i_vol));
+        if (env) pack_envelope(r, (float *)(h_in + i_eg), (int32_t *)(h_in + i_env));      // (gain rows past the utterances are never read)
     }
     bt.d_tok = (const zv::Seg *)(d_in + i_tok);
     bt.d_frm = (const zv::Seg *)(d_in + i_frm);
     if (ctl) bt.d_ctl = (const float *)(d_in + i_ctl);
     bt.has_targets = tg;
     if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
-    if (dur) bt.d_cum = (int32_t *)(io + o_cum);
+    if (dur || env) bt.d_cum = (int32_t *)(io + o_cum);         // an envelope's knots pass searches the scan behind the vocoder
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
     if (M.dec_plan(bt).runs) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
     if (vol)
     {
         bt.d_vol = (const float *)(d_in + i_vol);
         bt.d_levels = (zv::LevelRow *)(io + o_lvl);
+        bt.d_nframes = (const int32_t *)(io + o_nf);
+    }
+    if (env)
+    {
+        bt.d_env_gain = (const float *)(d_in + i_eg);
+        bt.d_env = (const int32_t *)(d_in + i_env);
         bt.d_nframes = (const int32_t *)(io + o_nf);
     }
     int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(d_in + i_ids), *d_pun = (int32_t *)(d_in + i_pun);
@@ -1070,6 +1133,37 @@ zv_status zv_synthesize_batch_begin_volume(zv_model *m, uint32_t lane, uint32_t 
 {
     return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
                                  durations, fitted != 0, target_frames, volume, levels});
+}
+
+// The envelope forms: the _volume requests plus the envelopes (NULL: the request of the _volume call).
+zv_status zv_synthesize_envelope(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                                 float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                 int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                 const zv_envelope *envelope)
+{
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody, phonemes, &durations, fitted != 0,
+                          &target_frames, volume, levels, envelope});
+}
+
+zv_status zv_synthesize_batch_envelope(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                       const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                       uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                       int32_t *const *durations, const uint32_t *target_frames, int fitted, const zv_volume *volume,
+                                       zv_level *levels, const zv_envelope *envelope)
+{
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                durations, fitted != 0, target_frames, volume, levels, envelope});
+}
+
+zv_status zv_synthesize_batch_begin_envelope(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                             const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                             const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                             const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                             const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                             const zv_envelope *envelope)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                 durations, fitted != 0, target_frames, volume, levels, envelope});
 }
 
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)

@@ -14,6 +14,7 @@
 #include "voc_plan.h"
 #include "stage_plan.h"    // att_plan, linear_plan, lr_plan, layernorm_tail_ok; the schedules' enc_plan and dec_plan
 #include "level.h"        // volume controls: LEVEL_CHUNK_SAMPLES, LEVEL_VOL_STRIDE, LevelRow
+#include "envelope.h"     // amplitude envelope: ENV_CTL_STRIDE, ENV_MAX_RAMP, ENV_MAX_GAIN
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -412,5 +413,20 @@ int        level_chunks(int max_rows, int hop);
 hipError_t launch_level_measure(hipStream_t s, const float *wav, const int32_t *n_frames, void *slab, const Segs &frames, int hop);
 hipError_t launch_level_apply(hipStream_t s, float *wav, const int32_t *n_frames, const void *slab, const float *vol, LevelRow *levels,
                               const Segs &frames, int hop);
+
+// ---- amplitude envelope (include/zerovox_amd.h "amplitude envelope", envelope.h): two passes ahead of the volume passes, over the same
+// finished waveform.  cum [token rows] is the length regulator's scan and gain [token rows] the per-phoneme gains, both indexed by
+// absolute token row (`tokens`); env [nseg][ENV_CTL_STRIDE] = {ramp_frames, fade_in_samples, fade_out_samples, unused}; n_frames [nseg]
+// the regulator's counts; `frames` the CAPACITY table or inline segment.
+//   knots: knots[frames[u].row0 + u + f] = B[f], f = 0 .. nf of segment u (uint32; the table has capacity rows + nseg entries); a segment
+//          without speech writes nothing
+//   apply: multiplies all rows * hop samples of every segment by the rule's per-sample gain (env_sample_gain), in place
+// No atomics, nothing to zero: apply reads only the knots of the same run.  env_hop_supported: the apply pass keeps the knots of one
+// chunk of LEVEL_CHUNK_SAMPLES samples in LDS, which bounds the hop from below (10 samples); launch_env_apply refuses any other.
+bool       env_hop_supported(int hop);
+hipError_t launch_env_knots(hipStream_t s, const int32_t *cum, const float *gain, const int32_t *env, const int32_t *n_frames,
+                            uint32_t *knots, const Segs &tokens, const Segs &frames);
+hipError_t launch_env_apply(hipStream_t s, float *wav, const int32_t *n_frames, const uint32_t *knots, const int32_t *env,
+                            const Segs &frames, int hop);
 
 }  // namespace zv

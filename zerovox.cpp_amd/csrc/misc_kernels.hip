@@ -6,4 +6,5 @@
 #include "regulator_kernels.hip"      // length regulator, target durations, fitted mode's frame table
 #include "runs_kernels.hip"           // run tables of vocoder and decoder
 #include "level_kernels.hip"          // level meter
+#include "envelope_kernels.hip"       // amplitude envelope
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

@@ -98,6 +98,12 @@ struct Batch
     const float   *d_vol = nullptr;
     LevelRow      *d_levels = nullptr;
     const int32_t *d_nframes = nullptr;
+    // Amplitude envelope (include/zerovox_amd.h "amplitude envelope", envelope.h), both set or none: the per-phoneme gains, f32 [n_rows]
+    // in HBM indexed by absolute token row like d_pctl, and the envelope rows, int32 [nseg][ENV_CTL_STRIDE].  With them d_cum (the
+    // knots pass searches the regulator's scan after the decoder and the vocoder have reused the arena) and d_nframes are set too.
+    // Keyed like d_ctl: the vocoder ends in two launches more, ahead of the volume passes; the VALUES are read at run time.
+    const float   *d_env_gain = nullptr;
+    const int32_t *d_env = nullptr;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -126,7 +132,8 @@ struct Batch
         return nseg == o.nseg && n_max == o.n_max && t_max == o.t_max && n_rows == o.n_rows && t_rows == o.t_rows && d_tok == o.d_tok &&
                d_frm == o.d_frm && (d_tok || memcmp(&tok1, &o.tok1, sizeof(Seg)) == 0) && (d_frm || memcmp(&frm1, &o.frm1, sizeof(Seg)) == 0) &&
                d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live && has_targets == o.has_targets &&
-               d_dec_runs == o.d_dec_runs && d_vol == o.d_vol && d_levels == o.d_levels && d_nframes == o.d_nframes;
+               d_dec_runs == o.d_dec_runs && d_vol == o.d_vol && d_levels == o.d_levels && d_nframes == o.d_nframes && d_env_gain == o.d_env_gain &&
+               d_env == o.d_env;
     }
 };
 
@@ -353,10 +360,15 @@ class Model
         // volume controls (kernels.h launch_level_measure): the partial totals, 16 bytes per (segment, chunk).  Sized by t_rows alone
         // (level_slab_entries) and carved in front of the run table, so that a sub-batch finds the table where the head put it
         void *level_slab;
+        // amplitude envelope (kernels.h launch_env_knots): the knots, one uint32 per frame and one more per segment.  Sized by t_rows
+        // alone (env_knot_entries) and carved in front of the run table like the slab
+        uint32_t *env_knots;
         float *mel_c; int32_t *eq; Seg *runs;
     };
     // entries of VocLayout::level_slab: >= nseg * level_chunks(t_max, hop) for every Batch with nseg * t_max <= t_rows, a sub-batch included
     size_t level_slab_entries(const Batch &b) const;
+    // entries of VocLayout::env_knots: >= t_rows + nseg for every Batch with nseg * t_max <= t_rows, a sub-batch included
+    size_t env_knot_entries(const Batch &b) const;
     struct DecLayout
     {
         int    nblk, hs, ss;        // per segment: statistics blocks, floats of AdaIN vectors, floats of (mean, rstd) pairs

@@ -71,6 +71,7 @@ Model::VocLayout Model::voc_layout(DeviceArena &a, const Batch &bt) const
     v.mel_c = a.take_n<float>(bt.t_rows * hp.audio_num_mels);
     v.eq = a.take_n<int32_t>(bt.t_rows);
     v.level_slab = a.take(level_slab_entries(bt) * 16);
+    v.env_knots = a.take_n<uint32_t>(env_knot_entries(bt));
     v.runs = a.take_n<Seg>(bt.nseg);
     return v;
 }
@@ -80,6 +81,8 @@ size_t Model::level_slab_entries(const Batch &bt) const
 {
     return (bt.t_rows * hp.audio_hop_size + LEVEL_CHUNK_SAMPLES - 1) / LEVEL_CHUNK_SAMPLES + bt.t_rows / (size_t)std::max(bt.t_max, 1) + 1;
 }
+
+size_t Model::env_knot_entries(const Batch &bt) const { return bt.t_rows + bt.t_rows / (size_t)std::max(bt.t_max, 1) + 1; }
 
 // HiFi-GAN vocoder (reference src/hifigan.cpp:187-377): fixed schedule of 2 + n_up * 7 launches
 void Model::vocode_dev(const Batch &bt, const float *d_mel, float *d_wav)
@@ -106,8 +109,9 @@ void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g
     {
         sub.d_vol = bt.d_vol + (size_t)g0 * LEVEL_VOL_STRIDE;
         sub.d_levels = bt.d_levels + g0;
-        sub.d_nframes = bt.d_nframes + g0;
     }
+    if (bt.d_nframes) sub.d_nframes = bt.d_nframes + g0;
+    if (bt.d_env) sub.d_env = bt.d_env + (size_t)g0 * ENV_CTL_STRIDE;          // (the gains and the scan go by absolute token row)
     sub.nseg = cnt;
     vocode_group(sub, d_mel, d_wav, 2, g0);
 }
@@ -448,6 +452,27 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         if (dbg_layer.kind == ZV_LAYER_VOC_OUTPUT) dbg_extract(d_wav, 1, 1, L);
         // fitted: the output conv stops at each utterance's last frame; the rest of its capacity is silence
         if (bt.d_frm_live) ZV_LAUNCH("voc_zero_tail", 4.0 * La, 0.0, launch_zero_tail(stream(), d_wav, 1, bt.frames_cap(), fr, rate));
+    }
+
+    // Amplitude envelope (envelope.h): the waveform of these segments is final, so build the knots from the regulator's scan and scale
+    // the capacity — ahead of the volume passes, which measure what the caller receives.  Only where the call carries an envelope;
+    // never under a one-layer tap.
+    if (bt.d_env && dbg_layer.kind < 0)
+    {
+        if (!bt.d_cum || !bt.d_nframes || !bt.d_env_gain) fail(ZV_ERR_DEVICE, "internal: an envelope without the scan, the frame counts or the gains");
+        // (the hop was checked with the request, capi.cpp check_request; launch_env_apply refuses any other)
+        // Segment u of THIS call keeps its knots at row0 + u + f, u counted from the call's first segment: consecutive tail groups write
+        // overlapping ranges of the table.  That is sound only because a group's knots pass and apply pass run back to back on the lane's
+        // one stream, ahead of the next group's; groups on streams of their own would need the batch's segment index (seg0 + u) here.
+        const Segs cap = bt.frames_cap();
+        const Segs tk{bt.d_tok ? bt.d_tok + seg0 : nullptr, bt.nseg, bt.n_max, bt.tok1};
+        if (bt.t_rows + (size_t)bt.nseg > env_knot_entries(bt)) fail(ZV_ERR_DEVICE, "internal: envelope knot table too small");
+        const double cap_rows = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg);
+        // algorithmic bytes: the knots written (by capacity) and the scan and gains read once; the waveform read and written
+        ZV_LAUNCH("voc_env_knots", 4.0 * (cap_rows + bt.nseg) + 8.0 * std::min((double)bt.n_rows, (double)bt.n_max * bt.nseg), 0.0,
+                  launch_env_knots(stream(), bt.d_cum, bt.d_env_gain, bt.d_env, bt.d_nframes, lay.env_knots, tk, cap));
+        ZV_LAUNCH("voc_env_apply", 8.0 * cap_rows * rate, 0.0,
+                  launch_env_apply(stream(), d_wav, bt.d_nframes, lay.env_knots, bt.d_env, cap, rate));
     }
 
     // Volume controls (level.h): the waveform of these segments is final, so measure the speech and scale the capacity — per tail

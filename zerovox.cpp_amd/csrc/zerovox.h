@@ -132,6 +132,10 @@ class ZeroVOXModel
     // rms and peak before the gain and the gain applied.  Works with everything above; values are checked when eval() runs.
     void set_volume(const zv_volume &v) { volume = v; has_volume = true; }
     const zv_level &get_level() const { return level; }
+    // amplitude envelope (include/zerovox_amd.h "amplitude envelope") for the eval() calls that follow: per-phoneme gains (copied:
+    // e->phoneme_gain is [n] or null; n must be eval()'s phoneme count), cross-fade half-width and the two fades, applied on the
+    // device ahead of the volume controls.  nullptr: none.  Works with everything above; values are checked when eval() runs.
+    void set_envelope(const zv_envelope *e, uint32_t n);
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
@@ -161,6 +165,9 @@ class ZeroVOXModel
     zv_volume            volume = {1.0f, 0.0f, 0.0f};
     bool                 has_volume = false;
     zv_level             level = {0.0f, 0.0f, 0.0f, 0};
+    zv_envelope          envelope = {nullptr, 0, 0, 0};
+    std::vector<float>   env_gain;
+    bool                 has_envelope = false, env_gain_set = false;
 };
 
 }  // namespace ZeroVOX

@@ -164,21 +164,36 @@ void ZeroVOXModel::set_phoneme_controls(const zv_phoneme_controls *p, uint32_t n
     record_durations = true;
 }
 
+void ZeroVOXModel::set_envelope(const zv_envelope *e, uint32_t n)
+{
+    has_envelope = e != nullptr;
+    env_gain_set = e && e->phoneme_gain;
+    if (env_gain_set) env_gain.assign(e->phoneme_gain, e->phoneme_gain + n);
+    else env_gain.clear();
+    envelope = e ? *e : zv_envelope{nullptr, 0, 0, 0};
+    envelope.phoneme_gain = nullptr;          // the gains live in env_gain
+}
+
 void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const float *style_embed, uint32_t num_phonemes)
 {
     const zv_prosody *pr = has_prosody ? &prosody : nullptr;
-    if (has_volume)
+    if (has_envelope && env_gain_set && env_gain.size() != num_phonemes)
+        throw zv::Error(ZV_ERR_ARG, "set_envelope: gains for " + std::to_string(env_gain.size()) + " phonemes, eval() has " +
+                                        std::to_string(num_phonemes));
+    if (has_volume || has_envelope)
     {
-        // the volume form takes what every other form takes (the level is measured on the finished waveform of the one-pass chain)
+        // the volume and envelope forms take what every other form takes (the finished waveform of the one-pass chain is scaled and measured)
         if (has_phonemes && pc_n != num_phonemes)
             throw zv::Error(ZV_ERR_ARG, "set_phoneme_controls: controls for " + std::to_string(pc_n) + " phonemes, eval() has " +
                                             std::to_string(num_phonemes));
         auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
         const zv_phoneme_controls pc = {ptr(pc_frames), ptr(pc_scale), ptr(pc_pitch), ptr(pc_energy)};
         if (record_durations) durations.assign(num_phonemes, 0);
-        chk(zv_synthesize_volume(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
-                                 has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
-                                 &volume, &level));
+        const zv_envelope env = {env_gain_set ? env_gain.data() : nullptr, envelope.ramp_frames, envelope.fade_in_samples,
+                                 envelope.fade_out_samples};
+        chk(zv_synthesize_envelope(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
+                                   has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
+                                   has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr));
         return;
     }
     if (record_durations || fitted || target_frames)

@@ -34,6 +34,11 @@
 //            level of L dB re full scale (-200 .. 0), no sample above P dB re full scale (-200 .. 0); linear = 10^(dB / 20).  The
 //            waveform is measured and scaled on the device; the measured rms / peak (before the gain) and the gain are printed.
 //            Work with everything above.  A bad value is a usage error.
+//   --phoneme-gain-db FILE, --ramp-frames R, --fade-in-ms X, --fade-out-ms X
+//            amplitude envelope (include/zerovox_amd.h "amplitude envelope"): FILE holds one gain in dB per phoneme of the utterance, one
+//            per line (-200 .. 24.08, linear = 10^(dB / 20) <= 16); neighbouring phonemes cross-fade over 2R + 2 frames (0 <= R <= 64);
+//            the speech fades in / out over floor(X * sampling rate / 1000 + 0.5) samples (0 <= X <= 600000).  Applied on the device
+//            ahead of the volume controls.  Work with everything above.  A wrong line count or a bad value is a usage error.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
 #include <algorithm>
 #include <cmath>
@@ -57,6 +62,7 @@ static void usage(FILE *f)
                "               [--duration-scale S] [--pitch-scale S] [--pitch-shift D] [--energy-scale S] [--energy-shift D]\n"
                "               [--phoneme-controls FILE] [--alignment FILE] [--target-frames F | --target-seconds S]\n"
                "               [--gain-db G] [--loudness-dbfs L] [--peak-dbfs P]\n"
+               "               [--phoneme-gain-db FILE] [--ramp-frames R] [--fade-in-ms X] [--fade-out-ms X]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
@@ -73,7 +79,11 @@ static void usage(FILE *f)
                "  --target-seconds S   the same for floor(S * sampling rate / hop size + 0.5) frames (S > 0)\n"
                "  --gain-db G          multiply the waveform by 10^(G / 20) (-200 <= G <= 60)\n"
                "  --loudness-dbfs L    bring the speech to an RMS level of L dB re full scale (-200 <= L <= 0)\n"
-               "  --peak-dbfs P        keep every sample at or under P dB re full scale (-200 <= P <= 0); prints rms / peak / gain\n",
+               "  --peak-dbfs P        keep every sample at or under P dB re full scale (-200 <= P <= 0); prints rms / peak / gain\n"
+               "  --phoneme-gain-db FILE  one gain in dB per phoneme, one per line (-200 <= dB <= 24.08: a linear gain of at most 16)\n"
+               "  --ramp-frames R      cross-fade neighbouring phonemes' gains over 2R + 2 frames (0 <= R <= 64), default 0\n"
+               "  --fade-in-ms X       the speech rises linearly from 0 over floor(X * sampling rate / 1000 + 0.5) samples\n"
+               "  --fade-out-ms X      the speech falls linearly to 0 over as many samples; what follows it is silence\n",
             k_default_model, k_default_out);
 }
 
@@ -150,6 +160,36 @@ static PhonemeControlFile read_phoneme_controls(const std::string &path, size_t 
     return pc;
 }
 
+// --phoneme-gain-db FILE for an utterance of n phonemes, as linear gains: a usage error (exit 2) on a wrong line count or a bad value
+static std::vector<float> read_phoneme_gains(const std::string &path, size_t n)
+{
+    auto bad = [&](const std::string &what) {
+        fprintf(stderr, "zerovox: --phoneme-gain-db %s: %s\n", path.c_str(), what.c_str());
+        usage(stderr);
+        exit(2);
+    };
+    std::ifstream f(path);
+    if (!f) bad("cannot open the file");
+    std::vector<float> gains;
+    std::string line;
+    size_t lineno = 0;
+    while (std::getline(f, line))
+    {
+        lineno++;
+        const size_t a = line.find_first_not_of(" \t\r"), b = line.find_last_not_of(" \t\r");
+        if (a == std::string::npos) continue;                                      // blank lines carry no phoneme
+        const std::string tok = line.substr(a, b - a + 1), where = "line " + std::to_string(lineno);
+        char *end = nullptr;
+        const double db = strtod(tok.c_str(), &end);
+        if (end != tok.c_str() + tok.size() || !std::isfinite(db)) bad(where + ": '" + tok + "' is not a finite number");
+        const float lin = (float)pow(10.0, db / 20.0);
+        if (!(db >= -200.0 && lin <= 16.0f)) bad(where + ": " + tok + " dB is outside [-200, 24.08]");
+        gains.push_back(lin);
+    }
+    if (gains.size() != n) bad(std::to_string(gains.size()) + " lines, the utterance has " + std::to_string(n) + " phonemes");
+    return gains;
+}
+
 // the utterance's phoneme ids before the model is loaded: line 1 of the utterance file, or the built-in utterance
 static std::vector<int32_t> utterance_ids(const std::string &utt_path)
 {
@@ -168,8 +208,10 @@ static std::vector<int32_t> utterance_ids(const std::string &utt_path)
 
 int main(int argc, char **argv)
 {
-    std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path;
-    bool trim = false, fit = false, info = false, controlled = false, leveled = false;
+    std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path, gain_path;
+    bool trim = false, fit = false, info = false, controlled = false, leveled = false, enveloped = false;
+    long ramp_frames = 0;              // --ramp-frames
+    double fade_ms[2] = {0.0, 0.0};    // --fade-in-ms, --fade-out-ms
     zv_volume volume = {1.0f, 0.0f, 0.0f};
     long target_frames = 0;            // --target-frames
     double target_seconds = 0.0;       // --target-seconds
@@ -228,6 +270,39 @@ int main(int argc, char **argv)
             else volume.peak_ceiling = lin;
             leveled = true;
         }
+        else if (a == "--phoneme-gain-db")
+        {
+            gain_path = need("--phoneme-gain-db");
+            enveloped = true;
+        }
+        else if (a == "--ramp-frames")
+        {
+            const std::string v = need("--ramp-frames");
+            char *end = nullptr;
+            ramp_frames = strtol(v.c_str(), &end, 10);
+            if (v.empty() || end != v.c_str() + v.size() || ramp_frames < 0 || ramp_frames > 64)
+            {
+                fprintf(stderr, "zerovox: --ramp-frames needs an integer in [0, 64], got '%s'\n", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+            enveloped = true;
+        }
+        else if (a == "--fade-in-ms" || a == "--fade-out-ms")
+        {
+            // a double, as written: the sample count is floor(ms * rate / 1000 + 0.5) of that double (capi.Envelope.from_db's)
+            const std::string v = need(a.c_str());
+            char *end = nullptr;
+            const double ms = strtod(v.c_str(), &end);
+            if (v.empty() || end != v.c_str() + v.size() || !(ms >= 0.0 && ms <= 600000.0))
+            {
+                fprintf(stderr, "zerovox: %s needs a number in [0, 600000] ms, got '%s'\n", a.c_str(), v.c_str());
+                usage(stderr);
+                return 2;
+            }
+            fade_ms[a == "--fade-out-ms"] = ms;
+            enveloped = true;
+        }
         else if (a == "--trim") trim = true;
         else if (a == "--fit") fit = true;
         else if (a == "--info") info = true;
@@ -278,14 +353,25 @@ int main(int argc, char **argv)
         // per-phoneme controls and timings: the file is checked against the utterance before the model is loaded
         std::vector<int32_t> ids0;
         PhonemeControlFile pcf;
-        if (!pc_path.empty() || !align_path.empty()) ids0 = utterance_ids(utt_path);
+        std::vector<float> gains;
+        if (!pc_path.empty() || !align_path.empty() || !gain_path.empty()) ids0 = utterance_ids(utt_path);
         if (!pc_path.empty()) pcf = read_phoneme_controls(pc_path, ids0.size());
+        if (!gain_path.empty()) gains = read_phoneme_gains(gain_path, ids0.size());
 
         ZeroVOX::ZeroVOXModel model(model_path);
         const ZeroVOX::zerovox_hparams &hp = model.get_hparams();
         if (controlled) model.set_prosody(prosody);
         if (fit) model.set_fitted(true);
         if (leveled) model.set_volume(volume);
+        if (enveloped)
+        {
+            // 600 000 ms at any rate below 3.5 MHz stay under the 0x7fffffff samples a fade may have
+            const double rate = hp.audio_sampling_rate;
+            const zv_envelope env = {gains.empty() ? nullptr : gains.data(), (uint32_t)ramp_frames,
+                                     (uint32_t)std::min(floor(fade_ms[0] * rate / 1000.0 + 0.5), 2147483647.0),
+                                     (uint32_t)std::min(floor(fade_ms[1] * rate / 1000.0 + 0.5), 2147483647.0)};
+            model.set_envelope(&env, (uint32_t)gains.size());
+        }
         if (target_seconds > 0.0)
             target_frames = (long)std::min(floor(target_seconds * hp.audio_sampling_rate / hp.audio_hop_size + 0.5), 1e9);
         if (target_frames > 0 || target_seconds > 0.0)
