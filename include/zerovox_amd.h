@@ -16,6 +16,7 @@
  *   *_target           the same with a target frame count the utterance's durations are fitted to
  *   *_volume           the same with a gain, a loudness target and a peak ceiling per utterance (zv_volume) and the measured level out
  *   *_envelope         the same with per-phoneme gains, cross-fades and fades per utterance (zv_envelope)
+ *   *_contour          the same with the level and peak of every frame and every phoneme out (zv_contour)
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file        src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -455,6 +456,63 @@ zv_status zv_synthesize_batch_begin_envelope(zv_model *m, uint32_t lane, uint32_
                                              const zv_phoneme_controls *phonemes, int32_t *const *durations,
                                              const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
                                              const zv_envelope *envelope);
+/* ---- level contour: per-frame and per-phoneme level and peak ----------------------------------------------------------------------
+ * The read side of the envelope and the missing half of the phoneme timings: durations[] tell WHEN a phoneme sounds, the contour HOW
+ * LOUD, at the same granularity and from the same call.  A caller who drives a mouth shape or a level meter, trims the model's
+ * leading and trailing silence, checks that a ducked phrase came out 6 dB down or looks for the one clipped phoneme of a batch needs
+ * no pass over the samples on the host: the contour forms meter the finished waveform on the device, inside the same captured graph
+ * and — for a large batch — per tail group, ahead of that group's download and behind the envelope and the volume passes.  The
+ * contour is a meter: it scales nothing.
+ * The rule, per utterance, with hop = audio_hop_size, T the capacity, w[0 .. T*hop) the waveform the SAME call writes to wav (after
+ * fitted zeroing, envelope and volume: what the caller receives), durations[] the phoneme timings of that call as the _phonemes
+ * forms define them, start_i the sum of the durations before i, and q_i, the peak's bit patterns and rms as the volume controls
+ * define them (a NaN or infinite sample: q = 0 and left out of the peak; -0.0 counts as 0):
+ *   frame    for 0 <= f < T, over the capacity: S_f = sum of q^2 over the samples w[f*hop .. f*hop + hop), an unsigned 64-bit integer;
+ *            P_f = the largest sign-cleared bit pattern of the finite samples among them, 0 when there is none.
+ *            frames[f] = {(float)rms(S_f, hop), the f32 with the bits P_f}, rms(S, k) = S > 0 ? sqrt((double)S / ((double)k *
+ *            274877906944.0)) : 0.  Fitted zeros give {0, 0}; an unfitted tail is measured like the speech.
+ *   phoneme  for 0 <= i < n, d = durations[i]: S = sum of S_f and P = max of P_f over start_i <= f < start_i + d (S < 2^62 as for the
+ *            volume controls).  phonemes[i] = {(float)rms(S, d*hop), the f32 with the bits P}.  d == 0 gives {0, 0}: a phoneme cut off
+ *            by T, a forced 0, a token at or past num_phonemes.
+ * Every f64 step is one IEEE operation and nothing depends on how the work is split: sums of integers, maxima of bit patterns.
+ * csrc/contour.h holds the rule as plain C++ (host reference included).  What follows, with nf = min(n_frames, T): the maximum of
+ * frames[f].peak over f < nf is the zv_level peak of a meter-only call (volume == NULL, levels given); the sum of S_f over f < nf is
+ * that call's S; the phonemes' sums partition the sum of S_f over f < min(sum of durations, T), and their maxima its peak.
+ * contour == NULL, or every struct with both pointers NULL: the request of the _envelope call, the same launches, the same graph,
+ * the same bits.  With a contour the waveform, n_frames, durations and levels keep exactly their bits.  Batches: contour[n_utt] or
+ * NULL; an utterance may ask for one table, both or none, and gives the rows of zv_synthesize_contour(..., &contour[u]).  The struct
+ * array is read before the call (_begin) returns; the tables it points to must stay valid until the call (batches in flight: _end)
+ * returns.  Arguments, limits and messages are those of the _envelope forms.  The frames pass reads whole 16-byte loads per frame,
+ * so a checkpoint's audio_hop_size must be a multiple of 4: the launcher refuses any other with ZV_ERR_DEVICE rather than carry a
+ * scalar path that no loadable checkpoint can reach (the loader accepts hop 300 alone).
+ * zv_synthesize_batch_begin_contour is finished by zv_synthesize_batch_end.
+ * Out of scope: zv_vocode*, zv_vocode_stream and the encode / decode entry points (they have no timings); any filtering or weighting
+ * of the level (A-weighting, LUFS gating); trimming itself — the caller trims from the contour. */
+typedef struct
+{
+    float rms, peak;
+} zv_frame_level;
+typedef struct
+{
+    zv_frame_level *frames;     /* [T] or NULL: one row per frame of the capacity       */
+    zv_frame_level *phonemes;   /* [n] or NULL: one row per token                       */
+} zv_contour;                   /* zero-initialised = none */
+zv_status zv_synthesize_contour(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                                float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                const zv_envelope *envelope, const zv_contour *contour);
+zv_status zv_synthesize_batch_contour(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                      const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                      float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                      const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                      const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                      const zv_envelope *envelope, const zv_contour *contour);
+zv_status zv_synthesize_batch_begin_contour(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                            const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                            const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                            const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                            const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                            const zv_envelope *envelope, const zv_contour *contour);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

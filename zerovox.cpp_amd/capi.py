@@ -27,6 +27,7 @@ SYMBOLS = [
     "zv_debug_voc_runs", "zv_debug_poison", "zv_encode_taps_target", "zv_synthesize_target", "zv_synthesize_batch_target",
     "zv_synthesize_batch_begin_target", "zv_synthesize_volume", "zv_synthesize_batch_volume", "zv_synthesize_batch_begin_volume",
     "zv_debug_mfma_chain", "zv_synthesize_envelope", "zv_synthesize_batch_envelope", "zv_synthesize_batch_begin_envelope",
+    "zv_synthesize_contour", "zv_synthesize_batch_contour", "zv_synthesize_batch_begin_contour",
 ]
 
 
@@ -129,6 +130,51 @@ def _check_levels(return_levels):
     if not isinstance(return_levels, (bool, np.bool_)):
         raise TypeError(f"return_levels must be a bool, not {type(return_levels).__name__}")
     return bool(return_levels)
+
+
+class ContourC(C.Structure):
+    """zv_contour of include/zerovox_amd.h: the two tables' pointers, zv_frame_level [T] and [n], each or NULL (a zeroed struct asks
+    for nothing)"""
+    _fields_ = [("frames", C.c_void_p), ("phonemes", C.c_void_p)]
+
+
+class Contour:
+    """An utterance's level contour (include/zerovox_amd.h "level contour"): .frames float32 [T, 2] and .phonemes float32 [n, 2],
+    columns (rms, peak) of the waveform the same call returned; None for a table that was not asked for.  dbfs() converts a
+    column or a table to dB re full scale (0 -> -inf).  .struct is the zv_contour, which points into the arrays (kept alive here)."""
+    CHOICES = (False, True, "frames", "phonemes")
+
+    def __init__(self, T: int, n: int, frames: bool = True, phonemes: bool = True):
+        self.frames = np.zeros((T, 2), np.float32) if frames else None
+        self.phonemes = np.zeros((n, 2), np.float32) if phonemes else None
+
+    @property
+    def struct(self) -> ContourC:
+        return ContourC(None if self.frames is None else self.frames.ctypes.data,
+                        None if self.phonemes is None else self.phonemes.ctypes.data)
+
+    @staticmethod
+    def dbfs(levels) -> np.ndarray:
+        """20 * log10(level), full scale = 1.0; -inf for a level of 0"""
+        a = np.asarray(levels, dtype=np.float64)
+        with np.errstate(divide="ignore"):
+            return 20.0 * np.log10(a)
+
+    def __repr__(self):
+        shape = lambda a: None if a is None else a.shape
+        return f"Contour(frames={shape(self.frames)}, phonemes={shape(self.phonemes)})"
+
+
+def _check_contour(return_contour, where: str = ""):
+    """return_contour -> (frames asked for, phonemes asked for), checked before anything reaches the library: False, True (both
+    tables), "frames" or "phonemes" """
+    if isinstance(return_contour, (bool, np.bool_)):
+        return bool(return_contour), bool(return_contour)
+    if isinstance(return_contour, str):
+        if return_contour in ("frames", "phonemes"):
+            return return_contour == "frames", return_contour == "phonemes"
+        raise ValueError(f"{where}return_contour = {return_contour!r}: expected False, True, 'frames' or 'phonemes'")
+    raise TypeError(f"{where}return_contour must be a bool, 'frames' or 'phonemes', not {type(return_contour).__name__}")
 
 
 class EnvelopeC(C.Structure):
@@ -343,6 +389,12 @@ def load_library(path: Optional[str] = None):
         lib.zv_synthesize_envelope.argtypes = lib.zv_synthesize_volume.argtypes + ev
         lib.zv_synthesize_batch_envelope.argtypes = lib.zv_synthesize_batch_volume.argtypes + ev
         lib.zv_synthesize_batch_begin_envelope.argtypes = lib.zv_synthesize_batch_begin_volume.argtypes + ev
+    # the contour forms: the _envelope argument lists and the contours (zv_contour, batches [n_utt]) or NULL
+    if hasattr(lib, "zv_synthesize_contour"):
+        ct = [C.POINTER(ContourC)]
+        lib.zv_synthesize_contour.argtypes = lib.zv_synthesize_envelope.argtypes + ct
+        lib.zv_synthesize_batch_contour.argtypes = lib.zv_synthesize_batch_envelope.argtypes + ct
+        lib.zv_synthesize_batch_begin_contour.argtypes = lib.zv_synthesize_batch_begin_envelope.argtypes + ct
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -417,13 +469,17 @@ def _check_target(target, T):
 
 
 def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None, volume=None, levels=None,
-                  envelope=None):
+                  envelope=None, contour=None):
     """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
     name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status.
     fitted: name_fitted, which takes everything (NULL for what the call lacks).  target (a frame count, or the batches' uint32
     array): name_target, which takes everything and the fitted flag.  volume / levels (a zv_volume and a zv_level, or the batches'
     arrays): name_volume, which takes everything the _target form takes and the two (a call without a target passes 0 / NULL).
-    envelope (a zv_envelope, or the batches' array): name_envelope, which takes everything the _volume form takes and the envelope"""
+    envelope (a zv_envelope, or the batches' array): name_envelope, which takes everything the _volume form takes and the envelope.
+    contour (a zv_contour, or the batches' array): name_contour, which takes everything the _envelope form takes and the contour;
+    only a call that asks for a contour goes there"""
+    if contour is not None:
+        return getattr(lib, name + "_contour")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour)
     if envelope is not None:
         return getattr(lib, name + "_envelope")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope)
     if volume is not None or levels is not None:
@@ -617,7 +673,7 @@ class Model:
 
     def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False,
                    fitted: bool = False, target_frames: Optional[int] = None, *, volume=None, return_levels: bool = False,
-                   envelope=None):
+                   envelope=None, return_contour=False):
         """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
         arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
         as a third element.  fitted: zv_synthesize_fitted — T is a capacity, the utterance is decoded and vocoded as the n_frames
@@ -627,7 +683,10 @@ class Model:
         volume (Volume, dict or (gain, target_rms, peak_ceiling)) or return_levels: zv_synthesize_volume — the waveform is measured
         and scaled on the device; return_levels adds the Level (rms and peak before the gain, the gain) as the last element.
         envelope (Envelope or dict of its fields): zv_synthesize_envelope — per-phoneme gains, cross-fades and fades, applied on the
-        device ahead of the volume"""
+        device ahead of the volume.
+        return_contour (False, True, "frames" or "phonemes"): zv_synthesize_contour — the level and peak of every frame and / or every
+        phoneme of the returned waveform, metered on the device; adds a Contour as the last element"""
+        want_frames, want_phonemes = _check_contour(return_contour)
         fitted = _check_fitted(fitted, [T])
         target = _check_target(target_frames, T)
         vol, return_levels = _volume(volume), _check_levels(return_levels)
@@ -641,36 +700,45 @@ class Model:
         pc = _phoneme_controls(phonemes, len(ids))
         dur = np.empty(len(ids), np.int32) if return_durations else None
         level = Level() if vol is not None or return_levels else None
-        if (level is not None or env is not None) and target is None:
-            target = 0                       # the _volume and _envelope forms take a count, 0 = none
+        contour = Contour(T, len(ids), want_frames, want_phonemes) if want_frames or want_phonemes else None
+        if (level is not None or env is not None or contour is not None) and target is None:
+            target = 0                       # the _volume, _envelope and _contour forms take a count, 0 = none
         self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur),
-                                fitted, target, _ref(vol), _ref(level), _ref(None if env is None else env.struct)))
+                                fitted, target, _ref(vol), _ref(level), _ref(None if env is None else env.struct),
+                                _ref(None if contour is None else contour.struct)))
         out = (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
-        return out + (level,) if return_levels else out
+        out = out + (level,) if return_levels else out
+        return out + (contour,) if contour is not None else out
 
     def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
-                      return_levels: bool = False, envelope=None) -> "BatchCall":
+                      return_levels: bool = False, envelope=None, return_contour=False) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
         buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list.  fitted: the
         zv_synthesize_batch_fitted / _begin_fitted entry points (the lane form: .begin(lane) / .end(lane))"""
-        return BatchCall(self, utterances, durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope)
+        return BatchCall(self, utterances, durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
+                         return_contour=return_contour)
 
     def synthesize_batch(self, utterances, return_durations: bool = False, fitted: bool = False, *, volume=None,
-                         return_levels: bool = False, envelope=None):
+                         return_levels: bool = False, envelope=None, return_contour=False):
         """utterances: list of (ids, puncts, style, T[, prosody[, phonemes[, target_frames]]]) -> list of (wav, n_frames); each
         utterance keeps its own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its
         per-phoneme controls (PhonemeControls, dict of arrays or None), with a seventh its target frame count (None / 0: none).  return_durations: (wav, n_frames, durations) tuples.  fitted:
         zv_synthesize_batch_fitted — every T is a capacity, wav keeps the capacity shape with zeros behind n_frames * hop.
         volume: a list, one Volume (dict, 3-sequence) or None per utterance — zv_synthesize_batch_volume; return_levels: every tuple
         gains the utterance's Level as its last element.  envelope: a list, one Envelope (dict) or None per utterance —
-        zv_synthesize_batch_envelope"""
-        call = BatchCall(self, utterances, return_durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope)
+        zv_synthesize_batch_envelope.  return_contour: False, True, "frames" or "phonemes" for the whole batch, or a list with one of
+        them per utterance — zv_synthesize_batch_contour; every tuple gains the utterance's Contour (None where it asked for none) as
+        its last element"""
+        call = BatchCall(self, utterances, return_durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
+                         return_contour=return_contour)
         call.run()
         res = call.results()
         if return_durations:
             res = [r + (d,) for r, d in zip(res, call.durations)]
         if call.return_levels:
             res = [r + (Level.from_buffer_copy(lv),) for r, lv in zip(res, call.levels)]
+        if call.contour is not None:
+            res = [r + (c,) for r, c in zip(res, call.contours)]
         return res
 
     # ---- device-resident API ----
@@ -753,11 +821,24 @@ class BatchCall:
     which holds every utterance's Level after run() / end().
     envelope (a list, one Envelope / dict or None per utterance): the _envelope entry points, with the zv_envelope array .envelope (None
     entries get the identity; set_envelope() rewrites an entry for the next run() / begin()); .ekeep[i] is utterance i's checked
-    Envelope, whose gains the array points into."""
+    Envelope, whose gains the array points into.
+    return_contour (False, True, "frames" or "phonemes" for the whole batch, or a list with one of them per utterance): where any
+    utterance asks for a table, the _contour entry points, with the zv_contour array .contour; .contours[i] is utterance i's Contour
+    (None where it asked for none), whose arrays hold its rows after run() / end()."""
 
     def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
-                 return_levels: bool = False, envelope=None):
+                 return_levels: bool = False, envelope=None, return_contour=False):
         self.fitted = _check_fitted(fitted, [u[3] for u in utterances])
+        if isinstance(return_contour, (list, tuple)):
+            if len(return_contour) != len(utterances):
+                raise ValueError(f"return_contour has {len(return_contour)} entries, the batch has {len(utterances)} utterances")
+            wishes = [_check_contour(w, f"utterance {i}: ") for i, w in enumerate(return_contour)]
+        else:
+            wishes = [_check_contour(return_contour)] * len(utterances)
+        self.contour = self.contours = None
+        if any(f or p for f, p in wishes):
+            self.contours = [Contour(u[3], len(u[0]), f, p) if f or p else None for (f, p), u in zip(wishes, utterances)]
+            self.contour = (ContourC * len(utterances))(*[c.struct if c is not None else ContourC() for c in self.contours])
         self.envelope = self.ekeep = None
         if envelope is not None:
             envs = list(envelope)
@@ -846,14 +927,14 @@ class BatchCall:
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope))
+                             self.volume, self.levels, self.envelope, self.contour))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope))
+                             self.volume, self.levels, self.envelope, self.contour))
 
     def end(self, lane: int):
         m = self.model

@@ -167,7 +167,17 @@ struct Request
     zv_level                  *levels = nullptr;
     // amplitude envelope (zv_*_envelope): [count] or null; each struct's phoneme_gain is [n[u]] or null
     const zv_envelope         *envelope = nullptr;
+    // level contour (zv_*_contour): [count] or null; each struct's tables are [T[u]] and [n[u]] or null
+    const zv_contour          *contour = nullptr;
 
+    // any utterance that asks for a table of its contour: then every row of both tables is written on the device, and the host
+    // downloads the tables that were asked for
+    bool contours() const
+    {
+        for (uint32_t u = 0; contour && u < count; u++)
+            if (contour[u].frames || contour[u].phonemes) return true;
+        return false;
+    }
     // the call carries an envelope: then every utterance gets a gain row per token and an envelope row (the identity where it has none)
     bool envelopes() const { return envelope != nullptr; }
     // the call measures levels: then every utterance gets a volume row (the identity where none is given) and a level row
@@ -215,6 +225,7 @@ struct Request
         if (volume) s.volume += a;
         if (levels) s.levels += a;
         if (envelope) s.envelope += a;
+        if (contour) s.contour += a;
         return s;
     }
 };
@@ -255,6 +266,7 @@ static void pack_volume(const Request &r, float *vol)
     }
 }
 static_assert(sizeof(zv_level) == sizeof(zv::LevelRow) && sizeof(zv_level) == 16, "zv_level is the kernels' LevelRow");
+static_assert(sizeof(zv_frame_level) == sizeof(zv::ContourRow) && sizeof(zv_frame_level) == 8, "zv_frame_level is the kernels' ContourRow");
 
 static void check_envelope(const zv_envelope &e, uint32_t n)
 {
@@ -415,7 +427,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const bool tg = r.targets(), pc = r.phoneme_controls() || tg, dur = r.timings();
         const size_t E = M.E(), b_ids = (size_t)n * 4, b_hid = (size_t)T * E * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
         const size_t b_ctl = r.prosody || tg ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
-        const bool vol = r.volumes() && !taps, env = r.envelopes() && !taps;
+        const bool vol = r.volumes() && !taps, env = r.envelopes() && !taps, ctr = r.contours() && !taps;
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
         // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
@@ -424,12 +436,15 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const size_t o_nf = L.at(4), o_ids = L.at(b_ids), o_pun = L.at(b_ids), o_sty = L.at(E * 4), o_ctl = L.at(b_ctl),
                      o_pctl = L.at(b_pctl), o_hid = L.at(b_hid);
         const size_t o_mel = taps ? 0 : L.at((size_t)T * M.hp.audio_num_mels * 4), o_wav = taps ? 0 : L.at(b_wav),
-                     o_cum = taps ? 0 : L.at(dur || env ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
+                     o_cum = taps ? 0 : L.at(dur || env || ctr ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
                      o_runs = L.at(!r.fitted && !taps ? sizeof(zv::Seg) : 0);
         // [volume row][level row] (volume controls: the row uploaded, the level written on the device)
         const size_t o_vol = L.at(vol ? zv::LEVEL_VOL_STRIDE * 4 : 0), o_lvl = L.at(vol ? sizeof(zv::LevelRow) : 0);
         // [gain row per token][envelope row] (amplitude envelope: both uploaded)
         const size_t o_eg = L.at(env ? b_ids : 0), o_env = L.at(env ? zv::ENV_CTL_STRIDE * 4 : 0);
+        // [frame rows][phoneme rows] (level contour: both written on the device; the last regions, so no other offset moves)
+        const size_t b_cfr = (size_t)T * sizeof(zv::ContourRow), b_cph = (size_t)n * sizeof(zv::ContourRow);
+        const size_t o_cfr = L.at(ctr ? b_cfr : 0), o_cph = L.at(ctr ? b_cph : 0);
         char *io = (char *)M.io_scratch(L.size());
         int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
@@ -491,12 +506,21 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         else
         {
             float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
-            if (dur || env) bt.d_cum = (int32_t *)(io + o_cum);       // an envelope's knots pass searches the scan behind the vocoder
+            // an envelope's knots pass and a contour's phonemes pass read the scan behind the vocoder
+            if (dur || env || ctr) bt.d_cum = (int32_t *)(io + o_cum);
+            if (ctr)
+            {
+                bt.d_ctr_frames = (zv::ContourRow *)(io + o_cfr);
+                bt.d_ctr_phonemes = (zv::ContourRow *)(io + o_cph);
+            }
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
             ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream()));
             if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), bt.d_cum, b_ids, hipMemcpyDeviceToHost, M.stream()));
             ZV_HIP(hipMemcpyAsync(r.out[0], d_wav, b_wav, hipMemcpyDeviceToHost, M.stream()));
             if (vol) ZV_HIP(hipMemcpyAsync(&level, io + o_lvl, sizeof(level), hipMemcpyDeviceToHost, M.stream()));
+            // the contour's tables go straight to the caller, like the waveform: the ones asked for
+            if (ctr && r.contour[0].frames) ZV_HIP(hipMemcpyAsync(r.contour[0].frames, io + o_cfr, b_cfr, hipMemcpyDeviceToHost, M.stream()));
+            if (ctr && r.contour[0].phonemes) ZV_HIP(hipMemcpyAsync(r.contour[0].phonemes, io + o_cph, b_cph, hipMemcpyDeviceToHost, M.stream()));
         }
         M.sync();
         if (vol && r.levels) r.levels[0] = level;
@@ -709,6 +733,11 @@ struct PendingBatch
     // volume controls (zv_synthesize_batch_begin_volume): the level rows land in h_lvl, handed out to levels[n_utt] (may be null)
     const zv_level       *h_lvl = nullptr;
     zv_level             *levels = nullptr;
+    // level contour (zv_synthesize_batch_begin_contour): the rows land in h_cfr (packed like the waveforms, a row per frame) and h_cph
+    // (packed like the tokens, noff[u] rows ahead of utterance u) and are handed out to the tables each utterance asked for
+    std::vector<size_t>   noff;
+    std::vector<zv_contour> contour;
+    const zv_frame_level *h_cfr = nullptr, *h_cph = nullptr;
 };
 static PendingBatch &pending_slot(zv_model *m, int lane)
 {
@@ -744,7 +773,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
     const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings(), vol = r.volumes(),
-               env = r.envelopes();
+               env = r.envelopes(), ctr = r.contours();
     uint32_t nmax = 0, tmax = 0, ntot = 0;
     for (uint32_t u = 0; u < r.count; u++)
     {
@@ -777,23 +806,33 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
     Layout dev;
     const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
-                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || env ? bt.n_rows * 4 : 0),
+                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || env || ctr ? bt.n_rows * 4 : 0),
                  o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0),      // fitted: the live frame table, written on the device
                  o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0),     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
-                 o_lvl = dev.at(vol ? (size_t)bt.nseg * sizeof(zv::LevelRow) : 0);             // volume controls: the level rows, written on the device
+                 o_lvl = dev.at(vol ? (size_t)bt.nseg * sizeof(zv::LevelRow) : 0),             // volume controls: the level rows, written on the device
+                 o_cfr = dev.at(ctr ? bt.t_rows * sizeof(zv::ContourRow) : 0),                 // level contour: the frame rows and the phoneme rows, next to them,
+                 o_cph = dev.at(ctr ? bt.n_rows * sizeof(zv::ContourRow) : 0);                 // by absolute frame row / token row, written on the device
     M.reserve_batch(bt);
     char *io = (char *)M.io_scratch(dev.size());
-    // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan]
+    // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan][level rows][contour frame rows]
+    // [contour phoneme rows] (contour: a table only where some utterance asks for it; the rows packed like the waveforms / the tokens)
     size_t wav_bytes = 0;
     pb.woff.assign(r.count, 0);
+    pb.noff.assign(r.count + 1, 0);
+    bool ctr_f = false, ctr_p = false;
     for (uint32_t u = 0; u < r.count; u++)
     {
         pb.woff[u] = wav_bytes;
         wav_bytes += (size_t)r.T[u] * hop * 4;
+        pb.noff[u + 1] = pb.noff[u] + r.n[u];
+        ctr_f = ctr_f || (ctr && r.contour[u].frames);
+        ctr_p = ctr_p || (ctr && r.contour[u].phonemes);
     }
+    const size_t frame_rows = wav_bytes / (hop * 4);
     Layout host;
     const size_t p_in = host.at(b_in), p_nf = host.at((size_t)bt.nseg * 4), p_wav = host.at(wav_bytes),
-                 p_cum = host.at(dur ? bt.n_rows * 4 : 0), p_lvl = host.at(vol ? (size_t)bt.nseg * sizeof(zv_level) : 0);
+                 p_cum = host.at(dur ? bt.n_rows * 4 : 0), p_lvl = host.at(vol ? (size_t)bt.nseg * sizeof(zv_level) : 0),
+                 p_cfr = host.at(ctr_f ? frame_rows * sizeof(zv_frame_level) : 0), p_cph = host.at(ctr_p ? (size_t)ntot * sizeof(zv_frame_level) : 0);
     char *pin = (char *)M.pinned_scratch(host.size());
     char *d_in = io + o_in, *h_in = pin + p_in;
     {
@@ -823,7 +862,13 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     if (ctl) bt.d_ctl = (const float *)(d_in + i_ctl);
     bt.has_targets = tg;
     if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
-    if (dur || env) bt.d_cum = (int32_t *)(io + o_cum);         // an envelope's knots pass searches the scan behind the vocoder
+    // an envelope's knots pass and a contour's phonemes pass read the scan behind the vocoder
+    if (dur || env || ctr) bt.d_cum = (int32_t *)(io + o_cum);
+    if (ctr)
+    {
+        bt.d_ctr_frames = (zv::ContourRow *)(io + o_cfr);
+        bt.d_ctr_phonemes = (zv::ContourRow *)(io + o_cph);
+    }
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
     if (M.dec_plan(bt).runs) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
     if (vol)
@@ -843,6 +888,17 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     int32_t *h_nf = (int32_t *)(pin + p_nf), *h_cum = dur ? (int32_t *)(pin + p_cum) : nullptr;
     char *h_wav = pin + p_wav;
     zv_level *h_lvl = vol ? (zv_level *)(pin + p_lvl) : nullptr;
+    zv_frame_level *h_cfr = ctr_f ? (zv_frame_level *)(pin + p_cfr) : nullptr, *h_cph = ctr_p ? (zv_frame_level *)(pin + p_cph) : nullptr;
+    // the contour rows of utterances [u0, u1) travel behind their waveforms on stream `st`: frame rows packed like the waveforms
+    // (a frame row per hop samples), phoneme rows like the tokens
+    auto contour_download = [&](uint32_t u0, uint32_t u1, hipStream_t st) {
+        const size_t f0 = pb.woff[u0] / (hop * 4), f1 = u1 < r.count ? pb.woff[u1] / (hop * 4) : frame_rows;
+        const size_t n0 = pb.noff[u0], n1 = pb.noff[u1];
+        if (h_cfr && f1 > f0)
+            ZV_HIP(hipMemcpyAsync(h_cfr + f0, bt.d_ctr_frames + f0, (f1 - f0) * sizeof(zv_frame_level), hipMemcpyDeviceToHost, st));
+        if (h_cph && n1 > n0)
+            ZV_HIP(hipMemcpyAsync(h_cph + n0, bt.d_ctr_phonemes + n0, (n1 - n0) * sizeof(zv_frame_level), hipMemcpyDeviceToHost, st));
+    };
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
     // run.  Same kernels on the same rows: same bits.
@@ -869,6 +925,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
             if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream()));
             ZV_HIP(hipMemcpyAsync(h_wav, d_wav, wav_bytes, hipMemcpyDeviceToHost, M.stream()));
             if (vol) ZV_HIP(hipMemcpyAsync(h_lvl, io + o_lvl, (size_t)bt.nseg * sizeof(zv_level), hipMemcpyDeviceToHost, M.stream()));
+            contour_download(0, r.count, M.stream());
             ZV_HIP(hipEventRecord(M.tail_event(1), M.stream()));
         }
         else
@@ -890,6 +947,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
                 ZV_HIP(hipEventRecord(M.tail_event(2 * g), M.stream()));
                 ZV_HIP(hipStreamWaitEvent(cs, M.tail_event(2 * g), 0));
                 ZV_HIP(hipMemcpyAsync(h_wav + o0, (const char *)d_wav + o0, o1 - o0, hipMemcpyDeviceToHost, cs));
+                contour_download(u0, u1, cs);
                 ZV_HIP(hipEventRecord(M.tail_event(2 * g + 1), cs));
             }
             ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream()));
@@ -915,6 +973,10 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     pb.h_cum = h_cum;
     pb.h_lvl = h_lvl;
     pb.levels = r.levels;
+    pb.h_cfr = h_cfr;
+    pb.h_cph = h_cph;
+    if (ctr) pb.contour.assign(r.contour, r.contour + r.count);      // the struct array is read here, the tables are written in batch_finish
+    else pb.contour.clear();
     pb.N.assign(r.n, r.n + r.count);
     if (dur) pb.dur.assign(r.durations, r.durations + r.count);
     else pb.dur.clear();
@@ -948,6 +1010,12 @@ static void batch_finish(zv_model *m, int lane)
         for (uint32_t u = 0; u < pb.n_utt; u++) pb.n_frames[u] = (uint32_t)pb.h_nf[u];
     if (pb.h_cum) durations_from_cum(pb.h_cum, pb.n_utt, pb.N.data(), pb.T.data(), pb.dur.data());
     if (pb.h_lvl && pb.levels) memcpy(pb.levels, pb.h_lvl, (size_t)pb.n_utt * sizeof(zv_level));
+    for (uint32_t u = 0; u < pb.n_utt && !pb.contour.empty(); u++)
+    {
+        const zv_contour &c = pb.contour[u];
+        if (c.frames) memcpy(c.frames, pb.h_cfr + pb.woff[u] / (pb.hop * 4), (size_t)pb.T[u] * sizeof(zv_frame_level));
+        if (c.phonemes) memcpy(c.phonemes, pb.h_cph + pb.noff[u], (size_t)pb.N[u] * sizeof(zv_frame_level));
+    }
 }
 
 // how many utterances from `a` on form one launch group: up to 64 utterances / 64 Ki frames of capacity
@@ -1164,6 +1232,37 @@ zv_status zv_synthesize_batch_begin_envelope(zv_model *m, uint32_t lane, uint32_
 {
     return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
                                  durations, fitted != 0, target_frames, volume, levels, envelope});
+}
+
+// The contour forms: the _envelope requests plus the contours (NULL, or no table asked for: the request of the _envelope call).
+zv_status zv_synthesize_contour(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                                float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                const zv_envelope *envelope, const zv_contour *contour)
+{
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody, phonemes, &durations, fitted != 0,
+                          &target_frames, volume, levels, envelope, contour});
+}
+
+zv_status zv_synthesize_batch_contour(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                      const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                      uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                      int32_t *const *durations, const uint32_t *target_frames, int fitted, const zv_volume *volume,
+                                      zv_level *levels, const zv_envelope *envelope, const zv_contour *contour)
+{
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                durations, fitted != 0, target_frames, volume, levels, envelope, contour});
+}
+
+zv_status zv_synthesize_batch_begin_contour(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                            const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                            const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                            const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                            const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                            const zv_envelope *envelope, const zv_contour *contour)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                 durations, fitted != 0, target_frames, volume, levels, envelope, contour});
 }
 
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)

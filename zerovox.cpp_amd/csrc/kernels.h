@@ -15,6 +15,7 @@
 #include "stage_plan.h"    // att_plan, linear_plan, lr_plan, layernorm_tail_ok; the schedules' enc_plan and dec_plan
 #include "level.h"        // volume controls: LEVEL_CHUNK_SAMPLES, LEVEL_VOL_STRIDE, LevelRow
 #include "envelope.h"     // amplitude envelope: ENV_CTL_STRIDE, ENV_MAX_RAMP, ENV_MAX_GAIN
+#include "contour.h"      // level contour: CONTOUR_CHUNK_FRAMES, ContourRow
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -428,5 +429,19 @@ hipError_t launch_env_knots(hipStream_t s, const int32_t *cum, const float *gain
                             uint32_t *knots, const Segs &tokens, const Segs &frames);
 hipError_t launch_env_apply(hipStream_t s, float *wav, const int32_t *n_frames, const uint32_t *knots, const int32_t *env,
                             const Segs &frames, int hop);
+
+// ---- level contour (include/zerovox_amd.h "level contour", contour.h): two passes behind the volume passes, over the waveform the
+// caller receives.  `frames` is the CAPACITY table or inline segment, `tokens` the token table; both passes index by ABSOLUTE row.
+//   frames:   slab[frames[u].row0 + f] = {S_f lo, S_f hi, P_f, 0} for every frame f of every segment's capacity, 16 bytes each, and,
+//             where rows is not null, rows[frames[u].row0 + f] = {rms, peak} of the frame
+//   phonemes: rows[tokens[u].row0 + i] = {rms, peak} of phoneme i, for every token row of every segment; its frames come from cum [token
+//             rows], the length regulator's scan, clipped to the segment's capacity as the phoneme timings are (contour_extent)
+// slab: 16-byte aligned, one entry per frame row; rows: 8-byte aligned.  No atomics, nothing to zero: phonemes reads only what frames
+// has stored in the same run.  The frames pass reads whole 16-byte loads per frame: launch_contour_frames refuses a hop that is no
+// multiple of 4 (contour_hop_supported) — the loader accepts hop 300 alone, so no scalar path could ever run.
+bool       contour_hop_supported(int hop);
+hipError_t launch_contour_frames(hipStream_t s, const float *wav, void *slab, ContourRow *rows, const Segs &frames, int hop);
+hipError_t launch_contour_phonemes(hipStream_t s, const int32_t *cum, const void *slab, ContourRow *rows, const Segs &tokens,
+                                   const Segs &frames, int hop);
 
 }  // namespace zv

@@ -7,4 +7,5 @@
 #include "runs_kernels.hip"           // run tables of vocoder and decoder
 #include "level_kernels.hip"          // level meter
 #include "envelope_kernels.hip"       // amplitude envelope
+#include "contour_kernels.hip"        // level contour
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

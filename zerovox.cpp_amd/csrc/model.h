@@ -104,6 +104,12 @@ struct Batch
     // Keyed like d_ctl: the vocoder ends in two launches more, ahead of the volume passes; the VALUES are read at run time.
     const float   *d_env_gain = nullptr;
     const int32_t *d_env = nullptr;
+    // Level contour (include/zerovox_amd.h "level contour", contour.h), both set or none: the frame rows, ContourRow [t_rows], and the
+    // phoneme rows, ContourRow [n_rows], in HBM outside the arena, indexed by absolute frame row / token row.  With them d_cum is set
+    // (the phonemes pass reads the regulator's scan behind the vocoder).  Keyed like d_vol: the vocoder ends in two launches more,
+    // behind the volume passes.  WHICH rows a caller receives is the host's business at download time: every row is written.
+    ContourRow *d_ctr_frames = nullptr;
+    ContourRow *d_ctr_phonemes = nullptr;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -133,7 +139,7 @@ struct Batch
                d_frm == o.d_frm && (d_tok || memcmp(&tok1, &o.tok1, sizeof(Seg)) == 0) && (d_frm || memcmp(&frm1, &o.frm1, sizeof(Seg)) == 0) &&
                d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live && has_targets == o.has_targets &&
                d_dec_runs == o.d_dec_runs && d_vol == o.d_vol && d_levels == o.d_levels && d_nframes == o.d_nframes && d_env_gain == o.d_env_gain &&
-               d_env == o.d_env;
+               d_env == o.d_env && d_ctr_frames == o.d_ctr_frames && d_ctr_phonemes == o.d_ctr_phonemes;
     }
 };
 
@@ -363,6 +369,9 @@ class Model
         // amplitude envelope (kernels.h launch_env_knots): the knots, one uint32 per frame and one more per segment.  Sized by t_rows
         // alone (env_knot_entries) and carved in front of the run table like the slab
         uint32_t *env_knots;
+        // level contour (kernels.h launch_contour_frames): the frames' totals, 16 bytes per frame row, t_rows entries, carved in front
+        // of the run table like the slab
+        void *contour_slab;
         float *mel_c; int32_t *eq; Seg *runs;
     };
     // entries of VocLayout::level_slab: >= nseg * level_chunks(t_max, hop) for every Batch with nseg * t_max <= t_rows, a sub-batch included

@@ -72,6 +72,7 @@ Model::VocLayout Model::voc_layout(DeviceArena &a, const Batch &bt) const
     v.eq = a.take_n<int32_t>(bt.t_rows);
     v.level_slab = a.take(level_slab_entries(bt) * 16);
     v.env_knots = a.take_n<uint32_t>(env_knot_entries(bt));
+    v.contour_slab = a.take(bt.t_rows * 16);
     v.runs = a.take_n<Seg>(bt.nseg);
     return v;
 }
@@ -495,6 +496,25 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         ZV_LAUNCH("voc_level_measure", 4.0 * speech_samples, 0.0, launch_level_measure(stream(), d_wav, bt.d_nframes, lay.level_slab, cap, rate));
         ZV_LAUNCH("voc_level_apply", 8.0 * cap_samples, 0.0,
                   launch_level_apply(stream(), d_wav, bt.d_nframes, lay.level_slab, bt.d_vol, bt.d_levels, cap, rate));
+    }
+
+    // Level contour (contour.h): behind the envelope and the volume passes, so it meters the waveform the caller receives — per tail
+    // group, ahead of the group's download.  Only where the call carries a contour; never under a one-layer tap.
+    if (bt.d_ctr_frames && dbg_layer.kind < 0)
+    {
+        if (!bt.d_cum || !bt.d_ctr_phonemes) fail(ZV_ERR_DEVICE, "internal: a contour without the scan or the phoneme rows");
+        // Slab entries and rows sit at a segment's ABSOLUTE frame row (the table's row0, which a sub-batch keeps) and absolute token
+        // row: consecutive tail groups write disjoint ranges.  Unlike the envelope's knot table this relies on no order between the
+        // groups, only on the phonemes pass running behind the frames pass of its own group on the lane's stream.
+        const Segs cap = bt.frames_cap();
+        const Segs tk{bt.d_tok ? bt.d_tok + seg0 : nullptr, bt.nseg, bt.n_max, bt.tok1};
+        const double cap_rows = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg);
+        const double tok_rows = std::min((double)bt.n_rows, (double)bt.n_max * bt.nseg);
+        // algorithmic bytes: the capacity's samples read once; the slab entries read (by capacity) and the phoneme rows written
+        ZV_LAUNCH("voc_contour_frames", 4.0 * cap_rows * rate, 0.0,
+                  launch_contour_frames(stream(), d_wav, lay.contour_slab, bt.d_ctr_frames, cap, rate));
+        ZV_LAUNCH("voc_contour_phonemes", 16.0 * cap_rows + 8.0 * tok_rows, 0.0,
+                  launch_contour_phonemes(stream(), bt.d_cum, lay.contour_slab, bt.d_ctr_phonemes, tk, cap, rate));
     }
 }
 

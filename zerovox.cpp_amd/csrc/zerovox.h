@@ -136,6 +136,12 @@ class ZeroVOXModel
     // e->phoneme_gain is [n] or null; n must be eval()'s phoneme count), cross-fade half-width and the two fades, applied on the
     // device ahead of the volume controls.  nullptr: none.  Works with everything above; values are checked when eval() runs.
     void set_envelope(const zv_envelope *e, uint32_t n);
+    // level contour (include/zerovox_amd.h "level contour") for the eval() calls that follow: the level and peak of every frame of the
+    // capacity and / or of every phoneme, metered on the device on the waveform get_wav() holds (behind envelope and volume).  A
+    // meter: nothing is scaled.  Works with everything above.
+    void set_contour(bool frames, bool phonemes) { contour_frames = frames; contour_phonemes = phonemes; }
+    const std::vector<zv_frame_level> &get_frame_levels() const { return frame_levels; }         // [max_seq_len], empty unless asked for
+    const std::vector<zv_frame_level> &get_phoneme_levels() const { return phoneme_levels; }     // [num_phonemes], likewise
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
@@ -168,6 +174,8 @@ class ZeroVOXModel
     zv_envelope          envelope = {nullptr, 0, 0, 0};
     std::vector<float>   env_gain;
     bool                 has_envelope = false, env_gain_set = false;
+    bool                 contour_frames = false, contour_phonemes = false;
+    std::vector<zv_frame_level> frame_levels, phoneme_levels;
 };
 
 }  // namespace ZeroVOX

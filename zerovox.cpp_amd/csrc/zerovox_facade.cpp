@@ -180,9 +180,11 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
     if (has_envelope && env_gain_set && env_gain.size() != num_phonemes)
         throw zv::Error(ZV_ERR_ARG, "set_envelope: gains for " + std::to_string(env_gain.size()) + " phonemes, eval() has " +
                                         std::to_string(num_phonemes));
-    if (has_volume || has_envelope)
+    frame_levels.assign(contour_frames ? hparams.max_seq_len : 0, zv_frame_level{0.0f, 0.0f});
+    phoneme_levels.assign(contour_phonemes ? num_phonemes : 0, zv_frame_level{0.0f, 0.0f});
+    if (has_volume || has_envelope || contour_frames || contour_phonemes)
     {
-        // the volume and envelope forms take what every other form takes (the finished waveform of the one-pass chain is scaled and measured)
+        // the volume, envelope and contour forms take what every other form takes (the finished waveform of the one-pass chain is scaled and measured)
         if (has_phonemes && pc_n != num_phonemes)
             throw zv::Error(ZV_ERR_ARG, "set_phoneme_controls: controls for " + std::to_string(pc_n) + " phonemes, eval() has " +
                                             std::to_string(num_phonemes));
@@ -191,9 +193,10 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
         if (record_durations) durations.assign(num_phonemes, 0);
         const zv_envelope env = {env_gain_set ? env_gain.data() : nullptr, envelope.ramp_frames, envelope.fade_in_samples,
                                  envelope.fade_out_samples};
-        chk(zv_synthesize_envelope(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
-                                   has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
-                                   has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr));
+        const zv_contour ctr = {contour_frames ? frame_levels.data() : nullptr, contour_phonemes ? phoneme_levels.data() : nullptr};
+        chk(zv_synthesize_contour(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
+                                  has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
+                                  has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr, &ctr));
         return;
     }
     if (record_durations || fitted || target_frames)

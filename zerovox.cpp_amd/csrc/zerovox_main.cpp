@@ -39,6 +39,11 @@
 //            per line (-200 .. 24.08, linear = 10^(dB / 20) <= 16); neighbouring phonemes cross-fade over 2R + 2 frames (0 <= R <= 64);
 //            the speech fades in / out over floor(X * sampling rate / 1000 + 0.5) samples (0 <= X <= 600000).  Applied on the device
 //            ahead of the volume controls.  Work with everything above.  A wrong line count or a bad value is a usage error.
+//   --contour FILE, --phoneme-levels FILE
+//            level contour (include/zerovox_amd.h "level contour"): the level and peak of every frame of the capacity (max_seq_len rows,
+//            also with --trim and --fit) / of every phoneme, metered on the device on the waveform that is written, as TSV: a header
+//            line, then index<TAB>rms<TAB>peak per row, linear re full scale, printed with %.9g (the f32 bits survive).  Work with
+//            everything above.  A missing file name is a usage error.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
 #include <algorithm>
 #include <cmath>
@@ -63,6 +68,7 @@ static void usage(FILE *f)
                "               [--phoneme-controls FILE] [--alignment FILE] [--target-frames F | --target-seconds S]\n"
                "               [--gain-db G] [--loudness-dbfs L] [--peak-dbfs P]\n"
                "               [--phoneme-gain-db FILE] [--ramp-frames R] [--fade-in-ms X] [--fade-out-ms X]\n"
+               "               [--contour FILE] [--phoneme-levels FILE]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
@@ -83,7 +89,9 @@ static void usage(FILE *f)
                "  --phoneme-gain-db FILE  one gain in dB per phoneme, one per line (-200 <= dB <= 24.08: a linear gain of at most 16)\n"
                "  --ramp-frames R      cross-fade neighbouring phonemes' gains over 2R + 2 frames (0 <= R <= 64), default 0\n"
                "  --fade-in-ms X       the speech rises linearly from 0 over floor(X * sampling rate / 1000 + 0.5) samples\n"
-               "  --fade-out-ms X      the speech falls linearly to 0 over as many samples; what follows it is silence\n",
+               "  --fade-out-ms X      the speech falls linearly to 0 over as many samples; what follows it is silence\n"
+               "  --contour FILE       write the level of every frame of the written waveform's capacity as TSV: index rms peak\n"
+               "  --phoneme-levels FILE  write the level of every phoneme likewise\n",
             k_default_model, k_default_out);
 }
 
@@ -208,7 +216,7 @@ static std::vector<int32_t> utterance_ids(const std::string &utt_path)
 
 int main(int argc, char **argv)
 {
-    std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path, gain_path;
+    std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path, gain_path, contour_path, plevel_path;
     bool trim = false, fit = false, info = false, controlled = false, leveled = false, enveloped = false;
     long ramp_frames = 0;              // --ramp-frames
     double fade_ms[2] = {0.0, 0.0};    // --fade-in-ms, --fade-out-ms
@@ -228,6 +236,8 @@ int main(int argc, char **argv)
         else if (a == "-o") out_path = need("-o");
         else if (a == "--phoneme-controls") pc_path = need("--phoneme-controls");
         else if (a == "--alignment") align_path = need("--alignment");
+        else if (a == "--contour") contour_path = need("--contour");
+        else if (a == "--phoneme-levels") plevel_path = need("--phoneme-levels");
         else if (a == "--target-frames")
         {
             const std::string v = need("--target-frames");
@@ -372,6 +382,7 @@ int main(int argc, char **argv)
                                      (uint32_t)std::min(floor(fade_ms[1] * rate / 1000.0 + 0.5), 2147483647.0)};
             model.set_envelope(&env, (uint32_t)gains.size());
         }
+        if (!contour_path.empty() || !plevel_path.empty()) model.set_contour(!contour_path.empty(), !plevel_path.empty());
         if (target_seconds > 0.0)
             target_frames = (long)std::min(floor(target_seconds * hp.audio_sampling_rate / hp.audio_hop_size + 0.5), 1e9);
         if (target_frames > 0 || target_seconds > 0.0)
@@ -435,6 +446,16 @@ int main(int argc, char **argv)
             }
             if (fclose(af) != 0) throw std::runtime_error("short write to '" + align_path + "'");
         }
+        // the contour's tables: %.9g prints an f32 so that it reads back to the same bits
+        auto write_levels = [](const std::string &path, const std::vector<zv_frame_level> &rows) {
+            FILE *cf = fopen(path.c_str(), "w");
+            if (!cf) throw std::runtime_error("cannot open '" + path + "' for writing");
+            fprintf(cf, "index\trms\tpeak\n");
+            for (size_t i = 0; i < rows.size(); i++) fprintf(cf, "%zu\t%.9g\t%.9g\n", i, (double)rows[i].rms, (double)rows[i].peak);
+            if (fclose(cf) != 0) throw std::runtime_error("short write to '" + path + "'");
+        };
+        if (!contour_path.empty()) write_levels(contour_path, model.get_frame_levels());
+        if (!plevel_path.empty()) write_levels(plevel_path, model.get_phoneme_levels());
         if (trim || fit)
         {
             const size_t n = (size_t)nf * hp.audio_hop_size;
