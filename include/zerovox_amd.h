@@ -17,6 +17,8 @@
  *   *_volume           the same with a gain, a loudness target and a peak ceiling per utterance (zv_volume) and the measured level out
  *   *_envelope         the same with per-phoneme gains, cross-fades and fades per utterance (zv_envelope)
  *   *_contour          the same with the level and peak of every frame and every phoneme out (zv_contour)
+ *   *_pitch            the same with the fundamental frequency and voicing of every frame and every phoneme out (zv_pitch)
+ *   zv_pitch_track     the pitch track of any waveform the caller brings
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file        src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -513,6 +515,91 @@ zv_status zv_synthesize_batch_begin_contour(zv_model *m, uint32_t lane, uint32_t
                                             const zv_phoneme_controls *phonemes, int32_t *const *durations,
                                             const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
                                             const zv_envelope *envelope, const zv_contour *contour);
+/* ---- pitch track: per-frame and per-phoneme fundamental frequency and voicing ------------------------------------------------------
+ * The read side of the pitch controls.  pitch_scale, pitch_shift and the per-phoneme pitch_shift[i] act on the variance predictor's
+ * output in prediction units; the pitch track tells what fundamental frequency came out, in Hz, per frame and per phoneme, from the
+ * same call and with no pass over the samples on the host: the pitch forms meter the finished waveform on the device, inside the same
+ * captured graph and — for a large batch — per tail group, ahead of that group's download and behind envelope, volume and contour.
+ * The pitch track is a meter: it changes no sample.  zv_pitch_track meters any waveform the caller brings (a reference recording).
+ * The rule, per utterance, with sr = audio_sampling_rate, hop = audio_hop_size, T the capacity, w[0 .. T*hop) the waveform the SAME
+ * call writes to wav (after fitted zeroing, envelope and volume: what the caller receives), durations[] and start_i as for the contour.
+ * Parameters, per utterance, each one at 0 takes its default: min_lag = sr / 441, max_lag = sr / 63, window = 2 * hop (integer
+ * divisions; lags in samples: 50, 350 and 600 at 22 050 Hz and hop 300, i.e. 63 .. 441 Hz), voiced_threshold = 0.5f.  With the
+ * defaults filled in, ZV_ERR_ARG before any work is enqueued unless 8 <= min_lag < max_lag <= 512, max_lag <= 8 * min_lag,
+ * 64 <= window <= 1024 and voiced_threshold is finite and in (0, 1]; the message names the entry point, the utterance and the
+ * field, and says so when the value is a default (the checkpoint's rate then needs explicit lags).  Three octaves at most: the
+ * search below starts at min_lag and must start outside the zero-lag lobe of the longest period it may report, which
+ * max_lag <= 8 * min_lag ensures even for a pure sinusoid.
+ * For frame 0 <= f < T, with Lmin = min_lag, Lmax = max_lag, W = window, M = W + Lmax + 1:
+ *   span     s0 = f*hop + hop/2 - M/2 (signed; both divisions of non-negative integers); y[t] = w[s0 + t] for 0 <= t < M where
+ *            0 <= s0 + t < T*hop and the sample is finite, else +0.0.  The span never reads another utterance's samples.
+ *   scale    Pk = the largest sign-cleared bit pattern in y.  Pk < 0x33800000 (a peak below 2^-24): the frame is silent, its row
+ *            {0, 0}.  Else e = (Pk >> 23) - 127, k = 9 - e, a[t] = sign(y[t]) * min((int64)((double)|y[t]| * 2^k + 0.5), 1023): the
+ *            conversion truncates, the product and the sum are single f64 operations; |a[t]| <= 1023, the peak lands in 512 .. 1023.
+ *   sums     for L in [Lmin - 1, Lmax + 1]: c(L) = sum over t < W of a[t] * a[t+L], E(L) = sum over t < W of a[t+L]^2, and
+ *            E0 = sum over t < W of a[t]^2: integers below 2^30, so no order of summation can show.
+ *   corr     r(L) = min((double)c(L) / sqrt((double)(uint64)(E0 * E(L))), 1.0) when c(L) > 0, E0 > 0 and E(L) > 0, else 0.
+ *   pick     rmax = max r(L) over Lmin <= L <= Lmax; rmax == 0: the row is {0, 0}.  L0 = the smallest L in that range with
+ *            r(L) >= 0.875 * rmax; L* = the smallest L >= L0 with L == Lmax or r(L+1) <= r(L); strength = r(L*).
+ *   refine   p = r(L*-1) - r(L*), n = r(L*+1) - r(L*), den = p + n.  den < 0: delta = ((r(L*-1) - r(L*+1)) / den) * 0.5, set to 0
+ *            unless -0.5 <= delta <= 0.5; else delta = 0.  f0 = (double)sr / ((double)L* + delta).
+ *   row      voiced = strength >= (double)voiced_threshold; frames[f] = {voiced ? (float)f0 : 0, (float)strength}; kept for the
+ *            phonemes: Fq = voiced ? (uint32)(f0 * 256.0 + 0.5) : 0, and the voiced flag.
+ * For phoneme 0 <= i < n, d = durations[i], over the frames start_i <= f < start_i + d: nv = the number of voiced frames, SF = the sum
+ * of their Fq (unsigned 64-bit); phonemes[i] = {nv > 0 ? (float)((double)SF / ((double)nv * 256.0)) : 0, d > 0 ? (float)((double)nv /
+ * (double)d) : 0}.  d == 0 gives {0, 0}.
+ * Every f64 step is one IEEE operation (the library builds with -ffp-contract=off); csrc/pitch.h holds the rule as plain C++ (host
+ * reference included).  What follows:
+ *   - multiplying the waveform by a power of two changes no row, as long as no sample becomes subnormal or infinite and the span's
+ *     peak stays at or above 2^-24;
+ *   - fitted zeros give {0, 0}; an unfitted tail is measured like the speech;
+ *   - a frame whose span reaches outside [0, T*hop) sees zeros there: its lag may be off near the two ends of an utterance.  That
+ *     is part of the rule, not an error;
+ *   - nothing depends on how lags or samples are dealt over lanes: integer sums, maxima and minima, ties going to the lower lag.
+ * pitch == NULL, or every struct with both table pointers NULL: the request of the _contour call, the same launches, the same graph,
+ * the same bits (the parameters of such a struct are not looked at).  With a pitch track the waveform, n_frames, durations, levels
+ * and contour rows keep exactly their bits.  Batches: pitch[n_utt] or NULL; an utterance may ask for one table, both or none, with
+ * its own parameters, and gives the rows of zv_synthesize_pitch(..., &pitch[u]).  The parameters travel in the batch's device input
+ * block like the other controls, so a replayed graph picks up new values.  The struct array is read before the call (_begin)
+ * returns; the tables it points to must stay valid until the call (batches in flight: _end) returns.  Arguments, limits and messages
+ * are otherwise those of the _contour forms.  zv_synthesize_batch_begin_pitch is finished by zv_synthesize_batch_end.
+ * zv_pitch_track meters a host waveform wav[T * hop] at the model's rate and hop, eagerly, on lane 0: pitch->frames is required,
+ * pitch->phonemes must be NULL (there are no timings), 0 < T <= zv_max_frames(), else ZV_ERR_ARG; the rows are those of the rule
+ * with w = wav.
+ * Out of scope: zv_vocode*, zv_vocode_stream and the encode / decode entry points; smoothing or tracking across frames (Viterbi,
+ * median filters: the caller filters the rows); any change of the pitch controls themselves; resampling. */
+typedef struct
+{
+    float f0_hz, strength;
+} zv_pitch_frame;               /* f0_hz 0 = unvoiced or silent */
+typedef struct
+{
+    float f0_hz, voiced;
+} zv_pitch_phoneme;             /* mean F0 of the voiced frames; share of voiced frames */
+typedef struct
+{
+    zv_pitch_frame   *frames;     /* [T] or NULL: one row per frame of the capacity */
+    zv_pitch_phoneme *phonemes;   /* [n] or NULL: one row per token                 */
+    uint32_t min_lag, max_lag, window;   /* 0 = default */
+    float    voiced_threshold;           /* 0 = default */
+} zv_pitch;                     /* zero-initialised = none */
+zv_status zv_synthesize_pitch(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                              float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                              int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                              const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch);
+zv_status zv_synthesize_batch_pitch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                    const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                    float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                    const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                    const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                    const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch);
+zv_status zv_synthesize_batch_begin_pitch(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                          const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                          const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                          const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                          const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                          const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch);
+zv_status zv_pitch_track(zv_model *m, const float *wav, uint32_t T, const zv_pitch *pitch);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

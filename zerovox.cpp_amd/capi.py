@@ -28,6 +28,7 @@ SYMBOLS = [
     "zv_synthesize_batch_begin_target", "zv_synthesize_volume", "zv_synthesize_batch_volume", "zv_synthesize_batch_begin_volume",
     "zv_debug_mfma_chain", "zv_synthesize_envelope", "zv_synthesize_batch_envelope", "zv_synthesize_batch_begin_envelope",
     "zv_synthesize_contour", "zv_synthesize_batch_contour", "zv_synthesize_batch_begin_contour",
+    "zv_synthesize_pitch", "zv_synthesize_batch_pitch", "zv_synthesize_batch_begin_pitch", "zv_pitch_track",
 ]
 
 
@@ -175,6 +176,77 @@ def _check_contour(return_contour, where: str = ""):
             return return_contour == "frames", return_contour == "phonemes"
         raise ValueError(f"{where}return_contour = {return_contour!r}: expected False, True, 'frames' or 'phonemes'")
     raise TypeError(f"{where}return_contour must be a bool, 'frames' or 'phonemes', not {type(return_contour).__name__}")
+
+
+class PitchC(C.Structure):
+    """zv_pitch of include/zerovox_amd.h: the two tables' pointers, zv_pitch_frame [T] and zv_pitch_phoneme [n], each or NULL, and the
+    parameters, 0 = default (a zeroed struct asks for nothing)"""
+    _fields_ = [("frames", C.c_void_p), ("phonemes", C.c_void_p), ("min_lag", C.c_uint32), ("max_lag", C.c_uint32),
+                ("window", C.c_uint32), ("voiced_threshold", C.c_float)]
+
+
+class PitchTrack:
+    """What a pitch track is asked for (include/zerovox_amd.h "pitch track"): the lags in samples, the window, the voicing threshold
+    (each 0: the default) and which tables.  from_hz converts a frequency range at a sampling rate to lags as the CLI does."""
+
+    def __init__(self, min_lag: int = 0, max_lag: int = 0, window: int = 0, voiced_threshold: float = 0.0, frames: bool = True,
+                 phonemes: bool = True):
+        for name, v in (("min_lag", min_lag), ("max_lag", max_lag), ("window", window)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"PitchTrack {name} must be an integer, not {type(v).__name__}")
+            if not 0 <= v <= 0xffffffff:
+                raise ValueError(f"PitchTrack {name} = {v} is outside [0, 4294967295]")
+        if isinstance(voiced_threshold, (bool, np.bool_)) or not isinstance(voiced_threshold, (int, float, np.integer, np.floating)):
+            raise TypeError(f"PitchTrack voiced_threshold must be a number, not {type(voiced_threshold).__name__}")
+        if not (isinstance(frames, (bool, np.bool_)) and isinstance(phonemes, (bool, np.bool_))):
+            raise TypeError("PitchTrack frames and phonemes must be bools")
+        self.min_lag, self.max_lag, self.window = int(min_lag), int(max_lag), int(window)
+        self.voiced_threshold = float(voiced_threshold)
+        self.frames, self.phonemes = bool(frames), bool(phonemes)
+
+    @classmethod
+    def from_hz(cls, sampling_rate: int, min_hz: float = 0.0, max_hz: float = 0.0, **kw):
+        """min_lag = sr / max_hz, max_lag = sr / min_hz, truncated; a frequency at 0 leaves its lag at the default"""
+        return cls(min_lag=int(sampling_rate / max_hz) if max_hz else 0, max_lag=int(sampling_rate / min_hz) if min_hz else 0, **kw)
+
+    def __repr__(self):
+        return (f"PitchTrack(min_lag={self.min_lag}, max_lag={self.max_lag}, window={self.window}, "
+                f"voiced_threshold={self.voiced_threshold}, frames={self.frames}, phonemes={self.phonemes})")
+
+
+class Pitch:
+    """An utterance's pitch track: .frames float32 [T, 2], columns (f0_hz, strength), and .phonemes float32 [n, 2], columns (mean
+    f0_hz of the voiced frames, share of voiced frames), of the waveform the same call returned; None for a table that was not asked
+    for.  .params is the PitchTrack; .struct is the zv_pitch, which points into the arrays (kept alive here)."""
+
+    def __init__(self, T: int, n: int, params: PitchTrack):
+        self.params = params
+        self.frames = np.zeros((T, 2), np.float32) if params.frames else None
+        self.phonemes = np.zeros((n, 2), np.float32) if params.phonemes else None
+
+    @property
+    def struct(self) -> PitchC:
+        p = self.params
+        return PitchC(None if self.frames is None else self.frames.ctypes.data, None if self.phonemes is None else self.phonemes.ctypes.data,
+                      p.min_lag, p.max_lag, p.window, p.voiced_threshold)
+
+    def __repr__(self):
+        shape = lambda a: None if a is None else a.shape
+        return f"Pitch(frames={shape(self.frames)}, phonemes={shape(self.phonemes)})"
+
+
+def _check_pitch(return_pitch, where: str = ""):
+    """return_pitch -> a PitchTrack or None (nothing asked for), checked before anything reaches the library: False, True (both
+    tables, default parameters), "frames", "phonemes" or a PitchTrack"""
+    if isinstance(return_pitch, PitchTrack):
+        return return_pitch if return_pitch.frames or return_pitch.phonemes else None
+    if isinstance(return_pitch, (bool, np.bool_)):
+        return PitchTrack() if return_pitch else None
+    if isinstance(return_pitch, str):
+        if return_pitch in ("frames", "phonemes"):
+            return PitchTrack(frames=return_pitch == "frames", phonemes=return_pitch == "phonemes")
+        raise ValueError(f"{where}return_pitch = {return_pitch!r}: expected False, True, 'frames', 'phonemes' or a PitchTrack")
+    raise TypeError(f"{where}return_pitch must be a bool, 'frames', 'phonemes' or a PitchTrack, not {type(return_pitch).__name__}")
 
 
 class EnvelopeC(C.Structure):
@@ -395,6 +467,13 @@ def load_library(path: Optional[str] = None):
         lib.zv_synthesize_contour.argtypes = lib.zv_synthesize_envelope.argtypes + ct
         lib.zv_synthesize_batch_contour.argtypes = lib.zv_synthesize_batch_envelope.argtypes + ct
         lib.zv_synthesize_batch_begin_contour.argtypes = lib.zv_synthesize_batch_begin_envelope.argtypes + ct
+    # the pitch forms: the _contour argument lists and the pitch tracks (zv_pitch, batches [n_utt]) or NULL; the stand-alone meter
+    if hasattr(lib, "zv_synthesize_pitch"):
+        pt = [C.POINTER(PitchC)]
+        lib.zv_synthesize_pitch.argtypes = lib.zv_synthesize_contour.argtypes + pt
+        lib.zv_synthesize_batch_pitch.argtypes = lib.zv_synthesize_batch_contour.argtypes + pt
+        lib.zv_synthesize_batch_begin_pitch.argtypes = lib.zv_synthesize_batch_begin_contour.argtypes + pt
+        lib.zv_pitch_track.argtypes = [vp, vp, C.c_uint32, C.POINTER(PitchC)]
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -469,7 +548,7 @@ def _check_target(target, T):
 
 
 def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None, volume=None, levels=None,
-                  envelope=None, contour=None):
+                  envelope=None, contour=None, pitch=None):
     """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
     name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status.
     fitted: name_fitted, which takes everything (NULL for what the call lacks).  target (a frame count, or the batches' uint32
@@ -477,7 +556,10 @@ def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, 
     arrays): name_volume, which takes everything the _target form takes and the two (a call without a target passes 0 / NULL).
     envelope (a zv_envelope, or the batches' array): name_envelope, which takes everything the _volume form takes and the envelope.
     contour (a zv_contour, or the batches' array): name_contour, which takes everything the _envelope form takes and the contour;
-    only a call that asks for a contour goes there"""
+    only a call that asks for a contour goes there.  pitch (a zv_pitch, or the batches' array): name_pitch, which takes everything the
+    _contour form takes and the pitch track; only a call that asks for a pitch track goes there"""
+    if pitch is not None:
+        return getattr(lib, name + "_pitch")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour, pitch)
     if contour is not None:
         return getattr(lib, name + "_contour")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour)
     if envelope is not None:
@@ -673,7 +755,7 @@ class Model:
 
     def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False,
                    fitted: bool = False, target_frames: Optional[int] = None, *, volume=None, return_levels: bool = False,
-                   envelope=None, return_contour=False):
+                   envelope=None, return_contour=False, return_pitch=False):
         """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
         arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
         as a third element.  fitted: zv_synthesize_fitted — T is a capacity, the utterance is decoded and vocoded as the n_frames
@@ -685,8 +767,11 @@ class Model:
         envelope (Envelope or dict of its fields): zv_synthesize_envelope — per-phoneme gains, cross-fades and fades, applied on the
         device ahead of the volume.
         return_contour (False, True, "frames" or "phonemes"): zv_synthesize_contour — the level and peak of every frame and / or every
-        phoneme of the returned waveform, metered on the device; adds a Contour as the last element"""
+        phoneme of the returned waveform, metered on the device; adds a Contour as the last element.
+        return_pitch (False, True, "frames", "phonemes" or a PitchTrack): zv_synthesize_pitch — the fundamental frequency and voicing
+        of every frame and / or every phoneme of the returned waveform, metered on the device; adds a Pitch as the last element"""
         want_frames, want_phonemes = _check_contour(return_contour)
+        track = _check_pitch(return_pitch)
         fitted = _check_fitted(fitted, [T])
         target = _check_target(target_frames, T)
         vol, return_levels = _volume(volume), _check_levels(return_levels)
@@ -701,25 +786,43 @@ class Model:
         dur = np.empty(len(ids), np.int32) if return_durations else None
         level = Level() if vol is not None or return_levels else None
         contour = Contour(T, len(ids), want_frames, want_phonemes) if want_frames or want_phonemes else None
-        if (level is not None or env is not None or contour is not None) and target is None:
-            target = 0                       # the _volume, _envelope and _contour forms take a count, 0 = none
+        pitch = Pitch(T, len(ids), track) if track is not None else None
+        if (level is not None or env is not None or contour is not None or pitch is not None) and target is None:
+            target = 0                       # the _volume, _envelope, _contour and _pitch forms take a count, 0 = none
         self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur),
                                 fitted, target, _ref(vol), _ref(level), _ref(None if env is None else env.struct),
-                                _ref(None if contour is None else contour.struct)))
+                                _ref(None if contour is None else contour.struct), _ref(None if pitch is None else pitch.struct)))
         out = (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
         out = out + (level,) if return_levels else out
-        return out + (contour,) if contour is not None else out
+        out = out + (contour,) if contour is not None else out
+        return out + (pitch,) if pitch is not None else out
+
+    def pitch_track(self, wav, params=None) -> Pitch:
+        """zv_pitch_track: the pitch track of a waveform the caller brings (float32 [T * hop] at the model's rate and hop), frames
+        only; params: a PitchTrack or None (the defaults)"""
+        if params is not None and not isinstance(params, PitchTrack):
+            raise TypeError(f"pitch_track: params must be a PitchTrack or None, not {type(params).__name__}")
+        p = params or PitchTrack()
+        track = PitchTrack(p.min_lag, p.max_lag, p.window, p.voiced_threshold, True, False)      # a waveform has no timings
+        w = np.ascontiguousarray(wav, dtype=np.float32)
+        hop = self.hp.audio_hop_size
+        if w.ndim != 1 or w.size == 0 or w.size % hop:
+            raise ValueError(f"pitch_track: the waveform must be a non-empty 1-D array of a multiple of {hop} samples, got shape {w.shape}")
+        pitch = Pitch(w.size // hop, 0, track)
+        st = pitch.struct
+        self._chk(self.lib.zv_pitch_track(self.h, _ptr(w), w.size // hop, C.byref(st)))
+        return pitch
 
     def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
-                      return_levels: bool = False, envelope=None, return_contour=False) -> "BatchCall":
+                      return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
         buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list.  fitted: the
         zv_synthesize_batch_fitted / _begin_fitted entry points (the lane form: .begin(lane) / .end(lane))"""
         return BatchCall(self, utterances, durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
-                         return_contour=return_contour)
+                         return_contour=return_contour, return_pitch=return_pitch)
 
     def synthesize_batch(self, utterances, return_durations: bool = False, fitted: bool = False, *, volume=None,
-                         return_levels: bool = False, envelope=None, return_contour=False):
+                         return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False):
         """utterances: list of (ids, puncts, style, T[, prosody[, phonemes[, target_frames]]]) -> list of (wav, n_frames); each
         utterance keeps its own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its
         per-phoneme controls (PhonemeControls, dict of arrays or None), with a seventh its target frame count (None / 0: none).  return_durations: (wav, n_frames, durations) tuples.  fitted:
@@ -728,9 +831,10 @@ class Model:
         gains the utterance's Level as its last element.  envelope: a list, one Envelope (dict) or None per utterance —
         zv_synthesize_batch_envelope.  return_contour: False, True, "frames" or "phonemes" for the whole batch, or a list with one of
         them per utterance — zv_synthesize_batch_contour; every tuple gains the utterance's Contour (None where it asked for none) as
-        its last element"""
+        its last element.  return_pitch: False, True, "frames", "phonemes" or a PitchTrack for the whole batch, or a list with one of
+        them per utterance — zv_synthesize_batch_pitch; every tuple gains the utterance's Pitch (None where it asked for none) last"""
         call = BatchCall(self, utterances, return_durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
-                         return_contour=return_contour)
+                         return_contour=return_contour, return_pitch=return_pitch)
         call.run()
         res = call.results()
         if return_durations:
@@ -739,6 +843,8 @@ class Model:
             res = [r + (Level.from_buffer_copy(lv),) for r, lv in zip(res, call.levels)]
         if call.contour is not None:
             res = [r + (c,) for r, c in zip(res, call.contours)]
+        if call.pitch is not None:
+            res = [r + (p,) for r, p in zip(res, call.pitches)]
         return res
 
     # ---- device-resident API ----
@@ -824,11 +930,24 @@ class BatchCall:
     Envelope, whose gains the array points into.
     return_contour (False, True, "frames" or "phonemes" for the whole batch, or a list with one of them per utterance): where any
     utterance asks for a table, the _contour entry points, with the zv_contour array .contour; .contours[i] is utterance i's Contour
-    (None where it asked for none), whose arrays hold its rows after run() / end()."""
+    (None where it asked for none), whose arrays hold its rows after run() / end().
+    return_pitch (False, True, "frames", "phonemes" or a PitchTrack for the whole batch, or a list with one of them per utterance): where
+    any utterance asks for a table, the _pitch entry points, with the zv_pitch array .pitch; .pitches[i] is utterance i's Pitch (None
+    where it asked for none); set_pitch() rewrites an entry's parameters and tables for the next run() / begin()."""
 
     def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
-                 return_levels: bool = False, envelope=None, return_contour=False):
+                 return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False):
         self.fitted = _check_fitted(fitted, [u[3] for u in utterances])
+        if isinstance(return_pitch, (list, tuple)):
+            if len(return_pitch) != len(utterances):
+                raise ValueError(f"return_pitch has {len(return_pitch)} entries, the batch has {len(utterances)} utterances")
+            tracks = [_check_pitch(w, f"utterance {i}: ") for i, w in enumerate(return_pitch)]
+        else:
+            tracks = [_check_pitch(return_pitch)] * len(utterances)
+        self.pitch = self.pitches = None
+        if any(t is not None for t in tracks):
+            self.pitches = [Pitch(u[3], len(u[0]), t) if t is not None else None for t, u in zip(tracks, utterances)]
+            self.pitch = (PitchC * len(utterances))(*[p.struct if p is not None else PitchC() for p in self.pitches])
         if isinstance(return_contour, (list, tuple)):
             if len(return_contour) != len(utterances):
                 raise ValueError(f"return_contour has {len(return_contour)} entries, the batch has {len(utterances)} utterances")
@@ -917,6 +1036,15 @@ class BatchCall:
         self.ekeep[i] = e
         self.envelope[i] = e.struct if e is not None else EnvelopeC()
 
+    def set_pitch(self, i: int, return_pitch):
+        """utterance i's pitch request (False / None: none) for the following run() / begin() (the call must have been built with
+        return_pitch=); .pitches[i] is replaced"""
+        if self.pitch is None:
+            raise ValueError("this BatchCall was built without a pitch track")
+        t = _check_pitch(False if return_pitch is None else return_pitch, f"utterance {i}: ")
+        self.pitches[i] = Pitch(int(self.Ts[i]), int(self.Ns[i]), t) if t is not None else None
+        self.pitch[i] = self.pitches[i].struct if t is not None else PitchC()
+
     def set_prosody(self, i: int, prosody):
         """utterance i's controls for the following run() / begin() (the call must have been built with controls)"""
         if self.prosody is None:
@@ -927,14 +1055,14 @@ class BatchCall:
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope, self.contour))
+                             self.volume, self.levels, self.envelope, self.contour, self.pitch))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope, self.contour))
+                             self.volume, self.levels, self.envelope, self.contour, self.pitch))
 
     def end(self, lane: int):
         m = self.model

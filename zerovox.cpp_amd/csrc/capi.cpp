@@ -169,7 +169,17 @@ struct Request
     const zv_envelope         *envelope = nullptr;
     // level contour (zv_*_contour): [count] or null; each struct's tables are [T[u]] and [n[u]] or null
     const zv_contour          *contour = nullptr;
+    // pitch track (zv_*_pitch): [count] or null; each struct's tables are [T[u]] and [n[u]] or null, its parameters 0 = default
+    const zv_pitch            *pitch = nullptr;
 
+    // any utterance that asks for a table of its pitch track: then every row of both tables is written on the device (an utterance
+    // that asks for none is metered at the cheapest parameters), and the host downloads the tables that were asked for
+    bool pitches() const
+    {
+        for (uint32_t u = 0; pitch && u < count; u++)
+            if (pitch[u].frames || pitch[u].phonemes) return true;
+        return false;
+    }
     // any utterance that asks for a table of its contour: then every row of both tables is written on the device, and the host
     // downloads the tables that were asked for
     bool contours() const
@@ -226,6 +236,7 @@ struct Request
         if (levels) s.levels += a;
         if (envelope) s.envelope += a;
         if (contour) s.contour += a;
+        if (pitch) s.pitch += a;
         return s;
     }
 };
@@ -267,6 +278,40 @@ static void pack_volume(const Request &r, float *vol)
 }
 static_assert(sizeof(zv_level) == sizeof(zv::LevelRow) && sizeof(zv_level) == 16, "zv_level is the kernels' LevelRow");
 static_assert(sizeof(zv_frame_level) == sizeof(zv::ContourRow) && sizeof(zv_frame_level) == 8, "zv_frame_level is the kernels' ContourRow");
+
+static_assert(sizeof(zv_pitch_frame) == sizeof(zv::PitchFrameRow) && sizeof(zv_pitch_frame) == 8, "zv_pitch_frame is the kernels' PitchFrameRow");
+static_assert(sizeof(zv_pitch_phoneme) == sizeof(zv::PitchPhonemeRow) && sizeof(zv_pitch_phoneme) == 8, "zv_pitch_phoneme is the kernels' PitchPhonemeRow");
+
+// a zv_pitch's parameters with their defaults filled in (pitch.h pitch_params_resolve), or ZV_ERR_ARG naming the field
+static zv::PitchParams resolve_pitch(const Model &M, const zv_pitch &p)
+{
+    zv::PitchParams q = {p.min_lag, p.max_lag, p.window, p.voiced_threshold};
+    bool defaulted = false;
+    if (const char *field = zv::pitch_params_resolve(M.hp.audio_sampling_rate, M.hp.audio_hop_size, q, &defaulted))
+    {
+        const double v = !strcmp(field, "min_lag") ? q.min_lag : !strcmp(field, "max_lag") ? q.max_lag : !strcmp(field, "window") ? q.window
+                                                                                                         : (double)q.voiced_threshold;
+        zv::fail(ZV_ERR_ARG, "pitch %s = %g breaks 8 <= min_lag < max_lag <= 512, max_lag <= 8 * min_lag, 64 <= window <= 1024, 0 < voiced_threshold <= 1%s",
+                 field, v, defaulted ? " (the default at this checkpoint's rate and hop: it needs explicit lags and window)" : "");
+    }
+    return q;
+}
+
+// a request's pitch parameters in the kernels' layout (pitch.h PITCH_PARAM_STRIDE), resolved; an utterance that asks for no table
+// gets the cheapest valid row (its rows are written and never downloaded)
+static void pack_pitch(const Model &M, const Request &r, uint32_t *par)
+{
+    for (uint32_t u = 0; u < r.count; u++)
+    {
+        zv::PitchParams q = {zv::PITCH_LAG_LO, zv::PITCH_LAG_LO + 1, zv::PITCH_WINDOW_LO, 0.5f};
+        if (r.pitch[u].frames || r.pitch[u].phonemes) q = resolve_pitch(M, r.pitch[u]);
+        uint32_t *c = par + (size_t)u * zv::PITCH_PARAM_STRIDE;
+        c[0] = q.min_lag;
+        c[1] = q.max_lag;
+        c[2] = q.window;
+        c[3] = zv::level_bits(q.voiced_threshold);
+    }
+}
 
 static void check_envelope(const zv_envelope &e, uint32_t n)
 {
@@ -344,6 +389,7 @@ static void check_request(zv_model *m, const Request &r)
             if (r.phonemes) check_phoneme_controls(M, r.phonemes[u], r.n[u]);
             if (r.volume) check_volume(r.volume[u]);
             if (r.envelope) check_envelope(r.envelope[u], r.n[u]);
+            if (r.pitch && (r.pitch[u].frames || r.pitch[u].phonemes)) resolve_pitch(M, r.pitch[u]);
             if (r.target_frames && r.target_frames[u] > r.T[u])
                 zv::fail(ZV_ERR_ARG, "target_frames = %u exceeds the capacity T = %u", r.target_frames[u], r.T[u]);
             if (tg && r.n[u] > (uint32_t)zv::FIT_MAX_TOKENS)      // one launch covers the request's utterances, with or without a target
@@ -427,7 +473,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const bool tg = r.targets(), pc = r.phoneme_controls() || tg, dur = r.timings();
         const size_t E = M.E(), b_ids = (size_t)n * 4, b_hid = (size_t)T * E * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
         const size_t b_ctl = r.prosody || tg ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
-        const bool vol = r.volumes() && !taps, env = r.envelopes() && !taps, ctr = r.contours() && !taps;
+        const bool vol = r.volumes() && !taps, env = r.envelopes() && !taps, ctr = r.contours() && !taps, pit = r.pitches() && !taps;
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
         // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
@@ -436,7 +482,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const size_t o_nf = L.at(4), o_ids = L.at(b_ids), o_pun = L.at(b_ids), o_sty = L.at(E * 4), o_ctl = L.at(b_ctl),
                      o_pctl = L.at(b_pctl), o_hid = L.at(b_hid);
         const size_t o_mel = taps ? 0 : L.at((size_t)T * M.hp.audio_num_mels * 4), o_wav = taps ? 0 : L.at(b_wav),
-                     o_cum = taps ? 0 : L.at(dur || env || ctr ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
+                     o_cum = taps ? 0 : L.at(dur || env || ctr || pit ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
                      o_runs = L.at(!r.fitted && !taps ? sizeof(zv::Seg) : 0);
         // [volume row][level row] (volume controls: the row uploaded, the level written on the device)
         const size_t o_vol = L.at(vol ? zv::LEVEL_VOL_STRIDE * 4 : 0), o_lvl = L.at(vol ? sizeof(zv::LevelRow) : 0);
@@ -445,6 +491,9 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         // [frame rows][phoneme rows] (level contour: both written on the device; the last regions, so no other offset moves)
         const size_t b_cfr = (size_t)T * sizeof(zv::ContourRow), b_cph = (size_t)n * sizeof(zv::ContourRow);
         const size_t o_cfr = L.at(ctr ? b_cfr : 0), o_cph = L.at(ctr ? b_cph : 0);
+        // [frame rows][phoneme rows][parameter row] (pitch track: the rows written on the device, the parameters uploaded; behind the contour's)
+        const size_t b_pfr = (size_t)T * sizeof(zv::PitchFrameRow), b_pph = (size_t)n * sizeof(zv::PitchPhonemeRow);
+        const size_t o_pfr = L.at(pit ? b_pfr : 0), o_pph = L.at(pit ? b_pph : 0), o_ppar = L.at(pit ? zv::PITCH_PARAM_STRIDE * 4 : 0);
         char *io = (char *)M.io_scratch(L.size());
         int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
@@ -489,6 +538,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
             ZV_HIP(hipMemcpyAsync(io + o_eg, egain.data(), b_ids, hipMemcpyHostToDevice, M.stream()));
             ZV_HIP(hipMemcpyAsync(io + o_env, erow, sizeof(erow), hipMemcpyHostToDevice, M.stream()));
         }
+        uint32_t prow[zv::PITCH_PARAM_STRIDE];                       // host staging, like ctl
         int32_t nf = 0;
         if (taps)
         {
@@ -507,11 +557,19 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         {
             float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
             // an envelope's knots pass and a contour's phonemes pass read the scan behind the vocoder
-            if (dur || env || ctr) bt.d_cum = (int32_t *)(io + o_cum);
+            if (dur || env || ctr || pit) bt.d_cum = (int32_t *)(io + o_cum);
             if (ctr)
             {
                 bt.d_ctr_frames = (zv::ContourRow *)(io + o_cfr);
                 bt.d_ctr_phonemes = (zv::ContourRow *)(io + o_cph);
+            }
+            if (pit)
+            {
+                pack_pitch(M, r, prow);
+                bt.d_pit_frames = (zv::PitchFrameRow *)(io + o_pfr);
+                bt.d_pit_phonemes = (zv::PitchPhonemeRow *)(io + o_pph);
+                bt.d_pit_par = (const uint32_t *)(io + o_ppar);
+                ZV_HIP(hipMemcpyAsync(io + o_ppar, prow, sizeof(prow), hipMemcpyHostToDevice, M.stream()));
             }
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
             ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream()));
@@ -521,6 +579,8 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
             // the contour's tables go straight to the caller, like the waveform: the ones asked for
             if (ctr && r.contour[0].frames) ZV_HIP(hipMemcpyAsync(r.contour[0].frames, io + o_cfr, b_cfr, hipMemcpyDeviceToHost, M.stream()));
             if (ctr && r.contour[0].phonemes) ZV_HIP(hipMemcpyAsync(r.contour[0].phonemes, io + o_cph, b_cph, hipMemcpyDeviceToHost, M.stream()));
+            if (pit && r.pitch[0].frames) ZV_HIP(hipMemcpyAsync(r.pitch[0].frames, io + o_pfr, b_pfr, hipMemcpyDeviceToHost, M.stream()));
+            if (pit && r.pitch[0].phonemes) ZV_HIP(hipMemcpyAsync(r.pitch[0].phonemes, io + o_pph, b_pph, hipMemcpyDeviceToHost, M.stream()));
         }
         M.sync();
         if (vol && r.levels) r.levels[0] = level;
@@ -738,6 +798,10 @@ struct PendingBatch
     std::vector<size_t>   noff;
     std::vector<zv_contour> contour;
     const zv_frame_level *h_cfr = nullptr, *h_cph = nullptr;
+    // pitch track (zv_synthesize_batch_begin_pitch): likewise, h_pfr packed like the waveforms and h_pph like the tokens
+    std::vector<zv_pitch> pitch;
+    const zv_pitch_frame   *h_pfr = nullptr;
+    const zv_pitch_phoneme *h_pph = nullptr;
 };
 static PendingBatch &pending_slot(zv_model *m, int lane)
 {
@@ -773,7 +837,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
     const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings(), vol = r.volumes(),
-               env = r.envelopes(), ctr = r.contours();
+               env = r.envelopes(), ctr = r.contours(), pit = r.pitches();
     uint32_t nmax = 0, tmax = 0, ntot = 0;
     for (uint32_t u = 0; u < r.count; u++)
     {
@@ -801,17 +865,20 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
                  i_vol = in.at(vol ? (size_t)bt.nseg * zv::LEVEL_VOL_STRIDE * 4 : 0),      // volume rows: only with volume controls, like the control rows
                  i_eg = in.at(env ? bt.n_rows * 4 : 0),                                    // envelope: a gain per token row and a row per utterance, likewise
                  i_env = in.at(env ? (size_t)bt.nseg * zv::ENV_CTL_STRIDE * 4 : 0),
+                 i_ppar = in.at(pit ? (size_t)bt.nseg * zv::PITCH_PARAM_STRIDE * 4 : 0),      // pitch track: a parameter row per utterance, likewise
                  b_in = in.size();
     // device block: [frame counts][input block][hidden][mel][wav][scan] (scan: only when timings are asked for, the length
     // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
     Layout dev;
     const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
-                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || env || ctr ? bt.n_rows * 4 : 0),
+                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || env || ctr || pit ? bt.n_rows * 4 : 0),
                  o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0),      // fitted: the live frame table, written on the device
                  o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0),     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
                  o_lvl = dev.at(vol ? (size_t)bt.nseg * sizeof(zv::LevelRow) : 0),             // volume controls: the level rows, written on the device
                  o_cfr = dev.at(ctr ? bt.t_rows * sizeof(zv::ContourRow) : 0),                 // level contour: the frame rows and the phoneme rows, next to them,
-                 o_cph = dev.at(ctr ? bt.n_rows * sizeof(zv::ContourRow) : 0);                 // by absolute frame row / token row, written on the device
+                 o_cph = dev.at(ctr ? bt.n_rows * sizeof(zv::ContourRow) : 0),                 // by absolute frame row / token row, written on the device
+                 o_pfr = dev.at(pit ? bt.t_rows * sizeof(zv::PitchFrameRow) : 0),              // pitch track: the same two tables
+                 o_pph = dev.at(pit ? bt.n_rows * sizeof(zv::PitchPhonemeRow) : 0);
     M.reserve_batch(bt);
     char *io = (char *)M.io_scratch(dev.size());
     // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan][level rows][contour frame rows]
@@ -819,7 +886,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     size_t wav_bytes = 0;
     pb.woff.assign(r.count, 0);
     pb.noff.assign(r.count + 1, 0);
-    bool ctr_f = false, ctr_p = false;
+    bool ctr_f = false, ctr_p = false, pit_f = false, pit_p = false;
     for (uint32_t u = 0; u < r.count; u++)
     {
         pb.woff[u] = wav_bytes;
@@ -827,12 +894,15 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         pb.noff[u + 1] = pb.noff[u] + r.n[u];
         ctr_f = ctr_f || (ctr && r.contour[u].frames);
         ctr_p = ctr_p || (ctr && r.contour[u].phonemes);
+        pit_f = pit_f || (pit && r.pitch[u].frames);
+        pit_p = pit_p || (pit && r.pitch[u].phonemes);
     }
     const size_t frame_rows = wav_bytes / (hop * 4);
     Layout host;
     const size_t p_in = host.at(b_in), p_nf = host.at((size_t)bt.nseg * 4), p_wav = host.at(wav_bytes),
                  p_cum = host.at(dur ? bt.n_rows * 4 : 0), p_lvl = host.at(vol ? (size_t)bt.nseg * sizeof(zv_level) : 0),
-                 p_cfr = host.at(ctr_f ? frame_rows * sizeof(zv_frame_level) : 0), p_cph = host.at(ctr_p ? (size_t)ntot * sizeof(zv_frame_level) : 0);
+                 p_cfr = host.at(ctr_f ? frame_rows * sizeof(zv_frame_level) : 0), p_cph = host.at(ctr_p ? (size_t)ntot * sizeof(zv_frame_level) : 0),
+                 p_pfr = host.at(pit_f ? frame_rows * sizeof(zv_pitch_frame) : 0), p_pph = host.at(pit_p ? (size_t)ntot * sizeof(zv_pitch_phoneme) : 0);
     char *pin = (char *)M.pinned_scratch(host.size());
     char *d_in = io + o_in, *h_in = pin + p_in;
     {
@@ -856,6 +926,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         pack_controls(r, (float *)(h_in + i_ctl), (float *)(h_in + i_pctl));      // (phoneme rows past the utterances are never read)
         if (vol) pack_volume(r, (float *)(h_in + i_vol));
         if (env) pack_envelope(r, (float *)(h_in + i_eg), (int32_t *)(h_in + i_env));      // (gain rows past the utterances are never read)
+        if (pit) pack_pitch(M, r, (uint32_t *)(h_in + i_ppar));
     }
     bt.d_tok = (const zv::Seg *)(d_in + i_tok);
     bt.d_frm = (const zv::Seg *)(d_in + i_frm);
@@ -863,11 +934,17 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     bt.has_targets = tg;
     if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
     // an envelope's knots pass and a contour's phonemes pass read the scan behind the vocoder
-    if (dur || env || ctr) bt.d_cum = (int32_t *)(io + o_cum);
+    if (dur || env || ctr || pit) bt.d_cum = (int32_t *)(io + o_cum);
     if (ctr)
     {
         bt.d_ctr_frames = (zv::ContourRow *)(io + o_cfr);
         bt.d_ctr_phonemes = (zv::ContourRow *)(io + o_cph);
+    }
+    if (pit)
+    {
+        bt.d_pit_frames = (zv::PitchFrameRow *)(io + o_pfr);
+        bt.d_pit_phonemes = (zv::PitchPhonemeRow *)(io + o_pph);
+        bt.d_pit_par = (const uint32_t *)(d_in + i_ppar);
     }
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
     if (M.dec_plan(bt).runs) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
@@ -889,7 +966,9 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     char *h_wav = pin + p_wav;
     zv_level *h_lvl = vol ? (zv_level *)(pin + p_lvl) : nullptr;
     zv_frame_level *h_cfr = ctr_f ? (zv_frame_level *)(pin + p_cfr) : nullptr, *h_cph = ctr_p ? (zv_frame_level *)(pin + p_cph) : nullptr;
-    // the contour rows of utterances [u0, u1) travel behind their waveforms on stream `st`: frame rows packed like the waveforms
+    zv_pitch_frame *h_pfr = pit_f ? (zv_pitch_frame *)(pin + p_pfr) : nullptr;
+    zv_pitch_phoneme *h_pph = pit_p ? (zv_pitch_phoneme *)(pin + p_pph) : nullptr;
+    // the contour rows and the pitch rows of utterances [u0, u1) travel behind their waveforms on stream `st`: frame rows packed like the waveforms
     // (a frame row per hop samples), phoneme rows like the tokens
     auto contour_download = [&](uint32_t u0, uint32_t u1, hipStream_t st) {
         const size_t f0 = pb.woff[u0] / (hop * 4), f1 = u1 < r.count ? pb.woff[u1] / (hop * 4) : frame_rows;
@@ -898,6 +977,10 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
             ZV_HIP(hipMemcpyAsync(h_cfr + f0, bt.d_ctr_frames + f0, (f1 - f0) * sizeof(zv_frame_level), hipMemcpyDeviceToHost, st));
         if (h_cph && n1 > n0)
             ZV_HIP(hipMemcpyAsync(h_cph + n0, bt.d_ctr_phonemes + n0, (n1 - n0) * sizeof(zv_frame_level), hipMemcpyDeviceToHost, st));
+        if (h_pfr && f1 > f0)
+            ZV_HIP(hipMemcpyAsync(h_pfr + f0, bt.d_pit_frames + f0, (f1 - f0) * sizeof(zv_pitch_frame), hipMemcpyDeviceToHost, st));
+        if (h_pph && n1 > n0)
+            ZV_HIP(hipMemcpyAsync(h_pph + n0, bt.d_pit_phonemes + n0, (n1 - n0) * sizeof(zv_pitch_phoneme), hipMemcpyDeviceToHost, st));
     };
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
@@ -977,6 +1060,10 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     pb.h_cph = h_cph;
     if (ctr) pb.contour.assign(r.contour, r.contour + r.count);      // the struct array is read here, the tables are written in batch_finish
     else pb.contour.clear();
+    pb.h_pfr = h_pfr;
+    pb.h_pph = h_pph;
+    if (pit) pb.pitch.assign(r.pitch, r.pitch + r.count);
+    else pb.pitch.clear();
     pb.N.assign(r.n, r.n + r.count);
     if (dur) pb.dur.assign(r.durations, r.durations + r.count);
     else pb.dur.clear();
@@ -1015,6 +1102,12 @@ static void batch_finish(zv_model *m, int lane)
         const zv_contour &c = pb.contour[u];
         if (c.frames) memcpy(c.frames, pb.h_cfr + pb.woff[u] / (pb.hop * 4), (size_t)pb.T[u] * sizeof(zv_frame_level));
         if (c.phonemes) memcpy(c.phonemes, pb.h_cph + pb.noff[u], (size_t)pb.N[u] * sizeof(zv_frame_level));
+    }
+    for (uint32_t u = 0; u < pb.n_utt && !pb.pitch.empty(); u++)
+    {
+        const zv_pitch &c = pb.pitch[u];
+        if (c.frames) memcpy(c.frames, pb.h_pfr + pb.woff[u] / (pb.hop * 4), (size_t)pb.T[u] * sizeof(zv_pitch_frame));
+        if (c.phonemes) memcpy(c.phonemes, pb.h_pph + pb.noff[u], (size_t)pb.N[u] * sizeof(zv_pitch_phoneme));
     }
 }
 
@@ -1263,6 +1356,72 @@ zv_status zv_synthesize_batch_begin_contour(zv_model *m, uint32_t lane, uint32_t
 {
     return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
                                  durations, fitted != 0, target_frames, volume, levels, envelope, contour});
+}
+
+// The pitch forms: the _contour requests plus the pitch tracks (NULL, or no table asked for: the request of the _contour call).
+zv_status zv_synthesize_pitch(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                              float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                              int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                              const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch)
+{
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody, phonemes, &durations, fitted != 0,
+                          &target_frames, volume, levels, envelope, contour, pitch});
+}
+
+zv_status zv_synthesize_batch_pitch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                    const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                    uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                    int32_t *const *durations, const uint32_t *target_frames, int fitted, const zv_volume *volume,
+                                    zv_level *levels, const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch)
+{
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                durations, fitted != 0, target_frames, volume, levels, envelope, contour, pitch});
+}
+
+zv_status zv_synthesize_batch_begin_pitch(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                          const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                          const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                          const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                          const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                          const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                 durations, fitted != 0, target_frames, volume, levels, envelope, contour, pitch});
+}
+
+// The stand-alone meter: a host waveform through the frames pass, eagerly, on lane 0, as one inline segment.
+zv_status zv_pitch_track(zv_model *m, const float *wav, uint32_t T, const zv_pitch *pitch)
+{
+    return guarded([&] {
+        if (!(m && wav && pitch)) zv::fail(ZV_ERR_ARG, "zv_pitch_track: null argument");
+        if (!pitch->frames) zv::fail(ZV_ERR_ARG, "zv_pitch_track: pitch->frames is required");
+        if (pitch->phonemes) zv::fail(ZV_ERR_ARG, "zv_pitch_track: pitch->phonemes must be NULL (a waveform has no phoneme timings)");
+        Model &M = *m->m;
+        zv::PitchParams q;
+        try
+        {
+            check_T(M, T);
+            q = resolve_pitch(M, *pitch);
+        }
+        catch (const zv::Error &e)
+        {
+            zv::fail(e.status, "zv_pitch_track: %s", e.what());
+        }
+        use_lane0(m);
+        const size_t hop = M.hp.audio_hop_size, b_wav = (size_t)T * hop * 4, b_rows = (size_t)T * sizeof(zv::PitchFrameRow);
+        Layout L;
+        const size_t o_wav = L.at(b_wav), o_rows = L.at(b_rows), o_slab = L.at((size_t)T * sizeof(zv::PitchSlabRow)),
+                     o_par = L.at(zv::PITCH_PARAM_STRIDE * 4);
+        char *io = (char *)M.io_scratch(L.size());
+        const uint32_t prow[zv::PITCH_PARAM_STRIDE] = {q.min_lag, q.max_lag, q.window, zv::level_bits(q.voiced_threshold)};
+        ZV_HIP(hipMemcpyAsync(io + o_wav, wav, b_wav, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_par, prow, sizeof(prow), hipMemcpyHostToDevice, M.stream()));
+        const zv::Segs one{nullptr, 1, (int)T, zv::Seg{0, (int32_t)T, 0, 0}};
+        ZV_HIP(zv::launch_pitch_frames(M.stream(), (const float *)(io + o_wav), io + o_slab, (zv::PitchFrameRow *)(io + o_rows),
+                                       (const uint32_t *)(io + o_par), one, (int)hop, (int)M.hp.audio_sampling_rate));
+        ZV_HIP(hipMemcpyAsync(pitch->frames, io + o_rows, b_rows, hipMemcpyDeviceToHost, M.stream()));
+        M.sync();
+    });
 }
 
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)

@@ -16,6 +16,7 @@
 #include "level.h"        // volume controls: LEVEL_CHUNK_SAMPLES, LEVEL_VOL_STRIDE, LevelRow
 #include "envelope.h"     // amplitude envelope: ENV_CTL_STRIDE, ENV_MAX_RAMP, ENV_MAX_GAIN
 #include "contour.h"      // level contour: CONTOUR_CHUNK_FRAMES, ContourRow
+#include "pitch.h"        // pitch track: PITCH_CHUNK_FRAMES, PITCH_PARAM_STRIDE, the rows
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -443,5 +444,18 @@ bool       contour_hop_supported(int hop);
 hipError_t launch_contour_frames(hipStream_t s, const float *wav, void *slab, ContourRow *rows, const Segs &frames, int hop);
 hipError_t launch_contour_phonemes(hipStream_t s, const int32_t *cum, const void *slab, ContourRow *rows, const Segs &tokens,
                                    const Segs &frames, int hop);
+
+// ---- pitch track (include/zerovox_amd.h "pitch track", pitch.h): two passes behind the level contour's, over the waveform the caller
+// receives.  `frames` is the CAPACITY table or inline segment, `tokens` the token table; both passes index by ABSOLUTE row.
+//   frames:   slab[frames[u].row0 + f] = {Fq, voiced} for every frame f of every segment's capacity, 8 bytes each, and, where rows is
+//             not null, rows[frames[u].row0 + f] = {f0_hz, strength}.  par [segments][PITCH_PARAM_STRIDE]: each segment's resolved
+//             parameters (pitch_params_resolve), read at run time; a row outside the rule's bounds makes its segment's waves return
+//             without a store.  A span never leaves its segment's own samples [row0 * hop, (row0 + rows) * hop).
+//   phonemes: rows[tokens[u].row0 + i] = {mean f0 of the voiced frames, their share} of phoneme i, for every token row of every segment;
+//             its frames come from cum, the length regulator's scan, clipped to the capacity (contour_extent)
+// slab and rows: 8-byte aligned.  No atomics, nothing to zero: phonemes reads only what frames has stored in the same run.
+hipError_t launch_pitch_frames(hipStream_t s, const float *wav, void *slab, PitchFrameRow *rows, const uint32_t *par, const Segs &frames, int hop,
+                               int sr);
+hipError_t launch_pitch_phonemes(hipStream_t s, const int32_t *cum, const void *slab, PitchPhonemeRow *rows, const Segs &tokens, const Segs &frames);
 
 }  // namespace zv

@@ -8,4 +8,5 @@
 #include "level_kernels.hip"          // level meter
 #include "envelope_kernels.hip"       // amplitude envelope
 #include "contour_kernels.hip"        // level contour
+#include "pitch_kernels.hip"          // pitch track
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

@@ -110,6 +110,13 @@ struct Batch
     // behind the volume passes.  WHICH rows a caller receives is the host's business at download time: every row is written.
     ContourRow *d_ctr_frames = nullptr;
     ContourRow *d_ctr_phonemes = nullptr;
+    // Pitch track (include/zerovox_amd.h "pitch track", pitch.h), all three set or none: the frame rows, PitchFrameRow [t_rows], the
+    // phoneme rows, PitchPhonemeRow [n_rows], both in HBM outside the arena and indexed by absolute frame row / token row, and the
+    // parameter rows, uint32 [nseg][PITCH_PARAM_STRIDE], resolved on the host and uploaded with the call: the VALUES are read at run
+    // time.  With them d_cum is set.  Keyed like the contour: the vocoder ends in two launches more, behind the contour's.
+    PitchFrameRow   *d_pit_frames = nullptr;
+    PitchPhonemeRow *d_pit_phonemes = nullptr;
+    const uint32_t  *d_pit_par = nullptr;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -139,7 +146,8 @@ struct Batch
                d_frm == o.d_frm && (d_tok || memcmp(&tok1, &o.tok1, sizeof(Seg)) == 0) && (d_frm || memcmp(&frm1, &o.frm1, sizeof(Seg)) == 0) &&
                d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live && has_targets == o.has_targets &&
                d_dec_runs == o.d_dec_runs && d_vol == o.d_vol && d_levels == o.d_levels && d_nframes == o.d_nframes && d_env_gain == o.d_env_gain &&
-               d_env == o.d_env && d_ctr_frames == o.d_ctr_frames && d_ctr_phonemes == o.d_ctr_phonemes;
+               d_env == o.d_env && d_ctr_frames == o.d_ctr_frames && d_ctr_phonemes == o.d_ctr_phonemes &&
+               d_pit_frames == o.d_pit_frames && d_pit_phonemes == o.d_pit_phonemes && d_pit_par == o.d_pit_par;
     }
 };
 
@@ -372,6 +380,8 @@ class Model
         // level contour (kernels.h launch_contour_frames): the frames' totals, 16 bytes per frame row, t_rows entries, carved in front
         // of the run table like the slab
         void *contour_slab;
+        // pitch track (kernels.h launch_pitch_frames): {Fq, voiced} per frame row, 8 bytes each, t_rows entries, carved likewise
+        void *pitch_slab;
         float *mel_c; int32_t *eq; Seg *runs;
     };
     // entries of VocLayout::level_slab: >= nseg * level_chunks(t_max, hop) for every Batch with nseg * t_max <= t_rows, a sub-batch included

@@ -73,6 +73,7 @@ Model::VocLayout Model::voc_layout(DeviceArena &a, const Batch &bt) const
     v.level_slab = a.take(level_slab_entries(bt) * 16);
     v.env_knots = a.take_n<uint32_t>(env_knot_entries(bt));
     v.contour_slab = a.take(bt.t_rows * 16);
+    v.pitch_slab = a.take(bt.t_rows * sizeof(PitchSlabRow));
     v.runs = a.take_n<Seg>(bt.nseg);
     return v;
 }
@@ -112,6 +113,7 @@ void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g
         sub.d_levels = bt.d_levels + g0;
     }
     if (bt.d_nframes) sub.d_nframes = bt.d_nframes + g0;
+    if (bt.d_pit_par) sub.d_pit_par = bt.d_pit_par + (size_t)g0 * PITCH_PARAM_STRIDE;      // (the rows go by absolute frame / token row)
     if (bt.d_env) sub.d_env = bt.d_env + (size_t)g0 * ENV_CTL_STRIDE;          // (the gains and the scan go by absolute token row)
     sub.nseg = cnt;
     vocode_group(sub, d_mel, d_wav, 2, g0);
@@ -515,6 +517,25 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
                   launch_contour_frames(stream(), d_wav, lay.contour_slab, bt.d_ctr_frames, cap, rate));
         ZV_LAUNCH("voc_contour_phonemes", 16.0 * cap_rows + 8.0 * tok_rows, 0.0,
                   launch_contour_phonemes(stream(), bt.d_cum, lay.contour_slab, bt.d_ctr_phonemes, tk, cap, rate));
+    }
+
+    // Pitch track (pitch.h): behind everything that changes the waveform, like the contour and with its indexing — per tail group,
+    // ahead of the group's download.  Only where the call carries a pitch request; never under a one-layer tap.
+    if (bt.d_pit_frames && dbg_layer.kind < 0)
+    {
+        if (!bt.d_cum || !bt.d_pit_phonemes || !bt.d_pit_par) fail(ZV_ERR_DEVICE, "internal: a pitch track without the scan, the phoneme rows or the parameters");
+        const Segs cap = bt.frames_cap();
+        const Segs tk{bt.d_tok ? bt.d_tok + seg0 : nullptr, bt.nseg, bt.n_max, bt.tok1};
+        const double cap_rows = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg);
+        const double tok_rows = std::min((double)bt.n_rows, (double)bt.n_max * bt.nseg);
+        // algorithmic bytes: the capacity's samples read once, a slab entry and a row written per frame; the slab read and a row written
+        // per token.  Operations, by capacity and at the DEFAULT parameters (the values are the device's: a caller's lags change the
+        // work, not this price): 2 per multiply-add, window x (max_lag - min_lag + 3) multiply-adds per frame.
+        const double macs = 2.0 * (double)rate * (double)(hp.audio_sampling_rate / 63 - hp.audio_sampling_rate / 441 + 3);
+        ZV_LAUNCH("voc_pitch_frames", 4.0 * cap_rows * rate + 16.0 * cap_rows, 2.0 * macs * cap_rows,
+                  launch_pitch_frames(stream(), d_wav, lay.pitch_slab, bt.d_pit_frames, bt.d_pit_par, cap, rate, (int)hp.audio_sampling_rate));
+        ZV_LAUNCH("voc_pitch_phonemes", 8.0 * cap_rows + 8.0 * tok_rows, 0.0,
+                  launch_pitch_phonemes(stream(), bt.d_cum, lay.pitch_slab, bt.d_pit_phonemes, tk, cap));
     }
 }
 

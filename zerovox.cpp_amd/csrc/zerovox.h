@@ -142,6 +142,13 @@ class ZeroVOXModel
     void set_contour(bool frames, bool phonemes) { contour_frames = frames; contour_phonemes = phonemes; }
     const std::vector<zv_frame_level> &get_frame_levels() const { return frame_levels; }         // [max_seq_len], empty unless asked for
     const std::vector<zv_frame_level> &get_phoneme_levels() const { return phoneme_levels; }     // [num_phonemes], likewise
+    // pitch track (include/zerovox_amd.h "pitch track") for the eval() calls that follow: the fundamental frequency and voicing of
+    // every frame of the capacity and / or of every phoneme, metered on the device on the waveform get_wav() holds.  params: the lags,
+    // the window and the threshold (its table pointers are ignored; nullptr or zeros: the defaults); they are checked when eval() runs.
+    // A meter: nothing is scaled.  Works with everything above.
+    void set_pitch(bool frames, bool phonemes, const zv_pitch *params = nullptr);
+    const std::vector<zv_pitch_frame> &get_pitch_frames() const { return pitch_frame_rows; }         // [max_seq_len], empty unless asked for
+    const std::vector<zv_pitch_phoneme> &get_pitch_phonemes() const { return pitch_phoneme_rows; }   // [num_phonemes], likewise
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
@@ -176,6 +183,10 @@ class ZeroVOXModel
     bool                 has_envelope = false, env_gain_set = false;
     bool                 contour_frames = false, contour_phonemes = false;
     std::vector<zv_frame_level> frame_levels, phoneme_levels;
+    bool                 pitch_frames = false, pitch_phonemes = false;
+    zv_pitch             pitch_params = {nullptr, nullptr, 0, 0, 0, 0.0f};
+    std::vector<zv_pitch_frame>   pitch_frame_rows;
+    std::vector<zv_pitch_phoneme> pitch_phoneme_rows;
 };
 
 }  // namespace ZeroVOX

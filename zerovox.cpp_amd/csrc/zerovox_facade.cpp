@@ -164,6 +164,15 @@ void ZeroVOXModel::set_phoneme_controls(const zv_phoneme_controls *p, uint32_t n
     record_durations = true;
 }
 
+void ZeroVOXModel::set_pitch(bool frames, bool phonemes, const zv_pitch *params)
+{
+    pitch_frames = frames;
+    pitch_phonemes = phonemes;
+    pitch_params = params ? *params : zv_pitch{nullptr, nullptr, 0, 0, 0, 0.0f};
+    pitch_params.frames = nullptr;
+    pitch_params.phonemes = nullptr;
+}
+
 void ZeroVOXModel::set_envelope(const zv_envelope *e, uint32_t n)
 {
     has_envelope = e != nullptr;
@@ -182,7 +191,9 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
                                         std::to_string(num_phonemes));
     frame_levels.assign(contour_frames ? hparams.max_seq_len : 0, zv_frame_level{0.0f, 0.0f});
     phoneme_levels.assign(contour_phonemes ? num_phonemes : 0, zv_frame_level{0.0f, 0.0f});
-    if (has_volume || has_envelope || contour_frames || contour_phonemes)
+    pitch_frame_rows.assign(pitch_frames ? hparams.max_seq_len : 0, zv_pitch_frame{0.0f, 0.0f});
+    pitch_phoneme_rows.assign(pitch_phonemes ? num_phonemes : 0, zv_pitch_phoneme{0.0f, 0.0f});
+    if (has_volume || has_envelope || contour_frames || contour_phonemes || pitch_frames || pitch_phonemes)
     {
         // the volume, envelope and contour forms take what every other form takes (the finished waveform of the one-pass chain is scaled and measured)
         if (has_phonemes && pc_n != num_phonemes)
@@ -194,6 +205,16 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
         const zv_envelope env = {env_gain_set ? env_gain.data() : nullptr, envelope.ramp_frames, envelope.fade_in_samples,
                                  envelope.fade_out_samples};
         const zv_contour ctr = {contour_frames ? frame_levels.data() : nullptr, contour_phonemes ? phoneme_levels.data() : nullptr};
+        if (pitch_frames || pitch_phonemes)
+        {
+            zv_pitch pit = pitch_params;
+            pit.frames = pitch_frames ? pitch_frame_rows.data() : nullptr;
+            pit.phonemes = pitch_phonemes ? pitch_phoneme_rows.data() : nullptr;
+            chk(zv_synthesize_pitch(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
+                                    has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
+                                    has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr, &ctr, &pit));
+            return;
+        }
         chk(zv_synthesize_contour(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
                                   has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
                                   has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr, &ctr));

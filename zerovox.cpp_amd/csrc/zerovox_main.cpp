@@ -44,6 +44,14 @@
 //            also with --trim and --fit) / of every phoneme, metered on the device on the waveform that is written, as TSV: a header
 //            line, then index<TAB>rms<TAB>peak per row, linear re full scale, printed with %.9g (the f32 bits survive).  Work with
 //            everything above.  A missing file name is a usage error.
+//   --pitch FILE, --phoneme-pitch FILE, --pitch-min-hz F, --pitch-max-hz F, --pitch-threshold X
+//            pitch track (include/zerovox_amd.h "pitch track"): the fundamental frequency and the correlation strength of every frame of
+//            the capacity / the mean F0 of the voiced frames and their share for every phoneme, metered on the device on the waveform
+//            that is written, as TSV: a header line, then index<TAB>f0_hz<TAB>strength (frames) or index<TAB>f0_hz<TAB>voiced (phonemes)
+//            per row, printed with %.9g.  The range in Hz becomes lags on the host, min_lag = floor(rate / max-hz) and max_lag =
+//            floor(rate / min-hz) (defaults: the library's, 63 .. 441 Hz at 22 050 Hz); the threshold is the voicing threshold in
+//            (0, 1], default 0.5.  A frequency that is not positive and finite, or a parameter without a file, is a usage error; the
+//            library checks the lags.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
 #include <algorithm>
 #include <cmath>
@@ -69,6 +77,7 @@ static void usage(FILE *f)
                "               [--gain-db G] [--loudness-dbfs L] [--peak-dbfs P]\n"
                "               [--phoneme-gain-db FILE] [--ramp-frames R] [--fade-in-ms X] [--fade-out-ms X]\n"
                "               [--contour FILE] [--phoneme-levels FILE]\n"
+               "               [--pitch FILE] [--phoneme-pitch FILE] [--pitch-min-hz F] [--pitch-max-hz F] [--pitch-threshold X]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
@@ -91,7 +100,11 @@ static void usage(FILE *f)
                "  --fade-in-ms X       the speech rises linearly from 0 over floor(X * sampling rate / 1000 + 0.5) samples\n"
                "  --fade-out-ms X      the speech falls linearly to 0 over as many samples; what follows it is silence\n"
                "  --contour FILE       write the level of every frame of the written waveform's capacity as TSV: index rms peak\n"
-               "  --phoneme-levels FILE  write the level of every phoneme likewise\n",
+               "  --phoneme-levels FILE  write the level of every phoneme likewise\n"
+               "  --pitch FILE         write the fundamental frequency of every frame of the capacity as TSV: index f0_hz strength\n"
+               "  --phoneme-pitch FILE write every phoneme's mean F0 and share of voiced frames as TSV: index f0_hz voiced\n"
+               "  --pitch-min-hz F, --pitch-max-hz F  the range searched (default 63 .. 441 Hz at 22 050 Hz, three octaves at most)\n"
+               "  --pitch-threshold X  the correlation strength from which a frame counts as voiced, 0 < X <= 1, default 0.5\n",
             k_default_model, k_default_out);
 }
 
@@ -216,7 +229,9 @@ static std::vector<int32_t> utterance_ids(const std::string &utt_path)
 
 int main(int argc, char **argv)
 {
-    std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path, gain_path, contour_path, plevel_path;
+    std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path, gain_path, contour_path, plevel_path, pitch_path, ppitch_path;
+    double pitch_hz[2] = {0.0, 0.0}, pitch_thr = 0.0;      // --pitch-min-hz, --pitch-max-hz, --pitch-threshold (0: the default)
+    bool pitch_param = false;
     bool trim = false, fit = false, info = false, controlled = false, leveled = false, enveloped = false;
     long ramp_frames = 0;              // --ramp-frames
     double fade_ms[2] = {0.0, 0.0};    // --fade-in-ms, --fade-out-ms
@@ -238,6 +253,24 @@ int main(int argc, char **argv)
         else if (a == "--alignment") align_path = need("--alignment");
         else if (a == "--contour") contour_path = need("--contour");
         else if (a == "--phoneme-levels") plevel_path = need("--phoneme-levels");
+        else if (a == "--pitch") pitch_path = need("--pitch");
+        else if (a == "--phoneme-pitch") ppitch_path = need("--phoneme-pitch");
+        else if (a == "--pitch-min-hz" || a == "--pitch-max-hz" || a == "--pitch-threshold")
+        {
+            const std::string v = need(a.c_str());
+            char *end = nullptr;
+            const double x = strtod(v.c_str(), &end);
+            const bool thr = a == "--pitch-threshold";
+            if (v.empty() || end != v.c_str() + v.size() || !(x > 0.0 && x <= (thr ? 1.0 : 1e6)))
+            {
+                fprintf(stderr, "zerovox: %s needs a number in (0, %s], got '%s'\n", a.c_str(), thr ? "1" : "1000000", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+            if (thr) pitch_thr = x;
+            else pitch_hz[a == "--pitch-max-hz"] = x;
+            pitch_param = true;
+        }
         else if (a == "--target-frames")
         {
             const std::string v = need("--target-frames");
@@ -338,6 +371,12 @@ int main(int argc, char **argv)
         else if (a == "-h" || a == "--help") { usage(stdout); return 0; }
         else { fprintf(stderr, "zerovox: unknown argument '%s'\n", a.c_str()); usage(stderr); return 2; }
     }
+    if (pitch_param && pitch_path.empty() && ppitch_path.empty())
+    {
+        fprintf(stderr, "zerovox: --pitch-min-hz, --pitch-max-hz and --pitch-threshold need --pitch FILE or --phoneme-pitch FILE\n");
+        usage(stderr);
+        return 2;
+    }
 
     try
     {
@@ -383,6 +422,14 @@ int main(int argc, char **argv)
             model.set_envelope(&env, (uint32_t)gains.size());
         }
         if (!contour_path.empty() || !plevel_path.empty()) model.set_contour(!contour_path.empty(), !plevel_path.empty());
+        if (!pitch_path.empty() || !ppitch_path.empty())
+        {
+            // Hz to lags on the host: the shortest lag is the highest frequency's period, truncated
+            const double rate = hp.audio_sampling_rate;
+            const zv_pitch pit = {nullptr, nullptr, pitch_hz[1] > 0.0 ? (uint32_t)std::min(floor(rate / pitch_hz[1]), 4294967295.0) : 0u,
+                                  pitch_hz[0] > 0.0 ? (uint32_t)std::min(floor(rate / pitch_hz[0]), 4294967295.0) : 0u, 0u, (float)pitch_thr};
+            model.set_pitch(!pitch_path.empty(), !ppitch_path.empty(), &pit);
+        }
         if (target_seconds > 0.0)
             target_frames = (long)std::min(floor(target_seconds * hp.audio_sampling_rate / hp.audio_hop_size + 0.5), 1e9);
         if (target_frames > 0 || target_seconds > 0.0)
@@ -456,6 +503,20 @@ int main(int argc, char **argv)
         };
         if (!contour_path.empty()) write_levels(contour_path, model.get_frame_levels());
         if (!plevel_path.empty()) write_levels(plevel_path, model.get_phoneme_levels());
+        if (!pitch_path.empty() || !ppitch_path.empty())
+        {
+            auto write_pitch = [](const std::string &path, const char *last, size_t rows, const float *ab) {
+                FILE *cf = fopen(path.c_str(), "w");
+                if (!cf) throw std::runtime_error("cannot open '" + path + "' for writing");
+                fprintf(cf, "index\tf0_hz\t%s\n", last);
+                for (size_t i = 0; i < rows; i++) fprintf(cf, "%zu\t%.9g\t%.9g\n", i, (double)ab[2 * i], (double)ab[2 * i + 1]);
+                if (fclose(cf) != 0) throw std::runtime_error("short write to '" + path + "'");
+            };
+            static_assert(sizeof(zv_pitch_frame) == 8 && sizeof(zv_pitch_phoneme) == 8, "two floats per row");
+            if (!pitch_path.empty()) write_pitch(pitch_path, "strength", model.get_pitch_frames().size(), &model.get_pitch_frames().data()->f0_hz);
+            if (!ppitch_path.empty())
+                write_pitch(ppitch_path, "voiced", model.get_pitch_phonemes().size(), &model.get_pitch_phonemes().data()->f0_hz);
+        }
         if (trim || fit)
         {
             const size_t n = (size_t)nf * hp.audio_hop_size;
