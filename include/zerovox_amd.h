@@ -19,6 +19,8 @@
  *   *_contour          the same with the level and peak of every frame and every phoneme out (zv_contour)
  *   *_pitch            the same with the fundamental frequency and voicing of every frame and every phoneme out (zv_pitch)
  *   zv_pitch_track     the pitch track of any waveform the caller brings
+ *   *_bands            the same with the level per frequency band of every frame and every phoneme out (zv_bands)
+ *   zv_band_levels     the band levels of any waveform the caller brings
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file        src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -600,6 +602,87 @@ zv_status zv_synthesize_batch_begin_pitch(zv_model *m, uint32_t lane, uint32_t n
                                           const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
                                           const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch);
 zv_status zv_pitch_track(zv_model *m, const float *wav, uint32_t T, const zv_pitch *pitch);
+/* ---- band levels: per-frame and per-phoneme level per frequency band ----------------------------------------------------------------
+ * The read side of timbre: the level of the waveform in up to 64 frequency bands, per frame and per phoneme, from the same call and
+ * with no pass over the samples on the host (a spectrogram view, a viseme driver, a sibilance check, the one muffled phoneme of a
+ * batch).  The bands forms meter the finished waveform on the device, inside the same captured graph and — for a large batch — per
+ * tail group, ahead of that group's download and behind envelope, volume, contour and pitch track.  Band levels are a meter: they
+ * change no sample.  zv_band_levels meters any waveform the caller brings.
+ * The rule, per utterance, with hop = audio_hop_size, T the capacity, w[0 .. T*hop) the waveform the SAME call writes to wav (what
+ * the caller receives), durations[] and start_i as for the contour.  N = 1024; bins 0 .. 512 of the N-point DFT; bin k lies at
+ * k * sr / 1024 Hz.  n_bands = 0 takes 16; edges = NULL takes the default edges 1,3,5,8,12,17,24,33,45,62,84,114,155,210,285,387,513
+ * (roughly third-octave steps from 22 Hz to the Nyquist frequency at 22 050 Hz, without DC) and then needs n_bands 0 or 16.  Band b
+ * covers the bins edges[b] <= k < edges[b+1].  ZV_ERR_ARG before any work is enqueued when n_bands > 64, when the edges are not
+ * strictly ascending, when edges[n_bands] > 513, or when edges is NULL and n_bands is neither 0 nor 16; the message names the entry
+ * point, the utterance and the field.
+ *   tables   wnd(t) = 0.5 - 0.5*cos(2*pi*t/N); C[k][t] = (int)floor(126*wnd(t)*cos(2*pi*((k*t) mod N)/N) + 0.5), S[k][t] likewise with
+ *            sin, (k*t) mod N reduced in integers: 8-bit integers in [-126, 126].  At the scale 126 no product comes nearer than
+ *            1.27e-5 to a half-integer, so any libm gives the same table.  It is built on the host at the first request and uploaded
+ *            once (1 MiB of device memory per model, outside the lanes' arenas).
+ *   frame    for 0 <= f < T: s0 = f*hop + hop/2 - N/2 (signed); y[t] = w[s0 + t] for 0 <= t < N where 0 <= s0 + t < T*hop and the
+ *            sample is finite, else +0.0.  The span never reads another utterance's samples.
+ *   scale    Pk = the largest sign-cleared bit pattern in y.  Pk < 0x33800000 (a peak below 2^-24): the frame is silent, its row all
+ *            zeros.  Else e = (Pk >> 23) - 127, k = 12 - e, a[t] = sign(y[t]) * min((int64)((double)|y[t]| * 2^k + 0.5), 8191): the
+ *            pitch track's quantiser at 13 bits.
+ *   sums     Re(k) = sum over t of a[t]*C[k][t], Im(k) = sum over t of a[t]*S[k][t]: integers below 2^29 (the rows of |C| and |S| sum
+ *            to at most 64 512), so no order of summation can show.  P(k) = Re^2 + Im^2 (unsigned 64-bit, below 2^59), Q(k) =
+ *            P(k) >> 6, S_b = the sum of Q(k) over band b's bins (below 2^63).
+ *   row      pw_b = ((double)S_b / 48774928.0) * 2^(-2k); frames[f][b] = (float)sqrt(pw_b).  48 774 928 = 8 * the sum of
+ *            round(126*wnd(t))^2: a sinusoid of amplitude A inside a band reads A / sqrt(2), the measure of the level contour.
+ *            Kept for the phonemes: v = pw_b * 2^38 + 0.5, Eq[f][b] = v >= 2^47 ? 2^47 : (uint64)v (it saturates above an RMS of
+ *            about 22, so 32 768 frames sum below 2^62).
+ * For phoneme 0 <= i < n, d = durations[i], SE = the sum of Eq[f][b] over the frames start_i <= f < start_i + d:
+ * phonemes[i][b] = d > 0 ? (float)sqrt((double)SE / ((double)d * 274877906944.0)) : 0.
+ * Every f64 step is one IEEE operation (the library builds with -ffp-contract=off); csrc/bands.h holds the rule as plain C++ (host
+ * reference included).  What follows:
+ *   - fitted zeros give zero rows; an unfitted tail is measured like the speech;
+ *   - a frame near either end of the utterance sees zeros outside [0, T*hop).  That is part of the rule, not an error;
+ *   - bins 0 and 512 are counted like the others (their power is not halved); the default edges leave out DC;
+ *   - multiplying the waveform by a power of two scales every row by it exactly, as long as no sample becomes subnormal or
+ *     infinite, the span's peak stays at or above 2^-24 and the kept power stays below its ceiling;
+ *   - the dynamic range inside ONE frame is bounded by the 8-bit twiddles: a band far from a strong tone reads about 50 dB below it
+ *     at the least, whatever is there.  Across frames the block scaling keeps the full range of the samples;
+ *   - nothing depends on how frames, bins or samples are dealt over lanes and matrix instructions: integer sums throughout.
+ * bands == NULL, or every struct with both table pointers NULL: the request of the _pitch call, the same launches, the same graph,
+ * the same bits (n_bands and edges of such a struct are not looked at).  With band levels the waveform, n_frames, durations, levels,
+ * contour rows and pitch rows keep exactly their bits.  Batches: bands[n_utt] or NULL; an utterance may ask for one table, both or
+ * none, with its own n_bands and edges, and gives the rows of zv_synthesize_bands(..., &bands[u]).  n_bands and the edges travel in
+ * the batch's device input block like the other controls, so a replayed graph picks up new values.  The struct array and the edges
+ * are read before the call (_begin) returns; the tables must stay valid until the call (batches in flight: _end) returns.
+ * Arguments, limits and messages are otherwise those of the _pitch forms.  zv_synthesize_batch_begin_bands is finished by
+ * zv_synthesize_batch_end.
+ * zv_band_levels meters a host waveform wav[T * hop] at the model's rate and hop, eagerly, on lane 0: bands->frames is required,
+ * bands->phonemes must be NULL (there are no timings), 0 < T <= zv_max_frames(), else ZV_ERR_ARG; the rows are those of the rule
+ * with w = wav.
+ * Out of scope: zv_vocode*, zv_vocode_stream and the encode / decode entry points; a full 513-bin table (64 caller-chosen bands
+ * cover it); mel or triangular weighting, log compression, MFCCs; a second twiddle digit for more than about 50 dB of range; other
+ * window lengths; smoothing across frames; any spectral control (EQ, de-essing: the caller acts on the rows). */
+typedef struct
+{
+    float          *frames;    /* [T][n_bands] or NULL: one row per frame of the capacity */
+    float          *phonemes;  /* [n][n_bands] or NULL: one row per token                 */
+    uint32_t        n_bands;   /* 0 = default (16); else 1 .. 64                          */
+    const uint32_t *edges;     /* [n_bands + 1] DFT bins, or NULL = the default edges     */
+} zv_bands;                    /* zero-initialised = none */
+zv_status zv_synthesize_bands(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                              float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                              int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                              const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch, const zv_bands *bands);
+zv_status zv_synthesize_batch_bands(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                    const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                    float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                    const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                    const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                    const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch,
+                                    const zv_bands *bands);
+zv_status zv_synthesize_batch_begin_bands(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                          const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                          const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                          const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                          const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                          const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch,
+                                          const zv_bands *bands);
+zv_status zv_band_levels(zv_model *m, const float *wav, uint32_t T, const zv_bands *bands);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

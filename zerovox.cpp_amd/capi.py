@@ -29,6 +29,7 @@ SYMBOLS = [
     "zv_debug_mfma_chain", "zv_synthesize_envelope", "zv_synthesize_batch_envelope", "zv_synthesize_batch_begin_envelope",
     "zv_synthesize_contour", "zv_synthesize_batch_contour", "zv_synthesize_batch_begin_contour",
     "zv_synthesize_pitch", "zv_synthesize_batch_pitch", "zv_synthesize_batch_begin_pitch", "zv_pitch_track",
+    "zv_synthesize_bands", "zv_synthesize_batch_bands", "zv_synthesize_batch_begin_bands", "zv_band_levels",
 ]
 
 
@@ -247,6 +248,103 @@ def _check_pitch(return_pitch, where: str = ""):
             return PitchTrack(frames=return_pitch == "frames", phonemes=return_pitch == "phonemes")
         raise ValueError(f"{where}return_pitch = {return_pitch!r}: expected False, True, 'frames', 'phonemes' or a PitchTrack")
     raise TypeError(f"{where}return_pitch must be a bool, 'frames', 'phonemes' or a PitchTrack, not {type(return_pitch).__name__}")
+
+
+class BandsC(C.Structure):
+    """zv_bands of include/zerovox_amd.h: the two tables' pointers, float [T][n_bands] and [n][n_bands], each or NULL, the band count
+    (0 = 16) and the edges' pointer, uint32 [n_bands + 1] or NULL = the default edges (a zeroed struct asks for nothing)"""
+    _fields_ = [("frames", C.c_void_p), ("phonemes", C.c_void_p), ("n_bands", C.c_uint32), ("edges", C.c_void_p)]
+
+
+class BandLevels:
+    """What band levels are asked for (include/zerovox_amd.h "band levels"): the band count (0: the default, 16), the edges in DFT bins
+    of the 1 024-point transform (None: the default edges; else n_bands + 1 ascending bins, n_bands 0 then meaning len(edges) - 1) and
+    which tables.  The library checks the values.  from_hz converts edges in Hz at a sampling rate as the CLI does."""
+    N = 1024
+    DEFAULT_EDGES = (1, 3, 5, 8, 12, 17, 24, 33, 45, 62, 84, 114, 155, 210, 285, 387, 513)
+
+    def __init__(self, n_bands: int = 0, edges=None, frames: bool = True, phonemes: bool = True):
+        if isinstance(n_bands, (bool, np.bool_)) or not isinstance(n_bands, (int, np.integer)):
+            raise TypeError(f"BandLevels n_bands must be an integer, not {type(n_bands).__name__}")
+        if not 0 <= n_bands <= 0xffffffff:
+            raise ValueError(f"BandLevels n_bands = {n_bands} is outside [0, 4294967295]")
+        if not (isinstance(frames, (bool, np.bool_)) and isinstance(phonemes, (bool, np.bool_))):
+            raise TypeError("BandLevels frames and phonemes must be bools")
+        self.edges = None
+        if edges is not None:
+            e = np.asarray(edges)
+            if e.ndim != 1 or e.size < 2 or e.dtype.kind not in "iu" or (e < 0).any() or (e > 0xffffffff).any():
+                raise ValueError("BandLevels edges must be a 1-D sequence of at least two non-negative integers")
+            if n_bands and e.size != n_bands + 1:
+                raise ValueError(f"BandLevels edges has {e.size} entries, n_bands = {n_bands} needs {n_bands + 1}")
+            self.edges = np.ascontiguousarray(e, dtype=np.uint32)
+            n_bands = e.size - 1
+        self.n_bands = int(n_bands)
+        self.frames, self.phonemes = bool(frames), bool(phonemes)
+
+    @property
+    def width(self) -> int:
+        """entries of a row: the band count with the default filled in"""
+        return self.n_bands or 16
+
+    @classmethod
+    def from_hz(cls, sampling_rate: int, edges_hz, **kw):
+        """edges in Hz -> bins round(hz * 1024 / sr); duplicates after rounding are refused"""
+        bins = [int(np.floor(float(hz) * cls.N / sampling_rate + 0.5)) for hz in edges_hz]
+        if any(b1 <= b0 for b0, b1 in zip(bins, bins[1:])):
+            raise ValueError(f"band edges {list(edges_hz)} Hz give the bins {bins}, which do not ascend strictly")
+        return cls(edges=bins, **kw)
+
+    def __repr__(self):
+        return (f"BandLevels(n_bands={self.n_bands}, edges={None if self.edges is None else self.edges.tolist()}, "
+                f"frames={self.frames}, phonemes={self.phonemes})")
+
+
+class Bands:
+    """An utterance's band levels: .frames float32 [T, n_bands] and .phonemes float32 [n, n_bands], the level (RMS re full scale) of
+    each band of the waveform the same call returned; None for a table that was not asked for.  .params is the BandLevels; .edges the
+    bins in force; dbfs() converts levels to dB re full scale (0 -> -inf); .struct is the zv_bands, which points into the arrays and
+    the edges (kept alive here)."""
+
+    def __init__(self, T: int, n: int, params: BandLevels):
+        self.params = params
+        self.frames = np.zeros((T, params.width), np.float32) if params.frames else None
+        self.phonemes = np.zeros((n, params.width), np.float32) if params.phonemes else None
+
+    @property
+    def edges(self) -> np.ndarray:
+        return np.asarray(BandLevels.DEFAULT_EDGES, np.uint32) if self.params.edges is None else self.params.edges
+
+    @property
+    def struct(self) -> BandsC:
+        p = self.params
+        return BandsC(None if self.frames is None else self.frames.ctypes.data, None if self.phonemes is None else self.phonemes.ctypes.data,
+                      p.n_bands, None if p.edges is None else p.edges.ctypes.data)
+
+    @staticmethod
+    def dbfs(levels) -> np.ndarray:
+        """20 * log10(level), full scale = 1.0; -inf for a level of 0"""
+        a = np.asarray(levels, dtype=np.float64)
+        with np.errstate(divide="ignore"):
+            return 20.0 * np.log10(a)
+
+    def __repr__(self):
+        shape = lambda a: None if a is None else a.shape
+        return f"Bands(frames={shape(self.frames)}, phonemes={shape(self.phonemes)})"
+
+
+def _check_bands(return_bands, where: str = ""):
+    """return_bands -> a BandLevels or None (nothing asked for), checked before anything reaches the library: False, True (both
+    tables, default bands), "frames", "phonemes" or a BandLevels"""
+    if isinstance(return_bands, BandLevels):
+        return return_bands if return_bands.frames or return_bands.phonemes else None
+    if isinstance(return_bands, (bool, np.bool_)):
+        return BandLevels() if return_bands else None
+    if isinstance(return_bands, str):
+        if return_bands in ("frames", "phonemes"):
+            return BandLevels(frames=return_bands == "frames", phonemes=return_bands == "phonemes")
+        raise ValueError(f"{where}return_bands = {return_bands!r}: expected False, True, 'frames', 'phonemes' or a BandLevels")
+    raise TypeError(f"{where}return_bands must be a bool, 'frames', 'phonemes' or a BandLevels, not {type(return_bands).__name__}")
 
 
 class EnvelopeC(C.Structure):
@@ -474,6 +572,13 @@ def load_library(path: Optional[str] = None):
         lib.zv_synthesize_batch_pitch.argtypes = lib.zv_synthesize_batch_contour.argtypes + pt
         lib.zv_synthesize_batch_begin_pitch.argtypes = lib.zv_synthesize_batch_begin_contour.argtypes + pt
         lib.zv_pitch_track.argtypes = [vp, vp, C.c_uint32, C.POINTER(PitchC)]
+    # the bands forms: the _pitch argument lists and the band levels (zv_bands, batches [n_utt]) or NULL; the stand-alone meter
+    if hasattr(lib, "zv_synthesize_bands"):
+        bt = [C.POINTER(BandsC)]
+        lib.zv_synthesize_bands.argtypes = lib.zv_synthesize_pitch.argtypes + bt
+        lib.zv_synthesize_batch_bands.argtypes = lib.zv_synthesize_batch_pitch.argtypes + bt
+        lib.zv_synthesize_batch_begin_bands.argtypes = lib.zv_synthesize_batch_begin_pitch.argtypes + bt
+        lib.zv_band_levels.argtypes = [vp, vp, C.c_uint32, C.POINTER(BandsC)]
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -548,7 +653,7 @@ def _check_target(target, T):
 
 
 def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None, volume=None, levels=None,
-                  envelope=None, contour=None, pitch=None):
+                  envelope=None, contour=None, pitch=None, bands=None):
     """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
     name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status.
     fitted: name_fitted, which takes everything (NULL for what the call lacks).  target (a frame count, or the batches' uint32
@@ -557,7 +662,11 @@ def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, 
     envelope (a zv_envelope, or the batches' array): name_envelope, which takes everything the _volume form takes and the envelope.
     contour (a zv_contour, or the batches' array): name_contour, which takes everything the _envelope form takes and the contour;
     only a call that asks for a contour goes there.  pitch (a zv_pitch, or the batches' array): name_pitch, which takes everything the
-    _contour form takes and the pitch track; only a call that asks for a pitch track goes there"""
+    _contour form takes and the pitch track; only a call that asks for a pitch track goes there.  bands (a zv_bands, or the batches'
+    array): name_bands, which takes everything the _pitch form takes and the band levels; only a call that asks for them goes there"""
+    if bands is not None:
+        return getattr(lib, name + "_bands")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour,
+                                             pitch, bands)
     if pitch is not None:
         return getattr(lib, name + "_pitch")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour, pitch)
     if contour is not None:
@@ -755,7 +864,7 @@ class Model:
 
     def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False,
                    fitted: bool = False, target_frames: Optional[int] = None, *, volume=None, return_levels: bool = False,
-                   envelope=None, return_contour=False, return_pitch=False):
+                   envelope=None, return_contour=False, return_pitch=False, return_bands=False):
         """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
         arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
         as a third element.  fitted: zv_synthesize_fitted — T is a capacity, the utterance is decoded and vocoded as the n_frames
@@ -769,9 +878,12 @@ class Model:
         return_contour (False, True, "frames" or "phonemes"): zv_synthesize_contour — the level and peak of every frame and / or every
         phoneme of the returned waveform, metered on the device; adds a Contour as the last element.
         return_pitch (False, True, "frames", "phonemes" or a PitchTrack): zv_synthesize_pitch — the fundamental frequency and voicing
-        of every frame and / or every phoneme of the returned waveform, metered on the device; adds a Pitch as the last element"""
+        of every frame and / or every phoneme of the returned waveform, metered on the device; adds a Pitch as the last element.
+        return_bands (False, True, "frames", "phonemes" or a BandLevels): zv_synthesize_bands — the level per frequency band of every
+        frame and / or every phoneme of the returned waveform, metered on the device; adds a Bands as the last element"""
         want_frames, want_phonemes = _check_contour(return_contour)
         track = _check_pitch(return_pitch)
+        spec = _check_bands(return_bands)
         fitted = _check_fitted(fitted, [T])
         target = _check_target(target_frames, T)
         vol, return_levels = _volume(volume), _check_levels(return_levels)
@@ -787,15 +899,34 @@ class Model:
         level = Level() if vol is not None or return_levels else None
         contour = Contour(T, len(ids), want_frames, want_phonemes) if want_frames or want_phonemes else None
         pitch = Pitch(T, len(ids), track) if track is not None else None
-        if (level is not None or env is not None or contour is not None or pitch is not None) and target is None:
-            target = 0                       # the _volume, _envelope, _contour and _pitch forms take a count, 0 = none
+        bands = Bands(T, len(ids), spec) if spec is not None else None
+        if (level is not None or env is not None or contour is not None or pitch is not None or bands is not None) and target is None:
+            target = 0                       # the _volume, _envelope, _contour, _pitch and _bands forms take a count, 0 = none
         self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur),
                                 fitted, target, _ref(vol), _ref(level), _ref(None if env is None else env.struct),
-                                _ref(None if contour is None else contour.struct), _ref(None if pitch is None else pitch.struct)))
+                                _ref(None if contour is None else contour.struct), _ref(None if pitch is None else pitch.struct),
+                                _ref(None if bands is None else bands.struct)))
         out = (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
         out = out + (level,) if return_levels else out
         out = out + (contour,) if contour is not None else out
-        return out + (pitch,) if pitch is not None else out
+        out = out + (pitch,) if pitch is not None else out
+        return out + (bands,) if bands is not None else out
+
+    def band_levels(self, wav, params=None) -> Bands:
+        """zv_band_levels: the band levels of a waveform the caller brings (float32 [T * hop] at the model's rate and hop), frames
+        only; params: a BandLevels or None (the default bands)"""
+        if params is not None and not isinstance(params, BandLevels):
+            raise TypeError(f"band_levels: params must be a BandLevels or None, not {type(params).__name__}")
+        p = params or BandLevels()
+        spec = BandLevels(p.n_bands if p.edges is None else 0, p.edges, True, False)      # a waveform has no timings
+        w = np.ascontiguousarray(wav, dtype=np.float32)
+        hop = self.hp.audio_hop_size
+        if w.ndim != 1 or w.size == 0 or w.size % hop:
+            raise ValueError(f"band_levels: the waveform must be a non-empty 1-D array of a multiple of {hop} samples, got shape {w.shape}")
+        bands = Bands(w.size // hop, 0, spec)
+        st = bands.struct
+        self._chk(self.lib.zv_band_levels(self.h, _ptr(w), w.size // hop, C.byref(st)))
+        return bands
 
     def pitch_track(self, wav, params=None) -> Pitch:
         """zv_pitch_track: the pitch track of a waveform the caller brings (float32 [T * hop] at the model's rate and hop), frames
@@ -814,15 +945,16 @@ class Model:
         return pitch
 
     def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
-                      return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False) -> "BatchCall":
+                      return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False,
+                      return_bands=False) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
         buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list.  fitted: the
         zv_synthesize_batch_fitted / _begin_fitted entry points (the lane form: .begin(lane) / .end(lane))"""
         return BatchCall(self, utterances, durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
-                         return_contour=return_contour, return_pitch=return_pitch)
+                         return_contour=return_contour, return_pitch=return_pitch, return_bands=return_bands)
 
     def synthesize_batch(self, utterances, return_durations: bool = False, fitted: bool = False, *, volume=None,
-                         return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False):
+                         return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False, return_bands=False):
         """utterances: list of (ids, puncts, style, T[, prosody[, phonemes[, target_frames]]]) -> list of (wav, n_frames); each
         utterance keeps its own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its
         per-phoneme controls (PhonemeControls, dict of arrays or None), with a seventh its target frame count (None / 0: none).  return_durations: (wav, n_frames, durations) tuples.  fitted:
@@ -832,9 +964,10 @@ class Model:
         zv_synthesize_batch_envelope.  return_contour: False, True, "frames" or "phonemes" for the whole batch, or a list with one of
         them per utterance — zv_synthesize_batch_contour; every tuple gains the utterance's Contour (None where it asked for none) as
         its last element.  return_pitch: False, True, "frames", "phonemes" or a PitchTrack for the whole batch, or a list with one of
-        them per utterance — zv_synthesize_batch_pitch; every tuple gains the utterance's Pitch (None where it asked for none) last"""
+        them per utterance — zv_synthesize_batch_pitch; every tuple gains the utterance's Pitch (None where it asked for none) last.
+        return_bands: likewise with a BandLevels — zv_synthesize_batch_bands; every tuple gains the utterance's Bands last"""
         call = BatchCall(self, utterances, return_durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
-                         return_contour=return_contour, return_pitch=return_pitch)
+                         return_contour=return_contour, return_pitch=return_pitch, return_bands=return_bands)
         call.run()
         res = call.results()
         if return_durations:
@@ -845,6 +978,8 @@ class Model:
             res = [r + (c,) for r, c in zip(res, call.contours)]
         if call.pitch is not None:
             res = [r + (p,) for r, p in zip(res, call.pitches)]
+        if call.band is not None:
+            res = [r + (b,) for r, b in zip(res, call.bands)]
         return res
 
     # ---- device-resident API ----
@@ -933,11 +1068,24 @@ class BatchCall:
     (None where it asked for none), whose arrays hold its rows after run() / end().
     return_pitch (False, True, "frames", "phonemes" or a PitchTrack for the whole batch, or a list with one of them per utterance): where
     any utterance asks for a table, the _pitch entry points, with the zv_pitch array .pitch; .pitches[i] is utterance i's Pitch (None
-    where it asked for none); set_pitch() rewrites an entry's parameters and tables for the next run() / begin()."""
+    where it asked for none); set_pitch() rewrites an entry's parameters and tables for the next run() / begin().
+    return_bands (False, True, "frames", "phonemes" or a BandLevels for the whole batch, or a list with one of them per utterance): where
+    any utterance asks for a table, the _bands entry points, with the zv_bands array .band; .bands[i] is utterance i's Bands (None where
+    it asked for none); set_bands() rewrites an entry's band count, edges and tables for the next run() / begin()."""
 
     def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
-                 return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False):
+                 return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False, return_bands=False):
         self.fitted = _check_fitted(fitted, [u[3] for u in utterances])
+        if isinstance(return_bands, (list, tuple)):
+            if len(return_bands) != len(utterances):
+                raise ValueError(f"return_bands has {len(return_bands)} entries, the batch has {len(utterances)} utterances")
+            specs = [_check_bands(w, f"utterance {i}: ") for i, w in enumerate(return_bands)]
+        else:
+            specs = [_check_bands(return_bands)] * len(utterances)
+        self.band = self.bands = None
+        if any(t is not None for t in specs):
+            self.bands = [Bands(u[3], len(u[0]), t) if t is not None else None for t, u in zip(specs, utterances)]
+            self.band = (BandsC * len(utterances))(*[b.struct if b is not None else BandsC() for b in self.bands])
         if isinstance(return_pitch, (list, tuple)):
             if len(return_pitch) != len(utterances):
                 raise ValueError(f"return_pitch has {len(return_pitch)} entries, the batch has {len(utterances)} utterances")
@@ -1045,6 +1193,15 @@ class BatchCall:
         self.pitches[i] = Pitch(int(self.Ts[i]), int(self.Ns[i]), t) if t is not None else None
         self.pitch[i] = self.pitches[i].struct if t is not None else PitchC()
 
+    def set_bands(self, i: int, return_bands):
+        """utterance i's band request (False / None: none) for the following run() / begin() (the call must have been built with
+        return_bands=); .bands[i] is replaced"""
+        if self.band is None:
+            raise ValueError("this BatchCall was built without band levels")
+        t = _check_bands(False if return_bands is None else return_bands, f"utterance {i}: ")
+        self.bands[i] = Bands(int(self.Ts[i]), int(self.Ns[i]), t) if t is not None else None
+        self.band[i] = self.bands[i].struct if t is not None else BandsC()
+
     def set_prosody(self, i: int, prosody):
         """utterance i's controls for the following run() / begin() (the call must have been built with controls)"""
         if self.prosody is None:
@@ -1055,14 +1212,14 @@ class BatchCall:
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope, self.contour, self.pitch))
+                             self.volume, self.levels, self.envelope, self.contour, self.pitch, self.band))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope, self.contour, self.pitch))
+                             self.volume, self.levels, self.envelope, self.contour, self.pitch, self.band))
 
     def end(self, lane: int):
         m = self.model

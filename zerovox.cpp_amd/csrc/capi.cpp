@@ -171,7 +171,17 @@ struct Request
     const zv_contour          *contour = nullptr;
     // pitch track (zv_*_pitch): [count] or null; each struct's tables are [T[u]] and [n[u]] or null, its parameters 0 = default
     const zv_pitch            *pitch = nullptr;
+    // band levels (zv_*_bands): [count] or null; each struct's tables are [T[u]][n_bands] and [n[u]][n_bands] or null
+    const zv_bands            *bands = nullptr;
 
+    // any utterance that asks for a table of its band levels: then the rows of every utterance that asks are written on the device (an
+    // utterance that asks for none is skipped by both passes: its parameter row says n_bands = 0), and the host downloads the tables
+    bool band_levels() const
+    {
+        for (uint32_t u = 0; bands && u < count; u++)
+            if (bands[u].frames || bands[u].phonemes) return true;
+        return false;
+    }
     // any utterance that asks for a table of its pitch track: then every row of both tables is written on the device (an utterance
     // that asks for none is metered at the cheapest parameters), and the host downloads the tables that were asked for
     bool pitches() const
@@ -237,6 +247,7 @@ struct Request
         if (envelope) s.envelope += a;
         if (contour) s.contour += a;
         if (pitch) s.pitch += a;
+        if (bands) s.bands += a;
         return s;
     }
 };
@@ -310,6 +321,31 @@ static void pack_pitch(const Model &M, const Request &r, uint32_t *par)
         c[1] = q.max_lag;
         c[2] = q.window;
         c[3] = zv::level_bits(q.voiced_threshold);
+    }
+}
+
+// a zv_bands' resolved parameter row (bands.h bands_resolve), or ZV_ERR_ARG naming the field
+static void resolve_bands(const zv_bands &b, uint32_t *row)
+{
+    if (const char *field = zv::bands_resolve(b.n_bands, b.edges, row))
+    {
+        if (!strcmp(field, "n_bands")) zv::fail(ZV_ERR_ARG, "bands n_bands = %u exceeds %u", b.n_bands, zv::BANDS_MAX);
+        if (!b.edges) zv::fail(ZV_ERR_ARG, "bands edges = NULL (the default edges) needs n_bands 0 or %u, got %u", zv::BANDS_DEFAULT, b.n_bands);
+        zv::fail(ZV_ERR_ARG, "bands edges must ascend strictly and end at or below %d (edges[n_bands] = %u)", zv::BANDS_BINS,
+                 b.edges[b.n_bands ? b.n_bands : zv::BANDS_DEFAULT]);
+    }
+}
+
+// a request's band parameters in the kernels' layout (bands.h BANDS_PARAM_STRIDE), resolved; an utterance that asks for no table gets
+// n_bands = 0, which both passes skip.  nb [count] (may be null) receives each utterance's band count
+static void pack_bands(const Request &r, uint32_t *par, uint32_t *nb)
+{
+    for (uint32_t u = 0; u < r.count; u++)
+    {
+        uint32_t *c = par + (size_t)u * zv::BANDS_PARAM_STRIDE;
+        memset(c, 0, zv::BANDS_PARAM_STRIDE * 4);
+        if (r.bands[u].frames || r.bands[u].phonemes) resolve_bands(r.bands[u], c);
+        if (nb) nb[u] = c[0];
     }
 }
 
@@ -390,6 +426,11 @@ static void check_request(zv_model *m, const Request &r)
             if (r.volume) check_volume(r.volume[u]);
             if (r.envelope) check_envelope(r.envelope[u], r.n[u]);
             if (r.pitch && (r.pitch[u].frames || r.pitch[u].phonemes)) resolve_pitch(M, r.pitch[u]);
+            if (r.bands && (r.bands[u].frames || r.bands[u].phonemes))
+            {
+                uint32_t row[zv::BANDS_PARAM_STRIDE];
+                resolve_bands(r.bands[u], row);
+            }
             if (r.target_frames && r.target_frames[u] > r.T[u])
                 zv::fail(ZV_ERR_ARG, "target_frames = %u exceeds the capacity T = %u", r.target_frames[u], r.T[u]);
             if (tg && r.n[u] > (uint32_t)zv::FIT_MAX_TOKENS)      // one launch covers the request's utterances, with or without a target
@@ -473,7 +514,9 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const bool tg = r.targets(), pc = r.phoneme_controls() || tg, dur = r.timings();
         const size_t E = M.E(), b_ids = (size_t)n * 4, b_hid = (size_t)T * E * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
         const size_t b_ctl = r.prosody || tg ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
-        const bool vol = r.volumes() && !taps, env = r.envelopes() && !taps, ctr = r.contours() && !taps, pit = r.pitches() && !taps;
+        const bool vol = r.volumes() && !taps, env = r.envelopes() && !taps, ctr = r.contours() && !taps, pit = r.pitches() && !taps,
+                   bnd = r.band_levels() && !taps;
+        const void *bnd_table = bnd ? M.bands_table() : nullptr;      // (allocates and copies on first use: ahead of everything enqueued)
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
         // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
@@ -482,7 +525,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const size_t o_nf = L.at(4), o_ids = L.at(b_ids), o_pun = L.at(b_ids), o_sty = L.at(E * 4), o_ctl = L.at(b_ctl),
                      o_pctl = L.at(b_pctl), o_hid = L.at(b_hid);
         const size_t o_mel = taps ? 0 : L.at((size_t)T * M.hp.audio_num_mels * 4), o_wav = taps ? 0 : L.at(b_wav),
-                     o_cum = taps ? 0 : L.at(dur || env || ctr || pit ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
+                     o_cum = taps ? 0 : L.at(dur || env || ctr || pit || bnd ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
                      o_runs = L.at(!r.fitted && !taps ? sizeof(zv::Seg) : 0);
         // [volume row][level row] (volume controls: the row uploaded, the level written on the device)
         const size_t o_vol = L.at(vol ? zv::LEVEL_VOL_STRIDE * 4 : 0), o_lvl = L.at(vol ? sizeof(zv::LevelRow) : 0);
@@ -494,6 +537,10 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         // [frame rows][phoneme rows][parameter row] (pitch track: the rows written on the device, the parameters uploaded; behind the contour's)
         const size_t b_pfr = (size_t)T * sizeof(zv::PitchFrameRow), b_pph = (size_t)n * sizeof(zv::PitchPhonemeRow);
         const size_t o_pfr = L.at(pit ? b_pfr : 0), o_pph = L.at(pit ? b_pph : 0), o_ppar = L.at(pit ? zv::PITCH_PARAM_STRIDE * 4 : 0);
+        // [frame rows][phoneme rows][kept powers][parameter row] (band levels: BANDS_ROW_STRIDE entries per row; behind the pitch track's)
+        const size_t b_bfr = (size_t)T * zv::BANDS_ROW_STRIDE * 4, b_bph = (size_t)n * zv::BANDS_ROW_STRIDE * 4;
+        const size_t o_bfr = L.at(bnd ? b_bfr : 0), o_bph = L.at(bnd ? b_bph : 0), o_bsl = L.at(bnd ? 2 * b_bfr : 0),
+                     o_bpar = L.at(bnd ? zv::BANDS_PARAM_STRIDE * 4 : 0);
         char *io = (char *)M.io_scratch(L.size());
         int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
@@ -539,6 +586,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
             ZV_HIP(hipMemcpyAsync(io + o_env, erow, sizeof(erow), hipMemcpyHostToDevice, M.stream()));
         }
         uint32_t prow[zv::PITCH_PARAM_STRIDE];                       // host staging, like ctl
+        uint32_t brow[zv::BANDS_PARAM_STRIDE];                       // likewise
         int32_t nf = 0;
         if (taps)
         {
@@ -557,11 +605,21 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         {
             float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
             // an envelope's knots pass and a contour's phonemes pass read the scan behind the vocoder
-            if (dur || env || ctr || pit) bt.d_cum = (int32_t *)(io + o_cum);
+            if (dur || env || ctr || pit || bnd) bt.d_cum = (int32_t *)(io + o_cum);
             if (ctr)
             {
                 bt.d_ctr_frames = (zv::ContourRow *)(io + o_cfr);
                 bt.d_ctr_phonemes = (zv::ContourRow *)(io + o_cph);
+            }
+            if (bnd)
+            {
+                pack_bands(r, brow, nullptr);
+                bt.d_bnd_frames = (float *)(io + o_bfr);
+                bt.d_bnd_phonemes = (float *)(io + o_bph);
+                bt.d_bnd_slab = (unsigned long long *)(io + o_bsl);
+                bt.d_bnd_par = (const uint32_t *)(io + o_bpar);
+                bt.d_bnd_table = bnd_table;
+                ZV_HIP(hipMemcpyAsync(io + o_bpar, brow, sizeof(brow), hipMemcpyHostToDevice, M.stream()));
             }
             if (pit)
             {
@@ -581,6 +639,13 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
             if (ctr && r.contour[0].phonemes) ZV_HIP(hipMemcpyAsync(r.contour[0].phonemes, io + o_cph, b_cph, hipMemcpyDeviceToHost, M.stream()));
             if (pit && r.pitch[0].frames) ZV_HIP(hipMemcpyAsync(r.pitch[0].frames, io + o_pfr, b_pfr, hipMemcpyDeviceToHost, M.stream()));
             if (pit && r.pitch[0].phonemes) ZV_HIP(hipMemcpyAsync(r.pitch[0].phonemes, io + o_pph, b_pph, hipMemcpyDeviceToHost, M.stream()));
+            // the band rows likewise: the device keeps BANDS_ROW_STRIDE entries per row, the caller receives the first n_bands of each
+            if (bnd && r.bands[0].frames)
+                ZV_HIP(hipMemcpy2DAsync(r.bands[0].frames, (size_t)brow[0] * 4, io + o_bfr, zv::BANDS_ROW_STRIDE * 4, (size_t)brow[0] * 4, T,
+                                        hipMemcpyDeviceToHost, M.stream()));
+            if (bnd && r.bands[0].phonemes)
+                ZV_HIP(hipMemcpy2DAsync(r.bands[0].phonemes, (size_t)brow[0] * 4, io + o_bph, zv::BANDS_ROW_STRIDE * 4, (size_t)brow[0] * 4, n,
+                                        hipMemcpyDeviceToHost, M.stream()));
         }
         M.sync();
         if (vol && r.levels) r.levels[0] = level;
@@ -802,6 +867,11 @@ struct PendingBatch
     std::vector<zv_pitch> pitch;
     const zv_pitch_frame   *h_pfr = nullptr;
     const zv_pitch_phoneme *h_pph = nullptr;
+    // band levels (zv_synthesize_batch_begin_bands): likewise, BANDS_ROW_STRIDE entries per row in the staging block; bands_nb: each
+    // utterance's resolved band count, the entries of a row the caller receives
+    std::vector<zv_bands> bands;
+    std::vector<uint32_t> bands_nb;
+    const float *h_bfr = nullptr, *h_bph = nullptr;
 };
 static PendingBatch &pending_slot(zv_model *m, int lane)
 {
@@ -837,7 +907,8 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
     const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings(), vol = r.volumes(),
-               env = r.envelopes(), ctr = r.contours(), pit = r.pitches();
+               env = r.envelopes(), ctr = r.contours(), pit = r.pitches(), bnd = r.band_levels();
+    const void *bnd_table = bnd ? M.bands_table() : nullptr;      // (allocates and copies on first use: ahead of everything enqueued)
     uint32_t nmax = 0, tmax = 0, ntot = 0;
     for (uint32_t u = 0; u < r.count; u++)
     {
@@ -866,19 +937,23 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
                  i_eg = in.at(env ? bt.n_rows * 4 : 0),                                    // envelope: a gain per token row and a row per utterance, likewise
                  i_env = in.at(env ? (size_t)bt.nseg * zv::ENV_CTL_STRIDE * 4 : 0),
                  i_ppar = in.at(pit ? (size_t)bt.nseg * zv::PITCH_PARAM_STRIDE * 4 : 0),      // pitch track: a parameter row per utterance, likewise
+                 i_bpar = in.at(bnd ? (size_t)bt.nseg * zv::BANDS_PARAM_STRIDE * 4 : 0),      // band levels: likewise
                  b_in = in.size();
     // device block: [frame counts][input block][hidden][mel][wav][scan] (scan: only when timings are asked for, the length
     // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
     Layout dev;
     const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
-                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || env || ctr || pit ? bt.n_rows * 4 : 0),
+                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || env || ctr || pit || bnd ? bt.n_rows * 4 : 0),
                  o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0),      // fitted: the live frame table, written on the device
                  o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0),     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
                  o_lvl = dev.at(vol ? (size_t)bt.nseg * sizeof(zv::LevelRow) : 0),             // volume controls: the level rows, written on the device
                  o_cfr = dev.at(ctr ? bt.t_rows * sizeof(zv::ContourRow) : 0),                 // level contour: the frame rows and the phoneme rows, next to them,
                  o_cph = dev.at(ctr ? bt.n_rows * sizeof(zv::ContourRow) : 0),                 // by absolute frame row / token row, written on the device
                  o_pfr = dev.at(pit ? bt.t_rows * sizeof(zv::PitchFrameRow) : 0),              // pitch track: the same two tables
-                 o_pph = dev.at(pit ? bt.n_rows * sizeof(zv::PitchPhonemeRow) : 0);
+                 o_pph = dev.at(pit ? bt.n_rows * sizeof(zv::PitchPhonemeRow) : 0),
+                 o_bfr = dev.at(bnd ? bt.t_rows * zv::BANDS_ROW_STRIDE * 4 : 0),               // band levels: the two tables and the kept powers
+                 o_bph = dev.at(bnd ? bt.n_rows * zv::BANDS_ROW_STRIDE * 4 : 0),
+                 o_bsl = dev.at(bnd ? bt.t_rows * zv::BANDS_ROW_STRIDE * 8 : 0);
     M.reserve_batch(bt);
     char *io = (char *)M.io_scratch(dev.size());
     // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan][level rows][contour frame rows]
@@ -886,7 +961,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     size_t wav_bytes = 0;
     pb.woff.assign(r.count, 0);
     pb.noff.assign(r.count + 1, 0);
-    bool ctr_f = false, ctr_p = false, pit_f = false, pit_p = false;
+    bool ctr_f = false, ctr_p = false, pit_f = false, pit_p = false, bnd_f = false, bnd_p = false;
     for (uint32_t u = 0; u < r.count; u++)
     {
         pb.woff[u] = wav_bytes;
@@ -896,13 +971,16 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         ctr_p = ctr_p || (ctr && r.contour[u].phonemes);
         pit_f = pit_f || (pit && r.pitch[u].frames);
         pit_p = pit_p || (pit && r.pitch[u].phonemes);
+        bnd_f = bnd_f || (bnd && r.bands[u].frames);
+        bnd_p = bnd_p || (bnd && r.bands[u].phonemes);
     }
     const size_t frame_rows = wav_bytes / (hop * 4);
     Layout host;
     const size_t p_in = host.at(b_in), p_nf = host.at((size_t)bt.nseg * 4), p_wav = host.at(wav_bytes),
                  p_cum = host.at(dur ? bt.n_rows * 4 : 0), p_lvl = host.at(vol ? (size_t)bt.nseg * sizeof(zv_level) : 0),
                  p_cfr = host.at(ctr_f ? frame_rows * sizeof(zv_frame_level) : 0), p_cph = host.at(ctr_p ? (size_t)ntot * sizeof(zv_frame_level) : 0),
-                 p_pfr = host.at(pit_f ? frame_rows * sizeof(zv_pitch_frame) : 0), p_pph = host.at(pit_p ? (size_t)ntot * sizeof(zv_pitch_phoneme) : 0);
+                 p_pfr = host.at(pit_f ? frame_rows * sizeof(zv_pitch_frame) : 0), p_pph = host.at(pit_p ? (size_t)ntot * sizeof(zv_pitch_phoneme) : 0),
+                 p_bfr = host.at(bnd_f ? frame_rows * zv::BANDS_ROW_STRIDE * 4 : 0), p_bph = host.at(bnd_p ? (size_t)ntot * zv::BANDS_ROW_STRIDE * 4 : 0);
     char *pin = (char *)M.pinned_scratch(host.size());
     char *d_in = io + o_in, *h_in = pin + p_in;
     {
@@ -927,6 +1005,12 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         if (vol) pack_volume(r, (float *)(h_in + i_vol));
         if (env) pack_envelope(r, (float *)(h_in + i_eg), (int32_t *)(h_in + i_env));      // (gain rows past the utterances are never read)
         if (pit) pack_pitch(M, r, (uint32_t *)(h_in + i_ppar));
+        pb.bands_nb.assign(bnd ? r.count : 0, 0);
+        if (bnd)
+        {
+            memset(h_in + i_bpar, 0, (size_t)bt.nseg * zv::BANDS_PARAM_STRIDE * 4);      // (segments past the utterances ask for nothing)
+            pack_bands(r, (uint32_t *)(h_in + i_bpar), pb.bands_nb.data());
+        }
     }
     bt.d_tok = (const zv::Seg *)(d_in + i_tok);
     bt.d_frm = (const zv::Seg *)(d_in + i_frm);
@@ -934,11 +1018,19 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     bt.has_targets = tg;
     if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
     // an envelope's knots pass and a contour's phonemes pass read the scan behind the vocoder
-    if (dur || env || ctr || pit) bt.d_cum = (int32_t *)(io + o_cum);
+    if (dur || env || ctr || pit || bnd) bt.d_cum = (int32_t *)(io + o_cum);
     if (ctr)
     {
         bt.d_ctr_frames = (zv::ContourRow *)(io + o_cfr);
         bt.d_ctr_phonemes = (zv::ContourRow *)(io + o_cph);
+    }
+    if (bnd)
+    {
+        bt.d_bnd_frames = (float *)(io + o_bfr);
+        bt.d_bnd_phonemes = (float *)(io + o_bph);
+        bt.d_bnd_slab = (unsigned long long *)(io + o_bsl);
+        bt.d_bnd_par = (const uint32_t *)(d_in + i_bpar);
+        bt.d_bnd_table = bnd_table;
     }
     if (pit)
     {
@@ -968,6 +1060,8 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     zv_frame_level *h_cfr = ctr_f ? (zv_frame_level *)(pin + p_cfr) : nullptr, *h_cph = ctr_p ? (zv_frame_level *)(pin + p_cph) : nullptr;
     zv_pitch_frame *h_pfr = pit_f ? (zv_pitch_frame *)(pin + p_pfr) : nullptr;
     zv_pitch_phoneme *h_pph = pit_p ? (zv_pitch_phoneme *)(pin + p_pph) : nullptr;
+    float *h_bfr = bnd_f ? (float *)(pin + p_bfr) : nullptr, *h_bph = bnd_p ? (float *)(pin + p_bph) : nullptr;
+    const size_t brs = zv::BANDS_ROW_STRIDE;
     // the contour rows and the pitch rows of utterances [u0, u1) travel behind their waveforms on stream `st`: frame rows packed like the waveforms
     // (a frame row per hop samples), phoneme rows like the tokens
     auto contour_download = [&](uint32_t u0, uint32_t u1, hipStream_t st) {
@@ -981,6 +1075,10 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
             ZV_HIP(hipMemcpyAsync(h_pfr + f0, bt.d_pit_frames + f0, (f1 - f0) * sizeof(zv_pitch_frame), hipMemcpyDeviceToHost, st));
         if (h_pph && n1 > n0)
             ZV_HIP(hipMemcpyAsync(h_pph + n0, bt.d_pit_phonemes + n0, (n1 - n0) * sizeof(zv_pitch_phoneme), hipMemcpyDeviceToHost, st));
+        if (h_bfr && f1 > f0)
+            ZV_HIP(hipMemcpyAsync(h_bfr + f0 * brs, bt.d_bnd_frames + f0 * brs, (f1 - f0) * brs * 4, hipMemcpyDeviceToHost, st));
+        if (h_bph && n1 > n0)
+            ZV_HIP(hipMemcpyAsync(h_bph + n0 * brs, bt.d_bnd_phonemes + n0 * brs, (n1 - n0) * brs * 4, hipMemcpyDeviceToHost, st));
     };
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
@@ -1064,6 +1162,10 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     pb.h_pph = h_pph;
     if (pit) pb.pitch.assign(r.pitch, r.pitch + r.count);
     else pb.pitch.clear();
+    pb.h_bfr = h_bfr;
+    pb.h_bph = h_bph;
+    if (bnd) pb.bands.assign(r.bands, r.bands + r.count);
+    else pb.bands.clear();
     pb.N.assign(r.n, r.n + r.count);
     if (dur) pb.dur.assign(r.durations, r.durations + r.count);
     else pb.dur.clear();
@@ -1108,6 +1210,15 @@ static void batch_finish(zv_model *m, int lane)
         const zv_pitch &c = pb.pitch[u];
         if (c.frames) memcpy(c.frames, pb.h_pfr + pb.woff[u] / (pb.hop * 4), (size_t)pb.T[u] * sizeof(zv_pitch_frame));
         if (c.phonemes) memcpy(c.phonemes, pb.h_pph + pb.noff[u], (size_t)pb.N[u] * sizeof(zv_pitch_phoneme));
+    }
+    // band rows: the staging block keeps BANDS_ROW_STRIDE entries per row, the caller receives the first n_bands of each
+    for (uint32_t u = 0; u < pb.n_utt && !pb.bands.empty(); u++)
+    {
+        const zv_bands &c = pb.bands[u];
+        const size_t nb = pb.bands_nb[u], brs = zv::BANDS_ROW_STRIDE;
+        const float *fr = pb.h_bfr ? pb.h_bfr + pb.woff[u] / (pb.hop * 4) * brs : nullptr, *ph = pb.h_bph ? pb.h_bph + pb.noff[u] * brs : nullptr;
+        for (size_t f = 0; c.frames && f < pb.T[u]; f++) memcpy(c.frames + f * nb, fr + f * brs, nb * 4);
+        for (size_t i = 0; c.phonemes && i < pb.N[u]; i++) memcpy(c.phonemes + i * nb, ph + i * brs, nb * 4);
     }
 }
 
@@ -1420,6 +1531,74 @@ zv_status zv_pitch_track(zv_model *m, const float *wav, uint32_t T, const zv_pit
         ZV_HIP(zv::launch_pitch_frames(M.stream(), (const float *)(io + o_wav), io + o_slab, (zv::PitchFrameRow *)(io + o_rows),
                                        (const uint32_t *)(io + o_par), one, (int)hop, (int)M.hp.audio_sampling_rate));
         ZV_HIP(hipMemcpyAsync(pitch->frames, io + o_rows, b_rows, hipMemcpyDeviceToHost, M.stream()));
+        M.sync();
+    });
+}
+
+// The bands forms: the _pitch requests plus the band levels (NULL, or no table asked for: the request of the _pitch call).
+zv_status zv_synthesize_bands(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                              float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                              int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                              const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch, const zv_bands *bands)
+{
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody, phonemes, &durations, fitted != 0,
+                          &target_frames, volume, levels, envelope, contour, pitch, bands});
+}
+
+zv_status zv_synthesize_batch_bands(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                    const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                    uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                    int32_t *const *durations, const uint32_t *target_frames, int fitted, const zv_volume *volume,
+                                    zv_level *levels, const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch,
+                                    const zv_bands *bands)
+{
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                durations, fitted != 0, target_frames, volume, levels, envelope, contour, pitch, bands});
+}
+
+zv_status zv_synthesize_batch_begin_bands(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                          const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                          const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                          const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                          const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                          const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch,
+                                          const zv_bands *bands)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                 durations, fitted != 0, target_frames, volume, levels, envelope, contour, pitch, bands});
+}
+
+// The stand-alone meter: a host waveform through the frames pass, eagerly, on lane 0, as one inline segment.
+zv_status zv_band_levels(zv_model *m, const float *wav, uint32_t T, const zv_bands *bands)
+{
+    return guarded([&] {
+        if (!(m && wav && bands)) zv::fail(ZV_ERR_ARG, "zv_band_levels: null argument");
+        if (!bands->frames) zv::fail(ZV_ERR_ARG, "zv_band_levels: bands->frames is required");
+        if (bands->phonemes) zv::fail(ZV_ERR_ARG, "zv_band_levels: bands->phonemes must be NULL (a waveform has no phoneme timings)");
+        Model &M = *m->m;
+        uint32_t brow[zv::BANDS_PARAM_STRIDE];
+        try
+        {
+            check_T(M, T);
+            resolve_bands(*bands, brow);
+        }
+        catch (const zv::Error &e)
+        {
+            zv::fail(e.status, "zv_band_levels: %s", e.what());
+        }
+        use_lane0(m);
+        const void *table = M.bands_table();
+        const size_t hop = M.hp.audio_hop_size, b_wav = (size_t)T * hop * 4, b_rows = (size_t)T * zv::BANDS_ROW_STRIDE * 4;
+        Layout L;
+        const size_t o_wav = L.at(b_wav), o_rows = L.at(b_rows), o_slab = L.at(2 * b_rows), o_par = L.at(sizeof(brow));
+        char *io = (char *)M.io_scratch(L.size());
+        ZV_HIP(hipMemcpyAsync(io + o_wav, wav, b_wav, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_par, brow, sizeof(brow), hipMemcpyHostToDevice, M.stream()));
+        const zv::Segs one{nullptr, 1, (int)T, zv::Seg{0, (int32_t)T, 0, 0}};
+        ZV_HIP(zv::launch_bands_frames(M.stream(), (const float *)(io + o_wav), table, io + o_slab, (float *)(io + o_rows),
+                                       (const uint32_t *)(io + o_par), one, (int)hop));
+        ZV_HIP(hipMemcpy2DAsync(bands->frames, (size_t)brow[0] * 4, io + o_rows, zv::BANDS_ROW_STRIDE * 4, (size_t)brow[0] * 4, T,
+                                hipMemcpyDeviceToHost, M.stream()));
         M.sync();
     });
 }

@@ -17,6 +17,7 @@
 #include "envelope.h"     // amplitude envelope: ENV_CTL_STRIDE, ENV_MAX_RAMP, ENV_MAX_GAIN
 #include "contour.h"      // level contour: CONTOUR_CHUNK_FRAMES, ContourRow
 #include "pitch.h"        // pitch track: PITCH_CHUNK_FRAMES, PITCH_PARAM_STRIDE, the rows
+#include "bands.h"        // band levels: BANDS_TILE_FRAMES, BANDS_PARAM_STRIDE, BANDS_ROW_STRIDE
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -457,5 +458,22 @@ hipError_t launch_contour_phonemes(hipStream_t s, const int32_t *cum, const void
 hipError_t launch_pitch_frames(hipStream_t s, const float *wav, void *slab, PitchFrameRow *rows, const uint32_t *par, const Segs &frames, int hop,
                                int sr);
 hipError_t launch_pitch_phonemes(hipStream_t s, const int32_t *cum, const void *slab, PitchPhonemeRow *rows, const Segs &tokens, const Segs &frames);
+
+// ---- band levels (include/zerovox_amd.h "band levels", bands.h): two passes behind the pitch track's, over the waveform the caller
+// receives.  `frames` is the CAPACITY table or inline segment, `tokens` the token table; both passes index by ABSOLUTE row, and every
+// row of rows and slab has BANDS_ROW_STRIDE entries of which the segment's first n_bands are written.
+//   frames:   slab[(frames[u].row0 + f) * BANDS_ROW_STRIDE + b] = the kept power Eq of band b of frame f (u64), for every frame of every
+//             segment's capacity, and, where rows is not null, rows[...same index] = the band's level.  table: the twiddle table in
+//             fragment order (bands_table_fragments, BANDS_TABLE_BYTES, 16-byte aligned).  par [segments][BANDS_PARAM_STRIDE]: each
+//             segment's resolved row (bands_resolve), read at run time; n_bands == 0 there: the segment is skipped by both passes.  A
+//             span never leaves its segment's own samples [row0 * hop, (row0 + rows) * hop).  The pass reads aligned 8-byte loads:
+//             wav 16-byte aligned and, as for the contour, a hop that is a multiple of 4 (contour_hop_supported), else it is refused.
+//   phonemes: rows[(tokens[u].row0 + i) * BANDS_ROW_STRIDE + b] = band b's level over phoneme i, for every token row of every segment;
+//             its frames come from cum, the length regulator's scan, clipped to the capacity (contour_extent)
+// slab: 8-byte aligned.  No HBM atomics, nothing to zero: phonemes reads only what frames has stored in the same run.
+hipError_t launch_bands_frames(hipStream_t s, const float *wav, const void *table, void *slab, float *rows, const uint32_t *par, const Segs &frames,
+                               int hop);
+hipError_t launch_bands_phonemes(hipStream_t s, const int32_t *cum, const void *slab, float *rows, const uint32_t *par, const Segs &tokens,
+                                 const Segs &frames);
 
 }  // namespace zv

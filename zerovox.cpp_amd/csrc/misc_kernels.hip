@@ -9,4 +9,5 @@
 #include "envelope_kernels.hip"       // amplitude envelope
 #include "contour_kernels.hip"        // level contour
 #include "pitch_kernels.hip"          // pitch track
+#include "bands_kernels.hip"          // band levels
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

@@ -117,6 +117,16 @@ struct Batch
     PitchFrameRow   *d_pit_frames = nullptr;
     PitchPhonemeRow *d_pit_phonemes = nullptr;
     const uint32_t  *d_pit_par = nullptr;
+    // Band levels (include/zerovox_amd.h "band levels", bands.h), all five set or none: the frame rows, f32 [t_rows][BANDS_ROW_STRIDE],
+    // the phoneme rows, f32 [n_rows][BANDS_ROW_STRIDE], the kept powers the frames pass leaves for the phonemes pass, u64 [t_rows]
+    // [BANDS_ROW_STRIDE], all in HBM outside the arena and indexed by absolute frame row / token row, the parameter rows, uint32 [nseg]
+    // [BANDS_PARAM_STRIDE], resolved on the host and uploaded with the call (the VALUES are read at run time), and the twiddle table
+    // (Model::bands_table).  With them d_cum is set.  Keyed like the pitch track: the vocoder ends in two launches more, behind its.
+    float              *d_bnd_frames = nullptr;
+    float              *d_bnd_phonemes = nullptr;
+    unsigned long long *d_bnd_slab = nullptr;
+    const uint32_t     *d_bnd_par = nullptr;
+    const void         *d_bnd_table = nullptr;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -147,7 +157,9 @@ struct Batch
                d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live && has_targets == o.has_targets &&
                d_dec_runs == o.d_dec_runs && d_vol == o.d_vol && d_levels == o.d_levels && d_nframes == o.d_nframes && d_env_gain == o.d_env_gain &&
                d_env == o.d_env && d_ctr_frames == o.d_ctr_frames && d_ctr_phonemes == o.d_ctr_phonemes &&
-               d_pit_frames == o.d_pit_frames && d_pit_phonemes == o.d_pit_phonemes && d_pit_par == o.d_pit_par;
+               d_pit_frames == o.d_pit_frames && d_pit_phonemes == o.d_pit_phonemes && d_pit_par == o.d_pit_par &&
+               d_bnd_frames == o.d_bnd_frames && d_bnd_phonemes == o.d_bnd_phonemes && d_bnd_slab == o.d_bnd_slab && d_bnd_par == o.d_bnd_par &&
+               d_bnd_table == o.d_bnd_table;
     }
 };
 
@@ -260,6 +272,11 @@ class Model
     // one that is not allocated (all three for a lane never selected).  Allocates nothing, selects nothing, drops no graph.
     void poison_lane(int i, int byte, size_t filled[3]);
 
+    // band levels: the twiddle table in the frames pass's fragment order (bands.h bands_table_fragments, BANDS_TABLE_BYTES of device
+    // memory outside the arenas), built on the host and uploaded at the first request, then kept for the model's life.  It allocates
+    // and copies synchronously, so the entry points call it before anything is enqueued or captured.
+    const void *bands_table();
+
     // scratch for host-buffer entry points (grows on demand)
     void *io_scratch(size_t bytes);
     // pinned host staging for batched D2H copies (an async copy into pageable memory blocks the host and would
@@ -287,6 +304,7 @@ class Model
   private:
     // ---- weights ----
     std::vector<void *> allocs_;
+    void  *bands_table_ = nullptr;
     void  *dev_alloc(size_t bytes);
     float *upload_f32(const GgufTensor &t, int pad_to = 0, float pad_value = 0.f);
     float *upload_vec(const GgufFile &g, const std::string &name, int expect_n, int pad_to = 0, float pad_value = 0.f);

@@ -18,6 +18,20 @@ void *Model::dev_alloc(size_t bytes)
     return p;
 }
 
+const void *Model::bands_table()
+{
+#if !defined(__HIP_DEVICE_COMPILE__)      // (bands.h keeps its host half out of device passes)
+    if (!bands_table_)
+    {
+        const std::vector<int8_t> img = bands_table_fragments(bands_tables());
+        void *d = dev_alloc(img.size());
+        ZV_HIP(hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice));
+        bands_table_ = d;
+    }
+#endif
+    return bands_table_;
+}
+
 float *Model::upload_f32(const GgufTensor &t, int pad_to, float pad_value)
 {
     if (t.type != GGML_F32) fail(ZV_ERR_SHAPE, "tensor %s: expected f32", t.name.c_str());

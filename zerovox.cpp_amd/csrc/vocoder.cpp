@@ -114,6 +114,7 @@ void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g
     }
     if (bt.d_nframes) sub.d_nframes = bt.d_nframes + g0;
     if (bt.d_pit_par) sub.d_pit_par = bt.d_pit_par + (size_t)g0 * PITCH_PARAM_STRIDE;      // (the rows go by absolute frame / token row)
+    if (bt.d_bnd_par) sub.d_bnd_par = bt.d_bnd_par + (size_t)g0 * BANDS_PARAM_STRIDE;      // (likewise)
     if (bt.d_env) sub.d_env = bt.d_env + (size_t)g0 * ENV_CTL_STRIDE;          // (the gains and the scan go by absolute token row)
     sub.nseg = cnt;
     vocode_group(sub, d_mel, d_wav, 2, g0);
@@ -536,6 +537,26 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
                   launch_pitch_frames(stream(), d_wav, lay.pitch_slab, bt.d_pit_frames, bt.d_pit_par, cap, rate, (int)hp.audio_sampling_rate));
         ZV_LAUNCH("voc_pitch_phonemes", 8.0 * cap_rows + 8.0 * tok_rows, 0.0,
                   launch_pitch_phonemes(stream(), bt.d_cum, lay.pitch_slab, bt.d_pit_phonemes, tk, cap));
+    }
+
+    // Band levels (bands.h): behind the pitch track's passes, with their indexing — per tail group, ahead of the group's download.  Only
+    // where the call carries a request; never under a one-layer tap.
+    if (bt.d_bnd_frames && dbg_layer.kind < 0)
+    {
+        if (!bt.d_cum || !bt.d_bnd_phonemes || !bt.d_bnd_slab || !bt.d_bnd_par || !bt.d_bnd_table)
+            fail(ZV_ERR_DEVICE, "internal: band levels without the scan, the phoneme rows, the slab, the parameters or the table");
+        const Segs cap = bt.frames_cap();
+        const Segs tk{bt.d_tok ? bt.d_tok + seg0 : nullptr, bt.nseg, bt.n_max, bt.tok1};
+        const double cap_rows = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg);
+        const double tok_rows = std::min((double)bt.n_rows, (double)bt.n_max * bt.nseg);
+        // algorithmic bytes: the capacity's samples read once, the table once per tile of frames, a slab row and a row written per
+        // frame; the slab read and a row written per token.  Operations: 2 per 8-bit multiply-add, both digit planes, 1 026 columns.
+        const double row_b = (double)BANDS_ROW_STRIDE;
+        ZV_LAUNCH("voc_bands_frames", 4.0 * cap_rows * rate + (double)BANDS_TABLE_BYTES * cap_rows / BANDS_TILE_FRAMES + 12.0 * row_b * cap_rows,
+                  2.0 * 2.0 * (double)BANDS_N * 2.0 * BANDS_BINS * cap_rows,
+                  launch_bands_frames(stream(), d_wav, bt.d_bnd_table, bt.d_bnd_slab, bt.d_bnd_frames, bt.d_bnd_par, cap, rate));
+        ZV_LAUNCH("voc_bands_phonemes", 8.0 * row_b * cap_rows + 4.0 * row_b * tok_rows, 0.0,
+                  launch_bands_phonemes(stream(), bt.d_cum, bt.d_bnd_slab, bt.d_bnd_phonemes, bt.d_bnd_par, tk, cap));
     }
 }
 

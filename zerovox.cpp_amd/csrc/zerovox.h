@@ -150,6 +150,15 @@ class ZeroVOXModel
     const std::vector<zv_pitch_frame> &get_pitch_frames() const { return pitch_frame_rows; }         // [max_seq_len], empty unless asked for
     const std::vector<zv_pitch_phoneme> &get_pitch_phonemes() const { return pitch_phoneme_rows; }   // [num_phonemes], likewise
 
+    // band levels (include/zerovox_amd.h "band levels") for the eval() calls that follow: the level per frequency band of every frame of
+    // the capacity and / or of every phoneme, metered on the device on the waveform get_wav() holds.  n_bands 0: 16; edges: n_bands + 1
+    // DFT bins, copied here, or nullptr: the default edges; they are checked when eval() runs.  A meter: nothing is scaled.
+    void set_bands(bool frames, bool phonemes, uint32_t n_bands = 0, const uint32_t *edges = nullptr);
+    uint32_t get_band_count() const { return (uint32_t)get_band_edges().size() - 1; }       // entries of a row
+    std::vector<uint32_t> get_band_edges() const;                                           // the edges in force: set_bands' or the library's defaults
+    const std::vector<float> &get_band_frames() const { return band_frame_rows; }           // [max_seq_len][bands], empty unless asked for
+    const std::vector<float> &get_band_phonemes() const { return band_phoneme_rows; }       // [num_phonemes][bands], likewise
+
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
     uint32_t     get_num_frames() const { return n_frames; }
@@ -187,6 +196,10 @@ class ZeroVOXModel
     zv_pitch             pitch_params = {nullptr, nullptr, 0, 0, 0, 0.0f};
     std::vector<zv_pitch_frame>   pitch_frame_rows;
     std::vector<zv_pitch_phoneme> pitch_phoneme_rows;
+    bool                 band_frames = false, band_phonemes = false;
+    uint32_t             band_count = 0;
+    std::vector<uint32_t> band_edges;
+    std::vector<float>   band_frame_rows, band_phoneme_rows;
 };
 
 }  // namespace ZeroVOX

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 
+#include "bands.h"         // BANDS_DEFAULT, BANDS_MAX, BANDS_DEFAULT_EDGES
 #include "common.h"
 
 namespace ZeroVOX
@@ -173,6 +174,22 @@ void ZeroVOXModel::set_pitch(bool frames, bool phonemes, const zv_pitch *params)
     pitch_params.phonemes = nullptr;
 }
 
+void ZeroVOXModel::set_bands(bool frames, bool phonemes, uint32_t n_bands, const uint32_t *edges)
+{
+    band_frames = frames;
+    band_phonemes = phonemes;
+    band_count = n_bands;
+    // (a count the library will refuse copies nothing: eval() reports it)
+    if (edges && n_bands <= zv::BANDS_MAX) band_edges.assign(edges, edges + (n_bands ? n_bands : zv::BANDS_DEFAULT) + 1);
+    else band_edges.clear();
+}
+
+std::vector<uint32_t> ZeroVOXModel::get_band_edges() const
+{
+    if (!band_edges.empty()) return band_edges;
+    return std::vector<uint32_t>(zv::BANDS_DEFAULT_EDGES, zv::BANDS_DEFAULT_EDGES + zv::BANDS_DEFAULT + 1);
+}
+
 void ZeroVOXModel::set_envelope(const zv_envelope *e, uint32_t n)
 {
     has_envelope = e != nullptr;
@@ -193,7 +210,10 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
     phoneme_levels.assign(contour_phonemes ? num_phonemes : 0, zv_frame_level{0.0f, 0.0f});
     pitch_frame_rows.assign(pitch_frames ? hparams.max_seq_len : 0, zv_pitch_frame{0.0f, 0.0f});
     pitch_phoneme_rows.assign(pitch_phonemes ? num_phonemes : 0, zv_pitch_phoneme{0.0f, 0.0f});
-    if (has_volume || has_envelope || contour_frames || contour_phonemes || pitch_frames || pitch_phonemes)
+    const size_t band_w = band_count && band_count <= zv::BANDS_MAX ? band_count : zv::BANDS_DEFAULT;
+    band_frame_rows.assign(band_frames ? (size_t)hparams.max_seq_len * band_w : 0, 0.0f);
+    band_phoneme_rows.assign(band_phonemes ? (size_t)num_phonemes * band_w : 0, 0.0f);
+    if (has_volume || has_envelope || contour_frames || contour_phonemes || pitch_frames || pitch_phonemes || band_frames || band_phonemes)
     {
         // the volume, envelope and contour forms take what every other form takes (the finished waveform of the one-pass chain is scaled and measured)
         if (has_phonemes && pc_n != num_phonemes)
@@ -205,6 +225,18 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
         const zv_envelope env = {env_gain_set ? env_gain.data() : nullptr, envelope.ramp_frames, envelope.fade_in_samples,
                                  envelope.fade_out_samples};
         const zv_contour ctr = {contour_frames ? frame_levels.data() : nullptr, contour_phonemes ? phoneme_levels.data() : nullptr};
+        if (band_frames || band_phonemes)
+        {
+            zv_pitch pit = pitch_params;
+            pit.frames = pitch_frames ? pitch_frame_rows.data() : nullptr;
+            pit.phonemes = pitch_phonemes ? pitch_phoneme_rows.data() : nullptr;
+            const zv_bands bnd = {band_frames ? band_frame_rows.data() : nullptr, band_phonemes ? band_phoneme_rows.data() : nullptr, band_count,
+                                  band_edges.empty() ? nullptr : band_edges.data()};
+            chk(zv_synthesize_bands(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
+                                    has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
+                                    has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr, &ctr, &pit, &bnd));
+            return;
+        }
         if (pitch_frames || pitch_phonemes)
         {
             zv_pitch pit = pitch_params;

@@ -52,6 +52,13 @@
 //            floor(rate / min-hz) (defaults: the library's, 63 .. 441 Hz at 22 050 Hz); the threshold is the voicing threshold in
 //            (0, 1], default 0.5.  A frequency that is not positive and finite, or a parameter without a file, is a usage error; the
 //            library checks the lags.
+//   --bands FILE, --phoneme-bands FILE, --band-edges-hz a,b,c,...
+//            band levels (include/zerovox_amd.h "band levels"): the level per frequency band of every frame of the capacity / of every
+//            phoneme, metered on the device on the waveform that is written, as TSV: a header line (index, then each band's range in
+//            bins as lo-hi), then index<TAB>level... per row, linear re full scale, printed with %.9g.  The edges in Hz (2 .. 65
+//            ascending values) become bins of the 1 024-point transform on the host, round(hz * 1024 / rate); without them the
+//            library's 16 default bands.  Edges that are not ascending positive numbers, or that come without a file, are a usage
+//            error; edges that fall on the same bin after rounding are refused once the checkpoint's rate is known.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
 #include <algorithm>
 #include <cmath>
@@ -78,6 +85,7 @@ static void usage(FILE *f)
                "               [--phoneme-gain-db FILE] [--ramp-frames R] [--fade-in-ms X] [--fade-out-ms X]\n"
                "               [--contour FILE] [--phoneme-levels FILE]\n"
                "               [--pitch FILE] [--phoneme-pitch FILE] [--pitch-min-hz F] [--pitch-max-hz F] [--pitch-threshold X]\n"
+               "               [--bands FILE] [--phoneme-bands FILE] [--band-edges-hz a,b,c,...]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
@@ -104,7 +112,10 @@ static void usage(FILE *f)
                "  --pitch FILE         write the fundamental frequency of every frame of the capacity as TSV: index f0_hz strength\n"
                "  --phoneme-pitch FILE write every phoneme's mean F0 and share of voiced frames as TSV: index f0_hz voiced\n"
                "  --pitch-min-hz F, --pitch-max-hz F  the range searched (default 63 .. 441 Hz at 22 050 Hz, three octaves at most)\n"
-               "  --pitch-threshold X  the correlation strength from which a frame counts as voiced, 0 < X <= 1, default 0.5\n",
+               "  --pitch-threshold X  the correlation strength from which a frame counts as voiced, 0 < X <= 1, default 0.5\n"
+               "  --bands FILE         write the level per frequency band of every frame of the capacity as TSV: index level...\n"
+               "  --phoneme-bands FILE write the level per frequency band of every phoneme likewise\n"
+               "  --band-edges-hz a,b,c,...  the bands' edges in Hz, 2 .. 65 ascending values (default: 16 bands, 22 Hz .. Nyquist at 22 050 Hz)\n",
             k_default_model, k_default_out);
 }
 
@@ -230,6 +241,8 @@ static std::vector<int32_t> utterance_ids(const std::string &utt_path)
 int main(int argc, char **argv)
 {
     std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path, gain_path, contour_path, plevel_path, pitch_path, ppitch_path;
+    std::string bands_path, pbands_path;
+    std::vector<double> band_hz;       // --band-edges-hz
     double pitch_hz[2] = {0.0, 0.0}, pitch_thr = 0.0;      // --pitch-min-hz, --pitch-max-hz, --pitch-threshold (0: the default)
     bool pitch_param = false;
     bool trim = false, fit = false, info = false, controlled = false, leveled = false, enveloped = false;
@@ -255,6 +268,30 @@ int main(int argc, char **argv)
         else if (a == "--phoneme-levels") plevel_path = need("--phoneme-levels");
         else if (a == "--pitch") pitch_path = need("--pitch");
         else if (a == "--phoneme-pitch") ppitch_path = need("--phoneme-pitch");
+        else if (a == "--bands") bands_path = need("--bands");
+        else if (a == "--phoneme-bands") pbands_path = need("--phoneme-bands");
+        else if (a == "--band-edges-hz")
+        {
+            const std::string v = need("--band-edges-hz");
+            bool ok = !v.empty();
+            band_hz.clear();
+            for (size_t at = 0; ok && at <= v.size();)
+            {
+                const size_t comma = std::min(v.find(',', at), v.size());
+                const std::string item = v.substr(at, comma - at);
+                char *end = nullptr;
+                const double x = strtod(item.c_str(), &end);
+                ok = !item.empty() && end == item.c_str() + item.size() && x > 0.0 && x <= 1e6 && (band_hz.empty() || x > band_hz.back());
+                band_hz.push_back(x);
+                at = comma + 1;
+            }
+            if (!ok || band_hz.size() < 2 || band_hz.size() > 65)
+            {
+                fprintf(stderr, "zerovox: --band-edges-hz needs 2 to 65 ascending numbers in (0, 1000000], separated by commas, got '%s'\n", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+        }
         else if (a == "--pitch-min-hz" || a == "--pitch-max-hz" || a == "--pitch-threshold")
         {
             const std::string v = need(a.c_str());
@@ -371,6 +408,12 @@ int main(int argc, char **argv)
         else if (a == "-h" || a == "--help") { usage(stdout); return 0; }
         else { fprintf(stderr, "zerovox: unknown argument '%s'\n", a.c_str()); usage(stderr); return 2; }
     }
+    if (!band_hz.empty() && bands_path.empty() && pbands_path.empty())
+    {
+        fprintf(stderr, "zerovox: --band-edges-hz needs --bands FILE or --phoneme-bands FILE\n");
+        usage(stderr);
+        return 2;
+    }
     if (pitch_param && pitch_path.empty() && ppitch_path.empty())
     {
         fprintf(stderr, "zerovox: --pitch-min-hz, --pitch-max-hz and --pitch-threshold need --pitch FILE or --phoneme-pitch FILE\n");
@@ -429,6 +472,20 @@ int main(int argc, char **argv)
             const zv_pitch pit = {nullptr, nullptr, pitch_hz[1] > 0.0 ? (uint32_t)std::min(floor(rate / pitch_hz[1]), 4294967295.0) : 0u,
                                   pitch_hz[0] > 0.0 ? (uint32_t)std::min(floor(rate / pitch_hz[0]), 4294967295.0) : 0u, 0u, (float)pitch_thr};
             model.set_pitch(!pitch_path.empty(), !ppitch_path.empty(), &pit);
+        }
+        std::vector<uint32_t> band_edges;      // the bins in force, for the TSV headers
+        if (!bands_path.empty() || !pbands_path.empty())
+        {
+            // Hz to bins on the host: round(hz * 1024 / rate)
+            for (double hz : band_hz) band_edges.push_back((uint32_t)std::min(floor(hz * 1024.0 / hp.audio_sampling_rate + 0.5), 4294967295.0));
+            for (size_t b = 1; b < band_edges.size(); b++)
+                if (band_edges[b] <= band_edges[b - 1])
+                    throw std::runtime_error("--band-edges-hz: " + std::to_string(band_hz[b - 1]) + " and " + std::to_string(band_hz[b]) +
+                                             " Hz fall on the same bin " + std::to_string(band_edges[b]) + " at " +
+                                             std::to_string(hp.audio_sampling_rate) + " Hz");
+            model.set_bands(!bands_path.empty(), !pbands_path.empty(), band_edges.empty() ? 0u : (uint32_t)band_edges.size() - 1,
+                            band_edges.empty() ? nullptr : band_edges.data());
+            band_edges = model.get_band_edges();       // the library's defaults where none were given
         }
         if (target_seconds > 0.0)
             target_frames = (long)std::min(floor(target_seconds * hp.audio_sampling_rate / hp.audio_hop_size + 0.5), 1e9);
@@ -516,6 +573,26 @@ int main(int argc, char **argv)
             if (!pitch_path.empty()) write_pitch(pitch_path, "strength", model.get_pitch_frames().size(), &model.get_pitch_frames().data()->f0_hz);
             if (!ppitch_path.empty())
                 write_pitch(ppitch_path, "voiced", model.get_pitch_phonemes().size(), &model.get_pitch_phonemes().data()->f0_hz);
+        }
+        if (!bands_path.empty() || !pbands_path.empty())
+        {
+            auto write_bands = [&](const std::string &path, const std::vector<float> &rows) {
+                FILE *cf = fopen(path.c_str(), "w");
+                if (!cf) throw std::runtime_error("cannot open '" + path + "' for writing");
+                const size_t nb = band_edges.size() - 1;
+                fprintf(cf, "index");
+                for (size_t b = 0; b < nb; b++) fprintf(cf, "\t%u-%u", band_edges[b], band_edges[b + 1]);
+                fprintf(cf, "\n");
+                for (size_t i = 0; i < rows.size() / nb; i++)
+                {
+                    fprintf(cf, "%zu", i);
+                    for (size_t b = 0; b < nb; b++) fprintf(cf, "\t%.9g", (double)rows[i * nb + b]);
+                    fprintf(cf, "\n");
+                }
+                if (fclose(cf) != 0) throw std::runtime_error("short write to '" + path + "'");
+            };
+            if (!bands_path.empty()) write_bands(bands_path, model.get_band_frames());
+            if (!pbands_path.empty()) write_bands(pbands_path, model.get_band_phonemes());
         }
         if (trim || fit)
         {
