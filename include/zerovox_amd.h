@@ -21,6 +21,8 @@
  *   zv_pitch_track     the pitch track of any waveform the caller brings
  *   *_bands            the same with the level per frequency band of every frame and every phoneme out (zv_bands)
  *   zv_band_levels     the band levels of any waveform the caller brings
+ *   *_filter           the same with a linear-phase FIR filter per utterance applied to the waveform on the device (zv_filter)
+ *   zv_filter_wave     the filter on any waveform the caller brings; zv_filter_design: band gains to taps, on the host
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file        src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -656,7 +658,7 @@ zv_status zv_pitch_track(zv_model *m, const float *wav, uint32_t T, const zv_pit
  * with w = wav.
  * Out of scope: zv_vocode*, zv_vocode_stream and the encode / decode entry points; a full 513-bin table (64 caller-chosen bands
  * cover it); mel or triangular weighting, log compression, MFCCs; a second twiddle digit for more than about 50 dB of range; other
- * window lengths; smoothing across frames; any spectral control (EQ, de-essing: the caller acts on the rows). */
+ * window lengths; smoothing across frames.  The write side of the rows, an equaliser per utterance, is zv_filter below. */
 typedef struct
 {
     float          *frames;    /* [T][n_bands] or NULL: one row per frame of the capacity */
@@ -683,6 +685,77 @@ zv_status zv_synthesize_batch_begin_bands(zv_model *m, uint32_t lane, uint32_t n
                                           const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch,
                                           const zv_bands *bands);
 zv_status zv_band_levels(zv_model *m, const float *wav, uint32_t T, const zv_bands *bands);
+/* ---- waveform filter: a linear-phase FIR equaliser per utterance ---------------------------------------------------------------------
+ * The write side of band levels: a telephone band, a bass cut for a small speaker, a presence lift, a softened sibilant band or a
+ * low-pass ahead of the caller's decimation, applied while the waveform is still in device memory.  The filter forms run it behind the
+ * vocoder's last convolution and AHEAD of envelope, volume controls and all meters, inside the same captured graph and — for a large
+ * batch — per tail group: the peak ceiling holds for the filtered signal, and contour, pitch and band rows describe the waveform
+ * the caller receives.  zv_filter_wave filters any waveform the caller brings; zv_filter_design turns band gains into taps.
+ * The rule, per utterance, with hop = audio_hop_size, F = n_frames in fitted mode and the capacity T otherwise, S = F*hop, x[0 .. S)
+ * the vocoder's waveform (what the _bands call would have written ahead of its envelope), L = n_taps, c = (L-1)/2, h = taps:
+ *   span     x'[j] = x[j] where 0 <= j < S and the sample is finite, else +0.0.  The span never reads another utterance's samples.
+ *   sample   for 0 <= n < S: acc = +0.0 (a double); for k = 0, 1, ..., L-1 in that order acc = acc + (double)h[k] * (double)x'[n + c - k];
+ *            y[n] = (float)acc.  The product of two f32 values is exact in f64, so every step is ONE IEEE addition whether or not a
+ *            compiler fuses it; the ascending order per output sample is part of the rule.
+ *   tail     for S <= n < T*hop: y[n] = +0.0f.  The fitted promise survives: wav[0 .. nf*hop) has the bits of the unfitted filtered
+ *            call at T = nf, and the rest is zero.
+ * y takes x's place for everything that follows in the call.  The centre tap is aligned with the sample: a symmetric filter adds no
+ * delay, so timings, contour, pitch and band rows keep pointing at the right samples.  Nothing depends on how samples are dealt over
+ * lanes, waves or workgroups.  csrc/filter.h holds the rule as plain C++ (host reference included).  What follows:
+ *   - L = 1, h = {1} returns x with -0.0 as +0.0 and non-finite samples as +0.0;
+ *   - a result beyond the f32 range becomes infinite by the conversion;
+ *   - samples near either end of the utterance see zeros outside [0, S).  That is part of the rule, not an error.
+ * ZV_ERR_ARG before any work is enqueued, the message naming the entry point, the utterance and the field: n_taps even or above 511,
+ * or 0 with taps not NULL ("filter n_taps"); a tap that is not finite ("filter taps").
+ * filter == NULL, or every struct with taps == NULL (n_taps of such a struct is not looked at): the request of the _bands call, the
+ * same launches, the same graph, the same bits.  Batches: filter[n_utt] or NULL; in a batch where some utterances carry a filter the
+ * others come through as exact copies of their bits (-0.0 and NaN patterns included) and give what the _bands call gives.  Tap counts
+ * and taps travel in the batch's device input block like the band edges, one row of 1 + 511 32-bit words per utterance, so a replayed
+ * graph picks up new taps and new tap counts.  The struct array and the taps are read before the call (_begin) returns.  With a
+ * filter the lane's arena holds one waveform more (the filter's input).  The filter never runs under zv_debug_layer.  Arguments,
+ * limits and messages are otherwise those of the _bands forms.  zv_synthesize_batch_begin_filter is finished by
+ * zv_synthesize_batch_end.
+ * zv_filter_wave filters a host waveform wav[T * hop] at the model's hop, eagerly, on lane 0, into out[T * hop] (out may be wav):
+ * the rule with x = wav and S = T*hop; filter->taps == NULL copies.  0 < T <= zv_max_frames(), else ZV_ERR_ARG.
+ * zv_filter_design is host only and needs no model and no device.  edges are bins of the 1 024-point DFT of zv_bands, with its
+ * defaults and its validation (n_bands 0 = 16; edges NULL = the default edges, then n_bands 0 or 16); gains[n_bands] are linear, >= 0
+ * and finite, else ZV_ERR_ARG ("gains"); n_taps as above; taps[n_taps] receives the result.  In f64, each tap rounded to f32 once:
+ *   m = -c .. c; w[m] = 0.5 + 0.5*cos(2*pi*m/(L+1)); lp(f)[m] = 2f at m = 0, else sin(2*pi*f*m)/(pi*m);
+ *   band b covers bins edges[b] <= k < edges[b+1], its cut-offs f_lo = max(edges[b] - 0.5, 0)/1024 and
+ *   f_hi = min(edges[b+1] - 0.5, 512)/1024 cycles per sample;
+ *   h[m+c] = [m == 0] + the sum over b, in order, of (gains[b] - 1) * (lp(f_hi)[m] - lp(f_lo)[m]) * w[m].
+ * All-ones gains give the delta filter exactly; bins outside every band keep gain 1.  The resolution is the window's: a step between
+ * neighbouring bands takes about 4096/(L+1) bins to complete — 16 bins, about 345 Hz at 22 050 Hz, at L = 255 — so the narrow
+ * low bands of the default edges cannot be set apart from their neighbours; away from the edges by that much the response is within
+ * 0.0063 times the sum of the gain steps of the gains asked for.
+ * Out of scope: filters that change inside an utterance (per phoneme, time-varying); IIR filters; resampling or any change of the
+ * output's rate or sample type; zv_vocode*, zv_vocode_stream and the encode / decode entry points. */
+typedef struct
+{
+    const float *taps;    /* [n_taps] or NULL = no filter */
+    uint32_t     n_taps;  /* odd, 1 .. 511; 0 with taps NULL */
+} zv_filter;              /* zero-initialised = none */
+zv_status zv_synthesize_filter(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                               float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                               int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                               const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch, const zv_bands *bands,
+                               const zv_filter *filter);
+zv_status zv_synthesize_batch_filter(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                     const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                                     float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                     const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                     const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                     const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch,
+                                     const zv_bands *bands, const zv_filter *filter);
+zv_status zv_synthesize_batch_begin_filter(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                           const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                           const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                           const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                           const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                           const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch,
+                                           const zv_bands *bands, const zv_filter *filter);
+zv_status zv_filter_wave(zv_model *m, const float *wav, uint32_t T, const zv_filter *filter, float *out);
+zv_status zv_filter_design(uint32_t n_bands, const uint32_t *edges, const float *gains, uint32_t n_taps, float *taps);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

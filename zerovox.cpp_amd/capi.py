@@ -30,6 +30,7 @@ SYMBOLS = [
     "zv_synthesize_contour", "zv_synthesize_batch_contour", "zv_synthesize_batch_begin_contour",
     "zv_synthesize_pitch", "zv_synthesize_batch_pitch", "zv_synthesize_batch_begin_pitch", "zv_pitch_track",
     "zv_synthesize_bands", "zv_synthesize_batch_bands", "zv_synthesize_batch_begin_bands", "zv_band_levels",
+    "zv_synthesize_filter", "zv_synthesize_batch_filter", "zv_synthesize_batch_begin_filter", "zv_filter_wave", "zv_filter_design",
 ]
 
 
@@ -347,6 +348,77 @@ def _check_bands(return_bands, where: str = ""):
     raise TypeError(f"{where}return_bands must be a bool, 'frames', 'phonemes' or a BandLevels, not {type(return_bands).__name__}")
 
 
+class FilterC(C.Structure):
+    """zv_filter of include/zerovox_amd.h: the taps' pointer, float [n_taps] or NULL = no filter, and the tap count (a zeroed struct is
+    no filter)"""
+    _fields_ = [("taps", C.c_void_p), ("n_taps", C.c_uint32)]
+
+
+class Filter:
+    """A waveform filter (include/zerovox_amd.h "waveform filter"): .taps float32 [n_taps], a linear-phase FIR whose centre tap is
+    aligned with the sample, applied on the device ahead of envelope, volume and all meters.  The library checks the values (an odd
+    count of 1 .. 511 finite taps).  Filter(None) is "no filter" (n_taps is then not looked at); from_band_gains_db designs the taps
+    from gains per band.  .struct is the zv_filter, which points into the array (kept alive here)."""
+
+    def __init__(self, taps, n_taps: Optional[int] = None):
+        if taps is None:
+            self.taps = None
+            self.n_taps = int(n_taps or 0)
+            return
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        if t.ndim != 1:
+            raise ValueError(f"Filter taps must be a 1-D sequence, got shape {t.shape}")
+        self.taps = t
+        self.n_taps = int(t.size if n_taps is None else n_taps)
+
+    @classmethod
+    def from_band_gains_db(cls, gains_db, edges=None, n_taps: int = 255):
+        """taps from a gain in dB per band (zv_filter_design): edges in bins of the 1 024-point DFT, None: the default edges of the
+        band levels (then 16 gains)"""
+        g = np.power(10.0, np.asarray(gains_db, dtype=np.float64) / 20.0).astype(np.float32)
+        return cls(filter_design(g, edges, n_taps))
+
+    @property
+    def struct(self) -> FilterC:
+        return FilterC(None if self.taps is None else self.taps.ctypes.data, self.n_taps)
+
+    def __repr__(self):
+        return f"Filter(n_taps={self.n_taps})" if self.taps is not None else "Filter(None)"
+
+
+def _filter(f, where: str = "") -> Optional[Filter]:
+    """filter= -> a Filter or None (nothing passed): a Filter, or a sequence of taps"""
+    if f is None or isinstance(f, Filter):
+        return f
+    if isinstance(f, (str, bytes, dict)):
+        raise TypeError(f"{where}filter must be a Filter, a sequence of taps or None, not {type(f).__name__}")
+    return Filter(f)
+
+
+def filter_design(gains, edges=None, n_taps: int = 255, lib=None) -> np.ndarray:
+    """zv_filter_design: linear gains per band -> float32 [n_taps]; edges: n_bands + 1 bins of the 1 024-point DFT, or None: the default
+    edges of the band levels (then 16 gains).  Host only: no model, no device."""
+    lib = lib or load_library()
+    g = np.ascontiguousarray(gains, dtype=np.float32)
+    if g.ndim != 1 or g.size == 0:
+        raise ValueError(f"filter_design: gains must be a non-empty 1-D sequence, got shape {g.shape}")
+    e = None
+    if edges is not None:
+        e = np.asarray(edges)
+        if e.ndim != 1 or e.dtype.kind not in "iu" or (e < 0).any() or (e > 0xffffffff).any():
+            raise ValueError("filter_design: edges must be a 1-D sequence of non-negative integers")
+        if e.size != g.size + 1:
+            raise ValueError(f"filter_design: edges has {e.size} entries, {g.size} gains need {g.size + 1}")
+        e = np.ascontiguousarray(e, dtype=np.uint32)
+    if isinstance(n_taps, (bool, np.bool_)) or not isinstance(n_taps, (int, np.integer)) or not 0 <= n_taps <= 0xffffffff:
+        raise ValueError(f"filter_design: n_taps = {n_taps!r} must be an integer in [0, 4294967295]")
+    taps = np.zeros(max(int(n_taps), 1), np.float32)
+    st = lib.zv_filter_design(g.size, _ptr(e), _ptr(g), int(n_taps), _ptr(taps))
+    if st != 0:
+        raise ZvError(st, lib.zv_last_error().decode("utf-8", "replace"))
+    return taps[:int(n_taps)]
+
+
 class EnvelopeC(C.Structure):
     """zv_envelope of include/zerovox_amd.h: the gains' pointer ([n] or NULL) and three integers (a zeroed struct is the identity)"""
     _fields_ = [("phoneme_gain", C.c_void_p), ("ramp_frames", C.c_uint32), ("fade_in_samples", C.c_uint32),
@@ -579,6 +651,15 @@ def load_library(path: Optional[str] = None):
         lib.zv_synthesize_batch_bands.argtypes = lib.zv_synthesize_batch_pitch.argtypes + bt
         lib.zv_synthesize_batch_begin_bands.argtypes = lib.zv_synthesize_batch_begin_pitch.argtypes + bt
         lib.zv_band_levels.argtypes = [vp, vp, C.c_uint32, C.POINTER(BandsC)]
+    # the filter forms: the _bands argument lists and the waveform filter (zv_filter, batches [n_utt]) or NULL; the stand-alone filter
+    # and the design
+    if hasattr(lib, "zv_synthesize_filter"):
+        ft = [C.POINTER(FilterC)]
+        lib.zv_synthesize_filter.argtypes = lib.zv_synthesize_bands.argtypes + ft
+        lib.zv_synthesize_batch_filter.argtypes = lib.zv_synthesize_batch_bands.argtypes + ft
+        lib.zv_synthesize_batch_begin_filter.argtypes = lib.zv_synthesize_batch_begin_bands.argtypes + ft
+        lib.zv_filter_wave.argtypes = [vp, vp, C.c_uint32, C.POINTER(FilterC), vp]
+        lib.zv_filter_design.argtypes = [C.c_uint32, vp, vp, C.c_uint32, vp]
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -653,7 +734,7 @@ def _check_target(target, T):
 
 
 def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None, volume=None, levels=None,
-                  envelope=None, contour=None, pitch=None, bands=None):
+                  envelope=None, contour=None, pitch=None, bands=None, filter=None):
     """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
     name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status.
     fitted: name_fitted, which takes everything (NULL for what the call lacks).  target (a frame count, or the batches' uint32
@@ -663,7 +744,12 @@ def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, 
     contour (a zv_contour, or the batches' array): name_contour, which takes everything the _envelope form takes and the contour;
     only a call that asks for a contour goes there.  pitch (a zv_pitch, or the batches' array): name_pitch, which takes everything the
     _contour form takes and the pitch track; only a call that asks for a pitch track goes there.  bands (a zv_bands, or the batches'
-    array): name_bands, which takes everything the _pitch form takes and the band levels; only a call that asks for them goes there"""
+    array): name_bands, which takes everything the _pitch form takes and the band levels; only a call that asks for them goes there.
+    filter (a zv_filter, or the batches' array): name_filter, which takes everything the _bands form takes and the filter; only a call
+    that passes a filter goes there"""
+    if filter is not None:
+        return getattr(lib, name + "_filter")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour,
+                                              pitch, bands, filter)
     if bands is not None:
         return getattr(lib, name + "_bands")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour,
                                              pitch, bands)
@@ -864,7 +950,7 @@ class Model:
 
     def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False,
                    fitted: bool = False, target_frames: Optional[int] = None, *, volume=None, return_levels: bool = False,
-                   envelope=None, return_contour=False, return_pitch=False, return_bands=False):
+                   envelope=None, return_contour=False, return_pitch=False, return_bands=False, filter=None):
         """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
         arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
         as a third element.  fitted: zv_synthesize_fitted — T is a capacity, the utterance is decoded and vocoded as the n_frames
@@ -880,7 +966,10 @@ class Model:
         return_pitch (False, True, "frames", "phonemes" or a PitchTrack): zv_synthesize_pitch — the fundamental frequency and voicing
         of every frame and / or every phoneme of the returned waveform, metered on the device; adds a Pitch as the last element.
         return_bands (False, True, "frames", "phonemes" or a BandLevels): zv_synthesize_bands — the level per frequency band of every
-        frame and / or every phoneme of the returned waveform, metered on the device; adds a Bands as the last element"""
+        frame and / or every phoneme of the returned waveform, metered on the device; adds a Bands as the last element.
+        filter (a Filter, a sequence of taps or None): zv_synthesize_filter — a linear-phase FIR applied to the waveform on the device,
+        ahead of envelope, volume and all meters"""
+        flt = _filter(filter)
         want_frames, want_phonemes = _check_contour(return_contour)
         track = _check_pitch(return_pitch)
         spec = _check_bands(return_bands)
@@ -900,17 +989,32 @@ class Model:
         contour = Contour(T, len(ids), want_frames, want_phonemes) if want_frames or want_phonemes else None
         pitch = Pitch(T, len(ids), track) if track is not None else None
         bands = Bands(T, len(ids), spec) if spec is not None else None
-        if (level is not None or env is not None or contour is not None or pitch is not None or bands is not None) and target is None:
-            target = 0                       # the _volume, _envelope, _contour, _pitch and _bands forms take a count, 0 = none
+        if (level is not None or env is not None or contour is not None or pitch is not None or bands is not None or flt is not None) and target is None:
+            target = 0                       # the _volume, _envelope, _contour, _pitch, _bands and _filter forms take a count, 0 = none
         self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur),
                                 fitted, target, _ref(vol), _ref(level), _ref(None if env is None else env.struct),
                                 _ref(None if contour is None else contour.struct), _ref(None if pitch is None else pitch.struct),
-                                _ref(None if bands is None else bands.struct)))
+                                _ref(None if bands is None else bands.struct), _ref(None if flt is None else flt.struct)))
         out = (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
         out = out + (level,) if return_levels else out
         out = out + (contour,) if contour is not None else out
         out = out + (pitch,) if pitch is not None else out
         return out + (bands,) if bands is not None else out
+
+    def filter_wave(self, wav, filter) -> np.ndarray:
+        """zv_filter_wave: a waveform the caller brings (float32 [T * hop] at the model's hop) through the filter (a Filter or a
+        sequence of taps) on the device; returns the filtered waveform"""
+        flt = _filter(filter)
+        if flt is None:
+            raise TypeError("filter_wave: filter must be a Filter or a sequence of taps, not None")
+        w = np.ascontiguousarray(wav, dtype=np.float32)
+        hop = self.hp.audio_hop_size
+        if w.ndim != 1 or w.size == 0 or w.size % hop:
+            raise ValueError(f"filter_wave: the waveform must be a non-empty 1-D array of a multiple of {hop} samples, got shape {w.shape}")
+        out = np.empty_like(w)
+        st = flt.struct
+        self._chk(self.lib.zv_filter_wave(self.h, _ptr(w), w.size // hop, C.byref(st), _ptr(out)))
+        return out
 
     def band_levels(self, wav, params=None) -> Bands:
         """zv_band_levels: the band levels of a waveform the caller brings (float32 [T * hop] at the model's rate and hop), frames
@@ -946,15 +1050,16 @@ class Model:
 
     def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
                       return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False,
-                      return_bands=False) -> "BatchCall":
+                      return_bands=False, filter=None) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
         buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list.  fitted: the
         zv_synthesize_batch_fitted / _begin_fitted entry points (the lane form: .begin(lane) / .end(lane))"""
         return BatchCall(self, utterances, durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
-                         return_contour=return_contour, return_pitch=return_pitch, return_bands=return_bands)
+                         return_contour=return_contour, return_pitch=return_pitch, return_bands=return_bands, filter=filter)
 
     def synthesize_batch(self, utterances, return_durations: bool = False, fitted: bool = False, *, volume=None,
-                         return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False, return_bands=False):
+                         return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False, return_bands=False,
+                         filter=None):
         """utterances: list of (ids, puncts, style, T[, prosody[, phonemes[, target_frames]]]) -> list of (wav, n_frames); each
         utterance keeps its own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its
         per-phoneme controls (PhonemeControls, dict of arrays or None), with a seventh its target frame count (None / 0: none).  return_durations: (wav, n_frames, durations) tuples.  fitted:
@@ -965,9 +1070,10 @@ class Model:
         them per utterance — zv_synthesize_batch_contour; every tuple gains the utterance's Contour (None where it asked for none) as
         its last element.  return_pitch: False, True, "frames", "phonemes" or a PitchTrack for the whole batch, or a list with one of
         them per utterance — zv_synthesize_batch_pitch; every tuple gains the utterance's Pitch (None where it asked for none) last.
-        return_bands: likewise with a BandLevels — zv_synthesize_batch_bands; every tuple gains the utterance's Bands last"""
+        return_bands: likewise with a BandLevels — zv_synthesize_batch_bands; every tuple gains the utterance's Bands last.
+        filter: a list with a Filter, a sequence of taps or None per utterance — zv_synthesize_batch_filter"""
         call = BatchCall(self, utterances, return_durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
-                         return_contour=return_contour, return_pitch=return_pitch, return_bands=return_bands)
+                         return_contour=return_contour, return_pitch=return_pitch, return_bands=return_bands, filter=filter)
         call.run()
         res = call.results()
         if return_durations:
@@ -1071,11 +1177,20 @@ class BatchCall:
     where it asked for none); set_pitch() rewrites an entry's parameters and tables for the next run() / begin().
     return_bands (False, True, "frames", "phonemes" or a BandLevels for the whole batch, or a list with one of them per utterance): where
     any utterance asks for a table, the _bands entry points, with the zv_bands array .band; .bands[i] is utterance i's Bands (None where
-    it asked for none); set_bands() rewrites an entry's band count, edges and tables for the next run() / begin()."""
+    it asked for none); set_bands() rewrites an entry's band count, edges and tables for the next run() / begin().
+    filter (a list with a Filter, a sequence of taps or None per utterance): the _filter entry points, with the zv_filter array .filter;
+    set_filter() rewrites an entry's taps for the next run() / begin()."""
 
     def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
-                 return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False, return_bands=False):
+                 return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False, return_bands=False, filter=None):
         self.fitted = _check_fitted(fitted, [u[3] for u in utterances])
+        self.filter = self.fkeep = None
+        if filter is not None:
+            flts = list(filter)
+            if len(flts) != len(utterances):
+                raise ValueError(f"filter has {len(flts)} entries, the batch has {len(utterances)} utterances")
+            self.fkeep = [_filter(f, f"utterance {i}: ") for i, f in enumerate(flts)]
+            self.filter = (FilterC * len(utterances))(*[f.struct if f is not None else FilterC() for f in self.fkeep])
         if isinstance(return_bands, (list, tuple)):
             if len(return_bands) != len(utterances):
                 raise ValueError(f"return_bands has {len(return_bands)} entries, the batch has {len(utterances)} utterances")
@@ -1202,6 +1317,14 @@ class BatchCall:
         self.bands[i] = Bands(int(self.Ts[i]), int(self.Ns[i]), t) if t is not None else None
         self.band[i] = self.bands[i].struct if t is not None else BandsC()
 
+    def set_filter(self, i: int, filter):
+        """utterance i's filter (a Filter, a sequence of taps or None: none) for the following run() / begin() (the call must have been
+        built with filter=)"""
+        if self.filter is None:
+            raise ValueError("this BatchCall was built without filters")
+        self.fkeep[i] = _filter(filter, f"utterance {i}: ")
+        self.filter[i] = self.fkeep[i].struct if self.fkeep[i] is not None else FilterC()
+
     def set_prosody(self, i: int, prosody):
         """utterance i's controls for the following run() / begin() (the call must have been built with controls)"""
         if self.prosody is None:
@@ -1212,14 +1335,14 @@ class BatchCall:
         m = self.model
         args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope, self.contour, self.pitch, self.band))
+                             self.volume, self.levels, self.envelope, self.contour, self.pitch, self.band, self.filter))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
         args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
         m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope, self.contour, self.pitch, self.band))
+                             self.volume, self.levels, self.envelope, self.contour, self.pitch, self.band, self.filter))
 
     def end(self, lane: int):
         m = self.model

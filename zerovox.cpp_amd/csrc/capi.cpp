@@ -173,7 +173,17 @@ struct Request
     const zv_pitch            *pitch = nullptr;
     // band levels (zv_*_bands): [count] or null; each struct's tables are [T[u]][n_bands] and [n[u]][n_bands] or null
     const zv_bands            *bands = nullptr;
+    // waveform filter (zv_*_filter): [count] or null; each struct's taps are [n_taps] or null = no filter for that utterance
+    const zv_filter           *filter = nullptr;
 
+    // any utterance with a filter: then every utterance gets a parameter row (n_taps = 0 where it has none: its bits are copied), the
+    // vocoder writes the filter-input region and the filter pass writes the waveform
+    bool filters() const
+    {
+        for (uint32_t u = 0; filter && u < count; u++)
+            if (filter[u].taps) return true;
+        return false;
+    }
     // any utterance that asks for a table of its band levels: then the rows of every utterance that asks are written on the device (an
     // utterance that asks for none is skipped by both passes: its parameter row says n_bands = 0), and the host downloads the tables
     bool band_levels() const
@@ -248,6 +258,7 @@ struct Request
         if (contour) s.contour += a;
         if (pitch) s.pitch += a;
         if (bands) s.bands += a;
+        if (filter) s.filter += a;
         return s;
     }
 };
@@ -349,6 +360,23 @@ static void pack_bands(const Request &r, uint32_t *par, uint32_t *nb)
     }
 }
 
+// a zv_filter's checks (filter.h filter_check), or ZV_ERR_ARG naming the field
+static void check_filter(const zv_filter &f)
+{
+    if (const char *field = zv::filter_check(f.taps, f.n_taps))
+    {
+        if (!strcmp(field, "n_taps"))
+            zv::fail(ZV_ERR_ARG, "filter n_taps = %u must be odd and in 1 .. %u", f.n_taps, zv::FILTER_MAX_TAPS);
+        zv::fail(ZV_ERR_ARG, "filter taps holds a value that is not finite");
+    }
+}
+
+// a request's filter rows in the kernel's layout (filter.h FILTER_PARAM_STRIDE); an utterance without a filter gets n_taps = 0
+static void pack_filter(const Request &r, uint32_t *par)
+{
+    for (uint32_t u = 0; u < r.count; u++) zv::filter_pack(r.filter[u].taps, r.filter[u].n_taps, par + (size_t)u * zv::FILTER_PARAM_STRIDE);
+}
+
 static void check_envelope(const zv_envelope &e, uint32_t n)
 {
     for (uint32_t i = 0; e.phoneme_gain && i < n; i++)
@@ -431,6 +459,7 @@ static void check_request(zv_model *m, const Request &r)
                 uint32_t row[zv::BANDS_PARAM_STRIDE];
                 resolve_bands(r.bands[u], row);
             }
+            if (r.filter) check_filter(r.filter[u]);
             if (r.target_frames && r.target_frames[u] > r.T[u])
                 zv::fail(ZV_ERR_ARG, "target_frames = %u exceeds the capacity T = %u", r.target_frames[u], r.T[u]);
             if (tg && r.n[u] > (uint32_t)zv::FIT_MAX_TOKENS)      // one launch covers the request's utterances, with or without a target
@@ -515,7 +544,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const size_t E = M.E(), b_ids = (size_t)n * 4, b_hid = (size_t)T * E * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
         const size_t b_ctl = r.prosody || tg ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
         const bool vol = r.volumes() && !taps, env = r.envelopes() && !taps, ctr = r.contours() && !taps, pit = r.pitches() && !taps,
-                   bnd = r.band_levels() && !taps;
+                   bnd = r.band_levels() && !taps, flt = r.filters() && !taps;
         const void *bnd_table = bnd ? M.bands_table() : nullptr;      // (allocates and copies on first use: ahead of everything enqueued)
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
@@ -541,6 +570,8 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const size_t b_bfr = (size_t)T * zv::BANDS_ROW_STRIDE * 4, b_bph = (size_t)n * zv::BANDS_ROW_STRIDE * 4;
         const size_t o_bfr = L.at(bnd ? b_bfr : 0), o_bph = L.at(bnd ? b_bph : 0), o_bsl = L.at(bnd ? 2 * b_bfr : 0),
                      o_bpar = L.at(bnd ? zv::BANDS_PARAM_STRIDE * 4 : 0);
+        // [parameter row] (waveform filter: uploaded; the last region)
+        const size_t o_fpar = L.at(flt ? zv::FILTER_PARAM_STRIDE * 4 : 0);
         char *io = (char *)M.io_scratch(L.size());
         int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
@@ -587,6 +618,7 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         }
         uint32_t prow[zv::PITCH_PARAM_STRIDE];                       // host staging, like ctl
         uint32_t brow[zv::BANDS_PARAM_STRIDE];                       // likewise
+        std::vector<uint32_t> frow(flt ? zv::FILTER_PARAM_STRIDE : 0);      // likewise
         int32_t nf = 0;
         if (taps)
         {
@@ -620,6 +652,12 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
                 bt.d_bnd_par = (const uint32_t *)(io + o_bpar);
                 bt.d_bnd_table = bnd_table;
                 ZV_HIP(hipMemcpyAsync(io + o_bpar, brow, sizeof(brow), hipMemcpyHostToDevice, M.stream()));
+            }
+            if (flt)
+            {
+                pack_filter(r, frow.data());
+                bt.d_flt_par = (const uint32_t *)(io + o_fpar);
+                ZV_HIP(hipMemcpyAsync(io + o_fpar, frow.data(), frow.size() * 4, hipMemcpyHostToDevice, M.stream()));
             }
             if (pit)
             {
@@ -907,7 +945,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
     const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings(), vol = r.volumes(),
-               env = r.envelopes(), ctr = r.contours(), pit = r.pitches(), bnd = r.band_levels();
+               env = r.envelopes(), ctr = r.contours(), pit = r.pitches(), bnd = r.band_levels(), flt = r.filters();
     const void *bnd_table = bnd ? M.bands_table() : nullptr;      // (allocates and copies on first use: ahead of everything enqueued)
     uint32_t nmax = 0, tmax = 0, ntot = 0;
     for (uint32_t u = 0; u < r.count; u++)
@@ -938,6 +976,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
                  i_env = in.at(env ? (size_t)bt.nseg * zv::ENV_CTL_STRIDE * 4 : 0),
                  i_ppar = in.at(pit ? (size_t)bt.nseg * zv::PITCH_PARAM_STRIDE * 4 : 0),      // pitch track: a parameter row per utterance, likewise
                  i_bpar = in.at(bnd ? (size_t)bt.nseg * zv::BANDS_PARAM_STRIDE * 4 : 0),      // band levels: likewise
+                 i_fpar = in.at(flt ? (size_t)bt.nseg * zv::FILTER_PARAM_STRIDE * 4 : 0),     // waveform filter: a row of tap count and taps per utterance, likewise
                  b_in = in.size();
     // device block: [frame counts][input block][hidden][mel][wav][scan] (scan: only when timings are asked for, the length
     // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
@@ -1011,6 +1050,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
             memset(h_in + i_bpar, 0, (size_t)bt.nseg * zv::BANDS_PARAM_STRIDE * 4);      // (segments past the utterances ask for nothing)
             pack_bands(r, (uint32_t *)(h_in + i_bpar), pb.bands_nb.data());
         }
+        if (flt) pack_filter(r, (uint32_t *)(h_in + i_fpar));
     }
     bt.d_tok = (const zv::Seg *)(d_in + i_tok);
     bt.d_frm = (const zv::Seg *)(d_in + i_frm);
@@ -1037,6 +1077,11 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         bt.d_pit_frames = (zv::PitchFrameRow *)(io + o_pfr);
         bt.d_pit_phonemes = (zv::PitchPhonemeRow *)(io + o_pph);
         bt.d_pit_par = (const uint32_t *)(d_in + i_ppar);
+    }
+    if (flt)
+    {
+        bt.d_flt_par = (const uint32_t *)(d_in + i_fpar);
+        M.reserve_batch(bt);       // the arena with the filter-input region (Model::voc_layout), ahead of everything enqueued
     }
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
     if (M.dec_plan(bt).runs) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
@@ -1566,6 +1611,92 @@ zv_status zv_synthesize_batch_begin_bands(zv_model *m, uint32_t lane, uint32_t n
 {
     return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
                                  durations, fitted != 0, target_frames, volume, levels, envelope, contour, pitch, bands});
+}
+
+// The filter forms: the _bands requests plus the waveform filter (NULL, or no taps anywhere: the request of the _bands call).
+zv_status zv_synthesize_filter(zv_model *m, const int32_t *ids, const int32_t *puncts, const float *style, uint32_t n, uint32_t T,
+                               float *wav, uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                               int32_t *durations, uint32_t target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                               const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch, const zv_bands *bands,
+                               const zv_filter *filter)
+{
+    return run_single(m, {__func__, 1, &ids, &puncts, &style, &n, &n, &T, &wav, n_frames, prosody, phonemes, &durations, fitted != 0,
+                          &target_frames, volume, levels, envelope, contour, pitch, bands, filter});
+}
+
+zv_status zv_synthesize_batch_filter(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                                     const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *wav,
+                                     uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                                     int32_t *const *durations, const uint32_t *target_frames, int fitted, const zv_volume *volume,
+                                     zv_level *levels, const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch,
+                                     const zv_bands *bands, const zv_filter *filter)
+{
+    return synthesize_batch(m, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                durations, fitted != 0, target_frames, volume, levels, envelope, contour, pitch, bands, filter});
+}
+
+zv_status zv_synthesize_batch_begin_filter(zv_model *m, uint32_t lane, uint32_t n_utt, const int32_t *const *ids,
+                                           const int32_t *const *puncts, const float *const *styles, const uint32_t *n_phonemes,
+                                           const uint32_t *T, float *const *wav, uint32_t *n_frames, const zv_prosody *prosody,
+                                           const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                                           const uint32_t *target_frames, int fitted, const zv_volume *volume, zv_level *levels,
+                                           const zv_envelope *envelope, const zv_contour *contour, const zv_pitch *pitch,
+                                           const zv_bands *bands, const zv_filter *filter)
+{
+    return begin_batch(m, lane, {__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, wav, n_frames, prosody, phonemes,
+                                 durations, fitted != 0, target_frames, volume, levels, envelope, contour, pitch, bands, filter});
+}
+
+// The stand-alone filter: a host waveform through the filter pass, eagerly, on lane 0, as one inline segment.  Input and output have
+// regions of their own in the I/O block, so out may be wav.
+zv_status zv_filter_wave(zv_model *m, const float *wav, uint32_t T, const zv_filter *filter, float *out)
+{
+    return guarded([&] {
+        if (!(m && wav && filter && out)) zv::fail(ZV_ERR_ARG, "zv_filter_wave: null argument");
+        Model &M = *m->m;
+        try
+        {
+            check_T(M, T);
+            check_filter(*filter);
+        }
+        catch (const zv::Error &e)
+        {
+            zv::fail(e.status, "zv_filter_wave: %s", e.what());
+        }
+        use_lane0(m);
+        const size_t hop = M.hp.audio_hop_size, b_wav = (size_t)T * hop * 4;
+        std::vector<uint32_t> frow(zv::FILTER_PARAM_STRIDE);
+        zv::filter_pack(filter->taps, filter->n_taps, frow.data());
+        Layout L;
+        const size_t o_in = L.at(b_wav), o_out = L.at(b_wav), o_par = L.at(frow.size() * 4);
+        char *io = (char *)M.io_scratch(L.size());
+        ZV_HIP(hipMemcpyAsync(io + o_in, wav, b_wav, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_par, frow.data(), frow.size() * 4, hipMemcpyHostToDevice, M.stream()));
+        const zv::Segs one{nullptr, 1, (int)T, zv::Seg{0, (int32_t)T, 0, 0}};
+        ZV_HIP(zv::launch_filter(M.stream(), (const float *)(io + o_in), (float *)(io + o_out), (const uint32_t *)(io + o_par), one, one, (int)hop));
+        ZV_HIP(hipMemcpyAsync(out, io + o_out, b_wav, hipMemcpyDeviceToHost, M.stream()));
+        M.sync();
+    });
+}
+
+// The design: host only, no model, no device (filter.h filter_design).
+zv_status zv_filter_design(uint32_t n_bands, const uint32_t *edges, const float *gains, uint32_t n_taps, float *taps)
+{
+    return guarded([&] {
+        if (!(gains && taps)) zv::fail(ZV_ERR_ARG, "zv_filter_design: null argument");
+#if !defined(__HIP_DEVICE_COMPILE__)      // (filter.h keeps its host half out of device passes)
+        if (const char *field = zv::filter_design(n_bands, edges, gains, n_taps, taps))
+        {
+            if (!strcmp(field, "n_bands")) zv::fail(ZV_ERR_ARG, "zv_filter_design: n_bands = %u exceeds %u", n_bands, zv::FILTER_BANDS_MAX);
+            if (!strcmp(field, "n_taps")) zv::fail(ZV_ERR_ARG, "zv_filter_design: n_taps = %u must be odd and in 1 .. %u", n_taps, zv::FILTER_MAX_TAPS);
+            if (!strcmp(field, "gains")) zv::fail(ZV_ERR_ARG, "zv_filter_design: gains holds a value that is negative or not finite");
+            if (!edges)
+                zv::fail(ZV_ERR_ARG, "zv_filter_design: edges = NULL (the default edges) needs n_bands 0 or %u, got %u", zv::FILTER_BANDS_DEFAULT, n_bands);
+            zv::fail(ZV_ERR_ARG, "zv_filter_design: edges must ascend strictly and end at or below %d (edges[n_bands] = %u)", zv::FILTER_DFT / 2 + 1,
+                     edges[n_bands ? n_bands : zv::FILTER_BANDS_DEFAULT]);
+        }
+#endif
+    });
 }
 
 // The stand-alone meter: a host waveform through the frames pass, eagerly, on lane 0, as one inline segment.

@@ -18,6 +18,7 @@
 #include "contour.h"      // level contour: CONTOUR_CHUNK_FRAMES, ContourRow
 #include "pitch.h"        // pitch track: PITCH_CHUNK_FRAMES, PITCH_PARAM_STRIDE, the rows
 #include "bands.h"        // band levels: BANDS_TILE_FRAMES, BANDS_PARAM_STRIDE, BANDS_ROW_STRIDE
+#include "filter.h"       // waveform filter: FILTER_TILE, FILTER_PARAM_STRIDE
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -475,5 +476,13 @@ hipError_t launch_bands_frames(hipStream_t s, const float *wav, const void *tabl
                                int hop);
 hipError_t launch_bands_phonemes(hipStream_t s, const int32_t *cum, const void *slab, float *rows, const uint32_t *par, const Segs &tokens,
                                  const Segs &frames);
+
+// ---- waveform filter (include/zerovox_amd.h "waveform filter", filter.h): one pass behind the output conv and ahead of the envelope,
+// from `in` to `out` (never in place; both indexed like the waveform, by ABSOLUTE frame row times hop).  `frames` is the CAPACITY table
+// or inline segment, `live` the table of the frames the vocoder ran over (the capacity again where the call is not fitted).  par
+// [segments][FILTER_PARAM_STRIDE]: each segment's row (filter_pack), read at run time.  Per segment, with S = min(live rows, capacity
+// rows) * hop: n_taps == 0 copies the capacity bit for bit; else out[0 .. S) is the rule over in[0 .. S) and out[S .. capacity) is
+// +0.0.  Nothing outside the segment's own span [row0 * hop, row0 * hop + S) is read.
+hipError_t launch_filter(hipStream_t s, const float *in, float *out, const uint32_t *par, const Segs &frames, const Segs &live, int hop);
 
 }  // namespace zv

@@ -10,4 +10,5 @@
 #include "contour_kernels.hip"        // level contour
 #include "pitch_kernels.hip"          // pitch track
 #include "bands_kernels.hip"          // band levels
+#include "filter_kernels.hip"         // waveform filter
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

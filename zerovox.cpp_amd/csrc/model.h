@@ -127,6 +127,11 @@ struct Batch
     unsigned long long *d_bnd_slab = nullptr;
     const uint32_t     *d_bnd_par = nullptr;
     const void         *d_bnd_table = nullptr;
+    // Waveform filter (include/zerovox_amd.h "waveform filter", filter.h): the parameter rows, uint32 [nseg][FILTER_PARAM_STRIDE], packed
+    // on the host and uploaded with the call (the VALUES, tap counts included, are read at run time), or null: no filter.  Keyed like
+    // d_vol: with it the vocoder's last convolution writes the filter-input region of the arena (VocLayout::filter_in, carved only
+    // then) and one launch more, ahead of the envelope's, writes the waveform.
+    const uint32_t     *d_flt_par = nullptr;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -159,7 +164,7 @@ struct Batch
                d_env == o.d_env && d_ctr_frames == o.d_ctr_frames && d_ctr_phonemes == o.d_ctr_phonemes &&
                d_pit_frames == o.d_pit_frames && d_pit_phonemes == o.d_pit_phonemes && d_pit_par == o.d_pit_par &&
                d_bnd_frames == o.d_bnd_frames && d_bnd_phonemes == o.d_bnd_phonemes && d_bnd_slab == o.d_bnd_slab && d_bnd_par == o.d_bnd_par &&
-               d_bnd_table == o.d_bnd_table;
+               d_bnd_table == o.d_bnd_table && d_flt_par == o.d_flt_par;
     }
 };
 
@@ -382,7 +387,7 @@ class Model
     //     arena_require a stage issues inside the capture asks for the same bytes; no layout shrinks when a capacity grows, so a
     //     sub-batch (vocode_tail) or a Batch that has gained d_cum never asks for more than the reservation did;
     //   * vocode_tail (part 2 of a split batch) sees the layout the head (part 1) carved: voc_layout reads t_rows alone, but for the
-    //     size of its last carve (the run table).
+    //     size of its last carve (the run table) and whether the batch carries a filter, which a sub-batch keeps.
     struct VocLayout
     {
         float *c0;
@@ -400,6 +405,9 @@ class Model
         void *contour_slab;
         // pitch track (kernels.h launch_pitch_frames): {Fq, voiced} per frame row, 8 bytes each, t_rows entries, carved likewise
         void *pitch_slab;
+        // waveform filter (kernels.h launch_filter): the vocoder's waveform ahead of the filter, t_rows * hop floats indexed like the
+        // waveform, carved likewise and only where the batch carries a filter (Batch::d_flt_par); null otherwise
+        float *filter_in;
         float *mel_c; int32_t *eq; Seg *runs;
     };
     // entries of VocLayout::level_slab: >= nseg * level_chunks(t_max, hop) for every Batch with nseg * t_max <= t_rows, a sub-batch included

@@ -74,6 +74,8 @@ Model::VocLayout Model::voc_layout(DeviceArena &a, const Batch &bt) const
     v.env_knots = a.take_n<uint32_t>(env_knot_entries(bt));
     v.contour_slab = a.take(bt.t_rows * 16);
     v.pitch_slab = a.take(bt.t_rows * sizeof(PitchSlabRow));
+    // the filter's input: the one region that exists only where a call asks for it (a waveform's worth of arena)
+    v.filter_in = bt.d_flt_par ? a.take_n<float>(bt.t_rows * hp.audio_hop_size) : nullptr;
     v.runs = a.take_n<Seg>(bt.nseg);
     return v;
 }
@@ -115,6 +117,7 @@ void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g
     if (bt.d_nframes) sub.d_nframes = bt.d_nframes + g0;
     if (bt.d_pit_par) sub.d_pit_par = bt.d_pit_par + (size_t)g0 * PITCH_PARAM_STRIDE;      // (the rows go by absolute frame / token row)
     if (bt.d_bnd_par) sub.d_bnd_par = bt.d_bnd_par + (size_t)g0 * BANDS_PARAM_STRIDE;      // (likewise)
+    if (bt.d_flt_par) sub.d_flt_par = bt.d_flt_par + (size_t)g0 * FILTER_PARAM_STRIDE;     // (likewise)
     if (bt.d_env) sub.d_env = bt.d_env + (size_t)g0 * ENV_CTL_STRIDE;          // (the gains and the scan go by absolute token row)
     sub.nseg = cnt;
     vocode_group(sub, d_mel, d_wav, 2, g0);
@@ -426,6 +429,11 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
 
     // V3: (sum of branches)/3 -> leaky_relu(0.01) -> conv k7 (C -> 1) + b -> tanh          (:315-345)
     skip_launch_ = part == 1;
+    // Waveform filter (filter.h): with a request the convolution, the fill and the fitted tail's zeros go to the filter-input region
+    // and the filter writes d_wav, so nothing behind it changes.  Never under a one-layer tap.
+    const bool filtered = bt.d_flt_par && dbg_layer.kind < 0;
+    float *const wav_out = d_wav;
+    if (filtered) d_wav = lay.filter_in;
     {
         OutConvArgs a;
         a.x0 = prev_merged ? prev_merged : prev_y[0];
@@ -456,6 +464,17 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         if (dbg_layer.kind == ZV_LAYER_VOC_OUTPUT) dbg_extract(d_wav, 1, 1, L);
         // fitted: the output conv stops at each utterance's last frame; the rest of its capacity is silence
         if (bt.d_frm_live) ZV_LAUNCH("voc_zero_tail", 4.0 * La, 0.0, launch_zero_tail(stream(), d_wav, 1, bt.frames_cap(), fr, rate));
+    }
+    if (filtered)
+    {
+        if (!lay.filter_in) fail(ZV_ERR_DEVICE, "internal: a filter without its input region");
+        const Segs cap = bt.frames_cap();
+        const double cap_samples = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg) * rate;
+        // algorithmic bytes: the capacity read and written once.  Operations, by capacity and at 255 taps (the counts are the device's: a
+        // caller's taps change the work, not this price): 2 per multiply-add.
+        ZV_LAUNCH("voc_filter", 8.0 * cap_samples, 2.0 * 255.0 * cap_samples,
+                  launch_filter(stream(), lay.filter_in, wav_out, bt.d_flt_par, cap, bt.frames(), rate));
+        d_wav = wav_out;
     }
 
     // Amplitude envelope (envelope.h): the waveform of these segments is final, so build the knots from the regulator's scan and scale

@@ -159,6 +159,10 @@ class ZeroVOXModel
     const std::vector<float> &get_band_frames() const { return band_frame_rows; }           // [max_seq_len][bands], empty unless asked for
     const std::vector<float> &get_band_phonemes() const { return band_phoneme_rows; }       // [num_phonemes][bands], likewise
 
+    // waveform filter (include/zerovox_amd.h "waveform filter") for the eval() calls that follow: n_taps taps of a linear-phase FIR,
+    // copied here, applied on the device ahead of envelope, volume and every meter; nullptr: none.  They are checked when eval() runs.
+    void set_filter(const float *taps, uint32_t n_taps);
+
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
     uint32_t     get_num_frames() const { return n_frames; }
@@ -200,6 +204,9 @@ class ZeroVOXModel
     uint32_t             band_count = 0;
     std::vector<uint32_t> band_edges;
     std::vector<float>   band_frame_rows, band_phoneme_rows;
+    bool                 has_filter = false;
+    uint32_t             filter_n = 0;
+    std::vector<float>   filter_taps;
 };
 
 }  // namespace ZeroVOX

@@ -190,6 +190,15 @@ std::vector<uint32_t> ZeroVOXModel::get_band_edges() const
     return std::vector<uint32_t>(zv::BANDS_DEFAULT_EDGES, zv::BANDS_DEFAULT_EDGES + zv::BANDS_DEFAULT + 1);
 }
 
+void ZeroVOXModel::set_filter(const float *taps, uint32_t n_taps)
+{
+    has_filter = taps != nullptr;
+    filter_n = n_taps;
+    // (a count the library will refuse copies one tap: eval() reports it)
+    if (taps) filter_taps.assign(taps, taps + (n_taps >= 1 && n_taps <= 511 ? n_taps : 1));
+    else filter_taps.clear();
+}
+
 void ZeroVOXModel::set_envelope(const zv_envelope *e, uint32_t n)
 {
     has_envelope = e != nullptr;
@@ -213,7 +222,8 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
     const size_t band_w = band_count && band_count <= zv::BANDS_MAX ? band_count : zv::BANDS_DEFAULT;
     band_frame_rows.assign(band_frames ? (size_t)hparams.max_seq_len * band_w : 0, 0.0f);
     band_phoneme_rows.assign(band_phonemes ? (size_t)num_phonemes * band_w : 0, 0.0f);
-    if (has_volume || has_envelope || contour_frames || contour_phonemes || pitch_frames || pitch_phonemes || band_frames || band_phonemes)
+    if (has_volume || has_envelope || contour_frames || contour_phonemes || pitch_frames || pitch_phonemes || band_frames || band_phonemes ||
+        has_filter)
     {
         // the volume, envelope and contour forms take what every other form takes (the finished waveform of the one-pass chain is scaled and measured)
         if (has_phonemes && pc_n != num_phonemes)
@@ -225,6 +235,20 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
         const zv_envelope env = {env_gain_set ? env_gain.data() : nullptr, envelope.ramp_frames, envelope.fade_in_samples,
                                  envelope.fade_out_samples};
         const zv_contour ctr = {contour_frames ? frame_levels.data() : nullptr, contour_phonemes ? phoneme_levels.data() : nullptr};
+        if (has_filter)
+        {
+            zv_pitch pit = pitch_params;
+            pit.frames = pitch_frames ? pitch_frame_rows.data() : nullptr;
+            pit.phonemes = pitch_phonemes ? pitch_phoneme_rows.data() : nullptr;
+            const zv_bands bnd = {band_frames ? band_frame_rows.data() : nullptr, band_phonemes ? band_phoneme_rows.data() : nullptr, band_count,
+                                  band_edges.empty() ? nullptr : band_edges.data()};
+            const zv_filter flt = {filter_taps.data(), filter_n};
+            chk(zv_synthesize_filter(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
+                                     has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
+                                     has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr, &ctr, &pit, &bnd,
+                                     &flt));
+            return;
+        }
         if (band_frames || band_phonemes)
         {
             zv_pitch pit = pitch_params;

@@ -59,6 +59,13 @@
 //            ascending values) become bins of the 1 024-point transform on the host, round(hz * 1024 / rate); without them the
 //            library's 16 default bands.  Edges that are not ascending positive numbers, or that come without a file, are a usage
 //            error; edges that fall on the same bin after rounding are refused once the checkpoint's rate is known.
+//   --eq-gain-db g0,g1,..., --eq-edges-hz a,b,c,..., --eq-taps L, --filter-taps FILE
+//            waveform filter (include/zerovox_amd.h "waveform filter"): a linear-phase FIR applied on the device ahead of the envelope,
+//            the volume controls and every meter above.  --eq-gain-db gives a gain in dB per band (1 .. 64 finite numbers; without
+//            --eq-edges-hz 16 of them, for the default bands of --bands); --eq-edges-hz the bands' edges, converted like
+//            --band-edges-hz; --eq-taps the tap count (odd, 1 .. 511, default 255).  The taps come from zv_filter_design.
+//            --filter-taps FILE reads the taps themselves, one per line, and excludes the other three.  A malformed value, a gain
+//            count that does not match the bands, or edges / a tap count without gains are usage errors; the library checks the taps.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
 #include <algorithm>
 #include <cmath>
@@ -86,6 +93,7 @@ static void usage(FILE *f)
                "               [--contour FILE] [--phoneme-levels FILE]\n"
                "               [--pitch FILE] [--phoneme-pitch FILE] [--pitch-min-hz F] [--pitch-max-hz F] [--pitch-threshold X]\n"
                "               [--bands FILE] [--phoneme-bands FILE] [--band-edges-hz a,b,c,...]\n"
+               "               [--eq-gain-db g0,g1,...] [--eq-edges-hz a,b,c,...] [--eq-taps L] [--filter-taps FILE]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
@@ -115,7 +123,11 @@ static void usage(FILE *f)
                "  --pitch-threshold X  the correlation strength from which a frame counts as voiced, 0 < X <= 1, default 0.5\n"
                "  --bands FILE         write the level per frequency band of every frame of the capacity as TSV: index level...\n"
                "  --phoneme-bands FILE write the level per frequency band of every phoneme likewise\n"
-               "  --band-edges-hz a,b,c,...  the bands' edges in Hz, 2 .. 65 ascending values (default: 16 bands, 22 Hz .. Nyquist at 22 050 Hz)\n",
+               "  --band-edges-hz a,b,c,...  the bands' edges in Hz, 2 .. 65 ascending values (default: 16 bands, 22 Hz .. Nyquist at 22 050 Hz)\n"
+               "  --eq-gain-db g0,g1,...  filter the waveform on the device: a gain in dB per band (16 for the default bands of --bands)\n"
+               "  --eq-edges-hz a,b,c,...  the equaliser's band edges in Hz, converted like --band-edges-hz\n"
+               "  --eq-taps L          the equaliser's tap count, odd, 1 .. 511, default 255 (a band step takes about 4096 / (L + 1) bins)\n"
+               "  --filter-taps FILE   filter the waveform with the taps in FILE, one per line (an odd count of 1 .. 511), instead\n",
             k_default_model, k_default_out);
 }
 
@@ -243,6 +255,10 @@ int main(int argc, char **argv)
     std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path, gain_path, contour_path, plevel_path, pitch_path, ppitch_path;
     std::string bands_path, pbands_path;
     std::vector<double> band_hz;       // --band-edges-hz
+    std::vector<double> eq_hz, eq_db;  // --eq-edges-hz, --eq-gain-db
+    long eq_taps = 255;                // --eq-taps
+    bool eq_taps_given = false;
+    std::string taps_path;             // --filter-taps
     double pitch_hz[2] = {0.0, 0.0}, pitch_thr = 0.0;      // --pitch-min-hz, --pitch-max-hz, --pitch-threshold (0: the default)
     bool pitch_param = false;
     bool trim = false, fit = false, info = false, controlled = false, leveled = false, enveloped = false;
@@ -270,28 +286,65 @@ int main(int argc, char **argv)
         else if (a == "--phoneme-pitch") ppitch_path = need("--phoneme-pitch");
         else if (a == "--bands") bands_path = need("--bands");
         else if (a == "--phoneme-bands") pbands_path = need("--phoneme-bands");
-        else if (a == "--band-edges-hz")
+        else if (a == "--band-edges-hz" || a == "--eq-edges-hz")
         {
-            const std::string v = need("--band-edges-hz");
+            const std::string v = need(a.c_str());
+            std::vector<double> &hz = a == "--eq-edges-hz" ? eq_hz : band_hz;
             bool ok = !v.empty();
-            band_hz.clear();
+            hz.clear();
             for (size_t at = 0; ok && at <= v.size();)
             {
                 const size_t comma = std::min(v.find(',', at), v.size());
                 const std::string item = v.substr(at, comma - at);
                 char *end = nullptr;
                 const double x = strtod(item.c_str(), &end);
-                ok = !item.empty() && end == item.c_str() + item.size() && x > 0.0 && x <= 1e6 && (band_hz.empty() || x > band_hz.back());
-                band_hz.push_back(x);
+                ok = !item.empty() && end == item.c_str() + item.size() && x > 0.0 && x <= 1e6 && (hz.empty() || x > hz.back());
+                hz.push_back(x);
                 at = comma + 1;
             }
-            if (!ok || band_hz.size() < 2 || band_hz.size() > 65)
+            if (!ok || hz.size() < 2 || hz.size() > 65)
             {
-                fprintf(stderr, "zerovox: --band-edges-hz needs 2 to 65 ascending numbers in (0, 1000000], separated by commas, got '%s'\n", v.c_str());
+                fprintf(stderr, "zerovox: %s needs 2 to 65 ascending numbers in (0, 1000000], separated by commas, got '%s'\n", a.c_str(), v.c_str());
                 usage(stderr);
                 return 2;
             }
         }
+        else if (a == "--eq-gain-db")
+        {
+            const std::string v = need("--eq-gain-db");
+            bool ok = !v.empty();
+            eq_db.clear();
+            for (size_t at = 0; ok && at <= v.size();)
+            {
+                const size_t comma = std::min(v.find(',', at), v.size());
+                const std::string item = v.substr(at, comma - at);
+                char *end = nullptr;
+                const double x = strtod(item.c_str(), &end);
+                ok = !item.empty() && end == item.c_str() + item.size() && std::isfinite(x);
+                eq_db.push_back(x);
+                at = comma + 1;
+            }
+            if (!ok || eq_db.size() > 64)
+            {
+                fprintf(stderr, "zerovox: --eq-gain-db needs 1 to 64 finite numbers separated by commas, got '%s'\n", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+        }
+        else if (a == "--eq-taps")
+        {
+            const std::string v = need("--eq-taps");
+            char *end = nullptr;
+            eq_taps = strtol(v.c_str(), &end, 10);
+            if (v.empty() || end != v.c_str() + v.size() || eq_taps < 1 || eq_taps > 511 || eq_taps % 2 == 0)
+            {
+                fprintf(stderr, "zerovox: --eq-taps needs an odd number in 1 .. 511, got '%s'\n", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+            eq_taps_given = true;
+        }
+        else if (a == "--filter-taps") taps_path = need("--filter-taps");
         else if (a == "--pitch-min-hz" || a == "--pitch-max-hz" || a == "--pitch-threshold")
         {
             const std::string v = need(a.c_str());
@@ -414,6 +467,48 @@ int main(int argc, char **argv)
         usage(stderr);
         return 2;
     }
+    if ((!eq_hz.empty() || eq_taps_given) && eq_db.empty())
+    {
+        fprintf(stderr, "zerovox: --eq-edges-hz and --eq-taps need --eq-gain-db\n");
+        usage(stderr);
+        return 2;
+    }
+    if (!taps_path.empty() && !eq_db.empty())
+    {
+        fprintf(stderr, "zerovox: --filter-taps and --eq-gain-db exclude each other\n");
+        usage(stderr);
+        return 2;
+    }
+    if (!eq_db.empty() && eq_db.size() != (eq_hz.empty() ? (size_t)16 : eq_hz.size() - 1))
+    {
+        fprintf(stderr, "zerovox: --eq-gain-db has %zu gains, %s gives %zu bands\n", eq_db.size(), eq_hz.empty() ? "the default" : "--eq-edges-hz",
+                eq_hz.empty() ? (size_t)16 : eq_hz.size() - 1);
+        usage(stderr);
+        return 2;
+    }
+    std::vector<float> filter_taps;        // --filter-taps, read ahead of the checkpoint
+    if (!taps_path.empty())
+    {
+        std::ifstream f(taps_path);
+        std::string line;
+        bool ok = (bool)f;
+        while (ok && std::getline(f, line))
+        {
+            if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+            const size_t a0 = line.find_first_not_of(" \t\r"), a1 = line.find_last_not_of(" \t\r");
+            const std::string item = line.substr(a0, a1 - a0 + 1);
+            char *end = nullptr;
+            const float x = strtof(item.c_str(), &end);
+            ok = end == item.c_str() + item.size() && filter_taps.size() < 4096;
+            filter_taps.push_back(x);
+        }
+        if (!ok || filter_taps.empty())
+        {
+            fprintf(stderr, "zerovox: --filter-taps: cannot read '%s' as one tap per line\n", taps_path.c_str());
+            usage(stderr);
+            return 2;
+        }
+    }
     if (pitch_param && pitch_path.empty() && ppitch_path.empty())
     {
         fprintf(stderr, "zerovox: --pitch-min-hz, --pitch-max-hz and --pitch-threshold need --pitch FILE or --phoneme-pitch FILE\n");
@@ -486,6 +581,25 @@ int main(int argc, char **argv)
             model.set_bands(!bands_path.empty(), !pbands_path.empty(), band_edges.empty() ? 0u : (uint32_t)band_edges.size() - 1,
                             band_edges.empty() ? nullptr : band_edges.data());
             band_edges = model.get_band_edges();       // the library's defaults where none were given
+        }
+        if (!filter_taps.empty()) model.set_filter(filter_taps.data(), (uint32_t)filter_taps.size());
+        if (!eq_db.empty())
+        {
+            // Hz to bins as for --band-edges-hz, dB to linear gains, then the library's design
+            std::vector<uint32_t> eq_edges;
+            for (double hz : eq_hz) eq_edges.push_back((uint32_t)std::min(floor(hz * 1024.0 / hp.audio_sampling_rate + 0.5), 4294967295.0));
+            for (size_t b = 1; b < eq_edges.size(); b++)
+                if (eq_edges[b] <= eq_edges[b - 1])
+                    throw std::runtime_error("--eq-edges-hz: " + std::to_string(eq_hz[b - 1]) + " and " + std::to_string(eq_hz[b]) +
+                                             " Hz fall on the same bin " + std::to_string(eq_edges[b]) + " at " +
+                                             std::to_string(hp.audio_sampling_rate) + " Hz");
+            std::vector<float> g;
+            for (double db : eq_db) g.push_back((float)pow(10.0, db / 20.0));
+            std::vector<float> taps((size_t)eq_taps);
+            if (zv_filter_design(eq_edges.empty() ? 0u : (uint32_t)eq_edges.size() - 1, eq_edges.empty() ? nullptr : eq_edges.data(), g.data(),
+                                 (uint32_t)eq_taps, taps.data()) != ZV_OK)
+                throw std::runtime_error(zv_last_error());
+            model.set_filter(taps.data(), (uint32_t)taps.size());
         }
         if (target_seconds > 0.0)
             target_frames = (long)std::min(floor(target_seconds * hp.audio_sampling_rate / hp.audio_hop_size + 0.5), 1e9);
