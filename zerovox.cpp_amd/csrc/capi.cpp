@@ -129,19 +129,7 @@ static void check_T(const Model &M, uint32_t T)
                  T, M.max_frames_per_utterance());
 }
 
-// The layout of an I/O block (io_scratch, pinned_scratch): regions in the order they are carved, each on a 256-byte boundary
-// (DeviceArena's rounding).  size() comes from the same carve, so it covers every region handed out.
-struct Layout
-{
-    size_t end = 0;
-    size_t at(size_t bytes)
-    {
-        const size_t o = zv::DeviceArena::align(end);
-        end = o + bytes;
-        return o;
-    }
-    size_t size() const { return zv::DeviceArena::align(end); }
-};
+using zv::Layout;      // wave_stages.h
 
 // One call's utterances, in the form the batch entry points take them; a single-utterance entry point makes a request of one
 // that points at its own arguments.  out[u] receives utterance u's waveform (zv_encode_taps*: its hidden frames); n_frames,
@@ -162,56 +150,9 @@ struct Request
     bool                       fitted = false;
     // target durations (zv_*_target): [count] or null, 0 = no target for that utterance
     const uint32_t            *target_frames = nullptr;
-    // volume controls (zv_*_volume): volume [count] or null (levels alone: a meter, every gain 1), levels [count] or null
-    const zv_volume           *volume = nullptr;
-    zv_level                  *levels = nullptr;
-    // amplitude envelope (zv_*_envelope): [count] or null; each struct's phoneme_gain is [n[u]] or null
-    const zv_envelope         *envelope = nullptr;
-    // level contour (zv_*_contour): [count] or null; each struct's tables are [T[u]] and [n[u]] or null
-    const zv_contour          *contour = nullptr;
-    // pitch track (zv_*_pitch): [count] or null; each struct's tables are [T[u]] and [n[u]] or null, its parameters 0 = default
-    const zv_pitch            *pitch = nullptr;
-    // band levels (zv_*_bands): [count] or null; each struct's tables are [T[u]][n_bands] and [n[u]][n_bands] or null
-    const zv_bands            *bands = nullptr;
-    // waveform filter (zv_*_filter): [count] or null; each struct's taps are [n_taps] or null = no filter for that utterance
-    const zv_filter           *filter = nullptr;
+    // the waveform stages' arguments (wave_stages.h), in the entry points' order: volume, levels, envelope, contour, pitch, bands, filter
+    zv::WaveArgs               wave;
 
-    // any utterance with a filter: then every utterance gets a parameter row (n_taps = 0 where it has none: its bits are copied), the
-    // vocoder writes the filter-input region and the filter pass writes the waveform
-    bool filters() const
-    {
-        for (uint32_t u = 0; filter && u < count; u++)
-            if (filter[u].taps) return true;
-        return false;
-    }
-    // any utterance that asks for a table of its band levels: then the rows of every utterance that asks are written on the device (an
-    // utterance that asks for none is skipped by both passes: its parameter row says n_bands = 0), and the host downloads the tables
-    bool band_levels() const
-    {
-        for (uint32_t u = 0; bands && u < count; u++)
-            if (bands[u].frames || bands[u].phonemes) return true;
-        return false;
-    }
-    // any utterance that asks for a table of its pitch track: then every row of both tables is written on the device (an utterance
-    // that asks for none is metered at the cheapest parameters), and the host downloads the tables that were asked for
-    bool pitches() const
-    {
-        for (uint32_t u = 0; pitch && u < count; u++)
-            if (pitch[u].frames || pitch[u].phonemes) return true;
-        return false;
-    }
-    // any utterance that asks for a table of its contour: then every row of both tables is written on the device, and the host
-    // downloads the tables that were asked for
-    bool contours() const
-    {
-        for (uint32_t u = 0; contour && u < count; u++)
-            if (contour[u].frames || contour[u].phonemes) return true;
-        return false;
-    }
-    // the call carries an envelope: then every utterance gets a gain row per token and an envelope row (the identity where it has none)
-    bool envelopes() const { return envelope != nullptr; }
-    // the call measures levels: then every utterance gets a volume row (the identity where none is given) and a level row
-    bool volumes() const { return volume || levels; }
     // any utterance with a target: then every utterance gets a ctl row and pctl rows (the identity where it has no controls), which
     // the device step between the duration predictor and the length regulator reads and rewrites (kernels.h launch_fit_durations)
     bool targets() const
@@ -252,13 +193,7 @@ struct Request
         if (phonemes) s.phonemes += a;
         if (durations) s.durations += a;
         if (target_frames) s.target_frames += a;
-        if (volume) s.volume += a;
-        if (levels) s.levels += a;
-        if (envelope) s.envelope += a;
-        if (contour) s.contour += a;
-        if (pitch) s.pitch += a;
-        if (bands) s.bands += a;
-        if (filter) s.filter += a;
+        s.wave = wave.slice(a);
         return s;
     }
 };
@@ -290,7 +225,7 @@ static void pack_volume(const Request &r, float *vol)
     static const zv_volume identity = {1.0f, 0.0f, 0.0f};
     for (uint32_t u = 0; u < r.count; u++)
     {
-        const zv_volume &v = r.volume ? r.volume[u] : identity;
+        const zv_volume &v = r.wave.volume ? r.wave.volume[u] : identity;
         float *c = vol + (size_t)u * zv::LEVEL_VOL_STRIDE;
         c[0] = v.gain;
         c[1] = v.target_rms;
@@ -326,7 +261,7 @@ static void pack_pitch(const Model &M, const Request &r, uint32_t *par)
     for (uint32_t u = 0; u < r.count; u++)
     {
         zv::PitchParams q = {zv::PITCH_LAG_LO, zv::PITCH_LAG_LO + 1, zv::PITCH_WINDOW_LO, 0.5f};
-        if (r.pitch[u].frames || r.pitch[u].phonemes) q = resolve_pitch(M, r.pitch[u]);
+        if (r.wave.pitch[u].frames || r.wave.pitch[u].phonemes) q = resolve_pitch(M, r.wave.pitch[u]);
         uint32_t *c = par + (size_t)u * zv::PITCH_PARAM_STRIDE;
         c[0] = q.min_lag;
         c[1] = q.max_lag;
@@ -348,15 +283,14 @@ static void resolve_bands(const zv_bands &b, uint32_t *row)
 }
 
 // a request's band parameters in the kernels' layout (bands.h BANDS_PARAM_STRIDE), resolved; an utterance that asks for no table gets
-// n_bands = 0, which both passes skip.  nb [count] (may be null) receives each utterance's band count
-static void pack_bands(const Request &r, uint32_t *par, uint32_t *nb)
+// n_bands = 0, which both passes skip.  A row's first word is the utterance's band count
+static void pack_bands(const Request &r, uint32_t *par)
 {
     for (uint32_t u = 0; u < r.count; u++)
     {
         uint32_t *c = par + (size_t)u * zv::BANDS_PARAM_STRIDE;
         memset(c, 0, zv::BANDS_PARAM_STRIDE * 4);
-        if (r.bands[u].frames || r.bands[u].phonemes) resolve_bands(r.bands[u], c);
-        if (nb) nb[u] = c[0];
+        if (r.wave.bands[u].frames || r.wave.bands[u].phonemes) resolve_bands(r.wave.bands[u], c);
     }
 }
 
@@ -374,7 +308,7 @@ static void check_filter(const zv_filter &f)
 // a request's filter rows in the kernel's layout (filter.h FILTER_PARAM_STRIDE); an utterance without a filter gets n_taps = 0
 static void pack_filter(const Request &r, uint32_t *par)
 {
-    for (uint32_t u = 0; u < r.count; u++) zv::filter_pack(r.filter[u].taps, r.filter[u].n_taps, par + (size_t)u * zv::FILTER_PARAM_STRIDE);
+    for (uint32_t u = 0; u < r.count; u++) zv::filter_pack(r.wave.filter[u].taps, r.wave.filter[u].n_taps, par + (size_t)u * zv::FILTER_PARAM_STRIDE);
 }
 
 static void check_envelope(const zv_envelope &e, uint32_t n)
@@ -398,7 +332,7 @@ static void pack_envelope(const Request &r, float *gain, int32_t *env)
 {
     for (uint32_t u = 0, row = 0; u < r.count; row += r.n[u], u++)
     {
-        const zv_envelope &e = r.envelope[u];
+        const zv_envelope &e = r.wave.envelope[u];
         for (uint32_t i = 0; i < r.n[u]; i++) gain[row + i] = e.phoneme_gain ? e.phoneme_gain[i] : 1.0f;
         int32_t *c = env + (size_t)u * zv::ENV_CTL_STRIDE;
         c[0] = (int32_t)e.ramp_frames;
@@ -406,6 +340,65 @@ static void pack_envelope(const Request &r, float *gain, int32_t *env)
         c[2] = (int32_t)e.fade_out_samples;
         c[3] = 0;
     }
+}
+
+// ---- the waveform stages as a group (wave_stages.h): what run_single and batch_enqueue share.  Besides check_request's lines only
+// pack_wave and wave_tables name the stages; nothing behind them does.
+// a request's stage rows in the kernels' layouts, in a host block at the planned offsets of its input regions (a batch's pinned input
+// block, a single utterance's host staging); token rows past the utterances are never read
+static void pack_wave(const Model &M, const Request &r, const zv::WaveAsk &ask, char *h, const zv::WaveOffsets &o)
+{
+    if (ask.on[zv::WS_VOLUME]) pack_volume(r, (float *)(h + o.at[zv::R_VOL]));
+    if (ask.on[zv::WS_ENVELOPE]) pack_envelope(r, (float *)(h + o.at[zv::R_ENV_GAIN]), (int32_t *)(h + o.at[zv::R_ENV]));
+    if (ask.on[zv::WS_PITCH]) pack_pitch(M, r, (uint32_t *)(h + o.at[zv::R_PIT_PAR]));
+    if (ask.on[zv::WS_BANDS]) pack_bands(r, (uint32_t *)(h + o.at[zv::R_BND_PAR]));
+    if (ask.on[zv::WS_FILTER]) pack_filter(r, (uint32_t *)(h + o.at[zv::R_FLT_PAR]));
+}
+
+// an utterance's table at the caller (null: not asked for) and the bytes of a row there
+struct RowDst { void *p; size_t row; };
+
+// One table a stage hands back: the device rows, the bytes of a device row (and of a staging row), the staging rows in a batch's pinned
+// block or null (a single utterance's rows go straight to the caller), and whether there is a row per utterance, token row or frame row
+struct RowTable { const char *dev; size_t dev_row; char *host; zv::WaveRowKind rows; };
+
+// The tables of a request, one per staging region that exists for it, and what each utterance receives of them, dst[k * count + u].
+// dev: the block of the device regions; host: the pinned block of the staging regions, or null; h, ho: the packed input regions and
+// their offsets, where a band table's n_bands is read (a band row at the caller is the first n_bands entries of the device's).
+static void wave_tables(const Request &r, const zv::WaveAsk &ask, const zv::WaveOffsets &o, const char *dev, char *host, const char *h,
+                        const zv::WaveOffsets &ho, std::vector<RowTable> &tabs, std::vector<RowDst> &dst)
+{
+    const zv::WaveArgs &w = r.wave;
+    tabs.clear();
+    dst.clear();
+    for (int id = 0; id < zv::R_COUNT; id++)
+    {
+        const zv::WaveRegion &g = zv::WAVE_REGIONS[id];
+        if (g.role != zv::WR_HOST || !zv::wave_region_exists(g, ask)) continue;
+        tabs.push_back(RowTable{dev + o.at[g.device], g.row_bytes, host ? host + o.at[id] : nullptr, g.rows});
+        for (uint32_t u = 0; u < r.count; u++)
+        {
+            const size_t band_row = ask.on[zv::WS_BANDS] ? 4 * (size_t)((const uint32_t *)(h + ho.at[zv::R_BND_PAR]))[(size_t)u * zv::BANDS_PARAM_STRIDE] : 0;
+            dst.push_back(id == zv::R_LEVELS_HOST         ? RowDst{w.levels ? w.levels + u : nullptr, sizeof(zv_level)}
+                          : id == zv::R_CTR_FRAMES_HOST   ? RowDst{w.contour[u].frames, sizeof(zv_frame_level)}
+                          : id == zv::R_CTR_PHONEMES_HOST ? RowDst{w.contour[u].phonemes, sizeof(zv_frame_level)}
+                          : id == zv::R_PIT_FRAMES_HOST   ? RowDst{w.pitch[u].frames, sizeof(zv_pitch_frame)}
+                          : id == zv::R_PIT_PHONEMES_HOST ? RowDst{w.pitch[u].phonemes, sizeof(zv_pitch_phoneme)}
+                          : id == zv::R_BND_FRAMES_HOST   ? RowDst{w.bands[u].frames, band_row}
+                                                          : RowDst{w.bands[u].phonemes, band_row});
+        }
+    }
+}
+
+// rows [first, first + count) of a table to dst on stream st, dst_row bytes of each: whole rows, or the leading part of each
+static void rows_download(const RowTable &t, size_t first, size_t count, void *dst, size_t dst_row, hipStream_t st)
+{
+    if (!count) return;
+    const char *src = t.dev + first * t.dev_row;
+    if (dst_row == t.dev_row)
+        ZV_HIP(hipMemcpyAsync(dst, src, count * t.dev_row, hipMemcpyDeviceToHost, st));
+    else
+        ZV_HIP(hipMemcpy2DAsync(dst, dst_row, src, t.dev_row, dst_row, count, hipMemcpyDeviceToHost, st));
 }
 
 static void check_phoneme_controls(const Model &M, const zv_phoneme_controls &p, uint32_t n)
@@ -436,7 +429,7 @@ static void check_request(zv_model *m, const Request &r)
     const Model &M = *m->m;
     const bool tg = r.targets();
     // the one limit of the envelope that is the checkpoint's, not an utterance's (kernels.h env_hop_supported)
-    if (r.envelope && !zv::env_hop_supported(M.hp.audio_hop_size))
+    if (r.wave.envelope && !zv::env_hop_supported(M.hp.audio_hop_size))
         zv::fail(ZV_ERR_ARG, "%s: an envelope needs audio_hop_size >= 10, the checkpoint has %d", r.fn, (int)M.hp.audio_hop_size);
     for (uint32_t u = 0; u < r.count; u++)
     {
@@ -451,15 +444,16 @@ static void check_request(zv_model *m, const Request &r)
             check_ids(M, r.ids[u], r.puncts[u], r.n[u]);
             if (r.prosody) check_prosody(r.prosody[u]);
             if (r.phonemes) check_phoneme_controls(M, r.phonemes[u], r.n[u]);
-            if (r.volume) check_volume(r.volume[u]);
-            if (r.envelope) check_envelope(r.envelope[u], r.n[u]);
-            if (r.pitch && (r.pitch[u].frames || r.pitch[u].phonemes)) resolve_pitch(M, r.pitch[u]);
-            if (r.bands && (r.bands[u].frames || r.bands[u].phonemes))
+            const zv::WaveArgs &w = r.wave;
+            if (w.volume) check_volume(w.volume[u]);
+            if (w.envelope) check_envelope(w.envelope[u], r.n[u]);
+            if (w.pitch && (w.pitch[u].frames || w.pitch[u].phonemes)) resolve_pitch(M, w.pitch[u]);
+            if (w.bands && (w.bands[u].frames || w.bands[u].phonemes))
             {
                 uint32_t row[zv::BANDS_PARAM_STRIDE];
-                resolve_bands(r.bands[u], row);
+                resolve_bands(w.bands[u], row);
             }
-            if (r.filter) check_filter(r.filter[u]);
+            if (w.filter) check_filter(w.filter[u]);
             if (r.target_frames && r.target_frames[u] > r.T[u])
                 zv::fail(ZV_ERR_ARG, "target_frames = %u exceeds the capacity T = %u", r.target_frames[u], r.T[u]);
             if (tg && r.n[u] > (uint32_t)zv::FIT_MAX_TOKENS)      // one launch covers the request's utterances, with or without a target
@@ -543,9 +537,8 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const bool tg = r.targets(), pc = r.phoneme_controls() || tg, dur = r.timings();
         const size_t E = M.E(), b_ids = (size_t)n * 4, b_hid = (size_t)T * E * 4, b_wav = (size_t)T * M.hp.audio_hop_size * 4;
         const size_t b_ctl = r.prosody || tg ? zv::CTL_STRIDE * 4 : 0, b_pctl = pc ? (size_t)n * zv::PCTL_STRIDE * 4 : 0;
-        const bool vol = r.volumes() && !taps, env = r.envelopes() && !taps, ctr = r.contours() && !taps, pit = r.pitches() && !taps,
-                   bnd = r.band_levels() && !taps, flt = r.filters() && !taps;
-        const void *bnd_table = bnd ? M.bands_table() : nullptr;      // (allocates and copies on first use: ahead of everything enqueued)
+        const zv::WaveAsk ask = taps ? zv::WaveAsk{} : r.wave.ask(1);      // (an encoder-taps call has no waveform)
+        const void *bands_table = ask.on[zv::WS_BANDS] ? M.bands_table() : nullptr;      // (allocates and copies on first use: ahead of everything enqueued)
         if (!taps) M.reserve(n, T);
         // [frame count][ids][puncts][style][controls][phoneme controls][hidden], and for the chain [mel][wav][scan] (scan: only when
         // timings are asked for, the length regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
@@ -554,24 +547,12 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         const size_t o_nf = L.at(4), o_ids = L.at(b_ids), o_pun = L.at(b_ids), o_sty = L.at(E * 4), o_ctl = L.at(b_ctl),
                      o_pctl = L.at(b_pctl), o_hid = L.at(b_hid);
         const size_t o_mel = taps ? 0 : L.at((size_t)T * M.hp.audio_num_mels * 4), o_wav = taps ? 0 : L.at(b_wav),
-                     o_cum = taps ? 0 : L.at(dur || env || ctr || pit || bnd ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
+                     o_cum = taps ? 0 : L.at(dur || ask.needs_scan() ? b_ids : 0), o_live = L.at(r.fitted && !taps ? sizeof(zv::Seg) : 0),
                      o_runs = L.at(!r.fitted && !taps ? sizeof(zv::Seg) : 0);
-        // [volume row][level row] (volume controls: the row uploaded, the level written on the device)
-        const size_t o_vol = L.at(vol ? zv::LEVEL_VOL_STRIDE * 4 : 0), o_lvl = L.at(vol ? sizeof(zv::LevelRow) : 0);
-        // [gain row per token][envelope row] (amplitude envelope: both uploaded)
-        const size_t o_eg = L.at(env ? b_ids : 0), o_env = L.at(env ? zv::ENV_CTL_STRIDE * 4 : 0);
-        // [frame rows][phoneme rows] (level contour: both written on the device; the last regions, so no other offset moves)
-        const size_t b_cfr = (size_t)T * sizeof(zv::ContourRow), b_cph = (size_t)n * sizeof(zv::ContourRow);
-        const size_t o_cfr = L.at(ctr ? b_cfr : 0), o_cph = L.at(ctr ? b_cph : 0);
-        // [frame rows][phoneme rows][parameter row] (pitch track: the rows written on the device, the parameters uploaded; behind the contour's)
-        const size_t b_pfr = (size_t)T * sizeof(zv::PitchFrameRow), b_pph = (size_t)n * sizeof(zv::PitchPhonemeRow);
-        const size_t o_pfr = L.at(pit ? b_pfr : 0), o_pph = L.at(pit ? b_pph : 0), o_ppar = L.at(pit ? zv::PITCH_PARAM_STRIDE * 4 : 0);
-        // [frame rows][phoneme rows][kept powers][parameter row] (band levels: BANDS_ROW_STRIDE entries per row; behind the pitch track's)
-        const size_t b_bfr = (size_t)T * zv::BANDS_ROW_STRIDE * 4, b_bph = (size_t)n * zv::BANDS_ROW_STRIDE * 4;
-        const size_t o_bfr = L.at(bnd ? b_bfr : 0), o_bph = L.at(bnd ? b_bph : 0), o_bsl = L.at(bnd ? 2 * b_bfr : 0),
-                     o_bpar = L.at(bnd ? zv::BANDS_PARAM_STRIDE * 4 : 0);
-        // [parameter row] (waveform filter: uploaded; the last region)
-        const size_t o_fpar = L.at(flt ? zv::FILTER_PARAM_STRIDE * 4 : 0);
+        // the waveform stages' regions (wave_stages.h), uploaded or written on the device; the last regions, so no other offset moves
+        const zv::WaveRows rows{1, n, T};
+        zv::WaveOffsets wo;
+        zv::wave_carve(L, ask, rows, zv::WR_INPUT | zv::WR_DEVICE, wo);
         char *io = (char *)M.io_scratch(L.size());
         int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(io + o_ids), *d_pun = (int32_t *)(io + o_pun);
         float *d_sty = (float *)(io + o_sty), *d_hid = (float *)(io + o_hid);
@@ -595,30 +576,19 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
             bt.d_pctl = (const float *)(io + o_pctl);
             ZV_HIP(hipMemcpyAsync(io + o_pctl, pctl.data(), b_pctl, hipMemcpyHostToDevice, M.stream()));
         }
-        float volrow[zv::LEVEL_VOL_STRIDE];
-        zv_level level = {0.0f, 0.0f, 0.0f, 0};
-        if (vol)
-        {
-            pack_volume(r, volrow);
-            bt.d_vol = (const float *)(io + o_vol);
-            bt.d_levels = (zv::LevelRow *)(io + o_lvl);
-            bt.d_nframes = d_nf;
-            ZV_HIP(hipMemcpyAsync(io + o_vol, volrow, sizeof(volrow), hipMemcpyHostToDevice, M.stream()));
-        }
-        std::vector<float> egain(env ? n : 0);                       // host staging, like ctl
-        int32_t erow[zv::ENV_CTL_STRIDE];
-        if (env)
-        {
-            pack_envelope(r, egain.data(), erow);
-            bt.d_env_gain = (const float *)(io + o_eg);
-            bt.d_env = (const int32_t *)(io + o_env);
-            bt.d_nframes = d_nf;
-            ZV_HIP(hipMemcpyAsync(io + o_eg, egain.data(), b_ids, hipMemcpyHostToDevice, M.stream()));
-            ZV_HIP(hipMemcpyAsync(io + o_env, erow, sizeof(erow), hipMemcpyHostToDevice, M.stream()));
-        }
-        uint32_t prow[zv::PITCH_PARAM_STRIDE];                       // host staging, like ctl
-        uint32_t brow[zv::BANDS_PARAM_STRIDE];                       // likewise
-        std::vector<uint32_t> frow(flt ? zv::FILTER_PARAM_STRIDE : 0);      // likewise
+        // the stages' rows: host staging like ctl, at the offsets of a block of the input regions alone
+        Layout S;
+        zv::WaveOffsets so;
+        zv::wave_carve(S, ask, rows, zv::WR_INPUT, so);
+        std::vector<char> stage(S.size());
+        pack_wave(M, r, ask, stage.data(), so);
+        bt.wave = zv::wave_bind(ask, wo, io, io, d_nf, bands_table);
+        for (int id = 0; id < zv::R_COUNT; id++)
+            if (const size_t bytes = zv::WAVE_REGIONS[id].role == zv::WR_INPUT ? zv::wave_region_bytes(id, ask, rows) : 0)
+                ZV_HIP(hipMemcpyAsync(io + wo.at[id], stage.data() + so.at[id], bytes, hipMemcpyHostToDevice, M.stream()));
+        std::vector<RowTable> tabs;      // the stages' tables and where each goes: straight to the caller, like the waveform
+        std::vector<RowDst> dst;
+        wave_tables(r, ask, wo, io, nullptr, stage.data(), so, tabs, dst);
         int32_t nf = 0;
         if (taps)
         {
@@ -636,57 +606,17 @@ static zv_status run_single(zv_model *m, const Request &r, std::optional<Taps> t
         else
         {
             float *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
-            // an envelope's knots pass and a contour's phonemes pass read the scan behind the vocoder
-            if (dur || env || ctr || pit || bnd) bt.d_cum = (int32_t *)(io + o_cum);
-            if (ctr)
-            {
-                bt.d_ctr_frames = (zv::ContourRow *)(io + o_cfr);
-                bt.d_ctr_phonemes = (zv::ContourRow *)(io + o_cph);
-            }
-            if (bnd)
-            {
-                pack_bands(r, brow, nullptr);
-                bt.d_bnd_frames = (float *)(io + o_bfr);
-                bt.d_bnd_phonemes = (float *)(io + o_bph);
-                bt.d_bnd_slab = (unsigned long long *)(io + o_bsl);
-                bt.d_bnd_par = (const uint32_t *)(io + o_bpar);
-                bt.d_bnd_table = bnd_table;
-                ZV_HIP(hipMemcpyAsync(io + o_bpar, brow, sizeof(brow), hipMemcpyHostToDevice, M.stream()));
-            }
-            if (flt)
-            {
-                pack_filter(r, frow.data());
-                bt.d_flt_par = (const uint32_t *)(io + o_fpar);
-                ZV_HIP(hipMemcpyAsync(io + o_fpar, frow.data(), frow.size() * 4, hipMemcpyHostToDevice, M.stream()));
-            }
-            if (pit)
-            {
-                pack_pitch(M, r, prow);
-                bt.d_pit_frames = (zv::PitchFrameRow *)(io + o_pfr);
-                bt.d_pit_phonemes = (zv::PitchPhonemeRow *)(io + o_pph);
-                bt.d_pit_par = (const uint32_t *)(io + o_ppar);
-                ZV_HIP(hipMemcpyAsync(io + o_ppar, prow, sizeof(prow), hipMemcpyHostToDevice, M.stream()));
-            }
+            // an envelope's knots pass and a table stage's phonemes pass read the scan behind the vocoder
+            if (dur || bt.wave.needs_scan()) bt.d_cum = (int32_t *)(io + o_cum);
             M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf);
             ZV_HIP(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, M.stream()));
             if (dur) ZV_HIP(hipMemcpyAsync(cum.data(), bt.d_cum, b_ids, hipMemcpyDeviceToHost, M.stream()));
             ZV_HIP(hipMemcpyAsync(r.out[0], d_wav, b_wav, hipMemcpyDeviceToHost, M.stream()));
-            if (vol) ZV_HIP(hipMemcpyAsync(&level, io + o_lvl, sizeof(level), hipMemcpyDeviceToHost, M.stream()));
-            // the contour's tables go straight to the caller, like the waveform: the ones asked for
-            if (ctr && r.contour[0].frames) ZV_HIP(hipMemcpyAsync(r.contour[0].frames, io + o_cfr, b_cfr, hipMemcpyDeviceToHost, M.stream()));
-            if (ctr && r.contour[0].phonemes) ZV_HIP(hipMemcpyAsync(r.contour[0].phonemes, io + o_cph, b_cph, hipMemcpyDeviceToHost, M.stream()));
-            if (pit && r.pitch[0].frames) ZV_HIP(hipMemcpyAsync(r.pitch[0].frames, io + o_pfr, b_pfr, hipMemcpyDeviceToHost, M.stream()));
-            if (pit && r.pitch[0].phonemes) ZV_HIP(hipMemcpyAsync(r.pitch[0].phonemes, io + o_pph, b_pph, hipMemcpyDeviceToHost, M.stream()));
-            // the band rows likewise: the device keeps BANDS_ROW_STRIDE entries per row, the caller receives the first n_bands of each
-            if (bnd && r.bands[0].frames)
-                ZV_HIP(hipMemcpy2DAsync(r.bands[0].frames, (size_t)brow[0] * 4, io + o_bfr, zv::BANDS_ROW_STRIDE * 4, (size_t)brow[0] * 4, T,
-                                        hipMemcpyDeviceToHost, M.stream()));
-            if (bnd && r.bands[0].phonemes)
-                ZV_HIP(hipMemcpy2DAsync(r.bands[0].phonemes, (size_t)brow[0] * 4, io + o_bph, zv::BANDS_ROW_STRIDE * 4, (size_t)brow[0] * 4, n,
-                                        hipMemcpyDeviceToHost, M.stream()));
+            for (size_t k = 0; k < tabs.size(); k++)
+                if (dst[k].p)
+                    rows_download(tabs[k], 0, rows[tabs[k].rows], dst[k].p, dst[k].row, M.stream());
         }
         M.sync();
-        if (vol && r.levels) r.levels[0] = level;
         if (r.n_frames) r.n_frames[0] = (uint32_t)nf;
         if (dur) durations_from_cum(cum.data(), 1, r.n, r.T, r.durations);
     });
@@ -893,23 +823,14 @@ struct PendingBatch
     std::vector<uint32_t> N;
     std::vector<int32_t *> dur;
     const int32_t        *h_cum = nullptr;
-    // volume controls (zv_synthesize_batch_begin_volume): the level rows land in h_lvl, handed out to levels[n_utt] (may be null)
-    const zv_level       *h_lvl = nullptr;
-    zv_level             *levels = nullptr;
-    // level contour (zv_synthesize_batch_begin_contour): the rows land in h_cfr (packed like the waveforms, a row per frame) and h_cph
-    // (packed like the tokens, noff[u] rows ahead of utterance u) and are handed out to the tables each utterance asked for
+    // the waveform stages' tables: the rows land in each table's staging — frame rows packed like the waveforms, phoneme rows like the
+    // tokens (noff[u] rows ahead of utterance u) — and are handed out to dst[k * n_utt + u], the table utterance u asked for (or null)
     std::vector<size_t>   noff;
-    std::vector<zv_contour> contour;
-    const zv_frame_level *h_cfr = nullptr, *h_cph = nullptr;
-    // pitch track (zv_synthesize_batch_begin_pitch): likewise, h_pfr packed like the waveforms and h_pph like the tokens
-    std::vector<zv_pitch> pitch;
-    const zv_pitch_frame   *h_pfr = nullptr;
-    const zv_pitch_phoneme *h_pph = nullptr;
-    // band levels (zv_synthesize_batch_begin_bands): likewise, BANDS_ROW_STRIDE entries per row in the staging block; bands_nb: each
-    // utterance's resolved band count, the entries of a row the caller receives
-    std::vector<zv_bands> bands;
-    std::vector<uint32_t> bands_nb;
-    const float *h_bfr = nullptr, *h_bph = nullptr;
+    std::vector<RowTable> tables;
+    std::vector<RowDst>   dst;
+    // utterance u's rows in a table of this row kind: the first, and how many
+    size_t first_row(zv::WaveRowKind k, uint32_t u) const { return k == zv::ROWS_UTTERANCE ? u : k == zv::ROWS_TOKEN ? noff[u] : woff[u] / (hop * 4); }
+    size_t row_count(zv::WaveRowKind k, uint32_t u) const { return k == zv::ROWS_UTTERANCE ? 1 : k == zv::ROWS_TOKEN ? N[u] : T[u]; }
 };
 static PendingBatch &pending_slot(zv_model *m, int lane)
 {
@@ -944,9 +865,9 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     if (pb.active) zv::fail(ZV_ERR_ARG, "lane %d already has a batch in flight", lane);
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
-    const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings(), vol = r.volumes(),
-               env = r.envelopes(), ctr = r.contours(), pit = r.pitches(), bnd = r.band_levels(), flt = r.filters();
-    const void *bnd_table = bnd ? M.bands_table() : nullptr;      // (allocates and copies on first use: ahead of everything enqueued)
+    const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings();
+    const zv::WaveAsk ask = r.wave.ask(r.count);
+    const void *bands_table = ask.on[zv::WS_BANDS] ? M.bands_table() : nullptr;      // (allocates and copies on first use: ahead of everything enqueued)
     uint32_t nmax = 0, tmax = 0, ntot = 0;
     for (uint32_t u = 0; u < r.count; u++)
     {
@@ -962,64 +883,46 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     bt.n_rows = (size_t)bt.nseg * bt.n_max;
     bt.t_rows = (size_t)bt.nseg * bt.t_max;
     // input block, uploaded in one copy from its pinned mirror: [token table][frame table][ids][puncts][styles][controls]
-    // [phoneme controls] (tables: one entry per utterance + one that spans all of them, see Batch::tokens_merged; controls: only
-    // with prosody or a target, one zv::CTL_STRIDE row per utterance; phoneme controls: only with per-phoneme controls or a target,
-    // one zv::PCTL_STRIDE row per token row — uploaded with the rest, so a replayed graph reads the values of this call, also where
-    // the previous run's fit_durations_kernel has rewritten the rows' frame column)
+    // [phoneme controls][the waveform stages' input regions] (tables: one entry per utterance + one that spans all of them, see
+    // Batch::tokens_merged; controls: only with prosody or a target, one zv::CTL_STRIDE row per utterance; phoneme controls: only with
+    // per-phoneme controls or a target, one zv::PCTL_STRIDE row per token row — uploaded with the rest, so a replayed graph reads the
+    // values of this call, also where the previous run's fit_durations_kernel has rewritten the rows' frame column)
     Layout in;
     const size_t b_tab = (size_t)(bt.nseg + 1) * sizeof(zv::Seg);
     const size_t i_tok = in.at(b_tab), i_frm = in.at(b_tab), i_ids = in.at(bt.n_rows * 4), i_pun = in.at(bt.n_rows * 4),
                  i_sty = in.at((size_t)bt.nseg * E * 4), i_ctl = in.at(ctl ? (size_t)bt.nseg * zv::CTL_STRIDE * 4 : 0),
-                 i_pctl = in.at(pc ? bt.n_rows * zv::PCTL_STRIDE * 4 : 0),
-                 i_vol = in.at(vol ? (size_t)bt.nseg * zv::LEVEL_VOL_STRIDE * 4 : 0),      // volume rows: only with volume controls, like the control rows
-                 i_eg = in.at(env ? bt.n_rows * 4 : 0),                                    // envelope: a gain per token row and a row per utterance, likewise
-                 i_env = in.at(env ? (size_t)bt.nseg * zv::ENV_CTL_STRIDE * 4 : 0),
-                 i_ppar = in.at(pit ? (size_t)bt.nseg * zv::PITCH_PARAM_STRIDE * 4 : 0),      // pitch track: a parameter row per utterance, likewise
-                 i_bpar = in.at(bnd ? (size_t)bt.nseg * zv::BANDS_PARAM_STRIDE * 4 : 0),      // band levels: likewise
-                 i_fpar = in.at(flt ? (size_t)bt.nseg * zv::FILTER_PARAM_STRIDE * 4 : 0),     // waveform filter: a row of tap count and taps per utterance, likewise
-                 b_in = in.size();
+                 i_pctl = in.at(pc ? bt.n_rows * zv::PCTL_STRIDE * 4 : 0);
+    const zv::WaveRows cap_rows{(size_t)bt.nseg, bt.n_rows, bt.t_rows};
+    zv::WaveOffsets wo;
+    zv::wave_carve(in, ask, cap_rows, zv::WR_INPUT, wo);      // (like the control rows: a region only where the request turns its stage on)
+    const size_t b_in = in.size();
     // device block: [frame counts][input block][hidden][mel][wav][scan] (scan: only when timings are asked for, the length
-    // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena)
+    // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena) [live frame table][decoder run table]
+    // [the waveform stages' device regions]
     Layout dev;
     const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
-                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || env || ctr || pit || bnd ? bt.n_rows * 4 : 0),
+                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || ask.needs_scan() ? bt.n_rows * 4 : 0),
                  o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0),      // fitted: the live frame table, written on the device
-                 o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0),     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
-                 o_lvl = dev.at(vol ? (size_t)bt.nseg * sizeof(zv::LevelRow) : 0),             // volume controls: the level rows, written on the device
-                 o_cfr = dev.at(ctr ? bt.t_rows * sizeof(zv::ContourRow) : 0),                 // level contour: the frame rows and the phoneme rows, next to them,
-                 o_cph = dev.at(ctr ? bt.n_rows * sizeof(zv::ContourRow) : 0),                 // by absolute frame row / token row, written on the device
-                 o_pfr = dev.at(pit ? bt.t_rows * sizeof(zv::PitchFrameRow) : 0),              // pitch track: the same two tables
-                 o_pph = dev.at(pit ? bt.n_rows * sizeof(zv::PitchPhonemeRow) : 0),
-                 o_bfr = dev.at(bnd ? bt.t_rows * zv::BANDS_ROW_STRIDE * 4 : 0),               // band levels: the two tables and the kept powers
-                 o_bph = dev.at(bnd ? bt.n_rows * zv::BANDS_ROW_STRIDE * 4 : 0),
-                 o_bsl = dev.at(bnd ? bt.t_rows * zv::BANDS_ROW_STRIDE * 8 : 0);
-    M.reserve_batch(bt);
+                 o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0);     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
+    zv::wave_carve(dev, ask, cap_rows, zv::WR_DEVICE, wo);
     char *io = (char *)M.io_scratch(dev.size());
-    // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan][level rows][contour frame rows]
-    // [contour phoneme rows] (contour: a table only where some utterance asks for it; the rows packed like the waveforms / the tokens)
+    // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan][the waveform stages' staging regions] (a
+    // table only where some utterance asks for it; the rows packed like the waveforms / the tokens)
     size_t wav_bytes = 0;
+    pb.hop = hop;
     pb.woff.assign(r.count, 0);
     pb.noff.assign(r.count + 1, 0);
-    bool ctr_f = false, ctr_p = false, pit_f = false, pit_p = false, bnd_f = false, bnd_p = false;
     for (uint32_t u = 0; u < r.count; u++)
     {
         pb.woff[u] = wav_bytes;
         wav_bytes += (size_t)r.T[u] * hop * 4;
         pb.noff[u + 1] = pb.noff[u] + r.n[u];
-        ctr_f = ctr_f || (ctr && r.contour[u].frames);
-        ctr_p = ctr_p || (ctr && r.contour[u].phonemes);
-        pit_f = pit_f || (pit && r.pitch[u].frames);
-        pit_p = pit_p || (pit && r.pitch[u].phonemes);
-        bnd_f = bnd_f || (bnd && r.bands[u].frames);
-        bnd_p = bnd_p || (bnd && r.bands[u].phonemes);
     }
     const size_t frame_rows = wav_bytes / (hop * 4);
     Layout host;
     const size_t p_in = host.at(b_in), p_nf = host.at((size_t)bt.nseg * 4), p_wav = host.at(wav_bytes),
-                 p_cum = host.at(dur ? bt.n_rows * 4 : 0), p_lvl = host.at(vol ? (size_t)bt.nseg * sizeof(zv_level) : 0),
-                 p_cfr = host.at(ctr_f ? frame_rows * sizeof(zv_frame_level) : 0), p_cph = host.at(ctr_p ? (size_t)ntot * sizeof(zv_frame_level) : 0),
-                 p_pfr = host.at(pit_f ? frame_rows * sizeof(zv_pitch_frame) : 0), p_pph = host.at(pit_p ? (size_t)ntot * sizeof(zv_pitch_phoneme) : 0),
-                 p_bfr = host.at(bnd_f ? frame_rows * zv::BANDS_ROW_STRIDE * 4 : 0), p_bph = host.at(bnd_p ? (size_t)ntot * zv::BANDS_ROW_STRIDE * 4 : 0);
+                 p_cum = host.at(dur ? bt.n_rows * 4 : 0);
+    zv::wave_carve(host, ask, zv::WaveRows{r.count, ntot, frame_rows}, zv::WR_HOST, wo);
     char *pin = (char *)M.pinned_scratch(host.size());
     char *d_in = io + o_in, *h_in = pin + p_in;
     {
@@ -1041,89 +944,34 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         h_tok[r.count] = zv::Seg{0, n0, n0, 0};
         h_frm[r.count] = zv::Seg{0, t0, 0, 0};
         pack_controls(r, (float *)(h_in + i_ctl), (float *)(h_in + i_pctl));      // (phoneme rows past the utterances are never read)
-        if (vol) pack_volume(r, (float *)(h_in + i_vol));
-        if (env) pack_envelope(r, (float *)(h_in + i_eg), (int32_t *)(h_in + i_env));      // (gain rows past the utterances are never read)
-        if (pit) pack_pitch(M, r, (uint32_t *)(h_in + i_ppar));
-        pb.bands_nb.assign(bnd ? r.count : 0, 0);
-        if (bnd)
-        {
-            memset(h_in + i_bpar, 0, (size_t)bt.nseg * zv::BANDS_PARAM_STRIDE * 4);      // (segments past the utterances ask for nothing)
-            pack_bands(r, (uint32_t *)(h_in + i_bpar), pb.bands_nb.data());
-        }
-        if (flt) pack_filter(r, (uint32_t *)(h_in + i_fpar));
+        pack_wave(M, r, ask, h_in, wo);
     }
     bt.d_tok = (const zv::Seg *)(d_in + i_tok);
     bt.d_frm = (const zv::Seg *)(d_in + i_frm);
     if (ctl) bt.d_ctl = (const float *)(d_in + i_ctl);
     bt.has_targets = tg;
     if (pc) bt.d_pctl = (const float *)(d_in + i_pctl);
-    // an envelope's knots pass and a contour's phonemes pass read the scan behind the vocoder
-    if (dur || env || ctr || pit || bnd) bt.d_cum = (int32_t *)(io + o_cum);
-    if (ctr)
-    {
-        bt.d_ctr_frames = (zv::ContourRow *)(io + o_cfr);
-        bt.d_ctr_phonemes = (zv::ContourRow *)(io + o_cph);
-    }
-    if (bnd)
-    {
-        bt.d_bnd_frames = (float *)(io + o_bfr);
-        bt.d_bnd_phonemes = (float *)(io + o_bph);
-        bt.d_bnd_slab = (unsigned long long *)(io + o_bsl);
-        bt.d_bnd_par = (const uint32_t *)(d_in + i_bpar);
-        bt.d_bnd_table = bnd_table;
-    }
-    if (pit)
-    {
-        bt.d_pit_frames = (zv::PitchFrameRow *)(io + o_pfr);
-        bt.d_pit_phonemes = (zv::PitchPhonemeRow *)(io + o_pph);
-        bt.d_pit_par = (const uint32_t *)(d_in + i_ppar);
-    }
-    if (flt)
-    {
-        bt.d_flt_par = (const uint32_t *)(d_in + i_fpar);
-        M.reserve_batch(bt);       // the arena with the filter-input region (Model::voc_layout), ahead of everything enqueued
-    }
+    bt.wave = zv::wave_bind(ask, wo, d_in, io, (const int32_t *)(io + o_nf), bands_table);
+    // the arena, ahead of everything enqueued: with the stages bound (a filter adds its input region to the vocoder's layout) and the scan
+    // not yet (without Batch::d_cum the encoder's layout keeps it in the arena), so one reservation asks for the largest of each
+    M.reserve_batch(bt);
+    // an envelope's knots pass and a table stage's phonemes pass read the scan behind the vocoder
+    if (dur || bt.wave.needs_scan()) bt.d_cum = (int32_t *)(io + o_cum);
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
     if (M.dec_plan(bt).runs) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
-    if (vol)
-    {
-        bt.d_vol = (const float *)(d_in + i_vol);
-        bt.d_levels = (zv::LevelRow *)(io + o_lvl);
-        bt.d_nframes = (const int32_t *)(io + o_nf);
-    }
-    if (env)
-    {
-        bt.d_env_gain = (const float *)(d_in + i_eg);
-        bt.d_env = (const int32_t *)(d_in + i_env);
-        bt.d_nframes = (const int32_t *)(io + o_nf);
-    }
     int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(d_in + i_ids), *d_pun = (int32_t *)(d_in + i_pun);
     float *d_sty = (float *)(d_in + i_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
     int32_t *h_nf = (int32_t *)(pin + p_nf), *h_cum = dur ? (int32_t *)(pin + p_cum) : nullptr;
     char *h_wav = pin + p_wav;
-    zv_level *h_lvl = vol ? (zv_level *)(pin + p_lvl) : nullptr;
-    zv_frame_level *h_cfr = ctr_f ? (zv_frame_level *)(pin + p_cfr) : nullptr, *h_cph = ctr_p ? (zv_frame_level *)(pin + p_cph) : nullptr;
-    zv_pitch_frame *h_pfr = pit_f ? (zv_pitch_frame *)(pin + p_pfr) : nullptr;
-    zv_pitch_phoneme *h_pph = pit_p ? (zv_pitch_phoneme *)(pin + p_pph) : nullptr;
-    float *h_bfr = bnd_f ? (float *)(pin + p_bfr) : nullptr, *h_bph = bnd_p ? (float *)(pin + p_bph) : nullptr;
-    const size_t brs = zv::BANDS_ROW_STRIDE;
-    // the contour rows and the pitch rows of utterances [u0, u1) travel behind their waveforms on stream `st`: frame rows packed like the waveforms
-    // (a frame row per hop samples), phoneme rows like the tokens
-    auto contour_download = [&](uint32_t u0, uint32_t u1, hipStream_t st) {
-        const size_t f0 = pb.woff[u0] / (hop * 4), f1 = u1 < r.count ? pb.woff[u1] / (hop * 4) : frame_rows;
-        const size_t n0 = pb.noff[u0], n1 = pb.noff[u1];
-        if (h_cfr && f1 > f0)
-            ZV_HIP(hipMemcpyAsync(h_cfr + f0, bt.d_ctr_frames + f0, (f1 - f0) * sizeof(zv_frame_level), hipMemcpyDeviceToHost, st));
-        if (h_cph && n1 > n0)
-            ZV_HIP(hipMemcpyAsync(h_cph + n0, bt.d_ctr_phonemes + n0, (n1 - n0) * sizeof(zv_frame_level), hipMemcpyDeviceToHost, st));
-        if (h_pfr && f1 > f0)
-            ZV_HIP(hipMemcpyAsync(h_pfr + f0, bt.d_pit_frames + f0, (f1 - f0) * sizeof(zv_pitch_frame), hipMemcpyDeviceToHost, st));
-        if (h_pph && n1 > n0)
-            ZV_HIP(hipMemcpyAsync(h_pph + n0, bt.d_pit_phonemes + n0, (n1 - n0) * sizeof(zv_pitch_phoneme), hipMemcpyDeviceToHost, st));
-        if (h_bfr && f1 > f0)
-            ZV_HIP(hipMemcpyAsync(h_bfr + f0 * brs, bt.d_bnd_frames + f0 * brs, (f1 - f0) * brs * 4, hipMemcpyDeviceToHost, st));
-        if (h_bph && n1 > n0)
-            ZV_HIP(hipMemcpyAsync(h_bph + n0 * brs, bt.d_bnd_phonemes + n0 * brs, (n1 - n0) * brs * 4, hipMemcpyDeviceToHost, st));
+    wave_tables(r, ask, wo, io, pin, h_in, wo, pb.tables, pb.dst);      // (the struct arrays are read here, the tables are written in batch_finish)
+    // the table rows of utterances [u0, u1) travel behind their waveforms on stream `st`; the per-utterance tables (whole) follow the last kernel
+    auto tables_download = [&](uint32_t u0, uint32_t u1, hipStream_t st, bool whole) {
+        for (const RowTable &t : pb.tables)
+        {
+            if ((t.rows == zv::ROWS_UTTERANCE) != whole) continue;
+            const size_t a = pb.first_row(t.rows, u0), b = u1 < r.count ? pb.first_row(t.rows, u1) : zv::WaveRows{r.count, ntot, frame_rows}[t.rows];
+            rows_download(t, a, b - a, t.host + a * t.dev_row, t.dev_row, st);
+        }
     };
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
@@ -1150,8 +998,8 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
             ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream()));
             if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream()));
             ZV_HIP(hipMemcpyAsync(h_wav, d_wav, wav_bytes, hipMemcpyDeviceToHost, M.stream()));
-            if (vol) ZV_HIP(hipMemcpyAsync(h_lvl, io + o_lvl, (size_t)bt.nseg * sizeof(zv_level), hipMemcpyDeviceToHost, M.stream()));
-            contour_download(0, r.count, M.stream());
+            tables_download(0, r.count, M.stream(), true);
+            tables_download(0, r.count, M.stream(), false);
             ZV_HIP(hipEventRecord(M.tail_event(1), M.stream()));
         }
         else
@@ -1173,12 +1021,12 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
                 ZV_HIP(hipEventRecord(M.tail_event(2 * g), M.stream()));
                 ZV_HIP(hipStreamWaitEvent(cs, M.tail_event(2 * g), 0));
                 ZV_HIP(hipMemcpyAsync(h_wav + o0, (const char *)d_wav + o0, o1 - o0, hipMemcpyDeviceToHost, cs));
-                contour_download(u0, u1, cs);
+                tables_download(u0, u1, cs, false);
                 ZV_HIP(hipEventRecord(M.tail_event(2 * g + 1), cs));
             }
             ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream()));
-            // the level rows of every group, behind the last group's kernels (batch_finish waits for the lane's stream)
-            if (vol) ZV_HIP(hipMemcpyAsync(h_lvl, io + o_lvl, (size_t)bt.nseg * sizeof(zv_level), hipMemcpyDeviceToHost, M.stream()));
+            // the per-utterance rows of every group, behind the last group's kernels (batch_finish waits for the lane's stream)
+            tables_download(0, r.count, M.stream(), true);
         }
     }
     catch (...)
@@ -1195,22 +1043,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     pb.n_frames = r.n_frames;
     pb.h_wav = h_wav;
     pb.h_nf = h_nf;
-    pb.hop = hop;
     pb.h_cum = h_cum;
-    pb.h_lvl = h_lvl;
-    pb.levels = r.levels;
-    pb.h_cfr = h_cfr;
-    pb.h_cph = h_cph;
-    if (ctr) pb.contour.assign(r.contour, r.contour + r.count);      // the struct array is read here, the tables are written in batch_finish
-    else pb.contour.clear();
-    pb.h_pfr = h_pfr;
-    pb.h_pph = h_pph;
-    if (pit) pb.pitch.assign(r.pitch, r.pitch + r.count);
-    else pb.pitch.clear();
-    pb.h_bfr = h_bfr;
-    pb.h_bph = h_bph;
-    if (bnd) pb.bands.assign(r.bands, r.bands + r.count);
-    else pb.bands.clear();
     pb.N.assign(r.n, r.n + r.count);
     if (dur) pb.dur.assign(r.durations, r.durations + r.count);
     else pb.dur.clear();
@@ -1243,28 +1076,17 @@ static void batch_finish(zv_model *m, int lane)
     if (pb.n_frames)
         for (uint32_t u = 0; u < pb.n_utt; u++) pb.n_frames[u] = (uint32_t)pb.h_nf[u];
     if (pb.h_cum) durations_from_cum(pb.h_cum, pb.n_utt, pb.N.data(), pb.T.data(), pb.dur.data());
-    if (pb.h_lvl && pb.levels) memcpy(pb.levels, pb.h_lvl, (size_t)pb.n_utt * sizeof(zv_level));
-    for (uint32_t u = 0; u < pb.n_utt && !pb.contour.empty(); u++)
-    {
-        const zv_contour &c = pb.contour[u];
-        if (c.frames) memcpy(c.frames, pb.h_cfr + pb.woff[u] / (pb.hop * 4), (size_t)pb.T[u] * sizeof(zv_frame_level));
-        if (c.phonemes) memcpy(c.phonemes, pb.h_cph + pb.noff[u], (size_t)pb.N[u] * sizeof(zv_frame_level));
-    }
-    for (uint32_t u = 0; u < pb.n_utt && !pb.pitch.empty(); u++)
-    {
-        const zv_pitch &c = pb.pitch[u];
-        if (c.frames) memcpy(c.frames, pb.h_pfr + pb.woff[u] / (pb.hop * 4), (size_t)pb.T[u] * sizeof(zv_pitch_frame));
-        if (c.phonemes) memcpy(c.phonemes, pb.h_pph + pb.noff[u], (size_t)pb.N[u] * sizeof(zv_pitch_phoneme));
-    }
-    // band rows: the staging block keeps BANDS_ROW_STRIDE entries per row, the caller receives the first n_bands of each
-    for (uint32_t u = 0; u < pb.n_utt && !pb.bands.empty(); u++)
-    {
-        const zv_bands &c = pb.bands[u];
-        const size_t nb = pb.bands_nb[u], brs = zv::BANDS_ROW_STRIDE;
-        const float *fr = pb.h_bfr ? pb.h_bfr + pb.woff[u] / (pb.hop * 4) * brs : nullptr, *ph = pb.h_bph ? pb.h_bph + pb.noff[u] * brs : nullptr;
-        for (size_t f = 0; c.frames && f < pb.T[u]; f++) memcpy(c.frames + f * nb, fr + f * brs, nb * 4);
-        for (size_t i = 0; c.phonemes && i < pb.N[u]; i++) memcpy(c.phonemes + i * nb, ph + i * brs, nb * 4);
-    }
+    for (size_t k = 0; k < pb.tables.size(); k++)
+        for (uint32_t u = 0; u < pb.n_utt; u++)
+        {
+            const RowTable &t = pb.tables[k];
+            const RowDst &d = pb.dst[k * pb.n_utt + u];
+            if (!d.p) continue;
+            const char *src = t.host + pb.first_row(t.rows, u) * t.dev_row;
+            const size_t count = pb.row_count(t.rows, u);
+            if (d.row == t.dev_row) memcpy(d.p, src, count * d.row);
+            else for (size_t i = 0; i < count; i++) memcpy((char *)d.p + i * d.row, src + i * t.dev_row, d.row);
+        }
 }
 
 // how many utterances from `a` on form one launch group: up to 64 utterances / 64 Ki frames of capacity
@@ -1545,7 +1367,25 @@ zv_status zv_synthesize_batch_begin_pitch(zv_model *m, uint32_t lane, uint32_t n
                                  durations, fitted != 0, target_frames, volume, levels, envelope, contour, pitch});
 }
 
-// The stand-alone meter: a host waveform through the frames pass, eagerly, on lane 0, as one inline segment.
+// The stand-alone passes (zv_pitch_track, zv_band_levels, zv_filter_wave): a host waveform wav[T * hop] in, one pass over it as one
+// inline segment, eagerly, on lane 0, rows out.  I/O block: [waveform][rows][slab][parameter row]; of each of the T device rows of
+// dev_row bytes the caller receives the first out_row.  launch(d_wav, d_rows, d_slab, d_par, segment) enqueues the pass.
+extern "C++" template <typename Launch>
+static void wave_pass(Model &M, const float *wav, uint32_t T, const void *par, size_t b_par, size_t dev_row, size_t slab_row, void *out,
+                      size_t out_row, Launch launch)
+{
+    const size_t hop = M.hp.audio_hop_size, b_wav = (size_t)T * hop * 4;
+    Layout L;
+    const size_t o_wav = L.at(b_wav), o_rows = L.at(T * dev_row), o_slab = L.at(T * slab_row), o_par = L.at(b_par);
+    char *io = (char *)M.io_scratch(L.size());
+    ZV_HIP(hipMemcpyAsync(io + o_wav, wav, b_wav, hipMemcpyHostToDevice, M.stream()));
+    ZV_HIP(hipMemcpyAsync(io + o_par, par, b_par, hipMemcpyHostToDevice, M.stream()));
+    ZV_HIP(launch((const float *)(io + o_wav), io + o_rows, io + o_slab, (const uint32_t *)(io + o_par), zv::Segs{nullptr, 1, (int)T, zv::Seg{0, (int32_t)T, 0, 0}}));
+    rows_download(RowTable{io + o_rows, dev_row, nullptr, zv::ROWS_FRAME}, 0, T, out, out_row, M.stream());
+    M.sync();
+}
+
+// The stand-alone meter: a host waveform through the frames pass (wave_pass).
 zv_status zv_pitch_track(zv_model *m, const float *wav, uint32_t T, const zv_pitch *pitch)
 {
     return guarded([&] {
@@ -1564,19 +1404,11 @@ zv_status zv_pitch_track(zv_model *m, const float *wav, uint32_t T, const zv_pit
             zv::fail(e.status, "zv_pitch_track: %s", e.what());
         }
         use_lane0(m);
-        const size_t hop = M.hp.audio_hop_size, b_wav = (size_t)T * hop * 4, b_rows = (size_t)T * sizeof(zv::PitchFrameRow);
-        Layout L;
-        const size_t o_wav = L.at(b_wav), o_rows = L.at(b_rows), o_slab = L.at((size_t)T * sizeof(zv::PitchSlabRow)),
-                     o_par = L.at(zv::PITCH_PARAM_STRIDE * 4);
-        char *io = (char *)M.io_scratch(L.size());
         const uint32_t prow[zv::PITCH_PARAM_STRIDE] = {q.min_lag, q.max_lag, q.window, zv::level_bits(q.voiced_threshold)};
-        ZV_HIP(hipMemcpyAsync(io + o_wav, wav, b_wav, hipMemcpyHostToDevice, M.stream()));
-        ZV_HIP(hipMemcpyAsync(io + o_par, prow, sizeof(prow), hipMemcpyHostToDevice, M.stream()));
-        const zv::Segs one{nullptr, 1, (int)T, zv::Seg{0, (int32_t)T, 0, 0}};
-        ZV_HIP(zv::launch_pitch_frames(M.stream(), (const float *)(io + o_wav), io + o_slab, (zv::PitchFrameRow *)(io + o_rows),
-                                       (const uint32_t *)(io + o_par), one, (int)hop, (int)M.hp.audio_sampling_rate));
-        ZV_HIP(hipMemcpyAsync(pitch->frames, io + o_rows, b_rows, hipMemcpyDeviceToHost, M.stream()));
-        M.sync();
+        wave_pass(M, wav, T, prow, sizeof(prow), sizeof(zv::PitchFrameRow), sizeof(zv::PitchSlabRow), pitch->frames, sizeof(zv_pitch_frame),
+                  [&](const float *d_wav, char *rows, char *slab, const uint32_t *d_par, const zv::Segs &one) {
+                      return zv::launch_pitch_frames(M.stream(), d_wav, slab, (zv::PitchFrameRow *)rows, d_par, one, (int)M.hp.audio_hop_size, (int)M.hp.audio_sampling_rate);
+                  });
     });
 }
 
@@ -1647,8 +1479,7 @@ zv_status zv_synthesize_batch_begin_filter(zv_model *m, uint32_t lane, uint32_t 
                                  durations, fitted != 0, target_frames, volume, levels, envelope, contour, pitch, bands, filter});
 }
 
-// The stand-alone filter: a host waveform through the filter pass, eagerly, on lane 0, as one inline segment.  Input and output have
-// regions of their own in the I/O block, so out may be wav.
+// The stand-alone filter: a host waveform through the filter pass (wave_pass); out may be wav.
 zv_status zv_filter_wave(zv_model *m, const float *wav, uint32_t T, const zv_filter *filter, float *out)
 {
     return guarded([&] {
@@ -1664,18 +1495,12 @@ zv_status zv_filter_wave(zv_model *m, const float *wav, uint32_t T, const zv_fil
             zv::fail(e.status, "zv_filter_wave: %s", e.what());
         }
         use_lane0(m);
-        const size_t hop = M.hp.audio_hop_size, b_wav = (size_t)T * hop * 4;
         std::vector<uint32_t> frow(zv::FILTER_PARAM_STRIDE);
         zv::filter_pack(filter->taps, filter->n_taps, frow.data());
-        Layout L;
-        const size_t o_in = L.at(b_wav), o_out = L.at(b_wav), o_par = L.at(frow.size() * 4);
-        char *io = (char *)M.io_scratch(L.size());
-        ZV_HIP(hipMemcpyAsync(io + o_in, wav, b_wav, hipMemcpyHostToDevice, M.stream()));
-        ZV_HIP(hipMemcpyAsync(io + o_par, frow.data(), frow.size() * 4, hipMemcpyHostToDevice, M.stream()));
-        const zv::Segs one{nullptr, 1, (int)T, zv::Seg{0, (int32_t)T, 0, 0}};
-        ZV_HIP(zv::launch_filter(M.stream(), (const float *)(io + o_in), (float *)(io + o_out), (const uint32_t *)(io + o_par), one, one, (int)hop));
-        ZV_HIP(hipMemcpyAsync(out, io + o_out, b_wav, hipMemcpyDeviceToHost, M.stream()));
-        M.sync();
+        const size_t b_frame = (size_t)M.hp.audio_hop_size * 4;      // the rows of this pass: the filtered waveform, a frame each
+        wave_pass(M, wav, T, frow.data(), frow.size() * 4, b_frame, 0, out, b_frame, [&](const float *d_wav, char *rows, char *, const uint32_t *d_par, const zv::Segs &one) {
+            return zv::launch_filter(M.stream(), d_wav, (float *)rows, d_par, one, one, (int)M.hp.audio_hop_size);
+        });
     });
 }
 
@@ -1699,7 +1524,7 @@ zv_status zv_filter_design(uint32_t n_bands, const uint32_t *edges, const float 
     });
 }
 
-// The stand-alone meter: a host waveform through the frames pass, eagerly, on lane 0, as one inline segment.
+// The stand-alone meter: a host waveform through the frames pass (wave_pass).
 zv_status zv_band_levels(zv_model *m, const float *wav, uint32_t T, const zv_bands *bands)
 {
     return guarded([&] {
@@ -1719,18 +1544,10 @@ zv_status zv_band_levels(zv_model *m, const float *wav, uint32_t T, const zv_ban
         }
         use_lane0(m);
         const void *table = M.bands_table();
-        const size_t hop = M.hp.audio_hop_size, b_wav = (size_t)T * hop * 4, b_rows = (size_t)T * zv::BANDS_ROW_STRIDE * 4;
-        Layout L;
-        const size_t o_wav = L.at(b_wav), o_rows = L.at(b_rows), o_slab = L.at(2 * b_rows), o_par = L.at(sizeof(brow));
-        char *io = (char *)M.io_scratch(L.size());
-        ZV_HIP(hipMemcpyAsync(io + o_wav, wav, b_wav, hipMemcpyHostToDevice, M.stream()));
-        ZV_HIP(hipMemcpyAsync(io + o_par, brow, sizeof(brow), hipMemcpyHostToDevice, M.stream()));
-        const zv::Segs one{nullptr, 1, (int)T, zv::Seg{0, (int32_t)T, 0, 0}};
-        ZV_HIP(zv::launch_bands_frames(M.stream(), (const float *)(io + o_wav), table, io + o_slab, (float *)(io + o_rows),
-                                       (const uint32_t *)(io + o_par), one, (int)hop));
-        ZV_HIP(hipMemcpy2DAsync(bands->frames, (size_t)brow[0] * 4, io + o_rows, zv::BANDS_ROW_STRIDE * 4, (size_t)brow[0] * 4, T,
-                                hipMemcpyDeviceToHost, M.stream()));
-        M.sync();
+        wave_pass(M, wav, T, brow, sizeof(brow), zv::BANDS_ROW_STRIDE * 4, zv::BANDS_ROW_STRIDE * 8, bands->frames, (size_t)brow[0] * 4,
+                  [&](const float *d_wav, char *rows, char *slab, const uint32_t *d_par, const zv::Segs &one) {
+                      return zv::launch_bands_frames(M.stream(), d_wav, table, slab, (float *)rows, d_par, one, (int)M.hp.audio_hop_size);
+                  });
     });
 }
 

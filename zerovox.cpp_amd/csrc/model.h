@@ -13,6 +13,7 @@
 #include "common.h"
 #include "gguf_reader.h"
 #include "kernels.h"
+#include "wave_stages.h"
 
 namespace zv
 {
@@ -30,12 +31,11 @@ struct DeviceArena
 {
     char  *base = nullptr;
     size_t cap = 0, used = 0;
-    static size_t align(size_t off) { return (off + 255) & ~(size_t)255; }     // every region starts on a 256-byte boundary
     // an arena that only counts: no memory behind it, take() hands out null and `used` ends up as the bytes a layout needs
     static DeviceArena counter() { return DeviceArena{nullptr, SIZE_MAX, 0}; }
     void  *take(size_t bytes)
     {
-        const size_t a = align(used);
+        const size_t a = region_align(used);      // every region starts on a 256-byte boundary (wave_stages.h)
         if (a + bytes > cap) fail(ZV_ERR_OOM, "device arena overflow (%zu + %zu > %zu)", a, bytes, cap);
         used = a + bytes;
         return base ? base + a : nullptr;
@@ -56,7 +56,7 @@ struct ProfEntry
 // CAPACITIES: they size grids and the arena, the real extents are read from the tables on the device, so one captured
 // graph serves every batch that fits.  A single utterance needs no table (inline segment).
 // A NEW FIELD: decide in same_schedule() below whether it keys a captured graph; whatever changes a grid, an arena offset or a kernel
-// argument does.  Deliberately not keyed: n_real (only host-side checks read it, the kernels take the real extents from the tables);
+// argument does.  A pointer of a waveform stage belongs in the group (`wave`, wave_stages.h), which is keyed as a whole.  Deliberately not keyed: n_real (only host-side checks read it, the kernels take the real extents from the tables);
 // the destination and size of chain_dev's input upload (they follow from the keyed buffers).
 struct Batch
 {
@@ -91,47 +91,9 @@ struct Batch
     // encoder launches fit_durations_kernel ahead of the length regulator (d_ctl and d_pctl are then both set).  Keyed: one launch
     // more.  WHICH utterances have a target, and its value, is read at run time: a replay picks up new targets.
     bool has_targets = false;
-    // Volume controls (include/zerovox_amd.h "volume controls", level.h), all three set or none: the volume rows, f32 [nseg]
-    // [LEVEL_VOL_STRIDE] in HBM, the level rows the vocoder's last step stores, LevelRow [nseg] in HBM outside the arena, and the
-    // regulator's frame counts [nseg] on the device (what tells speech from padding).  Keyed like d_ctl: with them the vocoder
-    // ends in two launches more; the VALUES are read at run time, so a replay picks up new ones.
-    const float   *d_vol = nullptr;
-    LevelRow      *d_levels = nullptr;
-    const int32_t *d_nframes = nullptr;
-    // Amplitude envelope (include/zerovox_amd.h "amplitude envelope", envelope.h), both set or none: the per-phoneme gains, f32 [n_rows]
-    // in HBM indexed by absolute token row like d_pctl, and the envelope rows, int32 [nseg][ENV_CTL_STRIDE].  With them d_cum (the
-    // knots pass searches the regulator's scan after the decoder and the vocoder have reused the arena) and d_nframes are set too.
-    // Keyed like d_ctl: the vocoder ends in two launches more, ahead of the volume passes; the VALUES are read at run time.
-    const float   *d_env_gain = nullptr;
-    const int32_t *d_env = nullptr;
-    // Level contour (include/zerovox_amd.h "level contour", contour.h), both set or none: the frame rows, ContourRow [t_rows], and the
-    // phoneme rows, ContourRow [n_rows], in HBM outside the arena, indexed by absolute frame row / token row.  With them d_cum is set
-    // (the phonemes pass reads the regulator's scan behind the vocoder).  Keyed like d_vol: the vocoder ends in two launches more,
-    // behind the volume passes.  WHICH rows a caller receives is the host's business at download time: every row is written.
-    ContourRow *d_ctr_frames = nullptr;
-    ContourRow *d_ctr_phonemes = nullptr;
-    // Pitch track (include/zerovox_amd.h "pitch track", pitch.h), all three set or none: the frame rows, PitchFrameRow [t_rows], the
-    // phoneme rows, PitchPhonemeRow [n_rows], both in HBM outside the arena and indexed by absolute frame row / token row, and the
-    // parameter rows, uint32 [nseg][PITCH_PARAM_STRIDE], resolved on the host and uploaded with the call: the VALUES are read at run
-    // time.  With them d_cum is set.  Keyed like the contour: the vocoder ends in two launches more, behind the contour's.
-    PitchFrameRow   *d_pit_frames = nullptr;
-    PitchPhonemeRow *d_pit_phonemes = nullptr;
-    const uint32_t  *d_pit_par = nullptr;
-    // Band levels (include/zerovox_amd.h "band levels", bands.h), all five set or none: the frame rows, f32 [t_rows][BANDS_ROW_STRIDE],
-    // the phoneme rows, f32 [n_rows][BANDS_ROW_STRIDE], the kept powers the frames pass leaves for the phonemes pass, u64 [t_rows]
-    // [BANDS_ROW_STRIDE], all in HBM outside the arena and indexed by absolute frame row / token row, the parameter rows, uint32 [nseg]
-    // [BANDS_PARAM_STRIDE], resolved on the host and uploaded with the call (the VALUES are read at run time), and the twiddle table
-    // (Model::bands_table).  With them d_cum is set.  Keyed like the pitch track: the vocoder ends in two launches more, behind its.
-    float              *d_bnd_frames = nullptr;
-    float              *d_bnd_phonemes = nullptr;
-    unsigned long long *d_bnd_slab = nullptr;
-    const uint32_t     *d_bnd_par = nullptr;
-    const void         *d_bnd_table = nullptr;
-    // Waveform filter (include/zerovox_amd.h "waveform filter", filter.h): the parameter rows, uint32 [nseg][FILTER_PARAM_STRIDE], packed
-    // on the host and uploaded with the call (the VALUES, tap counts included, are read at run time), or null: no filter.  Keyed like
-    // d_vol: with it the vocoder's last convolution writes the filter-input region of the arena (VocLayout::filter_in, carved only
-    // then) and one launch more, ahead of the envelope's, writes the waveform.
-    const uint32_t     *d_flt_par = nullptr;
+    // The waveform stages behind the vocoder's output convolution (wave_stages.h: volume, envelope, contour, pitch track, band levels,
+    // filter): their device pointers, all null where a stage is off.  Keyed as a whole, bytewise; a sub-batch takes its group().
+    WaveStages wave;
 
     static Batch single(uint32_t N, uint32_t T, uint32_t num_phonemes)
     {
@@ -154,17 +116,14 @@ struct Batch
     // the frames the decoder and the vocoder run over: the live table in fitted mode, else the capacity
     Segs frames() const { return d_frm_live ? Segs{d_frm_live, nseg, t_max, frm1} : frames_cap(); }
     // what of a Batch a captured schedule depends on: the capacities (grids, arena layout), the table pointers, the inline segments
-    // where there is no table, the four optional pointers that change the kernels' arguments and the flag that adds a launch
+    // where there is no table, the optional pointers that change the kernels' arguments, the flag that adds a launch and the waveform
+    // stages' group
     bool same_schedule(const Batch &o) const
     {
         return nseg == o.nseg && n_max == o.n_max && t_max == o.t_max && n_rows == o.n_rows && t_rows == o.t_rows && d_tok == o.d_tok &&
                d_frm == o.d_frm && (d_tok || memcmp(&tok1, &o.tok1, sizeof(Seg)) == 0) && (d_frm || memcmp(&frm1, &o.frm1, sizeof(Seg)) == 0) &&
                d_ctl == o.d_ctl && d_pctl == o.d_pctl && d_cum == o.d_cum && d_frm_live == o.d_frm_live && has_targets == o.has_targets &&
-               d_dec_runs == o.d_dec_runs && d_vol == o.d_vol && d_levels == o.d_levels && d_nframes == o.d_nframes && d_env_gain == o.d_env_gain &&
-               d_env == o.d_env && d_ctr_frames == o.d_ctr_frames && d_ctr_phonemes == o.d_ctr_phonemes &&
-               d_pit_frames == o.d_pit_frames && d_pit_phonemes == o.d_pit_phonemes && d_pit_par == o.d_pit_par &&
-               d_bnd_frames == o.d_bnd_frames && d_bnd_phonemes == o.d_bnd_phonemes && d_bnd_slab == o.d_bnd_slab && d_bnd_par == o.d_bnd_par &&
-               d_bnd_table == o.d_bnd_table && d_flt_par == o.d_flt_par;
+               d_dec_runs == o.d_dec_runs && wave == o.wave;
     }
 };
 
@@ -406,7 +365,7 @@ class Model
         // pitch track (kernels.h launch_pitch_frames): {Fq, voiced} per frame row, 8 bytes each, t_rows entries, carved likewise
         void *pitch_slab;
         // waveform filter (kernels.h launch_filter): the vocoder's waveform ahead of the filter, t_rows * hop floats indexed like the
-        // waveform, carved likewise and only where the batch carries a filter (Batch::d_flt_par); null otherwise
+        // waveform, carved likewise and only where the batch carries a filter (WaveStages::d_flt_par); null otherwise
         float *filter_in;
         float *mel_c; int32_t *eq; Seg *runs;
     };
@@ -424,6 +383,8 @@ class Model
     };
     struct EncLayout { int Vp; float *x, *y, *qkv, *o, *f, *va, *vb; _Float16 *hh; EncoderTaps t; };
     VocLayout voc_layout(DeviceArena &a, const Batch &b) const;
+    // the launches of the waveform stages over a (sub-)batch's finished waveform (wave_stages.cpp), behind vocode_group's output conv
+    void wave_stage_launches(const Batch &b, const VocLayout &lay, float *d_wav, int rate, int seg0);
     DecLayout dec_layout(DeviceArena &a, const Batch &b) const;
     EncLayout enc_layout(DeviceArena &a, const Batch &b) const;
     // the arena's one margin, behind the largest layout: reads that run past a stage's last buffer stay inside the allocation

@@ -75,7 +75,7 @@ Model::VocLayout Model::voc_layout(DeviceArena &a, const Batch &bt) const
     v.contour_slab = a.take(bt.t_rows * 16);
     v.pitch_slab = a.take(bt.t_rows * sizeof(PitchSlabRow));
     // the filter's input: the one region that exists only where a call asks for it (a waveform's worth of arena)
-    v.filter_in = bt.d_flt_par ? a.take_n<float>(bt.t_rows * hp.audio_hop_size) : nullptr;
+    v.filter_in = bt.wave.d_flt_par ? a.take_n<float>(bt.t_rows * hp.audio_hop_size) : nullptr;
     v.runs = a.take_n<Seg>(bt.nseg);
     return v;
 }
@@ -109,16 +109,7 @@ void Model::vocode_tail(const Batch &bt, const float *d_mel, float *d_wav, int g
     Batch sub = bt;
     sub.d_frm = bt.d_frm + g0;
     if (bt.d_frm_live) sub.d_frm_live = bt.d_frm_live + g0;
-    if (bt.d_vol)
-    {
-        sub.d_vol = bt.d_vol + (size_t)g0 * LEVEL_VOL_STRIDE;
-        sub.d_levels = bt.d_levels + g0;
-    }
-    if (bt.d_nframes) sub.d_nframes = bt.d_nframes + g0;
-    if (bt.d_pit_par) sub.d_pit_par = bt.d_pit_par + (size_t)g0 * PITCH_PARAM_STRIDE;      // (the rows go by absolute frame / token row)
-    if (bt.d_bnd_par) sub.d_bnd_par = bt.d_bnd_par + (size_t)g0 * BANDS_PARAM_STRIDE;      // (likewise)
-    if (bt.d_flt_par) sub.d_flt_par = bt.d_flt_par + (size_t)g0 * FILTER_PARAM_STRIDE;     // (likewise)
-    if (bt.d_env) sub.d_env = bt.d_env + (size_t)g0 * ENV_CTL_STRIDE;          // (the gains and the scan go by absolute token row)
+    sub.wave = bt.wave.group(g0);
     sub.nseg = cnt;
     vocode_group(sub, d_mel, d_wav, 2, g0);
 }
@@ -430,10 +421,10 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
     // V3: (sum of branches)/3 -> leaky_relu(0.01) -> conv k7 (C -> 1) + b -> tanh          (:315-345)
     skip_launch_ = part == 1;
     // Waveform filter (filter.h): with a request the convolution, the fill and the fitted tail's zeros go to the filter-input region
-    // and the filter writes d_wav, so nothing behind it changes.  Never under a one-layer tap.
-    const bool filtered = bt.d_flt_par && dbg_layer.kind < 0;
-    float *const wav_out = d_wav;
-    if (filtered) d_wav = lay.filter_in;
+    // and the filter pass writes d_wav, so nothing behind it changes.  Never under a one-layer tap.
+    const bool filtered = bt.wave.d_flt_par && dbg_layer.kind < 0;
+    if (filtered && !lay.filter_in) fail(ZV_ERR_DEVICE, "internal: a filter without its input region");
+    float *const conv_out = filtered ? lay.filter_in : d_wav;
     {
         OutConvArgs a;
         a.x0 = prev_merged ? prev_merged : prev_y[0];
@@ -447,7 +438,7 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
         a.slope = (float)1e-2;
         a.w = voc_.out_w;
         a.bias = voc_.out_b;
-        a.out = d_wav;
+        a.out = conv_out;
         a.segs = fr;
         a.rate = rate;
         a.runs = runs;
@@ -460,123 +451,13 @@ void Model::vocode_group(const Batch &bt, const float *d_mel, float *d_wav, int 
             a.pscale = 1.0f;
         }
         ZV_LAUNCH("voc_output_conv", 12.0 * La * C + 4.0 * La, 2.0 * La * C * a.K, launch_out_conv(stream(), a));
-        if (runs) ZV_LAUNCH("voc_run_fill", 8.0 * (L - La), 0.0, launch_voc_run_fill(stream(), d_wav, fr, rate));
-        if (dbg_layer.kind == ZV_LAYER_VOC_OUTPUT) dbg_extract(d_wav, 1, 1, L);
+        if (runs) ZV_LAUNCH("voc_run_fill", 8.0 * (L - La), 0.0, launch_voc_run_fill(stream(), conv_out, fr, rate));
+        if (dbg_layer.kind == ZV_LAYER_VOC_OUTPUT) dbg_extract(conv_out, 1, 1, L);
         // fitted: the output conv stops at each utterance's last frame; the rest of its capacity is silence
-        if (bt.d_frm_live) ZV_LAUNCH("voc_zero_tail", 4.0 * La, 0.0, launch_zero_tail(stream(), d_wav, 1, bt.frames_cap(), fr, rate));
+        if (bt.d_frm_live) ZV_LAUNCH("voc_zero_tail", 4.0 * La, 0.0, launch_zero_tail(stream(), conv_out, 1, bt.frames_cap(), fr, rate));
     }
-    if (filtered)
-    {
-        if (!lay.filter_in) fail(ZV_ERR_DEVICE, "internal: a filter without its input region");
-        const Segs cap = bt.frames_cap();
-        const double cap_samples = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg) * rate;
-        // algorithmic bytes: the capacity read and written once.  Operations, by capacity and at 255 taps (the counts are the device's: a
-        // caller's taps change the work, not this price): 2 per multiply-add.
-        ZV_LAUNCH("voc_filter", 8.0 * cap_samples, 2.0 * 255.0 * cap_samples,
-                  launch_filter(stream(), lay.filter_in, wav_out, bt.d_flt_par, cap, bt.frames(), rate));
-        d_wav = wav_out;
-    }
-
-    // Amplitude envelope (envelope.h): the waveform of these segments is final, so build the knots from the regulator's scan and scale
-    // the capacity — ahead of the volume passes, which measure what the caller receives.  Only where the call carries an envelope;
-    // never under a one-layer tap.
-    if (bt.d_env && dbg_layer.kind < 0)
-    {
-        if (!bt.d_cum || !bt.d_nframes || !bt.d_env_gain) fail(ZV_ERR_DEVICE, "internal: an envelope without the scan, the frame counts or the gains");
-        // (the hop was checked with the request, capi.cpp check_request; launch_env_apply refuses any other)
-        // Segment u of THIS call keeps its knots at row0 + u + f, u counted from the call's first segment: consecutive tail groups write
-        // overlapping ranges of the table.  That is sound only because a group's knots pass and apply pass run back to back on the lane's
-        // one stream, ahead of the next group's; groups on streams of their own would need the batch's segment index (seg0 + u) here.
-        const Segs cap = bt.frames_cap();
-        const Segs tk{bt.d_tok ? bt.d_tok + seg0 : nullptr, bt.nseg, bt.n_max, bt.tok1};
-        if (bt.t_rows + (size_t)bt.nseg > env_knot_entries(bt)) fail(ZV_ERR_DEVICE, "internal: envelope knot table too small");
-        const double cap_rows = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg);
-        // algorithmic bytes: the knots written (by capacity) and the scan and gains read once; the waveform read and written
-        ZV_LAUNCH("voc_env_knots", 4.0 * (cap_rows + bt.nseg) + 8.0 * std::min((double)bt.n_rows, (double)bt.n_max * bt.nseg), 0.0,
-                  launch_env_knots(stream(), bt.d_cum, bt.d_env_gain, bt.d_env, bt.d_nframes, lay.env_knots, tk, cap));
-        ZV_LAUNCH("voc_env_apply", 8.0 * cap_rows * rate, 0.0,
-                  launch_env_apply(stream(), d_wav, bt.d_nframes, lay.env_knots, bt.d_env, cap, rate));
-    }
-
-    // Volume controls (level.h): the waveform of these segments is final, so measure the speech and scale the capacity — per tail
-    // group, ahead of the group's download.  Only where the call carries volume; never under a one-layer tap.
-    if (bt.d_vol && dbg_layer.kind < 0)
-    {
-        const Segs cap = bt.frames_cap();
-        if ((size_t)bt.nseg * level_chunks(cap.max_rows, rate) > level_slab_entries(bt)) fail(ZV_ERR_DEVICE, "internal: level slab too small");
-        const double cap_samples = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg) * rate;
-        double speech_samples = cap_samples;
-        if (profiling && !skip_launch_)
-        {
-            // the profile states bytes moved: the speech the regulator produced (this path is eager and the host waits anyway)
-            std::vector<int32_t> nf((size_t)bt.nseg);
-            ZV_HIP(hipMemcpyAsync(nf.data(), bt.d_nframes, nf.size() * 4, hipMemcpyDeviceToHost, stream()));
-            ZV_HIP(hipStreamSynchronize(stream()));
-            speech_samples = 0;
-            for (int32_t f : nf) speech_samples += (double)std::min(std::max(f, 0), bt.t_max) * rate;
-        }
-        ZV_LAUNCH("voc_level_measure", 4.0 * speech_samples, 0.0, launch_level_measure(stream(), d_wav, bt.d_nframes, lay.level_slab, cap, rate));
-        ZV_LAUNCH("voc_level_apply", 8.0 * cap_samples, 0.0,
-                  launch_level_apply(stream(), d_wav, bt.d_nframes, lay.level_slab, bt.d_vol, bt.d_levels, cap, rate));
-    }
-
-    // Level contour (contour.h): behind the envelope and the volume passes, so it meters the waveform the caller receives — per tail
-    // group, ahead of the group's download.  Only where the call carries a contour; never under a one-layer tap.
-    if (bt.d_ctr_frames && dbg_layer.kind < 0)
-    {
-        if (!bt.d_cum || !bt.d_ctr_phonemes) fail(ZV_ERR_DEVICE, "internal: a contour without the scan or the phoneme rows");
-        // Slab entries and rows sit at a segment's ABSOLUTE frame row (the table's row0, which a sub-batch keeps) and absolute token
-        // row: consecutive tail groups write disjoint ranges.  Unlike the envelope's knot table this relies on no order between the
-        // groups, only on the phonemes pass running behind the frames pass of its own group on the lane's stream.
-        const Segs cap = bt.frames_cap();
-        const Segs tk{bt.d_tok ? bt.d_tok + seg0 : nullptr, bt.nseg, bt.n_max, bt.tok1};
-        const double cap_rows = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg);
-        const double tok_rows = std::min((double)bt.n_rows, (double)bt.n_max * bt.nseg);
-        // algorithmic bytes: the capacity's samples read once; the slab entries read (by capacity) and the phoneme rows written
-        ZV_LAUNCH("voc_contour_frames", 4.0 * cap_rows * rate, 0.0,
-                  launch_contour_frames(stream(), d_wav, lay.contour_slab, bt.d_ctr_frames, cap, rate));
-        ZV_LAUNCH("voc_contour_phonemes", 16.0 * cap_rows + 8.0 * tok_rows, 0.0,
-                  launch_contour_phonemes(stream(), bt.d_cum, lay.contour_slab, bt.d_ctr_phonemes, tk, cap, rate));
-    }
-
-    // Pitch track (pitch.h): behind everything that changes the waveform, like the contour and with its indexing — per tail group,
-    // ahead of the group's download.  Only where the call carries a pitch request; never under a one-layer tap.
-    if (bt.d_pit_frames && dbg_layer.kind < 0)
-    {
-        if (!bt.d_cum || !bt.d_pit_phonemes || !bt.d_pit_par) fail(ZV_ERR_DEVICE, "internal: a pitch track without the scan, the phoneme rows or the parameters");
-        const Segs cap = bt.frames_cap();
-        const Segs tk{bt.d_tok ? bt.d_tok + seg0 : nullptr, bt.nseg, bt.n_max, bt.tok1};
-        const double cap_rows = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg);
-        const double tok_rows = std::min((double)bt.n_rows, (double)bt.n_max * bt.nseg);
-        // algorithmic bytes: the capacity's samples read once, a slab entry and a row written per frame; the slab read and a row written
-        // per token.  Operations, by capacity and at the DEFAULT parameters (the values are the device's: a caller's lags change the
-        // work, not this price): 2 per multiply-add, window x (max_lag - min_lag + 3) multiply-adds per frame.
-        const double macs = 2.0 * (double)rate * (double)(hp.audio_sampling_rate / 63 - hp.audio_sampling_rate / 441 + 3);
-        ZV_LAUNCH("voc_pitch_frames", 4.0 * cap_rows * rate + 16.0 * cap_rows, 2.0 * macs * cap_rows,
-                  launch_pitch_frames(stream(), d_wav, lay.pitch_slab, bt.d_pit_frames, bt.d_pit_par, cap, rate, (int)hp.audio_sampling_rate));
-        ZV_LAUNCH("voc_pitch_phonemes", 8.0 * cap_rows + 8.0 * tok_rows, 0.0,
-                  launch_pitch_phonemes(stream(), bt.d_cum, lay.pitch_slab, bt.d_pit_phonemes, tk, cap));
-    }
-
-    // Band levels (bands.h): behind the pitch track's passes, with their indexing — per tail group, ahead of the group's download.  Only
-    // where the call carries a request; never under a one-layer tap.
-    if (bt.d_bnd_frames && dbg_layer.kind < 0)
-    {
-        if (!bt.d_cum || !bt.d_bnd_phonemes || !bt.d_bnd_slab || !bt.d_bnd_par || !bt.d_bnd_table)
-            fail(ZV_ERR_DEVICE, "internal: band levels without the scan, the phoneme rows, the slab, the parameters or the table");
-        const Segs cap = bt.frames_cap();
-        const Segs tk{bt.d_tok ? bt.d_tok + seg0 : nullptr, bt.nseg, bt.n_max, bt.tok1};
-        const double cap_rows = std::min((double)bt.t_rows, (double)bt.t_max * bt.nseg);
-        const double tok_rows = std::min((double)bt.n_rows, (double)bt.n_max * bt.nseg);
-        // algorithmic bytes: the capacity's samples read once, the table once per tile of frames, a slab row and a row written per
-        // frame; the slab read and a row written per token.  Operations: 2 per 8-bit multiply-add, both digit planes, 1 026 columns.
-        const double row_b = (double)BANDS_ROW_STRIDE;
-        ZV_LAUNCH("voc_bands_frames", 4.0 * cap_rows * rate + (double)BANDS_TABLE_BYTES * cap_rows / BANDS_TILE_FRAMES + 12.0 * row_b * cap_rows,
-                  2.0 * 2.0 * (double)BANDS_N * 2.0 * BANDS_BINS * cap_rows,
-                  launch_bands_frames(stream(), d_wav, bt.d_bnd_table, bt.d_bnd_slab, bt.d_bnd_frames, bt.d_bnd_par, cap, rate));
-        ZV_LAUNCH("voc_bands_phonemes", 8.0 * row_b * cap_rows + 4.0 * row_b * tok_rows, 0.0,
-                  launch_bands_phonemes(stream(), bt.d_cum, bt.d_bnd_slab, bt.d_bnd_phonemes, bt.d_bnd_par, tk, cap));
-    }
+    // the waveform of these segments is final: the stages a call carries, never under a one-layer tap
+    if (dbg_layer.kind < 0) wave_stage_launches(bt, lay, d_wav, rate, seg0);
 }
 
 }  // namespace zv
