@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -141,20 +141,36 @@ class ContourC(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("phonemes", C.c_void_p)]
 
 
-class Contour:
-    """An utterance's level contour (include/zerovox_amd.h "level contour"): .frames float32 [T, 2] and .phonemes float32 [n, 2],
-    columns (rms, peak) of the waveform the same call returned; None for a table that was not asked for.  dbfs() converts a
-    column or a table to dB re full scale (0 -> -inf).  .struct is the zv_contour, which points into the arrays (kept alive here)."""
-    CHOICES = (False, True, "frames", "phonemes")
+class PitchC(C.Structure):
+    """zv_pitch of include/zerovox_amd.h: the two tables' pointers, zv_pitch_frame [T] and zv_pitch_phoneme [n], each or NULL, and the
+    parameters, 0 = default (a zeroed struct asks for nothing)"""
+    _fields_ = [("frames", C.c_void_p), ("phonemes", C.c_void_p), ("min_lag", C.c_uint32), ("max_lag", C.c_uint32),
+                ("window", C.c_uint32), ("voiced_threshold", C.c_float)]
 
-    def __init__(self, T: int, n: int, frames: bool = True, phonemes: bool = True):
-        self.frames = np.zeros((T, 2), np.float32) if frames else None
-        self.phonemes = np.zeros((n, 2), np.float32) if phonemes else None
+
+class BandsC(C.Structure):
+    """zv_bands of include/zerovox_amd.h: the two tables' pointers, float [T][n_bands] and [n][n_bands], each or NULL, the band count
+    (0 = 16) and the edges' pointer, uint32 [n_bands + 1] or NULL = the default edges (a zeroed struct asks for nothing)"""
+    _fields_ = [("frames", C.c_void_p), ("phonemes", C.c_void_p), ("n_bands", C.c_uint32), ("edges", C.c_void_p)]
+
+
+class _Tables:
+    """What Contour, Pitch and Bands share: .frames float32 [T, width] and .phonemes float32 [n, width] of the waveform the same call
+    returned, None for a table that was not asked for; .struct is the subclass's C struct, which points into the arrays (kept alive
+    here) and carries the subclass's parameters behind the two pointers.  dbfs() converts levels to dB re full scale (0 -> -inf)."""
+    STRUCT = None
+
+    def __init__(self, T: int, n: int, width: int, frames: bool, phonemes: bool):
+        self.frames = np.zeros((T, width), np.float32) if frames else None
+        self.phonemes = np.zeros((n, width), np.float32) if phonemes else None
+
+    def _struct_params(self) -> tuple:
+        return ()
 
     @property
-    def struct(self) -> ContourC:
-        return ContourC(None if self.frames is None else self.frames.ctypes.data,
-                        None if self.phonemes is None else self.phonemes.ctypes.data)
+    def struct(self):
+        return self.STRUCT(None if self.frames is None else self.frames.ctypes.data,
+                           None if self.phonemes is None else self.phonemes.ctypes.data, *self._struct_params())
 
     @staticmethod
     def dbfs(levels) -> np.ndarray:
@@ -165,26 +181,23 @@ class Contour:
 
     def __repr__(self):
         shape = lambda a: None if a is None else a.shape
-        return f"Contour(frames={shape(self.frames)}, phonemes={shape(self.phonemes)})"
+        return f"{type(self).__name__}(frames={shape(self.frames)}, phonemes={shape(self.phonemes)})"
 
 
-def _check_contour(return_contour, where: str = ""):
-    """return_contour -> (frames asked for, phonemes asked for), checked before anything reaches the library: False, True (both
-    tables), "frames" or "phonemes" """
-    if isinstance(return_contour, (bool, np.bool_)):
-        return bool(return_contour), bool(return_contour)
-    if isinstance(return_contour, str):
-        if return_contour in ("frames", "phonemes"):
-            return return_contour == "frames", return_contour == "phonemes"
-        raise ValueError(f"{where}return_contour = {return_contour!r}: expected False, True, 'frames' or 'phonemes'")
-    raise TypeError(f"{where}return_contour must be a bool, 'frames' or 'phonemes', not {type(return_contour).__name__}")
+class Contour(_Tables):
+    """An utterance's level contour (include/zerovox_amd.h "level contour"): the tables' columns are (rms, peak)"""
+    STRUCT = ContourC
+    CHOICES = (False, True, "frames", "phonemes")
+
+    def __init__(self, T: int, n: int, frames: bool = True, phonemes: bool = True):
+        super().__init__(T, n, 2, frames, phonemes)
 
 
-class PitchC(C.Structure):
-    """zv_pitch of include/zerovox_amd.h: the two tables' pointers, zv_pitch_frame [T] and zv_pitch_phoneme [n], each or NULL, and the
-    parameters, 0 = default (a zeroed struct asks for nothing)"""
-    _fields_ = [("frames", C.c_void_p), ("phonemes", C.c_void_p), ("min_lag", C.c_uint32), ("max_lag", C.c_uint32),
-                ("window", C.c_uint32), ("voiced_threshold", C.c_float)]
+class _BothTables:
+    """what a contour is asked for: which tables, and no parameters"""
+
+    def __init__(self, frames: bool = True, phonemes: bool = True):
+        self.frames, self.phonemes = frames, phonemes
 
 
 class PitchTrack:
@@ -216,45 +229,18 @@ class PitchTrack:
                 f"voiced_threshold={self.voiced_threshold}, frames={self.frames}, phonemes={self.phonemes})")
 
 
-class Pitch:
-    """An utterance's pitch track: .frames float32 [T, 2], columns (f0_hz, strength), and .phonemes float32 [n, 2], columns (mean
-    f0_hz of the voiced frames, share of voiced frames), of the waveform the same call returned; None for a table that was not asked
-    for.  .params is the PitchTrack; .struct is the zv_pitch, which points into the arrays (kept alive here)."""
+class Pitch(_Tables):
+    """An utterance's pitch track: the columns of .frames are (f0_hz, strength), those of .phonemes (mean f0_hz of the voiced frames,
+    share of voiced frames).  .params is the PitchTrack."""
+    STRUCT = PitchC
 
     def __init__(self, T: int, n: int, params: PitchTrack):
         self.params = params
-        self.frames = np.zeros((T, 2), np.float32) if params.frames else None
-        self.phonemes = np.zeros((n, 2), np.float32) if params.phonemes else None
+        super().__init__(T, n, 2, params.frames, params.phonemes)
 
-    @property
-    def struct(self) -> PitchC:
+    def _struct_params(self):
         p = self.params
-        return PitchC(None if self.frames is None else self.frames.ctypes.data, None if self.phonemes is None else self.phonemes.ctypes.data,
-                      p.min_lag, p.max_lag, p.window, p.voiced_threshold)
-
-    def __repr__(self):
-        shape = lambda a: None if a is None else a.shape
-        return f"Pitch(frames={shape(self.frames)}, phonemes={shape(self.phonemes)})"
-
-
-def _check_pitch(return_pitch, where: str = ""):
-    """return_pitch -> a PitchTrack or None (nothing asked for), checked before anything reaches the library: False, True (both
-    tables, default parameters), "frames", "phonemes" or a PitchTrack"""
-    if isinstance(return_pitch, PitchTrack):
-        return return_pitch if return_pitch.frames or return_pitch.phonemes else None
-    if isinstance(return_pitch, (bool, np.bool_)):
-        return PitchTrack() if return_pitch else None
-    if isinstance(return_pitch, str):
-        if return_pitch in ("frames", "phonemes"):
-            return PitchTrack(frames=return_pitch == "frames", phonemes=return_pitch == "phonemes")
-        raise ValueError(f"{where}return_pitch = {return_pitch!r}: expected False, True, 'frames', 'phonemes' or a PitchTrack")
-    raise TypeError(f"{where}return_pitch must be a bool, 'frames', 'phonemes' or a PitchTrack, not {type(return_pitch).__name__}")
-
-
-class BandsC(C.Structure):
-    """zv_bands of include/zerovox_amd.h: the two tables' pointers, float [T][n_bands] and [n][n_bands], each or NULL, the band count
-    (0 = 16) and the edges' pointer, uint32 [n_bands + 1] or NULL = the default edges (a zeroed struct asks for nothing)"""
-    _fields_ = [("frames", C.c_void_p), ("phonemes", C.c_void_p), ("n_bands", C.c_uint32), ("edges", C.c_void_p)]
+        return p.min_lag, p.max_lag, p.window, p.voiced_threshold
 
 
 class BandLevels:
@@ -301,51 +287,37 @@ class BandLevels:
                 f"frames={self.frames}, phonemes={self.phonemes})")
 
 
-class Bands:
-    """An utterance's band levels: .frames float32 [T, n_bands] and .phonemes float32 [n, n_bands], the level (RMS re full scale) of
-    each band of the waveform the same call returned; None for a table that was not asked for.  .params is the BandLevels; .edges the
-    bins in force; dbfs() converts levels to dB re full scale (0 -> -inf); .struct is the zv_bands, which points into the arrays and
-    the edges (kept alive here)."""
+class Bands(_Tables):
+    """An utterance's band levels: a table's row holds the level (RMS re full scale) of each band.  .params is the BandLevels; .edges
+    the bins in force (the struct points into the edges too, which .params keeps alive)."""
+    STRUCT = BandsC
 
     def __init__(self, T: int, n: int, params: BandLevels):
         self.params = params
-        self.frames = np.zeros((T, params.width), np.float32) if params.frames else None
-        self.phonemes = np.zeros((n, params.width), np.float32) if params.phonemes else None
+        super().__init__(T, n, params.width, params.frames, params.phonemes)
 
     @property
     def edges(self) -> np.ndarray:
         return np.asarray(BandLevels.DEFAULT_EDGES, np.uint32) if self.params.edges is None else self.params.edges
 
-    @property
-    def struct(self) -> BandsC:
+    def _struct_params(self):
         p = self.params
-        return BandsC(None if self.frames is None else self.frames.ctypes.data, None if self.phonemes is None else self.phonemes.ctypes.data,
-                      p.n_bands, None if p.edges is None else p.edges.ctypes.data)
-
-    @staticmethod
-    def dbfs(levels) -> np.ndarray:
-        """20 * log10(level), full scale = 1.0; -inf for a level of 0"""
-        a = np.asarray(levels, dtype=np.float64)
-        with np.errstate(divide="ignore"):
-            return 20.0 * np.log10(a)
-
-    def __repr__(self):
-        shape = lambda a: None if a is None else a.shape
-        return f"Bands(frames={shape(self.frames)}, phonemes={shape(self.phonemes)})"
+        return p.n_bands, None if p.edges is None else p.edges.ctypes.data
 
 
-def _check_bands(return_bands, where: str = ""):
-    """return_bands -> a BandLevels or None (nothing asked for), checked before anything reaches the library: False, True (both
-    tables, default bands), "frames", "phonemes" or a BandLevels"""
-    if isinstance(return_bands, BandLevels):
-        return return_bands if return_bands.frames or return_bands.phonemes else None
-    if isinstance(return_bands, (bool, np.bool_)):
-        return BandLevels() if return_bands else None
-    if isinstance(return_bands, str):
-        if return_bands in ("frames", "phonemes"):
-            return BandLevels(frames=return_bands == "frames", phonemes=return_bands == "phonemes")
-        raise ValueError(f"{where}return_bands = {return_bands!r}: expected False, True, 'frames', 'phonemes' or a BandLevels")
-    raise TypeError(f"{where}return_bands must be a bool, 'frames', 'phonemes' or a BandLevels, not {type(return_bands).__name__}")
+def _check_tables(keyword: str, params_cls, wish, where: str = ""):
+    """a table request (the value of `keyword`) -> a params_cls or None (nothing asked for), checked before anything reaches the
+    library: False, True (both tables, default parameters), "frames", "phonemes" or, unless params_cls is _BothTables, a params_cls"""
+    kinds = "'frames' or 'phonemes'" if params_cls is _BothTables else f"'frames', 'phonemes' or a {params_cls.__name__}"
+    if isinstance(wish, params_cls):
+        return wish if wish.frames or wish.phonemes else None
+    if isinstance(wish, (bool, np.bool_)):
+        return params_cls() if wish else None
+    if isinstance(wish, str):
+        if wish in ("frames", "phonemes"):
+            return params_cls(frames=wish == "frames", phonemes=wish == "phonemes")
+        raise ValueError(f"{where}{keyword} = {wish!r}: expected False, True, {kinds}")
+    raise TypeError(f"{where}{keyword} must be a bool, {kinds}, not {type(wish).__name__}")
 
 
 class FilterC(C.Structure):
@@ -554,6 +526,52 @@ class ZvError(RuntimeError):
         self.status = status
 
 
+class Form(NamedTuple):
+    suffix: str         # appended to the entry point's name
+    args: tuple         # the arguments the rung adds: (keyword of _call_variant, ctype of the single call, ctype of the batch calls)
+    selects: tuple      # the keywords that select the rung
+
+
+# The ladder of entry-point forms, lowest rung first.  A form takes the arguments of every rung up to itself, NULL / 0 for what the
+# call lacks, and the forms agree bit for bit on those.  A call goes to the highest rung one of whose selecting arguments is not
+# None: _prosody with prosody controls; _phonemes with per-phoneme controls or a buffer for the phoneme timings; _target with a frame
+# count the durations are fitted to (single call: a uint32, 0 = none; batches: uint32 [n_utt] or NULL), which is also where the
+# `fitted` flag becomes an argument; _volume with volumes or a buffer for the levels; _envelope, _contour, _pitch, _bands and
+# _filter each with its struct (batches: an array [n_utt]).  _fitted is the one irregular form: it adds nothing to the _phonemes list,
+# and a call goes there when `fitted` is set and nothing from _target upward is present.
+_P, _vp, _u32 = C.POINTER, C.c_void_p, C.c_uint32
+FORMS = (
+    Form("_prosody", (("prosody", _P(Prosody), _P(Prosody)),), ("prosody",)),
+    Form("_phonemes", (("phonemes", _P(PhonemeControlsC), _P(PhonemeControlsC)), ("durations", _vp, _P(_vp))), ("phonemes", "durations")),
+    Form("_fitted", (), ()),
+    Form("_target", (("target", _u32, _P(_u32)), ("fitted", C.c_int, C.c_int)), ("target",)),
+    Form("_volume", (("volume", _P(Volume), _P(Volume)), ("levels", _P(Level), _P(Level))), ("volume", "levels")),
+    Form("_envelope", (("envelope", _P(EnvelopeC), _P(EnvelopeC)),), ("envelope",)),
+    Form("_contour", (("contour", _P(ContourC), _P(ContourC)),), ("contour",)),
+    Form("_pitch", (("pitch", _P(PitchC), _P(PitchC)),), ("pitch",)),
+    Form("_bands", (("bands", _P(BandsC), _P(BandsC)),), ("bands",)),
+    Form("_filter", (("filter", _P(FilterC), _P(FilterC)),), ("filter",)),
+)
+# entry point -> (the plain form's argtypes, the column of Form.args that holds its ctypes, its rungs).  zv_encode_taps has three
+# rungs, and its _target adds the count alone
+LADDERS = {
+    "zv_synthesize": ([_vp, _vp, _vp, _vp, _u32, _u32, _vp, _P(_u32)], 1, FORMS),
+    "zv_synthesize_batch": ([_vp, _u32, _P(_vp), _P(_vp), _P(_vp), _P(_u32), _P(_u32), _P(_vp), _P(_u32)], 2, FORMS),
+    "zv_synthesize_batch_begin": ([_vp, _u32, _u32, _P(_vp), _P(_vp), _P(_vp), _P(_u32), _P(_u32), _P(_vp), _P(_u32)], 2, FORMS),
+    "zv_encode_taps": ([_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _P(_u32), _vp, _vp, _vp, _vp, _vp, _vp], 1,
+                       FORMS[:2] + (FORMS[3]._replace(args=FORMS[3].args[:1]),)),
+}
+
+
+def _select(forms, given: dict):
+    """the walk of the ladder: (suffix, trailing arguments) of the form a call with the `given` arguments (keyword -> value) goes to"""
+    for top in range(len(forms) - 1, -1, -1):
+        form = forms[top]
+        if given["fitted"] if form.suffix == "_fitted" else any(given[k] is not None for k in form.selects):
+            return form.suffix, tuple(int(given[k]) if k == "fitted" else given[k] for f in forms[:top + 1] for k, *_ in f.args)
+    return "", ()
+
+
 _lib = None
 
 
@@ -565,6 +583,18 @@ def load_library(path: Optional[str] = None):
     if not os.path.exists(p):
         raise ZvError(-1, f"{p} not found: build it with `make -C zerovox.cpp_amd/csrc` (no CPU fallback exists)")
     lib = C.CDLL(p)
+    _bind(lib)
+    if path is None:
+        _lib = lib
+    _forward_env_switches(lib)
+    return lib
+
+
+def _bind(lib):
+    """argtypes / restype of every entry point `lib` carries (a CDLL, or any object with the symbols as attributes): every form of
+    LADDERS from the table, the rest written out.  The suffixed forms and the entry points of the second loop are bound where
+    present: an older build named by ZEROVOX_AMD_LIB for an A/B run may lack the upper ones, and a call that needs one then fails
+    with AttributeError; build() checks SYMBOLS on the tree's own library."""
     vp, u32, i32p, fp = C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p
     lib.zv_last_error.restype = C.c_char_p
     lib.zv_version.restype = C.c_char_p
@@ -574,16 +604,15 @@ def load_library(path: Optional[str] = None):
     lib.zv_model_get_hparams.argtypes = [vp, C.POINTER(HParams)]
     lib.zv_model_reserve.argtypes = [vp, u32, u32]
     lib.zv_encode.argtypes = [vp, i32p, i32p, fp, u32, u32, fp, C.POINTER(u32)]
-    lib.zv_encode_taps.argtypes = [vp, i32p, i32p, fp, u32, u32, u32, fp, C.POINTER(u32), fp, fp, fp, fp, i32p, i32p]
+    for name, (plain, column, forms) in LADDERS.items():
+        getattr(lib, name).argtypes = argtypes = list(plain)
+        for form in forms:
+            argtypes = argtypes + [arg[column] for arg in form.args]
+            if hasattr(lib, name + form.suffix):
+                getattr(lib, name + form.suffix).argtypes = argtypes
     lib.zv_debug_layer.argtypes = [vp, C.c_int, C.c_int, fp, u32, fp, fp]
-    if hasattr(lib, "zv_debug_mfma_chain"):
-        lib.zv_debug_mfma_chain.argtypes = [vp, C.c_int, C.c_void_p, C.c_void_p, fp, u32, fp]
     lib.zv_debug_set.argtypes = [C.c_char_p, C.c_int]
     lib.zv_debug_get.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
-    if hasattr(lib, "zv_debug_voc_runs"):        # (an older build named by ZEROVOX_AMD_LIB for an A/B run lacks it)
-        lib.zv_debug_voc_runs.argtypes = [vp, u32, C.c_void_p, u32, C.POINTER(u32)]
-    if hasattr(lib, "zv_debug_poison"):
-        lib.zv_debug_poison.argtypes = [vp, u32, C.c_int, C.POINTER(C.c_size_t)]
     lib.zv_batch_timeline.argtypes = [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u32)]
     lib.zv_max_frames.argtypes = [vp]
     lib.zv_max_frames.restype = u32
@@ -591,75 +620,16 @@ def load_library(path: Optional[str] = None):
     lib.zv_demo_utterance.restype = None
     lib.zv_decode.argtypes = [vp, fp, fp, u32, fp]
     lib.zv_vocode.argtypes = [vp, fp, u32, fp]
-    lib.zv_synthesize.argtypes = [vp, i32p, i32p, fp, u32, u32, fp, C.POINTER(u32)]
-    lib.zv_synthesize_batch.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u32), C.POINTER(u32),
-                                        C.POINTER(vp), C.POINTER(u32)]
-    lib.zv_synthesize_batch_begin.argtypes = [vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u32), C.POINTER(u32),
-                                              C.POINTER(vp), C.POINTER(u32)]
     lib.zv_synthesize_batch_end.argtypes = [vp, u32]
-    pp = C.POINTER(Prosody)
-    lib.zv_encode_taps_prosody.argtypes = lib.zv_encode_taps.argtypes + [pp]
-    lib.zv_synthesize_prosody.argtypes = lib.zv_synthesize.argtypes + [pp]
-    lib.zv_synthesize_batch_prosody.argtypes = lib.zv_synthesize_batch.argtypes + [pp]
-    lib.zv_synthesize_batch_begin_prosody.argtypes = lib.zv_synthesize_batch_begin.argtypes + [pp]
-    pc = C.POINTER(PhonemeControlsC)
-    lib.zv_encode_taps_phonemes.argtypes = lib.zv_encode_taps_prosody.argtypes + [pc, i32p]
-    lib.zv_synthesize_phonemes.argtypes = lib.zv_synthesize_prosody.argtypes + [pc, i32p]
-    lib.zv_synthesize_batch_phonemes.argtypes = lib.zv_synthesize_batch_prosody.argtypes + [pc, C.POINTER(vp)]
-    lib.zv_synthesize_batch_begin_phonemes.argtypes = lib.zv_synthesize_batch_begin_prosody.argtypes + [pc, C.POINTER(vp)]
-    # the fitted forms take the argument lists of their _phonemes counterparts (an older build named by ZEROVOX_AMD_LIB for an A/B
-    # run may lack them: calling one then fails with AttributeError; build() checks SYMBOLS on the tree's own library)
-    if hasattr(lib, "zv_synthesize_fitted"):
-        lib.zv_synthesize_fitted.argtypes = lib.zv_synthesize_phonemes.argtypes
-        lib.zv_synthesize_batch_fitted.argtypes = lib.zv_synthesize_batch_phonemes.argtypes
-        lib.zv_synthesize_batch_begin_fitted.argtypes = lib.zv_synthesize_batch_begin_phonemes.argtypes
-    # the target forms: the _phonemes argument lists, the target (batches: uint32 [n_utt] or NULL) and, for the synthesize forms, fitted
-    if hasattr(lib, "zv_synthesize_target"):
-        lib.zv_encode_taps_target.argtypes = lib.zv_encode_taps_phonemes.argtypes + [u32]
-        lib.zv_synthesize_target.argtypes = lib.zv_synthesize_phonemes.argtypes + [u32, C.c_int]
-        lib.zv_synthesize_batch_target.argtypes = lib.zv_synthesize_batch_phonemes.argtypes + [C.POINTER(u32), C.c_int]
-        lib.zv_synthesize_batch_begin_target.argtypes = lib.zv_synthesize_batch_begin_phonemes.argtypes + [C.POINTER(u32), C.c_int]
-    # the volume forms: the _target argument lists, the volumes (zv_volume, batches [n_utt]) and the levels (zv_level, likewise), each or NULL
-    if hasattr(lib, "zv_synthesize_volume"):
-        vl = [C.POINTER(Volume), C.POINTER(Level)]
-        lib.zv_synthesize_volume.argtypes = lib.zv_synthesize_target.argtypes + vl
-        lib.zv_synthesize_batch_volume.argtypes = lib.zv_synthesize_batch_target.argtypes + vl
-        lib.zv_synthesize_batch_begin_volume.argtypes = lib.zv_synthesize_batch_begin_target.argtypes + vl
-    # the envelope forms: the _volume argument lists and the envelopes (zv_envelope, batches [n_utt]) or NULL
-    if hasattr(lib, "zv_synthesize_envelope"):
-        ev = [C.POINTER(EnvelopeC)]
-        lib.zv_synthesize_envelope.argtypes = lib.zv_synthesize_volume.argtypes + ev
-        lib.zv_synthesize_batch_envelope.argtypes = lib.zv_synthesize_batch_volume.argtypes + ev
-        lib.zv_synthesize_batch_begin_envelope.argtypes = lib.zv_synthesize_batch_begin_volume.argtypes + ev
-    # the contour forms: the _envelope argument lists and the contours (zv_contour, batches [n_utt]) or NULL
-    if hasattr(lib, "zv_synthesize_contour"):
-        ct = [C.POINTER(ContourC)]
-        lib.zv_synthesize_contour.argtypes = lib.zv_synthesize_envelope.argtypes + ct
-        lib.zv_synthesize_batch_contour.argtypes = lib.zv_synthesize_batch_envelope.argtypes + ct
-        lib.zv_synthesize_batch_begin_contour.argtypes = lib.zv_synthesize_batch_begin_envelope.argtypes + ct
-    # the pitch forms: the _contour argument lists and the pitch tracks (zv_pitch, batches [n_utt]) or NULL; the stand-alone meter
-    if hasattr(lib, "zv_synthesize_pitch"):
-        pt = [C.POINTER(PitchC)]
-        lib.zv_synthesize_pitch.argtypes = lib.zv_synthesize_contour.argtypes + pt
-        lib.zv_synthesize_batch_pitch.argtypes = lib.zv_synthesize_batch_contour.argtypes + pt
-        lib.zv_synthesize_batch_begin_pitch.argtypes = lib.zv_synthesize_batch_begin_contour.argtypes + pt
-        lib.zv_pitch_track.argtypes = [vp, vp, C.c_uint32, C.POINTER(PitchC)]
-    # the bands forms: the _pitch argument lists and the band levels (zv_bands, batches [n_utt]) or NULL; the stand-alone meter
-    if hasattr(lib, "zv_synthesize_bands"):
-        bt = [C.POINTER(BandsC)]
-        lib.zv_synthesize_bands.argtypes = lib.zv_synthesize_pitch.argtypes + bt
-        lib.zv_synthesize_batch_bands.argtypes = lib.zv_synthesize_batch_pitch.argtypes + bt
-        lib.zv_synthesize_batch_begin_bands.argtypes = lib.zv_synthesize_batch_begin_pitch.argtypes + bt
-        lib.zv_band_levels.argtypes = [vp, vp, C.c_uint32, C.POINTER(BandsC)]
-    # the filter forms: the _bands argument lists and the waveform filter (zv_filter, batches [n_utt]) or NULL; the stand-alone filter
-    # and the design
-    if hasattr(lib, "zv_synthesize_filter"):
-        ft = [C.POINTER(FilterC)]
-        lib.zv_synthesize_filter.argtypes = lib.zv_synthesize_bands.argtypes + ft
-        lib.zv_synthesize_batch_filter.argtypes = lib.zv_synthesize_batch_bands.argtypes + ft
-        lib.zv_synthesize_batch_begin_filter.argtypes = lib.zv_synthesize_batch_begin_bands.argtypes + ft
-        lib.zv_filter_wave.argtypes = [vp, vp, C.c_uint32, C.POINTER(FilterC), vp]
-        lib.zv_filter_design.argtypes = [C.c_uint32, vp, vp, C.c_uint32, vp]
+    for name, argtypes in (("zv_debug_mfma_chain", [vp, C.c_int, vp, vp, fp, u32, fp]),
+                           ("zv_debug_voc_runs", [vp, u32, vp, u32, C.POINTER(u32)]),
+                           ("zv_debug_poison", [vp, u32, C.c_int, C.POINTER(C.c_size_t)]),
+                           ("zv_pitch_track", [vp, vp, u32, C.POINTER(PitchC)]),
+                           ("zv_band_levels", [vp, vp, u32, C.POINTER(BandsC)]),
+                           ("zv_filter_wave", [vp, vp, u32, C.POINTER(FilterC), vp]),
+                           ("zv_filter_design", [u32, vp, vp, u32, vp])):
+        if hasattr(lib, name):
+            getattr(lib, name).argtypes = argtypes
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -678,10 +648,6 @@ def load_library(path: Optional[str] = None):
     lib.zv_write_wav.argtypes = [C.c_char_p, fp, C.c_size_t, u32]
     lib.zv_gguf_inspect.argtypes = [C.c_char_p, C.POINTER(u32), C.POINTER(u32), C.c_int, C.c_char_p, C.POINTER(u32),
                                     C.POINTER(C.c_int64)]
-    if path is None:
-        _lib = lib
-    _forward_env_switches(lib)
-    return lib
 
 
 def _forward_env_switches(lib):
@@ -705,7 +671,8 @@ def _ptr(a):
 
 
 def _ref(x):
-    return None if x is None else C.byref(x)
+    """a struct, or a holder with one in .struct, by reference; None -> NULL"""
+    return None if x is None else C.byref(getattr(x, "struct", x))
 
 
 def _check_fitted(fitted, Ts):
@@ -735,41 +702,49 @@ def _check_target(target, T):
 
 def _call_variant(lib, name, args, prosody=None, phonemes=None, durations=None, fitted=False, target=None, volume=None, levels=None,
                   envelope=None, contour=None, pitch=None, bands=None, filter=None):
-    """entry point `name` in the form that carries what the call has: name_phonemes with per-phoneme controls or timings,
-    name_prosody with prosody alone, `name` itself with neither (the forms agree bit for bit on NULL controls); its status.
-    fitted: name_fitted, which takes everything (NULL for what the call lacks).  target (a frame count, or the batches' uint32
-    array): name_target, which takes everything and the fitted flag.  volume / levels (a zv_volume and a zv_level, or the batches'
-    arrays): name_volume, which takes everything the _target form takes and the two (a call without a target passes 0 / NULL).
-    envelope (a zv_envelope, or the batches' array): name_envelope, which takes everything the _volume form takes and the envelope.
-    contour (a zv_contour, or the batches' array): name_contour, which takes everything the _envelope form takes and the contour;
-    only a call that asks for a contour goes there.  pitch (a zv_pitch, or the batches' array): name_pitch, which takes everything the
-    _contour form takes and the pitch track; only a call that asks for a pitch track goes there.  bands (a zv_bands, or the batches'
-    array): name_bands, which takes everything the _pitch form takes and the band levels; only a call that asks for them goes there.
-    filter (a zv_filter, or the batches' array): name_filter, which takes everything the _bands form takes and the filter; only a call
-    that passes a filter goes there"""
-    if filter is not None:
-        return getattr(lib, name + "_filter")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour,
-                                              pitch, bands, filter)
-    if bands is not None:
-        return getattr(lib, name + "_bands")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour,
-                                             pitch, bands)
-    if pitch is not None:
-        return getattr(lib, name + "_pitch")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour, pitch)
-    if contour is not None:
-        return getattr(lib, name + "_contour")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope, contour)
-    if envelope is not None:
-        return getattr(lib, name + "_envelope")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels, envelope)
-    if volume is not None or levels is not None:
-        return getattr(lib, name + "_volume")(*args, prosody, phonemes, durations, target, int(fitted), volume, levels)
-    if target is not None:
-        return getattr(lib, name + "_target")(*args, prosody, phonemes, durations, target, int(fitted))
-    if fitted:
-        return getattr(lib, name + "_fitted")(*args, prosody, phonemes, durations)
-    if phonemes is not None or durations is not None:
-        return getattr(lib, name + "_phonemes")(*args, prosody, phonemes, durations)
-    if prosody is not None:
-        return getattr(lib, name + "_prosody")(*args, prosody)
-    return getattr(lib, name)(*args)
+    """entry point `name` in the form the ladder gives for what the call has (its own rungs in LADDERS, else all of FORMS); its
+    status"""
+    given = dict(prosody=prosody, phonemes=phonemes, durations=durations, fitted=fitted, target=target, volume=volume, levels=levels,
+                 envelope=envelope, contour=contour, pitch=pitch, bands=bands, filter=filter)
+    suffix, tail = _select(LADDERS[name][2] if name in LADDERS else FORMS, given)
+    return getattr(lib, name + suffix)(*args, *tail)
+
+
+class Option(NamedTuple):
+    """one per-utterance option of synthesize / BatchCall"""
+    keyword: str            # the keyword that carries it (for the first three: the name of the utterance tuple's element)
+    struct: type            # what the C call reads; struct() is "nothing asked for" / the identity
+    check: Callable         # (wish, n phonemes, T, where) -> the checked wish, None: nothing asked for
+    hold: Callable          # (checked wish, n phonemes, T) -> the holder: the struct itself, or an object whose .struct is it
+    batch_wide: bool        # one wish may stand for the whole batch (else: a list with one per utterance)
+    array: str              # BatchCall's attribute for the ctypes array, None: built without
+    keep: Optional[str]     # BatchCall's attribute for the list of holders the array points into
+    without: str = ""       # set_*: "this BatchCall was built without ..."
+
+    def holder(self, wish, n: int, T: int, where: str = ""):
+        checked = self.check(wish, n, T, where)
+        return None if checked is None else self.hold(checked, n, T)
+
+    def c(self, holder):
+        """the struct of a holder, None: the zeroed one"""
+        return self.struct() if holder is None else getattr(holder, "struct", holder)
+
+
+_as_checked = lambda checked, n, T: checked
+PROSODY = Option("prosody", Prosody, lambda w, n, T, where: _prosody(w), _as_checked, False, "prosody", None, "prosody controls")
+PHONEMES = Option("phonemes", PhonemeControlsC, lambda w, n, T, where: _phoneme_controls(w, n), _as_checked, False, "phonemes", "pkeep",
+                  "per-phoneme controls")
+TARGET = Option("target_frames", C.c_uint32, lambda w, n, T, where: _check_target(w, T), _as_checked, False, "targets", None,
+                "target frame counts")
+VOLUME = Option("volume", Volume, lambda w, n, T, where: _volume(w, where), _as_checked, False, "volume", None, "volume controls")
+ENVELOPE = Option("envelope", EnvelopeC, lambda w, n, T, where: _envelope(w, n, where), _as_checked, False, "envelope", "ekeep", "envelopes")
+CONTOUR = Option("return_contour", ContourC, lambda w, n, T, where: _check_tables("return_contour", _BothTables, w, where),
+                 lambda c, n, T: Contour(T, n, c.frames, c.phonemes), True, "contour", "contours")
+PITCH = Option("return_pitch", PitchC, lambda w, n, T, where: _check_tables("return_pitch", PitchTrack, w, where),
+               lambda c, n, T: Pitch(T, n, c), True, "pitch", "pitches", "a pitch track")
+BANDS = Option("return_bands", BandsC, lambda w, n, T, where: _check_tables("return_bands", BandLevels, w, where),
+               lambda c, n, T: Bands(T, n, c), True, "band", "bands", "band levels")
+FILTER = Option("filter", FilterC, lambda w, n, T, where: _filter(w, where), _as_checked, False, "filter", "fkeep", "filters")
 
 
 def debug_set(name: Optional[str], value: int = 0):
@@ -810,6 +785,14 @@ class switches:
         for k, v in self.saved.items():
             debug_set(k, v)
         return False
+
+
+def _waveform(hop: int, who: str, wav):
+    """a waveform the caller brings, float32 [T * hop] at the model's rate and hop -> (the array, T)"""
+    w = np.ascontiguousarray(wav, dtype=np.float32)
+    if w.ndim != 1 or w.size == 0 or w.size % hop:
+        raise ValueError(f"{who}: the waveform must be a non-empty 1-D array of a multiple of {hop} samples, got shape {w.shape}")
+    return w, w.size // hop
 
 
 class Model:
@@ -919,11 +902,10 @@ class Model:
     def encode(self, ids, puncts, style, T: int, num_phonemes: Optional[int] = None, prosody=None, phonemes=None,
                return_durations: bool = False, target_frames: Optional[int] = None) -> dict:
         """num_phonemes < len(ids): all ids are encoded, the length regulator walks the first num_phonemes (FS2Encoder::eval).
-        prosody (Prosody, dict or 5-sequence): zv_encode_taps_prosody; None: zv_encode_taps.
-        phonemes (PhonemeControls or dict of arrays [len(ids)]) or return_durations: zv_encode_taps_phonemes, and the result gains
-        "durations" (the phoneme timings, int32 [len(ids)]).
-        target_frames (0 <= frames <= T): zv_encode_taps_target — the durations are fitted to sum to exactly that many frames (0: the
-        bits of the call without it); None: the entry points above"""
+        zv_encode_taps in the form FORMS gives for what the call has.  prosody: a Prosody, dict or 5-sequence.  phonemes (a
+        PhonemeControls or dict of arrays [len(ids)]) or return_durations: the result gains "durations" (the phoneme timings, int32
+        [len(ids)]).  target_frames (0 <= frames <= T): the durations are fitted to sum to exactly that many frames (0: the bits of
+        the call without it)"""
         target = _check_target(target_frames, T)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
@@ -939,121 +921,96 @@ class Model:
         pc = _phoneme_controls(phonemes, N)
         if pc is not None or return_durations:
             out["durations"] = np.empty(N, np.int32)
-        if target is not None:
-            self._chk(self.lib.zv_encode_taps_target(*args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct),
-                                                     _ptr(out.get("durations")), target))
-        else:
-            self._chk(_call_variant(self.lib, "zv_encode_taps", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct),
-                                    _ptr(out.get("durations"))))
+        self._chk(_call_variant(self.lib, "zv_encode_taps", args, _ref(_prosody(prosody)), _ref(pc),
+                                _ptr(out.get("durations")), target=target))
         out["n_frames"] = int(nf.value)
         return out
 
     def synthesize(self, ids, puncts, style, T: int, prosody=None, phonemes=None, return_durations: bool = False,
                    fitted: bool = False, target_frames: Optional[int] = None, *, volume=None, return_levels: bool = False,
                    envelope=None, return_contour=False, return_pitch=False, return_bands=False, filter=None):
-        """prosody (Prosody, dict or 5-sequence): zv_synthesize_prosody; None: zv_synthesize.  phonemes (PhonemeControls or dict of
-        arrays [len(ids)]) or return_durations: zv_synthesize_phonemes; return_durations adds the phoneme timings (int32 [len(ids)])
-        as a third element.  fitted: zv_synthesize_fitted — T is a capacity, the utterance is decoded and vocoded as the n_frames
-        the length regulator fills; wav keeps the capacity shape [T * hop], zero behind n_frames * hop.
-        target_frames (0 <= frames <= T): zv_synthesize_target — the durations are fitted to sum to exactly that many frames (0: the
-        bits of the call without it); None: the entry points above.
-        volume (Volume, dict or (gain, target_rms, peak_ceiling)) or return_levels: zv_synthesize_volume — the waveform is measured
-        and scaled on the device; return_levels adds the Level (rms and peak before the gain, the gain) as the last element.
-        envelope (Envelope or dict of its fields): zv_synthesize_envelope — per-phoneme gains, cross-fades and fades, applied on the
-        device ahead of the volume.
-        return_contour (False, True, "frames" or "phonemes"): zv_synthesize_contour — the level and peak of every frame and / or every
-        phoneme of the returned waveform, metered on the device; adds a Contour as the last element.
-        return_pitch (False, True, "frames", "phonemes" or a PitchTrack): zv_synthesize_pitch — the fundamental frequency and voicing
-        of every frame and / or every phoneme of the returned waveform, metered on the device; adds a Pitch as the last element.
-        return_bands (False, True, "frames", "phonemes" or a BandLevels): zv_synthesize_bands — the level per frequency band of every
-        frame and / or every phoneme of the returned waveform, metered on the device; adds a Bands as the last element.
-        filter (a Filter, a sequence of taps or None): zv_synthesize_filter — a linear-phase FIR applied to the waveform on the device,
-        ahead of envelope, volume and all meters"""
-        flt = _filter(filter)
-        want_frames, want_phonemes = _check_contour(return_contour)
-        track = _check_pitch(return_pitch)
-        spec = _check_bands(return_bands)
+        """zv_synthesize in the form FORMS gives for what the call has -> (wav, n_frames), then what the return_* arguments add.
+        prosody: a Prosody, dict or 5-sequence.  phonemes: a PhonemeControls or dict of arrays [len(ids)].  return_durations adds the
+        phoneme timings (int32 [len(ids)]) as a third element.  fitted: T is a capacity, the utterance is decoded and vocoded as the
+        n_frames the length regulator fills; wav keeps the capacity shape [T * hop], zero behind n_frames * hop.
+        target_frames (0 <= frames <= T): the durations are fitted to sum to exactly that many frames (0: the bits of the call
+        without it).
+        volume (Volume, dict or (gain, target_rms, peak_ceiling)): the waveform is measured and scaled on the device; return_levels
+        adds the Level (rms and peak before the gain, the gain) as the last element.
+        envelope (Envelope or dict of its fields): per-phoneme gains, cross-fades and fades, applied on the device ahead of the volume.
+        return_contour (False, True, "frames" or "phonemes"), return_pitch (those, or a PitchTrack), return_bands (those, or a
+        BandLevels): the level and peak, the fundamental frequency and voicing, the level per frequency band of every frame and / or
+        every phoneme of the returned waveform, metered on the device; each adds its Contour, Pitch, Bands as the last element.
+        filter (a Filter, a sequence of taps or None): a linear-phase FIR applied to the waveform on the device, ahead of envelope,
+        volume and all meters"""
+        # every argument is checked before T sizes a buffer or the model is touched; the tables are built behind the checks
+        stages = (FILTER, CONTOUR, PITCH, BANDS)
+        asked = [opt.check(wish, None, T, "") for opt, wish in zip(stages, (filter, return_contour, return_pitch, return_bands))]
         fitted = _check_fitted(fitted, [T])
-        target = _check_target(target_frames, T)
-        vol, return_levels = _volume(volume), _check_levels(return_levels)
-        env = _envelope(envelope, len(ids))
+        target = TARGET.check(target_frames, None, T, "")
+        vol, return_levels = VOLUME.check(volume, None, T, ""), _check_levels(return_levels)
+        env = ENVELOPE.check(envelope, len(ids), T, "")
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         puncts = np.ascontiguousarray(puncts, dtype=np.int32)
         style = np.ascontiguousarray(style, dtype=np.float32)
         wav = np.empty(T * self.hp.audio_hop_size, np.float32)
         nf = C.c_uint32(0)
-        args = (self.h, _ptr(ids), _ptr(puncts), _ptr(style), len(ids), T, _ptr(wav), C.byref(nf))
-        pc = _phoneme_controls(phonemes, len(ids))
-        dur = np.empty(len(ids), np.int32) if return_durations else None
+        n = len(ids)
+        args = (self.h, _ptr(ids), _ptr(puncts), _ptr(style), n, T, _ptr(wav), C.byref(nf))
+        pc = PHONEMES.check(phonemes, n, T, "")
+        dur = np.empty(n, np.int32) if return_durations else None
         level = Level() if vol is not None or return_levels else None
-        contour = Contour(T, len(ids), want_frames, want_phonemes) if want_frames or want_phonemes else None
-        pitch = Pitch(T, len(ids), track) if track is not None else None
-        bands = Bands(T, len(ids), spec) if spec is not None else None
-        if (level is not None or env is not None or contour is not None or pitch is not None or bands is not None or flt is not None) and target is None:
-            target = 0                       # the _volume, _envelope, _contour, _pitch, _bands and _filter forms take a count, 0 = none
-        self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(None if pc is None else pc.struct), _ptr(dur),
-                                fitted, target, _ref(vol), _ref(level), _ref(None if env is None else env.struct),
-                                _ref(None if contour is None else contour.struct), _ref(None if pitch is None else pitch.struct),
-                                _ref(None if bands is None else bands.struct), _ref(None if flt is None else flt.struct)))
+        flt, contour, pitch, bands = (None if a is None else opt.hold(a, n, T) for opt, a in zip(stages, asked))
+        held = (vol, level, env, contour, pitch, bands, flt)
+        if target is None and any(h is not None for h in held):
+            target = 0                       # every form above _target takes the count, 0 = none
+        self._chk(_call_variant(self.lib, "zv_synthesize", args, _ref(_prosody(prosody)), _ref(pc), _ptr(dur), fitted, target,
+                                *map(_ref, held)))
         out = (wav, int(nf.value), dur) if return_durations else (wav, int(nf.value))
         out = out + (level,) if return_levels else out
-        out = out + (contour,) if contour is not None else out
-        out = out + (pitch,) if pitch is not None else out
-        return out + (bands,) if bands is not None else out
+        return out + tuple(h for h in (contour, pitch, bands) if h is not None)
 
     def filter_wave(self, wav, filter) -> np.ndarray:
-        """zv_filter_wave: a waveform the caller brings (float32 [T * hop] at the model's hop) through the filter (a Filter or a
-        sequence of taps) on the device; returns the filtered waveform"""
+        """zv_filter_wave: the waveform through the filter (a Filter or a sequence of taps) on the device; returns the filtered waveform"""
         flt = _filter(filter)
         if flt is None:
             raise TypeError("filter_wave: filter must be a Filter or a sequence of taps, not None")
-        w = np.ascontiguousarray(wav, dtype=np.float32)
-        hop = self.hp.audio_hop_size
-        if w.ndim != 1 or w.size == 0 or w.size % hop:
-            raise ValueError(f"filter_wave: the waveform must be a non-empty 1-D array of a multiple of {hop} samples, got shape {w.shape}")
+        w, T = _waveform(self.hp.audio_hop_size, "filter_wave", wav)
         out = np.empty_like(w)
         st = flt.struct
-        self._chk(self.lib.zv_filter_wave(self.h, _ptr(w), w.size // hop, C.byref(st), _ptr(out)))
+        self._chk(self.lib.zv_filter_wave(self.h, _ptr(w), T, C.byref(st), _ptr(out)))
         return out
 
     def band_levels(self, wav, params=None) -> Bands:
-        """zv_band_levels: the band levels of a waveform the caller brings (float32 [T * hop] at the model's rate and hop), frames
-        only; params: a BandLevels or None (the default bands)"""
+        """zv_band_levels: the band levels of the waveform, frames only; params: a BandLevels or None (the default bands)"""
         if params is not None and not isinstance(params, BandLevels):
             raise TypeError(f"band_levels: params must be a BandLevels or None, not {type(params).__name__}")
         p = params or BandLevels()
         spec = BandLevels(p.n_bands if p.edges is None else 0, p.edges, True, False)      # a waveform has no timings
-        w = np.ascontiguousarray(wav, dtype=np.float32)
-        hop = self.hp.audio_hop_size
-        if w.ndim != 1 or w.size == 0 or w.size % hop:
-            raise ValueError(f"band_levels: the waveform must be a non-empty 1-D array of a multiple of {hop} samples, got shape {w.shape}")
-        bands = Bands(w.size // hop, 0, spec)
+        w, T = _waveform(self.hp.audio_hop_size, "band_levels", wav)
+        bands = Bands(T, 0, spec)
         st = bands.struct
-        self._chk(self.lib.zv_band_levels(self.h, _ptr(w), w.size // hop, C.byref(st)))
+        self._chk(self.lib.zv_band_levels(self.h, _ptr(w), T, C.byref(st)))
         return bands
 
     def pitch_track(self, wav, params=None) -> Pitch:
-        """zv_pitch_track: the pitch track of a waveform the caller brings (float32 [T * hop] at the model's rate and hop), frames
-        only; params: a PitchTrack or None (the defaults)"""
+        """zv_pitch_track: the pitch track of the waveform, frames only; params: a PitchTrack or None (the defaults)"""
         if params is not None and not isinstance(params, PitchTrack):
             raise TypeError(f"pitch_track: params must be a PitchTrack or None, not {type(params).__name__}")
         p = params or PitchTrack()
         track = PitchTrack(p.min_lag, p.max_lag, p.window, p.voiced_threshold, True, False)      # a waveform has no timings
-        w = np.ascontiguousarray(wav, dtype=np.float32)
-        hop = self.hp.audio_hop_size
-        if w.ndim != 1 or w.size == 0 or w.size % hop:
-            raise ValueError(f"pitch_track: the waveform must be a non-empty 1-D array of a multiple of {hop} samples, got shape {w.shape}")
-        pitch = Pitch(w.size // hop, 0, track)
+        w, T = _waveform(self.hp.audio_hop_size, "pitch_track", wav)
+        pitch = Pitch(T, 0, track)
         st = pitch.struct
-        self._chk(self.lib.zv_pitch_track(self.h, _ptr(w), w.size // hop, C.byref(st)))
+        self._chk(self.lib.zv_pitch_track(self.h, _ptr(w), T, C.byref(st)))
         return pitch
 
     def prepare_batch(self, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
                       return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False,
                       return_bands=False, filter=None) -> "BatchCall":
         """argument arrays and output buffers of one zv_synthesize_batch call, built once (a C host would keep its
-        buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list.  fitted: the
-        zv_synthesize_batch_fitted / _begin_fitted entry points (the lane form: .begin(lane) / .end(lane))"""
+        buffers too): .run() is exactly one call of the C entry point, .results() the (wav, n_frames) list; the lane form is
+        .begin(lane) / .end(lane).  The arguments are BatchCall's"""
         return BatchCall(self, utterances, durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
                          return_contour=return_contour, return_pitch=return_pitch, return_bands=return_bands, filter=filter)
 
@@ -1062,16 +1019,12 @@ class Model:
                          filter=None):
         """utterances: list of (ids, puncts, style, T[, prosody[, phonemes[, target_frames]]]) -> list of (wav, n_frames); each
         utterance keeps its own (N, T) and, with a fifth element, its own prosody controls (None: identity), with a sixth its
-        per-phoneme controls (PhonemeControls, dict of arrays or None), with a seventh its target frame count (None / 0: none).  return_durations: (wav, n_frames, durations) tuples.  fitted:
-        zv_synthesize_batch_fitted — every T is a capacity, wav keeps the capacity shape with zeros behind n_frames * hop.
-        volume: a list, one Volume (dict, 3-sequence) or None per utterance — zv_synthesize_batch_volume; return_levels: every tuple
-        gains the utterance's Level as its last element.  envelope: a list, one Envelope (dict) or None per utterance —
-        zv_synthesize_batch_envelope.  return_contour: False, True, "frames" or "phonemes" for the whole batch, or a list with one of
-        them per utterance — zv_synthesize_batch_contour; every tuple gains the utterance's Contour (None where it asked for none) as
-        its last element.  return_pitch: False, True, "frames", "phonemes" or a PitchTrack for the whole batch, or a list with one of
-        them per utterance — zv_synthesize_batch_pitch; every tuple gains the utterance's Pitch (None where it asked for none) last.
-        return_bands: likewise with a BandLevels — zv_synthesize_batch_bands; every tuple gains the utterance's Bands last.
-        filter: a list with a Filter, a sequence of taps or None per utterance — zv_synthesize_batch_filter"""
+        per-phoneme controls (PhonemeControls, dict of arrays or None), with a seventh its target frame count (None / 0: none).
+        return_durations: (wav, n_frames, durations) tuples.  fitted: every T is a capacity, wav keeps the capacity shape with zeros
+        behind n_frames * hop.  volume, envelope, filter: a list with one value as synthesize takes it, or None, per utterance.
+        return_levels: every tuple gains the utterance's Level as its last element.  return_contour, return_pitch, return_bands: a
+        value as synthesize takes it for the whole batch, or a list with one per utterance; every tuple gains the utterance's
+        Contour, Pitch, Bands (None where it asked for none) as its last element"""
         call = BatchCall(self, utterances, return_durations, fitted, volume=volume, return_levels=return_levels, envelope=envelope,
                          return_contour=return_contour, return_pitch=return_pitch, return_bands=return_bands, filter=filter)
         call.run()
@@ -1080,12 +1033,9 @@ class Model:
             res = [r + (d,) for r, d in zip(res, call.durations)]
         if call.return_levels:
             res = [r + (Level.from_buffer_copy(lv),) for r, lv in zip(res, call.levels)]
-        if call.contour is not None:
-            res = [r + (c,) for r, c in zip(res, call.contours)]
-        if call.pitch is not None:
-            res = [r + (p,) for r, p in zip(res, call.pitches)]
-        if call.band is not None:
-            res = [r + (b,) for r, b in zip(res, call.bands)]
+        for opt in (CONTOUR, PITCH, BANDS):
+            if getattr(call, opt.array) is not None:
+                res = [r + (h,) for r, h in zip(res, getattr(call, opt.keep))]
         return res
 
     # ---- device-resident API ----
@@ -1155,103 +1105,34 @@ class Model:
 
 
 class BatchCall:
-    """utterances: (ids, puncts, style, T), (ids, puncts, style, T, prosody), (ids, puncts, style, T, prosody, phonemes) or
-    (ids, puncts, style, T, prosody, phonemes, target_frames) tuples.  When any utterance carries a target frame count (a seventh
-    element that is not None) the _target entry points are called with the uint32 array .targets (0 for the others), which
-    set_target_frames() rewrites in place: the next run() / begin() fits the durations to the new targets with the same buffers.  When any utterance carries a prosody (the others get the identity) the _prosody entry points are called with the
-    array .prosody, which set_prosody() rewrites in place: the next run() / begin() uses the new values with the same buffers (a
-    captured graph replays with them).  When any utterance carries per-phoneme controls, or durations=True, the _phonemes entry
-    points are called with the array .phonemes (set_phoneme_controls() rewrites an entry) and .durations[i] holds utterance i's
-    phoneme timings after run() / end().  fitted: the _fitted entry points, whatever controls the utterances carry.
-    volume (a list, one Volume / dict / 3-sequence or None per utterance) or return_levels: the _volume entry points, with the array
-    .volume (None entries get the identity; set_volume() rewrites an entry in place for the next run() / begin()) and the array .levels,
-    which holds every utterance's Level after run() / end().
-    envelope (a list, one Envelope / dict or None per utterance): the _envelope entry points, with the zv_envelope array .envelope (None
-    entries get the identity; set_envelope() rewrites an entry for the next run() / begin()); .ekeep[i] is utterance i's checked
-    Envelope, whose gains the array points into.
-    return_contour (False, True, "frames" or "phonemes" for the whole batch, or a list with one of them per utterance): where any
-    utterance asks for a table, the _contour entry points, with the zv_contour array .contour; .contours[i] is utterance i's Contour
-    (None where it asked for none), whose arrays hold its rows after run() / end().
-    return_pitch (False, True, "frames", "phonemes" or a PitchTrack for the whole batch, or a list with one of them per utterance): where
-    any utterance asks for a table, the _pitch entry points, with the zv_pitch array .pitch; .pitches[i] is utterance i's Pitch (None
-    where it asked for none); set_pitch() rewrites an entry's parameters and tables for the next run() / begin().
-    return_bands (False, True, "frames", "phonemes" or a BandLevels for the whole batch, or a list with one of them per utterance): where
-    any utterance asks for a table, the _bands entry points, with the zv_bands array .band; .bands[i] is utterance i's Bands (None where
-    it asked for none); set_bands() rewrites an entry's band count, edges and tables for the next run() / begin().
-    filter (a list with a Filter, a sequence of taps or None per utterance): the _filter entry points, with the zv_filter array .filter;
-    set_filter() rewrites an entry's taps for the next run() / begin()."""
+    """The argument arrays and output buffers of one zv_synthesize_batch call.  utterances: (ids, puncts, style, T[, prosody[, phonemes
+    [, target_frames]]]) tuples.  Every option (an Option each) has a ctypes array [n_utt] under the Option's .array name, which exists
+    when an utterance carries the option (the others get the zeroed struct) and is None otherwise; the form of the entry point
+    follows from which arrays exist (FORMS) and is settled here, once.  The set_* methods rewrite an entry in place: the next run() /
+    begin() uses the new values with the same buffers (a captured graph replays with them).  An option given as a keyword is one
+    wish for the whole batch (the return_* ones only) or a list with one per utterance, None for none.
+    .durations[i] holds utterance i's phoneme timings after run() / end() (durations=True, or any per-phoneme controls); .levels every
+    utterance's Level (volume or return_levels); .contours[i], .pitches[i] and .bands[i] utterance i's Contour, Pitch and Bands, None
+    where it asked for none; .ekeep[i], .fkeep[i] and .pkeep[i] its checked Envelope, Filter and PhonemeControls, whose arrays the
+    structs point into.  fitted: every T is a capacity."""
 
     def __init__(self, model: Model, utterances, durations: bool = False, fitted: bool = False, *, volume=None,
                  return_levels: bool = False, envelope=None, return_contour=False, return_pitch=False, return_bands=False, filter=None):
+        element = lambda k: [u[k] if len(u) > k else None for u in utterances]
         self.fitted = _check_fitted(fitted, [u[3] for u in utterances])
-        self.filter = self.fkeep = None
-        if filter is not None:
-            flts = list(filter)
-            if len(flts) != len(utterances):
-                raise ValueError(f"filter has {len(flts)} entries, the batch has {len(utterances)} utterances")
-            self.fkeep = [_filter(f, f"utterance {i}: ") for i, f in enumerate(flts)]
-            self.filter = (FilterC * len(utterances))(*[f.struct if f is not None else FilterC() for f in self.fkeep])
-        if isinstance(return_bands, (list, tuple)):
-            if len(return_bands) != len(utterances):
-                raise ValueError(f"return_bands has {len(return_bands)} entries, the batch has {len(utterances)} utterances")
-            specs = [_check_bands(w, f"utterance {i}: ") for i, w in enumerate(return_bands)]
-        else:
-            specs = [_check_bands(return_bands)] * len(utterances)
-        self.band = self.bands = None
-        if any(t is not None for t in specs):
-            self.bands = [Bands(u[3], len(u[0]), t) if t is not None else None for t, u in zip(specs, utterances)]
-            self.band = (BandsC * len(utterances))(*[b.struct if b is not None else BandsC() for b in self.bands])
-        if isinstance(return_pitch, (list, tuple)):
-            if len(return_pitch) != len(utterances):
-                raise ValueError(f"return_pitch has {len(return_pitch)} entries, the batch has {len(utterances)} utterances")
-            tracks = [_check_pitch(w, f"utterance {i}: ") for i, w in enumerate(return_pitch)]
-        else:
-            tracks = [_check_pitch(return_pitch)] * len(utterances)
-        self.pitch = self.pitches = None
-        if any(t is not None for t in tracks):
-            self.pitches = [Pitch(u[3], len(u[0]), t) if t is not None else None for t, u in zip(tracks, utterances)]
-            self.pitch = (PitchC * len(utterances))(*[p.struct if p is not None else PitchC() for p in self.pitches])
-        if isinstance(return_contour, (list, tuple)):
-            if len(return_contour) != len(utterances):
-                raise ValueError(f"return_contour has {len(return_contour)} entries, the batch has {len(utterances)} utterances")
-            wishes = [_check_contour(w, f"utterance {i}: ") for i, w in enumerate(return_contour)]
-        else:
-            wishes = [_check_contour(return_contour)] * len(utterances)
-        self.contour = self.contours = None
-        if any(f or p for f, p in wishes):
-            self.contours = [Contour(u[3], len(u[0]), f, p) if f or p else None for (f, p), u in zip(wishes, utterances)]
-            self.contour = (ContourC * len(utterances))(*[c.struct if c is not None else ContourC() for c in self.contours])
-        self.envelope = self.ekeep = None
-        if envelope is not None:
-            envs = list(envelope)
-            if len(envs) != len(utterances):
-                raise ValueError(f"envelope has {len(envs)} entries, the batch has {len(utterances)} utterances")
-            self.ekeep = [_envelope(e, len(u[0]), f"utterance {i}: ") for i, (e, u) in enumerate(zip(envs, utterances))]
-            self.envelope = (EnvelopeC * len(utterances))(*[e.struct if e is not None else EnvelopeC() for e in self.ekeep])
+        for opt, wish in ((FILTER, filter), (BANDS, return_bands), (PITCH, return_pitch), (CONTOUR, return_contour), (ENVELOPE, envelope)):
+            self._build(opt, wish, utterances, wish is not None and not opt.batch_wide)
         self.return_levels = _check_levels(return_levels)
-        self.volume = self.levels = None
-        if volume is not None:
-            vols = list(volume)
-            if len(vols) != len(utterances):
-                raise ValueError(f"volume has {len(vols)} entries, the batch has {len(utterances)} utterances")
-            vols = [_volume(v, f"utterance {i}: ") for i, v in enumerate(vols)]
-            self.volume = (Volume * len(utterances))(*[v if v is not None else Volume() for v in vols])
-        if self.volume is not None or self.return_levels:
-            self.levels = (Level * len(utterances))()
-        tgs = [_check_target(u[6], u[3]) if len(u) > 6 else None for u in utterances]
-        self.targets = None
-        if any(t is not None for t in tgs):
-            self.targets = (C.c_uint32 * len(utterances))(*[t or 0 for t in tgs])
+        self._build(VOLUME, volume, utterances, volume is not None)
+        self.levels = (Level * len(utterances))() if self.volume is not None or self.return_levels else None
+        self._build(TARGET, element(6), utterances)
         self.model = model
         n = self.n = len(utterances)
         self.keep, self.wavs = [], []
         P = C.c_void_p * n
         self.ids_p, self.pun_p, self.sty_p, self.wav_p = P(), P(), P(), P()
         self.Ns, self.Ts, self.nf = (C.c_uint32 * n)(), (C.c_uint32 * n)(), (C.c_uint32 * n)()
-        prs = [_prosody(u[4]) if len(u) > 4 else None for u in utterances]
-        self.prosody = None
-        if any(p is not None for p in prs):
-            self.prosody = (Prosody * n)(*[p if p is not None else Prosody() for p in prs])
+        self._build(PROSODY, element(4), utterances)
         for i, (ids, puncts, style, T) in enumerate(u[:4] for u in utterances):
             a = np.ascontiguousarray(ids, dtype=np.int32)
             b = np.ascontiguousarray(puncts, dtype=np.int32)
@@ -1261,88 +1142,87 @@ class BatchCall:
             self.wavs.append(w)
             self.ids_p[i], self.pun_p[i], self.sty_p[i], self.wav_p[i] = a.ctypes.data, b.ctypes.data, c.ctypes.data, w.ctypes.data
             self.Ns[i], self.Ts[i] = len(a), T
-        pcs = [_phoneme_controls(u[5], len(u[0])) if len(u) > 5 else None for u in utterances]
-        self.phonemes = self.durations = self.dur_p = None
-        self.pkeep = pcs
-        if durations or any(p is not None for p in pcs):
-            self.phonemes = (PhonemeControlsC * n)(*[p.struct if p is not None else PhonemeControlsC() for p in pcs])
+        self._build(PHONEMES, element(5), utterances, durations)
+        self.pkeep = self.pkeep or [None] * n
+        self.durations = self.dur_p = None
+        if self.phonemes is not None:
             self.durations = [np.zeros(int(self.Ns[i]), np.int32) for i in range(n)]
             self.dur_p = P(*[d.ctypes.data for d in self.durations])
+        # the per-step path walks no table: the symbols and the argument tuple of run() and begin(), settled once
+        suffix, tail = _select(FORMS, dict(prosody=self.prosody, phonemes=self.phonemes, durations=self.dur_p, fitted=self.fitted,
+                                           target=self.targets, volume=self.volume, levels=self.levels, envelope=self.envelope,
+                                           contour=self.contour, pitch=self.pitch, bands=self.band, filter=self.filter))
+        self._run, self._begin = "zv_synthesize_batch" + suffix, "zv_synthesize_batch_begin" + suffix
+        self._args = (self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf) + tail
+
+    def _build(self, opt: Option, wish, utterances, always: bool = False):
+        """opt's array and holders: from one wish for the whole batch or a list with one per utterance, each checked; the array exists
+        when an utterance asks for something, or `always`"""
+        n, holders = len(utterances), None
+        if isinstance(wish, (list, tuple)) if opt.batch_wide else wish is not None:
+            wish = list(wish)
+            if len(wish) != n:
+                raise ValueError(f"{opt.keyword} has {len(wish)} entries, the batch has {n} utterances")
+            holders = [opt.holder(w, len(u[0]), u[3], f"utterance {i}: ") for i, (w, u) in enumerate(zip(wish, utterances))]
+        elif opt.batch_wide:
+            checked = opt.check(wish, 0, 0, "")
+            holders = [None if checked is None else opt.hold(checked, len(u[0]), u[3]) for u in utterances]
+        exists = holders is not None and (always or any(h is not None for h in holders))
+        setattr(self, opt.array, (opt.struct * n)(*[opt.c(h) for h in holders]) if exists else None)
+        if opt.keep:
+            setattr(self, opt.keep, holders if exists else None)
+
+    def _set(self, opt: Option, i: int, wish):
+        """utterance i's entry of opt's array, and its holder, for the following run() / begin()"""
+        array = getattr(self, opt.array)
+        if array is None:
+            raise ValueError(f"this BatchCall was built without {opt.without}")
+        holder = opt.holder(wish, int(self.Ns[i]), int(self.Ts[i]), f"utterance {i}: ")
+        if opt.keep:
+            getattr(self, opt.keep)[i] = holder
+        array[i] = opt.c(holder)
 
     def set_phoneme_controls(self, i: int, controls):
-        """utterance i's per-phoneme controls (PhonemeControls, dict of arrays or None) for the following run() / begin() (the call
-        must have been built with per-phoneme controls or durations=True)"""
-        if self.phonemes is None:
-            raise ValueError("this BatchCall was built without per-phoneme controls")
-        pc = _phoneme_controls(controls, int(self.Ns[i]))
-        self.pkeep[i] = pc
-        self.phonemes[i] = pc.struct if pc is not None else PhonemeControlsC()
+        """utterance i's per-phoneme controls (PhonemeControls, dict of arrays or None); needs a call built with per-phoneme controls
+        or durations=True"""
+        self._set(PHONEMES, i, controls)
 
     def set_target_frames(self, i: int, frames):
-        """utterance i's target frame count (0 / None: none) for the following run() / begin() (the call must have been built with a
-        target on some utterance)"""
-        if self.targets is None:
-            raise ValueError("this BatchCall was built without target frame counts")
-        self.targets[i] = _check_target(frames, int(self.Ts[i])) or 0
+        """utterance i's target frame count (0 / None: none); needs a call built with a target on some utterance"""
+        self._set(TARGET, i, frames)
 
     def set_volume(self, i: int, volume):
-        """utterance i's volume (None: the identity) for the following run() / begin() (the call must have been built with volume=)"""
-        if self.volume is None:
-            raise ValueError("this BatchCall was built without volume controls")
-        self.volume[i] = _volume(volume, f"utterance {i}: ") or Volume()
+        """utterance i's volume (None: the identity); needs a call built with volume="""
+        self._set(VOLUME, i, volume)
 
     def set_envelope(self, i: int, envelope):
-        """utterance i's envelope (None: the identity) for the following run() / begin() (the call must have been built with envelope=)"""
-        if self.envelope is None:
-            raise ValueError("this BatchCall was built without envelopes")
-        e = _envelope(envelope, int(self.Ns[i]), f"utterance {i}: ")
-        self.ekeep[i] = e
-        self.envelope[i] = e.struct if e is not None else EnvelopeC()
+        """utterance i's envelope (None: the identity); needs a call built with envelope="""
+        self._set(ENVELOPE, i, envelope)
 
     def set_pitch(self, i: int, return_pitch):
-        """utterance i's pitch request (False / None: none) for the following run() / begin() (the call must have been built with
-        return_pitch=); .pitches[i] is replaced"""
-        if self.pitch is None:
-            raise ValueError("this BatchCall was built without a pitch track")
-        t = _check_pitch(False if return_pitch is None else return_pitch, f"utterance {i}: ")
-        self.pitches[i] = Pitch(int(self.Ts[i]), int(self.Ns[i]), t) if t is not None else None
-        self.pitch[i] = self.pitches[i].struct if t is not None else PitchC()
+        """utterance i's pitch request (False / None: none); needs a call built with return_pitch=; .pitches[i] is replaced"""
+        self._set(PITCH, i, False if return_pitch is None else return_pitch)
 
     def set_bands(self, i: int, return_bands):
-        """utterance i's band request (False / None: none) for the following run() / begin() (the call must have been built with
-        return_bands=); .bands[i] is replaced"""
-        if self.band is None:
-            raise ValueError("this BatchCall was built without band levels")
-        t = _check_bands(False if return_bands is None else return_bands, f"utterance {i}: ")
-        self.bands[i] = Bands(int(self.Ts[i]), int(self.Ns[i]), t) if t is not None else None
-        self.band[i] = self.bands[i].struct if t is not None else BandsC()
+        """utterance i's band request (False / None: none); needs a call built with return_bands=; .bands[i] is replaced"""
+        self._set(BANDS, i, False if return_bands is None else return_bands)
 
     def set_filter(self, i: int, filter):
-        """utterance i's filter (a Filter, a sequence of taps or None: none) for the following run() / begin() (the call must have been
-        built with filter=)"""
-        if self.filter is None:
-            raise ValueError("this BatchCall was built without filters")
-        self.fkeep[i] = _filter(filter, f"utterance {i}: ")
-        self.filter[i] = self.fkeep[i].struct if self.fkeep[i] is not None else FilterC()
+        """utterance i's filter (a Filter, a sequence of taps or None: none); needs a call built with filter="""
+        self._set(FILTER, i, filter)
 
     def set_prosody(self, i: int, prosody):
-        """utterance i's controls for the following run() / begin() (the call must have been built with controls)"""
-        if self.prosody is None:
-            raise ValueError("this BatchCall was built without prosody controls")
-        self.prosody[i] = _prosody(prosody) or Prosody()
+        """utterance i's controls (None: the identity); needs a call built with controls"""
+        self._set(PROSODY, i, prosody)
 
     def run(self):
         m = self.model
-        args = (m.h, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        m._chk(_call_variant(m.lib, "zv_synthesize_batch", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope, self.contour, self.pitch, self.band, self.filter))
+        m._chk(getattr(m.lib, self._run)(m.h, self.n, *self._args))
 
     def begin(self, lane: int):
         """zv_synthesize_batch_begin on `lane`: returns once everything is enqueued; results are valid after end(lane)"""
         m = self.model
-        args = (m.h, lane, self.n, self.ids_p, self.pun_p, self.sty_p, self.Ns, self.Ts, self.wav_p, self.nf)
-        m._chk(_call_variant(m.lib, "zv_synthesize_batch_begin", args, self.prosody, self.phonemes, self.dur_p, self.fitted, self.targets,
-                             self.volume, self.levels, self.envelope, self.contour, self.pitch, self.band, self.filter))
+        m._chk(getattr(m.lib, self._begin)(m.h, lane, self.n, *self._args))
 
     def end(self, lane: int):
         m = self.model

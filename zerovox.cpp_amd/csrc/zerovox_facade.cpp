@@ -211,9 +211,12 @@ void ZeroVOXModel::set_envelope(const zv_envelope *e, uint32_t n)
 
 void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const float *style_embed, uint32_t num_phonemes)
 {
-    const zv_prosody *pr = has_prosody ? &prosody : nullptr;
     if (has_envelope && env_gain_set && env_gain.size() != num_phonemes)
         throw zv::Error(ZV_ERR_ARG, "set_envelope: gains for " + std::to_string(env_gain.size()) + " phonemes, eval() has " +
+                                        std::to_string(num_phonemes));
+    // (set_phoneme_controls also turns the timings on, so every call that carries controls goes to a form that takes them)
+    if (has_phonemes && pc_n != num_phonemes)
+        throw zv::Error(ZV_ERR_ARG, "set_phoneme_controls: controls for " + std::to_string(pc_n) + " phonemes, eval() has " +
                                         std::to_string(num_phonemes));
     frame_levels.assign(contour_frames ? hparams.max_seq_len : 0, zv_frame_level{0.0f, 0.0f});
     phoneme_levels.assign(contour_phonemes ? num_phonemes : 0, zv_frame_level{0.0f, 0.0f});
@@ -222,123 +225,70 @@ void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const flo
     const size_t band_w = band_count && band_count <= zv::BANDS_MAX ? band_count : zv::BANDS_DEFAULT;
     band_frame_rows.assign(band_frames ? (size_t)hparams.max_seq_len * band_w : 0, 0.0f);
     band_phoneme_rows.assign(band_phonemes ? (size_t)num_phonemes * band_w : 0, 0.0f);
-    if (has_volume || has_envelope || contour_frames || contour_phonemes || pitch_frames || pitch_phonemes || band_frames || band_phonemes ||
-        has_filter)
-    {
-        // the volume, envelope and contour forms take what every other form takes (the finished waveform of the one-pass chain is scaled and measured)
-        if (has_phonemes && pc_n != num_phonemes)
-            throw zv::Error(ZV_ERR_ARG, "set_phoneme_controls: controls for " + std::to_string(pc_n) + " phonemes, eval() has " +
-                                            std::to_string(num_phonemes));
-        auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
-        const zv_phoneme_controls pc = {ptr(pc_frames), ptr(pc_scale), ptr(pc_pitch), ptr(pc_energy)};
-        if (record_durations) durations.assign(num_phonemes, 0);
-        const zv_envelope env = {env_gain_set ? env_gain.data() : nullptr, envelope.ramp_frames, envelope.fade_in_samples,
-                                 envelope.fade_out_samples};
-        const zv_contour ctr = {contour_frames ? frame_levels.data() : nullptr, contour_phonemes ? phoneme_levels.data() : nullptr};
-        if (has_filter)
-        {
-            zv_pitch pit = pitch_params;
-            pit.frames = pitch_frames ? pitch_frame_rows.data() : nullptr;
-            pit.phonemes = pitch_phonemes ? pitch_phoneme_rows.data() : nullptr;
-            const zv_bands bnd = {band_frames ? band_frame_rows.data() : nullptr, band_phonemes ? band_phoneme_rows.data() : nullptr, band_count,
-                                  band_edges.empty() ? nullptr : band_edges.data()};
-            const zv_filter flt = {filter_taps.data(), filter_n};
-            chk(zv_synthesize_filter(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
-                                     has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
-                                     has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr, &ctr, &pit, &bnd,
-                                     &flt));
-            return;
-        }
-        if (band_frames || band_phonemes)
-        {
-            zv_pitch pit = pitch_params;
-            pit.frames = pitch_frames ? pitch_frame_rows.data() : nullptr;
-            pit.phonemes = pitch_phonemes ? pitch_phoneme_rows.data() : nullptr;
-            const zv_bands bnd = {band_frames ? band_frame_rows.data() : nullptr, band_phonemes ? band_phoneme_rows.data() : nullptr, band_count,
-                                  band_edges.empty() ? nullptr : band_edges.data()};
-            chk(zv_synthesize_bands(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
-                                    has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
-                                    has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr, &ctr, &pit, &bnd));
-            return;
-        }
-        if (pitch_frames || pitch_phonemes)
-        {
-            zv_pitch pit = pitch_params;
-            pit.frames = pitch_frames ? pitch_frame_rows.data() : nullptr;
-            pit.phonemes = pitch_phonemes ? pitch_phoneme_rows.data() : nullptr;
-            chk(zv_synthesize_pitch(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
-                                    has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
-                                    has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr, &ctr, &pit));
-            return;
-        }
-        chk(zv_synthesize_contour(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr,
-                                  has_phonemes ? &pc : nullptr, record_durations ? durations.data() : nullptr, target_frames, fitted ? 1 : 0,
-                                  has_volume ? &volume : nullptr, has_volume ? &level : nullptr, has_envelope ? &env : nullptr, &ctr));
-        return;
-    }
-    if (record_durations || fitted || target_frames)
-    {
-        // the per-phoneme entry points (controls and / or timings) and the fitted one; N = num_phonemes on both of eval()'s paths
-        if (has_phonemes && pc_n != num_phonemes)
-        {
-            std::string msg = "set_phoneme_controls: controls for " + std::to_string(pc_n) + " phonemes, eval() has " +
-                              std::to_string(num_phonemes);
-            throw zv::Error(ZV_ERR_ARG, msg);
-        }
-        auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
-        const zv_phoneme_controls pc = {ptr(pc_frames), ptr(pc_scale), ptr(pc_pitch), ptr(pc_energy)};
-        const zv_phoneme_controls *pcp = has_phonemes ? &pc : nullptr;
-        if (record_durations) durations.assign(num_phonemes, 0);
-        if (target_frames)
-        {
-            // the target forms take what the _phonemes and _fitted forms take; the stage-by-stage path keeps N = MAX_N_PHONEMES
-            int32_t *dur = record_durations ? durations.data() : nullptr;
-            if (fitted || num_phonemes != (uint32_t)MAX_N_PHONEMES)
-            {
-                chk(zv_synthesize_target(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr, pcp,
-                                         dur, target_frames, fitted ? 1 : 0));
-                return;
-            }
-            chk(zv_encode_taps_target(model, src_seq, puncts, style_embed, MAX_N_PHONEMES, num_phonemes, hparams.max_seq_len, hidden_state,
-                                      &n_frames, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pr, pcp, dur, target_frames));
-            decoder->eval(hidden_state, style_embed, mel);
-            meldec->eval(mel, wav);
-            return;
-        }
-        if (fitted)
-        {
-            chk(zv_synthesize_fitted(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr, pcp,
-                                     record_durations ? durations.data() : nullptr));
-            return;
-        }
-        if (num_phonemes != (uint32_t)MAX_N_PHONEMES)
-        {
-            chk(zv_synthesize_phonemes(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr, pcp,
-                                       durations.data()));
-            return;
-        }
-        chk(zv_encode_taps_phonemes(model, src_seq, puncts, style_embed, MAX_N_PHONEMES, num_phonemes, hparams.max_seq_len, hidden_state,
-                                    &n_frames, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pr, pcp, durations.data()));
+    if (record_durations) durations.assign(num_phonemes, 0);
+
+    // what the setters asked for, each as the entry points take it; which of them a form takes is its place on the ladder
+    auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
+    const zv_prosody *pr = has_prosody ? &prosody : nullptr;
+    const zv_phoneme_controls pc = {ptr(pc_frames), ptr(pc_scale), ptr(pc_pitch), ptr(pc_energy)};
+    const zv_phoneme_controls *pcp = has_phonemes ? &pc : nullptr;
+    int32_t *dur = record_durations ? durations.data() : nullptr;
+    const int fit = fitted ? 1 : 0;
+    const zv_volume *vol = has_volume ? &volume : nullptr;
+    zv_level *lev = has_volume ? &level : nullptr;
+    const zv_envelope env = {env_gain_set ? env_gain.data() : nullptr, envelope.ramp_frames, envelope.fade_in_samples,
+                             envelope.fade_out_samples};
+    const zv_envelope *envp = has_envelope ? &env : nullptr;
+    const zv_contour ctr = {contour_frames ? frame_levels.data() : nullptr, contour_phonemes ? phoneme_levels.data() : nullptr};
+    const zv_pitch pit = {pitch_frames ? pitch_frame_rows.data() : nullptr, pitch_phonemes ? pitch_phoneme_rows.data() : nullptr,
+                          pitch_params.min_lag, pitch_params.max_lag, pitch_params.window, pitch_params.voiced_threshold};
+    const zv_bands bnd = {band_frames ? band_frame_rows.data() : nullptr, band_phonemes ? band_phoneme_rows.data() : nullptr, band_count,
+                          ptr(band_edges)};
+    const zv_filter flt = {filter_taps.data(), filter_n};
+    // a synthesize form on the whole utterance (N = num_phonemes), and an encoder form ahead of the stage objects (N = MAX_N_PHONEMES)
+    auto synthesize = [&](auto form, auto... more) {
+        chk(form(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, more...));
+    };
+    auto stages = [&](auto form, auto... more) {
+        chk(form(model, src_seq, puncts, style_embed, MAX_N_PHONEMES, num_phonemes, hparams.max_seq_len, hidden_state, &n_frames, nullptr,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, more...));
         decoder->eval(hidden_state, style_embed, mel);
         meldec->eval(mel, wav);
-        return;
-    }
-    if (num_phonemes != (uint32_t)MAX_N_PHONEMES)
+    };
+    const bool one_pass = fitted || num_phonemes != (uint32_t)MAX_N_PHONEMES;      // the stage objects are pinned to MAX_N_PHONEMES
+
+    // the waveform stages work on the finished waveform of the one-pass chain: the highest form asked for, never below _contour
+    if (has_filter)
+        synthesize(zv_synthesize_filter, pr, pcp, dur, target_frames, fit, vol, lev, envp, &ctr, &pit, &bnd, &flt);
+    else if (band_frames || band_phonemes)
+        synthesize(zv_synthesize_bands, pr, pcp, dur, target_frames, fit, vol, lev, envp, &ctr, &pit, &bnd);
+    else if (pitch_frames || pitch_phonemes)
+        synthesize(zv_synthesize_pitch, pr, pcp, dur, target_frames, fit, vol, lev, envp, &ctr, &pit);
+    else if (has_volume || has_envelope || contour_frames || contour_phonemes)
+        synthesize(zv_synthesize_contour, pr, pcp, dur, target_frames, fit, vol, lev, envp, &ctr);
+    else if (target_frames)
     {
-        // any length: run the C-ABI path directly with N = num_phonemes (the stage objects are pinned to MAX_N_PHONEMES)
-        chk(zv_synthesize_prosody(model, src_seq, puncts, style_embed, num_phonemes, hparams.max_seq_len, wav, &n_frames, pr));
-        return;
+        if (one_pass) synthesize(zv_synthesize_target, pr, pcp, dur, target_frames, fit);
+        else stages(zv_encode_taps_target, pr, pcp, dur, target_frames);
     }
-    if (pr)
+    else if (fitted)
+        synthesize(zv_synthesize_fitted, pr, pcp, dur);
+    else if (record_durations)
     {
-        // the encoder stage with controls (FS2Encoder::eval keeps the reference's signature): the same call it makes, plus prosody
-        chk(zv_encode_taps_prosody(model, src_seq, puncts, style_embed, MAX_N_PHONEMES, num_phonemes, hparams.max_seq_len,
-                                   hidden_state, &n_frames, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pr));
+        if (one_pass) synthesize(zv_synthesize_phonemes, pr, pcp, dur);
+        else stages(zv_encode_taps_phonemes, pr, pcp, dur);
     }
+    else if (one_pass)
+        synthesize(zv_synthesize_prosody, pr);
+    else if (pr)
+        stages(zv_encode_taps_prosody, pr);
     else
+    {
+        // the reference's own sequence of stage calls
         n_frames = encoder->eval(src_seq, puncts, style_embed, num_phonemes, hidden_state);
-    decoder->eval(hidden_state, style_embed, mel);
-    meldec->eval(mel, wav);
+        decoder->eval(hidden_state, style_embed, mel);
+        meldec->eval(mel, wav);
+    }
 }
 
 void ZeroVOXModel::eval(void)
