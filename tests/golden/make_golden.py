@@ -9,6 +9,7 @@ Run in the build container only (it needs /root/reference to have been compiled 
     python tests/golden/make_golden.py value_ranges    (only the value-range stage fixture)
     python tests/golden/make_golden.py resblock_geometries    (only the residual-block tap-count fixture)
     python tests/golden/make_golden.py encdec_geometries    (only the encoder / decoder width, FFN tap and mel-count fixture)
+    python tests/golden/make_golden.py voc_widths    (only the vocoder-width fixture)
 Fixtures hold inputs' *recipes* (geometry, seeds — inputs are regenerated bit-identically by
 zerovox.cpp_amd/synth.py) and the reference's OUTPUTS: in full for the small geometries, as strided
 samples + SHA-256 of the full f32 buffer for the full-size configs of BASELINE.json.  ISA of the
@@ -468,6 +469,28 @@ def encdec_geometries_case(tmp="/tmp"):
     np.savez_compressed(os.path.join(HERE, "encdec_geometries_N%d_T%d.npz" % (ED_N, ED_T)), **out)
 
 
+VW_T = 24                   # frames of the vocoder-width fixture
+
+
+def voc_widths_case(tmp="/tmp"):
+    """The reference's vocoder on every geometry of synth.VOC_WIDTH_GEOMETRIES (256, 496, 768 and 1 024 vocoder channels: stages the
+    project's schedule runs on other kernels than at 512, 128 and 48), VW_T frames of synth.vocoder_mel.  SHA-256 + strided samples
+    of every output."""
+    out = dict(geometries=np.array(synth.VOC_WIDTH_GEOMETRIES), seed_w=SEED_W, T=VW_T, seed_mel=7, stride=STRIDE)
+    for gname in synth.VOC_WIDTH_GEOMETRIES:
+        g = synth.GEOMETRIES[gname]
+        path = os.path.join(tmp, f"golden_{gname}.gguf")
+        synth.write_checkpoint(path, g, SEED_W)
+        _, tensors = gguf.read_gguf(path)
+        wav = zvoracle.run_reference(path, T=VW_T, voc=synth.vocoder_mel(g, tensors, 7, VW_T))["wav"]
+        assert wav.shape == (VW_T * g.hop_size,) and np.isfinite(wav).all(), gname
+        out[gname + "/wav_sha256"] = sha(wav)
+        out[gname + "/wav_samples"] = wav[::STRIDE].copy()
+        print(f"{gname}: wav rms {float(np.sqrt(np.mean(wav.astype(np.float64) ** 2))):.4f}")
+        os.remove(path)
+    np.savez_compressed(os.path.join(HERE, "voc_widths_T%d.npz" % VW_T), **out)
+
+
 if __name__ == "__main__":
     if not zvoracle.have_reference():
         sys.exit("oracle/_ref/zvref missing: run `make -C oracle ref` first")
@@ -485,6 +508,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["encdec_geometries"]:       # only the encoder / decoder geometry fixture
         encdec_geometries_case()
+        sys.exit(0)
+    if sys.argv[1:] == ["voc_widths"]:              # only the vocoder-width fixture
+        voc_widths_case()
         sys.exit(0)
     if sys.argv[1:] == ["heads"]:           # only the encoder head-count fixture
         heads_cases()
@@ -506,3 +532,4 @@ if __name__ == "__main__":
     value_ranges_case()
     resblock_geometries_case()
     encdec_geometries_case()
+    voc_widths_case()

@@ -404,6 +404,13 @@ static const struct { int K, n_dil, dil[3], R; BlockTile want; } TILES[] = {
     {3, 2, {1, 3}, 256, {4, 3, 1, 6, 244}},     {1, 1, {1}, 256, {1, 1, 0, 0, 256}},
 };
 
+// out_conv_lds_bytes / out_conv_supported: C, K -> bytes, fits LDS_DEFAULT
+static const struct { int C, K; size_t lds; bool ok; } OUT_CONV[] = {
+    {112, 7, 64448, true},  {128, 7, 73056, false}, {97, 7, 64448, true},   {113, 7, 73056, false}, {64, 7, 38624, true},
+    {48, 7, 30016, true},   {32, 7, 21408, true},   {31, 7, 21408, true},   {16, 7, 12800, true},   {3, 7, 12800, true},
+    {112, 1, 61664, true},  {128, 1, 69888, false},
+};
+
 #define FAIL(...) return printf(__VA_ARGS__), 1
 
 int main(int argc, char **argv)
@@ -493,6 +500,17 @@ int main(int argc, char **argv)
         if (t.sumd != q.want.sumd || t.dmax != q.want.dmax || t.h2 != q.want.h2 || t.halo != q.want.halo || t.TM != q.want.TM) FAIL("block_tile(K %d, %d dilations, R %d)\n", q.K, q.n_dil, q.R);
         n++;
     }
+    // the output conv's LDS: (256 + K - 1) rows of (2 Cp + 16) bytes + K Cp f16 weights within 64 KiB.  7 taps: 112 channels take
+    // 262 x 240 + 1 568 = 64 448 bytes, 128 take 262 x 272 + 1 792 = 73 056; real channels count padded to 16 (97 .. 112 are one Cp,
+    // 113 the next); the last stages the suite runs (64, 48, 32, 31, 16, 3 channels); an even or missing tap count is no 'same' conv
+    for (const auto &q : OUT_CONV)
+    {
+        if (out_conv_lds_bytes(q.C, q.K) != q.lds || out_conv_supported(q.C, q.K) != q.ok)
+            FAIL("out_conv(C %d, K %d): %zu bytes, supported %d; want %zu, %d\n", q.C, q.K, out_conv_lds_bytes(q.C, q.K), out_conv_supported(q.C, q.K), q.lds, q.ok);
+        n++;
+    }
+    if (out_conv_supported(0, 7) || out_conv_supported(32, 0) || out_conv_supported(32, 6)) FAIL("out_conv: degenerate shapes\n");
+    n++;
     printf("ok %d\n", n);
     return 0;
 }

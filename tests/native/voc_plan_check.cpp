@@ -26,22 +26,31 @@
 using namespace zv;
 
 // geometries: "medium"; "k5": its 32-channel stage's first branch has 5 taps (pair_supported(32, 5) is false: no fused weights);
-// "mixed64": the second branch of its 64-channel stage has 3 taps in its first pair and 5 in the other two
+// "mixed64": the second branch of its 64-channel stage has 3 taps in its first pair and 5 in the other two;
+// "v256", "v496", "v768", "v1024": the small checkpoint with that many vocoder channels (synth.VOC_WIDTH_GEOMETRIES).  What the loader
+// derives from the width, restated (model_load.cpp): a stage has (width >> (i + 1)) channels, padded to 16; its upsample conv reads
+// (width >> i) channels, padded to 16, and has scale x Cp output channels; the conv has its conv_gemm_kernel pack where Cin_p >= 128,
+// Cin_p % 64 == 0, there is a whole group of 8 output tiles and 3 Cin_p >= 768 (load_upsample).  WIDTHS below pins the result by hand.
+static int width_of(const std::string &name)
+{
+    return name == "v256" ? 256 : name == "v496" ? 496 : name == "v768" ? 768 : name == "v1024" ? 1024 : 512;
+}
 static VocGeom geometry(const std::string &name)
 {
     VocGeom g{};
     g.n_up = 4;
     g.n_dil = 3;
     g.dil[0] = 1, g.dil[1] = 3, g.dil[2] = 5;
-    g.in_Cout_p = 512;
+    const int width = width_of(name);
+    g.in_Cout_p = plan_round_up(width, 16);
     const int scales[4] = {5, 5, 4, 3}, taps[3] = {3, 7, 11};
     for (int i = 0; i < 4; i++)
     {
         VocStageGeom &s = g.st[i];
         s.scale = scales[i];
-        s.Cp = 256 >> i;
-        s.up_Cin_p = 512 >> i;
-        s.up_gemm = i < 2;
+        s.Cp = plan_round_up(width >> (i + 1), 16);
+        s.up_Cin_p = plan_round_up(width >> i, 16);
+        s.up_gemm = s.up_Cin_p >= 128 && (s.up_Cin_p & 63) == 0 && conv_gemm_groups(s.scale * s.Cp) >= 1 && 3 * s.up_Cin_p >= 768;
         for (int j = 0; j < 3; j++)
             for (int d = 0; d < 3; d++)
             {
@@ -161,6 +170,58 @@ static const Case CASES[] = {
     {"mixed64", "ZV_BLOCK64=-3", ONE(16), "r0 h0 -N000- -F000- -F100- -W000-"},
     {"mixed64", "ZV_BLOCK64=5", BENCH, "r1 h1 -F0003 pF0001 -F1001 -W000-"},
     {"medium", "ZV_BLOCK64=-11", ONE(16), "r0 h0 -N000- -F000- -F111- -W000-"},
+
+    // ---- other vocoder widths (synth.VOC_WIDTH_GEOMETRIES): a kernel goes with a stage's padded channel count, not its position.
+    // Per width: one short utterance, tests/parity_helpers.py BATCH_REGIME on one utterance of 40 frames, the benchmark batch's shape
+    // (large enough for every merged sum), and ZV_MERGE_ALWAYS on 40 frames (tests/test_gpu_vocoder_widths.py runs these shapes)
+#define BATCH_REGIME_SW "ZV_BLOCK64=-11 ZV_CONV_STREAM=2 ZV_CONV_GEMM=2 ZV_UP_GEMM=2 ZV_PAIR64_RING=2 ZV_TRIPLE_V2=3 ZV_FUSE256=1 ZV_PAIR_MT=0 ZV_DEC_PREPASS=1"
+    // 256: 128 / 64 / 32 / 16 channels.  Pairs of 128 at rate 5, of 64 at 25, whole blocks at 100 (its three outputs feed the next
+    // upsample conv), the 16-channel last stage unfused.  The first upsample conv alone has the pack (256 -> 5 x 128: 20 tiles, 768 deep)
+    // and reads the input conv's f16 output (256 == 256).  Batch: 5 x 32 768 / 118 = 1 388 >= 1 024 merges the 128-channel stage,
+    // 25 x 32 768 / 246 = 3 330 the 64-channel one, whose 3-tap branch goes to block64 (/ 244 = 3 357)
+    {"v256", "", ONE(24), "r0 h0 -F000- -F000- -W000- -N000-"},
+    {"v256", BATCH_REGIME_SW, ONE(40), "r0 h1 -F000- -F111- -W000- -N000-"},
+    {"v256", "", BENCH, "r1 h1 -F0001 -F1001 -W000- -N000-"},
+    {"v256", "ZV_MERGE_ALWAYS=1", ONE(40), "r0 h0 -F0001 -F0001 -W000- -N000-"},
+    // 496: 248 / 124 / 62 / 31 channels in 256 / 128 / 64 / 32 padded ones: medium's kernels.  The first upsample conv reads 496
+    // channels, no multiple of 64: no pack, so the input conv never writes f16; the second (256 -> 5 x 128) has it
+    {"v496", "", ONE(24), "r0 h0 -N000- -F000- -F000- -W000-"},
+    {"v496", BATCH_REGIME_SW, ONE(40), "r0 h0 -F000- pF000- -F111- -W000-"},
+    {"v496", "", BENCH, "r1 h0 -F0003 pF0001 -F1001 -W000-"},
+    {"v496", "ZV_MERGE_ALWAYS=1", ONE(40), "r0 h0 -N000- -F0001 -F0001 -W000-"},
+    {"v496", "ZV_MERGE_ALWAYS=1 ZV_MERGE_SEQ=0", ONE(40), "r0 h0 -N000- -F0001 -F0001 -W000-"},
+    // ... the whole-block kernel never merges: the output conv reads a merged sum of 31 channels only without it
+    {"v496", "ZV_MERGE_ALWAYS=1 ZV_NO_TRIPLE=1", ONE(40), "r0 h0 -N000- -F0001 -F0001 -F0001"},
+    // 768: 384 / 192 / 96 / 48 channels: pair_supported takes none of them.  Packs for 768 -> 5 x 384 (60 tiles: 7 groups + 4 tiles)
+    // and 384 -> 5 x 192 (30 tiles: 3 groups + 6); 192 -> 4 x 96 is 576 deep: none
+    {"v768", "", ONE(24), "r0 h0 -N000- -N000- -N000- -N000-"},
+    {"v768", BATCH_REGIME_SW, ONE(40), "r0 h1 -N000- pN000- -N000- -N000-"},
+    {"v768", "", BENCH, "r1 h1 -N000- pN000- -N000- -N000-"},
+    {"v768", "ZV_MERGE_ALWAYS=1", ONE(40), "r0 h0 -N000- -N000- -N000- -N000-"},
+    // 1024: 512 / 256 / 128 / 64 channels.  The 512-channel stage unfused; 256 channels at rate 25: (25 x 24 / 54) x 3 = 33 < 256 CUs, not
+    // enough rows for one short utterance; pairs of 128 at rate 100 and of 64 at rate 300, the last stage: its merged sum is the
+    // output conv's only input.  Packs for the first three upsample convs (1 024 -> 5 x 512, 512 -> 5 x 256, 256 -> 4 x 128: 768 deep)
+    {"v1024", "", ONE(24), "r0 h0 -N000- -N000- -F000- -F000-"},
+    {"v1024", BATCH_REGIME_SW, ONE(40), "r0 h1 -N000- pF000- pF000- -F111-"},
+    {"v1024", "", BENCH, "r1 h1 -N000- pF0003 pF0001 -F1001"},
+    {"v1024", "ZV_MERGE_ALWAYS=1", ONE(40), "r0 h0 -N000- -N000- -F0001 -F0001"},
+    {"v1024", "ZV_MERGE_ALWAYS=1 ZV_MERGE_SEQ=0", ONE(40), "r0 h0 -N000- -N000- -F0001 -F0001"},
+    {"v1024", BATCH_REGIME_SW " ZV_MERGE_ALWAYS=1", ONE(40), "r0 h1 -N000- pF0003 pF0001 -F1111"},
+    // a tail group of 4 utterances of a 16 x 900-frame batch (tests/test_gpu_vocoder_widths.py), fitted: 300 x 900 x 4 / 246 = 4 390 >= 1 024
+    // merges the 64-channel last stage inside the group, / 244 = 4 426 gives its 3-tap branch to block64; width 256: nothing to fuse there
+    // (a group runs its last stage only; the stages before it are planned, and run, for the whole batch)
+    {"v1024", "", with(call(4, 900, 14400), true, false, false, -1), "r0 h0 -N000- pF0003 pF0001 -F1001"},
+    {"v256", "", with(call(4, 900, 14400), true, false, false, -1), "r0 h0 -F000- -F000- -W000- -N000-"},
+};
+
+// what the loader makes of a width: padded output channels of the input conv; per stage padded channels, padded input channels of
+// the upsample conv, whether it has its conv_gemm_kernel pack
+static const struct { const char *name; int in_Cout_p, Cp[4], up_Cin_p[4]; bool up_gemm[4]; } WIDTHS[] = {
+    {"medium", 512, {256, 128, 64, 32}, {512, 256, 128, 64}, {true, true, false, false}},
+    {"v256", 256, {128, 64, 32, 16}, {256, 128, 64, 32}, {true, false, false, false}},
+    {"v496", 496, {256, 128, 64, 32}, {496, 256, 128, 64}, {false, true, false, false}},
+    {"v768", 768, {384, 192, 96, 48}, {768, 384, 192, 96}, {true, true, false, false}},
+    {"v1024", 1024, {512, 256, 128, 64}, {1024, 512, 256, 128}, {true, true, true, false}},
 };
 
 // one utterance of 16 frames, medium geometry (tests/parity_helpers.py: VOCODER_REGIMES by name, BATCH_REGIME as "batch_regime").
@@ -222,6 +283,14 @@ int main(int argc, char **argv)
             if (got != c.want)
                 return printf("%s [%s] nseg %d t_max %d t_rows %zu fitted %d runs_off %d dbg %d/%d:\n  got  %s\n  want %s\n", c.geom, c.switches, c.c.nseg,
                               c.c.t_max, c.c.t_rows, c.c.fitted, c.c.runs_off, c.c.dbg_active, c.c.dbg_stage, got.c_str(), c.want), 1;
+            n++;
+        }
+        for (const auto &q : WIDTHS)
+        {
+            const VocGeom g = geometry(q.name);
+            bool same = g.in_Cout_p == q.in_Cout_p;
+            for (int i = 0; i < 4; i++) same = same && g.st[i].Cp == q.Cp[i] && g.st[i].up_Cin_p == q.up_Cin_p[i] && g.st[i].up_gemm == q.up_gemm[i];
+            if (!same) return printf("geometry %s: not what the table says\n", q.name), 1;
             n++;
         }
         for (const auto &q : GROUPS)

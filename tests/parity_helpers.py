@@ -429,6 +429,24 @@ def receptive_radius(g, tensors):
     return worst
 
 
+# ---- the merged MRF sum as the output conv's input (tests/test_gpu_vocoder_widths.py, tests/test_voc_plan_cpu.py) -----------
+# (geometry, switches, plan of one utterance of WIDTH_MERGE_T frames as tests/native/voc_plan_check.cpp prints it, whether the last
+# stage stores the merged sum: the output conv then reads one tensor).  The GPU test runs these switches at this length; the CPU test
+# holds csrc/voc_plan.h to the plans, so the GPU test knows which form ran without a profile (the merged launch and the three
+# branches side by side are both one launch).  The 32-channel last stage of small_v496 runs the whole-block kernel, which never
+# merges: its merged sum (31 real channels) reaches the output conv only with that kernel off.
+WIDTH_MERGE_T = 40
+WIDTH_MERGE_CASES = (
+    ("small_v1024", {"ZV_MERGE_ALWAYS": 1}, "r0 h0 -N000- -N000- -F0001 -F0001", True),
+    ("small_v1024", {"ZV_MERGE_ALWAYS": 1, "ZV_MERGE_SEQ": 0}, "r0 h0 -N000- -N000- -F0001 -F0001", True),
+    ("small_v1024", {"ZV_MERGE_ALWAYS": 1, "ZV_FUSE256": 1}, "r0 h0 -N000- -F0003 -F0001 -F0001", True),
+    ("small_v496", {"ZV_MERGE_ALWAYS": 1}, "r0 h0 -N000- -F0001 -F0001 -W000-", False),
+    ("small_v496", {"ZV_MERGE_ALWAYS": 1, "ZV_MERGE_SEQ": 0}, "r0 h0 -N000- -F0001 -F0001 -W000-", False),
+    ("small_v496", {"ZV_MERGE_ALWAYS": 1, "ZV_NO_TRIPLE": 1}, "r0 h0 -N000- -F0001 -F0001 -F0001", True),
+    ("small_v496", {"ZV_MERGE_ALWAYS": 1, "ZV_MERGE_SEQ": 0, "ZV_NO_TRIPLE": 1, "ZV_FUSE256": 1}, "r0 h0 -F0001 -F0001 -F0001 -F0001", True),
+)
+
+
 # ---- decoder conv tile split (tests/test_gpu_encdec_geometries.py, tests/test_boundary_cpu.py) ------------------------------
 # restated from zerovox.cpp_amd/csrc/conv_gemm.hip (conv_gemm_groups / conv_gemm_tiles): a wide conv of a batch runs whole groups
 # of 8 32-channel output tiles on conv_gemm_kernel, which also takes ONE leftover tile; two or more leftovers run on

@@ -224,6 +224,44 @@ def test_receptive_radius_of_the_vocoder_geometries(ckpt):
         assert halo_from_convs1_d0(g, tensors) == 23, name
 
 
+def test_voc_width_geometries_reach_what_they_claim(ckpt):
+    """synth.VOC_WIDTH_GEOMETRIES: the width changes no tap count, so the receptive radius stays medium's 20 frames (the bound
+    tests/test_gpu_vocoder_widths.py holds zv_vocoder_halo_frames to); the tensors carry the width, halved per stage, the reference's
+    strides and 3 / 7 / 11 taps; the stages are the real and padded channel counts synth.py names (496: pad channels in every stage,
+    15.5 output tiles of the input conv; 768 and the first stage of 1024: no width a fused kernel takes); and the first upsample conv
+    of 768 channels splits into 7 groups of 8 tiles on conv_gemm_kernel and 4 tiles at nt_begin = 56"""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from parity_helpers import conv_gemm_groups, conv_gemm_tiles, receptive_radius
+    from zerovox_cpp_amd import synth
+    stages = {"small_v256": ((128, 64, 32, 16), (128, 64, 32, 16)), "small_v496": ((248, 124, 62, 31), (256, 128, 64, 32)),
+              "small_v768": ((384, 192, 96, 48), (384, 192, 96, 48)), "small_v1024": ((512, 256, 128, 64), (512, 256, 128, 64))}
+    assert tuple(stages) == synth.VOC_WIDTH_GEOMETRIES
+    fused = (32, 64, 128, 256)                              # csrc/conv_plan.h pair_supported
+    small = synth.SMALL
+    for name, (real, padded) in stages.items():
+        _, g, t = ckpt(name)
+        assert (g.E, g.conv_filter_size, g.encoder_layer, g.num_mels, g.max_seq_len) == (small.E, small.conv_filter_size, small.encoder_layer,
+                                                                                        small.num_mels, small.max_seq_len), name
+        assert g.upsample_scales == (5, 5, 4, 3) and g.resblock_kernels == (3, 7, 11) and g.hop_size == 300 and g.voc_kernel_size == 7, name
+        assert receptive_radius(g, t) == 20, name
+        C = g.voc_channels
+        assert C % 16 == 0 and t["_meldec.input_conv.w"].shape == (C, g.num_mels, 7), name
+        for i, (c, cp) in enumerate(zip(real, padded)):
+            assert c == C >> (i + 1) and cp == (c + 15) // 16 * 16, (name, i)
+            assert t[f"_meldec.upsamples.{i}.1.w"].shape == (c, C >> i, 2 * g.upsample_scales[i]), (name, i)
+            for j, k in enumerate(g.resblock_kernels):
+                for d in range(3):
+                    assert t[f"_meldec.blocks.{3 * i + j}.convs1.{d}.1.w"].shape == (c, c, k), (name, i, j, d)
+                    assert t[f"_meldec.blocks.{3 * i + j}.convs2.{d}.1.w"].shape == (c, c, k), (name, i, j, d)
+        assert t["_meldec.output_conv.1.w"].shape == (1, real[3], 7), name
+    assert all(cp in fused for cp in stages["small_v496"][1]) and all(c != cp for c, cp in zip(*stages["small_v496"]))
+    assert (496 + 15) // 16 * 16 == 496 and 496 % 32 == 16                     # the input conv's last output tile is half padding
+    assert not any(cp in fused for cp in stages["small_v768"][1]) and stages["small_v1024"][1][0] not in fused
+    assert [cp in fused for cp in stages["small_v256"][1]] == [True, True, True, False]
+    assert (5 * 384 // 32, conv_gemm_groups(5 * 384), conv_gemm_tiles(5 * 384)) == (60, 7, 56)
+
+
 def test_encdec_geometries_reach_what_they_claim(ckpt):
     """synth.ENCDEC_GEOMETRIES: every one is legal for the loader (E % 16 == 0, H divides E, odd FFN taps, num_mels % 16 == 0) and
     splits its decoder convs (E and 2E output channels) over conv_gemm_kernel and the generic kernel as synth.py says — e576 / e720

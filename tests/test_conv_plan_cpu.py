@@ -6,7 +6,10 @@ the memory-bound cap, every clause of the two-tiles-per-wave rule, ZV_CONV_MT / 
 clause, its switch, strips and two widths, the loader-wave form clause by clause with its XCD grids, its warm-up flag and the
 two-tile LDS overflow that falls back to the one-tile form, the split between conv_gemm_kernel and the generic kernel, the pair
 kernels' ring form, tile heights, ZV_PAIR_MT and LDS bytes, the whole-block kernels' tile, weight buffers, interleave and fallback,
-block64's grid and 80 KB refusal, and the shapes tests/test_gpu_conv_xcd.py and the benchmark batch were built for.  The cases once
+block64's grid and 80 KB refusal, the output conv's LDS bound (out_conv_supported: 7 taps take 112 channels, not 113 or 128; the loader
+refuses a checkpoint beyond it with ZV_ERR_SHAPE and launch_out_conv a call — pinned here alone: a checkpoint with a last stage of 128
+channels has 2 048 vocoder channels and, even with 1-tap residual blocks, about 100 MB of weights, too large for a GPU test of the
+refusal), and the shapes tests/test_gpu_conv_xcd.py and the benchmark batch were built for.  The cases once
 more through a build with -fsanitize=address,undefined, as a stand-alone program; and conv_gemm_groups / conv_gemm_tiles against their
 restatement in tests/parity_helpers.py."""
 import os
@@ -37,7 +40,7 @@ def exes(tmp_path_factory):
 
 def test_plans_forms_tiles_grids_and_lds(exes):
     r = subprocess.run([exes[0], "cases"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stdout.split()[0] == "ok" and int(r.stdout.split()[1]) >= 190, (r.stdout[-1000:], r.stderr[-500:])
+    assert r.returncode == 0 and r.stdout.split()[0] == "ok" and int(r.stdout.split()[1]) >= 212, (r.stdout[-1000:], r.stderr[-500:])
 
 
 def test_gemm_tiles_match_the_parity_helpers(exes):

@@ -342,6 +342,26 @@ def test_oracle_resblock_geometries(ckpt):
                 assert sha(zvoracle.run_reference(path, T=T, dec=(hid, style))["mel"]) == str(z["chain_mel_sha256"])
 
 
+def test_oracle_voc_widths(ckpt):
+    """the oracle on checkpoints of 256, 496, 768 and 1 024 vocoder channels (synth.VOC_WIDTH_GEOMETRIES) against the reference's
+    vocoder outputs (tests/golden/voc_widths_T24.npz) bit for bit; and live against oracle/_ref where it is present.  The reference
+    takes all four widths (it reads every channel count from the tensors' shapes): none stands on the oracle alone"""
+    from zerovox_cpp_amd import synth
+    from oracle import zvoracle
+    z = np.load(os.path.join(GOLD, "voc_widths_T24.npz"))
+    T, s = int(z["T"]), int(z["stride"])
+    assert tuple(str(n) for n in z["geometries"]) == synth.VOC_WIDTH_GEOMETRIES
+    for gname in synth.VOC_WIDTH_GEOMETRIES:
+        path, g, tensors = ckpt(gname, int(z["seed_w"]))
+        orc = zvoracle.Oracle(tensors)
+        mel_in = synth.vocoder_mel(g, tensors, int(z["seed_mel"]), T)
+        wav = orc.vocoder(mel_in)
+        assert wav.shape == (T * g.hop_size,), gname
+        assert np.array_equal(wav[::s], z[gname + "/wav_samples"]) and sha(wav) == str(z[gname + "/wav_sha256"]), gname
+        if zvoracle.have_reference():
+            assert sha(zvoracle.run_reference(path, T=T, voc=mel_in)["wav"]) == str(z[gname + "/wav_sha256"]), gname
+
+
 def test_oracle_encdec_geometries(ckpt):
     """the oracle on checkpoints of other widths, FFN tap counts, predictor widths and mel counts (synth.ENCDEC_GEOMETRIES: E = 576 /
     720 / 304 / 1 024, FFN taps (3, 3) / (17, 1) / (1, 5), V = 784, one encoder layer, 128 / 272 / 16 mels) against the reference's

@@ -7,7 +7,10 @@ frames, block64 from 2 499, the merged sum from 2 520 / 4 834 / 11 060 at 64 / 1
 whole-block kernel, the second upsample conv's operand pass from 3 277, run-shortening and the input conv's f16 output from 16 384
 rows), fitted, switched-off and tapped calls, the benchmark batch, a tail group of 4 of its utterances planned from 4 segments, a
 32-channel stage with a 5-tap pair (unfused as a whole), a 64-channel branch whose first two pairs differ in taps (not block64's,
-its neighbours are: the guard no checkpoint reaches), the tail group count, and the shared batch-switch rule.  Then every regime of
+its neighbours are: the guard no checkpoint reaches), the tail group count, and the shared batch-switch rule.  On the small
+checkpoint at 256, 496, 768 and 1 024 vocoder channels (synth.VOC_WIDTH_GEOMETRIES; what the loader derives from a width pinned by
+hand): one short utterance, BATCH_REGIME on one utterance, the benchmark batch's shape, ZV_MERGE_ALWAYS, and a tail group of 4 of
+16 x 900 fitted frames — fused, whole_block, block64[], merge and up_pass of every stage.  Then every regime of
 tests/parity_helpers.py (VOCODER_REGIMES, BATCH_REGIME) on one utterance of 16 frames.  The cases once more through a build with
 -fsanitize=address,undefined, as a stand-alone program."""
 import os
@@ -15,7 +18,7 @@ import subprocess
 
 import pytest
 
-from parity_helpers import BATCH_REGIME, VOCODER_REGIMES
+from parity_helpers import BATCH_REGIME, VOCODER_REGIMES, WIDTH_MERGE_CASES, WIDTH_MERGE_T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "zerovox.cpp_amd", "csrc")
@@ -38,7 +41,7 @@ def exes(tmp_path_factory):
 
 def test_plans_thresholds_and_group_counts(exes):
     r = subprocess.run([exes[0], "cases"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stdout.split()[0] == "ok" and int(r.stdout.split()[1]) >= 60, (r.stdout[-1000:], r.stderr[-500:])
+    assert r.returncode == 0 and r.stdout.split()[0] == "ok" and int(r.stdout.split()[1]) >= 88, (r.stdout[-1000:], r.stderr[-500:])
 
 
 def test_every_regime_of_the_parity_helpers(exes):
@@ -47,6 +50,19 @@ def test_every_regime_of_the_parity_helpers(exes):
     for name, sw in regimes:
         r = subprocess.run([exes[0], "regime", name] + ["%s=%d" % (k, int(v)) for k, v in sw.items()], capture_output=True, text=True, timeout=60)
         assert r.returncode == 0 and r.stdout.strip() == "ok", (name, r.stdout[-1000:], r.stderr[-500:])
+
+
+def test_merged_output_conv_cases_of_the_width_tests(exes):
+    """parity_helpers.WIDTH_MERGE_CASES: the plan of one utterance of WIDTH_MERGE_T frames under each case's switches is the one the
+    table states — tests/test_gpu_vocoder_widths.py runs exactly these and takes from the table which form ran.  At least one case
+    per width stores the last stage's merged sum (the output conv's one-input form)"""
+    assert {g for g, _, _, merged in WIDTH_MERGE_CASES if merged} == {"small_v1024", "small_v496"}
+    for gname, sw, plan, merged in WIDTH_MERGE_CASES:
+        assert gname.startswith("small_v")
+        r = subprocess.run([exes[0], "plan", gname[len("small_"):], "1", str(WIDTH_MERGE_T), str(WIDTH_MERGE_T)] +
+                           ["%s=%d" % (k, int(v)) for k, v in sw.items()], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0 and r.stdout.strip() == plan, (gname, sw, r.stdout[-1000:], r.stderr[-500:])
+        assert (plan.split()[-1][-1] == "1") == merged, (gname, sw)
 
 
 def test_header_under_address_and_undefined_sanitizers(exes):

@@ -1306,9 +1306,8 @@ __global__ __launch_bounds__(256) void out_conv_tanh_kernel(const OutConvArgs a)
 
 hipError_t launch_out_conv(hipStream_t s, const OutConvArgs &a)
 {
-    const int Cp = round_up(a.C, 16);
-    const size_t lds = (size_t)(256 + a.K - 1) * (Cp * 2 + 16) + (size_t)a.K * Cp * 2;
-    if (lds > 64 * 1024 || a.segs.nseg < 1) return hipErrorInvalidValue;
+    const size_t lds = out_conv_lds_bytes(a.C, a.K);
+    if (!out_conv_supported(a.C, a.K) || a.segs.nseg < 1) return hipErrorInvalidValue;
     const int tps = (a.segs.max_rows * a.rate + 255) / 256;
     hipLaunchKernelGGL(out_conv_tanh_kernel, dim3(tps * a.segs.nseg), dim3(256), lds, s, a);
     return hipGetLastError();

@@ -282,6 +282,17 @@ inline ConvPlan conv_plan(const ConvDesc *jobs, const ConvCall &c)
     return p;
 }
 
+// ---- the vocoder's output conv (conv.hip: out_conv_tanh_kernel) ----
+// C channels -> 1, K taps: a workgroup keeps its 256 output rows' operand window (256 + K - 1 rows of Cp f16 channels, 16 bytes of
+// row padding) and the K x Cp weights in LDS, inside what a launch gets without asking.  7 taps: Cp <= 112.  The loader refuses a
+// checkpoint whose last stage is wider, the launcher a call that is
+inline size_t out_conv_lds_bytes(int C, int K)
+{
+    const int Cp = plan_round_up(C, 16);
+    return (size_t)(256 + K - 1) * (Cp * 2 + 16) + (size_t)K * Cp * 2;
+}
+inline bool out_conv_supported(int C, int K) { return C >= 1 && K >= 1 && (K & 1) == 1 && out_conv_lds_bytes(C, K) <= LDS_DEFAULT; }
+
 // ---- the fused ResBlock kernels (conv1d_mfma.hip) ----
 constexpr int TRIPLE_MAX_DIL = 3;
 

@@ -305,6 +305,10 @@ Model::Model(const std::string &path, int dev) : device(dev)
         if ((hp.voc_channels >> n_up) != (uint32_t)C) fail(ZV_ERR_SHAPE, "vocoder channels %u do not halve down to %d over %d stages", hp.voc_channels, C, n_up);
         voc_.out_K = (int)w.ne[0];
         if (voc_.out_K != 7) fail(ZV_ERR_SHAPE, "tensor _meldec.output_conv.1.w: kernel size %d, the reference pads for 7", voc_.out_K);
+        // the output conv keeps a tile's operand rows and its weights in LDS (conv_plan.h): 7 taps take at most 112 channels
+        if (!out_conv_supported(C, voc_.out_K))
+            fail(ZV_ERR_SHAPE, "tensor _meldec.output_conv.1.w: %d input channels; the output conv runs at most 112 (%zu bytes of LDS, %zu allowed)", C,
+                 out_conv_lds_bytes(C, voc_.out_K), LDS_DEFAULT);
         voc_.out_C = C;
         const int Cp = round_up(C, 16);
         std::vector<uint16_t> h((size_t)voc_.out_K * Cp, 0);

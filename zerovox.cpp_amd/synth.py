@@ -199,9 +199,36 @@ ENCDEC_GEOMETRIES = ("medium_e576", "medium_e720", "small_e304", "medium_e1024")
 MEDIUM_M100 = Geometry(name="medium_m100", num_mels=100)
 MEDIUM_FFN8 = Geometry(name="medium_ffn8", conv_kernel_size=(8, 1))
 
+# SMALL with other vocoder widths (the width is the shape of `_meldec.input_conv.w`; it halves per upsample stage).  The schedule
+# picks a stage's kernels by its padded channel count Cp (csrc/voc_plan.h, csrc/conv_plan.h), not by its position, so each width
+# puts the kernels at other rates (5 / 25 / 100 / 300 rows per frame) than medium (256 / 128 / 64 / 32), small (64 / 32 / 16 / 16)
+# and tiny (32 / 16 / 16 / 16) do; tests/native/voc_plan_check.cpp pins the plan of each:
+#  * small_v256: 128 / 64 / 32 / 16 — resblock_pair_kernel<128> at rate 5 (behind it an upsample of stride 5), pair64 / block64 at
+#    rate 25, the whole-block 32-channel kernel at rate 100, its three outputs read by the next upsample conv's three-input
+#    prologue; the last stage (16 channels) on the generic conv kernel, as is the 16-channel output conv; tail groups split a last
+#    stage that is not the whole-block kernel;
+#  * small_v496: 248 / 124 / 62 / 31 real channels in 256 / 128 / 64 / 32 padded ones — every fused kernel, every upsample conv
+#    (padded Cout) and the output conv (C = 31) with pad channels; the input conv has 15.5 output tiles;
+#  * small_v768: 384 / 192 / 96 / 48 — no fused kernel anywhere: the generic kernel's 11-tap dilation-5 convs over a 256 + 128
+#    channel split and over 192 / 96 / 48 channels in one chunk, a 768 -> 5 x 384 upsample conv on conv_gemm_kernel (7 groups of 8
+#    tiles, 4 leftover tiles on conv1d_mfma_kernel from nt_begin = 56), stages of 1.5 output tiles;
+#  * small_v1024: 512 / 256 / 128 / 64 — an unfused 512-channel stage (two 256-channel chunks), resblock_pair_kernel<256> at rate
+#    25, <128> at rate 100, and a 64-channel last stage at rate 300: pair64 / block64 there, whose merged MRF sum the output conv
+#    reads, alone, in its one-input form (also inside a tail group)
+SMALL_V256 = Geometry(name="small_v256", emb_dim=112, punct_emb_dim=16, conv_filter_size=256, encoder_layer=2, encoder_head=2,
+                      vp_filter_size=64, ve_n_bins=64, max_seq_len=256, voc_channels=256)
+SMALL_V496 = Geometry(name="small_v496", emb_dim=112, punct_emb_dim=16, conv_filter_size=256, encoder_layer=2, encoder_head=2,
+                      vp_filter_size=64, ve_n_bins=64, max_seq_len=256, voc_channels=496)
+SMALL_V768 = Geometry(name="small_v768", emb_dim=112, punct_emb_dim=16, conv_filter_size=256, encoder_layer=2, encoder_head=2,
+                      vp_filter_size=64, ve_n_bins=64, max_seq_len=256, voc_channels=768)
+SMALL_V1024 = Geometry(name="small_v1024", emb_dim=112, punct_emb_dim=16, conv_filter_size=256, encoder_layer=2, encoder_head=2,
+                       vp_filter_size=64, ve_n_bins=64, max_seq_len=256, voc_channels=1024)
+VOC_WIDTH_GEOMETRIES = ("small_v256", "small_v496", "small_v768", "small_v1024")
+
 GEOMETRIES = {g.name: g for g in (MEDIUM, TINY, SMALL, MEDIUM8, MEDIUM_H1, MEDIUM_H3, MEDIUM_H4, MEDIUM_H8, MEDIUM_E1024,
                                   MEDIUM_RB357, MEDIUM_RB_WIDE, MEDIUM_RB_DILK, MEDIUM_RB_C1C2, MEDIUM_RB_C2WIDE, MEDIUM_UP4553,
-                                  MEDIUM_VOCK5, MEDIUM_E576, MEDIUM_E720, SMALL_E304, MEDIUM_M100, MEDIUM_FFN8)}
+                                  MEDIUM_VOCK5, MEDIUM_E576, MEDIUM_E720, SMALL_E304, MEDIUM_M100, MEDIUM_FFN8, SMALL_V256,
+                                  SMALL_V496, SMALL_V768, SMALL_V1024)}
 
 
 def sinusoid_table(n_position: int, d_hid: int) -> np.ndarray:
