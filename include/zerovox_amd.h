@@ -785,6 +785,38 @@ zv_status zv_synchronize(zv_model *m);
 /* capture the vocoder schedule for a given T into a hipGraph and replay it on later calls with the
  * same (T, d_mel, d_wav); 0 turns graph replay off */
 zv_status zv_set_graph_mode(zv_model *m, int on);
+/* The cache of captured graphs.  With graph mode on, a call that is not being profiled looks its graph up and replays it, or captures
+ * it first.  KEY: the entry point's kind, the lane, the switch epoch (every zv_debug_set advances it), the batch's capacities
+ * (utterances, longest phoneme count rounded up to 32, longest frame capacity rounded up to 64), which options the call carries and
+ * the lane's buffers it runs on.  The utterances' real lengths and every option's VALUES are read at run time and key nothing.
+ * VICTIM: the cache holds `capacity` graphs (16 by default).  A capture that finds it full removes exactly one: a graph of an older
+ * switch epoch if there is one (it can never be replayed again), otherwise the graph replayed or captured least recently; among
+ * several candidates the least recently used.  A lane that regrows its activation arena or one of its I/O blocks loses its own graphs,
+ * the other lanes keep theirs.  EVICTION WAITS FOR NO LANE: the removed graph is destroyed once the lane that replays it has passed
+ * an event recorded at that moment, which later captures check; only when more than `capacity` graphs wait like that does a capture wait,
+ * for the oldest of them alone.  A replay adds no event, no wait and no allocation.  Turning graph mode off keeps the graphs.
+ * The waveform's bits do not depend on whether a call was captured, replayed or run eagerly.
+ * zv_graph_stats, counts since zv_model_load:
+ *   capacity         the slots of the cache
+ *   entries          graphs held now, <= capacity
+ *   retired          graphs removed from the cache and not yet destroyed, <= capacity
+ *   lookups          calls that went through the cache (graph mode on, not profiling); a synthesize call is one or two of them
+ *   hits             lookups that replayed a held graph
+ *   captures         lookups that captured a new one
+ *   evictions        graphs of the current switch epoch removed as the least recently used (a full cache, or a smaller capacity)
+ *   stale_evictions  graphs of an older switch epoch removed for the same reasons
+ *   lane_drops       graphs removed because their lane regrew its arena or a block
+ *   full_drops       graphs removed when everything goes (zv_model_free)
+ * Always: lookups = hits + captures, and captures = entries + evictions + stale_evictions + lane_drops + full_drops.
+ * zv_set_graph_cache: capacity 1 .. 1024, anything else is ZV_ERR_ARG ("graph cache capacity") and changes nothing; a smaller capacity
+ * evicts by the victim rule until the cache fits.  zv_graph_cache_stats waits for nothing and touches no stream. */
+typedef struct
+{
+    uint32_t capacity, entries, retired, reserved; /* reserved = 0 */
+    uint64_t lookups, hits, captures, evictions, stale_evictions, lane_drops, full_drops;
+} zv_graph_stats;
+zv_status zv_set_graph_cache(zv_model *m, uint32_t capacity);
+zv_status zv_graph_cache_stats(zv_model *m, zv_graph_stats *out);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* per-kernel-family timing measured with HIP events on the model's stream (eager launches).  algo_bytes / algo_flops are

@@ -31,6 +31,7 @@ SYMBOLS = [
     "zv_synthesize_pitch", "zv_synthesize_batch_pitch", "zv_synthesize_batch_begin_pitch", "zv_pitch_track",
     "zv_synthesize_bands", "zv_synthesize_batch_bands", "zv_synthesize_batch_begin_bands", "zv_band_levels",
     "zv_synthesize_filter", "zv_synthesize_batch_filter", "zv_synthesize_batch_begin_filter", "zv_filter_wave", "zv_filter_design",
+    "zv_set_graph_cache", "zv_graph_cache_stats",
 ]
 
 
@@ -520,6 +521,20 @@ class KernelStat(C.Structure):
                 ("algo_bytes", C.c_double), ("algo_flops", C.c_double)]
 
 
+class GraphStats(C.Structure):
+    """zv_graph_stats: the captured-graph cache since the model was loaded.  lookups = hits + captures, and captures = entries +
+    evictions + stale_evictions + lane_drops + full_drops (the last two count graphs, not drops)."""
+    _fields_ = [("capacity", C.c_uint32), ("entries", C.c_uint32), ("retired", C.c_uint32), ("reserved", C.c_uint32),
+                ("lookups", C.c_uint64), ("hits", C.c_uint64), ("captures", C.c_uint64), ("evictions", C.c_uint64),
+                ("stale_evictions", C.c_uint64), ("lane_drops", C.c_uint64), ("full_drops", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+    def __repr__(self):
+        return "GraphStats(" + ", ".join(f"{k}={v}" for k, v in self.as_dict().items()) + ")"
+
+
 class ZvError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"zv_status {status}: {msg}")
@@ -627,7 +642,9 @@ def _bind(lib):
                            ("zv_pitch_track", [vp, vp, u32, C.POINTER(PitchC)]),
                            ("zv_band_levels", [vp, vp, u32, C.POINTER(BandsC)]),
                            ("zv_filter_wave", [vp, vp, u32, C.POINTER(FilterC), vp]),
-                           ("zv_filter_design", [u32, vp, vp, u32, vp])):
+                           ("zv_filter_design", [u32, vp, vp, u32, vp]),
+                           ("zv_set_graph_cache", [vp, u32]),
+                           ("zv_graph_cache_stats", [vp, C.POINTER(GraphStats)])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
@@ -1066,6 +1083,19 @@ class Model:
 
     def set_graph_mode(self, on: bool):
         self._chk(self.lib.zv_set_graph_mode(self.h, int(on)))
+
+    def set_graph_cache(self, capacity: int):
+        """zv_set_graph_cache: how many captured graphs the model keeps (1 .. 1024, 16 by default); a smaller capacity evicts the
+        least recently used, graphs of an older switch epoch first, and waits for no lane"""
+        if not 0 <= int(capacity) <= 0xFFFFFFFF:
+            raise ValueError(f"capacity {capacity} is no uint32")
+        self._chk(self.lib.zv_set_graph_cache(self.h, int(capacity)))
+
+    def graph_cache_stats(self) -> GraphStats:
+        """zv_graph_cache_stats: a GraphStats of the counts since load; waits for nothing"""
+        st = GraphStats()
+        self._chk(self.lib.zv_graph_cache_stats(self.h, C.byref(st)))
+        return st
 
     def reserve(self, max_phonemes: int, max_frames: int):
         self._chk(self.lib.zv_model_reserve(self.h, max_phonemes, max_frames))

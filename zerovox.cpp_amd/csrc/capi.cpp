@@ -1844,6 +1844,24 @@ zv_status zv_set_graph_mode(zv_model *m, int on)
     });
 }
 
+zv_status zv_set_graph_cache(zv_model *m, uint32_t capacity)
+{
+    return guarded([&] {
+        ZV_NEED(m, "null model");
+        ZV_NEED(zv::graph_capacity_ok(capacity), "graph cache capacity must be 1 .. 1024");
+        ZV_HIP(hipSetDevice(m->m->device));
+        m->m->set_graph_cache(capacity);
+    });
+}
+
+zv_status zv_graph_cache_stats(zv_model *m, zv_graph_stats *out)
+{
+    return guarded([&] {
+        ZV_NEED(m && out, "null argument");
+        m->m->graph_stats(out);
+    });
+}
+
 // ---- measurement -----------------------------------------------------------------------------
 
 zv_status zv_profile_begin(zv_model *m)

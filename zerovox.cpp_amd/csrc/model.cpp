@@ -94,6 +94,7 @@ void *Model::pinned_scratch(size_t bytes)
     if (bytes <= l.pinned_cap) return l.pinned;
     ZV_HIP(hipStreamSynchronize(l.stream));              // the block belongs to this lane: only its streams use it
     if (l.copy_stream) ZV_HIP(hipStreamSynchronize(l.copy_stream));
+    drop_lane_graphs();                                  // a batch graph's first node uploads from this block
     if (l.pinned) hipHostFree(l.pinned);
     l.pinned = nullptr;
     l.pinned_cap = 0;
@@ -107,6 +108,7 @@ void *Model::io_scratch(size_t bytes)
     Lane &l = lane();
     if (bytes <= l.io_cap) return l.io;
     ZV_HIP(hipStreamSynchronize(l.stream));
+    drop_lane_graphs();                                  // the lane's graphs name the block about to be freed
     if (l.io) hipFree(l.io);
     l.io = nullptr;
     l.io_cap = 0;
@@ -150,10 +152,10 @@ void Model::arena_require(size_t bytes)
 {
     if (bytes <= lane().arena.cap) return;
     ZV_HIP(hipStreamSynchronize(stream()));
-    // captured graphs hold pointers into the arena they were captured on: whichever lane regrows its arena, every graph
-    // goes (growth happens a handful of times per process, outside timed regions)
-    drop_graphs();
-    DeviceArena &ar = lane().arena;              // (drop_graphs does not touch lanes_)
+    // captured graphs hold pointers into the arena they were captured on, and only a lane's own graphs name its arena (model.h
+    // graphs_): the lane's slots go, the other lanes keep theirs and are not waited for
+    drop_lane_graphs();
+    DeviceArena &ar = lane().arena;
     if (ar.base) hipFree(ar.base);
     ar = DeviceArena();
     lane().runs_tab = nullptr;                   // the last run table lay in the arena just freed (voc_runs_last)
@@ -267,27 +269,110 @@ void Model::conv(const ConvJob *jobs, int n, const Segs &segs, int rate, const c
     ZV_LAUNCH(name, bytes, flops, launch_conv(stream(), jobs, n, n_cu, segs, rate));
 }
 
+// ---- the graph cache: graph_cache.h decides, this part owns the execs ----
+// No exec is destroyed with work of its own in flight, and no lane is synchronised to evict a graph.
+
+static void destroy_retired(hipGraphExec_t exec, hipEvent_t done)
+{
+    if (exec) hipGraphExecDestroy(exec);
+    if (done) hipEventDestroy(done);
+}
+
 void Model::drop_graphs()
 {
     sync_all_lanes();                            // an exec of another lane may still be running
-    for (auto &g : graphs_)
-        if (g.exec) hipGraphExecDestroy(g.exec);
-    graphs_.clear();
+    graphs_.drop_all([](CapturedGraph &&g, int) { destroy_retired(g.exec, nullptr); });
+    retired_.clear([](RetiredExec &&r) { destroy_retired(r.exec, r.done); });
+}
+
+void Model::drop_lane_graphs()
+{
+    graphs_.drop_lane(cur_lane_, [](CapturedGraph &&g, int) { destroy_retired(g.exec, nullptr); });
+}
+
+void Model::sweep_retired()
+{
+    retired_.sweep([](const RetiredExec &r) { return hipEventQuery(r.done) == hipSuccess; },
+                   [](RetiredExec &&r) { destroy_retired(r.exec, r.done); });
+    (void)hipGetLastError();                     // "not ready" is an answer, not an error for the next launch to report
+}
+
+// The slot has left the cache.  Everything its lane's stream was given so far, the exec's last replay included, lies ahead of an event
+// recorded on that stream now: the exec goes when the event has completed (sweep_retired), or at once where the stream is already idle.
+void Model::retire_graph(CapturedGraph &&g, int lane)
+{
+    hipStream_t s = lanes_[(size_t)lane].stream;
+    const hipError_t idle = hipStreamQuery(s);
+    (void)hipGetLastError();
+    if (idle == hipSuccess) return destroy_retired(g.exec, nullptr);
+    hipEvent_t done = nullptr;
+    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess || hipEventRecord(done, s) != hipSuccess)
+    {
+        hipStreamSynchronize(s);                 // no event to be had: the one stream the exec ran on, then the exec
+        return destroy_retired(g.exec, done);
+    }
+    // bounded by the cache's capacity: a full list waits for its oldest event alone
+    retired_.push(RetiredExec{g.exec, done}, graphs_.capacity(), [](const RetiredExec &r) { hipEventSynchronize(r.done); },
+                  [](RetiredExec &&r) { destroy_retired(r.exec, r.done); });
+}
+
+bool Model::set_graph_cache(uint64_t capacity)
+{
+    if (!graph_capacity_ok(capacity)) return false;
+    sweep_retired();
+    return graphs_.set_capacity(capacity, knob_epoch(), [this](CapturedGraph &&g, int lane) { retire_graph(std::move(g), lane); });
+}
+
+void Model::graph_stats(zv_graph_stats *out) const
+{
+    const GraphCounters &n = graphs_.counters();
+    memset(out, 0, sizeof(*out));
+    out->capacity = graphs_.capacity();
+    out->entries = (uint32_t)graphs_.entries();
+    out->retired = (uint32_t)retired_.size();
+    out->lookups = n.lookups;
+    out->hits = n.hits;
+    out->captures = n.captures;
+    out->evictions = n.evictions;
+    out->stale_evictions = n.stale_evictions;
+    out->lane_drops = n.lane_drops;
+    out->full_drops = n.full_drops;
+}
+
+// the hash of a graph's key: every field the full comparison reads (run_captured), field by field (a Batch has padding).  A keyed
+// field that is missing here costs a collision, which the full comparison settles; a field hashed but not keyed would cost hits
+static uint64_t graph_key_hash(int kind, int lane, unsigned epoch, const Batch &b, const void *const *key, size_t key_bytes)
+{
+    uint64_t h = GRAPH_HASH_SEED;
+    auto add = [&h](const auto &v) { h = graph_hash(h, &v, sizeof(v)); };
+    add(kind), add(lane), add(epoch);
+    add(b.nseg), add(b.n_max), add(b.t_max), add(b.n_rows), add(b.t_rows), add(b.d_tok), add(b.d_frm);
+    if (!b.d_tok) add(b.tok1);
+    if (!b.d_frm) add(b.frm1);
+    add(b.d_ctl), add(b.d_pctl), add(b.d_cum), add(b.d_frm_live), add(b.has_targets), add(b.d_dec_runs), add(b.wave);
+    return graph_hash(h, key, key_bytes);
 }
 
 // Replays the captured schedule for (kind, capacities, buffers) or captures it first.  The capacities decide grids and
 // arena layout; the segment tables are read by the kernels at run time, so a batch graph does not depend on the
-// utterances' lengths.
+// utterances' lengths.  A replay is a hash, a scan of the slots and a launch: no event, no wait, no allocation.
 template <typename F> void Model::run_captured(int kind, const Batch &b, const void *const (&key)[CapturedGraph::NKEY], F &&enqueue)
 {
-    for (auto &g : graphs_)
-        if (g.kind == kind && g.epoch == knob_epoch() && b.same_schedule(g.b) && memcmp(g.p, key, sizeof(key)) == 0)
-        {
-            ZV_HIP(hipGraphLaunch(g.exec, stream()));
-            lane().runs_tab = g.runs_tab;
-            lane().runs_n = g.runs_n;
-            return;
-        }
+    const unsigned epoch = knob_epoch();
+    const int      ln = cur_lane_;
+    const uint64_t hash = graph_key_hash(kind, ln, epoch, b, key, sizeof(key));
+    const int at = graphs_.find(hash, [&](const CapturedGraph &g) {
+        return g.kind == kind && g.lane == ln && g.epoch == epoch && b.same_schedule(g.b) && memcmp(g.p, key, sizeof(key)) == 0;
+    });
+    if (at >= 0)
+    {
+        const CapturedGraph &g = graphs_.hit(at);
+        ZV_HIP(hipGraphLaunch(g.exec, stream()));
+        lane().runs_tab = g.runs_tab;
+        lane().runs_n = g.runs_n;
+        return;
+    }
+    sweep_retired();
     reserve_batch(b);                            // hipMalloc is not capturable
     hipGraph_t graph = nullptr;
     lane().runs_tab = nullptr;
@@ -306,7 +391,8 @@ template <typename F> void Model::run_captured(int kind, const Batch &b, const v
     ZV_HIP(hipStreamEndCapture(stream(), &graph));
     CapturedGraph cg;
     cg.kind = kind;
-    cg.epoch = knob_epoch();       // a graph replays the kernel regime it was captured in: a later zv_debug_set captures anew
+    cg.lane = ln;
+    cg.epoch = epoch;              // a graph replays the kernel regime it was captured in: a later zv_debug_set captures anew
     cg.b = b;
     memcpy(cg.p, key, sizeof(key));
     cg.runs_tab = lane().runs_tab;
@@ -314,14 +400,10 @@ template <typename F> void Model::run_captured(int kind, const Batch &b, const v
     hipError_t e = hipGraphInstantiate(&cg.exec, graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
     if (e != hipSuccess) fail(ZV_ERR_DEVICE, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-    if (graphs_.size() >= 16)
-    {
-        // the oldest graphs may still be executing: drain the stream before their execs go away
-        ZV_HIP(hipStreamSynchronize(stream()));
-        drop_graphs();
-    }
-    graphs_.push_back(cg);
-    ZV_HIP(hipGraphLaunch(cg.exec, stream()));
+    hipGraphExec_t exec = cg.exec;
+    // a full cache gives up exactly one slot (graph_cache.h victim), whose exec may still be running on its own lane
+    graphs_.insert(hash, epoch, ln, std::move(cg), [this](CapturedGraph &&g, int lane) { retire_graph(std::move(g), lane); });
+    ZV_HIP(hipGraphLaunch(exec, stream()));
 }
 
 void Model::chain_dev(const Batch &b, const int32_t *d_ids, const int32_t *d_puncts, const float *d_styles, float *d_hidden,

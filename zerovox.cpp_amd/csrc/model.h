@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "gguf_reader.h"
+#include "graph_cache.h"
 #include "kernels.h"
 #include "wave_stages.h"
 
@@ -132,6 +133,7 @@ struct CapturedGraph
 {
     static constexpr int NKEY = 8;         // the buffers of a call that are not part of its Batch (chain_dev)
     int            kind = 0;               // 0 vocoder, 1 chain
+    int            lane = 0;               // the lane that captured it
     unsigned       epoch = 0;              // knob_epoch() at capture
     Batch          b;
     const void    *p[NKEY] = {};
@@ -249,6 +251,11 @@ class Model
 
     // graph replay of the vocoder schedule
     bool graph_mode = false;
+    // The cache of captured graphs (graph_cache.h holds the policy, DESIGN.md "Serving under changing shapes" the lifetime rule).
+    // set_graph_cache: 1 .. 1024 slots, shrinking evicts by the victim rule and waits for no lane; false for a capacity out of range.
+    // graph_stats: the counters since load; queries nothing on the device.
+    bool set_graph_cache(uint64_t capacity);
+    void graph_stats(zv_graph_stats *out) const;
     void vocode_dev_graph(const Batch &b, const float *d_mel, float *d_wav);
     // encoder -> decoder -> vocoder back to back (graph replay keyed by (capacities, buffers) when graph_mode is on).
     // h2d_src / h2d_dst / h2d_bytes (optional): an input upload that becomes the first node of the schedule
@@ -428,8 +435,17 @@ class Model
     hipEvent_t batch_events_[2 * BATCH_RING] = {};
 
     bool skip_launch_ = false;    // vocode_group: the launches of the part that is not asked for are skipped
-    std::vector<CapturedGraph> graphs_;
-    void drop_graphs();
+    // A slot belongs to the lane that captured it: its graph names that lane's arena, I/O block and pinned block, the caller's own
+    // device buffers (zv_vocode_device, lane 0) and model-lifetime blocks (weights, bands_table), nothing of another lane, and only
+    // that lane's stream ever replays it (the lane is part of the key).
+    GraphCache<CapturedGraph> graphs_;
+    // an exec that has left the cache while its lane's stream may still be replaying it, and the event recorded on that stream then
+    struct RetiredExec { hipGraphExec_t exec; hipEvent_t done; };
+    RetireList<RetiredExec> retired_;
+    void retire_graph(CapturedGraph &&g, int lane);     // destroys the exec once its lane has passed it; waits for no lane
+    void sweep_retired();                               // destroys what has finished (a query per entry)
+    void drop_lane_graphs();                            // the selected lane's slots; its stream has just been synchronised
+    void drop_graphs();                                 // every slot and the retire list, after synchronising every lane (teardown)
     template <typename F> void run_captured(int kind, const Batch &b, const void *const (&key)[CapturedGraph::NKEY], F &&enqueue);
 };
 
