@@ -818,6 +818,44 @@ typedef struct
 zv_status zv_set_graph_cache(zv_model *m, uint32_t capacity);
 zv_status zv_graph_cache_stats(zv_model *m, zv_graph_stats *out);
 
+/* ---- stages in batches -------------------------------------------------------------------- */
+/* The three stage calls over a batch: what zv_synthesize_batch does for the chain — row-concatenated tensors, a segment table in HBM,
+ * one launch per kernel, launch groups of at most 64 utterances / 64 Ki frames of capacity, a captured graph in graph mode — for one
+ * stage at a time.  For a caller that must know the frame counts before it picks capacities, a caller whose mels come from elsewhere,
+ * a caller that wants a batch's hidden or mel.  Utterance u's result is, bit for bit, that of the single call on its arguments:
+ *   zv_encode_batch   hidden, n_frames and durations of zv_encode_taps_target(m, ids[u], puncts[u], styles[u], n_phonemes[u],
+ *                     n_phonemes[u], T[u], hidden[u], &n_frames[u], NULL x 6, &prosody[u], &phonemes[u], durations[u],
+ *                     target_frames[u]), with that call's NULL conventions (prosody, phonemes, durations, target_frames, each NULL =
+ *                     none; an entry of durations may be NULL); n_frames and durations are also those zv_synthesize_batch_target
+ *                     gives for the same arguments.  hidden == NULL, or hidden[u] == NULL, is the PLANNING call: that utterance's
+ *                     hidden is neither staged nor downloaded, and with every hidden NULL only the frame counts (and the scan, where
+ *                     durations are asked for) travel to the host — the frame counts of a batch ahead of its synthesis, for fitted
+ *                     capacities, subtitle layout or slot fitting.
+ *   zv_decode_batch   mel of zv_decode(m, hidden[u], styles[u], T[u], mel[u]): the statistics cover exactly T[u] rows, and as for
+ *                     every stand-alone decode there is no run table (the hidden is the caller's).
+ *   zv_vocode_batch   wav of zv_vocode(m, mel[u], T[u], wav[u]); a padded tail is run-shortened as in any batch, and a batch whose
+ *                     waveforms reach 16 MiB runs its last stage in utterance groups whose downloads overlap the next group's kernels.
+ * zv_vocode_batch_begin / _end are the two halves on lane `lane` (< ZV_BATCH_LANES), as zv_synthesize_batch_begin / _end: one launch
+ * group (else ZV_ERR_ARG), mel[], T[], wav[] and their targets valid until _end, the bits of the synchronous call.  A lane holds one
+ * batch in flight of either kind, and each kind has its own _end: zv_synthesize_batch_end on a vocode batch, zv_vocode_batch_end on a
+ * synthesize batch or on an idle lane is ZV_ERR_ARG and leaves the lane as it is.
+ * Every argument is checked before anything is enqueued (ZV_ERR_ARG; the message names the entry point, the utterance and the
+ * argument): a NULL array or entry other than the optional ones above, n_utt == 0, n_phonemes[u] == 0, T[u] == 0 or above
+ * zv_max_frames(), and for zv_encode_batch the ids and controls as zv_synthesize_batch_target checks them.
+ * No waveform stage (volume ... filter) is taken here, and the tensors are the host's. */
+zv_status zv_encode_batch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                          const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T,
+                          float *const *hidden,            /* NULL, or [n_utt] of which each may be NULL: not downloaded */
+                          uint32_t *n_frames,              /* [n_utt] */
+                          const zv_prosody *prosody, const zv_phoneme_controls *phonemes, int32_t *const *durations,
+                          const uint32_t *target_frames);
+zv_status zv_decode_batch(zv_model *m, uint32_t n_utt, const float *const *hidden, const float *const *styles, const uint32_t *T,
+                          float *const *mel);
+zv_status zv_vocode_batch(zv_model *m, uint32_t n_utt, const float *const *mel, const uint32_t *T, float *const *wav);
+zv_status zv_vocode_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const float *const *mel, const uint32_t *T,
+                                float *const *wav);
+zv_status zv_vocode_batch_end(zv_model *m, uint32_t lane);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* per-kernel-family timing measured with HIP events on the model's stream (eager launches).  algo_bytes / algo_flops are
  * priced by CAPACITY rows, also for a fitted call (whose kernels do less than that when n_frames < T); the vocoder launches of

@@ -32,6 +32,7 @@ SYMBOLS = [
     "zv_synthesize_bands", "zv_synthesize_batch_bands", "zv_synthesize_batch_begin_bands", "zv_band_levels",
     "zv_synthesize_filter", "zv_synthesize_batch_filter", "zv_synthesize_batch_begin_filter", "zv_filter_wave", "zv_filter_design",
     "zv_set_graph_cache", "zv_graph_cache_stats",
+    "zv_encode_batch", "zv_decode_batch", "zv_vocode_batch", "zv_vocode_batch_begin", "zv_vocode_batch_end",
 ]
 
 
@@ -611,6 +612,7 @@ def _bind(lib):
     present: an older build named by ZEROVOX_AMD_LIB for an A/B run may lack the upper ones, and a call that needs one then fails
     with AttributeError; build() checks SYMBOLS on the tree's own library."""
     vp, u32, i32p, fp = C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p
+    pvp, pu32 = C.POINTER(vp), C.POINTER(u32)
     lib.zv_last_error.restype = C.c_char_p
     lib.zv_version.restype = C.c_char_p
     lib.zv_model_load.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
@@ -644,7 +646,13 @@ def _bind(lib):
                            ("zv_filter_wave", [vp, vp, u32, C.POINTER(FilterC), vp]),
                            ("zv_filter_design", [u32, vp, vp, u32, vp]),
                            ("zv_set_graph_cache", [vp, u32]),
-                           ("zv_graph_cache_stats", [vp, C.POINTER(GraphStats)])):
+                           ("zv_graph_cache_stats", [vp, C.POINTER(GraphStats)]),
+                           ("zv_encode_batch", [vp, u32, pvp, pvp, pvp, pu32, pu32, pvp, pu32, C.POINTER(Prosody), C.POINTER(PhonemeControlsC),
+                                                pvp, pu32]),
+                           ("zv_decode_batch", [vp, u32, pvp, pvp, pu32, pvp]),
+                           ("zv_vocode_batch", [vp, u32, pvp, pu32, pvp]),
+                           ("zv_vocode_batch_begin", [vp, u32, u32, pvp, pu32, pvp]),
+                           ("zv_vocode_batch_end", [vp, u32])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
@@ -802,6 +810,14 @@ class switches:
         for k, v in self.saved.items():
             debug_set(k, v)
         return False
+
+
+def _stage_symbol(lib, name: str):
+    """a stage-batch entry point of `lib`; an older library without it fails that call alone, naming the symbol"""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise AttributeError(f"the library has no {name}: it is older than the stage-batch calls")
+    return fn
 
 
 def _waveform(hop: int, who: str, wav):
@@ -1054,6 +1070,72 @@ class Model:
             if getattr(call, opt.array) is not None:
                 res = [r + (h,) for r, h in zip(res, getattr(call, opt.keep))]
         return res
+
+    # ---- the stages in batches (zv_encode_batch, zv_decode_batch, zv_vocode_batch*) ----
+    def encode_batch(self, utterances, return_hidden: bool = True, return_durations: bool = False) -> list:
+        """zv_encode_batch: the encoder over a batch.  utterances: the tuples synthesize_batch takes, (ids, puncts, style, T[, prosody
+        [, phonemes[, target_frames]]]) -> a list of dicts like encode's: "n_frames", "hidden" [T][E] unless return_hidden is False
+        (the planning call: only the frame counts leave the device), "durations" (int32 [len(ids)]) with return_durations or where
+        some utterance carries per-phoneme controls"""
+        fn = _stage_symbol(self.lib, "zv_encode_batch")
+        call = BatchCall(self, utterances, bool(return_durations))
+        hidden = [np.empty((int(T), self.E), np.float32) for T in call.Ts] if return_hidden else None
+        hid_p = (C.c_void_p * call.n)(*[h.ctypes.data for h in hidden]) if return_hidden else None
+        self._chk(fn(self.h, call.n, call.ids_p, call.pun_p, call.sty_p, call.Ns, call.Ts, hid_p, call.nf, call.prosody, call.phonemes,
+                     call.dur_p, call.targets))
+        out = [dict(n_frames=int(call.nf[i])) for i in range(call.n)]
+        for i, d in enumerate(out):
+            if return_hidden:
+                d["hidden"] = hidden[i]
+            if call.durations is not None:
+                d["durations"] = call.durations[i]
+        return out
+
+    def decode_batch(self, hiddens, styles) -> list:
+        """zv_decode_batch: hiddens [T_u][E] and styles [E], one per utterance -> the list of mels [T_u][num_mels]"""
+        fn = _stage_symbol(self.lib, "zv_decode_batch")
+        hid = [np.ascontiguousarray(h, dtype=np.float32) for h in hiddens]
+        sty = [np.ascontiguousarray(s, dtype=np.float32) for s in styles]
+        if len(hid) != len(sty):
+            raise ValueError(f"decode_batch: {len(hid)} hiddens, {len(sty)} styles")
+        n = len(hid)
+        mels = [np.empty((h.shape[0], self.hp.audio_num_mels), np.float32) for h in hid]
+        P = C.c_void_p * n
+        Ts = (C.c_uint32 * n)(*[h.shape[0] for h in hid])
+        self._chk(fn(self.h, n, P(*[h.ctypes.data for h in hid]), P(*[s.ctypes.data for s in sty]), Ts, P(*[m.ctypes.data for m in mels])))
+        return mels
+
+    @staticmethod
+    def _vocode_args(hop: int, mels):
+        """(n, the mel pointers, the frame counts, the waveform pointers) of a vocode batch, the mels and the waveforms themselves"""
+        mel = [np.ascontiguousarray(m, dtype=np.float32) for m in mels]
+        n = len(mel)
+        wavs = [np.empty(m.shape[0] * hop, np.float32) for m in mel]
+        P = C.c_void_p * n
+        return (n, P(*[m.ctypes.data for m in mel]), (C.c_uint32 * n)(*[m.shape[0] for m in mel]), P(*[w.ctypes.data for w in wavs])), mel, wavs
+
+    def vocode_batch(self, mels) -> list:
+        """zv_vocode_batch: mels [T_u][num_mels], one per utterance -> the list of waveforms [T_u * hop]"""
+        fn = _stage_symbol(self.lib, "zv_vocode_batch")
+        args, _mel, wavs = Model._vocode_args(self.hp.audio_hop_size, mels)
+        self._chk(fn(self.h, *args))
+        return wavs
+
+    def vocode_batch_begin(self, lane: int, mels):
+        """zv_vocode_batch_begin on `lane` (one launch group): returns once everything is enqueued; vocode_batch_end(lane) waits and
+        returns the waveforms"""
+        fn = _stage_symbol(self.lib, "zv_vocode_batch_begin")
+        args, mel, wavs = Model._vocode_args(self.hp.audio_hop_size, mels)
+        self._chk(fn(self.h, lane, args[0], *args[1:]))
+        if not hasattr(self, "_vocode_lanes"):
+            self._vocode_lanes = {}
+        self._vocode_lanes[lane] = (args, mel, wavs)      # the arrays the library reads and writes until _end
+
+    def vocode_batch_end(self, lane: int) -> list:
+        fn = _stage_symbol(self.lib, "zv_vocode_batch_end")
+        held = getattr(self, "_vocode_lanes", {})
+        self._chk(fn(self.h, lane))
+        return held.pop(lane)[2] if lane in held else None
 
     # ---- device-resident API ----
     def device_alloc(self, nbytes: int) -> int:

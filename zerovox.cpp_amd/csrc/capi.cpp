@@ -11,6 +11,7 @@
 #include "common.h"
 #include "model.h"
 #include "knobs.h"
+#include "stage_range.h"
 
 using zv::Model;
 
@@ -134,6 +135,9 @@ using zv::Layout;      // wave_stages.h
 // One call's utterances, in the form the batch entry points take them; a single-utterance entry point makes a request of one
 // that points at its own arguments.  out[u] receives utterance u's waveform (zv_encode_taps*: its hidden frames); n_frames,
 // prosody and phonemes are [count] or null; durations is [count] or null, and its entries may be null.
+// A batch request runs the stages of `range` (stage_range.h): out[u] receives what the last stage writes (an encoder-only request:
+// hidden, or null = not downloaded), src[u] is what the first stage reads where that is not the encoder (hidden, mel); what the range
+// does not read (ids, puncts, n, num_phonemes without the encoder; styles with the vocoder alone) is null.
 struct Request
 {
     const char                *fn;                     // the C entry point, for messages
@@ -152,6 +156,8 @@ struct Request
     const uint32_t            *target_frames = nullptr;
     // the waveform stages' arguments (wave_stages.h), in the entry points' order: volume, levels, envelope, contour, pitch, bands, filter
     zv::WaveArgs               wave;
+    zv::StageRange             range;
+    const float *const        *src = nullptr;
 
     // any utterance with a target: then every utterance gets a ctl row and pctl rows (the identity where it has no controls), which
     // the device step between the duration predictor and the length regulator reads and rewrites (kernels.h launch_fit_durations)
@@ -181,11 +187,12 @@ struct Request
     {
         Request s = *this;
         s.count = b - a;
-        s.ids += a;
-        s.puncts += a;
-        s.styles += a;
-        s.n += a;
-        s.num_phonemes += a;
+        if (ids) s.ids += a;
+        if (puncts) s.puncts += a;
+        if (styles) s.styles += a;
+        if (n) s.n += a;
+        if (num_phonemes) s.num_phonemes += a;
+        if (src) s.src += a;
         s.T += a;
         s.out += a;
         if (n_frames) s.n_frames += a;
@@ -236,6 +243,8 @@ static void pack_volume(const Request &r, float *vol)
 static_assert(sizeof(zv_level) == sizeof(zv::LevelRow) && sizeof(zv_level) == 16, "zv_level is the kernels' LevelRow");
 static_assert(sizeof(zv_frame_level) == sizeof(zv::ContourRow) && sizeof(zv_frame_level) == 8, "zv_frame_level is the kernels' ContourRow");
 
+static_assert(zv::SEG_BYTES == sizeof(zv::Seg) && zv::CTL_ROW_BYTES == zv::CTL_STRIDE * 4 && zv::PCTL_ROW_BYTES == zv::PCTL_STRIDE * 4,
+              "stage_range.h sizes the tables and control rows without kernels.h");
 static_assert(sizeof(zv_pitch_frame) == sizeof(zv::PitchFrameRow) && sizeof(zv_pitch_frame) == 8, "zv_pitch_frame is the kernels' PitchFrameRow");
 static_assert(sizeof(zv_pitch_phoneme) == sizeof(zv::PitchPhonemeRow) && sizeof(zv_pitch_phoneme) == 8, "zv_pitch_phoneme is the kernels' PitchPhonemeRow");
 
@@ -425,7 +434,9 @@ static void check_phoneme_controls(const Model &M, const zv_phoneme_controls &p,
 // entry point, the utterance and what is wrong (for per-phoneme controls the field and the phoneme).
 static void check_request(zv_model *m, const Request &r)
 {
-    if (!(m && r.ids && r.puncts && r.styles && r.n && r.T && r.out)) zv::fail(ZV_ERR_ARG, "%s: null argument", r.fn);
+    const bool enc = r.range.has(zv::ST_ENCODER);      // without it a request has no tokens: what it reads is src, frames by T
+    if (!(m && r.T && r.out && (enc ? r.ids && r.puncts && r.n && r.num_phonemes : r.src != nullptr) && (r.styles || r.range.first == zv::ST_VOCODER)))
+        zv::fail(ZV_ERR_ARG, "%s: null argument", r.fn);
     const Model &M = *m->m;
     const bool tg = r.targets();
     // the one limit of the envelope that is the checkpoint's, not an utterance's (kernels.h env_hop_supported)
@@ -435,7 +446,14 @@ static void check_request(zv_model *m, const Request &r)
     {
         try
         {
-            if (!(r.ids[u] && r.puncts[u] && r.styles[u] && r.out[u])) zv::fail(ZV_ERR_ARG, "null argument");
+            if (!enc)
+            {
+                if (!(r.src[u] && r.out[u] && (!r.styles || r.styles[u]))) zv::fail(ZV_ERR_ARG, "null argument");
+                check_T(M, r.T[u]);
+                continue;
+            }
+            // (an encoder-only request may leave an utterance's hidden where it is: the planning call)
+            if (!(r.ids[u] && r.puncts[u] && r.styles[u] && (r.out[u] || r.range.last == zv::ST_ENCODER))) zv::fail(ZV_ERR_ARG, "null argument");
             if (!(r.n[u] > 0 && r.T[u] > 0)) zv::fail(ZV_ERR_ARG, "n and T must be > 0");
             check_T(M, r.T[u]);
             if (r.num_phonemes[u] > r.n[u]) zv::fail(ZV_ERR_ARG, "num_phonemes exceeds n");
@@ -782,13 +800,16 @@ zv_status zv_synthesize_phonemes(zv_model *m, const int32_t *ids, const int32_t 
 // (utterances [a, b) of a launch group; off[], wav[] and T[] are indexed from the group's first utterance)
 static void scatter_out(const char *pin_wav, const size_t *off, float *const *wav, const uint32_t *T, size_t hop, uint32_t a, uint32_t b)
 {
+    // (hop: the floats of a frame of what the batch hands back, the waveform's hop for every batch that ends with the vocoder; an
+    // utterance without a destination, an encoder batch's planning entries, has nothing staged)
     size_t total = 0;
-    for (uint32_t u = a; u < b; u++) total += (size_t)T[u] * hop * 4;
+    for (uint32_t u = a; u < b; u++) total += wav[u] ? (size_t)T[u] * hop * 4 : 0;
     // (a group of the 8-group tail is 5 MB: with the old 8 MB threshold every group went out on one thread, 4 ms per batch between
     // a batch's end and the next batch's start on that lane)
     const unsigned nth = total > ((size_t)1 << 20) ? 4u : 1u;
     auto work = [&](unsigned k) {
-        for (uint32_t u = a + k; u < b; u += nth) memcpy(wav[u], pin_wav + off[u], (size_t)T[u] * hop * 4);
+        for (uint32_t u = a + k; u < b; u += nth)
+            if (wav[u]) memcpy(wav[u], pin_wav + off[u], (size_t)T[u] * hop * 4);
     };
     if (nth == 1)
     {
@@ -809,16 +830,17 @@ static void scatter_out(const char *pin_wav, const size_t *off, float *const *wa
 struct PendingBatch
 {
     bool                  active = false;
+    zv::StageRange        range;       // what is in flight: the chain, or one stage (zv_vocode_batch_begin); its _end must match
     uint32_t              n_utt = 0;
     int                   G = 1;
     std::vector<uint32_t> gb;          // group boundaries (utterance indices), G + 1 entries
     std::vector<size_t>   woff;        // byte offset of each utterance's waveform in the pinned block
     std::vector<uint32_t> T;
-    std::vector<float *>  wav;
+    std::vector<float *>  wav;         // (a batch that ends ahead of the vocoder: its mel or hidden rows; null = that utterance wants none)
     uint32_t             *n_frames = nullptr;
     const char           *h_wav = nullptr;
-    const int32_t        *h_nf = nullptr;
-    size_t                hop = 0;
+    const int32_t        *h_nf = nullptr;      // null for a batch without the encoder: no frame counts, no scan
+    size_t                hop = 0;             // floats of a frame of `wav`
     // phoneme timings (zv_synthesize_batch_begin_phonemes): the regulator's scan lands in h_cum, packed utterance after utterance
     std::vector<uint32_t> N;
     std::vector<int32_t *> dur;
@@ -863,17 +885,22 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     Model &M = *m->m;
     PendingBatch &pb = pending_slot(m, lane);
     if (pb.active) zv::fail(ZV_ERR_ARG, "lane %d already has a batch in flight", lane);
+    if (!r.range.valid() || (r.fitted && !r.range.full())) zv::fail(ZV_ERR_ARG, "internal: bad stage range");
     M.select_lane(lane);
     const size_t E = M.E(), Mm = M.hp.audio_num_mels, hop = M.hp.audio_hop_size;
+    // the stages this request runs (stage_range.h): the chain, or one stage over the batch.  Without the encoder there are no tokens:
+    // the capacities are those of one token per utterance, as a stand-alone decode or vocode of one utterance has them
+    const zv::StageRange sr = r.range;
+    const bool enc = sr.has(zv::ST_ENCODER), voc = sr.has(zv::ST_VOCODER);
     const bool tg = r.targets(), pc = r.phoneme_controls() || tg, ctl = r.prosody || tg, dur = r.timings();
     const zv::WaveAsk ask = r.wave.ask(r.count);
     const void *bands_table = ask.on[zv::WS_BANDS] ? M.bands_table() : nullptr;      // (allocates and copies on first use: ahead of everything enqueued)
-    uint32_t nmax = 0, tmax = 0, ntot = 0;
+    uint32_t nmax = enc ? 0 : 1, tmax = 0, ntot = 0;
     for (uint32_t u = 0; u < r.count; u++)
     {
-        nmax = std::max(nmax, r.n[u]);
+        if (enc) nmax = std::max(nmax, r.n[u]);
         tmax = std::max(tmax, r.T[u]);
-        ntot += r.n[u];
+        if (enc) ntot += r.n[u];
     }
     zv::Batch bt;
     bt.nseg = (int)r.count;
@@ -887,43 +914,42 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     // Batch::tokens_merged; controls: only with prosody or a target, one zv::CTL_STRIDE row per utterance; phoneme controls: only with
     // per-phoneme controls or a target, one zv::PCTL_STRIDE row per token row — uploaded with the rest, so a replayed graph reads the
     // values of this call, also where the previous run's fit_durations_kernel has rewritten the rows' frame column)
-    Layout in;
-    const size_t b_tab = (size_t)(bt.nseg + 1) * sizeof(zv::Seg);
-    const size_t i_tok = in.at(b_tab), i_frm = in.at(b_tab), i_ids = in.at(bt.n_rows * 4), i_pun = in.at(bt.n_rows * 4),
-                 i_sty = in.at((size_t)bt.nseg * E * 4), i_ctl = in.at(ctl ? (size_t)bt.nseg * zv::CTL_STRIDE * 4 : 0),
-                 i_pctl = in.at(pc ? bt.n_rows * zv::PCTL_STRIDE * 4 : 0);
-    const zv::WaveRows cap_rows{(size_t)bt.nseg, bt.n_rows, bt.t_rows};
-    zv::WaveOffsets wo;
-    zv::wave_carve(in, ask, cap_rows, zv::WR_INPUT, wo);      // (like the control rows: a region only where the request turns its stage on)
-    const size_t b_in = in.size();
+    // The three blocks are carved by stage_range.h's batch_carve, the chain's as they always were; a region the range does not touch
+    // takes no bytes (a stage batch has no token table without the encoder, no waveform without the vocoder, ...)
     // device block: [frame counts][input block][hidden][mel][wav][scan] (scan: only when timings are asked for, the length
     // regulator's `cum`, which the decoder and vocoder would otherwise overwrite in the arena) [live frame table][decoder run table]
     // [the waveform stages' device regions]
-    Layout dev;
-    const size_t o_nf = dev.at((size_t)bt.nseg * 4), o_in = dev.at(b_in), o_hid = dev.at(bt.t_rows * E * 4),
-                 o_mel = dev.at(bt.t_rows * Mm * 4), o_wav = dev.at(bt.t_rows * hop * 4), o_cum = dev.at(dur || ask.needs_scan() ? bt.n_rows * 4 : 0),
-                 o_live = dev.at(r.fitted ? (size_t)bt.nseg * sizeof(zv::Seg) : 0),      // fitted: the live frame table, written on the device
-                 o_runs = dev.at(!r.fitted ? (size_t)(bt.nseg + 1) * sizeof(zv::Seg) : 0);     // run-shortened decoding: the decoder's run table, likewise (+ the entry of the packed rows: Batch::d_dec_runs)
-    zv::wave_carve(dev, ask, cap_rows, zv::WR_DEVICE, wo);
-    char *io = (char *)M.io_scratch(dev.size());
     // pinned block: [input block][frame counts][waveforms, utterance after utterance][scan][the waveform stages' staging regions] (a
-    // table only where some utterance asks for it; the rows packed like the waveforms / the tokens)
+    // table only where some utterance asks for it; the rows packed like the waveforms / the tokens) [source rows] (a range that starts
+    // behind the encoder: the caller's hidden or mel rows, utterance after utterance, uploaded ahead of the schedule)
+    // What the batch hands back are the rows of its last stage (hidden, mel, waveform), staged for the utterances that want them.
+    zv::BatchShape q;
+    q.nseg = (size_t)bt.nseg, q.n_rows = bt.n_rows, q.t_rows = bt.t_rows, q.E = E, q.mels = Mm, q.hop = hop;
+    q.ctl = ctl, q.pctl = pc, q.timings = dur, q.fitted = r.fitted, q.n_tokens = ntot;
+    const size_t out_row = zv::stage_row_floats(sr.result(), q) * 4, src_row = enc ? 0 : zv::stage_row_floats(sr.source(), q) * 4;
     size_t wav_bytes = 0;
-    pb.hop = hop;
+    pb.hop = out_row / 4;
     pb.woff.assign(r.count, 0);
     pb.noff.assign(r.count + 1, 0);
+    std::vector<size_t> frm0(r.count + 1, 0);      // an utterance's first frame row in the concatenated tensors
     for (uint32_t u = 0; u < r.count; u++)
     {
         pb.woff[u] = wav_bytes;
-        wav_bytes += (size_t)r.T[u] * hop * 4;
-        pb.noff[u + 1] = pb.noff[u] + r.n[u];
+        if (r.out[u]) wav_bytes += (size_t)r.T[u] * out_row;
+        frm0[u + 1] = frm0[u] + r.T[u];
+        pb.noff[u + 1] = pb.noff[u] + (enc ? r.n[u] : 0);
     }
-    const size_t frame_rows = wav_bytes / (hop * 4);
-    Layout host;
-    const size_t p_in = host.at(b_in), p_nf = host.at((size_t)bt.nseg * 4), p_wav = host.at(wav_bytes),
-                 p_cum = host.at(dur ? bt.n_rows * 4 : 0);
-    zv::wave_carve(host, ask, zv::WaveRows{r.count, ntot, frame_rows}, zv::WR_HOST, wo);
-    char *pin = (char *)M.pinned_scratch(host.size());
+    const size_t frame_rows = frm0[r.count];
+    q.n_frames = frame_rows, q.result_bytes = wav_bytes, q.source_bytes = frame_rows * src_row;
+    const zv::BatchOffsets bo = zv::batch_carve(sr, q, ask);
+    const zv::WaveOffsets &wo = bo.wave;
+    const size_t i_tok = bo.at[zv::BI_TOK], i_frm = bo.at[zv::BI_FRM], i_ids = bo.at[zv::BI_IDS], i_pun = bo.at[zv::BI_PUN],
+                 i_sty = bo.at[zv::BI_STY], i_ctl = bo.at[zv::BI_CTL], i_pctl = bo.at[zv::BI_PCTL], b_in = bo.in_bytes;
+    const size_t o_nf = bo.at[zv::BD_NF], o_in = bo.at[zv::BD_IN], o_hid = bo.at[zv::BD_HID], o_mel = bo.at[zv::BD_MEL],
+                 o_wav = bo.at[zv::BD_WAV], o_cum = bo.at[zv::BD_CUM], o_live = bo.at[zv::BD_LIVE], o_runs = bo.at[zv::BD_RUNS];
+    const size_t p_in = bo.at[zv::BP_IN], p_nf = bo.at[zv::BP_NF], p_wav = bo.at[zv::BP_OUT], p_cum = bo.at[zv::BP_CUM], p_src = bo.at[zv::BP_SRC];
+    char *io = (char *)M.io_scratch(bo.dev_bytes);
+    char *pin = (char *)M.pinned_scratch(bo.pin_bytes);
     char *d_in = io + o_in, *h_in = pin + p_in;
     {
         zv::Seg *h_tok = (zv::Seg *)(h_in + i_tok), *h_frm = (zv::Seg *)(h_in + i_frm);
@@ -932,21 +958,25 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         int32_t n0 = 0, t0 = 0;
         for (uint32_t u = 0; u < r.count; u++)
         {
-            const int32_t n = (int32_t)r.n[u], t = (int32_t)r.T[u];
-            h_tok[u] = zv::Seg{n0, n, n, 0};
+            const int32_t n = enc ? (int32_t)r.n[u] : 0, t = (int32_t)r.T[u];
             h_frm[u] = zv::Seg{t0, t, 0, 0};
-            memcpy(h_ids + n0, r.ids[u], (size_t)n * 4);
-            memcpy(h_pun + n0, r.puncts[u], (size_t)n * 4);
-            memcpy(h_sty + (size_t)u * E, r.styles[u], E * 4);
+            if (enc)
+            {
+                h_tok[u] = zv::Seg{n0, n, n, 0};
+                memcpy(h_ids + n0, r.ids[u], (size_t)n * 4);
+                memcpy(h_pun + n0, r.puncts[u], (size_t)n * 4);
+            }
+            if (r.styles) memcpy(h_sty + (size_t)u * E, r.styles[u], E * 4);
+            if (!enc) memcpy(pin + p_src + frm0[u] * src_row, r.src[u], (size_t)t * src_row);
             n0 += n;
             t0 += t;
         }
-        h_tok[r.count] = zv::Seg{0, n0, n0, 0};
+        if (enc) h_tok[r.count] = zv::Seg{0, n0, n0, 0};
         h_frm[r.count] = zv::Seg{0, t0, 0, 0};
-        pack_controls(r, (float *)(h_in + i_ctl), (float *)(h_in + i_pctl));      // (phoneme rows past the utterances are never read)
+        if (enc) pack_controls(r, (float *)(h_in + i_ctl), (float *)(h_in + i_pctl));      // (phoneme rows past the utterances are never read)
         pack_wave(M, r, ask, h_in, wo);
     }
-    bt.d_tok = (const zv::Seg *)(d_in + i_tok);
+    if (enc) bt.d_tok = (const zv::Seg *)(d_in + i_tok);
     bt.d_frm = (const zv::Seg *)(d_in + i_frm);
     if (ctl) bt.d_ctl = (const float *)(d_in + i_ctl);
     bt.has_targets = tg;
@@ -956,13 +986,26 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     // not yet (without Batch::d_cum the encoder's layout keeps it in the arena), so one reservation asks for the largest of each
     M.reserve_batch(bt);
     // an envelope's knots pass and a table stage's phonemes pass read the scan behind the vocoder
-    if (dur || bt.wave.needs_scan()) bt.d_cum = (int32_t *)(io + o_cum);
+    if (enc && (dur || bt.wave.needs_scan())) bt.d_cum = (int32_t *)(io + o_cum);
     if (r.fitted) bt.d_frm_live = (zv::Seg *)(io + o_live);
-    if (M.dec_plan(bt).runs) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
+    // (a run table is the chain's: a stand-alone decode's hidden comes from the caller, Model::dec_plan)
+    if (enc && sr.has(zv::ST_DECODER) && M.dec_plan(bt).runs) bt.d_dec_runs = (zv::Seg *)(io + o_runs);
     int32_t *d_nf = (int32_t *)(io + o_nf), *d_ids = (int32_t *)(d_in + i_ids), *d_pun = (int32_t *)(d_in + i_pun);
     float *d_sty = (float *)(d_in + i_sty), *d_hid = (float *)(io + o_hid), *d_mel = (float *)(io + o_mel), *d_wav = (float *)(io + o_wav);
-    int32_t *h_nf = (int32_t *)(pin + p_nf), *h_cum = dur ? (int32_t *)(pin + p_cum) : nullptr;
+    int32_t *h_nf = enc ? (int32_t *)(pin + p_nf) : nullptr, *h_cum = dur ? (int32_t *)(pin + p_cum) : nullptr;
     char *h_wav = pin + p_wav;
+    // what the range reads from the caller and what it hands back, in the device block
+    float *d_src = sr.first == zv::ST_DECODER ? d_hid : sr.first == zv::ST_VOCODER ? d_mel : nullptr;
+    const char *d_out = (const char *)(sr.last == zv::ST_VOCODER ? d_wav : sr.last == zv::ST_DECODER ? d_mel : d_hid);
+    // the rows of the utterances that want them, one copy per run of neighbours (the chain: every utterance, one copy)
+    auto out_download = [&](hipStream_t st) {
+        for (uint32_t u = 0, v; u < r.count; u = v)
+        {
+            for (v = u + 1; r.out[u] && v < r.count && r.out[v]; v++) {}
+            if (r.out[u])
+                ZV_HIP(hipMemcpyAsync(h_wav + pb.woff[u], d_out + frm0[u] * out_row, (frm0[v] - frm0[u]) * out_row, hipMemcpyDeviceToHost, st));
+        }
+    };
     wave_tables(r, ask, wo, io, pin, h_in, wo, pb.tables, pb.dst);      // (the struct arrays are read here, the tables are written in batch_finish)
     // the table rows of utterances [u0, u1) travel behind their waveforms on stream `st`; the per-utterance tables (whole) follow the last kernel
     auto tables_download = [&](uint32_t u0, uint32_t u1, hipStream_t st, bool whole) {
@@ -976,7 +1019,7 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
     // Large batches: the last vocoder stage (two thirds of a waveform's bytes are produced there) runs in G groups of
     // utterances; a finished group's waveforms travel to the host on the lane's copy stream while the next group's kernels
     // run.  Same kernels on the same rows: same bits.
-    const int G = zv::voc_tail_groups(bt.nseg, wav_bytes, M.profiling, M.dbg_layer.kind >= 0);
+    const int G = voc ? zv::voc_tail_groups(bt.nseg, wav_bytes, M.profiling, M.dbg_layer.kind >= 0) : 1;
     // from here on work is queued that reads the lane's pinned input block and writes its I/O block: if anything fails the
     // lane's streams are drained before the error leaves, so an idle-looking lane never has work in flight
     try
@@ -991,21 +1034,23 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         // third queued behind them, built to close gaps a kernel trace had shown, changed nothing and was removed again.)
         const uint64_t seq = M.next_batch_seq();
         ZV_HIP(hipEventRecord(M.batch_event(seq, 0), M.stream()));
+        // the caller's hidden or mel, by its real size and ahead of the schedule (whose first node uploads the input block by capacity)
+        if (d_src) ZV_HIP(hipMemcpyAsync(d_src, pin + p_src, q.source_bytes, hipMemcpyHostToDevice, M.stream()));
         if (G <= 1)
         {
-            M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, h_in, d_in, b_in);
+            M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, h_in, d_in, b_in, 0, sr);
             ZV_HIP(hipEventRecord(M.batch_event(seq, 1), M.stream()));
-            ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream()));
+            if (enc) ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream()));
             if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream()));
-            ZV_HIP(hipMemcpyAsync(h_wav, d_wav, wav_bytes, hipMemcpyDeviceToHost, M.stream()));
+            out_download(M.stream());
             tables_download(0, r.count, M.stream(), true);
             tables_download(0, r.count, M.stream(), false);
             ZV_HIP(hipEventRecord(M.tail_event(1), M.stream()));
         }
         else
         {
-            M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, h_in, d_in, b_in, 1);
-            ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream()));
+            M.chain_dev(bt, d_ids, d_pun, d_sty, d_hid, d_mel, d_wav, d_nf, h_in, d_in, b_in, 1, sr);
+            if (enc) ZV_HIP(hipMemcpyAsync(h_nf, d_nf, (size_t)bt.nseg * 4, hipMemcpyDeviceToHost, M.stream()));
             if (dur) ZV_HIP(hipMemcpyAsync(h_cum, bt.d_cum, (size_t)ntot * 4, hipMemcpyDeviceToHost, M.stream()));
             for (int g = 1; g < G; g++)               // contiguous groups of about wav_bytes / G each
             {
@@ -1036,15 +1081,17 @@ static void batch_enqueue(zv_model *m, int lane, const Request &r)
         throw;
     }
     pb.active = true;
+    pb.range = sr;
     pb.n_utt = r.count;
     pb.G = G;
     pb.T.assign(r.T, r.T + r.count);
     pb.wav.assign(r.out, r.out + r.count);
-    pb.n_frames = r.n_frames;
+    pb.n_frames = enc ? r.n_frames : nullptr;
     pb.h_wav = h_wav;
     pb.h_nf = h_nf;
     pb.h_cum = h_cum;
-    pb.N.assign(r.n, r.n + r.count);
+    if (enc) pb.N.assign(r.n, r.n + r.count);
+    else pb.N.assign(r.count, 0);
     if (dur) pb.dur.assign(r.durations, r.durations + r.count);
     else pb.dur.clear();
 }
@@ -1556,6 +1603,96 @@ zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)
     return guarded([&] {
         ZV_NEED(m, "null argument");
         ZV_NEED(lane < ZV_BATCH_LANES, "lane out of range");
+        if (m->pending && m->pending[lane].active && !m->pending[lane].range.full())
+            zv::fail(ZV_ERR_ARG, "zv_synthesize_batch_end: lane %u holds a vocode batch (zv_vocode_batch_begin): finish it with zv_vocode_batch_end", lane);
+        ZV_HIP(hipSetDevice(m->m->device));
+        batch_finish(m, (int)lane);
+    });
+}
+
+// ---- the stages in batches (zv_encode_batch, zv_decode_batch, zv_vocode_batch*): the batch request path with a stage range of one
+// stage.  A call's own checks name the argument as the header does; check_request follows with the ids and the controls.
+struct StageArg { const char *name; const void *array; bool entries; };      // entries: a [n_utt] array of pointers, none of which may be null
+
+static void check_stage_args(const char *fn, const zv_model *m, uint32_t n_utt, std::initializer_list<StageArg> args, const uint32_t *n_phonemes,
+                             const uint32_t *T)
+{
+    if (!m) zv::fail(ZV_ERR_ARG, "%s: m is NULL", fn);
+    for (const StageArg &a : args)
+        if (!a.array) zv::fail(ZV_ERR_ARG, "%s: %s is NULL", fn, a.name);
+    if (!T) zv::fail(ZV_ERR_ARG, "%s: T is NULL", fn);
+    if (!n_utt) zv::fail(ZV_ERR_ARG, "%s: n_utt must be > 0", fn);
+    const uint32_t tmax = m->m->max_frames_per_utterance();
+    for (uint32_t u = 0; u < n_utt; u++)
+    {
+        for (const StageArg &a : args)
+            if (a.entries && !((const void *const *)a.array)[u]) zv::fail(ZV_ERR_ARG, "%s: utterance %u: %s is NULL", fn, u, a.name);
+        if (n_phonemes && !n_phonemes[u]) zv::fail(ZV_ERR_ARG, "%s: utterance %u: n_phonemes must be > 0", fn, u);
+        if (!T[u]) zv::fail(ZV_ERR_ARG, "%s: utterance %u: T must be > 0", fn, u);
+        if (T[u] > tmax) zv::fail(ZV_ERR_ARG, "%s: utterance %u: T = %u exceeds zv_max_frames() = %u frames per utterance", fn, u, T[u], tmax);
+    }
+}
+
+zv_status zv_encode_batch(zv_model *m, uint32_t n_utt, const int32_t *const *ids, const int32_t *const *puncts,
+                          const float *const *styles, const uint32_t *n_phonemes, const uint32_t *T, float *const *hidden,
+                          uint32_t *n_frames, const zv_prosody *prosody, const zv_phoneme_controls *phonemes,
+                          int32_t *const *durations, const uint32_t *target_frames)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    std::vector<float *> none;      // hidden == NULL: the planning call, no utterance's hidden leaves the device
+    zv_status st = guarded([&] {
+        check_stage_args(fn, m, n_utt, {{"ids", ids, true}, {"puncts", puncts, true}, {"styles", styles, true}, {"n_phonemes", n_phonemes, false},
+                                              {"n_frames", n_frames, false}}, n_phonemes, T);
+        if (!hidden) none.assign(n_utt, nullptr);
+    });
+    if (st != ZV_OK) return st;
+    Request r{__func__, n_utt, ids, puncts, styles, n_phonemes, n_phonemes, T, hidden ? hidden : none.data(), n_frames, prosody, phonemes,
+              durations, false, target_frames};
+    r.range = zv::StageRange{zv::ST_ENCODER, zv::ST_ENCODER};
+    return synthesize_batch(m, r);
+}
+
+zv_status zv_decode_batch(zv_model *m, uint32_t n_utt, const float *const *hidden, const float *const *styles, const uint32_t *T,
+                          float *const *mel)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    zv_status st = guarded([&] { check_stage_args(fn, m, n_utt, {{"hidden", hidden, true}, {"styles", styles, true}, {"mel", mel, true}}, nullptr, T); });
+    if (st != ZV_OK) return st;
+    Request r{__func__, n_utt, nullptr, nullptr, styles, nullptr, nullptr, T, mel};
+    r.range = zv::StageRange{zv::ST_DECODER, zv::ST_DECODER};
+    r.src = hidden;
+    return synthesize_batch(m, r);
+}
+
+static Request vocode_request(const char *fn, uint32_t n_utt, const float *const *mel, const uint32_t *T, float *const *wav)
+{
+    Request r{fn, n_utt, nullptr, nullptr, nullptr, nullptr, nullptr, T, wav};
+    r.range = zv::StageRange{zv::ST_VOCODER, zv::ST_VOCODER};
+    r.src = mel;
+    return r;
+}
+
+zv_status zv_vocode_batch(zv_model *m, uint32_t n_utt, const float *const *mel, const uint32_t *T, float *const *wav)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    zv_status st = guarded([&] { check_stage_args(fn, m, n_utt, {{"mel", mel, true}, {"wav", wav, true}}, nullptr, T); });
+    return st != ZV_OK ? st : synthesize_batch(m, vocode_request(__func__, n_utt, mel, T, wav));
+}
+
+zv_status zv_vocode_batch_begin(zv_model *m, uint32_t lane, uint32_t n_utt, const float *const *mel, const uint32_t *T, float *const *wav)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    zv_status st = guarded([&] { check_stage_args(fn, m, n_utt, {{"mel", mel, true}, {"wav", wav, true}}, nullptr, T); });
+    return st != ZV_OK ? st : begin_batch(m, lane, vocode_request(__func__, n_utt, mel, T, wav));
+}
+
+zv_status zv_vocode_batch_end(zv_model *m, uint32_t lane)
+{
+    return guarded([&] {
+        ZV_NEED(m, "null argument");
+        ZV_NEED(lane < ZV_BATCH_LANES, "lane out of range");
+        if (m->pending && m->pending[lane].active && !m->pending[lane].range.only(zv::ST_VOCODER))
+            zv::fail(ZV_ERR_ARG, "zv_vocode_batch_end: lane %u holds a synthesize batch (zv_synthesize_batch_begin): finish it with zv_synthesize_batch_end", lane);
         ZV_HIP(hipSetDevice(m->m->device));
         batch_finish(m, (int)lane);
     });

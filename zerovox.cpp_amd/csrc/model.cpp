@@ -407,19 +407,22 @@ template <typename F> void Model::run_captured(int kind, const Batch &b, const v
 }
 
 void Model::chain_dev(const Batch &b, const int32_t *d_ids, const int32_t *d_puncts, const float *d_styles, float *d_hidden,
-                      float *d_mel, float *d_wav, int32_t *d_nframes, const void *h2d_src, void *h2d_dst, size_t h2d_bytes, int voc_part)
+                      float *d_mel, float *d_wav, int32_t *d_nframes, const void *h2d_src, void *h2d_dst, size_t h2d_bytes, int voc_part,
+                      StageRange range)
 {
     auto run = [&]() {
         if (h2d_bytes) ZV_HIP(hipMemcpyAsync(h2d_dst, h2d_src, h2d_bytes, hipMemcpyHostToDevice, stream()));
-        encode_dev(b, d_ids, d_puncts, d_styles, d_hidden, d_nframes);
-        decode_dev(b, d_hidden, d_styles, d_mel);        // the reference vocodes all T frames (src/zerovox.cpp:326-334)
+        if (range.has(ST_ENCODER)) encode_dev(b, d_ids, d_puncts, d_styles, d_hidden, d_nframes);
+        if (range.has(ST_DECODER)) decode_dev(b, d_hidden, d_styles, d_mel);        // the reference vocodes all T frames (src/zerovox.cpp:326-334)
+        if (!range.has(ST_VOCODER)) return;
         if (voc_part == 1) vocode_group(b, d_mel, d_wav, 1);      // the caller runs the last stage in utterance groups
         else vocode_dev(b, d_mel, d_wav);
     };
     if (!graph_mode || profiling) return run();
     // the buffers that are not part of the Batch (what of the Batch keys a graph: Batch::same_schedule)
     const void *key[CapturedGraph::NKEY] = {d_ids, d_puncts, d_styles, d_hidden, d_mel, d_wav, d_nframes, h2d_src};
-    run_captured(voc_part == 1 ? 2 : 1, b, key, run);
+    // the stage range is part of the kind: the chain keeps 1 and 2, a stage batch's graphs are 4 * range.key() above them
+    run_captured((voc_part == 1 ? 2 : 1) + 4 * range.key(), b, key, run);
 }
 
 void Model::vocode_dev_graph(const Batch &b, const float *d_mel, float *d_wav)

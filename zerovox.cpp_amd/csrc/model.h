@@ -14,6 +14,7 @@
 #include "gguf_reader.h"
 #include "graph_cache.h"
 #include "kernels.h"
+#include "stage_range.h"
 #include "wave_stages.h"
 
 namespace zv
@@ -132,7 +133,7 @@ struct Batch
 struct CapturedGraph
 {
     static constexpr int NKEY = 8;         // the buffers of a call that are not part of its Batch (chain_dev)
-    int            kind = 0;               // 0 vocoder, 1 chain
+    int            kind = 0;               // 0 vocoder, 1 chain, 2 chain up to the vocoder's tail; + 4 * StageRange::key() for a stage batch
     int            lane = 0;               // the lane that captured it
     unsigned       epoch = 0;              // knob_epoch() at capture
     Batch          b;
@@ -259,9 +260,11 @@ class Model
     void vocode_dev_graph(const Batch &b, const float *d_mel, float *d_wav);
     // encoder -> decoder -> vocoder back to back (graph replay keyed by (capacities, buffers) when graph_mode is on).
     // h2d_src / h2d_dst / h2d_bytes (optional): an input upload that becomes the first node of the schedule
+    // range (stage_range.h): the stages that are enqueued, the full chain by default; a shorter range reads d_hidden / d_mel as the
+    // caller filled them, ignores the pointers of the stages it leaves out, and keys its graphs apart from the chain's
     void chain_dev(const Batch &b, const int32_t *d_ids, const int32_t *d_puncts, const float *d_styles, float *d_hidden,
                    float *d_mel, float *d_wav, int32_t *d_nframes, const void *h2d_src = nullptr, void *h2d_dst = nullptr,
-                   size_t h2d_bytes = 0, int voc_part = 0);
+                   size_t h2d_bytes = 0, int voc_part = 0, StageRange range = StageRange());
 
     // profiling (HIP events around every launch while enabled)
     bool profiling = false;

@@ -92,6 +92,9 @@ class HiFiGAN
             int num_resblock_dilations, const int64_t *resblock_dilations);
 
     void eval(const float *mel, float *wav);
+    // (not in the reference) n utterances in one call, mels[u] [T[u]][in_channels] -> wavs[u] [T[u] * hop_size]: zv_vocode_batch, every
+    // waveform the bits of a single vocode of that mel
+    void eval_batch(uint32_t n, const float *const *mels, const uint32_t *T, float *const *wavs);
 
   private:
     zv_model *model;

@@ -94,6 +94,11 @@ void HiFiGAN::eval(const float *mel, float *wav)
     chk(zv_vocode(model, mel, max_seq_len, wav));
 }
 
+void HiFiGAN::eval_batch(uint32_t n, const float *const *mels, const uint32_t *T, float *const *wavs)
+{
+    chk(zv_vocode_batch(model, n, mels, T, wavs));
+}
+
 // ---------------------------------------------------------------------------------------------------
 
 ZeroVOXModel::ZeroVOXModel(const std::string &fname)

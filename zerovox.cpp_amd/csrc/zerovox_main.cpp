@@ -9,7 +9,7 @@
 //     line 2: punctuation ids        (N integers)
 //     line 3: style embedding        (emb_dim + punct_emb_dim floats; a single 0 means the zero vector)
 //
-// usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info] [prosody flags] [target flags]
+// usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info] [--plan] [prosody flags] [target flags]
 //   --duration-scale S, --pitch-scale S, --pitch-shift D, --energy-scale S, --energy-shift D
 //            prosody controls (include/zerovox_amd.h zv_prosody): durations * S (0 < S <= 16), pitch / energy predictions
 //            p * S + D before bucketing; defaults 1, 1, 0, 1, 0 (the uncontrolled result).  A bad value is a usage error.
@@ -67,6 +67,8 @@
 //            --filter-taps FILE reads the taps themselves, one per line, and excludes the other three.  A malformed value, a gain
 //            count that does not match the bands, or edges / a tap count without gains are usage errors; the library checks the taps.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
+//   --plan   print the frame count of every utterance of the -u file (which may then hold several, three lines each) without decoding
+//            or vocoding, one line each: index n_phonemes n_frames seconds; the prosody flags apply to every utterance, then exit
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -85,7 +87,7 @@ static const char *k_default_out = "foo.wav";                   // reference src
 
 static void usage(FILE *f)
 {
-    fprintf(f, "usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info]\n"
+    fprintf(f, "usage: zerovox [-m model.gguf] [-u utterance.txt] [-o out.wav] [--trim] [--fit] [--info] [--plan]\n"
                "               [--duration-scale S] [--pitch-scale S] [--pitch-shift D] [--energy-scale S] [--energy-shift D]\n"
                "               [--phoneme-controls FILE] [--alignment FILE] [--target-frames F | --target-seconds S]\n"
                "               [--gain-db G] [--loudness-dbfs L] [--peak-dbfs P]\n"
@@ -105,6 +107,7 @@ static void usage(FILE *f)
                "                       frames -1 keeps the prediction, 0..32768 forces it; 0 < scale <= 16)\n"
                "  --alignment FILE     write the phoneme timings as TSV: index phoneme_id start_frame frames start_sample samples\n"
                "  --trim               write only the frames the length regulator produced (cut from the max_seq_len-frame run)\n"
+               "  --plan               print index n_phonemes n_frames seconds per utterance of the -u file (three lines each), then exit\n"
                "  --fit                synthesize only those frames (the utterance at its own length) and write them\n"
                "  --target-frames F    fit the durations to exactly F frames (1 <= F <= the checkpoint's max_seq_len)\n"
                "  --target-seconds S   the same for floor(S * sampling rate / hop size + 0.5) frames (S > 0)\n"
@@ -250,6 +253,63 @@ static std::vector<int32_t> utterance_ids(const std::string &utt_path)
     return parse_line<int32_t>(l1);
 }
 
+// --plan: the frame counts of the utterances in the -u file (three lines each, one utterance after the other; without -u the built-in
+// one), from one zv_encode_batch call without hidden: nothing is decoded or vocoded.  One line per utterance on stdout:
+// index n_phonemes n_frames seconds.  prosody: the flags' controls for every utterance, or null
+static int plan(const std::string &model_path, const std::string &utt_path, const zv_prosody *prosody)
+{
+    zv_model *m = nullptr;
+    if (zv_model_load(model_path.c_str(), 0, &m) != ZV_OK) throw std::runtime_error(zv_last_error());
+    struct Free { zv_model *m; ~Free() { zv_model_free(m); } } free_model{m};
+    zv_hparams hp;
+    if (zv_model_get_hparams(m, &hp) != ZV_OK) throw std::runtime_error(zv_last_error());
+    const size_t E = hp.emb_dim + hp.punct_emb_dim;
+    std::vector<std::vector<int32_t>> ids, puncts;
+    std::vector<std::vector<float>> styles;
+    if (utt_path.empty())
+    {
+        const int32_t *i0, *p0;
+        const float *s0;
+        uint32_t n = 0, ns = 0;
+        zv_demo_utterance(&i0, &p0, &s0, &n, &ns);
+        ids.emplace_back(i0, i0 + n), puncts.emplace_back(p0, p0 + n), styles.emplace_back(s0, s0 + ns);
+    }
+    else
+    {
+        std::ifstream f(utt_path);
+        if (!f) throw std::runtime_error("cannot open utterance file '" + utt_path + "'");
+        std::vector<std::string> lines;
+        for (std::string line; std::getline(f, line);)
+            if (line.find_first_not_of(" \t\r") != std::string::npos) lines.push_back(line);
+        if (lines.empty() || lines.size() % 3) throw std::runtime_error("utterance file needs three lines (ids, punctuation ids, style) per utterance");
+        for (size_t k = 0; k < lines.size(); k += 3)
+        {
+            ids.push_back(parse_line<int32_t>(lines[k])), puncts.push_back(parse_line<int32_t>(lines[k + 1]));
+            styles.push_back(parse_line<float>(lines[k + 2]));
+            if (styles.back().size() == 1 && styles.back()[0] == 0.0f) styles.back().assign(E, 0.0f);
+        }
+    }
+    const uint32_t n_utt = (uint32_t)ids.size();
+    std::vector<const int32_t *> pi(n_utt), pp(n_utt);
+    std::vector<const float *> ps(n_utt);
+    std::vector<uint32_t> n(n_utt), T(n_utt, hp.max_seq_len), nf(n_utt, 0);
+    std::vector<zv_prosody> pro(n_utt, prosody ? *prosody : zv_prosody{1.0f, 1.0f, 0.0f, 1.0f, 0.0f});
+    for (uint32_t u = 0; u < n_utt; u++)
+    {
+        if (ids[u].empty() || ids[u].size() != puncts[u].size())
+            throw std::runtime_error("utterance " + std::to_string(u) + ": need as many punctuation ids as phoneme ids (> 0)");
+        if (styles[u].size() != E)
+            throw std::runtime_error("utterance " + std::to_string(u) + ": style vector has " + std::to_string(styles[u].size()) + " values, model needs " + std::to_string(E));
+        pi[u] = ids[u].data(), pp[u] = puncts[u].data(), ps[u] = styles[u].data(), n[u] = (uint32_t)ids[u].size();
+    }
+    if (zv_encode_batch(m, n_utt, pi.data(), pp.data(), ps.data(), n.data(), T.data(), nullptr, nf.data(), prosody ? pro.data() : nullptr, nullptr,
+                        nullptr, nullptr) != ZV_OK)
+        throw std::runtime_error(zv_last_error());
+    for (uint32_t u = 0; u < n_utt; u++)
+        printf("%u %u %u %.3f\n", u, n[u], nf[u], (double)nf[u] * hp.audio_hop_size / hp.audio_sampling_rate);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path, gain_path, contour_path, plevel_path, pitch_path, ppitch_path;
@@ -261,7 +321,7 @@ int main(int argc, char **argv)
     std::string taps_path;             // --filter-taps
     double pitch_hz[2] = {0.0, 0.0}, pitch_thr = 0.0;      // --pitch-min-hz, --pitch-max-hz, --pitch-threshold (0: the default)
     bool pitch_param = false;
-    bool trim = false, fit = false, info = false, controlled = false, leveled = false, enveloped = false;
+    bool trim = false, fit = false, info = false, planning = false, controlled = false, leveled = false, enveloped = false;
     long ramp_frames = 0;              // --ramp-frames
     double fade_ms[2] = {0.0, 0.0};    // --fade-in-ms, --fade-out-ms
     zv_volume volume = {1.0f, 0.0f, 0.0f};
@@ -439,6 +499,7 @@ int main(int argc, char **argv)
         else if (a == "--trim") trim = true;
         else if (a == "--fit") fit = true;
         else if (a == "--info") info = true;
+        else if (a == "--plan") planning = true;
         else if (a == "--duration-scale" || a == "--pitch-scale" || a == "--pitch-shift" || a == "--energy-scale" || a == "--energy-shift")
         {
             const float x = parse_flag_float(a.c_str(), need(a.c_str()));
@@ -536,6 +597,8 @@ int main(int argc, char **argv)
             }
             return 0;
         }
+
+        if (planning) return plan(model_path, utt_path, controlled ? &prosody : nullptr);
 
         // per-phoneme controls and timings: the file is checked against the utterance before the model is loaded
         std::vector<int32_t> ids0;
