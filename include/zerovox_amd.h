@@ -23,7 +23,9 @@
  *   zv_band_levels     the band levels of any waveform the caller brings
  *   *_filter           the same with a linear-phase FIR filter per utterance applied to the waveform on the device (zv_filter)
  *   zv_filter_wave     the filter on any waveform the caller brings; zv_filter_design: band gains to taps, on the host
- *   zv_write_wav       <- ZeroVOXModel::write_wav_file        src/zerovox.cpp:337-391 (PCM16 mono RIFF)
+ *   zv_mel_wave        the log-mel rows of any waveform the caller brings (the vocoder's input domain); zv_mel_wave_batch: a batch of
+ *                      them in one launch per kernel; zv_mel_design: Slaney mel weights, on the host
+ *   zv_write_wav       <- ZeroVOXModel::write_wav_file       src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
  * Differences that are deliberate: the number of phonemes N and the number of frames
@@ -756,6 +758,59 @@ zv_status zv_synthesize_batch_begin_filter(zv_model *m, uint32_t lane, uint32_t 
                                            const zv_bands *bands, const zv_filter *filter);
 zv_status zv_filter_wave(zv_model *m, const float *wav, uint32_t T, const zv_filter *filter, float *out);
 zv_status zv_filter_design(uint32_t n_bands, const uint32_t *edges, const float *gains, uint32_t n_taps, float *taps);
+/* ---- mel analysis: a waveform's log-mel rows ---------------------------------------------------------------------------------------------
+ * The way back into the vocoder's input domain: zv_vocode* reads raw log-mel rows (hifigan.mean / hifigan.scale are applied inside the
+ * vocoder) and zv_mel_wave turns samples into such rows — for analysis-resynthesis of a converted checkpoint (wav -> mel -> zv_vocode ->
+ * wav), for the mel of a served waveform against the mel that went in, and for mels of recorded audio.  The transform is the band
+ * levels' 1 024-point DFT at twice the digits on both operands, exact on the i8 matrix cores.
+ * The rule, per utterance, with hop = audio_hop_size, M = audio_num_mels, S = T*hop samples x[0 .. S), N = 1024, 513 bins.  Every row
+ * can be restated bit for bit (csrc/mel.h holds the rule as plain C++, host reference included); nothing depends on how work is split
+ * over lanes, waves, instructions or workgroups.
+ *   span       frame f (0 <= f < T) covers the samples f*hop + centre - 512 + t, t = 0 .. 1023; centre is 0 .. hop-1 (0: librosa's
+ *              center=True; hop/2: the band levels' spans).  Outside [0, S): pad = 0 reads +0.0; pad = 1 reflects without repeating the
+ *              edge (-j -> j, S-1+j -> S-1-j) and needs S >= 513.  A non-finite sample counts as +0.0.  A span never reads another
+ *              utterance's samples.
+ *   quantise   the band levels' block quantiser: the span's peak exponent gives k, a = sign(y) * min((int64)(|y| * 2^k + 0.5), 8191); a
+ *              span whose peak is below 2^-24 is silent.  Two signed base-128 digits: hi = (a + 64) >> 7, lo = a - 128*hi.
+ *   table      C[k][t] = floor(8188 * w[t] * cos(2*pi*k*t/1024) + 0.5), S[k][t] likewise with sin, w the periodic Hann window of 1 024;
+ *              the entries are split into the same two digits.  (At 8 188 no product is within 1.4e-5 of a tie.)
+ *   sums       three i32 sums per (frame, bin, cos / sin): a2 = sum hi*Chi, a1 = sum (hi*Clo + lo*Chi), a0 = sum lo*Clo, each below 2^23;
+ *              Re = 16384*a2 + 128*a1 + a0 as int64 (below 2^37), Im likewise.
+ *   magnitude  each step one IEEE f64 operation: r = (double)Re; i = (double)Im; p = r*r; q = i*i; p = p + q; g = sqrt(p);
+ *              g = g * 2^-k; g = g / 8188.0.
+ *   mel        channel c: acc = +0.0, then for k = 0 .. 512 ascending acc = acc + (double)W[c][k] * g[k] — one multiply and one add,
+ *              each rounded.  W is the caller's weights[M*513] (finite f32) or the design below.
+ *   level      v = max(acc, (double)floor), floor 0 meaning 1e-10f; out = (float)L(v) for log = 0 (log10) or 1 (ln), (float)v for
+ *              log = 2.  L is not libm's logarithm but a fixed sequence of f64 steps (csrc/mel.h mel_ln: frexp, m folded into
+ *              [sqrt(1/2), sqrt(2)), s = (m-1)/(m+1), Horner over 1/13 .. 1/3, 1 in s*s, ln v = e*LN2 + 2*s*poly, log10 = ln * LOG10E,
+ *              the constants given as bit patterns), within 1e-11 of the logarithm.  A silent frame gives L(floor) in every channel.
+ * zv_mel_wave takes a host waveform wav[T * hop] at the model's rate and hop, eagerly, on lane 0, into out[T * num_mels];
+ * zv_mel_wave_batch takes n_utt of them in ONE launch per kernel, and utterance u receives the bits of its single call.  One zv_mel
+ * serves the batch.  0 < T[u] <= zv_max_frames(); the hop must be a multiple of 4, as for the band levels.  ZV_ERR_ARG before any
+ * work is enqueued, the message naming the entry point, the utterance and the field: centre >= hop, pad above 1 or pad = 1 with an
+ * utterance below 513 samples, log above 2, a floor that is negative or not finite, a weight that is not finite, or what
+ * zv_mel_design refuses.  The table (two digit planes, 2.2 MB) is built on the host at the first request; the weights travel with
+ * the call.  Never part of a captured graph or of the zv_synthesize* chain.
+ * zv_mel_design is host only and needs no model and no device: Slaney-scale triangular filters with Slaney area normalisation
+ * (librosa's defaults) on the bin centres f_k = k * sampling_rate / 1024, in f64, each weight rounded to f32 once:
+ *   mel(f) = 3f/200 below 1 000 Hz, else 15 + 27 * ln(f/1000) / ln(6.4), and hz() its inverse;
+ *   p[i] = hz(mel(fmin) + i * (mel(fmax) - mel(fmin)) / (num_mels + 1)), i = 0 .. num_mels + 1;
+ *   W[c][k] = max(0, min((f_k - p[c]) / (p[c+1] - p[c]), (p[c+2] - f_k) / (p[c+2] - p[c+1]))) * 2 / (p[c+2] - p[c]).
+ * fmax_hz = 0 means Nyquist.  ZV_ERR_ARG for a value that is not finite or negative, fmin_hz >= fmax_hz, fmax_hz above Nyquist, or
+ * num_mels 0 or above 256.
+ * Out of scope: other DFT sizes or window lengths; mel analysis inside the zv_synthesize* chain or a captured graph; a distance between
+ * mels (the caller subtracts); resampling. */
+typedef struct
+{
+    const float *weights;   /* [num_mels*513] or NULL = zv_mel_design(rate, num_mels, fmin_hz, fmax_hz) */
+    float        fmin_hz, fmax_hz;
+    uint32_t     centre, pad, log;
+    float        floor;
+} zv_mel;                   /* zero-initialised = Slaney 0 .. Nyquist, centre 0, zero padding, log10, floor 1e-10 */
+zv_status zv_mel_wave(zv_model *m, const float *wav, uint32_t T, const zv_mel *mel, float *out /* [T*num_mels] */);
+zv_status zv_mel_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint32_t *T, const zv_mel *mel /* one for the batch */,
+                            float *const *out);
+zv_status zv_mel_design(uint32_t sampling_rate, uint32_t num_mels, float fmin_hz, float fmax_hz, float *weights);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

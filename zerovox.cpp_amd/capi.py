@@ -33,6 +33,7 @@ SYMBOLS = [
     "zv_synthesize_filter", "zv_synthesize_batch_filter", "zv_synthesize_batch_begin_filter", "zv_filter_wave", "zv_filter_design",
     "zv_set_graph_cache", "zv_graph_cache_stats",
     "zv_encode_batch", "zv_decode_batch", "zv_vocode_batch", "zv_vocode_batch_begin", "zv_vocode_batch_end",
+    "zv_mel_wave", "zv_mel_wave_batch", "zv_mel_design",
 ]
 
 
@@ -393,6 +394,73 @@ def filter_design(gains, edges=None, n_taps: int = 255, lib=None) -> np.ndarray:
     return taps[:int(n_taps)]
 
 
+class MelC(C.Structure):
+    """zv_mel of include/zerovox_amd.h: the weights' pointer, float [num_mels * 513] or NULL = the design, and the scalars (a zeroed
+    struct is Slaney 0 .. Nyquist, centre 0, zero padding, log10, floor 1e-10)"""
+    _fields_ = [("weights", C.c_void_p), ("fmin_hz", C.c_float), ("fmax_hz", C.c_float), ("centre", C.c_uint32), ("pad", C.c_uint32),
+                ("log", C.c_uint32), ("floor", C.c_float)]
+
+
+class MelAnalysis:
+    """The parameters of mel analysis (include/zerovox_amd.h "mel analysis"): .weights float32 [num_mels, 513] or None (the design
+    from fmin_hz .. fmax_hz, 0 = Nyquist), centre (the sample of a hop a frame is centred on: 0 is librosa's center=True, hop // 2
+    the band levels' spans), pad ("zero" or "reflect", or 0 / 1), log ("log10", "ln" or "linear", or 0 / 1 / 2), floor (0 = 1e-10).
+    The library checks the values.  .struct is the zv_mel, which points into the weights (kept alive here)."""
+    PADS = {"zero": 0, "reflect": 1}
+    LOGS = {"log10": 0, "ln": 1, "linear": 2}
+    BINS = 513
+
+    def __init__(self, weights=None, fmin_hz: float = 0.0, fmax_hz: float = 0.0, centre: int = 0, pad=0, log=0, floor: float = 0.0):
+        self.weights = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.ndim != 2 or w.shape[1] != self.BINS:
+                raise ValueError(f"MelAnalysis weights must be [num_mels, {self.BINS}], got shape {w.shape}")
+            self.weights = w
+        if isinstance(pad, str) and pad not in self.PADS:
+            raise ValueError(f"MelAnalysis pad = {pad!r}: expected 'zero' or 'reflect'")
+        if isinstance(log, str) and log not in self.LOGS:
+            raise ValueError(f"MelAnalysis log = {log!r}: expected 'log10', 'ln' or 'linear'")
+        self.fmin_hz, self.fmax_hz, self.floor = float(fmin_hz), float(fmax_hz), float(floor)
+        self.centre = int(centre)
+        self.pad = self.PADS[pad] if isinstance(pad, str) else int(pad)
+        self.log = self.LOGS[log] if isinstance(log, str) else int(log)
+
+    @property
+    def struct(self) -> MelC:
+        return MelC(None if self.weights is None else self.weights.ctypes.data, self.fmin_hz, self.fmax_hz, self.centre, self.pad,
+                    self.log, self.floor)
+
+    def __repr__(self):
+        return (f"MelAnalysis(weights={None if self.weights is None else self.weights.shape}, fmin_hz={self.fmin_hz}, fmax_hz={self.fmax_hz}, "
+                f"centre={self.centre}, pad={self.pad}, log={self.log}, floor={self.floor})")
+
+
+def _mel_params(who: str, params, num_mels: int) -> MelAnalysis:
+    """params= of the mel calls -> a MelAnalysis, checked before anything reaches the library"""
+    if params is None:
+        return MelAnalysis()
+    if not isinstance(params, MelAnalysis):
+        raise TypeError(f"{who}: params must be a MelAnalysis or None, not {type(params).__name__}")
+    if params.weights is not None and params.weights.shape[0] != num_mels:
+        raise ValueError(f"{who}: the weights have {params.weights.shape[0]} rows, the model has {num_mels} mel channels")
+    return params
+
+
+def mel_design(sampling_rate: int, num_mels: int, fmin_hz: float = 0.0, fmax_hz: float = 0.0, lib=None) -> np.ndarray:
+    """zv_mel_design: Slaney mel weights float32 [num_mels, 513] on the bins of the 1 024-point DFT; fmax_hz 0 = Nyquist.  Host only:
+    no model, no device."""
+    lib = lib or load_library()
+    for name, v in (("sampling_rate", sampling_rate), ("num_mels", num_mels)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 0xffffffff:
+            raise ValueError(f"mel_design: {name} = {v!r} must be an integer in [0, 4294967295]")
+    w = np.zeros((min(max(int(num_mels), 1), 256), MelAnalysis.BINS), np.float32)
+    st = lib.zv_mel_design(int(sampling_rate), int(num_mels), float(fmin_hz), float(fmax_hz), _ptr(w))
+    if st != 0:
+        raise ZvError(st, lib.zv_last_error().decode("utf-8", "replace"))
+    return w
+
+
 class EnvelopeC(C.Structure):
     """zv_envelope of include/zerovox_amd.h: the gains' pointer ([n] or NULL) and three integers (a zeroed struct is the identity)"""
     _fields_ = [("phoneme_gain", C.c_void_p), ("ramp_frames", C.c_uint32), ("fade_in_samples", C.c_uint32),
@@ -652,7 +720,10 @@ def _bind(lib):
                            ("zv_decode_batch", [vp, u32, pvp, pvp, pu32, pvp]),
                            ("zv_vocode_batch", [vp, u32, pvp, pu32, pvp]),
                            ("zv_vocode_batch_begin", [vp, u32, u32, pvp, pu32, pvp]),
-                           ("zv_vocode_batch_end", [vp, u32])):
+                           ("zv_vocode_batch_end", [vp, u32]),
+                           ("zv_mel_wave", [vp, fp, u32, C.POINTER(MelC), fp]),
+                           ("zv_mel_wave_batch", [vp, u32, pvp, pu32, C.POINTER(MelC), pvp]),
+                           ("zv_mel_design", [u32, u32, C.c_float, C.c_float, fp])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
@@ -1025,6 +1096,37 @@ class Model:
         st = bands.struct
         self._chk(self.lib.zv_band_levels(self.h, _ptr(w), T, C.byref(st)))
         return bands
+
+    def mel_wave(self, wav, params=None) -> np.ndarray:
+        """zv_mel_wave: the log-mel rows [T][num_mels] of the waveform (the vocoder's input domain); params: a MelAnalysis or None
+        (Slaney weights 0 .. Nyquist, centre 0, zero padding, log10, floor 1e-10)"""
+        fn = _stage_symbol(self.lib, "zv_mel_wave")
+        p = _mel_params("mel_wave", params, self.hp.audio_num_mels)
+        w, T = _waveform(self.hp.audio_hop_size, "mel_wave", wav)
+        out = np.empty((T, self.hp.audio_num_mels), np.float32)
+        st = p.struct
+        self._chk(fn(self.h, _ptr(w), T, C.byref(st), _ptr(out)))
+        return out
+
+    def mel_wave_batch(self, wavs, params=None) -> list:
+        """zv_mel_wave_batch: waveforms [T_u * hop], one per utterance, through ONE launch per kernel -> the list of rows
+        [T_u][num_mels], each with the bits of its mel_wave; params serves the whole batch"""
+        fn = _stage_symbol(self.lib, "zv_mel_wave_batch")
+        p = _mel_params("mel_wave_batch", params, self.hp.audio_num_mels)
+        ws = [_waveform(self.hp.audio_hop_size, f"mel_wave_batch: utterance {u}", w) for u, w in enumerate(wavs)]
+        n = len(ws)
+        outs = [np.empty((T, self.hp.audio_num_mels), np.float32) for _, T in ws]
+        P = C.c_void_p * n
+        st = p.struct
+        self._chk(fn(self.h, n, P(*[w.ctypes.data for w, _ in ws]), (C.c_uint32 * n)(*[T for _, T in ws]), C.byref(st),
+                     P(*[o.ctypes.data for o in outs])))
+        return outs
+
+    def resynthesize(self, wav, params=None) -> np.ndarray:
+        """analysis-resynthesis: vocode(mel_wave(wav)), the acceptance check of a converted vocoder checkpoint.  params must keep the
+        vocoder's domain (the natural logarithm is what the reference's checkpoints were trained on: pass MelAnalysis(log="ln", ...)
+        with the training front end's fmin / fmax / floor where they differ from the defaults)"""
+        return self.vocode(self.mel_wave(wav, params))
 
     def pitch_track(self, wav, params=None) -> Pitch:
         """zv_pitch_track: the pitch track of the waveform, frames only; params: a PitchTrack or None (the defaults)"""

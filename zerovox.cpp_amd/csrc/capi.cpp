@@ -1598,6 +1598,118 @@ zv_status zv_band_levels(zv_model *m, const float *wav, uint32_t T, const zv_ban
     });
 }
 
+// ---- mel analysis (zv_mel_wave, zv_mel_wave_batch, zv_mel_design; the rule: mel.h): host waveforms in, their log-mel rows out,
+// eagerly, on lane 0.  I/O block: [waveforms][rows][slab][parameter block][segment table], every utterance at its absolute frame row;
+// one launch per kernel whatever the batch (stage_plan.h mel_plan).
+struct StageArg { const char *name; const void *array; bool entries; };      // entries: a [n_utt] array of pointers, none of which may be null
+static void check_stage_args(const char *fn, const zv_model *m, uint32_t n_utt, std::initializer_list<StageArg> args, const uint32_t *n_phonemes,
+                             const uint32_t *T);      // (with the stage batches, below)
+
+[[maybe_unused]] static void mel_fail(const char *fn, const char *field, const zv_mel &q, uint32_t hop, uint32_t num_mels, uint32_t rate)
+{
+    if (!strcmp(field, "centre")) zv::fail(ZV_ERR_ARG, "%s: mel centre = %u must be below the hop, %u", fn, q.centre, hop);
+    if (!strcmp(field, "pad")) zv::fail(ZV_ERR_ARG, "%s: mel pad = %u must be 0 (zeros) or 1 (reflect)", fn, q.pad);
+    if (!strcmp(field, "pad (T)")) zv::fail(ZV_ERR_ARG, "%s: mel pad = 1 (reflect) needs at least %d samples in every utterance", fn, zv::BANDS_BINS);      // (mel_run names the utterance first)
+    if (!strcmp(field, "log")) zv::fail(ZV_ERR_ARG, "%s: mel log = %u must be 0 (log10), 1 (ln) or 2 (linear)", fn, q.log);
+    if (!strcmp(field, "floor")) zv::fail(ZV_ERR_ARG, "%s: mel floor must be finite and >= 0", fn);
+    if (!strcmp(field, "weights")) zv::fail(ZV_ERR_ARG, "%s: mel weights holds a value that is not finite", fn);
+    if (!strcmp(field, "num_mels")) zv::fail(ZV_ERR_ARG, "%s: num_mels = %u must be in 1 .. %u", fn, num_mels, zv::MEL_MAX_MELS);
+    if (!strcmp(field, "sampling_rate")) zv::fail(ZV_ERR_ARG, "%s: sampling_rate must be > 0", fn);
+    if (!strcmp(field, "fmin_hz"))
+        zv::fail(ZV_ERR_ARG, "%s: mel fmin_hz = %g must be finite, >= 0 and below fmax_hz = %g (0 = Nyquist, %g)", fn, (double)q.fmin_hz, (double)q.fmax_hz, 0.5 * rate);
+    zv::fail(ZV_ERR_ARG, "%s: mel fmax_hz = %g must be finite, >= 0 and at most Nyquist, %g", fn, (double)q.fmax_hz, 0.5 * rate);
+}
+
+static void mel_run(zv_model *m, const char *fn, uint32_t n_utt, const float *const *wav, const uint32_t *T, const zv_mel *mel, float *const *out)
+{
+#if !defined(__HIP_DEVICE_COMPILE__)      // (mel.h keeps its host half out of device passes)
+    Model &M = *m->m;
+    const uint32_t hop = M.hp.audio_hop_size, nm = M.hp.audio_num_mels, rate = M.hp.audio_sampling_rate;
+    if (!mel) zv::fail(ZV_ERR_ARG, "%s: mel is NULL", fn);
+    if (hop < 4 || hop % 4) zv::fail(ZV_ERR_ARG, "%s: audio_hop_size = %u must be a multiple of 4", fn, hop);
+    uint64_t rows = 0;
+    uint32_t t_min = T[0], t_max = 0;
+    for (uint32_t u = 0; u < n_utt; u++)
+    {
+        rows += T[u];
+        t_min = std::min(t_min, T[u]);
+        t_max = std::max(t_max, T[u]);
+        if (mel->pad == 1u && (uint64_t)T[u] * hop < (uint64_t)zv::BANDS_BINS)
+            zv::fail(ZV_ERR_ARG, "%s: utterance %u: T = %u gives %llu samples, mel pad = 1 (reflect) needs at least %d", fn, u, T[u],
+                     (unsigned long long)T[u] * hop, zv::BANDS_BINS);
+    }
+    if (rows > (uint64_t)INT32_MAX) zv::fail(ZV_ERR_ARG, "%s: the batch holds %llu frames, more than %d", fn, (unsigned long long)rows, INT32_MAX);
+    std::vector<uint32_t> par;
+    const zv::MelParams q{mel->weights, mel->fmin_hz, mel->fmax_hz, mel->centre, mel->pad, mel->log, mel->floor};
+    if (const char *field = zv::mel_resolve(q, rate, hop, nm, (uint64_t)t_min * hop, par)) mel_fail(fn, field, *mel, hop, nm, rate);
+    use_lane0(m);
+    M.mel_table();                        // (allocates and copies on first use: ahead of everything enqueued)
+    std::vector<zv::Seg> segs(n_utt);
+    int32_t row0 = 0;
+    for (uint32_t u = 0; u < n_utt; u++)
+    {
+        segs[u] = zv::Seg{row0, (int32_t)T[u], 0, 0};
+        row0 += (int32_t)T[u];
+    }
+    Layout L;
+    const size_t o_wav = L.at(rows * hop * 4), o_rows = L.at(rows * nm * 4), o_slab = L.at(rows * zv::MEL_SLAB_STRIDE * 8), o_par = L.at(par.size() * 4),
+                 o_seg = L.at(segs.size() * sizeof(zv::Seg));
+    char *io = (char *)M.io_scratch(L.size());
+    for (uint32_t u = 0; u < n_utt; u++)
+        ZV_HIP(hipMemcpyAsync(io + o_wav + (size_t)segs[u].row0 * hop * 4, wav[u], (size_t)T[u] * hop * 4, hipMemcpyHostToDevice, M.stream()));
+    ZV_HIP(hipMemcpyAsync(io + o_par, par.data(), par.size() * 4, hipMemcpyHostToDevice, M.stream()));
+    ZV_HIP(hipMemcpyAsync(io + o_seg, segs.data(), segs.size() * sizeof(zv::Seg), hipMemcpyHostToDevice, M.stream()));
+    const zv::Segs frames{n_utt > 1 ? (const zv::Seg *)(io + o_seg) : nullptr, (int)n_utt, (int)t_max, segs[0]};
+    M.mel_launches((const float *)(io + o_wav), (double *)(io + o_slab), (float *)(io + o_rows), (const uint32_t *)(io + o_par), frames, (size_t)rows);
+    for (uint32_t u = 0; u < n_utt; u++)
+        ZV_HIP(hipMemcpyAsync(out[u], io + o_rows + (size_t)segs[u].row0 * nm * 4, (size_t)T[u] * nm * 4, hipMemcpyDeviceToHost, M.stream()));
+    M.sync();                             // (par and segs are pageable: the uploads have read them by now)
+#endif
+}
+
+zv_status zv_mel_wave(zv_model *m, const float *wav, uint32_t T, const zv_mel *mel, float *out)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!m) zv::fail(ZV_ERR_ARG, "%s: m is NULL", fn);
+        if (!wav) zv::fail(ZV_ERR_ARG, "%s: wav is NULL", fn);
+        if (!out) zv::fail(ZV_ERR_ARG, "%s: out is NULL", fn);
+        try
+        {
+            check_T(*m->m, T);
+        }
+        catch (const zv::Error &e)
+        {
+            zv::fail(e.status, "%s: %s", fn, e.what());
+        }
+        mel_run(m, fn, 1, &wav, &T, mel, &out);
+    });
+}
+
+zv_status zv_mel_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint32_t *T, const zv_mel *mel, float *const *out)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        check_stage_args(fn, m, n_utt, {{"wav", wav, true}, {"out", out, true}}, nullptr, T);
+        mel_run(m, fn, n_utt, wav, T, mel, out);
+    });
+}
+
+// The design: host only, no model, no device (mel.h mel_design).
+zv_status zv_mel_design(uint32_t sampling_rate, uint32_t num_mels, float fmin_hz, float fmax_hz, float *weights)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!weights) zv::fail(ZV_ERR_ARG, "%s: weights is NULL", fn);
+#if !defined(__HIP_DEVICE_COMPILE__)      // (mel.h keeps its host half out of device passes)
+        zv_mel q{};
+        q.fmin_hz = fmin_hz;
+        q.fmax_hz = fmax_hz;
+        if (const char *field = zv::mel_design(sampling_rate, num_mels, fmin_hz, fmax_hz, weights)) mel_fail(fn, field, q, 0, num_mels, sampling_rate);
+#endif
+    });
+}
+
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)
 {
     return guarded([&] {
@@ -1612,8 +1724,6 @@ zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)
 
 // ---- the stages in batches (zv_encode_batch, zv_decode_batch, zv_vocode_batch*): the batch request path with a stage range of one
 // stage.  A call's own checks name the argument as the header does; check_request follows with the ids and the controls.
-struct StageArg { const char *name; const void *array; bool entries; };      // entries: a [n_utt] array of pointers, none of which may be null
-
 static void check_stage_args(const char *fn, const zv_model *m, uint32_t n_utt, std::initializer_list<StageArg> args, const uint32_t *n_phonemes,
                              const uint32_t *T)
 {

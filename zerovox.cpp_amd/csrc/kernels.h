@@ -19,6 +19,7 @@
 #include "pitch.h"        // pitch track: PITCH_CHUNK_FRAMES, PITCH_PARAM_STRIDE, the rows
 #include "bands.h"        // band levels: BANDS_TILE_FRAMES, BANDS_PARAM_STRIDE, BANDS_ROW_STRIDE
 #include "filter.h"       // waveform filter: FILTER_TILE, FILTER_PARAM_STRIDE
+#include "mel.h"          // mel analysis: MEL_SLAB_STRIDE, MEL_TABLE_BYTES, the parameter block
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -484,5 +485,17 @@ hipError_t launch_bands_phonemes(hipStream_t s, const int32_t *cum, const void *
 // rows) * hop: n_taps == 0 copies the capacity bit for bit; else out[0 .. S) is the rule over in[0 .. S) and out[S .. capacity) is
 // +0.0.  Nothing outside the segment's own span [row0 * hop, row0 * hop + S) is read.
 hipError_t launch_filter(hipStream_t s, const float *in, float *out, const uint32_t *par, const Segs &frames, const Segs &live, int hop);
+
+// ---- mel analysis (include/zerovox_amd.h "mel analysis", mel.h): two passes over a waveform laid out like the vocoder's output, by
+// ABSOLUTE frame row times hop.  `frames` is the table of the utterances' frames or the inline segment; par the call's ONE parameter
+// block (mel_resolve, mel_par_words(num_mels) words), read at run time; the grids: stage_plan.h mel_plan.
+//   frames: slab[(frames[u].row0 + f) * MEL_SLAB_STRIDE + k] = the magnitude of bin k of frame f (f64), for every frame of every segment.
+//           table: both digit planes in fragment order (mel_table_fragments, MEL_TABLE_BYTES, 16-byte aligned).  A span never leaves
+//           its segment's own samples [row0 * hop, (row0 + rows) * hop): what lies outside is zero or the segment's own reflection.
+//   rows:   rows[(frames[u].row0 + f) * num_mels + c] = channel c of frame f, from the slab the frames pass stored in the same run.
+// The hop is a multiple of 4, as for the band levels, else both are refused.  No atomics, nothing to zero.
+hipError_t launch_mel_frames(hipStream_t s, const float *wav, const void *table, double *slab, const uint32_t *par, const Segs &frames, int hop,
+                             int num_mels);
+hipError_t launch_mel_rows(hipStream_t s, const double *slab, float *rows, const uint32_t *par, const Segs &frames, int hop, int num_mels);
 
 }  // namespace zv

@@ -11,4 +11,5 @@
 #include "pitch_kernels.hip"          // pitch track
 #include "bands_kernels.hip"          // band levels
 #include "filter_kernels.hip"         // waveform filter
+#include "mel_kernels.hip"            // mel analysis
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

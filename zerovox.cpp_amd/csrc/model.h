@@ -243,6 +243,11 @@ class Model
     // memory outside the arenas), built on the host and uploaded at the first request, then kept for the model's life.  It allocates
     // and copies synchronously, so the entry points call it before anything is enqueued or captured.
     const void *bands_table();
+    // mel analysis: both digit planes of its table likewise (mel.h mel_table_fragments, MEL_TABLE_BYTES)
+    const void *mel_table();
+    // the two launches of mel analysis on the lane's stream (wave_stages.cpp; kernels.h launch_mel_frames / launch_mel_rows), eager:
+    // d_wav the utterances' samples by absolute frame row, d_par the call's parameter block, total_rows the rows of all segments
+    void mel_launches(const float *d_wav, double *d_slab, float *d_rows, const uint32_t *d_par, const Segs &frames, size_t total_rows);
 
     // scratch for host-buffer entry points (grows on demand)
     void *io_scratch(size_t bytes);
@@ -278,7 +283,7 @@ class Model
   private:
     // ---- weights ----
     std::vector<void *> allocs_;
-    void  *bands_table_ = nullptr;
+    void  *bands_table_ = nullptr, *mel_table_ = nullptr;
     void  *dev_alloc(size_t bytes);
     float *upload_f32(const GgufTensor &t, int pad_to = 0, float pad_value = 0.f);
     float *upload_vec(const GgufFile &g, const std::string &name, int expect_n, int pad_to = 0, float pad_value = 0.f);

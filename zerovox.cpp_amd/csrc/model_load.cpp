@@ -32,6 +32,20 @@ const void *Model::bands_table()
     return bands_table_;
 }
 
+const void *Model::mel_table()
+{
+#if !defined(__HIP_DEVICE_COMPILE__)      // (mel.h keeps its host half out of device passes)
+    if (!mel_table_)
+    {
+        const std::vector<int8_t> img = mel_table_fragments(mel_tables());
+        void *d = dev_alloc(img.size());
+        ZV_HIP(hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice));
+        mel_table_ = d;
+    }
+#endif
+    return mel_table_;
+}
+
 float *Model::upload_f32(const GgufTensor &t, int pad_to, float pad_value)
 {
     if (t.type != GGML_F32) fail(ZV_ERR_SHAPE, "tensor %s: expected f32", t.name.c_str());

@@ -10,6 +10,7 @@
 
 #include "conv_plan.h"      // batch_switch / batch_rows, plan_round_up
 #include "knobs.h"
+#include "mel.h"            // MEL_TILE_FRAMES, MEL_ROWS_FRAMES, MEL_MAX_MELS
 
 namespace zv
 {
@@ -88,6 +89,19 @@ inline LrPlan lr_plan(int C, int ld, int ldh, int tokens_max, int frames_max, in
 // ---- LayerNorm launches that carry tail work (encoder_kernels.hip: launch_layernorm_tail) ----
 constexpr int LN_TAIL_MAX = 64 * 12;                    // the tail exists in the rows-in-registers form only: 12 channels per lane
 inline bool layernorm_tail_ok(int C) { return C <= LN_TAIL_MAX; }
+
+// ---- mel analysis (mel_kernels.hip): ONE launch per kernel over the segment table, whatever the batch ----
+struct MelPlan
+{
+    bool ok;                    // the hop is a multiple of 4 (as for the band levels), 1 <= num_mels <= MEL_MAX_MELS, a frame exists
+    int  frames_gx, rows_gx;    // mel_frames_kernel: tiles of MEL_TILE_FRAMES frames; mel_rows_kernel: groups of MEL_ROWS_FRAMES frames
+    int  gy;                    // segments, of both grids
+};
+inline MelPlan mel_plan(int max_rows, int nseg, int hop, int num_mels)
+{
+    const bool ok = max_rows >= 1 && nseg >= 1 && hop >= 4 && (hop & 3) == 0 && num_mels >= 1 && num_mels <= (int)MEL_MAX_MELS;
+    return MelPlan{ok, (max_rows + MEL_TILE_FRAMES - 1) / MEL_TILE_FRAMES, (max_rows + MEL_ROWS_FRAMES - 1) / MEL_ROWS_FRAMES, nseg};
+}
 
 // ---- the encoder's schedule (encoder.cpp) ----
 struct EncPlan

@@ -98,4 +98,17 @@ void Model::wave_stage_launches(const Batch &bt, const VocLayout &lay, float *d_
     }
 }
 
+// Mel analysis (mel.h): no stage of the chain — the stand-alone entry points' two launches over a waveform the caller brought.
+void Model::mel_launches(const float *d_wav, double *d_slab, float *d_rows, const uint32_t *d_par, const Segs &frames, size_t total_rows)
+{
+    const int hop = (int)hp.audio_hop_size, M = (int)hp.audio_num_mels;
+    const double rows = (double)total_rows;
+    // algorithmic bytes: the samples read once, the table once per tile of frames, a slab row written per frame; the slab read, the
+    // weights once and a row written per frame.  Operations: 2 per 8-bit multiply-add, four digit-plane products, 1 026 columns.
+    ZV_LAUNCH("mel_frames", 4.0 * rows * hop + (double)MEL_TABLE_BYTES * rows / MEL_TILE_FRAMES + 8.0 * MEL_SLAB_STRIDE * rows,
+              2.0 * 4.0 * (double)BANDS_N * 2.0 * BANDS_BINS * rows,
+              launch_mel_frames(stream(), d_wav, mel_table(), d_slab, d_par, frames, hop, M));
+    ZV_LAUNCH("mel_rows", 8.0 * MEL_SLAB_STRIDE * rows + 4.0 * M * (rows + BANDS_BINS), 0.0, launch_mel_rows(stream(), d_slab, d_rows, d_par, frames, hop, M));
+}
+
 }  // namespace zv

@@ -95,6 +95,9 @@ class HiFiGAN
     // (not in the reference) n utterances in one call, mels[u] [T[u]][in_channels] -> wavs[u] [T[u] * hop_size]: zv_vocode_batch, every
     // waveform the bits of a single vocode of that mel
     void eval_batch(uint32_t n, const float *const *mels, const uint32_t *T, float *const *wavs);
+    // (not in the reference) the way back: wav [max_seq_len * hop_size] -> mel [max_seq_len][in_channels], zv_mel_wave with natural-log
+    // Slaney mels over 0 .. Nyquist, reflect padding, centre 0 and the default floor — the domain eval reads
+    void analyze(const float *wav, float *mel);
 
   private:
     zv_model *model;

@@ -99,6 +99,14 @@ void HiFiGAN::eval_batch(uint32_t n, const float *const *mels, const uint32_t *T
     chk(zv_vocode_batch(model, n, mels, T, wavs));
 }
 
+void HiFiGAN::analyze(const float *wav, float *mel)
+{
+    zv_mel q{};
+    q.pad = 1;
+    q.log = 1;
+    chk(zv_mel_wave(model, wav, max_seq_len, &q, mel));
+}
+
 // ---------------------------------------------------------------------------------------------------
 
 ZeroVOXModel::ZeroVOXModel(const std::string &fname)

@@ -66,6 +66,11 @@
 //            --band-edges-hz; --eq-taps the tap count (odd, 1 .. 511, default 255).  The taps come from zv_filter_design.
 //            --filter-taps FILE reads the taps themselves, one per line, and excludes the other three.  A malformed value, a gain
 //            count that does not match the bands, or edges / a tap count without gains are usage errors; the library checks the taps.
+//   --analyze IN.wav, --mel-out FILE, --resynth OUT.wav, --mel-fmin HZ, --mel-fmax HZ, --mel-centre SAMPLE, --mel-pad reflect|zero
+//            mel analysis (include/zerovox_amd.h "mel analysis") in place of synthesis: the log-mel rows (natural logarithm, Slaney
+//            weights) of a mono PCM16 RIFF file at the model's rate — what zv_write_wav writes — as raw f32 [frames][mel channels], and /
+//            or the vocoder's waveform of those rows.  A file at another rate or with more channels is an error by name; nothing is
+//            resampled.  The mel flags without --analyze, or --analyze without an output, are usage errors.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
 //   --plan   print the frame count of every utterance of the -u file (which may then hold several, three lines each) without decoding
 //            or vocoding, one line each: index n_phonemes n_frames seconds; the prosody flags apply to every utterance, then exit
@@ -96,6 +101,8 @@ static void usage(FILE *f)
                "               [--pitch FILE] [--phoneme-pitch FILE] [--pitch-min-hz F] [--pitch-max-hz F] [--pitch-threshold X]\n"
                "               [--bands FILE] [--phoneme-bands FILE] [--band-edges-hz a,b,c,...]\n"
                "               [--eq-gain-db g0,g1,...] [--eq-edges-hz a,b,c,...] [--eq-taps L] [--filter-taps FILE]\n"
+               "       zerovox -m model.gguf --analyze in.wav [--mel-out rows.f32] [--resynth out.wav]\n"
+               "               [--mel-fmin HZ] [--mel-fmax HZ] [--mel-centre SAMPLE] [--mel-pad reflect|zero]\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
@@ -130,7 +137,11 @@ static void usage(FILE *f)
                "  --eq-gain-db g0,g1,...  filter the waveform on the device: a gain in dB per band (16 for the default bands of --bands)\n"
                "  --eq-edges-hz a,b,c,...  the equaliser's band edges in Hz, converted like --band-edges-hz\n"
                "  --eq-taps L          the equaliser's tap count, odd, 1 .. 511, default 255 (a band step takes about 4096 / (L + 1) bins)\n"
-               "  --filter-taps FILE   filter the waveform with the taps in FILE, one per line (an odd count of 1 .. 511), instead\n",
+               "  --filter-taps FILE   filter the waveform with the taps in FILE, one per line (an odd count of 1 .. 511), instead\n"
+               "  --analyze IN.wav     no synthesis: the log-mel rows (natural logarithm) of a mono PCM16 file at the model's rate, with\n"
+               "                       --mel-out FILE (raw f32 [frames][mel channels]) and / or --resynth OUT.wav (the vocoder's waveform of them);\n"
+               "                       --mel-fmin HZ, --mel-fmax HZ (default 0 .. Nyquist), --mel-centre SAMPLE (0 .. hop - 1, default 0),\n"
+               "                       --mel-pad reflect|zero (default reflect)\n",
             k_default_model, k_default_out);
 }
 
@@ -310,8 +321,72 @@ static int plan(const std::string &model_path, const std::string &utt_path, cons
     return 0;
 }
 
+// --analyze IN.wav: the file's log-mel rows (zv_mel_wave: natural logarithm, Slaney weights fmin .. fmax, the model's hop and channel
+// count) as raw little-endian f32 [T][num_mels] in --mel-out, and with --resynth OUT.wav the vocoder's waveform of those rows.  The
+// file must be what zv_write_wav writes: mono PCM16 RIFF at the model's rate; anything else is an error by name, nothing is resampled.
+// Samples behind the last whole hop are dropped.
+static int analyze(const std::string &model_path, const std::string &in_path, const std::string &mel_path, const std::string &resynth_path,
+                   const zv_mel &q)
+{
+    std::ifstream f(in_path, std::ios::binary);
+    if (!f) throw std::runtime_error("--analyze: cannot open '" + in_path + "'");
+    const std::vector<unsigned char> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    auto u16 = [&](size_t o) { return (uint32_t)b[o] | (uint32_t)b[o + 1] << 8; };
+    auto u32 = [&](size_t o) { return u16(o) | u16(o + 2) << 16; };
+    if (b.size() < 12 || memcmp(b.data(), "RIFF", 4) != 0 || memcmp(b.data() + 8, "WAVE", 4) != 0)
+        throw std::runtime_error("--analyze: '" + in_path + "' is not a RIFF/WAVE file");
+    uint32_t format = 0, channels = 0, rate = 0, bits = 0;
+    size_t data = 0, data_bytes = 0;
+    for (size_t o = 12; o + 8 <= b.size();)
+    {
+        const size_t n = u32(o + 4), body = o + 8;
+        if (!memcmp(b.data() + o, "fmt ", 4) && n >= 16 && body + 16 <= b.size())
+            format = u16(body), channels = u16(body + 2), rate = u32(body + 4), bits = u16(body + 14);
+        if (!memcmp(b.data() + o, "data", 4))
+        {
+            data = body, data_bytes = std::min(n, b.size() - body);
+            break;
+        }
+        o = body + n + (n & 1);
+    }
+    if (!rate || !data) throw std::runtime_error("--analyze: '" + in_path + "' has no fmt or no data chunk");
+    if (format != 1 || bits != 16) throw std::runtime_error("--analyze: '" + in_path + "' is not 16-bit PCM (format " + std::to_string(format) + ", " + std::to_string(bits) + " bits)");
+    if (channels != 1) throw std::runtime_error("--analyze: '" + in_path + "' has " + std::to_string(channels) + " channels, mono is needed");
+    zv_model *m = nullptr;
+    if (zv_model_load(model_path.c_str(), 0, &m) != ZV_OK) throw std::runtime_error(zv_last_error());
+    struct Free { zv_model *m; ~Free() { zv_model_free(m); } } free_model{m};
+    zv_hparams hp;
+    if (zv_model_get_hparams(m, &hp) != ZV_OK) throw std::runtime_error(zv_last_error());
+    if (rate != hp.audio_sampling_rate)
+        throw std::runtime_error("--analyze: '" + in_path + "' is at " + std::to_string(rate) + " Hz, the model at " + std::to_string(hp.audio_sampling_rate) + " Hz (nothing is resampled)");
+    const size_t T = data_bytes / 2 / hp.audio_hop_size;
+    if (T == 0 || T > zv_max_frames(m))
+        throw std::runtime_error("--analyze: '" + in_path + "' holds " + std::to_string(T) + " frames of " + std::to_string(hp.audio_hop_size) + " samples, 1 .. " + std::to_string(zv_max_frames(m)) + " are needed");
+    std::vector<float> wav(T * hp.audio_hop_size), mel(T * hp.audio_num_mels);
+    for (size_t i = 0; i < wav.size(); i++) wav[i] = (float)(int16_t)u16(data + 2 * i) / 32768.0f;
+    if (zv_mel_wave(m, wav.data(), (uint32_t)T, &q, mel.data()) != ZV_OK) throw std::runtime_error(zv_last_error());
+    if (!mel_path.empty())
+    {
+        std::ofstream o(mel_path, std::ios::binary);
+        o.write((const char *)mel.data(), (std::streamsize)(mel.size() * 4));
+        if (!o) throw std::runtime_error("--mel-out: cannot write '" + mel_path + "'");
+    }
+    printf("%s: %zu frames x %u mel channels\n", in_path.c_str(), T, hp.audio_num_mels);
+    if (!resynth_path.empty())
+    {
+        if (zv_vocode(m, mel.data(), (uint32_t)T, wav.data()) != ZV_OK) throw std::runtime_error(zv_last_error());
+        if (zv_write_wav(resynth_path.c_str(), wav.data(), wav.size(), hp.audio_sampling_rate) != ZV_OK) throw std::runtime_error(zv_last_error());
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    std::string analyze_path, melout_path, resynth_path;      // --analyze, --mel-out, --resynth
+    zv_mel mel_q{};                                            // --mel-fmin, --mel-fmax, --mel-centre, --mel-pad
+    mel_q.log = 1;
+    mel_q.pad = 1;
+    bool mel_flag = false;
     std::string model_path = k_default_model, out_path = k_default_out, utt_path, pc_path, align_path, gain_path, contour_path, plevel_path, pitch_path, ppitch_path;
     std::string bands_path, pbands_path;
     std::vector<double> band_hz;       // --band-edges-hz
@@ -405,6 +480,35 @@ int main(int argc, char **argv)
             eq_taps_given = true;
         }
         else if (a == "--filter-taps") taps_path = need("--filter-taps");
+        else if (a == "--analyze") analyze_path = need("--analyze");
+        else if (a == "--mel-out") melout_path = need("--mel-out"), mel_flag = true;
+        else if (a == "--resynth") resynth_path = need("--resynth"), mel_flag = true;
+        else if (a == "--mel-fmin") mel_q.fmin_hz = parse_flag_float("--mel-fmin", need("--mel-fmin")), mel_flag = true;
+        else if (a == "--mel-fmax") mel_q.fmax_hz = parse_flag_float("--mel-fmax", need("--mel-fmax")), mel_flag = true;
+        else if (a == "--mel-centre")
+        {
+            const std::string v = need("--mel-centre");
+            char *end = nullptr;
+            const long c = strtol(v.c_str(), &end, 10);
+            if (end == v.c_str() || *end || c < 0 || c > 0x7fffffffL)
+            {
+                fprintf(stderr, "zerovox: --mel-centre: '%s' is not a sample of a hop\n", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+            mel_q.centre = (uint32_t)c, mel_flag = true;
+        }
+        else if (a == "--mel-pad")
+        {
+            const std::string v = need("--mel-pad");
+            if (v != "reflect" && v != "zero")
+            {
+                fprintf(stderr, "zerovox: --mel-pad: '%s' is neither reflect nor zero\n", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+            mel_q.pad = v == "reflect", mel_flag = true;
+        }
         else if (a == "--pitch-min-hz" || a == "--pitch-max-hz" || a == "--pitch-threshold")
         {
             const std::string v = need(a.c_str());
@@ -522,6 +626,18 @@ int main(int argc, char **argv)
         else if (a == "-h" || a == "--help") { usage(stdout); return 0; }
         else { fprintf(stderr, "zerovox: unknown argument '%s'\n", a.c_str()); usage(stderr); return 2; }
     }
+    if (mel_flag && analyze_path.empty())
+    {
+        fprintf(stderr, "zerovox: --mel-out, --resynth, --mel-fmin, --mel-fmax, --mel-centre and --mel-pad need --analyze IN.wav\n");
+        usage(stderr);
+        return 2;
+    }
+    if (!analyze_path.empty() && melout_path.empty() && resynth_path.empty())
+    {
+        fprintf(stderr, "zerovox: --analyze needs --mel-out FILE or --resynth FILE\n");
+        usage(stderr);
+        return 2;
+    }
     if (!band_hz.empty() && bands_path.empty() && pbands_path.empty())
     {
         fprintf(stderr, "zerovox: --band-edges-hz needs --bands FILE or --phoneme-bands FILE\n");
@@ -599,6 +715,7 @@ int main(int argc, char **argv)
         }
 
         if (planning) return plan(model_path, utt_path, controlled ? &prosody : nullptr);
+        if (!analyze_path.empty()) return analyze(model_path, analyze_path, melout_path, resynth_path, mel_q);
 
         // per-phoneme controls and timings: the file is checked against the utterance before the model is loaded
         std::vector<int32_t> ids0;
