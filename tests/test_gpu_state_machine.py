@@ -2,7 +2,8 @@
 arenas, graph mode toggled, batches on the in-flight lanes, chunked vocoding) on ONE model must give, for every call,
 exactly the bits a second model gives that sees each distinct call once, eagerly, in a different order.
 A second generator, which leaves the first one's call sequence as it is, poisons lane 0 of the first model (zv_debug_poison: everything
-the lane keeps between calls) ahead of about one step in ten, and follows some synth calls and batches with their fitted forms."""
+the lane keeps between calls) ahead of about one step in ten, and follows some synth calls and batches with their fitted forms.
+tests/test_gpu_call_history.py walks every later entry point, the per-utterance asks and the cached graphs in the same way."""
 import numpy as np
 import pytest
 

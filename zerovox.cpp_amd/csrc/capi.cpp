@@ -1155,7 +1155,7 @@ static zv_status synthesize_batch(zv_model *m, const Request &r)
 {
       return guarded([&] {
         check_request(m, r);
-        ZV_HIP(hipSetDevice(m->m->device));
+        use_lane0(m);                             // refused like every synchronous call while lane 0 has a batch in flight, in the same words
         // Groups of up to 64 utterances / 64 Ki frames go through the chain as ONE launch per kernel: every tensor is
         // the row concatenation of the group, the segment tables tell the kernels where each utterance starts and ends.
         // Capacities are rounded up so that batches of similar shape replay the same captured graph.
