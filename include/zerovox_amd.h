@@ -25,6 +25,8 @@
  *   zv_filter_wave     the filter on any waveform the caller brings; zv_filter_design: band gains to taps, on the host
  *   zv_mel_wave        the log-mel rows of any waveform the caller brings (the vocoder's input domain); zv_mel_wave_batch: a batch of
  *                      them in one launch per kernel; zv_mel_design: Slaney mel weights, on the host
+ *   zv_mel_align       the dynamic-time-warping path between two sequences of mel rows: its spectral distance and the frame maps;
+ *                      zv_mel_align_batch: a batch of pairs in one launch per kernel; zv_align_durations: the timing transfer, on the host
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file       src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -799,7 +801,7 @@ zv_status zv_filter_design(uint32_t n_bands, const uint32_t *edges, const float 
  * fmax_hz = 0 means Nyquist.  ZV_ERR_ARG for a value that is not finite or negative, fmin_hz >= fmax_hz, fmax_hz above Nyquist, or
  * num_mels 0 or above 256.
  * Out of scope: other DFT sizes or window lengths; mel analysis inside the zv_synthesize* chain or a captured graph; a distance between
- * mels (the caller subtracts); resampling. */
+ * mels (see "mel alignment" below: zv_mel_align); resampling. */
 typedef struct
 {
     const float *weights;   /* [num_mels*513] or NULL = zv_mel_design(rate, num_mels, fmin_hz, fmax_hz) */
@@ -811,6 +813,64 @@ zv_status zv_mel_wave(zv_model *m, const float *wav, uint32_t T, const zv_mel *m
 zv_status zv_mel_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint32_t *T, const zv_mel *mel /* one for the batch */,
                             float *const *out);
 zv_status zv_mel_design(uint32_t sampling_rate, uint32_t num_mels, float fmin_hz, float fmax_hz, float *weights);
+/* ---- mel alignment: the DTW path between two sequences of mel rows, its distance and the timing transfer ---------------------------------
+ * Two sequences of mel rows rarely have the same number of frames: synthesised against recorded speech, the mel of a re-timed waveform
+ * against the mel that went in, a recording whose timing a synthesis is to follow.  zv_mel_align finds the dynamic-time-warping path
+ * between a[Ta][M] and b[Tb][M] (f32 rows of any kind: zv_mel_wave rows, decoder mels, anything of the same width), the spectral
+ * distance along it and the two frame maps; zv_align_durations turns a map into the durations of the other side.
+ * The rule, per pair.  Every output can be restated bit for bit (csrc/align.h holds the rule as plain C++, host reference included);
+ * nothing depends on how cells are dealt over lanes, waves, tiles or workgroups.
+ *   quantise   a non-finite value counts as +0.0; d = (double)x * (double)scale; d = min(max(d, -1023.0), 1023.0);
+ *              d = d + (d >= 0 ? 0.5 : -0.5); q = (int64)d, truncating — each one IEEE f64 operation.
+ *   normalise  (normalise = 1 only; per sequence and per channel m: it removes a recording's gain and a fixed channel response)
+ *              s = sum over t of q[t][m]; mean = floor((2*s + T) / (2*T)), a true floor (round half up); q' = q - mean.  Else q' = q.
+ *              |q'| <= 2046.
+ *   cost       c[i][j] = sum over m of (qa'[i][m] - qb'[j][m])^2, an integer below 2^32 (256 * 4092^2 = 4 286 582 784).
+ *   path       D[0][0] = c[0][0], else D[i][j] = c[i][j] + the least D of the predecessors that exist, examined in the order
+ *              (i-1, j-1), (i-1, j), (i, j-1); a later one wins only when it is strictly smaller.  D is int64 (below 2^45);
+ *              total = D[Ta-1][Tb-1].
+ *   walk       from (Ta-1, Tb-1) back to (0, 0) along the choices taken: path_len = L, the number of cells; map_a[i] = the smallest j
+ *              on the path in row i, map_b[j] = the smallest i on the path in column j.  The distance in walk order, from the end to
+ *              the start: acc = +0.0; per cell acc = acc + sqrt((double)c[i][j]); then acc = acc / (double)L; acc = acc / (double)scale
+ *              — each one IEEE operation.  distance is the mean Euclidean distance per path cell, in the rows' own unit.
+ * Limits: 1 <= M <= 256, 1 <= Ta, Tb <= ZV_ALIGN_MAX_FRAMES.  params->scale = 0 means 64.0, otherwise it must be finite and positive;
+ * params->normalise is 0 or 1; a zero-initialised zv_align is scale 64 without normalisation.  Everything else returns ZV_ERR_ARG
+ * before any work is enqueued, the message naming the entry point, the pair (batch form) and the field.  map_a [Ta] and map_b [Tb]
+ * may be NULL.  The calls run eagerly, on lane 0, like zv_mel_wave_batch.
+ * zv_mel_align_batch: ONE launch per kernel for a launch group of pairs, and pair p receives the bits of its single call.  A group
+ * holds at most 2^27 cells (Ta*Tb summed), where cost (u32) and choice (u8) take 640 MiB of the lane's I/O block; a larger batch runs
+ * as consecutive groups of consecutive pairs.  One zv_align serves the batch; the arrays map_a / map_b or entries of them may be NULL.
+ * The dot products of the cost run on v_mfma_i32_16x16x64_i8 over two signed base-128 digits of q' (hi = (q' + 64) >> 7,
+ * lo = q' - 128*hi), c = |qa'|^2 + |qb'|^2 - 2*(16384*hh + 128*(hl + lh) + ll) in int64.
+ * zv_align_durations is host only and needs neither a model nor a device: the timing transfer.  durations_a[n] are the frames per
+ * phoneme of sequence a (their sum must be Ta), map_a[Ta] the map of an alignment of a against a sequence of Tb frames.  With s_p
+ * the sum of durations_a before p: pos_0 = 0, pos_p = map_a[s_p] when s_p < Ta, else Tb, pos_n = Tb; durations_b[p] = pos_{p+1} - pos_p.
+ * ZV_ERR_ARG for a NULL pointer, a negative duration ("durations_a"), a sum other than Ta, or a map_a that is not non-decreasing
+ * inside [0, Tb).  The result is non-negative, sums to Tb, and is valid as zv_phoneme_controls duration_frames when
+ * Tb <= min(32768, zv_max_frames()).
+ * Out of scope: band constraints; other step patterns or slope weights; open-ended (sub-sequence) alignment; cepstra / MCD in dB (the
+ * caller converts distance); sequences beyond 4096 frames; alignment inside the zv_synthesize* chain or a captured graph; a pitch or
+ * energy transfer (zv_pitch_track and the maps give the caller what it needs); resampling. */
+#define ZV_ALIGN_MAX_FRAMES 4096
+typedef struct
+{
+    float    scale;         /* 0 = 64.0 */
+    uint32_t normalise;     /* 0 or 1 */
+} zv_align;                 /* zero-initialised = scale 64, no normalisation */
+typedef struct
+{
+    uint64_t total;         /* D[Ta-1][Tb-1] */
+    double   distance;
+    uint32_t path_len;
+    uint32_t reserved;
+} zv_alignment;
+zv_status zv_mel_align(zv_model *m, const float *a, uint32_t Ta, const float *b, uint32_t Tb, uint32_t M, const zv_align *params,
+                       zv_alignment *out, int32_t *map_a /* [Ta] or NULL */, int32_t *map_b /* [Tb] or NULL */);
+zv_status zv_mel_align_batch(zv_model *m, uint32_t n_pairs, const float *const *a, const uint32_t *Ta, const float *const *b,
+                             const uint32_t *Tb, uint32_t M, const zv_align *params /* one for the batch */, zv_alignment *out,
+                             int32_t *const *map_a /* array or entries may be NULL */, int32_t *const *map_b);
+zv_status zv_align_durations(uint32_t n, const int32_t *durations_a, uint32_t Ta, const int32_t *map_a, uint32_t Tb,
+                             int32_t *durations_b);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

@@ -34,6 +34,7 @@ SYMBOLS = [
     "zv_set_graph_cache", "zv_graph_cache_stats",
     "zv_encode_batch", "zv_decode_batch", "zv_vocode_batch", "zv_vocode_batch_begin", "zv_vocode_batch_end",
     "zv_mel_wave", "zv_mel_wave_batch", "zv_mel_design",
+    "zv_mel_align", "zv_mel_align_batch", "zv_align_durations",
 ]
 
 
@@ -461,6 +462,78 @@ def mel_design(sampling_rate: int, num_mels: int, fmin_hz: float = 0.0, fmax_hz:
     return w
 
 
+class AlignC(C.Structure):
+    """zv_align of include/zerovox_amd.h (a zeroed struct is scale 64 without normalisation)"""
+    _fields_ = [("scale", C.c_float), ("normalise", C.c_uint32)]
+
+
+class AlignmentC(C.Structure):
+    """zv_alignment of include/zerovox_amd.h"""
+    _fields_ = [("total", C.c_uint64), ("distance", C.c_double), ("path_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AlignParams:
+    """The parameters of mel alignment (include/zerovox_amd.h "mel alignment"): scale (the quantiser's steps per unit of the rows,
+    0 = 64) and normalise (remove every channel's mean per sequence: a recording's gain and fixed channel response).  The library
+    checks the values."""
+    MAX_FRAMES = 4096
+
+    def __init__(self, scale: float = 0.0, normalise=False):
+        self.scale = float(scale)
+        self.normalise = int(normalise)
+
+    @property
+    def struct(self) -> AlignC:
+        return AlignC(self.scale, self.normalise & 0xffffffff)
+
+    def __repr__(self):
+        return f"AlignParams(scale={self.scale}, normalise={self.normalise})"
+
+
+class Alignment:
+    """What mel alignment returns: total (the path's summed integer cost), distance (the mean Euclidean distance per path cell, in the
+    rows' own unit), path_len, map_a int32 [Ta] (the first frame of b on the path in each row of a) and map_b int32 [Tb]"""
+
+    def __init__(self, total: int, distance: float, path_len: int, map_a, map_b):
+        self.total, self.distance, self.path_len, self.map_a, self.map_b = int(total), float(distance), int(path_len), map_a, map_b
+
+    def __repr__(self):
+        return f"Alignment(total={self.total}, distance={self.distance!r}, path_len={self.path_len}, Ta={len(self.map_a)}, Tb={len(self.map_b)})"
+
+
+def _align_params(who: str, params) -> AlignParams:
+    if params is None:
+        return AlignParams()
+    if not isinstance(params, AlignParams):
+        raise TypeError(f"{who}: params must be an AlignParams or None, not {type(params).__name__}")
+    return params
+
+
+def _mel_rows(who: str, rows) -> np.ndarray:
+    r = np.ascontiguousarray(rows, dtype=np.float32)
+    if r.ndim != 2:
+        raise ValueError(f"{who}: the rows must be a 2-D array [frames, channels], got shape {r.shape}")
+    return r
+
+
+def align_durations(durations_a, map_a, Tb: int, lib=None) -> np.ndarray:
+    """zv_align_durations, the timing transfer: the frames per phoneme of sequence a and the map of its alignment against a sequence
+    of Tb frames -> the frames per phoneme on that sequence's clock, int32 [n], which sum to Tb.  Host only: no model, no device."""
+    lib = lib or load_library()
+    fn = _stage_symbol(lib, "zv_align_durations")
+    da = np.ascontiguousarray(durations_a, dtype=np.int32)
+    ma = np.ascontiguousarray(map_a, dtype=np.int32)
+    if da.ndim != 1 or ma.ndim != 1:
+        raise ValueError(f"align_durations: durations_a and map_a must be 1-D, got shapes {da.shape} and {ma.shape}")
+    if isinstance(Tb, (bool, np.bool_)) or not isinstance(Tb, (int, np.integer)) or not 0 <= Tb <= 0xffffffff:
+        raise ValueError(f"align_durations: Tb = {Tb!r} must be an integer in [0, 4294967295]")
+    db = np.zeros(da.size, np.int32)
+    st = fn(da.size, _ptr(da), ma.size, _ptr(ma), int(Tb), _ptr(db))
+    if st != 0:
+        raise ZvError(st, lib.zv_last_error().decode("utf-8", "replace"))
+    return db
+
+
 class EnvelopeC(C.Structure):
     """zv_envelope of include/zerovox_amd.h: the gains' pointer ([n] or NULL) and three integers (a zeroed struct is the identity)"""
     _fields_ = [("phoneme_gain", C.c_void_p), ("ramp_frames", C.c_uint32), ("fade_in_samples", C.c_uint32),
@@ -723,7 +796,10 @@ def _bind(lib):
                            ("zv_vocode_batch_end", [vp, u32]),
                            ("zv_mel_wave", [vp, fp, u32, C.POINTER(MelC), fp]),
                            ("zv_mel_wave_batch", [vp, u32, pvp, pu32, C.POINTER(MelC), pvp]),
-                           ("zv_mel_design", [u32, u32, C.c_float, C.c_float, fp])):
+                           ("zv_mel_design", [u32, u32, C.c_float, C.c_float, fp]),
+                           ("zv_mel_align", [vp, fp, u32, fp, u32, u32, C.POINTER(AlignC), C.POINTER(AlignmentC), vp, vp]),
+                           ("zv_mel_align_batch", [vp, u32, pvp, pu32, pvp, pu32, u32, C.POINTER(AlignC), C.POINTER(AlignmentC), pvp, pvp]),
+                           ("zv_align_durations", [u32, vp, u32, vp, u32, vp])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
@@ -1127,6 +1203,70 @@ class Model:
         vocoder's domain (the natural logarithm is what the reference's checkpoints were trained on: pass MelAnalysis(log="ln", ...)
         with the training front end's fmin / fmax / floor where they differ from the defaults)"""
         return self.vocode(self.mel_wave(wav, params))
+
+    def mel_align(self, a, b, params=None) -> Alignment:
+        """zv_mel_align: the dynamic-time-warping path between the rows a [Ta][M] and b [Tb][M] (float32, 1 <= M <= 256, at most 4 096
+        rows each) -> an Alignment; params: an AlignParams or None (scale 64, no normalisation)"""
+        fn = _stage_symbol(self.lib, "zv_mel_align")
+        p = _align_params("mel_align", params)
+        ra, rb = _mel_rows("mel_align: a", a), _mel_rows("mel_align: b", b)
+        if ra.shape[1] != rb.shape[1]:
+            raise ValueError(f"mel_align: a has {ra.shape[1]} channels, b has {rb.shape[1]}")
+        ma, mb = np.empty(ra.shape[0], np.int32), np.empty(rb.shape[0], np.int32)
+        st, out = p.struct, AlignmentC()
+        self._chk(fn(self.h, _ptr(ra), ra.shape[0], _ptr(rb), rb.shape[0], ra.shape[1], C.byref(st), C.byref(out), _ptr(ma), _ptr(mb)))
+        return Alignment(out.total, out.distance, out.path_len, ma, mb)
+
+    def mel_align_batch(self, pairs, params=None) -> list:
+        """zv_mel_align_batch: pairs of rows (a [Ta][M], b [Tb][M]) of one width through ONE launch per kernel per launch group -> the
+        list of Alignments, each with the bits of its mel_align; params serves the whole batch"""
+        fn = _stage_symbol(self.lib, "zv_mel_align_batch")
+        p = _align_params("mel_align_batch", params)
+        rows = [(_mel_rows(f"mel_align_batch: pair {k}: a", a), _mel_rows(f"mel_align_batch: pair {k}: b", b)) for k, (a, b) in enumerate(pairs)]
+        n = len(rows)
+        widths = {r.shape[1] for ab in rows for r in ab}
+        if len(widths) > 1:
+            raise ValueError(f"mel_align_batch: the rows have different widths: {sorted(widths)}")
+        M = widths.pop() if widths else 0
+        mas, mbs = [np.empty(a.shape[0], np.int32) for a, _ in rows], [np.empty(b.shape[0], np.int32) for _, b in rows]
+        P, U = C.c_void_p * n, C.c_uint32 * n
+        st, out = p.struct, (AlignmentC * n)()
+        self._chk(fn(self.h, n, P(*[a.ctypes.data for a, _ in rows]), U(*[a.shape[0] for a, _ in rows]), P(*[b.ctypes.data for _, b in rows]),
+                     U(*[b.shape[0] for _, b in rows]), M, C.byref(st), out, P(*[x.ctypes.data for x in mas]), P(*[x.ctypes.data for x in mbs])))
+        return [Alignment(o.total, o.distance, o.path_len, ma, mb) for o, ma, mb in zip(out, mas, mbs)]
+
+    def synthesize_like(self, ids, puncts, style, T: int, ref_wav, mel=None, align=None, **controls):
+        """"say this text with the timing of that take": a fitted synthesis at capacity T gives the model's own waveform and phoneme
+        timings; its mel rows and those of ref_wav (cut to whole hops, Tb frames) come from ONE mel_wave_batch (mel: a MelAnalysis,
+        default natural-log rows); mel_align (align: an AlignParams, default normalise on) maps the model's frames to the
+        reference's; align_durations moves the phoneme boundaries onto the reference's clock; a second fitted synthesis at T = Tb
+        with those duration_frames follows it.  controls: what synthesize takes besides return_*, fitted, target_frames and a
+        phonemes duration (prosody, phonemes as a dict, volume, envelope, filter).
+        -> (wav [Tb * hop], n_frames, durations_b, alignment)"""
+        for k in controls:
+            if k.startswith("return_") or k in ("fitted", "target_frames"):
+                raise TypeError(f"synthesize_like: {k} is not a control of this call")
+        ph = controls.pop("phonemes", None)
+        if ph is not None and not isinstance(ph, dict):
+            raise TypeError(f"synthesize_like: phonemes must be a dict of arrays or None, not {type(ph).__name__}")
+        if ph and (ph.get("duration_frames") is not None or ph.get("duration_scale") is not None):
+            raise ValueError("synthesize_like: phonemes carries a duration: the reference gives the timing")
+        hop = self.hp.audio_hop_size
+        ref = np.ascontiguousarray(ref_wav, dtype=np.float32)
+        if ref.ndim != 1 or ref.size < hop:
+            raise ValueError(f"synthesize_like: ref_wav must be a 1-D array of at least one hop ({hop} samples), got shape {ref.shape}")
+        Tb = ref.size // hop
+        mel = MelAnalysis(log="ln") if mel is None else mel
+        align = AlignParams(normalise=True) if align is None else align
+        wav, nf, dur_a = self.synthesize(ids, puncts, style, T, phonemes=ph, return_durations=True, fitted=True, **controls)
+        if nf < 1:
+            raise ValueError("synthesize_like: the model's own synthesis has no frames")
+        rows_a, rows_b = self.mel_wave_batch([wav[:nf * hop], ref[:Tb * hop]], mel)
+        alignment = self.mel_align(rows_a, rows_b, align)
+        dur_b = align_durations(dur_a, alignment.map_a, Tb, lib=self.lib)
+        wav2, nf2, _ = self.synthesize(ids, puncts, style, Tb, phonemes=dict(ph or {}, duration_frames=dur_b), return_durations=True,
+                                       fitted=True, **controls)
+        return wav2, nf2, dur_b, alignment
 
     def pitch_track(self, wav, params=None) -> Pitch:
         """zv_pitch_track: the pitch track of the waveform, frames only; params: a PitchTrack or None (the defaults)"""

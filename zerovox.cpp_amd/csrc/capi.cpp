@@ -1710,6 +1710,130 @@ zv_status zv_mel_design(uint32_t sampling_rate, uint32_t num_mels, float fmin_hz
     });
 }
 
+// ---- mel alignment (zv_mel_align, zv_mel_align_batch, zv_align_durations; the rule: align.h): host rows in, per pair the path's total,
+// distance, length and maps out, eagerly, on lane 0.  A batch runs as launch groups of consecutive pairs (align_group_end), each ONE
+// launch per kernel.  I/O block of a group: [rows f32][means][two digit planes][norms][cost u32][choice u8][totals][pair table], then
+// [result rows][maps], which come back as ONE download.
+static_assert(sizeof(zv_alignment) == sizeof(zv::AlignRow) && ZV_ALIGN_MAX_FRAMES == zv::ALIGN_MAX_FRAMES, "zv_alignment is align.h's AlignRow");
+
+static void align_run(zv_model *m, const char *fn, bool batch, uint32_t n_pairs, const float *const *a, const uint32_t *Ta, const float *const *b,
+                      const uint32_t *Tb, uint32_t Mm, const zv_align *params, zv_alignment *out, int32_t *const *map_a, int32_t *const *map_b)
+{
+    if (!m) zv::fail(ZV_ERR_ARG, "%s: m is NULL", fn);
+    if (!a) zv::fail(ZV_ERR_ARG, "%s: a is NULL", fn);
+    if (!Ta) zv::fail(ZV_ERR_ARG, "%s: Ta is NULL", fn);
+    if (!b) zv::fail(ZV_ERR_ARG, "%s: b is NULL", fn);
+    if (!Tb) zv::fail(ZV_ERR_ARG, "%s: Tb is NULL", fn);
+    if (!params) zv::fail(ZV_ERR_ARG, "%s: params is NULL", fn);
+    if (!out) zv::fail(ZV_ERR_ARG, "%s: out is NULL", fn);
+    if (!n_pairs) zv::fail(ZV_ERR_ARG, "%s: n_pairs must be > 0", fn);
+    if (Mm < 1 || Mm > zv::ALIGN_MAX_MELS) zv::fail(ZV_ERR_ARG, "%s: M = %u must be in 1 .. %u", fn, Mm, zv::ALIGN_MAX_MELS);
+    char who[32] = "";
+    for (uint32_t p = 0; p < n_pairs; p++)
+    {
+        if (batch) snprintf(who, sizeof who, "pair %u: ", p);
+        if (!a[p]) zv::fail(ZV_ERR_ARG, "%s: %sa is NULL", fn, who);
+        if (!b[p]) zv::fail(ZV_ERR_ARG, "%s: %sb is NULL", fn, who);
+        if (Ta[p] < 1 || Ta[p] > zv::ALIGN_MAX_FRAMES)
+            zv::fail(ZV_ERR_ARG, "%s: %sTa = %u must be in 1 .. ZV_ALIGN_MAX_FRAMES = %u", fn, who, Ta[p], zv::ALIGN_MAX_FRAMES);
+        if (Tb[p] < 1 || Tb[p] > zv::ALIGN_MAX_FRAMES)
+            zv::fail(ZV_ERR_ARG, "%s: %sTb = %u must be in 1 .. ZV_ALIGN_MAX_FRAMES = %u", fn, who, Tb[p], zv::ALIGN_MAX_FRAMES);
+    }
+    float scale = params->scale;
+    if (const char *field = zv::align_resolve(scale, params->normalise))
+    {
+        if (!strcmp(field, "scale")) zv::fail(ZV_ERR_ARG, "%s: align scale = %g must be finite and positive (0 = %g)", fn, (double)params->scale, (double)zv::ALIGN_SCALE);
+        zv::fail(ZV_ERR_ARG, "%s: align normalise = %u must be 0 or 1", fn, params->normalise);
+    }
+    Model &M = *m->m;
+    use_lane0(m);
+    const size_t K = (size_t)zv::align_k((int)Mm);
+    std::vector<zv::AlignPair> pairs;
+    std::vector<char> back;
+    for (uint32_t g0 = 0; g0 < n_pairs;)
+    {
+        const uint32_t g1 = zv::align_group_end(g0, n_pairs, Ta, Tb), n = g1 - g0;
+        pairs.resize(n);
+        size_t rows = 0, cells = 0, maps = 0;
+        uint32_t max_ta = 0, max_tb = 0;
+        for (uint32_t k = 0; k < n; k++)
+        {
+            const uint32_t ta = Ta[g0 + k], tb = Tb[g0 + k];
+            pairs[k] = zv::AlignPair{(int32_t)ta, (int32_t)tb, (int32_t)rows, (int32_t)(rows + ta), (int32_t)maps, 0, (uint64_t)cells};
+            rows += (size_t)ta + tb;
+            maps += (size_t)ta + tb;
+            cells += (size_t)ta * tb;
+            max_ta = std::max(max_ta, ta);
+            max_tb = std::max(max_tb, tb);
+        }
+        Layout L;
+        const size_t o_x = L.at(rows * Mm * 4), o_mean = L.at((size_t)2 * n * zv::ALIGN_MAX_MELS * 4), o_hi = L.at(rows * K), o_lo = L.at(rows * K),
+                     o_norm = L.at(rows * 4), o_cost = L.at(cells * 4), o_ch = L.at(cells), o_tot = L.at((size_t)n * 8),
+                     o_pair = L.at((size_t)n * sizeof(zv::AlignPair)), o_row = L.at((size_t)n * sizeof(zv::AlignRow)), o_map = L.at(maps * 4);
+        const size_t b_back = o_map + maps * 4 - o_row;
+        char *io = (char *)M.io_scratch(L.size());
+        for (uint32_t k = 0; k < n; k++)
+        {
+            ZV_HIP(hipMemcpyAsync(io + o_x + (size_t)pairs[k].row_a * Mm * 4, a[g0 + k], (size_t)pairs[k].Ta * Mm * 4, hipMemcpyHostToDevice, M.stream()));
+            ZV_HIP(hipMemcpyAsync(io + o_x + (size_t)pairs[k].row_b * Mm * 4, b[g0 + k], (size_t)pairs[k].Tb * Mm * 4, hipMemcpyHostToDevice, M.stream()));
+        }
+        ZV_HIP(hipMemcpyAsync(io + o_pair, pairs.data(), (size_t)n * sizeof(zv::AlignPair), hipMemcpyHostToDevice, M.stream()));
+        const zv::AlignJob job{(const float *)(io + o_x), (int32_t *)(io + o_mean), (int8_t *)(io + o_hi), (int8_t *)(io + o_lo), (int32_t *)(io + o_norm),
+                               (uint32_t *)(io + o_cost), (uint8_t *)(io + o_ch), (int64_t *)(io + o_tot), (zv::AlignRow *)(io + o_row),
+                               (int32_t *)(io + o_map), (const zv::AlignPair *)(io + o_pair), (int)n, (int)max_ta, (int)max_tb, (int)Mm, scale,
+                               params->normalise};
+        M.align_launches(job, rows, cells);
+        back.resize(b_back);
+        ZV_HIP(hipMemcpyAsync(back.data(), io + o_row, b_back, hipMemcpyDeviceToHost, M.stream()));
+        M.sync();                             // (pairs and back are pageable and reused by the next group)
+        const zv::AlignRow *res = (const zv::AlignRow *)back.data();
+        const int32_t *mp = (const int32_t *)(back.data() + (o_map - o_row));
+        for (uint32_t k = 0; k < n; k++)
+        {
+            out[g0 + k] = zv_alignment{res[k].total, res[k].distance, res[k].path_len, 0};
+            if (map_a && map_a[g0 + k]) memcpy(map_a[g0 + k], mp + pairs[k].map0, (size_t)pairs[k].Ta * 4);
+            if (map_b && map_b[g0 + k]) memcpy(map_b[g0 + k], mp + pairs[k].map0 + pairs[k].Ta, (size_t)pairs[k].Tb * 4);
+        }
+        g0 = g1;
+    }
+}
+
+zv_status zv_mel_align(zv_model *m, const float *a, uint32_t Ta, const float *b, uint32_t Tb, uint32_t M, const zv_align *params,
+                       zv_alignment *out, int32_t *map_a, int32_t *map_b)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!a) zv::fail(ZV_ERR_ARG, "%s: a is NULL", fn);
+        if (!b) zv::fail(ZV_ERR_ARG, "%s: b is NULL", fn);
+        align_run(m, fn, false, 1, &a, &Ta, &b, &Tb, M, params, out, &map_a, &map_b);
+    });
+}
+
+zv_status zv_mel_align_batch(zv_model *m, uint32_t n_pairs, const float *const *a, const uint32_t *Ta, const float *const *b, const uint32_t *Tb,
+                             uint32_t M, const zv_align *params, zv_alignment *out, int32_t *const *map_a, int32_t *const *map_b)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] { align_run(m, fn, true, n_pairs, a, Ta, b, Tb, M, params, out, map_a, map_b); });
+}
+
+// The timing transfer: host only, no model, no device (align.h align_durations).
+zv_status zv_align_durations(uint32_t n, const int32_t *durations_a, uint32_t Ta, const int32_t *map_a, uint32_t Tb, int32_t *durations_b)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!durations_a) zv::fail(ZV_ERR_ARG, "%s: durations_a is NULL", fn);
+        if (!map_a) zv::fail(ZV_ERR_ARG, "%s: map_a is NULL", fn);
+        if (!durations_b) zv::fail(ZV_ERR_ARG, "%s: durations_b is NULL", fn);
+        if (!n) zv::fail(ZV_ERR_ARG, "%s: n must be > 0", fn);
+        if (!Ta || !Tb) zv::fail(ZV_ERR_ARG, "%s: Ta = %u and Tb = %u must be > 0", fn, Ta, Tb);
+        const char *field = zv::align_durations(n, durations_a, Ta, map_a, Tb, durations_b);
+        if (!field) return;
+        if (!strcmp(field, "durations_a")) zv::fail(ZV_ERR_ARG, "%s: durations_a holds a negative duration", fn);
+        if (!strcmp(field, "sum")) zv::fail(ZV_ERR_ARG, "%s: the sum of durations_a must be Ta = %u", fn, Ta);
+        zv::fail(ZV_ERR_ARG, "%s: map_a must be non-decreasing inside [0, Tb = %u)", fn, Tb);
+    });
+}
+
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)
 {
     return guarded([&] {

@@ -20,6 +20,7 @@
 #include "bands.h"        // band levels: BANDS_TILE_FRAMES, BANDS_PARAM_STRIDE, BANDS_ROW_STRIDE
 #include "filter.h"       // waveform filter: FILTER_TILE, FILTER_PARAM_STRIDE
 #include "mel.h"          // mel analysis: MEL_SLAB_STRIDE, MEL_TABLE_BYTES, the parameter block
+#include "align.h"        // mel alignment: AlignPair, AlignRow, the tiles and ALIGN_DP_ROWS
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -497,5 +498,36 @@ hipError_t launch_filter(hipStream_t s, const float *in, float *out, const uint3
 hipError_t launch_mel_frames(hipStream_t s, const float *wav, const void *table, double *slab, const uint32_t *par, const Segs &frames, int hop,
                              int num_mels);
 hipError_t launch_mel_rows(hipStream_t s, const double *slab, float *rows, const uint32_t *par, const Segs &frames, int hop, int num_mels);
+
+// ---- mel alignment (include/zerovox_amd.h "mel alignment", align.h): five passes over ONE launch group of pairs, a launch each whatever
+// the group (align.h align_plan).  pairs[n_pairs] says where a pair's rows, cells and map entries lie (AlignPair); x holds the group's
+// f32 rows [row][M], sequence after sequence.
+//   means: means[(2 pair + side) * ALIGN_MAX_MELS + c] = the rounded mean of channel c of the sequence's quantised rows, or 0 without normalise
+//   quant: the two digit planes [row][align_k(M)] of q' (16-byte aligned, zeros behind channel M) and norms[row] = the sum of q'^2
+//   cost:  cost[cell0 + i * Tb + j] = norms[a i] + norms[b j] - 2 dot, the dot product in three digit-plane sums on the i8 matrix cores
+//   dp:    choice[cell0 + i * Tb + j] = the predecessor taken (0, 1, 2; ALIGN_NONE at the first cell), totals[pair] = D of the last cell
+//   walk:  rows[pair] = total, distance and path length, maps[map0 ..] = [map_a (Ta) | map_b (Tb)]
+// No atomics, nothing to zero: every entry a pass reads was stored by the passes before it in the same run.
+struct AlignJob
+{
+    const float *x;
+    int32_t *means;
+    int8_t *hi_plane, *lo_plane;
+    int32_t *norms;
+    uint32_t *cost;
+    uint8_t *choice;
+    int64_t *totals;
+    AlignRow *rows;
+    int32_t *maps;
+    const AlignPair *pairs;
+    int n_pairs, max_ta, max_tb, M;
+    float scale;            // resolved: finite and positive
+    uint32_t normalise;
+};
+hipError_t launch_align_means(hipStream_t s, const AlignJob &j);
+hipError_t launch_align_quant(hipStream_t s, const AlignJob &j);
+hipError_t launch_align_cost(hipStream_t s, const AlignJob &j);
+hipError_t launch_align_dp(hipStream_t s, const AlignJob &j);
+hipError_t launch_align_walk(hipStream_t s, const AlignJob &j);
 
 }  // namespace zv

@@ -12,4 +12,5 @@
 #include "bands_kernels.hip"          // band levels
 #include "filter_kernels.hip"         // waveform filter
 #include "mel_kernels.hip"            // mel analysis
+#include "align_kernels.hip"          // mel alignment
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

@@ -248,6 +248,9 @@ class Model
     // the two launches of mel analysis on the lane's stream (wave_stages.cpp; kernels.h launch_mel_frames / launch_mel_rows), eager:
     // d_wav the utterances' samples by absolute frame row, d_par the call's parameter block, total_rows the rows of all segments
     void mel_launches(const float *d_wav, double *d_slab, float *d_rows, const uint32_t *d_par, const Segs &frames, size_t total_rows);
+    // the five launches of mel alignment over one launch group of pairs, likewise (kernels.h launch_align_*); rows and cells: the group's
+    // sequence rows and matrix cells, for the profile's byte and operation counts
+    void align_launches(const AlignJob &job, size_t rows, size_t cells);
 
     // scratch for host-buffer entry points (grows on demand)
     void *io_scratch(size_t bytes);

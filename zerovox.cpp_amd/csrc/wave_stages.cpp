@@ -111,4 +111,18 @@ void Model::mel_launches(const float *d_wav, double *d_slab, float *d_rows, cons
     ZV_LAUNCH("mel_rows", 8.0 * MEL_SLAB_STRIDE * rows + 4.0 * M * (rows + BANDS_BINS), 0.0, launch_mel_rows(stream(), d_slab, d_rows, d_par, frames, hop, M));
 }
 
+// Mel alignment (align.h): no stage of the chain either — the stand-alone entry points' five launches over one launch group of pairs.
+void Model::align_launches(const AlignJob &job, size_t n_rows, size_t n_cells)
+{
+    const double rows = (double)n_rows, cells = (double)n_cells, M = job.M, K = align_k(job.M);
+    // algorithmic bytes: the rows read once per pass, the planes and norms written once; the planes read once per tile row / column (an
+    // upper estimate: rows * K * 2 per 64 cells' side), a u32 per cell; dp reads it and writes a byte; the walk is the path only.
+    // Operations: 2 per 8-bit multiply-add, four digit-plane products, K channels per cell.
+    ZV_LAUNCH("align_means", job.normalise ? 4.0 * rows * M : 0.0, 0.0, launch_align_means(stream(), job));
+    ZV_LAUNCH("align_quant", 4.0 * rows * M + 2.0 * rows * K + 4.0 * rows, 0.0, launch_align_quant(stream(), job));
+    ZV_LAUNCH("align_cost", 4.0 * cells + 2.0 * 2.0 * K * cells / ALIGN_TILE, 2.0 * 4.0 * K * cells, launch_align_cost(stream(), job));
+    ZV_LAUNCH("align_dp", 5.0 * cells, 0.0, launch_align_dp(stream(), job));
+    ZV_LAUNCH("align_walk", 5.0 * rows, 0.0, launch_align_walk(stream(), job));
+}
+
 }  // namespace zv

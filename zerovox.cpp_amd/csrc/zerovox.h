@@ -169,6 +169,18 @@ class ZeroVOXModel
     // copied here, applied on the device ahead of envelope, volume and every meter; nullptr: none.  They are checked when eval() runs.
     void set_filter(const float *taps, uint32_t n_taps);
 
+    // mel alignment (include/zerovox_amd.h "mel alignment"): zv_mel_align of the rows a [Ta][M] and b [Tb][M]; params nullptr: scale 64
+    // without normalisation; the maps may be nullptr.  Next to HiFiGAN::analyze, whose rows it takes.
+    zv_alignment align(const float *a, uint32_t Ta, const float *b, uint32_t Tb, uint32_t M, const zv_align *params = nullptr,
+                       int32_t *map_a = nullptr, int32_t *map_b = nullptr);
+    // "say this with the timing of that take" for the eval() calls that follow: ref_wav (copied; its whole hops, Tb <= max_seq_len
+    // frames) is a recording at the model's rate.  eval() then runs twice, fitted: the model's own timing first; the mel rows of both
+    // waveforms (zv_mel_wave_batch, natural logarithm) are aligned (zv_mel_align with normalise), zv_align_durations moves the phoneme
+    // boundaries onto the reference's clock, and the second run takes them as duration_frames: get_num_frames() == Tb, get_durations()
+    // the new timings, get_alignment() the alignment.  nullptr: off.  It excludes per-phoneme duration_frames and a target.
+    void set_time_like(const float *ref_wav, size_t n_samples);
+    const zv_alignment &get_alignment() const { return alignment; }
+
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }
     uint32_t     get_num_frames() const { return n_frames; }
@@ -213,6 +225,8 @@ class ZeroVOXModel
     bool                 has_filter = false;
     uint32_t             filter_n = 0;
     std::vector<float>   filter_taps;
+    std::vector<float>   like_wav;
+    zv_alignment         alignment = {0, 0.0, 0, 0};
 };
 
 }  // namespace ZeroVOX

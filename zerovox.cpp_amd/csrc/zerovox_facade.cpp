@@ -222,8 +222,71 @@ void ZeroVOXModel::set_envelope(const zv_envelope *e, uint32_t n)
     envelope.phoneme_gain = nullptr;          // the gains live in env_gain
 }
 
+zv_alignment ZeroVOXModel::align(const float *a, uint32_t Ta, const float *b, uint32_t Tb, uint32_t M, const zv_align *params, int32_t *map_a,
+                                 int32_t *map_b)
+{
+    const zv_align q{};
+    zv_alignment out{};
+    chk(zv_mel_align(model, a, Ta, b, Tb, M, params ? params : &q, &out, map_a, map_b));
+    return out;
+}
+
+void ZeroVOXModel::set_time_like(const float *ref_wav, size_t n_samples)
+{
+    if (ref_wav) like_wav.assign(ref_wav, ref_wav + n_samples);
+    else like_wav.clear();
+}
+
 void ZeroVOXModel::eval(const int32_t *src_seq, const int32_t *puncts, const float *style_embed, uint32_t num_phonemes)
 {
+    if (!like_wav.empty())
+    {
+        // the two runs of set_time_like: this function again, with the reference put aside
+        const size_t hop = hparams.audio_hop_size, Tb = like_wav.size() / hop;
+        if (!pc_frames.empty() || target_frames) throw zv::Error(ZV_ERR_ARG, "set_time_like: the reference gives the timing, duration_frames and a target exclude it");
+        if (Tb < 1 || Tb > hparams.max_seq_len)
+            throw zv::Error(ZV_ERR_ARG, "set_time_like: the reference holds " + std::to_string(Tb) + " frames, 1 .. max_seq_len = " +
+                                            std::to_string(hparams.max_seq_len) + " are needed");
+        std::vector<float> ref;
+        ref.swap(like_wav);
+        const bool was_fitted = fitted, had_phonemes = has_phonemes, recorded = record_durations;
+        auto restore = [&] {
+            like_wav.swap(ref);
+            fitted = was_fitted, has_phonemes = had_phonemes, record_durations = recorded;
+            pc_frames.clear();
+            if (!had_phonemes) pc_n = 0;
+        };
+        try
+        {
+            fitted = true;
+            record_durations = true;
+            eval(src_seq, puncts, style_embed, num_phonemes);
+            const uint32_t Ta = n_frames, M = hparams.audio_num_mels;
+            if (!Ta) throw zv::Error(ZV_ERR_ARG, "set_time_like: the model's own synthesis has no frames");
+            std::vector<float> rows_a((size_t)Ta * M), rows_b(Tb * M);
+            zv_mel mq{};
+            mq.log = 1;
+            const float *wavs[2] = {wav, ref.data()};
+            const uint32_t Ts[2] = {Ta, (uint32_t)Tb};
+            float *outs[2] = {rows_a.data(), rows_b.data()};
+            chk(zv_mel_wave_batch(model, 2, wavs, Ts, &mq, outs));
+            const zv_align aq{0.0f, 1};
+            std::vector<int32_t> map_a(Ta), frames(num_phonemes);
+            alignment = align(rows_a.data(), Ta, rows_b.data(), (uint32_t)Tb, M, &aq, map_a.data(), nullptr);
+            chk(zv_align_durations(num_phonemes, durations.data(), Ta, map_a.data(), (uint32_t)Tb, frames.data()));
+            pc_frames = frames;
+            has_phonemes = true;
+            pc_n = num_phonemes;
+            eval(src_seq, puncts, style_embed, num_phonemes);
+        }
+        catch (...)
+        {
+            restore();
+            throw;
+        }
+        restore();
+        return;
+    }
     if (has_envelope && env_gain_set && env_gain.size() != num_phonemes)
         throw zv::Error(ZV_ERR_ARG, "set_envelope: gains for " + std::to_string(env_gain.size()) + " phonemes, eval() has " +
                                         std::to_string(num_phonemes));

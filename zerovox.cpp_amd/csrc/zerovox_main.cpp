@@ -71,6 +71,16 @@
 //            weights) of a mono PCM16 RIFF file at the model's rate — what zv_write_wav writes — as raw f32 [frames][mel channels], and /
 //            or the vocoder's waveform of those rows.  A file at another rate or with more channels is an error by name; nothing is
 //            resampled.  The mel flags without --analyze, or --analyze without an output, are usage errors.
+//   --align A.f32 B.f32, --mel-width M, --align-scale S, --align-normalise, --map-out FILE
+//            mel alignment (include/zerovox_amd.h "mel alignment") in place of synthesis: the dynamic-time-warping path between two
+//            files of raw f32 rows [frames][M] (what --mel-out writes), printed as total, path length and distance; --map-out writes
+//            the two frame maps as TSV.  --mel-width is required (1 .. 256); a file that cannot be opened, holds no whole rows or more
+//            than 4 096 of them is an error by name ahead of the checkpoint.  The other four flags without --align are usage errors.
+//   --time-like REF.wav
+//            with the synthesis flags: the utterance with the timing of the reference, a mono PCM16 RIFF file at the model's rate.
+//            The utterance is synthesised (fitted), its mel rows are aligned to the reference's, the phoneme boundaries move onto the
+//            reference's clock and the utterance is synthesised again with those durations; the reference's whole hops are written.
+//            It excludes --align, --analyze, --phoneme-controls and the two targets.
 //   --info   list the checkpoint's tensors (name, type, shape), then exit (no GPU needed)
 //   --plan   print the frame count of every utterance of the -u file (which may then hold several, three lines each) without decoding
 //            or vocoding, one line each: index n_phonemes n_frames seconds; the prosody flags apply to every utterance, then exit
@@ -103,6 +113,8 @@ static void usage(FILE *f)
                "               [--eq-gain-db g0,g1,...] [--eq-edges-hz a,b,c,...] [--eq-taps L] [--filter-taps FILE]\n"
                "       zerovox -m model.gguf --analyze in.wav [--mel-out rows.f32] [--resynth out.wav]\n"
                "               [--mel-fmin HZ] [--mel-fmax HZ] [--mel-centre SAMPLE] [--mel-pad reflect|zero]\n"
+               "       zerovox -m model.gguf --align a.f32 b.f32 --mel-width M [--align-scale S] [--align-normalise] [--map-out map.tsv]\n"
+               "       zerovox ... --time-like ref.wav   (with the synthesis flags)\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
                "  --duration-scale S   every phoneme's duration times S (0 < S <= 16; 2 = twice as slow), default 1\n"
@@ -141,7 +153,13 @@ static void usage(FILE *f)
                "  --analyze IN.wav     no synthesis: the log-mel rows (natural logarithm) of a mono PCM16 file at the model's rate, with\n"
                "                       --mel-out FILE (raw f32 [frames][mel channels]) and / or --resynth OUT.wav (the vocoder's waveform of them);\n"
                "                       --mel-fmin HZ, --mel-fmax HZ (default 0 .. Nyquist), --mel-centre SAMPLE (0 .. hop - 1, default 0),\n"
-               "                       --mel-pad reflect|zero (default reflect)\n",
+               "                       --mel-pad reflect|zero (default reflect)\n"
+               "  --align A.f32 B.f32  no synthesis: the dynamic-time-warping path between two files of raw f32 rows [frames][M] (--mel-out's\n"
+               "                       format); prints total, path length and distance.  --mel-width M (1 .. 256, required), --align-scale S\n"
+               "                       (steps per unit of the rows, default 64), --align-normalise (remove every channel's mean per file),\n"
+               "                       --map-out FILE (TSV: side index frame, the first frame of the other file on the path)\n"
+               "  --time-like REF.wav  synthesise with the timing of REF.wav (mono PCM16 at the model's rate): the phoneme boundaries of a\n"
+               "                       first synthesis are moved onto the reference's clock along the alignment of the two mels\n",
             k_default_model, k_default_out);
 }
 
@@ -325,18 +343,19 @@ static int plan(const std::string &model_path, const std::string &utt_path, cons
 // count) as raw little-endian f32 [T][num_mels] in --mel-out, and with --resynth OUT.wav the vocoder's waveform of those rows.  The
 // file must be what zv_write_wav writes: mono PCM16 RIFF at the model's rate; anything else is an error by name, nothing is resampled.
 // Samples behind the last whole hop are dropped.
-static int analyze(const std::string &model_path, const std::string &in_path, const std::string &mel_path, const std::string &resynth_path,
-                   const zv_mel &q)
+// a mono PCM16 RIFF file's samples as floats (what zv_write_wav writes), refused by the flag's name otherwise
+static std::vector<float> read_pcm16(const std::string &flag, const std::string &in_path, uint32_t &rate)
 {
     std::ifstream f(in_path, std::ios::binary);
-    if (!f) throw std::runtime_error("--analyze: cannot open '" + in_path + "'");
+    if (!f) throw std::runtime_error(flag + ": cannot open '" + in_path + "'");
     const std::vector<unsigned char> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
     auto u16 = [&](size_t o) { return (uint32_t)b[o] | (uint32_t)b[o + 1] << 8; };
     auto u32 = [&](size_t o) { return u16(o) | u16(o + 2) << 16; };
     if (b.size() < 12 || memcmp(b.data(), "RIFF", 4) != 0 || memcmp(b.data() + 8, "WAVE", 4) != 0)
-        throw std::runtime_error("--analyze: '" + in_path + "' is not a RIFF/WAVE file");
-    uint32_t format = 0, channels = 0, rate = 0, bits = 0;
+        throw std::runtime_error(flag + ": '" + in_path + "' is not a RIFF/WAVE file");
+    uint32_t format = 0, channels = 0, bits = 0;
     size_t data = 0, data_bytes = 0;
+    rate = 0;
     for (size_t o = 12; o + 8 <= b.size();)
     {
         const size_t n = u32(o + 4), body = o + 8;
@@ -349,9 +368,19 @@ static int analyze(const std::string &model_path, const std::string &in_path, co
         }
         o = body + n + (n & 1);
     }
-    if (!rate || !data) throw std::runtime_error("--analyze: '" + in_path + "' has no fmt or no data chunk");
-    if (format != 1 || bits != 16) throw std::runtime_error("--analyze: '" + in_path + "' is not 16-bit PCM (format " + std::to_string(format) + ", " + std::to_string(bits) + " bits)");
-    if (channels != 1) throw std::runtime_error("--analyze: '" + in_path + "' has " + std::to_string(channels) + " channels, mono is needed");
+    if (!rate || !data) throw std::runtime_error(flag + ": '" + in_path + "' has no fmt or no data chunk");
+    if (format != 1 || bits != 16) throw std::runtime_error(flag + ": '" + in_path + "' is not 16-bit PCM (format " + std::to_string(format) + ", " + std::to_string(bits) + " bits)");
+    if (channels != 1) throw std::runtime_error(flag + ": '" + in_path + "' has " + std::to_string(channels) + " channels, mono is needed");
+    std::vector<float> x(data_bytes / 2);
+    for (size_t i = 0; i < x.size(); i++) x[i] = (float)(int16_t)u16(data + 2 * i) / 32768.0f;
+    return x;
+}
+
+static int analyze(const std::string &model_path, const std::string &in_path, const std::string &mel_path, const std::string &resynth_path,
+                   const zv_mel &q)
+{
+    uint32_t rate = 0;
+    const std::vector<float> pcm = read_pcm16("--analyze", in_path, rate);
     zv_model *m = nullptr;
     if (zv_model_load(model_path.c_str(), 0, &m) != ZV_OK) throw std::runtime_error(zv_last_error());
     struct Free { zv_model *m; ~Free() { zv_model_free(m); } } free_model{m};
@@ -359,11 +388,10 @@ static int analyze(const std::string &model_path, const std::string &in_path, co
     if (zv_model_get_hparams(m, &hp) != ZV_OK) throw std::runtime_error(zv_last_error());
     if (rate != hp.audio_sampling_rate)
         throw std::runtime_error("--analyze: '" + in_path + "' is at " + std::to_string(rate) + " Hz, the model at " + std::to_string(hp.audio_sampling_rate) + " Hz (nothing is resampled)");
-    const size_t T = data_bytes / 2 / hp.audio_hop_size;
+    const size_t T = pcm.size() / hp.audio_hop_size;
     if (T == 0 || T > zv_max_frames(m))
         throw std::runtime_error("--analyze: '" + in_path + "' holds " + std::to_string(T) + " frames of " + std::to_string(hp.audio_hop_size) + " samples, 1 .. " + std::to_string(zv_max_frames(m)) + " are needed");
-    std::vector<float> wav(T * hp.audio_hop_size), mel(T * hp.audio_num_mels);
-    for (size_t i = 0; i < wav.size(); i++) wav[i] = (float)(int16_t)u16(data + 2 * i) / 32768.0f;
+    std::vector<float> wav(pcm.begin(), pcm.begin() + T * hp.audio_hop_size), mel(T * hp.audio_num_mels);
     if (zv_mel_wave(m, wav.data(), (uint32_t)T, &q, mel.data()) != ZV_OK) throw std::runtime_error(zv_last_error());
     if (!mel_path.empty())
     {
@@ -380,8 +408,50 @@ static int analyze(const std::string &model_path, const std::string &in_path, co
     return 0;
 }
 
+// --align A.f32 B.f32: the files' rows, checked ahead of the checkpoint; then zv_mel_align and the printout
+static std::vector<float> read_rows(const std::string &path, uint32_t width)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("--align: cannot open '" + path + "'");
+    const std::vector<char> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    const size_t row = (size_t)width * 4;
+    if (b.empty() || b.size() % row)
+        throw std::runtime_error("--align: '" + path + "' holds " + std::to_string(b.size()) + " bytes, not whole rows of " + std::to_string(width) + " f32 values");
+    if (b.size() / row > ZV_ALIGN_MAX_FRAMES)
+        throw std::runtime_error("--align: '" + path + "' holds " + std::to_string(b.size() / row) + " rows, 1 .. " + std::to_string(ZV_ALIGN_MAX_FRAMES) + " are needed");
+    std::vector<float> x(b.size() / 4);
+    memcpy(x.data(), b.data(), b.size());
+    return x;
+}
+
+static int align_files(const std::string &model_path, const std::string &a_path, const std::string &b_path, uint32_t width, const zv_align &q,
+                       const std::string &map_path)
+{
+    const std::vector<float> a = read_rows(a_path, width), b = read_rows(b_path, width);
+    const uint32_t Ta = (uint32_t)(a.size() / width), Tb = (uint32_t)(b.size() / width);
+    ZeroVOX::ZeroVOXModel model(model_path);
+    std::vector<int32_t> map_a(Ta), map_b(Tb);
+    const zv_alignment r = model.align(a.data(), Ta, b.data(), Tb, width, &q, map_a.data(), map_b.data());
+    printf("%s (%u rows) against %s (%u rows), %u channels: total %llu path_len %u distance %.17g\n", a_path.c_str(), Ta, b_path.c_str(), Tb, width,
+           (unsigned long long)r.total, r.path_len, r.distance);
+    if (!map_path.empty())
+    {
+        FILE *mf = fopen(map_path.c_str(), "w");
+        if (!mf) throw std::runtime_error("--map-out: cannot open '" + map_path + "' for writing");
+        fprintf(mf, "side\tindex\tframe\n");
+        for (uint32_t i = 0; i < Ta; i++) fprintf(mf, "a\t%u\t%d\n", i, map_a[i]);
+        for (uint32_t j = 0; j < Tb; j++) fprintf(mf, "b\t%u\t%d\n", j, map_b[j]);
+        if (fclose(mf) != 0) throw std::runtime_error("short write to '" + map_path + "'");
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    std::string align_a, align_b, map_path, like_path;         // --align, --map-out, --time-like
+    zv_align align_q{};                                        // --align-scale, --align-normalise
+    long mel_width = 0;                                        // --mel-width
+    bool align_flag = false;
     std::string analyze_path, melout_path, resynth_path;      // --analyze, --mel-out, --resynth
     zv_mel mel_q{};                                            // --mel-fmin, --mel-fmax, --mel-centre, --mel-pad
     mel_q.log = 1;
@@ -481,6 +551,39 @@ int main(int argc, char **argv)
         }
         else if (a == "--filter-taps") taps_path = need("--filter-taps");
         else if (a == "--analyze") analyze_path = need("--analyze");
+        else if (a == "--align")
+        {
+            if (i + 2 >= argc) { fprintf(stderr, "zerovox: --align needs two files\n"); usage(stderr); return 2; }
+            align_a = argv[++i];
+            align_b = argv[++i];
+        }
+        else if (a == "--mel-width")
+        {
+            const std::string v = need("--mel-width");
+            char *end = nullptr;
+            mel_width = strtol(v.c_str(), &end, 10);
+            if (v.empty() || end != v.c_str() + v.size() || mel_width < 1 || mel_width > 256)
+            {
+                fprintf(stderr, "zerovox: --mel-width: '%s' is not a channel count of 1 .. 256\n", v.c_str());
+                usage(stderr);
+                return 2;
+            }
+            align_flag = true;
+        }
+        else if (a == "--align-scale")
+        {
+            align_q.scale = parse_flag_float("--align-scale", need("--align-scale"));
+            if (!(align_q.scale > 0.0f))
+            {
+                fprintf(stderr, "zerovox: --align-scale must be positive\n");
+                usage(stderr);
+                return 2;
+            }
+            align_flag = true;
+        }
+        else if (a == "--align-normalise") align_q.normalise = 1, align_flag = true;
+        else if (a == "--map-out") map_path = need("--map-out"), align_flag = true;
+        else if (a == "--time-like") like_path = need("--time-like");
         else if (a == "--mel-out") melout_path = need("--mel-out"), mel_flag = true;
         else if (a == "--resynth") resynth_path = need("--resynth"), mel_flag = true;
         else if (a == "--mel-fmin") mel_q.fmin_hz = parse_flag_float("--mel-fmin", need("--mel-fmin")), mel_flag = true;
@@ -638,6 +741,24 @@ int main(int argc, char **argv)
         usage(stderr);
         return 2;
     }
+    if (align_flag && align_a.empty())
+    {
+        fprintf(stderr, "zerovox: --mel-width, --align-scale, --align-normalise and --map-out need --align A.f32 B.f32\n");
+        usage(stderr);
+        return 2;
+    }
+    if (!align_a.empty() && !mel_width)
+    {
+        fprintf(stderr, "zerovox: --align needs --mel-width M\n");
+        usage(stderr);
+        return 2;
+    }
+    if (!like_path.empty() && (!align_a.empty() || !analyze_path.empty() || !pc_path.empty() || target_frames > 0 || target_seconds > 0.0))
+    {
+        fprintf(stderr, "zerovox: --time-like and --align, --analyze, --phoneme-controls, --target-frames, --target-seconds exclude each other\n");
+        usage(stderr);
+        return 2;
+    }
     if (!band_hz.empty() && bands_path.empty() && pbands_path.empty())
     {
         fprintf(stderr, "zerovox: --band-edges-hz needs --bands FILE or --phoneme-bands FILE\n");
@@ -716,6 +837,10 @@ int main(int argc, char **argv)
 
         if (planning) return plan(model_path, utt_path, controlled ? &prosody : nullptr);
         if (!analyze_path.empty()) return analyze(model_path, analyze_path, melout_path, resynth_path, mel_q);
+        if (!align_a.empty()) return align_files(model_path, align_a, align_b, (uint32_t)mel_width, align_q, map_path);
+        std::vector<float> like_wav;                            // --time-like, read ahead of the checkpoint
+        uint32_t like_rate = 0;
+        if (!like_path.empty()) like_wav = read_pcm16("--time-like", like_path, like_rate);
 
         // per-phoneme controls and timings: the file is checked against the utterance before the model is loaded
         std::vector<int32_t> ids0;
@@ -802,6 +927,14 @@ int main(int argc, char **argv)
         }
         else if (!align_path.empty())
             model.set_phoneme_controls(nullptr, (uint32_t)ids0.size());        // timings only
+        if (!like_path.empty())
+        {
+            if (like_rate != hp.audio_sampling_rate)
+                throw std::runtime_error("--time-like: '" + like_path + "' is at " + std::to_string(like_rate) + " Hz, the model at " +
+                                         std::to_string(hp.audio_sampling_rate) + " Hz (nothing is resampled)");
+            model.set_time_like(like_wav.data(), like_wav.size());
+            fit = true;                                         // the reference's whole hops are what is written
+        }
         if (utt_path.empty())
             model.eval();
         else
@@ -824,6 +957,11 @@ int main(int argc, char **argv)
         }
 
         const uint32_t nf = model.get_num_frames();
+        if (!like_path.empty())
+        {
+            const zv_alignment &al = model.get_alignment();
+            printf("time-like: %u frames, alignment total %llu path_len %u distance %.9g\n", nf, (unsigned long long)al.total, al.path_len, al.distance);
+        }
         if (leveled)
         {
             const zv_level &lv = model.get_level();
