@@ -27,6 +27,9 @@
  *                      them in one launch per kernel; zv_mel_design: Slaney mel weights, on the host
  *   zv_mel_align       the dynamic-time-warping path between two sequences of mel rows: its spectral distance and the frame maps;
  *                      zv_mel_align_batch: a batch of pairs in one launch per kernel; zv_align_durations: the timing transfer, on the host
+ *   zv_loudness_wave   the BS.1770 loudness (LUFS) and true peak (dBTP) of any waveform the caller brings, and the waveform brought to a
+ *                      LUFS target under a dBTP ceiling; zv_loudness_wave_batch: a batch of them in one launch per kernel;
+ *                      zv_loudness_design: the K-weighting filters, the step and the interpolator for a rate, on the host
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file       src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -871,6 +874,92 @@ zv_status zv_mel_align_batch(zv_model *m, uint32_t n_pairs, const float *const *
                              int32_t *const *map_a /* array or entries may be NULL */, int32_t *const *map_b);
 zv_status zv_align_durations(uint32_t n, const int32_t *durations_a, uint32_t Ta, const int32_t *map_a, uint32_t Tb,
                              int32_t *durations_b);
+/* ---- loudness: ITU-R BS.1770 integrated loudness, true peak and normalisation -------------------------------------------------------------
+ * Delivery specifications speak LUFS and dBTP ("-16 LUFS integrated, -1 dBTP"), not the RMS and sample peak of the volume controls.
+ * zv_loudness_wave takes a host waveform of T frames (T * hop samples at the model's rate), measures its first N = min(n_frames, T) * hop
+ * samples and, where out is given, returns all T * hop samples scaled by ONE gain: exactly the volume controls' division of labour.
+ * zv_loudness_wave_batch takes n_utt of them, one launch per kernel per launch group of consecutive utterances (at most 2^26 samples,
+ * capacities rounded up to 256); utterance u receives exactly the bits of its single call.  Both run eagerly on lane 0 like
+ * zv_mel_wave_batch, are never part of a captured graph or of the zv_synthesize* chain, and use scratch of lane 0's arena.
+ * zv_loudness_design is host only and needs neither a model nor a device.
+ *
+ * THE RULE.  Every f64 step is ONE IEEE operation (nothing is contracted into a fused multiply-add), denormals are kept, a sample that is not finite
+ * counts as +0.0: x'_n, n in [0, N); x' is +0.0 outside.  Nothing depends on how the work is split, because the rule fixes the split.
+ *   1. design (f64, on the host; the kernels take it as data).  With K = tan(pi f0 / fs):
+ *        shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G/20), Vb = Vh^0.4996667741545416,
+ *                   a0 = 1 + K/Q + K^2, b0 = (Vh + Vb K/Q + K^2)/a0, b1 = 2 (K^2 - Vh)/a0, b2 = (Vh - Vb K/Q + K^2)/a0,
+ *                   a1 = 2 (K^2 - 1)/a0, a2 = (1 - K/Q + K^2)/a0
+ *        high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773, b = (1, -2, 1), a1' and a2' by the same two formulas
+ *      (at 48 000 Hz the standard's table).  step = (fs + 5) / 10 samples.  M = A^256 by eight squarings P <- P P, every entry the
+ *      chain acc <- fma(P[i][k], P[k][j], acc), k = 0 .. 3 from +0.0 (four fused multiply-adds, written out; the one place besides
+ *      step 4 where a product is not rounded on its own), where A is the zero-input transition of the cascade
+ *      below on (p1, p2, q1, q2): rows (-a1, 1, 0, 0), (-a2, 0, 0, 0), (-2 - a1', 0, -a1', 1), (1 - a2', 0, -a2', 0).
+ *      interp[j] = (float)(sinc((j - 24)/4) * 0.5 (1 - cos(2 pi j / 48))), j = 0 .. 48, entries with |.| < 1e-6 set to 0.
+ *      sampling_rate must lie in 4 000 .. 768 000 (a step holds a chunk; the shelf lies below Nyquist).
+ *   2. K-weighting in chunks of 256 samples; chunk k covers x'[256 k .. 256 k + 256), k < ceil(N / 256).  One sample through the
+ *      cascade (transposed direct form II), state (p1, p2, q1, q2):
+ *        y = b0 x + p1;   p1 <- (b1 x + p2) - a1 y;   p2 <- b2 x - a2 y;
+ *        w = y + q1;      q1 <- (q2 - 2 y) - a1' w;   q2 <- y - a2' w            (y, w from the OLD state; every product, sum and
+ *      difference rounded on its own)
+ *      A: z_k = the state after chunk k run from the zero state.
+ *      B: s_0 = 0, s_(k+1)[r] = (((M[r][0] s_k[0] + M[r][1] s_k[1]) + M[r][2] s_k[2]) + M[r][3] s_k[3]) + z_k[r], r = 0 .. 3, in k.
+ *      C: chunk k run again from s_k; its outputs w are squared and added in ascending sample order, from +0.0, into the chunk's two
+ *         RUN sums: run 0 takes the samples n < e, run 1 those from e on, e = (256 k / step + 1) * step (integer division): the
+ *         intersections of the chunk with the 100 ms steps it meets.
+ *      D: E_j, j < J = N / step (whole steps only) = +0.0 plus the runs of step j, chunk after chunk in ascending order.
+ *   3. gating.  Momentary block i, 0 <= i <= J - 4: z_i = (((E_i + E_(i+1)) + E_(i+2)) + E_(i+3)) / (double)(4 step).  Absolute gate
+ *      z_i > Ga, Ga the f64 with the bits 0x3e7f791ec6e1d5aa (10^((-70 + 0.691)/10)); Gr = 0.1 * (sum / (double)count) over the blocks
+ *      past Ga; integrated = sum / (double)count over the blocks with z_i > Ga and z_i > Gr; both sums start at +0.0 and run in
+ *      ascending i.  momentary_max = max z_i.  Short-term block i, i + 30 <= J: (+0.0 + E_i + ... + E_(i+29), ascending) /
+ *      (double)(30 step); short_term_max their maximum.  No block, or none past the gates: mean square 0, LUFS -inf, a target does nothing.
+ *   4. true peak.  For f = 1, 2, 3 and n = 0 .. N + 10: v = the chain acc <- acc + (double)interp[f + 4 k] * x'_(n - k), k = 0 .. 11
+ *      ascending from +0.0 (the products are exact).  true_peak = the maximum of all |v| and of (double)sample_peak; sample_peak the
+ *      largest finite |x_n|, n < N.
+ *   5. gain.  zt = 10^(((double)target_lufs + 0.691) / 10) (the host's pow).  gd = (double)gain; with the target on and integrated > 0:
+ *      gd = sqrt(zt / integrated) * (double)gain; with the ceiling on and gd * true_peak > (double)ceiling: gd = (double)ceiling /
+ *      true_peak; g = (float)gd; where the ceiling applied, g steps one bit pattern towards 0 while (float)((double)g * true_peak) >
+ *      ceiling (at most four times).  out[i] = wav[i] * g, one f32 multiply, for all T * hop samples.
+ *   6. report.  lufs(z) = (float)(-0.691 + 10 * (L(z) * log10 e)) with L the fixed-sequence logarithm of the mel analysis (above), -inf
+ *      for z below 2^-1022; true_peak_dbtp = (float)(20 * (L(tp) * log10 e)) likewise.
+ * csrc/loudness.h holds the rule as plain C++ with a host reference, loud_reference(); tests/loudness_rule.py restates it in numpy.
+ *
+ * Arguments: every field finite; gain in [0, 1000]; flags within bits 0 and 1; with bit 0 target_lufs in [-70, 0]; with bit 1
+ * true_peak_ceiling in (0, 1] (linear: -1 dBTP is 10^(-1/20)); 0 < T <= zv_max_frames(); n_frames beyond T counts as T.  ask == NULL is the
+ * identity for every utterance; out == NULL (or a NULL entry) meters only and changes nothing in the result.
+ * Not covered: loudness range (LRA); channel weights (mono); resampling; a stage of the zv_synthesize* chain or a captured graph. */
+#define ZV_LOUDNESS_TARGET  1u
+#define ZV_LOUDNESS_CEILING 2u
+typedef struct
+{
+    float    gain;                  /* linear, applied with or without a target */
+    float    target_lufs;           /* bit 0 of flags */
+    float    true_peak_ceiling;     /* linear, bit 1 of flags */
+    uint32_t flags;
+} zv_loudness;                      /* identity: {1, 0, 0, 0} */
+typedef struct
+{
+    double   integrated_ms, momentary_max_ms, short_term_max_ms;     /* mean squares of the K-weighted signal */
+    double   true_peak;             /* linear */
+    uint32_t blocks, blocks_absolute, blocks_gated;      /* 400 ms blocks: all, past the absolute gate, past both gates */
+    float    sample_peak;
+    float    integrated_lufs, momentary_max_lufs, short_term_max_lufs, true_peak_dbtp;
+    float    gain;                  /* applied to out */
+    uint32_t reserved;
+} zv_loudness_result;
+typedef struct
+{
+    double   shelf_b[3], shelf_a[2];            /* b0 b1 b2, a1 a2 */
+    double   highpass_b[3], highpass_a[2];
+    double   M[16];                             /* row major */
+    float    interp[49];
+    uint32_t step;
+} zv_loudness_filter;
+zv_status zv_loudness_design(uint32_t sampling_rate, zv_loudness_filter *out);
+zv_status zv_loudness_wave(zv_model *m, const float *wav, uint32_t T, uint32_t n_frames, const zv_loudness *ask, zv_loudness_result *res,
+                           float *out /* [T * hop] or NULL: meter only */);
+zv_status zv_loudness_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint32_t *T,
+                                 const uint32_t *n_frames /* NULL = T */, const zv_loudness *ask /* [n_utt] or NULL */,
+                                 zv_loudness_result *res /* [n_utt] */, float *const *out /* array or entries may be NULL */);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

@@ -35,6 +35,7 @@ SYMBOLS = [
     "zv_encode_batch", "zv_decode_batch", "zv_vocode_batch", "zv_vocode_batch_begin", "zv_vocode_batch_end",
     "zv_mel_wave", "zv_mel_wave_batch", "zv_mel_design",
     "zv_mel_align", "zv_mel_align_batch", "zv_align_durations",
+    "zv_loudness_wave", "zv_loudness_wave_batch", "zv_loudness_design",
 ]
 
 
@@ -534,6 +535,95 @@ def align_durations(durations_a, map_a, Tb: int, lib=None) -> np.ndarray:
     return db
 
 
+class LoudnessC(C.Structure):
+    """zv_loudness of include/zerovox_amd.h (the identity is {1, 0, 0, 0})"""
+    _fields_ = [("gain", C.c_float), ("target_lufs", C.c_float), ("true_peak_ceiling", C.c_float), ("flags", C.c_uint32)]
+
+
+class LoudnessResultC(C.Structure):
+    """zv_loudness_result of include/zerovox_amd.h"""
+    _fields_ = [("integrated_ms", C.c_double), ("momentary_max_ms", C.c_double), ("short_term_max_ms", C.c_double), ("true_peak", C.c_double),
+                ("blocks", C.c_uint32), ("blocks_absolute", C.c_uint32), ("blocks_gated", C.c_uint32), ("sample_peak", C.c_float),
+                ("integrated_lufs", C.c_float), ("momentary_max_lufs", C.c_float), ("short_term_max_lufs", C.c_float),
+                ("true_peak_dbtp", C.c_float), ("gain", C.c_float), ("reserved", C.c_uint32)]
+
+
+class LoudnessFilterC(C.Structure):
+    """zv_loudness_filter of include/zerovox_amd.h"""
+    _fields_ = [("shelf_b", C.c_double * 3), ("shelf_a", C.c_double * 2), ("highpass_b", C.c_double * 3), ("highpass_a", C.c_double * 2),
+                ("M", C.c_double * 16), ("interp", C.c_float * 49), ("step", C.c_uint32)]
+
+
+class Loudness:
+    """What a loudness call asks for (include/zerovox_amd.h "loudness"): a linear gain, a target in LUFS (None: none) and a true-peak
+    ceiling, linear in (0, 1] (None: none).  from_lufs takes the ceiling in dBTP.  The library checks the values."""
+    TARGET, CEILING = 1, 2
+
+    def __init__(self, gain: float = 1.0, target_lufs=None, true_peak_ceiling=None):
+        self.gain = float(gain)
+        self.target_lufs = None if target_lufs is None else float(target_lufs)
+        self.true_peak_ceiling = None if true_peak_ceiling is None else float(true_peak_ceiling)
+
+    @classmethod
+    def from_lufs(cls, target: float, true_peak_dbtp=None, gain: float = 1.0):
+        """-16 LUFS under -1 dBTP: Loudness.from_lufs(-16.0, true_peak_dbtp=-1.0); the ceiling becomes float32(10^(dBTP / 20))"""
+        return cls(gain, target, None if true_peak_dbtp is None else float(np.float32(10.0 ** (float(true_peak_dbtp) / 20.0))))
+
+    @property
+    def struct(self) -> LoudnessC:
+        flags = (self.TARGET if self.target_lufs is not None else 0) | (self.CEILING if self.true_peak_ceiling is not None else 0)
+        return LoudnessC(self.gain, self.target_lufs or 0.0, self.true_peak_ceiling or 0.0, flags)
+
+    def __repr__(self):
+        return f"Loudness(gain={self.gain}, target_lufs={self.target_lufs}, true_peak_ceiling={self.true_peak_ceiling})"
+
+
+class LoudnessResult:
+    """What a loudness call measured: the float64 mean squares (integrated_ms, momentary_max_ms, short_term_max_ms), true_peak (linear,
+    float64), the block counts (blocks, blocks_absolute, blocks_gated), sample_peak and the four readings as float32
+    (integrated_lufs, momentary_max_lufs, short_term_max_lufs, true_peak_dbtp), and the gain that was applied"""
+    FIELDS = tuple(n for n, _ in LoudnessResultC._fields_ if n != "reserved")
+
+    def __init__(self, c: LoudnessResultC):
+        for n in self.FIELDS:
+            v = getattr(c, n)
+            setattr(self, n, np.float32(v) if dict(LoudnessResultC._fields_)[n] is C.c_float else v)
+
+    def __repr__(self):
+        return "LoudnessResult(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.FIELDS) + ")"
+
+
+class LoudnessFilter:
+    """zv_loudness_design's result: shelf_b, shelf_a, highpass_b, highpass_a and M (row major, 16) as lists of floats, c float32 [49]
+    (the interpolator) and step"""
+
+    def __init__(self, c: LoudnessFilterC):
+        self.shelf_b, self.shelf_a, self.highpass_b, self.highpass_a, self.M = (list(getattr(c, n)) for n in
+                                                                                 ("shelf_b", "shelf_a", "highpass_b", "highpass_a", "M"))
+        self.c = np.array(list(c.interp), np.float32)
+        self.step = int(c.step)
+
+
+def loudness_design(sampling_rate: int, lib=None) -> LoudnessFilter:
+    """zv_loudness_design: the K-weighting biquads, the gating step, M = A^256 and the true-peak interpolator for a sampling rate.
+    Host only: no model, no device."""
+    lib = lib or load_library()
+    fn = _stage_symbol(lib, "zv_loudness_design")
+    if isinstance(sampling_rate, (bool, np.bool_)) or not isinstance(sampling_rate, (int, np.integer)) or not 0 <= sampling_rate <= 0xffffffff:
+        raise ValueError(f"loudness_design: sampling_rate = {sampling_rate!r} must be an integer in [0, 4294967295]")
+    out = LoudnessFilterC()
+    st = fn(int(sampling_rate), C.byref(out))
+    if st != 0:
+        raise ZvError(st, lib.zv_last_error().decode("utf-8", "replace"))
+    return LoudnessFilter(out)
+
+
+def _loudness_ask(who: str, ask):
+    if ask is not None and not isinstance(ask, Loudness):
+        raise TypeError(f"{who}: ask must be a Loudness or None, not {type(ask).__name__}")
+    return ask
+
+
 class EnvelopeC(C.Structure):
     """zv_envelope of include/zerovox_amd.h: the gains' pointer ([n] or NULL) and three integers (a zeroed struct is the identity)"""
     _fields_ = [("phoneme_gain", C.c_void_p), ("ramp_frames", C.c_uint32), ("fade_in_samples", C.c_uint32),
@@ -799,7 +889,10 @@ def _bind(lib):
                            ("zv_mel_design", [u32, u32, C.c_float, C.c_float, fp]),
                            ("zv_mel_align", [vp, fp, u32, fp, u32, u32, C.POINTER(AlignC), C.POINTER(AlignmentC), vp, vp]),
                            ("zv_mel_align_batch", [vp, u32, pvp, pu32, pvp, pu32, u32, C.POINTER(AlignC), C.POINTER(AlignmentC), pvp, pvp]),
-                           ("zv_align_durations", [u32, vp, u32, vp, u32, vp])):
+                           ("zv_align_durations", [u32, vp, u32, vp, u32, vp]),
+                           ("zv_loudness_wave", [vp, fp, u32, u32, C.POINTER(LoudnessC), C.POINTER(LoudnessResultC), fp]),
+                           ("zv_loudness_wave_batch", [vp, u32, pvp, pu32, pu32, C.POINTER(LoudnessC), C.POINTER(LoudnessResultC), pvp]),
+                           ("zv_loudness_design", [u32, C.POINTER(LoudnessFilterC)])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
@@ -1197,6 +1290,44 @@ class Model:
         self._chk(fn(self.h, n, P(*[w.ctypes.data for w, _ in ws]), (C.c_uint32 * n)(*[T for _, T in ws]), C.byref(st),
                      P(*[o.ctypes.data for o in outs])))
         return outs
+
+    def loudness_wave(self, wav, ask=None, n_frames=None, apply=True):
+        """zv_loudness_wave: the BS.1770 loudness and the true peak of the waveform's first n_frames frames (None: all of it) and the
+        whole waveform scaled by one gain -> (LoudnessResult, float32 [T * hop]); ask: a Loudness or None (the identity);
+        apply=False meters only -> (LoudnessResult, None)"""
+        fn = _stage_symbol(self.lib, "zv_loudness_wave")
+        q = _loudness_ask("loudness_wave", ask)
+        w, T = _waveform(self.hp.audio_hop_size, "loudness_wave", wav)
+        out = np.empty_like(w) if apply else None
+        res = LoudnessResultC()
+        st = q.struct if q is not None else None
+        self._chk(fn(self.h, _ptr(w), T, T if n_frames is None else int(n_frames), C.byref(st) if q is not None else None, C.byref(res),
+                     _ptr(out) if apply else None))
+        return LoudnessResult(res), out
+
+    def loudness_wave_batch(self, wavs, asks=None, n_frames=None, apply=True):
+        """zv_loudness_wave_batch: waveforms [T_u * hop], one per utterance, through ONE launch per kernel per launch group -> the list
+        of (LoudnessResult, waveform or None), each with the bits of its loudness_wave; asks: None or one Loudness (or None) per
+        utterance; n_frames: None or one count per utterance; apply: a bool, or one per utterance"""
+        fn = _stage_symbol(self.lib, "zv_loudness_wave_batch")
+        ws = [_waveform(self.hp.audio_hop_size, f"loudness_wave_batch: utterance {u}", w) for u, w in enumerate(wavs)]
+        n = len(ws)
+        if asks is not None and len(asks) != n:
+            raise ValueError(f"loudness_wave_batch: {len(asks)} asks for {n} utterances")
+        if n_frames is not None and len(n_frames) != n:
+            raise ValueError(f"loudness_wave_batch: {len(n_frames)} frame counts for {n} utterances")
+        want = [bool(apply)] * n if isinstance(apply, (bool, np.bool_)) else [bool(a) for a in apply]
+        if len(want) != n:
+            raise ValueError(f"loudness_wave_batch: {len(want)} apply flags for {n} utterances")
+        qs = None
+        if asks is not None:
+            qs = (LoudnessC * n)(*[(_loudness_ask(f"loudness_wave_batch: utterance {u}", a) or Loudness()).struct for u, a in enumerate(asks)])
+        outs = [np.empty_like(w) if a else None for (w, _), a in zip(ws, want)]
+        res = (LoudnessResultC * n)()
+        P, U = C.c_void_p * n, C.c_uint32 * n
+        self._chk(fn(self.h, n, P(*[w.ctypes.data for w, _ in ws]), U(*[T for _, T in ws]),
+                     None if n_frames is None else U(*[int(f) for f in n_frames]), qs, res, P(*[None if o is None else o.ctypes.data for o in outs])))
+        return [(LoudnessResult(r), o) for r, o in zip(res, outs)]
 
     def resynthesize(self, wav, params=None) -> np.ndarray:
         """analysis-resynthesis: vocode(mel_wave(wav)), the acceptance check of a converted vocoder checkpoint.  params must keep the

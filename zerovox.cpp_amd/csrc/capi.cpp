@@ -1834,6 +1834,150 @@ zv_status zv_align_durations(uint32_t n, const int32_t *durations_a, uint32_t Ta
     });
 }
 
+// ---- loudness (zv_loudness_wave, zv_loudness_wave_batch, zv_loudness_design; the rule: loudness.h): host waveforms in, per utterance
+// the BS.1770 result and (where asked) the scaled waveform out, eagerly, on lane 0.  A batch runs as launch groups of consecutive
+// utterances (loud_group_end), each ONE launch per kernel.  I/O block of a group: [samples, every utterance on whole chunks][states][runs]
+// [step energies][blocks][peaks][segment table][asks][design][result rows].
+static_assert(sizeof(zv_loudness_result) == sizeof(zv::LoudRow) && sizeof(zv_loudness_filter) == sizeof(zv::LoudFilter) &&
+                  offsetof(zv_loudness_filter, interp) == offsetof(zv::LoudFilter, c) && offsetof(zv_loudness_result, gain) == offsetof(zv::LoudRow, gain) &&
+                  ZV_LOUDNESS_TARGET == zv::LOUD_FLAG_TARGET && ZV_LOUDNESS_CEILING == zv::LOUD_FLAG_CEILING,
+              "zv_loudness_result is loudness.h's LoudRow, zv_loudness_filter its LoudFilter");
+
+static void check_loudness(const char *fn, const char *who, const zv_loudness &q)
+{
+    const char *field = zv::loud_check(q.gain, q.target_lufs, q.true_peak_ceiling, q.flags);
+    if (!field) return;
+    if (!strcmp(field, "flags")) zv::fail(ZV_ERR_ARG, "%s: %sloudness flags = %u holds bits other than 0 (target) and 1 (ceiling)", fn, who, q.flags);
+    const float v = !strcmp(field, "gain") ? q.gain : !strcmp(field, "target_lufs") ? q.target_lufs : q.true_peak_ceiling;
+    if (!std::isfinite(v)) zv::fail(ZV_ERR_ARG, "%s: %sloudness %s = %g is not finite", fn, who, field, (double)v);
+    if (!strcmp(field, "gain")) zv::fail(ZV_ERR_ARG, "%s: %sloudness gain = %g is outside [0, 1000]", fn, who, (double)v);
+    if (!strcmp(field, "target_lufs")) zv::fail(ZV_ERR_ARG, "%s: %sloudness target_lufs = %g is outside [-70, 0]", fn, who, (double)v);
+    zv::fail(ZV_ERR_ARG, "%s: %sloudness true_peak_ceiling = %g is outside (0, 1]", fn, who, (double)v);
+}
+
+// the checks that need no model: res, then every utterance's ask by field
+static void check_loud_args(const char *fn, bool batch, uint32_t n_utt, const zv_loudness *ask, const zv_loudness_result *res)
+{
+    if (!res) zv::fail(ZV_ERR_ARG, "%s: res is NULL", fn);
+    char who[32] = "";
+    for (uint32_t u = 0; ask && u < n_utt; u++)
+    {
+        if (batch) snprintf(who, sizeof who, "utterance %u: ", u);
+        check_loudness(fn, who, ask[u]);
+    }
+}
+
+static void loud_run(zv_model *m, const char *fn, uint32_t n_utt, const float *const *wav, const uint32_t *T, const uint32_t *n_frames,
+                     const zv_loudness *ask, zv_loudness_result *res, float *const *out)
+{
+#if !defined(__HIP_DEVICE_COMPILE__)      // (loudness.h keeps its host half out of device passes)
+    Model &M = *m->m;
+    const uint32_t hop = M.hp.audio_hop_size, rate = M.hp.audio_sampling_rate;
+    zv::LoudFilter F;
+    if (zv::loud_design(rate, &F))
+        zv::fail(ZV_ERR_ARG, "%s: audio_sampling_rate = %u must be in %u .. %u", fn, rate, zv::LOUD_MIN_RATE, zv::LOUD_MAX_RATE);
+    use_lane0(m);
+    static const zv_loudness identity = {1.0f, 0.0f, 0.0f, 0u};
+    std::vector<zv::LoudSeg> segs;
+    std::vector<zv::LoudAsk> asks;
+    std::vector<zv::LoudRow> rows;
+    for (uint32_t g0 = 0; g0 < n_utt;)
+    {
+        const uint32_t g1 = zv::loud_group_end(g0, n_utt, T, hop), n = g1 - g0;
+        segs.resize(n);
+        asks.resize(n);
+        rows.resize(n);
+        int64_t x0 = 0, max_N = 0, max_total = 0;
+        size_t chunks = 0, steps = 0, tiles = 0, measured = 0, capacity = 0;
+        bool apply = false;
+        for (uint32_t k = 0; k < n; k++)
+        {
+            const uint32_t u = g0 + k, nf = n_frames ? std::min(n_frames[u], T[u]) : T[u];
+            const int64_t N = (int64_t)nf * hop, total = (int64_t)T[u] * hop;
+            segs[k] = zv::LoudSeg{x0, N, total, (int32_t)chunks, (int32_t)steps, (int32_t)tiles, 0};
+            const zv_loudness &q = ask ? ask[u] : identity;
+            asks[k] = zv::loud_ask(q.gain, q.target_lufs, q.true_peak_ceiling, q.flags);
+            x0 += (int64_t)zv::loud_padded((uint64_t)total);
+            chunks += (size_t)zv::loud_chunks(N);
+            steps += (size_t)(N / F.step);
+            tiles += (size_t)zv::loud_tp_tiles(N);
+            max_N = std::max(max_N, N);
+            max_total = std::max(max_total, total);
+            measured += (size_t)N;
+            capacity += (size_t)total;
+            apply = apply || (out && out[u]);
+        }
+        Layout L;
+        const size_t o_wav = L.at((size_t)x0 * 4), o_state = L.at(chunks * 32), o_runs = L.at(chunks * 16 + 16), o_energy = L.at(steps * 8 + 8),
+                     o_blocks = L.at(steps * 8 + 8), o_peaks = L.at(tiles * 16), o_seg = L.at((size_t)n * sizeof(zv::LoudSeg)),
+                     o_ask = L.at((size_t)n * sizeof(zv::LoudAsk)), o_des = L.at(sizeof(zv::LoudFilter)), o_row = L.at((size_t)n * sizeof(zv::LoudRow));
+        char *io = (char *)M.io_scratch(L.size());
+        for (uint32_t k = 0; k < n; k++)
+            ZV_HIP(hipMemcpyAsync(io + o_wav + (size_t)segs[k].x0 * 4, wav[g0 + k], (size_t)segs[k].total * 4, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_seg, segs.data(), (size_t)n * sizeof(zv::LoudSeg), hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_ask, asks.data(), (size_t)n * sizeof(zv::LoudAsk), hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_des, &F, sizeof F, hipMemcpyHostToDevice, M.stream()));
+        const zv::LoudJob job{(float *)(io + o_wav), (double *)(io + o_state), (double *)(io + o_runs), (double *)(io + o_energy), (double *)(io + o_blocks),
+                              (uint64_t *)(io + o_peaks), (zv::LoudRow *)(io + o_row), (const zv::LoudSeg *)(io + o_seg), (const zv::LoudAsk *)(io + o_ask),
+                              (const zv::LoudFilter *)(io + o_des), (int)n, max_N, max_total, F.step};
+        M.loud_launches(job, apply, measured, capacity);
+        ZV_HIP(hipMemcpyAsync(rows.data(), io + o_row, (size_t)n * sizeof(zv::LoudRow), hipMemcpyDeviceToHost, M.stream()));
+        for (uint32_t k = 0; k < n; k++)
+            if (out && out[g0 + k])
+                ZV_HIP(hipMemcpyAsync(out[g0 + k], io + o_wav + (size_t)segs[k].x0 * 4, (size_t)segs[k].total * 4, hipMemcpyDeviceToHost, M.stream()));
+        M.sync();                             // (segs, asks, rows and F are pageable and reused by the next group)
+        for (uint32_t k = 0; k < n; k++) memcpy(&res[g0 + k], &rows[k], sizeof(zv::LoudRow));
+        g0 = g1;
+    }
+#endif
+}
+
+zv_status zv_loudness_wave(zv_model *m, const float *wav, uint32_t T, uint32_t n_frames, const zv_loudness *ask, zv_loudness_result *res, float *out)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!m) zv::fail(ZV_ERR_ARG, "%s: m is NULL", fn);
+        if (!wav) zv::fail(ZV_ERR_ARG, "%s: wav is NULL", fn);
+        check_loud_args(fn, false, 1, ask, res);
+        try
+        {
+            check_T(*m->m, T);
+        }
+        catch (const zv::Error &e)
+        {
+            zv::fail(e.status, "%s: %s", fn, e.what());
+        }
+        loud_run(m, fn, 1, &wav, &T, &n_frames, ask, res, &out);
+    });
+}
+
+zv_status zv_loudness_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint32_t *T, const uint32_t *n_frames,
+                                 const zv_loudness *ask, zv_loudness_result *res, float *const *out)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!m) zv::fail(ZV_ERR_ARG, "%s: m is NULL", fn);
+        check_loud_args(fn, true, n_utt, ask, res);
+        check_stage_args(fn, m, n_utt, {{"wav", wav, true}}, nullptr, T);
+        loud_run(m, fn, n_utt, wav, T, n_frames, ask, res, out);
+    });
+}
+
+// The design: host only, no model, no device (loudness.h loud_design).
+zv_status zv_loudness_design(uint32_t sampling_rate, zv_loudness_filter *out)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!out) zv::fail(ZV_ERR_ARG, "%s: out is NULL", fn);
+#if !defined(__HIP_DEVICE_COMPILE__)      // (loudness.h keeps its host half out of device passes)
+        zv::LoudFilter F;
+        if (zv::loud_design(sampling_rate, &F))
+            zv::fail(ZV_ERR_ARG, "%s: sampling_rate = %u must be in %u .. %u", fn, sampling_rate, zv::LOUD_MIN_RATE, zv::LOUD_MAX_RATE);
+        memcpy(out, &F, sizeof F);
+#endif
+    });
+}
+
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)
 {
     return guarded([&] {

@@ -21,6 +21,7 @@
 #include "filter.h"       // waveform filter: FILTER_TILE, FILTER_PARAM_STRIDE
 #include "mel.h"          // mel analysis: MEL_SLAB_STRIDE, MEL_TABLE_BYTES, the parameter block
 #include "align.h"        // mel alignment: AlignPair, AlignRow, the tiles and ALIGN_DP_ROWS
+#include "loudness.h"     // loudness: LoudJob, LoudSeg, LoudAsk, LoudRow, LoudFilter
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -529,5 +530,18 @@ hipError_t launch_align_quant(hipStream_t s, const AlignJob &j);
 hipError_t launch_align_cost(hipStream_t s, const AlignJob &j);
 hipError_t launch_align_dp(hipStream_t s, const AlignJob &j);
 hipError_t launch_align_walk(hipStream_t s, const AlignJob &j);
+
+// ---- loudness (include/zerovox_amd.h "loudness", loudness.h): six passes over ONE launch group of utterances (LoudJob), a launch each
+// whatever the group (stage_plan.h loud_plan).  segs[nseg] says where an utterance's samples, chunks, steps and tiles lie (LoudSeg); every
+// utterance's samples start at a multiple of LOUD_CHUNK floats behind the 16-byte aligned wav and own whole chunks up to its capacity.
+//   chunks (phase_c false): state[chunk] = the end state of the chunk run from zero;  states: state[chunk] = its entry state, in place
+//   chunks (phase_c true):  runs[chunk] = the chunk's two run sums;  peak: peaks[tile] = the tile's true-peak and sample-peak bits
+//   gate:  rows[u] = the result (LoudRow), the gain included;  apply: wav scaled by rows[u].gain over the capacity, in place
+// No atomics, nothing to zero.  A group without a measured sample (max_N == 0) launches gate and apply alone.
+hipError_t launch_loud_chunks(hipStream_t s, const LoudJob &j, bool phase_c);
+hipError_t launch_loud_states(hipStream_t s, const LoudJob &j);
+hipError_t launch_loud_peak(hipStream_t s, const LoudJob &j);
+hipError_t launch_loud_gate(hipStream_t s, const LoudJob &j);
+hipError_t launch_loud_apply(hipStream_t s, const LoudJob &j);
 
 }  // namespace zv

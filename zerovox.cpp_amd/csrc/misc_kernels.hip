@@ -13,4 +13,5 @@
 #include "filter_kernels.hip"         // waveform filter
 #include "mel_kernels.hip"            // mel analysis
 #include "align_kernels.hip"          // mel alignment
+#include "loudness_kernels.hip"       // loudness
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

@@ -251,6 +251,9 @@ class Model
     // the five launches of mel alignment over one launch group of pairs, likewise (kernels.h launch_align_*); rows and cells: the group's
     // sequence rows and matrix cells, for the profile's byte and operation counts
     void align_launches(const AlignJob &job, size_t rows, size_t cells);
+    // the launches of loudness over one launch group of utterances, likewise (kernels.h launch_loud_*): five of them measure, the sixth
+    // scales (apply: the caller wants the waveform back); samples: the group's measured samples, capacity: the samples it scales
+    void loud_launches(const LoudJob &job, bool apply, size_t samples, size_t capacity);
 
     // scratch for host-buffer entry points (grows on demand)
     void *io_scratch(size_t bytes);

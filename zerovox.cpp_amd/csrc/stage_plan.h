@@ -11,6 +11,7 @@
 #include "conv_plan.h"      // batch_switch / batch_rows, plan_round_up
 #include "knobs.h"
 #include "mel.h"            // MEL_TILE_FRAMES, MEL_ROWS_FRAMES, MEL_MAX_MELS
+#include "loudness.h"       // LOUD_CHUNK, LOUD_WG_CHUNKS, LOUD_TP_TILE
 
 namespace zv
 {
@@ -145,6 +146,24 @@ inline DecPlan dec_plan(int nseg, int t_max, size_t t_rows, bool fitted, bool db
     p.runs = !fitted && !dbg_active && p.prepass && batch_switch(knob(ZV_DEC_RUNS), batch_rows((long)t_rows));
     p.pack = has_table && nseg > 1 && knob(ZV_DEC_PACK) != 0;
     return p;
+}
+
+// ---- loudness (loudness_kernels.hip): ONE launch per kernel over a launch group's utterances ----
+constexpr int LOUD_APPLY_TILE = 4096;                    // samples one workgroup of the apply pass scales: 256 lanes, four float4 each
+struct LoudPlan
+{
+    bool ok;                    // a sample is measured, the step holds a chunk (a chunk meets at most two steps)
+    int  chunks, chunk_gx;      // chunks of the longest span; phases A and C: workgroups of LOUD_WG_CHUNKS chunks, a lane each
+    int  tp_gx;                 // the true-peak pass: tiles of LOUD_TP_TILE outputs over the span and the interpolator's tail
+    int  steps;                 // whole 100 ms steps of the longest span
+    int  apply_gx;              // the apply pass: tiles of LOUD_APPLY_TILE samples of the longest capacity
+    int  states_gx, gy;         // phase B: a lane per utterance, 64 to a workgroup; utterances: grid y of A, C, true peak and apply, grid x of the gate
+};
+inline LoudPlan loud_plan(int64_t max_N, int64_t max_total, int nseg, uint32_t step)
+{
+    const bool ok = max_total >= 1 && max_N >= 0 && max_N <= max_total && nseg >= 1 && step >= (uint32_t)LOUD_CHUNK;
+    return LoudPlan{ok, (int)loud_chunks(max_N), (int)((loud_chunks(max_N) + LOUD_WG_CHUNKS - 1) / LOUD_WG_CHUNKS), (int)loud_tp_tiles(max_N),
+                    (int)(max_N / (step ? step : 1u)), (int)((max_total + LOUD_APPLY_TILE - 1) / LOUD_APPLY_TILE), (nseg + 63) / 64, nseg};
 }
 
 }  // namespace zv

@@ -125,4 +125,18 @@ void Model::align_launches(const AlignJob &job, size_t n_rows, size_t n_cells)
     ZV_LAUNCH("align_walk", 5.0 * rows, 0.0, launch_align_walk(stream(), job));
 }
 
+// Loudness (loudness.h): no stage of the chain either — the stand-alone entry points' launches over one launch group of utterances.
+void Model::loud_launches(const LoudJob &job, bool apply, size_t samples, size_t capacity)
+{
+    const double n = (double)samples, chunks = n / LOUD_CHUNK;
+    // algorithmic bytes: the samples read once per pass; a state (32 bytes) or two run sums (16) per chunk.  Operations: 16 f64 operations
+    // per sample in phase A, two more for the square in phase C; 28 per chunk in phase B; 3 x 12 multiply-adds per sample for the true peak.
+    ZV_LAUNCH("loud_chunks_a", 4.0 * n + 32.0 * chunks, 16.0 * n, launch_loud_chunks(stream(), job, false));
+    ZV_LAUNCH("loud_states", 64.0 * chunks, 28.0 * chunks, launch_loud_states(stream(), job));
+    ZV_LAUNCH("loud_chunks_c", 4.0 * n + 48.0 * chunks, 18.0 * n, launch_loud_chunks(stream(), job, true));
+    ZV_LAUNCH("loud_peak", 4.0 * n, 2.0 * 36.0 * n, launch_loud_peak(stream(), job));
+    ZV_LAUNCH("loud_gate", 16.0 * chunks, 0.0, launch_loud_gate(stream(), job));
+    if (apply) ZV_LAUNCH("loud_apply", 8.0 * (double)capacity, (double)capacity, launch_loud_apply(stream(), job));
+}
+
 }  // namespace zv

@@ -98,6 +98,10 @@ class HiFiGAN
     // (not in the reference) the way back: wav [max_seq_len * hop_size] -> mel [max_seq_len][in_channels], zv_mel_wave with natural-log
     // Slaney mels over 0 .. Nyquist, reflect padding, centre 0 and the default floor — the domain eval reads
     void analyze(const float *wav, float *mel);
+    // (not in the reference) the delivery meter: zv_loudness_wave over wav [max_seq_len * hop_size] — BS.1770 integrated loudness (LUFS),
+    // true peak (dBTP) and, where out [max_seq_len * hop_size] is given, the waveform under ask's gain, target and ceiling (nullptr: the
+    // identity, a meter)
+    zv_loudness_result loudness(const float *wav, const zv_loudness *ask = nullptr, float *out = nullptr);
 
   private:
     zv_model *model;
@@ -180,6 +184,9 @@ class ZeroVOXModel
     // the new timings, get_alignment() the alignment.  nullptr: off.  It excludes per-phoneme duration_frames and a target.
     void set_time_like(const float *ref_wav, size_t n_samples);
     const zv_alignment &get_alignment() const { return alignment; }
+    // loudness (include/zerovox_amd.h "loudness"): zv_loudness_wave over any waveform of T frames at the model's rate, its first
+    // n_frames measured; ask nullptr: the identity; out [T * hop] or nullptr (a meter).  Next to HiFiGAN::loudness, for other lengths.
+    zv_loudness_result loudness(const float *wav, uint32_t T, uint32_t n_frames, const zv_loudness *ask = nullptr, float *out = nullptr);
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }

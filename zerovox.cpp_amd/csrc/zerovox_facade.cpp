@@ -107,6 +107,13 @@ void HiFiGAN::analyze(const float *wav, float *mel)
     chk(zv_mel_wave(model, wav, max_seq_len, &q, mel));
 }
 
+zv_loudness_result HiFiGAN::loudness(const float *wav, const zv_loudness *ask, float *out)
+{
+    zv_loudness_result res{};
+    chk(zv_loudness_wave(model, wav, max_seq_len, max_seq_len, ask, &res, out));
+    return res;
+}
+
 // ---------------------------------------------------------------------------------------------------
 
 ZeroVOXModel::ZeroVOXModel(const std::string &fname)
@@ -229,6 +236,13 @@ zv_alignment ZeroVOXModel::align(const float *a, uint32_t Ta, const float *b, ui
     zv_alignment out{};
     chk(zv_mel_align(model, a, Ta, b, Tb, M, params ? params : &q, &out, map_a, map_b));
     return out;
+}
+
+zv_loudness_result ZeroVOXModel::loudness(const float *wav, uint32_t T, uint32_t n_frames, const zv_loudness *ask, float *out)
+{
+    zv_loudness_result res{};
+    chk(zv_loudness_wave(model, wav, T, n_frames, ask, &res, out));
+    return res;
 }
 
 void ZeroVOXModel::set_time_like(const float *ref_wav, size_t n_samples)

@@ -76,6 +76,12 @@
 //            files of raw f32 rows [frames][M] (what --mel-out writes), printed as total, path length and distance; --map-out writes
 //            the two frame maps as TSV.  --mel-width is required (1 .. 256); a file that cannot be opened, holds no whole rows or more
 //            than 4 096 of them is an error by name ahead of the checkpoint.  The other four flags without --align are usage errors.
+//   --loudness IN.wav, --lufs L, --true-peak-dbtp P
+//            --loudness: no synthesis; the BS.1770 report (zv_loudness_wave) of a mono PCM16 RIFF file at the model's rate: integrated,
+//            momentary-maximum and short-term-maximum loudness in LUFS, true peak in dBTP, sample peak, the block counts, and the gain
+//            --lufs / --true-peak-dbtp would apply.  Without --loudness the two flags normalise a synthesis run: the finished waveform
+//            (what -o receives) passes through the call before it is written.  --lufs in [-70, 0], --true-peak-dbtp <= 0;
+//            --true-peak-dbtp alone is a ceiling without a target.  A bad value is a usage error.
 //   --time-like REF.wav
 //            with the synthesis flags: the utterance with the timing of the reference, a mono PCM16 RIFF file at the model's rate.
 //            The utterance is synthesised (fitted), its mel rows are aligned to the reference's, the phoneme boundaries move onto the
@@ -114,6 +120,8 @@ static void usage(FILE *f)
                "       zerovox -m model.gguf --analyze in.wav [--mel-out rows.f32] [--resynth out.wav]\n"
                "               [--mel-fmin HZ] [--mel-fmax HZ] [--mel-centre SAMPLE] [--mel-pad reflect|zero]\n"
                "       zerovox -m model.gguf --align a.f32 b.f32 --mel-width M [--align-scale S] [--align-normalise] [--map-out map.tsv]\n"
+               "       zerovox -m model.gguf --loudness in.wav [--lufs L] [--true-peak-dbtp P]\n"
+               "       zerovox ... --lufs L [--true-peak-dbtp P]   (with the synthesis flags)\n"
                "       zerovox ... --time-like ref.wav   (with the synthesis flags)\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
@@ -158,6 +166,10 @@ static void usage(FILE *f)
                "                       format); prints total, path length and distance.  --mel-width M (1 .. 256, required), --align-scale S\n"
                "                       (steps per unit of the rows, default 64), --align-normalise (remove every channel's mean per file),\n"
                "                       --map-out FILE (TSV: side index frame, the first frame of the other file on the path)\n"
+               "  --loudness IN.wav    no synthesis: the ITU-R BS.1770 report of a mono PCM16 file at the model's rate: integrated, momentary and\n"
+               "                       short-term loudness (LUFS), true peak (dBTP), and the gain --lufs / --true-peak-dbtp would apply\n"
+               "  --lufs L             bring the finished waveform to L LUFS integrated (-70 .. 0) before it is written\n"
+               "  --true-peak-dbtp P   keep its true peak at or below P dBTP (P <= 0); with --lufs the ceiling wins\n"
                "  --time-like REF.wav  synthesise with the timing of REF.wav (mono PCM16 at the model's rate): the phoneme boundaries of a\n"
                "                       first synthesis are moved onto the reference's clock along the alignment of the two mels\n",
             k_default_model, k_default_out);
@@ -408,6 +420,35 @@ static int analyze(const std::string &model_path, const std::string &in_path, co
     return 0;
 }
 
+static void print_loudness(const char *what, const zv_loudness_result &r)
+{
+    printf("%s: integrated %.2f LUFS, momentary max %.2f LUFS, short-term max %.2f LUFS, true peak %.2f dBTP (sample peak %.6f), "
+           "blocks %u / %u / %u, gain %.6f\n",
+           what, (double)r.integrated_lufs, (double)r.momentary_max_lufs, (double)r.short_term_max_lufs, (double)r.true_peak_dbtp,
+           (double)r.sample_peak, r.blocks, r.blocks_absolute, r.blocks_gated, (double)r.gain);
+}
+
+// --loudness IN.wav: the file's BS.1770 report (zv_loudness_wave, a meter: nothing is written); the file as for --analyze
+static int loudness_file(const std::string &model_path, const std::string &in_path, const zv_loudness &q)
+{
+    uint32_t rate = 0;
+    const std::vector<float> pcm = read_pcm16("--loudness", in_path, rate);
+    zv_model *m = nullptr;
+    if (zv_model_load(model_path.c_str(), 0, &m) != ZV_OK) throw std::runtime_error(zv_last_error());
+    struct Free { zv_model *m; ~Free() { zv_model_free(m); } } free_model{m};
+    zv_hparams hp;
+    if (zv_model_get_hparams(m, &hp) != ZV_OK) throw std::runtime_error(zv_last_error());
+    if (rate != hp.audio_sampling_rate)
+        throw std::runtime_error("--loudness: '" + in_path + "' is at " + std::to_string(rate) + " Hz, the model at " + std::to_string(hp.audio_sampling_rate) + " Hz (nothing is resampled)");
+    const size_t T = pcm.size() / hp.audio_hop_size;
+    if (T == 0 || T > zv_max_frames(m))
+        throw std::runtime_error("--loudness: '" + in_path + "' holds " + std::to_string(T) + " frames of " + std::to_string(hp.audio_hop_size) + " samples, 1 .. " + std::to_string(zv_max_frames(m)) + " are needed");
+    zv_loudness_result r;
+    if (zv_loudness_wave(m, pcm.data(), (uint32_t)T, (uint32_t)T, &q, &r, nullptr) != ZV_OK) throw std::runtime_error(zv_last_error());
+    print_loudness(in_path.c_str(), r);
+    return 0;
+}
+
 // --align A.f32 B.f32: the files' rows, checked ahead of the checkpoint; then zv_mel_align and the printout
 static std::vector<float> read_rows(const std::string &path, uint32_t width)
 {
@@ -453,6 +494,8 @@ int main(int argc, char **argv)
     long mel_width = 0;                                        // --mel-width
     bool align_flag = false;
     std::string analyze_path, melout_path, resynth_path;      // --analyze, --mel-out, --resynth
+    std::string loudness_path;                                 // --loudness
+    zv_loudness loud_q = {1.0f, 0.0f, 0.0f, 0u};               // --lufs, --true-peak-dbtp
     zv_mel mel_q{};                                            // --mel-fmin, --mel-fmax, --mel-centre, --mel-pad
     mel_q.log = 1;
     mel_q.pad = 1;
@@ -584,6 +627,19 @@ int main(int argc, char **argv)
         else if (a == "--align-normalise") align_q.normalise = 1, align_flag = true;
         else if (a == "--map-out") map_path = need("--map-out"), align_flag = true;
         else if (a == "--time-like") like_path = need("--time-like");
+        else if (a == "--loudness") loudness_path = need("--loudness");
+        else if (a == "--lufs" || a == "--true-peak-dbtp")
+        {
+            const float v = parse_flag_float(a.c_str(), need(a.c_str()));
+            if (a == "--lufs" ? !(v >= -70.0f && v <= 0.0f) : !(v <= 0.0f && v >= -200.0f))
+            {
+                fprintf(stderr, "zerovox: %s %g is outside %s\n", a.c_str(), (double)v, a == "--lufs" ? "[-70, 0]" : "[-200, 0]");
+                usage(stderr);
+                return 2;
+            }
+            if (a == "--lufs") loud_q.target_lufs = v, loud_q.flags |= ZV_LOUDNESS_TARGET;
+            else loud_q.true_peak_ceiling = (float)pow(10.0, (double)v / 20.0), loud_q.flags |= ZV_LOUDNESS_CEILING;
+        }
         else if (a == "--mel-out") melout_path = need("--mel-out"), mel_flag = true;
         else if (a == "--resynth") resynth_path = need("--resynth"), mel_flag = true;
         else if (a == "--mel-fmin") mel_q.fmin_hz = parse_flag_float("--mel-fmin", need("--mel-fmin")), mel_flag = true;
@@ -741,6 +797,12 @@ int main(int argc, char **argv)
         usage(stderr);
         return 2;
     }
+    if (!loudness_path.empty() && (!analyze_path.empty() || !align_a.empty() || !like_path.empty() || planning))
+    {
+        fprintf(stderr, "zerovox: --loudness and --analyze, --align, --time-like, --plan exclude each other\n");
+        usage(stderr);
+        return 2;
+    }
     if (align_flag && align_a.empty())
     {
         fprintf(stderr, "zerovox: --mel-width, --align-scale, --align-normalise and --map-out need --align A.f32 B.f32\n");
@@ -837,6 +899,7 @@ int main(int argc, char **argv)
 
         if (planning) return plan(model_path, utt_path, controlled ? &prosody : nullptr);
         if (!analyze_path.empty()) return analyze(model_path, analyze_path, melout_path, resynth_path, mel_q);
+        if (!loudness_path.empty()) return loudness_file(model_path, loudness_path, loud_q);
         if (!align_a.empty()) return align_files(model_path, align_a, align_b, (uint32_t)mel_width, align_q, map_path);
         std::vector<float> like_wav;                            // --time-like, read ahead of the checkpoint
         uint32_t like_rate = 0;
@@ -1026,7 +1089,17 @@ int main(int argc, char **argv)
             if (!bands_path.empty()) write_bands(bands_path, model.get_band_frames());
             if (!pbands_path.empty()) write_bands(pbands_path, model.get_band_phonemes());
         }
-        if (trim || fit)
+        if (loud_q.flags)
+        {
+            // --lufs / --true-peak-dbtp: what -o receives, measured over the speech and scaled as a whole, then written
+            const uint32_t T = trim || fit ? nf : hp.max_seq_len;
+            std::vector<float> scaled((size_t)T * hp.audio_hop_size);
+            const zv_loudness_result r = T ? model.loudness(model.get_wav(), T, std::min(nf, T), &loud_q, scaled.data()) : zv_loudness_result{};
+            print_loudness("loudness before the gain", r);
+            if (zv_write_wav(out_path.c_str(), scaled.data(), scaled.size(), hp.audio_sampling_rate) != ZV_OK) throw std::runtime_error(zv_last_error());
+            printf("Successfully created %s with %zu samples (%u frames).\n", out_path.c_str(), scaled.size(), T);
+        }
+        else if (trim || fit)
         {
             const size_t n = (size_t)nf * hp.audio_hop_size;
             if (zv_write_wav(out_path.c_str(), model.get_wav(), n, hp.audio_sampling_rate) != ZV_OK)
