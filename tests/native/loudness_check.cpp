@@ -11,6 +11,8 @@
 //       -> the least time in ms of REPS runs of loud_reference (a meter) over N samples of noise
 //   loudness_check plan RATE HOP T...
 //       -> per T, for three utterances: ok, chunks, chunk workgroups, true-peak tiles, steps, apply tiles, phase-B workgroups, grid y
+//   loudness_check groups HOP T...
+//       -> one line: the end (one past the last utterance) of every launch group loud_group_end cuts the batch into, as loud_run walks it
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -58,6 +60,21 @@ int main(int argc, char **argv)
             const zv::LoudPlan p = zv::loud_plan((int64_t)T * hop, (int64_t)T * hop, 3, F.step);
             printf("%d %d %d %d %d %d %d %d\n", (int)p.ok, p.chunks, p.chunk_gx, p.tp_gx, p.steps, p.apply_gx, p.states_gx, p.gy);
         }
+        return 0;
+    }
+    if (argc >= 4 && !strcmp(argv[1], "groups"))
+    {
+        const uint32_t hop = (uint32_t)strtoul(argv[2], nullptr, 10), n = (uint32_t)(argc - 3);
+        std::vector<uint32_t> T(n);
+        for (uint32_t u = 0; u < n; u++) T[u] = (uint32_t)strtoul(argv[3 + u], nullptr, 10);
+        for (uint32_t g0 = 0; g0 < n;)
+        {
+            const uint32_t g1 = zv::loud_group_end(g0, n, T.data(), hop);
+            if (g1 <= g0) return 4;      // a group without an utterance: the walk would never end
+            printf("%u ", g1);
+            g0 = g1;
+        }
+        printf("\n");
         return 0;
     }
     if (argc == 11 && !strcmp(argv[1], "run"))
@@ -110,6 +127,6 @@ int main(int argc, char **argv)
         printf("%.3f %g\n", best, sink);
         return 0;
     }
-    fprintf(stderr, "usage: loudness_check design|run|check|plan|bench ...\n");
+    fprintf(stderr, "usage: loudness_check design|run|check|plan|groups|bench ...\n");
     return 1;
 }

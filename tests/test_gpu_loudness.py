@@ -1,12 +1,15 @@
 """-m gpu: loudness (include/zerovox_amd.h "loudness") on the tiny synthetic checkpoint (22 050 Hz, hop 300, so a 100 ms step is 2 205
-samples; the kernels depend on the rate, the hop, the lengths and the asks alone).
+samples; the kernels depend on the rate, the hop, the lengths and the asks alone).  This file stays at ONE rate, below 3.1 s (27
+momentary blocks, 33 true-peak tiles: one round of 64 of each of the gate kernel's loops), at five utterances in one launch group and
+at n_frames >= 1; other rates, longer spans, wider batches, n_frames = 0, a batch across a launch group's end and the ceiling's
+round-down step are tests/test_gpu_loudness_shapes.py.
 
 Every expectation is the rule restated in numpy (tests/loudness_rule.py) on the design the library itself returns (the design is data to
 the kernels): there is no tolerance anywhere but in the last test, the bits must match — every field of the result and every sample.
   * the single call with N = n_frames * hop on both sides of four steps (29 / 30 frames: no block / the first block) and of thirty steps
     (220 / 221 frames: no short-term block / the first), at N a whole number of chunks (64 frames = 75 chunks) and not, always with
     n_frames < T: the tail behind N is scaled and not measured.  221 frames are 259 chunks and 33 true-peak tiles: five workgroups of the
-    chunk passes and more than one slice of every pass over one utterance;
+    chunk passes and 33 of the peak pass over one utterance (the gate pass stays within its first round);
   * a ragged batch of five with an utterance below four steps, a silent one and one with a NaN and an infinity, under mixed asks (none,
     a target, a ceiling, both with the ceiling winning): every utterance has the bits of its single call;
   * the same batch after zv_debug_poison of lane 0 with both bytes;

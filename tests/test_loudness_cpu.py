@@ -3,12 +3,18 @@
  * tests/native/loudness_check.cpp drives zv::loud_reference at 22 050 Hz over N on both sides of four and of thirty steps, N a whole
    number of chunks and not, silence, a NaN and an infinity inside the span, leading silence (the absolute gate drops blocks) and a loud
    burst (the relative gate drops blocks), under asks of every kind: every field of the result and every output sample must agree;
- * the same input through a build with -fsanitize=address,undefined (a plain host program, nothing preloaded);
+ * the same comparison at 4 000 Hz (step 400: most chunks meet two steps), 5 120 Hz (step 512: no chunk holds an edge), 48 000 Hz and
+   768 000 Hz (the highest rate the design takes): N = 0, N on both sides of four and of thirty steps of that rate, and N of 65 and 129
+   blocks, more than one and more than two rounds of 64 of the gate kernel's loops;
+ * the same inputs through a build with -fsanitize=address,undefined (a plain host program, nothing preloaded);
+ * the ceiling's round-down step: a fixed waveform and a fixed list of ceilings of which some need it (tests/loudness_shapes.py);
  * the design: the standard's 48 kHz table within 1e-12, M against numpy's matrix power, the interpolator, the refused rates;
  * the decomposition is the standard: the chunked rule against one sequential pass over the whole signal with textbook gating;
  * conformance: EBU Tech 3341 cases 1, 3, 4 and 5 as mono at 22 050 Hz read -26.0 LUFS +- 0.1; EBU Tech 3341 true-peak tones of
    amplitude 0.5 read -6.0 dBTP +0.2 / -0.4;
- * the boundary: argument checks and messages without a device, the binding, an older library, the launch plan and the launch groups."""
+ * the boundary: argument checks and messages without a device, the binding, an older library, the launch plan and the launch groups
+   (loud_group_end, driven over lists of capacities: a sum of exactly 2^26 samples stays one group, one chunk more splits);
+ * the shapes of tests/test_gpu_loudness_shapes.py reach what they are for (tests/loudness_shapes.py: asserted here, without a device)."""
 import ctypes as C
 import math
 import os
@@ -21,6 +27,7 @@ import numpy as np
 import pytest
 
 import loudness_rule as LR
+import loudness_shapes as LS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "zerovox.cpp_amd", "csrc")
@@ -59,9 +66,17 @@ def native_design(exe, rate):
                                  c=np.array([int(v, 16) for v in t[26:75]], np.uint32).view(F), step=int(t[75]))
 
 
+OTHER_RATES = (4000, 5120, 48000, 768000)
+
+
 @pytest.fixture(scope="module")
-def D(exes):
-    return native_design(exes[0], SR)
+def designs(exes):
+    return {rate: native_design(exes[0], rate) for rate in (SR,) + OTHER_RATES}
+
+
+@pytest.fixture(scope="module")
+def D(designs):
+    return designs[SR]
 
 
 # ---- cases --------------------------------------------------------------------------------------------------------------------------------
@@ -71,7 +86,7 @@ def noise(seed, n, amp=0.1):
 
 
 def _cases():
-    """(name, x [total], N, (gain, target, ceiling, flags))"""
+    """(name, x [total], N, (gain, target, ceiling, flags), rate)"""
     none, target, ceiling, both = (1.0, 0.0, 0.0, 0), (1.0, -16.0, 0.0, 1), (2.0, 0.0, 0.25, 2), (1.5, -9.0, 0.2, 3)
     out = []
     for k, N in enumerate((4 * STEP - 1, 4 * STEP, 4 * STEP + 1, 30 * STEP - 1, 30 * STEP, 30 * STEP + 1, 256 * 80, 256 * 80 + 255, 255, 1)):
@@ -89,7 +104,17 @@ def _cases():
     out.append(("denormal", noise(23, 6 * STEP, 1e-40), 6 * STEP, target))
     out.append(("huge", noise(24, 6 * STEP, 1e30), 6 * STEP, ceiling))
     out.append(("zero gain", noise(25, 6 * STEP), 6 * STEP, (0.0, -20.0, 0.5, 3)))
+    out = [c + (SR,) for c in out]
+    for r, rate in enumerate(OTHER_RATES):
+        step = (rate + 5) // 10
+        for k, N in enumerate(rate_lengths(step)):
+            out.append(("%d Hz N=%d" % (rate, N), noise(100 + 10 * r + k, N + 300), N, (none, target, ceiling, both)[(k + r) % 4], rate))
     return out
+
+
+def rate_lengths(step):
+    """N = 0, both sides of four and of thirty steps, 65 blocks (68 steps and a rest) and 129 blocks (132 steps and a rest)"""
+    return (0, 4 * step - 1, 4 * step, 30 * step - 1, 30 * step, 68 * step + 5, 132 * step + 1)
 
 
 @pytest.fixture(scope="module")
@@ -97,11 +122,11 @@ def cases():
     return _cases()
 
 
-def _native(exe, tmp, x, N, q, meter=False):
+def _native(exe, tmp, x, N, q, meter=False, rate=SR):
     src, dst = str(tmp / "in.f32"), str(tmp / "out.f32")
     x.tofile(src)
     fb = lambda v: "%x" % LR.fbits(v)
-    r = subprocess.run([exe, "run", str(SR), str(N), str(x.size), fb(q[0]), fb(q[1]), fb(q[2]), str(q[3]), src, "-" if meter else dst],
+    r = subprocess.run([exe, "run", str(rate), str(N), str(x.size), fb(q[0]), fb(q[1]), fb(q[2]), str(q[3]), src, "-" if meter else dst],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     t = r.stdout.split()
@@ -112,18 +137,18 @@ def _native(exe, tmp, x, N, q, meter=False):
 @pytest.fixture(scope="module")
 def outputs(exes, cases, tmp_path_factory):
     tmp = tmp_path_factory.mktemp("loudness_io")
-    return [[_native(e, tmp, x, N, q) for _, x, N, q in cases] for e in exes]
+    return [[_native(e, tmp, x, N, q, rate=rate) for _, x, N, q, rate in cases] for e in exes]
 
 
 @pytest.fixture(scope="module")
-def restated(D, cases):
-    return [LR.rule(D, x, N, LR.ask(*q)) for _, x, N, q in cases]
+def restated(designs, cases):
+    return [LR.rule(designs[rate], x, N, LR.ask(*q)) for _, x, N, q, rate in cases]
 
 
 # ---- 1. bit for bit ---------------------------------------------------------------------------------------------------------------------------
 
 def test_header_equals_restatement_bit_for_bit(cases, outputs, restated):
-    for (name, x, N, q), (key, y), (res, out) in zip(cases, outputs[0], restated):
+    for (name, x, N, q, rate), (key, y), (res, out) in zip(cases, outputs[0], restated):
         assert key == LR.key(res), (name, key, LR.key(res))
         assert y.size == x.size and (y.view(np.uint32) == out.view(np.uint32)).all(), name
 
@@ -135,8 +160,8 @@ def test_sanitized_build_agrees(cases, outputs):
 
 def test_meter_only_gives_the_same_result(exes, cases, outputs, tmp_path):
     for k in (1, 13):
-        _, x, N, q = cases[k]
-        assert _native(exes[0], tmp_path, x, N, q, meter=True)[0] == outputs[0][k][0]
+        _, x, N, q, rate = cases[k]
+        assert _native(exes[0], tmp_path, x, N, q, meter=True, rate=rate)[0] == outputs[0][k][0]
 
 
 def test_the_cases_reach_what_they_are_for(cases, restated):
@@ -157,9 +182,20 @@ def test_the_cases_reach_what_they_are_for(cases, restated):
     n = by["nan and inf"]
     assert np.isfinite(n.true_peak) and np.isfinite(n.integrated_ms) and n.blocks_gated > 0
     # a ceiling that applied holds: (float)((double)g * tp) <= ceiling
-    for (name, x, N, q), (res, _) in zip(cases, restated):
+    for (name, x, N, q, rate), (res, _) in zip(cases, restated):
         if q[3] & 2:
             assert F(float(res.gain) * res.true_peak) <= F(q[2]), name
+    # the other rates: the block counts on both sides of four and thirty steps, one and two rounds of 64 blocks passed, N = 0
+    for rate in OTHER_RATES:
+        step = (rate + 5) // 10
+        r = [by["%d Hz N=%d" % (rate, N)] for N in rate_lengths(step)]
+        assert [v.blocks for v in r] == [0, 0, 1, 26, 27, 65, 129], rate
+        assert [v.short_term_max_ms > 0.0 for v in r] == [False, False, False, False, True, True, True], rate
+        assert all(v.blocks_gated == v.blocks for v in r), rate               # steady noise: every block counts, in every round
+        z = r[0]
+        assert z.true_peak == 0.0 and z.sample_peak == 0.0 and z.integrated_ms == 0.0 and math.isinf(z.true_peak_dbtp)
+        assert math.isinf(z.integrated_lufs) and math.isinf(z.momentary_max_lufs) and math.isinf(z.short_term_max_lufs)
+    assert [(rate + 5) // 10 for rate in OTHER_RATES] == [400, 512, 4800, 76800]
 
 
 def test_a_non_finite_sample_counts_as_zero(D):
@@ -168,6 +204,42 @@ def test_a_non_finite_sample_counts_as_zero(D):
     x[3000], x[9000] = np.nan, -np.inf
     y[3000], y[9000] = 0.0, 0.0
     assert LR.key(LR.rule(D, x, x.size)[0]) == LR.key(LR.rule(D, y, y.size)[0])
+
+
+def test_some_ceilings_need_the_round_down_step(exes, D, tmp_path):
+    """loud_gain's loop: (float)(ceiling / tp) may have rounded up, and then (float)(g tp) > ceiling.  One fixed waveform, one hundred
+    fixed ceilings (tests/loudness_shapes.py, run on the device by tests/test_gpu_loudness_shapes.py): the restatement says which of
+    them need the step (about one in sixteen does), and the header must agree on every one, bit for bit."""
+    x = LS.round_down_wave()
+    tp, _ = LR.true_peak(D, x, x.size)
+    needs, plain = LS.round_down_split(tp)
+    print("true peak", tp, ":", len(needs), "of", len(LS.ROUND_DOWN_CEILINGS), "ceilings need the step:", [float(c) for c in needs])
+    assert len(LS.ROUND_DOWN_CEILINGS) >= 64 and len(needs) >= 3 and len(plain) >= 3
+    for c in needs:                                                             # exactly one step down, and the promise holds after it
+        g = LR.gain(LR.ask(LS.ROUND_DOWN_GAIN, 0.0, c, LR.CEILING), 0.0, tp)
+        assert LR.fbits(g) == LR.fbits(F(float(c) / tp)) - 1 and F(float(F(float(c) / tp)) * tp) > c and F(float(g) * tp) <= c
+    base = LR.rule(D, x, x.size, out=False)[0]
+    for c in needs + plain[:3]:
+        q = (LS.ROUND_DOWN_GAIN, 0.0, float(c), LR.CEILING)
+        key, y = _native(exes[0], tmp_path, x, x.size, q)
+        want = types.SimpleNamespace(**{**vars(base), "gain": LR.gain(LR.ask(*q), base.integrated_ms, tp)})
+        assert key == LR.key(want), (c, key, LR.key(want))
+        assert (y.view(np.uint32) == (x * want.gain).view(np.uint32)).all(), c
+    assert _native(exes[1], tmp_path, x, x.size, (LS.ROUND_DOWN_GAIN, 0.0, float(needs[0]), LR.CEILING))[0][-1] == LR.fbits(F(float(needs[0]) / tp)) - 1
+
+
+@pytest.mark.parametrize("rate,nf", LS.GATE_CASES)
+def test_the_gate_shapes_reach_their_rounds(designs, rate, nf):
+    """the spans tests/test_gpu_loudness_shapes.py runs through the gate kernel's second and third rounds: their counts, and (asserted
+    inside LS.gate_reach, from the restatement's step energies, blocks and peaks) that the maxima, the blocks the gates drop and the
+    true peak lie where the case wants them"""
+    Dr = designs[rate]
+    want = {(4000, 90): (64, 38, 14), (4000, 91): (65, 39, 14), (4000, 175): (128, 102, 26), (4000, 176): (129, 103, 26),
+            (22050, 436): (56, 30, 64), (22050, 437): (56, 30, 65), (22050, 1500): (201, 175, 220)}[(rate, nf)]
+    for variant in LS.VARIANTS:
+        x = LS.gate_wave(rate, Dr.step, nf, nf + 2, variant)
+        r = LS.gate_reach(Dr, x, nf, variant)
+        assert (r.blocks, r.short_terms, r.tiles) == want, (variant, vars(r))
 
 
 # ---- 2. the design ------------------------------------------------------------------------------------------------------------------------------
@@ -448,6 +520,35 @@ def test_plan_is_one_launch_per_kernel_and_groups_end_at_2_26_samples(exes):
         assert apply_gx == -(-n // 4096) and states_gx == 1 and gy == 3
     src = open(os.path.join(CSRC, "loudness.h")).read()
     assert re.search(r"LOUD_GROUP_SAMPLES\s*=\s*1ull\s*<<\s*26", src) and "sum + p > LOUD_GROUP_SAMPLES" in src
+
+
+GROUP_BATCH = (300, [32768] * 7 + [50, 50, 1])         # (hop, T): the batch tests/test_gpu_loudness_shapes.py sends across a group's end
+
+
+def test_launch_groups_end_at_2_26_padded_samples(exes):
+    """loud_group_end itself, walked as loud_run walks it, against the rule restated (LS.group_ends) and against the ends worked out
+    by hand: capacities are rounded up to whole chunks first, a sum of exactly 2^26 samples stays one group, one chunk more splits, an
+    utterance that alone exceeds the limit is a group of its own, and no group is empty."""
+    def ends(hop, Ts):
+        r = subprocess.run([exes[0], "groups", str(hop)] + [str(t) for t in Ts], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, (r.returncode, r.stderr)
+        got = [int(v) for v in r.stdout.split()]
+        assert got == LS.group_ends(Ts, hop), (hop, Ts, got)
+        assert got[-1] == len(Ts) and all(b > a for a, b in zip([0] + got, got))       # every group holds an utterance; all are covered
+        return got
+    assert ends(256, [1 << 18]) == [1]                                         # exactly 2^26 samples
+    assert ends(256, [1 << 17, 1 << 17]) == [2]                                # a sum that lands on 2^26 stays in one group
+    assert ends(256, [1 << 17, (1 << 17) + 1]) == [1, 2]                       # one more chunk splits
+    assert ends(256, [1 << 17, 1 << 17, 1]) == [2, 3]
+    assert ends(255, [1 << 17, 1 << 17, 1]) == [3]                             # 2^26 - 2^18 samples and a chunk
+    assert ends(257, [1 << 17, 1 << 17]) == [1, 2]
+    assert ends(1, [(1 << 26) - 255, 1]) == [1, 2]                             # the padding counts: 2^26 - 255 samples are 2^26 padded
+    assert ends(1, [(1 << 26) - 256, 1]) == [2] and ends(1, [(1 << 26) - 256, 257]) == [1, 2]
+    assert ends(300, [(1 << 18) + 5] * 3 + [1]) == [1, 2, 3, 4]                # each alone exceeds the limit: a group of its own
+    assert ends(300, [60000, 100000, 100000, 1]) == [2, 4]
+    hop, Ts = GROUP_BATCH
+    assert ends(hop, Ts) == [6, 10] and 6 * 32768 * 300 <= 1 << 26 < 7 * 32768 * 300
+    assert ends(300, [1] * 200) == [200]
 
 
 def test_cli_knows_its_flags_and_refuses_bad_values(tmp_path):

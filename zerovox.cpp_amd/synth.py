@@ -225,10 +225,26 @@ SMALL_V1024 = Geometry(name="small_v1024", emb_dim=112, punct_emb_dim=16, conv_f
                        vp_filter_size=64, ve_n_bins=64, max_seq_len=256, voc_channels=1024)
 VOC_WIDTH_GEOMETRIES = ("small_v256", "small_v496", "small_v768", "small_v1024")
 
+# TINY at other sampling rates (`audio.sampling_rate` is a free KV of the checkpoint format; the hop stays 300).  Loudness takes
+# its 100 ms gating step from the rate, (rate + 5) / 10 samples, and cuts the signal into chunks of 256 (csrc/loudness.h):
+#  * tiny_sr4000: step 400, the lowest rate the design takes — most chunks meet two steps, a step spans two or three chunks;
+#  * tiny_sr5120: step 512, exactly two chunks — no chunk ever holds a step edge, its second run stays empty;
+#  * tiny_sr48000: step 4 800, the rate of the standard's own coefficient table;
+#  * tiny_sr3999: the loader takes it, loudness refuses it (a chunk could meet three steps)
+TINY_SR4000 = Geometry(name="tiny_sr4000", emb_dim=48, punct_emb_dim=16, conv_filter_size=72, encoder_layer=2, encoder_head=2,
+                       vp_filter_size=40, ve_n_bins=16, max_seq_len=64, voc_channels=48, sampling_rate=4000)
+TINY_SR5120 = Geometry(name="tiny_sr5120", emb_dim=48, punct_emb_dim=16, conv_filter_size=72, encoder_layer=2, encoder_head=2,
+                       vp_filter_size=40, ve_n_bins=16, max_seq_len=64, voc_channels=48, sampling_rate=5120)
+TINY_SR48000 = Geometry(name="tiny_sr48000", emb_dim=48, punct_emb_dim=16, conv_filter_size=72, encoder_layer=2, encoder_head=2,
+                        vp_filter_size=40, ve_n_bins=16, max_seq_len=64, voc_channels=48, sampling_rate=48000)
+TINY_SR3999 = Geometry(name="tiny_sr3999", emb_dim=48, punct_emb_dim=16, conv_filter_size=72, encoder_layer=2, encoder_head=2,
+                       vp_filter_size=40, ve_n_bins=16, max_seq_len=64, voc_channels=48, sampling_rate=3999)
+RATE_GEOMETRIES = ("tiny_sr4000", "tiny_sr5120", "tiny_sr48000")
+
 GEOMETRIES = {g.name: g for g in (MEDIUM, TINY, SMALL, MEDIUM8, MEDIUM_H1, MEDIUM_H3, MEDIUM_H4, MEDIUM_H8, MEDIUM_E1024,
                                   MEDIUM_RB357, MEDIUM_RB_WIDE, MEDIUM_RB_DILK, MEDIUM_RB_C1C2, MEDIUM_RB_C2WIDE, MEDIUM_UP4553,
                                   MEDIUM_VOCK5, MEDIUM_E576, MEDIUM_E720, SMALL_E304, MEDIUM_M100, MEDIUM_FFN8, SMALL_V256,
-                                  SMALL_V496, SMALL_V768, SMALL_V1024)}
+                                  SMALL_V496, SMALL_V768, SMALL_V1024, TINY_SR4000, TINY_SR5120, TINY_SR48000, TINY_SR3999)}
 
 
 def sinusoid_table(n_position: int, d_hid: int) -> np.ndarray:
