@@ -30,6 +30,9 @@
  *   zv_loudness_wave   the BS.1770 loudness (LUFS) and true peak (dBTP) of any waveform the caller brings, and the waveform brought to a
  *                      LUFS target under a dBTP ceiling; zv_loudness_wave_batch: a batch of them in one launch per kernel;
  *                      zv_loudness_design: the K-weighting filters, the step and the interpolator for a rate, on the host
+ *   zv_limit_wave      any waveform the caller brings behind a look-ahead peak limiter: a gain, then no sample above a ceiling;
+ *                      zv_limit_wave_batch: a batch of them in one launch per kernel; zv_limit_design: milliseconds as sample counts, on
+ *                      the host
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file       src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -960,6 +963,70 @@ zv_status zv_loudness_wave(zv_model *m, const float *wav, uint32_t T, uint32_t n
 zv_status zv_loudness_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint32_t *T,
                                  const uint32_t *n_frames /* NULL = T */, const zv_loudness *ask /* [n_utt] or NULL */,
                                  zv_loudness_result *res /* [n_utt] */, float *const *out /* array or entries may be NULL */);
+/* ---- limiter: a look-ahead peak limiter behind the loudness stage -----------------------------------------------------------------------
+ * zv_loudness_wave meets a LUFS target under a dBTP ceiling with ONE gain, so where the two conflict the target is missed (step 5
+ * above) — the normal case for speech, whose true peak often lies more than 15 dB above its integrated loudness.  The limiter takes
+ * the gain the target asked for, pulls down the samples around a peak and leaves the rest alone.
+ * zv_limit_wave takes a host waveform of T frames, measures its first N = min(n_frames, T) * hop samples and returns all T * hop samples
+ * limited; zv_limit_wave_batch takes n_utt of them, one launch per kernel per launch group of consecutive utterances (cut as for
+ * zv_loudness_wave_batch), and utterance u receives exactly the bits of its single call.  Both run eagerly on lane 0, are never part of
+ * a captured graph or of the zv_synthesize* chain, and use scratch of lane 0's arena.  The model's rate must lie in 4 000 .. 768 000, and
+ * the interpolator is the loudness design's.  zv_limit_design is host only.
+ *
+ * THE RULE.  Nothing in it is recursive along time and everything behind step 2 is integer, so no result depends on how the work is
+ * split.  Every f64 step is ONE IEEE operation (nothing is contracted); a sample that is not finite or lies outside [0, N) counts as
+ * +0.0 (x'), as in loudness.  ONE = 2^30, W = attack + release + 1.
+ *   1. peaks.  v_f(n), f = 1, 2, 3: loudness step 4's chain over interp[f + 4 k], k = 0 .. 11 ascending from +0.0.  For every integer m:
+ *      p_m = max(|x'_m| as f64, |v_1(m + 6)|, |v_2(m + 6)|, |v_3(m + 6)|), the peak of the interval [m, m + 1) on the 4x grid (the
+ *      interpolator's delay is 6 samples); p_m = 0 outside m in [-6, N + 4].  true_peak_before = max p_m, bit for bit zv_loudness_wave's
+ *      true_peak of the same span; sample_peak_before is its sample_peak.
+ *   2. required gain, 2.30 fixed point.  a_m = (double)gain * p_m; q_m = ONE where a_m <= (double)ceiling, else
+ *      q_m = (uint32_t)(((double)ceiling / a_m) * 2^30): one division, one exact scaling, truncated.  q_m = ONE wherever p_m = 0.
+ *   3. sliding minimum.  m_k = min q_j, j in [k - release, k + attack].
+ *   4. sliding mean.  s_n = floor((sum of m_k, k in [n - attack, n + release]) / W) in 64-bit integers.  Every window of step 3 that
+ *      enters this sum contains n, so s_n <= q_n: the gain has fallen to what a peak needs when the peak arrives; it falls over `attack`
+ *      samples and rises over `release` samples, in straight ramps.
+ *   5. apply, for all n in [0, T * hop): out_n = (float)(((double)wav_n * (double)gain) * ((double)s_n * 2^-30)).  wav_n is used as
+ *      stored (what is not finite passes through IEEE arithmetic); the tail behind N is scaled and not measured.
+ *   6. report.  true_peak_after, sample_peak_after: step 1 on out over [0, N).  min_gain = (float)((double)min s_n * 2^-30) over n in
+ *      [0, N) (1 where N = 0); limited_samples counts the n in [0, N) with s_n < ONE; true_peak_*_dbtp as in loudness step 6 and
+ *      reduction_db = (float)(20 * (L(min s_n * 2^-30) * log10 e)), -inf where min s_n = 0.
+ * THE PROMISE: every finite |out_n|, n in [0, N), is at most ceiling.  fl(|wav_n| gain) <= a_n because p_n >= |x'_n| and rounding is
+ * monotonic; s_n 2^-30 <= q_n 2^-30 <= fl(ceiling / a_n) <= (ceiling / a_n)(1 + 2^-53); so the f64 product of step 5 passes ceiling by
+ * at most a few units of 2^-52 relative, and since ceiling is an f32 value, whose upper neighbour lies 2^-23 relative above it, the
+ * rounding to f32 brings the product back to it.  true_peak_after <= ceiling is NOT promised: a gain that varies in time moves the
+ * peaks between the samples a little.
+ * csrc/limiter.h holds the rule as plain C++ with a host reference, limit_reference(); tests/limiter_rule.py restates it in numpy.
+ *
+ * Arguments: gain finite in [0, 1000] (applied ahead of the limiter: pass the gain a target-only zv_loudness_wave returned); ceiling
+ * in (0, 1], linear; attack in [1, 2047] and release in [1, 6144] samples; flags 0; wav, res and out (or every entry of theirs)
+ * non-NULL — a limiter without an output is the true-peak meter of zv_loudness_wave; 0 < T <= zv_max_frames(); n_frames beyond T counts
+ * as T.  ask == NULL is the identity for every utterance: gain 1, ceiling 1 and zv_limit_design's defaults for the model's rate.
+ * zv_limit_design: attack = floor(attack_ms * sampling_rate / 1000 + 0.5) in f64, brought into [1, 2047], release likewise into
+ * [1, 6144]; 0 ms means the default, 1.5 ms and 60 ms; negative or non-finite milliseconds and a rate outside 4 000 .. 768 000 are refused.
+ * Not covered: more than one channel; a ceiling on the true peak AFTER the limiter; a stage of the zv_synthesize* chain. */
+typedef struct
+{
+    float    gain;                  /* linear, applied ahead of the limiter */
+    float    ceiling;               /* linear, in (0, 1] */
+    uint32_t attack, release;       /* samples */
+    uint32_t flags;                 /* 0 */
+} zv_limiter;
+typedef struct
+{
+    double   true_peak_before, true_peak_after;     /* linear */
+    uint64_t limited_samples;
+    float    sample_peak_before, sample_peak_after;
+    float    min_gain;
+    float    true_peak_before_dbtp, true_peak_after_dbtp, reduction_db;
+} zv_limit_result;
+zv_status zv_limit_design(uint32_t sampling_rate, float attack_ms /* 0: 1.5 */, float release_ms /* 0: 60 */, uint32_t *attack,
+                          uint32_t *release);
+zv_status zv_limit_wave(zv_model *m, const float *wav, uint32_t T, uint32_t n_frames, const zv_limiter *ask, zv_limit_result *res,
+                        float *out /* [T * hop] */);
+zv_status zv_limit_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint32_t *T,
+                              const uint32_t *n_frames /* NULL = T */, const zv_limiter *ask /* [n_utt] or NULL */,
+                              zv_limit_result *res /* [n_utt] */, float *const *out /* [n_utt], every entry [T * hop] */);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

@@ -36,6 +36,7 @@ SYMBOLS = [
     "zv_mel_wave", "zv_mel_wave_batch", "zv_mel_design",
     "zv_mel_align", "zv_mel_align_batch", "zv_align_durations",
     "zv_loudness_wave", "zv_loudness_wave_batch", "zv_loudness_design",
+    "zv_limit_wave", "zv_limit_wave_batch", "zv_limit_design",
 ]
 
 
@@ -624,6 +625,77 @@ def _loudness_ask(who: str, ask):
     return ask
 
 
+class LimiterC(C.Structure):
+    """zv_limiter of include/zerovox_amd.h"""
+    _fields_ = [("gain", C.c_float), ("ceiling", C.c_float), ("attack", C.c_uint32), ("release", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LimitResultC(C.Structure):
+    """zv_limit_result of include/zerovox_amd.h"""
+    _fields_ = [("true_peak_before", C.c_double), ("true_peak_after", C.c_double), ("limited_samples", C.c_uint64),
+                ("sample_peak_before", C.c_float), ("sample_peak_after", C.c_float), ("min_gain", C.c_float),
+                ("true_peak_before_dbtp", C.c_float), ("true_peak_after_dbtp", C.c_float), ("reduction_db", C.c_float)]
+
+
+def limit_design(sampling_rate: int, attack_ms: float = 0.0, release_ms: float = 0.0, lib=None):
+    """zv_limit_design: (attack, release) in samples for milliseconds at a sampling rate; 0 ms means the default (1.5 ms, 60 ms).
+    Host only: no model, no device."""
+    lib = lib or load_library()
+    fn = _stage_symbol(lib, "zv_limit_design")
+    if isinstance(sampling_rate, (bool, np.bool_)) or not isinstance(sampling_rate, (int, np.integer)) or not 0 <= sampling_rate <= 0xffffffff:
+        raise ValueError(f"limit_design: sampling_rate = {sampling_rate!r} must be an integer in [0, 4294967295]")
+    a, r = C.c_uint32(), C.c_uint32()
+    st = fn(int(sampling_rate), float(attack_ms), float(release_ms), C.byref(a), C.byref(r))
+    if st != 0:
+        raise ZvError(st, lib.zv_last_error().decode("utf-8", "replace"))
+    return int(a.value), int(r.value)
+
+
+class Limiter:
+    """What a limiter call asks for (include/zerovox_amd.h "limiter"): a linear gain applied ahead of the limiter, a linear ceiling in
+    (0, 1], and the attack and release in samples.  from_dbtp takes the ceiling in dBTP, the gain in dB and the windows in milliseconds
+    at a sampling rate.  The library checks the values."""
+
+    def __init__(self, gain: float, ceiling: float, attack: int, release: int):
+        self.gain, self.ceiling, self.attack, self.release = float(gain), float(ceiling), int(attack), int(release)
+
+    @classmethod
+    def from_dbtp(cls, dbtp: float, gain_db: float = 0.0, attack_ms: float = 0.0, release_ms: float = 0.0, sampling_rate: int = 0, lib=None):
+        """-1 dBTP behind +6 dB at 22 050 Hz: Limiter.from_dbtp(-1.0, gain_db=6.0, sampling_rate=22050); ceiling and gain become
+        float32(10^(dB / 20)), the windows limit_design's counts (0 ms: the defaults)"""
+        a, r = limit_design(sampling_rate, attack_ms, release_ms, lib)
+        return cls(float(np.float32(10.0 ** (float(gain_db) / 20.0))), float(np.float32(10.0 ** (float(dbtp) / 20.0))), a, r)
+
+    @property
+    def struct(self) -> LimiterC:
+        if not (0 <= self.attack <= 0xffffffff and 0 <= self.release <= 0xffffffff):
+            raise ValueError(f"Limiter: attack = {self.attack} and release = {self.release} must fit 32 bits")
+        return LimiterC(self.gain, self.ceiling, self.attack, self.release, 0)
+
+    def __repr__(self):
+        return f"Limiter(gain={self.gain}, ceiling={self.ceiling}, attack={self.attack}, release={self.release})"
+
+
+class LimitResult:
+    """What a limiter call reports: true_peak_before and true_peak_after (linear, float64), limited_samples, and as float32
+    sample_peak_before, sample_peak_after, min_gain, true_peak_before_dbtp, true_peak_after_dbtp and reduction_db"""
+    FIELDS = tuple(n for n, _ in LimitResultC._fields_)
+
+    def __init__(self, c: LimitResultC):
+        for n in self.FIELDS:
+            v = getattr(c, n)
+            setattr(self, n, np.float32(v) if dict(LimitResultC._fields_)[n] is C.c_float else v)
+
+    def __repr__(self):
+        return "LimitResult(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.FIELDS) + ")"
+
+
+def _limit_ask(who: str, ask):
+    if ask is not None and not isinstance(ask, Limiter):
+        raise TypeError(f"{who}: ask must be a Limiter or None, not {type(ask).__name__}")
+    return ask
+
+
 class EnvelopeC(C.Structure):
     """zv_envelope of include/zerovox_amd.h: the gains' pointer ([n] or NULL) and three integers (a zeroed struct is the identity)"""
     _fields_ = [("phoneme_gain", C.c_void_p), ("ramp_frames", C.c_uint32), ("fade_in_samples", C.c_uint32),
@@ -892,7 +964,10 @@ def _bind(lib):
                            ("zv_align_durations", [u32, vp, u32, vp, u32, vp]),
                            ("zv_loudness_wave", [vp, fp, u32, u32, C.POINTER(LoudnessC), C.POINTER(LoudnessResultC), fp]),
                            ("zv_loudness_wave_batch", [vp, u32, pvp, pu32, pu32, C.POINTER(LoudnessC), C.POINTER(LoudnessResultC), pvp]),
-                           ("zv_loudness_design", [u32, C.POINTER(LoudnessFilterC)])):
+                           ("zv_loudness_design", [u32, C.POINTER(LoudnessFilterC)]),
+                           ("zv_limit_wave", [vp, fp, u32, u32, C.POINTER(LimiterC), C.POINTER(LimitResultC), fp]),
+                           ("zv_limit_wave_batch", [vp, u32, pvp, pu32, pu32, C.POINTER(LimiterC), C.POINTER(LimitResultC), pvp]),
+                           ("zv_limit_design", [u32, C.c_float, C.c_float, pu32, pu32])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
@@ -1328,6 +1403,50 @@ class Model:
         self._chk(fn(self.h, n, P(*[w.ctypes.data for w, _ in ws]), U(*[T for _, T in ws]),
                      None if n_frames is None else U(*[int(f) for f in n_frames]), qs, res, P(*[None if o is None else o.ctypes.data for o in outs])))
         return [(LoudnessResult(r), o) for r, o in zip(res, outs)]
+
+    def limit_wave(self, wav, ask=None, n_frames=None):
+        """zv_limit_wave: the waveform behind the look-ahead peak limiter, its first n_frames frames (None: all of it) measured ->
+        (LimitResult, float32 [T * hop]); ask: a Limiter or None (gain 1, ceiling 1, the default windows of the model's rate)"""
+        fn = _stage_symbol(self.lib, "zv_limit_wave")
+        q = _limit_ask("limit_wave", ask)
+        w, T = _waveform(self.hp.audio_hop_size, "limit_wave", wav)
+        out = np.empty_like(w)
+        res = LimitResultC()
+        st = q.struct if q is not None else None
+        self._chk(fn(self.h, _ptr(w), T, T if n_frames is None else int(n_frames), C.byref(st) if q is not None else None, C.byref(res), _ptr(out)))
+        return LimitResult(res), out
+
+    def limit_wave_batch(self, wavs, asks=None, n_frames=None):
+        """zv_limit_wave_batch: waveforms [T_u * hop], one per utterance, through ONE launch per kernel per launch group -> the list of
+        (LimitResult, waveform), each with the bits of its limit_wave; asks: None or one Limiter per utterance; n_frames: None or one
+        count per utterance"""
+        fn = _stage_symbol(self.lib, "zv_limit_wave_batch")
+        ws = [_waveform(self.hp.audio_hop_size, f"limit_wave_batch: utterance {u}", w) for u, w in enumerate(wavs)]
+        n = len(ws)
+        if asks is not None and len(asks) != n:
+            raise ValueError(f"limit_wave_batch: {len(asks)} asks for {n} utterances")
+        if n_frames is not None and len(n_frames) != n:
+            raise ValueError(f"limit_wave_batch: {len(n_frames)} frame counts for {n} utterances")
+        qs = None
+        if asks is not None:
+            if any(a is None for a in asks):
+                raise TypeError("limit_wave_batch: asks holds None (give every utterance a Limiter, or asks=None for the identity)")
+            qs = (LimiterC * n)(*[_limit_ask(f"limit_wave_batch: utterance {u}", a).struct for u, a in enumerate(asks)])
+        outs = [np.empty_like(w) for w, _ in ws]
+        res = (LimitResultC * n)()
+        P, U = C.c_void_p * n, C.c_uint32 * n
+        self._chk(fn(self.h, n, P(*[w.ctypes.data for w, _ in ws]), U(*[T for _, T in ws]),
+                     None if n_frames is None else U(*[int(f) for f in n_frames]), qs, res, P(*[o.ctypes.data for o in outs])))
+        return [(LimitResult(r), o) for r, o in zip(res, outs)]
+
+    def deliver(self, wav, lufs, dbtp, n_frames=None):
+        """A delivery chain for "lufs LUFS, dbtp dBTP": a target-only loudness meter, the limiter with that gain under the ceiling (the
+        default windows), then the meter on the result -> (LoudnessResult before, LimitResult, LoudnessResult after, waveform)"""
+        before, _ = self.loudness_wave(wav, Loudness.from_lufs(lufs), n_frames, apply=False)
+        a, r = limit_design(self.hp.audio_sampling_rate, lib=self.lib)
+        lim, out = self.limit_wave(wav, Limiter(float(before.gain), float(np.float32(10.0 ** (float(dbtp) / 20.0))), a, r), n_frames)
+        after, _ = self.loudness_wave(out, None, n_frames, apply=False)
+        return before, lim, after, out
 
     def resynthesize(self, wav, params=None) -> np.ndarray:
         """analysis-resynthesis: vocode(mel_wave(wav)), the acceptance check of a converted vocoder checkpoint.  params must keep the

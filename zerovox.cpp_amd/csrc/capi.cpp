@@ -1978,6 +1978,150 @@ zv_status zv_loudness_design(uint32_t sampling_rate, zv_loudness_filter *out)
     });
 }
 
+// ---- limiter (zv_limit_wave, zv_limit_wave_batch, zv_limit_design; the rule: limiter.h): host waveforms in, per utterance the limited
+// waveform and the report out, eagerly, on lane 0.  A batch runs as launch groups of consecutive utterances (loud_group_end), each ONE
+// launch per kernel.  I/O block of a group: [samples, every utterance on whole chunks][limited samples, likewise][q, every utterance on
+// whole tiles][m][peaks before][peaks after][statistics][segment table][asks][design][result rows].
+static_assert(sizeof(zv_limit_result) == sizeof(zv::LimitRow) && offsetof(zv_limit_result, min_gain) == offsetof(zv::LimitRow, min_gain) &&
+                  offsetof(zv_limit_result, limited_samples) == offsetof(zv::LimitRow, limited_samples),
+              "zv_limit_result is limiter.h's LimitRow");
+
+static void check_limiter(const char *fn, const char *who, const zv_limiter &q)
+{
+    const char *field = zv::limit_check(q.gain, q.ceiling, q.attack, q.release, q.flags);
+    if (!field) return;
+    if (!strcmp(field, "flags")) zv::fail(ZV_ERR_ARG, "%s: %slimiter flags = %u must be 0", fn, who, q.flags);
+    if (!strcmp(field, "attack")) zv::fail(ZV_ERR_ARG, "%s: %slimiter attack = %u is outside [1, %u] samples", fn, who, q.attack, zv::LIMIT_MAX_ATTACK);
+    if (!strcmp(field, "release")) zv::fail(ZV_ERR_ARG, "%s: %slimiter release = %u is outside [1, %u] samples", fn, who, q.release, zv::LIMIT_MAX_RELEASE);
+    const float v = !strcmp(field, "gain") ? q.gain : q.ceiling;
+    if (!std::isfinite(v)) zv::fail(ZV_ERR_ARG, "%s: %slimiter %s = %g is not finite", fn, who, field, (double)v);
+    if (!strcmp(field, "gain")) zv::fail(ZV_ERR_ARG, "%s: %slimiter gain = %g is outside [0, 1000]", fn, who, (double)v);
+    zv::fail(ZV_ERR_ARG, "%s: %slimiter ceiling = %g is outside (0, 1]", fn, who, (double)v);
+}
+
+// the checks that need no model: res, then every utterance's ask by field
+static void check_limit_args(const char *fn, bool batch, uint32_t n_utt, const zv_limiter *ask, const zv_limit_result *res)
+{
+    if (!res) zv::fail(ZV_ERR_ARG, "%s: res is NULL", fn);
+    char who[32] = "";
+    for (uint32_t u = 0; ask && u < n_utt; u++)
+    {
+        if (batch) snprintf(who, sizeof who, "utterance %u: ", u);
+        check_limiter(fn, who, ask[u]);
+    }
+}
+
+static void limit_run(zv_model *m, const char *fn, uint32_t n_utt, const float *const *wav, const uint32_t *T, const uint32_t *n_frames,
+                      const zv_limiter *ask, zv_limit_result *res, float *const *out)
+{
+#if !defined(__HIP_DEVICE_COMPILE__)      // (loudness.h keeps its host half out of device passes)
+    Model &M = *m->m;
+    const uint32_t hop = M.hp.audio_hop_size, rate = M.hp.audio_sampling_rate;
+    zv::LoudFilter F;
+    zv::LimitAsk identity{1.0f, 1.0f, 0u, 0u};
+    if (zv::loud_design(rate, &F) || zv::limit_design(rate, 0.0f, 0.0f, &identity.attack, &identity.release))
+        zv::fail(ZV_ERR_ARG, "%s: audio_sampling_rate = %u must be in %u .. %u", fn, rate, zv::LOUD_MIN_RATE, zv::LOUD_MAX_RATE);
+    use_lane0(m);
+    std::vector<zv::LimitSeg> segs;
+    std::vector<zv::LimitAsk> asks;
+    std::vector<zv::LimitRow> rows;
+    for (uint32_t g0 = 0; g0 < n_utt;)
+    {
+        const uint32_t g1 = zv::loud_group_end(g0, n_utt, T, hop), n = g1 - g0;
+        segs.resize(n);
+        asks.resize(n);
+        rows.resize(n);
+        int64_t x0 = 0, q0 = 0, m0 = 0, max_qlen = 0, max_total = 0, max_halo = 0;
+        size_t tiles = 0, stats = 0, measured = 0, capacity = 0;
+        for (uint32_t k = 0; k < n; k++)
+        {
+            const uint32_t u = g0 + k, nf = n_frames ? std::min(n_frames[u], T[u]) : T[u];
+            const int64_t N = (int64_t)nf * hop, total = (int64_t)T[u] * hop;
+            asks[k] = ask ? zv::LimitAsk{ask[u].gain, ask[u].ceiling, ask[u].attack, ask[u].release} : identity;
+            const int64_t H = zv::limit_halo(asks[k]), qlen = zv::limit_qlen(total, H);
+            segs[k] = zv::LimitSeg{x0, N, total, q0, m0, (int32_t)tiles, (int32_t)stats};
+            x0 += (int64_t)zv::loud_padded((uint64_t)total);
+            q0 += zv::limit_tiles(qlen) * zv::LIMIT_TILE;
+            m0 += (zv::limit_mlen(total, H) + 3) / 4 * 4;
+            tiles += (size_t)zv::limit_tiles(qlen);
+            stats += (size_t)zv::limit_tiles(total);
+            max_qlen = std::max(max_qlen, qlen);
+            max_total = std::max(max_total, total);
+            max_halo = std::max(max_halo, H);
+            measured += (size_t)N;
+            capacity += (size_t)total;
+        }
+        Layout L;
+        const size_t o_wav = L.at((size_t)x0 * 4), o_out = L.at((size_t)x0 * 4), o_q = L.at((size_t)q0 * 4), o_m = L.at((size_t)m0 * 4),
+                     o_pb = L.at(tiles * 16), o_pa = L.at(tiles * 16), o_st = L.at(stats * 8), o_seg = L.at((size_t)n * sizeof(zv::LimitSeg)),
+                     o_ask = L.at((size_t)n * sizeof(zv::LimitAsk)), o_des = L.at(sizeof(zv::LoudFilter)), o_row = L.at((size_t)n * sizeof(zv::LimitRow));
+        char *io = (char *)M.io_scratch(L.size());
+        for (uint32_t k = 0; k < n; k++)
+            ZV_HIP(hipMemcpyAsync(io + o_wav + (size_t)segs[k].x0 * 4, wav[g0 + k], (size_t)segs[k].total * 4, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_seg, segs.data(), (size_t)n * sizeof(zv::LimitSeg), hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_ask, asks.data(), (size_t)n * sizeof(zv::LimitAsk), hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_des, &F, sizeof F, hipMemcpyHostToDevice, M.stream()));
+        const zv::LimitJob job{(const float *)(io + o_wav), (float *)(io + o_out), (uint32_t *)(io + o_q), (uint32_t *)(io + o_m), (uint64_t *)(io + o_pb),
+                               (uint64_t *)(io + o_pa), (uint32_t *)(io + o_st), (zv::LimitRow *)(io + o_row), (const zv::LimitSeg *)(io + o_seg),
+                               (const zv::LimitAsk *)(io + o_ask), (const zv::LoudFilter *)(io + o_des), (int)n, (int)max_halo, max_qlen, max_total};
+        M.limit_launches(job, measured, capacity, (size_t)q0);
+        ZV_HIP(hipMemcpyAsync(rows.data(), io + o_row, (size_t)n * sizeof(zv::LimitRow), hipMemcpyDeviceToHost, M.stream()));
+        for (uint32_t k = 0; k < n; k++)
+            ZV_HIP(hipMemcpyAsync(out[g0 + k], io + o_out + (size_t)segs[k].x0 * 4, (size_t)segs[k].total * 4, hipMemcpyDeviceToHost, M.stream()));
+        M.sync();                             // (segs, asks, rows and F are pageable and reused by the next group)
+        for (uint32_t k = 0; k < n; k++) memcpy(&res[g0 + k], &rows[k], sizeof(zv::LimitRow));
+        g0 = g1;
+    }
+#endif
+}
+
+zv_status zv_limit_wave(zv_model *m, const float *wav, uint32_t T, uint32_t n_frames, const zv_limiter *ask, zv_limit_result *res, float *out)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!m) zv::fail(ZV_ERR_ARG, "%s: m is NULL", fn);
+        if (!wav) zv::fail(ZV_ERR_ARG, "%s: wav is NULL", fn);
+        if (!out) zv::fail(ZV_ERR_ARG, "%s: out is NULL (a limiter without an output is zv_loudness_wave's true-peak meter)", fn);
+        check_limit_args(fn, false, 1, ask, res);
+        try
+        {
+            check_T(*m->m, T);
+        }
+        catch (const zv::Error &e)
+        {
+            zv::fail(e.status, "%s: %s", fn, e.what());
+        }
+        limit_run(m, fn, 1, &wav, &T, &n_frames, ask, res, &out);
+    });
+}
+
+zv_status zv_limit_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint32_t *T, const uint32_t *n_frames,
+                              const zv_limiter *ask, zv_limit_result *res, float *const *out)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!m) zv::fail(ZV_ERR_ARG, "%s: m is NULL", fn);
+        check_limit_args(fn, true, n_utt, ask, res);
+        check_stage_args(fn, m, n_utt, {{"wav", wav, true}, {"out", out, true}}, nullptr, T);
+        limit_run(m, fn, n_utt, wav, T, n_frames, ask, res, out);
+    });
+}
+
+// The window lengths: host only, no model, no device (limiter.h limit_design).
+zv_status zv_limit_design(uint32_t sampling_rate, float attack_ms, float release_ms, uint32_t *attack, uint32_t *release)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!attack) zv::fail(ZV_ERR_ARG, "%s: attack is NULL", fn);
+        if (!release) zv::fail(ZV_ERR_ARG, "%s: release is NULL", fn);
+        const char *field = zv::limit_design(sampling_rate, attack_ms, release_ms, attack, release);
+        if (!field) return;
+        if (!strcmp(field, "sampling_rate"))
+            zv::fail(ZV_ERR_ARG, "%s: sampling_rate = %u must be in %u .. %u", fn, sampling_rate, zv::LOUD_MIN_RATE, zv::LOUD_MAX_RATE);
+        zv::fail(ZV_ERR_ARG, "%s: %s = %g must be finite and >= 0 (0: the default)", fn, field, (double)(!strcmp(field, "attack_ms") ? attack_ms : release_ms));
+    });
+}
+
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)
 {
     return guarded([&] {

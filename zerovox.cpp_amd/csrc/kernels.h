@@ -22,6 +22,7 @@
 #include "mel.h"          // mel analysis: MEL_SLAB_STRIDE, MEL_TABLE_BYTES, the parameter block
 #include "align.h"        // mel alignment: AlignPair, AlignRow, the tiles and ALIGN_DP_ROWS
 #include "loudness.h"     // loudness: LoudJob, LoudSeg, LoudAsk, LoudRow, LoudFilter
+#include "limiter.h"      // limiter: LimitJob, LimitSeg, LimitAsk, LimitRow
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -543,5 +544,16 @@ hipError_t launch_loud_states(hipStream_t s, const LoudJob &j);
 hipError_t launch_loud_peak(hipStream_t s, const LoudJob &j);
 hipError_t launch_loud_gate(hipStream_t s, const LoudJob &j);
 hipError_t launch_loud_apply(hipStream_t s, const LoudJob &j);
+
+// ---- limiter (include/zerovox_amd.h "limiter", limiter.h): five passes over ONE launch group of utterances (LimitJob), a launch each
+// whatever the group (stage_plan.h limit_plan).  segs[nseg] says where an utterance's samples, q, m, peak tiles and statistics lie
+// (LimitSeg); wav, out, q and m are 16-byte aligned, every utterance's q region holds whole tiles of LIMIT_TILE entries.
+//   peak (before): q per sample and peaks_before per tile from wav;  min: m from q;  mean: out and stats from m and wav;
+//   peak (after): peaks_after per tile from out;  reduce: rows[u] = the result (LimitRow)
+// hipErrorInvalidValue: a null or misaligned pointer, or a group limit_plan does not accept.
+hipError_t launch_limit_peak(hipStream_t s, const LimitJob &j, bool after);
+hipError_t launch_limit_min(hipStream_t s, const LimitJob &j);
+hipError_t launch_limit_mean(hipStream_t s, const LimitJob &j);
+hipError_t launch_limit_reduce(hipStream_t s, const LimitJob &j);
 
 }  // namespace zv

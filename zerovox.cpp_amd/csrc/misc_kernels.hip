@@ -14,4 +14,5 @@
 #include "mel_kernels.hip"            // mel analysis
 #include "align_kernels.hip"          // mel alignment
 #include "loudness_kernels.hip"       // loudness
+#include "limiter_kernels.hip"        // limiter
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

@@ -254,6 +254,8 @@ class Model
     // the launches of loudness over one launch group of utterances, likewise (kernels.h launch_loud_*): five of them measure, the sixth
     // scales (apply: the caller wants the waveform back); samples: the group's measured samples, capacity: the samples it scales
     void loud_launches(const LoudJob &job, bool apply, size_t samples, size_t capacity);
+    // the launches of the limiter over one launch group of utterances, likewise (kernels.h launch_limit_*); entries: the group's q entries
+    void limit_launches(const LimitJob &job, size_t samples, size_t capacity, size_t entries);
 
     // scratch for host-buffer entry points (grows on demand)
     void *io_scratch(size_t bytes);

@@ -12,6 +12,7 @@
 #include "knobs.h"
 #include "mel.h"            // MEL_TILE_FRAMES, MEL_ROWS_FRAMES, MEL_MAX_MELS
 #include "loudness.h"       // LOUD_CHUNK, LOUD_WG_CHUNKS, LOUD_TP_TILE
+#include "limiter.h"        // LIMIT_TILE, LIMIT_MAX_HALO
 
 namespace zv
 {
@@ -164,6 +165,31 @@ inline LoudPlan loud_plan(int64_t max_N, int64_t max_total, int nseg, uint32_t s
     const bool ok = max_total >= 1 && max_N >= 0 && max_N <= max_total && nseg >= 1 && step >= (uint32_t)LOUD_CHUNK;
     return LoudPlan{ok, (int)loud_chunks(max_N), (int)((loud_chunks(max_N) + LOUD_WG_CHUNKS - 1) / LOUD_WG_CHUNKS), (int)loud_tp_tiles(max_N),
                     (int)(max_N / (step ? step : 1u)), (int)((max_total + LOUD_APPLY_TILE - 1) / LOUD_APPLY_TILE), (nseg + 63) / 64, nseg};
+}
+
+// ---- limiter (limiter_kernels.hip): ONE launch per kernel over a launch group's utterances ----
+// A workgroup of the minimum and mean passes stages its LIMIT_TILE outputs' windows, LIMIT_TILE + halo entries: the minimum pass as u32
+// (the entries, over which the prefix minima are written) with LIMIT_TILE suffix minima behind them, the mean pass as 48-bit prefix sums
+// (a u32 and a u16 array) with a zero in front.  At the largest halo that is 48 KB and 60 KB: three and two workgroups fit a CU's
+// 160 KB.  LIMIT_LDS_TAIL bytes behind them hold the waves' partial results.
+constexpr int LIMIT_LDS_TAIL = 64;
+struct LimitPlan
+{
+    bool   ok;
+    int    peak_gx;             // the peak passes: tiles of LIMIT_TILE entries of the longest q
+    int    min_gx;              // the minimum pass: tiles of the longest m (at most the longest capacity + the largest halo)
+    int    mean_gx;             // the mean pass: tiles of the longest capacity
+    int    gy;                  // utterances: grid y of those passes, grid x of the reduction
+    int    stage;               // entries a workgroup stages, rounded up to 4
+    size_t min_lds, mean_lds;   // dynamic LDS of the two passes, in bytes
+};
+inline LimitPlan limit_plan(int64_t max_qlen, int64_t max_total, int max_halo, int nseg)
+{
+    const bool ok = max_total >= 1 && max_halo >= 2 && max_halo <= LIMIT_MAX_HALO && max_qlen >= limit_qlen(max_total, 2) && max_qlen <= limit_qlen(max_total, max_halo) &&
+                    nseg >= 1 && nseg <= 65535;
+    const int stage = limit_stage(max_halo);
+    return LimitPlan{ok, (int)limit_tiles(max_qlen), (int)limit_tiles(max_total + max_halo), (int)limit_tiles(max_total), nseg, stage,
+                     (size_t)(stage + LIMIT_TILE) * 4 + LIMIT_LDS_TAIL, (size_t)(stage + 4) * 6 + LIMIT_LDS_TAIL};
 }
 
 }  // namespace zv

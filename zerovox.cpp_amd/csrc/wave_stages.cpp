@@ -139,4 +139,19 @@ void Model::loud_launches(const LoudJob &job, bool apply, size_t samples, size_t
     if (apply) ZV_LAUNCH("loud_apply", 8.0 * (double)capacity, (double)capacity, launch_loud_apply(stream(), job));
 }
 
+// Limiter (limiter.h): no stage of the chain either — the stand-alone entry points' launches over one launch group of utterances.
+void Model::limit_launches(const LimitJob &job, size_t samples, size_t capacity, size_t entries)
+{
+    const double n = (double)samples, cap = (double)capacity, q = (double)entries;
+    // algorithmic bytes: the measured samples read and a q written per entry; q read and m written; m and the samples read and the
+    // output written; the output's measured span read.  Operations: 3 x 12 multiply-adds per sample for a peak pass and the required
+    // gain's multiply and divide; three comparisons per entry and scan, two scans; three additions per entry and a 64-bit division and
+    // four f64 operations per sample.
+    ZV_LAUNCH("limit_peak", 4.0 * n + 4.0 * q, 2.0 * 36.0 * n + 2.0 * n, launch_limit_peak(stream(), job, false));
+    ZV_LAUNCH("limit_min", 8.0 * q, 6.0 * q, launch_limit_min(stream(), job));
+    ZV_LAUNCH("limit_mean", 12.0 * cap + 4.0 * q, 3.0 * q + 5.0 * cap, launch_limit_mean(stream(), job));
+    ZV_LAUNCH("limit_peak_after", 4.0 * n, 2.0 * 36.0 * n, launch_limit_peak(stream(), job, true));
+    ZV_LAUNCH("limit_reduce", 24.0 * q / LIMIT_TILE, 0.0, launch_limit_reduce(stream(), job));
+}
+
 }  // namespace zv

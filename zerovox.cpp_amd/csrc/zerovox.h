@@ -102,6 +102,9 @@ class HiFiGAN
     // true peak (dBTP) and, where out [max_seq_len * hop_size] is given, the waveform under ask's gain, target and ceiling (nullptr: the
     // identity, a meter)
     zv_loudness_result loudness(const float *wav, const zv_loudness *ask = nullptr, float *out = nullptr);
+    // (not in the reference) the stage behind it: zv_limit_wave over wav [max_seq_len * hop_size] — the look-ahead peak limiter; out
+    // [max_seq_len * hop_size] is required; ask nullptr: gain 1, ceiling 1, the default windows.
+    zv_limit_result limit(const float *wav, const zv_limiter *ask, float *out);
 
   private:
     zv_model *model;
@@ -187,6 +190,9 @@ class ZeroVOXModel
     // loudness (include/zerovox_amd.h "loudness"): zv_loudness_wave over any waveform of T frames at the model's rate, its first
     // n_frames measured; ask nullptr: the identity; out [T * hop] or nullptr (a meter).  Next to HiFiGAN::loudness, for other lengths.
     zv_loudness_result loudness(const float *wav, uint32_t T, uint32_t n_frames, const zv_loudness *ask = nullptr, float *out = nullptr);
+    // limiter (include/zerovox_amd.h "limiter"): zv_limit_wave over any waveform of T frames at the model's rate, its first n_frames
+    // measured; ask nullptr: gain 1, ceiling 1, the default windows; out [T * hop].  Next to HiFiGAN::limit, for other lengths.
+    zv_limit_result limit(const float *wav, uint32_t T, uint32_t n_frames, const zv_limiter *ask, float *out);
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }

@@ -114,6 +114,13 @@ zv_loudness_result HiFiGAN::loudness(const float *wav, const zv_loudness *ask, f
     return res;
 }
 
+zv_limit_result HiFiGAN::limit(const float *wav, const zv_limiter *ask, float *out)
+{
+    zv_limit_result res{};
+    chk(zv_limit_wave(model, wav, max_seq_len, max_seq_len, ask, &res, out));
+    return res;
+}
+
 // ---------------------------------------------------------------------------------------------------
 
 ZeroVOXModel::ZeroVOXModel(const std::string &fname)
@@ -242,6 +249,13 @@ zv_loudness_result ZeroVOXModel::loudness(const float *wav, uint32_t T, uint32_t
 {
     zv_loudness_result res{};
     chk(zv_loudness_wave(model, wav, T, n_frames, ask, &res, out));
+    return res;
+}
+
+zv_limit_result ZeroVOXModel::limit(const float *wav, uint32_t T, uint32_t n_frames, const zv_limiter *ask, float *out)
+{
+    zv_limit_result res{};
+    chk(zv_limit_wave(model, wav, T, n_frames, ask, &res, out));
     return res;
 }
 

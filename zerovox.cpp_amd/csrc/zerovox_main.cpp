@@ -82,6 +82,12 @@
 //            --lufs / --true-peak-dbtp would apply.  Without --loudness the two flags normalise a synthesis run: the finished waveform
 //            (what -o receives) passes through the call before it is written.  --lufs in [-70, 0], --true-peak-dbtp <= 0;
 //            --true-peak-dbtp alone is a ceiling without a target.  A bad value is a usage error.
+//   --limit [IN.wav], --limit-dbtp P, --limit-gain-db G, --limit-attack-ms A, --limit-release-ms R
+//            --limit IN.wav -o OUT.wav: no synthesis; a mono PCM16 RIFF file at the model's rate through the look-ahead peak limiter
+//            (zv_limit_wave): G dB of gain (default 0) ahead of it, a ceiling of P dBTP (required, <= 0), windows of A and R ms (default
+//            1.5 and 60); the report is printed and the limited waveform written.  --limit without a file, together with --lufs L
+//            --true-peak-dbtp P on a synthesis run, meets the ceiling with the limiter instead of backing the gain off: the gain of the
+//            target alone goes ahead of the limiter, and the loudness of what was written is printed too.  A bad value is a usage error.
 //   --time-like REF.wav
 //            with the synthesis flags: the utterance with the timing of the reference, a mono PCM16 RIFF file at the model's rate.
 //            The utterance is synthesised (fitted), its mel rows are aligned to the reference's, the phoneme boundaries move onto the
@@ -121,6 +127,7 @@ static void usage(FILE *f)
                "               [--mel-fmin HZ] [--mel-fmax HZ] [--mel-centre SAMPLE] [--mel-pad reflect|zero]\n"
                "       zerovox -m model.gguf --align a.f32 b.f32 --mel-width M [--align-scale S] [--align-normalise] [--map-out map.tsv]\n"
                "       zerovox -m model.gguf --loudness in.wav [--lufs L] [--true-peak-dbtp P]\n"
+               "       zerovox -m model.gguf --limit in.wav -o out.wav --limit-dbtp P [--limit-gain-db G] [--limit-attack-ms A] [--limit-release-ms R]\n"
                "       zerovox ... --lufs L [--true-peak-dbtp P]   (with the synthesis flags)\n"
                "       zerovox ... --time-like ref.wav   (with the synthesis flags)\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
@@ -429,6 +436,48 @@ static void print_loudness(const char *what, const zv_loudness_result &r)
 }
 
 // --loudness IN.wav: the file's BS.1770 report (zv_loudness_wave, a meter: nothing is written); the file as for --analyze
+static void print_limit(const char *what, const zv_limit_result &r)
+{
+    printf("%s: true peak %.2f dBTP before, %.2f dBTP after (sample peak %.6f before, %.6f after), least gain %.6f (%.2f dB), "
+           "limited samples %llu\n",
+           what, (double)r.true_peak_before_dbtp, (double)r.true_peak_after_dbtp, (double)r.sample_peak_before, (double)r.sample_peak_after,
+           (double)r.min_gain, (double)r.reduction_db, (unsigned long long)r.limited_samples);
+}
+
+// what --limit-dbtp, --limit-gain-db and the two windows ask for at a rate
+struct LimitFlags { float dbtp = 0.0f, gain_db = 0.0f, attack_ms = 0.0f, release_ms = 0.0f; bool have_dbtp = false; };
+static zv_limiter limit_ask(const LimitFlags &f, uint32_t rate, float gain, float ceiling)
+{
+    zv_limiter q = {gain, ceiling, 0u, 0u, 0u};
+    if (zv_limit_design(rate, f.attack_ms, f.release_ms, &q.attack, &q.release) != ZV_OK) throw std::runtime_error(zv_last_error());
+    return q;
+}
+
+// --limit IN.wav -o OUT.wav: the file through zv_limit_wave; the file as for --analyze
+static int limit_file(const std::string &model_path, const std::string &in_path, const std::string &out_path, const LimitFlags &f)
+{
+    uint32_t rate = 0;
+    const std::vector<float> pcm = read_pcm16("--limit", in_path, rate);
+    zv_model *m = nullptr;
+    if (zv_model_load(model_path.c_str(), 0, &m) != ZV_OK) throw std::runtime_error(zv_last_error());
+    struct Free { zv_model *m; ~Free() { zv_model_free(m); } } free_model{m};
+    zv_hparams hp;
+    if (zv_model_get_hparams(m, &hp) != ZV_OK) throw std::runtime_error(zv_last_error());
+    if (rate != hp.audio_sampling_rate)
+        throw std::runtime_error("--limit: '" + in_path + "' is at " + std::to_string(rate) + " Hz, the model at " + std::to_string(hp.audio_sampling_rate) + " Hz (nothing is resampled)");
+    const size_t T = pcm.size() / hp.audio_hop_size;
+    if (T == 0 || T > zv_max_frames(m))
+        throw std::runtime_error("--limit: '" + in_path + "' holds " + std::to_string(T) + " frames of " + std::to_string(hp.audio_hop_size) + " samples, 1 .. " + std::to_string(zv_max_frames(m)) + " are needed");
+    const zv_limiter q = limit_ask(f, rate, (float)pow(10.0, (double)f.gain_db / 20.0), (float)pow(10.0, (double)f.dbtp / 20.0));
+    std::vector<float> out(T * hp.audio_hop_size);
+    zv_limit_result r;
+    if (zv_limit_wave(m, pcm.data(), (uint32_t)T, (uint32_t)T, &q, &r, out.data()) != ZV_OK) throw std::runtime_error(zv_last_error());
+    print_limit(in_path.c_str(), r);
+    if (zv_write_wav(out_path.c_str(), out.data(), out.size(), hp.audio_sampling_rate) != ZV_OK) throw std::runtime_error(zv_last_error());
+    printf("Successfully created %s with %zu samples (%zu frames).\n", out_path.c_str(), out.size(), T);
+    return 0;
+}
+
 static int loudness_file(const std::string &model_path, const std::string &in_path, const zv_loudness &q)
 {
     uint32_t rate = 0;
@@ -496,6 +545,9 @@ int main(int argc, char **argv)
     std::string analyze_path, melout_path, resynth_path;      // --analyze, --mel-out, --resynth
     std::string loudness_path;                                 // --loudness
     zv_loudness loud_q = {1.0f, 0.0f, 0.0f, 0u};               // --lufs, --true-peak-dbtp
+    bool limit = false;                                        // --limit
+    std::string limit_path;                                    // --limit IN.wav
+    LimitFlags limit_f;                                        // --limit-dbtp, --limit-gain-db, --limit-attack-ms, --limit-release-ms
     zv_mel mel_q{};                                            // --mel-fmin, --mel-fmax, --mel-centre, --mel-pad
     mel_q.log = 1;
     mel_q.pad = 1;
@@ -628,6 +680,26 @@ int main(int argc, char **argv)
         else if (a == "--map-out") map_path = need("--map-out"), align_flag = true;
         else if (a == "--time-like") like_path = need("--time-like");
         else if (a == "--loudness") loudness_path = need("--loudness");
+        else if (a == "--limit")
+        {
+            limit = true;
+            if (i + 1 < argc && argv[i + 1][0] != '-') limit_path = argv[++i];      // (a file; without one the flag joins --lufs / --true-peak-dbtp)
+        }
+        else if (a == "--limit-dbtp" || a == "--limit-gain-db" || a == "--limit-attack-ms" || a == "--limit-release-ms")
+        {
+            const float v = parse_flag_float(a.c_str(), need(a.c_str()));
+            const bool ms = a == "--limit-attack-ms" || a == "--limit-release-ms";
+            if (a == "--limit-dbtp" ? !(v <= 0.0f && v >= -200.0f) : ms ? !(v > 0.0f && v <= 10000.0f) : !(v >= -200.0f && v <= 60.0f))
+            {
+                fprintf(stderr, "zerovox: %s %g is outside %s\n", a.c_str(), (double)v, a == "--limit-dbtp" ? "[-200, 0]" : ms ? "(0, 10000]" : "[-200, 60]");
+                usage(stderr);
+                return 2;
+            }
+            if (a == "--limit-dbtp") limit_f.dbtp = v, limit_f.have_dbtp = true;
+            else if (a == "--limit-gain-db") limit_f.gain_db = v;
+            else if (a == "--limit-attack-ms") limit_f.attack_ms = v;
+            else limit_f.release_ms = v;
+        }
         else if (a == "--lufs" || a == "--true-peak-dbtp")
         {
             const float v = parse_flag_float(a.c_str(), need(a.c_str()));
@@ -803,6 +875,30 @@ int main(int argc, char **argv)
         usage(stderr);
         return 2;
     }
+    if (!limit_path.empty() && (!loudness_path.empty() || !analyze_path.empty() || !align_a.empty() || !like_path.empty() || planning))
+    {
+        fprintf(stderr, "zerovox: --limit IN.wav and --loudness, --analyze, --align, --time-like, --plan exclude each other\n");
+        usage(stderr);
+        return 2;
+    }
+    if (!limit_path.empty() && !limit_f.have_dbtp)
+    {
+        fprintf(stderr, "zerovox: --limit IN.wav needs --limit-dbtp P\n");
+        usage(stderr);
+        return 2;
+    }
+    if (limit && limit_path.empty() && loud_q.flags != (ZV_LOUDNESS_TARGET | ZV_LOUDNESS_CEILING))
+    {
+        fprintf(stderr, "zerovox: --limit needs a file (--limit IN.wav) or, on a synthesis run, both --lufs L and --true-peak-dbtp P\n");
+        usage(stderr);
+        return 2;
+    }
+    if (!limit && (limit_f.have_dbtp || limit_f.gain_db != 0.0f || limit_f.attack_ms != 0.0f || limit_f.release_ms != 0.0f))
+    {
+        fprintf(stderr, "zerovox: --limit-dbtp, --limit-gain-db, --limit-attack-ms and --limit-release-ms need --limit\n");
+        usage(stderr);
+        return 2;
+    }
     if (align_flag && align_a.empty())
     {
         fprintf(stderr, "zerovox: --mel-width, --align-scale, --align-normalise and --map-out need --align A.f32 B.f32\n");
@@ -900,6 +996,7 @@ int main(int argc, char **argv)
         if (planning) return plan(model_path, utt_path, controlled ? &prosody : nullptr);
         if (!analyze_path.empty()) return analyze(model_path, analyze_path, melout_path, resynth_path, mel_q);
         if (!loudness_path.empty()) return loudness_file(model_path, loudness_path, loud_q);
+        if (!limit_path.empty()) return limit_file(model_path, limit_path, out_path, limit_f);
         if (!align_a.empty()) return align_files(model_path, align_a, align_b, (uint32_t)mel_width, align_q, map_path);
         std::vector<float> like_wav;                            // --time-like, read ahead of the checkpoint
         uint32_t like_rate = 0;
@@ -1094,8 +1191,23 @@ int main(int argc, char **argv)
             // --lufs / --true-peak-dbtp: what -o receives, measured over the speech and scaled as a whole, then written
             const uint32_t T = trim || fit ? nf : hp.max_seq_len;
             std::vector<float> scaled((size_t)T * hp.audio_hop_size);
-            const zv_loudness_result r = T ? model.loudness(model.get_wav(), T, std::min(nf, T), &loud_q, scaled.data()) : zv_loudness_result{};
-            print_loudness("loudness before the gain", r);
+            zv_loudness_result r{};
+            if (limit && T)
+            {
+                // --limit: the gain of the target alone, then the limiter under the ceiling, then the meter on what is written
+                const zv_loudness target = {loud_q.gain, loud_q.target_lufs, 0.0f, ZV_LOUDNESS_TARGET};
+                r = model.loudness(model.get_wav(), T, std::min(nf, T), &target, nullptr);
+                const zv_limiter lq = limit_ask(limit_f, hp.audio_sampling_rate, r.gain, loud_q.true_peak_ceiling);
+                const zv_limit_result lr = model.limit(model.get_wav(), T, std::min(nf, T), &lq, scaled.data());
+                print_loudness("loudness before the gain", r);
+                print_limit("limiter", lr);
+                print_loudness("loudness after the limiter", model.loudness(scaled.data(), T, std::min(nf, T), nullptr, nullptr));
+            }
+            else
+            {
+                if (T) r = model.loudness(model.get_wav(), T, std::min(nf, T), &loud_q, scaled.data());
+                print_loudness("loudness before the gain", r);
+            }
             if (zv_write_wav(out_path.c_str(), scaled.data(), scaled.size(), hp.audio_sampling_rate) != ZV_OK) throw std::runtime_error(zv_last_error());
             printf("Successfully created %s with %zu samples (%u frames).\n", out_path.c_str(), scaled.size(), T);
         }
