@@ -33,6 +33,9 @@
  *   zv_limit_wave      any waveform the caller brings behind a look-ahead peak limiter: a gain, then no sample above a ceiling;
  *                      zv_limit_wave_batch: a batch of them in one launch per kernel; zv_limit_design: milliseconds as sample counts, on
  *                      the host
+ *   zv_resample_wave   any waveform the caller brings at another sample rate, as f32, as PCM16 with TPDF dither or both: the delivery
+ *                      step behind the limiter and the way in for a recording; zv_resample_wave_batch: a batch of them in one launch
+ *                      per kernel; zv_resample_design, zv_resample_count, zv_write_wav_pcm16: on the host
  *   zv_write_wav       <- ZeroVOXModel::write_wav_file       src/zerovox.cpp:337-391 (PCM16 mono RIFF)
  *   zv_last_error      <- std::runtime_error / die_fmt / GGML_ASSERT messages (src/zerovox.h:435-455)
  *
@@ -1027,6 +1030,81 @@ zv_status zv_limit_wave(zv_model *m, const float *wav, uint32_t T, uint32_t n_fr
 zv_status zv_limit_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint32_t *T,
                               const uint32_t *n_frames /* NULL = T */, const zv_limiter *ask /* [n_utt] or NULL */,
                               zv_limit_result *res /* [n_utt] */, float *const *out /* [n_utt], every entry [T * hop] */);
+/* ---- resampling: sample-rate conversion and PCM16 delivery, the step behind the limiter --------------------------------------------------
+ * The delivery chain filter -> loudness -> limiter ends in f32 at the model's rate; what a caller ships is 8 or 16 kHz for telephony,
+ * 44.1 or 48 kHz for video and broadcast, as 16-bit PCM with dither.  zv_resample_wave takes a host waveform of S_in SAMPLES (not
+ * frames: a recording is no multiple of the model's hop) and returns it at another rate as f32, as PCM16 or both; zv_resample_wave_batch
+ * takes n_utt of them under ONE ask, one launch per kernel per launch group of consecutive utterances (cut as for
+ * zv_loudness_wave_batch, over the padded input plus output samples), and utterance u dithers with seed + u and receives exactly the
+ * bits of its single call with that seed.  Both run eagerly on lane 0, are never part of a captured graph or of the zv_synthesize*
+ * chain, and use scratch of lane 0's arena.  The same call is the way in: a recording at 44.1 or 48 kHz is brought to the model's rate
+ * before zv_mel_wave, zv_loudness_wave or zv_limit_wave see it.  zv_resample_design, zv_resample_count and zv_write_wav_pcm16 are host
+ * only.
+ *
+ * THE RULE is a rational polyphase FIR.  Nothing in it is recursive along time, so nothing depends on how the work is split.
+ * g = gcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g; the table h[L][P] is f32 and P is even; half = P / 2; x[0 .. S_in) is
+ * the input.
+ *   count.   n_out = floor((S_in L + M - 1) / M) in 64-bit integers (zv_resample_count): the outputs whose time n M / L lies inside
+ *            [0, S_in).  zv_resample_count takes any S_in: it returns 0 where M is 0 and 2^64 - 1 where S_in L + M - 1 does not fit 64
+ *            bits (S_in above about 2^64 / L); the entry points bound S_in by zv_max_frames() * hop, far below.
+ *   span.    x'[j] = x[j] where 0 <= j < S_in and the sample is finite, else +0.0: the waveform filter's span rule.  It never reads
+ *            another utterance's samples.
+ *   sample.  For 0 <= n < n_out: t = n M (64-bit), i0 = t div L, p = t mod L; acc = +0.0 (double); for k = 0 .. P - 1 ascending:
+ *            acc = acc + (double)h[p][k] * (double)x'[i0 - half + 1 + k]; y[n] = (float)acc.  A product of two f32 values is exact in
+ *            f64, so each step is one IEEE addition whether or not it is fused.  The ascending order is part of the rule.  Output n
+ *            sits at input time n M / L with no delay, so frame and phoneme timings scale by L / M and keep pointing at the right samples.
+ *   PCM16    (only where a pcm output is asked for), per output, each step one IEEE f64 operation: z = (double)y[n] * 32768.0.  With
+ *            dither (flag bit 0): r = seed + (uint32_t)n * 0x9E3779B9; r ^= r >> 16; r *= 0x7feb352d; r ^= r >> 15; r *= 0x846ca68b;
+ *            r ^= r >> 16 (all mod 2^32); d = ((double)((r & 0xFFFF) + (r >> 16)) - 65535.0) * 2^-16 — TPDF with zero mean, +-1 LSB —
+ *            and z = z + d.  Then z = z + 0.5; q = floor(z), clamped to [-32768, 32767].  A NaN gives 0.  `clipped` counts the clamped
+ *            and the NaN samples.  Without the flag the dither step is left out entirely.
+ *   report.  n_out; clipped, 0 where no pcm output is asked for; sample_peak, the largest finite |y[n]| as a maximum of bit patterns,
+ *            like the level meter.
+ * csrc/resample.h holds the rule as plain C++ with a host reference, resample_reference(); tests/resample_rule.py restates it in numpy.
+ *
+ * THE DESIGN (zv_resample_design: host only, no model, no device) is data to the rule.  With s = min(1, L / M): half = ceil(zeros / s),
+ * P = 2 half.  For d = k - half + 1 - p / L: g(d) = s cutoff sinc(s cutoff d) I0(beta sqrt(1 - (d / half)^2)) / I0(beta), 0 where
+ * |d| > half; sinc(v) = sin(pi v) / (pi v); I0 is the power series sum ((v / 2)^j / j!)^2 in f64, summed until a term falls below
+ * 10^-17 of the sum.  Each phase row is divided by its own f64 sum — every phase has DC gain 1, a constant stays constant — and each
+ * entry is then rounded to f32 once.  A field that is 0 means its default: zeros = 32, beta = 9.0, cutoff = 0.91 (the fraction of the
+ * narrower Nyquist frequency at -6 dB).  Refused by name (ZV_ERR_ARG): rates outside 4 000 .. 768 000; L or M above 1 280;
+ * max(L / M, M / L) above 8; zeros outside 4 .. 64; beta outside (0, 20]; cutoff outside (0, 1]; P above 512; L P above 65 536.
+ * rate_in == rate_out is allowed and no special case: L = M = 1, a low-pass.  table == NULL returns the sizes only.
+ * What the defaults give, measured on the prototype assembled from the f32 rows by an FFT of 2^22 .. 2^23 points, for 22050 -> 48000
+ * (L 320, M 147, P 64), 22050 -> 8000 (160 / 441, P 178), 22050 -> 16000, 48000 -> 22050, 44100 -> 22050 and 22050 -> 44100: the stop
+ * band, from the narrower Nyquist frequency upward, -90.0 .. -90.6 dB; the pass band, up to 0.82 of it, -0.00028 .. +0.00027 dB; the
+ * level at 0.91 of it -6.00 .. -6.03 dB.
+ *
+ * Arguments: 1 <= S_in <= zv_max_frames() * hop; wav, ask and res non-NULL; at least one of out and pcm (in a batch: the array, and then
+ * every entry of it); flags within bit 0.  ask->table == NULL asks for the design of (rate_in, rate_out, zeros, beta, cutoff), built on
+ * the host at the first request and kept with the model.  A caller's table [L][P] travels with the call and is checked: finite entries,
+ * the limits above and gcd(L, M) = 1; the rates are then not looked at.  Everything is refused by name before any work is enqueued.
+ * zv_write_wav_pcm16 writes int16 samples as they are, a mono RIFF/WAVE file.
+ * Not covered: more than one channel; arbitrary (irrational or time-varying) ratios; noise-shaped dither; a rung of the
+ * zv_synthesize* chain (the chain's output stays f32 at the model's rate). */
+typedef struct
+{
+    uint32_t     rate_in, rate_out, zeros;      /* the design's: looked at where table == NULL */
+    float        beta, cutoff;
+    const float *table;                         /* a caller's table [L][P], or NULL = the design */
+    uint32_t     L, M, P;                       /* the caller's table's */
+    uint32_t     flags;                         /* bit 0: TPDF dither */
+    uint32_t     seed;
+} zv_resample;
+typedef struct
+{
+    uint64_t n_out, clipped;
+    float    sample_peak;
+} zv_resample_result;
+uint64_t  zv_resample_count(uint64_t S_in, uint32_t L, uint32_t M);
+zv_status zv_resample_design(uint32_t rate_in, uint32_t rate_out, uint32_t zeros /* 0: 32 */, float beta /* 0: 9 */, float cutoff /* 0: 0.91 */,
+                             uint32_t *L, uint32_t *M, uint32_t *P, float *table /* [L][P], or NULL: the sizes only */);
+zv_status zv_resample_wave(zv_model *m, const float *wav, uint64_t S_in, const zv_resample *ask, zv_resample_result *res,
+                           float *out /* [n_out] or NULL */, int16_t *pcm /* [n_out] or NULL */);
+zv_status zv_resample_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint64_t *S_in, const zv_resample *ask /* one */,
+                                 zv_resample_result *res /* [n_utt] */, float *const *out /* [n_utt] or NULL */,
+                                 int16_t *const *pcm /* [n_utt] or NULL */);
+zv_status zv_write_wav_pcm16(const char *path, const int16_t *pcm, size_t n, uint32_t sampling_rate);
 /* When the last batches ran on the GPU (measurement): for the most recent min(cap, batches begun, 64) batches, oldest first,
  * the times in ms — relative to the first one's start — at which the batch's first operation started and its last kernel
  * ended (HIP events on the lanes' streams; waits for every lane first).  The gaps of the union of [start, end] are the time the

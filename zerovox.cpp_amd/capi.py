@@ -37,6 +37,7 @@ SYMBOLS = [
     "zv_mel_align", "zv_mel_align_batch", "zv_align_durations",
     "zv_loudness_wave", "zv_loudness_wave_batch", "zv_loudness_design",
     "zv_limit_wave", "zv_limit_wave_batch", "zv_limit_design",
+    "zv_resample_wave", "zv_resample_wave_batch", "zv_resample_design", "zv_resample_count", "zv_write_wav_pcm16",
 ]
 
 
@@ -696,6 +697,106 @@ def _limit_ask(who: str, ask):
     return ask
 
 
+class ResampleC(C.Structure):
+    """zv_resample of include/zerovox_amd.h"""
+    _fields_ = [("rate_in", C.c_uint32), ("rate_out", C.c_uint32), ("zeros", C.c_uint32), ("beta", C.c_float), ("cutoff", C.c_float),
+                ("table", C.c_void_p), ("L", C.c_uint32), ("M", C.c_uint32), ("P", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint32)]
+
+
+class ResampleResultC(C.Structure):
+    """zv_resample_result of include/zerovox_amd.h"""
+    _fields_ = [("n_out", C.c_uint64), ("clipped", C.c_uint64), ("sample_peak", C.c_float)]
+
+
+def _u32_arg(who: str, name: str, v) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 0xffffffff:
+        raise ValueError(f"{who}: {name} = {v!r} must be an integer in [0, 4294967295]")
+    return int(v)
+
+
+def resample_design(rate_in: int, rate_out: int, zeros: int = 0, beta: float = 0.0, cutoff: float = 0.0, lib=None):
+    """zv_resample_design: (L, M, the table float32 [L, P]) of a Kaiser-windowed sinc for rate_in -> rate_out; 0 means the default
+    (zeros 32, beta 9, cutoff 0.91).  Host only: no model, no device."""
+    lib = lib or load_library()
+    fn = _stage_symbol(lib, "zv_resample_design")
+    args = [_u32_arg("resample_design", n, v) for n, v in (("rate_in", rate_in), ("rate_out", rate_out), ("zeros", zeros))] + [float(beta), float(cutoff)]
+    L, M, P = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    for table in (None, True):
+        if table:
+            table = np.empty((L.value, P.value), np.float32)
+        st = fn(*args, C.byref(L), C.byref(M), C.byref(P), _ptr(table))
+        if st != 0:
+            raise ZvError(st, lib.zv_last_error().decode("utf-8", "replace"))
+    return int(L.value), int(M.value), table
+
+
+def resample_count(S_in: int, L: int, M: int, lib=None) -> int:
+    """zv_resample_count: the outputs of S_in input samples under the ratio L / M"""
+    lib = lib or load_library()
+    return int(_stage_symbol(lib, "zv_resample_count")(int(S_in), _u32_arg("resample_count", "L", L), _u32_arg("resample_count", "M", M)))
+
+
+class Resample:
+    """What a resampling call asks for (include/zerovox_amd.h "resampling"): either the design of (rate_in, rate_out, zeros, beta,
+    cutoff; 0: the default), or a caller's table float32 [L, P] with its M; dither: TPDF dither of the PCM16 output under `seed`.  The
+    library checks the values."""
+
+    def __init__(self, rate_in: int = 0, rate_out: int = 0, zeros: int = 0, beta: float = 0.0, cutoff: float = 0.0, table=None, M: int = 0,
+                 dither: bool = False, seed: int = 0, flags=None):
+        self.rate_in, self.rate_out, self.zeros, self.beta, self.cutoff = rate_in, rate_out, zeros, float(beta), float(cutoff)
+        self.table = None if table is None else np.ascontiguousarray(table, dtype=np.float32)
+        if self.table is not None and self.table.ndim != 2:
+            raise ValueError(f"Resample: the table must be [L, P], got shape {self.table.shape}")
+        self.M, self.seed = M, seed
+        self.flags = (1 if dither else 0) if flags is None else flags
+
+    @property
+    def ratio(self):
+        """(L, M) of the ask: the table's, or the rates' in lowest terms"""
+        if self.table is not None:
+            return int(self.table.shape[0]), int(self.M)
+        g = int(np.gcd(int(self.rate_in), int(self.rate_out))) or 1
+        return int(self.rate_out) // g, int(self.rate_in) // g
+
+    @property
+    def struct(self) -> ResampleC:
+        u = lambda n, v: _u32_arg("Resample", n, v)
+        L, P = (0, 0) if self.table is None else self.table.shape
+        return ResampleC(u("rate_in", self.rate_in), u("rate_out", self.rate_out), u("zeros", self.zeros), self.beta, self.cutoff,
+                         None if self.table is None else self.table.ctypes.data, u("L", L), u("M", self.M), u("P", P), u("flags", self.flags),
+                         u("seed", self.seed))
+
+    def __repr__(self):
+        what = f"{self.rate_in} -> {self.rate_out}, zeros={self.zeros}, beta={self.beta}, cutoff={self.cutoff}" if self.table is None else \
+            f"table {self.table.shape}, M={self.M}"
+        return f"Resample({what}, flags={self.flags}, seed={self.seed})"
+
+
+class ResampleResult:
+    """What a resampling call reports: n_out, clipped (0 where no PCM16 was asked for) and sample_peak (float32)"""
+    FIELDS = ("n_out", "clipped", "sample_peak")
+
+    def __init__(self, c: ResampleResultC):
+        self.n_out, self.clipped, self.sample_peak = int(c.n_out), int(c.clipped), np.float32(c.sample_peak)
+
+    def __repr__(self):
+        return "ResampleResult(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in self.FIELDS) + ")"
+
+
+def _resample_ask(who: str, ask):
+    if not isinstance(ask, Resample):
+        raise TypeError(f"{who}: ask must be a Resample, not {type(ask).__name__}")
+    return ask
+
+
+def _samples(who: str, wav):
+    """a waveform of any length in samples, float32 [S]"""
+    w = np.ascontiguousarray(wav, dtype=np.float32)
+    if w.ndim != 1:
+        raise ValueError(f"{who}: the waveform must be a 1-D array, got shape {w.shape}")
+    return w
+
+
 class EnvelopeC(C.Structure):
     """zv_envelope of include/zerovox_amd.h: the gains' pointer ([n] or NULL) and three integers (a zeroed struct is the identity)"""
     _fields_ = [("phoneme_gain", C.c_void_p), ("ramp_frames", C.c_uint32), ("fade_in_samples", C.c_uint32),
@@ -967,9 +1068,16 @@ def _bind(lib):
                            ("zv_loudness_design", [u32, C.POINTER(LoudnessFilterC)]),
                            ("zv_limit_wave", [vp, fp, u32, u32, C.POINTER(LimiterC), C.POINTER(LimitResultC), fp]),
                            ("zv_limit_wave_batch", [vp, u32, pvp, pu32, pu32, C.POINTER(LimiterC), C.POINTER(LimitResultC), pvp]),
-                           ("zv_limit_design", [u32, C.c_float, C.c_float, pu32, pu32])):
+                           ("zv_limit_design", [u32, C.c_float, C.c_float, pu32, pu32]),
+                           ("zv_resample_wave", [vp, fp, C.c_uint64, C.POINTER(ResampleC), C.POINTER(ResampleResultC), fp, vp]),
+                           ("zv_resample_wave_batch", [vp, u32, pvp, C.POINTER(C.c_uint64), C.POINTER(ResampleC), C.POINTER(ResampleResultC), pvp, pvp]),
+                           ("zv_resample_design", [u32, u32, u32, C.c_float, C.c_float, pu32, pu32, pu32, fp]),
+                           ("zv_resample_count", [C.c_uint64, u32, u32]),
+                           ("zv_write_wav_pcm16", [C.c_char_p, vp, C.c_size_t, u32])):
         if hasattr(lib, name):
             getattr(lib, name).argtypes = argtypes
+    if hasattr(lib, "zv_resample_count"):
+        lib.zv_resample_count.restype = C.c_uint64
     lib.zv_device_alloc.argtypes = [vp, C.c_size_t]
     lib.zv_device_alloc.restype = vp
     lib.zv_device_free.argtypes = [vp, vp]
@@ -1439,14 +1547,52 @@ class Model:
                      None if n_frames is None else U(*[int(f) for f in n_frames]), qs, res, P(*[o.ctypes.data for o in outs])))
         return [(LimitResult(r), o) for r, o in zip(res, outs)]
 
-    def deliver(self, wav, lufs, dbtp, n_frames=None):
+    def resample_wave(self, wav, ask, out=True, pcm=False):
+        """zv_resample_wave: a waveform of any length in samples at another rate -> (ResampleResult, float32 [n_out] or None, int16
+        [n_out] or None); ask: a Resample; out, pcm: which of the two outputs to return (at least one)"""
+        fn = _stage_symbol(self.lib, "zv_resample_wave")
+        q = _resample_ask("resample_wave", ask)
+        w = _samples("resample_wave", wav)
+        n = resample_count(w.size, *q.ratio, lib=self.lib) if q.ratio[1] else 0
+        o = np.empty(n, np.float32) if out else None
+        p = np.empty(n, np.int16) if pcm else None
+        res = ResampleResultC()
+        self._chk(fn(self.h, _ptr(w), w.size, C.byref(q.struct), C.byref(res), _ptr(o), _ptr(p)))
+        assert res.n_out == n, (res.n_out, n)
+        return ResampleResult(res), o, p
+
+    def resample_wave_batch(self, wavs, ask, out=True, pcm=False):
+        """zv_resample_wave_batch: waveforms of any lengths under ONE ask, one launch per kernel per launch group -> the list of
+        (ResampleResult, float32 or None, int16 or None), utterance u with the bits of its resample_wave under seed + u"""
+        fn = _stage_symbol(self.lib, "zv_resample_wave_batch")
+        q = _resample_ask("resample_wave_batch", ask)
+        ws = [_samples(f"resample_wave_batch: utterance {u}", w) for u, w in enumerate(wavs)]
+        n = len(ws)
+        counts = [resample_count(w.size, *q.ratio, lib=self.lib) if q.ratio[1] else 0 for w in ws]
+        outs = [np.empty(c, np.float32) for c in counts] if out else None
+        pcms = [np.empty(c, np.int16) for c in counts] if pcm else None
+        res = (ResampleResultC * n)()
+        P = C.c_void_p * n
+        self._chk(fn(self.h, n, P(*[w.ctypes.data for w in ws]), (C.c_uint64 * n)(*[w.size for w in ws]), C.byref(q.struct), res,
+                     P(*[o.ctypes.data for o in outs]) if out else None, P(*[p.ctypes.data for p in pcms]) if pcm else None))
+        return [(ResampleResult(r), outs[u] if out else None, pcms[u] if pcm else None) for u, r in enumerate(res)]
+
+    def deliver(self, wav, lufs, dbtp, n_frames=None, rate=None, pcm16=False, dither=False):
         """A delivery chain for "lufs LUFS, dbtp dBTP": a target-only loudness meter, the limiter with that gain under the ceiling (the
-        default windows), then the meter on the result -> (LoudnessResult before, LimitResult, LoudnessResult after, waveform)"""
+        default windows), then the meter on the result -> (LoudnessResult before, LimitResult, LoudnessResult after, waveform).
+        rate (Hz) and pcm16 add the last step, resample_wave over the limited waveform (the default design; dither: TPDF, seed 0),
+        and the tuple gains (ResampleResult, the delivered samples: float32, or int16 where pcm16)"""
         before, _ = self.loudness_wave(wav, Loudness.from_lufs(lufs), n_frames, apply=False)
         a, r = limit_design(self.hp.audio_sampling_rate, lib=self.lib)
         lim, out = self.limit_wave(wav, Limiter(float(before.gain), float(np.float32(10.0 ** (float(dbtp) / 20.0))), a, r), n_frames)
         after, _ = self.loudness_wave(out, None, n_frames, apply=False)
-        return before, lim, after, out
+        if rate is None and not pcm16:
+            if dither:
+                raise ValueError("deliver: dither belongs to pcm16=True")
+            return before, lim, after, out
+        sr = self.hp.audio_sampling_rate
+        rs, f32, i16 = self.resample_wave(out, Resample(sr, sr if rate is None else rate, dither=dither), out=not pcm16, pcm=pcm16)
+        return before, lim, after, out, rs, i16 if pcm16 else f32
 
     def resynthesize(self, wav, params=None) -> np.ndarray:
         """analysis-resynthesis: vocode(mel_wave(wav)), the acceptance check of a converted vocoder checkpoint.  params must keep the
@@ -1860,6 +2006,15 @@ def gguf_inspect(path: str, tensor_index: int = -1):
     if tensor_index < 0:
         return n.value, T.value
     return n.value, T.value, name.value.decode(), typ.value, list(ne)
+
+
+def write_wav_pcm16(path: str, pcm: np.ndarray, sampling_rate: int):
+    """zv_write_wav_pcm16: int16 samples as they are, a mono RIFF/WAVE file"""
+    lib = load_library()
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    st = _stage_symbol(lib, "zv_write_wav_pcm16")(path.encode(), _ptr(pcm), pcm.size, sampling_rate)
+    if st != 0:
+        raise ZvError(st, lib.zv_last_error().decode())
 
 
 def write_wav(path: str, wav: np.ndarray, sampling_rate: int):

@@ -2122,6 +2122,179 @@ zv_status zv_limit_design(uint32_t sampling_rate, float attack_ms, float release
     });
 }
 
+// ---- resampling (zv_resample_wave, zv_resample_wave_batch, zv_resample_design, zv_resample_count; the rule: resample.h): host waveforms
+// in, per utterance the waveform at the other rate (f32, PCM16 or both) and the report out, eagerly, on lane 0.  A batch runs as launch
+// groups of consecutive utterances (resample_group_end), each ONE launch per kernel.  I/O block of a group: [inputs, every utterance on
+// whole chunks][f32 outputs, likewise][PCM16 outputs][table][statistics][segment table][result rows].
+static_assert(sizeof(zv_resample_result) == sizeof(zv::ResampleRow) && offsetof(zv_resample_result, sample_peak) == offsetof(zv::ResampleRow, sample_peak),
+              "zv_resample_result is resample.h's ResampleRow");
+
+[[maybe_unused]] static void resample_design_fail(const char *fn, const char *field, uint32_t rate_in, uint32_t rate_out, uint32_t zeros, float beta, float cutoff)
+{
+    const uint32_t g = zv::resample_gcd(rate_in, rate_out), L = g ? rate_out / g : 0, M = g ? rate_in / g : 0;
+    if (!strcmp(field, "rate_in") || !strcmp(field, "rate_out"))
+        zv::fail(ZV_ERR_ARG, "%s: resample %s = %u must be in %u .. %u", fn, field, !strcmp(field, "rate_in") ? rate_in : rate_out, zv::RESAMPLE_MIN_RATE,
+                 zv::RESAMPLE_MAX_RATE);
+    if (!strcmp(field, "L") || !strcmp(field, "M"))
+        zv::fail(ZV_ERR_ARG, "%s: resample %s = %u exceeds %u (rates %u -> %u: L = %u, M = %u)", fn, field, !strcmp(field, "L") ? L : M, zv::RESAMPLE_MAX_L,
+                 rate_in, rate_out, L, M);
+    if (!strcmp(field, "ratio")) zv::fail(ZV_ERR_ARG, "%s: resample ratio %u : %u exceeds %u", fn, L, M, zv::RESAMPLE_MAX_RATIO);
+    if (!strcmp(field, "zeros")) zv::fail(ZV_ERR_ARG, "%s: resample zeros = %u is outside %u .. %u (0: the default)", fn, zeros, zv::RESAMPLE_MIN_ZEROS, zv::RESAMPLE_MAX_ZEROS);
+    if (!strcmp(field, "beta")) zv::fail(ZV_ERR_ARG, "%s: resample beta = %g is outside (0, 20] (0: the default)", fn, (double)beta);
+    if (!strcmp(field, "cutoff")) zv::fail(ZV_ERR_ARG, "%s: resample cutoff = %g is outside (0, 1] (0: the default)", fn, (double)cutoff);
+    if (!strcmp(field, "P")) zv::fail(ZV_ERR_ARG, "%s: resample P exceeds %u taps per phase at zeros = %u and ratio %u : %u", fn, zv::RESAMPLE_MAX_P, zeros, L, M);
+    zv::fail(ZV_ERR_ARG, "%s: resample table size L * P exceeds %u entries (L = %u)", fn, zv::RESAMPLE_MAX_TABLE, L);
+}
+
+// the checks of an ask that need no model
+static void check_resample_ask(const char *fn, const zv_resample *q, const zv_resample_result *res)
+{
+    if (!q) zv::fail(ZV_ERR_ARG, "%s: ask is NULL", fn);
+    if (!res) zv::fail(ZV_ERR_ARG, "%s: res is NULL", fn);
+    if (q->flags & ~zv::RESAMPLE_FLAG_DITHER) zv::fail(ZV_ERR_ARG, "%s: resample flags = %u holds bits other than bit 0 (dither)", fn, q->flags);
+    if (!q->table) return;
+    const char *field = zv::resample_check_table(q->table, q->L, q->M, q->P);
+    if (!field) return;
+    if (!strcmp(field, "gcd")) zv::fail(ZV_ERR_ARG, "%s: resample L = %u and M = %u have a common divisor (gcd must be 1)", fn, q->L, q->M);
+    if (!strcmp(field, "table")) zv::fail(ZV_ERR_ARG, "%s: resample table holds an entry that is not finite", fn);
+    if (!strcmp(field, "ratio")) zv::fail(ZV_ERR_ARG, "%s: resample ratio %u : %u exceeds %u", fn, q->L, q->M, zv::RESAMPLE_MAX_RATIO);
+    if (!strcmp(field, "table size")) zv::fail(ZV_ERR_ARG, "%s: resample table size L * P = %u exceeds %u entries", fn, q->L * q->P, zv::RESAMPLE_MAX_TABLE);
+    if (!strcmp(field, "P")) zv::fail(ZV_ERR_ARG, "%s: resample P = %u must be even and in 2 .. %u", fn, q->P, zv::RESAMPLE_MAX_P);
+    zv::fail(ZV_ERR_ARG, "%s: resample %s = %u is outside 1 .. %u", fn, field, !strcmp(field, "L") ? q->L : q->M, zv::RESAMPLE_MAX_L);
+}
+
+static void resample_run(zv_model *m, const char *fn, bool batch, uint32_t n_utt, const float *const *wav, const uint64_t *S_in, const zv_resample *ask,
+                         zv_resample_result *res, float *const *out, int16_t *const *pcm)
+{
+#if !defined(__HIP_DEVICE_COMPILE__)      // (resample.h keeps its host half out of device passes)
+    Model &M = *m->m;
+    const uint64_t smax = (uint64_t)M.max_frames_per_utterance() * M.hp.audio_hop_size;
+    char who[32] = "";
+    for (uint32_t u = 0; u < n_utt; u++)
+    {
+        if (batch) snprintf(who, sizeof who, "utterance %u: ", u);
+        if (S_in[u] < 1 || S_in[u] > smax)
+            zv::fail(ZV_ERR_ARG, "%s: %sS_in = %llu is outside 1 .. zv_max_frames() * hop = %llu samples", fn, who, (unsigned long long)S_in[u], (unsigned long long)smax);
+    }
+    uint32_t L = ask->L, Mq = ask->M, P = ask->P;
+    const float *table = ask->table;
+    if (!table)
+    {
+        const Model::ResampleDesign *found = nullptr;
+        for (const Model::ResampleDesign &d : M.resample_designs)
+            if (d.rate_in == ask->rate_in && d.rate_out == ask->rate_out && d.zeros == ask->zeros && !memcmp(&d.beta, &ask->beta, 4) && !memcmp(&d.cutoff, &ask->cutoff, 4))
+                found = &d;
+        if (!found)
+        {
+            Model::ResampleDesign d{ask->rate_in, ask->rate_out, ask->zeros, ask->beta, ask->cutoff, 0, 0, 0, {}};
+            const char *field = zv::resample_design(d.rate_in, d.rate_out, d.zeros, d.beta, d.cutoff, &d.L, &d.M, &d.P, nullptr);
+            if (field) resample_design_fail(fn, field, d.rate_in, d.rate_out, d.zeros, d.beta, d.cutoff);
+            d.table.resize((size_t)d.L * d.P);
+            zv::resample_design(d.rate_in, d.rate_out, d.zeros, d.beta, d.cutoff, &d.L, &d.M, &d.P, d.table.data());
+            if (M.resample_designs.size() >= 16) M.resample_designs.erase(M.resample_designs.begin());
+            M.resample_designs.push_back(std::move(d));
+            found = &M.resample_designs.back();
+        }
+        L = found->L, Mq = found->M, P = found->P, table = found->table.data();
+    }
+    use_lane0(m);
+    std::vector<zv::ResampleSeg> segs;
+    std::vector<zv::ResampleRow> rows;
+    for (uint32_t g0 = 0; g0 < n_utt;)
+    {
+        const uint32_t g1 = zv::resample_group_end(g0, n_utt, S_in, L, Mq), n = g1 - g0;
+        segs.resize(n);
+        rows.resize(n);
+        int64_t x0 = 0, y0 = 0, max_n_out = 0;
+        size_t tiles = 0;
+        const int tile = zv::resample_tile_outputs(zv::resample_tile(L, Mq, P));
+        for (uint32_t k = 0; k < n; k++)
+        {
+            const uint32_t u = g0 + k;
+            const int64_t n_out = (int64_t)zv::resample_count(S_in[u], L, Mq);
+            segs[k] = zv::ResampleSeg{x0, (int64_t)S_in[u], y0, n_out, (int32_t)tiles, ask->seed + u};
+            x0 += (int64_t)zv::loud_padded(S_in[u]);
+            y0 += (int64_t)zv::loud_padded((uint64_t)n_out);
+            tiles += (size_t)zv::resample_tiles(n_out, tile);
+            max_n_out = std::max(max_n_out, n_out);
+        }
+        Layout Lo;
+        const size_t o_wav = Lo.at((size_t)x0 * 4), o_out = Lo.at(out ? (size_t)y0 * 4 : 0), o_pcm = Lo.at(pcm ? (size_t)y0 * 2 : 0),
+                     o_tab = Lo.at((size_t)L * P * 4), o_st = Lo.at(tiles * 8), o_seg = Lo.at((size_t)n * sizeof(zv::ResampleSeg)),
+                     o_row = Lo.at((size_t)n * sizeof(zv::ResampleRow));
+        char *io = (char *)M.io_scratch(Lo.size());
+        for (uint32_t k = 0; k < n; k++)
+            ZV_HIP(hipMemcpyAsync(io + o_wav + (size_t)segs[k].x0 * 4, wav[g0 + k], (size_t)segs[k].S_in * 4, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_tab, table, (size_t)L * P * 4, hipMemcpyHostToDevice, M.stream()));
+        ZV_HIP(hipMemcpyAsync(io + o_seg, segs.data(), (size_t)n * sizeof(zv::ResampleSeg), hipMemcpyHostToDevice, M.stream()));
+        const zv::ResampleJob job{(const float *)(io + o_wav), out ? (float *)(io + o_out) : nullptr, pcm ? (int16_t *)(io + o_pcm) : nullptr,
+                                  (const float *)(io + o_tab), (uint32_t *)(io + o_st), (zv::ResampleRow *)(io + o_row), (const zv::ResampleSeg *)(io + o_seg),
+                                  (int)n, L, Mq, P, ask->flags, max_n_out};
+        M.resample_launches(job, (size_t)x0, (size_t)y0);
+        ZV_HIP(hipMemcpyAsync(rows.data(), io + o_row, (size_t)n * sizeof(zv::ResampleRow), hipMemcpyDeviceToHost, M.stream()));
+        for (uint32_t k = 0; k < n; k++)
+        {
+            if (out) ZV_HIP(hipMemcpyAsync(out[g0 + k], io + o_out + (size_t)segs[k].y0 * 4, (size_t)segs[k].n_out * 4, hipMemcpyDeviceToHost, M.stream()));
+            if (pcm) ZV_HIP(hipMemcpyAsync(pcm[g0 + k], io + o_pcm + (size_t)segs[k].y0 * 2, (size_t)segs[k].n_out * 2, hipMemcpyDeviceToHost, M.stream()));
+        }
+        M.sync();                             // (segs and rows are pageable and reused by the next group)
+        for (uint32_t k = 0; k < n; k++) memcpy(&res[g0 + k], &rows[k], sizeof(zv::ResampleRow));
+        g0 = g1;
+    }
+#endif
+}
+
+uint64_t zv_resample_count(uint64_t S_in, uint32_t L, uint32_t M) { return zv::resample_count(S_in, L, M); }
+
+zv_status zv_resample_wave(zv_model *m, const float *wav, uint64_t S_in, const zv_resample *ask, zv_resample_result *res, float *out, int16_t *pcm)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!m) zv::fail(ZV_ERR_ARG, "%s: m is NULL", fn);
+        if (!wav) zv::fail(ZV_ERR_ARG, "%s: wav is NULL", fn);
+        if (!out && !pcm) zv::fail(ZV_ERR_ARG, "%s: out and pcm are both NULL (give at least one)", fn);
+        check_resample_ask(fn, ask, res);
+        resample_run(m, fn, false, 1, &wav, &S_in, ask, res, out ? &out : nullptr, pcm ? &pcm : nullptr);
+    });
+}
+
+zv_status zv_resample_wave_batch(zv_model *m, uint32_t n_utt, const float *const *wav, const uint64_t *S_in, const zv_resample *ask,
+                                 zv_resample_result *res, float *const *out, int16_t *const *pcm)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!m) zv::fail(ZV_ERR_ARG, "%s: m is NULL", fn);
+        if (!wav) zv::fail(ZV_ERR_ARG, "%s: wav is NULL", fn);
+        if (!S_in) zv::fail(ZV_ERR_ARG, "%s: S_in is NULL", fn);
+        if (!n_utt) zv::fail(ZV_ERR_ARG, "%s: n_utt must be > 0", fn);
+        if (!out && !pcm) zv::fail(ZV_ERR_ARG, "%s: out and pcm are both NULL (give at least one)", fn);
+        check_resample_ask(fn, ask, res);
+        for (uint32_t u = 0; u < n_utt; u++)
+        {
+            if (!wav[u]) zv::fail(ZV_ERR_ARG, "%s: utterance %u: wav is NULL", fn, u);
+            if (out && !out[u]) zv::fail(ZV_ERR_ARG, "%s: utterance %u: out is NULL", fn, u);
+            if (pcm && !pcm[u]) zv::fail(ZV_ERR_ARG, "%s: utterance %u: pcm is NULL", fn, u);
+        }
+        resample_run(m, fn, true, n_utt, wav, S_in, ask, res, out, pcm);
+    });
+}
+
+// The table: host only, no model, no device (resample.h resample_design).
+zv_status zv_resample_design(uint32_t rate_in, uint32_t rate_out, uint32_t zeros, float beta, float cutoff, uint32_t *L, uint32_t *M, uint32_t *P,
+                             float *table)
+{
+    const char *fn = __func__;      // (inside the lambda __func__ is the lambda's)
+    return guarded([&] {
+        if (!L) zv::fail(ZV_ERR_ARG, "%s: L is NULL", fn);
+        if (!M) zv::fail(ZV_ERR_ARG, "%s: M is NULL", fn);
+        if (!P) zv::fail(ZV_ERR_ARG, "%s: P is NULL", fn);
+#if !defined(__HIP_DEVICE_COMPILE__)      // (resample.h keeps its host half out of device passes)
+        const char *field = zv::resample_design(rate_in, rate_out, zeros, beta, cutoff, L, M, P, table);
+        if (field) resample_design_fail(fn, field, rate_in, rate_out, zeros, beta, cutoff);
+#endif
+    });
+}
+
 zv_status zv_synthesize_batch_end(zv_model *m, uint32_t lane)
 {
     return guarded([&] {
@@ -2630,6 +2803,39 @@ zv_status zv_write_wav(const char *path, const float *wav, size_t n_samples, uin
             pcm[i] = (int16_t)q;
         }
         ok = ok && fwrite(pcm.data(), 2, n_samples, f) == n_samples;
+        ok = (fclose(f) == 0) && ok;
+        if (!ok) zv::fail(ZV_ERR_IO, "short write to '%s'", path);
+    });
+}
+
+// int16 samples as they are (zv_resample_wave's pcm): nothing is scaled or rounded here
+zv_status zv_write_wav_pcm16(const char *path, const int16_t *pcm, size_t n, uint32_t sampling_rate)
+{
+    return guarded([&] {
+        ZV_NEED(path && pcm, "null argument");
+        if (n > (size_t)0x7FFFFFE0u / 2) zv::fail(ZV_ERR_ARG, "%zu samples do not fit a RIFF/WAVE file (32-bit sizes)", n);
+        FILE *f = fopen(path, "wb");
+        if (!f) zv::fail(ZV_ERR_IO, "cannot open '%s' for writing", path);
+        const uint32_t data_bytes = (uint32_t)(n * 2);
+        uint8_t hdr[44];
+        auto put32 = [&](int o, uint32_t v) { for (int i = 0; i < 4; i++) hdr[o + i] = (uint8_t)(v >> (8 * i)); };
+        auto put16 = [&](int o, uint16_t v) { hdr[o] = (uint8_t)v; hdr[o + 1] = (uint8_t)(v >> 8); };
+        memcpy(hdr, "RIFF", 4);
+        put32(4, 36 + data_bytes);
+        memcpy(hdr + 8, "WAVEfmt ", 8);
+        put32(16, 16);
+        put16(20, 1);                 // PCM
+        put16(22, 1);                 // mono
+        put32(24, sampling_rate);
+        put32(28, sampling_rate * 2);
+        put16(32, 2);
+        put16(34, 16);
+        memcpy(hdr + 36, "data", 4);
+        put32(40, data_bytes);
+        bool ok = fwrite(hdr, 1, 44, f) == 44;
+        std::vector<uint8_t> le(n * 2);
+        for (size_t i = 0; i < n; i++) le[2 * i] = (uint8_t)(uint16_t)pcm[i], le[2 * i + 1] = (uint8_t)((uint16_t)pcm[i] >> 8);
+        ok = ok && fwrite(le.data(), 2, n, f) == n;
         ok = (fclose(f) == 0) && ok;
         if (!ok) zv::fail(ZV_ERR_IO, "short write to '%s'", path);
     });

@@ -23,6 +23,7 @@
 #include "align.h"        // mel alignment: AlignPair, AlignRow, the tiles and ALIGN_DP_ROWS
 #include "loudness.h"     // loudness: LoudJob, LoudSeg, LoudAsk, LoudRow, LoudFilter
 #include "limiter.h"      // limiter: LimitJob, LimitSeg, LimitAsk, LimitRow
+#include "resample.h"     // resampling: ResampleJob, ResampleSeg, ResampleRow
 
 // Timing-only ablation bits (`dbg` fields of the job structs: skip staging / MFMA loops / stores ... — WRONG results) exist only
 // in diagnostic builds (-DZV_DIAG, see knobs.h).  In the shipped library every read of them is the constant 0 and the code
@@ -555,5 +556,13 @@ hipError_t launch_limit_peak(hipStream_t s, const LimitJob &j, bool after);
 hipError_t launch_limit_min(hipStream_t s, const LimitJob &j);
 hipError_t launch_limit_mean(hipStream_t s, const LimitJob &j);
 hipError_t launch_limit_reduce(hipStream_t s, const LimitJob &j);
+
+// ---- resampling (include/zerovox_amd.h "resampling", resample.h): two passes over ONE launch group of utterances (ResampleJob), a launch
+// each whatever the group (stage_plan.h resample_plan).  segs[nseg] says where an utterance's input, output and statistics lie
+// (ResampleSeg); wav, out and pcm are 16-byte aligned, the table 8-byte; out or pcm may be null, not both.
+//   resample: out and pcm per output and a (peak, clips) pair per tile from wav and the table;  reduce: rows[u] = the result (ResampleRow)
+// hipErrorInvalidValue: a null or misaligned pointer, or a group resample_plan does not accept.
+hipError_t launch_resample(hipStream_t s, const ResampleJob &j);
+hipError_t launch_resample_reduce(hipStream_t s, const ResampleJob &j);
 
 }  // namespace zv

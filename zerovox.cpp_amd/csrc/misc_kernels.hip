@@ -15,4 +15,5 @@
 #include "align_kernels.hip"          // mel alignment
 #include "loudness_kernels.hip"       // loudness
 #include "limiter_kernels.hip"        // limiter
+#include "resample_kernels.hip"       // resampling
 #include "mfma_chain_kernel.hip"      // test-only MFMA chain

@@ -256,6 +256,17 @@ class Model
     void loud_launches(const LoudJob &job, bool apply, size_t samples, size_t capacity);
     // the launches of the limiter over one launch group of utterances, likewise (kernels.h launch_limit_*); entries: the group's q entries
     void limit_launches(const LimitJob &job, size_t samples, size_t capacity, size_t entries);
+    // the launches of resampling over one launch group of utterances, likewise (kernels.h launch_resample*); in, out: the group's samples
+    void resample_launches(const ResampleJob &job, size_t in, size_t out);
+    // the designed tables of resampling, built on the host at the first request for their (rates, zeros, beta, cutoff) and kept
+    struct ResampleDesign
+    {
+        uint32_t rate_in, rate_out, zeros;
+        float beta, cutoff;
+        uint32_t L, M, P;
+        std::vector<float> table;
+    };
+    std::vector<ResampleDesign> resample_designs;
 
     // scratch for host-buffer entry points (grows on demand)
     void *io_scratch(size_t bytes);

@@ -13,6 +13,7 @@
 #include "mel.h"            // MEL_TILE_FRAMES, MEL_ROWS_FRAMES, MEL_MAX_MELS
 #include "loudness.h"       // LOUD_CHUNK, LOUD_WG_CHUNKS, LOUD_TP_TILE
 #include "limiter.h"        // LIMIT_TILE, LIMIT_MAX_HALO
+#include "resample.h"       // resample_tile, resample_check_shape
 
 namespace zv
 {
@@ -190,6 +191,24 @@ inline LimitPlan limit_plan(int64_t max_qlen, int64_t max_total, int max_halo, i
     const int stage = limit_stage(max_halo);
     return LimitPlan{ok, (int)limit_tiles(max_qlen), (int)limit_tiles(max_total + max_halo), (int)limit_tiles(max_total), nseg, stage,
                      (size_t)(stage + LIMIT_TILE) * 4 + LIMIT_LDS_TAIL, (size_t)(stage + 4) * 6 + LIMIT_LDS_TAIL};
+}
+
+// ---- resampling (resample_kernels.hip): ONE launch per kernel over a launch group's utterances ----
+// A workgroup covers one tile of resample_tile(L, M, P): R * S outputs, their input samples staged as f64 (RESAMPLE_STAGE at the most,
+// 64 000 bytes: two workgroups fit a CU's 160 KB); the reduction is a wave per utterance.
+struct ResamplePlan
+{
+    bool ok;
+    int  gx;        // tiles of the longest output
+    int  gy;        // utterances: grid y of the pass, grid x of the reduction
+    ResampleTile tile;
+};
+inline ResamplePlan resample_plan(int64_t max_n_out, int nseg, uint32_t L, uint32_t M, uint32_t P)
+{
+    if (max_n_out < 1 || nseg < 1 || nseg > 65535 || resample_check_shape(L, M, P)) return ResamplePlan{false, 0, 0, ResampleTile{0, 0, 0}};
+    const ResampleTile t = resample_tile(L, M, P);
+    const int64_t gx = resample_tiles(max_n_out, resample_tile_outputs(t));
+    return ResamplePlan{gx <= 0x7fffffff && resample_tile_stage(L, M, P, t.S, t.R) <= RESAMPLE_STAGE, (int)gx, nseg, t};
 }
 
 }  // namespace zv

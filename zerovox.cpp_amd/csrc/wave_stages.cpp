@@ -154,4 +154,15 @@ void Model::limit_launches(const LimitJob &job, size_t samples, size_t capacity,
     ZV_LAUNCH("limit_reduce", 24.0 * q / LIMIT_TILE, 0.0, launch_limit_reduce(stream(), job));
 }
 
+// Resampling (resample.h): no stage of the chain either — the stand-alone entry points' launches over one launch group of utterances.
+void Model::resample_launches(const ResampleJob &job, size_t in, size_t out)
+{
+    const double x = (double)in, y = (double)out, P = job.P;
+    // algorithmic bytes: the input read once, the table once, the outputs written (4 and 2 bytes a sample); a pair of words per tile.
+    // Operations: P f64 multiply-adds per output, and the dozen of the PCM16 conversion.
+    ZV_LAUNCH("resample", 4.0 * x + 4.0 * job.L * P + (job.out ? 4.0 : 0.0) * y + (job.pcm ? 2.0 : 0.0) * y, 2.0 * P * y + (job.pcm ? 12.0 * y : 0.0),
+              launch_resample(stream(), job));
+    ZV_LAUNCH("resample_reduce", 8.0 * y / resample_tile_outputs(resample_tile(job.L, job.M, job.P)), 0.0, launch_resample_reduce(stream(), job));
+}
+
 }  // namespace zv

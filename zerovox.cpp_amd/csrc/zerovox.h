@@ -105,6 +105,9 @@ class HiFiGAN
     // (not in the reference) the stage behind it: zv_limit_wave over wav [max_seq_len * hop_size] — the look-ahead peak limiter; out
     // [max_seq_len * hop_size] is required; ask nullptr: gain 1, ceiling 1, the default windows.
     zv_limit_result limit(const float *wav, const zv_limiter *ask, float *out);
+    // (not in the reference) the step behind that: zv_resample_wave over wav [max_seq_len * hop_size] — another sample rate, as f32
+    // (out), as PCM16 (pcm) or both, each [zv_resample_count(max_seq_len * hop_size, L, M)]; at least one of the two.
+    zv_resample_result resample(const float *wav, const zv_resample *ask, float *out, int16_t *pcm);
 
   private:
     zv_model *model;
@@ -193,6 +196,9 @@ class ZeroVOXModel
     // limiter (include/zerovox_amd.h "limiter"): zv_limit_wave over any waveform of T frames at the model's rate, its first n_frames
     // measured; ask nullptr: gain 1, ceiling 1, the default windows; out [T * hop].  Next to HiFiGAN::limit, for other lengths.
     zv_limit_result limit(const float *wav, uint32_t T, uint32_t n_frames, const zv_limiter *ask, float *out);
+    // resampling (include/zerovox_amd.h "resampling"): zv_resample_wave over any waveform of S_in samples — another sample rate, as f32
+    // (out), as PCM16 (pcm) or both, each [zv_resample_count(S_in, L, M)].  Next to HiFiGAN::resample, for other lengths.
+    zv_resample_result resample(const float *wav, uint64_t S_in, const zv_resample *ask, float *out, int16_t *pcm);
 
     const zerovox_hparams &get_hparams() const { return hparams; }
     const float *get_wav() const { return wav; }

@@ -121,6 +121,15 @@ zv_limit_result HiFiGAN::limit(const float *wav, const zv_limiter *ask, float *o
     return res;
 }
 
+zv_resample_result HiFiGAN::resample(const float *wav, const zv_resample *ask, float *out, int16_t *pcm)
+{
+    zv_resample_result res{};
+    zv_hparams hp;
+    chk(zv_model_get_hparams(model, &hp));
+    chk(zv_resample_wave(model, wav, (uint64_t)max_seq_len * hp.audio_hop_size, ask, &res, out, pcm));
+    return res;
+}
+
 // ---------------------------------------------------------------------------------------------------
 
 ZeroVOXModel::ZeroVOXModel(const std::string &fname)
@@ -256,6 +265,13 @@ zv_limit_result ZeroVOXModel::limit(const float *wav, uint32_t T, uint32_t n_fra
 {
     zv_limit_result res{};
     chk(zv_limit_wave(model, wav, T, n_frames, ask, &res, out));
+    return res;
+}
+
+zv_resample_result ZeroVOXModel::resample(const float *wav, uint64_t S_in, const zv_resample *ask, float *out, int16_t *pcm)
+{
+    zv_resample_result res{};
+    chk(zv_resample_wave(model, wav, S_in, ask, &res, out, pcm));
     return res;
 }
 

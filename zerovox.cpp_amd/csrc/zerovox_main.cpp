@@ -88,6 +88,14 @@
 //            1.5 and 60); the report is printed and the limited waveform written.  --limit without a file, together with --lufs L
 //            --true-peak-dbtp P on a synthesis run, meets the ceiling with the limiter instead of backing the gain off: the gain of the
 //            target alone goes ahead of the limiter, and the loudness of what was written is printed too.  A bad value is a usage error.
+//   --resample IN.wav, --rate R, --resample-zeros Z, --resample-beta B, --resample-cutoff C, --dither, --dither-seed N, --out-rate R
+//            --resample IN.wav -o OUT.wav --rate R: no synthesis; a mono PCM16 RIFF file at ANY rate brought to R Hz (zv_resample_wave:
+//            the design of zeros Z, beta B, cutoff C; 0 or absent: 32, 9, 0.91) and written as the device's PCM16 samples, with TPDF
+//            dither under seed N where --dither is given.  This is how a recording at 44.1 or 48 kHz reaches --analyze, --loudness,
+//            --limit and --time-like, which keep their refusal of another rate.  --out-rate R [--dither] on a synthesis run is the
+//            last step behind --lufs / --limit: what -o would receive goes through the same call and the file is written at R Hz from
+//            the device's int16 samples.  --rate without --resample, --resample without --rate, the design flags without either mode
+//            and a bad value are usage errors.
 //   --time-like REF.wav
 //            with the synthesis flags: the utterance with the timing of the reference, a mono PCM16 RIFF file at the model's rate.
 //            The utterance is synthesised (fitted), its mel rows are aligned to the reference's, the phoneme boundaries move onto the
@@ -128,7 +136,10 @@ static void usage(FILE *f)
                "       zerovox -m model.gguf --align a.f32 b.f32 --mel-width M [--align-scale S] [--align-normalise] [--map-out map.tsv]\n"
                "       zerovox -m model.gguf --loudness in.wav [--lufs L] [--true-peak-dbtp P]\n"
                "       zerovox -m model.gguf --limit in.wav -o out.wav --limit-dbtp P [--limit-gain-db G] [--limit-attack-ms A] [--limit-release-ms R]\n"
+               "       zerovox -m model.gguf --resample in.wav -o out.wav --rate R [--resample-zeros Z] [--resample-beta B] [--resample-cutoff C]\n"
+               "               [--dither] [--dither-seed N]\n"
                "       zerovox ... --lufs L [--true-peak-dbtp P]   (with the synthesis flags)\n"
+               "       zerovox ... --out-rate R [--dither] [--dither-seed N]   (with the synthesis flags)\n"
                "       zerovox ... --time-like ref.wav   (with the synthesis flags)\n"
                "  defaults: -m %s -o %s, built-in utterance (like the reference's main)\n"
                "  utterance.txt: line 1 phoneme ids, line 2 punctuation ids, line 3 style floats (or a single 0)\n"
@@ -177,6 +188,10 @@ static void usage(FILE *f)
                "                       short-term loudness (LUFS), true peak (dBTP), and the gain --lufs / --true-peak-dbtp would apply\n"
                "  --lufs L             bring the finished waveform to L LUFS integrated (-70 .. 0) before it is written\n"
                "  --true-peak-dbtp P   keep its true peak at or below P dBTP (P <= 0); with --lufs the ceiling wins\n"
+               "  --resample IN.wav    no synthesis: a mono PCM16 file at any rate brought to --rate R Hz on the device and written as PCM16;\n"
+               "                       --resample-zeros Z (4 .. 64, default 32), --resample-beta B ((0, 20], default 9), --resample-cutoff C\n"
+               "                       ((0, 1], default 0.91), --dither (TPDF, +-1 LSB), --dither-seed N (default 0)\n"
+               "  --out-rate R         write the finished waveform at R Hz, converted on the device (the last step behind --lufs / --limit)\n"
                "  --time-like REF.wav  synthesise with the timing of REF.wav (mono PCM16 at the model's rate): the phoneme boundaries of a\n"
                "                       first synthesis are moved onto the reference's clock along the alignment of the two mels\n",
             k_default_model, k_default_out);
@@ -478,6 +493,58 @@ static int limit_file(const std::string &model_path, const std::string &in_path,
     return 0;
 }
 
+// what --rate / --out-rate, the design flags and the dither flags ask for
+struct ResampleFlags { uint32_t rate = 0, zeros = 0, seed = 0; float beta = 0.0f, cutoff = 0.0f; bool dither = false, design = false, seeded = false; };
+static zv_resample resample_ask(const ResampleFlags &f, uint32_t rate_in)
+{
+    zv_resample q{};
+    q.rate_in = rate_in, q.rate_out = f.rate, q.zeros = f.zeros, q.beta = f.beta, q.cutoff = f.cutoff;
+    q.flags = f.dither ? 1u : 0u, q.seed = f.seed;
+    return q;
+}
+static void print_resample(const char *what, const zv_resample &q, uint64_t S_in, const zv_resample_result &r)
+{
+    uint32_t L = 0, M = 0, P = 0;
+    if (zv_resample_design(q.rate_in, q.rate_out, q.zeros, q.beta, q.cutoff, &L, &M, &P, nullptr) != ZV_OK) throw std::runtime_error(zv_last_error());
+    printf("%s: %u -> %u Hz (L %u, M %u, %u taps per phase), %llu -> %llu samples, sample peak %.6f, clipped %llu%s\n", what, q.rate_in, q.rate_out, L, M, P,
+           (unsigned long long)S_in, (unsigned long long)r.n_out, (double)r.sample_peak, (unsigned long long)r.clipped, q.flags ? ", dithered" : "");
+}
+// S_in samples as PCM16 at the ask's rate, written to out_path: `call(ask, pcm)` is the resampling call (the C-ABI's or the facade's)
+// over those samples; no samples give an empty file
+template <typename Call> static zv_resample_result resample_to_file(const char *what, uint64_t S_in, const zv_resample &q, const std::string &out_path, Call call)
+{
+    uint32_t L = 0, M = 0, P = 0;
+    if (zv_resample_design(q.rate_in, q.rate_out, q.zeros, q.beta, q.cutoff, &L, &M, &P, nullptr) != ZV_OK) throw std::runtime_error(zv_last_error());
+    std::vector<int16_t> pcm((size_t)zv_resample_count(S_in, L, M));
+    zv_resample_result r{};
+    if (S_in) r = call(q, pcm.data());
+    print_resample(what, q, S_in, r);
+    if (zv_write_wav_pcm16(out_path.c_str(), pcm.data(), pcm.size(), q.rate_out) != ZV_OK) throw std::runtime_error(zv_last_error());
+    printf("Successfully created %s with %zu samples at %u Hz.\n", out_path.c_str(), pcm.size(), q.rate_out);
+    return r;
+}
+
+// --resample IN.wav -o OUT.wav --rate R: a mono PCM16 RIFF file at any rate through zv_resample_wave
+static int resample_file(const std::string &model_path, const std::string &in_path, const std::string &out_path, const ResampleFlags &f)
+{
+    uint32_t rate = 0;
+    const std::vector<float> pcm = read_pcm16("--resample", in_path, rate);
+    zv_model *m = nullptr;
+    if (zv_model_load(model_path.c_str(), 0, &m) != ZV_OK) throw std::runtime_error(zv_last_error());
+    struct Free { zv_model *m; ~Free() { zv_model_free(m); } } free_model{m};
+    zv_hparams hp;
+    if (zv_model_get_hparams(m, &hp) != ZV_OK) throw std::runtime_error(zv_last_error());
+    const uint64_t most = (uint64_t)zv_max_frames(m) * hp.audio_hop_size;
+    if (pcm.empty() || pcm.size() > most)
+        throw std::runtime_error("--resample: '" + in_path + "' holds " + std::to_string(pcm.size()) + " samples, 1 .. " + std::to_string(most) + " are needed");
+    resample_to_file(in_path.c_str(), pcm.size(), resample_ask(f, rate), out_path, [&](const zv_resample &q, int16_t *out) {
+        zv_resample_result r{};
+        if (zv_resample_wave(m, pcm.data(), pcm.size(), &q, &r, nullptr, out) != ZV_OK) throw std::runtime_error(zv_last_error());
+        return r;
+    });
+    return 0;
+}
+
 static int loudness_file(const std::string &model_path, const std::string &in_path, const zv_loudness &q)
 {
     uint32_t rate = 0;
@@ -548,6 +615,9 @@ int main(int argc, char **argv)
     bool limit = false;                                        // --limit
     std::string limit_path;                                    // --limit IN.wav
     LimitFlags limit_f;                                        // --limit-dbtp, --limit-gain-db, --limit-attack-ms, --limit-release-ms
+    std::string resample_path;                                 // --resample IN.wav
+    ResampleFlags resample_f;                                  // --rate / --out-rate, --resample-zeros, --resample-beta, --resample-cutoff, --dither, --dither-seed
+    bool rate_flag = false, out_rate_flag = false;
     zv_mel mel_q{};                                            // --mel-fmin, --mel-fmax, --mel-centre, --mel-pad
     mel_q.log = 1;
     mel_q.pad = 1;
@@ -699,6 +769,37 @@ int main(int argc, char **argv)
             else if (a == "--limit-gain-db") limit_f.gain_db = v;
             else if (a == "--limit-attack-ms") limit_f.attack_ms = v;
             else limit_f.release_ms = v;
+        }
+        else if (a == "--resample") resample_path = need("--resample");
+        else if (a == "--dither") resample_f.dither = true;
+        else if (a == "--rate" || a == "--out-rate" || a == "--resample-zeros" || a == "--dither-seed")
+        {
+            const std::string v = need(a.c_str());
+            char *end = nullptr;
+            const unsigned long long n = strtoull(v.c_str(), &end, 10);
+            const bool rate = a == "--rate" || a == "--out-rate";
+            if (v.empty() || v[0] == '-' || end != v.c_str() + v.size() || n > 0xffffffffull || (rate && !(n >= 4000 && n <= 768000)) ||
+                (a == "--resample-zeros" && !(n >= 4 && n <= 64)))
+            {
+                fprintf(stderr, "zerovox: %s %s is not a whole number in %s\n", a.c_str(), v.c_str(), rate ? "[4000, 768000]" : a == "--resample-zeros" ? "[4, 64]" : "[0, 4294967295]");
+                usage(stderr);
+                return 2;
+            }
+            if (rate) resample_f.rate = (uint32_t)n, (a == "--rate" ? rate_flag : out_rate_flag) = true;
+            else if (a == "--resample-zeros") resample_f.zeros = (uint32_t)n, resample_f.design = true;
+            else resample_f.seed = (uint32_t)n, resample_f.seeded = true;
+        }
+        else if (a == "--resample-beta" || a == "--resample-cutoff")
+        {
+            const float v = parse_flag_float(a.c_str(), need(a.c_str()));
+            if (!(v > 0.0f && v <= (a == "--resample-beta" ? 20.0f : 1.0f)))
+            {
+                fprintf(stderr, "zerovox: %s %g is outside %s\n", a.c_str(), (double)v, a == "--resample-beta" ? "(0, 20]" : "(0, 1]");
+                usage(stderr);
+                return 2;
+            }
+            (a == "--resample-beta" ? resample_f.beta : resample_f.cutoff) = v;
+            resample_f.design = true;
         }
         else if (a == "--lufs" || a == "--true-peak-dbtp")
         {
@@ -899,6 +1000,25 @@ int main(int argc, char **argv)
         usage(stderr);
         return 2;
     }
+    if (resample_path.empty() ? rate_flag : !rate_flag || out_rate_flag)
+    {
+        fprintf(stderr, "zerovox: --resample IN.wav and --rate R need each other (--out-rate belongs to a synthesis run)\n");
+        usage(stderr);
+        return 2;
+    }
+    if (resample_path.empty() && !out_rate_flag && (resample_f.design || resample_f.dither || resample_f.seeded))
+    {
+        fprintf(stderr, "zerovox: --resample-zeros, --resample-beta, --resample-cutoff, --dither and --dither-seed need --resample IN.wav or --out-rate R\n");
+        usage(stderr);
+        return 2;
+    }
+    if ((!resample_path.empty() || out_rate_flag) &&
+        (!limit_path.empty() || !loudness_path.empty() || !analyze_path.empty() || !align_a.empty() || planning || (!resample_path.empty() && !like_path.empty())))
+    {
+        fprintf(stderr, "zerovox: --resample IN.wav and --out-rate exclude --limit IN.wav, --loudness, --analyze, --align, --plan (and --resample excludes --time-like)\n");
+        usage(stderr);
+        return 2;
+    }
     if (align_flag && align_a.empty())
     {
         fprintf(stderr, "zerovox: --mel-width, --align-scale, --align-normalise and --map-out need --align A.f32 B.f32\n");
@@ -997,6 +1117,7 @@ int main(int argc, char **argv)
         if (!analyze_path.empty()) return analyze(model_path, analyze_path, melout_path, resynth_path, mel_q);
         if (!loudness_path.empty()) return loudness_file(model_path, loudness_path, loud_q);
         if (!limit_path.empty()) return limit_file(model_path, limit_path, out_path, limit_f);
+        if (!resample_path.empty()) return resample_file(model_path, resample_path, out_path, resample_f);
         if (!align_a.empty()) return align_files(model_path, align_a, align_b, (uint32_t)mel_width, align_q, map_path);
         std::vector<float> like_wav;                            // --time-like, read ahead of the checkpoint
         uint32_t like_rate = 0;
@@ -1186,6 +1307,13 @@ int main(int argc, char **argv)
             if (!bands_path.empty()) write_bands(bands_path, model.get_band_frames());
             if (!pbands_path.empty()) write_bands(pbands_path, model.get_band_phonemes());
         }
+        // --out-rate R: what -o would receive goes through zv_resample_wave and is written at R Hz from the device's int16 samples
+        auto write_at_out_rate = [&](const float *data, size_t n) {
+            if (!out_rate_flag) return false;
+            resample_to_file("resample", n, resample_ask(resample_f, hp.audio_sampling_rate), out_path,
+                             [&](const zv_resample &q, int16_t *out) { return model.resample(data, n, &q, nullptr, out); });
+            return true;
+        };
         if (loud_q.flags)
         {
             // --lufs / --true-peak-dbtp: what -o receives, measured over the speech and scaled as a whole, then written
@@ -1208,18 +1336,21 @@ int main(int argc, char **argv)
                 if (T) r = model.loudness(model.get_wav(), T, std::min(nf, T), &loud_q, scaled.data());
                 print_loudness("loudness before the gain", r);
             }
+            if (write_at_out_rate(scaled.data(), scaled.size())) return 0;
             if (zv_write_wav(out_path.c_str(), scaled.data(), scaled.size(), hp.audio_sampling_rate) != ZV_OK) throw std::runtime_error(zv_last_error());
             printf("Successfully created %s with %zu samples (%u frames).\n", out_path.c_str(), scaled.size(), T);
         }
         else if (trim || fit)
         {
             const size_t n = (size_t)nf * hp.audio_hop_size;
+            if (write_at_out_rate(model.get_wav(), n)) return 0;
             if (zv_write_wav(out_path.c_str(), model.get_wav(), n, hp.audio_sampling_rate) != ZV_OK)
                 throw std::runtime_error(zv_last_error());
             printf("Successfully created %s with %zu samples (%u frames).\n", out_path.c_str(), n, nf);
         }
         else
         {
+            if (write_at_out_rate(model.get_wav(), (size_t)hp.max_seq_len * hp.audio_hop_size)) return 0;
             if (!model.write_wav_file(out_path)) throw std::runtime_error(zv_last_error());
             printf("Successfully created %s with %zu samples.\n", out_path.c_str(), (size_t)hp.max_seq_len * hp.audio_hop_size);
         }
